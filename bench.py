@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- frames/sec of dense Farneback flow @1080p on N MI355X GPUs (BASELINE.json).
 
-  python bench.py --gpus N --steps K --warmup W [--repeats R]
+  python bench.py --gpus N --steps K --warmup W [--repeats R] [--dump-outputs DIR]
   N>1: either under the launcher (python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...,
   RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment) or plainly -- without WORLD_SIZE in the
   environment the script starts that launcher itself as a CHILD process before anything touches the GPU and
@@ -20,6 +20,11 @@ Prints ONE JSON line (rank 0) with `roofline` (dominant kernel: compulsory bytes
 built / its mean duration from HIP events on the kernel's stream inside the timed region / 8 TB/s),
 `pipeline` (the whole step against the same peak) and, at N=1, `cpu_baseline` (the CPU oracle timed
 on this host on a bounded sample of the same clip).
+
+--dump-outputs DIR: after the last timed window rank 0 writes what the last timed step handed its caller as
+DIR/<name>.npy (dump_outputs() below).  The clip is generated from a fixed seed and the stream's state repeats every
+two steps (four for c5; the untimed time-based warm-up runs in blocks of four), so the same arguments give the same
+inputs and the same last step from run to run: two builds can be compared file by file.
 """
 import argparse
 import json
@@ -118,6 +123,47 @@ def measured_memory_roof():
     return None
 
 
+DUMP_FLOW_BYTES = 48 << 20    # flow.npy's share of the 64 MB a dump may take; the other files are a few KB
+
+
+def dump_sample_index(n, keep, seed=20240607):
+    """`keep` or fewer of the indices 0 .. n-1, ascending: one per block of ceil(n / keep) consecutive indices, at an
+    offset inside the block drawn from RandomState(seed) -- the same indices for the same (n, keep) on every run."""
+    block = -(-n // keep)
+    base = np.arange(0, n, block, dtype=np.int64)
+    return np.minimum(base + np.random.RandomState(seed).randint(0, block, base.size), n - 1)
+
+
+def dump_outputs(path, ctx, flow, with_hist):
+    """Writes the arrays the caller of the last timed step holds into `path` (float32 as computed; the int32 counters
+    as float64, exact) and returns {name: shape}:
+      flow              the step's flow fields [pairs, H, W, 2] -- whole when they fit DUMP_FLOW_BYTES, else the
+                        [n, 2] vectors at the pixels dump_sample_index(pairs * H * W, DUMP_FLOW_BYTES // 8) picks
+      hist_words        the step's RC_HIST_WORDS counters (hist, hist2d, histsum, histsum2d)
+      upper, upper2d, prop_above_upper     the thresholds derived from them
+    (config c3's seed points are advected in place from step to step, so where they stand depends on how many untimed
+    steps the time-based warm-up ran: they are not part of the dump)"""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    if isinstance(flow, torch.Tensor):
+        if flow.numel() * 4 > DUMP_FLOW_BYTES:
+            px = flow.reshape(-1, 2)
+            flow = px[torch.from_numpy(dump_sample_index(px.shape[0], DUMP_FLOW_BYTES // 8)).to(px.device)]
+        flow = flow.cpu().numpy()
+    arrays["flow"] = flow
+    if with_hist:
+        st = ctx.histogram_read()
+        arrays["hist_words"] = ctx.histogram_words().cpu().numpy().astype(np.float64)
+        arrays["upper"] = np.array([st.UPPER], np.float32)
+        arrays["upper2d"] = st.UPPER2d
+        arrays["prop_above_upper"] = st.prop_above_upper
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64)
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def launcher_command(argv, gpus, port=None):
     """The child command a plain `python bench.py --gpus N` (N > 1, no WORLD_SIZE) starts: the same launcher line the
     driver uses, one rank per GPU, rendezvous on 127.0.0.1."""
@@ -187,6 +233,9 @@ def main():
                          "call (rcflow_push_frame_dev); host = frames from host memory through the page-locked double "
                          "buffer, flow stays on the device (rcflow_push_frame_u8; PCIe-inclusive upload); host-stateless = "
                          "the literal two-image drop-in with host pointers and the flow copied back (rcflow_farneback_u8)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (flow fields -- a fixed seeded sample of "
+                         "them beyond 48 MB --, histogram counters, thresholds) as DIR/<name>.npy, float32 / float64")
     args = ap.parse_args()
     if args.gpus < 1 or args.steps < 1 or args.repeats < 1:
         ap.error("--gpus, --steps and --repeats must be positive")
@@ -445,6 +494,10 @@ def main():
     if events:
         ctx.profile_enable(False)
         prof = ctx.profile_read()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        stateless = args.mode == "host-stateless"            # its flow is on the host and it runs no analysis
+        dumped = dump_outputs(args.dump_outputs, ctx, host_flow if stateless else flows, not stateless)
     # evidence that N ranks sat on N devices: every rank's device uuid / PCI location, gathered
     ident = device_identity(torch, dev)
     ident.update(rank=rank, local_rank=local_rank, host=os.uname().nodename)
@@ -499,6 +552,8 @@ def main():
                                      "materialises M and fuses two iterations, so it moves far fewer bytes than this "
                                      "model -- a throughput yardstick (70 % = 10 278 frames/s), not a roofline fraction"},
         }
+        if dumped:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if prof:
             tot = sum(p["total_ms"] for p in prof)
             dom = max(prof, key=lambda p: p["total_ms"])

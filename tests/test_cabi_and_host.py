@@ -150,6 +150,23 @@ def test_bench_self_launch_command():
     assert json.loads(out.stdout)["launch"] is None
 
 
+def test_bench_dump_sample_index():
+    """bench.py --dump-outputs writes a flow batch beyond its byte share as a sample: one pixel per block of consecutive
+    pixels at a seeded offset.  The same indices on every call, ascending without repeats, inside the array, never more
+    than asked for, and spread over the whole of it (the headline's 32 fields of 1080p stay under 48 MB)."""
+    import numpy as np
+    import bench
+    n = 32 * 1080 * 1920
+    keep = bench.DUMP_FLOW_BYTES // 8
+    idx = bench.dump_sample_index(n, keep)
+    assert np.array_equal(idx, bench.dump_sample_index(n, keep))
+    assert idx.size <= keep and idx.size * 8 > bench.DUMP_FLOW_BYTES // 2 and bench.DUMP_FLOW_BYTES <= 60 << 20
+    assert idx[0] >= 0 and idx[-1] < n and (np.diff(idx) > 0).all() and np.diff(idx).max() < 2 * -(-n // keep)
+    for n, keep in [(10, 3), (7, 7), (5, 1), (1000, 999)]:
+        idx = bench.dump_sample_index(n, keep)
+        assert 0 < idx.size <= keep and idx.min() >= 0 and idx.max() < n and (np.diff(idx) > 0).all()
+
+
 def test_tile_chain_plan_invariants():
     """Host logic of the fused winsize-3 flow kernel's tile chains (option `chain`): the pair groups of a launch cover
     every pair exactly once in order, no group is longer than the option, the groups over the last `chain` pairs halve

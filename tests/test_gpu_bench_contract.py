@@ -51,6 +51,56 @@ def test_bench_prints_one_contract_line():
     assert c["kind"] == "port" and c["cores"] == 1 and c["value"] > 0
 
 
+@pytest.mark.parametrize("config, pairs, runs", [("c2", 5, 2), ("c1", 4, 1)])
+def test_bench_dump_outputs(tmp_path, config, pairs, runs):
+    """--dump-outputs DIR leaves what the last timed step computed as DIR/<name>.npy: float32 / float64 only, under 64 MB,
+    the same from run to run, and equal to the library's own answer for that step computed here -- the step's flow fields
+    (the seeded pixel sample of them when the batch is beyond 48 MB: 5 fields of 1080p; the whole batch at 640x480) and
+    the histogram counters and thresholds of those fields."""
+    import numpy as np
+    import bench
+    from ripcurrents_amd import synth
+    from ripcurrents_amd.api import Context
+
+    def run(d):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", config, "--steps", "3", "--warmup", "1",
+                              "--pairs", str(pairs), "--warmup-seconds", "0.2", "--repeats", "2", "--no-roof", "--no-cpu-baseline",
+                              "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        j = json.loads(lines[0])
+        got = {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+        assert sorted(got) == ["flow", "hist_words", "prop_above_upper", "upper", "upper2d"]
+        assert j["dumped_outputs"]["arrays"] == {k: list(a.shape) for k, a in got.items()}
+        assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64 << 20
+        return j, got
+
+    j, got = run(tmp_path / "a")
+    for r in range(1, runs):
+        _, again = run(tmp_path / ("b%d" % r))
+        assert all(np.array_equal(got[k], again[k], equal_nan=True) for k in got)
+    # the step the dump is of: the clip forwards on even steps, backwards on odd ones (warm-up steps included)
+    w, h = (640, 480) if config == "c1" else (1920, 1080)
+    clip = (synth.translating_clip if config == "c1" else synth.surf_clip)(w, h, pairs + 1, seed=1234, device="cuda")
+    last = j["warmup_steps_run"] + j["repeats"] * j["steps"] - 1
+    with Context(w, h) as c:
+        want = c.farneback_clip(clip if last % 2 == 0 else clip.flip(0).contiguous(), **bench.PARAMS)
+        c.analysis_reset(w, h)
+        c.histogram_accumulate_clip(want)
+        c.thresholds()
+        st = c.histogram_read()
+        words = c.histogram_words().cpu().numpy()
+    want = want.cpu().numpy()
+    if want.nbytes > bench.DUMP_FLOW_BYTES:
+        want = want.reshape(-1, 2)[bench.dump_sample_index(pairs * h * w, bench.DUMP_FLOW_BYTES // 8)]
+    assert got["flow"].dtype == np.float32 and np.array_equal(got["flow"], want)
+    assert words.any() and np.array_equal(got["hist_words"], words)
+    assert got["upper"][0] == np.float32(st.UPPER) and np.array_equal(got["upper2d"], st.UPPER2d)
+    assert np.array_equal(got["prop_above_upper"], st.prop_above_upper, equal_nan=True)
+
+
 @pytest.mark.parametrize("how", ["launcher", "plain"])
 def test_bench_two_ranks_rehearsal(how):
     """The N>1 path of bench.py end to end on the one GPU of the test box, both ways the driver may start it: under
