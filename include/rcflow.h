@@ -43,9 +43,24 @@ enum {
     RC_ECOMM = -7     /* collective layer not initialised / failed */
 };
 
-/* cv::OPTFLOW_FARNEBACK_GAUSSIAN; cv::OPTFLOW_USE_INITIAL_FLOW (4) is rejected with
- * RC_EINVAL: no reference call site uses it. */
+/* cv::OPTFLOW_FARNEBACK_GAUSSIAN and cv::OPTFLOW_USE_INITIAL_FLOW; any other bit is RC_EINVAL.
+ * RC_FARNEBACK_USE_INITIAL_FLOW: the flow argument is in/out.  As in optflow.cpp calc(), its content is reduced to the
+ * coarsest scale with resize(INTER_AREA), multiplied by pyr_scale^levels (levels as cropped, rcflow_level_geometry) and
+ * starts that scale instead of zeros; every finer scale proceeds as without the flag.  The field must be 8-byte aligned
+ * (pointer and strides).  Where the initial field comes from, per entry point:
+ *   rcflow_farneback_dev / _u8          d_flow_xy / flow_xy, in/out;
+ *   rcflow_push_frame_dev               d_flow_xy, in/out: the same buffer passed every frame gives the temporal warm start
+ *                                       (pair t starts from the field of pair t - 1); a priming call (returns 1) neither
+ *                                       reads nor writes it;
+ *   rcflow_push_frame_u8 / _acquired,   the slot's resident field of the previous pair (rcflow_stream_flow_ptr); the first
+ *   rcflow_frame_loop_step              pair after a priming call starts from zero, bit-identical to the flag unset;
+ *   rcflow_push_batch_dev               d_flows_xy[z], in/out per stream z (the captured launch sequence includes the
+ *                                       reduction);
+ *   rcflow_push_clip_dev,               RC_EINVAL: the pairs of a clip are solved together, a pair cannot wait for its
+ *   rcflow_farneback_clip_dev           predecessor's field.
+ * The bit is part of rc_farneback_params: a stream that toggles it primes again like after any other parameter change. */
 #define RC_FARNEBACK_GAUSSIAN 256
+#define RC_FARNEBACK_USE_INITIAL_FLOW 4
 
 /* ripcurrents.hpp:7-9 */
 #define RC_HIST_BINS 50
@@ -211,6 +226,11 @@ int rcflow_stage_polyexp_dev(rc_ctx* ctx, int stream, const float* d_I, int w, i
 int rcflow_stage_flow_iter_dev(rc_ctx* ctx, int stream, const float* d_R0_5,
                                const float* d_R1_5, const float* d_flow_in, int w, int h,
                                int winsize, int flags, float* d_flow_out);
+/* The reduction RC_FARNEBACK_USE_INITIAL_FLOW applies to the initial field: resize(flow, Size(wk, hk), INTER_AREA) to the
+ * coarsest scale k = cropped levels, times (float)pyr_scale^k.  d_flow_xy: h x w float2 with a byte step;
+ * d_out: hk x wk float2, dense. */
+int rcflow_stage_initial_flow_dev(rc_ctx* ctx, int stream, const float* d_flow_xy, size_t flow_step,
+                                  int w, int h, double pyr_scale, int levels, float* d_out /* hk*wk*2 */);
 
 /* ------------------------------------------------------------------ B: analysis
  * Per-slot device-resident state mirrors the locals of ripcurrents.cpp:133-176:

@@ -69,8 +69,10 @@ inline void calcOpticalFlowFarneback(cv::InputArray _prev, cv::InputArray _next,
                                      double poly_sigma, int flags) {
     cv::Mat prev = _prev.getMat(), next = _next.getMat();
     CV_Assert(prev.size() == next.size() && prev.type() == CV_8UC1 && next.type() == CV_8UC1 && pyr_scale < 1);
-    _flow.create(prev.size(), CV_32FC2);
+    // OPTFLOW_USE_INITIAL_FLOW: `flow` is in/out and must already hold a field of the frames' size (optflow.cpp calc())
+    if (!(flags & cv::OPTFLOW_USE_INITIAL_FLOW)) _flow.create(prev.size(), CV_32FC2);
     cv::Mat flow = _flow.getMat();
+    CV_Assert(flow.size() == prev.size() && flow.type() == CV_32FC2);
     ContextLease lease(prev.cols, prev.rows);
     int rc = rcflow_farneback_u8(lease.get(), 0, prev.data, prev.step, next.data,
                                  next.step, prev.cols, prev.rows, flow.ptr<float>(), flow.step, pyr_scale, levels,

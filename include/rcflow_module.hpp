@@ -83,7 +83,8 @@ class Pipeline {
 
     // cv::calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, iterations,
     // poly_n, poly_sigma, flags): 8UC1 in, CV_32FC2 out (flow.data may be null: the field then
-    // only stays resident for the analysis calls).
+    // only stays resident for the analysis calls).  flags & RC_FARNEBACK_USE_INITIAL_FLOW: the two-image call takes `flow`
+    // as in/out; pushFrame / pushAcquired / loopStep start every pair from the resident field of the previous one.
     // The frame loop itself (ripcurrents.cpp:194-221: capture, calcOpticalFlowFarneback(u_f2, u_f1, ...),
     // u_f1.copyTo(u_f2)) with the previous frame kept on the device: one upload and one pyramid + expansion
     // per frame (rcflow_push_frame_dev).  Returns false for the call that primes the stream (the first one, or
@@ -168,6 +169,12 @@ class Pipeline {
         uint8_t* df = (uint8_t*)d_frames_;
         hip_check(hipMemcpy2D(df, w_, prev.data, prev.step, w_, h_, hipMemcpyHostToDevice), "upload prev");
         hip_check(hipMemcpy2D(df + (size_t)w_ * h_, w_, next.data, next.step, w_, h_, hipMemcpyHostToDevice), "upload next");
+        if (flags & RC_FARNEBACK_USE_INITIAL_FLOW) {
+            // OPTFLOW_USE_INITIAL_FLOW: `flow` is in/out -- its content starts the coarsest scale (include/rcflow.h)
+            if (!flow.data || flow.rows != h_ || flow.cols != w_ || flow.channels != 2 || flow.elem != 4)
+                throw Error(RC_EINVAL, "OPTFLOW_USE_INITIAL_FLOW: flow must hold a CV_32FC2 field of the frame size");
+            hip_check(hipMemcpy2D(d_flow_, (size_t)w_ * 8, flow.data, flow.step, (size_t)w_ * 8, h_, hipMemcpyHostToDevice), "upload initial flow");
+        }
         rc_farneback_params p = {pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
         check(rcflow_farneback_dev(ctx_, 0, df, w_, df + (size_t)w_ * h_, w_, w_, h_, (float*)d_flow_, (size_t)w_ * 8, &p));
         flow_src_ = (float*)d_flow_;

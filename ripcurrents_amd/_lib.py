@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("RCFLOW_LIB") or os.path.join(_HERE, "librcflow.so")
 
 RC_OK = 0
 RC_FARNEBACK_GAUSSIAN = 256
+RC_FARNEBACK_USE_INITIAL_FLOW = 4
 HIST_BINS, HIST_DIRECTIONS, HIST_RESOLUTION = 50, 36, 20
 HIST_WORDS = HIST_BINS + HIST_DIRECTIONS * HIST_BINS + 1 + HIST_DIRECTIONS
 COMM_ID_BYTES = 128     # RC_COMM_ID_BYTES = sizeof(ncclUniqueId)
@@ -71,6 +72,7 @@ SIGNATURES = {
     "rcflow_stage_pyr_level_dev": [_vp, _i, _vp, _sz, _i, _i, _d, _i, _vp],
     "rcflow_stage_polyexp_dev": [_vp, _i, _vp, _i, _i, _i, _d, _vp],
     "rcflow_stage_flow_iter_dev": [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "rcflow_stage_initial_flow_dev": [_vp, _i, _vp, _sz, _i, _i, _d, _i, _vp],
     "rcflow_analysis_reset": [_vp, _i, _i, _i],
     "rcflow_histogram_dev": [_vp, _i, _vp, _sz, _i, _i],
     "rcflow_histogram_clip_dev": [_vp, _i, _vp, _sz, _sz, _i, _i, _i],

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import FarnebackParams, HIST_BINS, HIST_DIRECTIONS, HIST_WORDS, check
+from ._lib import FarnebackParams, HIST_BINS, HIST_DIRECTIONS, HIST_WORDS, RC_FARNEBACK_USE_INITIAL_FLOW, RcflowError, check
 
 __all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState"]
 
@@ -33,6 +33,18 @@ def _params(pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags):
 
 def _is_t(x):
     return isinstance(x, torch.Tensor)
+
+
+def _check_initial_flow(prev, flow):
+    """OPTFLOW_USE_INITIAL_FLOW: `flow` is HxWx2 float32 with dense pixels, on the side (host / device) of the images."""
+    if _is_t(prev):
+        ok = _is_t(flow) and flow.is_cuda and flow.dtype == torch.float32 and flow.dim() == 3 and \
+            flow.stride(2) == 1 and flow.stride(1) == 2
+    else:
+        ok = isinstance(flow, np.ndarray) and flow.dtype == np.float32 and flow.ndim == 3 and \
+            flow.strides[2] == 4 and flow.strides[1] == 8
+    if not ok or tuple(flow.shape) != (prev.shape[0], prev.shape[1], 2):
+        raise RcflowError(-1, "OPTFLOW_USE_INITIAL_FLOW: `flow` must be HxWx2 float32 with dense pixels, where the images are")
 
 
 class HistState:
@@ -124,7 +136,13 @@ class Context:
 
         numpy inputs use the host-pointer entry point (copy in, compute, copy out);
         CUDA tensors use the device entry point and return a CUDA tensor (asynchronous).
+        With flags & 4 (OPTFLOW_USE_INITIAL_FLOW) `flow` is in/out: its content starts the coarsest scale
+        (HxWx2 float32, a numpy array for numpy images, a CUDA tensor for tensors) and the result replaces it.
         """
+        if int(flags) & RC_FARNEBACK_USE_INITIAL_FLOW:
+            if flow is None:        # OpenCV asserts on an empty initial flow
+                raise RcflowError(-1, "OPTFLOW_USE_INITIAL_FLOW needs the initial flow field in `flow`")
+            _check_initial_flow(prev, flow)
         if _is_t(prev):
             if prev.shape != next.shape or prev.dim() != 2:
                 raise ValueError("prev and next must be HxW and equal in size")
@@ -155,7 +173,8 @@ class Context:
         return flow
 
     def push_frame(self, frame, flow=None, stream=0, **kw):
-        """Streaming frame loop (ripcurrents.cpp:194-221): returns None for the first frame."""
+        """Streaming frame loop (ripcurrents.cpp:194-221): returns None for the first frame.
+        With flags=4 `flow` is in/out: pass the same tensor every frame for the temporal warm start."""
         frame = self._dev(frame, torch.uint8)
         h, w = frame.shape
         p = _params(kw.get("pyr_scale", 0.5), kw.get("levels", 2), kw.get("winsize", 3),
@@ -319,6 +338,21 @@ class Context:
         check(self._lib.rcflow_stage_polyexp_dev(self._h, stream, self._ptr(I), w, h, poly_n, poly_sigma,
                                                  self._ptr(R)))
         return R
+
+    def stage_initial_flow(self, flow, pyr_scale, levels, stream=0):
+        """The reduction OPTFLOW_USE_INITIAL_FLOW applies to the initial field (rcflow_stage_initial_flow_dev):
+        HxWx2 float32 (any row stride) -> the coarsest scale's h_k x w_k x 2, times pyr_scale^k."""
+        flow = self._dev(flow, torch.float32)
+        if flow.dim() != 3 or flow.shape[2] != 2 or flow.stride(2) != 1 or flow.stride(1) != 2:
+            flow = flow.contiguous()
+        h, w = flow.shape[:2]
+        L, _, _ = self.level_geometry(w, h, pyr_scale, levels, 0)
+        _, wk, hk = self.level_geometry(w, h, pyr_scale, levels, L)
+        out = torch.empty((hk, wk, 2), dtype=torch.float32, device=self.device)
+        self._bind(stream)
+        check(self._lib.rcflow_stage_initial_flow_dev(self._h, stream, self._ptr(flow), flow.stride(0) * 4, w, h,
+                                                      pyr_scale, levels, self._ptr(out)))
+        return out
 
     def stage_flow_iter(self, R0, R1, flow_in, winsize, flags, stream=0):
         R0 = self._dev(R0, torch.float32).contiguous()

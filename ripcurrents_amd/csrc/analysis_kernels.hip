@@ -1596,8 +1596,8 @@ __global__ __launch_bounds__(RC_BLOCK) void k_resize_area_bgr_to_gray(RcAreaArgs
 }
 
 // computeResizeAreaTab (resize.cpp), grouped by destination index
-static void area_tab(int ssize, int dsize, double scale, std::vector<int>& start, std::vector<int>& si,
-                     std::vector<float>& alpha) {
+void rc_area_tab(int ssize, int dsize, double scale, std::vector<int>& start, std::vector<int>& si,
+                 std::vector<float>& alpha) {
     start.assign(dsize + 1, 0); si.clear(); alpha.clear();
     for (int dx = 0; dx < dsize; dx++) {
         start[dx] = (int)si.size();
@@ -1634,8 +1634,8 @@ extern "C" int rcflow_resize_area_bgr_to_gray_dev(rc_ctx* ctx, int stream, const
     if (!a.fast) {
         std::vector<int> xs, xi, ys, yi;
         std::vector<float> xa, ya;
-        area_tab(sw, dw, scale_x, xs, xi, xa);
-        area_tab(sh, dh, scale_y, ys, yi, ya);
+        rc_area_tab(sw, dw, scale_x, xs, xi, xa);
+        rc_area_tab(sh, dh, scale_y, ys, yi, ya);
         const size_t nx = xi.size(), ny = yi.size();
         const size_t bytes = 4 * ((size_t)(dw + 1) + 2 * nx + (size_t)(dh + 1) + 2 * ny);
         int rc = rc_buf_ensure(s->area_tab, bytes);

@@ -214,6 +214,25 @@ void rc_launch_polyexp_multi(const RcPolyArgs* a, int nlev, int frames, hipStrea
 namespace rc_flow_fast { RC_FLOW_DECLS }
 namespace rc_flow_exact { RC_FLOW_DECLS }
 
+// OPTFLOW_USE_INITIAL_FLOW (initial_flow_kernels.hip): `pairs` caller fields of W x H float2 reduced with INTER_AREA to
+// the coarsest scale w x h and multiplied by mul = (float)pyr_scale^levels.
+struct RcFlowAreaArgs {
+    const char* src;          // field of pair 0
+    size_t src_step;          // bytes per row
+    size_t src_pair_stride;   // bytes per pair
+    int W, H;
+    float2* dst;              // [pairs][h][w] dense
+    size_t dst_pair_stride;   // elements
+    int w, h;
+    float mul;
+    int fast, ix, iy;         // both ratios integers (resizeAreaFast_): W == ix * w, H == iy * h
+    // fractional ratios (resizeArea_): DecimateAlpha tables grouped by destination index; xstart has w + 1 entries
+    const int* xstart; const int* xsi; const float* xalpha;
+    const int* ystart; const int* ysi; const float* yalpha;
+    int lds_tab;              // the column-table entries of every 64-column block fit the kernel's LDS staging
+};
+void rc_launch_flow_area_init(const RcFlowAreaArgs& a, int pairs, hipStream_t s);
+
 // interleave helpers for the stage-level test entry points
 void rc_launch_pack_R5(const float* R5, float4* RA, float* RB, int n, hipStream_t s);
 void rc_launch_unpack_R5(const float4* RA, const float* RB, float* R5, int n, hipStream_t s);

@@ -23,6 +23,7 @@ struct RcPlan {
     int nslots = 0, chunk = 0;
     int exact_taps = 0;
     int exact = 0;
+    RcFlowAreaArgs seed;   // RC_FARNEBACK_USE_INITIAL_FLOW: reduction of the initial field to the coarsest scale (tables in RcSlot::seed_tab)
 };
 
 // Device-resident analysis state of one stream slot (ripcurrents.cpp:133-176).
@@ -73,8 +74,10 @@ struct RcSlot {
     int pin_i = 0;
     int pin_acq = -1, pin_w = 0, pin_h = 0;   // staging buffer handed to the host by rcflow_frame_buffer_acquire, not yet pushed
     int flow_w = 0, flow_h = 0;   // size of the flow field resident in stage_flow (0: none yet)
+    int flow_fresh = 0;           // stage_flow holds the flow of the stream's PREVIOUS pair (the warm start of RC_FARNEBACK_USE_INITIAL_FLOW)
     RcBuf lk;                  // sparse PyrLK pyramids + derivatives (lk_kernels.hip)
     RcBuf area_tab;            // INTER_AREA decimation tables
+    RcBuf seed, seed_tab;      // RC_FARNEBACK_USE_INITIAL_FLOW: the initial field at the coarsest scale [pairs][h_k][w_k] float2, its tables
     int primed = 0, cur_slot = 0;
     // lockstep batch of streams (rcflow_push_batch_dev): parity of the ring, captured graphs
     int batch_primed = 0, batch_cur = 0;
@@ -127,7 +130,8 @@ struct rc_ctx {
 
 enum { RC_K_PYR = 0, RC_K_POLY = 1, RC_K_ITER = 2, RC_K_HIST = 3, RC_K_THRESH = 4, RC_K_CLASSIFY = 5,
        RC_K_ADVECT_FIELD = 6, RC_K_ADVECT_POINTS = 7, RC_K_POSTOP = 8, RC_K_COLOR = 9, RC_K_ITER2 = 10,
-       RC_K_PREPROC = 11, RC_K_EDGES = 12, RC_K_DISPLAY = 13, RC_K_HSV2BGR = 14, RC_K_OVERLAY = 15, RC_K_KINDS = 16 };
+       RC_K_PREPROC = 11, RC_K_EDGES = 12, RC_K_DISPLAY = 13, RC_K_HSV2BGR = 14, RC_K_OVERLAY = 15, RC_K_FLOW_SEED = 16,
+       RC_K_KINDS = 17 };
 
 void rc_set_error(const char* fmt, ...);
 int rc_buf_ensure(RcBuf& b, size_t bytes);
@@ -142,6 +146,10 @@ int rc_classify_accumulate(rc_ctx* ctx, int stream, const float* d_flow, size_t 
 int rc_loop_counter(rc_ctx* ctx, RcSlot& s, bool set, int value);
 int rc_hist_book(RcSlot& s, int w, int h, bool commit);
 int rc_analysis_ensure(rc_ctx* ctx, RcSlot& s, int w, int h);
+// computeResizeAreaTab (resize.cpp) grouped by destination index (analysis_kernels.hip)
+void rc_area_tab(int ssize, int dsize, double scale, std::vector<int>& start, std::vector<int>& si, std::vector<float>& alpha);
+// initial_flow_kernels.hip
+int rc_flow_area_prepare(RcBuf& tab, int W, int H, int w, int h, RcFlowAreaArgs& a);
 
 struct RcProfScope {
     rc_ctx* ctx;

@@ -75,7 +75,7 @@ static const char* kKindNames[RC_K_KINDS] = {"pyr_level", "polyexp", "flow_iter"
                                              "thresholds", "classify_accumulate", "advect_field",
                                              "advect_points", "flow_postop", "flow_color", "flow_iter_x2",
                                              "frame_preproc", "create_edges", "streamline_display", "hsv_to_bgr",
-                                             "create_output"};
+                                             "create_output", "flow_area_init"};
 // The reference's wall-clock buckets (ripcurrents.cpp:103-109, sampled at :205,223,293,314,411,483, printed at
 // :518-524) and the kernels that do each bucket's work here.  time_polar has no kernel of its own: the
 // cartToPolar of :305-309 is fused into the histogram and classification kernels; classify_accumulate spans
@@ -85,7 +85,7 @@ static const int kBucketOfKind[RC_K_KINDS] = {
     /* pyr_level */ 0, /* polyexp */ 0, /* flow_iter */ 0, /* polar_hist */ 2, /* thresholds */ 2,
     /* classify_accumulate */ 2, /* advect_field */ 6, /* advect_points */ 6, /* flow_postop */ 0, /* flow_color */ 2,
     /* flow_iter_x2 */ 0, /* frame_preproc */ 0, /* create_edges */ 4, /* streamline_display */ 6, /* hsv_to_bgr */ 2,
-    /* create_output */ 3};
+    /* create_output */ 3, /* flow_area_init */ 0};
 static const char* kBucketNames[RC_PROFILE_BUCKETS] = {"farneback", "polar", "threshold", "overlay", "erosion", "codec", "stream"};
 static char g_names[RC_K_KINDS * RC_MAX_LEVELS][40];
 
@@ -205,6 +205,7 @@ static void slot_free(RcSlot& s) {
     }
     rc_batch_graph_drop(s);
     rc_buf_free(s.stage_u8); rc_buf_free(s.stage_flow); rc_buf_free(s.lk); rc_buf_free(s.area_tab);
+    rc_buf_free(s.seed); rc_buf_free(s.seed_tab);
     rc_buf_free(s.exM); rc_buf_free(s.exV); rc_buf_free(s.exG);
     for (int i = 0; i < 2; i++) {
         if (s.pin[i]) (void)hipHostFree(s.pin[i]);
@@ -543,7 +544,7 @@ static int params_valid(const rc_farneback_params* p) {
     if (p->iterations < 0 || p->iterations > 1000) return 0;
     if (p->poly_n < 1 || p->poly_n > RC_MAX_POLY_N) return 0;
     if (!(p->poly_sigma >= 0)) return 0;
-    if (p->flags & ~RC_FARNEBACK_GAUSSIAN) return 0;   // USE_INITIAL_FLOW unsupported
+    if (p->flags & ~(RC_FARNEBACK_GAUSSIAN | RC_FARNEBACK_USE_INITIAL_FLOW)) return 0;
     return 1;
 }
 
@@ -610,9 +611,48 @@ static int ensure_plan(rc_ctx* ctx, RcSlot& s, int w, int h, const rc_farneback_
         if ((rc = rc_buf_ensure(s.FA[k], n * chunk * sizeof(float2)))) return rc;
         if ((rc = rc_buf_ensure(s.FB[k], n * chunk * sizeof(float2)))) return rc;
     }
+    memset(&pl.seed, 0, sizeof(pl.seed));
+    if (p->flags & RC_FARNEBACK_USE_INITIAL_FLOW) {
+        // optflow.cpp calc(): the initial field goes through resize(INTER_AREA) to the coarsest scale and is multiplied by
+        // scale = pyr_scale^L; the tables of a fractional ratio are staged here, once per plan (the stream is idle)
+        if ((rc = rc_flow_area_prepare(s.seed_tab, w, h, pl.lv[L].w, pl.lv[L].h, pl.seed))) return rc;
+        double scale = 1;
+        for (int i = 0; i < L; i++) scale *= p->pyr_scale;
+        pl.seed.mul = (float)scale;
+    }
     s.primed = 0;
     s.batch_primed = 0;
     pl.valid = true;
+    return RC_OK;
+}
+
+// RC_FARNEBACK_USE_INITIAL_FLOW: where a call's initial flow fields lie (device, W x H float2 per pair)
+struct RcSeed {
+    const float* field;
+    size_t step, pair_stride;   // bytes
+};
+
+static int seed_layout_ok(const void* p, size_t step, size_t pair_stride) {
+    if ((((uintptr_t)p) | step | pair_stride) & 7) { rc_set_error("initial flow: pointer and strides must be multiples of 8 bytes"); return 0; }
+    return 1;
+}
+
+// Reduces the pairs' initial fields to the coarsest scale on the slot's stream (one launch, before the scale's first flow
+// launch); *out = [pairs][h_k][w_k] float2.
+static int launch_seed(rc_ctx* ctx, RcSlot& s, int pairs, const RcSeed& seed, const float2** out) {
+    RcPlan& pl = s.plan;
+    const int k = pl.nlev - 1;
+    const size_t n = (size_t)pl.lv[k].w * pl.lv[k].h;
+    int rc;
+    if ((rc = rc_buf_ensure(s.seed, (size_t)pairs * n * sizeof(float2)))) return rc;
+    RcFlowAreaArgs a = pl.seed;
+    a.src = (const char*)seed.field; a.src_step = seed.step; a.src_pair_stride = seed.pair_stride;
+    a.dst = (float2*)s.seed.p; a.dst_pair_stride = n;
+    {
+        RcProfScope ps(ctx, s.cur, RC_K_FLOW_SEED, k, (double)pairs * (8. * pl.w * pl.h + 8. * n));
+        rc_launch_flow_area_init(a, pairs, s.cur);
+    }
+    *out = (const float2*)s.seed.p;
     return RC_OK;
 }
 
@@ -722,7 +762,7 @@ static int expand_frames(rc_ctx* ctx, RcSlot& s, const uint8_t* d_src, size_t fr
 
 // Option "exact": the level driver over exact_kernels.hip (M and the window's column sums in HBM).
 static int compute_flows_exact(rc_ctx* ctx, RcSlot& s, int pairs, int slot0, float* d_out, size_t out_pair_stride,
-                               size_t out_step, int slot1, int zstep) {
+                               size_t out_step, int slot1, int zstep, const RcSeed* seed) {
     RcPlan& pl = s.plan;
     const int iters = pl.prm.iterations;
     const size_t n0 = (size_t)pl.lv[0].w * pl.lv[0].h;
@@ -732,6 +772,8 @@ static int compute_flows_exact(rc_ctx* ctx, RcSlot& s, int pairs, int slot0, flo
     const size_t n0p = (size_t)pl.lv[0].w * ((pl.lv[0].h + 15) & ~15);
     if ((rc = rc_buf_ensure(s.exV, pl.win.gaussian ? n0 * 5 * pairs * sizeof(float) : n0p * 5 * pairs * sizeof(double)))) return rc;
     if (!pl.win.gaussian && (rc = rc_buf_ensure(s.exG, n0 * 5 * pairs * sizeof(double)))) return rc;
+    const float2* seeded = nullptr;
+    if (seed && (rc = launch_seed(ctx, s, pairs, *seed, &seeded))) return rc;
     const float2* coarse = nullptr;
     int cw = 0, ch = 0;
     for (int k = pl.nlev - 1; k >= 0; k--) {
@@ -747,9 +789,13 @@ static int compute_flows_exact(rc_ctx* ctx, RcSlot& s, int pairs, int slot0, flo
             a.fin = coarse; a.fin_pair_stride = (size_t)cw * ch; a.fin_w = cw; a.fin_h = ch;
             a.up_scale_x = 1. / ((double)L.w / cw); a.up_scale_y = 1. / ((double)L.h / ch);
             a.up_mul = (float)(1. / pl.prm.pyr_scale);
+        } else if (seeded) {
+            // the coarsest scale starts from the reduced initial field (already scaled): an equal-size resize is a copy
+            a.fin = seeded; a.fin_pair_stride = a.n; a.fin_w = L.w; a.fin_h = L.h;
+            a.up_scale_x = a.up_scale_y = 1.; a.up_mul = 1.f;
         }
         const double nb = (double)pairs * a.n;
-        { RcProfScope ps(ctx, s.cur, RC_K_ITER, k, 8. * nb + (coarse ? 8. * pairs * cw * ch : 0.));
+        { RcProfScope ps(ctx, s.cur, RC_K_ITER, k, 8. * nb + (coarse ? 8. * pairs * cw * ch : seeded ? 8. * nb : 0.));
           rc_launch_exact_flow_init(a, pairs, s.cur); }
         for (int i = 0; i < iters; i++) {
             if (k == 0 && i == iters - 1) { a.out = (char*)d_out; a.out_step = out_step; a.out_pair_stride = out_pair_stride; }
@@ -776,15 +822,17 @@ static int compute_flows_exact(rc_ctx* ctx, RcSlot& s, int pairs, int slot0, flo
 
 // Coarse-to-fine flow for `pairs` frame pairs whose expansions sit in slots slot0+z, slot0+z+1.
 static int compute_flows(rc_ctx* ctx, RcSlot& s, int pairs, int slot0, float* d_out, size_t out_pair_stride,
-                         size_t out_step, int slot1 = -1, int zstep = 1) {
+                         size_t out_step, int slot1 = -1, int zstep = 1, const RcSeed* seed = nullptr) {
     if (!s.in_ts_push) s.ts_streak = 0;
     // option "exact": box windows replay upstream's running sums (exact_kernels.hip); Gaussian windows run the
     // kernels below from the build of flow_iter_kernels.hip that keeps upstream's operation order
     if (s.plan.exact && !s.plan.win.gaussian)
-        return compute_flows_exact(ctx, s, pairs, slot0, d_out, out_pair_stride, out_step, slot1, zstep);
+        return compute_flows_exact(ctx, s, pairs, slot0, d_out, out_pair_stride, out_step, slot1, zstep, seed);
     const bool exact = s.plan.exact != 0;
     RcPlan& pl = s.plan;
     const int iters = pl.prm.iterations;
+    const float2* seeded = nullptr;
+    if (seed) { int rc = launch_seed(ctx, s, pairs, *seed, &seeded); if (rc) return rc; }
     const float2* coarse = nullptr;
     int cw = 0, ch = 0;
     for (int k = pl.nlev - 1; k >= 0; k--) {
@@ -806,7 +854,8 @@ static int compute_flows(rc_ctx* ctx, RcSlot& s, int pairs, int slot0, float* d_
         for (int i = 0; i < passes;) {
             double in_bytes;
             if (i == 0) {
-                if (!coarse) { a.in_mode = 0; a.fin = nullptr; in_bytes = 0; }
+                if (!coarse && seeded) { a.in_mode = 1; a.fin = seeded; a.fin_pair_stride = n; in_bytes = 8. * n; }
+                else if (!coarse) { a.in_mode = 0; a.fin = nullptr; in_bytes = 0; }
                 else {
                     a.in_mode = 2; a.fin = coarse; a.fin_pair_stride = (size_t)cw * ch;
                     a.fin_w = cw; a.fin_h = ch;
@@ -879,9 +928,14 @@ extern "C" int rcflow_farneback_dev(rc_ctx* ctx, int stream, const uint8_t* d_pr
     s->primed = 0;
     s->batch_primed = 0;
     s->flow_w = s->flow_h = 0;      // the stream starts over: no resident flow field of its own (rcflow_stream_flow_ptr)
+    s->flow_fresh = 0;
     if ((rc = expand_frames(ctx, *s, d_prev, 0, prev_step, 1, 0))) return rc;
     if ((rc = expand_frames(ctx, *s, d_next, 0, next_step, 1, 1))) return rc;
-    return compute_flows(ctx, *s, 1, 0, d_flow, 0, flow_step);
+    // OPTFLOW_USE_INITIAL_FLOW: d_flow is in/out (read by the reduction before any launch writes it)
+    const RcSeed seed = {d_flow, flow_step, 0};
+    const bool use_seed = (p->flags & RC_FARNEBACK_USE_INITIAL_FLOW) != 0;
+    if (use_seed && !seed_layout_ok(d_flow, flow_step, 0)) return RC_EINVAL;
+    return compute_flows(ctx, *s, 1, 0, d_flow, 0, flow_step, -1, 1, use_seed ? &seed : nullptr);
 }
 
 extern "C" int rcflow_farneback_u8(rc_ctx* ctx, int stream, const uint8_t* prev, size_t prev_step,
@@ -904,6 +958,8 @@ extern "C" int rcflow_farneback_u8(rc_ctx* ctx, int stream, const uint8_t* prev,
     uint8_t* du = (uint8_t*)s->stage_u8.p;
     RC_HIP(hipMemcpy2DAsync(du, w, prev, prev_step, w, h, hipMemcpyHostToDevice, s->cur));
     RC_HIP(hipMemcpy2DAsync(du + fb, w, next, next_step, w, h, hipMemcpyHostToDevice, s->cur));
+    if (flags & RC_FARNEBACK_USE_INITIAL_FLOW)      // `flow` is in/out, as in OpenCV
+        RC_HIP(hipMemcpy2DAsync(s->stage_flow.p, (size_t)w * 8, flow, flow_step, (size_t)w * 8, h, hipMemcpyHostToDevice, s->cur));
     rc = rcflow_farneback_dev(ctx, stream, du, w, du + fb, w, w, h, (float*)s->stage_flow.p, (size_t)w * 8, &p);
     if (rc) return rc;
     RC_HIP(hipMemcpy2DAsync(flow, flow_step, s->stage_flow.p, (size_t)w * 8, (size_t)w * 8, h,
@@ -918,6 +974,7 @@ extern "C" int rcflow_stream_reset(rc_ctx* ctx, int stream) {
     s->primed = 0;
     s->cur_slot = 0;
     s->flow_w = s->flow_h = 0;
+    s->flow_fresh = 0;
     return RC_OK;
 }
 
@@ -934,9 +991,12 @@ struct RcFrameAux {
     hipEvent_t after_upload;                             // recorded behind the upload (staging buffer free again)
 };
 
+// RC_FARNEBACK_USE_INITIAL_FLOW: d_flow is in/out.  `resident` = d_flow is the slot's own resident field (the host-frame
+// loop): it seeds the pair only while it holds the flow of the stream's previous pair (RcSlot::flow_fresh); the first
+// pair after a priming call starts from zero.
 static int push_frame_core(rc_ctx* ctx, RcSlot* s, int stream, const uint8_t* d_frame, size_t step, int w, int h,
                            float* d_flow, size_t flow_step, const rc_farneback_params* p, bool two_streams,
-                           const RcFrameAux* up) {
+                           const RcFrameAux* up, bool resident) {
     int was_valid = s->plan.valid;
     int rc = ensure_plan(ctx, *s, w, h, p, ctx->chunk);
     if (rc) return rc;
@@ -954,9 +1014,15 @@ static int push_frame_core(rc_ctx* ctx, RcSlot* s, int stream, const uint8_t* d_
         if ((rc = expand_frames(ctx, *s, d_frame, 0, step, 1, 0))) return rc;
         s->primed = 1;
         s->cur_slot = 0;
+        s->flow_fresh = 0;
         return 1;
     }
     if (!d_flow || flow_step < (size_t)w * 8) { rc_set_error("bad flow buffer"); return RC_EINVAL; }
+    const RcSeed seed_desc = {d_flow, flow_step, 0};
+    const bool use_seed = (p->flags & RC_FARNEBACK_USE_INITIAL_FLOW) && (!resident || s->flow_fresh);
+    if (use_seed && !seed_layout_ok(d_flow, flow_step, 0)) return RC_EINVAL;
+    const RcSeed* seed = use_seed ? &seed_desc : nullptr;
+    s->flow_fresh = 0;
     const int nxt = (s->cur_slot + 1) % s->plan.nslots;
     if (two_streams && !ctx->prof_on && s->plan.nslots >= 4) {
         if (!s->aux) RC_HIP(hipStreamCreateWithFlags(&s->aux, hipStreamNonBlocking));
@@ -987,7 +1053,7 @@ static int push_frame_core(rc_ctx* ctx, RcSlot* s, int stream, const uint8_t* d_
         if (rc) { s->in_ts_push = false; return rc; }
         RC_HIP(hipEventRecord(expanded, s->aux));
         RC_HIP(hipStreamWaitEvent(main_stream, expanded, 0));
-        rc = compute_flows(ctx, *s, 1, s->cur_slot, d_flow, 0, flow_step);
+        rc = compute_flows(ctx, *s, 1, s->cur_slot, d_flow, 0, flow_step, -1, 1, seed);
         s->in_ts_push = false;
         if (rc) return rc;
         RC_HIP(hipEventRecord(s->flow_done[older], main_stream));
@@ -998,7 +1064,7 @@ static int push_frame_core(rc_ctx* ctx, RcSlot* s, int stream, const uint8_t* d_
     }
     if ((rc = upload_on(s->cur))) return rc;
     if ((rc = expand_frames(ctx, *s, d_frame, 0, step, 1, nxt))) return rc;
-    if ((rc = compute_flows(ctx, *s, 1, s->cur_slot, d_flow, 0, flow_step))) return rc;
+    if ((rc = compute_flows(ctx, *s, 1, s->cur_slot, d_flow, 0, flow_step, -1, 1, seed))) return rc;
     s->cur_slot = nxt;
     return RC_OK;
 }
@@ -1011,7 +1077,7 @@ extern "C" int rcflow_push_frame_dev(rc_ctx* ctx, int stream, const uint8_t* d_f
     RC_HIP(hipSetDevice(ctx->device));
     // option "frame_overlap" = 2: the caller guarantees that d_frame is complete when the call is made (a resident clip, a
     // producer it has synchronised) -- only then may the expansion start without waiting for the slot's stream
-    return push_frame_core(ctx, s, stream, d_frame, step, w, h, d_flow, flow_step, p, ctx->frame_overlap >= 2, nullptr);
+    return push_frame_core(ctx, s, stream, d_frame, step, w, h, d_flow, flow_step, p, ctx->frame_overlap >= 2, nullptr, false);
 }
 
 // The reference's frame loop with HOST frames (ripcurrents.cpp:198-221: video.read -> resize -> cvtColor ->
@@ -1054,8 +1120,8 @@ static int push_staged_frame(rc_ctx* ctx, RcSlot* s, int stream, int i, int w, i
     s->pin_acq = -1;
     // the upload belongs to the expansion's side of the two-stream frame loop (option "frame_overlap" >= 1)
     RcFrameAux up = {s->pin[i], d_frame, fb, s->pin_free[i]};
-    const int rc = push_frame_core(ctx, s, stream, d_frame, w, w, h, (float*)s->stage_flow.p, (size_t)w * 8, p, ctx->frame_overlap >= 1, &up);
-    if (rc == RC_OK) { s->flow_w = w; s->flow_h = h; }
+    const int rc = push_frame_core(ctx, s, stream, d_frame, w, w, h, (float*)s->stage_flow.p, (size_t)w * 8, p, ctx->frame_overlap >= 1, &up, true);
+    if (rc == RC_OK) { s->flow_w = w; s->flow_h = h; s->flow_fresh = 1; }
     else if (rc == 1) { s->flow_w = s->flow_h = 0; }
     return rc;
 }
@@ -1131,10 +1197,16 @@ extern "C" int rcflow_push_clip_dev(rc_ctx* ctx, int stream, const uint8_t* d_fr
         rc_set_error("clip strides smaller than a frame");
         return RC_EINVAL;
     }
+    if (p && (p->flags & RC_FARNEBACK_USE_INITIAL_FLOW)) {
+        rc_set_error("RC_FARNEBACK_USE_INITIAL_FLOW is not available for clips: the pairs of a clip are solved together, "
+                     "a pair cannot wait for its predecessor's field (use the frame-at-a-time entry points)");
+        return RC_EINVAL;
+    }
     RC_HIP(hipSetDevice(ctx->device));
     int rc = ensure_plan(ctx, *s, w, h, p, ctx->chunk);          // a new size / parameter set drops `primed`
     if (rc) return rc;
     s->batch_primed = 0;
+    s->flow_fresh = 0;
     const int C = s->plan.chunk, ns = s->plan.nslots;
     int t = 0, s0 = s->cur_slot;
     if (!s->primed) {
@@ -1177,6 +1249,11 @@ extern "C" int rcflow_farneback_clip_dev(rc_ctx* ctx, int stream, const uint8_t*
     if (step < (size_t)w || flow_step < (size_t)w * 8 || frame_stride < step * (size_t)(h - 1) + w ||
         flow_frame_stride < flow_step * (size_t)(h - 1) + (size_t)w * 8) {
         rc_set_error("clip strides smaller than a frame");
+        return RC_EINVAL;
+    }
+    if (p && (p->flags & RC_FARNEBACK_USE_INITIAL_FLOW)) {
+        rc_set_error("RC_FARNEBACK_USE_INITIAL_FLOW is not available for clips: the pairs of a clip are solved together, "
+                     "a pair cannot wait for its predecessor's field (use the frame-at-a-time entry points)");
         return RC_EINVAL;
     }
     RC_HIP(hipSetDevice(ctx->device));
@@ -1258,6 +1335,7 @@ void rc_loop_graph_drop(RcSlot& s) {
 struct RcLoopKey {          // everything a captured launch sequence has baked in
     rc_frame_loop loop;
     int w, h, pin, ring, ablate, chain;
+    int seeded;             // RC_FARNEBACK_USE_INITIAL_FLOW: the sequence starts with the reduction of the resident field
     void* hip_stream;
     void* d_frame; void* pin_host; void* d_flow;
 };
@@ -1281,7 +1359,7 @@ static int loop_analysis(rc_ctx* ctx, RcSlot& s, int stream, const rc_frame_loop
 }
 
 // upload + expansion + flow + the analysis chain of one frame on s.cur (eager or under stream capture)
-static int loop_launches(rc_ctx* ctx, RcSlot& s, int stream, const rc_frame_loop& L, int pin, int w, int h) {
+static int loop_launches(rc_ctx* ctx, RcSlot& s, int stream, const rc_frame_loop& L, int pin, int w, int h, bool seeded) {
     const size_t fb = (size_t)w * h, fs = (size_t)w * 8;
     uint8_t* d_frame = (uint8_t*)s.stage_u8.p + (size_t)pin * fb;
     float* d_flow = (float*)s.stage_flow.p;
@@ -1289,7 +1367,9 @@ static int loop_launches(rc_ctx* ctx, RcSlot& s, int stream, const rc_frame_loop
     RC_HIP(hipMemcpyAsync(d_frame, s.pin[pin], fb, hipMemcpyHostToDevice, s.cur));
     int rc;
     if ((rc = expand_frames(ctx, s, d_frame, 0, w, 1, nxt))) return rc;
-    if ((rc = compute_flows(ctx, s, 1, cur, d_flow, 0, fs, nxt))) return rc;
+    // warm start: the resident field of the previous pair is read by the reduction before this pair's flow overwrites it
+    const RcSeed seed = {d_flow, fs, 0};
+    if ((rc = compute_flows(ctx, s, 1, cur, d_flow, 0, fs, nxt, 1, seeded ? &seed : nullptr))) return rc;
     return loop_analysis(ctx, s, stream, L, w, h);
 }
 
@@ -1343,6 +1423,7 @@ extern "C" int rcflow_frame_loop_step(rc_ctx* ctx, int stream, const rc_farnebac
         s->primed = 1; s->cur_slot = 0;
         s->pin_i = pin ^ 1; s->pin_acq = -1;
         s->flow_w = s->flow_h = 0;
+        s->flow_fresh = 0;
         return 1;
     }
     const int cur = s->cur_slot;
@@ -1351,6 +1432,8 @@ extern "C" int rcflow_frame_loop_step(rc_ctx* ctx, int stream, const rc_farnebac
     memset(&key, 0, sizeof(key));
     key.loop = *loop;
     key.w = w; key.h = h; key.pin = pin; key.ring = cur; key.ablate = ctx->ablate; key.chain = ctx->chain;
+    const bool seeded = (p->flags & RC_FARNEBACK_USE_INITIAL_FLOW) && s->flow_fresh && s->flow_w == w && s->flow_h == h;
+    key.seeded = seeded;
     key.hip_stream = (void*)s->cur;
     key.d_frame = (uint8_t*)s->stage_u8.p + (size_t)pin * fb; key.pin_host = s->pin[pin]; key.d_flow = s->stage_flow.p;
     const bool graph_ok = !ctx->prof_on && s->cur != nullptr;
@@ -1365,7 +1448,7 @@ extern "C" int rcflow_frame_loop_step(rc_ctx* ctx, int stream, const rc_farnebac
         if ((rc = rc_hist_book(*s, w, h, false))) return rc;
         hipGraph_t graph = nullptr;
         RC_HIP(hipStreamBeginCapture(s->cur, hipStreamCaptureModeRelaxed));
-        rc = loop_launches(ctx, *s, stream, *loop, pin, w, h);
+        rc = loop_launches(ctx, *s, stream, *loop, pin, w, h, seeded);
         hipError_t e = hipStreamEndCapture(s->cur, &graph);
         if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         if (e != hipSuccess || !graph) { rc_set_error("hipStreamEndCapture failed: %s", hipGetErrorString(e)); return RC_EHIP; }
@@ -1377,7 +1460,7 @@ extern "C" int rcflow_frame_loop_step(rc_ctx* ctx, int stream, const rc_farnebac
         RC_HIP(hipGraphLaunch(exec, s->cur));
     } else {
         if (s->loop_exec[cur]) { (void)hipGraphExecDestroy((hipGraphExec_t)s->loop_exec[cur]); s->loop_exec[cur] = nullptr; }
-        if ((rc = loop_launches(ctx, *s, stream, *loop, pin, w, h))) return rc;
+        if ((rc = loop_launches(ctx, *s, stream, *loop, pin, w, h, seeded))) return rc;
         memcpy(s->loop_key[cur], &key, sizeof(key));
         s->loop_eager[cur] = 1;
     }
@@ -1385,6 +1468,7 @@ extern "C" int rcflow_frame_loop_step(rc_ctx* ctx, int stream, const rc_farnebac
     s->cur_slot = cur ^ 1;
     s->pin_i = pin ^ 1; s->pin_acq = -1;
     s->flow_w = w; s->flow_h = h;
+    s->flow_fresh = 1;
     s->loop_fc++;
     return RC_OK;
 }
@@ -1402,7 +1486,10 @@ static int batch_launches(rc_ctx* ctx, RcSlot& s, const uint8_t* d_frames, size_
                           float* d_flows, size_t flow_frame_stride, size_t flow_step, int cur) {
     int rc = expand_frames(ctx, s, d_frames, frame_stride, step, S, cur ^ 1, 2);
     if (rc) return rc;
-    return compute_flows(ctx, s, S, cur, d_flows, flow_frame_stride, flow_step, cur ^ 1, 2);
+    // RC_FARNEBACK_USE_INITIAL_FLOW: d_flows[z] is in/out per stream; the reduction is part of the (captured) sequence
+    const RcSeed seed = {d_flows, flow_step, flow_frame_stride};
+    const bool use_seed = (s.plan.prm.flags & RC_FARNEBACK_USE_INITIAL_FLOW) != 0;
+    return compute_flows(ctx, s, S, cur, d_flows, flow_frame_stride, flow_step, cur ^ 1, 2, use_seed ? &seed : nullptr);
 }
 
 extern "C" int rcflow_push_batch_dev(rc_ctx* ctx, int stream, const uint8_t* d_frames, size_t frame_stride, size_t step,
@@ -1431,6 +1518,7 @@ extern "C" int rcflow_push_batch_dev(rc_ctx* ctx, int stream, const uint8_t* d_f
         rc_set_error("bad flow batch buffer");
         return RC_EINVAL;
     }
+    if ((p->flags & RC_FARNEBACK_USE_INITIAL_FLOW) && !seed_layout_ok(d_flows, flow_step, nstreams > 1 ? flow_frame_stride : 0)) return RC_EINVAL;
     const int cur = s->batch_cur;
     RcBatchKey key = {d_frames, frame_stride, step, d_flows, flow_frame_stride, flow_step, (void*)s->cur};
     const bool graph_ok = use_graph && !ctx->prof_on;
@@ -1571,6 +1659,39 @@ extern "C" int rcflow_stage_flow_iter_dev(rc_ctx* ctx, int stream, const float* 
     a.fout = (char*)d_flow_out; a.fout_step = (size_t)w * 8; a.fout_pair_stride = n * 8;
     a.solve = 1; a.win = win; a.xcd_remap = ctx->xcd_remap;
     rc_flow_fast::rc_launch_flow_iter(a, 1, s->cur);
+    RC_HIP(hipGetLastError());
+    return RC_OK;
+}
+
+// INTER_AREA reduction of an initial flow field to the coarsest scale, times pyr_scale^levels (optflow.cpp calc() with
+// OPTFLOW_USE_INITIAL_FLOW): the kernel the level drivers launch, on its own for the parity tests.
+extern "C" int rcflow_stage_initial_flow_dev(rc_ctx* ctx, int stream, const float* d_flow_xy, size_t flow_step, int w,
+                                             int h, double pyr_scale, int levels, float* d_out) {
+    RcSlot* s = rc_slot(ctx, stream);
+    if (!s) return RC_EINVAL;
+    if (!d_flow_xy || !d_out || w <= 0 || h <= 0 || !(pyr_scale > 0 && pyr_scale < 1) || levels < 0 || levels >= RC_MAX_LEVELS ||
+        flow_step < (size_t)w * 8) {
+        rc_set_error("bad initial-flow arguments");
+        return RC_EINVAL;
+    }
+    if (!seed_layout_ok(d_flow_xy, flow_step, 0)) return RC_EINVAL;
+    RC_HIP(hipSetDevice(ctx->device));
+    const int L = crop_levels(w, h, pyr_scale, levels);
+    RcLevel lv;
+    level_geom(w, h, pyr_scale, L, lv);
+    RC_HIP(hipStreamSynchronize(s->cur));      // a previous launch may still read the tables
+    RcFlowAreaArgs a;
+    int rc = rc_flow_area_prepare(s->stage_f32[3], w, h, lv.w, lv.h, a);
+    if (rc) return rc;
+    double scale = 1;
+    for (int i = 0; i < L; i++) scale *= pyr_scale;
+    a.mul = (float)scale;
+    a.src = (const char*)d_flow_xy; a.src_step = flow_step; a.src_pair_stride = 0;
+    a.dst = (float2*)d_out; a.dst_pair_stride = (size_t)lv.w * lv.h;
+    {
+        RcProfScope ps(ctx, s->cur, RC_K_FLOW_SEED, L, 8. * w * h + 8. * lv.w * lv.h);
+        rc_launch_flow_area_init(a, 1, s->cur);
+    }
     RC_HIP(hipGetLastError());
     return RC_OK;
 }
