@@ -7,7 +7,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# RCFLOW_LIB selects another build of the same library (e.g. the diagnostic stamps build)
+# RCFLOW_LIB selects another build of the same library (e.g. for an A/B run of two builds)
 LIB_PATH = os.environ.get("RCFLOW_LIB") or os.path.join(_HERE, "librcflow.so")
 
 RC_OK = 0

@@ -64,27 +64,8 @@ __device__ __forceinline__ const float2* rc_row2(const float* base, size_t step,
 // fall into a handful of bins: lanes are grouped by key with ballots and each group
 // costs one LDS atomic (added with the group's population count).
 #define RC_HIST_COPIES 16
-template <int ROUNDS>
-__device__ __forceinline__ void rc_hist_add(int* lh, int key) {
-    // Peel off the most popular key(s) of the wave with scalar control flow (ballot masks in
-    // SGPRs, the leader's key by v_readlane): a uniform field would otherwise serialise 64
-    // same-address LDS atomics.  What is left takes plain per-lane LDS atomics (distinct keys
-    // do not conflict); on textured flows more than one round cost more than it saved.
-    unsigned long long todo = __ballot(key >= 0);
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int round = 0; round < ROUNDS; round++) {
-        if (!todo) break;
-        int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
-        int k = __builtin_amdgcn_readlane(key, leader);
-        unsigned long long same = __ballot(key == k);
-        if (lane == leader) atomicAdd(&lh[k], __popcll(same));
-        if (key == k) key = -1;
-        todo &= ~same;
-    }
-    if (key >= 0) atomicAdd(&lh[key], 1);
-}
 
+// the key in the reference's own arithmetic (-1: not counted)
 __device__ __forceinline__ int rc_hist_key(float2 f) {
     float mag = sqrtf(f.x * f.x + f.y * f.y);
     int bin = rc_cvt_i32_x86(mag * RC_HIST_RESOLUTION);      // NaN: INT_MIN, not counted
@@ -92,84 +73,7 @@ __device__ __forceinline__ int rc_hist_key(float2 f) {
     return rc_dir_index(rc_fast_atan2_deg(f.y, f.x)) * RC_HIST_BINS + bin;
 }
 
-
-template <int ROUNDS>
-__global__ __launch_bounds__(RC_BLOCK) void k_polar_hist(const float* flow0, size_t frame_stride, size_t step,
-                                                         int w, int h, int* parts) {
-    __shared__ int lh[RC_HIST_DIRECTIONS * RC_HIST_BINS];
-    const float* flow = (const float*)((const char*)flow0 + (size_t)blockIdx.y * frame_stride);
-    for (int i = threadIdx.x; i < RC_HIST_DIRECTIONS * RC_HIST_BINS; i += RC_BLOCK) lh[i] = 0;
-    __syncthreads();
-    const int w2 = (w + 1) >> 1;
-    const int total = w2 * h;                 // the entry point bounds w * h
-    const int span = (int)gridDim.x * RC_BLOCK;
-    // every lane runs the same number of rounds so the ballots see whole waves; four loads are in
-    // flight per thread before the first is consumed
-    const int rounds = (total + span - 1) / span;
-    // (row, pair-in-row) of the thread's item, advanced by `span` items per round without a division
-    const int i0 = (int)blockIdx.x * RC_BLOCK + threadIdx.x;
-    int yy = i0 / w2, xx = i0 - yy * w2;
-    const int dy = span / w2, dx = span - dy * w2;
-    constexpr int UNR = 4;
-    // The next batch's loads are issued before the current batch is binned, so that a wave never computes
-    // with nothing in flight (-4 %; the loads alone take 84 us per 32 1080p fields, the kernel 145: the
-    // rest is instruction issue -- correctly rounded sqrt and divisions, ballots -- not memory)
-    float4 vn[UNR];
-    int nn[UNR];
-    auto load_batch = [&](int it0) {
-#pragma unroll
-        for (int u = 0; u < UNR; u++) {
-            nn[u] = 0;
-            vn[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            const int y = yy, x = xx * 2;
-            yy += dy; xx += dx;
-            if (xx >= w2) { xx -= w2; yy++; }
-            if (it0 + u < rounds && y < h) {
-                const float2* r = rc_row2(flow, step, y) + x;
-                if (x + 1 < w && (((size_t)r) & 15) == 0) {
-                    typedef float rc_f4 __attribute__((ext_vector_type(4)));
-                    const rc_f4 t = __builtin_nontemporal_load((const rc_f4*)r);
-                    vn[u] = make_float4(t.x, t.y, t.z, t.w);
-                    nn[u] = 2;
-                } else {
-                    float2 a0 = r[0];
-                    float2 a1 = x + 1 < w ? r[1] : make_float2(0.f, 0.f);
-                    vn[u] = make_float4(a0.x, a0.y, a1.x, a1.y);
-                    nn[u] = x + 1 < w ? 2 : 1;
-                }
-            }
-        }
-    };
-    load_batch(0);
-    for (int it0 = 0; it0 < rounds; it0 += UNR) {
-        float4 v[UNR];
-        int nv[UNR];
-#pragma unroll
-        for (int u = 0; u < UNR; u++) { v[u] = vn[u]; nv[u] = nn[u]; }
-        if (it0 + UNR < rounds) load_batch(it0 + UNR);
-#pragma unroll
-        for (int u = 0; u < UNR; u++) {
-            if (it0 + u < rounds) {      // block-uniform
-                int k0 = nv[u] >= 1 ? rc_hist_key(make_float2(v[u].x, v[u].y)) : -1;
-                int k1 = nv[u] >= 2 ? rc_hist_key(make_float2(v[u].z, v[u].w)) : -1;
-                rc_hist_add<ROUNDS>(lh, k0);
-                rc_hist_add<ROUNDS>(lh, k1);
-            }
-        }
-    }
-    __syncthreads();
-    // flush into one of RC_HIST_COPIES partial tables: blocks that share a table queue on
-    // the same addresses, so the copies keep those chains short
-    int* part = parts + (size_t)((blockIdx.x + blockIdx.y * gridDim.x) % RC_HIST_COPIES) *
-                            (RC_HIST_DIRECTIONS * RC_HIST_BINS);
-    for (int i = threadIdx.x; i < RC_HIST_DIRECTIONS * RC_HIST_BINS; i += RC_BLOCK) {
-        int v = lh[i];
-        if (v) atomicAdd(&part[i], v);
-    }
-}
-
-// ---- second form of the histogram kernel (the one that runs; k_polar_hist above is kept behind option
-// "ablate" bit RC_ABL_HIST_V1 for A/B runs).  Two changes, same counts:
+// ---- the histogram kernel.  Same counts as one exact key and one LDS atomic per pixel, by two means:
 //  * the key.  ripcurrents.cpp:305-309 + ripcurrents_module.cpp:97-100 cost a correctly rounded sqrt and two IEEE
 //    divisions per pixel (min/max inside fastAtan2, and (angle*36)/360).  Here the magnitude is s*rsq(s) and the
 //    quotients are products with v_rcp_f32 / a constant -- each within a few ulps of the exact value -- and a pixel
@@ -182,9 +86,6 @@ __global__ __launch_bounds__(RC_BLOCK) void k_polar_hist(const float* flow0, siz
 //    goes through the wave-level step: the first lane's key is broadcast, the counts of all lanes holding it are
 //    summed with DPP / permute steps and added by one LDS atomic; lanes holding another key add their own pair.
 //    One scalar round per 8 pixels instead of one per pixel.
-#ifndef RC_HIST_ABL
-#define RC_HIST_ABL 0     // diagnostic builds only (scripts/r3/variant_ana.sh)
-#endif
 __device__ __forceinline__ int rc_hist_key_fast(float2 f, bool& exact_needed) {
     const float s = f.x * f.x + f.y * f.y;
     const float m = __builtin_amdgcn_sqrtf(s);                       // v_sqrt_f32 (1 ulp); 0 -> 0, NaN -> NaN, inf -> inf
@@ -289,15 +190,6 @@ __global__ __launch_bounds__(RC_BLOCK) void k_polar_hist_rows(const float* flow0
     auto process = [&](const float4 (&v)[NR], const int (&nv)[NR]) {
         int k[2 * NR];
         bool redo = false;
-#if RC_HIST_ABL == 2     // timing-only build: the loads alone
-        {
-            float acc = 0.f;
-#pragma unroll
-            for (int r = 0; r < NR; r++) acc += v[r].x + v[r].y + v[r].z + v[r].w;
-            if (acc == 12345.678f) atomicAdd(&lh[0], 1);
-            return;
-        }
-#endif
         unsigned em = 0;                         // bit i: key i has to be taken again with the reference's own arithmetic
         if constexpr (plain) {
             // (a lane without an item skips the keys altogether: whole waves do in the last round)
@@ -333,15 +225,6 @@ __global__ __launch_bounds__(RC_BLOCK) void k_polar_hist_rows(const float* flow0
                 if (em >> (2 * r + 1) & 1u) k[2 * r + 1] = rc_hist_key(make_float2(v[r].z, v[r].w));
             }
         }
-#if RC_HIST_ABL == 1     // timing-only build: loads and keys, no aggregation
-        {
-            int acc = 0;
-#pragma unroll
-            for (int i = 0; i < 2 * NR; i++) acc ^= k[i];
-            if (acc == 0x12345678) atomicAdd(&lh[0], 1);
-            return;
-        }
-#endif
         // lane level: the first key and its multiplicity; other keys singly
         const int A = k[0];
         int cnt = 1;
@@ -923,32 +806,24 @@ extern "C" int rcflow_histogram_clip_dev(rc_ctx* ctx, int stream, const float* d
     s->an.hist_added += (long long)w * h * count;
     {
         RcProfScope ps(ctx, s->cur, RC_K_HIST, 0, 8. * w * h * count);
-        long long per_frame = ((long long)(w + 1) / 2) * h;
-        int nb = grid_for(per_frame);
         // many light blocks: the partial tables keep the flush chains short, and one ballot round catches the dominant
         // bin of a wave.  8192 blocks per launch = four items per thread at 32 frames of 1080p: one more round of prefetch
         // than 16384 (134 -> 129 us), 4096: 131, 32768: 147 (profiles/r03_notes.md)
         int cap = (ctx->hist_blocks > 0 ? ctx->hist_blocks : 8192) / count;
         if (cap < 8) cap = 8;
-        if (nb > cap) nb = cap;
-        if (ctx->ablate & RC_ABL_HIST_V1) {
-            hipLaunchKernelGGL(k_polar_hist<1>, dim3(nb, count), dim3(RC_BLOCK), 0, s->cur, d_flows, flow_frame_stride,
+        // items are 2 x 4 pixel columns
+        int nb4 = grid_for(((long long)(w + 1) / 2) * ((h + 3) / 4));
+        if (nb4 > cap) nb4 = cap;
+        // every item whole (even width, height a multiple of the item's four rows), every row of every frame 16-byte
+        // aligned, offsets inside a frame below 4 GB: the kernel's plain form
+        const bool plain = ((w & 1) | (h & 3)) == 0 && ((((size_t)d_flows) | flow_step | (count > 1 ? flow_frame_stride : 0)) & 15) == 0 &&
+                           (size_t)h * flow_step < ((size_t)1 << 32);
+        if (plain)
+            hipLaunchKernelGGL(k_polar_hist_rows<true>, dim3(nb4, count), dim3(RC_BLOCK), 0, s->cur, d_flows, flow_frame_stride,
                                flow_step, w, h, (int*)s->an.hist_part.p);
-        } else {
-            // items are 2 x 4 pixel columns: a quarter of the items of the first form for the same block count
-            int nb4 = grid_for(((long long)(w + 1) / 2) * ((h + 3) / 4));
-            if (nb4 > cap) nb4 = cap;
-            // every item whole (even width, height a multiple of the item's four rows), every row of every frame 16-byte
-            // aligned, offsets inside a frame below 4 GB: the kernel's plain form
-            const bool plain = ((w & 1) | (h & 3)) == 0 && ((((size_t)d_flows) | flow_step | (count > 1 ? flow_frame_stride : 0)) & 15) == 0 &&
-                               (size_t)h * flow_step < ((size_t)1 << 32);
-            if (plain)
-                hipLaunchKernelGGL(k_polar_hist_rows<true>, dim3(nb4, count), dim3(RC_BLOCK), 0, s->cur, d_flows, flow_frame_stride,
-                                   flow_step, w, h, (int*)s->an.hist_part.p);
-            else
-                hipLaunchKernelGGL(k_polar_hist_rows<false>, dim3(nb4, count), dim3(RC_BLOCK), 0, s->cur, d_flows, flow_frame_stride,
-                                   flow_step, w, h, (int*)s->an.hist_part.p);
-        }
+        else
+            hipLaunchKernelGGL(k_polar_hist_rows<false>, dim3(nb4, count), dim3(RC_BLOCK), 0, s->cur, d_flows, flow_frame_stride,
+                               flow_step, w, h, (int*)s->an.hist_part.p);
         hipLaunchKernelGGL(k_hist_fold, dim3((RC_HIST_DIRECTIONS * RC_HIST_BINS + RC_BLOCK - 1) / RC_BLOCK),
                            dim3(RC_BLOCK), 0, s->cur, (int*)s->an.hist_part.p, (int*)s->an.hist.p);
     }

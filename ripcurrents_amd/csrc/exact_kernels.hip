@@ -89,9 +89,7 @@ __global__ __launch_bounds__(256) void k_exact_polyexp(RcPolyArgs a) {
 // results in three LDS planes; horizontal pass = one thread per (row, 4 pixels) over a register window of
 // 4 + 2N columns read as float4s, the six double accumulators of a pixel advanced in upstream's tap order
 // (the chains of different accumulators are independent, so plane by plane gives the same bits).
-#ifndef RC_EXP_WAVES
 #define RC_EXP_WAVES 2
-#endif
 // TH rows per block: 32, or 8 for launches of a few dozen tiles (a launch of fewer blocks than the GPU holds lasts one
 // block's lifetime; the vertical pass's register window spans R + 2 N rows whatever TH is).  Same bits.
 template <int N, int TH = 32>
@@ -202,9 +200,9 @@ static void launch_exact_polyexp_t(const RcPolyArgs& a, int frames, hipStream_t 
 }
 
 void rc_launch_exact_polyexp(const RcPolyArgs& a, int frames, hipStream_t s) {
-    if (a.pk.n == 15 && !a.no_fast_u8) { launch_exact_polyexp_t<15>(a, frames, s); return; }
-    if (a.pk.n == 7 && !a.no_fast_u8) { launch_exact_polyexp_t<7>(a, frames, s); return; }
-    if (a.pk.n == 5 && !a.no_fast_u8) { launch_exact_polyexp_t<5>(a, frames, s); return; }
+    if (a.pk.n == 15) { launch_exact_polyexp_t<15>(a, frames, s); return; }
+    if (a.pk.n == 7) { launch_exact_polyexp_t<7>(a, frames, s); return; }
+    if (a.pk.n == 5) { launch_exact_polyexp_t<5>(a, frames, s); return; }
     const size_t lds = sizeof(float) * 3 * RC_EX_TH * (RC_EX_TW + 2 * a.pk.n);
     dim3 grid((a.w + RC_EX_TW - 1) / RC_EX_TW, (a.h + RC_EX_TH - 1) / RC_EX_TH, frames);
     hipLaunchKernelGGL(k_exact_polyexp, grid, dim3(256), lds, s, a);

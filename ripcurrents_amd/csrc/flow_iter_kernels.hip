@@ -23,9 +23,7 @@
 #include "rc_device.h"
 
 #define RC_ITER_BATCH 3
-#ifndef RC_RR_D
 #define RC_RR_D 3         // displacements below this many pixels are served from the LDS window (28 x 28 tile)
-#endif
 
 // This file is compiled twice.  The default build (namespace rc_flow_fast) is the fast arithmetic:
 // sums of products as fused multiply-adds, the winsize-3 solve in fp32 (Kahan).  With -DRC_EXACT_BUILD
@@ -91,15 +89,9 @@ __device__ __forceinline__ void rc_gather_issue(RcGather& g, const float4* __res
     g.e00 = RB1[p]; g.e01 = RB1[p + p1]; g.e10 = RB1[p + pw]; g.e11 = RB1[p + pw + p1];
 }
 
-#ifndef RC_HALF_WEIGHTS
-#define RC_HALF_WEIGHTS 1     // fast build: the averages with R0 folded into the interpolation (0 = the separate sums of round 2)
-#endif
-#if defined(RC_EXACT_BUILD) || !RC_HALF_WEIGHTS
-#define RC_M_PLAIN 1
-#endif
 // R0 as rc_matrices_reg takes it: halved in the fast build (exact: a power of two), untouched in the exact build
 __device__ __forceinline__ void rc_r0_prep(float4& A0, float& B0) {
-#ifndef RC_M_PLAIN
+#ifndef RC_EXACT_BUILD
     A0.x *= 0.5f; A0.y *= 0.5f; A0.z *= 0.5f; A0.w *= 0.5f; B0 *= 0.5f;
 #endif
 }
@@ -107,14 +99,10 @@ __device__ __forceinline__ void rc_r0_prep(float4& A0, float& B0) {
 __device__ __forceinline__ RcM5 rc_matrices_reg(const float4 A0, const float B0, const RcGather& g, float dx,
                                                 float dy, int X, int Y, int w, int h, bool BORDER = true) {
     float fx = g.fx, fy = g.fy;
-#ifdef RC_M_PLAIN
+#ifdef RC_EXACT_BUILD
     float a00 = (1.f - fx) * (1.f - fy), a01 = fx * (1.f - fy);
     float a10 = (1.f - fx) * fy, a11 = fx * fy;
-#ifdef RC_EXACT_BUILD
 #define RC_BILIN(c, e) (a00 * e##00 c + a01 * e##01 c + a10 * e##10 c + a11 * e##11 c)
-#else
-#define RC_BILIN(c, e) RC_FMA(a11, e##11 c, RC_FMA(a10, e##10 c, RC_FMA(a01, e##01 c, a00 * e##00 c)))
-#endif
     float r2 = RC_BILIN(.x, g.q), r3 = RC_BILIN(.y, g.q), r4 = RC_BILIN(.z, g.q), r5 = RC_BILIN(.w, g.q);
     float r6 = RC_BILIN(, g.e);
 #undef RC_BILIN
@@ -706,10 +694,6 @@ __global__ __launch_bounds__(RC_W3_THREADS) void k_flow_iter_w3(RcIterArgs a) {
     const float2* __restrict__ fin = a.fin + (size_t)z * a.fin_pair_stride;
     char* fout = a.fout + (size_t)z * a.fout_pair_stride;
 
-    if (a.ablate & RC_ABL_EMPTY_BLOCKS) {              // ablation: empty block
-        if (tid == 9999) *(float*)fout = 1.f;
-        return;
-    }
     int gx[NIT], gy[NIT];
 #pragma unroll
     for (int q = 0; q < NIT; q++) {
@@ -779,10 +763,6 @@ __global__ __launch_bounds__(RC_W3_THREADS) void k_flow_iter_w3(RcIterArgs a) {
         }
     }
     __syncthreads();
-    if (a.ablate & RC_ABL_NO_WINDOW) {              // ablation: no window / solve / store
-        if (Ms[tid] == 12345.678f) *(float*)fout = 1.f;
-        return;
-    }
 
     // ---- 3x3 window + solve: lane = column, RPT rows per thread
     constexpr int RPT = TH / (RC_W3_THREADS / TW);
@@ -1127,9 +1107,6 @@ __device__ __forceinline__ void rc_rrc_issue_window(const float4* __restrict__ R
 // image) take a straight-line path: every lane gathers from the LDS window at an index clamped into it, and a
 // lane whose displacement leaves the window (|flow| >= D, rare) is redone from global memory afterwards.  The
 // values are those of rc_gather_window + rc_matrices_reg, which border blocks keep using: same bits.
-#ifndef RC_RRC_ABL
-#define RC_RRC_ABL 0      // timing-only cuts of k_flow_iter2_rrc (never in the product): 1 = no window DMA after the head of a chain, 2 = the loads alone
-#endif
 template <bool INTERIOR, int NIT, int WW, int WH, int WP>
 __device__ __forceinline__ void rc_rr_matrices(float (&m)[NIT][5], const float4 (&A0)[NIT], const float (&B0)[NIT],
                                                const float (&dx)[NIT], const float (&dy)[NIT], const float4* LA,
@@ -1236,28 +1213,6 @@ __device__ __forceinline__ void rc_rrc_body(const RcIterArgs& a, const int zb, c
         asm volatile("" : "+v"(tid));
         RC_RRC_COORDS(tid)
         rc_all_barrier();     // this pair's window has landed (and the previous pair's exchange rows are dead)
-#if RC_RRC_ABL == 2
-        if (a.w > 0) {        // timing-only build: the loads and the hand-over alone
-            if (more) {
-#pragma unroll
-                for (int q = 0; q < NIT; q++) {
-                    const int i = (gys[q] - oy) * WP + (gxo - ox);
-                    A0[q].x += LA[i].x + LA[i].w;
-                    B0[q] += LB[i];
-                }
-                rc_lds_barrier();
-                const size_t n1 = (size_t)((a.slot1 + (z + 1) * a.zstep) % a.nslots) * a.R_slot_stride;
-                rc_rrc_issue_window<INTERIOR, NT, WP, WN, NWL>(a.RA + n1, a.RB + n1, lds_a, lds_b, tid, ox, oy, w, h);
-                rc_rr_flow_in<IN_MODE, NIT, MW, MH, INTERIOR>(a, a.fin + (size_t)(z + 1) * a.fin_pair_stride, tx0, ty0, gxo, gys, dx, dy);
-            } else {
-                float acc = dx[0] + dy[NIT - 1];
-#pragma unroll
-                for (int q = 0; q < NIT; q++) acc += A0[q].x + A0[q].w + B0[q];
-                if (acc == 12345.678f) *(float*)a.fout = acc;
-            }
-            continue;
-        }
-#endif
 
         // ---- M0 on the whole grid, in registers
         float m[NIT][5];
@@ -1307,12 +1262,10 @@ __device__ __forceinline__ void rc_rrc_body(const RcIterArgs& a, const int zb, c
         rc_lds_barrier();     // (border blocks: the aliased M1 planes have been read by everyone too)
 
         // ---- the next pair's window is requested before this pair's last window sums, solve and stores
-#if RC_RRC_ABL != 1
         if (more) {
             const size_t n1 = (size_t)((a.slot1 + (z + 1) * a.zstep) % a.nslots) * a.R_slot_stride;
             rc_rrc_issue_window<INTERIOR, NT, WP, WN, NWL>(a.RA + n1, a.RB + n1, lds_a, lds_b, tid, ox, oy, w, h);
         }
-#endif
 
         // ---- flow2 on the tile
         {
@@ -1472,7 +1425,7 @@ void rc_launch_flow_iter(const RcIterArgs& a, int pairs, hipStream_t s) {
         return;
     }
     if (m == 1) { g ? launch_iter_t<64, 16, 1, 1>(a, pairs, s) : launch_iter_t<64, 16, 1, 0>(a, pairs, s); return; }
-    if (a.solve && !(a.ablate & RC_ABL_GENERIC_WINDOW)) {
+    if (a.solve) {
         // 16 waves per CU: LDS 50 KB (m = 2) -> 3 blocks x 512 threads, 64 KB (m = 5) -> 2 x 1024, 142 KB (m = 10, 64 x 32 tile) -> 1 x 1024
         if (m == 2) { g ? launch_iter_big<2, 1, 512>(a, pairs, s) : launch_iter_big<2, 0, 512>(a, pairs, s); return; }
         // Gaussian winsize 10 / 20: the strip-sweep kernel once the launch is big enough to fill the GPU
@@ -1481,16 +1434,11 @@ void rc_launch_flow_iter(const RcIterArgs& a, int pairs, hipStream_t s) {
         const long long work = (long long)a.w * a.h * pairs;
         if (g && (m == 5 || m == 10) && !(a.ablate & RC_ABL_TILE_WINDOW) &&
             ((a.ablate & RC_ABL_FORCE_SWEEP) || work >= (m == 10 ? 900000ll : 8000000ll))) {
-            if (a.ablate & RC_ABL_SWEEP_512T) { m == 5 ? launch_iter_sweep<5, 512, 2>(a, pairs, s) : launch_iter_sweep<10, 512, 2>(a, pairs, s); }
-            else { m == 5 ? launch_iter_sweep<5, 1024, 1>(a, pairs, s) : launch_iter_sweep<10, 1024, 1>(a, pairs, s); }
+            m == 5 ? launch_iter_sweep<5, 1024, 1>(a, pairs, s) : launch_iter_sweep<10, 1024, 1>(a, pairs, s);
             return;
         }
         if (m == 5) { g ? launch_iter_big<5, 1, 1024>(a, pairs, s) : launch_iter_big<5, 0, 1024>(a, pairs, s); return; }   // (64 wide: 6 % slower, one block per CU)
-        if (m == 10) {
-            if (a.ablate & RC_ABL_BIG_32WIDE) { g ? launch_iter_big<10, 1, 1024>(a, pairs, s) : launch_iter_big<10, 0, 1024>(a, pairs, s); }
-            else { g ? launch_iter_big<10, 1, 1024, 64>(a, pairs, s) : launch_iter_big<10, 0, 1024, 64>(a, pairs, s); }
-            return;
-        }
+        if (m == 10) { g ? launch_iter_big<10, 1, 1024, 64>(a, pairs, s) : launch_iter_big<10, 0, 1024, 64>(a, pairs, s); return; }
     }
     if (m == 2) { g ? launch_iter_t<64, 16, 2, 1>(a, pairs, s) : launch_iter_t<64, 16, 2, 0>(a, pairs, s); return; }
     if (m == 5) { g ? launch_iter_t<32, 32, 5, 1>(a, pairs, s) : launch_iter_t<32, 32, 5, 0>(a, pairs, s); return; }

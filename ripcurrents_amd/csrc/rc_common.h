@@ -88,31 +88,21 @@ struct RcPolyArgs {
     int slot0, nslots, zstep;
     int w, h;
     int tile_h;               // rows per block: 32 or 48 (option "poly_tile_h")
-    int no_fast_u8;           // diagnostic: byte-wise staging for every tile
     int valu_vertical;        // option "poly_mfma" = 0: vertical pass on the VALU instead of the matrix cores
-    long long* stamps;        // diagnostic s_memtime stamps (RC_STAMPS builds; null in production)
     RcPolyK pk;
     int npyr;                 // scale 0 only: pyramid scales 1..npyr come out of this launch too
     RcPyrFused py[2];
 };
 
-// Option "ablate": earlier kernel forms and timing-only cuts kept for same-box A/B runs (0 in production).
-// The first three change results (timing only); every other bit selects a bit-identical alternative.
+// Option "ablate" (0 in production): every bit selects a bit-identical alternative form of a kernel, or forces a
+// production kernel at launch sizes that would not pick it; the bit-identity tests compare the forms.
 enum RcAblate : int {
-    RC_ABL_STAGE_A_ONLY = 1,         // winsize-3 kernels: stop after the first matrices stage
     RC_ABL_EXACT_PLAIN_SCANS = 2,    // option exact, box windows of winsize 3 / 5: the plain scans (V and G row-major in HBM, separate solve)
     RC_ABL_EXACT_FUSED_M = 16,       // option exact, box windows of winsize 3 / 5: FarnebackUpdateMatrices inside the column scan (measured slower)
-    RC_ABL_NO_WINDOW = 4,            // skip window / solve / store
-    RC_ABL_EMPTY_BLOCKS = 8,         // launch cost only
-    RC_ABL_NO_FAST_U8 = 2048,        // expansion at scale 0: per-byte staging instead of dwords + v_perm
     RC_ABL_PYR_STAGED = 4096,        // pyramid: per-pixel / LDS-staged kernels
-    RC_ABL_GENERIC_WINDOW = 8192,    // windows 5 / 10 / 20: runtime-sized generic kernel
-    RC_ABL_BIG_32WIDE = 32768,       // winsize 20 tile kernel: 32-wide tiles
     RC_ABL_TILE_WINDOW = 65536,      // Gaussian winsize 10 / 20: tile kernel even for large launches
-    RC_ABL_SWEEP_512T = 131072,      // strip-sweep kernel with 512 threads
     RC_ABL_FORCE_SWEEP = 8388608,    // strip-sweep kernel even for small launches
     RC_ABL_FORCE_CHAIN = 33554432,   // fused winsize-3 kernel: tile chains (option "chain") even for launches too small to want them
-    RC_ABL_HIST_V1 = 16777216,       // histogram: the first form of the kernel (one scalar round per pixel, exact key everywhere)
 };
 
 struct RcIterArgs {
@@ -137,7 +127,7 @@ struct RcIterArgs {
     int tiles_x, tiles_y;
     int solve;                // 0: write flow_in (iterations == 0), 1: normal
     int xcd_remap;            // XCD-aware tile order (speed only)
-    int ablate;               // timing-only ablation bits (0 in production)
+    int ablate;               // option "ablate" (RcAblate; 0 in production)
     int addr32;               // every offset inside one frame's R planes and one pair's flow field fits 32 bits (set by the level driver)
     int chain_min_blocks;     // option "chain_min_blocks": a launch keeps at least this many blocks when its chains are shortened (0 = 4096)
     int chain;                // option "chain": consecutive pairs a block of the fused winsize-3 kernel walks on its tile (<= 1: none)

@@ -120,7 +120,6 @@ struct rc_ctx {
     int fuse_pyr = 1;         // scale-0 expansion also writes pyramid scales 1 and 2 (exact 2:1 / 4:1 sizes)
     int ablate = 0;
     void* comm = nullptr;      // RcComm (comm_rccl.hip): the histogram all-reduce over RCCL
-    void* stamps = nullptr;
     int prof_on = 0;
     std::vector<RcProfRec> prof_pending;
     std::vector<hipEvent_t> ev_pool;

@@ -260,13 +260,6 @@ extern "C" int rcflow_use_own_stream(rc_ctx* ctx, int stream) {
     return RC_OK;
 }
 
-extern "C" int rcflow_debug_read_stamps(rc_ctx* ctx, long long* out, int n) {
-    if (!ctx || !ctx->stamps || !out || n > 8 * 4096) return RC_EINVAL;
-    RC_HIP(hipDeviceSynchronize());
-    RC_HIP(hipMemcpy(out, ctx->stamps, (size_t)n * 8, hipMemcpyDeviceToHost));
-    return RC_OK;
-}
-
 // Diagnostic (not part of include/rcflow.h; tests/test_cabi_and_host.py): the pair groups the fused winsize-3 kernel would
 // walk for a launch of `pairs` consecutive pairs of a w x h scale with option chain = `chain` -- pure host logic, no GPU.
 extern "C" int rcflow_debug_chain_plan(int w, int h, int pairs, int chain, int force, int* starts, int cap) {
@@ -329,15 +322,6 @@ extern "C" int rcflow_set_option(rc_ctx* ctx, const char* name, int value) {
         ctx->fuse_pyr = value != 0;
     } else if (!strcmp(name, "ablate")) {
         ctx->ablate = value;
-    } else if (!strcmp(name, "stamps")) {
-        // diagnostic: value != 0 allocates a stamp buffer that the scale-0 flow kernel fills
-        if (value && !ctx->stamps) {
-            if (hipMalloc(&ctx->stamps, 8 * 8 * 4096) != hipSuccess) return RC_ENOMEM;
-            (void)hipMemset(ctx->stamps, 0, 8 * 8 * 4096);
-        } else if (!value && ctx->stamps) {
-            (void)hipFree(ctx->stamps);
-            ctx->stamps = nullptr;
-        }
     } else {
         rc_set_error("unknown option %s", name);
         return RC_EINVAL;
@@ -671,8 +655,7 @@ static int expand_frames(rc_ctx* ctx, RcSlot& s, const uint8_t* d_src, size_t fr
         memset(&q, 0, sizeof(q));
         q.RA = (float4*)s.RA[k].p; q.RB = (float*)s.RB[k].p; q.R_slot_stride = n;
         q.slot0 = dslot0; q.nslots = pl.nslots; q.zstep = zstep; q.w = L.w; q.h = L.h; q.pk = pl.pk;
-        q.tile_h = ctx->poly_tile_h; q.no_fast_u8 = (ctx->ablate & RC_ABL_NO_FAST_U8) != 0; q.valu_vertical = !ctx->poly_mfma;
-        q.stamps = (k == 0) ? (long long*)ctx->stamps : nullptr;
+        q.tile_h = ctx->poly_tile_h; q.valu_vertical = !ctx->poly_mfma;
         if (k == 0 && !pl.exact) {
             // scale 0: pyramid (3x3 blur, identity resize) fused into the expansion
             q.src8 = d_src; q.src8_step = step; q.src8_frame_stride = frame_stride;
