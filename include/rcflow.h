@@ -337,6 +337,61 @@ int rcflow_resize_bgr_to_gray_dev(rc_ctx* ctx, int stream, const uint8_t* d_bgr,
 int rcflow_resize_area_bgr_to_gray_dev(rc_ctx* ctx, int stream, const uint8_t* d_bgr, size_t step,
                                        int sw, int sh, uint8_t* d_gray, size_t gray_step, int dw, int dh);
 
+/* The resize alone, 8UC3 out: resize(frame, resized_frame, Size(dw,dh), 0, 0, INTER_LINEAR) as the time-exposure
+ * pipelines call it (main.cpp:1227, :1302).  Same fixed-point arithmetic as rcflow_resize_bgr_to_gray_dev. */
+int rcflow_resize_bgr_dev(rc_ctx* ctx, int stream, const uint8_t* d_bgr, size_t step, int sw, int sh,
+                          uint8_t* d_out, size_t out_step, int dw, int dh);
+
+/* ------------------------------------------------------------------ time-exposure images
+ * compute_timex (main.cpp:1195-1263) and compute_brightColor (main.cpp:1265-1383) on frames resident on the device.
+ * All images are 8UC3; "channel 0 / 1 / 2" are the bytes as they come (the reference feeds BGR frames to
+ * COLOR_RGB2HSV and back through COLOR_HSV2RGB, so byte 0 plays "R" both ways).
+ *   RC_TIMEX_MEAN     sum (fp32) += frame; out = convertTo(8U) of sum * (float)(1.0 / n), n = frames so far (:1231-1241).
+ *   The ring products keep the last `window` frames in HSV (all zero at open), slot c = (frames so far) % window
+ *   written before the product is taken (:1305-1363), with q(v) = convertTo(8U) of v * (float)(1.0 / window):
+ *   RC_TIMEX_AVERAGE  per channel min(255, sum of q(slot)) -- the reference's saturating adds of non-negative terms;
+ *   RC_TIMEX_BRIGHT   the triple of the slot with the largest V, RC_TIMEX_DARK the smallest, where slot 0 takes part
+ *                     DIVIDED (q of all three channels: the reference seeds with buffer_hsv[0] / windowSize) and the
+ *                     lowest slot index wins ties (its walk replaces on strictly better only).
+ * Every product is the bits of the reference's rescan of the whole ring, kept incrementally: bytes per frame do not
+ * grow with the window, except that a pixel whose BRIGHT / DARK winner is overwritten by a worse sample walks the V
+ * plane of the ring again.  When profiling is on the launches are recorded as "timex@0" (mean) and "timex@1" (ring
+ * products), the stage kernels below as "frame_color@0..2"; rcflow_profile_read_buckets books them under "overlay". */
+#define RC_TIMEX_MEAN 1      /* main.cpp:1195-1263 */
+#define RC_TIMEX_AVERAGE 2   /* main.cpp:1265-1383, option 0 */
+#define RC_TIMEX_BRIGHT 4    /* option 1 */
+#define RC_TIMEX_DARK 8      /* option 2 */
+/* Opens the slot's time-exposure state for w x h frames: `products` is a mask of the above; the three ring products
+ * share one ring of `window` frames (1..4096; ignored for MEAN alone).  Allocates everything it will ever need
+ * (window * 3 bytes per pixel for the ring; RC_ENOMEM with the byte count in rcflow_last_error if it does not fit);
+ * re-opening replaces the state.  RC_EINVAL for a bad mask or window, RC_ESIZE beyond the context's max_w x max_h.
+ * The state is zeroed asynchronously on the stream the slot has at this call (so does rcflow_timex_reset).  The first
+ * push after it waits for that zeroing even if rcflow_set_hip_stream moved the slot in between; beyond that, as for
+ * every entry point, work queued on the slot's former stream is the caller's to order when the slot changes stream. */
+int rcflow_timex_open(rc_ctx* ctx, int stream, int w, int h, int window, int products);
+/* One frame: d_frame 8UC3 of the opened size.  d_out[4]: device 8UC3 images for MEAN, AVERAGE, BRIGHT, DARK in that
+ * order; an entry (or d_out itself) may be NULL: the state is still updated.  RC_EINVAL for an entry of a product that
+ * is not open, for a step below 3 * w, and for an output that overlaps the frame or another output (in place is not
+ * supported); RC_ESTATE before rcflow_timex_open.  Asynchronous on the slot's stream, one launch for MEAN and one for
+ * all ring products. */
+int rcflow_timex_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_frame, size_t step,
+                          uint8_t* const d_out[4], const size_t out_step[4]);
+/* zeroes sums, ring, slot index and frame count; keeps the allocation */
+int rcflow_timex_reset(rc_ctx* ctx, int stream);
+/* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
+int rcflow_timex_close(rc_ctx* ctx, int stream);
+/* any pointer may be NULL; window is 0 for MEAN alone; device_bytes = everything the state holds on the device.
+ * RC_ESTATE when nothing is open on the slot. */
+int rcflow_timex_info(rc_ctx* ctx, int stream, int* w, int* h, int* window, int* products,
+                      long long* frames_pushed, size_t* device_bytes);
+/* cvtColor(COLOR_RGB2HSV) and cvtColor(COLOR_HSV2RGB) on 8UC3 images (color_hsv.cpp, hue range 180), the stages of
+ * the ring products: integer forward (H = hue / 2, S, V in 0..255), through float back; a hue byte above 179 wraps.
+ * In place (same pointer and step) is allowed. */
+int rcflow_rgb_to_hsv_u8_dev(rc_ctx* ctx, int stream, const uint8_t* d_rgb, size_t step, int w, int h,
+                             uint8_t* d_hsv, size_t hsv_step);
+int rcflow_hsv_to_rgb_u8_dev(rc_ctx* ctx, int stream, const uint8_t* d_hsv, size_t hsv_step, int w, int h,
+                             uint8_t* d_rgb, size_t step);
+
 /* Display path, ripcurrents.cpp:233-273 (= streamline_displacement / _total_motion / _ratio /
  * _positions, ripcurrents_module.cpp:13-60) on the slot's streamline field (rcflow_advect_field_dev):
  * which 0 = |pt|, 1 = dist, 2 = |pt| / dist; minMaxLoc + convertTo(CV_8UC1, 255/max) +
@@ -416,7 +471,7 @@ int rcflow_profile_read(rc_ctx* ctx, int cap, const char** names, int* launches,
 
 /* The same totals under the reference's own bucket names, in the order it prints them (ripcurrents.cpp:103-109,
  * :518-524): farneback, polar, threshold, overlay, erosion, codec, stream ("pathlines").  GPU time of the kernels
- * that do each bucket's work; "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
+ * that do each bucket's work ("overlay" includes the time-exposure images and the 8-bit colour stages); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
  * classification kernels, booked under "threshold"), "codec" is 0 (video decode is host I/O outside the library).
  * names / ms: RC_PROFILE_BUCKETS entries each (either may be NULL).  Returns RC_PROFILE_BUCKETS. */
 #define RC_PROFILE_BUCKETS 7

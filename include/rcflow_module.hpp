@@ -12,6 +12,7 @@
 //   streamline                 ripcurrents.hpp:23   ripcurrents_module.cpp:486-528
 //   Streakline                 Streakline.hpp:8-20  Streakline.cpp:11-71
 //   Timeline, PopulationMap    ripcurrents.hpp:64-75, 86-95  ripcurrents_module.cpp:751-807, 1140-1196
+//   timexOpen / timexPush      compute_timex main.cpp:1195-1263, compute_brightColor main.cpp:1265-1383
 // rc::Mat is a non-owning view with cv::Mat's fields (data, step, rows, cols); with OpenCV
 // present, include/rcflow_cv.hpp converts cv::Mat to it.  Errors are thrown as
 // rc::Error (the reference's OpenCV calls throw cv::Exception and are never caught).
@@ -294,6 +295,39 @@ class Pipeline {
         }
         check(rc);
     }
+
+    // The time-exposure pipelines on frames of the pipeline's size: compute_timex (main.cpp:1195-1263, RC_TIMEX_MEAN)
+    // and compute_brightColor (main.cpp:1265-1383: RC_TIMEX_AVERAGE / _BRIGHT / _DARK = its options 0 / 1 / 2 over a
+    // ring of `window` frames).  timexPush takes the resized 8UC3 frame (main.cpp:1227, :1302) and fills the images
+    // asked for (8UC3 of the frame size; an empty Mat skips that product's image, its state is still updated) with
+    // what the reference writes to its output video after this frame.
+    void timexOpen(int window, int products) { check(rcflow_timex_open(ctx_, 0, w_, h_, window, products)); }
+    void timexPush(const Mat& frame, Mat& mean, Mat& average, Mat& bright, Mat& dark) {
+        Mat* outs[4] = {&mean, &average, &bright, &dark};
+        const size_t img = ((size_t)w_ * h_ * 3 + 255) & ~(size_t)255;
+        auto is_8uc3 = [this](const Mat& m) { return m.rows == h_ && m.cols == w_ && m.channels == 3 && m.elem == 1; };
+        if (frame.empty() || !is_8uc3(frame)) throw Error(RC_EINVAL, "timexPush: frame must be 8UC3 of the pipeline's size");
+        for (Mat* m : outs)
+            if (!m->empty() && !is_8uc3(*m)) throw Error(RC_EINVAL, "timexPush: images must be 8UC3 of the frame size");
+        uint8_t* b = (uint8_t*)scratch(5 * img);                 // grow-only: the frame and the four images
+        hip_check(hipMemcpy2D(b, (size_t)w_ * 3, frame.data, frame.step, (size_t)w_ * 3, h_, hipMemcpyHostToDevice), "upload frame");
+        uint8_t* d_out[4];
+        size_t out_step[4];
+        for (int k = 0; k < 4; k++) {
+            d_out[k] = outs[k]->empty() ? nullptr : b + (k + 1) * img;
+            out_step[k] = (size_t)w_ * 3;
+        }
+        int rc = rcflow_timex_push_dev(ctx_, 0, b, (size_t)w_ * 3, d_out, out_step);
+        if (rc == RC_OK) rc = rcflow_sync(ctx_, 0);
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < 4 && rc == RC_OK && e == hipSuccess; k++)
+            if (d_out[k])
+                e = hipMemcpy2D(outs[k]->data, outs[k]->step, d_out[k], (size_t)w_ * 3, (size_t)w_ * 3, h_, hipMemcpyDeviceToHost);
+        check(rc);
+        hip_check(e, "download time-exposure image");
+    }
+    void timexReset() { check(rcflow_timex_reset(ctx_, 0)); }
+    void timexClose() { check(rcflow_timex_close(ctx_, 0)); }
 
     int width() const { return w_; }
     int height() const { return h_; }

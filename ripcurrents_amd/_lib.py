@@ -16,6 +16,8 @@ RC_FARNEBACK_USE_INITIAL_FLOW = 4
 HIST_BINS, HIST_DIRECTIONS, HIST_RESOLUTION = 50, 36, 20
 HIST_WORDS = HIST_BINS + HIST_DIRECTIONS * HIST_BINS + 1 + HIST_DIRECTIONS
 COMM_ID_BYTES = 128     # RC_COMM_ID_BYTES = sizeof(ncclUniqueId)
+# RC_TIMEX_*: product name -> mask bit; the order is the order of rcflow_timex_push_dev's d_out[4]
+TIMEX_PRODUCTS = {"mean": 1, "average": 2, "bright": 4, "dark": 8}
 
 ERRORS = {-1: "RC_EINVAL", -2: "RC_ENOMEM", -3: "RC_EHIP", -4: "RC_ENODEV", -5: "RC_ESIZE",
           -6: "RC_ESTATE", -7: "RC_ECOMM"}
@@ -99,6 +101,15 @@ SIGNATURES = {
     "rcflow_create_output_dev": [_vp, _i, _vp, _sz, _vp, _sz, _i, _i],
     "rcflow_resize_bgr_to_gray_dev": [_vp, _i, _vp, _sz, _i, _i, _vp, _sz, _i, _i],
     "rcflow_resize_area_bgr_to_gray_dev": [_vp, _i, _vp, _sz, _i, _i, _vp, _sz, _i, _i],
+    "rcflow_resize_bgr_dev": [_vp, _i, _vp, _sz, _i, _i, _vp, _sz, _i, _i],
+    "rcflow_timex_open": [_vp, _i, _i, _i, _i, _i],
+    "rcflow_timex_push_dev": [_vp, _i, _vp, _sz, C.POINTER(_vp), C.POINTER(_sz)],
+    "rcflow_timex_reset": [_vp, _i],
+    "rcflow_timex_close": [_vp, _i],
+    "rcflow_timex_info": [_vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_longlong),
+                          C.POINTER(_sz)],
+    "rcflow_rgb_to_hsv_u8_dev": [_vp, _i, _vp, _sz, _i, _i, _vp, _sz],
+    "rcflow_hsv_to_rgb_u8_dev": [_vp, _i, _vp, _sz, _i, _i, _vp, _sz],
     "rcflow_streamline_display_dev": [_vp, _i, _i, _vp, _sz, C.POINTER(_f)],
     "rcflow_streamline_positions_dev": [_vp, _i, _vp, _sz],
     "rcflow_hsv_to_bgr_dev": [_vp, _i, _vp, _sz, _i, _i, _vp, _sz],

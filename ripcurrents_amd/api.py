@@ -11,6 +11,7 @@ Names, argument order and meaning follow the reference (paths relative to
   get_delta                  ripcurrents_module.cpp:650-679  (ripcurrents.hpp:58)
   Streakline                 Streakline.hpp:8-20, Streakline.cpp:11-71
   subtructAverage / subtructMeanMagnitude / stabilizer / vectorToColor / shearRateToColor
+  timex_*                    compute_timex main.cpp:1195-1263, compute_brightColor main.cpp:1265-1383
 
 torch is used for device memory and streams only; all compute is in the HIP library.
 Arrays cross this layer as torch CUDA tensors (zero copy) or numpy arrays (copied).
@@ -21,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import FarnebackParams, HIST_BINS, HIST_DIRECTIONS, HIST_WORDS, RC_FARNEBACK_USE_INITIAL_FLOW, RcflowError, check
+from ._lib import FarnebackParams, HIST_BINS, HIST_DIRECTIONS, HIST_WORDS, RC_FARNEBACK_USE_INITIAL_FLOW, TIMEX_PRODUCTS, RcflowError, check
 
 __all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState"]
 
@@ -632,6 +633,109 @@ class Context:
         fn = self._lib.rcflow_resize_area_bgr_to_gray_dev if interpolation == "area" else self._lib.rcflow_resize_bgr_to_gray_dev
         check(fn(self._h, stream, self._ptr(f), f.stride(0), sw, sh, self._ptr(out), out.stride(0), dw, dh))
         return out
+
+    def resize_bgr(self, frame, dw, dh, stream=0):
+        """resize(frame, Size(dw,dh), 0, 0, INTER_LINEAR) on an 8UC3 frame (main.cpp:1227, :1302) -> (dh, dw, 3) uint8."""
+        f = self._img3(frame)
+        sh, sw = f.shape[:2]
+        out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=self.device)
+        self._bind(stream)
+        check(self._lib.rcflow_resize_bgr_dev(self._h, stream, self._ptr(f), f.stride(0), sw, sh, self._ptr(out),
+                                              out.stride(0), dw, dh))
+        return out
+
+    # ------------------------------------------------------------------ time-exposure images
+    def _img3(self, a):
+        """An (h, w, 3) uint8 device image with dense pixels; rows may have any step (views are taken as they are)."""
+        t = self._dev(a, torch.uint8)
+        if t.dim() != 3 or t.shape[2] != 3:
+            raise ValueError("expected an HxWx3 uint8 image")
+        if t.stride(2) != 1 or t.stride(1) != 3 or t.stride(0) < 3 * t.shape[1]:
+            t = t.contiguous()
+        return t
+
+    def _check_out3(self, t, shape, what):
+        """A caller's output image: uint8 on this device, of `shape`, dense pixels (rows may have any step)."""
+        if not _is_t(t) or not t.is_cuda or t.device != self.device or t.dtype != torch.uint8 or tuple(t.shape) != tuple(shape) \
+                or t.stride(2) != 1 or t.stride(1) != 3 or t.stride(0) < 3 * shape[1]:
+            raise ValueError("%s must be a uint8 device image of shape %s with dense pixels" % (what, tuple(shape)))
+        return t
+
+    def _cvt_u8(self, fn, img, out, stream):
+        a = self._img3(img)
+        h, w = a.shape[:2]
+        if out is None:
+            out = torch.empty((h, w, 3), dtype=torch.uint8, device=self.device)
+        else:
+            self._check_out3(out, a.shape, "out")
+        self._bind(stream)
+        check(fn(self._h, stream, self._ptr(a), a.stride(0), w, h, self._ptr(out), out.stride(0)))
+        return out
+
+    def rgb_to_hsv_u8(self, img, out=None, stream=0):
+        """cvtColor(img, COLOR_RGB2HSV) on 8UC3 (main.cpp:1308): byte 0 of `img` plays R; H in 0..179.
+        `out` (optional): the image to write, `img` itself for in place."""
+        return self._cvt_u8(self._lib.rcflow_rgb_to_hsv_u8_dev, img, out, stream)
+
+    def hsv_to_rgb_u8(self, img, out=None, stream=0):
+        """cvtColor(img, COLOR_HSV2RGB) on 8UC3 (main.cpp:1361)."""
+        return self._cvt_u8(self._lib.rcflow_hsv_to_rgb_u8_dev, img, out, stream)
+
+    def timex_open(self, w, h, window=50, products=("mean",), stream=0):
+        """Opens the slot's time-exposure state: products out of "mean" (compute_timex, main.cpp:1195-1263), "average",
+        "bright", "dark" (compute_brightColor options 0, 1, 2, main.cpp:1265-1383, over a ring of `window` frames)."""
+        mask = 0
+        for name in products:
+            if name not in TIMEX_PRODUCTS:
+                raise ValueError("unknown time-exposure product %r" % (name,))
+            mask |= TIMEX_PRODUCTS[name]
+        self._bind(stream)          # the state is zeroed on the slot's stream: the one the pushes will run on
+        check(self._lib.rcflow_timex_open(self._h, stream, int(w), int(h), int(window), mask))
+
+    def timex_info(self, stream=0):
+        """dict(w, h, window, products (names, in output order), frames_pushed, device_bytes) of the open state."""
+        w, h, win, prod = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        frames, nbytes = C.c_longlong(0), C.c_size_t(0)
+        check(self._lib.rcflow_timex_info(self._h, stream, C.byref(w), C.byref(h), C.byref(win), C.byref(prod),
+                                          C.byref(frames), C.byref(nbytes)))
+        return dict(w=w.value, h=h.value, window=win.value,
+                    products=tuple(n for n, bit in TIMEX_PRODUCTS.items() if prod.value & bit),
+                    frames_pushed=frames.value, device_bytes=nbytes.value)
+
+    def timex_push(self, frame, out=None, stream=0):
+        """One frame (HxWx3 uint8) into the slot's time-exposure state -> {product name: (h, w, 3) uint8 device image}
+        for every open product, as the reference shows after this frame.  `out` (optional) maps product names to
+        preallocated images to write into, or to None to update that product's state without producing its image."""
+        info = self.timex_info(stream)
+        f = self._img3(frame)
+        if tuple(f.shape[:2]) != (info["h"], info["w"]):
+            raise ValueError("frame must be %dx%dx3, as opened" % (info["h"], info["w"]))
+        out = dict(out or {})
+        res = {}
+        ptrs, steps = (C.c_void_p * 4)(), (C.c_size_t * 4)()
+        for k, name in enumerate(TIMEX_PRODUCTS):
+            if name in out:
+                t = out[name]
+                if t is None:
+                    continue
+                self._check_out3(t, f.shape, "out[%r]" % name)
+            elif name in info["products"]:
+                t = torch.empty(tuple(f.shape), dtype=torch.uint8, device=self.device)
+            else:
+                continue
+            res[name] = t
+            ptrs[k], steps[k] = t.data_ptr(), t.stride(0)
+        self._bind(stream)
+        check(self._lib.rcflow_timex_push_dev(self._h, stream, self._ptr(f), f.stride(0), ptrs, steps))
+        return res
+
+    def timex_reset(self, stream=0):
+        self._bind(stream)
+        check(self._lib.rcflow_timex_reset(self._h, stream))
+
+    def timex_close(self, stream=0):
+        self._bind(stream)          # waits for the pushes queued on that stream before freeing
+        check(self._lib.rcflow_timex_close(self._h, stream))
 
     def _an_size(self, stream):
         w, h = C.c_int(0), C.c_int(0)

@@ -702,12 +702,9 @@ __global__ __launch_bounds__(RC_BLOCK) void k_create_edges(const uint8_t* mask, 
 
 // Frame pre-processing (ripcurrents.cpp:209-210): resize(8UC3, INTER_LINEAR) with resize.cpp's
 // 11-bit fixed-point coefficients, then cvtColor(BGR2GRAY) with its 14-bit ones; one thread
-// per output pixel, integer arithmetic throughout (bit-exact).
-__global__ __launch_bounds__(RC_BLOCK) void k_resize_bgr_to_gray(const uint8_t* bgr, size_t step, int sw, int sh,
-                                                                 uint8_t* gray, size_t gray_step, int dw, int dh,
-                                                                 double scale_x, double scale_y) {
-    const int dx = blockIdx.x * 64 + (threadIdx.x & 63), dy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (dx >= dw || dy >= dh) return;
+// per output pixel, integer arithmetic throughout (bit-exact).  rc_resize_bgr_px: the resized 8UC3 pixel.
+__device__ __forceinline__ void rc_resize_bgr_px(const uint8_t* bgr, size_t step, int sw, int sh, int dx, int dy,
+                                                 double scale_x, double scale_y, int px[3]) {
     float fx = (float)((dx + 0.5) * scale_x - 0.5);
     int sx = (int)floorf(fx);
     fx -= sx;
@@ -722,7 +719,6 @@ __global__ __launch_bounds__(RC_BLOCK) void k_resize_bgr_to_gray(const uint8_t* 
     const int b0 = __float2int_rn((1.f - fy) * 2048.f), b1 = __float2int_rn(fy * 2048.f);
     const uint8_t* S0 = bgr + (size_t)sy0 * step;
     const uint8_t* S1 = bgr + (size_t)sy1 * step;
-    int px[3];
 #pragma unroll
     for (int c = 0; c < 3; c++) {
         int h0 = S0[sx * 3 + c] * a0 + S0[sx1 * 3 + c] * a1;
@@ -730,7 +726,27 @@ __global__ __launch_bounds__(RC_BLOCK) void k_resize_bgr_to_gray(const uint8_t* 
         int v = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
         px[c] = min(max(v, 0), 255);
     }
+}
+
+__global__ __launch_bounds__(RC_BLOCK) void k_resize_bgr_to_gray(const uint8_t* bgr, size_t step, int sw, int sh,
+                                                                 uint8_t* gray, size_t gray_step, int dw, int dh,
+                                                                 double scale_x, double scale_y) {
+    const int dx = blockIdx.x * 64 + (threadIdx.x & 63), dy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (dx >= dw || dy >= dh) return;
+    int px[3];
+    rc_resize_bgr_px(bgr, step, sw, sh, dx, dy, scale_x, scale_y, px);
     gray[(size_t)dy * gray_step + dx] = (uint8_t)((px[0] * 1868 + px[1] * 9617 + px[2] * 4899 + (1 << 13)) >> 14);
+}
+
+// The resize alone (main.cpp:1227, :1302: the colour frame of the time-exposure pipelines): 8UC3 out
+__global__ __launch_bounds__(RC_BLOCK) void k_resize_bgr(const uint8_t* bgr, size_t step, int sw, int sh, uint8_t* out,
+                                                         size_t out_step, int dw, int dh, double scale_x, double scale_y) {
+    const int dx = blockIdx.x * 64 + (threadIdx.x & 63), dy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (dx >= dw || dy >= dh) return;
+    int px[3];
+    rc_resize_bgr_px(bgr, step, sw, sh, dx, dy, scale_x, scale_y, px);
+    uint8_t* o = out + (size_t)dy * out_step + 3 * dx;
+    o[0] = (uint8_t)px[0]; o[1] = (uint8_t)px[1]; o[2] = (uint8_t)px[2];
 }
 
 // ============================================================================ host side
@@ -1198,6 +1214,25 @@ extern "C" int rcflow_resize_bgr_to_gray_dev(rc_ctx* ctx, int stream, const uint
         RcProfScope ps(ctx, s->cur, RC_K_PREPROC, 0, 3. * sw * sh + 1. * dw * dh);
         hipLaunchKernelGGL(k_resize_bgr_to_gray, dim3((dw + 63) / 64, (dh + 3) / 4), dim3(RC_BLOCK), 0, s->cur, d_bgr, step,
                            sw, sh, d_gray, gray_step, dw, dh, scale_x, scale_y);
+    }
+    RC_HIP(hipGetLastError());
+    return RC_OK;
+}
+
+extern "C" int rcflow_resize_bgr_dev(rc_ctx* ctx, int stream, const uint8_t* d_bgr, size_t step, int sw, int sh,
+                                     uint8_t* d_out, size_t out_step, int dw, int dh) {
+    RcSlot* s = rc_slot(ctx, stream);
+    if (!s) return RC_EINVAL;
+    if (!d_bgr || !d_out || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || step < (size_t)sw * 3 || out_step < (size_t)dw * 3) {
+        rc_set_error("bad frame arguments");
+        return RC_EINVAL;
+    }
+    RC_HIP(hipSetDevice(ctx->device));
+    double scale_x = 1. / ((double)dw / sw), scale_y = 1. / ((double)dh / sh);
+    {
+        RcProfScope ps(ctx, s->cur, RC_K_COLOR_U8, 2, 3. * sw * sh + 3. * dw * dh);
+        hipLaunchKernelGGL(k_resize_bgr, dim3((dw + 63) / 64, (dh + 3) / 4), dim3(RC_BLOCK), 0, s->cur, d_bgr, step,
+                           sw, sh, d_out, out_step, dw, dh, scale_x, scale_y);
     }
     RC_HIP(hipGetLastError());
     return RC_OK;

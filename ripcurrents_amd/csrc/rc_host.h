@@ -41,6 +41,26 @@ struct RcAnalysis {
     RcBuf loopc;       // one int32: framecount of rcflow_frame_loop_step (incremented on the device)
 };
 
+// Time-exposure state of one stream slot (timex_kernels.hip; main.cpp:1195-1383).  Everything is allocated by
+// rcflow_timex_open and released by rcflow_timex_close / rcflow_destroy.
+struct RcTimex {
+    bool open = false;
+    int w = 0, h = 0, window = 0, products = 0;   // window = 0: MEAN alone, no ring
+    int pitch = 0;            // row pitch of the state planes in pixels (w rounded up to 4)
+    size_t plane = 0;         // pixels per state plane
+    int cur = 0;              // ring slot the next frame goes to (currentBuffer, main.cpp:1290)
+    long long frames = 0;     // frames pushed since open / reset (framecount, main.cpp:1219)
+    RcBuf sum;                // MEAN: [h][pitch][3] fp32 (sum_rgb, main.cpp:1216)
+    RcBuf ring;               // [window][H, S, V][plane] bytes (buffer_hsv, main.cpp:1292-1295)
+    RcBuf avg;                // AVERAGE: [H, S, V][plane] uint16 sums of the slots' quotients
+    RcBuf bd_idx[2], bd_hsv[2];   // BRIGHT, DARK: the winner's slot (uint16) and output triple (uint32) per pixel
+    // open / reset zero the state asynchronously on the stream the slot had then; the first push after it waits for
+    // this event when the slot has been moved to another stream in between
+    hipEvent_t zeroed = nullptr;
+    hipStream_t zero_stream = nullptr;
+    bool zero_pending = false;
+};
+
 struct RcBatchKey {
     const void* frames; size_t frame_stride, step;
     void* flows; size_t flow_frame_stride, flow_step;
@@ -91,6 +111,7 @@ struct RcSlot {
     unsigned char loop_key[2][160] = {};
     int loop_fc = 0;
     RcAnalysis an;
+    RcTimex tx;
 };
 
 struct RcProfRec {
@@ -130,7 +151,8 @@ struct rc_ctx {
 enum { RC_K_PYR = 0, RC_K_POLY = 1, RC_K_ITER = 2, RC_K_HIST = 3, RC_K_THRESH = 4, RC_K_CLASSIFY = 5,
        RC_K_ADVECT_FIELD = 6, RC_K_ADVECT_POINTS = 7, RC_K_POSTOP = 8, RC_K_COLOR = 9, RC_K_ITER2 = 10,
        RC_K_PREPROC = 11, RC_K_EDGES = 12, RC_K_DISPLAY = 13, RC_K_HSV2BGR = 14, RC_K_OVERLAY = 15, RC_K_FLOW_SEED = 16,
-       RC_K_KINDS = 17 };
+       RC_K_TIMEX = 17 /* @0 mean, @1 ring products */, RC_K_COLOR_U8 = 18 /* @0 rgb_to_hsv, @1 hsv_to_rgb, @2 resize_bgr */,
+       RC_K_KINDS = 19 };
 
 void rc_set_error(const char* fmt, ...);
 int rc_buf_ensure(RcBuf& b, size_t bytes);
@@ -147,6 +169,8 @@ int rc_hist_book(RcSlot& s, int w, int h, bool commit);
 int rc_analysis_ensure(rc_ctx* ctx, RcSlot& s, int w, int h);
 // computeResizeAreaTab (resize.cpp) grouped by destination index (analysis_kernels.hip)
 void rc_area_tab(int ssize, int dsize, double scale, std::vector<int>& start, std::vector<int>& si, std::vector<float>& alpha);
+// timex_kernels.hip
+void rc_timex_free(RcSlot& s);
 // initial_flow_kernels.hip
 int rc_flow_area_prepare(RcBuf& tab, int W, int H, int w, int h, RcFlowAreaArgs& a);
 
