@@ -342,6 +342,66 @@ int rcflow_resize_area_bgr_to_gray_dev(rc_ctx* ctx, int stream, const uint8_t* d
 int rcflow_resize_bgr_dev(rc_ctx* ctx, int stream, const uint8_t* d_bgr, size_t step, int sw, int sh,
                           uint8_t* d_out, size_t out_step, int dw, int dh);
 
+/* The INTER_AREA resize alone, 8UC3 out: resize(frame, frame, Size(dw,dh), 0, 0, INTER_AREA) as compute_phaseCorrelate
+ * calls it on every frame (main.cpp:1707, :1723).  Same arithmetic and the same refusals as
+ * rcflow_resize_area_bgr_to_gray_dev (shrinking only).  Recorded as "frame_color@3". */
+int rcflow_resize_area_bgr_dev(rc_ctx* ctx, int stream, const uint8_t* d_bgr, size_t step, int sw, int sh,
+                               uint8_t* d_out, size_t out_step, int dw, int dh);
+
+/* ------------------------------------------------------------------ frame stabilisation
+ * compute_phaseCorrelate (main.cpp:1684-1775) on frames resident on the device: every frame is registered to the last
+ * CORRECTED frame on a patch that does not move (the reference: 50 x 50 at (XDIM - 50, 50)) by
+ * cv::phaseCorrelate(prev_patch, curr_patch, hann) and translated back by cv::warpAffine, before any flow is taken
+ * from it.  (rcflow_stabilizer_dev above is a different thing: it corrects a flow field after the fact.)
+ * The OpenCV functions are restated from upstream 4.1.0 (phasecorr.cpp, imgwarp.cpp), parity-unpinned:
+ *   patches zero-padded to getOptimalDFTSize (2^a 3^b 5^c) N x M, multiplied by createHanningWindow of the unpadded
+ *   size (the square root of the product of the raised cosines), P = F(a) conj F(b), C = P |P| / (|P|^2 + FLT_EPSILON),
+ *   unscaled inverse DFT, fftShift, first maximum in row-major order, 5 x 5 centroid in double clipped to the surface
+ *   (values as they are), response = sum of the box / (M N), shift = (N / 2.0, M / 2.0) - centroid: b(x) = a(x - d)
+ *   gives +d.  fftShift sends index i to (i + floor(n / 2)) mod n while the centre stays n / 2.0, so an odd optimal
+ *   size reports a constant +0.5 px on that axis; reproduced.
+ *   warpAffine(src, [1 0 -sx; 0 1 -sy]) is dst(x, y) = src(x + sx, y + sy), INTER_LINEAR in 8-bit fixed point
+ *   (X0 = cvRound(sx * 1024) + 16, Y0 = cvRound((y + sy) * 1024) + 16 per row, fractions of 1/32 px, weights of 2^15,
+ *   out = (sum + 2^14) >> 15), BORDER_CONSTANT 0 tap by tap; at fraction (0, 0) the source pixel itself.
+ * The DFTs are direct sums in fp32 against twiddle tables made on the host in double (no rocFFT / hipFFT).
+ * When profiling is on: "framestab@0" the correlation as one workgroup (patch in LDS; optimal sizes up to about
+ * 100 x 100), "framestab@1" the warp, "framestab@2..6" the correlation's passes as launches of their own for larger
+ * patches; rcflow_profile_read_buckets books them under "farneback" with the resize stages. */
+/* Stage: phaseCorrelate of two 32FC1 patches on the device, w, h in 8..256 with optimal DFT sizes up to 256 x 256
+ * (RC_EINVAL / RC_ESIZE otherwise).  d_result: three doubles on the device (shift_x, shift_y, response).
+ * Asynchronous; the tables of the last patch size are cached per slot (a change of size synchronises the slot). */
+int rcflow_phase_correlate_dev(rc_ctx* ctx, int stream, const float* d_a, size_t a_step, const float* d_b, size_t b_step,
+                               int w, int h, int use_hann, double* d_result);
+/* Stage: the reference's warpAffine call for a shift known to the host.  Not in place (RC_EINVAL when d_out overlaps
+ * d_bgr); RC_EINVAL for a shift that is not finite or beyond 2^20 px. */
+int rcflow_warp_translate_bgr_dev(rc_ctx* ctx, int stream, const uint8_t* d_bgr, size_t step, int w, int h,
+                                  uint8_t* d_out, size_t out_step, double shift_x, double shift_y);
+/* Opens the slot's stabilisation state for 8UC3 frames of w x h and the patch (roi_x, roi_y, roi_w, roi_h): inside the
+ * frame, at least 8 x 8 (RC_EINVAL), optimal DFT sizes up to 256 x 256 and the frame within the context's size
+ * (RC_ESIZE).  Builds the window and the twiddle tables on the host in double and allocates everything a push needs;
+ * re-opening replaces the state.  Stream rules as for rcflow_timex_open: the state is zeroed on the stream the slot
+ * has at this call (so does rcflow_framestab_reset) and the first push waits for that. */
+int rcflow_framestab_open(rc_ctx* ctx, int stream, int w, int h, int roi_x, int roi_y, int roi_w, int roi_h);
+/* One frame in, the corrected frame out (both 8UC3 of the opened size).  d_result (device, three doubles, may be
+ * NULL) receives shift_x, shift_y, response.  The first push after open / reset has nothing to register against: it
+ * copies the frame, reports (0, 0, 0) and becomes `prev` (the reference emits nothing for its first frame: the one
+ * stated deviation).  The state keeps the gray patch of the corrected frame itself; d_out is the caller's to overwrite.
+ * No host synchronisation and no device-to-host copy: the warp reads the shift from device memory.  RC_EINVAL for a
+ * step below 3 * w, a null image, or d_out overlapping d_frame; RC_ESTATE before rcflow_framestab_open; a refused
+ * push leaves the state as it was. */
+int rcflow_framestab_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_frame, size_t step, uint8_t* d_out,
+                              size_t out_step, double* d_result);
+/* Blocks until the slot's stream has finished; result = shift_x, shift_y, response of the last push. */
+int rcflow_framestab_read(rc_ctx* ctx, int stream, double result[3], long long* frames_pushed);
+/* the next push is a first push again; keeps the allocation */
+int rcflow_framestab_reset(rc_ctx* ctx, int stream);
+/* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
+int rcflow_framestab_close(rc_ctx* ctx, int stream);
+/* any pointer may be NULL; roi = x, y, w, h; dft_size = N (columns), M (rows); launches_per_push = 2 when the
+ * correlation runs as one workgroup, 6 otherwise.  RC_ESTATE when nothing is open on the slot. */
+int rcflow_framestab_info(rc_ctx* ctx, int stream, int* w, int* h, int roi[4], int dft_size[2], int* launches_per_push,
+                          long long* frames_pushed, size_t* device_bytes);
+
 /* ------------------------------------------------------------------ time-exposure images
  * compute_timex (main.cpp:1195-1263) and compute_brightColor (main.cpp:1265-1383) on frames resident on the device.
  * All images are 8UC3; "channel 0 / 1 / 2" are the bytes as they come (the reference feeds BGR frames to
@@ -356,7 +416,7 @@ int rcflow_resize_bgr_dev(rc_ctx* ctx, int stream, const uint8_t* d_bgr, size_t 
  * Every product is the bits of the reference's rescan of the whole ring, kept incrementally: bytes per frame do not
  * grow with the window, except that a pixel whose BRIGHT / DARK winner is overwritten by a worse sample walks the V
  * plane of the ring again.  When profiling is on the launches are recorded as "timex@0" (mean) and "timex@1" (ring
- * products), the stage kernels below as "frame_color@0..2"; rcflow_profile_read_buckets books them under "overlay". */
+ * products), the stage kernels below as "frame_color@0..1", the colour resizes as "frame_color@2..3"; rcflow_profile_read_buckets books them under "overlay". */
 #define RC_TIMEX_MEAN 1      /* main.cpp:1195-1263 */
 #define RC_TIMEX_AVERAGE 2   /* main.cpp:1265-1383, option 0 */
 #define RC_TIMEX_BRIGHT 4    /* option 1 */
@@ -471,7 +531,7 @@ int rcflow_profile_read(rc_ctx* ctx, int cap, const char** names, int* launches,
 
 /* The same totals under the reference's own bucket names, in the order it prints them (ripcurrents.cpp:103-109,
  * :518-524): farneback, polar, threshold, overlay, erosion, codec, stream ("pathlines").  GPU time of the kernels
- * that do each bucket's work ("overlay" includes the time-exposure images and the 8-bit colour stages); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
+ * that do each bucket's work ("overlay" includes the time-exposure images and the 8-bit colour stages, "farneback" the frame stabilisation); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
  * classification kernels, booked under "threshold"), "codec" is 0 (video decode is host I/O outside the library).
  * names / ms: RC_PROFILE_BUCKETS entries each (either may be NULL).  Returns RC_PROFILE_BUCKETS. */
 #define RC_PROFILE_BUCKETS 7

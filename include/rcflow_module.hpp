@@ -13,6 +13,7 @@
 //   Streakline                 Streakline.hpp:8-20  Streakline.cpp:11-71
 //   Timeline, PopulationMap    ripcurrents.hpp:64-75, 86-95  ripcurrents_module.cpp:751-807, 1140-1196
 //   timexOpen / timexPush      compute_timex main.cpp:1195-1263, compute_brightColor main.cpp:1265-1383
+//   framestabOpen / framestabPush   compute_phaseCorrelate main.cpp:1684-1775
 // rc::Mat is a non-owning view with cv::Mat's fields (data, step, rows, cols); with OpenCV
 // present, include/rcflow_cv.hpp converts cv::Mat to it.  Errors are thrown as
 // rc::Error (the reference's OpenCV calls throw cv::Exception and are never caught).
@@ -328,6 +329,29 @@ class Pipeline {
     }
     void timexReset() { check(rcflow_timex_reset(ctx_, 0)); }
     void timexClose() { check(rcflow_timex_close(ctx_, 0)); }
+
+    // compute_phaseCorrelate (main.cpp:1684-1775) on frames of the pipeline's size: framestabPush takes the resized
+    // 8UC3 frame (main.cpp:1723) and fills `corrected` (8UC3 of the frame size) with what the reference writes to its
+    // output video, registered to the last corrected frame on the patch given at open (default: the reference's
+    // roi, main.cpp:1728-1732).  shift (optional): shift_x, shift_y, response of this frame (main.cpp:1745).
+    void framestabOpen() { framestabOpen(w_ - 50, 50, 50, 50); }
+    void framestabOpen(int roi_x, int roi_y, int roi_w, int roi_h) { check(rcflow_framestab_open(ctx_, 0, w_, h_, roi_x, roi_y, roi_w, roi_h)); }
+    void framestabPush(const Mat& frame, Mat& corrected, double shift[3] = nullptr) {
+        const size_t img = ((size_t)w_ * h_ * 3 + 255) & ~(size_t)255;
+        auto is_8uc3 = [this](const Mat& m) { return !m.empty() && m.rows == h_ && m.cols == w_ && m.channels == 3 && m.elem == 1; };
+        if (!is_8uc3(frame) || !is_8uc3(corrected)) throw Error(RC_EINVAL, "framestabPush: frame and corrected must be 8UC3 of the pipeline's size");
+        uint8_t* b = (uint8_t*)scratch(2 * img);                 // grow-only: the frame and the corrected frame
+        hip_check(hipMemcpy2D(b, (size_t)w_ * 3, frame.data, frame.step, (size_t)w_ * 3, h_, hipMemcpyHostToDevice), "upload frame");
+        int rc = rcflow_framestab_push_dev(ctx_, 0, b, (size_t)w_ * 3, b + img, (size_t)w_ * 3, nullptr);
+        double r[3] = {0., 0., 0.};
+        if (rc == RC_OK) rc = rcflow_framestab_read(ctx_, 0, r, nullptr);      // waits for the push
+        check(rc);
+        hip_check(hipMemcpy2D(corrected.data, corrected.step, b + img, (size_t)w_ * 3, (size_t)w_ * 3, h_, hipMemcpyDeviceToHost),
+                  "download corrected frame");
+        if (shift) { shift[0] = r[0]; shift[1] = r[1]; shift[2] = r[2]; }
+    }
+    void framestabReset() { check(rcflow_framestab_reset(ctx_, 0)); }
+    void framestabClose() { check(rcflow_framestab_close(ctx_, 0)); }
 
     int width() const { return w_; }
     int height() const { return h_; }

@@ -102,6 +102,16 @@ SIGNATURES = {
     "rcflow_resize_bgr_to_gray_dev": [_vp, _i, _vp, _sz, _i, _i, _vp, _sz, _i, _i],
     "rcflow_resize_area_bgr_to_gray_dev": [_vp, _i, _vp, _sz, _i, _i, _vp, _sz, _i, _i],
     "rcflow_resize_bgr_dev": [_vp, _i, _vp, _sz, _i, _i, _vp, _sz, _i, _i],
+    "rcflow_resize_area_bgr_dev": [_vp, _i, _vp, _sz, _i, _i, _vp, _sz, _i, _i],
+    "rcflow_phase_correlate_dev": [_vp, _i, _vp, _sz, _vp, _sz, _i, _i, _i, _vp],
+    "rcflow_warp_translate_bgr_dev": [_vp, _i, _vp, _sz, _i, _i, _vp, _sz, _d, _d],
+    "rcflow_framestab_open": [_vp, _i, _i, _i, _i, _i, _i, _i],
+    "rcflow_framestab_push_dev": [_vp, _i, _vp, _sz, _vp, _sz, _vp],
+    "rcflow_framestab_read": [_vp, _i, C.POINTER(_d), C.POINTER(C.c_longlong)],
+    "rcflow_framestab_reset": [_vp, _i],
+    "rcflow_framestab_close": [_vp, _i],
+    "rcflow_framestab_info": [_vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
+                              C.POINTER(C.c_longlong), C.POINTER(_sz)],
     "rcflow_timex_open": [_vp, _i, _i, _i, _i, _i],
     "rcflow_timex_push_dev": [_vp, _i, _vp, _sz, C.POINTER(_vp), C.POINTER(_sz)],
     "rcflow_timex_reset": [_vp, _i],

@@ -12,6 +12,7 @@ Names, argument order and meaning follow the reference (paths relative to
   Streakline                 Streakline.hpp:8-20, Streakline.cpp:11-71
   subtructAverage / subtructMeanMagnitude / stabilizer / vectorToColor / shearRateToColor
   timex_*                    compute_timex main.cpp:1195-1263, compute_brightColor main.cpp:1265-1383
+  framestab_*                compute_phaseCorrelate main.cpp:1684-1775 (phase_correlate, warp_translate: its stages)
 
 torch is used for device memory and streams only; all compute is in the HIP library.
 Arrays cross this layer as torch CUDA tensors (zero copy) or numpy arrays (copied).
@@ -634,14 +635,17 @@ class Context:
         check(fn(self._h, stream, self._ptr(f), f.stride(0), sw, sh, self._ptr(out), out.stride(0), dw, dh))
         return out
 
-    def resize_bgr(self, frame, dw, dh, stream=0):
-        """resize(frame, Size(dw,dh), 0, 0, INTER_LINEAR) on an 8UC3 frame (main.cpp:1227, :1302) -> (dh, dw, 3) uint8."""
+    def resize_bgr(self, frame, dw, dh, stream=0, interpolation="linear"):
+        """resize(frame, Size(dw,dh), 0, 0, INTER_LINEAR) on an 8UC3 frame (main.cpp:1227, :1302) -> (dh, dw, 3) uint8;
+        interpolation="area": INTER_AREA, as compute_phaseCorrelate resizes every frame (main.cpp:1707, :1723)."""
+        if interpolation not in ("linear", "area"):
+            raise ValueError("interpolation must be \"linear\" or \"area\"")
         f = self._img3(frame)
         sh, sw = f.shape[:2]
         out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=self.device)
         self._bind(stream)
-        check(self._lib.rcflow_resize_bgr_dev(self._h, stream, self._ptr(f), f.stride(0), sw, sh, self._ptr(out),
-                                              out.stride(0), dw, dh))
+        fn = self._lib.rcflow_resize_area_bgr_dev if interpolation == "area" else self._lib.rcflow_resize_bgr_dev
+        check(fn(self._h, stream, self._ptr(f), f.stride(0), sw, sh, self._ptr(out), out.stride(0), dw, dh))
         return out
 
     # ------------------------------------------------------------------ time-exposure images
@@ -736,6 +740,94 @@ class Context:
     def timex_close(self, stream=0):
         self._bind(stream)          # waits for the pushes queued on that stream before freeing
         check(self._lib.rcflow_timex_close(self._h, stream))
+
+    # ------------------------------------------------------------------ frame stabilisation
+    def phase_correlate(self, a, b, window=True, out=None, stream=0):
+        """cv::phaseCorrelate(a, b, hann) of two float32 patches (main.cpp:1745; `window=False`: without the Hann
+        window) -> device tensor of 3 float64: shift_x, shift_y, response.  b(x) = a(x - d) gives shift +d.
+        `out` (optional): a float64 device tensor of 3 to write.  Asynchronous: read the result after a sync."""
+        ta, tb = self._dev(a, torch.float32), self._dev(b, torch.float32)
+        if ta.dim() != 2 or ta.shape != tb.shape:
+            raise ValueError("expected two 2-D float32 patches of one size")
+        ta = ta if ta.stride(1) == 1 else ta.contiguous()
+        tb = tb if tb.stride(1) == 1 else tb.contiguous()
+        h, w = ta.shape
+        if out is None:
+            out = torch.empty(3, dtype=torch.float64, device=self.device)
+        elif not _is_t(out) or not out.is_cuda or out.dtype != torch.float64 or out.numel() != 3 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float64 device tensor of 3")
+        self._bind(stream)
+        check(self._lib.rcflow_phase_correlate_dev(self._h, stream, self._ptr(ta), ta.stride(0) * 4, self._ptr(tb),
+                                                   tb.stride(0) * 4, w, h, 1 if window else 0, self._ptr(out)))
+        return out
+
+    def warp_translate(self, frame, shift_x, shift_y, out=None, stream=0):
+        """warpAffine(frame, [1 0 -shift_x; 0 1 -shift_y]) on an 8UC3 frame (main.cpp:1749-1751): out(x, y) =
+        frame(x + shift_x, y + shift_y), bilinear in 1/32 px, zero outside.  `out` (optional): the image to write."""
+        f = self._img3(frame)
+        if out is None:
+            out = torch.empty(tuple(f.shape), dtype=torch.uint8, device=self.device)
+        else:
+            self._check_out3(out, f.shape, "out")
+        self._bind(stream)
+        check(self._lib.rcflow_warp_translate_bgr_dev(self._h, stream, self._ptr(f), f.stride(0), f.shape[1], f.shape[0],
+                                                      self._ptr(out), out.stride(0), float(shift_x), float(shift_y)))
+        return out
+
+    def framestab_open(self, w, h, roi=None, stream=0):
+        """Opens the slot's stabilisation state (compute_phaseCorrelate, main.cpp:1684-1775) for w x h frames.
+        roi = (x, y, w, h) of the static patch to track; default: the reference's (w - 50, 50, 50, 50)."""
+        x, y, rw, rh = (int(w) - 50, 50, 50, 50) if roi is None else (int(v) for v in roi)
+        self._bind(stream)          # the state is zeroed on the slot's stream: the one the pushes will run on
+        check(self._lib.rcflow_framestab_open(self._h, stream, int(w), int(h), x, y, rw, rh))
+
+    def framestab_info(self, stream=0):
+        """dict(w, h, roi, dft_size (N, M), launches_per_push, frames_pushed, device_bytes) of the open state."""
+        w, h, lp = C.c_int(0), C.c_int(0), C.c_int(0)
+        roi, dft = (C.c_int * 4)(), (C.c_int * 2)()
+        frames, nbytes = C.c_longlong(0), C.c_size_t(0)
+        check(self._lib.rcflow_framestab_info(self._h, stream, C.byref(w), C.byref(h), roi, dft, C.byref(lp),
+                                              C.byref(frames), C.byref(nbytes)))
+        return dict(w=w.value, h=h.value, roi=tuple(roi), dft_size=tuple(dft), launches_per_push=lp.value,
+                    frames_pushed=frames.value, device_bytes=nbytes.value)
+
+    def framestab_push(self, frame, out=None, result=None, stream=0):
+        """One frame (HxWx3 uint8) -> the corrected frame (device image; `out`: a preallocated one to write).
+        `result` (optional): a contiguous float64 device tensor of 3 that receives shift_x, shift_y, response of this
+        push; nothing is synchronised, so a row of a larger tensor per push collects a whole clip's track."""
+        info = self.framestab_info(stream)
+        f = self._img3(frame)
+        if tuple(f.shape[:2]) != (info["h"], info["w"]):
+            raise ValueError("frame must be %dx%dx3, as opened" % (info["h"], info["w"]))
+        if out is None:
+            out = torch.empty(tuple(f.shape), dtype=torch.uint8, device=self.device)
+        else:
+            self._check_out3(out, f.shape, "out")
+        rp = C.c_void_p(None)
+        if result is not None:
+            if not _is_t(result) or not result.is_cuda or result.dtype != torch.float64 or result.numel() != 3 \
+                    or not result.is_contiguous():
+                raise ValueError("result must be a contiguous float64 device tensor of 3")
+            rp = self._ptr(result)
+        self._bind(stream)
+        check(self._lib.rcflow_framestab_push_dev(self._h, stream, self._ptr(f), f.stride(0), self._ptr(out), out.stride(0), rp))
+        return out
+
+    def framestab_read(self, stream=0):
+        """Waits for the slot's stream -> ((shift_x, shift_y, response) of the last push, frames pushed)."""
+        r = (C.c_double * 3)()
+        n = C.c_longlong(0)
+        self._bind(stream)
+        check(self._lib.rcflow_framestab_read(self._h, stream, r, C.byref(n)))
+        return (r[0], r[1], r[2]), n.value
+
+    def framestab_reset(self, stream=0):
+        self._bind(stream)
+        check(self._lib.rcflow_framestab_reset(self._h, stream))
+
+    def framestab_close(self, stream=0):
+        self._bind(stream)          # waits for the pushes queued on that stream before freeing
+        check(self._lib.rcflow_framestab_close(self._h, stream))
 
     def _an_size(self, stream):
         w, h = C.c_int(0), C.c_int(0)

@@ -1465,10 +1465,8 @@ struct RcAreaArgs {
     uint8_t* gray; size_t gray_step;
 };
 
-__global__ __launch_bounds__(RC_BLOCK) void k_resize_area_bgr_to_gray(RcAreaArgs a) {
-    const int dx = blockIdx.x * 64 + (threadIdx.x & 63), dy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (dx >= a.dw || dy >= a.dh) return;
-    int px[3];
+// rc_resize_area_px: the resized 8UC3 pixel
+__device__ __forceinline__ void rc_resize_area_px(const RcAreaArgs& a, int dx, int dy, int px[3]) {
     if (a.fast) {
         int sum[3] = {0, 0, 0};
         for (int ky = 0; ky < a.iscale_y; ky++) {
@@ -1502,7 +1500,24 @@ __global__ __launch_bounds__(RC_BLOCK) void k_resize_area_bgr_to_gray(RcAreaArgs
             px[c] = v < 0 ? 0 : (v > 255 ? 255 : v);
         }
     }
+}
+
+__global__ __launch_bounds__(RC_BLOCK) void k_resize_area_bgr_to_gray(RcAreaArgs a) {
+    const int dx = blockIdx.x * 64 + (threadIdx.x & 63), dy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (dx >= a.dw || dy >= a.dh) return;
+    int px[3];
+    rc_resize_area_px(a, dx, dy, px);
     a.gray[(size_t)dy * a.gray_step + dx] = (uint8_t)((px[0] * 1868 + px[1] * 9617 + px[2] * 4899 + (1 << 13)) >> 14);
+}
+
+// The resize alone (main.cpp:1707, :1723: the colour frame of compute_phaseCorrelate): 8UC3 out, through a.gray / a.gray_step
+__global__ __launch_bounds__(RC_BLOCK) void k_resize_area_bgr(RcAreaArgs a) {
+    const int dx = blockIdx.x * 64 + (threadIdx.x & 63), dy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (dx >= a.dw || dy >= a.dh) return;
+    int px[3];
+    rc_resize_area_px(a, dx, dy, px);
+    uint8_t* o = a.gray + (size_t)dy * a.gray_step + 3 * dx;
+    o[0] = (uint8_t)px[0]; o[1] = (uint8_t)px[1]; o[2] = (uint8_t)px[2];
 }
 
 // computeResizeAreaTab (resize.cpp), grouped by destination index
@@ -1523,11 +1538,12 @@ void rc_area_tab(int ssize, int dsize, double scale, std::vector<int>& start, st
     start[dsize] = (int)si.size();
 }
 
-extern "C" int rcflow_resize_area_bgr_to_gray_dev(rc_ctx* ctx, int stream, const uint8_t* d_bgr, size_t step, int sw,
-                                                  int sh, uint8_t* d_gray, size_t gray_step, int dw, int dh) {
+// out_ch = 1: gray (rcflow_resize_area_bgr_to_gray_dev); 3: the resized colour frame (rcflow_resize_area_bgr_dev)
+static int resize_area_run(rc_ctx* ctx, int stream, const uint8_t* d_bgr, size_t step, int sw, int sh, uint8_t* d_gray,
+                           size_t gray_step, int dw, int dh, int out_ch) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    if (!d_bgr || !d_gray || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || step < (size_t)sw * 3 || gray_step < (size_t)dw) {
+    if (!d_bgr || !d_gray || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || step < (size_t)sw * 3 || gray_step < (size_t)dw * out_ch) {
         rc_set_error("bad frame arguments");
         return RC_EINVAL;
     }
@@ -1563,12 +1579,24 @@ extern "C" int rcflow_resize_area_bgr_to_gray_dev(rc_ctx* ctx, int stream, const
         RC_HIP(hipMemcpy(d_ya, ya.data(), 4 * ny, hipMemcpyHostToDevice));
         a.xstart = d_xs; a.xsi = d_xi; a.xalpha = d_xa; a.ystart = d_ys; a.ysi = d_yi; a.yalpha = d_ya;
     }
-    {
+    if (out_ch == 1) {
         RcProfScope ps(ctx, s->cur, RC_K_PREPROC, 0, 3. * sw * sh + 1. * dw * dh);
         hipLaunchKernelGGL(k_resize_area_bgr_to_gray, dim3((dw + 63) / 64, (dh + 3) / 4), dim3(RC_BLOCK), 0, s->cur, a);
+    } else {
+        RcProfScope ps(ctx, s->cur, RC_K_COLOR_U8, 3, 3. * sw * sh + 3. * dw * dh);
+        hipLaunchKernelGGL(k_resize_area_bgr, dim3((dw + 63) / 64, (dh + 3) / 4), dim3(RC_BLOCK), 0, s->cur, a);
     }
     RC_HIP(hipGetLastError());
     return RC_OK;
+}
+
+extern "C" int rcflow_resize_area_bgr_to_gray_dev(rc_ctx* ctx, int stream, const uint8_t* d_bgr, size_t step, int sw,
+                                                  int sh, uint8_t* d_gray, size_t gray_step, int dw, int dh) {
+    return resize_area_run(ctx, stream, d_bgr, step, sw, sh, d_gray, gray_step, dw, dh, 1);
+}
+extern "C" int rcflow_resize_area_bgr_dev(rc_ctx* ctx, int stream, const uint8_t* d_bgr, size_t step, int sw, int sh,
+                                          uint8_t* d_out, size_t out_step, int dw, int dh) {
+    return resize_area_run(ctx, stream, d_bgr, step, sw, sh, d_out, out_step, dw, dh, 3);
 }
 
 // create_output(subframe, outmask) ripcurrents_module.cpp:225-244 (ripcurrents.cpp:487-505): the frame the

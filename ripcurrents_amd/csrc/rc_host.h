@@ -61,6 +61,31 @@ struct RcTimex {
     bool zero_pending = false;
 };
 
+// Frame stabilisation state of one stream slot (stab_kernels.hip; main.cpp:1684-1775).  Everything is allocated by
+// rcflow_framestab_open and released by rcflow_framestab_close / rcflow_destroy.
+struct RcFrameStab {
+    bool open = false;
+    int w = 0, h = 0;               // frame size
+    int rx = 0, ry = 0, rw = 0, rh = 0;   // the tracked patch (roi, main.cpp:1728-1732)
+    int N = 0, M = 0;               // optimal DFT sizes of the patch columns, rows
+    size_t lds = 0;                 // LDS bytes of the one-workgroup correlate; 0: a launch per pass over `scratch`
+    long long frames = 0;           // frames pushed since open / reset
+    RcBuf tab;                      // Hann window [rh][rw] | twiddles of N | twiddles of M (float)
+    RcBuf prev;                     // [rh][rw] float: gray ROI of the last CORRECTED frame (prev, main.cpp:1759)
+    RcBuf res;                      // 3 doubles: shift_x, shift_y, response of the last push
+    RcBuf scratch;                  // spectra of the launch-per-pass form
+    // zeroed asynchronously by open / reset on the stream the slot had then, as RcTimex
+    hipEvent_t zeroed = nullptr;
+    hipStream_t zero_stream = nullptr;
+    bool zero_pending = false;
+};
+
+// rcflow_phase_correlate_dev: the tables (and spectra scratch) of the last patch size, cached per slot
+struct RcPhaseCorr {
+    int w = 0, h = 0;
+    RcBuf tab, scratch;
+};
+
 struct RcBatchKey {
     const void* frames; size_t frame_stride, step;
     void* flows; size_t flow_frame_stride, flow_step;
@@ -112,6 +137,8 @@ struct RcSlot {
     int loop_fc = 0;
     RcAnalysis an;
     RcTimex tx;
+    RcFrameStab fs;
+    RcPhaseCorr pc;
 };
 
 struct RcProfRec {
@@ -151,8 +178,9 @@ struct rc_ctx {
 enum { RC_K_PYR = 0, RC_K_POLY = 1, RC_K_ITER = 2, RC_K_HIST = 3, RC_K_THRESH = 4, RC_K_CLASSIFY = 5,
        RC_K_ADVECT_FIELD = 6, RC_K_ADVECT_POINTS = 7, RC_K_POSTOP = 8, RC_K_COLOR = 9, RC_K_ITER2 = 10,
        RC_K_PREPROC = 11, RC_K_EDGES = 12, RC_K_DISPLAY = 13, RC_K_HSV2BGR = 14, RC_K_OVERLAY = 15, RC_K_FLOW_SEED = 16,
-       RC_K_TIMEX = 17 /* @0 mean, @1 ring products */, RC_K_COLOR_U8 = 18 /* @0 rgb_to_hsv, @1 hsv_to_rgb, @2 resize_bgr */,
-       RC_K_KINDS = 19 };
+       RC_K_TIMEX = 17 /* @0 mean, @1 ring products */, RC_K_COLOR_U8 = 18 /* @0 rgb_to_hsv, @1 hsv_to_rgb, @2 resize_bgr, @3 resize_area_bgr */,
+       RC_K_FRAMESTAB = 19 /* @0 correlate in one workgroup, @1 warp, @2..6 the correlate passes as launches of their own */,
+       RC_K_KINDS = 20 };
 
 void rc_set_error(const char* fmt, ...);
 int rc_buf_ensure(RcBuf& b, size_t bytes);
@@ -171,6 +199,8 @@ int rc_analysis_ensure(rc_ctx* ctx, RcSlot& s, int w, int h);
 void rc_area_tab(int ssize, int dsize, double scale, std::vector<int>& start, std::vector<int>& si, std::vector<float>& alpha);
 // timex_kernels.hip
 void rc_timex_free(RcSlot& s);
+// stab_kernels.hip
+void rc_framestab_free(RcSlot& s);
 // initial_flow_kernels.hip
 int rc_flow_area_prepare(RcBuf& tab, int W, int H, int w, int h, RcFlowAreaArgs& a);
 

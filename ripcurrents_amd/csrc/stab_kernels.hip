@@ -1,0 +1,642 @@
+// stab_kernels.hip -- frame stabilisation on the device: the reference's compute_phaseCorrelate (main.cpp:1684-1775).
+// Per frame: phaseCorrelate(prev_roi, curr_roi, hann) on a patch of beach that does not move, then
+// warpAffine(curr, [1 0 -shift.x; 0 1 -shift.y]) and the corrected frame becomes `prev`.  phaseCorrelate,
+// createHanningWindow, getOptimalDFTSize and warpAffine are OpenCV's (4.1.0 phasecorr.cpp, imgwarp.cpp), restated
+// here from knowledge of upstream: parity-unpinned.
+//
+// Correlate.  Patches w x h, zero-padded to the optimal DFT sizes N x M (N/2 + 1 = Nh bins kept per row):
+//   load      a, b = patch * window (float), zeros in the padding                       ab: 2 x [M][N] float
+//   rows      A, B = row DFT of a, b, bins 0..Nh-1                                      AB: 2 x [M][Nh] float2
+//   columns   FA, FB = column DFT of A, B; P = FA conj(FB); C = P m / (m m + eps)       C:  [M][Nh] float2 over ab
+//   icolumns  D = inverse column DFT of C (no scale)                                    D:  [M][Nh] float2 over AB
+//   irows     r = inverse row DFT of D through D(y, N - v) = conj D(y, v)               r:  [M][N] float over ab
+//   peak      first maximum of fftShift(r) in row-major order, 5 x 5 centroid in fp64, three doubles out
+// Every DFT is a direct sum against a twiddle table indexed by j k mod n (made on the host in double): no size
+// restriction, no radix error growth, and at these sizes a launch is bound by the latency of the dependent passes, not
+// by flops.  When ab + AB + tables fit the LDS (ST_LDS_MAX) the passes run in ONE workgroup with barriers between
+// them; beyond that each pass is a launch of its own over the same device functions, ab and AB in a scratch buffer.
+//
+// Warp.  dst(x, y) = src(x + shift.x, y + shift.y) in warpAffine's 8-bit fixed point: 1/32 px fractions, weights of
+// 2^15, taps outside the frame count 0.  A thread owns 4 consecutive pixels of a row, stored as one dwordx3; a wave
+// owns a row, so the row's Y0, fraction and weights are wave-uniform.  The shift is read from device memory (the
+// correlate launch before it wrote it) or passed as an argument.  Lanes inside the ROI also write the gray float patch
+// of the corrected frame: the `prev` of the next push.
+
+#include <float.h>
+#include <math.h>
+#include <string.h>
+
+#include <vector>
+
+#include "rc_device.h"
+#include "rc_host.h"
+
+#define ST_BLOCK 1024                    // the correlate workgroup: 16 waves
+#define ST_RED_BYTES 256                 // per-wave (value, index) of the arg-max
+#define ST_LDS_MAX (160 * 1024)
+#define ST_ROWS 4                        // warp: rows per block, one per wave
+static_assert(RC_BLOCK == 64 * ST_ROWS, "a warp block is ST_ROWS waves, one row (or run of rows) each");
+
+struct StArgs {
+    const float* a; size_t a_step;       // prev patch, byte step
+    const float* b; size_t b_step;       // curr patch; or, when bgr is set, the ROI of an 8UC3 frame (gray on the fly)
+    const uint8_t* bgr; size_t bgr_step;
+    const float* win;                    // [h][w] Hann window of the unpadded size, or null
+    const float2* twN; const float2* twM;   // (cos, sin)(2 pi j / n), j < n
+    float* ab; float2* AB;               // scratch of the launch-per-pass form (the LDS form carves its own)
+    double* res; double* res2;           // shift_x, shift_y, response (res2: the caller's copy, may be null)
+    int w, h, N, M, Nh;
+};
+
+// ---------------------------------------------------------------------------- pass bodies
+// (t0, nt): this thread's index and the number of threads sharing the pass
+__device__ __forceinline__ float st_gray(const uint8_t* p) {
+    return (float)((p[0] * 1868 + p[1] * 9617 + p[2] * 4899 + (1 << 13)) >> 14);
+}
+
+__device__ __forceinline__ void st_load(const StArgs& p, float* a, float* b, int t0, int nt) {
+    for (int i = t0; i < p.M * p.N; i += nt) {
+        const int y = i / p.N, x = i - y * p.N;
+        float va = 0.f, vb = 0.f;
+        if (x < p.w && y < p.h) {
+            va = ((const float*)((const char*)p.a + (size_t)y * p.a_step))[x];
+            vb = p.bgr ? st_gray(p.bgr + (size_t)y * p.bgr_step + 3 * x)
+                       : ((const float*)((const char*)p.b + (size_t)y * p.b_step))[x];
+            if (p.win) { const float wv = p.win[y * p.w + x]; va *= wv; vb *= wv; }
+        }
+        a[i] = va; b[i] = vb;
+    }
+}
+
+// A[y][k] = sum_x a[y][x] e^(-2 pi i x k / N), both patches against the same twiddles
+__device__ __forceinline__ void st_rows(const StArgs& p, const float* a, const float* b, const float2* tw, float2* A, float2* B,
+                                        int t0, int nt) {
+    for (int i = t0; i < p.M * p.Nh; i += nt) {
+        const int y = i / p.Nh, k = i - y * p.Nh;
+        float ar = 0.f, ai = 0.f, br = 0.f, bi = 0.f;
+        if (y < p.h) {
+            const float* ra = a + y * p.N;
+            const float* rb = b + y * p.N;
+            int j = 0;
+            for (int x = 0; x < p.w; x++) {
+                const float2 t = tw[j];
+                ar += ra[x] * t.x; ai -= ra[x] * t.y;
+                br += rb[x] * t.x; bi -= rb[x] * t.y;
+                j += k; if (j >= p.N) j -= p.N;
+            }
+        }
+        A[i] = make_float2(ar, ai); B[i] = make_float2(br, bi);
+    }
+}
+
+// FA, FB = column DFTs; cross power spectrum, normalised as magSpectrums + divSpectrums do
+__device__ __forceinline__ void st_cols(const StArgs& p, const float2* A, const float2* B, const float2* tw, float2* C, int t0, int nt) {
+    for (int i = t0; i < p.M * p.Nh; i += nt) {
+        const int u = i / p.Nh, v = i - u * p.Nh;
+        float ar = 0.f, ai = 0.f, br = 0.f, bi = 0.f;
+        int j = 0;
+        for (int y = 0; y < p.h; y++) {
+            const float2 t = tw[j], za = A[y * p.Nh + v], zb = B[y * p.Nh + v];
+            ar += za.x * t.x + za.y * t.y; ai += za.y * t.x - za.x * t.y;
+            br += zb.x * t.x + zb.y * t.y; bi += zb.y * t.x - zb.x * t.y;
+            j += u; if (j >= p.M) j -= p.M;
+        }
+        const float pr = ar * br + ai * bi, pi = ai * br - ar * bi;
+        const float m = (float)sqrt((double)pr * pr + (double)pi * pi);
+        const double den = (double)(m * m + FLT_EPSILON);
+        C[i] = make_float2((float)((double)(pr * m) / den), (float)((double)(pi * m) / den));
+    }
+}
+
+// D[y][v] = sum_u C[u][v] e^(+2 pi i u y / M)
+__device__ __forceinline__ void st_icols(const StArgs& p, const float2* C, const float2* tw, float2* D, int t0, int nt) {
+    for (int i = t0; i < p.M * p.Nh; i += nt) {
+        const int y = i / p.Nh, v = i - y * p.Nh;
+        float dr = 0.f, di = 0.f;
+        int j = 0;
+        for (int u = 0; u < p.M; u++) {
+            const float2 t = tw[j], z = C[u * p.Nh + v];
+            dr += z.x * t.x - z.y * t.y; di += z.x * t.y + z.y * t.x;
+            j += y; if (j >= p.M) j -= p.M;
+        }
+        D[i] = make_float2(dr, di);
+    }
+}
+
+// r[y][x] = Re sum_{v < N} D[y][v] e^(+2 pi i v x / N) with D[y][N - v] = conj D[y][v]
+__device__ __forceinline__ void st_irows(const StArgs& p, const float2* D, const float2* tw, float* r, int t0, int nt) {
+    const int vmax = (p.N - 1) / 2;
+    for (int i = t0; i < p.M * p.N; i += nt) {
+        const int y = i / p.N, x = i - y * p.N;
+        const float2* d = D + y * p.Nh;
+        float s = 0.f;
+        int j = x;
+        for (int v = 1; v <= vmax; v++) {
+            const float2 t = tw[j];
+            s += d[v].x * t.x - d[v].y * t.y;
+            j += x; if (j >= p.N) j -= p.N;
+        }
+        float e = d[0].x;
+        if (!(p.N & 1)) e += (x & 1) ? -d[p.N / 2].x : d[p.N / 2].x;
+        r[i] = e + 2.f * s;
+    }
+}
+
+// fftShift (phasecorr.cpp): index i goes to (i + floor(n / 2)) mod n, for odd n too
+__device__ __forceinline__ float st_shifted(const StArgs& p, const float* r, int Y, int X) {
+    int y = Y - p.M / 2, x = X - p.N / 2;
+    if (y < 0) y += p.M;
+    if (x < 0) x += p.N;
+    return r[y * p.N + x];
+}
+
+// minMaxLoc over the shifted surface (lowest row-major index on ties), weightedCentroid in a 5 x 5 box clipped to the
+// surface (fp64, values as they are), response = sum / (M N), shift = (N / 2.0, M / 2.0) - centroid.  One workgroup.
+__device__ __forceinline__ void st_peak(const StArgs& p, const float* r, char* red) {
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = threadIdx.x; i < p.M * p.N; i += blockDim.x) {
+        const int Y = i / p.N, X = i - Y * p.N;
+        const float v = st_shifted(p, r, Y, X);
+        if (v > bv || bi == 0x7fffffff) { bv = v; bi = i; }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
+    }
+    float* rv = (float*)red;
+    int* ri = (int*)(red + ST_RED_BYTES / 2);
+    const int wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    if ((threadIdx.x & 63) == 0) { rv[wave] = bv; ri[wave] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < nw; k++)
+            if (ri[k] != 0x7fffffff && (bi == 0x7fffffff || rv[k] > bv || (rv[k] == bv && ri[k] < bi))) { bv = rv[k]; bi = ri[k]; }
+        const int PY = bi / p.N, PX = bi - PY * p.N;
+        const int minr = max(PY - 2, 0), maxr = min(PY + 2, p.M - 1), minc = max(PX - 2, 0), maxc = min(PX + 2, p.N - 1);
+        double cx = 0., cy = 0., sum = 0.;
+        for (int Y = minr; Y <= maxr; Y++)
+            for (int X = minc; X <= maxc; X++) {
+                const double v = (double)st_shifted(p, r, Y, X);
+                cx += (double)X * v; cy += (double)Y * v; sum += v;
+            }
+        const double response = sum / (double)(p.M * p.N);
+        sum += DBL_EPSILON;
+        const double sx = (double)p.N / 2.0 - cx / sum, sy = (double)p.M / 2.0 - cy / sum;
+        p.res[0] = sx; p.res[1] = sy; p.res[2] = response;
+        if (p.res2) { p.res2[0] = sx; p.res2[1] = sy; p.res2[2] = response; }
+    }
+}
+
+// ---------------------------------------------------------------------------- correlate kernels
+// One workgroup, everything in LDS: 8 M N (ab) + 16 M Nh (AB) + 8 (N + M) (twiddles) + ST_RED_BYTES bytes
+__global__ __launch_bounds__(ST_BLOCK) void k_stab_correlate(const StArgs p) {
+    extern __shared__ __attribute__((aligned(16))) char st_smem[];
+    float* a = (float*)st_smem;
+    float* b = a + p.M * p.N;
+    float2* A = (float2*)(b + p.M * p.N);
+    float2* B = A + p.M * p.Nh;
+    float2* twN = B + p.M * p.Nh;
+    float2* twM = twN + p.N;
+    char* red = (char*)(twM + p.M);
+    const int t0 = threadIdx.x, nt = ST_BLOCK;
+    for (int i = t0; i < p.N; i += nt) twN[i] = p.twN[i];
+    for (int i = t0; i < p.M; i += nt) twM[i] = p.twM[i];
+    st_load(p, a, b, t0, nt);
+    __syncthreads();
+    st_rows(p, a, b, twN, A, B, t0, nt);
+    __syncthreads();
+    st_cols(p, A, B, twM, (float2*)a, t0, nt);
+    __syncthreads();
+    st_icols(p, (const float2*)a, twM, A, t0, nt);
+    __syncthreads();
+    st_irows(p, A, twN, a, t0, nt);
+    __syncthreads();
+    st_peak(p, a, red);
+}
+
+// The same passes as launches of their own, ab and AB in device memory (p.ab, p.AB)
+#define ST_GRID_T0 (int)(blockIdx.x * blockDim.x + threadIdx.x), (int)(gridDim.x * blockDim.x)
+__global__ __launch_bounds__(RC_BLOCK) void k_stab_rows(const StArgs p) {
+    // load and row pass in one launch: a thread's row-pass sums read whole rows, which other threads would have to
+    // have loaded; so every output reads its row straight from the patches instead (the load pass folded in)
+    const int t0 = blockIdx.x * blockDim.x + threadIdx.x, nt = gridDim.x * blockDim.x;
+    for (int i = t0; i < p.M * p.Nh; i += nt) {
+        const int y = i / p.Nh, k = i - y * p.Nh;
+        float ar = 0.f, ai = 0.f, br = 0.f, bi = 0.f;
+        if (y < p.h) {
+            const float* ra = (const float*)((const char*)p.a + (size_t)y * p.a_step);
+            const float* rb = (const float*)((const char*)p.b + (size_t)y * p.b_step);
+            const uint8_t* rg = p.bgr ? p.bgr + (size_t)y * p.bgr_step : nullptr;
+            int j = 0;
+            for (int x = 0; x < p.w; x++) {
+                const float2 t = p.twN[j];
+                float va = ra[x], vb = rg ? st_gray(rg + 3 * x) : rb[x];
+                if (p.win) { const float wv = p.win[y * p.w + x]; va *= wv; vb *= wv; }
+                ar += va * t.x; ai -= va * t.y;
+                br += vb * t.x; bi -= vb * t.y;
+                j += k; if (j >= p.N) j -= p.N;
+            }
+        }
+        p.AB[i] = make_float2(ar, ai); p.AB[p.M * p.Nh + i] = make_float2(br, bi);
+    }
+}
+__global__ __launch_bounds__(RC_BLOCK) void k_stab_cols(const StArgs p) {
+    st_cols(p, p.AB, p.AB + p.M * p.Nh, p.twM, (float2*)p.ab, ST_GRID_T0);
+}
+__global__ __launch_bounds__(RC_BLOCK) void k_stab_icols(const StArgs p) {
+    st_icols(p, (const float2*)p.ab, p.twM, p.AB, ST_GRID_T0);
+}
+__global__ __launch_bounds__(RC_BLOCK) void k_stab_irows(const StArgs p) {
+    st_irows(p, p.AB, p.twN, p.ab, ST_GRID_T0);
+}
+__global__ __launch_bounds__(ST_BLOCK) void k_stab_peak(const StArgs p) {
+    __shared__ __attribute__((aligned(16))) char red[ST_RED_BYTES];
+    st_peak(p, p.ab, red);
+}
+
+// ---------------------------------------------------------------------------- warp
+struct StWarpArgs {
+    const uint8_t* src; size_t step;
+    uint8_t* dst; size_t dst_step;
+    const double* d_shift;               // shift_x, shift_y on the device; null: sx, sy below
+    double sx, sy;
+    float* patch;                        // [rh][rw] gray float of the corrected frame's ROI, or null
+    int w, h, rows, rx, ry, rw, rh;
+};
+
+// pixel (x, y) of the source as byte0 | byte1 << 8 | byte2 << 16; 0 outside the frame (BORDER_CONSTANT, value 0)
+__device__ __forceinline__ uint32_t st_tap(const StWarpArgs& a, int x, int y) {
+    if ((unsigned)x >= (unsigned)a.w || (unsigned)y >= (unsigned)a.h) return 0u;
+    const uint8_t* p = a.src + (size_t)y * a.step + 3 * (size_t)x;
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+}
+// 5 consecutive pixels from 16 bytes
+__device__ __forceinline__ void st_unpack5(const uint8_t* p, uint32_t px[5]) {
+    uint4 q;
+    __builtin_memcpy(&q, p, 16);
+    px[0] = q.x & 0xffffffu;
+    px[1] = (q.x >> 24) | ((q.y & 0xffffu) << 8);
+    px[2] = (q.y >> 16) | ((q.z & 0xffu) << 16);
+    px[3] = q.z >> 8;
+    px[4] = q.w & 0xffffffu;
+}
+
+__global__ __launch_bounds__(RC_BLOCK) void k_stab_warp(const StWarpArgs a) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int x0 = 4 * (blockIdx.x * 64 + (threadIdx.x & 63)), n = min(4, a.w - x0);
+    double sx = a.sx, sy = a.sy;
+    if (a.d_shift) { sx = a.d_shift[0]; sy = a.d_shift[1]; }
+    // X0 = cvRound(shift.x * 1024) + 16; X = (X0 + 1024 x) >> 5: the same fraction for every pixel
+    const int X0 = __double2int_rn(sx * 1024.0) + 16;
+    const int fx = (X0 >> 5) & 31, xs = x0 + (X0 >> 10);
+    if (n <= 0) return;
+    const int yb = (blockIdx.y * ST_ROWS + wave) * a.rows;
+    for (int y = yb; y < min(yb + a.rows, a.h); y++) {
+        // y is inside the rounding: (1.0 * y + shift.y) * 1024 in double, per row
+        const int Y0 = __double2int_rn(((double)y + sy) * 1024.0) + 16;
+        const int fy = (Y0 >> 5) & 31, ys = Y0 >> 10;
+        const int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;
+        uint32_t p0[5], p1[5];
+        if (n == 4 && xs >= 0 && xs + 5 < a.w && ys >= 0 && ys + 1 < a.h) {
+            const uint8_t* s0 = a.src + (size_t)ys * a.step + 3 * (size_t)xs;
+            st_unpack5(s0, p0);
+            st_unpack5(s0 + a.step, p1);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 5; k++) { p0[k] = st_tap(a, xs + k, ys); p1[k] = st_tap(a, xs + k, ys + 1); }
+        }
+        uint32_t o[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            o[k] = 0;
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const int sh = 8 * c;
+                const int v = (int)((p0[k] >> sh) & 255u) * w00 + (int)((p0[k + 1] >> sh) & 255u) * w01 +
+                              (int)((p1[k] >> sh) & 255u) * w10 + (int)((p1[k + 1] >> sh) & 255u) * w11;
+                o[k] |= (uint32_t)((v + (1 << 14)) >> 15) << sh;
+            }
+        }
+        uint8_t* d = a.dst + (size_t)y * a.dst_step + 3 * (size_t)x0;
+        if (n == 4) {
+            uint32_t q[3] = {o[0] | (o[1] << 24), (o[1] >> 8) | (o[2] << 16), (o[2] >> 16) | (o[3] << 8)};
+            __builtin_memcpy(d, q, 12);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (k < n) { d[3 * k] = (uint8_t)o[k]; d[3 * k + 1] = (uint8_t)(o[k] >> 8); d[3 * k + 2] = (uint8_t)(o[k] >> 16); }
+        }
+        if (a.patch && (unsigned)(y - a.ry) < (unsigned)a.rh) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int px = x0 + k - a.rx;
+                if (k < n && (unsigned)px < (unsigned)a.rw)
+                    a.patch[(y - a.ry) * a.rw + px] = (float)(int)(((o[k] & 255u) * 1868u + ((o[k] >> 8) & 255u) * 9617u +
+                                                                   (o[k] >> 16) * 4899u + (1u << 13)) >> 14);
+            }
+        }
+    }
+}
+
+// ============================================================================ host side
+// getOptimalDFTSize: the smallest 2^a 3^b 5^c >= n
+static int st_optimal(int n) {
+    for (int m = n;; m++) {
+        int k = m;
+        while (k % 2 == 0) k /= 2;
+        while (k % 3 == 0) k /= 3;
+        while (k % 5 == 0) k /= 5;
+        if (k == 1) return m;
+    }
+}
+
+struct StPlan {
+    int w = 0, h = 0, N = 0, M = 0, Nh = 0;
+    size_t lds = 0;                      // bytes of the one-workgroup form
+    size_t scratch = 0;                  // bytes of ab + AB
+    bool fits = false;
+};
+static StPlan st_plan(int w, int h) {
+    StPlan q;
+    q.w = w; q.h = h; q.N = st_optimal(w); q.M = st_optimal(h); q.Nh = q.N / 2 + 1;
+    q.scratch = (size_t)8 * q.M * q.N + (size_t)16 * q.M * q.Nh;
+    q.lds = q.scratch + (size_t)8 * (q.N + q.M) + ST_RED_BYTES;
+    q.fits = q.lds <= ST_LDS_MAX;
+    return q;
+}
+
+// tab: window [h][w] | twN [N] float2 | twM [M] float2, made in double.  createHanningWindow: the product of the two
+// raised-cosine factors (double) rounded to float, then a float square root.
+static int st_tables(RcBuf& tab, const StPlan& q, hipStream_t cur) {
+    std::vector<float> t((size_t)q.w * q.h + 2 * (size_t)(q.N + q.M));
+    const double c0 = 2.0 * M_PI / (double)(q.w - 1), c1 = 2.0 * M_PI / (double)(q.h - 1);
+    for (int i = 0; i < q.h; i++) {
+        const double wr = 0.5 * (1.0 - cos(c1 * i));
+        for (int j = 0; j < q.w; j++) t[(size_t)i * q.w + j] = sqrtf((float)(wr * (0.5 * (1.0 - cos(c0 * j)))));
+    }
+    float* tw = t.data() + (size_t)q.w * q.h;
+    for (int j = 0; j < q.N; j++) { tw[2 * j] = (float)cos(2.0 * M_PI * j / q.N); tw[2 * j + 1] = (float)sin(2.0 * M_PI * j / q.N); }
+    tw += 2 * q.N;
+    for (int j = 0; j < q.M; j++) { tw[2 * j] = (float)cos(2.0 * M_PI * j / q.M); tw[2 * j + 1] = (float)sin(2.0 * M_PI * j / q.M); }
+    int rc = rc_buf_ensure(tab, t.size() * sizeof(float));
+    if (rc) return rc;
+    RC_HIP(hipStreamSynchronize(cur));          // a previous launch may still read the old tables
+    RC_HIP(hipMemcpy(tab.p, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
+    return RC_OK;
+}
+
+static void st_fill(StArgs& p, const StPlan& q, const RcBuf& tab, const RcBuf& scratch, bool hann) {
+    p.w = q.w; p.h = q.h; p.N = q.N; p.M = q.M; p.Nh = q.Nh;
+    const float* t = (const float*)tab.p;
+    p.win = hann ? t : nullptr;
+    p.twN = (const float2*)(t + (size_t)q.w * q.h);
+    p.twM = p.twN + q.N;
+    p.ab = (float*)scratch.p;
+    p.AB = scratch.p ? (float2*)((char*)scratch.p + (size_t)8 * q.M * q.N) : nullptr;
+}
+
+// launches: "framestab@0" the one-workgroup form; "framestab@2..6" the passes of the large form
+static int st_correlate(rc_ctx* ctx, hipStream_t cur, const StArgs& p, const StPlan& q) {
+    const double in_bytes = (p.bgr ? 7. : 8.) * q.w * q.h + (p.win ? 4. * q.w * q.h : 0.) + 8. * (q.N + q.M);
+    if (q.fits) {
+        if (q.lds > 64 * 1024) {
+            (void)hipFuncSetAttribute((const void*)k_stab_correlate, hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS_MAX);
+            (void)hipGetLastError();
+        }
+        RcProfScope ps(ctx, cur, RC_K_FRAMESTAB, 0, in_bytes + 24. + (p.res2 ? 24. : 0.));
+        hipLaunchKernelGGL(k_stab_correlate, dim3(1), dim3(ST_BLOCK), q.lds, cur, p);
+    } else {
+        const double half = 8. * q.M * q.Nh, full = 4. * q.M * q.N;
+        const dim3 gh((q.M * q.Nh + RC_BLOCK - 1) / RC_BLOCK), gf((q.M * q.N + RC_BLOCK - 1) / RC_BLOCK);
+        { RcProfScope ps(ctx, cur, RC_K_FRAMESTAB, 2, in_bytes + 2. * half); hipLaunchKernelGGL(k_stab_rows, gh, dim3(RC_BLOCK), 0, cur, p); }
+        { RcProfScope ps(ctx, cur, RC_K_FRAMESTAB, 3, 3. * half); hipLaunchKernelGGL(k_stab_cols, gh, dim3(RC_BLOCK), 0, cur, p); }
+        { RcProfScope ps(ctx, cur, RC_K_FRAMESTAB, 4, 2. * half); hipLaunchKernelGGL(k_stab_icols, gh, dim3(RC_BLOCK), 0, cur, p); }
+        { RcProfScope ps(ctx, cur, RC_K_FRAMESTAB, 5, half + full); hipLaunchKernelGGL(k_stab_irows, gf, dim3(RC_BLOCK), 0, cur, p); }
+        { RcProfScope ps(ctx, cur, RC_K_FRAMESTAB, 6, full + 24. + (p.res2 ? 24. : 0.)); hipLaunchKernelGGL(k_stab_peak, dim3(1), dim3(ST_BLOCK), 0, cur, p); }
+    }
+    RC_HIP(hipGetLastError());
+    return RC_OK;
+}
+
+static int st_check_patch(const char* who, int w, int h, StPlan& q) {
+    if (w < 8 || h < 8) { rc_set_error("%s: patch %d x %d is below 8 x 8", who, w, h); return RC_EINVAL; }
+    if (w > 256 || h > 256) { rc_set_error("%s: patch %d x %d: the optimal DFT size exceeds 256 x 256", who, w, h); return RC_ESIZE; }
+    q = st_plan(w, h);
+    if (q.N > 256 || q.M > 256) {
+        rc_set_error("%s: patch %d x %d has the optimal DFT size %d x %d, above 256 x 256", who, w, h, q.N, q.M);
+        return RC_ESIZE;
+    }
+    return RC_OK;
+}
+
+extern "C" int rcflow_phase_correlate_dev(rc_ctx* ctx, int stream, const float* d_a, size_t a_step, const float* d_b, size_t b_step,
+                                          int w, int h, int use_hann, double* d_result) {
+    RcSlot* s = rc_slot(ctx, stream);
+    if (!s) return RC_EINVAL;
+    if (!d_a || !d_b || !d_result || w <= 0 || h <= 0 || a_step < (size_t)w * 4 || b_step < (size_t)w * 4 || (a_step & 3) || (b_step & 3)) {
+        rc_set_error("rcflow_phase_correlate_dev: bad patch arguments");
+        return RC_EINVAL;
+    }
+    StPlan q;
+    int rc = st_check_patch("rcflow_phase_correlate_dev", w, h, q);
+    if (rc) return rc;
+    RC_HIP(hipSetDevice(ctx->device));
+    RcPhaseCorr& pc = s->pc;
+    if (pc.w != w || pc.h != h) {
+        pc.w = pc.h = 0;
+        if ((rc = st_tables(pc.tab, q, s->cur))) return rc;
+        if (!q.fits && (rc = rc_buf_ensure(pc.scratch, q.scratch))) return rc;
+        pc.w = w; pc.h = h;
+    }
+    StArgs p;
+    memset(&p, 0, sizeof(p));
+    st_fill(p, q, pc.tab, pc.scratch, use_hann != 0);
+    p.a = d_a; p.a_step = a_step; p.b = d_b; p.b_step = b_step;
+    p.res = d_result;
+    return st_correlate(ctx, s->cur, p, q);
+}
+
+static bool st_overlap(const uint8_t* a, size_t astep, const uint8_t* b, size_t bstep, int w, int h) {
+    const uint8_t* ae = a + (size_t)(h - 1) * astep + (size_t)3 * w;
+    const uint8_t* be = b + (size_t)(h - 1) * bstep + (size_t)3 * w;
+    return a < be && b < ae;
+}
+
+static void st_warp_launch(rc_ctx* ctx, hipStream_t cur, StWarpArgs& a) {
+    a.rows = (long long)a.w * a.h >= (1 << 20) ? 2 : 1;
+    const dim3 grid(((a.w + 3) / 4 + 63) / 64, (a.h + ST_ROWS * a.rows - 1) / (ST_ROWS * a.rows));
+    RcProfScope ps(ctx, cur, RC_K_FRAMESTAB, 1, 6. * a.w * a.h + (a.patch ? 4. * a.rw * a.rh : 0.) + (a.d_shift ? 16. : 0.));
+    hipLaunchKernelGGL(k_stab_warp, grid, dim3(RC_BLOCK), 0, cur, a);
+}
+
+extern "C" int rcflow_warp_translate_bgr_dev(rc_ctx* ctx, int stream, const uint8_t* d_bgr, size_t step, int w, int h, uint8_t* d_out,
+                                             size_t out_step, double shift_x, double shift_y) {
+    RcSlot* s = rc_slot(ctx, stream);
+    if (!s) return RC_EINVAL;
+    if (!d_bgr || !d_out || w <= 0 || h <= 0 || step < (size_t)3 * w || out_step < (size_t)3 * w) {
+        rc_set_error("bad image arguments");
+        return RC_EINVAL;
+    }
+    // the fixed-point coordinates are 32-bit with 10 fraction bits
+    if (!(fabs(shift_x) <= 1048576.) || !(fabs(shift_y) <= 1048576.)) {
+        rc_set_error("rcflow_warp_translate_bgr_dev: shift (%g, %g) is not finite or beyond 2^20 px", shift_x, shift_y);
+        return RC_EINVAL;
+    }
+    if (w > ctx->max_w || h > ctx->max_h) { rc_set_error("frame exceeds the context size"); return RC_ESIZE; }
+    if (st_overlap(d_out, out_step, d_bgr, step, w, h)) { rc_set_error("d_out overlaps the frame (the warp is not in place)"); return RC_EINVAL; }
+    RC_HIP(hipSetDevice(ctx->device));
+    StWarpArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = d_bgr; a.step = step; a.dst = d_out; a.dst_step = out_step; a.w = w; a.h = h;
+    a.sx = shift_x; a.sy = shift_y;
+    st_warp_launch(ctx, s->cur, a);
+    RC_HIP(hipGetLastError());
+    return RC_OK;
+}
+
+// ---------------------------------------------------------------------------- the pipeline (main.cpp:1707-1759)
+static void fs_free(RcFrameStab& f) {
+    rc_buf_free(f.tab); rc_buf_free(f.prev); rc_buf_free(f.res); rc_buf_free(f.scratch);
+    if (f.zeroed) (void)hipEventDestroy(f.zeroed);
+    f = RcFrameStab();
+}
+void rc_framestab_free(RcSlot& s) { fs_free(s.fs); }
+
+// nothing to register against yet: frame count, result and prev patch to zero, on the stream the slot has NOW
+static int fs_zero(RcSlot& s) {
+    RcFrameStab& f = s.fs;
+    RC_HIP(hipMemsetAsync(f.prev.p, 0, f.prev.bytes, s.cur));
+    RC_HIP(hipMemsetAsync(f.res.p, 0, f.res.bytes, s.cur));
+    if (!f.zeroed) RC_HIP(hipEventCreateWithFlags(&f.zeroed, hipEventDisableTiming));
+    RC_HIP(hipEventRecord(f.zeroed, s.cur));
+    f.zero_stream = s.cur;
+    f.zero_pending = true;
+    f.frames = 0;
+    return RC_OK;
+}
+
+extern "C" int rcflow_framestab_open(rc_ctx* ctx, int stream, int w, int h, int roi_x, int roi_y, int roi_w, int roi_h) {
+    RcSlot* s = rc_slot(ctx, stream);
+    if (!s) return RC_EINVAL;
+    if (w <= 0 || h <= 0) { rc_set_error("rcflow_framestab_open: bad frame size %d x %d", w, h); return RC_EINVAL; }
+    if (roi_x < 0 || roi_y < 0 || roi_w <= 0 || roi_h <= 0 || roi_x > w - roi_w || roi_y > h - roi_h) {
+        rc_set_error("rcflow_framestab_open: ROI (%d, %d, %d x %d) is not inside the %d x %d frame", roi_x, roi_y, roi_w, roi_h, w, h);
+        return RC_EINVAL;
+    }
+    StPlan q;
+    int rc = st_check_patch("rcflow_framestab_open", roi_w, roi_h, q);
+    if (rc) return rc;
+    if (w > ctx->max_w || h > ctx->max_h) { rc_set_error("frame exceeds the context size"); return RC_ESIZE; }
+    RC_HIP(hipSetDevice(ctx->device));
+    RcFrameStab& f = s->fs;
+    if (f.open) RC_HIP(hipStreamSynchronize(s->cur));     // launches still reading the state being replaced
+    fs_free(f);
+    f.w = w; f.h = h; f.rx = roi_x; f.ry = roi_y; f.rw = roi_w; f.rh = roi_h;
+    f.N = q.N; f.M = q.M; f.lds = q.fits ? q.lds : 0;
+    rc = st_tables(f.tab, q, s->cur);
+    if (!rc) rc = rc_buf_ensure(f.prev, (size_t)roi_w * roi_h * sizeof(float));
+    if (!rc) rc = rc_buf_ensure(f.res, 3 * sizeof(double));
+    if (!rc && !q.fits) rc = rc_buf_ensure(f.scratch, q.scratch);
+    if (rc) {
+        (void)hipGetLastError();
+        fs_free(f);
+        return rc;
+    }
+    f.open = true;
+    if ((rc = fs_zero(*s))) { fs_free(f); return rc; }
+    return RC_OK;
+}
+
+extern "C" int rcflow_framestab_reset(rc_ctx* ctx, int stream) {
+    RcSlot* s = rc_slot(ctx, stream);
+    if (!s) return RC_EINVAL;
+    if (!s->fs.open) { rc_set_error("rcflow_framestab_reset before rcflow_framestab_open"); return RC_ESTATE; }
+    RC_HIP(hipSetDevice(ctx->device));
+    return fs_zero(*s);
+}
+
+extern "C" int rcflow_framestab_close(rc_ctx* ctx, int stream) {
+    RcSlot* s = rc_slot(ctx, stream);
+    if (!s) return RC_EINVAL;
+    if (!s->fs.open) return RC_OK;
+    RC_HIP(hipSetDevice(ctx->device));
+    RC_HIP(hipStreamSynchronize(s->cur));
+    fs_free(s->fs);
+    return RC_OK;
+}
+
+extern "C" int rcflow_framestab_info(rc_ctx* ctx, int stream, int* w, int* h, int roi[4], int dft_size[2], int* launches_per_push,
+                                     long long* frames_pushed, size_t* device_bytes) {
+    RcSlot* s = rc_slot(ctx, stream);
+    if (!s) return RC_EINVAL;
+    const RcFrameStab& f = s->fs;
+    if (!f.open) { rc_set_error("no stabilisation state is open on the slot (rcflow_framestab_open)"); return RC_ESTATE; }
+    if (w) *w = f.w;
+    if (h) *h = f.h;
+    if (roi) { roi[0] = f.rx; roi[1] = f.ry; roi[2] = f.rw; roi[3] = f.rh; }
+    if (dft_size) { dft_size[0] = f.N; dft_size[1] = f.M; }
+    if (launches_per_push) *launches_per_push = f.lds ? 2 : 6;
+    if (frames_pushed) *frames_pushed = f.frames;
+    if (device_bytes) *device_bytes = f.tab.bytes + f.prev.bytes + f.res.bytes + f.scratch.bytes;
+    return RC_OK;
+}
+
+extern "C" int rcflow_framestab_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_frame, size_t step, uint8_t* d_out, size_t out_step,
+                                         double* d_result) {
+    RcSlot* s = rc_slot(ctx, stream);
+    if (!s) return RC_EINVAL;
+    RcFrameStab& f = s->fs;
+    if (!f.open) { rc_set_error("rcflow_framestab_push_dev before rcflow_framestab_open"); return RC_ESTATE; }
+    if (!d_frame || !d_out || step < (size_t)3 * f.w || out_step < (size_t)3 * f.w) {
+        rc_set_error("rcflow_framestab_push_dev: bad frame arguments (a step below 3 * w, or a null image)");
+        return RC_EINVAL;
+    }
+    if (st_overlap(d_out, out_step, d_frame, step, f.w, f.h)) { rc_set_error("d_out overlaps the frame (the warp is not in place)"); return RC_EINVAL; }
+    RC_HIP(hipSetDevice(ctx->device));
+    if (f.zero_pending) {
+        if (s->cur != f.zero_stream) RC_HIP(hipStreamWaitEvent(s->cur, f.zeroed, 0));
+        f.zero_pending = false;
+    }
+    StWarpArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = d_frame; a.step = step; a.dst = d_out; a.dst_step = out_step; a.w = f.w; a.h = f.h;
+    a.patch = (float*)f.prev.p; a.rx = f.rx; a.ry = f.ry; a.rw = f.rw; a.rh = f.rh;
+    if (f.frames == 0) {
+        // the first frame is copied (shift 0: every pixel is its own source) and becomes prev; result (0, 0, 0)
+        RC_HIP(hipMemsetAsync(f.res.p, 0, f.res.bytes, s->cur));
+        if (d_result) RC_HIP(hipMemsetAsync(d_result, 0, 3 * sizeof(double), s->cur));
+    } else {
+        const StPlan q = st_plan(f.rw, f.rh);
+        StArgs p;
+        memset(&p, 0, sizeof(p));
+        st_fill(p, q, f.tab, f.scratch, true);
+        p.a = (const float*)f.prev.p; p.a_step = (size_t)f.rw * sizeof(float);
+        p.bgr = d_frame + (size_t)f.ry * step + (size_t)3 * f.rx; p.bgr_step = step;
+        p.res = (double*)f.res.p; p.res2 = d_result;
+        int rc = st_correlate(ctx, s->cur, p, q);
+        if (rc) return rc;
+        a.d_shift = (const double*)f.res.p;
+    }
+    st_warp_launch(ctx, s->cur, a);
+    RC_HIP(hipGetLastError());
+    f.frames++;
+    return RC_OK;
+}
+
+extern "C" int rcflow_framestab_read(rc_ctx* ctx, int stream, double result[3], long long* frames_pushed) {
+    RcSlot* s = rc_slot(ctx, stream);
+    if (!s) return RC_EINVAL;
+    RcFrameStab& f = s->fs;
+    if (!f.open) { rc_set_error("rcflow_framestab_read before rcflow_framestab_open"); return RC_ESTATE; }
+    RC_HIP(hipSetDevice(ctx->device));
+    if (f.zero_pending && s->cur != f.zero_stream) RC_HIP(hipStreamWaitEvent(s->cur, f.zeroed, 0));
+    double r[3] = {0., 0., 0.};
+    RC_HIP(hipMemcpyAsync(r, f.res.p, sizeof(r), hipMemcpyDeviceToHost, s->cur));
+    RC_HIP(hipStreamSynchronize(s->cur));
+    if (result) { result[0] = r[0]; result[1] = r[1]; result[2] = r[2]; }
+    if (frames_pushed) *frames_pushed = f.frames;
+    return RC_OK;
+}
