@@ -402,6 +402,86 @@ int rcflow_framestab_close(rc_ctx* ctx, int stream);
 int rcflow_framestab_info(rc_ctx* ctx, int stream, int* w, int* h, int roi[4], int dft_size[2], int* launches_per_push,
                           long long* frames_pushed, size_t* device_bytes);
 
+/* ------------------------------------------------------------------ general warps; several patches, a fitted motion
+ * What the reference's other stabiliser, stabilize (main.cpp:1556-1682), does to a frame -- a planar correction,
+ * warpPerspective(curr, M.inv()) -- without its AKAZE features, matcher and RANSAC: the motion is estimated by the
+ * patch correlation above on SEVERAL static patches, gated by their response, fitted on the device, and the frame is
+ * corrected by cv::warpAffine.  cv::warpAffine and cv::warpPerspective are also stages for a matrix the caller has.
+ * Both are restated from upstream 4.1.0 (imgwarp.cpp, the CPU path), parity-unpinned; 8UC3, INTER_LINEAR,
+ * BORDER_CONSTANT value 0, a destination size of its own.  THE BIT-EXACT CONTRACT IS STATED ON THE
+ * DESTINATION-TO-SOURCE MATRIX M (what RC_WARP_INVERSE_MAP passes as given):
+ *   affine       adelta[x] = cvRound(M0 x 1024), bdelta[x] = cvRound(M3 x 1024); per row X0 = cvRound((M1 y + M2) 1024) + 16,
+ *                Y0 = cvRound((M4 y + M5) 1024) + 16; X = (X0 + adelta[x]) >> 5, Y = (Y0 + bdelta[x]) >> 5; source pixel
+ *                (sat_short(X >> 5), sat_short(Y >> 5)), fractions X & 31, Y & 31 (1/32 px).  cvRound is round-half-even;
+ *                every product and sum rounds on its own.  M = [1 0 sx; 0 1 sy] is rcflow_warp_translate_bgr_dev bit for bit.
+ *   perspective  double per pixel, AND THE BITS DEPEND ON UPSTREAM'S TILING: the destination is walked in blocks of bw0
+ *                columns, bh0 = min(16, dh), bw0 = min(1024 / bh0, dw) (64 for any real frame).  With xb the block's
+ *                first column and x1 = x - xb: X0 = M0 xb + M1 y + M2, Y0 = M3 xb + M4 y + M5, W0 = M6 xb + M7 y + M8 (left
+ *                to right); W = W0 + M6 x1; W = W ? 32 / W : 0; X = cvRound(max(INT_MIN, min(INT_MAX, (X0 + M0 x1) W))), Y
+ *                likewise; then >> 5, & 31 and sat_short as above.  Nothing is refused for its range: a point at infinity
+ *                (W = 0) reads source pixel (0, 0), and beyond it, where W changes sign, the other sheet of the map.
+ *   sample       as rcflow_warp_translate_bgr_dev: weights (32 - fy)(32 - fx) 32, (32 - fy) fx 32, fy (32 - fx) 32,
+ *                fy fx 32 of 2^15, out = (sum + 2^14) >> 15 per channel, a tap outside the source counts 0.
+ * Without RC_WARP_INVERSE_MAP the matrix is inverted on the host in double first (affine: warpAffine's own sequence,
+ * D = M0 M4 - M1 M3, ..., b1 = -M0 M2 - M1 M5; perspective: the cofactor inverse times 1 / det); that is a convenience,
+ * held to a tolerance on the matrix, not to bits on the image.
+ * RC_EINVAL: a null pointer, a step below 3 * w, d_out overlapping d_bgr (not in place), an entry that is not finite,
+ * a singular matrix in the forward form, unknown flag bits; for the affine form a matrix whose terms carry a
+ * destination corner beyond 2^20 px (|M0| (dw - 1) + |M1| (dh - 1) + |M2| and the same of M3..M5: the translate warp's
+ * bound, it keeps every cvRound within int).  RC_ESIZE: source or destination beyond the context's size.  A refused
+ * call writes nothing.  Asynchronous.  Recorded as "framestab@8" (affine) and "framestab@9" (perspective). */
+#define RC_WARP_INVERSE_MAP 16      /* cv::WARP_INVERSE_MAP: M maps destination to source as given */
+int rcflow_warp_affine_bgr_dev(rc_ctx* ctx, int stream, const uint8_t* d_bgr, size_t step, int sw, int sh,
+                               uint8_t* d_out, size_t out_step, int dw, int dh, const double M[6], int flags);
+int rcflow_warp_perspective_bgr_dev(rc_ctx* ctx, int stream, const uint8_t* d_bgr, size_t step, int sw, int sh,
+                                    uint8_t* d_out, size_t out_step, int dw, int dh, const double M[9], int flags);
+
+/* A stabilisation slot with 1..RC_STAB_MAX_PATCHES static patches and a fitted motion.  rcflow_framestab_push_dev /
+ * _read / _reset / _close / _info serve a slot opened either way; a slot opened by rcflow_framestab_open runs the code it
+ * always ran.
+ *   patches    rois = n x (x, y, w, h), all of ONE size (one window, one twiddle set), each inside the frame, at least
+ *              8 x 8 (RC_EINVAL) and small enough for the one-workgroup correlation (optimal sizes up to about
+ *              100 x 100; RC_ESIZE beyond: the launch-per-pass form stays single-patch).  They may overlap.
+ *   correlate  ONE launch of n workgroups ("framestab@7"), workgroup k the single-patch correlation of patch k: shift k
+ *              is what a single-patch slot on that patch computes, bit for bit.
+ *   gate       patch k takes part iff response_k >= min_response (NaN fails).
+ *   fit        fp64, by the workgroup of that launch that finishes last.  Patch centre c_k = (x + (w - 1) / 2,
+ *              y + (h - 1) / 2); with d_k the shift of patch k, T(c_k) ~ c_k + d_k: T maps the corrected frame to the
+ *              incoming one and the correction is dst(p) = src(T p), rcflow_warp_affine_bgr_dev with RC_WARP_INVERSE_MAP
+ *              reading T from device memory.  The DISPLACEMENT d = B (p - pbar) + t is fitted by unweighted least squares
+ *              over the gated patches on coordinates centred on their mean pbar (t = the mean shift), so a still scene
+ *              gives T = I exactly: RC_STAB_TRANSLATION B = 0; RC_STAB_SIMILARITY B = [a -b; b a],
+ *              a = sum(u.d) / sum(u.u), b = sum(u x d) / sum(u.u); RC_STAB_AFFINE the two rows of B from the 2 x 2 normal
+ *              matrix [Sxx Sxy; Sxy Syy].  T = [I + B | t - B pbar].
+ *   ladder     affine needs 3 gated patches and det > 1e-12 Sxx Syy (not collinear), else similarity; similarity needs
+ *              2 and sum(u.u) > 0, else translation; translation needs 1; none: the identity, model_used = 0 and the
+ *              frame is copied.  One patch with RC_STAB_TRANSLATION gives T = [1 0 dx; 0 1 dy] and a frame, result and kept
+ *              patch bit-identical to rcflow_framestab_open's slot.
+ *   previous   default: every frame is registered against the last CORRECTED frame, the warp writes the gray patches
+ *              of its output (the reference's chain).  RC_STAB_ANCHOR_FIRST: against the first frame after open / reset,
+ *              whose patches are kept for good; the residual cannot walk (total excursion must stay within a patch).
+ * A push is two launches ("framestab@7", "framestab@8"), free of host synchronisation and device-to-host copies; the
+ * first push after open / reset copies the frame and reports zeros and the identity.  For such a slot
+ * rcflow_framestab_read and d_result give the displacement of the frame centre ((w - 1) / 2, (h - 1) / 2) under T and the
+ * smallest response among the patches used (0 when none); rcflow_framestab_info reports patch 0. */
+enum { RC_STAB_TRANSLATION = 1, RC_STAB_SIMILARITY = 2, RC_STAB_AFFINE = 3 };
+#define RC_STAB_ANCHOR_FIRST 1      /* register against the first frame after open / reset, not the last corrected one */
+#define RC_STAB_MAX_PATCHES 16
+/* RC_EINVAL: n outside 1..16, a patch outside the frame, below 8 x 8 or of another size than patch 0, an unknown model
+ * or flag bit, a min_response that is NaN; RC_ESIZE: see above, or a frame beyond the context's size.  A refused open
+ * leaves the slot's state as it was.  Stream rules as rcflow_framestab_open. */
+int rcflow_framestab_open_multi(rc_ctx* ctx, int stream, int w, int h, const int* rois /* n x (x, y, w, h) */, int n,
+                                int model, double min_response, int flags);
+/* Blocks until the slot's stream has finished.  motion = T (row-major 2 x 3) of the last push, model_used = the rung
+ * of the ladder it came from (0: identity), shifts = n x (dx, dy, response) of every patch, gated or not (may be NULL,
+ * as any other pointer).  Before the second push: the identity, 0, 0, zeros.  For a slot opened by
+ * rcflow_framestab_open: [1 0 dx; 0 1 dy], RC_STAB_TRANSLATION, 1, its one shift. */
+int rcflow_framestab_read_motion(rc_ctx* ctx, int stream, double motion[6], int* model_used, int* patches_used,
+                                 double* shifts /* n x (dx, dy, response), may be NULL */, long long* frames_pushed);
+/* any pointer may be NULL; rois receives min(n, cap) patches.  A slot opened by rcflow_framestab_open reports n = 1,
+ * RC_STAB_TRANSLATION, min_response = -infinity (it has no gate), flags = 0.  RC_ESTATE when nothing is open. */
+int rcflow_framestab_info_multi(rc_ctx* ctx, int stream, int* n, int* rois, int cap, int* model, double* min_response, int* flags);
+
 /* ------------------------------------------------------------------ time-exposure images
  * compute_timex (main.cpp:1195-1263) and compute_brightColor (main.cpp:1265-1383) on frames resident on the device.
  * All images are 8UC3; "channel 0 / 1 / 2" are the bytes as they come (the reference feeds BGR frames to

@@ -14,6 +14,7 @@
 //   Timeline, PopulationMap    ripcurrents.hpp:64-75, 86-95  ripcurrents_module.cpp:751-807, 1140-1196
 //   timexOpen / timexPush      compute_timex main.cpp:1195-1263, compute_brightColor main.cpp:1265-1383
 //   framestabOpen / framestabPush   compute_phaseCorrelate main.cpp:1684-1775
+//   framestabOpenMulti, warpAffine, warpPerspective   the correction of stabilize (main.cpp:1556-1682) by that estimator
 // rc::Mat is a non-owning view with cv::Mat's fields (data, step, rows, cols); with OpenCV
 // present, include/rcflow_cv.hpp converts cv::Mat to it.  Errors are thrown as
 // rc::Error (the reference's OpenCV calls throw cv::Exception and are never caught).
@@ -350,6 +351,19 @@ class Pipeline {
                   "download corrected frame");
         if (shift) { shift[0] = r[0]; shift[1] = r[1]; shift[2] = r[2]; }
     }
+    // Several static patches (n x (x, y, w, h), one size) and a fitted motion: model RC_STAB_TRANSLATION / _SIMILARITY /
+    // _AFFINE over the patches whose response reaches min_response; flags: RC_STAB_ANCHOR_FIRST.  framestabPush then
+    // corrects roll and zoom too, and framestabMotion reads the 2 x 3 motion of the last push (corrected(p) = frame(T p)).
+    void framestabOpenMulti(const std::vector<int>& rois, int model = RC_STAB_SIMILARITY, double min_response = 0., int flags = 0) {
+        check(rcflow_framestab_open_multi(ctx_, 0, w_, h_, rois.data(), (int)(rois.size() / 4), model, min_response, flags));
+    }
+    void framestabMotion(double motion[6], int* model_used = nullptr, int* patches_used = nullptr) {
+        check(rcflow_framestab_read_motion(ctx_, 0, motion, model_used, patches_used, nullptr, nullptr));
+    }
+    // cv::warpAffine / cv::warpPerspective(src, dst, M, dst.size(), INTER_LINEAR [| WARP_INVERSE_MAP]) on 8UC3 host
+    // images of any size within the pipeline's (flags: 0 or RC_WARP_INVERSE_MAP).
+    void warpAffine(const Mat& src, Mat& dst, const double M[6], int flags = 0) { warp(src, dst, M, flags, false); }
+    void warpPerspective(const Mat& src, Mat& dst, const double M[9], int flags = 0) { warp(src, dst, M, flags, true); }
     void framestabReset() { check(rcflow_framestab_reset(ctx_, 0)); }
     void framestabClose() { check(rcflow_framestab_close(ctx_, 0)); }
 
@@ -357,6 +371,19 @@ class Pipeline {
     int height() const { return h_; }
 
   private:
+    void warp(const Mat& src, Mat& dst, const double* M, int flags, bool perspective) {
+        auto is_8uc3 = [](const Mat& m) { return !m.empty() && m.channels == 3 && m.elem == 1; };
+        if (!is_8uc3(src) || !is_8uc3(dst)) throw Error(RC_EINVAL, "warp: src and dst must be 8UC3");
+        const size_t sb = ((size_t)src.cols * src.rows * 3 + 255) & ~(size_t)255, db = (size_t)dst.cols * dst.rows * 3;
+        uint8_t* b = (uint8_t*)scratch(sb + db);
+        hip_check(hipMemcpy2D(b, (size_t)src.cols * 3, src.data, src.step, (size_t)src.cols * 3, src.rows, hipMemcpyHostToDevice), "upload image");
+        int rc = (perspective ? rcflow_warp_perspective_bgr_dev : rcflow_warp_affine_bgr_dev)(
+            ctx_, 0, b, (size_t)src.cols * 3, src.cols, src.rows, b + sb, (size_t)dst.cols * 3, dst.cols, dst.rows, M, flags);
+        if (rc == RC_OK) rc = rcflow_sync(ctx_, 0);
+        check(rc);
+        hip_check(hipMemcpy2D(dst.data, dst.step, b + sb, (size_t)dst.cols * 3, (size_t)dst.cols * 3, dst.rows, hipMemcpyDeviceToHost),
+                  "download warped image");
+    }
     // grow-only device scratch for the per-frame helpers (seeds, traces, display image, LK points)
     void* scratch(size_t bytes) {
         if (bytes > scratch_bytes_) {

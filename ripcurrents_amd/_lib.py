@@ -18,6 +18,11 @@ HIST_WORDS = HIST_BINS + HIST_DIRECTIONS * HIST_BINS + 1 + HIST_DIRECTIONS
 COMM_ID_BYTES = 128     # RC_COMM_ID_BYTES = sizeof(ncclUniqueId)
 # RC_TIMEX_*: product name -> mask bit; the order is the order of rcflow_timex_push_dev's d_out[4]
 TIMEX_PRODUCTS = {"mean": 1, "average": 2, "bright": 4, "dark": 8}
+RC_WARP_INVERSE_MAP = 16
+# RC_STAB_*: the motion models of rcflow_framestab_open_multi, and its one flag
+STAB_MODELS = {"translation": 1, "similarity": 2, "affine": 3}
+RC_STAB_ANCHOR_FIRST = 1
+RC_STAB_MAX_PATCHES = 16
 
 ERRORS = {-1: "RC_EINVAL", -2: "RC_ENOMEM", -3: "RC_EHIP", -4: "RC_ENODEV", -5: "RC_ESIZE",
           -6: "RC_ESTATE", -7: "RC_ECOMM"}
@@ -112,6 +117,11 @@ SIGNATURES = {
     "rcflow_framestab_close": [_vp, _i],
     "rcflow_framestab_info": [_vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
                               C.POINTER(C.c_longlong), C.POINTER(_sz)],
+    "rcflow_warp_affine_bgr_dev": [_vp, _i, _vp, _sz, _i, _i, _vp, _sz, _i, _i, C.POINTER(_d), _i],
+    "rcflow_warp_perspective_bgr_dev": [_vp, _i, _vp, _sz, _i, _i, _vp, _sz, _i, _i, C.POINTER(_d), _i],
+    "rcflow_framestab_open_multi": [_vp, _i, _i, _i, C.POINTER(_i), _i, _i, _d, _i],
+    "rcflow_framestab_read_motion": [_vp, _i, C.POINTER(_d), C.POINTER(_i), C.POINTER(_i), C.POINTER(_d), C.POINTER(C.c_longlong)],
+    "rcflow_framestab_info_multi": [_vp, _i, C.POINTER(_i), C.POINTER(_i), _i, C.POINTER(_i), C.POINTER(_d), C.POINTER(_i)],
     "rcflow_timex_open": [_vp, _i, _i, _i, _i, _i],
     "rcflow_timex_push_dev": [_vp, _i, _vp, _sz, C.POINTER(_vp), C.POINTER(_sz)],
     "rcflow_timex_reset": [_vp, _i],

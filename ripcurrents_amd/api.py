@@ -24,6 +24,7 @@ import torch
 
 from . import _lib
 from ._lib import FarnebackParams, HIST_BINS, HIST_DIRECTIONS, HIST_WORDS, RC_FARNEBACK_USE_INITIAL_FLOW, TIMEX_PRODUCTS, RcflowError, check
+from ._lib import RC_STAB_ANCHOR_FIRST, RC_STAB_MAX_PATCHES, RC_WARP_INVERSE_MAP, STAB_MODELS
 
 __all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState"]
 
@@ -774,12 +775,69 @@ class Context:
                                                       self._ptr(out), out.stride(0), float(shift_x), float(shift_y)))
         return out
 
-    def framestab_open(self, w, h, roi=None, stream=0):
+    def _warp(self, fn, nm, frame, M, inverse_map, dsize, out, stream):
+        f = self._img3(frame)
+        dw, dh = (f.shape[1], f.shape[0]) if dsize is None else (int(dsize[0]), int(dsize[1]))
+        m = np.ascontiguousarray(np.asarray(M, np.float64)).reshape(-1)
+        if m.size != nm:
+            raise ValueError("expected a matrix of %d entries" % nm)
+        if out is None:
+            out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=self.device)
+        else:
+            self._check_out3(out, (dh, dw, 3), "out")
+        self._bind(stream)
+        check(fn(self._h, stream, self._ptr(f), f.stride(0), f.shape[1], f.shape[0], self._ptr(out), out.stride(0), dw, dh,
+                 m.ctypes.data_as(C.POINTER(C.c_double)), RC_WARP_INVERSE_MAP if inverse_map else 0))
+        return out
+
+    def warp_affine(self, frame, M, inverse_map=False, dsize=None, out=None, stream=0):
+        """cv::warpAffine(frame, M (2 x 3), dsize = (dw, dh), INTER_LINEAR [| WARP_INVERSE_MAP]) on an 8UC3 frame, zero
+        outside.  inverse_map: M maps destination to source as given (the form the bit-exact contract is stated on);
+        otherwise it is inverted on the host first.  dsize: default the source's; `out`: the image to write."""
+        return self._warp(self._lib.rcflow_warp_affine_bgr_dev, 6, frame, M, inverse_map, dsize, out, stream)
+
+    def warp_perspective(self, frame, M, inverse_map=False, dsize=None, out=None, stream=0):
+        """cv::warpPerspective(frame, M (3 x 3), dsize, INTER_LINEAR [| WARP_INVERSE_MAP]) on an 8UC3 frame: as warp_affine."""
+        return self._warp(self._lib.rcflow_warp_perspective_bgr_dev, 9, frame, M, inverse_map, dsize, out, stream)
+
+    def framestab_open(self, w, h, roi=None, stream=0, rois=None, model="similarity", min_response=0.0, anchor="previous"):
         """Opens the slot's stabilisation state (compute_phaseCorrelate, main.cpp:1684-1775) for w x h frames.
-        roi = (x, y, w, h) of the static patch to track; default: the reference's (w - 50, 50, 50, 50)."""
-        x, y, rw, rh = (int(w) - 50, 50, 50, 50) if roi is None else (int(v) for v in roi)
+        roi = (x, y, w, h) of the static patch to track; default: the reference's (w - 50, 50, 50, 50).
+        rois = [(x, y, w, h), ...] instead: 1..16 static patches of one size, and a motion fitted to their shifts
+        (model "translation" | "similarity" | "affine") over the patches whose response is at least min_response;
+        anchor "previous" registers every frame against the last corrected one, "first" against the first frame after
+        open / reset.  The frame is then corrected for roll and zoom too (see framestab_motion)."""
         self._bind(stream)          # the state is zeroed on the slot's stream: the one the pushes will run on
-        check(self._lib.rcflow_framestab_open(self._h, stream, int(w), int(h), x, y, rw, rh))
+        if rois is None:
+            x, y, rw, rh = (int(w) - 50, 50, 50, 50) if roi is None else (int(v) for v in roi)
+            check(self._lib.rcflow_framestab_open(self._h, stream, int(w), int(h), x, y, rw, rh))
+            return
+        if roi is not None:
+            raise ValueError("give roi or rois, not both")
+        if model not in STAB_MODELS or anchor not in ("previous", "first"):
+            raise ValueError("model must be one of %s, anchor \"previous\" or \"first\"" % sorted(STAB_MODELS))
+        r = np.ascontiguousarray(np.asarray(rois, np.int32)).reshape(-1, 4)
+        check(self._lib.rcflow_framestab_open_multi(self._h, stream, int(w), int(h), r.ctypes.data_as(C.POINTER(C.c_int)), len(r),
+                                                    STAB_MODELS[model], float(min_response),
+                                                    RC_STAB_ANCHOR_FIRST if anchor == "first" else 0))
+
+    def framestab_motion(self, stream=0):
+        """Waits for the slot's stream -> dict(motion (2 x 3 float64: T maps the corrected frame to the incoming one,
+        corrected(p) = frame(T p)), model_used ("translation" | "similarity" | "affine" | None: the identity),
+        patches_used, shifts (n x 3: dx, dy, response of every patch), frames_pushed, rois, model, min_response, anchor)."""
+        n, model, flags, minr = C.c_int(0), C.c_int(0), C.c_int(0), C.c_double(0.)
+        rois = (C.c_int * (4 * RC_STAB_MAX_PATCHES))()
+        check(self._lib.rcflow_framestab_info_multi(self._h, stream, C.byref(n), rois, RC_STAB_MAX_PATCHES, C.byref(model),
+                                                    C.byref(minr), C.byref(flags)))
+        mo, sh = (C.c_double * 6)(), (C.c_double * (3 * RC_STAB_MAX_PATCHES))()
+        used, cnt, frames = C.c_int(0), C.c_int(0), C.c_longlong(0)
+        self._bind(stream)
+        check(self._lib.rcflow_framestab_read_motion(self._h, stream, mo, C.byref(used), C.byref(cnt), sh, C.byref(frames)))
+        names = {v: k for k, v in STAB_MODELS.items()}
+        return dict(motion=np.array(mo[:]).reshape(2, 3), model_used=names.get(used.value), patches_used=cnt.value,
+                    shifts=np.array(sh[:3 * n.value]).reshape(n.value, 3), frames_pushed=frames.value,
+                    rois=[tuple(rois[4 * k:4 * k + 4]) for k in range(n.value)], model=names[model.value],
+                    min_response=minr.value, anchor="first" if flags.value & RC_STAB_ANCHOR_FIRST else "previous")
 
     def framestab_info(self, stream=0):
         """dict(w, h, roi, dft_size (N, M), launches_per_push, frames_pushed, device_bytes) of the open state."""

@@ -78,6 +78,27 @@ struct RcFrameStab {
     hipEvent_t zeroed = nullptr;
     hipStream_t zero_stream = nullptr;
     bool zero_pending = false;
+    // rcflow_framestab_open_multi (n = 0: the single-patch slot above).  The patches share rw x rh, tab and the LDS
+    // plan; prev holds n patches; res holds RC_FS_* doubles: result | motion | used | ticket | the n shifts
+    int n = 0, model = 0, flags = 0;
+    double min_response = 0.;
+    int px[RC_STAB_MAX_PATCHES] = {}, py[RC_STAB_MAX_PATCHES] = {};
+};
+// layout of RcFrameStab::res for a multi-patch slot, in doubles
+enum { RC_FS_RESULT = 0 /* 3 */, RC_FS_MOTION = 3 /* 6 */, RC_FS_USED = 9 /* int model_used, patches_used */,
+       RC_FS_TICKET = 10 /* unsigned arrivals of the running correlate launch */, RC_FS_SHIFTS = 16 /* n x 3 */ };
+
+// warp_kernels.hip: one launch of the affine / perspective warp
+struct RcWarpArgs {
+    const uint8_t* src; size_t step;
+    uint8_t* dst; size_t dst_step;
+    int sw, sh, dw, dh;
+    double M[9];                         // destination to source; affine: M[0..5]
+    const double* d_M;                   // affine: the six entries on the device instead (the stabiliser's fit), or null
+    int bw0;                             // perspective: columns per block of upstream's tiling (set by rc_warp_launch)
+    float* patch;                        // affine: [npatch][rh][rw] gray float of the OUTPUT inside each ROI, or null
+    int npatch, rw, rh;
+    int rx[RC_STAB_MAX_PATCHES], ry[RC_STAB_MAX_PATCHES];
 };
 
 // rcflow_phase_correlate_dev: the tables (and spectra scratch) of the last patch size, cached per slot
@@ -179,7 +200,8 @@ enum { RC_K_PYR = 0, RC_K_POLY = 1, RC_K_ITER = 2, RC_K_HIST = 3, RC_K_THRESH = 
        RC_K_ADVECT_FIELD = 6, RC_K_ADVECT_POINTS = 7, RC_K_POSTOP = 8, RC_K_COLOR = 9, RC_K_ITER2 = 10,
        RC_K_PREPROC = 11, RC_K_EDGES = 12, RC_K_DISPLAY = 13, RC_K_HSV2BGR = 14, RC_K_OVERLAY = 15, RC_K_FLOW_SEED = 16,
        RC_K_TIMEX = 17 /* @0 mean, @1 ring products */, RC_K_COLOR_U8 = 18 /* @0 rgb_to_hsv, @1 hsv_to_rgb, @2 resize_bgr, @3 resize_area_bgr */,
-       RC_K_FRAMESTAB = 19 /* @0 correlate in one workgroup, @1 warp, @2..6 the correlate passes as launches of their own */,
+       RC_K_FRAMESTAB = 19 /* @0 correlate in one workgroup, @1 warp, @2..6 the correlate passes as launches of their own,
+                              @7 multi-patch correlate + fit, @8 affine warp, @9 perspective warp */,
        RC_K_KINDS = 20 };
 
 void rc_set_error(const char* fmt, ...);
@@ -201,6 +223,8 @@ void rc_area_tab(int ssize, int dsize, double scale, std::vector<int>& start, st
 void rc_timex_free(RcSlot& s);
 // stab_kernels.hip
 void rc_framestab_free(RcSlot& s);
+// warp_kernels.hip
+void rc_warp_launch(rc_ctx* ctx, hipStream_t cur, RcWarpArgs& a, bool perspective);
 // initial_flow_kernels.hip
 int rc_flow_area_prepare(RcBuf& tab, int W, int H, int w, int h, RcFlowAreaArgs& a);
 

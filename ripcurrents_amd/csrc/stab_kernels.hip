@@ -1,4 +1,6 @@
-// stab_kernels.hip -- frame stabilisation on the device: the reference's compute_phaseCorrelate (main.cpp:1684-1775).
+// stab_kernels.hip -- frame stabilisation on the device: the reference's compute_phaseCorrelate (main.cpp:1684-1775),
+// and the same estimator on several patches with a motion fitted to them (rcflow_framestab_open_multi; the correcting
+// warp of that form is warp_kernels.hip's).
 // Per frame: phaseCorrelate(prev_roi, curr_roi, hann) on a patch of beach that does not move, then
 // warpAffine(curr, [1 0 -shift.x; 0 1 -shift.y]) and the corrected frame becomes `prev`.  phaseCorrelate,
 // createHanningWindow, getOptimalDFTSize and warpAffine are OpenCV's (4.1.0 phasecorr.cpp, imgwarp.cpp), restated
@@ -192,8 +194,8 @@ __device__ __forceinline__ void st_peak(const StArgs& p, const float* r, char* r
 
 // ---------------------------------------------------------------------------- correlate kernels
 // One workgroup, everything in LDS: 8 M N (ab) + 16 M Nh (AB) + 8 (N + M) (twiddles) + ST_RED_BYTES bytes
-__global__ __launch_bounds__(ST_BLOCK) void k_stab_correlate(const StArgs p) {
-    extern __shared__ __attribute__((aligned(16))) char st_smem[];
+extern __shared__ __attribute__((aligned(16))) char st_smem[];
+__device__ __forceinline__ void st_correlate_wg(const StArgs& p) {
     float* a = (float*)st_smem;
     float* b = a + p.M * p.N;
     float2* A = (float2*)(b + p.M * p.N);
@@ -215,6 +217,104 @@ __global__ __launch_bounds__(ST_BLOCK) void k_stab_correlate(const StArgs p) {
     st_irows(p, A, twN, a, t0, nt);
     __syncthreads();
     st_peak(p, a, red);
+}
+__global__ __launch_bounds__(ST_BLOCK) void k_stab_correlate(const StArgs p) { st_correlate_wg(p); }
+
+// ---------------------------------------------------------------------------- several patches, a fitted motion
+// Workgroup k correlates patch k (the body above, unchanged) and thread 0 of the workgroup that finishes LAST fits the
+// motion to the gated shifts, so a push stays at two launches.  Hand-off between workgroups (they run on different CUs
+// and XCDs, whose L1 / L2 do not see each other's plain stores): thread 0 stores its three doubles again with
+// agent-scope atomic stores, drains them, does ONE agent-scope release fence, drains again, then draws a ticket with an
+// agent-scope atomic add; the thread that draws n - 1 does ONE agent-scope acquire fence and reads all the shifts with
+// agent-scope atomic loads.  Nothing waits for anything: no spinning, any dispatch order works.  The last arriver zeroes
+// the ticket for the next push (stream order), and open / reset zero it with the rest of the state.
+struct StMultiArgs {
+    StArgs p;                            // sizes and tables; a = the prev patch 0; b, bgr, res are set per workgroup
+    const uint8_t* frame; size_t step;   // the incoming frame
+    double* state;                       // RcFrameStab::res (RC_FS_*)
+    double* res2;                        // the caller's copy of the result, or null
+    double min_response;
+    int n, model, fw, fh;
+    int rx[RC_STAB_MAX_PATCHES], ry[RC_STAB_MAX_PATCHES];
+};
+
+__device__ __forceinline__ double st_ld(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// One lane, fp64; products and sums round one by one (-ffp-contract=off), in the order of tests/_framewarp_ref.py
+__device__ void st_fit(const StMultiArgs& m) {
+    const double* sh = m.state + RC_FS_SHIFTS;
+    const double hx = ((double)m.p.w - 1.0) / 2.0, hy = ((double)m.p.h - 1.0) / 2.0;
+    double px = 0., py = 0., tx = 0., ty = 0., rmin = INFINITY;
+    unsigned mask = 0;
+    int cnt = 0;
+    for (int k = 0; k < m.n; k++) {
+        const double r = st_ld(sh + 3 * k + 2);
+        if (!(r >= m.min_response)) continue;
+        mask |= 1u << k; cnt++;
+        px += (double)m.rx[k] + hx; py += (double)m.ry[k] + hy;
+        tx += st_ld(sh + 3 * k); ty += st_ld(sh + 3 * k + 1);
+        rmin = r < rmin ? r : rmin;
+    }
+    double b00 = 0., b01 = 0., b10 = 0., b11 = 0.;
+    int used = 0;
+    if (cnt) {
+        const double dn = (double)cnt;
+        px /= dn; py /= dn; tx /= dn; ty /= dn;
+        double sxx = 0., sxy = 0., syy = 0., xdx = 0., ydx = 0., xdy = 0., ydy = 0.;
+        for (int k = 0; k < m.n; k++) {
+            if (!(mask >> k & 1u)) continue;
+            const double ux = ((double)m.rx[k] + hx) - px, uy = ((double)m.ry[k] + hy) - py;
+            const double ex = st_ld(sh + 3 * k) - tx, ey = st_ld(sh + 3 * k + 1) - ty;
+            sxx += ux * ux; sxy += ux * uy; syy += uy * uy;
+            xdx += ux * ex; ydx += uy * ex; xdy += ux * ey; ydy += uy * ey;
+        }
+        used = RC_STAB_TRANSLATION;
+        const double det = sxx * syy - sxy * sxy;
+        if (m.model >= RC_STAB_AFFINE && cnt >= 3 && det > 1e-12 * (sxx * syy)) {
+            used = RC_STAB_AFFINE;
+            b00 = (xdx * syy - ydx * sxy) / det; b01 = (ydx * sxx - xdx * sxy) / det;
+            b10 = (xdy * syy - ydy * sxy) / det; b11 = (ydy * sxx - xdy * sxy) / det;
+        } else if (m.model >= RC_STAB_SIMILARITY && cnt >= 2 && sxx + syy > 0.) {
+            used = RC_STAB_SIMILARITY;
+            const double a = (xdx + ydy) / (sxx + syy), b = (xdy - ydx) / (sxx + syy);
+            b00 = a; b01 = -b; b10 = b; b11 = a;
+        }
+    } else {
+        rmin = 0.;
+    }
+    double* mo = m.state + RC_FS_MOTION;
+    mo[0] = 1.0 + b00; mo[1] = b01; mo[2] = tx - (b00 * px + b01 * py);
+    mo[3] = b10; mo[4] = 1.0 + b11; mo[5] = ty - (b10 * px + b11 * py);
+    const double cx = ((double)m.fw - 1.0) / 2.0 - px, cy = ((double)m.fh - 1.0) / 2.0 - py;
+    const double r0 = cnt ? (b00 * cx + b01 * cy) + tx : 0., r1 = cnt ? (b10 * cx + b11 * cy) + ty : 0.;
+    double* res = m.state + RC_FS_RESULT;
+    res[0] = r0; res[1] = r1; res[2] = rmin;
+    if (m.res2) { m.res2[0] = r0; m.res2[1] = r1; m.res2[2] = rmin; }
+    int* u = (int*)(m.state + RC_FS_USED);
+    u[0] = used; u[1] = cnt;
+}
+
+__global__ __launch_bounds__(ST_BLOCK) void k_stab_correlate_multi(const StMultiArgs m) {
+    const int k = blockIdx.x;
+    StArgs p = m.p;
+    p.a = m.p.a + (size_t)k * p.w * p.h;
+    p.bgr = m.frame + (size_t)m.ry[k] * m.step + 3 * (size_t)m.rx[k];
+    p.res = m.state + RC_FS_SHIFTS + 3 * k;
+    p.res2 = nullptr;
+    st_correlate_wg(p);
+    if (threadIdx.x != 0) return;
+    // this thread wrote p.res (st_peak); again as write-through stores, then release, then the ticket
+#pragma unroll
+    for (int i = 0; i < 3; i++) __hip_atomic_store(p.res + i, p.res[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    unsigned* ticket = (unsigned*)(m.state + RC_FS_TICKET);
+    const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t != (unsigned)(m.n - 1)) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    st_fit(m);
 }
 
 // The same passes as launches of their own, ab and AB in device memory (p.ab, p.AB)
@@ -584,6 +684,147 @@ extern "C" int rcflow_framestab_info(rc_ctx* ctx, int stream, int* w, int* h, in
     return RC_OK;
 }
 
+// A push of a slot opened by rcflow_framestab_open_multi: "framestab@7" (n workgroups + the fit), "framestab@8"
+static int fs_push_multi(rc_ctx* ctx, RcSlot& s, const uint8_t* d_frame, size_t step, uint8_t* d_out, size_t out_step, double* d_result) {
+    RcFrameStab& f = s.fs;
+    RcWarpArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = d_frame; a.step = step; a.sw = f.w; a.sh = f.h; a.dst = d_out; a.dst_step = out_step; a.dw = f.w; a.dh = f.h;
+    a.M[0] = a.M[4] = 1.;
+    if (f.frames == 0 || !(f.flags & RC_STAB_ANCHOR_FIRST)) {
+        a.patch = (float*)f.prev.p; a.npatch = f.n; a.rw = f.rw; a.rh = f.rh;
+        memcpy(a.rx, f.px, sizeof(a.rx)); memcpy(a.ry, f.py, sizeof(a.ry));
+    }
+    if (f.frames == 0) {
+        // the first frame is copied (the identity: every pixel is its own source) and its patches become prev
+        RC_HIP(hipMemsetAsync(f.res.p, 0, f.res.bytes, s.cur));
+        if (d_result) RC_HIP(hipMemsetAsync(d_result, 0, 3 * sizeof(double), s.cur));
+    } else {
+        const StPlan q = st_plan(f.rw, f.rh);
+        StMultiArgs m;
+        memset(&m, 0, sizeof(m));
+        st_fill(m.p, q, f.tab, f.scratch, true);
+        m.p.a = (const float*)f.prev.p; m.p.a_step = (size_t)f.rw * sizeof(float); m.p.bgr_step = step;
+        m.frame = d_frame; m.step = step;
+        m.state = (double*)f.res.p; m.res2 = d_result;
+        m.min_response = f.min_response; m.n = f.n; m.model = f.model; m.fw = f.w; m.fh = f.h;
+        memcpy(m.rx, f.px, sizeof(m.rx)); memcpy(m.ry, f.py, sizeof(m.ry));
+        if (q.lds > 64 * 1024) {
+            (void)hipFuncSetAttribute((const void*)k_stab_correlate_multi, hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS_MAX);
+            (void)hipGetLastError();
+        }
+        {
+            const double in_bytes = 7. * q.w * q.h + 4. * q.w * q.h + 8. * (q.N + q.M);
+            RcProfScope ps(ctx, s.cur, RC_K_FRAMESTAB, 7, f.n * (in_bytes + 24.) + 72. + (d_result ? 24. : 0.));
+            hipLaunchKernelGGL(k_stab_correlate_multi, dim3(f.n), dim3(ST_BLOCK), q.lds, s.cur, m);
+        }
+        RC_HIP(hipGetLastError());
+        a.d_M = (const double*)f.res.p + RC_FS_MOTION;
+    }
+    rc_warp_launch(ctx, s.cur, a, false);
+    RC_HIP(hipGetLastError());
+    f.frames++;
+    return RC_OK;
+}
+
+extern "C" int rcflow_framestab_open_multi(rc_ctx* ctx, int stream, int w, int h, const int* rois, int n, int model, double min_response,
+                                           int flags) {
+    static const char* who = "rcflow_framestab_open_multi";
+    RcSlot* s = rc_slot(ctx, stream);
+    if (!s) return RC_EINVAL;
+    if (w <= 0 || h <= 0) { rc_set_error("%s: bad frame size %d x %d", who, w, h); return RC_EINVAL; }
+    if (!rois || n < 1 || n > RC_STAB_MAX_PATCHES) { rc_set_error("%s: %d patches (1..%d)", who, n, RC_STAB_MAX_PATCHES); return RC_EINVAL; }
+    if (model < RC_STAB_TRANSLATION || model > RC_STAB_AFFINE || (flags & ~RC_STAB_ANCHOR_FIRST) || min_response != min_response) {
+        rc_set_error("%s: unknown model %d or flag bits 0x%x, or min_response is NaN", who, model, flags);
+        return RC_EINVAL;
+    }
+    const int rw = rois[2], rh = rois[3];
+    for (int k = 0; k < n; k++) {
+        const int* r = rois + 4 * k;
+        if (r[0] < 0 || r[1] < 0 || r[2] <= 0 || r[3] <= 0 || r[0] > w - r[2] || r[1] > h - r[3]) {
+            rc_set_error("%s: patch %d (%d, %d, %d x %d) is not inside the %d x %d frame", who, k, r[0], r[1], r[2], r[3], w, h);
+            return RC_EINVAL;
+        }
+        if (r[2] != rw || r[3] != rh) { rc_set_error("%s: patch %d is %d x %d, patch 0 is %d x %d (one size for all)", who, k, r[2], r[3], rw, rh); return RC_EINVAL; }
+    }
+    StPlan q;
+    int rc = st_check_patch(who, rw, rh, q);
+    if (rc) return rc;
+    if (!q.fits) {
+        rc_set_error("%s: patch %d x %d (DFT %d x %d) is beyond the one-workgroup correlation; larger patches are single-patch (rcflow_framestab_open)",
+                     who, rw, rh, q.N, q.M);
+        return RC_ESIZE;
+    }
+    if (w > ctx->max_w || h > ctx->max_h) { rc_set_error("frame exceeds the context size"); return RC_ESIZE; }
+    RC_HIP(hipSetDevice(ctx->device));
+    RcFrameStab& f = s->fs;
+    if (f.open) RC_HIP(hipStreamSynchronize(s->cur));     // launches still reading the state being replaced
+    fs_free(f);
+    f.w = w; f.h = h; f.rx = rois[0]; f.ry = rois[1]; f.rw = rw; f.rh = rh;
+    f.N = q.N; f.M = q.M; f.lds = q.lds;
+    f.n = n; f.model = model; f.flags = flags; f.min_response = min_response;
+    for (int k = 0; k < n; k++) { f.px[k] = rois[4 * k]; f.py[k] = rois[4 * k + 1]; }
+    rc = st_tables(f.tab, q, s->cur);
+    if (!rc) rc = rc_buf_ensure(f.prev, (size_t)n * rw * rh * sizeof(float));
+    if (!rc) rc = rc_buf_ensure(f.res, (size_t)(RC_FS_SHIFTS + 3 * RC_STAB_MAX_PATCHES) * sizeof(double));
+    if (rc) {
+        (void)hipGetLastError();
+        fs_free(f);
+        return rc;
+    }
+    f.open = true;
+    if ((rc = fs_zero(*s))) { fs_free(f); return rc; }
+    return RC_OK;
+}
+
+extern "C" int rcflow_framestab_info_multi(rc_ctx* ctx, int stream, int* n, int* rois, int cap, int* model, double* min_response, int* flags) {
+    RcSlot* s = rc_slot(ctx, stream);
+    if (!s) return RC_EINVAL;
+    const RcFrameStab& f = s->fs;
+    if (!f.open) { rc_set_error("no stabilisation state is open on the slot (rcflow_framestab_open)"); return RC_ESTATE; }
+    const int np = f.n ? f.n : 1;
+    if (n) *n = np;
+    if (rois)
+        for (int k = 0; k < np && k < cap; k++) {
+            rois[4 * k] = f.n ? f.px[k] : f.rx; rois[4 * k + 1] = f.n ? f.py[k] : f.ry; rois[4 * k + 2] = f.rw; rois[4 * k + 3] = f.rh;
+        }
+    if (model) *model = f.n ? f.model : RC_STAB_TRANSLATION;
+    if (min_response) *min_response = f.n ? f.min_response : -INFINITY;
+    if (flags) *flags = f.flags;
+    return RC_OK;
+}
+
+extern "C" int rcflow_framestab_read_motion(rc_ctx* ctx, int stream, double motion[6], int* model_used, int* patches_used, double* shifts,
+                                            long long* frames_pushed) {
+    RcSlot* s = rc_slot(ctx, stream);
+    if (!s) return RC_EINVAL;
+    RcFrameStab& f = s->fs;
+    if (!f.open) { rc_set_error("rcflow_framestab_read_motion before rcflow_framestab_open"); return RC_ESTATE; }
+    RC_HIP(hipSetDevice(ctx->device));
+    if (f.zero_pending && s->cur != f.zero_stream) RC_HIP(hipStreamWaitEvent(s->cur, f.zeroed, 0));
+    double st[RC_FS_SHIFTS + 3 * RC_STAB_MAX_PATCHES] = {};
+    RC_HIP(hipMemcpyAsync(st, f.res.p, f.n ? sizeof(st) : 3 * sizeof(double), hipMemcpyDeviceToHost, s->cur));
+    RC_HIP(hipStreamSynchronize(s->cur));
+    const bool fitted = f.frames > 1;                        // the first push registers against nothing
+    double mo[6] = {1., 0., 0., 0., 1., 0.};
+    int used[2] = {0, 0};
+    const int np = f.n ? f.n : 1;
+    if (fitted && f.n) {
+        memcpy(mo, st + RC_FS_MOTION, sizeof(mo));
+        memcpy(used, st + RC_FS_USED, sizeof(used));
+    } else if (fitted) {
+        mo[2] = st[0]; mo[5] = st[1];
+        used[0] = RC_STAB_TRANSLATION; used[1] = 1;
+    }
+    if (motion) memcpy(motion, mo, sizeof(mo));
+    if (model_used) *model_used = used[0];
+    if (patches_used) *patches_used = used[1];
+    if (shifts)
+        for (int i = 0; i < 3 * np; i++) shifts[i] = fitted ? (f.n ? st[RC_FS_SHIFTS + i] : st[i]) : 0.;
+    if (frames_pushed) *frames_pushed = f.frames;
+    return RC_OK;
+}
+
 extern "C" int rcflow_framestab_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_frame, size_t step, uint8_t* d_out, size_t out_step,
                                          double* d_result) {
     RcSlot* s = rc_slot(ctx, stream);
@@ -600,6 +841,7 @@ extern "C" int rcflow_framestab_push_dev(rc_ctx* ctx, int stream, const uint8_t*
         if (s->cur != f.zero_stream) RC_HIP(hipStreamWaitEvent(s->cur, f.zeroed, 0));
         f.zero_pending = false;
     }
+    if (f.n) return fs_push_multi(ctx, *s, d_frame, step, d_out, out_step, d_result);
     StWarpArgs a;
     memset(&a, 0, sizeof(a));
     a.src = d_frame; a.step = step; a.dst = d_out; a.dst_step = out_step; a.w = f.w; a.h = f.h;
