@@ -551,7 +551,8 @@ int rcflow_jet_lut(uint8_t* lut_bgr /* 768 */);
 /* Sparse pyramidal Lucas-Kanade: cv::calcOpticalFlowPyrLK(prev, next, prevPts, nextPts, status, err,
  * winSize, maxLevel, criteria, flags, minEigThreshold) on 8UC1 device images -- Streakline.cpp:32,
  * ripcurrents_module.cpp:716, :738, :775, :1162.  d_prev_pts / d_next_pts: npts x (x, y) floats on the
- * device; d_status npts bytes; d_err npts floats or NULL.  crit_type bit 0 = TermCriteria::COUNT,
+ * device; d_status npts bytes; d_err npts floats or NULL (without it, as upstream, the residual pass and
+ * the bounds test of the final position in it are skipped).  crit_type bit 0 = TermCriteria::COUNT,
  * bit 1 = EPS; flags: 4 = OPTFLOW_USE_INITIAL_FLOW (d_next_pts is then also an input), 8 =
  * OPTFLOW_LK_GET_MIN_EIGENVALS.  maxLevel < 8, windows up to 128x128. */
 int rcflow_pyrlk_dev(rc_ctx* ctx, int stream, const uint8_t* d_prev, size_t prev_step,

@@ -9,13 +9,20 @@
  * in raster order.  Reference call sites: Streakline.cpp:32, ripcurrents_module.cpp:775 and :1162
  * (win 50x50, maxLevel 3, COUNT+EPS 30 / 0.1, flags 10, minEig 1e-4); :716, :738 (win 21x21).
  * SURVEY.md section 8(f) row 3.
+ *
+ * exact_sums (orc_pyrlk_ex, orc_streakline_step_lk_ex): the window sums A11, A12, A22, b1, b2 and
+ * the err residual are accumulated in int64 and converted to float once, before the FLT_SCALE
+ * multiply, as the device kernel k_lk_track does.  Nothing else differs, so the kernel can be held
+ * to this mode bit for bit; the default stays upstream's raster-order float sums.
  */
 #include "rc_oracle.h"
 
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
+#include <thread>
 #include <vector>
 
 namespace {
@@ -151,10 +158,10 @@ extern "C" int orc_pyrlk_levels(int w, int h, int win_w, int win_h, int max_leve
     return max_level;
 }
 
-extern "C" int orc_pyrlk(const uint8_t* prev, size_t prev_step, const uint8_t* next, size_t next_step, int w,
-                         int h, const float* prev_pts, float* next_pts, int npts, uint8_t* status, float* err,
-                         int win_w, int win_h, int max_level, int crit_type, int max_count, double epsilon,
-                         int flags, double min_eig_threshold) {
+extern "C" int orc_pyrlk_ex(const uint8_t* prev, size_t prev_step, const uint8_t* next, size_t next_step, int w,
+                            int h, const float* prev_pts, float* next_pts, int npts, uint8_t* status, float* err,
+                            int win_w, int win_h, int max_level, int crit_type, int max_count, double epsilon,
+                            int flags, double min_eig_threshold, int exact_sums, int nthreads) {
     if (!prev || !next || !prev_pts || !next_pts || !status || npts < 0 || w < 1 || h < 1 || win_w <= 2 ||
         win_h <= 2 || max_level < 0)
         return -1;
@@ -172,16 +179,19 @@ extern "C" int orc_pyrlk(const uint8_t* prev, size_t prev_step, const uint8_t* n
     max_level = std::min(lp, ln);
 
     for (int i = 0; i < npts; i++) { status[i] = 1; if (err) err[i] = 0.f; }
-    std::vector<int16_t> Ibuf((size_t)win_w * win_h), dIbuf((size_t)win_w * win_h * 2);
+    const bool exact = exact_sums != 0;
     const int W_BITS = 14, W_BITS1 = 14;
     const float FLT_SCALE = 1.f / (1 << 20);
     const float halfx = (win_w - 1) * 0.5f, halfy = (win_h - 1) * 0.5f;
 
+    // points are independent of each other: a range of them, all levels, with its own patch buffers
+    auto track = [&](int pt_begin, int pt_end) {
+    std::vector<int16_t> Ibuf((size_t)win_w * win_h), dIbuf((size_t)win_w * win_h * 2);
     for (int level = max_level; level >= 0; level--) {
         const Level& I = P[level];
         const Level& J = N[level];
         const int stepI = I.pitch(), stepJ = J.pitch(), dstep = I.pitch() * 2;
-        for (int pt = 0; pt < npts; pt++) {
+        for (int pt = pt_begin; pt < pt_end; pt++) {
             float px = prev_pts[2 * pt] * (float)(1. / (1 << level));
             float py = prev_pts[2 * pt + 1] * (float)(1. / (1 << level));
             float nx, ny;
@@ -208,6 +218,7 @@ extern "C" int orc_pyrlk(const uint8_t* prev, size_t prev_step, const uint8_t* n
             int iw10 = cv_round((1.f - a) * b * (1 << W_BITS));
             int iw11 = (1 << W_BITS) - iw00 - iw01 - iw10;
             float iA11 = 0, iA12 = 0, iA22 = 0;
+            int64_t sA11 = 0, sA12 = 0, sA22 = 0;
             for (int y = 0; y < win_h; y++) {
                 const uint8_t* src = I.I(y + ipy) + ipx;
                 const int16_t* dsrc = I.D(y + ipy) + ipx * 2;
@@ -223,11 +234,18 @@ extern "C" int orc_pyrlk(const uint8_t* prev, size_t prev_step, const uint8_t* n
                     Ip[x] = (int16_t)ival;
                     dIp[0] = (int16_t)ixval;
                     dIp[1] = (int16_t)iyval;
-                    iA11 += (float)(ixval * ixval);
-                    iA12 += (float)(ixval * iyval);
-                    iA22 += (float)(iyval * iyval);
+                    if (exact) {
+                        sA11 += (int64_t)ixval * ixval;
+                        sA12 += (int64_t)ixval * iyval;
+                        sA22 += (int64_t)iyval * iyval;
+                    } else {
+                        iA11 += (float)(ixval * ixval);
+                        iA12 += (float)(ixval * iyval);
+                        iA22 += (float)(iyval * iyval);
+                    }
                 }
             }
+            if (exact) { iA11 = (float)sA11; iA12 = (float)sA12; iA22 = (float)sA22; }
             float A11 = iA11 * FLT_SCALE, A12 = iA12 * FLT_SCALE, A22 = iA22 * FLT_SCALE;
             float D = A11 * A22 - A12 * A12;
             float minEig = (A22 + A11 - std::sqrt((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) /
@@ -252,6 +270,7 @@ extern "C" int orc_pyrlk(const uint8_t* prev, size_t prev_step, const uint8_t* n
                 iw10 = cv_round((1.f - a) * b * (1 << W_BITS));
                 iw11 = (1 << W_BITS) - iw00 - iw01 - iw10;
                 float ib1 = 0, ib2 = 0;
+                int64_t sb1 = 0, sb2 = 0;
                 for (int y = 0; y < win_h; y++) {
                     const uint8_t* Jp = J.I(y + iny) + inx;
                     const int16_t* Ip = Ibuf.data() + (size_t)y * win_w;
@@ -259,10 +278,16 @@ extern "C" int orc_pyrlk(const uint8_t* prev, size_t prev_step, const uint8_t* n
                     for (int x = 0; x < win_w; x++, dIp += 2) {
                         int diff = descale(Jp[x] * iw00 + Jp[x + 1] * iw01 + Jp[x + stepJ] * iw10 +
                                            Jp[x + stepJ + 1] * iw11, W_BITS1 - 5) - Ip[x];
-                        ib1 += (float)(diff * dIp[0]);
-                        ib2 += (float)(diff * dIp[1]);
+                        if (exact) {
+                            sb1 += (int64_t)diff * dIp[0];
+                            sb2 += (int64_t)diff * dIp[1];
+                        } else {
+                            ib1 += (float)(diff * dIp[0]);
+                            ib2 += (float)(diff * dIp[1]);
+                        }
                     }
                 }
+                if (exact) { ib1 = (float)sb1; ib2 = (float)sb2; }
                 float b1 = ib1 * FLT_SCALE, b2 = ib2 * FLT_SCALE;
                 float dx = (float)((A12 * b2 - A22 * b1) * D), dy = (float)((A12 * b1 - A11 * b2) * D);
                 nx += dx; ny += dy;
@@ -288,35 +313,58 @@ extern "C" int orc_pyrlk(const uint8_t* prev, size_t prev_step, const uint8_t* n
                 iw10 = cv_round((1.f - aa) * bb * (1 << W_BITS));
                 iw11 = (1 << W_BITS) - iw00 - iw01 - iw10;
                 float errval = 0.f;
+                int64_t serr = 0;
                 for (int y = 0; y < win_h; y++) {
                     const uint8_t* Jp = J.I(y + iny) + inx;
                     const int16_t* Ip = Ibuf.data() + (size_t)y * win_w;
                     for (int x = 0; x < win_w; x++) {
                         int diff = descale(Jp[x] * iw00 + Jp[x + 1] * iw01 + Jp[x + stepJ] * iw10 +
                                            Jp[x + stepJ + 1] * iw11, W_BITS1 - 5) - Ip[x];
-                        errval += std::abs((float)diff);
+                        if (exact) serr += diff < 0 ? -diff : diff;
+                        else errval += std::abs((float)diff);
                     }
                 }
+                if (exact) errval = (float)serr;
                 err[pt] = errval * 1.f / (32 * win_w * win_h);
             }
         }
     }
+    };
+    if (nthreads <= 1 || npts < 2 * nthreads) {
+        track(0, npts);
+    } else {
+        std::vector<std::thread> th;
+        const int chunk = (npts + nthreads - 1) / nthreads;
+        for (int t = 0; t < nthreads; t++) {
+            const int a = t * chunk, b = std::min(npts, a + chunk);
+            if (a < b) th.emplace_back(track, a, b);
+        }
+        for (auto& t : th) t.join();
+    }
     return 0;
+}
+
+extern "C" int orc_pyrlk(const uint8_t* prev, size_t prev_step, const uint8_t* next, size_t next_step, int w,
+                         int h, const float* prev_pts, float* next_pts, int npts, uint8_t* status, float* err,
+                         int win_w, int win_h, int max_level, int crit_type, int max_count, double epsilon,
+                         int flags, double min_eig_threshold) {
+    return orc_pyrlk_ex(prev, prev_step, next, next_step, w, h, prev_pts, next_pts, npts, status, err, win_w, win_h,
+                        max_level, crit_type, max_count, epsilon, flags, min_eig_threshold, 0, 1);
 }
 
 /* Streakline.cpp:22-71 with the reference's own mover: vertices advanced by PyrLK
  * (win 50x50, maxLevel 3, 30 iterations / eps 0.1, flags 10, minEig 1e-4), jumps above a tenth
  * of the frame reverted, generation point inserted at index 0, frame counter advanced. */
-extern "C" int orc_streakline_step_lk(float* verts, int* nverts, float gen_x, float gen_y, const uint8_t* prev,
-                                      size_t prev_step, const uint8_t* next, size_t next_step, int w, int h,
-                                      int* frame_count) {
+extern "C" int orc_streakline_step_lk_ex(float* verts, int* nverts, float gen_x, float gen_y, const uint8_t* prev,
+                                         size_t prev_step, const uint8_t* next, size_t next_step, int w, int h,
+                                         int* frame_count, int exact_sums) {
     int n = *nverts;
     std::vector<float> nextv((size_t)2 * std::max(n, 1));
     std::vector<uint8_t> st(std::max(n, 1));
     std::vector<float> er(std::max(n, 1));
     if (n > 0) {
-        int rc = orc_pyrlk(prev, prev_step, next, next_step, w, h, verts, nextv.data(), n, st.data(), er.data(), 50,
-                           50, 3, 3, 30, 0.1, 10, 1e-4);
+        int rc = orc_pyrlk_ex(prev, prev_step, next, next_step, w, h, verts, nextv.data(), n, st.data(), er.data(), 50,
+                              50, 3, 3, 30, 0.1, 10, 1e-4, exact_sums, 1);
         if (rc) return rc;
         for (int i = 0; i < n; i++) {
             if (std::abs(verts[2 * i] - nextv[2 * i]) > w * 0.1 || std::abs(verts[2 * i + 1] - nextv[2 * i + 1]) > h * 0.1) {
@@ -331,4 +379,11 @@ extern "C" int orc_streakline_step_lk(float* verts, int* nverts, float gen_x, fl
     *nverts = n + 1;
     (*frame_count)++;
     return 0;
+}
+
+extern "C" int orc_streakline_step_lk(float* verts, int* nverts, float gen_x, float gen_y, const uint8_t* prev,
+                                      size_t prev_step, const uint8_t* next, size_t next_step, int w, int h,
+                                      int* frame_count) {
+    return orc_streakline_step_lk_ex(verts, nverts, gen_x, gen_y, prev, prev_step, next, next_step, w, h, frame_count,
+                                     0);
 }

@@ -343,8 +343,14 @@ CRIT_COUNT, CRIT_EPS = 1, 2
 
 
 def pyrlk(prev, nxt, prev_pts, next_pts=None, win=(21, 21), max_level=3, crit_type=CRIT_COUNT | CRIT_EPS,
-          max_count=30, epsilon=0.01, flags=0, min_eig_threshold=1e-4):
-    """cv::calcOpticalFlowPyrLK on two HxW uint8 images.  Returns (next_pts, status, err)."""
+          max_count=30, epsilon=0.01, flags=0, min_eig_threshold=1e-4, exact_sums=False, nthreads=1,
+          with_err=True):
+    """cv::calcOpticalFlowPyrLK on two HxW uint8 images.  Returns (next_pts, status, err).
+
+    exact_sums=True sums the window products in int64 and converts once (order-free, what the device
+    kernel does); the default is upstream's raster-order float sums.  nthreads splits the point list
+    (same result).  with_err=False passes err = NULL, as a caller without the err output does: upstream
+    then skips the residual pass and its last bounds test, and err comes back as None."""
     prev = np.ascontiguousarray(prev, dtype=np.uint8)
     nxt = np.ascontiguousarray(nxt, dtype=np.uint8)
     h, w = prev.shape
@@ -353,13 +359,14 @@ def pyrlk(prev, nxt, prev_pts, next_pts=None, win=(21, 21), max_level=3, crit_ty
     q = np.zeros((n, 2), np.float32) if next_pts is None else _f32(next_pts).reshape(-1, 2).copy()
     status = np.zeros(n, np.uint8)
     err = np.zeros(n, np.float32)
-    rc = lib().orc_pyrlk(_p(prev, C.c_uint8), C.c_size_t(prev.strides[0]), _p(nxt, C.c_uint8),
-                         C.c_size_t(nxt.strides[0]), w, h, _p(p), _p(q), n, _p(status, C.c_uint8), _p(err),
-                         win[0], win[1], max_level, crit_type, max_count, C.c_double(epsilon), flags,
-                         C.c_double(min_eig_threshold))
+    rc = lib().orc_pyrlk_ex(_p(prev, C.c_uint8), C.c_size_t(prev.strides[0]), _p(nxt, C.c_uint8),
+                            C.c_size_t(nxt.strides[0]), w, h, _p(p), _p(q), n, _p(status, C.c_uint8),
+                            _p(err) if with_err else None, win[0], win[1], max_level, crit_type, max_count,
+                            C.c_double(epsilon), flags, C.c_double(min_eig_threshold), int(bool(exact_sums)),
+                            int(nthreads))
     if rc != 0:
         raise ValueError("orc_pyrlk rejected its arguments (rc=%d)" % rc)
-    return q, status, err
+    return q, status, (err if with_err else None)
 
 
 def pyrlk_levels(w, h, win, max_level):
@@ -383,15 +390,15 @@ def scharr_deriv(img):
     return out
 
 
-def streakline_step_lk(verts, nverts, gen, prev, nxt, frame_count):
+def streakline_step_lk(verts, nverts, gen, prev, nxt, frame_count, exact_sums=False):
     prev = np.ascontiguousarray(prev, dtype=np.uint8)
     nxt = np.ascontiguousarray(nxt, dtype=np.uint8)
     h, w = prev.shape
     n = C.c_int(nverts)
     fc = C.c_int(frame_count)
-    rc = lib().orc_streakline_step_lk(_p(verts), C.byref(n), C.c_float(gen[0]), C.c_float(gen[1]),
-                                      _p(prev, C.c_uint8), C.c_size_t(prev.strides[0]), _p(nxt, C.c_uint8),
-                                      C.c_size_t(nxt.strides[0]), w, h, C.byref(fc))
+    rc = lib().orc_streakline_step_lk_ex(_p(verts), C.byref(n), C.c_float(gen[0]), C.c_float(gen[1]),
+                                         _p(prev, C.c_uint8), C.c_size_t(prev.strides[0]), _p(nxt, C.c_uint8),
+                                         C.c_size_t(nxt.strides[0]), w, h, C.byref(fc), int(bool(exact_sums)))
     if rc != 0:
         raise ValueError("orc_streakline_step_lk failed (rc=%d)" % rc)
     return n.value, fc.value

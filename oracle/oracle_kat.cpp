@@ -127,6 +127,34 @@ int main() {
         orc_resize_area_bgr_to_gray(bgr8.data(), 211 * 3, 211, 133, gray.data(), w, w, h);
         show("resize area", gray);
     }
+    {   // sparse PyrLK: float sums, exact sums (threaded == single-threaded), err absent, the LK streakline step
+        const int w = 97, h = 70, n = 40;
+        std::vector<uint8_t> a, b;
+        frame(a, w, h, 0); frame(b, w, h, 1);
+        std::vector<float> p(2 * n), q(2 * n, 0.f), q2(2 * n, 0.f), er(n), er2(n);
+        std::vector<uint8_t> st(n), st2(n);
+        for (int i = 0; i < n; i++) { p[2 * i] = (float)((i * 37) % 120) - 10.25f; p[2 * i + 1] = (float)((i * 23) % 90) - 9.5f; }
+        p[0] = NAN; p[3] = INFINITY; p[4] = 3e38f; p[6] = 2147483648.f;
+        const int wins[][2] = {{21, 21}, {5, 9}, {9, 5}, {3, 3}};
+        for (auto& wn : wins) {
+            if (orc_pyrlk(a.data(), w, b.data(), w, w, h, p.data(), q.data(), n, st.data(), er.data(), wn[0], wn[1], 3, 3, 30, 0.01, 0, 1e-4)) return 5;
+            snprintf(name, sizeof(name), "pyrlk float %dx%d", wn[0], wn[1]);
+            show(name, q); show(name, st); show(name, er);
+            if (orc_pyrlk_ex(a.data(), w, b.data(), w, w, h, p.data(), q.data(), n, st.data(), er.data(), wn[0], wn[1], 3, 3, 30, 0.01, 0, 1e-4, 1, 1)) return 5;
+            if (orc_pyrlk_ex(a.data(), w, b.data(), w, w, h, p.data(), q2.data(), n, st2.data(), er2.data(), wn[0], wn[1], 3, 3, 30, 0.01, 0, 1e-4, 1, 3)) return 5;
+            if (memcmp(q.data(), q2.data(), q.size() * 4) || memcmp(st.data(), st2.data(), n) || memcmp(er.data(), er2.data(), n * 4)) { printf("threads change pyrlk\n"); return 6; }
+            snprintf(name, sizeof(name), "pyrlk exact %dx%d", wn[0], wn[1]);
+            show(name, q); show(name, st); show(name, er);
+            if (orc_pyrlk_ex(a.data(), w, b.data(), w, w, h, p.data(), q2.data(), n, st2.data(), nullptr, wn[0], wn[1], 2, 1, 5, 0.01, 8, 1e-3, 1, 2)) return 5;
+            snprintf(name, sizeof(name), "pyrlk exact no err %dx%d", wn[0], wn[1]);
+            show(name, q2); show(name, st2);
+        }
+        std::vector<float> verts(2 * 16, 0.f);
+        verts[0] = 48.f; verts[1] = 40.f;
+        int nv = 1, fc = 1;
+        for (int it = 0; it < 3; it++) orc_streakline_step_lk_ex(verts.data(), &nv, 48.f, 40.f, a.data(), w, b.data(), w, w, h, &fc, it & 1);
+        show("streakline lk", verts);
+    }
     printf("oracle_kat: ok\n");
     return 0;
 }

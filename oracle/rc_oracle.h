@@ -183,6 +183,14 @@ int orc_pyrlk(const uint8_t* prev, size_t prev_step, const uint8_t* next, size_t
               int h, const float* prev_pts, float* next_pts, int npts, uint8_t* status, float* err,
               int win_w, int win_h, int max_level, int crit_type, int max_count, double epsilon,
               int flags, double min_eig_threshold);
+/* The same with a switch: exact_sums != 0 accumulates A11, A12, A22, b1, b2 and the err residual in
+ * int64 and converts once to float before the FLT_SCALE multiply (what the device kernel does), so
+ * the result no longer depends on the summation order.  exact_sums == 0 is orc_pyrlk.  nthreads > 1
+ * splits the point list over threads; points are independent, so the result does not depend on it. */
+int orc_pyrlk_ex(const uint8_t* prev, size_t prev_step, const uint8_t* next, size_t next_step, int w,
+                 int h, const float* prev_pts, float* next_pts, int npts, uint8_t* status, float* err,
+                 int win_w, int win_h, int max_level, int crit_type, int max_count, double epsilon,
+                 int flags, double min_eig_threshold, int exact_sums, int nthreads);
 int orc_pyrlk_levels(int w, int h, int win_w, int win_h, int max_level);  /* last level actually used */
 int orc_pyrdown_u8(const uint8_t* src, size_t step, int w, int h, uint8_t* dst, size_t dst_step);
 int orc_scharr_deriv(const uint8_t* src, size_t step, int w, int h, int16_t* dxy);  /* h*w*2 (dx, dy) */
@@ -190,6 +198,9 @@ int orc_scharr_deriv(const uint8_t* src, size_t step, int w, int h, int16_t* dxy
 int orc_streakline_step_lk(float* verts, int* nverts, float gen_x, float gen_y, const uint8_t* prev,
                            size_t prev_step, const uint8_t* next, size_t next_step, int w, int h,
                            int* frame_count);
+int orc_streakline_step_lk_ex(float* verts, int* nverts, float gen_x, float gen_y, const uint8_t* prev,
+                              size_t prev_step, const uint8_t* next, size_t next_step, int w, int h,
+                              int* frame_count, int exact_sums);
 
 #ifdef __cplusplus
 }

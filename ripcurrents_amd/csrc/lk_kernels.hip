@@ -1,7 +1,8 @@
 // lk_kernels.hip -- sparse pyramidal Lucas-Kanade for gfx950.
 //
 // Replaces cv::calcOpticalFlowPyrLK at Streakline.cpp:32, ripcurrents_module.cpp:716, :738, :775,
-// :1162 (8UC1 images, <= a few hundred points).  Arithmetic follows OpenCV 4.1.0 lkpyramid.cpp:
+// :1162 (8UC1 images; a few hundred vertices at most of these, every pixel of a 640x480 frame, 307 200
+// points, at :716).  Arithmetic follows OpenCV 4.1.0 lkpyramid.cpp:
 // 8-bit pyramid by pyrDown (REFLECT_101), Scharr derivatives in int16, W_BITS = 14 fixed-point
 // bilinear weights, 2x2 system per point, <= maxCount Newton steps per level.  The window sums
 // are exact integers here (int64 partial sums, tree-reduced) where upstream adds floats in raster
@@ -209,8 +210,9 @@ __global__ __launch_bounds__(RC_LK_THREADS) void k_lk_track(RcLkArgs a) {
             }
             pdx = dx; pdy = dy;
         }
-        if (ok && level == 0 && !get_min_eig) {
-            // L1 residual of the final position (the err output without GET_MIN_EIGENVALS)
+        if (ok && a.err && level == 0 && !get_min_eig) {
+            // L1 residual of the final position (the err output without GET_MIN_EIGENVALS).  Upstream runs this
+            // pass, and the bounds test in it that can still clear the status, only when err is asked for.
             const float fx = nxt.x - halfx, fy = nxt.y - halfy;
             const int inx = rc_cvt_i32_x86(floorf(fx)), iny = rc_cvt_i32_x86(floorf(fy));
             if (inx < -win_w || inx >= L.w || iny < -win_h || iny >= L.h) {
@@ -348,7 +350,7 @@ extern "C" int rcflow_pyrlk_u8(rc_ctx* ctx, int stream, const uint8_t* prev, siz
     RC_HIP(hipMemcpyAsync(d, prev_pts, pts, hipMemcpyHostToDevice, s->cur));
     if (flags & 4) RC_HIP(hipMemcpyAsync(d + pts, next_pts, pts, hipMemcpyHostToDevice, s->cur));
     rc = rcflow_pyrlk_dev(ctx, stream, d_img, w, d_img + img, w, w, h, (const float*)d, (float*)(d + pts), npts,
-                          (uint8_t*)(d + 2 * pts + (size_t)npts * 4), (float*)(d + 2 * pts), win_w, win_h, max_level,
+                          (uint8_t*)(d + 2 * pts + (size_t)npts * 4), err ? (float*)(d + 2 * pts) : nullptr, win_w, win_h, max_level,
                           crit_type, max_count, epsilon, flags, min_eig_threshold);
     if (rc) return rc;
     RC_HIP(hipMemcpyAsync(next_pts, d + pts, pts, hipMemcpyDeviceToHost, s->cur));

@@ -21,7 +21,26 @@ from oracle import oracle          # noqa: E402
 from ripcurrents_amd import synth  # noqa: E402
 
 
+def pyrlk_exact():
+    """Sparse PyrLK with order-free window sums (oracle.pyrlk(exact_sums=True)), which the device kernel and the
+    numpy restatement tests/_lk_ref.py both reproduce bit for bit: three window shapes, two criteria, the point
+    classes of tests/_lk_ref.py with initial estimates."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import _lk_ref as R
+    lk = synth.surf_clip(160, 120, 2, seed=78)
+    pts = R.point_classes(160, 120, (21, 21), 3)
+    guess = R.guesses(pts, 160, 120)
+    out = dict(prev=lk[0], next=lk[1], pts=pts, guess=guess)
+    for tag, win, eps, flags in R.GOLDEN_CASES:
+        with np.errstate(all="ignore"):
+            q, st, er = oracle.pyrlk(lk[0], lk[1], pts, next_pts=guess, win=win, max_level=3, epsilon=eps, flags=flags,
+                                     exact_sums=True)
+        out["next_" + tag], out["status_" + tag], out["err_" + tag] = q, st, er
+    np.savez_compressed(os.path.join(HERE, "pyrlk_exact_160x120.npz"), **out)
+
+
 def main():
+    pyrlk_exact()
     clip = synth.surf_clip(96, 80, 2, seed=1234)
     p = dict(pyr_scale=0.5, levels=2, winsize=3, iters=2, poly_n=15, poly_sigma=1.2, flags=0)
     # every Farneback fixture carries the conditioning of its pixels (determinant of the final solve, minimum along the

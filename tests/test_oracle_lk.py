@@ -38,6 +38,17 @@ def test_level_rule(orc):
     assert orc.pyrlk_levels(320, 240, (50, 50), 3) == 2       # 40x30 would be <= 50
     assert orc.pyrlk_levels(320, 240, (21, 21), 3) == 3
     assert orc.pyrlk_levels(64, 64, (50, 50), 3) == 0
+    # the sizes and windows of tests/test_lk_ref.py and tests/test_gpu_lk.py
+    assert orc.pyrlk_levels(333, 251, (21, 21), 7) == 3       # 21x16 would be <= 21
+    assert orc.pyrlk_levels(64, 48, (21, 21), 3) == 1         # 16x12
+    assert orc.pyrlk_levels(64, 48, (5, 9), 7) == 2           # 8x6: 6 <= 9
+    assert orc.pyrlk_levels(21, 17, (21, 21), 3) == 0 and orc.pyrlk_levels(16, 16, (21, 21), 7) == 0
+    assert orc.pyrlk_levels(5, 400, (3, 3), 7) == 0 and orc.pyrlk_levels(400, 5, (3, 3), 7) == 0     # (5 + 1) / 2 <= 3
+    assert orc.pyrlk_levels(1920, 1080, (21, 21), 7) == 5     # 30x17 would be <= 21
+    assert orc.pyrlk_levels(3840, 2160, (21, 21), 7) == 6
+    assert orc.pyrlk_levels(1920, 1080, (128, 128), 3) == 3   # level 3 is 240x135; 120x68 would end it there anyway
+    assert orc.pyrlk_levels(1920, 1080, (128, 128), 7) == 3
+    assert orc.pyrlk_levels(3840, 2160, (50, 50), 5) == 5 and orc.pyrlk_levels(640, 480, (21, 21), 0) == 0
 
 
 def test_translation_recovered(orc):
