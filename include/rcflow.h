@@ -532,6 +532,68 @@ int rcflow_rgb_to_hsv_u8_dev(rc_ctx* ctx, int stream, const uint8_t* d_rgb, size
 int rcflow_hsv_to_rgb_u8_dev(rc_ctx* ctx, int stream, const uint8_t* d_hsv, size_t hsv_step, int w, int h,
                              uint8_t* d_rgb, size_t step);
 
+/* ------------------------------------------------------------------ opposing-flow map
+ * Where does the water run against the waves?  averageVector (ripcurrents_module.cpp:386-484; its call is commented out at
+ * main_old.cpp:352) finished: a window mean of the flow field, a global direction, a grid of cells, and the cells whose
+ * summed mean vector points away from the global one.  One launch per push ("ripmap@0"; "ripmap@1" only for a mask),
+ * nothing synchronises.  Per pixel:
+ *   v      the flow (source 0, main.cpp:1142-1153), or get_delta from a zero point with dt = 2 and the slot's UPPER
+ *          (source 1, ripcurrents_module.cpp:395-397: rcflow_get_delta_field_dev's arithmetic; needs rcflow_analysis_reset);
+ *   mean   a = avg - slot * inv; slot = v; avg = a + v * inv, inv = 1 / window: the bits of a chain of
+ *          rcflow_window_mean_dev calls over a ring the library owns ([window][h][w rounded up to 2] float2);
+ *   sums   q = (int64)rint(avg * 65536) per component, added per cell with the cell's pixel count n; a pixel with a
+ *          component that is not finite or beyond 2^40 in |q| (2^24 px) is left out and counted as bad.  Integer sums do
+ *          not depend on the order of addition.  Cell of pixel (x, y): (min(x / (w / grid_x), grid_x - 1), likewise y):
+ *          the reference's integer cell size, the remainder columns and rows going to the last cell;
+ *   colour rcflow_vector_to_color_dev's triple of the mean, scaled by the PREVIOUS push's maximum |avg| (the first push:
+ *          the reference's 1e-6); this push's maximum stays on the device for the next one.
+ * Then the launch's last-arriving workgroup: G = the sum of all cells' (Sx, Sy); for every cell, in double, each
+ * operation rounded on its own: dot = Sx*Gx + Sy*Gy, cc = Sx*Sx + Sy*Sy, gg = Gx*Gx + Gy*Gy;
+ *   opposed  iff  n > 0 && dot < 0 && dot*dot > K*(cc*gg) && cc >= ((M*65536)*n)^2
+ * K = min_opposition_cos2 (default 0.3454915028125263 = cos^2(0.7 pi), ripcurrents_module.cpp:471), M = min_cell_mag
+ * (px, default 0: off).
+ *   cells    grid_y x grid_x x (mean x, mean y, angle to G in degrees [0, 180], opposed ? 1 : 0) floats,
+ *            means as (float)((double)S / 65536 / n), zeros for an empty cell;
+ *   summary  8 doubles: direction of G in degrees [0, 360), |mean of the frame| in px, opposed cells, cells with n > 0,
+ *            bad pixels, frames pushed, this push's maximum |avg|, 0.
+ * Angles are atan2 in double and for people (tolerance 1e-9 degrees); no decision depends on them.  While fewer than
+ * `window` fields have been pushed the mean is a partial one (zeros in the unfilled slots, as the reference's);
+ * RC_RIPMAP_WAIT_FULL holds every cell at "not opposed" until the ring is full.
+ * THE RING IS window * h * w * 8 BYTES: 5 GB for the reference's 300 fields at 1080p, 0.74 GB at 640 x 480. */
+#define RC_RIPMAP_WAIT_FULL 1      /* flags bit 0 */
+#define RC_RIPMAP_MAX_CELLS 16384
+/* Opens the slot's map for w x h fields.  Allocates everything it will ever need (RC_ENOMEM with the byte count in
+ * rcflow_last_error if it does not fit); re-opening replaces the state, a refused open leaves it as it was.  RC_EINVAL:
+ * window outside 1..4096, a grid below 1 x 1, wider or higher than the frame (w < grid_x, h < grid_y) or beyond
+ * RC_RIPMAP_MAX_CELLS cells, source other than 0 / 1, unknown flag bits; RC_ESIZE beyond the context's max_w x max_h.
+ * Zeroed asynchronously on the stream the slot has at this call; stream rules as rcflow_timex_open. */
+int rcflow_ripmap_open(rc_ctx* ctx, int stream, int w, int h, int window, int grid_x, int grid_y, int source, int flags);
+/* One field.  d_flow_xy: CV_32FC2 of the opened size (flow_step a multiple of 8), or NULL: the field the slot's frame
+ * loop left resident (rcflow_stream_flow_ptr: after rcflow_push_frame_u8 / _acquired / rcflow_frame_loop_step; RC_ESTATE
+ * when there is none, RC_ESIZE when it has another size).
+ * Each output may be NULL: d_hsv 8UC3 (h x w), d_mask h x w bytes, 255 inside an opposed cell (what
+ * rcflow_create_edges_dev / rcflow_create_output_dev take; costs the second launch), d_cells and d_summary as above.
+ * The state is updated whatever is asked for.  RC_ESTATE before rcflow_ripmap_open; a refused push changes nothing. */
+int rcflow_ripmap_push_dev(rc_ctx* ctx, int stream, const float* d_flow_xy, size_t flow_step, uint8_t* d_hsv,
+                           size_t hsv_step, uint8_t* d_mask, size_t mask_step, float* d_cells, double* d_summary);
+/* Copies the window mean as it stands (CV_32FC2, mean_step >= 8 * w) to device memory, asynchronously on the slot's
+ * stream: the field rcflow_vector_to_color_dev, rcflow_subtract_average_dev ... take. */
+int rcflow_ripmap_mean_dev(rc_ctx* ctx, int stream, float* d_mean_xy, size_t mean_step);
+/* Blocks until the slot's stream has finished; for hosts and tests.  cells, summary as above; sums: grid_y x grid_x x
+ * (Sx, Sy, n) int64 of the last push.  Any pointer may be NULL.  Before the first push: zeros. */
+int rcflow_ripmap_read(rc_ctx* ctx, int stream, float* cells, double* summary, long long* sums, long long* frames_pushed);
+/* the decision's two numbers, from the next push on.  RC_EINVAL unless 0 <= min_opposition_cos2 < 1 and
+ * 0 <= min_cell_mag < 1e6; open restores the defaults, reset keeps what was set. */
+int rcflow_ripmap_set(rc_ctx* ctx, int stream, double min_opposition_cos2, double min_cell_mag);
+/* zeroes ring, mean, maximum and frame count; keeps the allocation and what rcflow_ripmap_set set */
+int rcflow_ripmap_reset(rc_ctx* ctx, int stream);
+/* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
+int rcflow_ripmap_close(rc_ctx* ctx, int stream);
+/* any pointer may be NULL; device_bytes = everything the state holds on the device.  RC_ESTATE when nothing is open. */
+int rcflow_ripmap_info(rc_ctx* ctx, int stream, int* w, int* h, int* window, int* grid_x, int* grid_y, int* source,
+                       int* flags, double* min_opposition_cos2, double* min_cell_mag, long long* frames_pushed,
+                       size_t* device_bytes);
+
 /* Display path, ripcurrents.cpp:233-273 (= streamline_displacement / _total_motion / _ratio /
  * _positions, ripcurrents_module.cpp:13-60) on the slot's streamline field (rcflow_advect_field_dev):
  * which 0 = |pt|, 1 = dist, 2 = |pt| / dist; minMaxLoc + convertTo(CV_8UC1, 255/max) +
@@ -612,7 +674,7 @@ int rcflow_profile_read(rc_ctx* ctx, int cap, const char** names, int* launches,
 
 /* The same totals under the reference's own bucket names, in the order it prints them (ripcurrents.cpp:103-109,
  * :518-524): farneback, polar, threshold, overlay, erosion, codec, stream ("pathlines").  GPU time of the kernels
- * that do each bucket's work ("overlay" includes the time-exposure images and the 8-bit colour stages, "farneback" the frame stabilisation); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
+ * that do each bucket's work ("overlay" includes the time-exposure images and the 8-bit colour stages, "farneback" the frame stabilisation and the opposing-flow map); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
  * classification kernels, booked under "threshold"), "codec" is 0 (video decode is host I/O outside the library).
  * names / ms: RC_PROFILE_BUCKETS entries each (either may be NULL).  Returns RC_PROFILE_BUCKETS. */
 #define RC_PROFILE_BUCKETS 7

@@ -15,6 +15,7 @@
 //   timexOpen / timexPush      compute_timex main.cpp:1195-1263, compute_brightColor main.cpp:1265-1383
 //   framestabOpen / framestabPush   compute_phaseCorrelate main.cpp:1684-1775
 //   framestabOpenMulti, warpAffine, warpPerspective   the correction of stabilize (main.cpp:1556-1682) by that estimator
+//   RipMap                     averageVector ripcurrents_module.cpp:386-484, finished (the opposing-flow map)
 // rc::Mat is a non-owning view with cv::Mat's fields (data, step, rows, cols); with OpenCV
 // present, include/rcflow_cv.hpp converts cv::Mat to it.  Errors are thrown as
 // rc::Error (the reference's OpenCV calls throw cv::Exception and are never caught).
@@ -22,6 +23,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <stdexcept>
@@ -509,6 +511,79 @@ class PopulationMap {
         pipe.calcOpticalFlowPyrLK(u_prev, u_current, vertices, next, status, err, 50, 50, 3, 3, 30, 0.1, 10, 1e-4);
         vertices = next;
     }
+};
+
+// The opposing-flow map (rcflow_ripmap_*): averageVector (ripcurrents.hpp, ripcurrents_module.cpp:386-484) finished.  Works
+// on the flow field resident in the pipeline: push() after calcOpticalFlowFarneback / pushFrame / loopStep, or
+// push(flow) with a host field.  One launch per push, nothing waits until read().
+class RipMap {
+  public:
+    struct Cell { float mean_x, mean_y, angle, opposed; };
+    struct Result {
+        std::vector<Cell> cells;            // grid_y x grid_x
+        std::vector<long long> sums;        // grid_y x grid_x x (Sx, Sy, n)
+        double direction = 0, mean_magnitude = 0, max_magnitude = 0;
+        long long opposed_cells = 0, live_cells = 0, bad_pixels = 0, frames_pushed = 0;
+        int grid_x = 0, grid_y = 0;
+        bool opposed(int cx, int cy) const { return cells[(size_t)cy * grid_x + cx].opposed != 0.f; }
+    };
+
+    RipMap(Pipeline& pipe, int window = 300, int grid_x = 30, int grid_y = 30, int source = 0, int flags = 0)
+        : pipe_(pipe), gx_(grid_x), gy_(grid_y) {
+        check(rcflow_ripmap_open(pipe.context(), 0, pipe.width(), pipe.height(), window, grid_x, grid_y, source, flags));
+    }
+    ~RipMap() {
+        (void)rcflow_ripmap_close(pipe_.context(), 0);
+        if (d_field_) (void)hipFree(d_field_);
+    }
+    RipMap(const RipMap&) = delete;
+    RipMap& operator=(const RipMap&) = delete;
+
+    void set(double min_opposition_cos2, double min_cell_mag) {
+        check(rcflow_ripmap_set(pipe_.context(), 0, min_opposition_cos2, min_cell_mag));
+    }
+    // the pipeline's resident flow field
+    void push() { check(rcflow_ripmap_push_dev(pipe_.context(), 0, pipe_.device_flow(), (size_t)pipe_.width() * 8, nullptr, 0, nullptr, 0, nullptr, nullptr)); }
+    // a host field (CV_32FC2 of the pipeline's size)
+    void push(const Mat& flow) {
+        const int w = pipe_.width(), h = pipe_.height();
+        if (flow.empty() || flow.rows != h || flow.cols != w || flow.channels != 2 || flow.elem != 4)
+            throw Error(RC_EINVAL, "RipMap::push: flow must be CV_32FC2 of the pipeline's size");
+        if (!d_field_) hip_check(hipMalloc(&d_field_, (size_t)w * h * 8), "hipMalloc field");
+        check(rcflow_sync(pipe_.context(), 0));                  // the last push may still be reading the staging field
+        hip_check(hipMemcpy2D(d_field_, (size_t)w * 8, flow.data, flow.step, (size_t)w * 8, h, hipMemcpyHostToDevice), "upload field");
+        check(rcflow_ripmap_push_dev(pipe_.context(), 0, (const float*)d_field_, (size_t)w * 8, nullptr, 0, nullptr, 0, nullptr, nullptr));
+    }
+    // waits for the pipeline's stream
+    Result read() {
+        Result r;
+        r.grid_x = gx_; r.grid_y = gy_;
+        r.cells.resize((size_t)gx_ * gy_);
+        r.sums.resize((size_t)gx_ * gy_ * 3);
+        double s[8];
+        check(rcflow_ripmap_read(pipe_.context(), 0, (float*)r.cells.data(), s, r.sums.data(), &r.frames_pushed));
+        r.direction = s[0]; r.mean_magnitude = s[1]; r.opposed_cells = (long long)s[2]; r.live_cells = (long long)s[3];
+        r.bad_pixels = (long long)s[4]; r.max_magnitude = s[6];
+        return r;
+    }
+    // 8UC1 of the frame size, 255 inside the cells the last push found opposed: what create_edges / create_output take
+    void mask(Mat& m) {
+        const int w = pipe_.width(), h = pipe_.height();
+        if (m.empty() || m.rows != h || m.cols != w || m.channels != 1 || m.elem != 1)
+            throw Error(RC_EINVAL, "RipMap::mask: the mask must be 8UC1 of the pipeline's size");
+        Result r = read();
+        for (int y = 0; y < h; y++) {
+            unsigned char* row = (unsigned char*)m.data + (size_t)y * m.step;
+            const int cy = std::min(y / (h / gy_), gy_ - 1);
+            for (int x = 0; x < w; x++) row[x] = r.opposed(std::min(x / (w / gx_), gx_ - 1), cy) ? 255 : 0;
+        }
+    }
+    void reset() { check(rcflow_ripmap_reset(pipe_.context(), 0)); }
+
+  private:
+    Pipeline& pipe_;
+    int gx_, gy_;
+    void* d_field_ = nullptr;
 };
 
 }  // namespace rc

@@ -23,6 +23,9 @@ RC_WARP_INVERSE_MAP = 16
 STAB_MODELS = {"translation": 1, "similarity": 2, "affine": 3}
 RC_STAB_ANCHOR_FIRST = 1
 RC_STAB_MAX_PATCHES = 16
+# rcflow_ripmap_open: its one flag, and the source names
+RC_RIPMAP_WAIT_FULL = 1
+RIPMAP_SOURCES = {"flow": 0, "delta": 1}
 
 ERRORS = {-1: "RC_EINVAL", -2: "RC_ENOMEM", -3: "RC_EHIP", -4: "RC_ENODEV", -5: "RC_ESIZE",
           -6: "RC_ESTATE", -7: "RC_ECOMM"}
@@ -128,6 +131,15 @@ SIGNATURES = {
     "rcflow_timex_close": [_vp, _i],
     "rcflow_timex_info": [_vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_longlong),
                           C.POINTER(_sz)],
+    "rcflow_ripmap_open": [_vp, _i, _i, _i, _i, _i, _i, _i, _i],
+    "rcflow_ripmap_push_dev": [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp],
+    "rcflow_ripmap_mean_dev": [_vp, _i, _vp, _sz],
+    "rcflow_ripmap_read": [_vp, _i, _vp, _vp, _vp, C.POINTER(C.c_longlong)],
+    "rcflow_ripmap_set": [_vp, _i, _d, _d],
+    "rcflow_ripmap_reset": [_vp, _i],
+    "rcflow_ripmap_close": [_vp, _i],
+    "rcflow_ripmap_info": [_vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
+                           C.POINTER(_i), C.POINTER(_d), C.POINTER(_d), C.POINTER(C.c_longlong), C.POINTER(_sz)],
     "rcflow_rgb_to_hsv_u8_dev": [_vp, _i, _vp, _sz, _i, _i, _vp, _sz],
     "rcflow_hsv_to_rgb_u8_dev": [_vp, _i, _vp, _sz, _i, _i, _vp, _sz],
     "rcflow_streamline_display_dev": [_vp, _i, _i, _vp, _sz, C.POINTER(_f)],

@@ -13,6 +13,7 @@ Names, argument order and meaning follow the reference (paths relative to
   subtructAverage / subtructMeanMagnitude / stabilizer / vectorToColor / shearRateToColor
   timex_*                    compute_timex main.cpp:1195-1263, compute_brightColor main.cpp:1265-1383
   framestab_*                compute_phaseCorrelate main.cpp:1684-1775 (phase_correlate, warp_translate: its stages)
+  ripmap_*                   averageVector ripcurrents_module.cpp:386-484, finished (the opposing-flow map)
 
 torch is used for device memory and streams only; all compute is in the HIP library.
 Arrays cross this layer as torch CUDA tensors (zero copy) or numpy arrays (copied).
@@ -25,6 +26,7 @@ import torch
 from . import _lib
 from ._lib import FarnebackParams, HIST_BINS, HIST_DIRECTIONS, HIST_WORDS, RC_FARNEBACK_USE_INITIAL_FLOW, TIMEX_PRODUCTS, RcflowError, check
 from ._lib import RC_STAB_ANCHOR_FIRST, RC_STAB_MAX_PATCHES, RC_WARP_INVERSE_MAP, STAB_MODELS
+from ._lib import RC_RIPMAP_WAIT_FULL, RIPMAP_SOURCES
 
 __all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState"]
 
@@ -886,6 +888,105 @@ class Context:
     def framestab_close(self, stream=0):
         self._bind(stream)          # waits for the pushes queued on that stream before freeing
         check(self._lib.rcflow_framestab_close(self._h, stream))
+
+    # ------------------------------------------------------------------ the opposing-flow map
+    def ripmap_open(self, w, h, window=300, grid=(30, 30), source="flow", wait_full=False, stream=0):
+        """Opens the slot's opposing-flow map (averageVector, ripcurrents_module.cpp:386-484, finished) for w x h flow
+        fields: a mean over the last `window` fields, summed per cell of a grid = (grid_x, grid_y), and the cells whose
+        summed mean points away from the frame's.  source "flow": the field as it is; "delta": get_delta from a zero point
+        with dt = 2 and the slot's UPPER.  wait_full: no cell is opposed until `window` fields have been pushed.
+        The ring takes window * h * w * 8 bytes of device memory."""
+        if source not in RIPMAP_SOURCES:
+            raise ValueError("source must be one of %s" % sorted(RIPMAP_SOURCES))
+        self._bind(stream)          # the state is zeroed on the slot's stream: the one the pushes will run on
+        check(self._lib.rcflow_ripmap_open(self._h, stream, int(w), int(h), int(window), int(grid[0]), int(grid[1]),
+                                           RIPMAP_SOURCES[source], RC_RIPMAP_WAIT_FULL if wait_full else 0))
+
+    def ripmap_info(self, stream=0):
+        """dict(w, h, window, grid, source, wait_full, min_opposition_cos2, min_cell_mag, frames_pushed, device_bytes)."""
+        v = [C.c_int(0) for _ in range(7)]
+        k, m = C.c_double(0.), C.c_double(0.)
+        frames, nbytes = C.c_longlong(0), C.c_size_t(0)
+        check(self._lib.rcflow_ripmap_info(self._h, stream, *[C.byref(x) for x in v], C.byref(k), C.byref(m), C.byref(frames),
+                                           C.byref(nbytes)))
+        w, h, window, gx, gy, source, flags = (x.value for x in v)
+        return dict(w=w, h=h, window=window, grid=(gx, gy), source={b: a for a, b in RIPMAP_SOURCES.items()}[source],
+                    wait_full=bool(flags & RC_RIPMAP_WAIT_FULL), min_opposition_cos2=k.value, min_cell_mag=m.value,
+                    frames_pushed=frames.value, device_bytes=nbytes.value)
+
+    def ripmap_set(self, min_opposition_cos2=0.3454915028125263, min_cell_mag=0.0, stream=0):
+        """The decision's numbers: a cell is opposed when cos^2 of its angle to the frame's direction exceeds
+        min_opposition_cos2 on the far side (default: 0.7 pi, the reference's) and its mean is at least min_cell_mag px."""
+        check(self._lib.rcflow_ripmap_set(self._h, stream, float(min_opposition_cos2), float(min_cell_mag)))
+
+    def ripmap_push(self, flow=None, hsv=None, mask=None, cells=None, summary=None, stream=0):
+        """One flow field (HxWx2 float32, pixels dense, rows may be padded; None: the field push_frame_host / frame_loop_step
+        left on the slot).
+        Outputs are preallocated device tensors, each optional: hsv HxWx3 uint8 (vectorToColor of the mean, scaled by the
+        previous push's maximum), mask HxW uint8 (255 inside an opposed cell), cells grid_y x grid_x x 4 float32
+        (mean x, mean y, angle to the frame's direction, opposed), summary 8 float64.  Nothing is synchronised."""
+        info = self.ripmap_info(stream)
+        h, w, (gx, gy) = info["h"], info["w"], info["grid"]
+        fp, fstep = C.c_void_p(None), 0
+        if flow is not None:
+            flow = self._dev(flow, torch.float32)
+            if flow.dim() != 3 or tuple(flow.shape) != (h, w, 2) or flow.stride(2) != 1 or flow.stride(1) != 2:
+                raise ValueError("flow must be %dx%dx2 float32 with dense pixels, as opened" % (h, w))
+            fp, fstep = self._ptr(flow), flow.stride(0) * 4
+        hp, hstep, mp, mstep, cp, sp = C.c_void_p(None), 0, C.c_void_p(None), 0, C.c_void_p(None), C.c_void_p(None)
+        if hsv is not None:
+            self._check_out3(hsv, (h, w, 3), "hsv")
+            hp, hstep = self._ptr(hsv), hsv.stride(0)
+        if mask is not None:
+            if not _is_t(mask) or not mask.is_cuda or mask.dtype != torch.uint8 or tuple(mask.shape) != (h, w) or mask.stride(1) != 1:
+                raise ValueError("mask must be a %dx%d uint8 device tensor with dense rows" % (h, w))
+            mp, mstep = self._ptr(mask), mask.stride(0)
+        if cells is not None:
+            if not _is_t(cells) or not cells.is_cuda or cells.dtype != torch.float32 or tuple(cells.shape) != (gy, gx, 4) \
+                    or not cells.is_contiguous():
+                raise ValueError("cells must be a contiguous %dx%dx4 float32 device tensor" % (gy, gx))
+            cp = self._ptr(cells)
+        if summary is not None:
+            if not _is_t(summary) or not summary.is_cuda or summary.dtype != torch.float64 or summary.numel() != 8 \
+                    or not summary.is_contiguous():
+                raise ValueError("summary must be a contiguous float64 device tensor of 8")
+            sp = self._ptr(summary)
+        self._bind(stream)
+        check(self._lib.rcflow_ripmap_push_dev(self._h, stream, fp, fstep, hp, hstep, mp, mstep, cp, sp))
+
+    def ripmap_mean(self, out=None, stream=0):
+        """The window mean as it stands -> HxWx2 float32 device tensor (a copy, queued on the slot's stream)."""
+        info = self.ripmap_info(stream)
+        if out is None:
+            out = torch.empty((info["h"], info["w"], 2), dtype=torch.float32, device=self.device)
+        elif not _is_t(out) or not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (info["h"], info["w"], 2) \
+                or out.stride(2) != 1 or out.stride(1) != 2:
+            raise ValueError("out must be a %dx%dx2 float32 device tensor with dense pixels" % (info["h"], info["w"]))
+        self._bind(stream)
+        check(self._lib.rcflow_ripmap_mean_dev(self._h, stream, self._ptr(out), out.stride(0) * 4))
+        return out
+
+    def ripmap_read(self, stream=0):
+        """Waits for the slot's stream -> dict(cells (grid_y x grid_x x 4 float32), opposed (bool grid), summary (8 float64),
+        direction, mean_magnitude, opposed_cells, live_cells, bad_pixels, max_magnitude, sums (grid_y x grid_x x 3 int64:
+        Sx, Sy, n), frames_pushed) of the last push."""
+        gx, gy = self.ripmap_info(stream)["grid"]
+        cells, summary = np.zeros((gy, gx, 4), np.float32), np.zeros(8, np.float64)
+        sums, frames = np.zeros((gy, gx, 3), np.int64), C.c_longlong(0)
+        self._bind(stream)
+        check(self._lib.rcflow_ripmap_read(self._h, stream, cells.ctypes.data, summary.ctypes.data, sums.ctypes.data,
+                                           C.byref(frames)))
+        return dict(cells=cells, opposed=cells[..., 3] != 0, summary=summary, direction=summary[0], mean_magnitude=summary[1],
+                    opposed_cells=int(summary[2]), live_cells=int(summary[3]), bad_pixels=int(summary[4]),
+                    max_magnitude=summary[6], sums=sums, frames_pushed=frames.value)
+
+    def ripmap_reset(self, stream=0):
+        self._bind(stream)
+        check(self._lib.rcflow_ripmap_reset(self._h, stream))
+
+    def ripmap_close(self, stream=0):
+        self._bind(stream)          # waits for the pushes queued on that stream before freeing
+        check(self._lib.rcflow_ripmap_close(self._h, stream))
 
     def _an_size(self, stream):
         w, h = C.c_int(0), C.c_int(0)

@@ -54,10 +54,6 @@ __device__ __forceinline__ int rc_dir_index(float angle) {
     return d;
 }
 
-__device__ __forceinline__ const float2* rc_row2(const float* base, size_t step, int y) {
-    return (const float2*)((const char*)base + (size_t)y * step);
-}
-
 // ============================================================================ B1+B2 histogram
 // Block-private hist2d[36][50] in LDS; hist, histsum and histsum2d are its marginals and
 // are formed when the block flushes.  Flow fields are smooth, so most lanes of a wave
@@ -414,21 +410,6 @@ __global__ __launch_bounds__(RC_BLOCK) void k_classify_accumulate(ClassifyArgs a
 }
 
 // ============================================================================ B4/B5 advection
-// Bilinear sampler shared by every streamline variant (ripcurrents_module.cpp:494-508).
-__device__ __forceinline__ bool rc_sample_flow(const float* flow, size_t step, int w, int h, float x, float y,
-                                               float& dx, float& dy) {
-    int xind = rc_cvt_i32_x86(floorf(x)), yind = rc_cvt_i32_x86(floorf(y));
-    float xrem = x - xind, yrem = y - yind;
-    if (xind < 1 || yind < 1 || xind + 2 > w || yind + 2 > h) return false;
-    const float2* r0 = rc_row2(flow, step, yind) + xind;
-    const float2* r1 = rc_row2(flow, step, yind + 1) + xind;
-    float2 p00 = r0[0], p01 = r0[1], p10 = r1[0], p11 = r1[1];
-    float wa = 1 - xrem, wb = 1 - yrem;
-    dx = p00.x * wa * wb + p01.x * xrem * wb + p10.x * wa * yrem + p11.x * xrem * yrem;
-    dy = p00.y * wa * wb + p01.y * xrem * wb + p10.y * wa * yrem + p11.y * xrem * yrem;
-    return true;
-}
-
 __global__ __launch_bounds__(RC_BLOCK) void k_advect_field(float2* pt, float* dist, const float* flow,
                                                            size_t step, int w, int h, float dt, int iterations,
                                                            float UPPER_arg, const float* thr) {
@@ -589,14 +570,6 @@ __global__ void k_window_mean(float* avg, float* slot, const float* cur, size_t 
 }
 
 // ============================================================================ B8 colouring
-// `uchar = float` as x86 compiles it: cvttss2si then the low byte (NaN/overflow -> INT_MIN).
-__device__ __forceinline__ uint8_t rc_f2u8(float v) {
-    int iv;
-    if (!(v > -2147483904.f && v < 2147483648.f)) iv = INT_MIN;
-    else iv = (int)v;
-    return (uint8_t)(iv & 0xFF);
-}
-
 __global__ __launch_bounds__(RC_BLOCK) void k_vector_to_color(const float* flow, size_t step, int w, int h,
                                                               uint8_t* hsv, size_t hsv_step, float max_disp) {
     const long long total = (long long)w * h;

@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 
 #include "../../include/rcflow.h"
@@ -18,6 +19,34 @@
 // for the x86 result (x < 1 || x + 2 > w) then reject such positions instead of letting them through.
 __device__ __forceinline__ int rc_cvt_i32_x86(float v) {
     return (v >= -2147483648.f && v < 2147483648.f) ? (int)v : (int)0x80000000;
+}
+
+// helpers the analysis kernels share (analysis_kernels.hip, ripmap_kernels.hip)
+__device__ __forceinline__ const float2* rc_row2(const float* base, size_t step, int y) {
+    return (const float2*)((const char*)base + (size_t)y * step);
+}
+
+// Bilinear sampler shared by every streamline variant (ripcurrents_module.cpp:494-508).
+__device__ __forceinline__ bool rc_sample_flow(const float* flow, size_t step, int w, int h, float x, float y,
+                                               float& dx, float& dy) {
+    int xind = rc_cvt_i32_x86(floorf(x)), yind = rc_cvt_i32_x86(floorf(y));
+    float xrem = x - xind, yrem = y - yind;
+    if (xind < 1 || yind < 1 || xind + 2 > w || yind + 2 > h) return false;
+    const float2* r0 = rc_row2(flow, step, yind) + xind;
+    const float2* r1 = rc_row2(flow, step, yind + 1) + xind;
+    float2 p00 = r0[0], p01 = r0[1], p10 = r1[0], p11 = r1[1];
+    float wa = 1 - xrem, wb = 1 - yrem;
+    dx = p00.x * wa * wb + p01.x * xrem * wb + p10.x * wa * yrem + p11.x * xrem * yrem;
+    dy = p00.y * wa * wb + p01.y * xrem * wb + p10.y * wa * yrem + p11.y * xrem * yrem;
+    return true;
+}
+
+// `uchar = float` as x86 compiles it: cvttss2si then the low byte (NaN/overflow -> INT_MIN).
+__device__ __forceinline__ uint8_t rc_f2u8(float v) {
+    int iv;
+    if (!(v > -2147483904.f && v < 2147483648.f)) iv = INT_MIN;
+    else iv = (int)v;
+    return (uint8_t)(iv & 0xFF);
 }
 
 // Geometry and constants of one pyramid scale.

@@ -88,6 +88,26 @@ struct RcFrameStab {
 enum { RC_FS_RESULT = 0 /* 3 */, RC_FS_MOTION = 3 /* 6 */, RC_FS_USED = 9 /* int model_used, patches_used */,
        RC_FS_TICKET = 10 /* unsigned arrivals of the running correlate launch */, RC_FS_SHIFTS = 16 /* n x 3 */ };
 
+// Opposing-flow map of one stream slot (ripmap_kernels.hip; averageVector, ripcurrents_module.cpp:386-484).  Everything is
+// allocated by rcflow_ripmap_open and released by rcflow_ripmap_close / rcflow_destroy.
+struct RcRipMap {
+    bool open = false;
+    int w = 0, h = 0, window = 0, gx = 0, gy = 0, source = 0, flags = 0;
+    int pitch = 0;            // row pitch of ring and mean in pixels (w rounded up to 2: 16-byte rows)
+    int cur = 0;              // ring slot the next field goes to
+    long long frames = 0;     // fields pushed since open / reset
+    double K = 0.3454915028125263;   // min_opposition_cos2: cos^2(0.7 pi), ripcurrents_module.cpp:471
+    double M = 0.;            // min_cell_mag
+    RcBuf ring;               // [window][h][pitch] float2
+    RcBuf avg;                // [h][pitch] float2: the window mean
+    RcBuf acc;                // RmCtl | [gy][gx][Sx, Sy, n] int64, zero between launches
+    RcBuf out;                // the last push: cells [cells] float4 | sums [cells][3] int64 | summary 8 doubles
+    // zeroed asynchronously by open / reset on the stream the slot had then, as RcTimex
+    hipEvent_t zeroed = nullptr;
+    hipStream_t zero_stream = nullptr;
+    bool zero_pending = false;
+};
+
 // warp_kernels.hip: one launch of the affine / perspective warp
 struct RcWarpArgs {
     const uint8_t* src; size_t step;
@@ -159,6 +179,7 @@ struct RcSlot {
     RcAnalysis an;
     RcTimex tx;
     RcFrameStab fs;
+    RcRipMap rm;
     RcPhaseCorr pc;
 };
 
@@ -202,7 +223,8 @@ enum { RC_K_PYR = 0, RC_K_POLY = 1, RC_K_ITER = 2, RC_K_HIST = 3, RC_K_THRESH = 
        RC_K_TIMEX = 17 /* @0 mean, @1 ring products */, RC_K_COLOR_U8 = 18 /* @0 rgb_to_hsv, @1 hsv_to_rgb, @2 resize_bgr, @3 resize_area_bgr */,
        RC_K_FRAMESTAB = 19 /* @0 correlate in one workgroup, @1 warp, @2..6 the correlate passes as launches of their own,
                               @7 multi-patch correlate + fit, @8 affine warp, @9 perspective warp */,
-       RC_K_KINDS = 20 };
+       RC_K_RIPMAP = 20 /* @0 ring, mean, cell sums, colour and the finish, @1 mask */,
+       RC_K_KINDS = 21 };
 
 void rc_set_error(const char* fmt, ...);
 int rc_buf_ensure(RcBuf& b, size_t bytes);
@@ -223,6 +245,8 @@ void rc_area_tab(int ssize, int dsize, double scale, std::vector<int>& start, st
 void rc_timex_free(RcSlot& s);
 // stab_kernels.hip
 void rc_framestab_free(RcSlot& s);
+// ripmap_kernels.hip
+void rc_ripmap_free(RcSlot& s);
 // warp_kernels.hip
 void rc_warp_launch(rc_ctx* ctx, hipStream_t cur, RcWarpArgs& a, bool perspective);
 // initial_flow_kernels.hip

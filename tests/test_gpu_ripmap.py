@@ -1,0 +1,349 @@
+"""The opposing-flow map on the device (ripmap_kernels.hip) against its numpy statement (tests/_ripmap_ref.py), after every
+push: mean, sums, counts, flags and mask bit for bit; cell means as floats; angles within 1e-9 degrees."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import _ripmap_ref as R
+from ripcurrents_amd import synth
+from ripcurrents_amd._lib import RcflowError
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EINVAL, ESIZE, ESTATE = -1, -5, -6
+f32 = np.float32
+
+
+def fields(w, h, n, seed=3, scale=2.0):
+    """n smooth flow fields with a slow drift plus noise, host float32."""
+    rng = np.random.RandomState(seed)
+    y, x = np.mgrid[0:h, 0:w].astype(f32)
+    out = []
+    for t in range(n):
+        fx = np.sin(x / 37.0 + 0.3 * t) + 0.5 * np.cos(y / 23.0) + 0.8
+        fy = 0.6 * np.cos(x / 41.0) - np.sin(y / 29.0 - 0.2 * t)
+        f = np.stack([fx, fy], -1).astype(f32) * f32(scale)
+        out.append(f + (rng.standard_normal((h, w, 2)) * 0.3).astype(f32))
+    return out
+
+
+def compare(got, want, hsv=None, mask=None, mean=None, what=""):
+    assert np.array_equal(got["sums"], want["sums"]), "sums differ " + what
+    assert got["bad_pixels"] == want["bad_pixels"] and got["frames_pushed"] == want["frames_pushed"], what
+    assert np.array_equal(got["opposed"], want["opposed"]), "flags differ " + what
+    assert got["opposed_cells"] == want["opposed_cells"] and got["live_cells"] == want["live_cells"], what
+    assert np.array_equal(got["cells"][..., :2], want["cells"][..., :2]), "cell means differ " + what
+    assert np.allclose(got["cells"][..., 2], want["cells"][..., 2], rtol=0, atol=2e-5), what     # float32 storage of an angle
+    assert abs(got["direction"] - want["direction"]) <= 1e-9, what
+    assert abs(got["mean_magnitude"] - want["mean_magnitude"]) <= 1e-12 * max(1.0, want["mean_magnitude"]), what
+    wm = want["max_magnitude"]
+    assert f32(got["max_magnitude"]) == wm or (np.isnan(wm) and np.isnan(got["max_magnitude"])), what
+    if mean is not None:
+        assert np.array_equal(mean.view(np.uint32), want["mean"].view(np.uint32)), "mean differs " + what
+    if mask is not None:
+        assert np.array_equal(mask, want["mask"]), "mask differs " + what
+    if hsv is not None:
+        assert np.array_equal(hsv, want["hsv"]), "colour differs " + what
+
+
+def run(ctx, flows, window, grid, stream=0, source="flow", wait_full=False, K=None, M=0.0, orc=None, pad=0, reopen=True,
+        check_mean=True, chain=True):
+    """Pushes the fields into the device session and the numpy one; compares after every push."""
+    h, w = flows[0].shape[:2]
+    if reopen:
+        ctx.ripmap_open(w, h, window, grid, source=source, wait_full=wait_full, stream=stream)
+        if K is not None or M:
+            ctx.ripmap_set(R.K_DEFAULT if K is None else K, M, stream=stream)
+    ref = R.RipMapRef(w, h, window, grid, source=1 if source == "delta" else 0, wait_full=wait_full,
+                      K=R.K_DEFAULT if K is None else K, M=M, color=orc.vector_to_color if orc else None)
+    hsv = torch.zeros((h, w, 3), dtype=torch.uint8, device="cuda") if orc else None
+    mask = torch.zeros((h, w), dtype=torch.uint8, device="cuda")
+    cells = torch.zeros((grid[1], grid[0], 4), dtype=torch.float32, device="cuda")
+    summary = torch.zeros(8, dtype=torch.float64, device="cuda")
+    # the chain of rcflow_window_mean_dev calls the mean must equal bit for bit
+    davg = torch.zeros((h, w, 2), dtype=torch.float32, device="cuda")
+    dring = torch.zeros((window, h, w, 2), dtype=torch.float32, device="cuda")
+    for t, f in enumerate(flows):
+        buf = torch.zeros((h, w + pad, 2), dtype=torch.float32, device="cuda")
+        buf[:, :w] = torch.as_tensor(f).cuda()
+        d = buf[:, :w]
+        ctx.ripmap_push(d, hsv=hsv, mask=mask, cells=cells, summary=summary, stream=stream)
+        got = ctx.ripmap_read(stream=stream)
+        want = ref.push(f)
+        mean = ctx.ripmap_mean(stream=stream).cpu().numpy() if check_mean else None
+        compare(got, want, hsv.cpu().numpy() if orc else None, mask.cpu().numpy(), mean, "after push %d" % (t + 1))
+        assert np.array_equal(cells.cpu().numpy(), got["cells"]) and np.array_equal(summary.cpu().numpy(), got["summary"])
+        if chain and source == "flow":
+            ctx.window_mean(davg, dring[t % window], d.contiguous(), window, stream=stream)
+            assert np.array_equal(davg.cpu().numpy().view(np.uint32), mean.view(np.uint32)), "chain differs after push %d" % (t + 1)
+    return ref
+
+
+# ---------------------------------------------------------------------------- the mean and the ring
+@pytest.mark.parametrize("window", [1, 3, 10])
+def test_mean_equals_chained_window_mean_with_ring_wrap(ctx, window):
+    run(ctx, fields(97, 61, 25), window, (7, 5))
+    ctx.ripmap_close()
+
+
+def test_sizes(ctx, orc):
+    run(ctx, fields(640, 480, 4), 3, (30, 30), orc=orc)
+    run(ctx, fields(33, 31, 4), 2, (30, 30), orc=orc)          # cells of one pixel: the block's footprint passes the LDS table
+    run(ctx, fields(64, 48, 4), 2, (1, 1), orc=orc)
+    run(ctx, fields(97, 61, 4), 2, (7, 5), orc=orc, pad=3)     # a padded flow_step, rows 8-byte aligned only
+    run(ctx, fields(130, 9, 3), 2, (4, 2), orc=orc)
+    ctx.ripmap_close()
+
+
+def test_1080p(ctx):
+    run(ctx, fields(1920, 1080, 5), 4, (30, 30), chain=False)
+    ctx.ripmap_close()
+
+
+def test_colour_equals_vector_to_color_fed_the_same_maxima(ctx):
+    w, h = 320, 240
+    flows = fields(w, h, 5, seed=9)
+    ctx.ripmap_open(w, h, 3, (8, 6))
+    hsv = torch.zeros((h, w, 3), dtype=torch.uint8, device="cuda")
+    scale = 1e-6
+    for f in flows:
+        ctx.ripmap_push(torch.as_tensor(f).cuda(), hsv=hsv)
+        want, new_scale = ctx.vectorToColor(ctx.ripmap_mean(), scale)
+        assert np.array_equal(hsv.cpu().numpy(), want.cpu().numpy())
+        assert ctx.ripmap_read()["max_magnitude"] == new_scale
+        scale = new_scale                                      # the scale lags one push
+    ctx.ripmap_close()
+
+
+def test_resident_flow_field(ctx):
+    w, h = 256, 192
+    clip = synth.surf_clip(w, h, 4)
+    ctx.stream_reset()
+    ctx.ripmap_open(w, h, 2, (8, 6))
+    ref = R.RipMapRef(w, h, 2, (8, 6))
+    with pytest.raises(RcflowError) as e:
+        ctx.ripmap_push(None)
+    assert e.value.code == ESTATE
+    for t in range(4):
+        flow = ctx.push_frame_host(clip[t])                    # the flow field stays on the slot
+        if flow is None:
+            continue
+        ctx.ripmap_push(None)
+        compare(ctx.ripmap_read(), ref.push(flow.cpu().numpy()), mean=ctx.ripmap_mean().cpu().numpy())
+    ctx.ripmap_open(128, 96, 2, (4, 4))
+    with pytest.raises(RcflowError) as e:
+        ctx.ripmap_push(None)
+    assert e.value.code == ESIZE
+    ctx.ripmap_close()
+    ctx.stream_reset()
+
+
+def test_source_delta_equals_get_delta_field_then_source_flow(ctx):
+    w, h = 97, 61
+    flows = fields(w, h, 4, seed=11, scale=30.0)
+    flows[1][20, 30] = (90, 90)                                # |v| > UPPER: stays zero
+    flows[2][10, 10] = (np.nan, 0)                             # poisons its left and upper neighbours' samples too
+    ctx.analysis_reset(w, h)
+    ctx.ripmap_open(w, h, 3, (7, 5), source="delta", stream=0)
+    ctx.ripmap_open(w, h, 3, (7, 5), source="flow", stream=1)
+    ref = R.RipMapRef(w, h, 3, (7, 5), source=1, UPPER=100.0)
+    for f in flows:
+        d = torch.as_tensor(f).cuda()
+        ctx.ripmap_push(d, stream=0)
+        delta = ctx.get_delta_field(torch.zeros((h, w, 2), dtype=torch.float32, device="cuda"), d, 2.0, -1.0)
+        assert np.array_equal(delta.cpu().numpy(), R.get_delta_zero(f, 100.0), equal_nan=True)
+        ctx.ripmap_push(delta, stream=1)
+        a, b = ctx.ripmap_read(stream=0), ctx.ripmap_read(stream=1)
+        assert np.array_equal(a["sums"], b["sums"]) and np.array_equal(a["cells"], b["cells"], equal_nan=True)
+        assert np.array_equal(ctx.ripmap_mean(stream=0).cpu().numpy().view(np.uint32), ctx.ripmap_mean(stream=1).cpu().numpy().view(np.uint32))
+        compare(a, ref.push(f))
+    ctx.ripmap_close(stream=0)
+    ctx.ripmap_close(stream=1)
+
+
+def test_bad_pixels_land_in_bad_and_nowhere_else(ctx):
+    w, h = 64, 48
+    f = np.zeros((h, w, 2), f32)
+    f[...] = (1.0, 0.5)
+    f[3, 5] = (np.nan, 0)
+    f[4, 6] = (0, -np.inf)
+    f[5, 7] = (1e9, 0)
+    f[6, 8] = (1e6, 0)
+    ref = run(ctx, [f], 1, (4, 4), check_mean=False, chain=False)
+    got = ctx.ripmap_read()
+    assert got["bad_pixels"] == 3 and got["sums"][..., 2].sum() == w * h - 3
+    assert got["sums"][0, 0, 0] == (12 * 16 - 4) * 65536 + 1000000 * 65536          # 1e6 px summed exactly
+    assert ref.frames == 1
+    ctx.ripmap_close()
+
+
+def test_min_cell_mag_fill_gate_and_reset(ctx):
+    w, h = 300, 240
+    f = np.zeros((h, w, 2), f32)
+    f[...] = (1.0, 0.0)
+    f[32:40, 20:40] = (-0.25, 0.0)
+    run(ctx, [f] * 4, 3, (30, 30), wait_full=True)
+    assert ctx.ripmap_read()["opposed_cells"] == 2
+    first = None
+    for M, n in ((0.25, 2), (0.26, 0)):
+        ctx.ripmap_set(min_cell_mag=M)
+        ctx.ripmap_reset()
+        assert ctx.ripmap_info()["min_cell_mag"] == M and ctx.ripmap_info()["frames_pushed"] == 0
+        for t in range(3):
+            ctx.ripmap_push(torch.as_tensor(f).cuda())
+            r = ctx.ripmap_read()
+            assert r["opposed_cells"] == (n if t == 2 else 0)
+            if t == 0:                                          # reset returns the first push's bits
+                assert first is None or (np.array_equal(first["sums"], r["sums"]) and first["max_magnitude"] == r["max_magnitude"])
+                first = first or r
+    with pytest.raises(RcflowError):
+        ctx.ripmap_set(min_opposition_cos2=1.0)
+    ctx.ripmap_close()
+
+
+def test_two_slots_and_a_moved_stream(ctx):
+    a, b = fields(97, 61, 6, seed=1), fields(130, 40, 6, seed=2)
+    ctx.ripmap_open(97, 61, 3, (7, 5), stream=0)
+    ctx.ripmap_open(130, 40, 2, (5, 4), stream=1)
+    ra, rb = R.RipMapRef(97, 61, 3, (7, 5)), R.RipMapRef(130, 40, 2, (5, 4))
+    s1 = torch.cuda.Stream()
+    for t in range(6):
+        ctx.ripmap_push(torch.as_tensor(a[t]).cuda(), stream=0)
+        with torch.cuda.stream(s1):
+            ctx.ripmap_push(torch.as_tensor(b[t]).cuda(), stream=1)
+        compare(ctx.ripmap_read(stream=0), ra.push(a[t]))
+        with torch.cuda.stream(s1):
+            compare(ctx.ripmap_read(stream=1), rb.push(b[t]))
+    ctx.ripmap_close(stream=1)
+    # opened (zeroed) on one stream, first pushed on another
+    big = fields(1920, 1080, 1, seed=4)[0]
+    ctx.ripmap_open(1920, 1080, 8, (30, 30), stream=0)
+    with torch.cuda.stream(torch.cuda.Stream()):
+        d = torch.as_tensor(big).cuda()
+        ctx.ripmap_push(d, stream=0)
+        compare(ctx.ripmap_read(stream=0), R.RipMapRef(1920, 1080, 8).push(big), mean=ctx.ripmap_mean(stream=0).cpu().numpy())
+    ctx.ripmap_close(stream=0)
+
+
+def test_refusals_leave_the_state_as_it_was(ctx):
+    w, h = 97, 61
+    ctx.ripmap_close()
+    with pytest.raises(RcflowError) as e:
+        ctx.ripmap_push(torch.zeros((h, w, 2), device="cuda"))
+    assert e.value.code == ESTATE
+    flows = fields(w, h, 3)
+    ref = run(ctx, flows[:2], 3, (7, 5))
+    lib, hd = ctx._lib, ctx._h
+    for args in ((w, h, 0, 7, 5, 0, 0), (w, h, 3, 98, 5, 0, 0), (w, h, 3, 7, 62, 0, 0), (w, h, 3, 0, 5, 0, 0),
+                 (w, h, 3, 7, 5, 2, 0), (w, h, 3, 7, 5, 0, 2), (0, h, 3, 7, 5, 0, 0)):
+        assert lib.rcflow_ripmap_open(hd, 0, *args) == EINVAL, args
+    assert lib.rcflow_ripmap_open(hd, 0, 4000, 61, 3, 7, 5, 0, 0) == ESIZE
+    d = torch.as_tensor(flows[2]).cuda()
+    hsv = torch.zeros((h, w, 3), dtype=torch.uint8, device="cuda")
+    p, z = C.c_void_p(d.data_ptr()), C.c_void_p(None)
+    assert lib.rcflow_ripmap_push_dev(hd, 0, p, w * 8 - 8, z, 0, z, 0, z, z) == EINVAL
+    assert lib.rcflow_ripmap_push_dev(hd, 0, p, w * 8 + 4, z, 0, z, 0, z, z) == EINVAL
+    assert lib.rcflow_ripmap_push_dev(hd, 0, p, w * 8, C.c_void_p(hsv.data_ptr()), 3 * w - 1, z, 0, z, z) == EINVAL
+    assert lib.rcflow_ripmap_push_dev(hd, 0, p, w * 8, z, 0, C.c_void_p(hsv.data_ptr()), w - 1, z, z) == EINVAL
+    assert lib.rcflow_ripmap_mean_dev(hd, 0, z, w * 8) == EINVAL
+    with pytest.raises(ValueError):
+        ctx.ripmap_push(torch.zeros((h, w + 1, 2), device="cuda"))
+    info = ctx.ripmap_info()
+    assert (info["w"], info["h"], info["window"], info["grid"], info["frames_pushed"]) == (w, h, 3, (7, 5), 2)
+    assert info["device_bytes"] >= 4 * 98 * 61 * 8
+    ctx.ripmap_push(d)                                          # the third push follows the second as if nothing had been tried
+    compare(ctx.ripmap_read(), ref.push(flows[2]), mean=ctx.ripmap_mean().cpu().numpy())
+    ctx.ripmap_close()
+    ctx.ripmap_close()                                          # nothing open: RC_OK
+    with pytest.raises(RcflowError) as e:
+        ctx.ripmap_read()
+    assert e.value.code == ESTATE
+
+
+# ---------------------------------------------------------------------------- a scene end to end
+def jet_scene(w, h, n, cols, seed=5):
+    """Waves towards the shore (texture moving down, +y, 1.5 px per frame) and a seaward jet (the same texture moving up,
+    -y, 1 px per frame) in the columns cols[0]..cols[1]: 8-bit frames with a little sensor noise."""
+    rng = np.random.RandomState(seed)
+    H = h + 4 * n
+    tex = rng.standard_normal((H, w)).astype(np.float64)
+    k = np.exp(-0.5 * (np.arange(-6, 7) / 2.0) ** 2)
+    k /= k.sum()
+    tex = np.apply_along_axis(lambda r: np.convolve(r, k, mode="same"), 1, tex)
+    tex = np.apply_along_axis(lambda c: np.convolve(c, k, mode="same"), 0, tex)
+    tex = (tex - tex.min()) / (tex.max() - tex.min())
+    yy = np.arange(h, dtype=np.float64)
+    frames = []
+    for t in range(n):
+        def shifted(dy):
+            pos = yy - dy * t + 2 * n          # sample position in the texture
+            i = np.floor(pos).astype(int)
+            a = (pos - i)[:, None]
+            return tex[i] * (1 - a) + tex[i + 1] * a
+        img = shifted(1.5)
+        img[:, cols[0]:cols[1]] = shifted(-1.0)[:, cols[0]:cols[1]]
+        frames.append(np.clip(img * 200 + 25 + rng.standard_normal((h, w)), 0, 255).astype(np.uint8))
+    return frames
+
+
+def test_synthetic_scene_flags_the_jet(ctx):
+    w, h, window, grid = 320, 240, 20, (16, 12)                # cells of 20 x 20 pixels
+    cols = (120, 160)                                          # the jet: cell columns 6 and 7
+    frames = jet_scene(w, h, window + 12, cols)
+    ctx.stream_reset()
+    ctx.ripmap_open(w, h, window, grid, wait_full=True)
+    want = np.zeros((12, 16), bool)
+    want[:, 6:8] = True
+    seen = []
+    for t, fr in enumerate(frames):
+        flow = ctx.push_frame_host(fr, winsize=15, iterations=3, levels=3)
+        if flow is None:
+            continue
+        ctx.ripmap_push(None)
+        r = ctx.ripmap_read()
+        seen.append(r["opposed"])
+        if r["frames_pushed"] < window:
+            assert r["opposed_cells"] == 0
+    full = seen[window - 1:]
+    assert len(full) >= 10
+    for k, o in enumerate(full):
+        # inner rows: the first and last cell rows see the frame border of the flow
+        assert np.array_equal(o[1:-1], want[1:-1]), "flags of the filled ring, push %d:\n%s" % (window + k, o.astype(int))
+    r = ctx.ripmap_read()
+    assert 60 < r["direction"] < 120                            # the waves run towards +y
+    ctx.ripmap_close()
+    ctx.stream_reset()
+
+
+# ---------------------------------------------------------------------------- the C++ mirror
+def test_cpp_ripmap_against_ctypes(ctx, tmp_path):
+    """rc::RipMap (include/rcflow_module.hpp) compiled as tests/cpp's programs are and run on a seeded field sequence;
+    the sums and flags it prints equal the ctypes session's on the same fields."""
+    exe = str(tmp_path / "test_ripmap")
+    src = os.path.join(ROOT, "tests", "cpp", "test_ripmap.cpp")
+    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"),
+           src, "-o", exe, "-L" + os.path.join(ROOT, "ripcurrents_amd"), "-lrcflow", "-L/opt/rocm/lib", "-lamdhip64",
+           "-Wl,-rpath," + os.path.join(ROOT, "ripcurrents_amd"), "-Wl,-rpath,/opt/rocm/lib"]
+    b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert b.returncode == 0, b.stderr[-4000:]
+    w, h, window, gx, gy, n = 97, 61, 3, 7, 5, 5
+    r = subprocess.run([exe, str(w), str(h), str(window), str(gx), str(gy), str(n)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "test_ripmap: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [l.split() for l in r.stdout.splitlines() if l.startswith("push ")]
+    assert len(lines) == n
+    # the program's fields: v(x, y, t) = ((x * 7 + y * 3 + t * 11) % 17 - 8) / 4, ((x * 5 + y * 13 + t * 7) % 19 - 9) / 4
+    y, x = np.mgrid[0:h, 0:w]
+    ctx.ripmap_open(w, h, window, (gx, gy))
+    for t, l in enumerate(lines):
+        f = np.stack([((x * 7 + y * 3 + t * 11) % 17 - 8) / 4.0, ((x * 5 + y * 13 + t * 7) % 19 - 9) / 4.0], -1).astype(f32)
+        ctx.ripmap_push(torch.as_tensor(f).cuda())
+        got = ctx.ripmap_read()
+        vals = [int(v) for v in l[2:]]
+        assert vals[0] == got["opposed_cells"] and vals[1] == got["live_cells"] and vals[2] == got["bad_pixels"]
+        assert vals[3:] == got["sums"].ravel().tolist(), "push %d" % (t + 1)
+    ctx.ripmap_close()
