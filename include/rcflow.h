@@ -379,8 +379,10 @@ int rcflow_warp_translate_bgr_dev(rc_ctx* ctx, int stream, const uint8_t* d_bgr,
 /* Opens the slot's stabilisation state for 8UC3 frames of w x h and the patch (roi_x, roi_y, roi_w, roi_h): inside the
  * frame, at least 8 x 8 (RC_EINVAL), optimal DFT sizes up to 256 x 256 and the frame within the context's size
  * (RC_ESIZE).  Builds the window and the twiddle tables on the host in double and allocates everything a push needs;
- * re-opening replaces the state.  Stream rules as for rcflow_timex_open: the state is zeroed on the stream the slot
- * has at this call (so does rcflow_framestab_reset) and the first push waits for that. */
+ * re-opening replaces the state, and a refused open (RC_ENOMEM included) leaves the open state as it was: the new state is
+ * allocated before the old one is freed, so both are resident for the length of a re-open.  Stream rules as for
+ * rcflow_timex_open: the state is zeroed on the stream the slot has at this call (so does rcflow_framestab_reset) and the
+ * first push waits for that. */
 int rcflow_framestab_open(rc_ctx* ctx, int stream, int w, int h, int roi_x, int roi_y, int roi_w, int roi_h);
 /* One frame in, the corrected frame out (both 8UC3 of the opened size).  d_result (device, three doubles, may be
  * NULL) receives shift_x, shift_y, response.  The first push after open / reset has nothing to register against: it
@@ -504,7 +506,9 @@ int rcflow_framestab_info_multi(rc_ctx* ctx, int stream, int* n, int* rois, int 
 /* Opens the slot's time-exposure state for w x h frames: `products` is a mask of the above; the three ring products
  * share one ring of `window` frames (1..4096; ignored for MEAN alone).  Allocates everything it will ever need
  * (window * 3 bytes per pixel for the ring; RC_ENOMEM with the byte count in rcflow_last_error if it does not fit);
- * re-opening replaces the state.  RC_EINVAL for a bad mask or window, RC_ESIZE beyond the context's max_w x max_h.
+ * re-opening replaces the state, and a refused open (RC_ENOMEM included) leaves the open state as it was: the new state is
+ * allocated before the old one is freed, so both are resident for the length of a re-open (rcflow_timex_close first
+ * where two rings do not fit).  RC_EINVAL for a bad mask or window, RC_ESIZE beyond the context's max_w x max_h.
  * The state is zeroed asynchronously on the stream the slot has at this call (so does rcflow_timex_reset).  The first
  * push after it waits for that zeroing even if rcflow_set_hip_stream moved the slot in between; beyond that, as for
  * every entry point, work queued on the slot's former stream is the caller's to order when the slot changes stream. */
@@ -563,7 +567,8 @@ int rcflow_hsv_to_rgb_u8_dev(rc_ctx* ctx, int stream, const uint8_t* d_hsv, size
 #define RC_RIPMAP_WAIT_FULL 1      /* flags bit 0 */
 #define RC_RIPMAP_MAX_CELLS 16384
 /* Opens the slot's map for w x h fields.  Allocates everything it will ever need (RC_ENOMEM with the byte count in
- * rcflow_last_error if it does not fit); re-opening replaces the state, a refused open leaves it as it was.  RC_EINVAL:
+ * rcflow_last_error if it does not fit); re-opening replaces the state, a refused open leaves it as it was (as
+ * rcflow_timex_open: old and new state are resident together for the length of a re-open).  RC_EINVAL:
  * window outside 1..4096, a grid below 1 x 1, wider or higher than the frame (w < grid_x, h < grid_y) or beyond
  * RC_RIPMAP_MAX_CELLS cells, source other than 0 / 1, unknown flag bits; RC_ESIZE beyond the context's max_w x max_h.
  * Zeroed asynchronously on the stream the slot has at this call; stream rules as rcflow_timex_open. */

@@ -40,6 +40,28 @@ def _is_t(x):
     return isinstance(x, torch.Tensor)
 
 
+def _check_out(t, device, dtype, what, shape=None, numel=None, dense=False):
+    """A caller's output tensor: on `device` (its pointer goes to a kernel there), of `dtype`, of `shape` or of `numel`
+    elements; contiguous, or with dense=True dense pixels in rows that may be padded (a view is taken as it is)."""
+    ok = _is_t(t) and t.is_cuda and t.device == device and t.dtype == dtype
+    if ok and shape is not None:
+        ok = tuple(t.shape) == tuple(shape)
+    if ok and numel is not None:
+        ok = t.numel() == numel
+    if ok and dense:
+        inner = [1]                                # strides of the contiguous tensor below the row
+        for n in reversed(tuple(t.shape)[2:]):
+            inner.insert(0, inner[0] * n)
+        ok = list(t.stride()[1:]) == inner and t.stride(0) >= inner[0] * t.shape[1]
+    elif ok:
+        ok = t.is_contiguous()
+    if not ok:
+        raise ValueError("%s must be a %s tensor on %s, %s, %s" % (
+            what, str(dtype).replace("torch.", ""), device, "of shape %s" % (tuple(shape),) if shape is not None else "of %d" % numel,
+            "with dense pixels" if dense else "contiguous"))
+    return t
+
+
 def _check_initial_flow(prev, flow):
     """OPTFLOW_USE_INITIAL_FLOW: `flow` is HxWx2 float32 with dense pixels, on the side (host / device) of the images."""
     if _is_t(prev):
@@ -661,20 +683,13 @@ class Context:
             t = t.contiguous()
         return t
 
-    def _check_out3(self, t, shape, what):
-        """A caller's output image: uint8 on this device, of `shape`, dense pixels (rows may have any step)."""
-        if not _is_t(t) or not t.is_cuda or t.device != self.device or t.dtype != torch.uint8 or tuple(t.shape) != tuple(shape) \
-                or t.stride(2) != 1 or t.stride(1) != 3 or t.stride(0) < 3 * shape[1]:
-            raise ValueError("%s must be a uint8 device image of shape %s with dense pixels" % (what, tuple(shape)))
-        return t
-
     def _cvt_u8(self, fn, img, out, stream):
         a = self._img3(img)
         h, w = a.shape[:2]
         if out is None:
             out = torch.empty((h, w, 3), dtype=torch.uint8, device=self.device)
         else:
-            self._check_out3(out, a.shape, "out")
+            _check_out(out, self.device, torch.uint8, "out", shape=a.shape, dense=True)
         self._bind(stream)
         check(fn(self._h, stream, self._ptr(a), a.stride(0), w, h, self._ptr(out), out.stride(0)))
         return out
@@ -725,7 +740,7 @@ class Context:
                 t = out[name]
                 if t is None:
                     continue
-                self._check_out3(t, f.shape, "out[%r]" % name)
+                _check_out(t, self.device, torch.uint8, "out[%r]" % name, shape=f.shape, dense=True)
             elif name in info["products"]:
                 t = torch.empty(tuple(f.shape), dtype=torch.uint8, device=self.device)
             else:
@@ -757,8 +772,8 @@ class Context:
         h, w = ta.shape
         if out is None:
             out = torch.empty(3, dtype=torch.float64, device=self.device)
-        elif not _is_t(out) or not out.is_cuda or out.dtype != torch.float64 or out.numel() != 3 or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float64 device tensor of 3")
+        else:
+            _check_out(out, self.device, torch.float64, "out", numel=3)
         self._bind(stream)
         check(self._lib.rcflow_phase_correlate_dev(self._h, stream, self._ptr(ta), ta.stride(0) * 4, self._ptr(tb),
                                                    tb.stride(0) * 4, w, h, 1 if window else 0, self._ptr(out)))
@@ -771,7 +786,7 @@ class Context:
         if out is None:
             out = torch.empty(tuple(f.shape), dtype=torch.uint8, device=self.device)
         else:
-            self._check_out3(out, f.shape, "out")
+            _check_out(out, self.device, torch.uint8, "out", shape=f.shape, dense=True)
         self._bind(stream)
         check(self._lib.rcflow_warp_translate_bgr_dev(self._h, stream, self._ptr(f), f.stride(0), f.shape[1], f.shape[0],
                                                       self._ptr(out), out.stride(0), float(shift_x), float(shift_y)))
@@ -786,7 +801,7 @@ class Context:
         if out is None:
             out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=self.device)
         else:
-            self._check_out3(out, (dh, dw, 3), "out")
+            _check_out(out, self.device, torch.uint8, "out", shape=(dh, dw, 3), dense=True)
         self._bind(stream)
         check(fn(self._h, stream, self._ptr(f), f.stride(0), f.shape[1], f.shape[0], self._ptr(out), out.stride(0), dw, dh,
                  m.ctypes.data_as(C.POINTER(C.c_double)), RC_WARP_INVERSE_MAP if inverse_map else 0))
@@ -862,13 +877,10 @@ class Context:
         if out is None:
             out = torch.empty(tuple(f.shape), dtype=torch.uint8, device=self.device)
         else:
-            self._check_out3(out, f.shape, "out")
+            _check_out(out, self.device, torch.uint8, "out", shape=f.shape, dense=True)
         rp = C.c_void_p(None)
         if result is not None:
-            if not _is_t(result) or not result.is_cuda or result.dtype != torch.float64 or result.numel() != 3 \
-                    or not result.is_contiguous():
-                raise ValueError("result must be a contiguous float64 device tensor of 3")
-            rp = self._ptr(result)
+            rp = self._ptr(_check_out(result, self.device, torch.float64, "result", numel=3))
         self._bind(stream)
         check(self._lib.rcflow_framestab_push_dev(self._h, stream, self._ptr(f), f.stride(0), self._ptr(out), out.stride(0), rp))
         return out
@@ -935,22 +947,15 @@ class Context:
             fp, fstep = self._ptr(flow), flow.stride(0) * 4
         hp, hstep, mp, mstep, cp, sp = C.c_void_p(None), 0, C.c_void_p(None), 0, C.c_void_p(None), C.c_void_p(None)
         if hsv is not None:
-            self._check_out3(hsv, (h, w, 3), "hsv")
+            _check_out(hsv, self.device, torch.uint8, "hsv", shape=(h, w, 3), dense=True)
             hp, hstep = self._ptr(hsv), hsv.stride(0)
         if mask is not None:
-            if not _is_t(mask) or not mask.is_cuda or mask.dtype != torch.uint8 or tuple(mask.shape) != (h, w) or mask.stride(1) != 1:
-                raise ValueError("mask must be a %dx%d uint8 device tensor with dense rows" % (h, w))
+            _check_out(mask, self.device, torch.uint8, "mask", shape=(h, w), dense=True)
             mp, mstep = self._ptr(mask), mask.stride(0)
         if cells is not None:
-            if not _is_t(cells) or not cells.is_cuda or cells.dtype != torch.float32 or tuple(cells.shape) != (gy, gx, 4) \
-                    or not cells.is_contiguous():
-                raise ValueError("cells must be a contiguous %dx%dx4 float32 device tensor" % (gy, gx))
-            cp = self._ptr(cells)
+            cp = self._ptr(_check_out(cells, self.device, torch.float32, "cells", shape=(gy, gx, 4)))
         if summary is not None:
-            if not _is_t(summary) or not summary.is_cuda or summary.dtype != torch.float64 or summary.numel() != 8 \
-                    or not summary.is_contiguous():
-                raise ValueError("summary must be a contiguous float64 device tensor of 8")
-            sp = self._ptr(summary)
+            sp = self._ptr(_check_out(summary, self.device, torch.float64, "summary", numel=8))
         self._bind(stream)
         check(self._lib.rcflow_ripmap_push_dev(self._h, stream, fp, fstep, hp, hstep, mp, mstep, cp, sp))
 
@@ -959,9 +964,8 @@ class Context:
         info = self.ripmap_info(stream)
         if out is None:
             out = torch.empty((info["h"], info["w"], 2), dtype=torch.float32, device=self.device)
-        elif not _is_t(out) or not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (info["h"], info["w"], 2) \
-                or out.stride(2) != 1 or out.stride(1) != 2:
-            raise ValueError("out must be a %dx%dx2 float32 device tensor with dense pixels" % (info["h"], info["w"]))
+        else:
+            _check_out(out, self.device, torch.float32, "out", shape=(info["h"], info["w"], 2), dense=True)
         self._bind(stream)
         check(self._lib.rcflow_ripmap_mean_dev(self._h, stream, self._ptr(out), out.stride(0) * 4))
         return out

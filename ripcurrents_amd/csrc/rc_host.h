@@ -1,6 +1,7 @@
 // rc_host.h -- host-side context, plans and stream slots of librcflow (internal).
 #pragma once
 
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -41,6 +42,14 @@ struct RcAnalysis {
     RcBuf loopc;       // one int32: framecount of rcflow_frame_loop_step (incremented on the device)
 };
 
+// open / reset zero a product's state asynchronously on the stream the slot has then; whoever touches the state next
+// waits for this event when the slot has been moved to another stream in between (rcflow_set_hip_stream)
+struct RcZeroFence {
+    hipEvent_t ev = nullptr;
+    hipStream_t stream = nullptr;
+    bool pending = false;
+};
+
 // Time-exposure state of one stream slot (timex_kernels.hip; main.cpp:1195-1383).  Everything is allocated by
 // rcflow_timex_open and released by rcflow_timex_close / rcflow_destroy.
 struct RcTimex {
@@ -54,11 +63,7 @@ struct RcTimex {
     RcBuf ring;               // [window][H, S, V][plane] bytes (buffer_hsv, main.cpp:1292-1295)
     RcBuf avg;                // AVERAGE: [H, S, V][plane] uint16 sums of the slots' quotients
     RcBuf bd_idx[2], bd_hsv[2];   // BRIGHT, DARK: the winner's slot (uint16) and output triple (uint32) per pixel
-    // open / reset zero the state asynchronously on the stream the slot had then; the first push after it waits for
-    // this event when the slot has been moved to another stream in between
-    hipEvent_t zeroed = nullptr;
-    hipStream_t zero_stream = nullptr;
-    bool zero_pending = false;
+    RcZeroFence zf;
 };
 
 // Frame stabilisation state of one stream slot (stab_kernels.hip; main.cpp:1684-1775).  Everything is allocated by
@@ -74,10 +79,7 @@ struct RcFrameStab {
     RcBuf prev;                     // [rh][rw] float: gray ROI of the last CORRECTED frame (prev, main.cpp:1759)
     RcBuf res;                      // 3 doubles: shift_x, shift_y, response of the last push
     RcBuf scratch;                  // spectra of the launch-per-pass form
-    // zeroed asynchronously by open / reset on the stream the slot had then, as RcTimex
-    hipEvent_t zeroed = nullptr;
-    hipStream_t zero_stream = nullptr;
-    bool zero_pending = false;
+    RcZeroFence zf;
     // rcflow_framestab_open_multi (n = 0: the single-patch slot above).  The patches share rw x rh, tab and the LDS
     // plan; prev holds n patches; res holds RC_FS_* doubles: result | motion | used | ticket | the n shifts
     int n = 0, model = 0, flags = 0;
@@ -102,10 +104,7 @@ struct RcRipMap {
     RcBuf avg;                // [h][pitch] float2: the window mean
     RcBuf acc;                // RmCtl | [gy][gx][Sx, Sy, n] int64, zero between launches
     RcBuf out;                // the last push: cells [cells] float4 | sums [cells][3] int64 | summary 8 doubles
-    // zeroed asynchronously by open / reset on the stream the slot had then, as RcTimex
-    hipEvent_t zeroed = nullptr;
-    hipStream_t zero_stream = nullptr;
-    bool zero_pending = false;
+    RcZeroFence zf;
 };
 
 // warp_kernels.hip: one launch of the affine / perspective warp
@@ -241,12 +240,16 @@ int rc_hist_book(RcSlot& s, int w, int h, bool commit);
 int rc_analysis_ensure(rc_ctx* ctx, RcSlot& s, int w, int h);
 // computeResizeAreaTab (resize.cpp) grouped by destination index (analysis_kernels.hip)
 void rc_area_tab(int ssize, int dsize, double scale, std::vector<int>& start, std::vector<int>& si, std::vector<float>& alpha);
-// timex_kernels.hip
-void rc_timex_free(RcSlot& s);
-// stab_kernels.hip
-void rc_framestab_free(RcSlot& s);
-// ripmap_kernels.hip
-void rc_ripmap_free(RcSlot& s);
+// the zeroing of a product's state: memsets of the buffers that are allocated on `cur`, then the event
+int rc_fence_zero(RcZeroFence& z, hipStream_t cur, std::initializer_list<RcBuf*> bufs);
+// makes `cur` wait for a pending zeroing made on another stream.  consume: the caller queues work on `cur` that later
+// callers are ordered behind (a push); a call that only reads leaves the fence pending
+int rc_fence_wait(RcZeroFence& z, hipStream_t cur, bool consume);
+void rc_fence_free(RcZeroFence& z);
+// 8UC3 image arguments.  who, what: the entry point and the argument, for the text
+bool rc_img3_overlap(const uint8_t* a, size_t astep, int aw, int ah, const uint8_t* b, size_t bstep, int bw, int bh);
+int rc_img3_check(const char* who, const char* what, const uint8_t* p, size_t step, int w, int h);   // RC_EINVAL: null, empty, step < 3 w
+int rc_fits_context(const char* who, const rc_ctx* ctx, int w, int h);                                // RC_ESIZE
 // warp_kernels.hip
 void rc_warp_launch(rc_ctx* ctx, hipStream_t cur, RcWarpArgs& a, bool perspective);
 // initial_flow_kernels.hip
@@ -270,3 +273,56 @@ struct RcProfScope {
             return RC_EHIP;                                                           \
         }                                                                             \
     } while (0)
+
+// ---------------------------------------------------------------------------- per-slot products
+// RcTimex, RcFrameStab and RcRipMap share one lifecycle.  A product supplies
+//   void rc_state_free(T&)             frees every buffer and the fence; the state is T() again
+//   int rc_state_zero(RcSlot&, T&)     rc_fence_zero of what open / reset clear, and the counters
+// and open / reset / close are written once, here.
+void rc_state_free(RcTimex& t);
+void rc_state_free(RcFrameStab& f);
+void rc_state_free(RcRipMap& m);
+int rc_state_zero(RcSlot& s, RcTimex& t);
+int rc_state_zero(RcSlot& s, RcFrameStab& f);
+int rc_state_zero(RcSlot& s, RcRipMap& m);
+
+// The tail of every open.  The caller has validated, selected the device and built `fresh` (rc: what its allocations
+// returned).  The state that is open is touched only once nothing can be refused any more: a refused open leaves it as it
+// was, at the price of both states being resident for the length of a re-open.
+template <class T>
+int rc_state_install(RcSlot& s, T& cur, T& fresh, int rc) {
+    if (!rc && cur.open && hipStreamSynchronize(s.cur) != hipSuccess) {   // launches still reading the state being replaced
+        rc_set_error("hipStreamSynchronize failed before a re-open");
+        rc = RC_EHIP;
+    }
+    if (rc) {                                             // rc_buf_ensure has set the text, with the byte count
+        (void)hipGetLastError();
+        rc_state_free(fresh);
+        return rc;
+    }
+    rc_state_free(cur);
+    cur = fresh;
+    cur.open = true;
+    if ((rc = rc_state_zero(s, cur))) rc_state_free(cur);
+    return rc;
+}
+
+template <class T>
+int rc_state_reset(rc_ctx* ctx, int stream, T RcSlot::*member, const char* product) {
+    RcSlot* s = rc_slot(ctx, stream);
+    if (!s) return RC_EINVAL;
+    if (!(s->*member).open) { rc_set_error("%s_reset before %s_open", product, product); return RC_ESTATE; }
+    RC_HIP(hipSetDevice(ctx->device));
+    return rc_state_zero(*s, s->*member);
+}
+
+template <class T>
+int rc_state_close(rc_ctx* ctx, int stream, T RcSlot::*member) {
+    RcSlot* s = rc_slot(ctx, stream);
+    if (!s) return RC_EINVAL;
+    if (!(s->*member).open) return RC_OK;
+    RC_HIP(hipSetDevice(ctx->device));
+    RC_HIP(hipStreamSynchronize(s->cur));
+    rc_state_free(s->*member);
+    return RC_OK;
+}

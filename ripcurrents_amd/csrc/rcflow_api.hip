@@ -48,6 +48,43 @@ RcSlot* rc_slot(rc_ctx* ctx, int stream) {
     return &ctx->slots[stream];
 }
 
+// ---------------------------------------------------------------------------- per-slot products: fence, image arguments
+int rc_fence_zero(RcZeroFence& z, hipStream_t cur, std::initializer_list<RcBuf*> bufs) {
+    for (RcBuf* b : bufs)
+        if (b->p) RC_HIP(hipMemsetAsync(b->p, 0, b->bytes, cur));
+    if (!z.ev) RC_HIP(hipEventCreateWithFlags(&z.ev, hipEventDisableTiming));
+    RC_HIP(hipEventRecord(z.ev, cur));
+    z.stream = cur;
+    z.pending = true;
+    return RC_OK;
+}
+int rc_fence_wait(RcZeroFence& z, hipStream_t cur, bool consume) {
+    if (!z.pending) return RC_OK;
+    if (cur != z.stream) RC_HIP(hipStreamWaitEvent(cur, z.ev, 0));
+    if (consume) z.pending = false;
+    return RC_OK;
+}
+void rc_fence_free(RcZeroFence& z) {
+    if (z.ev) (void)hipEventDestroy(z.ev);
+    z = RcZeroFence();
+}
+
+bool rc_img3_overlap(const uint8_t* a, size_t astep, int aw, int ah, const uint8_t* b, size_t bstep, int bw, int bh) {
+    const uint8_t* ae = a + (size_t)(ah - 1) * astep + (size_t)3 * aw;
+    const uint8_t* be = b + (size_t)(bh - 1) * bstep + (size_t)3 * bw;
+    return a < be && b < ae;
+}
+int rc_img3_check(const char* who, const char* what, const uint8_t* p, size_t step, int w, int h) {
+    if (p && w > 0 && h > 0 && step >= (size_t)3 * w) return RC_OK;
+    rc_set_error("%s: bad image argument %s (a null pointer, an empty size, or a step below 3 * w)", who, what);
+    return RC_EINVAL;
+}
+int rc_fits_context(const char* who, const rc_ctx* ctx, int w, int h) {
+    if (w <= ctx->max_w && h <= ctx->max_h) return RC_OK;
+    rc_set_error("%s: %d x %d exceeds the context size %d x %d", who, w, h, ctx->max_w, ctx->max_h);
+    return RC_ESIZE;
+}
+
 // ---------------------------------------------------------------------------- profiling
 RcProfScope::RcProfScope(rc_ctx* c, hipStream_t st, int kind, int level, double alg_bytes, double survey_bytes)
     : ctx(c), s(st), id(kind * RC_MAX_LEVELS + level), bytes(alg_bytes),
@@ -220,9 +257,9 @@ static void slot_free(RcSlot& s) {
     for (auto& b : s.stage_f32) rc_buf_free(b);
     rc_buf_free(s.an.hist); rc_buf_free(s.an.hist_part); rc_buf_free(s.an.thr); rc_buf_free(s.an.acc);
     rc_buf_free(s.an.pt); rc_buf_free(s.an.dist); rc_buf_free(s.an.scratch); rc_buf_free(s.an.jet); rc_buf_free(s.an.loopc);
-    rc_timex_free(s);
-    rc_framestab_free(s);
-    rc_ripmap_free(s);
+    rc_state_free(s.tx);
+    rc_state_free(s.fs);
+    rc_state_free(s.rm);
     rc_buf_free(s.pc.tab); rc_buf_free(s.pc.scratch);
     rc_loop_graph_drop(s);
     for (auto& e : s.fev) { if (e) (void)hipEventDestroy(e); e = nullptr; }

@@ -21,8 +21,8 @@
 // from row to row: it accumulates in registers while the cell row stays, then the wave reduces per cell column,
 // the block's waves meet in LDS, and the block issues one 64-bit atomic per sum and cell it touched.
 
-#include "rc_device.h"
 #include "rc_host.h"
+#include "rc_pix3.h"
 
 #define RM_WAVES 4
 static_assert(RC_BLOCK == 64 * RM_WAVES, "a block is RM_WAVES waves, a run of rows each");
@@ -315,15 +315,15 @@ __global__ __launch_bounds__(RC_BLOCK) void k_ripmap(const RmArgs a) {
     if (last) rm_finish(a, red);
 }
 
-// "ripmap@1": 255 inside an opposed cell.  A thread owns 4 consecutive pixels of a row.
+// "ripmap@1": 255 inside an opposed cell.  A thread owns 4 consecutive pixels of a row (rc_pix3.h's span, one byte each).
 __global__ __launch_bounds__(RC_BLOCK) void k_ripmap_mask(const float4* cells, int w, int h, int gx, int gy, int cw, int ch,
                                                           uint8_t* mask, size_t mask_step) {
-    const int x0 = 4 * (blockIdx.x * 64 + (threadIdx.x & 63)), y = blockIdx.y * RM_WAVES + (threadIdx.x >> 6);
-    if (x0 >= w || y >= h) return;
+    const RcPix3Span t = rc_pix3_span(w, 1);
+    const int x0 = t.x0, n = t.n, y = t.y0;
+    if (n <= 0 || y >= h) return;
     const float4* row = cells + (size_t)min(y / ch, gy - 1) * gx;
     uint8_t* q = mask + (size_t)y * mask_step + x0;
     uint32_t m = 0;
-    const int n = min(4, w - x0);
     for (int k = 0; k < n; k++)
         if (row[min((x0 + k) / cw, gx - 1)].w != 0.f) m |= 255u << (8 * k);
     if (n == 4) __builtin_memcpy(q, &m, 4);
@@ -332,12 +332,11 @@ __global__ __launch_bounds__(RC_BLOCK) void k_ripmap_mask(const float4* cells, i
 }
 
 // ============================================================================ host side
-static void rm_free(RcRipMap& m) {
+void rc_state_free(RcRipMap& m) {
     rc_buf_free(m.ring); rc_buf_free(m.avg); rc_buf_free(m.acc); rc_buf_free(m.out);
-    if (m.zeroed) (void)hipEventDestroy(m.zeroed);
+    rc_fence_free(m.zf);
     m = RcRipMap();
 }
-void rc_ripmap_free(RcSlot& s) { rm_free(s.rm); }
 
 static size_t rm_cells(const RcRipMap& m) { return (size_t)m.gx * m.gy; }
 // RcRipMap::out: cells [cells] float4 | sums [cells][3] int64 | summary 8 doubles
@@ -345,18 +344,10 @@ static float4* rm_out_cells(const RcRipMap& m) { return (float4*)m.out.p; }
 static long long* rm_out_sums(const RcRipMap& m) { return (long long*)((char*)m.out.p + rm_cells(m) * 16); }
 static double* rm_out_summary(const RcRipMap& m) { return (double*)((char*)m.out.p + rm_cells(m) * 40); }
 
-static int rm_zero(RcSlot& s) {
-    RcRipMap& m = s.rm;
-    RcBuf* all[] = {&m.ring, &m.avg, &m.acc, &m.out};
-    for (RcBuf* b : all) RC_HIP(hipMemsetAsync(b->p, 0, b->bytes, s.cur));
-    // the zeroing runs on the stream the slot has NOW; the first push may come on another one (rcflow_set_hip_stream)
-    if (!m.zeroed) RC_HIP(hipEventCreateWithFlags(&m.zeroed, hipEventDisableTiming));
-    RC_HIP(hipEventRecord(m.zeroed, s.cur));
-    m.zero_stream = s.cur;
-    m.zero_pending = true;
-    m.frames = 0;
-    m.cur = 0;
-    return RC_OK;
+int rc_state_zero(RcSlot& s, RcRipMap& m) {
+    const int rc = rc_fence_zero(m.zf, s.cur, {&m.ring, &m.avg, &m.acc, &m.out});
+    if (!rc) m.frames = m.cur = 0;
+    return rc;
 }
 
 extern "C" int rcflow_ripmap_open(rc_ctx* ctx, int stream, int w, int h, int window, int grid_x, int grid_y, int source,
@@ -374,29 +365,18 @@ extern "C" int rcflow_ripmap_open(rc_ctx* ctx, int stream, int w, int h, int win
         rc_set_error("rcflow_ripmap_open: bad source %d or flags %d", source, flags);
         return RC_EINVAL;
     }
-    if (w > ctx->max_w || h > ctx->max_h) { rc_set_error("frame exceeds the context size"); return RC_ESIZE; }
+    int rc = rc_fits_context("rcflow_ripmap_open", ctx, w, h);
+    if (rc) return rc;
     RC_HIP(hipSetDevice(ctx->device));
-    // everything is allocated before the slot's state is touched: a refused open leaves it as it was
     RcRipMap n;
     n.w = w; n.h = h; n.window = window; n.gx = grid_x; n.gy = grid_y; n.source = source; n.flags = flags;
     n.pitch = (w + 1) & ~1;
     const size_t plane = (size_t)n.pitch * h * sizeof(float2), nc = rm_cells(n);
-    int rc = rc_buf_ensure(n.ring, plane * (size_t)window);
+    rc = rc_buf_ensure(n.ring, plane * (size_t)window);
     if (!rc) rc = rc_buf_ensure(n.avg, plane);
     if (!rc) rc = rc_buf_ensure(n.acc, sizeof(RmCtl) + nc * 24);
     if (!rc) rc = rc_buf_ensure(n.out, nc * 40 + 64);
-    if (rc) {                                             // rc_buf_ensure has set the text, with the byte count
-        (void)hipGetLastError();
-        rm_free(n);
-        return rc;
-    }
-    RcRipMap& m = s->rm;
-    if (m.open) RC_HIP(hipStreamSynchronize(s->cur));     // launches still reading the state being replaced
-    rm_free(m);
-    m = n;
-    m.open = true;
-    if ((rc = rm_zero(*s))) { rm_free(m); return rc; }
-    return RC_OK;
+    return rc_state_install(*s, s->rm, n, rc);
 }
 
 extern "C" int rcflow_ripmap_set(rc_ctx* ctx, int stream, double min_opposition_cos2, double min_cell_mag) {
@@ -412,23 +392,8 @@ extern "C" int rcflow_ripmap_set(rc_ctx* ctx, int stream, double min_opposition_
     return RC_OK;
 }
 
-extern "C" int rcflow_ripmap_reset(rc_ctx* ctx, int stream) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    if (!s->rm.open) { rc_set_error("rcflow_ripmap_reset before rcflow_ripmap_open"); return RC_ESTATE; }
-    RC_HIP(hipSetDevice(ctx->device));
-    return rm_zero(*s);
-}
-
-extern "C" int rcflow_ripmap_close(rc_ctx* ctx, int stream) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    if (!s->rm.open) return RC_OK;
-    RC_HIP(hipSetDevice(ctx->device));
-    RC_HIP(hipStreamSynchronize(s->cur));
-    rm_free(s->rm);
-    return RC_OK;
-}
+extern "C" int rcflow_ripmap_reset(rc_ctx* ctx, int stream) { return rc_state_reset(ctx, stream, &RcSlot::rm, "rcflow_ripmap"); }
+extern "C" int rcflow_ripmap_close(rc_ctx* ctx, int stream) { return rc_state_close(ctx, stream, &RcSlot::rm); }
 
 extern "C" int rcflow_ripmap_info(rc_ctx* ctx, int stream, int* w, int* h, int* window, int* grid_x, int* grid_y, int* source,
                                   int* flags, double* min_opposition_cos2, double* min_cell_mag, long long* frames_pushed,
@@ -451,15 +416,6 @@ extern "C" int rcflow_ripmap_info(rc_ctx* ctx, int stream, int* w, int* h, int* 
     return RC_OK;
 }
 
-static int rm_wait_zeroed(RcSlot& s) {
-    RcRipMap& m = s.rm;
-    if (m.zero_pending) {
-        if (s.cur != m.zero_stream) RC_HIP(hipStreamWaitEvent(s.cur, m.zeroed, 0));
-        m.zero_pending = false;
-    }
-    return RC_OK;
-}
-
 extern "C" int rcflow_ripmap_push_dev(rc_ctx* ctx, int stream, const float* d_flow_xy, size_t flow_step, uint8_t* d_hsv,
                                       size_t hsv_step, uint8_t* d_mask, size_t mask_step, float* d_cells, double* d_summary) {
     RcSlot* s = rc_slot(ctx, stream);
@@ -478,13 +434,11 @@ extern "C" int rcflow_ripmap_push_dev(rc_ctx* ctx, int stream, const float* d_fl
         rc_set_error("bad flow field argument");
         return RC_EINVAL;
     }
-    if ((d_hsv && hsv_step < (size_t)3 * m.w) || (d_mask && mask_step < (size_t)m.w)) {
-        rc_set_error("output step smaller than a row");
-        return RC_EINVAL;
-    }
+    if (d_hsv && rc_img3_check("rcflow_ripmap_push_dev", "d_hsv", d_hsv, hsv_step, m.w, m.h)) return RC_EINVAL;
+    if (d_mask && mask_step < (size_t)m.w) { rc_set_error("rcflow_ripmap_push_dev: mask_step is below w"); return RC_EINVAL; }
     if (m.source == 1 && !s->an.thr.p) { rc_set_error("source 1 reads UPPER from the slot's analysis state (rcflow_analysis_reset)"); return RC_ESTATE; }
     RC_HIP(hipSetDevice(ctx->device));
-    int rc = rm_wait_zeroed(*s);
+    int rc = rc_fence_wait(m.zf, s->cur, true);
     if (rc) return rc;
     RmArgs a;
     a.flow = d_flow_xy; a.flow_step = flow_step;
@@ -498,7 +452,7 @@ extern "C" int rcflow_ripmap_push_dev(rc_ctx* ctx, int stream, const float* d_fl
     a.sums = rm_out_sums(m); a.cells = rm_out_cells(m); a.summary = rm_out_summary(m);
     a.cells2 = (float4*)d_cells; a.summary2 = d_summary;
     a.w = m.w; a.h = m.h; a.pitch = m.pitch;
-    a.rows = (long long)m.w * m.h >= (1 << 20) ? 4 : 1;   // runs of rows once there are waves enough to fill the device
+    a.rows = rc_rows_per_wave(m.w, m.h, 4);
     a.gx = m.gx; a.gy = m.gy; a.cw = m.w / m.gx; a.ch = m.h / m.gy;
     a.inv = (float)(1. / (float)m.window);                // rcflow_window_mean_dev's
     a.first_scale = m.frames == 0 ? 1e-6f : 0.f;
@@ -517,7 +471,7 @@ extern "C" int rcflow_ripmap_push_dev(rc_ctx* ctx, int stream, const float* d_fl
     m.cur = m.cur + 1 >= m.window ? 0 : m.cur + 1;
     if (d_mask) {
         RcProfScope ps(ctx, s->cur, RC_K_RIPMAP, 1, (double)m.w * m.h);
-        hipLaunchKernelGGL(k_ripmap_mask, dim3(((m.w + 3) / 4 + 63) / 64, (m.h + RM_WAVES - 1) / RM_WAVES), dim3(RC_BLOCK), 0, s->cur,
+        hipLaunchKernelGGL(k_ripmap_mask, rc_pix3_grid(m.w, m.h, 1), dim3(RC_BLOCK), 0, s->cur,
                            a.cells, m.w, m.h, m.gx, m.gy, a.cw, a.ch, d_mask, mask_step);
     }
     RC_HIP(hipGetLastError());
@@ -527,11 +481,11 @@ extern "C" int rcflow_ripmap_push_dev(rc_ctx* ctx, int stream, const float* d_fl
 extern "C" int rcflow_ripmap_mean_dev(rc_ctx* ctx, int stream, float* d_mean_xy, size_t mean_step) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    const RcRipMap& m = s->rm;
+    RcRipMap& m = s->rm;
     if (!m.open) { rc_set_error("rcflow_ripmap_mean_dev before rcflow_ripmap_open"); return RC_ESTATE; }
     if (!d_mean_xy || mean_step < (size_t)m.w * 8) { rc_set_error("bad mean field argument"); return RC_EINVAL; }
     RC_HIP(hipSetDevice(ctx->device));
-    int rc = rm_wait_zeroed(*s);
+    int rc = rc_fence_wait(m.zf, s->cur, true);
     if (rc) return rc;
     RC_HIP(hipMemcpy2DAsync(d_mean_xy, mean_step, m.avg.p, (size_t)m.pitch * 8, (size_t)m.w * 8, m.h, hipMemcpyDeviceToDevice, s->cur));
     return RC_OK;
@@ -541,10 +495,10 @@ extern "C" int rcflow_ripmap_read(rc_ctx* ctx, int stream, float* cells, double*
                                   long long* frames_pushed) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    const RcRipMap& m = s->rm;
+    RcRipMap& m = s->rm;
     if (!m.open) { rc_set_error("rcflow_ripmap_read before rcflow_ripmap_open"); return RC_ESTATE; }
     RC_HIP(hipSetDevice(ctx->device));
-    int rc = rm_wait_zeroed(*s);
+    int rc = rc_fence_wait(m.zf, s->cur, true);
     if (rc) return rc;
     const size_t nc = rm_cells(m);
     if (sums) RC_HIP(hipMemcpyAsync(sums, rm_out_sums(m), nc * 24, hipMemcpyDeviceToHost, s->cur));

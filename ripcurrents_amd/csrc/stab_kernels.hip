@@ -30,14 +30,12 @@
 
 #include <vector>
 
-#include "rc_device.h"
 #include "rc_host.h"
+#include "rc_pix3.h"
 
 #define ST_BLOCK 1024                    // the correlate workgroup: 16 waves
 #define ST_RED_BYTES 256                 // per-wave (value, index) of the arg-max
 #define ST_LDS_MAX (160 * 1024)
-#define ST_ROWS 4                        // warp: rows per block, one per wave
-static_assert(RC_BLOCK == 64 * ST_ROWS, "a warp block is ST_ROWS waves, one row (or run of rows) each");
 
 struct StArgs {
     const float* a; size_t a_step;       // prev patch, byte step
@@ -367,23 +365,6 @@ struct StWarpArgs {
     int w, h, rows, rx, ry, rw, rh;
 };
 
-// pixel (x, y) of the source as byte0 | byte1 << 8 | byte2 << 16; 0 outside the frame (BORDER_CONSTANT, value 0)
-__device__ __forceinline__ uint32_t st_tap(const StWarpArgs& a, int x, int y) {
-    if ((unsigned)x >= (unsigned)a.w || (unsigned)y >= (unsigned)a.h) return 0u;
-    const uint8_t* p = a.src + (size_t)y * a.step + 3 * (size_t)x;
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
-}
-// 5 consecutive pixels from 16 bytes
-__device__ __forceinline__ void st_unpack5(const uint8_t* p, uint32_t px[5]) {
-    uint4 q;
-    __builtin_memcpy(&q, p, 16);
-    px[0] = q.x & 0xffffffu;
-    px[1] = (q.x >> 24) | ((q.y & 0xffffu) << 8);
-    px[2] = (q.y >> 16) | ((q.z & 0xffu) << 16);
-    px[3] = q.z >> 8;
-    px[4] = q.w & 0xffffffu;
-}
-
 __global__ __launch_bounds__(RC_BLOCK) void k_stab_warp(const StWarpArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int x0 = 4 * (blockIdx.x * 64 + (threadIdx.x & 63)), n = min(4, a.w - x0);
@@ -393,49 +374,32 @@ __global__ __launch_bounds__(RC_BLOCK) void k_stab_warp(const StWarpArgs a) {
     const int X0 = __double2int_rn(sx * 1024.0) + 16;
     const int fx = (X0 >> 5) & 31, xs = x0 + (X0 >> 10);
     if (n <= 0) return;
-    const int yb = (blockIdx.y * ST_ROWS + wave) * a.rows;
+    const int yb = (blockIdx.y * RC_PIX3_WAVES + wave) * a.rows;
     for (int y = yb; y < min(yb + a.rows, a.h); y++) {
         // y is inside the rounding: (1.0 * y + shift.y) * 1024 in double, per row
         const int Y0 = __double2int_rn(((double)y + sy) * 1024.0) + 16;
         const int fy = (Y0 >> 5) & 31, ys = Y0 >> 10;
-        const int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;
         uint32_t p0[5], p1[5];
         if (n == 4 && xs >= 0 && xs + 5 < a.w && ys >= 0 && ys + 1 < a.h) {
             const uint8_t* s0 = a.src + (size_t)ys * a.step + 3 * (size_t)xs;
-            st_unpack5(s0, p0);
-            st_unpack5(s0 + a.step, p1);
+            rc_pix3_unpack5(s0, p0);
+            rc_pix3_unpack5(s0 + a.step, p1);
         } else {
 #pragma unroll
-            for (int k = 0; k < 5; k++) { p0[k] = st_tap(a, xs + k, ys); p1[k] = st_tap(a, xs + k, ys + 1); }
+            for (int k = 0; k < 5; k++) {
+                p0[k] = rc_pix3_tap(a.src, a.step, a.w, a.h, xs + k, ys);
+                p1[k] = rc_pix3_tap(a.src, a.step, a.w, a.h, xs + k, ys + 1);
+            }
         }
         uint32_t o[4];
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            o[k] = 0;
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                const int sh = 8 * c;
-                const int v = (int)((p0[k] >> sh) & 255u) * w00 + (int)((p0[k + 1] >> sh) & 255u) * w01 +
-                              (int)((p1[k] >> sh) & 255u) * w10 + (int)((p1[k + 1] >> sh) & 255u) * w11;
-                o[k] |= (uint32_t)((v + (1 << 14)) >> 15) << sh;
-            }
-        }
-        uint8_t* d = a.dst + (size_t)y * a.dst_step + 3 * (size_t)x0;
-        if (n == 4) {
-            uint32_t q[3] = {o[0] | (o[1] << 24), (o[1] >> 8) | (o[2] << 16), (o[2] >> 16) | (o[3] << 8)};
-            __builtin_memcpy(d, q, 12);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-                if (k < n) { d[3 * k] = (uint8_t)o[k]; d[3 * k + 1] = (uint8_t)(o[k] >> 8); d[3 * k + 2] = (uint8_t)(o[k] >> 16); }
-        }
+        for (int k = 0; k < 4; k++) o[k] = rc_pix3_bilinear(p0[k], p0[k + 1], p1[k], p1[k + 1], fx, fy);
+        rc_pix3_store4(a.dst + (size_t)y * a.dst_step, x0, n, o);
         if (a.patch && (unsigned)(y - a.ry) < (unsigned)a.rh) {
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 const int px = x0 + k - a.rx;
-                if (k < n && (unsigned)px < (unsigned)a.rw)
-                    a.patch[(y - a.ry) * a.rw + px] = (float)(int)(((o[k] & 255u) * 1868u + ((o[k] >> 8) & 255u) * 9617u +
-                                                                   (o[k] >> 16) * 4899u + (1u << 13)) >> 14);
+                if (k < n && (unsigned)px < (unsigned)a.rw) a.patch[(y - a.ry) * a.rw + px] = rc_pix3_gray(o[k]);
             }
         }
     }
@@ -559,34 +523,25 @@ extern "C" int rcflow_phase_correlate_dev(rc_ctx* ctx, int stream, const float* 
     return st_correlate(ctx, s->cur, p, q);
 }
 
-static bool st_overlap(const uint8_t* a, size_t astep, const uint8_t* b, size_t bstep, int w, int h) {
-    const uint8_t* ae = a + (size_t)(h - 1) * astep + (size_t)3 * w;
-    const uint8_t* be = b + (size_t)(h - 1) * bstep + (size_t)3 * w;
-    return a < be && b < ae;
-}
-
 static void st_warp_launch(rc_ctx* ctx, hipStream_t cur, StWarpArgs& a) {
-    a.rows = (long long)a.w * a.h >= (1 << 20) ? 2 : 1;
-    const dim3 grid(((a.w + 3) / 4 + 63) / 64, (a.h + ST_ROWS * a.rows - 1) / (ST_ROWS * a.rows));
+    a.rows = rc_rows_per_wave(a.w, a.h, 2);
     RcProfScope ps(ctx, cur, RC_K_FRAMESTAB, 1, 6. * a.w * a.h + (a.patch ? 4. * a.rw * a.rh : 0.) + (a.d_shift ? 16. : 0.));
-    hipLaunchKernelGGL(k_stab_warp, grid, dim3(RC_BLOCK), 0, cur, a);
+    hipLaunchKernelGGL(k_stab_warp, rc_pix3_grid(a.w, a.h, a.rows), dim3(RC_BLOCK), 0, cur, a);
 }
 
 extern "C" int rcflow_warp_translate_bgr_dev(rc_ctx* ctx, int stream, const uint8_t* d_bgr, size_t step, int w, int h, uint8_t* d_out,
                                              size_t out_step, double shift_x, double shift_y) {
+    static const char* who = "rcflow_warp_translate_bgr_dev";
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    if (!d_bgr || !d_out || w <= 0 || h <= 0 || step < (size_t)3 * w || out_step < (size_t)3 * w) {
-        rc_set_error("bad image arguments");
-        return RC_EINVAL;
-    }
+    if (rc_img3_check(who, "d_bgr", d_bgr, step, w, h) || rc_img3_check(who, "d_out", d_out, out_step, w, h)) return RC_EINVAL;
     // the fixed-point coordinates are 32-bit with 10 fraction bits
     if (!(fabs(shift_x) <= 1048576.) || !(fabs(shift_y) <= 1048576.)) {
-        rc_set_error("rcflow_warp_translate_bgr_dev: shift (%g, %g) is not finite or beyond 2^20 px", shift_x, shift_y);
+        rc_set_error("%s: shift (%g, %g) is not finite or beyond 2^20 px", who, shift_x, shift_y);
         return RC_EINVAL;
     }
-    if (w > ctx->max_w || h > ctx->max_h) { rc_set_error("frame exceeds the context size"); return RC_ESIZE; }
-    if (st_overlap(d_out, out_step, d_bgr, step, w, h)) { rc_set_error("d_out overlaps the frame (the warp is not in place)"); return RC_EINVAL; }
+    if (rc_fits_context(who, ctx, w, h)) return RC_ESIZE;
+    if (rc_img3_overlap(d_out, out_step, w, h, d_bgr, step, w, h)) { rc_set_error("%s: d_out overlaps the frame (the warp is not in place)", who); return RC_EINVAL; }
     RC_HIP(hipSetDevice(ctx->device));
     StWarpArgs a;
     memset(&a, 0, sizeof(a));
@@ -598,75 +553,76 @@ extern "C" int rcflow_warp_translate_bgr_dev(rc_ctx* ctx, int stream, const uint
 }
 
 // ---------------------------------------------------------------------------- the pipeline (main.cpp:1707-1759)
-static void fs_free(RcFrameStab& f) {
+void rc_state_free(RcFrameStab& f) {
     rc_buf_free(f.tab); rc_buf_free(f.prev); rc_buf_free(f.res); rc_buf_free(f.scratch);
-    if (f.zeroed) (void)hipEventDestroy(f.zeroed);
+    rc_fence_free(f.zf);
     f = RcFrameStab();
 }
-void rc_framestab_free(RcSlot& s) { fs_free(s.fs); }
 
-// nothing to register against yet: frame count, result and prev patch to zero, on the stream the slot has NOW
-static int fs_zero(RcSlot& s) {
-    RcFrameStab& f = s.fs;
-    RC_HIP(hipMemsetAsync(f.prev.p, 0, f.prev.bytes, s.cur));
-    RC_HIP(hipMemsetAsync(f.res.p, 0, f.res.bytes, s.cur));
-    if (!f.zeroed) RC_HIP(hipEventCreateWithFlags(&f.zeroed, hipEventDisableTiming));
-    RC_HIP(hipEventRecord(f.zeroed, s.cur));
-    f.zero_stream = s.cur;
-    f.zero_pending = true;
-    f.frames = 0;
-    return RC_OK;
+// nothing to register against yet: frame count, result and prev patch to zero
+int rc_state_zero(RcSlot& s, RcFrameStab& f) {
+    const int rc = rc_fence_zero(f.zf, s.cur, {&f.prev, &f.res});
+    if (!rc) f.frames = 0;
+    return rc;
+}
+
+// Both opens behind their own argument checks: n patches of one size at rois (n = 0: the single-patch slot, one ROI)
+static int fs_open(const char* who, rc_ctx* ctx, RcSlot& s, int w, int h, const int* rois, int n, int model, double min_response, int flags) {
+    const int np = n ? n : 1, rw = rois[2], rh = rois[3];
+    for (int k = 0; k < np; k++) {
+        const int* r = rois + 4 * k;
+        if (r[0] < 0 || r[1] < 0 || r[2] <= 0 || r[3] <= 0 || r[0] > w - r[2] || r[1] > h - r[3]) {
+            rc_set_error("%s: patch %d (%d, %d, %d x %d) is not inside the %d x %d frame", who, k, r[0], r[1], r[2], r[3], w, h);
+            return RC_EINVAL;
+        }
+        if (r[2] != rw || r[3] != rh) { rc_set_error("%s: patch %d is %d x %d, patch 0 is %d x %d (one size for all)", who, k, r[2], r[3], rw, rh); return RC_EINVAL; }
+    }
+    StPlan q;
+    int rc = st_check_patch(who, rw, rh, q);
+    if (rc) return rc;
+    if (n && !q.fits) {
+        rc_set_error("%s: patch %d x %d (DFT %d x %d) is beyond the one-workgroup correlation; larger patches are single-patch (rcflow_framestab_open)",
+                     who, rw, rh, q.N, q.M);
+        return RC_ESIZE;
+    }
+    if ((rc = rc_fits_context(who, ctx, w, h))) return rc;
+    RC_HIP(hipSetDevice(ctx->device));
+    RcFrameStab f;
+    f.w = w; f.h = h; f.rx = rois[0]; f.ry = rois[1]; f.rw = rw; f.rh = rh;
+    f.N = q.N; f.M = q.M; f.lds = q.fits ? q.lds : 0;
+    f.n = n; f.model = model; f.flags = flags; f.min_response = min_response;
+    for (int k = 0; k < n; k++) { f.px[k] = rois[4 * k]; f.py[k] = rois[4 * k + 1]; }
+    rc = st_tables(f.tab, q, s.cur);
+    if (!rc) rc = rc_buf_ensure(f.prev, (size_t)np * rw * rh * sizeof(float));
+    if (!rc) rc = rc_buf_ensure(f.res, (size_t)(n ? RC_FS_SHIFTS + 3 * RC_STAB_MAX_PATCHES : 3) * sizeof(double));
+    if (!rc && !q.fits) rc = rc_buf_ensure(f.scratch, q.scratch);
+    return rc_state_install(s, s.fs, f, rc);
 }
 
 extern "C" int rcflow_framestab_open(rc_ctx* ctx, int stream, int w, int h, int roi_x, int roi_y, int roi_w, int roi_h) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
     if (w <= 0 || h <= 0) { rc_set_error("rcflow_framestab_open: bad frame size %d x %d", w, h); return RC_EINVAL; }
-    if (roi_x < 0 || roi_y < 0 || roi_w <= 0 || roi_h <= 0 || roi_x > w - roi_w || roi_y > h - roi_h) {
-        rc_set_error("rcflow_framestab_open: ROI (%d, %d, %d x %d) is not inside the %d x %d frame", roi_x, roi_y, roi_w, roi_h, w, h);
+    const int roi[4] = {roi_x, roi_y, roi_w, roi_h};
+    return fs_open("rcflow_framestab_open", ctx, *s, w, h, roi, 0, 0, 0., 0);
+}
+
+extern "C" int rcflow_framestab_open_multi(rc_ctx* ctx, int stream, int w, int h, const int* rois, int n, int model, double min_response,
+                                           int flags) {
+    static const char* who = "rcflow_framestab_open_multi";
+    RcSlot* s = rc_slot(ctx, stream);
+    if (!s) return RC_EINVAL;
+    if (w <= 0 || h <= 0) { rc_set_error("%s: bad frame size %d x %d", who, w, h); return RC_EINVAL; }
+    if (!rois || n < 1 || n > RC_STAB_MAX_PATCHES) { rc_set_error("%s: %d patches (1..%d)", who, n, RC_STAB_MAX_PATCHES); return RC_EINVAL; }
+    if (model < RC_STAB_TRANSLATION || model > RC_STAB_AFFINE || (flags & ~RC_STAB_ANCHOR_FIRST) || min_response != min_response) {
+        rc_set_error("%s: unknown model %d or flag bits 0x%x, or min_response is NaN", who, model, flags);
         return RC_EINVAL;
     }
-    StPlan q;
-    int rc = st_check_patch("rcflow_framestab_open", roi_w, roi_h, q);
-    if (rc) return rc;
-    if (w > ctx->max_w || h > ctx->max_h) { rc_set_error("frame exceeds the context size"); return RC_ESIZE; }
-    RC_HIP(hipSetDevice(ctx->device));
-    RcFrameStab& f = s->fs;
-    if (f.open) RC_HIP(hipStreamSynchronize(s->cur));     // launches still reading the state being replaced
-    fs_free(f);
-    f.w = w; f.h = h; f.rx = roi_x; f.ry = roi_y; f.rw = roi_w; f.rh = roi_h;
-    f.N = q.N; f.M = q.M; f.lds = q.fits ? q.lds : 0;
-    rc = st_tables(f.tab, q, s->cur);
-    if (!rc) rc = rc_buf_ensure(f.prev, (size_t)roi_w * roi_h * sizeof(float));
-    if (!rc) rc = rc_buf_ensure(f.res, 3 * sizeof(double));
-    if (!rc && !q.fits) rc = rc_buf_ensure(f.scratch, q.scratch);
-    if (rc) {
-        (void)hipGetLastError();
-        fs_free(f);
-        return rc;
-    }
-    f.open = true;
-    if ((rc = fs_zero(*s))) { fs_free(f); return rc; }
-    return RC_OK;
+    return fs_open(who, ctx, *s, w, h, rois, n, model, min_response, flags);
 }
 
-extern "C" int rcflow_framestab_reset(rc_ctx* ctx, int stream) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    if (!s->fs.open) { rc_set_error("rcflow_framestab_reset before rcflow_framestab_open"); return RC_ESTATE; }
-    RC_HIP(hipSetDevice(ctx->device));
-    return fs_zero(*s);
-}
-
-extern "C" int rcflow_framestab_close(rc_ctx* ctx, int stream) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    if (!s->fs.open) return RC_OK;
-    RC_HIP(hipSetDevice(ctx->device));
-    RC_HIP(hipStreamSynchronize(s->cur));
-    fs_free(s->fs);
-    return RC_OK;
-}
+extern "C" int rcflow_framestab_reset(rc_ctx* ctx, int stream) { return rc_state_reset(ctx, stream, &RcSlot::fs, "rcflow_framestab"); }
+extern "C" int rcflow_framestab_close(rc_ctx* ctx, int stream) { return rc_state_close(ctx, stream, &RcSlot::fs); }
 
 extern "C" int rcflow_framestab_info(rc_ctx* ctx, int stream, int* w, int* h, int roi[4], int dft_size[2], int* launches_per_push,
                                      long long* frames_pushed, size_t* device_bytes) {
@@ -681,99 +637,6 @@ extern "C" int rcflow_framestab_info(rc_ctx* ctx, int stream, int* w, int* h, in
     if (launches_per_push) *launches_per_push = f.lds ? 2 : 6;
     if (frames_pushed) *frames_pushed = f.frames;
     if (device_bytes) *device_bytes = f.tab.bytes + f.prev.bytes + f.res.bytes + f.scratch.bytes;
-    return RC_OK;
-}
-
-// A push of a slot opened by rcflow_framestab_open_multi: "framestab@7" (n workgroups + the fit), "framestab@8"
-static int fs_push_multi(rc_ctx* ctx, RcSlot& s, const uint8_t* d_frame, size_t step, uint8_t* d_out, size_t out_step, double* d_result) {
-    RcFrameStab& f = s.fs;
-    RcWarpArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src = d_frame; a.step = step; a.sw = f.w; a.sh = f.h; a.dst = d_out; a.dst_step = out_step; a.dw = f.w; a.dh = f.h;
-    a.M[0] = a.M[4] = 1.;
-    if (f.frames == 0 || !(f.flags & RC_STAB_ANCHOR_FIRST)) {
-        a.patch = (float*)f.prev.p; a.npatch = f.n; a.rw = f.rw; a.rh = f.rh;
-        memcpy(a.rx, f.px, sizeof(a.rx)); memcpy(a.ry, f.py, sizeof(a.ry));
-    }
-    if (f.frames == 0) {
-        // the first frame is copied (the identity: every pixel is its own source) and its patches become prev
-        RC_HIP(hipMemsetAsync(f.res.p, 0, f.res.bytes, s.cur));
-        if (d_result) RC_HIP(hipMemsetAsync(d_result, 0, 3 * sizeof(double), s.cur));
-    } else {
-        const StPlan q = st_plan(f.rw, f.rh);
-        StMultiArgs m;
-        memset(&m, 0, sizeof(m));
-        st_fill(m.p, q, f.tab, f.scratch, true);
-        m.p.a = (const float*)f.prev.p; m.p.a_step = (size_t)f.rw * sizeof(float); m.p.bgr_step = step;
-        m.frame = d_frame; m.step = step;
-        m.state = (double*)f.res.p; m.res2 = d_result;
-        m.min_response = f.min_response; m.n = f.n; m.model = f.model; m.fw = f.w; m.fh = f.h;
-        memcpy(m.rx, f.px, sizeof(m.rx)); memcpy(m.ry, f.py, sizeof(m.ry));
-        if (q.lds > 64 * 1024) {
-            (void)hipFuncSetAttribute((const void*)k_stab_correlate_multi, hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS_MAX);
-            (void)hipGetLastError();
-        }
-        {
-            const double in_bytes = 7. * q.w * q.h + 4. * q.w * q.h + 8. * (q.N + q.M);
-            RcProfScope ps(ctx, s.cur, RC_K_FRAMESTAB, 7, f.n * (in_bytes + 24.) + 72. + (d_result ? 24. : 0.));
-            hipLaunchKernelGGL(k_stab_correlate_multi, dim3(f.n), dim3(ST_BLOCK), q.lds, s.cur, m);
-        }
-        RC_HIP(hipGetLastError());
-        a.d_M = (const double*)f.res.p + RC_FS_MOTION;
-    }
-    rc_warp_launch(ctx, s.cur, a, false);
-    RC_HIP(hipGetLastError());
-    f.frames++;
-    return RC_OK;
-}
-
-extern "C" int rcflow_framestab_open_multi(rc_ctx* ctx, int stream, int w, int h, const int* rois, int n, int model, double min_response,
-                                           int flags) {
-    static const char* who = "rcflow_framestab_open_multi";
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    if (w <= 0 || h <= 0) { rc_set_error("%s: bad frame size %d x %d", who, w, h); return RC_EINVAL; }
-    if (!rois || n < 1 || n > RC_STAB_MAX_PATCHES) { rc_set_error("%s: %d patches (1..%d)", who, n, RC_STAB_MAX_PATCHES); return RC_EINVAL; }
-    if (model < RC_STAB_TRANSLATION || model > RC_STAB_AFFINE || (flags & ~RC_STAB_ANCHOR_FIRST) || min_response != min_response) {
-        rc_set_error("%s: unknown model %d or flag bits 0x%x, or min_response is NaN", who, model, flags);
-        return RC_EINVAL;
-    }
-    const int rw = rois[2], rh = rois[3];
-    for (int k = 0; k < n; k++) {
-        const int* r = rois + 4 * k;
-        if (r[0] < 0 || r[1] < 0 || r[2] <= 0 || r[3] <= 0 || r[0] > w - r[2] || r[1] > h - r[3]) {
-            rc_set_error("%s: patch %d (%d, %d, %d x %d) is not inside the %d x %d frame", who, k, r[0], r[1], r[2], r[3], w, h);
-            return RC_EINVAL;
-        }
-        if (r[2] != rw || r[3] != rh) { rc_set_error("%s: patch %d is %d x %d, patch 0 is %d x %d (one size for all)", who, k, r[2], r[3], rw, rh); return RC_EINVAL; }
-    }
-    StPlan q;
-    int rc = st_check_patch(who, rw, rh, q);
-    if (rc) return rc;
-    if (!q.fits) {
-        rc_set_error("%s: patch %d x %d (DFT %d x %d) is beyond the one-workgroup correlation; larger patches are single-patch (rcflow_framestab_open)",
-                     who, rw, rh, q.N, q.M);
-        return RC_ESIZE;
-    }
-    if (w > ctx->max_w || h > ctx->max_h) { rc_set_error("frame exceeds the context size"); return RC_ESIZE; }
-    RC_HIP(hipSetDevice(ctx->device));
-    RcFrameStab& f = s->fs;
-    if (f.open) RC_HIP(hipStreamSynchronize(s->cur));     // launches still reading the state being replaced
-    fs_free(f);
-    f.w = w; f.h = h; f.rx = rois[0]; f.ry = rois[1]; f.rw = rw; f.rh = rh;
-    f.N = q.N; f.M = q.M; f.lds = q.lds;
-    f.n = n; f.model = model; f.flags = flags; f.min_response = min_response;
-    for (int k = 0; k < n; k++) { f.px[k] = rois[4 * k]; f.py[k] = rois[4 * k + 1]; }
-    rc = st_tables(f.tab, q, s->cur);
-    if (!rc) rc = rc_buf_ensure(f.prev, (size_t)n * rw * rh * sizeof(float));
-    if (!rc) rc = rc_buf_ensure(f.res, (size_t)(RC_FS_SHIFTS + 3 * RC_STAB_MAX_PATCHES) * sizeof(double));
-    if (rc) {
-        (void)hipGetLastError();
-        fs_free(f);
-        return rc;
-    }
-    f.open = true;
-    if ((rc = fs_zero(*s))) { fs_free(f); return rc; }
     return RC_OK;
 }
 
@@ -794,6 +657,82 @@ extern "C" int rcflow_framestab_info_multi(rc_ctx* ctx, int stream, int* n, int*
     return RC_OK;
 }
 
+// Registers the frame against prev.  The single-patch slot: "framestab@0" (or "@2..6"), the shift into res.  A slot of
+// rcflow_framestab_open_multi: "framestab@7" (n workgroups + the fit), the motion into res + RC_FS_MOTION.
+static int fs_correlate(rc_ctx* ctx, RcSlot& s, const uint8_t* d_frame, size_t step, double* d_result) {
+    const RcFrameStab& f = s.fs;
+    const StPlan q = st_plan(f.rw, f.rh);
+    StMultiArgs m;
+    memset(&m, 0, sizeof(m));
+    StArgs& p = m.p;                                     // the single-patch launch takes this part alone
+    st_fill(p, q, f.tab, f.scratch, true);
+    p.a = (const float*)f.prev.p; p.a_step = (size_t)f.rw * sizeof(float); p.bgr_step = step;
+    if (!f.n) {
+        p.bgr = d_frame + (size_t)f.ry * step + (size_t)3 * f.rx;
+        p.res = (double*)f.res.p; p.res2 = d_result;
+        return st_correlate(ctx, s.cur, p, q);
+    }
+    m.frame = d_frame; m.step = step;
+    m.state = (double*)f.res.p; m.res2 = d_result;
+    m.min_response = f.min_response; m.n = f.n; m.model = f.model; m.fw = f.w; m.fh = f.h;
+    memcpy(m.rx, f.px, sizeof(m.rx)); memcpy(m.ry, f.py, sizeof(m.ry));
+    if (q.lds > 64 * 1024) {
+        (void)hipFuncSetAttribute((const void*)k_stab_correlate_multi, hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS_MAX);
+        (void)hipGetLastError();
+    }
+    {
+        const double in_bytes = 7. * q.w * q.h + 4. * q.w * q.h + 8. * (q.N + q.M);
+        RcProfScope ps(ctx, s.cur, RC_K_FRAMESTAB, 7, f.n * (in_bytes + 24.) + 72. + (d_result ? 24. : 0.));
+        hipLaunchKernelGGL(k_stab_correlate_multi, dim3(f.n), dim3(ST_BLOCK), q.lds, s.cur, m);
+    }
+    RC_HIP(hipGetLastError());
+    return RC_OK;
+}
+
+extern "C" int rcflow_framestab_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_frame, size_t step, uint8_t* d_out, size_t out_step,
+                                         double* d_result) {
+    static const char* who = "rcflow_framestab_push_dev";
+    RcSlot* s = rc_slot(ctx, stream);
+    if (!s) return RC_EINVAL;
+    RcFrameStab& f = s->fs;
+    if (!f.open) { rc_set_error("%s before rcflow_framestab_open", who); return RC_ESTATE; }
+    if (rc_img3_check(who, "d_frame", d_frame, step, f.w, f.h) || rc_img3_check(who, "d_out", d_out, out_step, f.w, f.h)) return RC_EINVAL;
+    if (rc_img3_overlap(d_out, out_step, f.w, f.h, d_frame, step, f.w, f.h)) { rc_set_error("%s: d_out overlaps the frame (the warp is not in place)", who); return RC_EINVAL; }
+    RC_HIP(hipSetDevice(ctx->device));
+    int rc = rc_fence_wait(f.zf, s->cur, true);
+    if (rc) return rc;
+    const bool first = f.frames == 0;
+    if (first) {
+        // the first frame is copied (shift 0, the identity: every pixel is its own source) and becomes prev; result (0, 0, 0)
+        RC_HIP(hipMemsetAsync(f.res.p, 0, f.res.bytes, s->cur));
+        if (d_result) RC_HIP(hipMemsetAsync(d_result, 0, 3 * sizeof(double), s->cur));
+    } else if ((rc = fs_correlate(ctx, *s, d_frame, step, d_result))) {
+        return rc;
+    }
+    if (f.n) {                                           // "framestab@8": the fitted motion, read from device memory
+        RcWarpArgs a;
+        memset(&a, 0, sizeof(a));
+        a.src = d_frame; a.step = step; a.sw = f.w; a.sh = f.h; a.dst = d_out; a.dst_step = out_step; a.dw = f.w; a.dh = f.h;
+        a.M[0] = a.M[4] = 1.;
+        if (first || !(f.flags & RC_STAB_ANCHOR_FIRST)) {
+            a.patch = (float*)f.prev.p; a.npatch = f.n; a.rw = f.rw; a.rh = f.rh;
+            memcpy(a.rx, f.px, sizeof(a.rx)); memcpy(a.ry, f.py, sizeof(a.ry));
+        }
+        if (!first) a.d_M = (const double*)f.res.p + RC_FS_MOTION;
+        rc_warp_launch(ctx, s->cur, a, false);
+    } else {                                             // "framestab@1": the shift, read from device memory
+        StWarpArgs a;
+        memset(&a, 0, sizeof(a));
+        a.src = d_frame; a.step = step; a.dst = d_out; a.dst_step = out_step; a.w = f.w; a.h = f.h;
+        a.patch = (float*)f.prev.p; a.rx = f.rx; a.ry = f.ry; a.rw = f.rw; a.rh = f.rh;
+        if (!first) a.d_shift = (const double*)f.res.p;
+        st_warp_launch(ctx, s->cur, a);
+    }
+    RC_HIP(hipGetLastError());
+    f.frames++;
+    return RC_OK;
+}
+
 extern "C" int rcflow_framestab_read_motion(rc_ctx* ctx, int stream, double motion[6], int* model_used, int* patches_used, double* shifts,
                                             long long* frames_pushed) {
     RcSlot* s = rc_slot(ctx, stream);
@@ -801,7 +740,8 @@ extern "C" int rcflow_framestab_read_motion(rc_ctx* ctx, int stream, double moti
     RcFrameStab& f = s->fs;
     if (!f.open) { rc_set_error("rcflow_framestab_read_motion before rcflow_framestab_open"); return RC_ESTATE; }
     RC_HIP(hipSetDevice(ctx->device));
-    if (f.zero_pending && s->cur != f.zero_stream) RC_HIP(hipStreamWaitEvent(s->cur, f.zeroed, 0));
+    int rc = rc_fence_wait(f.zf, s->cur, false);
+    if (rc) return rc;
     double st[RC_FS_SHIFTS + 3 * RC_STAB_MAX_PATCHES] = {};
     RC_HIP(hipMemcpyAsync(st, f.res.p, f.n ? sizeof(st) : 3 * sizeof(double), hipMemcpyDeviceToHost, s->cur));
     RC_HIP(hipStreamSynchronize(s->cur));
@@ -825,56 +765,14 @@ extern "C" int rcflow_framestab_read_motion(rc_ctx* ctx, int stream, double moti
     return RC_OK;
 }
 
-extern "C" int rcflow_framestab_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_frame, size_t step, uint8_t* d_out, size_t out_step,
-                                         double* d_result) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    RcFrameStab& f = s->fs;
-    if (!f.open) { rc_set_error("rcflow_framestab_push_dev before rcflow_framestab_open"); return RC_ESTATE; }
-    if (!d_frame || !d_out || step < (size_t)3 * f.w || out_step < (size_t)3 * f.w) {
-        rc_set_error("rcflow_framestab_push_dev: bad frame arguments (a step below 3 * w, or a null image)");
-        return RC_EINVAL;
-    }
-    if (st_overlap(d_out, out_step, d_frame, step, f.w, f.h)) { rc_set_error("d_out overlaps the frame (the warp is not in place)"); return RC_EINVAL; }
-    RC_HIP(hipSetDevice(ctx->device));
-    if (f.zero_pending) {
-        if (s->cur != f.zero_stream) RC_HIP(hipStreamWaitEvent(s->cur, f.zeroed, 0));
-        f.zero_pending = false;
-    }
-    if (f.n) return fs_push_multi(ctx, *s, d_frame, step, d_out, out_step, d_result);
-    StWarpArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src = d_frame; a.step = step; a.dst = d_out; a.dst_step = out_step; a.w = f.w; a.h = f.h;
-    a.patch = (float*)f.prev.p; a.rx = f.rx; a.ry = f.ry; a.rw = f.rw; a.rh = f.rh;
-    if (f.frames == 0) {
-        // the first frame is copied (shift 0: every pixel is its own source) and becomes prev; result (0, 0, 0)
-        RC_HIP(hipMemsetAsync(f.res.p, 0, f.res.bytes, s->cur));
-        if (d_result) RC_HIP(hipMemsetAsync(d_result, 0, 3 * sizeof(double), s->cur));
-    } else {
-        const StPlan q = st_plan(f.rw, f.rh);
-        StArgs p;
-        memset(&p, 0, sizeof(p));
-        st_fill(p, q, f.tab, f.scratch, true);
-        p.a = (const float*)f.prev.p; p.a_step = (size_t)f.rw * sizeof(float);
-        p.bgr = d_frame + (size_t)f.ry * step + (size_t)3 * f.rx; p.bgr_step = step;
-        p.res = (double*)f.res.p; p.res2 = d_result;
-        int rc = st_correlate(ctx, s->cur, p, q);
-        if (rc) return rc;
-        a.d_shift = (const double*)f.res.p;
-    }
-    st_warp_launch(ctx, s->cur, a);
-    RC_HIP(hipGetLastError());
-    f.frames++;
-    return RC_OK;
-}
-
 extern "C" int rcflow_framestab_read(rc_ctx* ctx, int stream, double result[3], long long* frames_pushed) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
     RcFrameStab& f = s->fs;
     if (!f.open) { rc_set_error("rcflow_framestab_read before rcflow_framestab_open"); return RC_ESTATE; }
     RC_HIP(hipSetDevice(ctx->device));
-    if (f.zero_pending && s->cur != f.zero_stream) RC_HIP(hipStreamWaitEvent(s->cur, f.zeroed, 0));
+    int rc = rc_fence_wait(f.zf, s->cur, false);
+    if (rc) return rc;
     double r[3] = {0., 0., 0.};
     RC_HIP(hipMemcpyAsync(r, f.res.p, sizeof(r), hipMemcpyDeviceToHost, s->cur));
     RC_HIP(hipStreamSynchronize(s->cur));

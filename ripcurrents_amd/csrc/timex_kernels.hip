@@ -14,53 +14,12 @@
 //            keeps it the winner when the new value is not worse (everything below it was strictly worse, everything
 //            above it not better); otherwise that pixel walks the V plane of the ring again as the reference does.
 //
-// Layout: a thread owns 4 consecutive pixels of a row: 12 B of an 8UC3 image as one dwordx3 access (the images
-// are only byte aligned; global memory takes unaligned dwords on this target and the compiler emits them for a
-// byte-aligned 12-byte copy), the w % 4 tail pixel by pixel.  The state is planar with a row pitch of a multiple
+// Layout: rc_pix3.h's (a thread owns 4 consecutive pixels of a row).  The state is planar with a row pitch of a multiple
 // of 4 pixels, so that every state access of a thread is one aligned dword / dwordx2 / dwordx4.
 
-#include "rc_device.h"
 #include "rc_host.h"
+#include "rc_pix3.h"
 
-#define TX_ROWS 4   // rows per block: one per wave, times `rows` per wave
-static_assert(RC_BLOCK == 64 * TX_ROWS, "a block is TX_ROWS waves, one row (or run of rows) each");
-
-// ---------------------------------------------------------------------------- pixels
-// a pixel travels as byte0 | byte1 << 8 | byte2 << 16
-typedef uint32_t tx_u32x3 __attribute__((ext_vector_type(3)));   // copied as a whole: one dwordx3
-__device__ __forceinline__ void tx_load4(const uint8_t* row, int x0, int n, uint32_t px[4]) {
-    const uint8_t* p = row + 3 * (size_t)x0;
-    if (n == 4) {
-        tx_u32x3 w;
-        __builtin_memcpy(&w, p, 12);
-        px[0] = w[0] & 0xffffffu;
-        px[1] = (w[0] >> 24) | ((w[1] & 0xffffu) << 8);
-        px[2] = (w[1] >> 16) | ((w[2] & 0xffu) << 16);
-        px[3] = w[2] >> 8;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            px[k] = k < n ? (uint32_t)p[3 * k] | ((uint32_t)p[3 * k + 1] << 8) | ((uint32_t)p[3 * k + 2] << 16) : 0u;
-    }
-}
-__device__ __forceinline__ void tx_store4(uint8_t* row, int x0, int n, const uint32_t px[4]) {
-    uint8_t* p = row + 3 * (size_t)x0;
-    if (n == 4) {
-        tx_u32x3 w;
-        w[0] = px[0] | (px[1] << 24);
-        w[1] = (px[1] >> 8) | (px[2] << 16);
-        w[2] = (px[2] >> 16) | (px[3] << 8);
-        __builtin_memcpy(p, &w, 12);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (k < n) {
-                p[3 * k] = (uint8_t)px[k];
-                p[3 * k + 1] = (uint8_t)(px[k] >> 8);
-                p[3 * k + 2] = (uint8_t)(px[k] >> 16);
-            }
-    }
-}
 __device__ __forceinline__ uint32_t tx_byte(uint32_t v, int k) { return (v >> (8 * k)) & 255u; }
 
 // ---------------------------------------------------------------------------- colour conversions
@@ -115,44 +74,34 @@ __device__ __forceinline__ uint32_t tx_hsv_to_rgb(uint32_t p) {
     return tx_sat_u8(r * 255.f) | (tx_sat_u8(g * 255.f) << 8) | (tx_sat_u8(b * 255.f) << 16);
 }
 
-// thread -> its pixels: columns x0 .. x0 + n - 1 (n <= 0: none) of the rows y0 .. y0 + rows - 1
-struct TxSpan { int x0, n, y0; };
-__device__ __forceinline__ TxSpan tx_span(int w, int rows) {
-    TxSpan t;
-    t.x0 = 4 * (blockIdx.x * 64 + (threadIdx.x & 63));
-    t.n = min(4, w - t.x0);
-    t.y0 = (blockIdx.y * TX_ROWS + (threadIdx.x >> 6)) * rows;
-    return t;
-}
-
 __global__ __launch_bounds__(RC_BLOCK) void k_rgb_to_hsv_u8(const uint8_t* rgb, size_t step, int w, int h, uint8_t* hsv,
                                                             size_t hsv_step, int rows) {
     __shared__ int sdiv[256], hdiv[256];
     tx_hsv_tables(sdiv, hdiv);
     __syncthreads();
-    const TxSpan t = tx_span(w, rows);
+    const RcPix3Span t = rc_pix3_span(w, rows);
     const int x0 = t.x0, n = t.n;
     if (n <= 0) return;
     for (int y = t.y0; y < min(t.y0 + rows, h); y++) {
         uint32_t px[4];
-        tx_load4(rgb + (size_t)y * step, x0, n, px);
+        rc_pix3_load4(rgb + (size_t)y * step, x0, n, px);
 #pragma unroll
         for (int k = 0; k < 4; k++) px[k] = tx_rgb_to_hsv(px[k], sdiv, hdiv);
-        tx_store4(hsv + (size_t)y * hsv_step, x0, n, px);
+        rc_pix3_store4(hsv + (size_t)y * hsv_step, x0, n, px);
     }
 }
 
 __global__ __launch_bounds__(RC_BLOCK) void k_hsv_to_rgb_u8(const uint8_t* hsv, size_t hsv_step, int w, int h, uint8_t* rgb,
                                                             size_t step, int rows) {
-    const TxSpan t = tx_span(w, rows);
+    const RcPix3Span t = rc_pix3_span(w, rows);
     const int x0 = t.x0, n = t.n;
     if (n <= 0) return;
     for (int y = t.y0; y < min(t.y0 + rows, h); y++) {
         uint32_t px[4];
-        tx_load4(hsv + (size_t)y * hsv_step, x0, n, px);
+        rc_pix3_load4(hsv + (size_t)y * hsv_step, x0, n, px);
 #pragma unroll
         for (int k = 0; k < 4; k++) px[k] = tx_hsv_to_rgb(px[k]);
-        tx_store4(rgb + (size_t)y * step, x0, n, px);
+        rc_pix3_store4(rgb + (size_t)y * step, x0, n, px);
     }
 }
 
@@ -160,12 +109,12 @@ __global__ __launch_bounds__(RC_BLOCK) void k_hsv_to_rgb_u8(const uint8_t* hsv, 
 // sum: [h][pitch][3] fp32.  sum += frame; out = convertTo(8U) of sum * (float)(1.0 / n)
 __global__ __launch_bounds__(RC_BLOCK) void k_timex_mean(const uint8_t* frame, size_t step, int w, int h, float* sum, int pitch,
                                                          float rn, uint8_t* out, size_t out_step, int rows) {
-    const TxSpan t = tx_span(w, rows);
+    const RcPix3Span t = rc_pix3_span(w, rows);
     const int x0 = t.x0, n = t.n;
     if (n <= 0) return;
     for (int y = t.y0; y < min(t.y0 + rows, h); y++) {
         uint32_t px[4];
-        tx_load4(frame + (size_t)y * step, x0, n, px);
+        rc_pix3_load4(frame + (size_t)y * step, x0, n, px);
         float4* sp = (float4*)(sum + ((size_t)y * pitch + x0) * 3);
         float4 q[3] = {sp[0], sp[1], sp[2]};
         float* s = (float*)q;
@@ -180,7 +129,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_timex_mean(const uint8_t* frame, s
             px[k] = o;
         }
         sp[0] = q[0]; sp[1] = q[1]; sp[2] = q[2];
-        if (out) tx_store4(out + (size_t)y * out_step, x0, n, px);
+        if (out) rc_pix3_store4(out + (size_t)y * out_step, x0, n, px);
     }
 }
 
@@ -266,7 +215,7 @@ __device__ __forceinline__ void tx_emit(uint8_t* out, size_t out_step, int y, in
     if (!out) return;
 #pragma unroll
     for (int k = 0; k < 4; k++) hsv[k] = tx_hsv_to_rgb(hsv[k]);
-    tx_store4(out + (size_t)y * out_step, x0, n, hsv);
+    rc_pix3_store4(out + (size_t)y * out_step, x0, n, hsv);
 }
 
 __global__ __launch_bounds__(RC_BLOCK) void k_timex_ring(const TxRingArgs a) {
@@ -275,12 +224,12 @@ __global__ __launch_bounds__(RC_BLOCK) void k_timex_ring(const TxRingArgs a) {
     tx_hsv_tables(sdiv, hdiv);
     for (int i = threadIdx.x; i < 256; i += RC_BLOCK) qt[i] = (uint8_t)tx_sat_u8((float)i * a.rw);
     __syncthreads();
-    const TxSpan t = tx_span(a.w, a.rows);
+    const RcPix3Span t = rc_pix3_span(a.w, a.rows);
     const int x0 = t.x0, n = t.n;
     if (n <= 0) return;
     for (int y = t.y0; y < min(t.y0 + a.rows, a.h); y++) {
         uint32_t px[4], res[4];
-        tx_load4(a.frame + (size_t)y * a.step, x0, n, px);
+        rc_pix3_load4(a.frame + (size_t)y * a.step, x0, n, px);
         uint32_t hn = 0, sn = 0, vn = 0;
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -323,36 +272,21 @@ __global__ __launch_bounds__(RC_BLOCK) void k_timex_ring(const TxRingArgs a) {
 }
 
 // ============================================================================ host side
-static dim3 tx_grid(int w, int h, int& rows) {
-    rows = (long long)w * h >= (1 << 20) ? 2 : 1;         // two rows per wave once there are waves enough to fill the device
-    return dim3(((w + 3) / 4 + 63) / 64, (h + TX_ROWS * rows - 1) / (TX_ROWS * rows));
-}
-
-static void tx_free(RcTimex& t) {
+void rc_state_free(RcTimex& t) {
     rc_buf_free(t.sum); rc_buf_free(t.ring); rc_buf_free(t.avg);
     for (int i = 0; i < 2; i++) { rc_buf_free(t.bd_idx[i]); rc_buf_free(t.bd_hsv[i]); }
-    if (t.zeroed) (void)hipEventDestroy(t.zeroed);
+    rc_fence_free(t.zf);
     t = RcTimex();
 }
-void rc_timex_free(RcSlot& s) { tx_free(s.tx); }
 
 static size_t tx_bytes(const RcTimex& t) {
     return t.sum.bytes + t.ring.bytes + t.avg.bytes + t.bd_idx[0].bytes + t.bd_idx[1].bytes + t.bd_hsv[0].bytes + t.bd_hsv[1].bytes;
 }
 
-static int tx_zero(RcSlot& s) {
-    RcTimex& t = s.tx;
-    RcBuf* all[] = {&t.sum, &t.ring, &t.avg, &t.bd_idx[0], &t.bd_idx[1], &t.bd_hsv[0], &t.bd_hsv[1]};
-    for (RcBuf* b : all)
-        if (b->p) RC_HIP(hipMemsetAsync(b->p, 0, b->bytes, s.cur));
-    // the zeroing runs on the stream the slot has NOW; the first push may come on another one (rcflow_set_hip_stream)
-    if (!t.zeroed) RC_HIP(hipEventCreateWithFlags(&t.zeroed, hipEventDisableTiming));
-    RC_HIP(hipEventRecord(t.zeroed, s.cur));
-    t.zero_stream = s.cur;
-    t.zero_pending = true;
-    t.frames = 0;
-    t.cur = 0;
-    return RC_OK;
+int rc_state_zero(RcSlot& s, RcTimex& t) {
+    const int rc = rc_fence_zero(t.zf, s.cur, {&t.sum, &t.ring, &t.avg, &t.bd_idx[0], &t.bd_idx[1], &t.bd_hsv[0], &t.bd_hsv[1]});
+    if (!rc) t.frames = t.cur = 0;
+    return rc;
 }
 
 extern "C" int rcflow_timex_open(rc_ctx* ctx, int stream, int w, int h, int window, int products) {
@@ -365,16 +299,14 @@ extern "C" int rcflow_timex_open(rc_ctx* ctx, int stream, int w, int h, int wind
         rc_set_error("rcflow_timex_open: window %d outside 1..4096", window);
         return RC_EINVAL;
     }
-    if (w > ctx->max_w || h > ctx->max_h) { rc_set_error("frame exceeds the context size"); return RC_ESIZE; }
+    int rc = rc_fits_context("rcflow_timex_open", ctx, w, h);
+    if (rc) return rc;
     RC_HIP(hipSetDevice(ctx->device));
-    RcTimex& t = s->tx;
-    if (t.open) RC_HIP(hipStreamSynchronize(s->cur));     // launches still reading the state being replaced
-    tx_free(t);
+    RcTimex t;
     t.w = w; t.h = h; t.products = products;
     t.window = ring_products ? window : 0;
     t.pitch = (w + 3) & ~3;
     t.plane = ((size_t)t.pitch * h + 255) & ~(size_t)255;
-    int rc = RC_OK;
     if (products & RC_TIMEX_MEAN) rc = rc_buf_ensure(t.sum, t.plane * 3 * sizeof(float));
     if (!rc && ring_products) rc = rc_buf_ensure(t.ring, t.plane * 3 * (size_t)window);
     if (!rc && (products & RC_TIMEX_AVERAGE)) rc = rc_buf_ensure(t.avg, t.plane * 3 * sizeof(uint16_t));
@@ -383,33 +315,11 @@ extern "C" int rcflow_timex_open(rc_ctx* ctx, int stream, int w, int h, int wind
             rc = rc_buf_ensure(t.bd_idx[i], t.plane * sizeof(uint16_t));
             if (!rc) rc = rc_buf_ensure(t.bd_hsv[i], t.plane * sizeof(uint32_t));
         }
-    if (rc) {                                             // rc_buf_ensure has set the text, with the byte count
-        (void)hipGetLastError();
-        tx_free(t);
-        return rc;
-    }
-    t.open = true;
-    if ((rc = tx_zero(*s))) { tx_free(t); return rc; }
-    return RC_OK;
+    return rc_state_install(*s, s->tx, t, rc);
 }
 
-extern "C" int rcflow_timex_reset(rc_ctx* ctx, int stream) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    if (!s->tx.open) { rc_set_error("rcflow_timex_reset before rcflow_timex_open"); return RC_ESTATE; }
-    RC_HIP(hipSetDevice(ctx->device));
-    return tx_zero(*s);
-}
-
-extern "C" int rcflow_timex_close(rc_ctx* ctx, int stream) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    if (!s->tx.open) return RC_OK;
-    RC_HIP(hipSetDevice(ctx->device));
-    RC_HIP(hipStreamSynchronize(s->cur));
-    tx_free(s->tx);
-    return RC_OK;
-}
+extern "C" int rcflow_timex_reset(rc_ctx* ctx, int stream) { return rc_state_reset(ctx, stream, &RcSlot::tx, "rcflow_timex"); }
+extern "C" int rcflow_timex_close(rc_ctx* ctx, int stream) { return rc_state_close(ctx, stream, &RcSlot::tx); }
 
 extern "C" int rcflow_timex_info(rc_ctx* ctx, int stream, int* w, int* h, int* window, int* products,
                                  long long* frames_pushed, size_t* device_bytes) {
@@ -426,41 +336,34 @@ extern "C" int rcflow_timex_info(rc_ctx* ctx, int stream, int* w, int* h, int* w
     return RC_OK;
 }
 
-static bool tx_overlap(const uint8_t* a, size_t astep, const uint8_t* b, size_t bstep, int w, int h) {
-    const uint8_t* ae = a + (size_t)(h - 1) * astep + (size_t)3 * w;
-    const uint8_t* be = b + (size_t)(h - 1) * bstep + (size_t)3 * w;
-    return a < be && b < ae;
-}
-
 extern "C" int rcflow_timex_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_frame, size_t step, uint8_t* const d_out[4],
                                      const size_t out_step[4]) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
     RcTimex& t = s->tx;
     if (!t.open) { rc_set_error("rcflow_timex_push_dev before rcflow_timex_open"); return RC_ESTATE; }
-    if (!d_frame || step < (size_t)3 * t.w) { rc_set_error("bad frame arguments"); return RC_EINVAL; }
+    static const char* who = "rcflow_timex_push_dev";
+    if (rc_img3_check(who, "d_frame", d_frame, step, t.w, t.h)) return RC_EINVAL;
     uint8_t* out[4] = {nullptr, nullptr, nullptr, nullptr};
     size_t ostep[4] = {0, 0, 0, 0};
     for (int k = 0; k < 4; k++) {
         if (!d_out || !d_out[k]) continue;
         if (!(t.products & (1 << k))) { rc_set_error("d_out[%d] given for a product that is not open", k); return RC_EINVAL; }
-        if (!out_step || out_step[k] < (size_t)3 * t.w) { rc_set_error("bad step of d_out[%d]", k); return RC_EINVAL; }
+        if (rc_img3_check(who, "d_out[k]", d_out[k], out_step ? out_step[k] : 0, t.w, t.h)) return RC_EINVAL;
         out[k] = d_out[k]; ostep[k] = out_step[k];
         // rows are converted in place in registers, but another product's launch still has to read the frame
-        if (tx_overlap(out[k], ostep[k], d_frame, step, t.w, t.h)) { rc_set_error("d_out[%d] overlaps the frame", k); return RC_EINVAL; }
+        if (rc_img3_overlap(out[k], ostep[k], t.w, t.h, d_frame, step, t.w, t.h)) { rc_set_error("d_out[%d] overlaps the frame", k); return RC_EINVAL; }
         for (int j = 0; j < k; j++)
-            if (out[j] && tx_overlap(out[k], ostep[k], out[j], ostep[j], t.w, t.h)) {
+            if (out[j] && rc_img3_overlap(out[k], ostep[k], t.w, t.h, out[j], ostep[j], t.w, t.h)) {
                 rc_set_error("d_out[%d] overlaps d_out[%d]", k, j);
                 return RC_EINVAL;
             }
     }
     RC_HIP(hipSetDevice(ctx->device));
-    if (t.zero_pending) {
-        if (s->cur != t.zero_stream) RC_HIP(hipStreamWaitEvent(s->cur, t.zeroed, 0));
-        t.zero_pending = false;
-    }
-    int rows;
-    const dim3 grid = tx_grid(t.w, t.h, rows);
+    int rc = rc_fence_wait(t.zf, s->cur, true);
+    if (rc) return rc;
+    const int rows = rc_rows_per_wave(t.w, t.h, 2);
+    const dim3 grid = rc_pix3_grid(t.w, t.h, rows);
     const double npx = (double)t.w * t.h;
     t.frames++;
     if (t.products & RC_TIMEX_MEAN) {
@@ -496,14 +399,12 @@ static int tx_convert(rc_ctx* ctx, int stream, const uint8_t* d_in, size_t in_st
                       bool to_hsv) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    if (!d_in || !d_out || w <= 0 || h <= 0 || in_step < (size_t)3 * w || out_step < (size_t)3 * w) {
-        rc_set_error("bad image arguments");
-        return RC_EINVAL;
-    }
-    if (w > ctx->max_w || h > ctx->max_h) { rc_set_error("frame exceeds the context size"); return RC_ESIZE; }
+    const char* who = to_hsv ? "rcflow_rgb_to_hsv_u8_dev" : "rcflow_hsv_to_rgb_u8_dev";
+    if (rc_img3_check(who, "input", d_in, in_step, w, h) || rc_img3_check(who, "output", d_out, out_step, w, h)) return RC_EINVAL;
+    if (rc_fits_context(who, ctx, w, h)) return RC_ESIZE;
     RC_HIP(hipSetDevice(ctx->device));
-    int rows;
-    const dim3 grid = tx_grid(w, h, rows);
+    const int rows = rc_rows_per_wave(w, h, 2);
+    const dim3 grid = rc_pix3_grid(w, h, rows);
     {
         RcProfScope ps(ctx, s->cur, RC_K_COLOR_U8, to_hsv ? 0 : 1, 6. * w * h);
         if (to_hsv) hipLaunchKernelGGL(k_rgb_to_hsv_u8, grid, dim3(RC_BLOCK), 0, s->cur, d_in, in_step, w, h, d_out, out_step, rows);

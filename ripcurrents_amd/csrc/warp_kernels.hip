@@ -10,8 +10,7 @@
 //   perspective  double per pixel, in upstream's blocks of bw0 columns (64 for any real frame) starting at xb:
 //                X0 = M0 xb + M1 y + M2 (Y0, W0 likewise), W = W0 + M6 (x - xb), W = W ? 32 / W : 0,
 //                X = cvRound(max(INT_MIN, min(INT_MAX, (X0 + M0 (x - xb)) W))), then as above.  The bits of X depend on xb.
-// Sample: remap's 8-bit table form, exactly k_stab_warp's: weights (32 - fy)(32 - fx) 32, ... of 2^15,
-// out = (sum + 2^14) >> 15 per channel, a tap outside the source counts 0.
+// Sample: remap's 8-bit table form (rc_pix3_bilinear, shared with k_stab_warp), a tap outside the source counts 0.
 //
 // A lane owns 4 consecutive destination pixels of a row and stores them as one dwordx3 (a w % 4 tail by bytes); a wave
 // owns 256 pixels of one row.  The source is a gather: a pixel whose 2 x 2 footprint (and the byte pair behind it) lies
@@ -22,18 +21,8 @@
 #include <math.h>
 #include <string.h>
 
-#include "rc_device.h"
 #include "rc_host.h"
-
-#define WP_ROWS 4                        // rows per block, one per wave
-static_assert(RC_BLOCK == 64 * WP_ROWS, "a warp block is WP_ROWS waves, one row each");
-
-// pixel (x, y) of the source as byte0 | byte1 << 8 | byte2 << 16; 0 outside the frame (BORDER_CONSTANT, value 0)
-__device__ __forceinline__ uint32_t wp_tap(const RcWarpArgs& a, int x, int y) {
-    if ((unsigned)x >= (unsigned)a.sw || (unsigned)y >= (unsigned)a.sh) return 0u;
-    const uint8_t* p = a.src + (size_t)y * a.step + 3 * (size_t)x;
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
-}
+#include "rc_pix3.h"
 
 __device__ __forceinline__ int wp_sat_short(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
 
@@ -46,7 +35,7 @@ __device__ __forceinline__ double wp_clamp_int(double v) {
 template <int PERSP>
 __global__ __launch_bounds__(RC_BLOCK) void k_warp(const RcWarpArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int y = blockIdx.y * WP_ROWS + wave;
+    const int y = blockIdx.y * RC_PIX3_WAVES + wave;
     const int x0 = 4 * (blockIdx.x * 64 + (threadIdx.x & 63)), n = min(4, a.dw - x0);
     if (y >= a.dh || n <= 0) return;
     double M[9];
@@ -87,34 +76,15 @@ __global__ __launch_bounds__(RC_BLOCK) void k_warp(const RcWarpArgs a) {
         if (sx >= 0 && sx + 2 < a.sw && sy >= 0 && sy + 1 < a.sh) {
             // two pixels = 6 of the 8 bytes; pixel sx + 2 exists, so the load stays inside the row
             const uint8_t* s0 = a.src + (size_t)sy * a.step + 3 * (size_t)sx;
-            uint2 q0, q1;
-            __builtin_memcpy(&q0, s0, 8);
-            __builtin_memcpy(&q1, s0 + a.step, 8);
-            p00 = q0.x & 0xffffffu; p01 = (q0.x >> 24) | ((q0.y & 0xffffu) << 8);
-            p10 = q1.x & 0xffffffu; p11 = (q1.x >> 24) | ((q1.y & 0xffffu) << 8);
+            rc_pix3_unpack2(s0, p00, p01);
+            rc_pix3_unpack2(s0 + a.step, p10, p11);
         } else {
-            p00 = wp_tap(a, sx, sy); p01 = wp_tap(a, sx + 1, sy);
-            p10 = wp_tap(a, sx, sy + 1); p11 = wp_tap(a, sx + 1, sy + 1);
+            p00 = rc_pix3_tap(a.src, a.step, a.sw, a.sh, sx, sy); p01 = rc_pix3_tap(a.src, a.step, a.sw, a.sh, sx + 1, sy);
+            p10 = rc_pix3_tap(a.src, a.step, a.sw, a.sh, sx, sy + 1); p11 = rc_pix3_tap(a.src, a.step, a.sw, a.sh, sx + 1, sy + 1);
         }
-        const int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;
-        o[k] = 0;
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const int sh = 8 * c;
-            const int v = (int)((p00 >> sh) & 255u) * w00 + (int)((p01 >> sh) & 255u) * w01 +
-                          (int)((p10 >> sh) & 255u) * w10 + (int)((p11 >> sh) & 255u) * w11;
-            o[k] |= (uint32_t)((v + (1 << 14)) >> 15) << sh;
-        }
+        o[k] = rc_pix3_bilinear(p00, p01, p10, p11, fx, fy);
     }
-    uint8_t* d = a.dst + (size_t)y * a.dst_step + 3 * (size_t)x0;
-    if (n == 4) {
-        uint32_t q[3] = {o[0] | (o[1] << 24), (o[1] >> 8) | (o[2] << 16), (o[2] >> 16) | (o[3] << 8)};
-        __builtin_memcpy(d, q, 12);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (k < n) { d[3 * k] = (uint8_t)o[k]; d[3 * k + 1] = (uint8_t)(o[k] >> 8); d[3 * k + 2] = (uint8_t)(o[k] >> 16); }
-    }
+    rc_pix3_store4(a.dst + (size_t)y * a.dst_step, x0, n, o);
     // the stabiliser's kept patches: gray float of the corrected frame inside every ROI (they may overlap)
     if (!PERSP && a.patch) {
         for (int r = 0; r < a.npatch; r++) {
@@ -123,8 +93,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_warp(const RcWarpArgs a) {
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 const int px = x0 + k - a.rx[r];
-                if (k < n && (unsigned)px < (unsigned)a.rw)
-                    row[px] = (float)(int)(((o[k] & 255u) * 1868u + ((o[k] >> 8) & 255u) * 9617u + (o[k] >> 16) * 4899u + (1u << 13)) >> 14);
+                if (k < n && (unsigned)px < (unsigned)a.rw) row[px] = rc_pix3_gray(o[k]);
             }
         }
     }
@@ -135,7 +104,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_warp(const RcWarpArgs a) {
 void rc_warp_launch(rc_ctx* ctx, hipStream_t cur, RcWarpArgs& a, bool perspective) {
     const int bh0 = a.dh < 16 ? a.dh : 16;
     a.bw0 = 1024 / bh0 < a.dw ? 1024 / bh0 : a.dw;
-    const dim3 grid(((a.dw + 3) / 4 + 63) / 64, (a.dh + WP_ROWS - 1) / WP_ROWS);
+    const dim3 grid = rc_pix3_grid(a.dw, a.dh, 1);
     // compulsory bytes: the destination once, as many source bytes (the footprint of a near-identity map), the patches
     const double bytes = 6. * a.dw * a.dh + (a.patch ? 4. * a.npatch * a.rw * a.rh : 0.) + (a.d_M ? 48. : 0.);
     RcProfScope ps(ctx, cur, RC_K_FRAMESTAB, perspective ? 9 : 8, bytes);
@@ -143,26 +112,15 @@ void rc_warp_launch(rc_ctx* ctx, hipStream_t cur, RcWarpArgs& a, bool perspectiv
     else hipLaunchKernelGGL(k_warp<0>, grid, dim3(RC_BLOCK), 0, cur, a);
 }
 
-static bool wp_overlap(const uint8_t* a, size_t astep, int aw, int ah, const uint8_t* b, size_t bstep, int bw, int bh) {
-    const uint8_t* ae = a + (size_t)(ah - 1) * astep + (size_t)3 * aw;
-    const uint8_t* be = b + (size_t)(bh - 1) * bstep + (size_t)3 * bw;
-    return a < be && b < ae;
-}
-
 static int wp_check(const char* who, rc_ctx* ctx, const uint8_t* d_bgr, size_t step, int sw, int sh, uint8_t* d_out, size_t out_step,
                     int dw, int dh, const double* M, int nm, int flags) {
-    if (!d_bgr || !d_out || !M || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || step < (size_t)3 * sw || out_step < (size_t)3 * dw) {
-        rc_set_error("%s: bad image arguments (a null pointer, an empty size, or a step below 3 * w)", who);
-        return RC_EINVAL;
-    }
+    if (rc_img3_check(who, "d_bgr", d_bgr, step, sw, sh) || rc_img3_check(who, "d_out", d_out, out_step, dw, dh)) return RC_EINVAL;
+    if (!M) { rc_set_error("%s: no matrix", who); return RC_EINVAL; }
     if (flags & ~RC_WARP_INVERSE_MAP) { rc_set_error("%s: unknown flag bits 0x%x", who, flags & ~RC_WARP_INVERSE_MAP); return RC_EINVAL; }
     for (int i = 0; i < nm; i++)
         if (!isfinite(M[i])) { rc_set_error("%s: matrix entry %d is not finite", who, i); return RC_EINVAL; }
-    if (sw > ctx->max_w || sh > ctx->max_h || dw > ctx->max_w || dh > ctx->max_h) {
-        rc_set_error("%s: source %d x %d or destination %d x %d exceeds the context size", who, sw, sh, dw, dh);
-        return RC_ESIZE;
-    }
-    if (wp_overlap(d_out, out_step, dw, dh, d_bgr, step, sw, sh)) { rc_set_error("%s: d_out overlaps the frame (the warp is not in place)", who); return RC_EINVAL; }
+    if (rc_fits_context(who, ctx, sw, sh) || rc_fits_context(who, ctx, dw, dh)) return RC_ESIZE;
+    if (rc_img3_overlap(d_out, out_step, dw, dh, d_bgr, step, sw, sh)) { rc_set_error("%s: d_out overlaps the frame (the warp is not in place)", who); return RC_EINVAL; }
     return RC_OK;
 }
 

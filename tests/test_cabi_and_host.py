@@ -199,3 +199,14 @@ def test_tile_chain_plan_invariants():
         assert lens[-1] == 1 or pairs <= 1                                    # the launch ends on chains of one
         tail = [l for l in lens if l < max(lens)]
         assert tail == sorted(tail, reverse=True), lens                       # halving tail, never growing again
+
+
+def test_output_validator_refuses_what_is_not_on_the_device():
+    import torch
+    from ripcurrents_amd.api import _check_out
+    dev = torch.device("cuda", 0)
+    for t in (None, np.zeros(3), torch.zeros(3, dtype=torch.float64)):      # no tensor at all; a host tensor
+        with pytest.raises(ValueError):
+            _check_out(t, dev, torch.float64, "out", numel=3)
+        with pytest.raises(ValueError):
+            _check_out(t, dev, torch.float64, "out", shape=(1, 1, 3), dense=True)

@@ -276,6 +276,10 @@ def test_refusals(ctx):
     assert ctx.timex_info()["frames_pushed"] == 1
     with pytest.raises(ValueError):
         ctx.timex_push(torch.zeros((48, 65, 3), dtype=torch.uint8, device="cuda"))
+    from ripcurrents_amd.api import _check_out
+    assert _check_out(out, ctx.device, torch.uint8, "out", shape=(48, 64, 3), dense=True) is out
+    with pytest.raises(ValueError):                                                                       # an image of another GPU
+        _check_out(out, torch.device("cuda", ctx.device.index + 1), torch.uint8, "out", shape=(48, 64, 3), dense=True)
     with pytest.raises(ValueError):
         ctx.timex_open(64, 48, 5, ("median",))
     ctx.timex_close()
