@@ -484,6 +484,115 @@ int rcflow_framestab_read_motion(rc_ctx* ctx, int stream, double motion[6], int*
  * RC_STAB_TRANSLATION, min_response = -infinity (it has no gate), flags = 0.  RC_ESTATE when nothing is open. */
 int rcflow_framestab_info_multi(rc_ctx* ctx, int stream, int* n, int* rois, int cap, int* model, double* min_response, int* flags);
 
+/* ---- Tracked corners and a robust fitted motion (corner_kernels.hip, fit_kernels.hip).
+ *
+ * CORNER CELLS.  One best Shi-Tomasi corner per grid cell of an 8UC1 image (bucketed selection; the greedy
+ * minimum-distance pass of goodFeaturesToTrack is not offered).  All integers:
+ *   dx = (p(x+1,y-1) + 2 p(x+1,y) + p(x+1,y+1)) - (p(x-1,y-1) + 2 p(x-1,y) + p(x-1,y+1)), dy likewise (3 x 3 Sobel pair);
+ *   a = sum dx dx, b = sum dx dy, c = sum dy dy over the 3 x 3 block around the pixel;
+ *   R = (a + c) - ceil(sqrt((a - c)^2 + 4 b^2)), the root exact (int64): twice the smaller eigenvalue of [a b; b c]
+ *   rounded down, the ordering of cv::cornerMinEigenVal(blockSize 3, ksize 3).  R >= 0.
+ * Candidates are the pixels at least `margin` (>= 2) from every border; the candidate rectangle is cut into
+ * cells_x x cells_y cells of floor(width / cells_x) x floor(height / cells_y) pixels, the last column and row taking the
+ * remainder.  Per cell the largest R, ties to the lowest (y, x).  A cell whose best R is 0 or below min_score reports
+ * score 0 and its centre ((x0 + x1 - 1) / 2, (y0 + y1 - 1) / 2).  Output in cell order (row-major): d_pts = cells x
+ * (x, y) float, d_scores = cells int32.  RC_EINVAL: margin < 2, min_score < 0, cells outside 1..RC_CORNER_MAX_CELLS, a
+ * cell side below 8 px; RC_ESIZE beyond the context's size.  One launch ("trackstab@5"), asynchronous. */
+#define RC_CORNER_MAX_CELLS 4096
+int rcflow_corners_dev(rc_ctx* ctx, int stream, const uint8_t* d_gray, size_t step, int w, int h, int cells_x, int cells_y,
+                       int margin, int min_score, float* d_pts, int* d_scores);
+
+/* ROBUST FIT.  From n <= RC_FIT_MAX_POINTS pairs p_i -> q_i (float x, y), a status byte and optionally a score each, the
+ * 3 x 3 double T with q ~ T p, by RANSAC whose sampler is a stated function of (seed, hypothesis, draw): the result is a
+ * function of the input.  Everything below is fp64, one rounding per written operation (no fused multiply-add).
+ *   valid      status == 1, |q - p|^2 <= max_shift^2 (NaN fails) and, when scores are given, score > 0, score >= min_score
+ *              and score >= quality * (the largest of all n scores).  The valid pairs keep their input order.
+ *   sampler    mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 (uint32).
+ *              draw(seed, j, d) = mix(mix(seed + 0x9E3779B9 (j + 1)) + 0x85EBCA6B (d + 1)); index = draw * n_valid >> 32
+ *              (64-bit product).  Hypothesis j takes draws d = 0, 1, ... and skips an index it already holds; without its
+ *              k distinct indices after 16 draws, or with n_valid < k, it is void (0 inliers).  k = 1, 2, 3, 4 pairs for
+ *              RC_STAB_TRANSLATION, _SIMILARITY, _AFFINE, _HOMOGRAPHY.
+ *   coordinates  S = max(w, h), c = (w / 2, h / 2): P = (p - c) / S, Q = (q - c) / S, D = (q - p) / S.  The DISPLACEMENT
+ *              is fitted, E = T_norm - I, so a still scene gives T = I exactly.
+ *   solve      translation: E = [0 0 mean Dx; 0 0 mean Dy].  Similarity / affine: the closed forms of
+ *              rcflow_framestab_open_multi above on P centred on its mean and D centred on its mean (affine needs
+ *              det > 1e-12 Sxx Syy, similarity Sxx + Syy > 0).  Homography: unknowns z = (e00 e01 e02 e10 e11 e12 g0 g1),
+ *              rows [Px Py 1 0 0 0 -Qx Px -Qx Py | Dx] and [0 0 0 Px Py 1 -Qy Px -Qy Py | Dy]; the minimal sample is the
+ *              8 x 8 system solved by Gaussian elimination with partial pivoting (first largest |pivot|; void below 1e-9),
+ *              row update m[r][k] - f m[c][k] with f = m[r][c] / m[c][c], back substitution s - m[c][k] z[k] for
+ *              ascending k.  A least-squares homography solves the normal equations (entry (r, k) = sum of
+ *              r1[r] r1[k] + r2[r] r2[k]) by the same elimination (fails below 1e-12).
+ *   to pixels  F[i][0] = E[i][0] / S, F[i][1] = E[i][1] / S, F[i][2] = E[i][2] - (E[i][0] cx + E[i][1] cy) / S;
+ *              G[0][j] = S F[0][j] + cx F[2][j], G[1][j] = S F[1][j] + cy F[2][j], G[2][j] = F[2][j]; T = I + G; a
+ *              homography is divided by T[8], which must exceed 0.1.  Any entry not finite: the solve failed.
+ *   inlier     X = (T0 px + T1 py) + T2, Y, W likewise; W > 0 and (X / W - qx)^2 + (Y / W - qy)^2 <= inlier_px^2.
+ *   best       most inliers, ties to the lowest hypothesis index.
+ *   refit      by the workgroup that finishes last: least squares of the model on the winner's inliers, recount under
+ *              the refit, refit again, recount.  Sums run over the valid list in a fixed order: partial sum t of 256 adds
+ *              the terms of the pairs t, t + 256, ... (0.0 for a pair that is no inlier); each group of 64 partial sums is
+ *              folded by halves (v[i] + v[i + 32], then 16, ... 1); the four results are added as ((s0 + s1) + s2) + s3.
+ *   ladder     the model needs max(2 k, k + 2) inliers after the refits (3, 4, 6, 8) and solves that succeed; else the
+ *              next simpler model is fitted once to the inliers at hand and recounted, down to the identity with
+ *              model_used = 0 (the inliers are then those of the identity).  When every hypothesis is void (all samples
+ *              degenerate, e.g. collinear pairs under RC_STAB_AFFINE) there is no inlier to step down with: the identity.
+ * Defaults: hypotheses 0 = RC_FIT_DEFAULT_HYPOTHESES, max_shift 0 = 0.1 max(w, h), inlier_px 0 = 1.  Output on the
+ * device: *d_result, d_inlier[n] (1 for an inlier of the final T), d_samples (may be NULL) = hypotheses x 4 input
+ * indices, -1 where unused or void.  RC_EINVAL: n outside 0..RC_FIT_MAX_POINTS, an unknown model, hypotheses beyond
+ * RC_FIT_MAX_HYPOTHESES, a gate that is negative or not finite, quality outside 0..1, a null pointer.  One launch
+ * ("trackstab@4"), asynchronous; calls on one slot are ordered by its stream. */
+#define RC_STAB_HOMOGRAPHY 4
+#define RC_FIT_MAX_POINTS 4096
+#define RC_FIT_MAX_HYPOTHESES 4096
+#define RC_FIT_DEFAULT_HYPOTHESES 512
+typedef struct rc_fit_params {
+    int model, hypotheses;
+    unsigned seed;
+    int min_score;
+    double quality, max_shift, inlier_px;
+} rc_fit_params;
+typedef struct rc_fit_result {
+    double T[9];
+    int model_used, n_valid, n_inliers, winner;
+} rc_fit_result;
+int rcflow_fit_motion_dev(rc_ctx* ctx, int stream, const float* d_p, const float* d_q, const uint8_t* d_status,
+                          const int* d_scores /* may be NULL */, int n, int w, int h, const rc_fit_params* prm,
+                          rc_fit_result* d_result, uint8_t* d_inlier, int* d_samples /* may be NULL */);
+
+/* A stabilisation slot that finds its own points: corners of the reference frame, tracked into the incoming frame by the
+ * sparse PyrLK of rcflow_pyrlk_dev, a robust fit of the tracks, the warp.  Served by rcflow_framestab_push_dev / _read /
+ * _reset / _close like the other two forms; no host synchronisation and no device-to-host copy in a push:
+ *   gray of the incoming frame (COLOR_BGR2GRAY, 14-bit fixed point)   "trackstab@0"
+ *   its pyramid                                                        "trackstab@1" per level
+ *   PyrLK from the kept corners of the reference frame                 "trackstab@3" (err not computed, min eigenvalue 1e-4)
+ *   the fit above on (corner, track, status, corner score)             "trackstab@4"
+ *   dst(p) = src(T p): the affine warp ("framestab@8") or, when the model asked for is RC_STAB_HOMOGRAPHY, the
+ *   perspective warp ("framestab@9"), reading T from device memory
+ *   unless RC_STAB_ANCHOR_FIRST: gray, pyramid, Scharr derivatives ("trackstab@2") and corner cells ("trackstab@5") of
+ *   the CORRECTED frame, kept for the next push.  Anchored, those of the first frame are kept for good.
+ * cells 0 x 0: cells of about `side` x `side` px, side = 40 raised in steps of 8 until round(w / side) round(h / side)
+ * <= RC_CORNER_MAX_CELLS (16 x 12 at 640 x 480).  margin = win / 2 + 2.  win 0: 21; max_level < 0: 3; max_count 0: 30;
+ * epsilon 0: 0.01; min_score 0: 1.  The first push after open / reset copies the frame and reports the identity and zeros.
+ * rcflow_framestab_read / d_result give the displacement of the frame centre under T and n_inliers / n_valid (0 when
+ * none).  rcflow_framestab_read_motion returns the 2 x 3 of T, RC_EINVAL when the model used was a homography;
+ * rcflow_framestab_info_multi reports n = 0; rcflow_framestab_info reports roi = the candidate rectangle.
+ * RC_EINVAL: a bad frame size, a null params, win even or outside 3..63, max_level > 7, an unknown model or flag bit, gates
+ * as rcflow_fit_motion_dev, cells as rcflow_corners_dev; RC_ESIZE beyond the context's size.  A refused open leaves the
+ * slot's state as it was. */
+typedef struct rc_stab_tracks {
+    int cells_x, cells_y;
+    int min_score; double quality;
+    int win, max_level, max_count; double epsilon;
+    double max_shift;
+    int model, hypotheses; unsigned seed; double inlier_px;
+    int flags;
+} rc_stab_tracks;
+int rcflow_framestab_open_tracks(rc_ctx* ctx, int stream, int w, int h, const rc_stab_tracks* prm);
+/* Blocks until the slot's stream has finished.  Any pointer may be NULL.  pts = min(cells, cap) x (px, py, qx, qy): the
+ * corner in the reference frame and its track in the last frame pushed; inlier = one byte each; cells = their number.
+ * Before the second push: the identity and zeros.  RC_ESTATE unless the slot was opened by rcflow_framestab_open_tracks. */
+int rcflow_framestab_read_tracks(rc_ctx* ctx, int stream, double T[9], int* model_used, int* n_valid, int* n_inliers,
+                                 float* pts, uint8_t* inlier, int* scores, int cap, int* cells, long long* frames_pushed);
+
 /* ------------------------------------------------------------------ time-exposure images
  * compute_timex (main.cpp:1195-1263) and compute_brightColor (main.cpp:1265-1383) on frames resident on the device.
  * All images are 8UC3; "channel 0 / 1 / 2" are the bytes as they come (the reference feeds BGR frames to

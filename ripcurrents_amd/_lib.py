@@ -21,6 +21,10 @@ TIMEX_PRODUCTS = {"mean": 1, "average": 2, "bright": 4, "dark": 8}
 RC_WARP_INVERSE_MAP = 16
 # RC_STAB_*: the motion models of rcflow_framestab_open_multi, and its one flag
 STAB_MODELS = {"translation": 1, "similarity": 2, "affine": 3}
+# rcflow_fit_motion_dev / rcflow_framestab_open_tracks add the homography
+FIT_MODELS = dict(STAB_MODELS, homography=4)
+RC_CORNER_MAX_CELLS = 4096
+RC_FIT_MAX_POINTS = 4096
 RC_STAB_ANCHOR_FIRST = 1
 RC_STAB_MAX_PATCHES = 16
 # rcflow_ripmap_open: its one flag, and the source names
@@ -49,6 +53,26 @@ class FrameLoop(C.Structure):
                 ("seed_variant", C.c_int), ("seed_dt", C.c_float), ("seed_iterations", C.c_int), ("seed_upper", C.c_float),
                 ("MID", C.c_float), ("LOWER", C.c_float), ("d_outmask", C.c_void_p), ("mask_step", C.c_size_t),
                 ("d_edges", C.c_void_p), ("edges_step", C.c_size_t), ("use_graph", C.c_int)]
+
+
+class FitParams(C.Structure):
+    """rc_fit_params (include/rcflow.h)."""
+    _fields_ = [("model", C.c_int), ("hypotheses", C.c_int), ("seed", C.c_uint), ("min_score", C.c_int),
+                ("quality", C.c_double), ("max_shift", C.c_double), ("inlier_px", C.c_double)]
+
+
+class FitResult(C.Structure):
+    """rc_fit_result (include/rcflow.h): 88 bytes on the device."""
+    _fields_ = [("T", C.c_double * 9), ("model_used", C.c_int), ("n_valid", C.c_int), ("n_inliers", C.c_int),
+                ("winner", C.c_int)]
+
+
+class StabTracks(C.Structure):
+    """rc_stab_tracks (include/rcflow.h)."""
+    _fields_ = [("cells_x", C.c_int), ("cells_y", C.c_int), ("min_score", C.c_int), ("quality", C.c_double),
+                ("win", C.c_int), ("max_level", C.c_int), ("max_count", C.c_int), ("epsilon", C.c_double),
+                ("max_shift", C.c_double), ("model", C.c_int), ("hypotheses", C.c_int), ("seed", C.c_uint),
+                ("inlier_px", C.c_double), ("flags", C.c_int)]
 
 
 _vp, _sz, _i, _f, _d = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_double
@@ -125,6 +149,11 @@ SIGNATURES = {
     "rcflow_framestab_open_multi": [_vp, _i, _i, _i, C.POINTER(_i), _i, _i, _d, _i],
     "rcflow_framestab_read_motion": [_vp, _i, C.POINTER(_d), C.POINTER(_i), C.POINTER(_i), C.POINTER(_d), C.POINTER(C.c_longlong)],
     "rcflow_framestab_info_multi": [_vp, _i, C.POINTER(_i), C.POINTER(_i), _i, C.POINTER(_i), C.POINTER(_d), C.POINTER(_i)],
+    "rcflow_corners_dev": [_vp, _i, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp, _vp],
+    "rcflow_fit_motion_dev": [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(FitParams), _vp, _vp, _vp],
+    "rcflow_framestab_open_tracks": [_vp, _i, _i, _i, C.POINTER(StabTracks)],
+    "rcflow_framestab_read_tracks": [_vp, _i, C.POINTER(_d), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _vp, _vp, _vp, _i,
+                                     C.POINTER(_i), C.POINTER(C.c_longlong)],
     "rcflow_timex_open": [_vp, _i, _i, _i, _i, _i],
     "rcflow_timex_push_dev": [_vp, _i, _vp, _sz, C.POINTER(_vp), C.POINTER(_sz)],
     "rcflow_timex_reset": [_vp, _i],

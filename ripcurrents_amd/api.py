@@ -25,7 +25,7 @@ import torch
 
 from . import _lib
 from ._lib import FarnebackParams, HIST_BINS, HIST_DIRECTIONS, HIST_WORDS, RC_FARNEBACK_USE_INITIAL_FLOW, TIMEX_PRODUCTS, RcflowError, check
-from ._lib import RC_STAB_ANCHOR_FIRST, RC_STAB_MAX_PATCHES, RC_WARP_INVERSE_MAP, STAB_MODELS
+from ._lib import RC_STAB_ANCHOR_FIRST, RC_STAB_MAX_PATCHES, RC_WARP_INVERSE_MAP, STAB_MODELS, FIT_MODELS, FitParams, StabTracks
 from ._lib import RC_RIPMAP_WAIT_FULL, RIPMAP_SOURCES
 
 __all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState"]
@@ -850,7 +850,7 @@ class Context:
         used, cnt, frames = C.c_int(0), C.c_int(0), C.c_longlong(0)
         self._bind(stream)
         check(self._lib.rcflow_framestab_read_motion(self._h, stream, mo, C.byref(used), C.byref(cnt), sh, C.byref(frames)))
-        names = {v: k for k, v in STAB_MODELS.items()}
+        names = {v: k for k, v in FIT_MODELS.items()}
         return dict(motion=np.array(mo[:]).reshape(2, 3), model_used=names.get(used.value), patches_used=cnt.value,
                     shifts=np.array(sh[:3 * n.value]).reshape(n.value, 3), frames_pushed=frames.value,
                     rois=[tuple(rois[4 * k:4 * k + 4]) for k in range(n.value)], model=names[model.value],
@@ -900,6 +900,99 @@ class Context:
     def framestab_close(self, stream=0):
         self._bind(stream)          # waits for the pushes queued on that stream before freeing
         check(self._lib.rcflow_framestab_close(self._h, stream))
+
+    # ------------------------------------------------------------------ tracked corners, a robust fitted motion
+    def corners(self, gray, cells=(16, 12), margin=12, min_score=1, pts=None, scores=None, stream=0):
+        """One best Shi-Tomasi corner per grid cell of an 8UC1 image (include/rcflow.h states the integer response and the
+        cells) -> (pts [cells, 2] float32 (x, y), scores [cells] int32; 0 and the cell centre for a cell without a
+        corner), on the device, in cell order.  `pts`, `scores` (optional): tensors to write."""
+        g = self._dev(gray, torch.uint8)
+        if g.dim() != 2:
+            raise ValueError("expected a 2-D uint8 image")
+        g = g if g.stride(1) == 1 else g.contiguous()
+        h, w = g.shape
+        n = int(cells[0]) * int(cells[1])
+        if pts is None:
+            pts = torch.empty((max(n, 0), 2), dtype=torch.float32, device=self.device)
+        else:
+            _check_out(pts, self.device, torch.float32, "pts", shape=(n, 2))
+        if scores is None:
+            scores = torch.empty((max(n, 0),), dtype=torch.int32, device=self.device)
+        else:
+            _check_out(scores, self.device, torch.int32, "scores", shape=(n,))
+        self._bind(stream)
+        check(self._lib.rcflow_corners_dev(self._h, stream, self._ptr(g), g.stride(0), w, h, int(cells[0]), int(cells[1]), int(margin),
+                                           int(min_score), self._ptr(pts), self._ptr(scores)))
+        return pts, scores
+
+    def fit_motion(self, p, q, status, size, scores=None, model="similarity", hypotheses=0, seed=0, min_score=0, quality=0.0,
+                   max_shift=0.0, inlier_px=0.0, want_samples=False, stream=0):
+        """Robust fit of q ~ T p over point pairs (RANSAC with the stated counter-based sampler, two least-squares refits,
+        the ladder; include/rcflow.h).  p, q: [n, 2] float32; status: [n] uint8; scores: [n] int32 or None; size = (w, h).
+        Waits for the stream -> dict(T (3 x 3 float64), model_used (name or None), n_valid, n_inliers, winner,
+        inlier ([n] uint8), samples ([hypotheses, 4] int32 when asked for))."""
+        if model not in FIT_MODELS:
+            raise ValueError("model must be one of %s" % sorted(FIT_MODELS))
+        tp = self._dev(p, torch.float32).reshape(-1, 2).contiguous()
+        tq = self._dev(q, torch.float32).reshape(-1, 2).contiguous()
+        ts = self._dev(status, torch.uint8).reshape(-1).contiguous()
+        n = tp.shape[0]
+        if tq.shape[0] != n or ts.shape[0] != n:
+            raise ValueError("p, q and status differ in length")
+        tsc = None
+        if scores is not None:
+            tsc = self._dev(scores, torch.int32).reshape(-1).contiguous()
+            if tsc.shape[0] != n:
+                raise ValueError("scores and p differ in length")
+        prm = FitParams(FIT_MODELS[model], int(hypotheses), int(seed) & 0xffffffff, int(min_score), float(quality), float(max_shift),
+                        float(inlier_px))
+        res = torch.zeros(11, dtype=torch.float64, device=self.device)
+        inl = torch.zeros(max(n, 1), dtype=torch.uint8, device=self.device)
+        nh = int(hypotheses) if hypotheses else 512
+        smp = torch.full((max(nh, 1), 4), -1, dtype=torch.int32, device=self.device) if want_samples else None
+        self._bind(stream)
+        check(self._lib.rcflow_fit_motion_dev(self._h, stream, self._ptr(tp), self._ptr(tq), self._ptr(ts),
+                                              self._ptr(tsc) if tsc is not None else C.c_void_p(None), n, int(size[0]), int(size[1]),
+                                              C.byref(prm), self._ptr(res), self._ptr(inl),
+                                              self._ptr(smp) if smp is not None else C.c_void_p(None)))
+        self.sync(stream)
+        raw = res.cpu().numpy()
+        ints = raw[9:].view(np.int32)
+        names = {v: k for k, v in FIT_MODELS.items()}
+        out = dict(T=raw[:9].reshape(3, 3).copy(), model_used=names.get(int(ints[0])), n_valid=int(ints[1]), n_inliers=int(ints[2]),
+                   winner=int(ints[3]), inlier=inl[:n].cpu().numpy())
+        if smp is not None:
+            out["samples"] = smp.cpu().numpy()
+        return out
+
+    def framestab_open_tracks(self, w, h, model="similarity", cells=(0, 0), min_score=0, quality=0.0, win=21, max_level=3, max_count=30,
+                              epsilon=0.01, max_shift=0.0, hypotheses=0, seed=0, inlier_px=0.0, anchor="previous", stream=0):
+        """Opens the slot's stabilisation state in its tracking form: corners of the reference frame chosen on the device
+        (one per grid cell), tracked by PyrLK, a robust fit (model "translation" | "similarity" | "affine" | "homography"),
+        the warp.  framestab_push / _read / _reset / _close serve it; framestab_read_tracks returns T and the tracks.
+        cells (0, 0): about 40 x 40 px each; anchor as framestab_open."""
+        if model not in FIT_MODELS or anchor not in ("previous", "first"):
+            raise ValueError("model must be one of %s, anchor \"previous\" or \"first\"" % sorted(FIT_MODELS))
+        prm = StabTracks(int(cells[0]), int(cells[1]), int(min_score), float(quality), int(win), int(max_level), int(max_count),
+                         float(epsilon), float(max_shift), FIT_MODELS[model], int(hypotheses), int(seed) & 0xffffffff, float(inlier_px),
+                         RC_STAB_ANCHOR_FIRST if anchor == "first" else 0)
+        self._bind(stream)
+        check(self._lib.rcflow_framestab_open_tracks(self._h, stream, int(w), int(h), C.byref(prm)))
+
+    def framestab_read_tracks(self, stream=0):
+        """Waits for the slot's stream -> dict(T (3 x 3: corrected(p) = frame(T p)), model_used (name or None), n_valid,
+        n_inliers, pts ([cells, 4]: corner x, y in the reference frame, its track x, y), inlier, scores, frames_pushed)."""
+        cells, used, nv, ni, frames = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_longlong(0)
+        T = (C.c_double * 9)()
+        self._bind(stream)
+        check(self._lib.rcflow_framestab_read_tracks(self._h, stream, None, None, None, None, None, None, None, 0, C.byref(cells), None))
+        n = cells.value
+        pts, inl, sc = np.zeros((n, 4), np.float32), np.zeros(n, np.uint8), np.zeros(n, np.int32)
+        check(self._lib.rcflow_framestab_read_tracks(self._h, stream, T, C.byref(used), C.byref(nv), C.byref(ni), pts.ctypes.data,
+                                                     inl.ctypes.data, sc.ctypes.data, n, C.byref(cells), C.byref(frames)))
+        names = {v: k for k, v in FIT_MODELS.items()}
+        return dict(T=np.array(T[:]).reshape(3, 3), model_used=names.get(used.value), n_valid=nv.value, n_inliers=ni.value, pts=pts,
+                    inlier=inl, scores=sc, frames_pushed=frames.value)
 
     # ------------------------------------------------------------------ the opposing-flow map
     def ripmap_open(self, w, h, window=300, grid=(30, 30), source="flow", wait_full=False, stream=0):

@@ -247,6 +247,68 @@ static int lk_levels(int w, int h, int win_w, int win_h, int max_level) {
     return max_level;
 }
 
+// ---------------------------------------------------------------------------- the two halves of a PyrLK call
+// plan: levels 0..top of one image's pyramid, packed (pitch = level width), with or without the Scharr derivatives
+RcLkPyr rc_lk_plan(int w, int h, int win_w, int win_h, int max_level, bool deriv) {
+    RcLkPyr q;
+    memset(&q, 0, sizeof(q));
+    q.top = lk_levels(w, h, win_w, win_h, max_level);
+    q.deriv = deriv;
+    q.lw[0] = w; q.lh[0] = h;
+    for (int l = 1; l <= q.top; l++) { q.lw[l] = (q.lw[l - 1] + 1) / 2; q.lh[l] = (q.lh[l - 1] + 1) / 2; }
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    for (int l = 0; l <= q.top; l++) {
+        q.offI[l] = take((size_t)q.lw[l] * q.lh[l]);
+        if (deriv) q.offD[l] = take((size_t)q.lw[l] * q.lh[l] * 4);
+    }
+    q.bytes = off;
+    return q;
+}
+
+// levels 1..top (and the derivatives of every level) of the image whose level 0 lies at base + offI[0].
+// "trackstab@1" a pyrDown, "trackstab@2" a Scharr launch
+void rc_lk_build(rc_ctx* ctx, hipStream_t cur, const RcLkPyr& q, unsigned char* base) {
+    for (int l = 0; l <= q.top; l++) {
+        const dim3 g((q.lw[l] + 63) / 64, (q.lh[l] + 3) / 4);
+        if (l > 0) {
+            RcProfScope ps(ctx, cur, RC_K_TRACKSTAB, 1, 1.25 * q.lw[l - 1] * q.lh[l - 1]);
+            hipLaunchKernelGGL(k_lk_pyrdown, g, dim3(RC_BLOCK), 0, cur, base + q.offI[l - 1], (size_t)q.lw[l - 1], q.lw[l - 1], q.lh[l - 1],
+                               base + q.offI[l], q.lw[l], q.lh[l]);
+        }
+        if (q.deriv) {
+            RcProfScope ps(ctx, cur, RC_K_TRACKSTAB, 2, 5. * q.lw[l] * q.lh[l]);
+            hipLaunchKernelGGL(k_lk_scharr, g, dim3(RC_BLOCK), 0, cur, base + q.offI[l], (size_t)q.lw[l], q.lw[l], q.lh[l],
+                               (int16_t*)(base + q.offD[l]));
+        }
+    }
+}
+
+// "trackstab@3": npts points from the pyramid `ref` (with derivatives) at ref_base into the pyramid `cur` at cur_base.
+// max_count and epsilon as SparsePyrLKOpticalFlowImpl::calc leaves them (clamped; epsilon NOT yet squared)
+void rc_lk_track(rc_ctx* ctx, hipStream_t cur_stream, const RcLkPyr& ref, const unsigned char* ref_base, const unsigned char* cur_base,
+                 const RcLkPyr& cur, const float* d_prev_pts, float* d_next_pts, int npts, uint8_t* d_status, float* d_err, int win_w, int win_h,
+                 int max_count, double epsilon, int flags, double min_eig_threshold) {
+    RcLkArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int l = 0; l <= ref.top; l++) {
+        a.lv[l].I = ref_base + ref.offI[l];
+        a.lv[l].J = cur_base + cur.offI[l];
+        a.lv[l].dI = (const int16_t*)(ref_base + ref.offD[l]);
+        a.lv[l].w = ref.lw[l]; a.lv[l].h = ref.lh[l];
+    }
+    a.max_level = ref.top;
+    a.prev_pts = (const float2*)d_prev_pts; a.next_pts = (float2*)d_next_pts;
+    a.status = d_status; a.err = d_err;
+    a.npts = npts; a.win_w = win_w; a.win_h = win_h; a.max_count = max_count; a.flags = flags;
+    a.epsilon = epsilon * epsilon; a.min_eig = min_eig_threshold;
+    const int win_n = win_w * win_h;
+    size_t lds = 3 * RC_LK_THREADS * sizeof(long long) + (size_t)((win_n + 1) & ~1) * sizeof(short) + (size_t)win_n * sizeof(short2);
+    RC_ALLOW_LDS((k_lk_track), lds);
+    RcProfScope ps(ctx, cur_stream, RC_K_TRACKSTAB, 3, 21. * npts);
+    hipLaunchKernelGGL(k_lk_track, dim3(npts), dim3(RC_LK_THREADS), lds, cur_stream, a);
+}
+
 extern "C" int rcflow_pyrlk_levels(int w, int h, int win_w, int win_h, int max_level) {
     if (w < 1 || h < 1 || win_w < 3 || win_h < 3 || max_level < 0) return RC_EINVAL;
     return lk_levels(w, h, win_w, win_h, max_level);
@@ -273,54 +335,19 @@ extern "C" int rcflow_pyrlk_dev(rc_ctx* ctx, int stream, const uint8_t* d_prev, 
     else max_count = max_count < 0 ? 0 : (max_count > 100 ? 100 : max_count);
     if ((crit_type & 2) == 0) epsilon = 0.01;
     else epsilon = epsilon < 0. ? 0. : (epsilon > 10. ? 10. : epsilon);
-    epsilon *= epsilon;
     RC_HIP(hipSetDevice(ctx->device));
-    const int top = lk_levels(w, h, win_w, win_h, max_level);
-
-    // scratch: levels 1..top of both pyramids (u8) and the derivatives of every prev level
-    size_t off = 0, offI[RC_LK_MAX_LEVELS] = {0}, offJ[RC_LK_MAX_LEVELS] = {0}, offD[RC_LK_MAX_LEVELS] = {0};
-    int lw[RC_LK_MAX_LEVELS], lh[RC_LK_MAX_LEVELS];
-    lw[0] = w; lh[0] = h;
-    for (int l = 1; l <= top; l++) { lw[l] = (lw[l - 1] + 1) / 2; lh[l] = (lh[l - 1] + 1) / 2; }
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    // level 0 is copied tightly too (pitch = w) so that the tracker has one addressing form
-    for (int l = 0; l <= top; l++) {
-        offI[l] = take((size_t)lw[l] * lh[l]);
-        offJ[l] = take((size_t)lw[l] * lh[l]);
-        offD[l] = take((size_t)lw[l] * lh[l] * 4);
-    }
-    int rc = rc_buf_ensure(s->lk, off);
+    // scratch: both pyramids (u8; level 0 is copied tightly too, pitch = w, so that the tracker has one addressing form)
+    // and the derivatives of every prev level
+    const RcLkPyr ref = rc_lk_plan(w, h, win_w, win_h, max_level, true), cur = rc_lk_plan(w, h, win_w, win_h, max_level, false);
+    int rc = rc_buf_ensure(s->lk, ref.bytes + cur.bytes);
     if (rc) return rc;
     unsigned char* base = (unsigned char*)s->lk.p;
-    RC_HIP(hipMemcpy2DAsync(base + offI[0], w, d_prev, prev_step, w, h, hipMemcpyDeviceToDevice, s->cur));
-    RC_HIP(hipMemcpy2DAsync(base + offJ[0], w, d_next, next_step, w, h, hipMemcpyDeviceToDevice, s->cur));
-    RcLkArgs a;
-    memset(&a, 0, sizeof(a));
-    for (int l = 0; l <= top; l++) {
-        if (l > 0) {
-            dim3 g((lw[l] + 63) / 64, (lh[l] + 3) / 4);
-            hipLaunchKernelGGL(k_lk_pyrdown, g, dim3(RC_BLOCK), 0, s->cur, base + offI[l - 1], (size_t)lw[l - 1], lw[l - 1],
-                               lh[l - 1], base + offI[l], lw[l], lh[l]);
-            hipLaunchKernelGGL(k_lk_pyrdown, g, dim3(RC_BLOCK), 0, s->cur, base + offJ[l - 1], (size_t)lw[l - 1], lw[l - 1],
-                               lh[l - 1], base + offJ[l], lw[l], lh[l]);
-        }
-        dim3 g((lw[l] + 63) / 64, (lh[l] + 3) / 4);
-        hipLaunchKernelGGL(k_lk_scharr, g, dim3(RC_BLOCK), 0, s->cur, base + offI[l], (size_t)lw[l], lw[l], lh[l],
-                           (int16_t*)(base + offD[l]));
-        a.lv[l].I = base + offI[l];
-        a.lv[l].J = base + offJ[l];
-        a.lv[l].dI = (const int16_t*)(base + offD[l]);
-        a.lv[l].w = lw[l]; a.lv[l].h = lh[l];
-    }
-    a.max_level = top;
-    a.prev_pts = (const float2*)d_prev_pts; a.next_pts = (float2*)d_next_pts;
-    a.status = d_status; a.err = d_err;
-    a.npts = npts; a.win_w = win_w; a.win_h = win_h; a.max_count = max_count; a.flags = flags;
-    a.epsilon = epsilon; a.min_eig = min_eig_threshold;
-    const int win_n = win_w * win_h;
-    size_t lds = 3 * RC_LK_THREADS * sizeof(long long) + (size_t)((win_n + 1) & ~1) * sizeof(short) + (size_t)win_n * sizeof(short2);
-    RC_ALLOW_LDS((k_lk_track), lds);
-    hipLaunchKernelGGL(k_lk_track, dim3(npts), dim3(RC_LK_THREADS), lds, s->cur, a);
+    RC_HIP(hipMemcpy2DAsync(base + ref.offI[0], w, d_prev, prev_step, w, h, hipMemcpyDeviceToDevice, s->cur));
+    RC_HIP(hipMemcpy2DAsync(base + ref.bytes + cur.offI[0], w, d_next, next_step, w, h, hipMemcpyDeviceToDevice, s->cur));
+    rc_lk_build(ctx, s->cur, ref, base);
+    rc_lk_build(ctx, s->cur, cur, base + ref.bytes);
+    rc_lk_track(ctx, s->cur, ref, base, base + ref.bytes, cur, d_prev_pts, d_next_pts, npts, d_status, d_err, win_w, win_h,
+                max_count, epsilon, flags, min_eig_threshold);
     RC_HIP(hipGetLastError());
     return RC_OK;
 }

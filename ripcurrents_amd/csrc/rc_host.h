@@ -42,6 +42,13 @@ struct RcAnalysis {
     RcBuf loopc;       // one int32: framecount of rcflow_frame_loop_step (incremented on the device)
 };
 
+// lk_kernels.hip: the two halves of a PyrLK call (pyramid of one image; track), for the tracking stabiliser
+struct RcLkPyr {
+    int top; bool deriv;
+    int lw[8], lh[8];
+    size_t offI[8], offD[8], bytes;
+};
+
 // open / reset zero a product's state asynchronously on the stream the slot has then; whoever touches the state next
 // waits for this event when the slot has been moved to another stream in between (rcflow_set_hip_stream)
 struct RcZeroFence {
@@ -85,7 +92,17 @@ struct RcFrameStab {
     int n = 0, model = 0, flags = 0;
     double min_response = 0.;
     int px[RC_STAB_MAX_PATCHES] = {}, py[RC_STAB_MAX_PATCHES] = {};
+    // rcflow_framestab_open_tracks (tracks = false: one of the two forms above).  res holds RC_FT_* doubles
+    bool tracks = false;
+    rc_stab_tracks tp{};            // the parameters with every default resolved
+    int ncells = 0, margin = 0;
+    RcLkPyr ref{}, cur{};           // pyramid plans: the reference frame (with derivatives), the incoming frame
+    RcBuf lkref, lkcur;             // their bytes
+    RcBuf trk;                      // corners [2][ncells] float2 | tracks | scores [2][ncells] int | status | inlier (stab_kernels.hip)
+    int pcur = 0; bool pflip = false;   // the corner slot in use; a chained push left the next corners in the other one
 };
+// layout of RcFrameStab::res for a tracks slot, in doubles: the result of rcflow_framestab_read, rc_fit_result, the fit's two words
+enum { RC_FT_RESULT = 0 /* 3 */, RC_FT_FIT = 4 /* 11 */, RC_FT_WS = 16 /* 2 */, RC_FT_DOUBLES = 18 };
 // layout of RcFrameStab::res for a multi-patch slot, in doubles
 enum { RC_FS_RESULT = 0 /* 3 */, RC_FS_MOTION = 3 /* 6 */, RC_FS_USED = 9 /* int model_used, patches_used */,
        RC_FS_TICKET = 10 /* unsigned arrivals of the running correlate launch */, RC_FS_SHIFTS = 16 /* n x 3 */ };
@@ -113,7 +130,7 @@ struct RcWarpArgs {
     uint8_t* dst; size_t dst_step;
     int sw, sh, dw, dh;
     double M[9];                         // destination to source; affine: M[0..5]
-    const double* d_M;                   // affine: the six entries on the device instead (the stabiliser's fit), or null
+    const double* d_M;                   // the matrix on the device instead (the stabiliser's fit; affine 6, perspective 9 entries), or null
     int bw0;                             // perspective: columns per block of upstream's tiling (set by rc_warp_launch)
     float* patch;                        // affine: [npatch][rh][rw] gray float of the OUTPUT inside each ROI, or null
     int npatch, rw, rh;
@@ -161,6 +178,7 @@ struct RcSlot {
     int flow_w = 0, flow_h = 0;   // size of the flow field resident in stage_flow (0: none yet)
     int flow_fresh = 0;           // stage_flow holds the flow of the stream's PREVIOUS pair (the warm start of RC_FARNEBACK_USE_INITIAL_FLOW)
     RcBuf lk;                  // sparse PyrLK pyramids + derivatives (lk_kernels.hip)
+    RcBuf fit_ws;              // rcflow_fit_motion_dev: best and ticket of the running launch (fit_kernels.hip)
     RcBuf area_tab;            // INTER_AREA decimation tables
     RcBuf seed, seed_tab;      // RC_FARNEBACK_USE_INITIAL_FLOW: the initial field at the coarsest scale [pairs][h_k][w_k] float2, its tables
     int primed = 0, cur_slot = 0;
@@ -223,7 +241,8 @@ enum { RC_K_PYR = 0, RC_K_POLY = 1, RC_K_ITER = 2, RC_K_HIST = 3, RC_K_THRESH = 
        RC_K_FRAMESTAB = 19 /* @0 correlate in one workgroup, @1 warp, @2..6 the correlate passes as launches of their own,
                               @7 multi-patch correlate + fit, @8 affine warp, @9 perspective warp */,
        RC_K_RIPMAP = 20 /* @0 ring, mean, cell sums, colour and the finish, @1 mask */,
-       RC_K_KINDS = 21 };
+       RC_K_TRACKSTAB = 21 /* @0 gray, @1 pyrDown, @2 Scharr, @3 PyrLK track, @4 robust fit, @5 corner cells */,
+       RC_K_KINDS = 22 };
 
 void rc_set_error(const char* fmt, ...);
 int rc_buf_ensure(RcBuf& b, size_t bytes);
@@ -250,6 +269,21 @@ void rc_fence_free(RcZeroFence& z);
 bool rc_img3_overlap(const uint8_t* a, size_t astep, int aw, int ah, const uint8_t* b, size_t bstep, int bw, int bh);
 int rc_img3_check(const char* who, const char* what, const uint8_t* p, size_t step, int w, int h);   // RC_EINVAL: null, empty, step < 3 w
 int rc_fits_context(const char* who, const rc_ctx* ctx, int w, int h);                                // RC_ESIZE
+// lk_kernels.hip: the two halves of a PyrLK call (pyramid of one image; track), for the tracking stabiliser
+RcLkPyr rc_lk_plan(int w, int h, int win_w, int win_h, int max_level, bool deriv);
+void rc_lk_build(rc_ctx* ctx, hipStream_t cur, const RcLkPyr& q, unsigned char* base);
+void rc_lk_track(rc_ctx* ctx, hipStream_t cur_stream, const RcLkPyr& ref, const unsigned char* ref_base, const unsigned char* cur_base,
+                 const RcLkPyr& cur, const float* d_prev_pts, float* d_next_pts, int npts, uint8_t* d_status, float* d_err, int win_w, int win_h,
+                 int max_count, double epsilon, int flags, double min_eig_threshold);
+// corner_kernels.hip, fit_kernels.hip
+void rc_gray_launch(rc_ctx* ctx, hipStream_t cur, const uint8_t* d_bgr, size_t step, int w, int h, uint8_t* d_gray);
+int rc_corner_check(const char* who, int w, int h, int cells_x, int cells_y, int margin, int min_score);
+void rc_corner_launch(rc_ctx* ctx, hipStream_t cur, const uint8_t* d_gray, size_t step, int w, int h, int cells_x, int cells_y, int margin,
+                      int min_score, float* d_pts, int* d_scores);
+int rc_fit_check(const char* who, int n, int w, int h, const rc_fit_params* prm);
+void rc_fit_launch(rc_ctx* ctx, hipStream_t cur, const float* d_p, const float* d_q, const uint8_t* d_status, const int* d_scores, int n, int w,
+                   int h, const rc_fit_params& prm, rc_fit_result* d_result, uint8_t* d_inlier, int* d_samples, void* d_ws, double* d_res,
+                   double* d_res2);
 // warp_kernels.hip
 void rc_warp_launch(rc_ctx* ctx, hipStream_t cur, RcWarpArgs& a, bool perspective);
 // initial_flow_kernels.hip

@@ -112,7 +112,7 @@ static const char* kKindNames[RC_K_KINDS] = {"pyr_level", "polyexp", "flow_iter"
                                              "thresholds", "classify_accumulate", "advect_field",
                                              "advect_points", "flow_postop", "flow_color", "flow_iter_x2",
                                              "frame_preproc", "create_edges", "streamline_display", "hsv_to_bgr",
-                                             "create_output", "flow_area_init", "timex", "frame_color", "framestab", "ripmap"};
+                                             "create_output", "flow_area_init", "timex", "frame_color", "framestab", "ripmap", "trackstab"};
 // The reference's wall-clock buckets (ripcurrents.cpp:103-109, sampled at :205,223,293,314,411,483, printed at
 // :518-524) and the kernels that do each bucket's work here.  time_polar has no kernel of its own: the
 // cartToPolar of :305-309 is fused into the histogram and classification kernels; classify_accumulate spans
@@ -126,7 +126,7 @@ static const int kBucketOfKind[RC_K_KINDS] = {
     /* pyr_level */ 0, /* polyexp */ 0, /* flow_iter */ 0, /* polar_hist */ 2, /* thresholds */ 2,
     /* classify_accumulate */ 2, /* advect_field */ 6, /* advect_points */ 6, /* flow_postop */ 0, /* flow_color */ 2,
     /* flow_iter_x2 */ 0, /* frame_preproc */ 0, /* create_edges */ 4, /* streamline_display */ 6, /* hsv_to_bgr */ 2,
-    /* create_output */ 3, /* flow_area_init */ 0, /* timex */ 3, /* frame_color */ 3, /* framestab */ 0, /* ripmap */ 0};
+    /* create_output */ 3, /* flow_area_init */ 0, /* timex */ 3, /* frame_color */ 3, /* framestab */ 0, /* ripmap */ 0, /* trackstab */ 0};
 static const char* kBucketNames[RC_PROFILE_BUCKETS] = {"farneback", "polar", "threshold", "overlay", "erosion", "codec", "stream"};
 static char g_names[RC_K_KINDS * RC_MAX_LEVELS][40];
 
@@ -245,7 +245,7 @@ static void slot_free(RcSlot& s) {
         rc_buf_free(s.FA[k]); rc_buf_free(s.FB[k]);
     }
     rc_batch_graph_drop(s);
-    rc_buf_free(s.stage_u8); rc_buf_free(s.stage_flow); rc_buf_free(s.lk); rc_buf_free(s.area_tab);
+    rc_buf_free(s.stage_u8); rc_buf_free(s.stage_flow); rc_buf_free(s.lk); rc_buf_free(s.fit_ws); rc_buf_free(s.area_tab);
     rc_buf_free(s.seed); rc_buf_free(s.seed_tab);
     rc_buf_free(s.exM); rc_buf_free(s.exV); rc_buf_free(s.exG);
     for (int i = 0; i < 2; i++) {

@@ -36,6 +36,7 @@
 #define ST_BLOCK 1024                    // the correlate workgroup: 16 waves
 #define ST_RED_BYTES 256                 // per-wave (value, index) of the arg-max
 #define ST_LDS_MAX (160 * 1024)
+#define FT_TRK_BYTES 34                  // per cell of RcFrameStab::trk (the tracking form)
 
 struct StArgs {
     const float* a; size_t a_step;       // prev patch, byte step
@@ -555,14 +556,15 @@ extern "C" int rcflow_warp_translate_bgr_dev(rc_ctx* ctx, int stream, const uint
 // ---------------------------------------------------------------------------- the pipeline (main.cpp:1707-1759)
 void rc_state_free(RcFrameStab& f) {
     rc_buf_free(f.tab); rc_buf_free(f.prev); rc_buf_free(f.res); rc_buf_free(f.scratch);
+    rc_buf_free(f.lkref); rc_buf_free(f.lkcur); rc_buf_free(f.trk);
     rc_fence_free(f.zf);
     f = RcFrameStab();
 }
 
 // nothing to register against yet: frame count, result and prev patch to zero
 int rc_state_zero(RcSlot& s, RcFrameStab& f) {
-    const int rc = rc_fence_zero(f.zf, s.cur, {&f.prev, &f.res});
-    if (!rc) f.frames = 0;
+    const int rc = rc_fence_zero(f.zf, s.cur, {&f.prev, &f.res, &f.trk});
+    if (!rc) { f.frames = 0; f.pcur = 0; f.pflip = false; }
     return rc;
 }
 
@@ -621,6 +623,148 @@ extern "C" int rcflow_framestab_open_multi(rc_ctx* ctx, int stream, int w, int h
     return fs_open(who, ctx, *s, w, h, rois, n, model, min_response, flags);
 }
 
+
+// ---------------------------------------------------------------------------- the tracking form
+static int ft_cells_default(int w, int h, int& cx, int& cy) {
+    int side = 40;
+    for (;; side += 8) {
+        cx = (w + side / 2) / side; cy = (h + side / 2) / side;
+        cx = cx < 1 ? 1 : cx; cy = cy < 1 ? 1 : cy;
+        if ((long long)cx * cy <= RC_CORNER_MAX_CELLS) return side;
+    }
+}
+
+extern "C" int rcflow_framestab_open_tracks(rc_ctx* ctx, int stream, int w, int h, const rc_stab_tracks* prm) {
+    static const char* who = "rcflow_framestab_open_tracks";
+    RcSlot* s = rc_slot(ctx, stream);
+    if (!s) return RC_EINVAL;
+    if (w <= 0 || h <= 0) { rc_set_error("%s: bad frame size %d x %d", who, w, h); return RC_EINVAL; }
+    if (!prm) { rc_set_error("%s: no parameters", who); return RC_EINVAL; }
+    rc_stab_tracks t = *prm;
+    if (t.win == 0) t.win = 21;
+    if (t.max_level < 0) t.max_level = 3;
+    if (t.max_count == 0) t.max_count = 30;
+    if (t.epsilon == 0.) t.epsilon = 0.01;
+    if (t.min_score == 0) t.min_score = 1;
+    if (t.hypotheses == 0) t.hypotheses = RC_FIT_DEFAULT_HYPOTHESES;
+    if (t.win < 3 || t.win > 63 || !(t.win & 1) || t.max_level > 7 || t.max_count < 1 || t.max_count > 100 || !(t.epsilon > 0. && t.epsilon <= 10.) ||
+        (t.flags & ~RC_STAB_ANCHOR_FIRST)) {
+        rc_set_error("%s: win %d (odd, 3..63), max_level %d (<= 7), max_count %d (1..100), epsilon %g (0..10] or flag bits 0x%x", who, t.win,
+                     t.max_level, t.max_count, t.epsilon, t.flags);
+        return RC_EINVAL;
+    }
+    const int margin = t.win / 2 + 2;
+    if (t.cells_x == 0 && t.cells_y == 0) ft_cells_default(w, h, t.cells_x, t.cells_y);
+    int rc = rc_corner_check(who, w, h, t.cells_x, t.cells_y, margin, t.min_score);
+    if (rc) return rc;
+    const int nc = t.cells_x * t.cells_y;
+    const rc_fit_params fp = {t.model, t.hypotheses, t.seed, t.min_score, t.quality, t.max_shift, t.inlier_px};
+    if ((rc = rc_fit_check(who, nc, w, h, &fp))) return rc;
+    if ((rc = rc_fits_context(who, ctx, w, h))) return rc;
+    RC_HIP(hipSetDevice(ctx->device));
+    RcFrameStab f;
+    f.w = w; f.h = h; f.rx = margin; f.ry = margin; f.rw = w - 2 * margin; f.rh = h - 2 * margin;
+    f.flags = t.flags; f.model = t.model;
+    f.tracks = true; f.tp = t; f.ncells = nc; f.margin = margin;
+    f.ref = rc_lk_plan(w, h, t.win, t.win, t.max_level, true);
+    f.cur = rc_lk_plan(w, h, t.win, t.win, t.max_level, false);
+    rc = rc_buf_ensure(f.lkref, f.ref.bytes);
+    if (!rc) rc = rc_buf_ensure(f.lkcur, f.cur.bytes);
+    if (!rc) rc = rc_buf_ensure(f.trk, (size_t)nc * FT_TRK_BYTES);
+    if (!rc) rc = rc_buf_ensure(f.res, RC_FT_DOUBLES * sizeof(double));
+    return rc_state_install(*s, s->fs, f, rc);
+}
+
+// trk: corners [2][ncells] float2 | tracks [ncells] float2 | scores [2][ncells] int | status [ncells] | inlier [ncells].  Slot
+// pcur holds the corners the last push tracked; a chained push writes the corrected frame's corners into the other slot
+// and the next push takes them over (a flip on the host), so that a read in between still pairs corner and track.
+struct FtBufs { float* p; float* pn; float* q; int* scores; int* scores_n; uint8_t* status; uint8_t* inlier; };
+static FtBufs ft_bufs(const RcFrameStab& f) {
+    FtBufs b;
+    float* base = (float*)f.trk.p;
+    const int nc = f.ncells;
+    b.p = base + 2 * nc * f.pcur; b.pn = base + 2 * nc * (1 - f.pcur); b.q = base + 4 * nc;
+    int* sc = (int*)(base + 6 * nc);
+    b.scores = sc + nc * f.pcur; b.scores_n = sc + nc * (1 - f.pcur);
+    b.status = (uint8_t*)(sc + 2 * nc); b.inlier = b.status + nc;
+    return b;
+}
+
+// One push of a tracks slot: gray, pyramid, track, fit (not on the first push); the warp reading T; then, chained or
+// first, gray + pyramid + derivatives + corners of the corrected frame
+static int fs_push_tracks(rc_ctx* ctx, RcSlot& s, const uint8_t* d_frame, size_t step, uint8_t* d_out, size_t out_step, double* d_result, bool first) {
+    RcFrameStab& f = s.fs;
+    const rc_stab_tracks& t = f.tp;
+    if (f.pflip) { f.pcur = 1 - f.pcur; f.pflip = false; }
+    const FtBufs b = ft_bufs(f);
+    double* res = (double*)f.res.p;
+    unsigned char* rb = (unsigned char*)f.lkref.p;
+    if (!first) {
+        unsigned char* cb = (unsigned char*)f.lkcur.p;
+        rc_gray_launch(ctx, s.cur, d_frame, step, f.w, f.h, cb + f.cur.offI[0]);
+        rc_lk_build(ctx, s.cur, f.cur, cb);
+        rc_lk_track(ctx, s.cur, f.ref, rb, cb, f.cur, b.p, b.q, f.ncells, b.status, nullptr, t.win, t.win, t.max_count, t.epsilon, 0, 1e-4);
+        const rc_fit_params fp = {t.model, t.hypotheses, t.seed, t.min_score, t.quality, t.max_shift, t.inlier_px};
+        rc_fit_launch(ctx, s.cur, b.p, b.q, b.status, b.scores, f.ncells, f.w, f.h, fp, (rc_fit_result*)(res + RC_FT_FIT), b.inlier, nullptr,
+                      res + RC_FT_WS, res + RC_FT_RESULT, d_result);
+    }
+    RcWarpArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = d_frame; a.step = step; a.sw = f.w; a.sh = f.h; a.dst = d_out; a.dst_step = out_step; a.dw = f.w; a.dh = f.h;
+    a.M[0] = a.M[4] = a.M[8] = 1.;
+    if (!first) a.d_M = res + RC_FT_FIT;
+    rc_warp_launch(ctx, s.cur, a, t.model == RC_STAB_HOMOGRAPHY);
+    if (first || !(t.flags & RC_STAB_ANCHOR_FIRST)) {
+        rc_gray_launch(ctx, s.cur, d_out, out_step, f.w, f.h, rb + f.ref.offI[0]);
+        rc_lk_build(ctx, s.cur, f.ref, rb);
+        rc_corner_launch(ctx, s.cur, rb + f.ref.offI[0], (size_t)f.w, f.w, f.h, t.cells_x, t.cells_y, f.margin, t.min_score,
+                         first ? b.p : b.pn, first ? b.scores : b.scores_n);
+        f.pflip = !first;
+    }
+    RC_HIP(hipGetLastError());
+    return RC_OK;
+}
+
+extern "C" int rcflow_framestab_read_tracks(rc_ctx* ctx, int stream, double T[9], int* model_used, int* n_valid, int* n_inliers, float* pts,
+                                            uint8_t* inlier, int* scores, int cap, int* cells, long long* frames_pushed) {
+    RcSlot* s = rc_slot(ctx, stream);
+    if (!s) return RC_EINVAL;
+    RcFrameStab& f = s->fs;
+    if (!f.open || !f.tracks) { rc_set_error("rcflow_framestab_read_tracks: the slot has no state opened by rcflow_framestab_open_tracks"); return RC_ESTATE; }
+    RC_HIP(hipSetDevice(ctx->device));
+    int rc = rc_fence_wait(f.zf, s->cur, false);
+    if (rc) return rc;
+    double st[RC_FT_DOUBLES] = {};
+    std::vector<unsigned char> host((size_t)f.ncells * FT_TRK_BYTES);
+    RC_HIP(hipMemcpyAsync(st, f.res.p, sizeof(st), hipMemcpyDeviceToHost, s->cur));
+    RC_HIP(hipMemcpyAsync(host.data(), f.trk.p, host.size(), hipMemcpyDeviceToHost, s->cur));
+    RC_HIP(hipStreamSynchronize(s->cur));
+    const bool fitted = f.frames > 1;
+    rc_fit_result r;
+    memcpy(&r, st + RC_FT_FIT, sizeof(r));
+    if (!fitted) {
+        memset(&r, 0, sizeof(r));
+        r.T[0] = r.T[4] = r.T[8] = 1.;
+    }
+    if (T) memcpy(T, r.T, sizeof(r.T));
+    if (model_used) *model_used = r.model_used;
+    if (n_valid) *n_valid = r.n_valid;
+    if (n_inliers) *n_inliers = r.n_inliers;
+    const int nc = f.ncells, m = cap < nc ? (cap < 0 ? 0 : cap) : nc;
+    const float* hp = (const float*)host.data() + 2 * nc * f.pcur;
+    const float* hq = (const float*)host.data() + 4 * nc;
+    const int* hs = (const int*)((const float*)host.data() + 6 * nc) + nc * f.pcur;
+    const unsigned char* hi = (const unsigned char*)((const float*)host.data() + 8 * nc) + nc;
+    for (int k = 0; k < m; k++) {
+        if (pts) { pts[4 * k] = hp[2 * k]; pts[4 * k + 1] = hp[2 * k + 1]; pts[4 * k + 2] = fitted ? hq[2 * k] : hp[2 * k]; pts[4 * k + 3] = fitted ? hq[2 * k + 1] : hp[2 * k + 1]; }
+        if (inlier) inlier[k] = fitted ? hi[k] : 0;
+        if (scores) scores[k] = hs[k];
+    }
+    if (cells) *cells = nc;
+    if (frames_pushed) *frames_pushed = f.frames;
+    return RC_OK;
+}
+
 extern "C" int rcflow_framestab_reset(rc_ctx* ctx, int stream) { return rc_state_reset(ctx, stream, &RcSlot::fs, "rcflow_framestab"); }
 extern "C" int rcflow_framestab_close(rc_ctx* ctx, int stream) { return rc_state_close(ctx, stream, &RcSlot::fs); }
 
@@ -634,9 +778,13 @@ extern "C" int rcflow_framestab_info(rc_ctx* ctx, int stream, int* w, int* h, in
     if (h) *h = f.h;
     if (roi) { roi[0] = f.rx; roi[1] = f.ry; roi[2] = f.rw; roi[3] = f.rh; }
     if (dft_size) { dft_size[0] = f.N; dft_size[1] = f.M; }
-    if (launches_per_push) *launches_per_push = f.lds ? 2 : 6;
+    if (launches_per_push) {
+        *launches_per_push = f.lds ? 2 : 6;
+        // gray + pyramid + track + fit + warp, and chained: gray + pyramid + derivatives + corners
+        if (f.tracks) *launches_per_push = 4 + f.cur.top + ((f.flags & RC_STAB_ANCHOR_FIRST) ? 0 : 3 + 2 * f.ref.top);
+    }
     if (frames_pushed) *frames_pushed = f.frames;
-    if (device_bytes) *device_bytes = f.tab.bytes + f.prev.bytes + f.res.bytes + f.scratch.bytes;
+    if (device_bytes) *device_bytes = f.tab.bytes + f.prev.bytes + f.res.bytes + f.scratch.bytes + f.lkref.bytes + f.lkcur.bytes + f.trk.bytes;
     return RC_OK;
 }
 
@@ -645,13 +793,13 @@ extern "C" int rcflow_framestab_info_multi(rc_ctx* ctx, int stream, int* n, int*
     if (!s) return RC_EINVAL;
     const RcFrameStab& f = s->fs;
     if (!f.open) { rc_set_error("no stabilisation state is open on the slot (rcflow_framestab_open)"); return RC_ESTATE; }
-    const int np = f.n ? f.n : 1;
+    const int np = f.tracks ? 0 : (f.n ? f.n : 1);
     if (n) *n = np;
     if (rois)
         for (int k = 0; k < np && k < cap; k++) {
             rois[4 * k] = f.n ? f.px[k] : f.rx; rois[4 * k + 1] = f.n ? f.py[k] : f.ry; rois[4 * k + 2] = f.rw; rois[4 * k + 3] = f.rh;
         }
-    if (model) *model = f.n ? f.model : RC_STAB_TRANSLATION;
+    if (model) *model = f.n || f.tracks ? f.model : RC_STAB_TRANSLATION;
     if (min_response) *min_response = f.n ? f.min_response : -INFINITY;
     if (flags) *flags = f.flags;
     return RC_OK;
@@ -706,10 +854,12 @@ extern "C" int rcflow_framestab_push_dev(rc_ctx* ctx, int stream, const uint8_t*
         // the first frame is copied (shift 0, the identity: every pixel is its own source) and becomes prev; result (0, 0, 0)
         RC_HIP(hipMemsetAsync(f.res.p, 0, f.res.bytes, s->cur));
         if (d_result) RC_HIP(hipMemsetAsync(d_result, 0, 3 * sizeof(double), s->cur));
-    } else if ((rc = fs_correlate(ctx, *s, d_frame, step, d_result))) {
+    } else if (!f.tracks && (rc = fs_correlate(ctx, *s, d_frame, step, d_result))) {
         return rc;
     }
-    if (f.n) {                                           // "framestab@8": the fitted motion, read from device memory
+    if (f.tracks) {
+        if ((rc = fs_push_tracks(ctx, *s, d_frame, step, d_out, out_step, d_result, first))) return rc;
+    } else if (f.n) {                                    // "framestab@8": the fitted motion, read from device memory
         RcWarpArgs a;
         memset(&a, 0, sizeof(a));
         a.src = d_frame; a.step = step; a.sw = f.w; a.sh = f.h; a.dst = d_out; a.dst_step = out_step; a.dw = f.w; a.dh = f.h;
@@ -743,13 +893,22 @@ extern "C" int rcflow_framestab_read_motion(rc_ctx* ctx, int stream, double moti
     int rc = rc_fence_wait(f.zf, s->cur, false);
     if (rc) return rc;
     double st[RC_FS_SHIFTS + 3 * RC_STAB_MAX_PATCHES] = {};
-    RC_HIP(hipMemcpyAsync(st, f.res.p, f.n ? sizeof(st) : 3 * sizeof(double), hipMemcpyDeviceToHost, s->cur));
+    RC_HIP(hipMemcpyAsync(st, f.res.p, f.tracks ? RC_FT_DOUBLES * sizeof(double) : f.n ? sizeof(st) : 3 * sizeof(double), hipMemcpyDeviceToHost, s->cur));
     RC_HIP(hipStreamSynchronize(s->cur));
     const bool fitted = f.frames > 1;                        // the first push registers against nothing
     double mo[6] = {1., 0., 0., 0., 1., 0.};
     int used[2] = {0, 0};
-    const int np = f.n ? f.n : 1;
-    if (fitted && f.n) {
+    const int np = f.tracks ? 0 : (f.n ? f.n : 1);
+    if (fitted && f.tracks) {
+        rc_fit_result r;
+        memcpy(&r, st + RC_FT_FIT, sizeof(r));
+        if (r.model_used == RC_STAB_HOMOGRAPHY) {
+            rc_set_error("rcflow_framestab_read_motion: the motion of the last push is a homography (rcflow_framestab_read_tracks returns it)");
+            return RC_EINVAL;
+        }
+        memcpy(mo, r.T, sizeof(mo));
+        used[0] = r.model_used; used[1] = r.n_inliers;
+    } else if (fitted && f.n) {
         memcpy(mo, st + RC_FS_MOTION, sizeof(mo));
         memcpy(used, st + RC_FS_USED, sizeof(used));
     } else if (fitted) {

@@ -41,9 +41,9 @@ __global__ __launch_bounds__(RC_BLOCK) void k_warp(const RcWarpArgs a) {
     double M[9];
 #pragma unroll
     for (int i = 0; i < 9; i++) M[i] = a.M[i];
-    if (!PERSP && a.d_M) {
+    if (a.d_M) {                                         // the stabiliser's fit: 2 x 3, or 3 x 3 for the perspective form
 #pragma unroll
-        for (int i = 0; i < 6; i++) M[i] = a.d_M[i];
+        for (int i = 0; i < (PERSP ? 9 : 6); i++) M[i] = a.d_M[i];
     }
     const double yd = (double)y;
     int X0 = 0, Y0 = 0;
@@ -106,7 +106,7 @@ void rc_warp_launch(rc_ctx* ctx, hipStream_t cur, RcWarpArgs& a, bool perspectiv
     a.bw0 = 1024 / bh0 < a.dw ? 1024 / bh0 : a.dw;
     const dim3 grid = rc_pix3_grid(a.dw, a.dh, 1);
     // compulsory bytes: the destination once, as many source bytes (the footprint of a near-identity map), the patches
-    const double bytes = 6. * a.dw * a.dh + (a.patch ? 4. * a.npatch * a.rw * a.rh : 0.) + (a.d_M ? 48. : 0.);
+    const double bytes = 6. * a.dw * a.dh + (a.patch ? 4. * a.npatch * a.rw * a.rh : 0.) + (a.d_M ? (perspective ? 72. : 48.) : 0.);
     RcProfScope ps(ctx, cur, RC_K_FRAMESTAB, perspective ? 9 : 8, bytes);
     if (perspective) hipLaunchKernelGGL(k_warp<1>, grid, dim3(RC_BLOCK), 0, cur, a);
     else hipLaunchKernelGGL(k_warp<0>, grid, dim3(RC_BLOCK), 0, cur, a);
