@@ -293,7 +293,8 @@ int rcflow_advect_field_read(rc_ctx* ctx, int stream, float* pt_xy /* h*w*2 */,
  * (ripcurrents.cpp:283-285, ripcurrents_module.cpp:72-75): variants
  * 0 ripcurrents_module.cpp:486-528, 1 :531-569, 2 :572-606, 3 ripcurrents.cpp:656-698,
  * 4 pathlines.cpp:9-46.  d_pts is n x (x,y), updated in place; d_trace (optional)
- * receives the position after every step (n*iters*2 floats) for the host to draw. */
+ * receives the position after every step (n*iters*2 floats), for the host to draw or for rcflow_trace_prims_dev
+ * and rcflow_draw_dev to draw where it lies. */
 int rcflow_advect_points_dev(rc_ctx* ctx, int stream, float* d_pts, int n,
                              const float* d_flow_xy, size_t flow_step, int w, int h, float dt,
                              int iterations, float UPPER, int variant, float* d_trace);
@@ -707,6 +708,127 @@ int rcflow_ripmap_close(rc_ctx* ctx, int stream);
 int rcflow_ripmap_info(rc_ctx* ctx, int stream, int* w, int* h, int* window, int* grid_x, int* grid_y, int* source,
                        int* flags, double* min_opposition_cos2, double* min_cell_mag, long long* frames_pushed,
                        size_t* device_bytes);
+
+/* ------------------------------------------------------------------ drawing: discs and lines into 8-bit images
+ * What circle(..., FILLED), line(..., thickness, 8) and the addWeighted(overlay, .5, img, .5) of the tracer pipelines leave
+ * in a frame (Streakline.cpp:57-66, ripcurrents_module.cpp:800-805, :1186-1194, :522), painted on the device.  The painting
+ * rules are this library's own, in integers only; they are NOT a restatement of OpenCV's drawing.cpp (DESIGN 7f says
+ * where they are known to differ):
+ *  - order: primitives paint in list order; a later one overwrites (or blends over) an earlier one;
+ *  - disc of radius r at (x0, y0): pixel (x, y) is lit iff (x - x0)^2 + (y - y0)^2 <= r^2 + r (radius r + 1/2);
+ *  - line of thickness 1 from (x0, y0) to (x1, y1), 8-connected: with adx = |x1 - x0| >= ady = |y1 - y0|, for every x
+ *    between the ends the one pixel y = y0 + sgn(y1 - y0) * ((2 ady |x - x0| + adx) / (2 adx)) (integer division); the steep
+ *    case with x and y exchanged; a zero-length line is its one pixel.  Not symmetric in its ends;
+ *  - line of thickness t = 2..8: lit iff 4 d^2 <= t^2, d the exact distance from the pixel centre to the segment
+ *    (projection inside the segment: 4 cross^2 <= t^2 |b|^2; outside: the distance to the nearer end);
+ *  - blend (RC_DRAW_BLEND): per channel p <- cvRound(0.5 c + 0.5 p), half to even: s = c + p, s >> 1 for even s, else
+ *    (s >> 1) + ((s >> 1) & 1); only covered pixels change;
+ *  - a primitive with a coordinate beyond |v| <= RC_DRAW_COORD_MAX, a radius outside 0..RC_DRAW_COORD_MAX, a thickness
+ *    outside 1..RC_DRAW_MAX_THICKNESS or an unknown kind is skipped and counted, never clamped.  Within the bound no product
+ *    of the tests leaves 64 bits.  Primitives may lie partly or wholly off the image;
+ *  - a pixel no primitive covers keeps its bytes: a lane that covers nothing stores nothing, so row padding is never written.
+ * Colour: byte0 | byte1 << 8 | byte2 << 16, the 8UC3 pixel's bytes in memory order (CV_RGB(r, g, b) is b | g << 8 | r << 16);
+ * a 1-channel image takes byte0. */
+#define RC_DRAW_DISC 1
+#define RC_DRAW_LINE 2
+#define RC_DRAW_BLEND 1            /* rc_draw_prim::flags */
+#define RC_DRAW_COORD_MAX 16383
+#define RC_DRAW_MAX_THICKNESS 8
+#define RC_DRAW_MAX_PRIMS (1 << 24)
+typedef struct rc_draw_prim {      /* 32 bytes */
+    int32_t kind;                  /* RC_DRAW_DISC | RC_DRAW_LINE */
+    int32_t x0, y0;                /* the centre; a line's first end */
+    int32_t x1, y1;                /* a line's second end (a disc ignores them) */
+    int32_t size;                  /* radius; thickness */
+    uint32_t color;
+    uint32_t flags;                /* RC_DRAW_BLEND */
+} rc_draw_prim;
+/* Stage: paints n primitives (device memory) into a w x h image of 1 or 3 channels in place, on the slot's stream.  One
+ * launch ("tracers@1"): a workgroup per 64 x 16 tile gathers the primitives whose box meets the tile, in list order, and
+ * every pixel is painted by the one lane that owns it; no atomics, no scratch.  d_skipped (optional, device) is
+ * INCREASED by the number of skipped primitives.  w, h <= RC_DRAW_COORD_MAX + 1, n <= RC_DRAW_MAX_PRIMS (RC_ESIZE beyond);
+ * n = 0 launches nothing. */
+int rcflow_draw_dev(rc_ctx* ctx, int stream, uint8_t* d_img, size_t step, int w, int h, int channels,
+                    const rc_draw_prim* d_prims, int n, unsigned long long* d_skipped);
+/* Stage: the d_trace of rcflow_advect_points_dev as thin lines, what the pathline overlay paints with
+ * cv::line(overlay, *pt, newpt, color, 1) per step (ripcurrents_module.cpp:522, :563, :600).  d_start (optional): the n
+ * seeds before the advection; with it seed s gives iters lines (start -> step 0 -> ...), without it iters - 1.  Seed after
+ * seed, step after step, into d_prims (n * (iters - (d_start ? 0 : 1)) records).  Coordinates are ROUNDED half to even
+ * (the Point2f -> Point conversion of that call; a value that is not finite or beyond int32 becomes INT32_MIN and is
+ * skipped by the drawing).  "tracers@2". */
+int rcflow_trace_prims_dev(rc_ctx* ctx, int stream, const float* d_start, const float* d_trace, int n, int iters,
+                           uint32_t color, rc_draw_prim* d_prims);
+
+/* ------------------------------------------------------------------ tracer lines: streaklines, timelines, point clouds
+ * compute_streaklines / compute_timelines / compute_populationMap (main.cpp:78-176; Streakline.cpp:22-71,
+ * ripcurrents_module.cpp:751-807, :1140-1196) with every vertex of every line of a stream resident on the device.  Per
+ * push, on the slot's stream, with no host synchronisation and no device-to-host copy:
+ *   1. move.  RC_TRACERS_LK: pyramid and Scharr derivatives of the incoming gray frame only, ONE sparse PyrLK launch over
+ *      all vertices of all lines from the kept pyramid of the previous frame, then the pyramids swap.  The first push (and
+ *      the first after a reset) primes: nothing moves, nothing is drawn, the call returns 1.  RC_TRACERS_FLOW: one step of
+ *      rcflow_advect_points_dev's variant 4 with the slot's dt on the caller's field or the slot's resident one;
+ *   2. book-keeping and primitives, one launch ("tracers@0").  Streakline: a moved vertex with |dx| > 0.1 w or
+ *      |dy| > 0.1 h (float difference, compared in double) keeps its old position, then the generation point becomes the
+ *      newest vertex.  Timeline, cloud: every vertex takes its moved position, whatever PyrLK's status says.  The
+ *      primitives, in the reference's painting order, with coordinates TRUNCATED toward zero (Point(float, float)):
+ *      streakline: disc 3 CV_RGB(0,100,0) at the generation point, line to vertex 0, disc 2 CV_RGB(0,0,100) at vertex 0,
+ *      per edge a disc 2 at its far vertex and a line CV_RGB(100,0,0); timeline: disc 4, per edge a line of thickness 2 and
+ *      a disc 4; cloud: per vertex a disc 10 CV_RGB(100,0,0) blended at 0.5;
+ *   3. draw (rcflow_draw_dev's launch) into d_canvas, when one is given.
+ * Deviation: the reference's streakline grows without bound; here it is a ring of max_vertices, and once full every push
+ * drops the oldest vertex (counted in rcflow_tracers_info).  The host knows every count without reading the device. */
+#define RC_TRACERS_LK 0
+#define RC_TRACERS_FLOW 1
+#define RC_TRACER_STREAK 0
+#define RC_TRACER_TIMELINE 1
+#define RC_TRACER_CLOUD 2
+#define RC_TRACERS_MAX_LINES 256
+#define RC_TRACERS_MAX_POINTS (1 << 20)
+typedef struct rc_tracers_params {
+    int mover;          /* RC_TRACERS_LK | RC_TRACERS_FLOW */
+    int max_lines;      /* 1..RC_TRACERS_MAX_LINES */
+    int max_vertices;   /* ring length of a streakline, >= 2 */
+    int max_points;     /* all vertices of the session together, <= RC_TRACERS_MAX_POINTS; 0: max_lines * max_vertices */
+    /* LK mover; win_w = 0 takes the reference's whole call (Streakline.cpp:32): 50 x 50, 3, COUNT+EPS, 30, 0.1, flags 10, 1e-4 */
+    int win_w, win_h, max_level, crit_type, max_count, lk_flags;
+    double epsilon, min_eig;
+    float dt;           /* FLOW mover */
+} rc_tracers_params;
+typedef struct rc_tracers_info {
+    int w, h, mover, max_lines, max_vertices, max_points;
+    int lines, points, prims;          /* as they stand; prims: of the last drawing push */
+    int primed;                        /* LK mover: a previous frame is held */
+    long long pushes;                  /* moves since open / reset (a priming push is none) */
+    long long dropped;                 /* streakline vertices the rings have let go */
+    size_t device_bytes;
+} rc_tracers_info;
+/* Allocates the state on the slot.  Re-opening replaces it; a refused open leaves the open state as it was. */
+int rcflow_tracers_open(rc_ctx* ctx, int stream, int w, int h, const rc_tracers_params* prm);
+/* Adds a line from n host points (x, y) and returns its id (0, 1, ...), or a negative code.  RC_TRACER_STREAK: n = 1, the
+ * generation point; RC_TRACER_TIMELINE, RC_TRACER_CLOUD: the n vertices.  Lines paint in the order they were added.
+ * Blocking (a set-up call): it waits for the slot's stream.  RC_ESIZE when max_lines or max_points would be passed
+ * (a streakline reserves max_vertices points). */
+int rcflow_tracers_add(rc_ctx* ctx, int stream, int kind, const float* xy, int n);
+/* One frame.  d_gray (8UC1, w x h): LK mover, else ignored.  d_flow_xy (32FC2): FLOW mover, NULL = the slot's resident
+ * field (RC_ESTATE when there is none, RC_ESIZE when its size differs).  d_canvas (8UC3, w x h, drawn in place): optional.
+ * Every refusal is decided before anything is queued and leaves the session as it was.  Returns RC_OK, or 1 from a
+ * priming push. */
+int rcflow_tracers_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_gray, size_t gray_step, const float* d_flow_xy,
+                            size_t flow_step, uint8_t* d_canvas, size_t canvas_step);
+/* Blocks until the slot's stream has finished; for hosts and tests.  The vertices of `line` in the reference's order
+ * (a streakline newest first) into xy (cap points; RC_ESIZE when it holds more), their number into n; skipped (may be
+ * NULL): primitives the session's drawing has skipped since open / reset. */
+int rcflow_tracers_read(rc_ctx* ctx, int stream, int line, float* xy, int cap, int* n, long long* skipped);
+/* The primitives of the last push (device memory owned by the session, valid until the next call on it) and their number:
+ * for a caller that paints them elsewhere with rcflow_draw_dev.  Either pointer may be NULL. */
+int rcflow_tracers_prims(rc_ctx* ctx, int stream, const rc_draw_prim** d_prims, int* n);
+/* never blocks; RC_ESTATE when nothing is open */
+int rcflow_tracers_info(rc_ctx* ctx, int stream, rc_tracers_info* info);
+/* Back to the lines as they were added: every line keeps its id and its first vertices, the counters and the skipped word
+ * are zero, the LK mover primes again.  Asynchronous, on the slot's stream. */
+int rcflow_tracers_reset(rc_ctx* ctx, int stream);
+/* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
+int rcflow_tracers_close(rc_ctx* ctx, int stream);
 
 /* Display path, ripcurrents.cpp:233-273 (= streamline_displacement / _total_motion / _ratio /
  * _positions, ripcurrents_module.cpp:13-60) on the slot's streamline field (rcflow_advect_field_dev):

@@ -429,7 +429,8 @@ class Pipeline {
 
 // Streakline.hpp:8-20.  run(): runLK's bookkeeping (Streakline.cpp:22-71) with the vertices moved
 // through the dense flow field resident in the pipeline (the main.cpp:961-977 precedent);
-// runLK(): the same with the reference's own mover, sparse PyrLK.  Drawing stays with the caller.
+// runLK(): the same with the reference's own mover, sparse PyrLK.  Drawing stays with the caller (rc::Tracers keeps the
+// vertices on the device and draws there).
 class Streakline {
   public:
     int numberOfVertices;
@@ -584,6 +585,89 @@ class RipMap {
     Pipeline& pipe_;
     int gx_, gy_;
     void* d_field_ = nullptr;
+};
+
+// Tracer lines on the device (rcflow_tracers_*): compute_streaklines / compute_timelines / compute_populationMap
+// (main.cpp:78-176) with every vertex resident, moved once per push and drawn into the caller's frame by the library.
+// Host images in, host images out, as the rest of this class family; nothing is read back but the frame.
+class Tracers {
+  public:
+    // mover RC_TRACERS_LK: the reference's PyrLK call (Streakline.cpp:32); RC_TRACERS_FLOW: one step of the flow field
+    // resident in the pipeline with dt
+    Tracers(Pipeline& pipe, int mover = RC_TRACERS_LK, int max_lines = 16, int max_vertices = 1024, float dt = 1.f) : pipe_(pipe) {
+        rc_tracers_params p{};
+        p.mover = mover; p.max_lines = max_lines; p.max_vertices = max_vertices; p.dt = dt;
+        check(rcflow_tracers_open(pipe.context(), 0, pipe.width(), pipe.height(), &p));
+    }
+    ~Tracers() {
+        (void)rcflow_tracers_close(pipe_.context(), 0);
+        if (d_gray_) (void)hipFree(d_gray_);
+        if (d_canvas_) (void)hipFree(d_canvas_);
+    }
+    Tracers(const Tracers&) = delete;
+    Tracers& operator=(const Tracers&) = delete;
+
+    int addStreakline(Pixel2 pixel) { const float xy[2] = {pixel.x, pixel.y}; return checked(rcflow_tracers_add(pipe_.context(), 0, RC_TRACER_STREAK, xy, 1)); }
+    // Timeline's constructor arithmetic (ripcurrents_module.cpp:751-762): numberOfVertices + 1 points on the segment
+    int addTimeline(Pixel2 lineStart, Pixel2 lineEnd, int numberOfVertices) {
+        const float diffX = (lineEnd.x - lineStart.x) / (float)numberOfVertices, diffY = (lineEnd.y - lineStart.y) / (float)numberOfVertices;
+        std::vector<float> xy;
+        for (int i = 0; i <= numberOfVertices; i++) { xy.push_back(lineStart.x + diffX * (float)i); xy.push_back(lineStart.y + diffY * (float)i); }
+        return checked(rcflow_tracers_add(pipe_.context(), 0, RC_TRACER_TIMELINE, xy.data(), numberOfVertices + 1));
+    }
+    int addCloud(const std::vector<Pixel2>& pts) {
+        std::vector<float> xy;
+        for (const Pixel2& p : pts) { xy.push_back(p.x); xy.push_back(p.y); }
+        return checked(rcflow_tracers_add(pipe_.context(), 0, RC_TRACER_CLOUD, xy.data(), (int)pts.size()));
+    }
+    // LK mover: the gray frame (8UC1) moves the lines; outImg (8UC3, optional) gets them drawn, as runLK(u_prev, u_current, outImg)
+    // does.  Returns false from the priming push (the first frame).
+    bool push(const Mat& gray, Mat* outImg = nullptr) {
+        const int w = pipe_.width(), h = pipe_.height();
+        if (gray.empty() || gray.rows != h || gray.cols != w || gray.channels != 1 || gray.elem != 1)
+            throw Error(RC_EINVAL, "Tracers::push: the frame must be 8UC1 of the pipeline's size");
+        if (!d_gray_) hip_check(hipMalloc(&d_gray_, (size_t)w * h), "hipMalloc gray");
+        check(rcflow_sync(pipe_.context(), 0));
+        hip_check(hipMemcpy2D(d_gray_, (size_t)w, gray.data, gray.step, (size_t)w, h, hipMemcpyHostToDevice), "upload gray");
+        return run((const uint8_t*)d_gray_, outImg);
+    }
+    // FLOW mover: the pipeline's resident flow field
+    bool push(Mat* outImg = nullptr) { return run(nullptr, outImg); }
+    // waits for the pipeline's stream; the reference's order (a streakline newest first)
+    std::vector<Pixel2> vertices(int line) {
+        int n = 0;
+        check(rcflow_tracers_read(pipe_.context(), 0, line, nullptr, 0, &n, nullptr));
+        std::vector<float> xy((size_t)2 * (n > 0 ? n : 1));
+        check(rcflow_tracers_read(pipe_.context(), 0, line, xy.data(), n, &n, nullptr));
+        std::vector<Pixel2> v;
+        for (int i = 0; i < n; i++) v.push_back(Pixel2{xy[2 * i], xy[2 * i + 1]});
+        return v;
+    }
+    rc_tracers_info info() { rc_tracers_info i; check(rcflow_tracers_info(pipe_.context(), 0, &i)); return i; }
+    void reset() { check(rcflow_tracers_reset(pipe_.context(), 0)); }
+
+  private:
+    static int checked(int rc) { check(rc); return rc; }
+    bool run(const uint8_t* d_gray, Mat* outImg) {
+        const int w = pipe_.width(), h = pipe_.height();
+        uint8_t* canvas = nullptr;
+        if (outImg) {
+            if (outImg->empty() || outImg->rows != h || outImg->cols != w || outImg->channels != 3 || outImg->elem != 1)
+                throw Error(RC_EINVAL, "Tracers::push: outImg must be 8UC3 of the pipeline's size");
+            if (!d_canvas_) hip_check(hipMalloc(&d_canvas_, (size_t)w * h * 3), "hipMalloc canvas");
+            check(rcflow_sync(pipe_.context(), 0));
+            hip_check(hipMemcpy2D(d_canvas_, (size_t)w * 3, outImg->data, outImg->step, (size_t)w * 3, h, hipMemcpyHostToDevice), "upload canvas");
+            canvas = (uint8_t*)d_canvas_;
+        }
+        const int rc = checked(rcflow_tracers_push_dev(pipe_.context(), 0, d_gray, (size_t)w, nullptr, 0, canvas, (size_t)w * 3));
+        if (outImg) {
+            check(rcflow_sync(pipe_.context(), 0));
+            hip_check(hipMemcpy2D(outImg->data, outImg->step, d_canvas_, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost), "download canvas");
+        }
+        return rc == 0;
+    }
+    Pipeline& pipe_;
+    void *d_gray_ = nullptr, *d_canvas_ = nullptr;
 };
 
 }  // namespace rc

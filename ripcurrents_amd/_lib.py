@@ -31,6 +31,13 @@ RC_STAB_MAX_PATCHES = 16
 RC_RIPMAP_WAIT_FULL = 1
 RIPMAP_SOURCES = {"flow": 0, "delta": 1}
 
+# rcflow_draw_dev: rc_draw_prim::kind / flags and the bounds of include/rcflow.h
+RC_DRAW_DISC, RC_DRAW_LINE, RC_DRAW_BLEND = 1, 2, 1
+RC_DRAW_COORD_MAX, RC_DRAW_MAX_THICKNESS = 16383, 8
+# rcflow_tracers_*: movers and line kinds
+TRACERS_MOVERS = {"lk": 0, "flow": 1}
+TRACER_KINDS = {"streak": 0, "timeline": 1, "cloud": 2}
+
 ERRORS = {-1: "RC_EINVAL", -2: "RC_ENOMEM", -3: "RC_EHIP", -4: "RC_ENODEV", -5: "RC_ESIZE",
           -6: "RC_ESTATE", -7: "RC_ECOMM"}
 
@@ -53,6 +60,27 @@ class FrameLoop(C.Structure):
                 ("seed_variant", C.c_int), ("seed_dt", C.c_float), ("seed_iterations", C.c_int), ("seed_upper", C.c_float),
                 ("MID", C.c_float), ("LOWER", C.c_float), ("d_outmask", C.c_void_p), ("mask_step", C.c_size_t),
                 ("d_edges", C.c_void_p), ("edges_step", C.c_size_t), ("use_graph", C.c_int)]
+
+
+class DrawPrim(C.Structure):
+    """rc_draw_prim (include/rcflow.h), 32 bytes; numpy: api.DRAW_PRIM_DTYPE."""
+    _fields_ = [("kind", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32),
+                ("size", C.c_int32), ("color", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class TracersParams(C.Structure):
+    """rc_tracers_params (include/rcflow.h)."""
+    _fields_ = [("mover", C.c_int), ("max_lines", C.c_int), ("max_vertices", C.c_int), ("max_points", C.c_int),
+                ("win_w", C.c_int), ("win_h", C.c_int), ("max_level", C.c_int), ("crit_type", C.c_int),
+                ("max_count", C.c_int), ("lk_flags", C.c_int), ("epsilon", C.c_double), ("min_eig", C.c_double),
+                ("dt", C.c_float)]
+
+
+class TracersInfo(C.Structure):
+    """rc_tracers_info (include/rcflow.h)."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("mover", C.c_int), ("max_lines", C.c_int), ("max_vertices", C.c_int),
+                ("max_points", C.c_int), ("lines", C.c_int), ("points", C.c_int), ("prims", C.c_int), ("primed", C.c_int),
+                ("pushes", C.c_longlong), ("dropped", C.c_longlong), ("device_bytes", C.c_size_t)]
 
 
 class FitParams(C.Structure):
@@ -179,6 +207,16 @@ SIGNATURES = {
     "rcflow_pyrlk_dev": [_vp, _i, _vp, _sz, _vp, _sz, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _d, _i, _d],
     "rcflow_pyrlk_u8": [_vp, _i, _vp, _sz, _vp, _sz, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _d, _i, _d],
     "rcflow_pyrlk_levels": [_i, _i, _i, _i, _i],
+    "rcflow_draw_dev": [_vp, _i, _vp, _sz, _i, _i, _i, _vp, _i, _vp],
+    "rcflow_trace_prims_dev": [_vp, _i, _vp, _vp, _i, _i, C.c_uint32, _vp],
+    "rcflow_tracers_open": [_vp, _i, _i, _i, C.POINTER(TracersParams)],
+    "rcflow_tracers_add": [_vp, _i, _i, _vp, _i],
+    "rcflow_tracers_push_dev": [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz],
+    "rcflow_tracers_read": [_vp, _i, _i, _vp, _i, C.POINTER(_i), C.POINTER(C.c_longlong)],
+    "rcflow_tracers_prims": [_vp, _i, C.POINTER(_vp), C.POINTER(_i)],
+    "rcflow_tracers_info": [_vp, _i, C.POINTER(TracersInfo)],
+    "rcflow_tracers_reset": [_vp, _i],
+    "rcflow_tracers_close": [_vp, _i],
     "rcflow_comm_unique_id": [_vp],
     "rcflow_comm_init": [_vp, _vp, _i, _i],
     "rcflow_comm_destroy": [_vp],

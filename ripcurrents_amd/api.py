@@ -14,6 +14,8 @@ Names, argument order and meaning follow the reference (paths relative to
   timex_*                    compute_timex main.cpp:1195-1263, compute_brightColor main.cpp:1265-1383
   framestab_*                compute_phaseCorrelate main.cpp:1684-1775 (phase_correlate, warp_translate: its stages)
   ripmap_*                   averageVector ripcurrents_module.cpp:386-484, finished (the opposing-flow map)
+  tracers_* / draw           compute_streaklines / compute_timelines / compute_populationMap main.cpp:78-176 with the vertices
+                             and the drawing (Streakline.cpp:57-66, ripcurrents_module.cpp:800-805, :1186-1194) on the device
 
 torch is used for device memory and streams only; all compute is in the HIP library.
 Arrays cross this layer as torch CUDA tensors (zero copy) or numpy arrays (copied).
@@ -27,8 +29,14 @@ from . import _lib
 from ._lib import FarnebackParams, HIST_BINS, HIST_DIRECTIONS, HIST_WORDS, RC_FARNEBACK_USE_INITIAL_FLOW, TIMEX_PRODUCTS, RcflowError, check
 from ._lib import RC_STAB_ANCHOR_FIRST, RC_STAB_MAX_PATCHES, RC_WARP_INVERSE_MAP, STAB_MODELS, FIT_MODELS, FitParams, StabTracks
 from ._lib import RC_RIPMAP_WAIT_FULL, RIPMAP_SOURCES
+from ._lib import TRACERS_MOVERS, TRACER_KINDS, TracersInfo, TracersParams
 
 __all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState"]
+
+
+# rc_draw_prim as a numpy record (32 bytes): what Context.draw takes and Context.tracers_prims returns
+DRAW_PRIM_DTYPE = np.dtype([("kind", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("size", "<i4"),
+                            ("color", "<u4"), ("flags", "<u4")])
 
 
 def _params(pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags):
@@ -1084,6 +1092,151 @@ class Context:
     def ripmap_close(self, stream=0):
         self._bind(stream)          # waits for the pushes queued on that stream before freeing
         check(self._lib.rcflow_ripmap_close(self._h, stream))
+
+    # ------------------------------------------------------------------ tracer lines and drawing
+    def draw(self, img, prims, skipped=None, stream=0):
+        """rcflow_draw_dev: paints the primitives into img (HxW or HxWx3 uint8 device tensor, dense pixels, rows may be
+        padded) in place, in list order, by the rules of include/rcflow.h.  prims: a device uint8 / int32 tensor holding
+        32-byte rc_draw_prim records, or a numpy array of DRAW_PRIM_DTYPE (copied to the device).  skipped: an optional
+        one-element int64 device tensor that is increased by the number of skipped primitives."""
+        if not (_is_t(img) and img.is_cuda and img.device == self.device and img.dtype == torch.uint8 and img.dim() in (2, 3)):
+            raise ValueError("img must be a uint8 tensor on %s of shape HxW or HxWx3" % self.device)
+        ch = 1 if img.dim() == 2 else int(img.shape[2])
+        if ch not in (1, 3) or img.stride(1) != ch or (img.dim() == 3 and img.stride(2) != 1) or img.stride(0) < ch * img.shape[1]:
+            raise ValueError("img must have 1 or 3 channels and dense pixels")
+        if isinstance(prims, np.ndarray):
+            if prims.dtype != DRAW_PRIM_DTYPE:
+                raise ValueError("prims must have dtype DRAW_PRIM_DTYPE")
+            prims = torch.from_numpy(np.ascontiguousarray(prims).view(np.uint8).reshape(-1)).to(self.device)
+        if not (_is_t(prims) and prims.is_cuda and prims.device == self.device and prims.is_contiguous()):
+            raise ValueError("prims must be a contiguous tensor on %s or a numpy array of DRAW_PRIM_DTYPE" % self.device)
+        nbytes = prims.numel() * prims.element_size()
+        if nbytes % 32:
+            raise ValueError("prims must hold whole 32-byte records")
+        sp = C.c_void_p(None)
+        if skipped is not None:
+            sp = self._ptr(_check_out(skipped, self.device, torch.int64, "skipped", numel=1))
+        self._bind(stream)
+        check(self._lib.rcflow_draw_dev(self._h, stream, self._ptr(img), img.stride(0), int(img.shape[1]), int(img.shape[0]), ch,
+                                        self._ptr(prims), nbytes // 32, sp))
+        return img
+
+    def trace_prims(self, trace, start=None, color=0xffffff, stream=0):
+        """rcflow_trace_prims_dev: the trace of streamline(..., trace=True) (n x iters x 2 float32 on the device) as thin
+        lines with rounded ends -> a device uint8 tensor of rc_draw_prim records for draw().  start: the n seeds before
+        the advection (n x 2), optional."""
+        tr = _check_out(trace, self.device, torch.float32, "trace", shape=tuple(trace.shape[:2]) + (2,))
+        n, iters = int(tr.shape[0]), int(tr.shape[1])
+        st = None if start is None else self._dev(start, torch.float32).reshape(n, 2).contiguous()
+        per = iters if st is not None else iters - 1
+        out = torch.empty((n * per, 32), dtype=torch.uint8, device=self.device)
+        self._bind(stream)
+        check(self._lib.rcflow_trace_prims_dev(self._h, stream, None if st is None else self._ptr(st), self._ptr(tr), n, iters,
+                                               int(color), self._ptr(out)))
+        return out
+
+    def tracers_open(self, w, h, mover="lk", max_lines=16, max_vertices=1024, max_points=0, lk=None, dt=1.0, stream=0):
+        """Opens the slot's tracer session for w x h frames: streaklines, timelines and point clouds whose vertices stay on
+        the device (compute_streaklines / compute_timelines / compute_populationMap, main.cpp:78-176).  mover "lk": sparse
+        PyrLK between consecutive gray frames; lk = dict(win=(w, h), max_level, crit_type, max_count, epsilon, flags,
+        min_eig_threshold), None: the reference's call (Streakline.cpp:32).  mover "flow": one step of the dense field
+        with dt (Streakline.run).  A streakline is a ring of max_vertices; max_points bounds all vertices together
+        (0: max_lines * max_vertices)."""
+        if mover not in TRACERS_MOVERS:
+            raise ValueError("mover must be one of %s" % sorted(TRACERS_MOVERS))
+        p = TracersParams(mover=TRACERS_MOVERS[mover], max_lines=int(max_lines), max_vertices=int(max_vertices),
+                          max_points=int(max_points), dt=float(dt))
+        if lk is not None:
+            win = lk.get("win", (50, 50))
+            p.win_w, p.win_h, p.max_level = int(win[0]), int(win[1]), int(lk.get("max_level", 3))
+            p.crit_type, p.max_count, p.epsilon = int(lk.get("crit_type", 3)), int(lk.get("max_count", 30)), float(lk.get("epsilon", 0.1))
+            p.lk_flags, p.min_eig = int(lk.get("flags", 10)), float(lk.get("min_eig_threshold", 1e-4))
+        self._bind(stream)          # the state is zeroed on the slot's stream: the one the pushes will run on
+        check(self._lib.rcflow_tracers_open(self._h, stream, int(w), int(h), C.byref(p)))
+
+    def tracers_add(self, kind, xy, stream=0):
+        """Adds a line from host points -> its id.  kind "streak": xy is the generation point; "timeline", "cloud": the
+        n x 2 vertices.  Blocking."""
+        if kind not in TRACER_KINDS:
+            raise ValueError("kind must be one of %s" % sorted(TRACER_KINDS))
+        a = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        self._bind(stream)
+        return check(self._lib.rcflow_tracers_add(self._h, stream, TRACER_KINDS[kind], a.ctypes.data, a.shape[0]))
+
+    def tracers_add_streakline(self, pixel, stream=0):
+        return self.tracers_add("streak", [pixel], stream)
+
+    def tracers_add_timeline(self, lineStart, lineEnd, numberOfVertices, stream=0):
+        """Timeline's constructor (ripcurrents_module.cpp:751-762): numberOfVertices + 1 points on the segment."""
+        return self.tracers_add("timeline", Timeline(lineStart, lineEnd, numberOfVertices).vertices, stream)
+
+    def tracers_add_cloud(self, rectStart, rectEnd, numberOfVertices, rng=None, stream=0):
+        """PopulationMap's constructor (ripcurrents_module.cpp:1140-1152) with `rng` in place of rand()."""
+        return self.tracers_add("cloud", PopulationMap(rectStart, rectEnd, numberOfVertices, rng).vertices, stream)
+
+    def tracers_info(self, stream=0):
+        """dict of rc_tracers_info; never blocks."""
+        info = TracersInfo()
+        check(self._lib.rcflow_tracers_info(self._h, stream, C.byref(info)))
+        d = {k: getattr(info, k) for k, _ in TracersInfo._fields_}
+        d["mover"] = {b: a for a, b in TRACERS_MOVERS.items()}[info.mover]
+        d["primed"] = bool(info.primed)
+        return d
+
+    def tracers_push(self, gray=None, flow=None, canvas=None, stream=0):
+        """One frame: moves every vertex of every line, does the reference's book-keeping and, with canvas (HxWx3 uint8
+        device tensor, dense pixels), draws the lines into it in place.  gray: HxW uint8 (mover "lk"); flow: HxWx2 float32
+        (mover "flow"; None: the field push_frame_host / frame_loop_step left on the slot).  Nothing is synchronised.
+        Returns False from a priming push (mover "lk": the first frame), else True."""
+        info = self.tracers_info(stream)
+        h, w = info["h"], info["w"]
+        gp, gstep, fp, fstep, cp, cstep = C.c_void_p(None), 0, C.c_void_p(None), 0, C.c_void_p(None), 0
+        if info["mover"] == "lk":
+            g = self._dev(gray, torch.uint8)
+            if g.dim() != 2 or tuple(g.shape) != (h, w) or g.stride(1) != 1:
+                raise ValueError("gray must be %dx%d uint8 with dense pixels, as opened" % (h, w))
+            gp, gstep = self._ptr(g), g.stride(0)
+        elif flow is not None:
+            flow = self._dev(flow, torch.float32)
+            if flow.dim() != 3 or tuple(flow.shape) != (h, w, 2) or flow.stride(2) != 1 or flow.stride(1) != 2:
+                raise ValueError("flow must be %dx%dx2 float32 with dense pixels, as opened" % (h, w))
+            fp, fstep = self._ptr(flow), flow.stride(0) * 4
+        if canvas is not None:
+            _check_out(canvas, self.device, torch.uint8, "canvas", shape=(h, w, 3), dense=True)
+            cp, cstep = self._ptr(canvas), canvas.stride(0)
+        self._bind(stream)
+        return check(self._lib.rcflow_tracers_push_dev(self._h, stream, gp, gstep, fp, fstep, cp, cstep)) == 0
+
+    def tracers_read(self, line, stream=0):
+        """Waits for the slot's stream -> (vertices n x 2 float32 in the reference's order: a streakline newest first,
+        primitives skipped by the session's drawing so far)."""
+        n, sk = C.c_int(0), C.c_longlong(0)
+        self._bind(stream)
+        check(self._lib.rcflow_tracers_read(self._h, stream, int(line), None, 0, C.byref(n), None))
+        xy = np.zeros((max(n.value, 1), 2), np.float32)
+        check(self._lib.rcflow_tracers_read(self._h, stream, int(line), xy.ctypes.data, xy.shape[0], C.byref(n), C.byref(sk)))
+        return xy[:n.value], sk.value
+
+    def tracers_prims(self, stream=0):
+        """The primitives of the last push -> numpy array of DRAW_PRIM_DTYPE (waits for the slot's stream; for tests and
+        hosts that paint elsewhere)."""
+        ptr, n = C.c_void_p(None), C.c_int(0)
+        check(self._lib.rcflow_tracers_prims(self._h, stream, C.byref(ptr), C.byref(n)))
+        if not n.value:
+            return np.zeros(0, DRAW_PRIM_DTYPE)
+        self._bind(stream)          # the copy below runs on torch's current stream, behind the pushes
+        if stream in self._own:
+            self.sync(stream)
+        host = _alias_tensor(ptr.value, n.value * 8, torch.int32, self.device).cpu()
+        return host.numpy().view(DRAW_PRIM_DTYPE).reshape(-1).copy()
+
+    def tracers_reset(self, stream=0):
+        self._bind(stream)
+        check(self._lib.rcflow_tracers_reset(self._h, stream))
+
+    def tracers_close(self, stream=0):
+        self._bind(stream)          # waits for the pushes queued on that stream before freeing
+        check(self._lib.rcflow_tracers_close(self._h, stream))
 
     def _an_size(self, stream):
         w, h = C.c_int(0), C.c_int(0)

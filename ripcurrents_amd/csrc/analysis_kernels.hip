@@ -1012,6 +1012,13 @@ static int thr_ptr(rc_ctx* ctx, RcSlot& s, float UPPER, const float** thr) {
     return RC_OK;
 }
 
+void rc_advect_points_launch(rc_ctx* ctx, hipStream_t cur, float* d_pts, int n, const float* d_flow, size_t flow_step, int w, int h, float dt,
+                             int iterations, float UPPER, const float* thr, int variant, float* d_trace) {
+    RcProfScope ps(ctx, cur, RC_K_ADVECT_POINTS, 0, 16. * n);
+    hipLaunchKernelGGL(k_advect_points, dim3((n + 63) / 64), dim3(64), 0, cur, (float2*)d_pts, n, d_flow, flow_step, w, h, dt, iterations,
+                       UPPER, thr, variant, (float2*)d_trace);
+}
+
 extern "C" int rcflow_advect_points_dev(rc_ctx* ctx, int stream, float* d_pts, int n, const float* d_flow,
                                         size_t flow_step, int w, int h, float dt, int iterations, float UPPER,
                                         int variant, float* d_trace) {
@@ -1025,11 +1032,7 @@ extern "C" int rcflow_advect_points_dev(rc_ctx* ctx, int stream, float* d_pts, i
     RC_HIP(hipSetDevice(ctx->device));
     const float* thr;
     if ((rc = thr_ptr(ctx, *s, UPPER, &thr))) return rc;
-    {
-        RcProfScope ps(ctx, s->cur, RC_K_ADVECT_POINTS, 0, 16. * n);
-        hipLaunchKernelGGL(k_advect_points, dim3((n + 63) / 64), dim3(64), 0, s->cur, (float2*)d_pts, n, d_flow,
-                           flow_step, w, h, dt, iterations, UPPER, thr, variant, (float2*)d_trace);
-    }
+    rc_advect_points_launch(ctx, s->cur, d_pts, n, d_flow, flow_step, w, h, dt, iterations, UPPER, thr, variant, d_trace);
     RC_HIP(hipGetLastError());
     return RC_OK;
 }

@@ -124,6 +124,34 @@ struct RcRipMap {
     RcZeroFence zf;
 };
 
+// Tracer lines of one stream slot (tracer_kernels.hip; Streakline.cpp:22-71, ripcurrents_module.cpp:751-807, :1140-1196).
+// Everything is allocated by rcflow_tracers_open and released by rcflow_tracers_close / rcflow_destroy.  The vertices of
+// all lines lie compacted, line after line, a streakline oldest first; the host knows every count: a streakline of age a
+// (moves since it was added or the session was reset) has min(cap, 1 + a) vertices.
+struct RcTrLineH { int kind, cap, n0; long long t_add; };
+struct RcTracers {
+    bool open = false;
+    int w = 0, h = 0;
+    rc_tracers_params prm{};        // every default resolved, the LK criteria as SparsePyrLKOpticalFlowImpl::calc clamps them
+    std::vector<RcTrLineH> lines;
+    int reserved = 0;               // points the lines may grow to (a streakline: max_vertices), <= prm.max_points
+    int init_n = 0;                 // points in `init`
+    int cur = 0;                    // which half of pos holds the vertices
+    long long t = 0, t_reset = 0;   // moves since open; at the last reset
+    long long dropped = 0;
+    bool primed = false; int pyr_cur = 0;   // LK mover: pyr[pyr_cur] holds the previous frame
+    int nprims = 0;                 // of the last push
+    RcLkPyr plan{};
+    RcBuf pyr;                      // LK mover: two pyramids with derivatives
+    RcBuf pos;                      // P[2] | Q[2], max_points float2 each: the vertices; moved (LK) / the copy the advection moves (FLOW)
+    RcBuf init;                     // the lines as they were added, compacted: what reset restores
+    RcBuf tab;                      // max_lines TrLine records
+    RcBuf prims;                    // 2 max_points + max_lines records
+    RcBuf status;                   // LK mover: max_points bytes nobody reads (ripcurrents_module.cpp:794)
+    RcBuf ctr;                      // one uint64: primitives skipped
+    RcZeroFence zf;
+};
+
 // warp_kernels.hip: one launch of the affine / perspective warp
 struct RcWarpArgs {
     const uint8_t* src; size_t step;
@@ -197,6 +225,7 @@ struct RcSlot {
     RcTimex tx;
     RcFrameStab fs;
     RcRipMap rm;
+    RcTracers tr;
     RcPhaseCorr pc;
 };
 
@@ -242,7 +271,8 @@ enum { RC_K_PYR = 0, RC_K_POLY = 1, RC_K_ITER = 2, RC_K_HIST = 3, RC_K_THRESH = 
                               @7 multi-patch correlate + fit, @8 affine warp, @9 perspective warp */,
        RC_K_RIPMAP = 20 /* @0 ring, mean, cell sums, colour and the finish, @1 mask */,
        RC_K_TRACKSTAB = 21 /* @0 gray, @1 pyrDown, @2 Scharr, @3 PyrLK track, @4 robust fit, @5 corner cells */,
-       RC_K_KINDS = 22 };
+       RC_K_TRACERS = 22 /* @0 book-keeping and primitives, @1 draw, @2 trace to lines */,
+       RC_K_KINDS = 23 };
 
 void rc_set_error(const char* fmt, ...);
 int rc_buf_ensure(RcBuf& b, size_t bytes);
@@ -284,6 +314,12 @@ int rc_fit_check(const char* who, int n, int w, int h, const rc_fit_params* prm)
 void rc_fit_launch(rc_ctx* ctx, hipStream_t cur, const float* d_p, const float* d_q, const uint8_t* d_status, const int* d_scores, int n, int w,
                    int h, const rc_fit_params& prm, rc_fit_result* d_result, uint8_t* d_inlier, int* d_samples, void* d_ws, double* d_res,
                    double* d_res2);
+// analysis_kernels.hip: the launch of rcflow_advect_points_dev ("advect_points@0"); thr may be null when UPPER >= 0
+void rc_advect_points_launch(rc_ctx* ctx, hipStream_t cur, float* d_pts, int n, const float* d_flow, size_t flow_step, int w, int h, float dt,
+                             int iterations, float UPPER, const float* thr, int variant, float* d_trace);
+// draw_kernels.hip ("tracers@1"); the arguments have been checked
+void rc_draw_launch(rc_ctx* ctx, hipStream_t cur, uint8_t* d_img, size_t step, int w, int h, int channels, const rc_draw_prim* d_prims,
+                    int n, unsigned long long* d_skipped);
 // warp_kernels.hip
 void rc_warp_launch(rc_ctx* ctx, hipStream_t cur, RcWarpArgs& a, bool perspective);
 // initial_flow_kernels.hip
@@ -309,16 +345,18 @@ struct RcProfScope {
     } while (0)
 
 // ---------------------------------------------------------------------------- per-slot products
-// RcTimex, RcFrameStab and RcRipMap share one lifecycle.  A product supplies
+// RcTimex, RcFrameStab, RcRipMap and RcTracers share one lifecycle.  A product supplies
 //   void rc_state_free(T&)             frees every buffer and the fence; the state is T() again
 //   int rc_state_zero(RcSlot&, T&)     rc_fence_zero of what open / reset clear, and the counters
 // and open / reset / close are written once, here.
 void rc_state_free(RcTimex& t);
 void rc_state_free(RcFrameStab& f);
 void rc_state_free(RcRipMap& m);
+void rc_state_free(RcTracers& t);
 int rc_state_zero(RcSlot& s, RcTimex& t);
 int rc_state_zero(RcSlot& s, RcFrameStab& f);
 int rc_state_zero(RcSlot& s, RcRipMap& m);
+int rc_state_zero(RcSlot& s, RcTracers& t);
 
 // The tail of every open.  The caller has validated, selected the device and built `fresh` (rc: what its allocations
 // returned).  The state that is open is touched only once nothing can be refused any more: a refused open leaves it as it

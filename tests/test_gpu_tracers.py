@@ -1,0 +1,435 @@
+"""Tracer lines on the device (tracer_kernels.hip, draw_kernels.hip): positions against the host classes of api.py driven
+with the same frames, the canvas and the drawing stage against the numpy statement (tests/_tracers_ref.py); everything is
+compared after every push, bit for bit."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import _tracers_ref as R
+from ripcurrents_amd import synth
+from ripcurrents_amd._lib import RcflowError
+from ripcurrents_amd.api import DRAW_PRIM_DTYPE, PopulationMap, Streakline, Timeline
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EINVAL, ESIZE, ESTATE = -1, -5, -6
+f32 = np.float32
+
+
+def padded(a, pad, fill=0):
+    """a device copy of the host array `a` as a view into rows that are `pad` elements longer; returns (view, whole)"""
+    t = torch.as_tensor(a)
+    whole = torch.full((t.shape[0], t.shape[1] * (t.shape[2] if t.dim() == 3 else 1) + pad), fill, dtype=t.dtype)
+    whole[:, :whole.shape[1] - pad] = t.reshape(t.shape[0], -1)
+    whole = whole.cuda()
+    view = whole[:, :whole.shape[1] - pad].view(t.shape) if t.dim() == 2 else \
+        torch.as_strided(whole, tuple(t.shape), (whole.stride(0), t.shape[2], 1))
+    return view, whole
+
+
+def frame_bgr(w, h, t):
+    y, x = np.mgrid[0:h, 0:w]
+    return np.stack([(x * 3 + y + t * 5) % 256, (x + y * 7 + t) % 256, (x * y + t * 11) % 256], -1).astype(np.uint8)
+
+
+def build_lines(ctx, w, h, stream=0):
+    """five streaklines, two timelines and a cloud in one session; returns the host twins in the session's order"""
+    host = []
+    for i in range(5):
+        p = (w * (i + 1) / 6.0, h / 2.0 + 9 * i)
+        assert ctx.tracers_add_streakline(p, stream=stream) == len(host)
+        host.append(Streakline(p))
+    for a, b, n in [((w * 0.2, h * 0.25), (w * 0.8, h * 0.3), 9), ((w * 0.3, h * 0.8), (w * 0.35, h * 0.2), 6)]:
+        assert ctx.tracers_add_timeline(a, b, n, stream=stream) == len(host)
+        host.append(Timeline(a, b, n))
+    rect = ((w * 0.15, h * 0.15), (w * 0.45, h * 0.4))
+    assert ctx.tracers_add_cloud(rect[0], rect[1], 12, rng=np.random.RandomState(5), stream=stream) == len(host)
+    host.append(PopulationMap(rect[0], rect[1], 12, rng=np.random.RandomState(5)))
+    return host
+
+
+def ref_session(host, w, h, max_vertices):
+    s = R.Session(w, h, max_vertices)
+    for o in host:
+        kind = R.STREAK if isinstance(o, Streakline) else (R.TIMELINE if isinstance(o, Timeline) else R.CLOUD)
+        s.add(kind, np.asarray(o.vertices, f32).reshape(-1, 2))
+    return s
+
+
+def check_push(ctx, host, ref, canvas_dev, canvas_in, whole=None, what="", stream=0):
+    """after a push: every line equals its host twin, the primitives and the canvas equal the numpy statement"""
+    for i, o in enumerate(host):
+        got, _ = ctx.tracers_read(i, stream=stream)
+        want = np.asarray(o.vertices, f32).reshape(-1, 2)[:ref.max_vertices]
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), "line %d differs from its host class %s" % (i, what)
+        ref.lines[i].v = want.copy()
+    prims = ctx.tracers_prims(stream=stream)
+    want_p = ref.prims()
+    assert prims.dtype == DRAW_PRIM_DTYPE and np.array_equal(prims, want_p.astype(DRAW_PRIM_DTYPE)), "primitives differ " + what
+    want = canvas_in.copy()
+    R.draw(want, want_p)
+    got = canvas_dev.cpu().numpy()
+    assert np.array_equal(got, want), "canvas differs %s (%d pixels)" % (what, int((got != want).any(-1).sum()))
+    touched = np.zeros(want.shape[:2], bool)
+    for p in want_p:
+        if R.valid(p):
+            touched |= R.mask(p, want.shape[1], want.shape[0])
+    assert np.array_equal(got[~touched], canvas_in[~touched]), "a pixel outside every primitive changed " + what
+    assert touched.any()
+    if whole is not None:
+        assert (whole[:, canvas_dev.shape[1] * 3:] == 0xA5).all().item(), "padding bytes changed " + what
+
+
+@pytest.mark.parametrize("w,h,pad", [(640, 480, 0), (333, 251, 5)])
+def test_lk_session_against_the_host_classes(ctx, w, h, pad):
+    n = 13
+    clip = synth.surf_clip(w, h, n, seed=77)
+    ctx.tracers_open(w, h, "lk", max_lines=8, max_vertices=64)
+    host = build_lines(ctx, w, h)
+    ref = ref_session(host, w, h, 64)
+    info = ctx.tracers_info()
+    assert info["lines"] == 8 and info["points"] == 5 + 10 + 7 + 12 and not info["primed"] and info["pushes"] == 0
+    for t in range(n):
+        gray, _ = padded(clip[t], pad)
+        cin = frame_bgr(w, h, t)
+        canvas, whole = padded(cin, pad, 0xA5)
+        moved = ctx.tracers_push(gray=gray, canvas=canvas)
+        assert moved == (t > 0)
+        if t == 0:
+            assert np.array_equal(canvas.cpu().numpy(), cin), "the priming push drew"
+            continue
+        for o in host:
+            o.runLK(ctx, clip[t - 1], clip[t])
+        check_push(ctx, host, ref, canvas, cin, whole if pad else None, "at push %d" % t)
+    info = ctx.tracers_info()
+    assert info["pushes"] == n - 1 and info["points"] == 5 * n + 29 and info["dropped"] == 0 and info["primed"]
+    assert info["prims"] == 5 * (2 * n + 1) + 19 + 13 + 12
+    ctx.tracers_close()
+
+
+def smooth_field(w, h, t):
+    y, x = np.mgrid[0:h, 0:w].astype(f32)
+    return np.stack([2.5 * np.sin(x / 31.0 + 0.4 * t) + 1.5, 2.0 * np.cos(y / 27.0 - 0.3 * t) - 0.5], -1).astype(f32)
+
+
+def run_flow_session(ctx, w, h, fields, resident, max_vertices=64, pad=0, stream=0):
+    ctx.tracers_open(w, h, "flow", max_lines=8, max_vertices=max_vertices, dt=1.0, stream=stream)
+    pts = [(w * (i + 1) / 6.0, h / 2.0 + 9 * i) for i in range(5)]
+    host = [Streakline(p) for p in pts]
+    for p in pts:
+        ctx.tracers_add_streakline(p, stream=stream)
+    ref = ref_session(host, w, h, max_vertices)
+    out = []
+    for t, f in enumerate(fields):
+        cin = frame_bgr(w, h, t)
+        canvas, whole = padded(cin, pad, 0xA5)
+        if resident:
+            d = torch.as_tensor(f).cuda()
+            ctx.tracers_push(flow=d, canvas=canvas, stream=stream)
+        else:
+            d, _ = padded(f, 2 * pad)
+            ctx.tracers_push(flow=d, canvas=canvas, stream=stream)
+        for o in host:
+            o.run(ctx, f, w, h, dt=1.0, stream=stream)
+        check_push(ctx, host, ref, canvas, cin, whole if pad else None, "at push %d" % (t + 1), stream=stream)
+        out.append((canvas.cpu().numpy(), [np.asarray(o.vertices, f32) for o in host]))
+    return host, out
+
+
+@pytest.mark.parametrize("w,h,pad", [(640, 480, 0), (333, 251, 3)])
+def test_flow_session_against_streakline_run(ctx, w, h, pad):
+    fields = [smooth_field(w, h, t) for t in range(12)]
+    # one crafted field: a single huge vector under the second streakline's generation point, so that the rejection fires
+    gx, gy = int(w * 2 / 6.0), int(h / 2.0 + 9)
+    fields[4][gy - 1:gy + 3, gx - 1:gx + 3] = (w * 0.5, 0.0)
+    host, out = run_flow_session(ctx, w, h, fields, False, pad=pad)
+    v = out[4][1][1]                                             # the second streakline after the crafted field
+    assert np.array_equal(v[1], v[0]), "the vertex on the generation point did not refuse the jump"
+    assert not np.array_equal(out[3][1][1][1], out[3][1][1][0])
+    info = ctx.tracers_info()
+    assert info["pushes"] == 12 and info["points"] == 5 * 13
+    ctx.tracers_close()
+
+
+def test_flow_session_on_the_resident_field(ctx):
+    w, h = 320, 240
+    clip = synth.surf_clip(w, h, 4, seed=9)
+    ctx.tracers_open(w, h, "flow", max_lines=4, max_vertices=16)
+    ctx.tracers_add_streakline((100, 100))
+    ctx.stream_reset()
+    with pytest.raises(RcflowError) as e:
+        ctx.tracers_push()
+    assert e.value.code == ESTATE
+    host = Streakline((100, 100))
+    ref = ref_session([host], w, h, 16)
+    for t in range(4):
+        resident = ctx.push_frame_host(clip[t])
+        if t == 0:
+            assert resident is None
+            continue
+        cin = frame_bgr(w, h, t)
+        canvas = torch.as_tensor(cin).cuda()
+        ctx.tracers_push(canvas=canvas)
+        flow = resident.reshape(h, w, 2).clone()
+        host.run(ctx, flow, w, h, dt=1.0)
+        check_push(ctx, [host], ref, canvas, cin, None, "resident field, push %d" % t)
+    ctx.tracers_close()
+    ctx.stream_reset()
+
+
+def test_ring_expiry_reset_and_refusals(ctx):
+    w, h, mv = 200, 150, 4
+    fields = [smooth_field(w, h, t) for t in range(7)]
+    ctx.tracers_open(w, h, "flow", max_lines=2, max_vertices=mv, max_points=10)
+    ctx.tracers_add_streakline((60, 70))
+    tl = np.array([[20, 20], [30, 25], [40, 30]], f32)
+    ctx.tracers_add("timeline", tl)
+    ref = R.Session(w, h, mv)
+    ref.add(R.STREAK, [[60, 70]])
+    ref.add(R.TIMELINE, tl)
+
+    def state():
+        return ctx.tracers_info(), [ctx.tracers_read(i)[0].copy() for i in range(2)]
+
+    def step(f):
+        allv = ref.all_vertices()
+        moved, _ = ctx.streamline(allv, f, 1.0, 1, 0.0, variant=4)
+        ctx.tracers_push(flow=torch.as_tensor(f).cuda())
+        ref.push(moved.cpu().numpy())
+        for i in range(2):
+            got = ctx.tracers_read(i)[0]
+            assert np.array_equal(got.view(np.uint32), ref.lines[i].v.view(np.uint32)), "line %d" % i
+
+    for f in fields[:6]:
+        step(f)
+    info = ctx.tracers_info()
+    assert info["points"] == mv + 3 and info["dropped"] == 3 == ref.lines[0].dropped and info["pushes"] == 6
+    # every refusal leaves info and the lines as they were, and the next push gives what it would have given
+    before = state()
+    dflow = torch.as_tensor(fields[6]).cuda()
+    for call, code in [(lambda: ctx.tracers_add("cloud", np.zeros((4, 2), f32)), ESIZE),         # 4 + 3 + 4 > 10 points
+                       (lambda: ctx.tracers_add("streak", np.zeros((2, 2), f32)), EINVAL),
+                       (lambda: ctx._lib.rcflow_tracers_push_dev(ctx._h, 0, None, 0, dflow.data_ptr(), w * 8 - 8, None, 0), EINVAL),
+                       (lambda: ctx._lib.rcflow_tracers_push_dev(ctx._h, 0, None, 0, dflow.data_ptr(), w * 8, dflow.data_ptr(), w), EINVAL),
+                       (lambda: ctx._lib.rcflow_tracers_read(ctx._h, 0, 5, None, 0, None, None), EINVAL),
+                       (lambda: ctx.tracers_open(w, h, "flow", max_lines=0), EINVAL),
+                       (lambda: ctx.tracers_open(w, h, "lk", max_lines=2, max_vertices=8, lk=dict(win=(2, 2))), EINVAL),
+                       (lambda: ctx.tracers_open(5000, 100, "flow"), ESIZE)]:
+        try:
+            rc = call()
+        except RcflowError as e:
+            rc = e.code
+        assert rc == code
+        after = state()
+        assert after[0] == before[0] and all(np.array_equal(a, b) for a, b in zip(after[1], before[1]))
+    step(fields[6])
+    # reset: the lines as they were added, counters zero; the session then repeats itself
+    ctx.tracers_reset()
+    info = ctx.tracers_info()
+    assert info["points"] == 4 and info["pushes"] == 0 and info["dropped"] == 0 and info["lines"] == 2
+    assert np.array_equal(ctx.tracers_read(0)[0], np.array([[60, 70]], f32)) and np.array_equal(ctx.tracers_read(1)[0], tl)
+    ref.reset()
+    for f in fields[:3]:
+        step(f)
+    # a line added after pushes starts its own age
+    ctx.tracers_close()
+    ctx.tracers_open(w, h, "flow", max_lines=3, max_vertices=mv)
+    ref = R.Session(w, h, mv)
+    ctx.tracers_add_streakline((60, 70)); ref.add(R.STREAK, [[60, 70]])
+    step2 = fields[:5]
+    for k, f in enumerate(step2):
+        if k == 2:
+            ctx.tracers_add_streakline((90, 40)); ref.add(R.STREAK, [[90, 40]])
+        allv = ref.all_vertices()
+        moved, _ = ctx.streamline(allv, f, 1.0, 1, 0.0, variant=4)
+        ctx.tracers_push(flow=torch.as_tensor(f).cuda())
+        ref.push(moved.cpu().numpy())
+        for i in range(len(ref.lines)):
+            assert np.array_equal(ctx.tracers_read(i)[0].view(np.uint32), ref.lines[i].v.view(np.uint32))
+    ctx.tracers_close()
+    with pytest.raises(RcflowError) as e:
+        ctx.tracers_info()
+    assert e.value.code == ESTATE
+
+
+def test_two_slots_on_two_streams(ctx):
+    w, h = 333, 251
+    fa = [smooth_field(w, h, t) for t in range(5)]
+    fb = [smooth_field(w, h, t + 20)[:, ::-1].copy() for t in range(5)]
+    _, alone_a = run_flow_session(ctx, w, h, fa, False, stream=0)
+    ctx.tracers_close(0)
+    _, alone_b = run_flow_session(ctx, w, h, fb, False, stream=1)
+    ctx.tracers_close(1)
+    s0, s1 = torch.cuda.Stream(), torch.cuda.Stream()
+    pts = [(w * (i + 1) / 6.0, h / 2.0 + 9 * i) for i in range(5)]
+    for st, ts in ((0, s0), (1, s1)):
+        with torch.cuda.stream(ts):
+            ctx.tracers_open(w, h, "flow", max_lines=8, max_vertices=64, stream=st)
+            for p in pts:
+                ctx.tracers_add_streakline(p, stream=st)
+    outs = {0: [], 1: []}
+    for t in range(5):
+        for st, ts, f in ((0, s0, fa[t]), (1, s1, fb[t])):
+            with torch.cuda.stream(ts):
+                canvas = torch.as_tensor(frame_bgr(w, h, t)).cuda()
+                ctx.tracers_push(flow=torch.as_tensor(f).cuda(), canvas=canvas, stream=st)
+                outs[st].append(canvas)
+    torch.cuda.synchronize()
+    for t in range(5):
+        assert np.array_equal(outs[0][t].cpu().numpy(), alone_a[t][0]) and np.array_equal(outs[1][t].cpu().numpy(), alone_b[t][0])
+    for st, ts in ((0, s0), (1, s1)):
+        with torch.cuda.stream(ts):
+            ctx.tracers_close(st)
+
+
+def test_launches_per_push(ctx):
+    """LK mover = top pyrDowns + (top + 1) Scharr launches + one track + one book-keeping + one draw; FLOW mover = one
+    advection + one book-keeping + one draw."""
+    w, h = 640, 480
+    clip = synth.surf_clip(w, h, 4, seed=3)
+    canvas = torch.zeros((h, w, 3), dtype=torch.uint8, device="cuda")
+    ctx.tracers_open(w, h, "lk", max_lines=8, max_vertices=32)
+    build_lines(ctx, w, h)
+    frames = [torch.as_tensor(c).cuda() for c in clip]
+    ctx.tracers_push(gray=frames[0])
+    ctx.profile_enable(True)
+    ctx.profile_reset()
+    for t in range(1, 4):
+        ctx.tracers_push(gray=frames[t], canvas=canvas)
+    torch.cuda.synchronize()
+    prof = {r["kernel"]: r["launches"] for r in ctx.profile_read() if r["launches"]}
+    top = ctx.pyrlk_levels(w, h, (50, 50), 3)
+    assert prof == {"trackstab@1": 3 * top, "trackstab@2": 3 * (top + 1), "trackstab@3": 3, "tracers@0": 3, "tracers@1": 3}, prof
+    ctx.tracers_close()
+    ctx.tracers_open(w, h, "flow", max_lines=8, max_vertices=32)
+    ctx.tracers_add_streakline((100, 100))
+    f = torch.as_tensor(smooth_field(w, h, 0)).cuda()
+    ctx.profile_reset()
+    for t in range(3):
+        ctx.tracers_push(flow=f, canvas=canvas)
+    torch.cuda.synchronize()
+    prof = {r["kernel"]: r["launches"] for r in ctx.profile_read() if r["launches"]}
+    assert prof == {"advect_points@0": 3, "tracers@0": 3, "tracers@1": 3}, prof
+    ctx.profile_enable(False)
+    ctx.tracers_close()
+
+
+# ---------------------------------------------------------------------------- the drawing stage alone
+def random_prims(rng, n, w, h):
+    p = np.zeros(n, R.PRIM)
+    p["kind"] = rng.choice([R.DISC, R.LINE, R.LINE, 0, 3], n, p=[0.45, 0.3, 0.2, 0.025, 0.025])
+    for k, m in (("x0", w), ("x1", w), ("y0", h), ("y1", h)):
+        p[k] = rng.randint(-40, m + 40, n)
+    near = rng.rand(n) < 0.85                                    # most lines are short, as tracer edges are
+    p["x1"] = np.where(near, p["x0"] + rng.randint(-25, 26, n), p["x1"])
+    p["y1"] = np.where(near, p["y0"] + rng.randint(-25, 26, n), p["y1"])
+    deg = rng.rand(n) < 0.05
+    p["x1"] = np.where(deg, p["x0"], p["x1"])
+    p["y1"] = np.where(deg, p["y0"], p["y1"])
+    thick = rng.rand(n) < 0.4
+    p["size"] = np.where(p["kind"] == R.DISC, rng.randint(0, 12, n), np.where(thick, rng.randint(2, 9, n), 1))
+    bad = rng.rand(n) < 0.02
+    p["size"] = np.where(bad, rng.choice([-1, 0, 9, 20000], n), p["size"])
+    far = rng.rand(n) < 0.02
+    p["x0"] = np.where(far, rng.choice([-16384, 16384, -2 ** 31, 16383], n), p["x0"])
+    p["color"] = rng.randint(0, 2 ** 24, n).astype(np.uint32) | (rng.randint(0, 256, n).astype(np.uint32) << 24)
+    p["flags"] = (rng.rand(n) < 0.3).astype(np.uint32)
+    return p
+
+
+@pytest.mark.parametrize("n,w,h,ch", [(10000, 333, 251, 3), (10000, 258, 130, 1), (65536, 641, 363, 3), (65536, 509, 300, 1)])
+def test_draw_stage_against_numpy(ctx, n, w, h, ch):
+    rng = np.random.RandomState(n + w)
+    prims = random_prims(rng, n, w, h)
+    img = rng.randint(0, 256, (h, w, ch)).astype(np.uint8) if ch == 3 else rng.randint(0, 256, (h, w)).astype(np.uint8)
+    pad = 7
+    step = w * ch + pad
+    # an unaligned base pointer: the image starts 1 byte into the allocation; guard bytes before, between and after the rows
+    buf = torch.full((1 + h * step + 16,), 0xA5, dtype=torch.uint8, device="cuda")
+    view = torch.as_strided(buf, (h, w, ch) if ch == 3 else (h, w), (step, ch, 1) if ch == 3 else (step, 1), 1)
+    view.copy_(torch.as_tensor(img).cuda())
+    assert view.data_ptr() % 4 != 0
+    skipped = torch.zeros(1, dtype=torch.int64, device="cuda")
+    ctx.draw(view, prims.astype(DRAW_PRIM_DTYPE), skipped=skipped)
+    want = img.copy()
+    nskip = R.draw(want, prims)
+    got = view.cpu().numpy()
+    assert np.array_equal(got, want), "%d pixels differ" % int((got != want).sum())
+    assert int(skipped.item()) == nskip and nskip > 0
+    host = buf.cpu().numpy()
+    assert host[0] == 0xA5 and (host[1 + h * step:] == 0xA5).all()
+    rows = host[1:1 + h * step].reshape(h, step)
+    assert (rows[:, w * ch:] == 0xA5).all(), "guard bytes in the padding changed"
+    # refusals
+    for call in (lambda: ctx._lib.rcflow_draw_dev(ctx._h, 0, view.data_ptr(), w * ch - 1, w, h, ch, skipped.data_ptr(), 0, None),
+                 lambda: ctx._lib.rcflow_draw_dev(ctx._h, 0, view.data_ptr(), step, w, h, 2, skipped.data_ptr(), 0, None),
+                 lambda: ctx._lib.rcflow_draw_dev(ctx._h, 0, view.data_ptr(), step, w, h, ch, None, 5, None)):
+        assert call() == EINVAL
+    assert ctx._lib.rcflow_draw_dev(ctx._h, 0, view.data_ptr(), 70000, 16385, 1, ch, skipped.data_ptr(), 1, None) == ESIZE
+    assert np.array_equal(view.cpu().numpy(), want)
+
+
+def test_trace_of_advect_points_drawn(ctx):
+    w, h, n, iters = 640, 480, 64, 100
+    f = smooth_field(w, h, 2) * f32(3)
+    rng = np.random.RandomState(8)
+    seeds = np.stack([rng.uniform(5, w - 5, n), rng.uniform(5, h - 5, n)], -1).astype(f32)
+    seeds[:4] = [[-3, 10], [w + 2, 5], [0.5, 0.5], [w - 1.5, h - 1.5]]          # dead from the start
+    pts, trace = ctx.streamline(seeds.copy(), f, 8.0, iters, 1e9, variant=3, trace=True)
+    tr = trace.cpu().numpy()
+    for start in (None, seeds):
+        prims_dev = ctx.trace_prims(trace, start=start, color=0x20c0ff)
+        want_p = R.trace_prims(tr, start, 0x20c0ff)
+        assert np.array_equal(prims_dev.cpu().numpy().view(DRAW_PRIM_DTYPE).reshape(-1), want_p.astype(DRAW_PRIM_DTYPE))
+        cin = frame_bgr(w, h, 3)
+        canvas = torch.as_tensor(cin).cuda()
+        ctx.draw(canvas, prims_dev)
+        want = cin.copy()
+        R.draw(want, want_p)
+        assert np.array_equal(canvas.cpu().numpy(), want) and (want != cin).any()
+
+
+# ---------------------------------------------------------------------------- the C++ mirror
+def test_cpp_tracers_against_ctypes(ctx, tmp_path):
+    """rc::Tracers (include/rcflow_module.hpp) compiled as tests/cpp's programs are and run on a seeded frame sequence; the
+    vertices and the frame checksums it prints equal the ctypes session's on the same frames."""
+    exe = str(tmp_path / "test_tracers")
+    src = os.path.join(ROOT, "tests", "cpp", "test_tracers.cpp")
+    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"),
+           src, "-o", exe, "-L" + os.path.join(ROOT, "ripcurrents_amd"), "-lrcflow", "-L/opt/rocm/lib", "-lamdhip64",
+           "-Wl,-rpath," + os.path.join(ROOT, "ripcurrents_amd"), "-Wl,-rpath,/opt/rocm/lib"]
+    b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert b.returncode == 0, b.stderr[-4000:]
+    w, h, n = 320, 200, 6
+    r = subprocess.run([exe, str(w), str(h), str(n)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "test_tracers: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("push ")]
+    assert len(lines) == n
+    ctx.tracers_open(w, h, "lk", max_lines=8, max_vertices=6)
+    for i in range(5):
+        ctx.tracers_add_streakline((float(w // 6 * (i + 1)), float(h // 2 + 7 * i)))
+    ctx.tracers_add_timeline((f32(w) / f32(4), f32(h) / f32(4)), (f32(w) * f32(3) / f32(4), f32(h) / f32(3)), 7)
+    ctx.tracers_add("cloud", np.array([[f32(w) * f32(0.3), f32(h) * f32(0.7)], [f32(w) * f32(0.5), f32(h) * f32(0.75)],
+                                       [f32(w) * f32(0.7), f32(h) * f32(0.6)]], f32))
+    y, x = np.mgrid[0:h, 0:w].astype(np.int64)
+    for t, l in enumerate(lines):
+        u, v = x - t + 1000, y - t // 2 + 1000
+        gray = (128 + ((u * u + 3 * v * v + 5 * u * v) % 97) - 48 + ((u // 8 + v // 8) & 1) * 40).astype(np.uint8)
+        img = ((np.arange(w * h * 3, dtype=np.int64) * 7 + t) % 256).astype(np.uint8).reshape(h, w, 3)
+        canvas = torch.as_tensor(img).cuda()
+        ctx.tracers_push(gray=torch.as_tensor(gray).cuda(), canvas=canvas)
+        fnv = 1469598103934665603
+        for chunk in canvas.cpu().numpy().reshape(-1).tolist():
+            fnv = ((fnv ^ chunk) * 1099511628211) & (2 ** 64 - 1)
+        parts = l.split(" | ")
+        assert parts[0].split() == ["push", str(t), "%016x" % fnv], "frame checksum at push %d" % t
+        for i, part in enumerate(parts[1:]):
+            words = part.split()
+            got = ctx.tracers_read(i)[0]
+            assert int(words[0]) == len(got)
+            assert [int(q, 16) for q in words[1:]] == got.view(np.uint32).reshape(-1).tolist(), "line %d at push %d" % (i, t)
+    ctx.tracers_close()
