@@ -830,6 +830,105 @@ int rcflow_tracers_reset(rc_ctx* ctx, int stream);
 /* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
 int rcflow_tracers_close(rc_ctx* ctx, int stream);
 
+/* ------------------------------------------------------------------ rip regions: connected components, labelled and measured
+ * From pixels to detections: the components of a mask (the outmask of rcflow_classify_accumulate_dev, the d_mask of
+ * rcflow_ripmap_push_dev) numbered, filtered by area and measured on the device.  A push is SEVEN launches
+ * ("regions@0" .. "regions@6") whatever the mask holds, with no host synchronisation and no device-to-host copy;
+ * rcflow_regions_prims_dev is one more ("regions@7").  All integers are exact and do not depend on the order of addition.
+ *
+ * Input per push: d_mask, 8UC1, w x h, step >= w; a pixel is foreground iff its byte is non-zero (1 and 128 count like
+ * 255).  Optionally d_flow_xy (CV_32FC2, 8-byte aligned, flow_step a multiple of 8), or NULL: no flow statistics (zeros).
+ * Connectivity 4 or 8, fixed at open.
+ *  1. Components.  Maximal 4- or 8-connected sets of foreground pixels.  first(C) = the smallest y * w + x of a
+ *     component.  Components are numbered 1, 2, ... in increasing order of first (raster order of first appearance: the
+ *     numbering of scipy.ndimage.label with the cross / the full 3 x 3 structure).
+ *  2. Filter.  area(C) = number of pixels.  Components with area < min_area are dropped; the kept ones are renumbered
+ *     1..K in the same order.  min_area = 1 keeps everything.
+ *  3. Outputs of a push (device memory, each may be NULL; the state is updated whatever is asked for):
+ *     d_labels   int32 h x w (4-byte aligned, labels_step a multiple of 4, >= 4 w): the kept number of the pixel's
+ *                component, 0 for background and for dropped components.  All K numbers appear, also beyond max_regions.
+ *     d_mask_out 8UC1: 255 where d_labels would be non-zero, else 0 (an area opening: what rcflow_create_edges_dev /
+ *                rcflow_create_output_dev take next).  It may be d_mask itself with the same step (in place); any other
+ *                overlap of the byte ranges [first byte, last byte] of an input or output with another output is RC_EINVAL.
+ *     d_regions  max_regions records rc_region (8-byte aligned), the first min(K, max_regions) kept components in
+ *                order; the rest of the array is zero bytes.
+ *     d_summary  8 int64: components before the filter, K, records written, foreground pixels, pixels in kept
+ *                components, flow pixels left out as bad (kept components only, also those beyond max_regions), pushes
+ *                since open / reset (this one included), largest kept area.
+ *     Row padding of every output is never written.
+ *  4. rc_region: the integer part: label, area, the inclusive box x0, y0, x1, y1, first_x, first_y, edges (bit 0..3:
+ *     touches column 0, row 0, column w - 1, row h - 1), bad; sx, sy, sxx, syy, sxy: sums of x, y, x*x, y*y, x*y over its
+ *     pixels; fx, fy: sums of q = (int64)rint(v * 65536) per flow component over its pixels, where a pixel with a
+ *     component that is not finite or with |q| > 2^40 is left out of both sums and counted in bad: the rule and the
+ *     scale of rcflow_ripmap_* ("sums" above), so a region's mean flow and a cell's mean flow are the same kind of number.
+ *     The derived part, in double, each operation rounded on its own (no fused multiply-add), n = area, m = n - bad:
+ *       cx = sx / n;  cy = sy / n;
+ *       mean_fx = m ? (float)(fx / 65536 / m) : 0;  mean_fy likewise;
+ *       mxx = sxx / n - cx * cx;  myy = syy / n - cy * cy;  mxy = sxy / n - cx * cy;
+ *       t = (mxx + myy) * 0.5;  d = (mxx - myy) * 0.5;  r = sqrt(d * d + mxy * mxy);
+ *       var_major = t + r;  var_minor = t - r   (px^2; rounding may leave var_minor a hair below 0);
+ *       angle = atan2(mxy, d) * 0.5 * (180 / pi), + 180 when negative, 0 when that gives 180: the major axis, degrees in
+ *       [0, 180), x to the right and y DOWN.
+ *     The derived part is for people: no decision in the library depends on it.
+ *  5. Primitives.  rcflow_regions_prims_dev turns the records of the last push into 6 * max_regions primitives for
+ *     rcflow_draw_dev, record after record: the four box edges as lines of `thickness` (top (x0,y0)-(x1,y0), right
+ *     (x1,y0)-(x1,y1), bottom (x1,y1)-(x0,y1), left (x0,y1)-(x0,y0)), a disc of disc_radius at the centroid rounded in
+ *     integers (px = (2 sx + n) / (2 n), py likewise), and, when flow_scale != 0 and n > bad, a line of `thickness` from
+ *     there to (px + (int32)rint(fx / 65536 / m * flow_scale), py + ...) with the mean taken in double as above (a step
+ *     that is not finite or beyond 2^30 gives the coordinate INT32_MIN, which the drawing skips).  Slots without a record
+ *     (and the flow line when it is off) are all-zero records, kind = 0: rcflow_draw_dev skips them as an unknown kind AND
+ *     COUNTS THEM in d_skipped when one is given.  The count is fixed, so the host never reads the device to know it. */
+typedef struct rc_regions_params {
+    int connectivity;   /* 4 | 8 */
+    int min_area;       /* >= 1 */
+    int max_regions;    /* 1..RC_REGIONS_MAX */
+    int flags;          /* 0 */
+} rc_regions_params;
+#define RC_REGIONS_MAX 65536
+#define RC_REGIONS_LAUNCHES 7      /* per push, whatever the mask holds */
+typedef struct rc_region {         /* 144 bytes */
+    int32_t label, area;
+    int32_t x0, y0, x1, y1;
+    int32_t first_x, first_y;
+    int32_t edges, bad;
+    int64_t sx, sy, sxx, syy, sxy;
+    int64_t fx, fy;
+    double cx, cy;
+    double var_major, var_minor, angle;
+    float mean_fx, mean_fy;
+} rc_region;
+typedef struct rc_regions_info {
+    int w, h, connectivity, min_area, max_regions, flags;
+    int launches_per_push;             /* RC_REGIONS_LAUNCHES */
+    long long pushes;                  /* since open / reset */
+    size_t device_bytes;
+} rc_regions_info;
+/* Allocates everything the slot will ever need (labels and area scratch: 4 bytes per pixel each; RC_ENOMEM with the
+ * byte count in rcflow_last_error).  Re-opening replaces the state; a refused open leaves the open state as it was.
+ * RC_EINVAL: connectivity other than 4 / 8, min_area < 1, max_regions outside 1..RC_REGIONS_MAX, unknown flag bits, a
+ * frame of 2^31 pixels or more; RC_ESIZE beyond the context's max_w x max_h. */
+int rcflow_regions_open(rc_ctx* ctx, int stream, int w, int h, const rc_regions_params* prm);
+/* One mask.  Every refusal is decided before anything is queued and leaves the state as it was. */
+int rcflow_regions_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_mask, size_t mask_step,
+                            const float* d_flow_xy, size_t flow_step,
+                            int32_t* d_labels, size_t labels_step, uint8_t* d_mask_out, size_t mask_out_step,
+                            rc_region* d_regions, long long* d_summary);
+/* 6 * max_regions primitives from the records of the last push (before the first push: all kind 0) into d_prims.
+ * RC_EINVAL: thickness outside 1..RC_DRAW_MAX_THICKNESS, disc_radius outside 0..RC_DRAW_COORD_MAX, flow_scale not finite. */
+int rcflow_regions_prims_dev(rc_ctx* ctx, int stream, uint32_t color, int thickness, int disc_radius, double flow_scale,
+                             rc_draw_prim* d_prims);
+/* Blocks until the slot's stream has finished; for hosts and tests.  The records of the last push: min(cap, records
+ * written) of them into regions, records written into n, the summary; any pointer may be NULL.  Before the first push: zeros. */
+int rcflow_regions_read(rc_ctx* ctx, int stream, rc_region* regions, int cap, int* n, long long summary[8]);
+/* min_area from the next push on (RC_EINVAL below 1); open restores the parameter, reset keeps what was set */
+int rcflow_regions_set(rc_ctx* ctx, int stream, int min_area);
+/* zeroes the kept records, the summary and the push count; asynchronous, on the slot's stream */
+int rcflow_regions_reset(rc_ctx* ctx, int stream);
+/* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
+int rcflow_regions_close(rc_ctx* ctx, int stream);
+/* never blocks; RC_ESTATE when nothing is open */
+int rcflow_regions_info(rc_ctx* ctx, int stream, rc_regions_info* info);
+
 /* Display path, ripcurrents.cpp:233-273 (= streamline_displacement / _total_motion / _ratio /
  * _positions, ripcurrents_module.cpp:13-60) on the slot's streamline field (rcflow_advect_field_dev):
  * which 0 = |pt|, 1 = dist, 2 = |pt| / dist; minMaxLoc + convertTo(CV_8UC1, 255/max) +

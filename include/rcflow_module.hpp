@@ -670,4 +670,75 @@ class Tracers {
     void *d_gray_ = nullptr, *d_canvas_ = nullptr;
 };
 
+// Rip regions on the device (rcflow_regions_*): the connected components of a mask (outmask of the classification, the
+// opposing-flow map's mask) numbered in raster order, filtered by area and measured.  Host images in, host images and
+// records out, as the rest of this class family.
+class Regions {
+  public:
+    Regions(Pipeline& pipe, int connectivity = 8, int min_area = 1, int max_regions = 1024) : pipe_(pipe), max_regions_(max_regions) {
+        rc_regions_params p{};
+        p.connectivity = connectivity; p.min_area = min_area; p.max_regions = max_regions;
+        check(rcflow_regions_open(pipe.context(), 0, pipe.width(), pipe.height(), &p));
+    }
+    ~Regions() {
+        (void)rcflow_regions_close(pipe_.context(), 0);
+        for (void* p : {d_mask_, d_labels_, d_prims_, d_canvas_}) if (p) (void)hipFree(p);
+    }
+    Regions(const Regions&) = delete;
+    Regions& operator=(const Regions&) = delete;
+
+    // mask: 8UC1 of the pipeline's size, non-zero is foreground.  with_flow: the pipeline's resident flow field gives the
+    // records their flow sums.  labels (32SC1, optional) and maskOut (8UC1, optional; may be `mask`) are filled when given.
+    void push(const Mat& mask, bool with_flow = false, Mat* labels = nullptr, Mat* maskOut = nullptr) {
+        const int w = pipe_.width(), h = pipe_.height();
+        if (mask.empty() || mask.rows != h || mask.cols != w || mask.channels != 1 || mask.elem != 1)
+            throw Error(RC_EINVAL, "Regions::push: the mask must be 8UC1 of the pipeline's size");
+        if (labels && (labels->empty() || labels->rows != h || labels->cols != w || labels->channels != 1 || labels->elem != 4))
+            throw Error(RC_EINVAL, "Regions::push: labels must be 32SC1 of the pipeline's size");
+        if (maskOut && (maskOut->empty() || maskOut->rows != h || maskOut->cols != w || maskOut->channels != 1 || maskOut->elem != 1))
+            throw Error(RC_EINVAL, "Regions::push: maskOut must be 8UC1 of the pipeline's size");
+        if (with_flow && !pipe_.device_flow()) throw Error(RC_ESTATE, "Regions::push: the pipeline holds no flow field");
+        if (!d_mask_) hip_check(hipMalloc(&d_mask_, (size_t)w * h), "hipMalloc mask");
+        if (labels && !d_labels_) hip_check(hipMalloc(&d_labels_, (size_t)w * h * 4), "hipMalloc labels");
+        check(rcflow_sync(pipe_.context(), 0));
+        hip_check(hipMemcpy2D(d_mask_, (size_t)w, mask.data, mask.step, (size_t)w, h, hipMemcpyHostToDevice), "upload mask");
+        check(rcflow_regions_push_dev(pipe_.context(), 0, (const uint8_t*)d_mask_, (size_t)w, with_flow ? pipe_.device_flow() : nullptr,
+                                      (size_t)w * 8, labels ? (int32_t*)d_labels_ : nullptr, (size_t)w * 4,
+                                      maskOut ? (uint8_t*)d_mask_ : nullptr, (size_t)w, nullptr, nullptr));
+        if (labels || maskOut) check(rcflow_sync(pipe_.context(), 0));
+        if (labels) hip_check(hipMemcpy2D(labels->data, labels->step, d_labels_, (size_t)w * 4, (size_t)w * 4, h, hipMemcpyDeviceToHost), "download labels");
+        if (maskOut) hip_check(hipMemcpy2D(maskOut->data, maskOut->step, d_mask_, (size_t)w, (size_t)w, h, hipMemcpyDeviceToHost), "download mask");
+    }
+    // waits for the pipeline's stream: the records of the last push, in order; summary (optional): the 8 words of include/rcflow.h
+    std::vector<rc_region> regions(long long* summary = nullptr) {
+        std::vector<rc_region> r((size_t)max_regions_);
+        int n = 0;
+        check(rcflow_regions_read(pipe_.context(), 0, r.data(), max_regions_, &n, summary));
+        r.resize((size_t)n);
+        return r;
+    }
+    // paints the boxes, centroids and (flow_scale != 0) mean-flow lines of the last push into img (8UC3)
+    void draw(Mat& img, uint32_t color = 0x00ffff, int thickness = 1, int disc_radius = 3, double flow_scale = 0.) {
+        const int w = pipe_.width(), h = pipe_.height();
+        if (img.empty() || img.rows != h || img.cols != w || img.channels != 3 || img.elem != 1)
+            throw Error(RC_EINVAL, "Regions::draw: img must be 8UC3 of the pipeline's size");
+        if (!d_prims_) hip_check(hipMalloc(&d_prims_, (size_t)6 * max_regions_ * sizeof(rc_draw_prim)), "hipMalloc prims");
+        if (!d_canvas_) hip_check(hipMalloc(&d_canvas_, (size_t)w * h * 3), "hipMalloc canvas");
+        check(rcflow_sync(pipe_.context(), 0));
+        hip_check(hipMemcpy2D(d_canvas_, (size_t)w * 3, img.data, img.step, (size_t)w * 3, h, hipMemcpyHostToDevice), "upload canvas");
+        check(rcflow_regions_prims_dev(pipe_.context(), 0, color, thickness, disc_radius, flow_scale, (rc_draw_prim*)d_prims_));
+        check(rcflow_draw_dev(pipe_.context(), 0, (uint8_t*)d_canvas_, (size_t)w * 3, w, h, 3, (const rc_draw_prim*)d_prims_, 6 * max_regions_, nullptr));
+        check(rcflow_sync(pipe_.context(), 0));
+        hip_check(hipMemcpy2D(img.data, img.step, d_canvas_, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost), "download canvas");
+    }
+    void setMinArea(int min_area) { check(rcflow_regions_set(pipe_.context(), 0, min_area)); }
+    rc_regions_info info() { rc_regions_info i; check(rcflow_regions_info(pipe_.context(), 0, &i)); return i; }
+    void reset() { check(rcflow_regions_reset(pipe_.context(), 0)); }
+
+  private:
+    Pipeline& pipe_;
+    int max_regions_;
+    void *d_mask_ = nullptr, *d_labels_ = nullptr, *d_prims_ = nullptr, *d_canvas_ = nullptr;
+};
+
 }  // namespace rc

@@ -37,6 +37,8 @@ RC_DRAW_COORD_MAX, RC_DRAW_MAX_THICKNESS = 16383, 8
 # rcflow_tracers_*: movers and line kinds
 TRACERS_MOVERS = {"lk": 0, "flow": 1}
 TRACER_KINDS = {"streak": 0, "timeline": 1, "cloud": 2}
+# rcflow_regions_*: the bound on max_regions, the launches of a push
+RC_REGIONS_MAX, RC_REGIONS_LAUNCHES = 65536, 7
 
 ERRORS = {-1: "RC_EINVAL", -2: "RC_ENOMEM", -3: "RC_EHIP", -4: "RC_ENODEV", -5: "RC_ESIZE",
           -6: "RC_ESTATE", -7: "RC_ECOMM"}
@@ -81,6 +83,26 @@ class TracersInfo(C.Structure):
     _fields_ = [("w", C.c_int), ("h", C.c_int), ("mover", C.c_int), ("max_lines", C.c_int), ("max_vertices", C.c_int),
                 ("max_points", C.c_int), ("lines", C.c_int), ("points", C.c_int), ("prims", C.c_int), ("primed", C.c_int),
                 ("pushes", C.c_longlong), ("dropped", C.c_longlong), ("device_bytes", C.c_size_t)]
+
+
+class RegionsParams(C.Structure):
+    """rc_regions_params (include/rcflow.h)."""
+    _fields_ = [("connectivity", C.c_int), ("min_area", C.c_int), ("max_regions", C.c_int), ("flags", C.c_int)]
+
+
+class Region(C.Structure):
+    """rc_region (include/rcflow.h), 144 bytes; numpy: api.REGION_DTYPE."""
+    _fields_ = [("label", C.c_int32), ("area", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32),
+                ("y1", C.c_int32), ("first_x", C.c_int32), ("first_y", C.c_int32), ("edges", C.c_int32), ("bad", C.c_int32),
+                ("sx", C.c_int64), ("sy", C.c_int64), ("sxx", C.c_int64), ("syy", C.c_int64), ("sxy", C.c_int64),
+                ("fx", C.c_int64), ("fy", C.c_int64), ("cx", C.c_double), ("cy", C.c_double), ("var_major", C.c_double),
+                ("var_minor", C.c_double), ("angle", C.c_double), ("mean_fx", C.c_float), ("mean_fy", C.c_float)]
+
+
+class RegionsInfo(C.Structure):
+    """rc_regions_info (include/rcflow.h)."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("connectivity", C.c_int), ("min_area", C.c_int), ("max_regions", C.c_int),
+                ("flags", C.c_int), ("launches_per_push", C.c_int), ("pushes", C.c_longlong), ("device_bytes", C.c_size_t)]
 
 
 class FitParams(C.Structure):
@@ -217,6 +239,14 @@ SIGNATURES = {
     "rcflow_tracers_info": [_vp, _i, C.POINTER(TracersInfo)],
     "rcflow_tracers_reset": [_vp, _i],
     "rcflow_tracers_close": [_vp, _i],
+    "rcflow_regions_open": [_vp, _i, _i, _i, C.POINTER(RegionsParams)],
+    "rcflow_regions_push_dev": [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp],
+    "rcflow_regions_prims_dev": [_vp, _i, C.c_uint32, _i, _i, _d, _vp],
+    "rcflow_regions_read": [_vp, _i, _vp, _i, C.POINTER(_i), _vp],
+    "rcflow_regions_set": [_vp, _i, _i],
+    "rcflow_regions_reset": [_vp, _i],
+    "rcflow_regions_close": [_vp, _i],
+    "rcflow_regions_info": [_vp, _i, C.POINTER(RegionsInfo)],
     "rcflow_comm_unique_id": [_vp],
     "rcflow_comm_init": [_vp, _vp, _i, _i],
     "rcflow_comm_destroy": [_vp],

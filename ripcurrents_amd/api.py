@@ -30,6 +30,7 @@ from ._lib import FarnebackParams, HIST_BINS, HIST_DIRECTIONS, HIST_WORDS, RC_FA
 from ._lib import RC_STAB_ANCHOR_FIRST, RC_STAB_MAX_PATCHES, RC_WARP_INVERSE_MAP, STAB_MODELS, FIT_MODELS, FitParams, StabTracks
 from ._lib import RC_RIPMAP_WAIT_FULL, RIPMAP_SOURCES
 from ._lib import TRACERS_MOVERS, TRACER_KINDS, TracersInfo, TracersParams
+from ._lib import RegionsInfo, RegionsParams
 
 __all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState"]
 
@@ -37,6 +38,15 @@ __all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMa
 # rc_draw_prim as a numpy record (32 bytes): what Context.draw takes and Context.tracers_prims returns
 DRAW_PRIM_DTYPE = np.dtype([("kind", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("size", "<i4"),
                             ("color", "<u4"), ("flags", "<u4")])
+
+# rc_region as a numpy record (144 bytes): what Context.regions_read returns
+REGION_DTYPE = np.dtype([("label", "<i4"), ("area", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"),
+                         ("first_x", "<i4"), ("first_y", "<i4"), ("edges", "<i4"), ("bad", "<i4"),
+                         ("sx", "<i8"), ("sy", "<i8"), ("sxx", "<i8"), ("syy", "<i8"), ("sxy", "<i8"), ("fx", "<i8"), ("fy", "<i8"),
+                         ("cx", "<f8"), ("cy", "<f8"), ("var_major", "<f8"), ("var_minor", "<f8"), ("angle", "<f8"),
+                         ("mean_fx", "<f4"), ("mean_fy", "<f4")])
+# the eight words of a regions summary, in order
+REGIONS_SUMMARY = ("components", "kept", "records", "foreground", "kept_pixels", "bad_pixels", "pushes", "largest_area")
 
 
 def _params(pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags):
@@ -1237,6 +1247,84 @@ class Context:
     def tracers_close(self, stream=0):
         self._bind(stream)          # waits for the pushes queued on that stream before freeing
         check(self._lib.rcflow_tracers_close(self._h, stream))
+
+    # ------------------------------------------------------------------ rip regions
+    def regions_open(self, w, h, connectivity=8, min_area=1, max_regions=1024, stream=0):
+        """Opens the slot's region labelling for w x h masks: connected components (4 or 8 neighbours) numbered in raster
+        order of their first pixel, those below min_area pixels dropped, the first max_regions of the rest measured
+        (include/rcflow.h, "rip regions").  Labels and area scratch take 8 bytes per pixel of device memory."""
+        p = RegionsParams(connectivity=int(connectivity), min_area=int(min_area), max_regions=int(max_regions), flags=0)
+        self._bind(stream)          # the state is zeroed on the slot's stream: the one the pushes will run on
+        check(self._lib.rcflow_regions_open(self._h, stream, int(w), int(h), C.byref(p)))
+
+    def regions_info(self, stream=0):
+        """dict of rc_regions_info; never blocks."""
+        info = RegionsInfo()
+        check(self._lib.rcflow_regions_info(self._h, stream, C.byref(info)))
+        return {k: getattr(info, k) for k, _ in RegionsInfo._fields_}
+
+    def regions_set(self, min_area, stream=0):
+        """min_area from the next push on."""
+        check(self._lib.rcflow_regions_set(self._h, stream, int(min_area)))
+
+    def regions_push(self, mask, flow=None, labels=None, mask_out=None, regions=None, summary=None, stream=0):
+        """One mask (HxW uint8 device tensor, dense pixels, rows may be padded; non-zero is foreground): RC_REGIONS_LAUNCHES
+        launches, nothing is synchronised.  flow: HxWx2 float32 (dense pixels) for the per-region flow sums, or None.
+        Outputs are preallocated device tensors, each optional: labels HxW int32, mask_out HxW uint8 (255 inside a kept
+        component; may be `mask` itself), regions a contiguous uint8 tensor of max_regions * 144 bytes (rc_region records,
+        REGION_DTYPE), summary 8 int64.  The records and the summary also stay on the slot for regions_read / regions_prims."""
+        info = self.regions_info(stream)
+        h, w = info["h"], info["w"]
+        _check_out(mask, self.device, torch.uint8, "mask", shape=(h, w), dense=True)
+        fp, fstep, lp, lstep, op, ostep, rp, sp = C.c_void_p(None), 0, C.c_void_p(None), 0, C.c_void_p(None), 0, C.c_void_p(None), C.c_void_p(None)
+        if flow is not None:
+            flow = self._dev(flow, torch.float32)
+            if flow.dim() != 3 or tuple(flow.shape) != (h, w, 2) or flow.stride(2) != 1 or flow.stride(1) != 2:
+                raise ValueError("flow must be %dx%dx2 float32 with dense pixels, as opened" % (h, w))
+            fp, fstep = self._ptr(flow), flow.stride(0) * 4
+        if labels is not None:
+            _check_out(labels, self.device, torch.int32, "labels", shape=(h, w), dense=True)
+            lp, lstep = self._ptr(labels), labels.stride(0) * 4
+        if mask_out is not None:
+            _check_out(mask_out, self.device, torch.uint8, "mask_out", shape=(h, w), dense=True)
+            op, ostep = self._ptr(mask_out), mask_out.stride(0)
+        if regions is not None:
+            rp = self._ptr(_check_out(regions, self.device, torch.uint8, "regions", numel=info["max_regions"] * REGION_DTYPE.itemsize))
+        if summary is not None:
+            sp = self._ptr(_check_out(summary, self.device, torch.int64, "summary", numel=8))
+        self._bind(stream)
+        check(self._lib.rcflow_regions_push_dev(self._h, stream, self._ptr(mask), mask.stride(0), fp, fstep, lp, lstep, op, ostep, rp, sp))
+
+    def regions_prims(self, color=0x00ffff, thickness=1, disc_radius=3, flow_scale=0.0, out=None, stream=0):
+        """The records of the last push as 6 * max_regions primitives for draw() -> a device uint8 tensor of rc_draw_prim
+        records: per record its box (four lines), a disc at the centroid and, with flow_scale != 0, a line along the mean
+        flow times flow_scale; slots without a record are kind 0, which draw() skips (and counts)."""
+        n = 6 * self.regions_info(stream)["max_regions"]
+        if out is None:
+            out = torch.empty((n, 32), dtype=torch.uint8, device=self.device)
+        else:
+            _check_out(out, self.device, torch.uint8, "out", numel=n * 32)
+        self._bind(stream)
+        check(self._lib.rcflow_regions_prims_dev(self._h, stream, int(color), int(thickness), int(disc_radius), float(flow_scale),
+                                                 self._ptr(out)))
+        return out
+
+    def regions_read(self, stream=0):
+        """Waits for the slot's stream -> (records of the last push as a numpy array of REGION_DTYPE, dict of the summary
+        with the names of REGIONS_SUMMARY)."""
+        cap = self.regions_info(stream)["max_regions"]
+        rec, n, summ = np.zeros(cap, REGION_DTYPE), C.c_int(0), np.zeros(8, np.int64)
+        self._bind(stream)
+        check(self._lib.rcflow_regions_read(self._h, stream, rec.ctypes.data, cap, C.byref(n), summ.ctypes.data))
+        return rec[:n.value].copy(), dict(zip(REGIONS_SUMMARY, (int(v) for v in summ)))
+
+    def regions_reset(self, stream=0):
+        self._bind(stream)
+        check(self._lib.rcflow_regions_reset(self._h, stream))
+
+    def regions_close(self, stream=0):
+        self._bind(stream)          # waits for the pushes queued on that stream before freeing
+        check(self._lib.rcflow_regions_close(self._h, stream))
 
     def _an_size(self, stream):
         w, h = C.c_int(0), C.c_int(0)

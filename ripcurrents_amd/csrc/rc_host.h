@@ -152,6 +152,21 @@ struct RcTracers {
     RcZeroFence zf;
 };
 
+// Rip regions of one stream slot (region_kernels.hip): connected components of a mask, numbered in raster order, filtered
+// and measured.  Everything is allocated by rcflow_regions_open and released by rcflow_regions_close / rcflow_destroy.
+struct RcRegions {
+    bool open = false;
+    int w = 0, h = 0;
+    rc_regions_params prm{};        // min_area: as rcflow_regions_set left it
+    long long pushes = 0;           // since open / reset
+    RcBuf par;                      // [h * w] int32: the union-find's parent, -1 for background; after a push every pixel's root
+    RcBuf area;                     // [h * w] int32: a root's area, then its kept number
+    RcBuf rows;                     // per row: kept roots, roots, foreground pixels, largest kept area (int32 [4][h]) | kept pixels (int64 [h])
+    RcBuf acc;                      // RgCtl | max_regions RgAcc: the sums the statistics launch adds into
+    RcBuf out;                      // the last push: 8 int64 summary | max_regions rc_region
+    RcZeroFence zf;
+};
+
 // warp_kernels.hip: one launch of the affine / perspective warp
 struct RcWarpArgs {
     const uint8_t* src; size_t step;
@@ -226,6 +241,7 @@ struct RcSlot {
     RcFrameStab fs;
     RcRipMap rm;
     RcTracers tr;
+    RcRegions rg;
     RcPhaseCorr pc;
 };
 
@@ -272,7 +288,9 @@ enum { RC_K_PYR = 0, RC_K_POLY = 1, RC_K_ITER = 2, RC_K_HIST = 3, RC_K_THRESH = 
        RC_K_RIPMAP = 20 /* @0 ring, mean, cell sums, colour and the finish, @1 mask */,
        RC_K_TRACKSTAB = 21 /* @0 gray, @1 pyrDown, @2 Scharr, @3 PyrLK track, @4 robust fit, @5 corner cells */,
        RC_K_TRACERS = 22 /* @0 book-keeping and primitives, @1 draw, @2 trace to lines */,
-       RC_K_KINDS = 23 };
+       RC_K_REGIONS = 23 /* @0 runs, @1 merge, @2 flatten and count, @3 row counts, @4 numbers, @5 outputs and sums, @6 records,
+                            @7 primitives */,
+       RC_K_KINDS = 24 };
 
 void rc_set_error(const char* fmt, ...);
 int rc_buf_ensure(RcBuf& b, size_t bytes);
@@ -345,7 +363,7 @@ struct RcProfScope {
     } while (0)
 
 // ---------------------------------------------------------------------------- per-slot products
-// RcTimex, RcFrameStab, RcRipMap and RcTracers share one lifecycle.  A product supplies
+// RcTimex, RcFrameStab, RcRipMap, RcTracers and RcRegions share one lifecycle.  A product supplies
 //   void rc_state_free(T&)             frees every buffer and the fence; the state is T() again
 //   int rc_state_zero(RcSlot&, T&)     rc_fence_zero of what open / reset clear, and the counters
 // and open / reset / close are written once, here.
@@ -353,10 +371,12 @@ void rc_state_free(RcTimex& t);
 void rc_state_free(RcFrameStab& f);
 void rc_state_free(RcRipMap& m);
 void rc_state_free(RcTracers& t);
+void rc_state_free(RcRegions& g);
 int rc_state_zero(RcSlot& s, RcTimex& t);
 int rc_state_zero(RcSlot& s, RcFrameStab& f);
 int rc_state_zero(RcSlot& s, RcRipMap& m);
 int rc_state_zero(RcSlot& s, RcTracers& t);
+int rc_state_zero(RcSlot& s, RcRegions& g);
 
 // The tail of every open.  The caller has validated, selected the device and built `fresh` (rc: what its allocations
 // returned).  The state that is open is touched only once nothing can be refused any more: a refused open leaves it as it
