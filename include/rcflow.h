@@ -929,6 +929,110 @@ int rcflow_regions_close(rc_ctx* ctx, int stream);
 /* never blocks; RC_ESTATE when nothing is open */
 int rcflow_regions_info(rc_ctx* ctx, int stream, rc_regions_info* info);
 
+/* ------------------------------------------------------------------ rip tracks: regions followed from push to push
+ * The numbers of rcflow_regions_* are raster-order numbers of one mask.  This state gives every region an identity that
+ * lasts: it consumes the device outputs of rcflow_regions_push_dev (label image, records, summary), keeps a table of tracks
+ * with hits, misses and confirmation, and emits a mask of the confirmed regions that does not flicker with the input.  A push
+ * is SIX launches ("tracks@0" .. "tracks@5") whatever the labels hold, with no host synchronisation and no device-to-host
+ * copy; rcflow_tracks_prims_dev is one more ("tracks@6").  The rules are integer-only: nothing depends on the order of
+ * atomics, and numbers are given by rank, never by arrival.
+ *
+ * State: the footprint P, int32 [h][w]: slot + 1 of the track that last covered the pixel, or 0; the table of max_tracks
+ * records rc_track (a free slot is all zero bytes, a used one has id >= 1); next_id (1 after open / reset); the push count
+ * (on the device, so a captured launch sequence stays valid); the overlap table [max_regions + 1][max_tracks] int32.
+ *
+ * One push, n = 1, 2, ...  R = min(d_regions_summary[2], max_regions) (records written, read on the device; a negative
+ * word counts as 0).  A label outside 1..R is background: negative labels, labels beyond max_regions, the components
+ * beyond the records.  Nothing is indexed with such a label.  Record c is d_regions[c - 1]; its area is >= 1, as in every
+ * record rcflow_regions_push_dev writes (a record with area <= 0 gives px = py = 0).
+ *  0. Free.  A slot whose record carried RC_TRACK_ENDED after the previous push becomes zero bytes.  The tracks alive "at
+ *     the start" are the other used slots.
+ *  1. Overlap.  ov[c][t] = number of pixels with label c in 1..R and P = t + 1.
+ *  2. Claim.  best(c) = the alive track with the largest ov[c][t] among those with ov[c][t] >= min_overlap, the smaller
+ *     id among equals; there may be none.
+ *  3. Winner.  For an alive t, among the c with best(c) = t: the one with the largest ov[c][t], the lowest c among equals.
+ *  4. Update.  Every alive track: age += 1.  With a winner c: flags = SEEN (| SPLIT when more than one c claimed it),
+ *     hits += 1, misses = 0, label = c, overlap = ov[c][t]; area, x0, y0, x1, y1 from record c; px = (2 sx + area) /
+ *     (2 area), py likewise (the integers of rcflow_regions_prims_dev); area_sum += area, fx_sum += fx, fy_sum += fy,
+ *     m_sum += area - bad.  Without one: flags = COASTING (| MERGED when some c has ov[c][t] >= min_overlap),
+ *     misses += 1, label = 0, overlap = 0, the geometry stays as last seen; misses > max_misses adds ENDED.  Then
+ *     CONFIRMED is added whenever hits >= min_hits, and mean_fx = m_sum ? (float)((double)fx_sum / 65536 / m_sum) : 0,
+ *     each operation rounded on its own; mean_fy likewise.
+ *  5. Births.  The regions c in 1..R that won no track, in ascending c, take the free slots in ascending slot (those freed
+ *     in step 0 count, those that ended in this push do not): the k-th region the k-th slot, id = next_id + k (k from 0);
+ *     next_id grows by the number born.  parent = the id of best(c) when there is one (a split child), else 0; flags =
+ *     BORN | SEEN (| CONFIRMED when min_hits <= 1); age = hits = 1, first_push = n, overlap = 0; px0 = px, py0 = py, kept
+ *     for life; the sums are those of this region alone.  Regions beyond the free slots stay untracked and are counted.
+ *  6. Paint.  P = slot(c) + 1 where the pixel's label c is in 1..R (0 when c is untracked); elsewhere the old P when that
+ *     track is alive and not ENDED after step 4, else 0.  So a coasting track keeps what is left of its last footprint,
+ *     and a region that comes back there within max_misses pushes gets its id back.
+ *  7. Outputs (device memory, each may be NULL; the state is updated whatever is asked for; row padding is never written):
+ *     d_tracks          max_tracks records in slot order (8-byte aligned).
+ *     d_track_of_label  int32 [max_regions + 1]: slot + 1 of the label's track; entry 0, untracked labels and entries
+ *                       above R are 0.
+ *     d_mask_out        8UC1: 255 where the pixel's label is in 1..R and its track is CONFIRMED, else 0: what
+ *                       rcflow_create_edges_dev / rcflow_create_output_dev take next.
+ *     d_summary         8 int64: tracks alive and not ended; confirmed among them; born; ended; seen (births included);
+ *                       coasting (those that ended in this push included); regions left untracked; n.
+ * rc_track: slot is the record's index; the other fields as the steps name them.
+ * Primitives: rcflow_tracks_prims_dev writes 5 * max_tracks primitives, slot after slot: for a track that is CONFIRMED and
+ * not ENDED the four box edges in the order of rcflow_regions_prims_dev and a disc at (px, py); all-zero records else. */
+#define RC_TRACKS_MAX_REGIONS 1024
+#define RC_TRACKS_MAX 1024
+#define RC_TRACKS_LAUNCHES 6       /* per push, whatever the labels hold */
+enum { RC_TRACK_SEEN = 1, RC_TRACK_BORN = 2, RC_TRACK_COASTING = 4, RC_TRACK_ENDED = 8,
+       RC_TRACK_SPLIT = 16, RC_TRACK_MERGED = 32, RC_TRACK_CONFIRMED = 64 };
+typedef struct rc_tracks_params {
+    int max_regions;   /* 1..RC_TRACKS_MAX_REGIONS: labels above it are background */
+    int max_tracks;    /* 1..RC_TRACKS_MAX slots */
+    int min_overlap;   /* >= 1 pixels */
+    int max_misses;    /* 0..65535 consecutive pushes a track may go unseen */
+    int min_hits;      /* >= 1: pushes seen before RC_TRACK_CONFIRMED */
+    int flags;         /* 0 */
+} rc_tracks_params;
+typedef struct rc_track {          /* 128 bytes; a free slot is all zero bytes */
+    int64_t id, parent, first_push;
+    int64_t area_sum, fx_sum, fy_sum, m_sum;
+    int32_t slot, label, flags, age, hits, misses;
+    int32_t area, x0, y0, x1, y1, px, py, px0, py0, overlap;
+    float mean_fx, mean_fy;
+} rc_track;
+typedef struct rc_tracks_info {
+    int w, h;
+    rc_tracks_params prm;
+    int launches_per_push;             /* RC_TRACKS_LAUNCHES */
+    long long pushes;                  /* calls since open / reset */
+    size_t device_bytes;
+} rc_tracks_info;
+/* Allocates everything the slot will ever need (the footprint: 4 bytes per pixel; the overlap table; RC_ENOMEM with the
+ * byte count in rcflow_last_error).  Re-opening replaces the state; a refused open leaves the open state as it was.
+ * RC_EINVAL: a parameter out of range, unknown flag bits, a frame of 2^31 pixels or more; RC_ESIZE beyond the context's
+ * max_w x max_h. */
+int rcflow_tracks_open(rc_ctx* ctx, int stream, int w, int h, const rc_tracks_params* prm);
+/* One set of regions.  d_labels: int32 h x w (4-byte aligned, labels_step a multiple of 4, >= 4 w); d_regions: at least
+ * max_regions records or as many as d_regions_summary[2] says (8-byte aligned); d_regions_summary: the 8 int64 of
+ * rcflow_regions_push_dev.  Every refusal is decided before anything is queued and leaves the state as it was: RC_EINVAL
+ * for a NULL input, a bad step, a pointer without the natural alignment of its element, an output whose byte range
+ * [first byte, last byte] overlaps an input's or another output's (d_regions counts as max_regions records); RC_ESTATE
+ * before open. */
+int rcflow_tracks_push_dev(rc_ctx* ctx, int stream, const int32_t* d_labels, size_t labels_step,
+                           const rc_region* d_regions, const long long* d_regions_summary,
+                           rc_track* d_tracks, int32_t* d_track_of_label, uint8_t* d_mask_out, size_t mask_out_step,
+                           long long* d_summary);
+/* 5 * max_tracks primitives from the table as the last push left it (before the first push: all kind 0) into d_prims.
+ * RC_EINVAL: thickness outside 1..RC_DRAW_MAX_THICKNESS, disc_radius outside 0..RC_DRAW_COORD_MAX. */
+int rcflow_tracks_prims_dev(rc_ctx* ctx, int stream, uint32_t color, int thickness, int disc_radius, rc_draw_prim* d_prims);
+/* Blocks until the slot's stream has finished; for hosts and tests.  The first min(cap, max_tracks) records of the table
+ * in slot order, the footprint (h * w int32, dense), the summary of the last push; any pointer may be NULL.  Before the
+ * first push: zeros. */
+int rcflow_tracks_read(rc_ctx* ctx, int stream, rc_track* tracks, int cap, int32_t* footprint /* h*w */, long long summary[8]);
+/* never blocks; RC_ESTATE when nothing is open */
+int rcflow_tracks_info(rc_ctx* ctx, int stream, rc_tracks_info* info);
+/* no track, an empty footprint, next_id 1, n 0; keeps the allocation; asynchronous, on the slot's stream */
+int rcflow_tracks_reset(rc_ctx* ctx, int stream);
+/* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
+int rcflow_tracks_close(rc_ctx* ctx, int stream);
+
 /* Display path, ripcurrents.cpp:233-273 (= streamline_displacement / _total_motion / _ratio /
  * _positions, ripcurrents_module.cpp:13-60) on the slot's streamline field (rcflow_advect_field_dev):
  * which 0 = |pt|, 1 = dist, 2 = |pt| / dist; minMaxLoc + convertTo(CV_8UC1, 255/max) +

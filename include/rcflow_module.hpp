@@ -734,11 +734,89 @@ class Regions {
     void setMinArea(int min_area) { check(rcflow_regions_set(pipe_.context(), 0, min_area)); }
     rc_regions_info info() { rc_regions_info i; check(rcflow_regions_info(pipe_.context(), 0, &i)); return i; }
     void reset() { check(rcflow_regions_reset(pipe_.context(), 0)); }
+    int maxRegions() const { return max_regions_; }
 
   private:
     Pipeline& pipe_;
     int max_regions_;
     void *d_mask_ = nullptr, *d_labels_ = nullptr, *d_prims_ = nullptr, *d_canvas_ = nullptr;
+};
+
+// Rip tracks on the device (rcflow_tracks_*): the regions of a Regions object followed from push to push, with hits, misses
+// and confirmation.  push() labels the mask with the Regions state and hands its label image, records and summary to the
+// tracks without any of them leaving the device.  Host images in, host images and records out.
+class Tracks {
+  public:
+    Tracks(Pipeline& pipe, Regions& regions, int max_tracks = 64, int min_overlap = 1, int max_misses = 2, int min_hits = 3)
+        : pipe_(pipe), max_regions_(std::min(regions.maxRegions(), RC_TRACKS_MAX_REGIONS)), rg_records_(regions.maxRegions()), max_tracks_(max_tracks) {
+        rc_tracks_params p{};
+        p.max_regions = max_regions_; p.max_tracks = max_tracks; p.min_overlap = min_overlap; p.max_misses = max_misses; p.min_hits = min_hits;
+        check(rcflow_tracks_open(pipe.context(), 0, pipe.width(), pipe.height(), &p));
+    }
+    ~Tracks() {
+        (void)rcflow_tracks_close(pipe_.context(), 0);
+        for (void* p : {d_mask_, d_labels_, d_records_, d_summary_, d_out_, d_prims_, d_canvas_}) if (p) (void)hipFree(p);
+    }
+    Tracks(const Tracks&) = delete;
+    Tracks& operator=(const Tracks&) = delete;
+
+    // mask: 8UC1 of the pipeline's size, non-zero is foreground: one regions push and one tracks push.  with_flow: the
+    // pipeline's resident flow field gives regions and tracks their flow sums.  maskOut (8UC1, optional; may be `mask`): 255
+    // inside the regions of confirmed tracks.
+    void push(const Mat& mask, bool with_flow = false, Mat* maskOut = nullptr) {
+        const int w = pipe_.width(), h = pipe_.height();
+        if (mask.empty() || mask.rows != h || mask.cols != w || mask.channels != 1 || mask.elem != 1)
+            throw Error(RC_EINVAL, "Tracks::push: the mask must be 8UC1 of the pipeline's size");
+        if (maskOut && (maskOut->empty() || maskOut->rows != h || maskOut->cols != w || maskOut->channels != 1 || maskOut->elem != 1))
+            throw Error(RC_EINVAL, "Tracks::push: maskOut must be 8UC1 of the pipeline's size");
+        if (with_flow && !pipe_.device_flow()) throw Error(RC_ESTATE, "Tracks::push: the pipeline holds no flow field");
+        if (!d_mask_) hip_check(hipMalloc(&d_mask_, (size_t)w * h), "hipMalloc mask");
+        if (!d_labels_) hip_check(hipMalloc(&d_labels_, (size_t)w * h * 4), "hipMalloc labels");
+        if (!d_records_) hip_check(hipMalloc(&d_records_, (size_t)rg_records_ * sizeof(rc_region)), "hipMalloc records");
+        if (!d_summary_) hip_check(hipMalloc(&d_summary_, 64), "hipMalloc summary");
+        if (maskOut && !d_out_) hip_check(hipMalloc(&d_out_, (size_t)w * h), "hipMalloc mask out");
+        check(rcflow_sync(pipe_.context(), 0));
+        hip_check(hipMemcpy2D(d_mask_, (size_t)w, mask.data, mask.step, (size_t)w, h, hipMemcpyHostToDevice), "upload mask");
+        check(rcflow_regions_push_dev(pipe_.context(), 0, (const uint8_t*)d_mask_, (size_t)w, with_flow ? pipe_.device_flow() : nullptr,
+                                      (size_t)w * 8, (int32_t*)d_labels_, (size_t)w * 4, nullptr, 0, (rc_region*)d_records_, (long long*)d_summary_));
+        check(rcflow_tracks_push_dev(pipe_.context(), 0, (const int32_t*)d_labels_, (size_t)w * 4, (const rc_region*)d_records_,
+                                     (const long long*)d_summary_, nullptr, nullptr, maskOut ? (uint8_t*)d_out_ : nullptr, (size_t)w, nullptr));
+        if (maskOut) {
+            check(rcflow_sync(pipe_.context(), 0));
+            hip_check(hipMemcpy2D(maskOut->data, maskOut->step, d_out_, (size_t)w, (size_t)w, h, hipMemcpyDeviceToHost), "download mask");
+        }
+    }
+    // waits for the pipeline's stream: the used slots of the table after the last push, in slot order; summary (optional):
+    // the 8 words of include/rcflow.h; footprint (optional): h * w words, slot + 1 of the track that last covered the pixel
+    std::vector<rc_track> tracks(long long* summary = nullptr, std::vector<int32_t>* footprint = nullptr) {
+        std::vector<rc_track> t((size_t)max_tracks_), usedSlots;
+        if (footprint) footprint->resize((size_t)pipe_.width() * pipe_.height());
+        check(rcflow_tracks_read(pipe_.context(), 0, t.data(), max_tracks_, footprint ? footprint->data() : nullptr, summary));
+        for (const rc_track& q : t) if (q.id) usedSlots.push_back(q);
+        return usedSlots;
+    }
+    // paints the boxes and centroids of the confirmed tracks into img (8UC3)
+    void draw(Mat& img, uint32_t color = 0x00ffff, int thickness = 1, int disc_radius = 3) {
+        const int w = pipe_.width(), h = pipe_.height();
+        if (img.empty() || img.rows != h || img.cols != w || img.channels != 3 || img.elem != 1)
+            throw Error(RC_EINVAL, "Tracks::draw: img must be 8UC3 of the pipeline's size");
+        if (!d_prims_) hip_check(hipMalloc(&d_prims_, (size_t)5 * max_tracks_ * sizeof(rc_draw_prim)), "hipMalloc prims");
+        if (!d_canvas_) hip_check(hipMalloc(&d_canvas_, (size_t)w * h * 3), "hipMalloc canvas");
+        check(rcflow_sync(pipe_.context(), 0));
+        hip_check(hipMemcpy2D(d_canvas_, (size_t)w * 3, img.data, img.step, (size_t)w * 3, h, hipMemcpyHostToDevice), "upload canvas");
+        check(rcflow_tracks_prims_dev(pipe_.context(), 0, color, thickness, disc_radius, (rc_draw_prim*)d_prims_));
+        check(rcflow_draw_dev(pipe_.context(), 0, (uint8_t*)d_canvas_, (size_t)w * 3, w, h, 3, (const rc_draw_prim*)d_prims_, 5 * max_tracks_, nullptr));
+        check(rcflow_sync(pipe_.context(), 0));
+        hip_check(hipMemcpy2D(img.data, img.step, d_canvas_, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost), "download canvas");
+    }
+    rc_tracks_info info() { rc_tracks_info i; check(rcflow_tracks_info(pipe_.context(), 0, &i)); return i; }
+    void reset() { check(rcflow_tracks_reset(pipe_.context(), 0)); }
+
+  private:
+    Pipeline& pipe_;
+    int max_regions_, rg_records_, max_tracks_;
+    void *d_mask_ = nullptr, *d_labels_ = nullptr, *d_records_ = nullptr, *d_summary_ = nullptr, *d_out_ = nullptr, *d_prims_ = nullptr,
+         *d_canvas_ = nullptr;
 };
 
 }  // namespace rc

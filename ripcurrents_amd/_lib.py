@@ -39,6 +39,9 @@ TRACERS_MOVERS = {"lk": 0, "flow": 1}
 TRACER_KINDS = {"streak": 0, "timeline": 1, "cloud": 2}
 # rcflow_regions_*: the bound on max_regions, the launches of a push
 RC_REGIONS_MAX, RC_REGIONS_LAUNCHES = 65536, 7
+# rcflow_tracks_*: the bounds on max_regions and max_tracks, the launches of a push, rc_track::flags
+RC_TRACKS_MAX_REGIONS, RC_TRACKS_MAX, RC_TRACKS_LAUNCHES = 1024, 1024, 6
+TRACK_FLAGS = {"seen": 1, "born": 2, "coasting": 4, "ended": 8, "split": 16, "merged": 32, "confirmed": 64}
 
 ERRORS = {-1: "RC_EINVAL", -2: "RC_ENOMEM", -3: "RC_EHIP", -4: "RC_ENODEV", -5: "RC_ESIZE",
           -6: "RC_ESTATE", -7: "RC_ECOMM"}
@@ -103,6 +106,27 @@ class RegionsInfo(C.Structure):
     """rc_regions_info (include/rcflow.h)."""
     _fields_ = [("w", C.c_int), ("h", C.c_int), ("connectivity", C.c_int), ("min_area", C.c_int), ("max_regions", C.c_int),
                 ("flags", C.c_int), ("launches_per_push", C.c_int), ("pushes", C.c_longlong), ("device_bytes", C.c_size_t)]
+
+
+class TracksParams(C.Structure):
+    """rc_tracks_params (include/rcflow.h)."""
+    _fields_ = [("max_regions", C.c_int), ("max_tracks", C.c_int), ("min_overlap", C.c_int), ("max_misses", C.c_int),
+                ("min_hits", C.c_int), ("flags", C.c_int)]
+
+
+class Track(C.Structure):
+    """rc_track (include/rcflow.h), 128 bytes; numpy: api.TRACK_DTYPE."""
+    _fields_ = [("id", C.c_int64), ("parent", C.c_int64), ("first_push", C.c_int64), ("area_sum", C.c_int64), ("fx_sum", C.c_int64),
+                ("fy_sum", C.c_int64), ("m_sum", C.c_int64), ("slot", C.c_int32), ("label", C.c_int32), ("flags", C.c_int32),
+                ("age", C.c_int32), ("hits", C.c_int32), ("misses", C.c_int32), ("area", C.c_int32), ("x0", C.c_int32),
+                ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32), ("px", C.c_int32), ("py", C.c_int32), ("px0", C.c_int32),
+                ("py0", C.c_int32), ("overlap", C.c_int32), ("mean_fx", C.c_float), ("mean_fy", C.c_float)]
+
+
+class TracksInfo(C.Structure):
+    """rc_tracks_info (include/rcflow.h)."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", TracksParams), ("launches_per_push", C.c_int), ("pushes", C.c_longlong),
+                ("device_bytes", C.c_size_t)]
 
 
 class FitParams(C.Structure):
@@ -247,6 +271,13 @@ SIGNATURES = {
     "rcflow_regions_reset": [_vp, _i],
     "rcflow_regions_close": [_vp, _i],
     "rcflow_regions_info": [_vp, _i, C.POINTER(RegionsInfo)],
+    "rcflow_tracks_open": [_vp, _i, _i, _i, C.POINTER(TracksParams)],
+    "rcflow_tracks_push_dev": [_vp, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    "rcflow_tracks_prims_dev": [_vp, _i, C.c_uint32, _i, _i, _vp],
+    "rcflow_tracks_read": [_vp, _i, _vp, _i, _vp, _vp],
+    "rcflow_tracks_info": [_vp, _i, C.POINTER(TracksInfo)],
+    "rcflow_tracks_reset": [_vp, _i],
+    "rcflow_tracks_close": [_vp, _i],
     "rcflow_comm_unique_id": [_vp],
     "rcflow_comm_init": [_vp, _vp, _i, _i],
     "rcflow_comm_destroy": [_vp],

@@ -31,6 +31,7 @@ from ._lib import RC_STAB_ANCHOR_FIRST, RC_STAB_MAX_PATCHES, RC_WARP_INVERSE_MAP
 from ._lib import RC_RIPMAP_WAIT_FULL, RIPMAP_SOURCES
 from ._lib import TRACERS_MOVERS, TRACER_KINDS, TracersInfo, TracersParams
 from ._lib import RegionsInfo, RegionsParams
+from ._lib import TracksInfo, TracksParams
 
 __all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState"]
 
@@ -47,6 +48,13 @@ REGION_DTYPE = np.dtype([("label", "<i4"), ("area", "<i4"), ("x0", "<i4"), ("y0"
                          ("mean_fx", "<f4"), ("mean_fy", "<f4")])
 # the eight words of a regions summary, in order
 REGIONS_SUMMARY = ("components", "kept", "records", "foreground", "kept_pixels", "bad_pixels", "pushes", "largest_area")
+# rc_track as a numpy record (128 bytes): what Context.tracks_read returns
+TRACK_DTYPE = np.dtype([("id", "<i8"), ("parent", "<i8"), ("first_push", "<i8"), ("area_sum", "<i8"), ("fx_sum", "<i8"), ("fy_sum", "<i8"),
+                        ("m_sum", "<i8"), ("slot", "<i4"), ("label", "<i4"), ("flags", "<i4"), ("age", "<i4"), ("hits", "<i4"),
+                        ("misses", "<i4"), ("area", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("px", "<i4"),
+                        ("py", "<i4"), ("px0", "<i4"), ("py0", "<i4"), ("overlap", "<i4"), ("mean_fx", "<f4"), ("mean_fy", "<f4")])
+# the eight words of a tracks summary, in order
+TRACKS_SUMMARY = ("alive", "confirmed", "born", "ended", "seen", "coasting", "untracked", "pushes")
 
 
 def _params(pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags):
@@ -1325,6 +1333,84 @@ class Context:
     def regions_close(self, stream=0):
         self._bind(stream)          # waits for the pushes queued on that stream before freeing
         check(self._lib.rcflow_regions_close(self._h, stream))
+
+    # ------------------------------------------------------------------ rip tracks
+    def tracks_open(self, w, h, max_regions=1024, max_tracks=64, min_overlap=1, max_misses=2, min_hits=3, stream=0):
+        """Opens the slot's region tracking for w x h label images: the regions of regions_push followed from push to push
+        by the overlap of their pixels with the footprint the tracks left, with hits, misses and confirmation
+        (include/rcflow.h, "rip tracks").  The footprint takes 4 bytes per pixel of device memory."""
+        p = TracksParams(max_regions=int(max_regions), max_tracks=int(max_tracks), min_overlap=int(min_overlap),
+                         max_misses=int(max_misses), min_hits=int(min_hits), flags=0)
+        self._bind(stream)          # the state is zeroed on the slot's stream: the one the pushes will run on
+        check(self._lib.rcflow_tracks_open(self._h, stream, int(w), int(h), C.byref(p)))
+
+    def tracks_info(self, stream=0):
+        """dict of rc_tracks_info, the parameters beside the rest; never blocks."""
+        info = TracksInfo()
+        check(self._lib.rcflow_tracks_info(self._h, stream, C.byref(info)))
+        d = {k: getattr(info, k) for k, _ in TracksInfo._fields_ if k != "prm"}
+        d.update({k: getattr(info.prm, k) for k, _ in TracksParams._fields_})
+        return d
+
+    def tracks_push(self, labels, regions, regions_summary, tracks=None, track_of_label=None, mask_out=None, summary=None, stream=0):
+        """One set of regions, as regions_push left it on the device: labels HxW int32 (dense pixels, rows may be padded),
+        regions the uint8 tensor of rc_region records, at least the max_regions of tracks_open (the push reads up to that
+        many, whatever the summary says), regions_summary its 8 int64.  RC_TRACKS_LAUNCHES launches, nothing is
+        synchronised.  Outputs are preallocated device tensors, each optional: tracks a contiguous uint8 tensor of
+        max_tracks * 128 bytes (rc_track records, TRACK_DTYPE), track_of_label max_regions + 1 int32, mask_out HxW uint8
+        (255 inside the regions of confirmed tracks), summary 8 int64.  The table and the summary also stay on the slot for
+        tracks_read / tracks_prims."""
+        info = self.tracks_info(stream)
+        h, w = info["h"], info["w"]
+        _check_out(labels, self.device, torch.int32, "labels", shape=(h, w), dense=True)
+        ok = _is_t(regions) and regions.is_cuda and regions.device == self.device and regions.dtype == torch.uint8 and regions.is_contiguous()
+        if not ok or regions.numel() % REGION_DTYPE.itemsize or regions.numel() < info["max_regions"] * REGION_DTYPE.itemsize:
+            raise ValueError("regions must be a contiguous uint8 tensor of at least max_regions (%d) rc_region records on %s" % (
+                info["max_regions"], self.device))
+        _check_out(regions_summary, self.device, torch.int64, "regions_summary", numel=8)
+        tp, lp, op, ostep, sp = C.c_void_p(None), C.c_void_p(None), C.c_void_p(None), 0, C.c_void_p(None)
+        if tracks is not None:
+            tp = self._ptr(_check_out(tracks, self.device, torch.uint8, "tracks", numel=info["max_tracks"] * TRACK_DTYPE.itemsize))
+        if track_of_label is not None:
+            lp = self._ptr(_check_out(track_of_label, self.device, torch.int32, "track_of_label", numel=info["max_regions"] + 1))
+        if mask_out is not None:
+            _check_out(mask_out, self.device, torch.uint8, "mask_out", shape=(h, w), dense=True)
+            op, ostep = self._ptr(mask_out), mask_out.stride(0)
+        if summary is not None:
+            sp = self._ptr(_check_out(summary, self.device, torch.int64, "summary", numel=8))
+        self._bind(stream)
+        check(self._lib.rcflow_tracks_push_dev(self._h, stream, self._ptr(labels), labels.stride(0) * 4, self._ptr(regions),
+                                               self._ptr(regions_summary), tp, lp, op, ostep, sp))
+
+    def tracks_prims(self, color=0x00ffff, thickness=1, disc_radius=3, out=None, stream=0):
+        """The table of the last push as 5 * max_tracks primitives for draw() -> a device uint8 tensor of rc_draw_prim
+        records: per confirmed track that has not ended its box (four lines) and a disc at its centroid; every other slot
+        is kind 0, which draw() skips (and counts)."""
+        n = 5 * self.tracks_info(stream)["max_tracks"]
+        if out is None:
+            out = torch.empty((n, 32), dtype=torch.uint8, device=self.device)
+        else:
+            _check_out(out, self.device, torch.uint8, "out", numel=n * 32)
+        self._bind(stream)
+        check(self._lib.rcflow_tracks_prims_dev(self._h, stream, int(color), int(thickness), int(disc_radius), self._ptr(out)))
+        return out
+
+    def tracks_read(self, stream=0):
+        """Waits for the slot's stream -> (the table as a numpy array of max_tracks TRACK_DTYPE records in slot order, the
+        footprint as an HxW int32 array, dict of the summary with the names of TRACKS_SUMMARY)."""
+        info = self.tracks_info(stream)
+        tab, foot, summ = np.zeros(info["max_tracks"], TRACK_DTYPE), np.zeros((info["h"], info["w"]), np.int32), np.zeros(8, np.int64)
+        self._bind(stream)
+        check(self._lib.rcflow_tracks_read(self._h, stream, tab.ctypes.data, len(tab), foot.ctypes.data, summ.ctypes.data))
+        return tab, foot, dict(zip(TRACKS_SUMMARY, (int(v) for v in summ)))
+
+    def tracks_reset(self, stream=0):
+        self._bind(stream)
+        check(self._lib.rcflow_tracks_reset(self._h, stream))
+
+    def tracks_close(self, stream=0):
+        self._bind(stream)          # waits for the pushes queued on that stream before freeing
+        check(self._lib.rcflow_tracks_close(self._h, stream))
 
     def _an_size(self, stream):
         w, h = C.c_int(0), C.c_int(0)

@@ -167,6 +167,20 @@ struct RcRegions {
     RcZeroFence zf;
 };
 
+// Rip tracks of one stream slot (track_kernels.hip): the regions of rcflow_regions_push_dev followed from push to push.
+// Everything is allocated by rcflow_tracks_open and released by rcflow_tracks_close / rcflow_destroy.
+struct RcTracks {
+    bool open = false;
+    int w = 0, h = 0;
+    rc_tracks_params prm{};
+    long long pushes = 0;           // calls since open / reset, for rcflow_tracks_info; the kernels count in aux
+    RcBuf foot;                     // [h * w] int32: slot + 1 of the track that last covered the pixel, or 0
+    RcBuf ov;                       // [max_regions + 1][max_tracks] int32: the overlap table, zeroed by every push
+    RcBuf aux;                      // TkCtl (next_id - 1, pushes) | the per-label and per-slot words between the launches (TkTabs)
+    RcBuf out;                      // the last push: 8 int64 summary | max_tracks rc_track, the table itself
+    RcZeroFence zf;
+};
+
 // warp_kernels.hip: one launch of the affine / perspective warp
 struct RcWarpArgs {
     const uint8_t* src; size_t step;
@@ -242,6 +256,7 @@ struct RcSlot {
     RcRipMap rm;
     RcTracers tr;
     RcRegions rg;
+    RcTracks tk;
     RcPhaseCorr pc;
 };
 
@@ -290,7 +305,9 @@ enum { RC_K_PYR = 0, RC_K_POLY = 1, RC_K_ITER = 2, RC_K_HIST = 3, RC_K_THRESH = 
        RC_K_TRACERS = 22 /* @0 book-keeping and primitives, @1 draw, @2 trace to lines */,
        RC_K_REGIONS = 23 /* @0 runs, @1 merge, @2 flatten and count, @3 row counts, @4 numbers, @5 outputs and sums, @6 records,
                             @7 primitives */,
-       RC_K_KINDS = 24 };
+       RC_K_TRACKS = 24 /* @0 prepare, @1 overlap, @2 claim, @3 winner and update, @4 births and summary, @5 paint and outputs,
+                           @6 primitives */,
+       RC_K_KINDS = 25 };
 
 void rc_set_error(const char* fmt, ...);
 int rc_buf_ensure(RcBuf& b, size_t bytes);
@@ -363,7 +380,7 @@ struct RcProfScope {
     } while (0)
 
 // ---------------------------------------------------------------------------- per-slot products
-// RcTimex, RcFrameStab, RcRipMap, RcTracers and RcRegions share one lifecycle.  A product supplies
+// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions and RcTracks share one lifecycle.  A product supplies
 //   void rc_state_free(T&)             frees every buffer and the fence; the state is T() again
 //   int rc_state_zero(RcSlot&, T&)     rc_fence_zero of what open / reset clear, and the counters
 // and open / reset / close are written once, here.
@@ -372,11 +389,13 @@ void rc_state_free(RcFrameStab& f);
 void rc_state_free(RcRipMap& m);
 void rc_state_free(RcTracers& t);
 void rc_state_free(RcRegions& g);
+void rc_state_free(RcTracks& g);
 int rc_state_zero(RcSlot& s, RcTimex& t);
 int rc_state_zero(RcSlot& s, RcFrameStab& f);
 int rc_state_zero(RcSlot& s, RcRipMap& m);
 int rc_state_zero(RcSlot& s, RcTracers& t);
 int rc_state_zero(RcSlot& s, RcRegions& g);
+int rc_state_zero(RcSlot& s, RcTracks& g);
 
 // The tail of every open.  The caller has validated, selected the device and built `fresh` (rc: what its allocations
 // returned).  The state that is open is touched only once nothing can be refused any more: a refused open leaves it as it

@@ -112,7 +112,7 @@ static const char* kKindNames[RC_K_KINDS] = {"pyr_level", "polyexp", "flow_iter"
                                              "thresholds", "classify_accumulate", "advect_field",
                                              "advect_points", "flow_postop", "flow_color", "flow_iter_x2",
                                              "frame_preproc", "create_edges", "streamline_display", "hsv_to_bgr",
-                                             "create_output", "flow_area_init", "timex", "frame_color", "framestab", "ripmap", "trackstab", "tracers", "regions"};
+                                             "create_output", "flow_area_init", "timex", "frame_color", "framestab", "ripmap", "trackstab", "tracers", "regions", "tracks"};
 // The reference's wall-clock buckets (ripcurrents.cpp:103-109, sampled at :205,223,293,314,411,483, printed at
 // :518-524) and the kernels that do each bucket's work here.  time_polar has no kernel of its own: the
 // cartToPolar of :305-309 is fused into the histogram and classification kernels; classify_accumulate spans
@@ -123,12 +123,13 @@ static const char* kKindNames[RC_K_KINDS] = {"pyr_level", "polyexp", "flow_iter"
 // frame the flow is taken from and is booked with the resize stages (frame_preproc), under "farneback".  The opposing-flow map works on the flow field as the
 // post-ops (flow_postop) do and is booked with them, under "farneback".
 // The tracer lines (book-keeping, primitives, drawing) are the reference's "pathlines" work and are booked under "stream".
-// The rip regions label and measure the mask the classification leaves and are booked with it, under "threshold".
+// The rip regions label and measure the mask the classification leaves and are booked with it, under "threshold"; the rip
+// tracks follow those regions and are booked with them.
 static const int kBucketOfKind[RC_K_KINDS] = {
     /* pyr_level */ 0, /* polyexp */ 0, /* flow_iter */ 0, /* polar_hist */ 2, /* thresholds */ 2,
     /* classify_accumulate */ 2, /* advect_field */ 6, /* advect_points */ 6, /* flow_postop */ 0, /* flow_color */ 2,
     /* flow_iter_x2 */ 0, /* frame_preproc */ 0, /* create_edges */ 4, /* streamline_display */ 6, /* hsv_to_bgr */ 2,
-    /* create_output */ 3, /* flow_area_init */ 0, /* timex */ 3, /* frame_color */ 3, /* framestab */ 0, /* ripmap */ 0, /* trackstab */ 0, /* tracers */ 6, /* regions */ 2};
+    /* create_output */ 3, /* flow_area_init */ 0, /* timex */ 3, /* frame_color */ 3, /* framestab */ 0, /* ripmap */ 0, /* trackstab */ 0, /* tracers */ 6, /* regions */ 2, /* tracks */ 2};
 static const char* kBucketNames[RC_PROFILE_BUCKETS] = {"farneback", "polar", "threshold", "overlay", "erosion", "codec", "stream"};
 static char g_names[RC_K_KINDS * RC_MAX_LEVELS][40];
 
@@ -264,6 +265,7 @@ static void slot_free(RcSlot& s) {
     rc_state_free(s.rm);
     rc_state_free(s.tr);
     rc_state_free(s.rg);
+    rc_state_free(s.tk);
     rc_buf_free(s.pc.tab); rc_buf_free(s.pc.scratch);
     rc_loop_graph_drop(s);
     for (auto& e : s.fev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
