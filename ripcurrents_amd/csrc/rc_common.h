@@ -6,10 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/rcflow.h"
-
-#define RC_MAX_LEVELS 12
-#define RC_MAX_POLY_N 32      // taps -n..n kept on device
-#define RC_MAX_WIN_M 32       // window radius winsize/2
+#include "rc_plan.h"   // RcLevel, RcPolyK, RcWindow and the RC_MAX_* bounds
 
 // Built with -ffp-contract=off: a*b+c rounds twice unless written as fmaf().
 #define RC_FMA(a, b, c) __builtin_fmaf((a), (b), (c))
@@ -48,38 +45,6 @@ __device__ __forceinline__ uint8_t rc_f2u8(float v) {
     else iv = (int)v;
     return (uint8_t)(iv & 0xFF);
 }
-
-// Geometry and constants of one pyramid scale.
-struct RcLevel {
-    int w, h;            // level size (cvRound(W*scale))
-    double scale_x;      // W0 / w   (resize.cpp scale_x)
-    double scale_y;
-    double sigma;        // pyramid blur sigma
-    int ksize;           // pyramid blur taps
-    int pyr_tw, pyr_th;  // pyr_level tile
-    int pyr_reg_w, pyr_reg_h;  // LDS source region bounds (bytes / rows)
-    size_t pyr_lds;
-};
-
-// Polynomial-expansion constants (FarnebackPrepareGaussian), taps 0..n.
-struct RcPolyK {
-    float g[RC_MAX_POLY_N + 1];
-    float xg[RC_MAX_POLY_N + 1];
-    float xxg[RC_MAX_POLY_N + 1];
-    double ig11, ig03, ig33, ig55;
-    double kdc;   // coefficient of the removed DC term in the yy/xx outputs
-    int n;        // requested radius
-    int n_eff;    // radius actually evaluated
-};
-
-// Window of FarnebackUpdateFlow_*: box (scale = 1/bs^2) or Gaussian (float taps).
-struct RcWindow {
-    float k[RC_MAX_WIN_M + 1];
-    double box_scale;
-    double box_eps;           // 1e-3 / box_scale^2: regulariser for unscaled window sums
-    int m;
-    int gaussian;
-};
 
 struct RcPyrArgs {
     const uint8_t* src;       // frame 0

@@ -200,10 +200,13 @@ struct RcPhaseCorr {
     RcBuf tab, scratch;
 };
 
-struct RcBatchKey {
-    const void* frames; size_t frame_stride, step;
-    void* flows; size_t flow_frame_stride, flow_step;
-    void* hip_stream;
+// A launch sequence captured per ring parity (rcflow_frame_loop_step, rcflow_push_batch_dev).  The first call with a key
+// issues the launches eagerly and remembers the key, the second call with the same key captures them while issuing and
+// launches the graph, later calls replay it; another key starts over (rc_graph_step in rcflow_api.hip).
+struct RcGraphCache {
+    void* exec[2] = {nullptr, nullptr};
+    int eager[2] = {0, 0};
+    unsigned char key[2][160] = {};   // everything the sequence has baked in, as bytes
 };
 
 struct RcSlot {
@@ -241,14 +244,10 @@ struct RcSlot {
     int primed = 0, cur_slot = 0;
     // lockstep batch of streams (rcflow_push_batch_dev): parity of the ring, captured graphs
     int batch_primed = 0, batch_cur = 0;
-    void* batch_exec[2] = {nullptr, nullptr};
-    int batch_eager[2] = {0, 0};
-    RcBatchKey batch_key[2] = {};
-    // rcflow_frame_loop_step: one captured launch sequence per ring parity, the configuration they were captured for,
-    // the stream's flow-field counter (host copy; the kernels read the device word an.loopc)
-    void* loop_exec[2] = {nullptr, nullptr};
-    int loop_eager[2] = {0, 0};
-    unsigned char loop_key[2][160] = {};
+    RcGraphCache batch_graph;
+    // rcflow_frame_loop_step: the captured sequences, the stream's flow-field counter (host copy; the kernels read the
+    // device word an.loopc)
+    RcGraphCache loop_graph;
     int loop_fc = 0;
     RcAnalysis an;
     RcTimex tx;
@@ -294,27 +293,63 @@ struct rc_ctx {
     std::vector<double> prof_ms, prof_bytes, prof_model_bytes;
 };
 
-enum { RC_K_PYR = 0, RC_K_POLY = 1, RC_K_ITER = 2, RC_K_HIST = 3, RC_K_THRESH = 4, RC_K_CLASSIFY = 5,
-       RC_K_ADVECT_FIELD = 6, RC_K_ADVECT_POINTS = 7, RC_K_POSTOP = 8, RC_K_COLOR = 9, RC_K_ITER2 = 10,
-       RC_K_PREPROC = 11, RC_K_EDGES = 12, RC_K_DISPLAY = 13, RC_K_HSV2BGR = 14, RC_K_OVERLAY = 15, RC_K_FLOW_SEED = 16,
-       RC_K_TIMEX = 17 /* @0 mean, @1 ring products */, RC_K_COLOR_U8 = 18 /* @0 rgb_to_hsv, @1 hsv_to_rgb, @2 resize_bgr, @3 resize_area_bgr */,
-       RC_K_FRAMESTAB = 19 /* @0 correlate in one workgroup, @1 warp, @2..6 the correlate passes as launches of their own,
-                              @7 multi-patch correlate + fit, @8 affine warp, @9 perspective warp */,
-       RC_K_RIPMAP = 20 /* @0 ring, mean, cell sums, colour and the finish, @1 mask */,
-       RC_K_TRACKSTAB = 21 /* @0 gray, @1 pyrDown, @2 Scharr, @3 PyrLK track, @4 robust fit, @5 corner cells */,
-       RC_K_TRACERS = 22 /* @0 book-keeping and primitives, @1 draw, @2 trace to lines */,
-       RC_K_REGIONS = 23 /* @0 runs, @1 merge, @2 flatten and count, @3 row counts, @4 numbers, @5 outputs and sums, @6 records,
-                            @7 primitives */,
-       RC_K_TRACKS = 24 /* @0 prepare, @1 overlap, @2 claim, @3 winner and update, @4 births and summary, @5 paint and outputs,
-                           @6 primitives */,
-       RC_K_KINDS = 25 };
+// ---------------------------------------------------------------------------- profile kinds
+// The reference's wall-clock buckets (ripcurrents.cpp:103-109, sampled at :205,223,293,314,411,483, printed at
+// :518-524) and the kernels that do each bucket's work here.  time_polar has no kernel of its own: the
+// cartToPolar of :305-309 is fused into the histogram and classification kernels; classify_accumulate spans
+// :376-439 (the reference samples time_threshold at :411, inside it) and is booked under "threshold";
+// time_codec (video decode) is host I/O outside this library.  The time-exposure images and the 8-bit colour stages
+// (main.cpp:1195-1383, pipelines the timed loop of ripcurrents.cpp does not have) produce frames for display and are
+// booked with the other display-frame kernel, under "overlay".  Frame stabilisation (main.cpp:1684-1775) prepares the
+// frame the flow is taken from and is booked with the resize stages (frame_preproc), under "farneback".  The opposing-flow map works on the flow field as the
+// post-ops (flow_postop) do and is booked with them, under "farneback".
+// The tracer lines (book-keeping, primitives, drawing) are the reference's "pathlines" work and are booked under "stream".
+// The rip regions label and measure the mask the classification leaves and are booked with it, under "threshold"; the rip
+// tracks follow those regions and are booked with them.
+#define RC_BUCKET_TABLE(X) \
+    X(RC_B_FARNEBACK, "farneback") X(RC_B_POLAR, "polar") X(RC_B_THRESHOLD, "threshold") X(RC_B_OVERLAY, "overlay") \
+    X(RC_B_EROSION, "erosion") X(RC_B_CODEC, "codec") X(RC_B_STREAM, "stream")
+// One row per kind: enum name (its id is the row's position), the text name rcflow_profile_read reports as name@level,
+// the bucket.  A new kind is a new row at the end.
+#define RC_KIND_TABLE(X) \
+    X(RC_K_PYR, "pyr_level", RC_B_FARNEBACK) \
+    X(RC_K_POLY, "polyexp", RC_B_FARNEBACK) \
+    X(RC_K_ITER, "flow_iter", RC_B_FARNEBACK) \
+    X(RC_K_HIST, "polar_hist", RC_B_THRESHOLD) \
+    X(RC_K_THRESH, "thresholds", RC_B_THRESHOLD) \
+    X(RC_K_CLASSIFY, "classify_accumulate", RC_B_THRESHOLD) \
+    X(RC_K_ADVECT_FIELD, "advect_field", RC_B_STREAM) \
+    X(RC_K_ADVECT_POINTS, "advect_points", RC_B_STREAM) \
+    X(RC_K_POSTOP, "flow_postop", RC_B_FARNEBACK) \
+    X(RC_K_COLOR, "flow_color", RC_B_THRESHOLD) \
+    X(RC_K_ITER2, "flow_iter_x2", RC_B_FARNEBACK) \
+    X(RC_K_PREPROC, "frame_preproc", RC_B_FARNEBACK) \
+    X(RC_K_EDGES, "create_edges", RC_B_EROSION) \
+    X(RC_K_DISPLAY, "streamline_display", RC_B_STREAM) \
+    X(RC_K_HSV2BGR, "hsv_to_bgr", RC_B_THRESHOLD) \
+    X(RC_K_OVERLAY, "create_output", RC_B_OVERLAY) \
+    X(RC_K_FLOW_SEED, "flow_area_init", RC_B_FARNEBACK) \
+    X(RC_K_TIMEX, "timex", RC_B_OVERLAY) /* @0 mean, @1 ring products */ \
+    X(RC_K_COLOR_U8, "frame_color", RC_B_OVERLAY) /* @0 rgb_to_hsv, @1 hsv_to_rgb, @2 resize_bgr, @3 resize_area_bgr */ \
+    X(RC_K_FRAMESTAB, "framestab", RC_B_FARNEBACK) /* @0 correlate in one workgroup, @1 warp, @2..6 the correlate passes as launches of their own,
+                                                      @7 multi-patch correlate + fit, @8 affine warp, @9 perspective warp */ \
+    X(RC_K_RIPMAP, "ripmap", RC_B_FARNEBACK) /* @0 ring, mean, cell sums, colour and the finish, @1 mask */ \
+    X(RC_K_TRACKSTAB, "trackstab", RC_B_FARNEBACK) /* @0 gray, @1 pyrDown, @2 Scharr, @3 PyrLK track, @4 robust fit, @5 corner cells */ \
+    X(RC_K_TRACERS, "tracers", RC_B_STREAM) /* @0 book-keeping and primitives, @1 draw, @2 trace to lines */ \
+    X(RC_K_REGIONS, "regions", RC_B_THRESHOLD) /* @0 runs, @1 merge, @2 flatten and count, @3 row counts, @4 numbers, @5 outputs and sums, @6 records,
+                                                  @7 primitives */ \
+    X(RC_K_TRACKS, "tracks", RC_B_THRESHOLD) /* @0 prepare, @1 overlap, @2 claim, @3 winner and update, @4 births and summary, @5 paint and outputs,
+                                                @6 primitives */
+#define RC_ROW_ID(id, ...) id,
+enum { RC_BUCKET_TABLE(RC_ROW_ID) RC_B_BUCKETS };
+enum { RC_KIND_TABLE(RC_ROW_ID) RC_K_KINDS };
+static_assert(RC_B_BUCKETS == RC_PROFILE_BUCKETS, "include/rcflow.h promises RC_PROFILE_BUCKETS buckets");
 
 void rc_set_error(const char* fmt, ...);
 int rc_buf_ensure(RcBuf& b, size_t bytes);
 void rc_buf_free(RcBuf& b);
 RcSlot* rc_slot(rc_ctx* ctx, int stream);
-void rc_batch_graph_drop(RcSlot& s);
-void rc_loop_graph_drop(RcSlot& s);
+void rc_graph_drop(RcGraphCache& g);
 // analysis_kernels.hip, for rcflow_frame_loop_step
 int rc_classify_accumulate(rc_ctx* ctx, int stream, const float* d_flow, size_t flow_step, int w, int h, int framecount,
                            float MID, float LOWER, float* d_polar, size_t polar_step, float* d_wclass, size_t wc_step,

@@ -108,29 +108,12 @@ RcProfScope::~RcProfScope() {
     ctx->prof_pending.push_back({id, e0, e1, bytes, model_bytes});
 }
 
-static const char* kKindNames[RC_K_KINDS] = {"pyr_level", "polyexp", "flow_iter", "polar_hist",
-                                             "thresholds", "classify_accumulate", "advect_field",
-                                             "advect_points", "flow_postop", "flow_color", "flow_iter_x2",
-                                             "frame_preproc", "create_edges", "streamline_display", "hsv_to_bgr",
-                                             "create_output", "flow_area_init", "timex", "frame_color", "framestab", "ripmap", "trackstab", "tracers", "regions", "tracks"};
-// The reference's wall-clock buckets (ripcurrents.cpp:103-109, sampled at :205,223,293,314,411,483, printed at
-// :518-524) and the kernels that do each bucket's work here.  time_polar has no kernel of its own: the
-// cartToPolar of :305-309 is fused into the histogram and classification kernels; classify_accumulate spans
-// :376-439 (the reference samples time_threshold at :411, inside it) and is booked under "threshold";
-// time_codec (video decode) is host I/O outside this library.  The time-exposure images and the 8-bit colour stages
-// (main.cpp:1195-1383, pipelines the timed loop of ripcurrents.cpp does not have) produce frames for display and are
-// booked with the other display-frame kernel, under "overlay".  Frame stabilisation (main.cpp:1684-1775) prepares the
-// frame the flow is taken from and is booked with the resize stages (frame_preproc), under "farneback".  The opposing-flow map works on the flow field as the
-// post-ops (flow_postop) do and is booked with them, under "farneback".
-// The tracer lines (book-keeping, primitives, drawing) are the reference's "pathlines" work and are booked under "stream".
-// The rip regions label and measure the mask the classification leaves and are booked with it, under "threshold"; the rip
-// tracks follow those regions and are booked with them.
-static const int kBucketOfKind[RC_K_KINDS] = {
-    /* pyr_level */ 0, /* polyexp */ 0, /* flow_iter */ 0, /* polar_hist */ 2, /* thresholds */ 2,
-    /* classify_accumulate */ 2, /* advect_field */ 6, /* advect_points */ 6, /* flow_postop */ 0, /* flow_color */ 2,
-    /* flow_iter_x2 */ 0, /* frame_preproc */ 0, /* create_edges */ 4, /* streamline_display */ 6, /* hsv_to_bgr */ 2,
-    /* create_output */ 3, /* flow_area_init */ 0, /* timex */ 3, /* frame_color */ 3, /* framestab */ 0, /* ripmap */ 0, /* trackstab */ 0, /* tracers */ 6, /* regions */ 2, /* tracks */ 2};
-static const char* kBucketNames[RC_PROFILE_BUCKETS] = {"farneback", "polar", "threshold", "overlay", "erosion", "codec", "stream"};
+// the tables of rc_host.h, by id
+#define RC_ROW_NAME(id, name, ...) name,
+#define RC_ROW_BUCKET(id, name, bucket) bucket,
+static const char* const kKindNames[RC_K_KINDS] = {RC_KIND_TABLE(RC_ROW_NAME)};
+static const int kBucketOfKind[RC_K_KINDS] = {RC_KIND_TABLE(RC_ROW_BUCKET)};
+static const char* const kBucketNames[RC_B_BUCKETS] = {RC_BUCKET_TABLE(RC_ROW_NAME)};
 static char g_names[RC_K_KINDS * RC_MAX_LEVELS][40];
 
 static void prof_resolve(rc_ctx* ctx) {
@@ -247,7 +230,7 @@ static void slot_free(RcSlot& s) {
         rc_buf_free(s.I[k]); rc_buf_free(s.RA[k]); rc_buf_free(s.RB[k]);
         rc_buf_free(s.FA[k]); rc_buf_free(s.FB[k]);
     }
-    rc_batch_graph_drop(s);
+    rc_graph_drop(s.batch_graph);
     rc_buf_free(s.stage_u8); rc_buf_free(s.stage_flow); rc_buf_free(s.lk); rc_buf_free(s.fit_ws); rc_buf_free(s.area_tab);
     rc_buf_free(s.seed); rc_buf_free(s.seed_tab);
     rc_buf_free(s.exM); rc_buf_free(s.exV); rc_buf_free(s.exG);
@@ -267,7 +250,7 @@ static void slot_free(RcSlot& s) {
     rc_state_free(s.rg);
     rc_state_free(s.tk);
     rc_buf_free(s.pc.tab); rc_buf_free(s.pc.scratch);
-    rc_loop_graph_drop(s);
+    rc_graph_drop(s.loop_graph);
     for (auto& e : s.fev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     for (auto& e : s.flow_done) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     if (s.own) (void)hipStreamDestroy(s.own);
@@ -334,6 +317,35 @@ extern "C" int rcflow_debug_level_flow_ptr(rc_ctx* ctx, int stream, int level, i
     return *d_flow ? RC_OK : RC_ESTATE;
 }
 
+// Diagnostics (not part of include/rcflow.h; tests/test_plan_host.py): the plan arithmetic of rc_plan.cpp and the kind table
+// of rc_host.h as the driver uses them -- pure host logic, no context, no GPU.  Taps 0..n of g, xg, xxg; ig = ig11, ig03,
+// ig33, ig55.
+extern "C" int rcflow_debug_plan_poly(int n, double sigma, int exact_taps, float* g, float* xg, float* xxg, double* ig, int* n_eff,
+                                      double* kdc) {
+    if (n < 1 || n > RC_MAX_POLY_N || !(sigma >= 0) || !g || !xg || !xxg || !ig || !n_eff || !kdc) return RC_EINVAL;
+    RcPolyK pk;
+    const int rc = rc_plan_prepare_poly(n, sigma, exact_taps, pk);
+    if (rc) return rc;
+    memcpy(g, pk.g, (n + 1) * sizeof(float));
+    memcpy(xg, pk.xg, (n + 1) * sizeof(float));
+    memcpy(xxg, pk.xxg, (n + 1) * sizeof(float));
+    ig[0] = pk.ig11; ig[1] = pk.ig03; ig[2] = pk.ig33; ig[3] = pk.ig55;
+    *n_eff = pk.n_eff;
+    *kdc = pk.kdc;
+    return RC_OK;
+}
+extern "C" int rcflow_debug_plan_pyr_kernel(int ksize, double sigma, float* taps) {
+    if (ksize < 1 || ksize > 1023 || !(sigma >= 0) || !taps) return RC_EINVAL;
+    rc_plan_gaussian_kernel(ksize, sigma, taps);
+    return RC_OK;
+}
+extern "C" int rcflow_debug_kind(int id, const char** name, const char** bucket) {
+    if (id < 0 || id >= RC_K_KINDS || !name || !bucket) return RC_EINVAL;
+    *name = kKindNames[id];
+    *bucket = kBucketNames[kBucketOfKind[id]];
+    return RC_OK;
+}
+
 extern "C" int rcflow_set_option(rc_ctx* ctx, const char* name, int value) {
     if (!ctx || !name) return RC_EINVAL;
     if (!strcmp(name, "chunk")) {
@@ -381,211 +393,19 @@ extern "C" int rcflow_set_option(rc_ctx* ctx, const char* name, int value) {
     return RC_OK;
 }
 
-// ---------------------------------------------------------------------------- plan (A7 geometry)
-static inline int cv_round(double v) { return (int)nearbyint(v); }   // round half to even
-
-static int crop_levels(int w, int h, double pyr_scale, int levels) {
-    const int min_size = 32;   // optflow.cpp calc()
-    int k;
-    double scale = 1;
-    for (k = 0; k < levels; k++) {
-        scale *= pyr_scale;
-        if (w * scale < min_size || h * scale < min_size) break;
-    }
-    return k;
-}
-
-static void level_geom(int w, int h, double pyr_scale, int k, RcLevel& L) {
-    double scale = 1;
-    for (int i = 0; i < k; i++) scale *= pyr_scale;
-    L.sigma = (1. / scale - 1) * 0.5;
-    int smooth_sz = cv_round(L.sigma * 5) | 1;
-    L.ksize = smooth_sz > 3 ? smooth_sz : 3;
-    L.w = cv_round(w * scale);
-    L.h = cv_round(h * scale);
-    L.scale_x = 1. / ((double)L.w / w);
-    L.scale_y = 1. / ((double)L.h / h);
-}
-
+// ---------------------------------------------------------------------------- plan (A7 geometry; the arithmetic is rc_plan.cpp)
 extern "C" int rcflow_level_geometry(int w, int h, double pyr_scale, int levels, int k, int* wk, int* hk) {
     if (w <= 0 || h <= 0 || !(pyr_scale > 0 && pyr_scale < 1) || levels < 0 || k < 0) return RC_EINVAL;
     RcLevel L;
-    level_geom(w, h, pyr_scale, k, L);
+    rc_plan_level_geom(w, h, pyr_scale, k, L);
     if (wk) *wk = L.w;
     if (hk) *hk = L.h;
-    return crop_levels(w, h, pyr_scale, levels);
-}
-
-// smooth.cpp getGaussianKernel(n, sigma, CV_32F)
-static void host_gaussian_kernel(int n, double sigma, float* cf) {
-    static const float tab1[] = {1.f};
-    static const float tab3[] = {0.25f, 0.5f, 0.25f};
-    static const float tab5[] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
-    static const float tab7[] = {0.03125f, 0.109375f, 0.21875f, 0.28125f, 0.21875f, 0.109375f, 0.03125f};
-    const float* fixed = nullptr;
-    if (n % 2 == 1 && n <= 7 && sigma <= 0) fixed = n == 1 ? tab1 : n == 3 ? tab3 : n == 5 ? tab5 : tab7;
-    double sx = sigma > 0 ? sigma : ((n - 1) * 0.5 - 1) * 0.3 + 0.8;
-    double scale2x = -0.5 / (sx * sx), sum = 0;
-    for (int i = 0; i < n; i++) {
-        double x = i - (n - 1) * 0.5;
-        double t = fixed ? (double)fixed[i] : exp(scale2x * x * x);
-        cf[i] = (float)t;
-        sum += cf[i];
-    }
-    sum = 1. / sum;
-    for (int i = 0; i < n; i++) cf[i] = (float)(cf[i] * sum);
-}
-
-// optflow.cpp FarnebackPrepareGaussian; the 6x6 moment matrix is inverted by Cholesky.
-static int host_prepare_poly(int n, double sigma, int exact_taps, RcPolyK& pk) {
-    if (sigma < FLT_EPSILON) sigma = n * 0.3;
-    std::vector<float> gb(2 * n + 1), xgb(2 * n + 1), xxgb(2 * n + 1);
-    float *g = gb.data() + n, *xg = xgb.data() + n, *xxg = xxgb.data() + n;
-    double s = 0.;
-    for (int x = -n; x <= n; x++) {
-        g[x] = (float)exp(-x * x / (2 * sigma * sigma));
-        s += g[x];
-    }
-    s = 1. / s;
-    for (int x = -n; x <= n; x++) {
-        g[x] = (float)(g[x] * s);
-        xg[x] = (float)(x * g[x]);
-        xxg[x] = (float)(x * x * g[x]);
-    }
-    double G[6][6] = {{0}};
-    for (int y = -n; y <= n; y++)
-        for (int x = -n; x <= n; x++) {
-            G[0][0] += g[y] * g[x];
-            G[1][1] += g[y] * g[x] * x * x;
-            G[3][3] += g[y] * g[x] * x * x * x * x;
-            G[5][5] += g[y] * g[x] * x * x * y * y;
-        }
-    G[2][2] = G[0][3] = G[0][4] = G[3][0] = G[4][0] = G[1][1];
-    G[4][4] = G[3][3];
-    G[3][4] = G[4][3] = G[5][5];
-    // invG = G.inv(DECOMP_CHOLESKY): cv::invert -> hal::Cholesky64f on the identity (core/src/matrix_decomp.cpp
-    // CholImpl<double>: 1/sqrt(pivot) on the diagonal, forward then backward substitution), restated
-    // operation for operation so that the four scalars carry upstream's bits.
-    double L[6][6], inv[6][6];
-    for (int i = 0; i < 6; i++)
-        for (int j = 0; j < 6; j++) { L[i][j] = G[i][j]; inv[i][j] = i == j ? 1. : 0.; }
-    for (int i = 0; i < 6; i++) {
-        double v;
-        int j, k;
-        for (j = 0; j < i; j++) {
-            v = L[i][j];
-            for (k = 0; k < j; k++) v -= L[i][k] * L[j][k];
-            L[i][j] = v * L[j][j];
-        }
-        v = L[i][i];
-        for (k = 0; k < j; k++) { double t = L[i][k]; v -= t * t; }
-        if (!(v >= DBL_EPSILON)) return RC_EINVAL;
-        L[i][i] = 1. / sqrt(v);
-    }
-    for (int i = 0; i < 6; i++)
-        for (int j = 0; j < 6; j++) {
-            double v = inv[i][j];
-            for (int k = 0; k < i; k++) v -= L[i][k] * inv[k][j];
-            inv[i][j] = v * L[i][i];
-        }
-    for (int i = 5; i >= 0; i--)
-        for (int j = 0; j < 6; j++) {
-            double v = inv[i][j];
-            for (int k = 5; k > i; k--) v -= L[k][i] * inv[k][j];
-            inv[i][j] = v * L[i][i];
-        }
-    pk.ig11 = inv[1][1];
-    pk.ig03 = inv[0][3];
-    pk.ig33 = inv[3][3];
-    pk.ig55 = inv[5][5];
-    pk.n = n;
-    // Taps whose combined weight cannot change any sum beyond 1e-9 of its kernel mass are
-    // dropped (poly_n = 15 with sigma = 1.2 evaluates 19 of its 31 taps; "exact_taps"
-    // keeps all of them).
-    int n_thr = n;
-    if (!exact_taps) {
-        double m0 = 0, m1 = 0, m2 = 0;
-        for (int k = 1; k <= n; k++) { m0 += g[k]; m1 += fabs(xg[k]); m2 += xxg[k]; }
-        double t0 = 0, t1 = 0, t2 = 0;
-        for (int k = n; k >= 1; k--) {
-            t0 += g[k]; t1 += fabs(xg[k]); t2 += xxg[k];
-            if (t0 > 1e-8 * (m0 + g[0]) || t1 > 1e-8 * m1 || t2 > 1e-8 * m2) break;
-            n_thr = k - 1;
-        }
-        if (n_thr < 1) n_thr = 1;
-    }
-    static const int inst[] = {3, 5, 7, 8, 9, 12, 16, 24, 32};
-    int R = 32;
-    for (int v : inst)
-        if (v >= n_thr) { R = v; break; }
-    pk.n_eff = R < n ? R : n;
-    memset(pk.g, 0, sizeof(pk.g));
-    memset(pk.xg, 0, sizeof(pk.xg));
-    memset(pk.xxg, 0, sizeof(pk.xxg));
-    double sg = 0, s2 = 0;
-    for (int k = 0; k <= pk.n_eff; k++) {
-        pk.g[k] = g[k];
-        pk.xg[k] = xg[k];
-        pk.xxg[k] = xxg[k];
-        sg += (k ? 2. : 1.) * g[k];
-        s2 += (k ? 2. : 0.) * xxg[k];
-    }
-    pk.kdc = sg * sg * pk.ig03 + sg * s2 * pk.ig33;
-    return RC_OK;
-}
-
-static void host_window(int winsize, int flags, RcWindow& win) {
-    int m = winsize / 2;
-    memset(&win, 0, sizeof(win));
-    win.m = m;
-    win.gaussian = (flags & RC_FARNEBACK_GAUSSIAN) ? 1 : 0;
-    win.box_scale = 1. / ((double)winsize * winsize);
-    win.box_eps = 1e-3 / (win.box_scale * win.box_scale);
-    double sigma = m * 0.3, s = 1;
-    win.k[0] = (float)s;
-    for (int i = 1; i <= m; i++) {
-        float t = (float)exp(-i * i / (2 * sigma * sigma));
-        win.k[i] = t;
-        s += t * 2;
-    }
-    s = 1. / s;
-    for (int i = 0; i <= m; i++) win.k[i] = (float)(win.k[i] * s);
-}
-
-static void pick_pyr_tile(RcLevel& L, int W0, int H0) {
-    // tw <= 128 and th <= 128 (the coordinate tables are filled by threads 0..127 / 128..255)
-    static const int tiles[][2] = {{64, 16}, {64, 8}, {64, 4}, {32, 8}, {16, 8}, {16, 4}, {8, 4}, {4, 4}, {2, 2}, {1, 1}};
-    int r = L.ksize / 2;
-    for (auto& t : tiles) {
-        int tw = t[0], th = t[1];
-        int rw = (int)ceil(tw * L.scale_x) + 2 * r + 4;
-        int rh = (int)ceil(th * L.scale_y) + 2 * r + 4;
-        if (rw > W0 + 2 * r + 2) rw = W0 + 2 * r + 2;
-        if (rh > H0 + 2 * r + 2) rh = H0 + 2 * r + 2;
-        int rwp = (rw + 15) & ~15;
-        size_t lds = (size_t)rh * rwp + sizeof(float) * ((size_t)rh * 2 * tw + 3 * tw + 3 * th + L.ksize);
-        if (lds <= 40 * 1024 || tw == 1) {
-            L.pyr_tw = tw; L.pyr_th = th; L.pyr_reg_w = rwp; L.pyr_reg_h = rh; L.pyr_lds = lds;
-            return;
-        }
-    }
-}
-
-static int params_valid(const rc_farneback_params* p) {
-    if (!p) return 0;
-    if (!(p->pyr_scale > 0 && p->pyr_scale < 1)) return 0;
-    if (p->levels < 0 || p->levels >= RC_MAX_LEVELS) return 0;
-    if (p->winsize < 1 || p->winsize / 2 > 24) return 0;
-    if (p->iterations < 0 || p->iterations > 1000) return 0;
-    if (p->poly_n < 1 || p->poly_n > RC_MAX_POLY_N) return 0;
-    if (!(p->poly_sigma >= 0)) return 0;
-    if (p->flags & ~(RC_FARNEBACK_GAUSSIAN | RC_FARNEBACK_USE_INITIAL_FLOW)) return 0;
-    return 1;
+    return rc_plan_crop_levels(w, h, pyr_scale, levels);
 }
 
 static int ensure_plan(rc_ctx* ctx, RcSlot& s, int w, int h, const rc_farneback_params* p, int chunk, int nslots = 0) {
     if (nslots <= 0) nslots = chunk + 1;
-    if (w <= 0 || h <= 0 || !params_valid(p)) {
+    if (w <= 0 || h <= 0 || !rc_plan_params_valid(p)) {
         rc_set_error("invalid Farneback arguments (w=%d h=%d)", w, h);
         return RC_EINVAL;
     }
@@ -608,8 +428,8 @@ static int ensure_plan(rc_ctx* ctx, RcSlot& s, int w, int h, const rc_farneback_
     if (pl.valid && pl.w == w && pl.h == h && same_prm && pl.chunk == chunk &&
         pl.nslots == nslots && pl.exact_taps == ctx->exact_taps && pl.exact == exact)
         return RC_OK;
-    rc_batch_graph_drop(s);
-    rc_loop_graph_drop(s);
+    rc_graph_drop(s.batch_graph);
+    rc_graph_drop(s.loop_graph);
     RC_HIP(hipStreamSynchronize(s.cur));
     if (s.aux) RC_HIP(hipStreamSynchronize(s.aux));
     pl.valid = false;
@@ -620,22 +440,22 @@ static int ensure_plan(rc_ctx* ctx, RcSlot& s, int w, int h, const rc_farneback_
     pl.prm.flags = p->flags;
     pl.exact_taps = ctx->exact_taps;
     pl.exact = exact;
-    int L = crop_levels(w, h, p->pyr_scale, p->levels);
+    int L = rc_plan_crop_levels(w, h, p->pyr_scale, p->levels);
     pl.nlev = L + 1;
     size_t kern_total = 0;
     for (int k = 0; k <= L; k++) {
-        level_geom(w, h, p->pyr_scale, k, pl.lv[k]);
+        rc_plan_level_geom(w, h, p->pyr_scale, k, pl.lv[k]);
         if (pl.lv[k].ksize > 1023) { rc_set_error("pyramid blur too wide"); return RC_EINVAL; }
-        pick_pyr_tile(pl.lv[k], w, h);
+        rc_plan_pick_pyr_tile(pl.lv[k], w, h);
         pl.kern_off[k] = kern_total;
         kern_total += (pl.lv[k].ksize + 3) & ~3;
     }
-    int rc = host_prepare_poly(p->poly_n, p->poly_sigma, ctx->exact_taps || exact, pl.pk);
+    int rc = rc_plan_prepare_poly(p->poly_n, p->poly_sigma, ctx->exact_taps || exact, pl.pk);
     if (rc) { rc_set_error("polynomial-expansion moment matrix is not positive definite"); return rc; }
-    host_window(p->winsize, p->flags, pl.win);
+    rc_plan_window(p->winsize, p->flags, pl.win);
 
     std::vector<float> kh(kern_total, 0.f);
-    for (int k = 0; k <= L; k++) host_gaussian_kernel(pl.lv[k].ksize, pl.lv[k].sigma > 0 ? pl.lv[k].sigma : 0., kh.data() + pl.kern_off[k]);
+    for (int k = 0; k <= L; k++) rc_plan_gaussian_kernel(pl.lv[k].ksize, pl.lv[k].sigma > 0 ? pl.lv[k].sigma : 0., kh.data() + pl.kern_off[k]);
     if ((rc = rc_buf_ensure(s.kern, kern_total * sizeof(float)))) return rc;
     RC_HIP(hipMemcpy(s.kern.p, kh.data(), kern_total * sizeof(float), hipMemcpyHostToDevice));
     for (int k = 0; k <= L; k++) {
@@ -651,9 +471,7 @@ static int ensure_plan(rc_ctx* ctx, RcSlot& s, int w, int h, const rc_farneback_
         // optflow.cpp calc(): the initial field goes through resize(INTER_AREA) to the coarsest scale and is multiplied by
         // scale = pyr_scale^L; the tables of a fractional ratio are staged here, once per plan (the stream is idle)
         if ((rc = rc_flow_area_prepare(s.seed_tab, w, h, pl.lv[L].w, pl.lv[L].h, pl.seed))) return rc;
-        double scale = 1;
-        for (int i = 0; i < L; i++) scale *= p->pyr_scale;
-        pl.seed.mul = (float)scale;
+        pl.seed.mul = (float)rc_plan_scale_pow(p->pyr_scale, L);
     }
     s.primed = 0;
     s.batch_primed = 0;
@@ -692,6 +510,23 @@ static int launch_seed(rc_ctx* ctx, RcSlot& s, int pairs, const RcSeed& seed, co
 }
 
 // ---------------------------------------------------------------------------- level driver
+// The pyramid launch of scale k (geometry L) of W0 x H0 frames: frame z goes to slot (dslot0 + z * zstep) % nslots of dst.
+static RcPyrArgs pyr_args(const rc_ctx* ctx, const RcLevel& L, int k, const uint8_t* src, size_t step, size_t frame_stride, int W0,
+                          int H0, const float* kern, float* dst, size_t dst_slot_stride, int dslot0, int nslots, int zstep) {
+    RcPyrArgs p;
+    memset(&p, 0, sizeof(p));
+    p.src = src; p.src_step = step; p.src_frame_stride = frame_stride;
+    p.W0 = W0; p.H0 = H0;
+    p.dst = dst; p.dst_slot_stride = dst_slot_stride;
+    p.dslot0 = dslot0; p.nslots = nslots; p.zstep = zstep;
+    p.w = L.w; p.h = L.h; p.scale_x = L.scale_x; p.scale_y = L.scale_y;
+    p.ksize = L.ksize; p.kern = kern;
+    p.tw = L.pyr_tw; p.th = L.pyr_th; p.reg_wp = L.pyr_reg_w; p.reg_hmax = L.pyr_reg_h;
+    p.direct = (ctx->ablate & RC_ABL_PYR_STAGED) != 0;
+    p.fixed3 = k == 0 && L.ksize == 3 && !(L.sigma > 0) && L.w == W0 && L.h == H0;
+    return p;
+}
+
 // Pyramid + polynomial expansion of `count` frames into R slots dslot0.. (A1 + A2).
 static int expand_frames(rc_ctx* ctx, RcSlot& s, const uint8_t* d_src, size_t frame_stride, size_t step,
                          int count, int dslot0, int zstep = 1) {
@@ -713,17 +548,8 @@ static int expand_frames(rc_ctx* ctx, RcSlot& s, const uint8_t* d_src, size_t fr
             continue;
         }
         q.I = (const float*)s.I[k].p; q.I_slot_stride = n;
-        RcPyrArgs& p = pa[k];
-        memset(&p, 0, sizeof(p));
-        p.src = d_src; p.src_step = step; p.src_frame_stride = frame_stride;
-        p.W0 = pl.w; p.H0 = pl.h;
-        p.dst = (float*)s.I[k].p; p.dst_slot_stride = n;
-        p.dslot0 = dslot0; p.nslots = pl.nslots; p.zstep = zstep;
-        p.w = L.w; p.h = L.h; p.scale_x = L.scale_x; p.scale_y = L.scale_y;
-        p.ksize = L.ksize; p.kern = (const float*)s.kern.p + pl.kern_off[k];
-        p.tw = L.pyr_tw; p.th = L.pyr_th; p.reg_wp = L.pyr_reg_w; p.reg_hmax = L.pyr_reg_h;
-        p.direct = (ctx->ablate & RC_ABL_PYR_STAGED) != 0;
-        p.fixed3 = k == 0 && L.ksize == 3 && !(L.sigma > 0) && L.w == pl.w && L.h == pl.h;
+        pa[k] = pyr_args(ctx, L, k, d_src, step, frame_stride, pl.w, pl.h, (const float*)s.kern.p + pl.kern_off[k],
+                         (float*)s.I[k].p, n, dslot0, pl.nslots, zstep);
     }
     auto npx = [&](int k) { return (double)pl.lv[k].w * pl.lv[k].h; };
     if (pl.exact) {
@@ -1028,15 +854,12 @@ struct RcFrameAux {
 // RC_FARNEBACK_USE_INITIAL_FLOW: d_flow is in/out.  `resident` = d_flow is the slot's own resident field (the host-frame
 // loop): it seeds the pair only while it holds the flow of the stream's previous pair (RcSlot::flow_fresh); the first
 // pair after a priming call starts from zero.
-static int push_frame_core(rc_ctx* ctx, RcSlot* s, int stream, const uint8_t* d_frame, size_t step, int w, int h,
+static int push_frame_core(rc_ctx* ctx, RcSlot* s, const uint8_t* d_frame, size_t step, int w, int h,
                            float* d_flow, size_t flow_step, const rc_farneback_params* p, bool two_streams,
                            const RcFrameAux* up, bool resident) {
-    int was_valid = s->plan.valid;
-    int rc = ensure_plan(ctx, *s, w, h, p, ctx->chunk);
+    int rc = ensure_plan(ctx, *s, w, h, p, ctx->chunk);   // a rebuilt plan drops `primed`
     if (rc) return rc;
-    if (!was_valid) s->primed = 0;
     s->batch_primed = 0;
-    (void)stream;
     auto upload_on = [&](hipStream_t st) -> int {
         if (!up) return RC_OK;
         RC_HIP(hipMemcpyAsync(up->d_dst, up->host_src, up->bytes, hipMemcpyHostToDevice, st));
@@ -1111,7 +934,7 @@ extern "C" int rcflow_push_frame_dev(rc_ctx* ctx, int stream, const uint8_t* d_f
     RC_HIP(hipSetDevice(ctx->device));
     // option "frame_overlap" = 2: the caller guarantees that d_frame is complete when the call is made (a resident clip, a
     // producer it has synchronised) -- only then may the expansion start without waiting for the slot's stream
-    return push_frame_core(ctx, s, stream, d_frame, step, w, h, d_flow, flow_step, p, ctx->frame_overlap >= 2, nullptr, false);
+    return push_frame_core(ctx, s, d_frame, step, w, h, d_flow, flow_step, p, ctx->frame_overlap >= 2, nullptr, false);
 }
 
 // The reference's frame loop with HOST frames (ripcurrents.cpp:198-221: video.read -> resize -> cvtColor ->
@@ -1147,14 +970,14 @@ static int frame_staging_next(rc_ctx* ctx, RcSlot* s, int w, int h, int* idx) {
 }
 
 // Upload of staging buffer i (dense w x h bytes) + one step of the frame loop
-static int push_staged_frame(rc_ctx* ctx, RcSlot* s, int stream, int i, int w, int h, const rc_farneback_params* p) {
+static int push_staged_frame(rc_ctx* ctx, RcSlot* s, int i, int w, int h, const rc_farneback_params* p) {
     const size_t fb = (size_t)w * h;
     uint8_t* d_frame = (uint8_t*)s->stage_u8.p + (size_t)i * fb;
     s->pin_i = i ^ 1;
     s->pin_acq = -1;
     // the upload belongs to the expansion's side of the two-stream frame loop (option "frame_overlap" >= 1)
     RcFrameAux up = {s->pin[i], d_frame, fb, s->pin_free[i]};
-    const int rc = push_frame_core(ctx, s, stream, d_frame, w, w, h, (float*)s->stage_flow.p, (size_t)w * 8, p, ctx->frame_overlap >= 1, &up, true);
+    const int rc = push_frame_core(ctx, s, d_frame, w, w, h, (float*)s->stage_flow.p, (size_t)w * 8, p, ctx->frame_overlap >= 1, &up, true);
     if (rc == RC_OK) { s->flow_w = w; s->flow_h = h; s->flow_fresh = 1; }
     else if (rc == 1) { s->flow_w = s->flow_h = 0; }
     return rc;
@@ -1169,7 +992,7 @@ extern "C" int rcflow_push_frame_u8(rc_ctx* ctx, int stream, const uint8_t* fram
     uint8_t* dst = (uint8_t*)s->pin[i];
     if (step == (size_t)w) memcpy(dst, frame, (size_t)w * h);
     else for (int y = 0; y < h; y++) memcpy(dst + (size_t)y * w, frame + (size_t)y * step, w);
-    return push_staged_frame(ctx, s, stream, i, w, h, p);
+    return push_staged_frame(ctx, s, i, w, h, p);
 }
 
 // The same loop without the copy: the host produces the frame INTO the staging buffer (e.g. as the destination of the
@@ -1189,7 +1012,7 @@ extern "C" int rcflow_push_frame_acquired(rc_ctx* ctx, int stream, const rc_farn
     if (!s) return RC_EINVAL;
     if (s->pin_acq < 0 || s->pin_acq != s->pin_i) { rc_set_error("no frame buffer acquired (rcflow_frame_buffer_acquire) since the last push"); return RC_ESTATE; }
     RC_HIP(hipSetDevice(ctx->device));
-    return push_staged_frame(ctx, s, stream, s->pin_acq, s->pin_w, s->pin_h, p);
+    return push_staged_frame(ctx, s, s->pin_acq, s->pin_w, s->pin_h, p);
 }
 
 // Device address of the flow field the last rcflow_push_frame_u8 produced (w x h float2, dense rows), for the
@@ -1357,15 +1180,59 @@ extern "C" int rcflow_farneback_clip_dev(rc_ctx* ctx, int stream, const uint8_t*
     return rc;
 }
 
-// ---------------------------------------------------------------------------- the whole frame loop, one launch per frame
-void rc_loop_graph_drop(RcSlot& s) {
+// ---------------------------------------------------------------------------- captured launch sequences
+void rc_graph_drop(RcGraphCache& g) {
     for (int i = 0; i < 2; i++) {
-        if (s.loop_exec[i]) (void)hipGraphExecDestroy((hipGraphExec_t)s.loop_exec[i]);
-        s.loop_exec[i] = nullptr;
-        s.loop_eager[i] = 0;
+        if (g.exec[i]) (void)hipGraphExecDestroy((hipGraphExec_t)g.exec[i]);
+        g.exec[i] = nullptr;
+        g.eager[i] = 0;
     }
 }
 
+// what the next rc_graph_step with these arguments does
+enum { RC_GRAPH_EAGER, RC_GRAPH_CAPTURE, RC_GRAPH_REPLAY };
+static int graph_state(const RcGraphCache& g, int parity, const void* key, size_t key_bytes, bool allowed) {
+    if (!allowed || memcmp(key, g.key[parity], key_bytes)) return RC_GRAPH_EAGER;
+    return g.exec[parity] ? RC_GRAPH_REPLAY : g.eager[parity] ? RC_GRAPH_CAPTURE : RC_GRAPH_EAGER;
+}
+
+// One call's launches of ring parity `parity`: issue(stream) queues them on a stream.  A first call with `key`, and any call
+// for which graphs are not `allowed`, issues them on `run`; the second call with the same key captures them on `cap` while
+// issuing (capture executes nothing), instantiates and launches the graph on `run`; later calls replay it there.  The
+// captured sequence is one linear chain on one stream.
+template <class Key, class Issue>
+static int rc_graph_step(RcGraphCache& g, int parity, const Key& key, bool allowed, hipStream_t cap, hipStream_t run, Issue issue) {
+    static_assert(sizeof(Key) <= sizeof(g.key[0]), "RcGraphCache::key too small");
+    int rc;
+    switch (graph_state(g, parity, &key, sizeof(key), allowed)) {
+    case RC_GRAPH_REPLAY:
+        RC_HIP(hipGraphLaunch((hipGraphExec_t)g.exec[parity], run));
+        return RC_OK;
+    case RC_GRAPH_CAPTURE: {
+        hipGraph_t graph = nullptr;
+        RC_HIP(hipStreamBeginCapture(cap, hipStreamCaptureModeRelaxed));
+        rc = issue(cap);
+        hipError_t e = hipStreamEndCapture(cap, &graph);
+        if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+        if (e != hipSuccess || !graph) { rc_set_error("hipStreamEndCapture failed: %s", hipGetErrorString(e)); return RC_EHIP; }
+        hipGraphExec_t exec = nullptr;
+        e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(graph);
+        if (e != hipSuccess) { rc_set_error("hipGraphInstantiate failed: %s", hipGetErrorString(e)); return RC_EHIP; }
+        g.exec[parity] = exec;                                // (none to replace: with an exec this state is RC_GRAPH_REPLAY)
+        RC_HIP(hipGraphLaunch(exec, run));
+        return RC_OK;
+    }
+    default:
+        if (g.exec[parity]) { (void)hipGraphExecDestroy((hipGraphExec_t)g.exec[parity]); g.exec[parity] = nullptr; }
+        if ((rc = issue(run))) return rc;
+        memcpy(g.key[parity], &key, sizeof(key));
+        g.eager[parity] = 1;
+        return RC_OK;
+    }
+}
+
+// ---------------------------------------------------------------------------- the whole frame loop, one launch per frame
 struct RcLoopKey {          // everything a captured launch sequence has baked in
     rc_frame_loop loop;
     int w, h, pin, ring, ablate, chain;
@@ -1373,7 +1240,6 @@ struct RcLoopKey {          // everything a captured launch sequence has baked i
     void* hip_stream;
     void* d_frame; void* pin_host; void* d_flow;
 };
-static_assert(sizeof(RcLoopKey) <= sizeof(((RcSlot*)nullptr)->loop_key[0]), "RcSlot::loop_key too small");
 
 // the analysis chain of one frame on the resident flow field (ripcurrents.cpp:229-479), on s.cur
 static int loop_analysis(rc_ctx* ctx, RcSlot& s, int stream, const rc_frame_loop& L, int w, int h) {
@@ -1407,8 +1273,6 @@ static int loop_launches(rc_ctx* ctx, RcSlot& s, int stream, const rc_frame_loop
     return loop_analysis(ctx, s, stream, L, w, h);
 }
 
-static int push_staged_frame(rc_ctx* ctx, RcSlot* s, int stream, int i, int w, int h, const rc_farneback_params* p);
-
 extern "C" int rcflow_frame_loop_step(rc_ctx* ctx, int stream, const rc_farneback_params* p, const rc_frame_loop* loop) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s || !p || !loop) { if (s) rc_set_error("null argument"); return RC_EINVAL; }
@@ -1428,7 +1292,7 @@ extern "C" int rcflow_frame_loop_step(rc_ctx* ctx, int stream, const rc_farnebac
         // and analysis kernels, which the slot's stream may still be executing) followed by the analysis launches --
         // measured faster than one linear captured sequence per frame, which cannot overlap across frames
         if ((rc = rc_analysis_ensure(ctx, *s, w, h))) return rc;
-        rc = push_staged_frame(ctx, s, stream, pin, w, h, p);
+        rc = push_staged_frame(ctx, s, pin, w, h, p);
         if (rc < 0) return rc;
         if (rc == 1) {
             s->loop_fc = 0;
@@ -1439,15 +1303,13 @@ extern "C" int rcflow_frame_loop_step(rc_ctx* ctx, int stream, const rc_farnebac
         s->loop_fc++;
         return RC_OK;
     }
-    const bool was_valid = s->plan.valid;
     rc = ensure_plan(ctx, *s, w, h, p, 1, 2);                // a ring of two expansions: the captured sequences alternate
     if (rc) return rc;
-    if (!was_valid) s->primed = 0;
     s->batch_primed = 0;
     if ((rc = rc_analysis_ensure(ctx, *s, w, h))) return rc;
     const size_t fb = (size_t)w * h;
     if (!s->primed) {
-        rc_loop_graph_drop(*s);
+        rc_graph_drop(s->loop_graph);
         uint8_t* d_frame = (uint8_t*)s->stage_u8.p + (size_t)pin * fb;
         RC_HIP(hipMemcpyAsync(d_frame, s->pin[pin], fb, hipMemcpyHostToDevice, s->cur));
         RC_HIP(hipEventRecord(s->pin_free[pin], s->cur));
@@ -1470,34 +1332,14 @@ extern "C" int rcflow_frame_loop_step(rc_ctx* ctx, int stream, const rc_farnebac
     key.seeded = seeded;
     key.hip_stream = (void*)s->cur;
     key.d_frame = (uint8_t*)s->stage_u8.p + (size_t)pin * fb; key.pin_host = s->pin[pin]; key.d_flow = s->stage_flow.p;
-    const bool graph_ok = !ctx->prof_on && s->cur != nullptr;
-    const bool same = !memcmp(&key, s->loop_key[cur], sizeof(key));
-    if (graph_ok && s->loop_exec[cur] && same) {
-        // steady state: one launch replays the frame's whole sequence; what the eager calls book on the host is booked here
-        if ((rc = rc_hist_book(*s, w, h, true))) return rc;
-        RC_HIP(hipGraphLaunch((hipGraphExec_t)s->loop_exec[cur], s->cur));
-        s->ts_streak = 0;
-    } else if (graph_ok && s->loop_eager[cur] && same) {
-        // second frame of this parity with the same configuration: capture the sequence while issuing it, then launch it
-        if ((rc = rc_hist_book(*s, w, h, false))) return rc;
-        hipGraph_t graph = nullptr;
-        RC_HIP(hipStreamBeginCapture(s->cur, hipStreamCaptureModeRelaxed));
-        rc = loop_launches(ctx, *s, stream, *loop, pin, w, h, seeded);
-        hipError_t e = hipStreamEndCapture(s->cur, &graph);
-        if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        if (e != hipSuccess || !graph) { rc_set_error("hipStreamEndCapture failed: %s", hipGetErrorString(e)); return RC_EHIP; }
-        hipGraphExec_t exec = nullptr;
-        e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (e != hipSuccess) { rc_set_error("hipGraphInstantiate failed: %s", hipGetErrorString(e)); return RC_EHIP; }
-        s->loop_exec[cur] = exec;
-        RC_HIP(hipGraphLaunch(exec, s->cur));
-    } else {
-        if (s->loop_exec[cur]) { (void)hipGraphExecDestroy((hipGraphExec_t)s->loop_exec[cur]); s->loop_exec[cur] = nullptr; }
-        if ((rc = loop_launches(ctx, *s, stream, *loop, pin, w, h, seeded))) return rc;
-        memcpy(s->loop_key[cur], &key, sizeof(key));
-        s->loop_eager[cur] = 1;
-    }
+    const bool graph_ok = !ctx->prof_on && s->cur != nullptr;   // (the null stream cannot capture: eager there)
+    // what the eager calls book on the host is booked here for a replay, and checked before a capture (whose calls book)
+    const int state = graph_state(s->loop_graph, cur, &key, sizeof(key), graph_ok);
+    if (state != RC_GRAPH_EAGER && (rc = rc_hist_book(*s, w, h, state == RC_GRAPH_REPLAY))) return rc;
+    if ((rc = rc_graph_step(s->loop_graph, cur, key, graph_ok, s->cur, s->cur,
+                            [&](hipStream_t) { return loop_launches(ctx, *s, stream, *loop, pin, w, h, seeded); })))
+        return rc;
+    if (state == RC_GRAPH_REPLAY) s->ts_streak = 0;
     RC_HIP(hipEventRecord(s->pin_free[pin], s->cur));        // (behind the whole frame: the staging buffer comes round two frames later)
     s->cur_slot = cur ^ 1;
     s->pin_i = pin ^ 1; s->pin_acq = -1;
@@ -1508,13 +1350,11 @@ extern "C" int rcflow_frame_loop_step(rc_ctx* ctx, int stream, const rc_farnebac
 }
 
 // ---------------------------------------------------------------------------- lockstep batch of streams
-void rc_batch_graph_drop(RcSlot& s) {
-    for (int i = 0; i < 2; i++) {
-        if (s.batch_exec[i]) (void)hipGraphExecDestroy((hipGraphExec_t)s.batch_exec[i]);
-        s.batch_exec[i] = nullptr;
-        s.batch_eager[i] = 0;
-    }
-}
+struct RcBatchKey {         // everything a captured launch sequence has baked in
+    const void* frames; size_t frame_stride, step;
+    void* flows; size_t flow_frame_stride, flow_step;
+    void* hip_stream;
+};
 
 static int batch_launches(rc_ctx* ctx, RcSlot& s, const uint8_t* d_frames, size_t frame_stride, size_t step, int S,
                           float* d_flows, size_t flow_frame_stride, size_t flow_step, int cur) {
@@ -1541,7 +1381,7 @@ extern "C" int rcflow_push_batch_dev(rc_ctx* ctx, int stream, const uint8_t* d_f
     if (rc) return rc;
     s->primed = 0;
     if (!s->batch_primed) {
-        rc_batch_graph_drop(*s);
+        rc_graph_drop(s->batch_graph);
         if ((rc = expand_frames(ctx, *s, d_frames, frame_stride, step, nstreams, 0, 2))) return rc;
         s->batch_primed = 1;
         s->batch_cur = 0;
@@ -1554,38 +1394,16 @@ extern "C" int rcflow_push_batch_dev(rc_ctx* ctx, int stream, const uint8_t* d_f
     }
     if ((p->flags & RC_FARNEBACK_USE_INITIAL_FLOW) && !seed_layout_ok(d_flows, flow_step, nstreams > 1 ? flow_frame_stride : 0)) return RC_EINVAL;
     const int cur = s->batch_cur;
-    RcBatchKey key = {d_frames, frame_stride, step, d_flows, flow_frame_stride, flow_step, (void*)s->cur};
-    const bool graph_ok = use_graph && !ctx->prof_on;
-    if (graph_ok && s->batch_exec[cur] && !memcmp(&key, &s->batch_key[cur], sizeof(key))) {
-        // steady state: replay the captured launch sequence of this parity
-        RC_HIP(hipGraphLaunch((hipGraphExec_t)s->batch_exec[cur], s->cur));
-    } else if (graph_ok && s->batch_eager[cur] && !memcmp(&key, &s->batch_key[cur], sizeof(key))) {
-        // second time with the same buffers: capture while launching
-        // the null stream cannot capture: record on the slot's own stream (capture executes
-        // nothing) and launch the instantiated graph on the caller's stream
-        hipGraph_t graph = nullptr;
-        hipStream_t run_stream = s->cur, cap_stream = s->cur ? s->cur : s->own;
-        RC_HIP(hipStreamBeginCapture(cap_stream, hipStreamCaptureModeRelaxed));
-        s->cur = cap_stream;
-        rc = batch_launches(ctx, *s, d_frames, frame_stride, step, nstreams, d_flows, flow_frame_stride, flow_step, cur);
+    const RcBatchKey key = {d_frames, frame_stride, step, d_flows, flow_frame_stride, flow_step, (void*)s->cur};
+    // the null stream cannot capture: the sequence is recorded on the slot's own stream and the graph launched on the caller's
+    hipStream_t run_stream = s->cur, cap_stream = s->cur ? s->cur : s->own;
+    rc = rc_graph_step(s->batch_graph, cur, key, use_graph && !ctx->prof_on, cap_stream, run_stream, [&](hipStream_t st) {
+        s->cur = st;
+        const int r = batch_launches(ctx, *s, d_frames, frame_stride, step, nstreams, d_flows, flow_frame_stride, flow_step, cur);
         s->cur = run_stream;
-        hipError_t e = hipStreamEndCapture(cap_stream, &graph);
-        if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        if (e != hipSuccess || !graph) { rc_set_error("hipStreamEndCapture failed: %s", hipGetErrorString(e)); return RC_EHIP; }
-        hipGraphExec_t exec = nullptr;
-        e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (e != hipSuccess) { rc_set_error("hipGraphInstantiate failed: %s", hipGetErrorString(e)); return RC_EHIP; }
-        if (s->batch_exec[cur]) (void)hipGraphExecDestroy((hipGraphExec_t)s->batch_exec[cur]);
-        s->batch_exec[cur] = exec;
-        RC_HIP(hipGraphLaunch(exec, s->cur));
-    } else {
-        if (s->batch_exec[cur]) { (void)hipGraphExecDestroy((hipGraphExec_t)s->batch_exec[cur]); s->batch_exec[cur] = nullptr; }
-        if ((rc = batch_launches(ctx, *s, d_frames, frame_stride, step, nstreams, d_flows, flow_frame_stride, flow_step, cur)))
-            return rc;
-        s->batch_key[cur] = key;
-        s->batch_eager[cur] = 1;
-    }
+        return r;
+    });
+    if (rc) return rc;
     s->batch_cur = cur ^ 1;
     return RC_OK;
 }
@@ -1594,7 +1412,7 @@ extern "C" int rcflow_batch_reset(rc_ctx* ctx, int stream) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
     RC_HIP(hipStreamSynchronize(s->cur));
-    rc_batch_graph_drop(*s);
+    rc_graph_drop(s->batch_graph);
     s->batch_primed = 0;
     s->batch_cur = 0;
     return RC_OK;
@@ -1607,22 +1425,15 @@ extern "C" int rcflow_stage_pyr_level_dev(rc_ctx* ctx, int stream, const uint8_t
     if (!s || !d_img || !d_out || k < 0 || k >= RC_MAX_LEVELS || !(pyr_scale > 0 && pyr_scale < 1)) return RC_EINVAL;
     RC_HIP(hipSetDevice(ctx->device));
     RcLevel L;
-    level_geom(w, h, pyr_scale, k, L);
-    pick_pyr_tile(L, w, h);
+    rc_plan_level_geom(w, h, pyr_scale, k, L);
+    rc_plan_pick_pyr_tile(L, w, h);
     std::vector<float> kh(L.ksize);
-    host_gaussian_kernel(L.ksize, L.sigma > 0 ? L.sigma : 0., kh.data());
+    rc_plan_gaussian_kernel(L.ksize, L.sigma > 0 ? L.sigma : 0., kh.data());
     int rc = rc_buf_ensure(s->stage_f32[0], kh.size() * sizeof(float));
     if (rc) return rc;
     RC_HIP(hipMemcpyAsync(s->stage_f32[0].p, kh.data(), kh.size() * sizeof(float), hipMemcpyHostToDevice, s->cur));
     RC_HIP(hipStreamSynchronize(s->cur));
-    RcPyrArgs pa;
-    pa.src = d_img; pa.src_step = step; pa.src_frame_stride = 0; pa.W0 = w; pa.H0 = h;
-    pa.dst = d_out; pa.dst_slot_stride = 0; pa.dslot0 = 0; pa.nslots = 1; pa.zstep = 1;
-    pa.w = L.w; pa.h = L.h; pa.scale_x = L.scale_x; pa.scale_y = L.scale_y;
-    pa.ksize = L.ksize; pa.kern = (const float*)s->stage_f32[0].p;
-    pa.tw = L.pyr_tw; pa.th = L.pyr_th; pa.reg_wp = L.pyr_reg_w; pa.reg_hmax = L.pyr_reg_h;
-    pa.direct = (ctx->ablate & RC_ABL_PYR_STAGED) != 0;
-    pa.fixed3 = k == 0 && L.ksize == 3 && !(L.sigma > 0) && L.w == w && L.h == h;
+    const RcPyrArgs pa = pyr_args(ctx, L, k, d_img, step, 0, w, h, (const float*)s->stage_f32[0].p, d_out, 0, 0, 1, 1);
     rc_launch_pyr(pa, 1, L.pyr_lds, s->cur);
     RC_HIP(hipGetLastError());
     return RC_OK;
@@ -1642,7 +1453,7 @@ extern "C" int rcflow_stage_polyexp_dev(rc_ctx* ctx, int stream, const float* d_
     qa.I = d_I; qa.I_slot_stride = 0;
     qa.RA = (float4*)s->stage_f32[0].p; qa.RB = (float*)s->stage_f32[1].p; qa.R_slot_stride = 0;
     qa.slot0 = 0; qa.nslots = 1; qa.zstep = 1; qa.w = w; qa.h = h; qa.tile_h = ctx->poly_tile_h; qa.valu_vertical = !ctx->poly_mfma;
-    if ((rc = host_prepare_poly(poly_n, poly_sigma, ctx->exact_taps || ctx->exact == 1, qa.pk))) return rc;
+    if ((rc = rc_plan_prepare_poly(poly_n, poly_sigma, ctx->exact_taps || ctx->exact == 1, qa.pk))) return rc;
     if (ctx->exact == 1) rc_launch_exact_polyexp(qa, 1, s->cur);
     else rc_launch_polyexp(qa, 1, s->cur);
     rc_launch_unpack_R5(qa.RA, qa.RB, d_R5, (int)n, s->cur);
@@ -1667,7 +1478,7 @@ extern "C" int rcflow_stage_flow_iter_dev(rc_ctx* ctx, int stream, const float* 
     rc_launch_pack_R5(d_R0, RA, RB, (int)n, s->cur);
     rc_launch_pack_R5(d_R1, RA + n, RB + n, (int)n, s->cur);
     RcWindow win;
-    host_window(winsize, flags, win);
+    rc_plan_window(winsize, flags, win);
     if (ctx->exact == 1) {
         if ((rc = rc_buf_ensure(s->exM, n * 5 * sizeof(float)))) return rc;
         if ((rc = rc_buf_ensure(s->exV, (size_t)w * ((h + 15) & ~15) * 5 * sizeof(double)))) return rc;
@@ -1710,16 +1521,14 @@ extern "C" int rcflow_stage_initial_flow_dev(rc_ctx* ctx, int stream, const floa
     }
     if (!seed_layout_ok(d_flow_xy, flow_step, 0)) return RC_EINVAL;
     RC_HIP(hipSetDevice(ctx->device));
-    const int L = crop_levels(w, h, pyr_scale, levels);
+    const int L = rc_plan_crop_levels(w, h, pyr_scale, levels);
     RcLevel lv;
-    level_geom(w, h, pyr_scale, L, lv);
+    rc_plan_level_geom(w, h, pyr_scale, L, lv);
     RC_HIP(hipStreamSynchronize(s->cur));      // a previous launch may still read the tables
     RcFlowAreaArgs a;
     int rc = rc_flow_area_prepare(s->stage_f32[3], w, h, lv.w, lv.h, a);
     if (rc) return rc;
-    double scale = 1;
-    for (int i = 0; i < L; i++) scale *= pyr_scale;
-    a.mul = (float)scale;
+    a.mul = (float)rc_plan_scale_pow(pyr_scale, L);
     a.src = (const char*)d_flow_xy; a.src_step = flow_step; a.src_pair_stride = 0;
     a.dst = (float2*)d_out; a.dst_pair_stride = (size_t)lv.w * lv.h;
     {
