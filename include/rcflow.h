@@ -1033,6 +1033,113 @@ int rcflow_tracks_reset(rc_ctx* ctx, int stream);
 /* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
 int rcflow_tracks_close(rc_ctx* ctx, int stream);
 
+/* ------------------------------------------------------------------ motion templates: history, gradient, wave direction
+ * globalOrientation (ripcurrents.hpp, ripcurrents_module.cpp:319-359): where the waves are going, taken from frame
+ * differences alone, with no flow field: the second opinion beside the direction rcflow_ripmap_* sums from the flow.  It is
+ * the reference's one use of OpenCV's motion templates (motempl::updateMotionHistory, calcMotionGradient,
+ * calcGlobalOrientation); the arithmetic below restates optflow/src/motempl.cpp and is not pinned to an OpenCV build
+ * (DESIGN 7i lists the constants to re-verify).  The history lives on the device from push to push.  A push is THREE
+ * launches ("motion@0" .. "motion@2") with no host synchronisation and no device-to-host copy; rcflow_motion_prims_dev is
+ * one more ("motion@3").  All fp32 unless stated, each operation rounded on its own (no fused multiply-add).
+ *
+ *  1. Update ("motion@0").  ts = (float)timestamp, delbound = (float)(timestamp - duration) (the difference in double).
+ *       s   = |cur - prev| > diff_threshold, in integers: the absdiff + threshold(THRESH_BINARY) of :321-323;
+ *       mhi = s ? ts : (mhi < delbound ? 0 : mhi);      prev = cur, kept by the library.
+ *     The first push after open / reset has no previous frame: its silhouette is empty and the outputs are those of the
+ *     history as it stands (zeros).
+ *  2. Gradient ("motion@1"), aperture 3, replicate border, p = mhi, indices [row][col]:
+ *       dx = (p[-1][+1] - p[-1][-1]) + 2 * (p[0][+1] - p[0][-1]) + (p[+1][+1] - p[+1][-1])   in this order of operations,
+ *       dy likewise with rows and columns exchanged;
+ *       orient = fastAtan2(dy, dx) in degrees (OpenCV's polynomial; 360.0f occurs);
+ *       mask = !(|dx| < eps && |dy| < eps), eps = 1e-4f * 9;
+ *       mn, mx = minimum and maximum of the 3 x 3 neighbourhood (erode / dilate, one iteration), d0 = mx - mn:
+ *       mask = 0 where d0 < (float)delta1 or (float)delta2 < d0;  orient = 0 wherever mask == 0.
+ *  3. Orientation of a set of pixels: every grid cell, and the whole frame.  Cell of pixel (x, y) as rcflow_ripmap_*:
+ *     (min(x / (w / grid_x), grid_x - 1), likewise y).
+ *       histogram  12 bins over the set's masked pixels, idx = floor((double)orient * (12.0 / 360.0)); a pixel whose idx is
+ *                  outside 0..11 (orient == 360.0f) is masked but not counted.  peak_bin = the fullest bin, the lowest on a
+ *                  tie; base = (float)(peak_bin * 30);
+ *       tsmax      the maximum mhi over the set's masked pixels, 0 for none;
+ *       a = (float)(254. / 255. / duration);  b = (float)(1. - (double)tsmax * (double)a);
+ *       del = (float)((double)tsmax - duration);
+ *       per pixel with mask && mhi > del:  wgt = mhi * a + b;  rel = orient - base;  rel += rel < -180 ? 360 : 0;  then
+ *                  rel += rel > 180 ? -360 : 0;  if |rel| < 45:  t = wgt * rel,
+ *                  S += (int64)rint((double)t * 2^32),  W += (int64)rint((double)wgt * 2^32),  n_used += 1;
+ *       angle = (double)base + (W ? (double)S / (double)W : 0), - 360 when >= 360, + 360 when < 0.
+ *     S and W are integer sums and do not depend on the order of addition (upstream adds floats in raster order, which no
+ *     parallel sum reproduces); |t| < 46 and at most 2^24 pixels keep |S| < 2^62.  The quantisation moves the angle by at
+ *     most 46 * 2^-33 * 255 = 1.4e-6 degrees, every weight being above 1 / 255.
+ *  4. Picture (d_vis, 8UC3): v = mhi > delbound ? (mhi - delbound) / (float)duration : 0; byte = rint(v * 255) (half to
+ *     even) saturated to 0..255, in all three channels.
+ *  5. Primitives.  rcflow_motion_prims_dev turns the records of the last push into 2 * (cells + 1) primitives for
+ *     rcflow_draw_dev: per cell, in row order, a disc at the cell's centre (px, py) = ((first column + last column) / 2,
+ *     likewise rows) and a line of `thickness` from there to (px + (int32)rint(length * cos(angle)), py + (int32)rint(length
+ *     * sin(angle))), the angle in radians as angle * (pi / 180) in double, y DOWN; the frame's pair comes last, at
+ *     ((w - 1) / 2, (h - 1) / 2).  cos and sin are the device's, in double: a line's far end is good to one pixel.  A set
+ *     with W == 0 gives two all-zero records (kind 0), which rcflow_draw_dev skips AND COUNTS in d_skipped.  No arrowheads.
+ *
+ * RC_MOTION_FRESH: the reference's literal call (:321-333): the history is zeroed before every update, the stamp is 1 and
+ * the duration is 1 whatever the parameters and the timestamp say (the timestamp is still checked).  The history is then
+ * the silhouette as 0.0 / 1.0 (the reference's "min-max normalised" image) and the picture 0 / 255 (its hist_gray).
+ * Deviations from the reference: an empty silhouette gives an all-zero history, an empty mask and angle 0 (it divides 0 by
+ * 0 there); its read of the float orientation image as double (:352) is not reproduced. */
+#define RC_MOTION_FRESH 1          /* flags bit 0 */
+#define RC_MOTION_AUTO_TIME (-1.0) /* timestamp: pushes since open / reset + 1 */
+#define RC_MOTION_LAUNCHES 3       /* per push, whatever is asked for */
+#define RC_MOTION_MAX_PIXELS (1 << 24)
+typedef struct rc_motion_params {
+    int diff_threshold;     /* 0..255; the reference: 30 */
+    double duration;        /* finite, > 0; the reference: 1 */
+    double delta1, delta2;  /* finite, > 0; swapped when delta1 > delta2; the reference: 0.25, 1 */
+    int grid_x, grid_y;     /* >= 1, <= w, h, at most RC_RIPMAP_MAX_CELLS cells; the reference's arrows: (w / 30, h / 30) */
+    int flags;              /* RC_MOTION_FRESH */
+} rc_motion_params;
+typedef struct rc_motion_cell {    /* 40 bytes */
+    double angle;                  /* degrees in [0, 360), x to the right, y DOWN; base when W == 0 */
+    long long S, W;
+    float tsmax;
+    int n_masked, n_used, peak_bin;
+} rc_motion_cell;
+typedef struct rc_motion_info {
+    int w, h;
+    rc_motion_params prm;              /* deltas in order */
+    int launches_per_push;             /* RC_MOTION_LAUNCHES */
+    long long pushes;                  /* since open / reset */
+    double last_timestamp;             /* of the last push; 0 before the first */
+    size_t device_bytes;
+} rc_motion_info;
+/* Allocates everything the slot will ever need: history 4 B/px, previous gray frame 1 B/px, orientation 4 B/px, mask
+ * 1 B/px (rows of w rounded up to 4 pixels), the cell tables.  Re-opening replaces the state; a refused open leaves the
+ * open state as it was.  RC_EINVAL: no parameters, diff_threshold outside 0..255, duration or a delta not finite or <= 0,
+ * a grid below 1 x 1, wider or higher than the frame or beyond RC_RIPMAP_MAX_CELLS cells, unknown flag bits; RC_ESIZE
+ * beyond the context's max_w x max_h or more than RC_MOTION_MAX_PIXELS pixels (the bound the integer sums are sized for). */
+int rcflow_motion_open(rc_ctx* ctx, int stream, int w, int h, const rc_motion_params* prm);
+/* One gray frame (8UC1, w x h, step >= w).  timestamp: RC_MOTION_AUTO_TIME, or finite, >= 0 and <= 2^24; either way the
+ * stamp must be greater than the last push's (RC_EINVAL).  Outputs (device memory, each may be NULL; the state is updated
+ * whatever is asked for): d_mhi, d_orient 32FC1 (4-byte aligned, a step that is a multiple of 4 and >= 4 w), d_mask 8UC1
+ * (255 / 0, step >= w), d_vis 8UC3 (step >= 3 w), d_cells grid_y x grid_x records and d_frame one record (8-byte aligned).
+ * An output whose byte range [first byte, last byte] overlaps the frame's or another output's is RC_EINVAL.  Row padding
+ * is never written.  Every refusal is decided before anything is queued and leaves the state as it was; RC_ESTATE before
+ * rcflow_motion_open. */
+int rcflow_motion_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_gray, size_t step, double timestamp,
+                           float* d_mhi, size_t mhi_step, float* d_orient, size_t orient_step, uint8_t* d_mask, size_t mask_step,
+                           uint8_t* d_vis, size_t vis_step, rc_motion_cell* d_cells, rc_motion_cell* d_frame);
+/* 2 * (grid_x * grid_y + 1) primitives from the records of the last push (before the first push: all kind 0) into d_prims.
+ * RC_EINVAL: d_prims NULL or not 4-byte aligned, thickness outside 1..RC_DRAW_MAX_THICKNESS, disc_radius outside
+ * 0..RC_DRAW_COORD_MAX, length not finite or beyond RC_DRAW_COORD_MAX in magnitude. */
+int rcflow_motion_prims_dev(rc_ctx* ctx, int stream, uint32_t color, int thickness, int disc_radius, double length,
+                            rc_draw_prim* d_prims);
+/* Blocks until the slot's stream has finished; for hosts and tests.  The records of the last push: the first min(cap,
+ * cells) cells in row order, the frame's record, the pixels of the last silhouette; any pointer may be NULL.  Before the
+ * first push: zeros. */
+int rcflow_motion_read(rc_ctx* ctx, int stream, rc_motion_cell* cells, int cap, rc_motion_cell* frame, long long* silhouette);
+/* zeroes the history, forgets the previous frame, the last stamp and the push count; asynchronous, on the slot's stream */
+int rcflow_motion_reset(rc_ctx* ctx, int stream);
+/* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
+int rcflow_motion_close(rc_ctx* ctx, int stream);
+/* never blocks; RC_ESTATE when nothing is open */
+int rcflow_motion_info(rc_ctx* ctx, int stream, rc_motion_info* info);
+
 /* Display path, ripcurrents.cpp:233-273 (= streamline_displacement / _total_motion / _ratio /
  * _positions, ripcurrents_module.cpp:13-60) on the slot's streamline field (rcflow_advect_field_dev):
  * which 0 = |pt|, 1 = dist, 2 = |pt| / dist; minMaxLoc + convertTo(CV_8UC1, 255/max) +
@@ -1113,7 +1220,7 @@ int rcflow_profile_read(rc_ctx* ctx, int cap, const char** names, int* launches,
 
 /* The same totals under the reference's own bucket names, in the order it prints them (ripcurrents.cpp:103-109,
  * :518-524): farneback, polar, threshold, overlay, erosion, codec, stream ("pathlines").  GPU time of the kernels
- * that do each bucket's work ("overlay" includes the time-exposure images and the 8-bit colour stages, "farneback" the frame stabilisation and the opposing-flow map); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
+ * that do each bucket's work ("overlay" includes the time-exposure images and the 8-bit colour stages, "farneback" the frame stabilisation, the opposing-flow map and the motion templates); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
  * classification kernels, booked under "threshold"), "codec" is 0 (video decode is host I/O outside the library).
  * names / ms: RC_PROFILE_BUCKETS entries each (either may be NULL).  Returns RC_PROFILE_BUCKETS. */
 #define RC_PROFILE_BUCKETS 7

@@ -819,4 +819,75 @@ class Tracks {
          *d_canvas_ = nullptr;
 };
 
+// Motion templates on the device (rcflow_motion_*): globalOrientation (ripcurrents.hpp, ripcurrents_module.cpp:319-359) with
+// a history that lives from push to push; fresh = true is the reference's literal call (the history zeroed before every
+// update).  Host gray frames in; the direction, the per-cell records and the picture out.
+class MotionTemplates {
+  public:
+    // the reference's numbers; its arrows every 30 px are grid (width / 30, height / 30)
+    MotionTemplates(Pipeline& pipe, int diff_threshold = 30, double duration = 1., double delta1 = 0.25, double delta2 = 1., int grid_x = 1,
+                    int grid_y = 1, bool fresh = false)
+        : pipe_(pipe), cells_(grid_x * grid_y) {
+        rc_motion_params p{};
+        p.diff_threshold = diff_threshold; p.duration = duration; p.delta1 = delta1; p.delta2 = delta2;
+        p.grid_x = grid_x; p.grid_y = grid_y; p.flags = fresh ? RC_MOTION_FRESH : 0;
+        check(rcflow_motion_open(pipe.context(), 0, pipe.width(), pipe.height(), &p));
+    }
+    ~MotionTemplates() {
+        (void)rcflow_motion_close(pipe_.context(), 0);
+        for (void* p : {d_gray_, d_vis_, d_prims_}) if (p) (void)hipFree(p);
+    }
+    MotionTemplates(const MotionTemplates&) = delete;
+    MotionTemplates& operator=(const MotionTemplates&) = delete;
+
+    // gray: 8UC1 of the pipeline's size.  picture (8UC3, optional): the history as a grey image (hist_gray of :333).
+    void push(const Mat& gray, double timestamp = RC_MOTION_AUTO_TIME, Mat* picture = nullptr) {
+        const int w = pipe_.width(), h = pipe_.height();
+        if (gray.empty() || gray.rows != h || gray.cols != w || gray.channels != 1 || gray.elem != 1)
+            throw Error(RC_EINVAL, "MotionTemplates::push: the frame must be 8UC1 of the pipeline's size");
+        if (picture && (picture->empty() || picture->rows != h || picture->cols != w || picture->channels != 3 || picture->elem != 1))
+            throw Error(RC_EINVAL, "MotionTemplates::push: the picture must be 8UC3 of the pipeline's size");
+        if (!d_gray_) hip_check(hipMalloc(&d_gray_, (size_t)w * h), "hipMalloc gray");
+        if (picture && !d_vis_) hip_check(hipMalloc(&d_vis_, (size_t)w * h * 3), "hipMalloc picture");
+        check(rcflow_sync(pipe_.context(), 0));                  // the last push may still be reading the staging frame
+        hip_check(hipMemcpy2D(d_gray_, (size_t)w, gray.data, gray.step, (size_t)w, h, hipMemcpyHostToDevice), "upload frame");
+        check(rcflow_motion_push_dev(pipe_.context(), 0, (const uint8_t*)d_gray_, (size_t)w, timestamp, nullptr, 0, nullptr, 0, nullptr, 0,
+                                     picture ? (uint8_t*)d_vis_ : nullptr, (size_t)w * 3, nullptr, nullptr));
+        if (picture) {
+            check(rcflow_sync(pipe_.context(), 0));
+            hip_check(hipMemcpy2D(picture->data, picture->step, d_vis_, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost), "download picture");
+        }
+    }
+    // waits for the pipeline's stream: the frame's record of the last push; cells (optional): grid_y x grid_x records
+    rc_motion_cell read(std::vector<rc_motion_cell>* cells = nullptr, long long* silhouette = nullptr) {
+        rc_motion_cell f;
+        if (cells) cells->resize((size_t)cells_);
+        check(rcflow_motion_read(pipe_.context(), 0, cells ? cells->data() : nullptr, cells ? cells_ : 0, &f, silhouette));
+        return f;
+    }
+    // degrees in [0, 360), x to the right, y down
+    double angle() { return read().angle; }
+    // paints a disc and a line of `length` pixels per cell and for the frame into img (8UC3); no arrowheads
+    void draw(Mat& img, uint32_t color = 0x00ffff, int thickness = 1, int disc_radius = 2, double length = 15.) {
+        const int w = pipe_.width(), h = pipe_.height(), n = 2 * (cells_ + 1);
+        if (img.empty() || img.rows != h || img.cols != w || img.channels != 3 || img.elem != 1)
+            throw Error(RC_EINVAL, "MotionTemplates::draw: img must be 8UC3 of the pipeline's size");
+        if (!d_prims_) hip_check(hipMalloc(&d_prims_, (size_t)n * sizeof(rc_draw_prim)), "hipMalloc prims");
+        if (!d_vis_) hip_check(hipMalloc(&d_vis_, (size_t)w * h * 3), "hipMalloc picture");
+        check(rcflow_sync(pipe_.context(), 0));
+        hip_check(hipMemcpy2D(d_vis_, (size_t)w * 3, img.data, img.step, (size_t)w * 3, h, hipMemcpyHostToDevice), "upload canvas");
+        check(rcflow_motion_prims_dev(pipe_.context(), 0, color, thickness, disc_radius, length, (rc_draw_prim*)d_prims_));
+        check(rcflow_draw_dev(pipe_.context(), 0, (uint8_t*)d_vis_, (size_t)w * 3, w, h, 3, (const rc_draw_prim*)d_prims_, n, nullptr));
+        check(rcflow_sync(pipe_.context(), 0));
+        hip_check(hipMemcpy2D(img.data, img.step, d_vis_, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost), "download canvas");
+    }
+    rc_motion_info info() { rc_motion_info i; check(rcflow_motion_info(pipe_.context(), 0, &i)); return i; }
+    void reset() { check(rcflow_motion_reset(pipe_.context(), 0)); }
+
+  private:
+    Pipeline& pipe_;
+    int cells_;
+    void *d_gray_ = nullptr, *d_vis_ = nullptr, *d_prims_ = nullptr;
+};
+
 }  // namespace rc

@@ -42,6 +42,8 @@ RC_REGIONS_MAX, RC_REGIONS_LAUNCHES = 65536, 7
 # rcflow_tracks_*: the bounds on max_regions and max_tracks, the launches of a push, rc_track::flags
 RC_TRACKS_MAX_REGIONS, RC_TRACKS_MAX, RC_TRACKS_LAUNCHES = 1024, 1024, 6
 TRACK_FLAGS = {"seen": 1, "born": 2, "coasting": 4, "ended": 8, "split": 16, "merged": 32, "confirmed": 64}
+# rcflow_motion_*: its one flag, the automatic stamp, the launches of a push
+RC_MOTION_FRESH, RC_MOTION_AUTO_TIME, RC_MOTION_LAUNCHES = 1, -1.0, 3
 
 ERRORS = {-1: "RC_EINVAL", -2: "RC_ENOMEM", -3: "RC_EHIP", -4: "RC_ENODEV", -5: "RC_ESIZE",
           -6: "RC_ESTATE", -7: "RC_ECOMM"}
@@ -127,6 +129,24 @@ class TracksInfo(C.Structure):
     """rc_tracks_info (include/rcflow.h)."""
     _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", TracksParams), ("launches_per_push", C.c_int), ("pushes", C.c_longlong),
                 ("device_bytes", C.c_size_t)]
+
+
+class MotionParams(C.Structure):
+    """rc_motion_params (include/rcflow.h)."""
+    _fields_ = [("diff_threshold", C.c_int), ("duration", C.c_double), ("delta1", C.c_double), ("delta2", C.c_double),
+                ("grid_x", C.c_int), ("grid_y", C.c_int), ("flags", C.c_int)]
+
+
+class MotionCell(C.Structure):
+    """rc_motion_cell (include/rcflow.h), 40 bytes; numpy: api.MOTION_CELL_DTYPE."""
+    _fields_ = [("angle", C.c_double), ("S", C.c_longlong), ("W", C.c_longlong), ("tsmax", C.c_float), ("n_masked", C.c_int),
+                ("n_used", C.c_int), ("peak_bin", C.c_int)]
+
+
+class MotionInfo(C.Structure):
+    """rc_motion_info (include/rcflow.h)."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", MotionParams), ("launches_per_push", C.c_int), ("pushes", C.c_longlong),
+                ("last_timestamp", C.c_double), ("device_bytes", C.c_size_t)]
 
 
 class FitParams(C.Structure):
@@ -278,6 +298,13 @@ SIGNATURES = {
     "rcflow_tracks_info": [_vp, _i, C.POINTER(TracksInfo)],
     "rcflow_tracks_reset": [_vp, _i],
     "rcflow_tracks_close": [_vp, _i],
+    "rcflow_motion_open": [_vp, _i, _i, _i, C.POINTER(MotionParams)],
+    "rcflow_motion_push_dev": [_vp, _i, _vp, _sz, _d, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp],
+    "rcflow_motion_prims_dev": [_vp, _i, C.c_uint32, _i, _i, _d, _vp],
+    "rcflow_motion_read": [_vp, _i, _vp, _i, _vp, C.POINTER(C.c_longlong)],
+    "rcflow_motion_reset": [_vp, _i],
+    "rcflow_motion_close": [_vp, _i],
+    "rcflow_motion_info": [_vp, _i, C.POINTER(MotionInfo)],
     "rcflow_comm_unique_id": [_vp],
     "rcflow_comm_init": [_vp, _vp, _i, _i],
     "rcflow_comm_destroy": [_vp],

@@ -14,6 +14,7 @@ Names, argument order and meaning follow the reference (paths relative to
   timex_*                    compute_timex main.cpp:1195-1263, compute_brightColor main.cpp:1265-1383
   framestab_*                compute_phaseCorrelate main.cpp:1684-1775 (phase_correlate, warp_translate: its stages)
   ripmap_*                   averageVector ripcurrents_module.cpp:386-484, finished (the opposing-flow map)
+  motion_* / globalOrientation  ripcurrents_module.cpp:319-359: motion history, gradient and orientation kept on the device
   tracers_* / draw           compute_streaklines / compute_timelines / compute_populationMap main.cpp:78-176 with the vertices
                              and the drawing (Streakline.cpp:57-66, ripcurrents_module.cpp:800-805, :1186-1194) on the device
 
@@ -32,6 +33,7 @@ from ._lib import RC_RIPMAP_WAIT_FULL, RIPMAP_SOURCES
 from ._lib import TRACERS_MOVERS, TRACER_KINDS, TracersInfo, TracersParams
 from ._lib import RegionsInfo, RegionsParams
 from ._lib import TracksInfo, TracksParams
+from ._lib import RC_MOTION_AUTO_TIME, RC_MOTION_FRESH, MotionInfo, MotionParams
 
 __all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState"]
 
@@ -55,6 +57,9 @@ TRACK_DTYPE = np.dtype([("id", "<i8"), ("parent", "<i8"), ("first_push", "<i8"),
                         ("py", "<i4"), ("px0", "<i4"), ("py0", "<i4"), ("overlap", "<i4"), ("mean_fx", "<f4"), ("mean_fy", "<f4")])
 # the eight words of a tracks summary, in order
 TRACKS_SUMMARY = ("alive", "confirmed", "born", "ended", "seen", "coasting", "untracked", "pushes")
+# rc_motion_cell as a numpy record (40 bytes): what Context.motion_read returns, per cell and for the frame
+MOTION_CELL_DTYPE = np.dtype([("angle", "<f8"), ("S", "<i8"), ("W", "<i8"), ("tsmax", "<f4"), ("n_masked", "<i4"), ("n_used", "<i4"),
+                              ("peak_bin", "<i4")])
 
 
 def _params(pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags):
@@ -1110,6 +1115,102 @@ class Context:
     def ripmap_close(self, stream=0):
         self._bind(stream)          # waits for the pushes queued on that stream before freeing
         check(self._lib.rcflow_ripmap_close(self._h, stream))
+
+    # ------------------------------------------------------------------ motion templates
+    def motion_open(self, w, h, diff_threshold=30, duration=1.0, delta1=0.25, delta2=1.0, grid=(1, 1), fresh=False, stream=0):
+        """Opens the slot's motion templates for w x h gray frames (include/rcflow.h, "motion templates"): a motion history
+        kept on the device from push to push, its gradient, and the orientation of every cell of grid = (grid_x, grid_y) and
+        of the frame.  The defaults are the reference's numbers (globalOrientation, ripcurrents_module.cpp:319-359); its
+        arrows every 30 px are grid=(w // 30, h // 30).  fresh: the reference's literal call, the history zeroed before
+        every update (RC_MOTION_FRESH).  The state takes about 10 bytes per pixel of device memory."""
+        p = MotionParams(diff_threshold=int(diff_threshold), duration=float(duration), delta1=float(delta1), delta2=float(delta2),
+                         grid_x=int(grid[0]), grid_y=int(grid[1]), flags=RC_MOTION_FRESH if fresh else 0)
+        self._bind(stream)          # the state is zeroed on the slot's stream: the one the pushes will run on
+        check(self._lib.rcflow_motion_open(self._h, stream, int(w), int(h), C.byref(p)))
+
+    def motion_info(self, stream=0):
+        """dict(w, h, diff_threshold, duration, delta1, delta2, grid, fresh, launches_per_push, pushes, last_timestamp,
+        device_bytes); never blocks."""
+        i = MotionInfo()
+        check(self._lib.rcflow_motion_info(self._h, stream, C.byref(i)))
+        return dict(w=i.w, h=i.h, diff_threshold=i.prm.diff_threshold, duration=i.prm.duration, delta1=i.prm.delta1, delta2=i.prm.delta2,
+                    grid=(i.prm.grid_x, i.prm.grid_y), fresh=bool(i.prm.flags & RC_MOTION_FRESH), launches_per_push=i.launches_per_push,
+                    pushes=i.pushes, last_timestamp=i.last_timestamp, device_bytes=i.device_bytes)
+
+    def motion_push(self, gray, timestamp=None, mhi=None, orient=None, mask=None, vis=None, cells=None, frame=None, stream=0):
+        """One gray frame (HxW uint8 device tensor, dense pixels, rows may be padded): three launches, nothing is synchronised.
+        timestamp: None for "pushes so far + 1", else a number greater than the last push's.  Outputs are preallocated
+        device tensors, each optional: mhi and orient HxW float32, mask HxW uint8 (255 / 0), vis HxWx3 uint8 (the history as
+        a grey picture), cells a contiguous uint8 tensor of grid_y * grid_x * 40 bytes (rc_motion_cell records,
+        MOTION_CELL_DTYPE), frame one such record.  The records also stay on the slot for motion_read / motion_prims."""
+        info = self.motion_info(stream)
+        h, w, (gx, gy) = info["h"], info["w"], info["grid"]
+        _check_out(gray, self.device, torch.uint8, "gray", shape=(h, w), dense=True)
+        null = C.c_void_p(None)
+        ptr, step = [null] * 4, [0] * 4
+        for k, (t, dtype, name, shape) in enumerate(((mhi, torch.float32, "mhi", (h, w)), (orient, torch.float32, "orient", (h, w)),
+                                                     (mask, torch.uint8, "mask", (h, w)), (vis, torch.uint8, "vis", (h, w, 3)))):
+            if t is not None:
+                _check_out(t, self.device, dtype, name, shape=shape, dense=True)
+                ptr[k], step[k] = self._ptr(t), t.stride(0) * t.element_size()
+        cp = null if cells is None else self._ptr(_check_out(cells, self.device, torch.uint8, "cells",
+                                                             numel=gx * gy * MOTION_CELL_DTYPE.itemsize))
+        fp = null if frame is None else self._ptr(_check_out(frame, self.device, torch.uint8, "frame", numel=MOTION_CELL_DTYPE.itemsize))
+        self._bind(stream)
+        check(self._lib.rcflow_motion_push_dev(self._h, stream, self._ptr(gray), gray.stride(0),
+                                               RC_MOTION_AUTO_TIME if timestamp is None else float(timestamp),
+                                               ptr[0], step[0], ptr[1], step[1], ptr[2], step[2], ptr[3], step[3], cp, fp))
+
+    def motion_read(self, stream=0):
+        """Waits for the slot's stream -> dict(cells (grid_y x grid_x numpy array of MOTION_CELL_DTYPE), frame (one record),
+        angle (the frame's, degrees in [0, 360), y down), silhouette (pixels of the last silhouette)) of the last push."""
+        gx, gy = self.motion_info(stream)["grid"]
+        cells, frame, sil = np.zeros(gx * gy, MOTION_CELL_DTYPE), np.zeros(1, MOTION_CELL_DTYPE), C.c_longlong(0)
+        self._bind(stream)
+        check(self._lib.rcflow_motion_read(self._h, stream, cells.ctypes.data, gx * gy, frame.ctypes.data, C.byref(sil)))
+        return dict(cells=cells.reshape(gy, gx), frame=frame[0], angle=float(frame[0]["angle"]), silhouette=sil.value)
+
+    def motion_prims(self, color=0x00ffff, thickness=1, disc_radius=2, length=15.0, out=None, stream=0):
+        """The records of the last push as 2 * (cells + 1) primitives for draw() -> a device uint8 tensor of rc_draw_prim
+        records: per cell a disc at its centre and a line of `length` pixels along its angle, the frame's pair last at the
+        image centre; a set without a direction (W == 0) gives kind 0, which draw() skips (and counts)."""
+        gx, gy = self.motion_info(stream)["grid"]
+        n = 2 * (gx * gy + 1)
+        if out is None:
+            out = torch.empty((n, 32), dtype=torch.uint8, device=self.device)
+        else:
+            _check_out(out, self.device, torch.uint8, "out", numel=n * 32)
+        self._bind(stream)
+        check(self._lib.rcflow_motion_prims_dev(self._h, stream, int(color), int(thickness), int(disc_radius), float(length), self._ptr(out)))
+        return out
+
+    def motion_reset(self, stream=0):
+        self._bind(stream)
+        check(self._lib.rcflow_motion_reset(self._h, stream))
+
+    def motion_close(self, stream=0):
+        self._bind(stream)          # waits for the pushes queued on that stream before freeing
+        check(self._lib.rcflow_motion_close(self._h, stream))
+
+    def globalOrientation(self, prev, cur, stream=0):
+        """The reference's call in one line (ripcurrents_module.cpp:319-359): the direction of the motion between two gray
+        frames -> (angle in degrees, HxWx3 uint8 picture of the silhouette: its hist_gray before the arrows).  Opens the
+        slot's motion templates with fresh=True and the reference's numbers unless a session of that size is open; with an
+        open session of another kind its parameters hold."""
+        prev, cur = self._dev(prev, torch.uint8), self._dev(cur, torch.uint8)
+        h, w = int(cur.shape[0]), int(cur.shape[1])
+        try:
+            info = self.motion_info(stream)
+        except RcflowError:
+            info = None
+        if info is None or (info["w"], info["h"]) != (w, h):
+            self.motion_open(w, h, fresh=True, stream=stream)
+        else:
+            self.motion_reset(stream)
+        vis = torch.empty((h, w, 3), dtype=torch.uint8, device=self.device)
+        self.motion_push(prev, stream=stream)
+        self.motion_push(cur, vis=vis, stream=stream)
+        return self.motion_read(stream)["angle"], vis
 
     # ------------------------------------------------------------------ tracer lines and drawing
     def draw(self, img, prims, skipped=None, stream=0):

@@ -1,6 +1,8 @@
 // rc_device.h -- device-side helpers shared by the gfx950 kernels.
 #pragma once
 
+#include <cfloat>
+
 #include "rc_common.h"
 
 #define RC_BLOCK 256
@@ -39,3 +41,23 @@ __device__ __forceinline__ int rc_xcd_remap(int b, int nt) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
+// OpenCV core fastAtan32f (degrees), mathfuncs_core: 7th-order odd polynomial.
+__device__ __forceinline__ float rc_fast_atan2_deg(float y, float x) {
+    const float p1 = 0.9997878412794807f * (float)(180 / 3.14159265358979323846);
+    const float p3 = -0.3258083974640975f * (float)(180 / 3.14159265358979323846);
+    const float p5 = 0.1555786518463281f * (float)(180 / 3.14159265358979323846);
+    const float p7 = -0.04432655554792128f * (float)(180 / 3.14159265358979323846);
+    float ax = fabsf(x), ay = fabsf(y);
+    // upstream branches on ax >= ay; both branches divide the smaller by the larger and run the same
+    // polynomial, so one division and one polynomial on (min, max) give the same bits without the
+    // compiler evaluating both sides
+    const bool xmajor = ax >= ay;
+    const float lo = xmajor ? ay : ax, hi = xmajor ? ax : ay;
+    const float c = lo / (hi + (float)DBL_EPSILON);
+    const float c2 = c * c;
+    float a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
+    if (!xmajor) a = 90.f - a;
+    if (x < 0) a = 180.f - a;
+    if (y < 0) a = 360.f - a;
+    return a;
+}

@@ -249,6 +249,7 @@ static void slot_free(RcSlot& s) {
     rc_state_free(s.tr);
     rc_state_free(s.rg);
     rc_state_free(s.tk);
+    rc_state_free(s.mt);
     rc_buf_free(s.pc.tab); rc_buf_free(s.pc.scratch);
     rc_graph_drop(s.loop_graph);
     for (auto& e : s.fev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
@@ -340,7 +341,7 @@ extern "C" int rcflow_debug_plan_pyr_kernel(int ksize, double sigma, float* taps
     return RC_OK;
 }
 extern "C" int rcflow_debug_kind(int id, const char** name, const char** bucket) {
-    if (id < 0 || id >= RC_K_KINDS || !name || !bucket) return RC_EINVAL;
+    if (id < 0 || id >= RC_K_LISTED || !name || !bucket) return RC_EINVAL;
     *name = kKindNames[id];
     *bucket = kBucketNames[kBucketOfKind[id]];
     return RC_OK;
