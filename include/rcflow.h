@@ -849,7 +849,7 @@ int rcflow_tracers_close(rc_ctx* ctx, int stream);
  *                component, 0 for background and for dropped components.  All K numbers appear, also beyond max_regions.
  *     d_mask_out 8UC1: 255 where d_labels would be non-zero, else 0 (an area opening: what rcflow_create_edges_dev /
  *                rcflow_create_output_dev take next).  It may be d_mask itself with the same step (in place); any other
- *                overlap of the byte ranges [first byte, last byte] of an input or output with another output is RC_EINVAL.
+ *                overlap of the byte ranges [first byte, past the last) of an input or output with another output is RC_EINVAL.
  *     d_regions  max_regions records rc_region (8-byte aligned), the first min(K, max_regions) kept components in
  *                order; the rest of the array is zero bytes.
  *     d_summary  8 int64: components before the filter, K, records written, foreground pixels, pixels in kept
@@ -1013,7 +1013,7 @@ int rcflow_tracks_open(rc_ctx* ctx, int stream, int w, int h, const rc_tracks_pa
  * max_regions records or as many as d_regions_summary[2] says (8-byte aligned); d_regions_summary: the 8 int64 of
  * rcflow_regions_push_dev.  Every refusal is decided before anything is queued and leaves the state as it was: RC_EINVAL
  * for a NULL input, a bad step, a pointer without the natural alignment of its element, an output whose byte range
- * [first byte, last byte] overlaps an input's or another output's (d_regions counts as max_regions records); RC_ESTATE
+ * [first byte, past the last) overlaps an input's or another output's (d_regions counts as max_regions records); RC_ESTATE
  * before open. */
 int rcflow_tracks_push_dev(rc_ctx* ctx, int stream, const int32_t* d_labels, size_t labels_step,
                            const rc_region* d_regions, const long long* d_regions_summary,
@@ -1118,7 +1118,7 @@ int rcflow_motion_open(rc_ctx* ctx, int stream, int w, int h, const rc_motion_pa
  * stamp must be greater than the last push's (RC_EINVAL).  Outputs (device memory, each may be NULL; the state is updated
  * whatever is asked for): d_mhi, d_orient 32FC1 (4-byte aligned, a step that is a multiple of 4 and >= 4 w), d_mask 8UC1
  * (255 / 0, step >= w), d_vis 8UC3 (step >= 3 w), d_cells grid_y x grid_x records and d_frame one record (8-byte aligned).
- * An output whose byte range [first byte, last byte] overlaps the frame's or another output's is RC_EINVAL.  Row padding
+ * An output whose byte range [first byte, past the last) overlaps the frame's or another output's is RC_EINVAL.  Row padding
  * is never written.  Every refusal is decided before anything is queued and leaves the state as it was; RC_ESTATE before
  * rcflow_motion_open. */
 int rcflow_motion_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_gray, size_t step, double timestamp,

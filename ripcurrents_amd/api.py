@@ -429,6 +429,23 @@ class Context:
         self._bind(stream)
         check(self._lib.rcflow_analysis_reset(self._h, stream, w, h))
 
+    def _out_image(self, t, dtype, name, shape):
+        """An optional output image of dense pixels -> (pointer, byte step); (NULL, 0) for None."""
+        if t is None:
+            return C.c_void_p(None), 0
+        _check_out(t, self.device, dtype, name, shape=shape, dense=True)
+        return self._ptr(t), t.stride(0) * t.element_size()
+
+    def _out_array(self, t, dtype, name, numel):
+        """An optional contiguous output of `numel` elements -> its pointer; NULL for None."""
+        return C.c_void_p(None) if t is None else self._ptr(_check_out(t, self.device, dtype, name, numel=numel))
+
+    def _prims_out(self, out, n):
+        """The output of a *_prims method: n rc_draw_prim records, allocated here or the caller's, checked."""
+        if out is None:
+            return torch.empty((n, 32), dtype=torch.uint8, device=self.device)
+        return _check_out(out, self.device, torch.uint8, "out", numel=n * 32)
+
     def _flow(self, flow):
         flow = self._dev(flow, torch.float32)
         if flow.dim() != 3 or flow.shape[2] != 2 or flow.stride(2) != 1 or flow.stride(1) != 2:
@@ -1069,17 +1086,10 @@ class Context:
             if flow.dim() != 3 or tuple(flow.shape) != (h, w, 2) or flow.stride(2) != 1 or flow.stride(1) != 2:
                 raise ValueError("flow must be %dx%dx2 float32 with dense pixels, as opened" % (h, w))
             fp, fstep = self._ptr(flow), flow.stride(0) * 4
-        hp, hstep, mp, mstep, cp, sp = C.c_void_p(None), 0, C.c_void_p(None), 0, C.c_void_p(None), C.c_void_p(None)
-        if hsv is not None:
-            _check_out(hsv, self.device, torch.uint8, "hsv", shape=(h, w, 3), dense=True)
-            hp, hstep = self._ptr(hsv), hsv.stride(0)
-        if mask is not None:
-            _check_out(mask, self.device, torch.uint8, "mask", shape=(h, w), dense=True)
-            mp, mstep = self._ptr(mask), mask.stride(0)
-        if cells is not None:
-            cp = self._ptr(_check_out(cells, self.device, torch.float32, "cells", shape=(gy, gx, 4)))
-        if summary is not None:
-            sp = self._ptr(_check_out(summary, self.device, torch.float64, "summary", numel=8))
+        hp, hstep = self._out_image(hsv, torch.uint8, "hsv", (h, w, 3))
+        mp, mstep = self._out_image(mask, torch.uint8, "mask", (h, w))
+        cp = C.c_void_p(None) if cells is None else self._ptr(_check_out(cells, self.device, torch.float32, "cells", shape=(gy, gx, 4)))
+        sp = self._out_array(summary, torch.float64, "summary", 8)
         self._bind(stream)
         check(self._lib.rcflow_ripmap_push_dev(self._h, stream, fp, fstep, hp, hstep, mp, mstep, cp, sp))
 
@@ -1146,20 +1156,13 @@ class Context:
         info = self.motion_info(stream)
         h, w, (gx, gy) = info["h"], info["w"], info["grid"]
         _check_out(gray, self.device, torch.uint8, "gray", shape=(h, w), dense=True)
-        null = C.c_void_p(None)
-        ptr, step = [null] * 4, [0] * 4
-        for k, (t, dtype, name, shape) in enumerate(((mhi, torch.float32, "mhi", (h, w)), (orient, torch.float32, "orient", (h, w)),
-                                                     (mask, torch.uint8, "mask", (h, w)), (vis, torch.uint8, "vis", (h, w, 3)))):
-            if t is not None:
-                _check_out(t, self.device, dtype, name, shape=shape, dense=True)
-                ptr[k], step[k] = self._ptr(t), t.stride(0) * t.element_size()
-        cp = null if cells is None else self._ptr(_check_out(cells, self.device, torch.uint8, "cells",
-                                                             numel=gx * gy * MOTION_CELL_DTYPE.itemsize))
-        fp = null if frame is None else self._ptr(_check_out(frame, self.device, torch.uint8, "frame", numel=MOTION_CELL_DTYPE.itemsize))
+        images = (self._out_image(mhi, torch.float32, "mhi", (h, w)) + self._out_image(orient, torch.float32, "orient", (h, w)) +
+                  self._out_image(mask, torch.uint8, "mask", (h, w)) + self._out_image(vis, torch.uint8, "vis", (h, w, 3)))
+        cp = self._out_array(cells, torch.uint8, "cells", gx * gy * MOTION_CELL_DTYPE.itemsize)
+        fp = self._out_array(frame, torch.uint8, "frame", MOTION_CELL_DTYPE.itemsize)
         self._bind(stream)
         check(self._lib.rcflow_motion_push_dev(self._h, stream, self._ptr(gray), gray.stride(0),
-                                               RC_MOTION_AUTO_TIME if timestamp is None else float(timestamp),
-                                               ptr[0], step[0], ptr[1], step[1], ptr[2], step[2], ptr[3], step[3], cp, fp))
+                                               RC_MOTION_AUTO_TIME if timestamp is None else float(timestamp), *images, cp, fp))
 
     def motion_read(self, stream=0):
         """Waits for the slot's stream -> dict(cells (grid_y x grid_x numpy array of MOTION_CELL_DTYPE), frame (one record),
@@ -1176,10 +1179,7 @@ class Context:
         image centre; a set without a direction (W == 0) gives kind 0, which draw() skips (and counts)."""
         gx, gy = self.motion_info(stream)["grid"]
         n = 2 * (gx * gy + 1)
-        if out is None:
-            out = torch.empty((n, 32), dtype=torch.uint8, device=self.device)
-        else:
-            _check_out(out, self.device, torch.uint8, "out", numel=n * 32)
+        out = self._prims_out(out, n)
         self._bind(stream)
         check(self._lib.rcflow_motion_prims_dev(self._h, stream, int(color), int(thickness), int(disc_radius), float(length), self._ptr(out)))
         return out
@@ -1385,22 +1385,16 @@ class Context:
         info = self.regions_info(stream)
         h, w = info["h"], info["w"]
         _check_out(mask, self.device, torch.uint8, "mask", shape=(h, w), dense=True)
-        fp, fstep, lp, lstep, op, ostep, rp, sp = C.c_void_p(None), 0, C.c_void_p(None), 0, C.c_void_p(None), 0, C.c_void_p(None), C.c_void_p(None)
+        fp, fstep = C.c_void_p(None), 0
         if flow is not None:
             flow = self._dev(flow, torch.float32)
             if flow.dim() != 3 or tuple(flow.shape) != (h, w, 2) or flow.stride(2) != 1 or flow.stride(1) != 2:
                 raise ValueError("flow must be %dx%dx2 float32 with dense pixels, as opened" % (h, w))
             fp, fstep = self._ptr(flow), flow.stride(0) * 4
-        if labels is not None:
-            _check_out(labels, self.device, torch.int32, "labels", shape=(h, w), dense=True)
-            lp, lstep = self._ptr(labels), labels.stride(0) * 4
-        if mask_out is not None:
-            _check_out(mask_out, self.device, torch.uint8, "mask_out", shape=(h, w), dense=True)
-            op, ostep = self._ptr(mask_out), mask_out.stride(0)
-        if regions is not None:
-            rp = self._ptr(_check_out(regions, self.device, torch.uint8, "regions", numel=info["max_regions"] * REGION_DTYPE.itemsize))
-        if summary is not None:
-            sp = self._ptr(_check_out(summary, self.device, torch.int64, "summary", numel=8))
+        lp, lstep = self._out_image(labels, torch.int32, "labels", (h, w))
+        op, ostep = self._out_image(mask_out, torch.uint8, "mask_out", (h, w))
+        rp = self._out_array(regions, torch.uint8, "regions", info["max_regions"] * REGION_DTYPE.itemsize)
+        sp = self._out_array(summary, torch.int64, "summary", 8)
         self._bind(stream)
         check(self._lib.rcflow_regions_push_dev(self._h, stream, self._ptr(mask), mask.stride(0), fp, fstep, lp, lstep, op, ostep, rp, sp))
 
@@ -1409,10 +1403,7 @@ class Context:
         records: per record its box (four lines), a disc at the centroid and, with flow_scale != 0, a line along the mean
         flow times flow_scale; slots without a record are kind 0, which draw() skips (and counts)."""
         n = 6 * self.regions_info(stream)["max_regions"]
-        if out is None:
-            out = torch.empty((n, 32), dtype=torch.uint8, device=self.device)
-        else:
-            _check_out(out, self.device, torch.uint8, "out", numel=n * 32)
+        out = self._prims_out(out, n)
         self._bind(stream)
         check(self._lib.rcflow_regions_prims_dev(self._h, stream, int(color), int(thickness), int(disc_radius), float(flow_scale),
                                                  self._ptr(out)))
@@ -1469,16 +1460,10 @@ class Context:
             raise ValueError("regions must be a contiguous uint8 tensor of at least max_regions (%d) rc_region records on %s" % (
                 info["max_regions"], self.device))
         _check_out(regions_summary, self.device, torch.int64, "regions_summary", numel=8)
-        tp, lp, op, ostep, sp = C.c_void_p(None), C.c_void_p(None), C.c_void_p(None), 0, C.c_void_p(None)
-        if tracks is not None:
-            tp = self._ptr(_check_out(tracks, self.device, torch.uint8, "tracks", numel=info["max_tracks"] * TRACK_DTYPE.itemsize))
-        if track_of_label is not None:
-            lp = self._ptr(_check_out(track_of_label, self.device, torch.int32, "track_of_label", numel=info["max_regions"] + 1))
-        if mask_out is not None:
-            _check_out(mask_out, self.device, torch.uint8, "mask_out", shape=(h, w), dense=True)
-            op, ostep = self._ptr(mask_out), mask_out.stride(0)
-        if summary is not None:
-            sp = self._ptr(_check_out(summary, self.device, torch.int64, "summary", numel=8))
+        tp = self._out_array(tracks, torch.uint8, "tracks", info["max_tracks"] * TRACK_DTYPE.itemsize)
+        lp = self._out_array(track_of_label, torch.int32, "track_of_label", info["max_regions"] + 1)
+        op, ostep = self._out_image(mask_out, torch.uint8, "mask_out", (h, w))
+        sp = self._out_array(summary, torch.int64, "summary", 8)
         self._bind(stream)
         check(self._lib.rcflow_tracks_push_dev(self._h, stream, self._ptr(labels), labels.stride(0) * 4, self._ptr(regions),
                                                self._ptr(regions_summary), tp, lp, op, ostep, sp))
@@ -1488,10 +1473,7 @@ class Context:
         records: per confirmed track that has not ended its box (four lines) and a disc at its centroid; every other slot
         is kind 0, which draw() skips (and counts)."""
         n = 5 * self.tracks_info(stream)["max_tracks"]
-        if out is None:
-            out = torch.empty((n, 32), dtype=torch.uint8, device=self.device)
-        else:
-            _check_out(out, self.device, torch.uint8, "out", numel=n * 32)
+        out = self._prims_out(out, n)
         self._bind(stream)
         check(self._lib.rcflow_tracks_prims_dev(self._h, stream, int(color), int(thickness), int(disc_radius), self._ptr(out)))
         return out

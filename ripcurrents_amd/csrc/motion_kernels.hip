@@ -482,54 +482,29 @@ extern "C" int rcflow_motion_open(rc_ctx* ctx, int stream, int w, int h, const r
     return rc_state_install(*s, s->mt, n, rc);
 }
 
-// the byte range [first byte, last byte] of an argument
-struct MtSpan { const char* what; const char* lo; const char* hi; };
-static MtSpan mt_span(const char* what, const void* p, size_t step, size_t row_bytes, int h) {
-    return {what, (const char*)p, (const char*)p + (size_t)(h - 1) * step + row_bytes};
-}
-
 extern "C" int rcflow_motion_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_gray, size_t step, double timestamp, float* d_mhi,
                                       size_t mhi_step, float* d_orient, size_t orient_step, uint8_t* d_mask, size_t mask_step, uint8_t* d_vis,
                                       size_t vis_step, rc_motion_cell* d_cells, rc_motion_cell* d_frame) {
     static const char* who = "rcflow_motion_push_dev";
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    RcMotion& m = s->mt;
-    if (!m.open) { rc_set_error("%s before rcflow_motion_open", who); return RC_ESTATE; }
+    RcSlot* s; RcMotion* mp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::mt, who, s, mp)) return rc;
+    RcMotion& m = *mp;
     const int w = m.w, h = m.h;
-    if (!d_gray || step < (size_t)w) { rc_set_error("%s: bad image argument d_gray (a null pointer or a step below w)", who); return RC_EINVAL; }
     const double ts = timestamp == RC_MOTION_AUTO_TIME ? (double)(m.pushes + 1) : timestamp;
     if (!(ts >= 0. && ts <= 16777216.)) { rc_set_error("%s: the timestamp must be RC_MOTION_AUTO_TIME or in 0..2^24", who); return RC_EINVAL; }
     if (m.pushes > 0 && !(ts > m.last_ts)) {
         rc_set_error("%s: timestamp %.17g is not greater than the last push's %.17g", who, ts, m.last_ts);
         return RC_EINVAL;
     }
-    if (d_mhi && (mhi_step < (size_t)w * 4 || (mhi_step & 3) || ((uintptr_t)d_mhi & 3))) {
-        rc_set_error("%s: bad image argument d_mhi (4-byte aligned, a step that is a multiple of 4 and at least 4 * w)", who);
-        return RC_EINVAL;
-    }
-    if (d_orient && (orient_step < (size_t)w * 4 || (orient_step & 3) || ((uintptr_t)d_orient & 3))) {
-        rc_set_error("%s: bad image argument d_orient (4-byte aligned, a step that is a multiple of 4 and at least 4 * w)", who);
-        return RC_EINVAL;
-    }
-    if (d_mask && mask_step < (size_t)w) { rc_set_error("%s: bad image argument d_mask (a step below w)", who); return RC_EINVAL; }
-    if (d_vis && rc_img3_check(who, "d_vis", d_vis, vis_step, w, h)) return RC_EINVAL;
-    if (((uintptr_t)d_cells & 7) || ((uintptr_t)d_frame & 7)) { rc_set_error("%s: d_cells and d_frame must be 8-byte aligned", who); return RC_EINVAL; }
-    MtSpan sp[7];
-    int n = 0;
-    sp[n++] = mt_span("d_gray", d_gray, step, (size_t)w, h);
-    if (d_mhi) sp[n++] = mt_span("d_mhi", d_mhi, mhi_step, (size_t)w * 4, h);
-    if (d_orient) sp[n++] = mt_span("d_orient", d_orient, orient_step, (size_t)w * 4, h);
-    if (d_mask) sp[n++] = mt_span("d_mask", d_mask, mask_step, (size_t)w, h);
-    if (d_vis) sp[n++] = mt_span("d_vis", d_vis, vis_step, (size_t)w * 3, h);
-    if (d_cells) sp[n++] = mt_span("d_cells", d_cells, 0, mt_cells(m) * sizeof(rc_motion_cell), 1);
-    if (d_frame) sp[n++] = mt_span("d_frame", d_frame, 0, sizeof(rc_motion_cell), 1);
-    for (int i = 0; i < n; i++)
-        for (int j = i + 1; j < n; j++)
-            if (!(sp[i].hi <= sp[j].lo || sp[j].hi <= sp[i].lo)) {
-                rc_set_error("%s: %s overlaps %s", who, sp[i].what, sp[j].what);
-                return RC_EINVAL;
-            }
+    RcArgs a(who, w, h);
+    a.image("d_gray", d_gray, step, 1, 1, RC_ARG_IN);
+    a.image("d_mhi", d_mhi, mhi_step, 4, 4, RC_ARG_OUT | RC_ARG_OPTIONAL);
+    a.image("d_orient", d_orient, orient_step, 4, 4, RC_ARG_OUT | RC_ARG_OPTIONAL);
+    a.image("d_mask", d_mask, mask_step, 1, 1, RC_ARG_OUT | RC_ARG_OPTIONAL);
+    a.image("d_vis", d_vis, vis_step, 3, 1, RC_ARG_OUT | RC_ARG_OPTIONAL);
+    a.array("d_cells", d_cells, mt_cells(m) * sizeof(rc_motion_cell), 8, RC_ARG_OUT | RC_ARG_OPTIONAL);
+    a.array("d_frame", d_frame, sizeof(rc_motion_cell), 8, RC_ARG_OUT | RC_ARG_OPTIONAL);
+    if (a.check()) return RC_EINVAL;
     RC_HIP(hipSetDevice(ctx->device));
     int rc = rc_fence_wait(m.zf, s->cur, true);
     if (rc) return rc;
@@ -592,16 +567,12 @@ extern "C" int rcflow_motion_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_
 
 extern "C" int rcflow_motion_prims_dev(rc_ctx* ctx, int stream, uint32_t color, int thickness, int disc_radius, double length,
                                        rc_draw_prim* d_prims) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    RcMotion& m = s->mt;
-    if (!m.open) { rc_set_error("rcflow_motion_prims_dev before rcflow_motion_open"); return RC_ESTATE; }
-    if (!d_prims || ((uintptr_t)d_prims & 3) || thickness < 1 || thickness > RC_DRAW_MAX_THICKNESS || disc_radius < 0 ||
-        disc_radius > RC_DRAW_COORD_MAX || !(fabs(length) <= (double)RC_DRAW_COORD_MAX)) {
-        rc_set_error("rcflow_motion_prims_dev: d_prims (4-byte aligned), thickness 1..%d, disc_radius 0..%d, |length| <= %d",
-                     RC_DRAW_MAX_THICKNESS, RC_DRAW_COORD_MAX, RC_DRAW_COORD_MAX);
-        return RC_EINVAL;
-    }
+    static const char* who = "rcflow_motion_prims_dev";
+    RcSlot* s; RcMotion* mp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::mt, who, s, mp)) return rc;
+    RcMotion& m = *mp;
+    if (rc_prims_check(who, d_prims, thickness, disc_radius)) return RC_EINVAL;
+    if (!(fabs(length) <= (double)RC_DRAW_COORD_MAX)) { rc_set_error("%s: |length| <= %d", who, RC_DRAW_COORD_MAX); return RC_EINVAL; }
     RC_HIP(hipSetDevice(ctx->device));
     int rc = rc_fence_wait(m.zf, s->cur, true);
     if (rc) return rc;
@@ -614,10 +585,9 @@ extern "C" int rcflow_motion_prims_dev(rc_ctx* ctx, int stream, uint32_t color, 
 }
 
 extern "C" int rcflow_motion_read(rc_ctx* ctx, int stream, rc_motion_cell* cells, int cap, rc_motion_cell* frame, long long* silhouette) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    RcMotion& m = s->mt;
-    if (!m.open) { rc_set_error("rcflow_motion_read before rcflow_motion_open"); return RC_ESTATE; }
+    RcSlot* s; RcMotion* mp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::mt, "rcflow_motion_read", s, mp)) return rc;
+    RcMotion& m = *mp;
     if (cap < 0 || (cap && !cells)) { rc_set_error("rcflow_motion_read: a bad buffer"); return RC_EINVAL; }
     RC_HIP(hipSetDevice(ctx->device));
     int rc = rc_fence_wait(m.zf, s->cur, true);
@@ -631,10 +601,9 @@ extern "C" int rcflow_motion_read(rc_ctx* ctx, int stream, rc_motion_cell* cells
 }
 
 extern "C" int rcflow_motion_info(rc_ctx* ctx, int stream, rc_motion_info* info) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    const RcMotion& m = s->mt;
-    if (!m.open) { rc_set_error("no motion templates are open on the slot (rcflow_motion_open)"); return RC_ESTATE; }
+    RcSlot* s; RcMotion* mp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::mt, "rcflow_motion_info", s, mp)) return rc;
+    const RcMotion& m = *mp;
     if (!info) return RC_OK;
     memset(info, 0, sizeof(*info));
     info->w = m.w; info->h = m.h; info->prm = m.prm;
@@ -645,5 +614,5 @@ extern "C" int rcflow_motion_info(rc_ctx* ctx, int stream, rc_motion_info* info)
     return RC_OK;
 }
 
-extern "C" int rcflow_motion_reset(rc_ctx* ctx, int stream) { return rc_state_reset(ctx, stream, &RcSlot::mt, "rcflow_motion"); }
+extern "C" int rcflow_motion_reset(rc_ctx* ctx, int stream) { return rc_state_reset(ctx, stream, &RcSlot::mt, "rcflow_motion_reset"); }
 extern "C" int rcflow_motion_close(rc_ctx* ctx, int stream) { return rc_state_close(ctx, stream, &RcSlot::mt); }

@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 
+#include "rc_args.h"
 #include "rc_common.h"
 
 struct RcBuf {
@@ -370,7 +371,6 @@ enum { RC_K_LISTED = RC_K_MOTION };
 static_assert(RC_K_LISTED == 25, "the rows before RC_K_MOTION keep their ids");
 static_assert(RC_B_BUCKETS == RC_PROFILE_BUCKETS, "include/rcflow.h promises RC_PROFILE_BUCKETS buckets");
 
-void rc_set_error(const char* fmt, ...);
 int rc_buf_ensure(RcBuf& b, size_t bytes);
 void rc_buf_free(RcBuf& b);
 RcSlot* rc_slot(rc_ctx* ctx, int stream);
@@ -390,9 +390,11 @@ int rc_fence_zero(RcZeroFence& z, hipStream_t cur, std::initializer_list<RcBuf*>
 // callers are ordered behind (a push); a call that only reads leaves the fence pending
 int rc_fence_wait(RcZeroFence& z, hipStream_t cur, bool consume);
 void rc_fence_free(RcZeroFence& z);
-// 8UC3 image arguments.  who, what: the entry point and the argument, for the text
-bool rc_img3_overlap(const uint8_t* a, size_t astep, int aw, int ah, const uint8_t* b, size_t bstep, int bw, int bh);
+// 8UC3 image arguments, on RcArgs (rc_args.h).  who, what: the entry point and the argument, for the text
 int rc_img3_check(const char* who, const char* what, const uint8_t* p, size_t step, int w, int h);   // RC_EINVAL: null, empty, step < 3 w
+// an input and an output of its own size that may not overlap it: the form of both, then the overlap (RC_EINVAL)
+int rc_img3_pair(const char* who, const char* in_name, const uint8_t* in, size_t in_step, int sw, int sh, const char* out_name,
+                 const uint8_t* out, size_t out_step, int dw, int dh);
 int rc_fits_context(const char* who, const rc_ctx* ctx, int w, int h);                                // RC_ESIZE
 // lk_kernels.hip: the two halves of a PyrLK call (pyramid of one image; track), for the tracking stabiliser
 RcLkPyr rc_lk_plan(int w, int h, int win_w, int win_h, int max_level, bool deriv);
@@ -480,13 +482,23 @@ int rc_state_install(RcSlot& s, T& cur, T& fresh, int rc) {
     return rc;
 }
 
+// The head of every entry point that works on an open product: the slot and the product's state on it.  RC_EINVAL for a
+// bad slot, RC_ESTATE while the product is closed.  Selecting the device and waiting for the zeroing stay with the caller
 template <class T>
-int rc_state_reset(rc_ctx* ctx, int stream, T RcSlot::*member, const char* product) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    if (!(s->*member).open) { rc_set_error("%s_reset before %s_open", product, product); return RC_ESTATE; }
+int rc_state_get(rc_ctx* ctx, int stream, T RcSlot::*member, const char* who, RcSlot*& s, T*& st) {
+    if (!(s = rc_slot(ctx, stream))) return RC_EINVAL;
+    st = &(s->*member);
+    if (st->open) return RC_OK;
+    rc_set_error("%s: the product is not open on the slot (its open call comes first)", who);
+    return RC_ESTATE;
+}
+
+template <class T>
+int rc_state_reset(rc_ctx* ctx, int stream, T RcSlot::*member, const char* who) {
+    RcSlot* s; T* st;
+    if (int rc = rc_state_get(ctx, stream, member, who, s, st)) return rc;
     RC_HIP(hipSetDevice(ctx->device));
-    return rc_state_zero(*s, s->*member);
+    return rc_state_zero(*s, *st);
 }
 
 template <class T>

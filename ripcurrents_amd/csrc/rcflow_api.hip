@@ -69,15 +69,15 @@ void rc_fence_free(RcZeroFence& z) {
     z = RcZeroFence();
 }
 
-bool rc_img3_overlap(const uint8_t* a, size_t astep, int aw, int ah, const uint8_t* b, size_t bstep, int bw, int bh) {
-    const uint8_t* ae = a + (size_t)(ah - 1) * astep + (size_t)3 * aw;
-    const uint8_t* be = b + (size_t)(bh - 1) * bstep + (size_t)3 * bw;
-    return a < be && b < ae;
-}
 int rc_img3_check(const char* who, const char* what, const uint8_t* p, size_t step, int w, int h) {
-    if (p && w > 0 && h > 0 && step >= (size_t)3 * w) return RC_OK;
-    rc_set_error("%s: bad image argument %s (a null pointer, an empty size, or a step below 3 * w)", who, what);
-    return RC_EINVAL;
+    return rc_image_check(who, what, p, step, w, h, 3, 1, RC_ARG_IN);
+}
+int rc_img3_pair(const char* who, const char* in_name, const uint8_t* in, size_t in_step, int sw, int sh, const char* out_name,
+                 const uint8_t* out, size_t out_step, int dw, int dh) {
+    RcArgs a(who, sw, sh);
+    a.image(in_name, in, in_step, 3, 1, RC_ARG_IN);
+    a.image(out_name, out, out_step, 3, 1, RC_ARG_OUT, dw, dh);
+    return a.check();
 }
 int rc_fits_context(const char* who, const rc_ctx* ctx, int w, int h) {
     if (w <= ctx->max_w && h <= ctx->max_h) return RC_OK;

@@ -524,49 +524,22 @@ extern "C" int rcflow_regions_open(rc_ctx* ctx, int stream, int w, int h, const 
     return rc_state_install(*s, s->rg, n, rc);
 }
 
-// the byte range [first byte, last byte] of an image argument
-struct RgSpan { const char* what; const char* lo; const char* hi; };
-static RgSpan rg_span(const char* what, const void* p, size_t step, size_t row_bytes, int h) {
-    return {what, (const char*)p, (const char*)p + (size_t)(h - 1) * step + row_bytes};
-}
-
 extern "C" int rcflow_regions_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_mask, size_t mask_step, const float* d_flow_xy,
                                        size_t flow_step, int32_t* d_labels, size_t labels_step, uint8_t* d_mask_out, size_t mask_out_step,
                                        rc_region* d_regions, long long* d_summary) {
     static const char* who = "rcflow_regions_push_dev";
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    RcRegions& g = s->rg;
-    if (!g.open) { rc_set_error("%s before rcflow_regions_open", who); return RC_ESTATE; }
+    RcSlot* s; RcRegions* gp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::rg, who, s, gp)) return rc;
+    RcRegions& g = *gp;
     const int w = g.w, h = g.h;
-    if (!d_mask || mask_step < (size_t)w) { rc_set_error("%s: bad image argument d_mask (a null pointer or a step below w)", who); return RC_EINVAL; }
-    if (d_flow_xy && (flow_step < (size_t)w * 8 || (flow_step & 7) || ((uintptr_t)d_flow_xy & 7))) {
-        rc_set_error("%s: bad flow field argument (8-byte aligned, a step that is a multiple of 8 and at least 8 * w)", who);
-        return RC_EINVAL;
-    }
-    if (d_labels && (labels_step < (size_t)w * 4 || (labels_step & 3) || ((uintptr_t)d_labels & 3))) {
-        rc_set_error("%s: bad image argument d_labels (4-byte aligned, a step that is a multiple of 4 and at least 4 * w)", who);
-        return RC_EINVAL;
-    }
-    if (d_mask_out && mask_out_step < (size_t)w) { rc_set_error("%s: bad image argument d_mask_out (a step below w)", who); return RC_EINVAL; }
-    if (((uintptr_t)d_regions & 7) || ((uintptr_t)d_summary & 7)) { rc_set_error("%s: d_regions and d_summary must be 8-byte aligned", who); return RC_EINVAL; }
-    RgSpan sp[6];
-    int nin = 0, n = 0;
-    sp[n++] = rg_span("d_mask", d_mask, mask_step, (size_t)w, h);
-    if (d_flow_xy) sp[n++] = rg_span("d_flow_xy", d_flow_xy, flow_step, (size_t)w * 8, h);
-    nin = n;
-    if (d_labels) sp[n++] = rg_span("d_labels", d_labels, labels_step, (size_t)w * 4, h);
-    const int imo = d_mask_out ? n : -1;
-    if (d_mask_out) sp[n++] = rg_span("d_mask_out", d_mask_out, mask_out_step, (size_t)w, h);
-    if (d_regions) sp[n++] = rg_span("d_regions", d_regions, 0, (size_t)g.prm.max_regions * sizeof(rc_region), 1);
-    if (d_summary) sp[n++] = rg_span("d_summary", d_summary, 0, 64, 1);
-    for (int i = 0; i < n; i++)
-        for (int j = i + 1 > nin ? i + 1 : nin; j < n; j++) {
-            if (sp[i].hi <= sp[j].lo || sp[j].hi <= sp[i].lo) continue;
-            if (i == 0 && j == imo && d_mask_out == d_mask && mask_out_step == mask_step) continue;   // in place
-            rc_set_error("%s: %s overlaps %s", who, sp[i].what, sp[j].what);
-            return RC_EINVAL;
-        }
+    RcArgs a(who, w, h);
+    const int im = a.image("d_mask", d_mask, mask_step, 1, 1, RC_ARG_IN);
+    a.image("d_flow_xy", d_flow_xy, flow_step, 8, 8, RC_ARG_IN | RC_ARG_OPTIONAL);
+    a.image("d_labels", d_labels, labels_step, 4, 4, RC_ARG_OUT | RC_ARG_OPTIONAL);
+    a.in_place(a.image("d_mask_out", d_mask_out, mask_out_step, 1, 1, RC_ARG_OUT | RC_ARG_OPTIONAL), im);
+    a.array("d_regions", d_regions, (size_t)g.prm.max_regions * sizeof(rc_region), 8, RC_ARG_OUT | RC_ARG_OPTIONAL);
+    a.array("d_summary", d_summary, 64, 8, RC_ARG_OUT | RC_ARG_OPTIONAL);
+    if (a.check()) return RC_EINVAL;
     RC_HIP(hipSetDevice(ctx->device));
     int rc = rc_fence_wait(g.zf, s->cur, true);
     if (rc) return rc;
@@ -609,16 +582,12 @@ extern "C" int rcflow_regions_push_dev(rc_ctx* ctx, int stream, const uint8_t* d
 
 extern "C" int rcflow_regions_prims_dev(rc_ctx* ctx, int stream, uint32_t color, int thickness, int disc_radius, double flow_scale,
                                         rc_draw_prim* d_prims) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    RcRegions& g = s->rg;
-    if (!g.open) { rc_set_error("rcflow_regions_prims_dev before rcflow_regions_open"); return RC_ESTATE; }
-    if (!d_prims || ((uintptr_t)d_prims & 3) || thickness < 1 || thickness > RC_DRAW_MAX_THICKNESS || disc_radius < 0 ||
-        disc_radius > RC_DRAW_COORD_MAX || !(fabs(flow_scale) <= 1.7976931348623157e308)) {
-        rc_set_error("rcflow_regions_prims_dev: d_prims (4-byte aligned), thickness 1..%d, disc_radius 0..%d, a finite flow_scale",
-                     RC_DRAW_MAX_THICKNESS, RC_DRAW_COORD_MAX);
-        return RC_EINVAL;
-    }
+    static const char* who = "rcflow_regions_prims_dev";
+    RcSlot* s; RcRegions* gp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::rg, who, s, gp)) return rc;
+    RcRegions& g = *gp;
+    if (rc_prims_check(who, d_prims, thickness, disc_radius)) return RC_EINVAL;
+    if (!(fabs(flow_scale) <= 1.7976931348623157e308)) { rc_set_error("%s: flow_scale is not finite", who); return RC_EINVAL; }
     RC_HIP(hipSetDevice(ctx->device));
     int rc = rc_fence_wait(g.zf, s->cur, true);
     if (rc) return rc;
@@ -630,10 +599,9 @@ extern "C" int rcflow_regions_prims_dev(rc_ctx* ctx, int stream, uint32_t color,
 }
 
 extern "C" int rcflow_regions_read(rc_ctx* ctx, int stream, rc_region* regions, int cap, int* n, long long summary[8]) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    RcRegions& g = s->rg;
-    if (!g.open) { rc_set_error("rcflow_regions_read before rcflow_regions_open"); return RC_ESTATE; }
+    RcSlot* s; RcRegions* gp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::rg, "rcflow_regions_read", s, gp)) return rc;
+    RcRegions& g = *gp;
     if (cap < 0 || (cap && !regions)) { rc_set_error("rcflow_regions_read: a bad buffer"); return RC_EINVAL; }
     RC_HIP(hipSetDevice(ctx->device));
     int rc = rc_fence_wait(g.zf, s->cur, true);
@@ -653,19 +621,17 @@ extern "C" int rcflow_regions_read(rc_ctx* ctx, int stream, rc_region* regions, 
 }
 
 extern "C" int rcflow_regions_set(rc_ctx* ctx, int stream, int min_area) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    if (!s->rg.open) { rc_set_error("rcflow_regions_set before rcflow_regions_open"); return RC_ESTATE; }
+    RcSlot* s; RcRegions* g;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::rg, "rcflow_regions_set", s, g)) return rc;
     if (min_area < 1) { rc_set_error("rcflow_regions_set: min_area >= 1"); return RC_EINVAL; }
-    s->rg.prm.min_area = min_area;
+    g->prm.min_area = min_area;
     return RC_OK;
 }
 
 extern "C" int rcflow_regions_info(rc_ctx* ctx, int stream, rc_regions_info* info) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    const RcRegions& g = s->rg;
-    if (!g.open) { rc_set_error("no regions state is open on the slot (rcflow_regions_open)"); return RC_ESTATE; }
+    RcSlot* s; RcRegions* gp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::rg, "rcflow_regions_info", s, gp)) return rc;
+    const RcRegions& g = *gp;
     if (!info) return RC_OK;
     memset(info, 0, sizeof(*info));
     info->w = g.w; info->h = g.h; info->connectivity = g.prm.connectivity; info->min_area = g.prm.min_area;
@@ -676,5 +642,5 @@ extern "C" int rcflow_regions_info(rc_ctx* ctx, int stream, rc_regions_info* inf
     return RC_OK;
 }
 
-extern "C" int rcflow_regions_reset(rc_ctx* ctx, int stream) { return rc_state_reset(ctx, stream, &RcSlot::rg, "rcflow_regions"); }
+extern "C" int rcflow_regions_reset(rc_ctx* ctx, int stream) { return rc_state_reset(ctx, stream, &RcSlot::rg, "rcflow_regions_reset"); }
 extern "C" int rcflow_regions_close(rc_ctx* ctx, int stream) { return rc_state_close(ctx, stream, &RcSlot::rg); }

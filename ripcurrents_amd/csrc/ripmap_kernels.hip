@@ -380,28 +380,26 @@ extern "C" int rcflow_ripmap_open(rc_ctx* ctx, int stream, int w, int h, int win
 }
 
 extern "C" int rcflow_ripmap_set(rc_ctx* ctx, int stream, double min_opposition_cos2, double min_cell_mag) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    if (!s->rm.open) { rc_set_error("rcflow_ripmap_set before rcflow_ripmap_open"); return RC_ESTATE; }
+    RcSlot* s; RcRipMap* m;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::rm, "rcflow_ripmap_set", s, m)) return rc;
     if (!(min_opposition_cos2 >= 0. && min_opposition_cos2 < 1.) || !(min_cell_mag >= 0. && min_cell_mag < 1e6)) {
         rc_set_error("rcflow_ripmap_set: min_opposition_cos2 must be in [0, 1), min_cell_mag in [0, 1e6)");
         return RC_EINVAL;
     }
-    s->rm.K = min_opposition_cos2;
-    s->rm.M = min_cell_mag;
+    m->K = min_opposition_cos2;
+    m->M = min_cell_mag;
     return RC_OK;
 }
 
-extern "C" int rcflow_ripmap_reset(rc_ctx* ctx, int stream) { return rc_state_reset(ctx, stream, &RcSlot::rm, "rcflow_ripmap"); }
+extern "C" int rcflow_ripmap_reset(rc_ctx* ctx, int stream) { return rc_state_reset(ctx, stream, &RcSlot::rm, "rcflow_ripmap_reset"); }
 extern "C" int rcflow_ripmap_close(rc_ctx* ctx, int stream) { return rc_state_close(ctx, stream, &RcSlot::rm); }
 
 extern "C" int rcflow_ripmap_info(rc_ctx* ctx, int stream, int* w, int* h, int* window, int* grid_x, int* grid_y, int* source,
                                   int* flags, double* min_opposition_cos2, double* min_cell_mag, long long* frames_pushed,
                                   size_t* device_bytes) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    const RcRipMap& m = s->rm;
-    if (!m.open) { rc_set_error("no opposing-flow map is open on the slot (rcflow_ripmap_open)"); return RC_ESTATE; }
+    RcSlot* s; RcRipMap* mp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::rm, "rcflow_ripmap_info", s, mp)) return rc;
+    const RcRipMap& m = *mp;
     if (w) *w = m.w;
     if (h) *h = m.h;
     if (window) *window = m.window;
@@ -418,10 +416,10 @@ extern "C" int rcflow_ripmap_info(rc_ctx* ctx, int stream, int* w, int* h, int* 
 
 extern "C" int rcflow_ripmap_push_dev(rc_ctx* ctx, int stream, const float* d_flow_xy, size_t flow_step, uint8_t* d_hsv,
                                       size_t hsv_step, uint8_t* d_mask, size_t mask_step, float* d_cells, double* d_summary) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    RcRipMap& m = s->rm;
-    if (!m.open) { rc_set_error("rcflow_ripmap_push_dev before rcflow_ripmap_open"); return RC_ESTATE; }
+    static const char* who = "rcflow_ripmap_push_dev";
+    RcSlot* s; RcRipMap* mp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::rm, who, s, mp)) return rc;
+    RcRipMap& m = *mp;
     if (!d_flow_xy) {                                     // the slot's resident field (rcflow_stream_flow_ptr)
         if (!s->flow_w) { rc_set_error("no flow field is resident on the slot yet"); return RC_ESTATE; }
         if (s->flow_w != m.w || s->flow_h != m.h) {
@@ -430,12 +428,11 @@ extern "C" int rcflow_ripmap_push_dev(rc_ctx* ctx, int stream, const float* d_fl
         }
         d_flow_xy = (const float*)s->stage_flow.p;
         flow_step = (size_t)m.w * 8;
-    } else if (flow_step < (size_t)m.w * 8 || (flow_step & 7)) {
-        rc_set_error("bad flow field argument");
+    } else if (rc_image_check(who, "d_flow_xy", d_flow_xy, flow_step, m.w, m.h, 8, 8, RC_ARG_IN | RC_ARG_ANY_BASE)) {
         return RC_EINVAL;
     }
-    if (d_hsv && rc_img3_check("rcflow_ripmap_push_dev", "d_hsv", d_hsv, hsv_step, m.w, m.h)) return RC_EINVAL;
-    if (d_mask && mask_step < (size_t)m.w) { rc_set_error("rcflow_ripmap_push_dev: mask_step is below w"); return RC_EINVAL; }
+    if (rc_image_check(who, "d_hsv", d_hsv, hsv_step, m.w, m.h, 3, 1, RC_ARG_OUT | RC_ARG_OPTIONAL)) return RC_EINVAL;
+    if (rc_image_check(who, "d_mask", d_mask, mask_step, m.w, m.h, 1, 1, RC_ARG_OUT | RC_ARG_OPTIONAL)) return RC_EINVAL;
     if (m.source == 1 && !s->an.thr.p) { rc_set_error("source 1 reads UPPER from the slot's analysis state (rcflow_analysis_reset)"); return RC_ESTATE; }
     RC_HIP(hipSetDevice(ctx->device));
     int rc = rc_fence_wait(m.zf, s->cur, true);
@@ -479,11 +476,11 @@ extern "C" int rcflow_ripmap_push_dev(rc_ctx* ctx, int stream, const float* d_fl
 }
 
 extern "C" int rcflow_ripmap_mean_dev(rc_ctx* ctx, int stream, float* d_mean_xy, size_t mean_step) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    RcRipMap& m = s->rm;
-    if (!m.open) { rc_set_error("rcflow_ripmap_mean_dev before rcflow_ripmap_open"); return RC_ESTATE; }
-    if (!d_mean_xy || mean_step < (size_t)m.w * 8) { rc_set_error("bad mean field argument"); return RC_EINVAL; }
+    static const char* who = "rcflow_ripmap_mean_dev";
+    RcSlot* s; RcRipMap* mp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::rm, who, s, mp)) return rc;
+    RcRipMap& m = *mp;
+    if (rc_image_check(who, "d_mean_xy", d_mean_xy, mean_step, m.w, m.h, 8, 1, RC_ARG_OUT)) return RC_EINVAL;
     RC_HIP(hipSetDevice(ctx->device));
     int rc = rc_fence_wait(m.zf, s->cur, true);
     if (rc) return rc;
@@ -493,10 +490,9 @@ extern "C" int rcflow_ripmap_mean_dev(rc_ctx* ctx, int stream, float* d_mean_xy,
 
 extern "C" int rcflow_ripmap_read(rc_ctx* ctx, int stream, float* cells, double* summary, long long* sums,
                                   long long* frames_pushed) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    RcRipMap& m = s->rm;
-    if (!m.open) { rc_set_error("rcflow_ripmap_read before rcflow_ripmap_open"); return RC_ESTATE; }
+    RcSlot* s; RcRipMap* mp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::rm, "rcflow_ripmap_read", s, mp)) return rc;
+    RcRipMap& m = *mp;
     RC_HIP(hipSetDevice(ctx->device));
     int rc = rc_fence_wait(m.zf, s->cur, true);
     if (rc) return rc;

@@ -542,7 +542,7 @@ extern "C" int rcflow_warp_translate_bgr_dev(rc_ctx* ctx, int stream, const uint
         return RC_EINVAL;
     }
     if (rc_fits_context(who, ctx, w, h)) return RC_ESIZE;
-    if (rc_img3_overlap(d_out, out_step, w, h, d_bgr, step, w, h)) { rc_set_error("%s: d_out overlaps the frame (the warp is not in place)", who); return RC_EINVAL; }
+    if (rc_img3_pair(who, "d_bgr", d_bgr, step, w, h, "d_out", d_out, out_step, w, h)) return RC_EINVAL;   // the warp is not in place
     RC_HIP(hipSetDevice(ctx->device));
     StWarpArgs a;
     memset(&a, 0, sizeof(a));
@@ -727,10 +727,11 @@ static int fs_push_tracks(rc_ctx* ctx, RcSlot& s, const uint8_t* d_frame, size_t
 
 extern "C" int rcflow_framestab_read_tracks(rc_ctx* ctx, int stream, double T[9], int* model_used, int* n_valid, int* n_inliers, float* pts,
                                             uint8_t* inlier, int* scores, int cap, int* cells, long long* frames_pushed) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    RcFrameStab& f = s->fs;
-    if (!f.open || !f.tracks) { rc_set_error("rcflow_framestab_read_tracks: the slot has no state opened by rcflow_framestab_open_tracks"); return RC_ESTATE; }
+    static const char* who = "rcflow_framestab_read_tracks";
+    RcSlot* s; RcFrameStab* fp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::fs, who, s, fp)) return rc;
+    RcFrameStab& f = *fp;
+    if (!f.tracks) { rc_set_error("%s: the slot's state was not opened by rcflow_framestab_open_tracks", who); return RC_ESTATE; }
     RC_HIP(hipSetDevice(ctx->device));
     int rc = rc_fence_wait(f.zf, s->cur, false);
     if (rc) return rc;
@@ -765,15 +766,14 @@ extern "C" int rcflow_framestab_read_tracks(rc_ctx* ctx, int stream, double T[9]
     return RC_OK;
 }
 
-extern "C" int rcflow_framestab_reset(rc_ctx* ctx, int stream) { return rc_state_reset(ctx, stream, &RcSlot::fs, "rcflow_framestab"); }
+extern "C" int rcflow_framestab_reset(rc_ctx* ctx, int stream) { return rc_state_reset(ctx, stream, &RcSlot::fs, "rcflow_framestab_reset"); }
 extern "C" int rcflow_framestab_close(rc_ctx* ctx, int stream) { return rc_state_close(ctx, stream, &RcSlot::fs); }
 
 extern "C" int rcflow_framestab_info(rc_ctx* ctx, int stream, int* w, int* h, int roi[4], int dft_size[2], int* launches_per_push,
                                      long long* frames_pushed, size_t* device_bytes) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    const RcFrameStab& f = s->fs;
-    if (!f.open) { rc_set_error("no stabilisation state is open on the slot (rcflow_framestab_open)"); return RC_ESTATE; }
+    RcSlot* s; RcFrameStab* fp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::fs, "rcflow_framestab_info", s, fp)) return rc;
+    const RcFrameStab& f = *fp;
     if (w) *w = f.w;
     if (h) *h = f.h;
     if (roi) { roi[0] = f.rx; roi[1] = f.ry; roi[2] = f.rw; roi[3] = f.rh; }
@@ -789,10 +789,9 @@ extern "C" int rcflow_framestab_info(rc_ctx* ctx, int stream, int* w, int* h, in
 }
 
 extern "C" int rcflow_framestab_info_multi(rc_ctx* ctx, int stream, int* n, int* rois, int cap, int* model, double* min_response, int* flags) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    const RcFrameStab& f = s->fs;
-    if (!f.open) { rc_set_error("no stabilisation state is open on the slot (rcflow_framestab_open)"); return RC_ESTATE; }
+    RcSlot* s; RcFrameStab* fp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::fs, "rcflow_framestab_info_multi", s, fp)) return rc;
+    const RcFrameStab& f = *fp;
     const int np = f.tracks ? 0 : (f.n ? f.n : 1);
     if (n) *n = np;
     if (rois)
@@ -840,12 +839,10 @@ static int fs_correlate(rc_ctx* ctx, RcSlot& s, const uint8_t* d_frame, size_t s
 extern "C" int rcflow_framestab_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_frame, size_t step, uint8_t* d_out, size_t out_step,
                                          double* d_result) {
     static const char* who = "rcflow_framestab_push_dev";
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    RcFrameStab& f = s->fs;
-    if (!f.open) { rc_set_error("%s before rcflow_framestab_open", who); return RC_ESTATE; }
-    if (rc_img3_check(who, "d_frame", d_frame, step, f.w, f.h) || rc_img3_check(who, "d_out", d_out, out_step, f.w, f.h)) return RC_EINVAL;
-    if (rc_img3_overlap(d_out, out_step, f.w, f.h, d_frame, step, f.w, f.h)) { rc_set_error("%s: d_out overlaps the frame (the warp is not in place)", who); return RC_EINVAL; }
+    RcSlot* s; RcFrameStab* fp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::fs, who, s, fp)) return rc;
+    RcFrameStab& f = *fp;
+    if (rc_img3_pair(who, "d_frame", d_frame, step, f.w, f.h, "d_out", d_out, out_step, f.w, f.h)) return RC_EINVAL;   // the warp is not in place
     RC_HIP(hipSetDevice(ctx->device));
     int rc = rc_fence_wait(f.zf, s->cur, true);
     if (rc) return rc;
@@ -885,10 +882,9 @@ extern "C" int rcflow_framestab_push_dev(rc_ctx* ctx, int stream, const uint8_t*
 
 extern "C" int rcflow_framestab_read_motion(rc_ctx* ctx, int stream, double motion[6], int* model_used, int* patches_used, double* shifts,
                                             long long* frames_pushed) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    RcFrameStab& f = s->fs;
-    if (!f.open) { rc_set_error("rcflow_framestab_read_motion before rcflow_framestab_open"); return RC_ESTATE; }
+    RcSlot* s; RcFrameStab* fp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::fs, "rcflow_framestab_read_motion", s, fp)) return rc;
+    RcFrameStab& f = *fp;
     RC_HIP(hipSetDevice(ctx->device));
     int rc = rc_fence_wait(f.zf, s->cur, false);
     if (rc) return rc;
@@ -925,10 +921,9 @@ extern "C" int rcflow_framestab_read_motion(rc_ctx* ctx, int stream, double moti
 }
 
 extern "C" int rcflow_framestab_read(rc_ctx* ctx, int stream, double result[3], long long* frames_pushed) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    RcFrameStab& f = s->fs;
-    if (!f.open) { rc_set_error("rcflow_framestab_read before rcflow_framestab_open"); return RC_ESTATE; }
+    RcSlot* s; RcFrameStab* fp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::fs, "rcflow_framestab_read", s, fp)) return rc;
+    RcFrameStab& f = *fp;
     RC_HIP(hipSetDevice(ctx->device));
     int rc = rc_fence_wait(f.zf, s->cur, false);
     if (rc) return rc;

@@ -318,15 +318,14 @@ extern "C" int rcflow_timex_open(rc_ctx* ctx, int stream, int w, int h, int wind
     return rc_state_install(*s, s->tx, t, rc);
 }
 
-extern "C" int rcflow_timex_reset(rc_ctx* ctx, int stream) { return rc_state_reset(ctx, stream, &RcSlot::tx, "rcflow_timex"); }
+extern "C" int rcflow_timex_reset(rc_ctx* ctx, int stream) { return rc_state_reset(ctx, stream, &RcSlot::tx, "rcflow_timex_reset"); }
 extern "C" int rcflow_timex_close(rc_ctx* ctx, int stream) { return rc_state_close(ctx, stream, &RcSlot::tx); }
 
 extern "C" int rcflow_timex_info(rc_ctx* ctx, int stream, int* w, int* h, int* window, int* products,
                                  long long* frames_pushed, size_t* device_bytes) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    const RcTimex& t = s->tx;
-    if (!t.open) { rc_set_error("no time-exposure state is open on the slot (rcflow_timex_open)"); return RC_ESTATE; }
+    RcSlot* s; RcTimex* tp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::tx, "rcflow_timex_info", s, tp)) return rc;
+    const RcTimex& t = *tp;
     if (w) *w = t.w;
     if (h) *h = t.h;
     if (window) *window = t.window;
@@ -338,27 +337,23 @@ extern "C" int rcflow_timex_info(rc_ctx* ctx, int stream, int* w, int* h, int* w
 
 extern "C" int rcflow_timex_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_frame, size_t step, uint8_t* const d_out[4],
                                      const size_t out_step[4]) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    RcTimex& t = s->tx;
-    if (!t.open) { rc_set_error("rcflow_timex_push_dev before rcflow_timex_open"); return RC_ESTATE; }
     static const char* who = "rcflow_timex_push_dev";
-    if (rc_img3_check(who, "d_frame", d_frame, step, t.w, t.h)) return RC_EINVAL;
+    static const char* const names[4] = {"d_out[0]", "d_out[1]", "d_out[2]", "d_out[3]"};
+    RcSlot* s; RcTimex* tp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::tx, who, s, tp)) return rc;
+    RcTimex& t = *tp;
     uint8_t* out[4] = {nullptr, nullptr, nullptr, nullptr};
     size_t ostep[4] = {0, 0, 0, 0};
+    // rows are converted in place in registers, but another product's launch still has to read the frame: an output is apart from it
+    RcArgs a(who, t.w, t.h);
+    a.image("d_frame", d_frame, step, 3, 1, RC_ARG_IN);
     for (int k = 0; k < 4; k++) {
         if (!d_out || !d_out[k]) continue;
-        if (!(t.products & (1 << k))) { rc_set_error("d_out[%d] given for a product that is not open", k); return RC_EINVAL; }
-        if (rc_img3_check(who, "d_out[k]", d_out[k], out_step ? out_step[k] : 0, t.w, t.h)) return RC_EINVAL;
-        out[k] = d_out[k]; ostep[k] = out_step[k];
-        // rows are converted in place in registers, but another product's launch still has to read the frame
-        if (rc_img3_overlap(out[k], ostep[k], t.w, t.h, d_frame, step, t.w, t.h)) { rc_set_error("d_out[%d] overlaps the frame", k); return RC_EINVAL; }
-        for (int j = 0; j < k; j++)
-            if (out[j] && rc_img3_overlap(out[k], ostep[k], t.w, t.h, out[j], ostep[j], t.w, t.h)) {
-                rc_set_error("d_out[%d] overlaps d_out[%d]", k, j);
-                return RC_EINVAL;
-            }
+        if (!(t.products & (1 << k))) { rc_set_error("%s: d_out[%d] given for a product that is not open", who, k); return RC_EINVAL; }
+        out[k] = d_out[k]; ostep[k] = out_step ? out_step[k] : 0;
+        a.image(names[k], out[k], ostep[k], 3, 1, RC_ARG_OUT);
     }
+    if (a.check()) return RC_EINVAL;
     RC_HIP(hipSetDevice(ctx->device));
     int rc = rc_fence_wait(t.zf, s->cur, true);
     if (rc) return rc;

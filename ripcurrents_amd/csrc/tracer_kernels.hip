@@ -218,10 +218,9 @@ extern "C" int rcflow_tracers_open(rc_ctx* ctx, int stream, int w, int h, const 
 }
 
 extern "C" int rcflow_tracers_add(rc_ctx* ctx, int stream, int kind, const float* xy, int n) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    RcTracers& t = s->tr;
-    if (!t.open) { rc_set_error("rcflow_tracers_add before rcflow_tracers_open"); return RC_ESTATE; }
+    RcSlot* s; RcTracers* tp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::tr, "rcflow_tracers_add", s, tp)) return rc;
+    RcTracers& t = *tp;
     if (kind < RC_TRACER_STREAK || kind > RC_TRACER_CLOUD || !xy || n < 1 || (kind == RC_TRACER_STREAK && n != 1)) {
         rc_set_error("rcflow_tracers_add: kind 0..2, n >= 1 points (a streakline: its generation point alone)");
         return RC_EINVAL;
@@ -254,13 +253,13 @@ extern "C" int rcflow_tracers_add(rc_ctx* ctx, int stream, int kind, const float
 
 extern "C" int rcflow_tracers_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_gray, size_t gray_step, const float* d_flow_xy,
                                        size_t flow_step, uint8_t* d_canvas, size_t canvas_step) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    RcTracers& t = s->tr;
-    if (!t.open) { rc_set_error("rcflow_tracers_push_dev before rcflow_tracers_open"); return RC_ESTATE; }
+    static const char* who = "rcflow_tracers_push_dev";
+    RcSlot* s; RcTracers* tp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::tr, who, s, tp)) return rc;
+    RcTracers& t = *tp;
     const bool lk = t.prm.mover == RC_TRACERS_LK;
     if (lk) {
-        if (!d_gray || gray_step < (size_t)t.w) { rc_set_error("rcflow_tracers_push_dev: bad gray frame argument"); return RC_EINVAL; }
+        if (rc_image_check(who, "d_gray", d_gray, gray_step, t.w, t.h, 1, 1, RC_ARG_IN)) return RC_EINVAL;
     } else if (!d_flow_xy) {                              // the slot's resident field (rcflow_stream_flow_ptr)
         if (!s->flow_w) { rc_set_error("no flow field is resident on the slot yet"); return RC_ESTATE; }
         if (s->flow_w != t.w || s->flow_h != t.h) {
@@ -269,11 +268,10 @@ extern "C" int rcflow_tracers_push_dev(rc_ctx* ctx, int stream, const uint8_t* d
         }
         d_flow_xy = (const float*)s->stage_flow.p;
         flow_step = (size_t)t.w * 8;
-    } else if (flow_step < (size_t)t.w * 8 || (flow_step & 7)) {
-        rc_set_error("bad flow field argument");
+    } else if (rc_image_check(who, "d_flow_xy", d_flow_xy, flow_step, t.w, t.h, 8, 8, RC_ARG_IN | RC_ARG_ANY_BASE)) {
         return RC_EINVAL;
     }
-    if (d_canvas && rc_img3_check("rcflow_tracers_push_dev", "d_canvas", d_canvas, canvas_step, t.w, t.h)) return RC_EINVAL;
+    if (rc_image_check(who, "d_canvas", d_canvas, canvas_step, t.w, t.h, 3, 1, RC_ARG_OUT | RC_ARG_OPTIONAL)) return RC_EINVAL;
     if (d_canvas && (t.w > RC_DRAW_COORD_MAX + 1 || t.h > RC_DRAW_COORD_MAX + 1)) {
         rc_set_error("rcflow_tracers_push_dev: drawing takes frames up to %d x %d", RC_DRAW_COORD_MAX + 1, RC_DRAW_COORD_MAX + 1);
         return RC_ESIZE;
@@ -333,10 +331,9 @@ extern "C" int rcflow_tracers_push_dev(rc_ctx* ctx, int stream, const uint8_t* d
 }
 
 extern "C" int rcflow_tracers_read(rc_ctx* ctx, int stream, int line, float* xy, int cap, int* n, long long* skipped) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    RcTracers& t = s->tr;
-    if (!t.open) { rc_set_error("rcflow_tracers_read before rcflow_tracers_open"); return RC_ESTATE; }
+    RcSlot* s; RcTracers* tp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::tr, "rcflow_tracers_read", s, tp)) return rc;
+    RcTracers& t = *tp;
     if (line < 0 || line >= (int)t.lines.size() || cap < 0 || (cap && !xy)) { rc_set_error("rcflow_tracers_read: no line %d, or a bad buffer", line); return RC_EINVAL; }
     int off = 0;
     for (int l = 0; l < line; l++) off += tr_line_count(t, t.lines[l]);
@@ -361,19 +358,17 @@ extern "C" int rcflow_tracers_read(rc_ctx* ctx, int stream, int line, float* xy,
 }
 
 extern "C" int rcflow_tracers_prims(rc_ctx* ctx, int stream, const rc_draw_prim** d_prims, int* n) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    if (!s->tr.open) { rc_set_error("no tracer session is open on the slot (rcflow_tracers_open)"); return RC_ESTATE; }
-    if (d_prims) *d_prims = (const rc_draw_prim*)s->tr.prims.p;
-    if (n) *n = s->tr.nprims;
+    RcSlot* s; RcTracers* t;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::tr, "rcflow_tracers_prims", s, t)) return rc;
+    if (d_prims) *d_prims = (const rc_draw_prim*)t->prims.p;
+    if (n) *n = t->nprims;
     return RC_OK;
 }
 
 extern "C" int rcflow_tracers_info(rc_ctx* ctx, int stream, rc_tracers_info* info) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    const RcTracers& t = s->tr;
-    if (!t.open) { rc_set_error("no tracer session is open on the slot (rcflow_tracers_open)"); return RC_ESTATE; }
+    RcSlot* s; RcTracers* tp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::tr, "rcflow_tracers_info", s, tp)) return rc;
+    const RcTracers& t = *tp;
     if (!info) return RC_OK;
     memset(info, 0, sizeof(*info));
     info->w = t.w; info->h = t.h; info->mover = t.prm.mover;
@@ -386,5 +381,5 @@ extern "C" int rcflow_tracers_info(rc_ctx* ctx, int stream, rc_tracers_info* inf
     return RC_OK;
 }
 
-extern "C" int rcflow_tracers_reset(rc_ctx* ctx, int stream) { return rc_state_reset(ctx, stream, &RcSlot::tr, "rcflow_tracers"); }
+extern "C" int rcflow_tracers_reset(rc_ctx* ctx, int stream) { return rc_state_reset(ctx, stream, &RcSlot::tr, "rcflow_tracers_reset"); }
 extern "C" int rcflow_tracers_close(rc_ctx* ctx, int stream) { return rc_state_close(ctx, stream, &RcSlot::tr); }

@@ -381,48 +381,24 @@ extern "C" int rcflow_tracks_open(rc_ctx* ctx, int stream, int w, int h, const r
     return rc_state_install(*s, s->tk, n, rc);
 }
 
-// the byte range [first byte, last byte] of an argument
-struct TkSpan { const char* what; const char* lo; const char* hi; };
-static TkSpan tk_span(const char* what, const void* p, size_t step, size_t row_bytes, int h) {
-    return {what, (const char*)p, (const char*)p + (size_t)(h - 1) * step + row_bytes};
-}
-
 extern "C" int rcflow_tracks_push_dev(rc_ctx* ctx, int stream, const int32_t* d_labels, size_t labels_step, const rc_region* d_regions,
                                       const long long* d_regions_summary, rc_track* d_tracks, int32_t* d_track_of_label, uint8_t* d_mask_out,
                                       size_t mask_out_step, long long* d_summary) {
     static const char* who = "rcflow_tracks_push_dev";
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    RcTracks& g = s->tk;
-    if (!g.open) { rc_set_error("%s before rcflow_tracks_open", who); return RC_ESTATE; }
+    RcSlot* s; RcTracks* gp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::tk, who, s, gp)) return rc;
+    RcTracks& g = *gp;
     const int w = g.w, h = g.h, NR = g.prm.max_regions, NT = g.prm.max_tracks;
     if (!d_labels || !d_regions || !d_regions_summary) { rc_set_error("%s: d_labels, d_regions and d_regions_summary are needed", who); return RC_EINVAL; }
-    if (labels_step < (size_t)w * 4 || (labels_step & 3) || ((uintptr_t)d_labels & 3)) {
-        rc_set_error("%s: bad image argument d_labels (4-byte aligned, a step that is a multiple of 4 and at least 4 * w)", who);
-        return RC_EINVAL;
-    }
-    if (d_mask_out && mask_out_step < (size_t)w) { rc_set_error("%s: bad image argument d_mask_out (a step below w)", who); return RC_EINVAL; }
-    if (((uintptr_t)d_regions & 7) || ((uintptr_t)d_regions_summary & 7) || ((uintptr_t)d_tracks & 7) || ((uintptr_t)d_summary & 7) ||
-        ((uintptr_t)d_track_of_label & 3)) {
-        rc_set_error("%s: d_regions, d_regions_summary, d_tracks and d_summary must be 8-byte aligned, d_track_of_label 4-byte aligned", who);
-        return RC_EINVAL;
-    }
-    TkSpan sp[7];
-    int n = 0;
-    sp[n++] = tk_span("d_labels", d_labels, labels_step, (size_t)w * 4, h);
-    sp[n++] = tk_span("d_regions", d_regions, 0, (size_t)NR * sizeof(rc_region), 1);
-    sp[n++] = tk_span("d_regions_summary", d_regions_summary, 0, 64, 1);
-    const int nin = n;
-    if (d_tracks) sp[n++] = tk_span("d_tracks", d_tracks, 0, (size_t)NT * sizeof(rc_track), 1);
-    if (d_track_of_label) sp[n++] = tk_span("d_track_of_label", d_track_of_label, 0, ((size_t)NR + 1) * 4, 1);
-    if (d_mask_out) sp[n++] = tk_span("d_mask_out", d_mask_out, mask_out_step, (size_t)w, h);
-    if (d_summary) sp[n++] = tk_span("d_summary", d_summary, 0, 64, 1);
-    for (int i = 0; i < n; i++)
-        for (int j = i + 1 > nin ? i + 1 : nin; j < n; j++) {
-            if (sp[i].hi <= sp[j].lo || sp[j].hi <= sp[i].lo) continue;
-            rc_set_error("%s: %s overlaps %s", who, sp[i].what, sp[j].what);
-            return RC_EINVAL;
-        }
+    RcArgs a(who, w, h);
+    a.image("d_labels", d_labels, labels_step, 4, 4, RC_ARG_IN);
+    a.array("d_regions", d_regions, (size_t)NR * sizeof(rc_region), 8, RC_ARG_IN);
+    a.array("d_regions_summary", d_regions_summary, 64, 8, RC_ARG_IN);
+    a.array("d_tracks", d_tracks, (size_t)NT * sizeof(rc_track), 8, RC_ARG_OUT | RC_ARG_OPTIONAL);
+    a.array("d_track_of_label", d_track_of_label, ((size_t)NR + 1) * 4, 4, RC_ARG_OUT | RC_ARG_OPTIONAL);
+    a.image("d_mask_out", d_mask_out, mask_out_step, 1, 1, RC_ARG_OUT | RC_ARG_OPTIONAL);
+    a.array("d_summary", d_summary, 64, 8, RC_ARG_OUT | RC_ARG_OPTIONAL);
+    if (a.check()) return RC_EINVAL;
     RC_HIP(hipSetDevice(ctx->device));
     int rc = rc_fence_wait(g.zf, s->cur, true);
     if (rc) return rc;
@@ -454,16 +430,11 @@ extern "C" int rcflow_tracks_push_dev(rc_ctx* ctx, int stream, const int32_t* d_
 }
 
 extern "C" int rcflow_tracks_prims_dev(rc_ctx* ctx, int stream, uint32_t color, int thickness, int disc_radius, rc_draw_prim* d_prims) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    RcTracks& g = s->tk;
-    if (!g.open) { rc_set_error("rcflow_tracks_prims_dev before rcflow_tracks_open"); return RC_ESTATE; }
-    if (!d_prims || ((uintptr_t)d_prims & 3) || thickness < 1 || thickness > RC_DRAW_MAX_THICKNESS || disc_radius < 0 ||
-        disc_radius > RC_DRAW_COORD_MAX) {
-        rc_set_error("rcflow_tracks_prims_dev: d_prims (4-byte aligned), thickness 1..%d, disc_radius 0..%d", RC_DRAW_MAX_THICKNESS,
-                     RC_DRAW_COORD_MAX);
-        return RC_EINVAL;
-    }
+    static const char* who = "rcflow_tracks_prims_dev";
+    RcSlot* s; RcTracks* gp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::tk, who, s, gp)) return rc;
+    RcTracks& g = *gp;
+    if (rc_prims_check(who, d_prims, thickness, disc_radius)) return RC_EINVAL;
     RC_HIP(hipSetDevice(ctx->device));
     int rc = rc_fence_wait(g.zf, s->cur, true);
     if (rc) return rc;
@@ -475,10 +446,9 @@ extern "C" int rcflow_tracks_prims_dev(rc_ctx* ctx, int stream, uint32_t color, 
 }
 
 extern "C" int rcflow_tracks_read(rc_ctx* ctx, int stream, rc_track* tracks, int cap, int32_t* footprint, long long summary[8]) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    RcTracks& g = s->tk;
-    if (!g.open) { rc_set_error("rcflow_tracks_read before rcflow_tracks_open"); return RC_ESTATE; }
+    RcSlot* s; RcTracks* gp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::tk, "rcflow_tracks_read", s, gp)) return rc;
+    RcTracks& g = *gp;
     if (cap < 0 || (cap && !tracks)) { rc_set_error("rcflow_tracks_read: a bad buffer"); return RC_EINVAL; }
     RC_HIP(hipSetDevice(ctx->device));
     int rc = rc_fence_wait(g.zf, s->cur, true);
@@ -495,10 +465,9 @@ extern "C" int rcflow_tracks_read(rc_ctx* ctx, int stream, rc_track* tracks, int
 }
 
 extern "C" int rcflow_tracks_info(rc_ctx* ctx, int stream, rc_tracks_info* info) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    const RcTracks& g = s->tk;
-    if (!g.open) { rc_set_error("no tracks state is open on the slot (rcflow_tracks_open)"); return RC_ESTATE; }
+    RcSlot* s; RcTracks* gp;
+    if (int rc = rc_state_get(ctx, stream, &RcSlot::tk, "rcflow_tracks_info", s, gp)) return rc;
+    const RcTracks& g = *gp;
     if (!info) return RC_OK;
     memset(info, 0, sizeof(*info));
     info->w = g.w; info->h = g.h; info->prm = g.prm;
@@ -508,5 +477,5 @@ extern "C" int rcflow_tracks_info(rc_ctx* ctx, int stream, rc_tracks_info* info)
     return RC_OK;
 }
 
-extern "C" int rcflow_tracks_reset(rc_ctx* ctx, int stream) { return rc_state_reset(ctx, stream, &RcSlot::tk, "rcflow_tracks"); }
+extern "C" int rcflow_tracks_reset(rc_ctx* ctx, int stream) { return rc_state_reset(ctx, stream, &RcSlot::tk, "rcflow_tracks_reset"); }
 extern "C" int rcflow_tracks_close(rc_ctx* ctx, int stream) { return rc_state_close(ctx, stream, &RcSlot::tk); }

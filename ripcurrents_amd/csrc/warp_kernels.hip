@@ -120,8 +120,7 @@ static int wp_check(const char* who, rc_ctx* ctx, const uint8_t* d_bgr, size_t s
     for (int i = 0; i < nm; i++)
         if (!isfinite(M[i])) { rc_set_error("%s: matrix entry %d is not finite", who, i); return RC_EINVAL; }
     if (rc_fits_context(who, ctx, sw, sh) || rc_fits_context(who, ctx, dw, dh)) return RC_ESIZE;
-    if (rc_img3_overlap(d_out, out_step, dw, dh, d_bgr, step, sw, sh)) { rc_set_error("%s: d_out overlaps the frame (the warp is not in place)", who); return RC_EINVAL; }
-    return RC_OK;
+    return rc_img3_pair(who, "d_bgr", d_bgr, step, sw, sh, "d_out", d_out, out_step, dw, dh);   // the warp is not in place
 }
 
 extern "C" int rcflow_warp_affine_bgr_dev(rc_ctx* ctx, int stream, const uint8_t* d_bgr, size_t step, int sw, int sh, uint8_t* d_out,

@@ -314,9 +314,27 @@ def test_every_refusal_returns_its_code_and_queues_nothing(ctx, orc):
     # nothing was queued and nothing changed: the third push gives what the statement gives
     ctx.motion_push(g, timestamp=3.0, **out.kw())
     compare(ctx.motion_read(), out.host(), ref.push(frames[2], 3.0), "(after the refusals)")
+    # an accepted boundary: the mask begins at the first byte after the frame's range, in one allocation
+    one = torch.full((2 * h * w + 64,), SENTINEL, dtype=torch.uint8, device="cuda")
+    tg, tm = one[:h * w].view(h, w), one[h * w:2 * h * w].view(h, w)
+    assert tm.data_ptr() == tg.data_ptr() + (h - 1) * tg.stride(0) + w
+    tg.copy_(dev_frame(frames[3]))
+    ctx.motion_push(tg, timestamp=4.0, mask=tm)
+    touching, want4 = ctx.motion_read(), ref.push(frames[3], 4.0)
+    compare(touching, None, want4, "(the mask right after the frame)")
+    assert np.array_equal(tm.cpu().numpy(), want4["mask"]) and np.array_equal(tg.cpu().numpy(), frames[3]) and (one[2 * h * w:] == SENTINEL).all()
+    ctx.motion_open(w, h, grid=(7, 5), stream=1, **TEX)         # the same four pushes with separate allocations, on the other slot
+    sep = torch.zeros((h, w), dtype=torch.uint8, device="cuda")
+    for t in range(4):
+        ctx.motion_push(dev_frame(frames[t]), timestamp=t + 1.0, mask=sep, stream=1)
+    apart = ctx.motion_read(stream=1)
+    ctx.motion_close(stream=1)
+    assert np.array_equal(tm.cpu().numpy(), sep.cpu().numpy()) and touching["silhouette"] == apart["silhouette"]
+    records_equal(touching["cells"], apart["cells"], "(touching against separate allocations)")
+    records_equal(touching["frame"], apart["frame"], "(touching against separate allocations)")
     ctx.motion_push(dev_frame(frames[3]), timestamp=2.0 ** 24)      # the largest stamp
     with pytest.raises(RcflowError) as e:
-        ctx.motion_push(g)                                      # automatic: pushes + 1 = 5 is not greater
+        ctx.motion_push(g)                                      # automatic: pushes + 1 = 6 is not greater
     assert e.value.code == EINVAL
     ctx.motion_close()
 

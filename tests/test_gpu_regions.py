@@ -280,7 +280,19 @@ def test_set_reset_reopen_refusals(ctx):
         assert rc == code, "refusal %d gave %d" % (i, rc)
         after = (ctx.regions_info(), ctx.regions_read())
         assert after[0] == before[0] and np.array_equal(after[1][0], before[1][0]) and after[1][1] == before[1][1], "refusal %d changed the state" % i
-    push_and_check(ctx, m, 4, 20, 32, opened=True, pushes=3)
+    want = push_and_check(ctx, m, 4, 20, 32, opened=True, pushes=3)
+    # an accepted boundary: the labels begin at the first byte after the mask's range, in one allocation
+    one = torch.full((5 * h * w + 64,), FENCE, dtype=torch.uint8, device="cuda")
+    tm, tl = one[:h * w].view(h, w), one[h * w:5 * h * w].view(torch.int32).view(h, w)
+    assert tl.data_ptr() == tm.data_ptr() + (h - 1) * tm.stride(0) + w
+    tm.copy_(dm)
+    ctx.regions_push(tm, labels=tl)
+    touching = ctx.regions_read()
+    ctx.regions_push(dm, labels=lab)                          # the same with separate allocations
+    apart = ctx.regions_read()
+    assert np.array_equal(tl.cpu().numpy(), lab.cpu().numpy()) and np.array_equal(tl.cpu().numpy(), want["labels"])
+    assert np.array_equal(tm.cpu().numpy(), m) and (one[5 * h * w:] == FENCE).all()
+    assert touching[0].tobytes() == apart[0].tobytes() and dict(touching[1], pushes=5) == apart[1] and touching[1]["pushes"] == 4
     ctx.regions_reset()
     assert ctx.regions_info()["pushes"] == 0 and ctx.regions_info()["min_area"] == 20
     rec, summ = ctx.regions_read()
