@@ -8,8 +8,8 @@
 //   (flow_iter_kernels.hip holds A3-A6)
 // Data layout in HBM (all fp32):
 //   I_k   [slot][h][w]            float
-//   RA_k  [slot][h][w]            float4 (y, x, yy, xx)  -- one 16-B load per pixel/texel
-//   RB_k  [slot][h][w]            float  (xy)
+//   RA_k  [slot][h][w]            float4 (y, x, yy, xx)  -- one 16-B load per pixel/texel; stored at 1/2 of upstream's R
+//   RB_k  [slot][h][w]            float  (xy)            -- stored at 1/4 (option "exact": unscaled)
 //   flow  [pair][h][w]            float2 (x, y)  == CV_32FC2
 // Compiled with -ffp-contract=off; fused multiply-adds are written explicitly (RC_FMA)
 // in the convolution loops and nowhere else, so the gather / matrix / resize arithmetic
@@ -476,12 +476,18 @@ void rc_launch_pyr(const RcPyrArgs& a, int frames, size_t lds, hipStream_t s) {
 
 // ===================================================================== A2 polyexp
 // 64x32 output tile per 512-thread block.  Separable: horizontal pass first (three sums
-// per pixel: g, x*g, x*x*g), staged through LDS, vertical pass last so that every lane of
-// a wave owns one column and all LDS reads and the 16-B global stores are conflict-free
-// and coalesced.  Each thread of the vertical pass produces 4 rows from a register
-// window.  A per-tile constant is subtracted before the sums and its exact contribution
-// (pk.kdc) is added back in the double-precision epilogue: the yy/xx coefficients are
-// differences of O(100) sums, and this keeps them at fp32's best.
+// per pixel), staged through LDS, vertical pass last so that every lane of a wave owns one
+// column and all LDS reads and the 16-B global stores are conflict-free and coalesced.
+// Each thread of the vertical pass produces 4 rows from a register window.
+// The constants upstream multiplies the six filter products with are folded into the taps
+// on the host (RcPolyK::qh, xga, xgb; the planes come out at their stored scale, (y, x, yy,
+// xx) / 2 and xy / 4):
+//   h0 = g_h     h1 = xga_h     h2 = qh_h
+//   y = xga_v(h0)   yy = qh_v(h0)   |   x = g_v(h1)   xy = xgb_v(h1)   |   xx = g_v(h2)
+// five vertical filters instead of six, and yy / xx no longer formed per pixel as the
+// difference ig03 b1 + ig33 b5 of O(100) sums: that cancellation happens once, in double,
+// inside qh.  A per-tile constant is subtracted before the sums and its exact contribution
+// to yy and xx (dc * pk.kdch) is added back in the epilogue.
 // PYR = 1 (with U8): the block also writes its part of pyramid scales 1 and 2 (exact half / quarter
 // sizes) from the staged bytes, so those scales need neither their own launch nor their own pass
 // over the frame; the staging then covers virtual rows ty0 - R - 1 .. and (border tiles) virtual
@@ -790,13 +796,13 @@ __device__ __forceinline__ void rc_polyexp_body(const RcPolyArgs& a, int bx, int
 #pragma unroll
         for (int p = 0; p < 4; p++) {
             const int c = RP + p;
-            float s0 = v[c] * a.pk.g[0], s1 = 0.f, s2 = 0.f;
+            float s0 = v[c] * a.pk.g[0], s1 = 0.f, s2 = v[c] * a.pk.qh[0];
 #pragma unroll
             for (int k = 1; k <= R; k++) {
                 float sm = v[c + k] + v[c - k], df = v[c + k] - v[c - k];
                 s0 = RC_FMA(sm, a.pk.g[k], s0);
-                s1 = RC_FMA(df, a.pk.xg[k], s1);
-                s2 = RC_FMA(sm, a.pk.xxg[k], s2);
+                s1 = RC_FMA(df, a.pk.xga[k], s1);
+                s2 = RC_FMA(sm, a.pk.qh[k], s2);
             }
             h0[p] = s0; h1[p] = s1; h2[p] = s2;
         }
@@ -811,54 +817,54 @@ __device__ __forceinline__ void rc_polyexp_body(const RcPolyArgs& a, int bx, int
         // ---- vertical pass on the matrix cores: Out(16 x 16) = T(16 x K) x In(K x 16) per wave, T the
         // banded Toeplitz matrix of a vertical filter (K = 16 + 2R rows in, rounded up to 4s).
         // v_mfma_f32_16x16x4_f32 is an exact f32 fmaf chain in k order, runs beside the VALU
-        // (which is what bounds this kernel) and takes the 6 filter x plane products
-        //   b1 = g.h0  b3 = xg.h0  b5 = xxg.h0 | b2 = g.h1  b6 = xg.h1 | b4 = g.h2.
+        // (which is what bounds this kernel) and takes the 5 filter x plane products
+        //   b3 = xga.h0  b5 = qh.h0 | b2 = g.h1  b6 = xgb.h1 | b4 = g.h2.
         // Lane l holds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15]; D: row 4 (l >> 4) + r, col l & 15.
         static_assert(TH == 32, "8 waves = 2 x 4 sub-tiles of 16 x 16");
         constexpr int KS = (16 + 2 * R + 3) / 4;
-        float* wt = hs + 3 * INH * TW;                  // [3][2R+1] taps by offset -R..R: g, xg (odd), xxg
-        if (tid < 3 * (2 * R + 1)) {
-            const int f3 = tid / (2 * R + 1), t = tid - f3 * (2 * R + 1), k = t < R ? R - t : t - R;
-            wt[tid] = f3 == 0 ? a.pk.g[k] : (f3 == 1 ? (t < R ? -a.pk.xg[k] : (t == R ? 0.f : a.pk.xg[k])) : a.pk.xxg[k]);
+        float* wt = hs + 3 * INH * TW;                  // [4][2R+1] taps by offset -R..R: g, xga (odd), qh, xgb (odd)
+        if (tid < 4 * (2 * R + 1)) {
+            const int f4 = tid / (2 * R + 1), t = tid - f4 * (2 * R + 1), k = t < R ? R - t : t - R;
+            const float odd = f4 == 1 ? a.pk.xga[k] : a.pk.xgb[k];
+            wt[tid] = f4 == 0 ? a.pk.g[k] : (f4 == 2 ? a.pk.qh[k] : (t < R ? -odd : (t == R ? 0.f : odd)));
         }
         __syncthreads();
         const int lane = tid & 63, wv = tid >> 6;
         const int i = lane & 15, kk = lane >> 4;
         const int y0 = 16 * (wv >> 2), x0 = 16 * (wv & 3);
-        rc_f32x4 c1 = {0, 0, 0, 0}, c2 = c1, c3 = c1, c4 = c1, c5 = c1, c6 = c1;
+        rc_f32x4 c2 = {0, 0, 0, 0}, c3 = c2, c4 = c2, c5 = c2, c6 = c2;
 #pragma unroll
         for (int s = 0; s < KS; s++) {
             const int t = 4 * s + kk - i;               // tap index of A[i][4s + kk]
             const bool on = (unsigned)t <= (unsigned)(2 * R);
             const float wg = on ? wt[t] : 0.f, wx = on ? wt[2 * R + 1 + t] : 0.f, wq = on ? wt[2 * (2 * R + 1) + t] : 0.f;
+            const float wy = on ? wt[3 * (2 * R + 1) + t] : 0.f;
             const int row = min(y0 + 4 * s + kk, INH - 1);          // rows past the band have zero weight
             const float* bp = hs + row * TW + x0 + i;
             const float p0 = bp[0], p1 = bp[INH * TW], p2 = bp[2 * INH * TW];
-            c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wg, p0, c1, 0, 0, 0);
             c3 = __builtin_amdgcn_mfma_f32_16x16x4f32(wx, p0, c3, 0, 0, 0);
             c5 = __builtin_amdgcn_mfma_f32_16x16x4f32(wq, p0, c5, 0, 0, 0);
             c2 = __builtin_amdgcn_mfma_f32_16x16x4f32(wg, p1, c2, 0, 0, 0);
-            c6 = __builtin_amdgcn_mfma_f32_16x16x4f32(wx, p1, c6, 0, 0, 0);
+            c6 = __builtin_amdgcn_mfma_f32_16x16x4f32(wy, p1, c6, 0, 0, 0);
             c4 = __builtin_amdgcn_mfma_f32_16x16x4f32(wg, p2, c4, 0, 0, 0);
         }
         const int gx = tx0 + x0 + i;
         if (gx < w) {
             float4* RA = a.RA + (size_t)slot * a.R_slot_stride;
             float* RB = a.RB + (size_t)slot * a.R_slot_stride;
-            const double dck = (double)dc * a.pk.kdc;
-            const float ig11f = (float)a.pk.ig11, ig55f = (float)a.pk.ig55;
+            const float dck = (float)((double)dc * a.pk.kdch);
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 const int gy = ty0 + y0 + 4 * kk + r;
                 if (gy < h) {
                     float4 ra;
-                    ra.x = c3[r] * ig11f;
-                    ra.y = c2[r] * ig11f;
-                    ra.z = (float)((double)c1[r] * a.pk.ig03 + (double)c5[r] * a.pk.ig33 + dck);
-                    ra.w = (float)((double)c1[r] * a.pk.ig03 + (double)c4[r] * a.pk.ig33 + dck);
+                    ra.x = c3[r];
+                    ra.y = c2[r];
+                    ra.z = c5[r] + dck;
+                    ra.w = c4[r] + dck;
                     size_t p = (size_t)gy * w + gx;
                     RA[p] = ra;
-                    RB[p] = c6[r] * ig55f;
+                    RB[p] = c6[r];
                 }
             }
         }
@@ -869,22 +875,21 @@ __device__ __forceinline__ void rc_polyexp_body(const RcPolyArgs& a, int bx, int
     static_assert(NR * (RC_POLY_BLOCK / 64) == TH, "tile height must be a multiple of 8");
     const int x = tid & 63, o0 = (tid >> 6) * NR;
     constexpr int NW = NR + 2 * R;
-    float b1[NR], b2[NR], b3[NR], b4[NR], b5[NR], b6[NR];
+    float b2[NR], b3[NR], b4[NR], b5[NR], b6[NR];
     {
         float c[NW];
 #pragma unroll
         for (int q = 0; q < NW; q++) c[q] = hs[(o0 + q) * TW + x];
 #pragma unroll
         for (int o = 0; o < NR; o++) {
-            float s1 = c[o + R] * a.pk.g[0], s3 = 0.f, s5 = 0.f;
+            float s3 = 0.f, s5 = c[o + R] * a.pk.qh[0];
 #pragma unroll
             for (int k = 1; k <= R; k++) {
                 float sm = c[o + R + k] + c[o + R - k], df = c[o + R + k] - c[o + R - k];
-                s1 = RC_FMA(sm, a.pk.g[k], s1);
-                s3 = RC_FMA(df, a.pk.xg[k], s3);
-                s5 = RC_FMA(sm, a.pk.xxg[k], s5);
+                s3 = RC_FMA(df, a.pk.xga[k], s3);
+                s5 = RC_FMA(sm, a.pk.qh[k], s5);
             }
-            b1[o] = s1; b3[o] = s3; b5[o] = s5;
+            b3[o] = s3; b5[o] = s5;
         }
     }
     {
@@ -897,7 +902,7 @@ __device__ __forceinline__ void rc_polyexp_body(const RcPolyArgs& a, int bx, int
 #pragma unroll
             for (int k = 1; k <= R; k++) {
                 s2 = RC_FMA(c[o + R + k] + c[o + R - k], a.pk.g[k], s2);
-                s6 = RC_FMA(c[o + R + k] - c[o + R - k], a.pk.xg[k], s6);
+                s6 = RC_FMA(c[o + R + k] - c[o + R - k], a.pk.xgb[k], s6);
             }
             b2[o] = s2; b6[o] = s6;
         }
@@ -918,31 +923,23 @@ __device__ __forceinline__ void rc_polyexp_body(const RcPolyArgs& a, int bx, int
     if (gx < w) {
         float4* RA = a.RA + (size_t)slot * a.R_slot_stride;
         float* RB = a.RB + (size_t)slot * a.R_slot_stride;
-        const double dck = (double)dc * a.pk.kdc;
-        const float ig11f = (float)a.pk.ig11, ig55f = (float)a.pk.ig55;
-        // yy / xx = b1 ig03 + b5 ig33 + dc kdc with the three double constants split into float pairs (hi + lo): the hi
-        // chain carries the value, the lo chain the constants' rounding -- eight fp32 operations per pixel instead of
-        // twelve at fp64 rate; what is left is the rounding of the hi chain's two partial sums (<= 1 ulp each).
-        // Measured against the double epilogue: -2 % of the kernel, parity statistics unchanged.
-        const float ig03h = (float)a.pk.ig03, ig03l = (float)(a.pk.ig03 - (double)ig03h);
-        const float ig33h = (float)a.pk.ig33, ig33l = (float)(a.pk.ig33 - (double)ig33h);
-        const float dckh = (float)dck, dckl = (float)(dck - (double)dckh);
+        // the removed constant's share of yy and xx (the odd filters do not see it), at the stored scale
+        const float dck = (float)((double)dc * a.pk.kdch);
 #pragma unroll
         for (int o = 0; o < NR; o++) {
             int gy = ty0 + o0 + o;
             if (gy < h) {
                 float4 ra;
-                ra.x = b3[o] * ig11f;
-                ra.y = b2[o] * ig11f;
-                const float th = RC_FMA(b1[o], ig03h, dckh), tl = RC_FMA(b1[o], ig03l, dckl);
-                ra.z = RC_FMA(b5[o], ig33h, th) + RC_FMA(b5[o], ig33l, tl);
-                ra.w = RC_FMA(b4[o], ig33h, th) + RC_FMA(b4[o], ig33l, tl);
+                ra.x = b3[o];
+                ra.y = b2[o];
+                ra.z = b5[o] + dck;
+                ra.w = b4[o] + dck;
                 size_t p = (size_t)gy * w + gx;
                 // streaming stores: R is written once here and read by the flow kernels much later (the
                 // batch's R does not fit the caches), and this kernel is bound by its writes (-1.4 % per pair)
                 __builtin_nontemporal_store(ra.x, &RA[p].x); __builtin_nontemporal_store(ra.y, &RA[p].y);
                 __builtin_nontemporal_store(ra.z, &RA[p].z); __builtin_nontemporal_store(ra.w, &RA[p].w);
-                __builtin_nontemporal_store(b6[o] * ig55f, &RB[p]);
+                __builtin_nontemporal_store(b6[o], &RB[p]);
             }
         }
     }
@@ -977,11 +974,12 @@ __global__ __launch_bounds__(RC_POLY_BLOCK) void k_polyexp_multi(RcPolyArgs a0, 
     }
 }
 
+static_assert(3 * sizeof(RcPolyArgs) + 10 * sizeof(int) <= 4096, "k_polyexp_multi's arguments fit the kernel-argument segment");
 template <int R>
 static void launch_polyexp_multi_t(const RcPolyArgs* a, int nlev, int frames, hipStream_t s) {
     constexpr int RP = (R + 3) & ~3;
     constexpr int INW = 64 + 2 * RP, INH = 32 + 2 * R;
-    constexpr size_t lds_hs = sizeof(float) * (3 * (size_t)INH * 64 + 3 * (2 * R + 1)), lds_ub = (size_t)(INH + 2) * (INW + 8);
+    constexpr size_t lds_hs = sizeof(float) * (3 * (size_t)INH * 64 + 4 * (2 * R + 1)), lds_ub = (size_t)(INH + 2) * (INW + 8);
     constexpr size_t lds = sizeof(float) * (size_t)INH * INW + (lds_hs > lds_ub ? lds_hs : lds_ub);
     RC_ALLOW_LDS((k_polyexp_multi<R>), lds);
     int gx[3] = {1, 1, 1}, gy[3] = {1, 1, 1}, n[3] = {0, 0, 0};
@@ -1009,7 +1007,7 @@ template <int R, int U8, int TH, int MFMA, int PYR = 0>
 static void launch_polyexp_th(const RcPolyArgs& a, int frames, hipStream_t s) {
     constexpr int RP = (R + 3) & ~3;
     constexpr int INW = 64 + 2 * RP, INH = TH + 2 * R;
-    constexpr size_t lds_hs = sizeof(float) * (3 * (size_t)INH * 64 + 3 * (2 * R + 1)), lds_ub = (size_t)(INH + 2) * (INW + 8);
+    constexpr size_t lds_hs = sizeof(float) * (3 * (size_t)INH * 64 + 4 * (2 * R + 1)), lds_ub = (size_t)(INH + 2) * (INW + 8);
     constexpr size_t lds = sizeof(float) * (size_t)INH * INW + (lds_hs > lds_ub ? lds_hs : lds_ub);
     RC_ALLOW_LDS((k_polyexp<R, U8, TH, MFMA, PYR>), lds);
     dim3 grid((a.w + 63) / 64, (a.h + TH - 1) / TH, frames);
@@ -1059,24 +1057,28 @@ void rc_launch_polyexp(const RcPolyArgs& a, int frames, hipStream_t s) {
 }
 
 // ===================================================================== test helpers
-__global__ void k_pack_R5(const float* R5, float4* RA, float* RB, int n) {
+// sa / sb: the stored scale of the (y, x, yy, xx) / xy planes over upstream's R: 1/2 and 1/4 for
+// the fast kernels, 1 for option "exact"; powers of two, so packing and unpacking are exact
+__global__ void k_pack_R5(const float* R5, float4* RA, float* RB, int n, float sa, float sb) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {
-        RA[i] = make_float4(R5[5 * i], R5[5 * i + 1], R5[5 * i + 2], R5[5 * i + 3]);
-        RB[i] = R5[5 * i + 4];
+        RA[i] = make_float4(R5[5 * i] * sa, R5[5 * i + 1] * sa, R5[5 * i + 2] * sa, R5[5 * i + 3] * sa);
+        RB[i] = R5[5 * i + 4] * sb;
     }
 }
-__global__ void k_unpack_R5(const float4* RA, const float* RB, float* R5, int n) {
+__global__ void k_unpack_R5(const float4* RA, const float* RB, float* R5, int n, float ua, float ub) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {
         float4 v = RA[i];
-        R5[5 * i] = v.x; R5[5 * i + 1] = v.y; R5[5 * i + 2] = v.z; R5[5 * i + 3] = v.w;
-        R5[5 * i + 4] = RB[i];
+        R5[5 * i] = v.x * ua; R5[5 * i + 1] = v.y * ua; R5[5 * i + 2] = v.z * ua; R5[5 * i + 3] = v.w * ua;
+        R5[5 * i + 4] = RB[i] * ub;
     }
 }
-void rc_launch_pack_R5(const float* R5, float4* RA, float* RB, int n, hipStream_t s) {
-    hipLaunchKernelGGL(k_pack_R5, dim3((n + 255) / 256), dim3(256), 0, s, R5, RA, RB, n);
+void rc_launch_pack_R5(const float* R5, float4* RA, float* RB, int n, int fast_scale, hipStream_t s) {
+    hipLaunchKernelGGL(k_pack_R5, dim3((n + 255) / 256), dim3(256), 0, s, R5, RA, RB, n, fast_scale ? 0.5f : 1.f,
+                       fast_scale ? 0.25f : 1.f);
 }
-void rc_launch_unpack_R5(const float4* RA, const float* RB, float* R5, int n, hipStream_t s) {
-    hipLaunchKernelGGL(k_unpack_R5, dim3((n + 255) / 256), dim3(256), 0, s, RA, RB, R5, n);
+void rc_launch_unpack_R5(const float4* RA, const float* RB, float* R5, int n, int fast_scale, hipStream_t s) {
+    hipLaunchKernelGGL(k_unpack_R5, dim3((n + 255) / 256), dim3(256), 0, s, RA, RB, R5, n, fast_scale ? 2.f : 1.f,
+                       fast_scale ? 4.f : 1.f);
 }

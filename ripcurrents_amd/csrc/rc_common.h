@@ -218,5 +218,5 @@ struct RcFlowAreaArgs {
 void rc_launch_flow_area_init(const RcFlowAreaArgs& a, int pairs, hipStream_t s);
 
 // interleave helpers for the stage-level test entry points
-void rc_launch_pack_R5(const float* R5, float4* RA, float* RB, int n, hipStream_t s);
-void rc_launch_unpack_R5(const float4* RA, const float* RB, float* R5, int n, hipStream_t s);
+void rc_launch_pack_R5(const float* R5, float4* RA, float* RB, int n, int fast_scale, hipStream_t s);
+void rc_launch_unpack_R5(const float4* RA, const float* RB, float* R5, int n, int fast_scale, hipStream_t s);

@@ -154,6 +154,17 @@ int rc_plan_prepare_poly(int n, double sigma, int exact_taps, RcPolyK& pk) {
         s2 += (k ? 2. : 0.) * xxg[k];
     }
     pk.kdc = sg * sg * pk.ig03 + sg * s2 * pk.ig33;
+    // the derived taps (rc_plan.h): ig03 g + ig33 xxg cancels in double here, once, instead of per pixel in the kernel
+    memset(pk.qh, 0, sizeof(pk.qh));
+    memset(pk.xga, 0, sizeof(pk.xga));
+    memset(pk.xgb, 0, sizeof(pk.xgb));
+    const double sa = pk.ig11 * 0.5, sb = (pk.ig55 * 0.25) / sa;
+    for (int k = 0; k <= pk.n_eff; k++) {
+        pk.qh[k] = (float)(0.5 * (pk.ig03 * (double)g[k] + pk.ig33 * (double)xxg[k]));
+        pk.xga[k] = (float)((double)xg[k] * sa);
+        pk.xgb[k] = (float)((double)xg[k] * sb);
+    }
+    pk.kdch = 0.5 * pk.kdc;
     return RC_OK;
 }
 

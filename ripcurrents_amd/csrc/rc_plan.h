@@ -31,6 +31,13 @@ struct RcPolyK {
     double kdc;   // coefficient of the removed DC term in the yy/xx outputs
     int n;        // requested radius
     int n_eff;    // radius actually evaluated
+    // Derived taps of the fast expansion: the constants its outputs are multiplied with, folded into
+    // the filters.  Each is formed in double from the values above and rounded to float once; the outputs come out at the
+    // stored scale of the fast R planes ((y, x, yy, xx) / 2, xy / 4: DESIGN.md section 3).
+    float qh[RC_MAX_POLY_N + 1];    // (ig03 g + ig33 xxg) / 2: yy = qh_v(g_h), xx = g_v(qh_h)
+    float xga[RC_MAX_POLY_N + 1];   // xg ig11 / 2: y = xga_v(g_h), x = g_v(xga_h)
+    float xgb[RC_MAX_POLY_N + 1];   // xg (ig55 / 4) / (ig11 / 2): xy = xgb_v(xga_h)
+    double kdch;                    // kdc / 2
 };
 
 // Window of FarnebackUpdateFlow_*: box (scale = 1/bs^2) or Gaussian (float taps).

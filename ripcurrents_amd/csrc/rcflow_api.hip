@@ -335,6 +335,18 @@ extern "C" int rcflow_debug_plan_poly(int n, double sigma, int exact_taps, float
     *kdc = pk.kdc;
     return RC_OK;
 }
+// the derived taps of the fast expansion (RcPolyK::qh, xga, xgb: taps 0..n; kdch)
+extern "C" int rcflow_debug_plan_poly_folded(int n, double sigma, int exact_taps, float* qh, float* xga, float* xgb, double* kdch) {
+    if (n < 1 || n > RC_MAX_POLY_N || !(sigma >= 0) || !qh || !xga || !xgb || !kdch) return RC_EINVAL;
+    RcPolyK pk;
+    const int rc = rc_plan_prepare_poly(n, sigma, exact_taps, pk);
+    if (rc) return rc;
+    memcpy(qh, pk.qh, (n + 1) * sizeof(float));
+    memcpy(xga, pk.xga, (n + 1) * sizeof(float));
+    memcpy(xgb, pk.xgb, (n + 1) * sizeof(float));
+    *kdch = pk.kdch;
+    return RC_OK;
+}
 extern "C" int rcflow_debug_plan_pyr_kernel(int ksize, double sigma, float* taps) {
     if (ksize < 1 || ksize > 1023 || !(sigma >= 0) || !taps) return RC_EINVAL;
     rc_plan_gaussian_kernel(ksize, sigma, taps);
@@ -1457,7 +1469,7 @@ extern "C" int rcflow_stage_polyexp_dev(rc_ctx* ctx, int stream, const float* d_
     if ((rc = rc_plan_prepare_poly(poly_n, poly_sigma, ctx->exact_taps || ctx->exact == 1, qa.pk))) return rc;
     if (ctx->exact == 1) rc_launch_exact_polyexp(qa, 1, s->cur);
     else rc_launch_polyexp(qa, 1, s->cur);
-    rc_launch_unpack_R5(qa.RA, qa.RB, d_R5, (int)n, s->cur);
+    rc_launch_unpack_R5(qa.RA, qa.RB, d_R5, (int)n, ctx->exact != 1, s->cur);   // d_R5 is upstream's R in both builds
     RC_HIP(hipGetLastError());
     return RC_OK;
 }
@@ -1476,8 +1488,9 @@ extern "C" int rcflow_stage_flow_iter_dev(rc_ctx* ctx, int stream, const float* 
     if ((rc = rc_buf_ensure(s->stage_f32[1], 2 * n * sizeof(float)))) return rc;
     float4* RA = (float4*)s->stage_f32[0].p;
     float* RB = (float*)s->stage_f32[1].p;
-    rc_launch_pack_R5(d_R0, RA, RB, (int)n, s->cur);
-    rc_launch_pack_R5(d_R1, RA + n, RB + n, (int)n, s->cur);
+    // d_R0 / d_R1 are upstream's R; the fast kernels read the planes at their stored scale
+    rc_launch_pack_R5(d_R0, RA, RB, (int)n, ctx->exact != 1, s->cur);
+    rc_launch_pack_R5(d_R1, RA + n, RB + n, (int)n, ctx->exact != 1, s->cur);
     RcWindow win;
     rc_plan_window(winsize, flags, win);
     if (ctx->exact == 1) {
