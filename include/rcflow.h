@@ -1140,6 +1140,93 @@ int rcflow_motion_close(rc_ctx* ctx, int stream);
 /* never blocks; RC_ESTATE when nothing is open */
 int rcflow_motion_info(rc_ctx* ctx, int stream, rc_motion_info* info);
 
+/* ------------------------------------------------------------------ flow map and FTLE: Lagrangian ridges from a field ring
+ * "Where did the water that is here come from, over the last T frames", as a per-pixel number a detector can threshold: the
+ * finite-time Lyapunov exponent of the flow map over a sliding window of fields.  In backward time its ridges are the
+ * attracting lines along which foam and sediment collect, the feeder and the neck of a rip.  The reference has no such
+ * product (its streamline_field, ripcurrents_module.cpp:608-648, integrates forward from the first frame for ever); the
+ * sampler and the Euler step are its own, and RC_FTLE_FORWARD over fields that all fit the window is bit for bit what
+ * rcflow_advect_field_dev leaves after the same fields with iterations 1 and UPPER +inf.  tests/_ftle_ref.py states the
+ * following in numpy.  All fp32 unless stated, each operation rounded on its own (no fused multiply-add).
+ *
+ *  State: a ring of the last `window` fields; n = min(pushes, window) of them are held.
+ *  1. Flow map ("ftle@1").  A particle starts at every pixel (xo, yo) with displacement D = (0, 0), alive, steps = 0.
+ *     RC_FTLE_FORWARD visits the held fields oldest to newest with sdt = dt, RC_FTLE_BACKWARD newest to oldest with
+ *     sdt = -dt.  At each field, while the particle is alive: x = D.x + xo, y = D.y + yo; the bilinear sample (dx, dy) of
+ *     the field at (x, y) exactly as the streamline sampler takes it (ripcurrents_module.cpp:494-508): indices (int)floorf(.)
+ *     as x86 converts (NaN and out of range: INT_MIN), rejected when xind < 1 || yind < 1 || xind + 2 > w || yind + 2 > h,
+ *     the weights, the four products and the three additions in its order.  The particle stops for good when the sample is
+ *     rejected or dx or dy is not finite; else D.x = D.x + dx * sdt, D.y = D.y + dy * sdt (one multiply, one add each) and
+ *     steps += 1.  A stopped particle keeps its D.  There is no UPPER cut-off.  D is always finite.
+ *  2. Deformation ("ftle@2"), s = spacing.  Pixel (x, y) is VALID when s <= x < w - s, s <= y < h - s and the pixel and its
+ *     four neighbours at +-s in x and in y all have steps == n.  inv = 1.0f / (float)(2 s); E, W, S, N the neighbours at
+ *     x + s, x - s, y + s, y - s:
+ *       a = 1 + (D_E.x - D_W.x) * inv    b = (D_S.x - D_N.x) * inv    c = (D_E.y - D_W.y) * inv    d = 1 + (D_S.y - D_N.y) * inv
+ *       c11 = a*a + c*c    c12 = a*b + c*d    c22 = b*b + d*d    m = (c11 + c22) * 0.5f    q = (c11 - c22) * 0.5f
+ *       lam = m + sqrtf(q*q + c12*c12)                 the largest eigenvalue of the Cauchy-Green tensor
+ *       ftle = (float)(log((double)lam) / (double)(2 n))      per frame: the caller multiplies by frames per second.
+ *     The logarithm is the device's, in double: its last-place error moves the float by at most one unit in the last place.
+ *     Displacements near the top of the float range (a field value like 1e30 met at the last step) can overflow the
+ *     products: lam is then +inf, or NaN, which is stored as the one pattern 0x7fc00000 in lam and in ftle.  Where the
+ *     pixel is not valid lam, ftle and mask are 0.
+ *  3. Mask (8UC1, 255 / 0): valid && lam >= lam_thr, lam_thr = (float)exp(2.0 * n * threshold), computed on the host in
+ *     double for every push: decided on lam, never on the logarithm.  It is what rcflow_regions_push_dev takes.
+ *  4. Picture (8UC3): entry i of rcflow_jet_lut, i = rint(ftle / (float)vis_max * 255) saturated to 0..255 (NaN: 0); black
+ *     where the pixel is not valid.
+ *  5. Summary, 8 int64: n | valid pixels | mask pixels | particles with steps < n | the bits of the largest lam over the
+ *     valid pixels as uint32 (NaN excepted; 0 for none) | pushes since open / reset | 0 | 0. */
+#define RC_FTLE_FORWARD 0
+#define RC_FTLE_BACKWARD 1
+#define RC_FTLE_MAX_WINDOW 256
+#define RC_FTLE_MAX_SPACING 16
+#define RC_FTLE_MAX_RING_BYTES (4ull << 30)
+#define RC_FTLE_LAUNCHES 3         /* of a push that computes; a push with no output is one */
+typedef struct rc_ftle_params {
+    int window;             /* 1..RC_FTLE_MAX_WINDOW fields */
+    int direction;          /* RC_FTLE_FORWARD, RC_FTLE_BACKWARD */
+    float dt;               /* finite, > 0: frames per field */
+    int spacing;            /* 1..RC_FTLE_MAX_SPACING: half-width of the central differences */
+    double threshold;       /* finite: the mask's bound on ftle, per frame */
+    double vis_max;         /* finite, > 0: the ftle the picture's last colour stands for */
+    int flags;              /* 0 */
+} rc_ftle_params;
+typedef struct rc_ftle_info {
+    int w, h;
+    rc_ftle_params prm;                /* threshold and vis_max as rcflow_ftle_set left them */
+    int launches_per_push;             /* RC_FTLE_LAUNCHES */
+    int held;                          /* n: fields in the ring */
+    long long pushes;                  /* since open / reset */
+    size_t device_bytes;
+} rc_ftle_info;
+/* Allocates everything the slot will ever need: the ring (8 B/px per field, rows of w rounded up to 2 pixels: 16.6 MB a
+ * field at 1080p), the map 8 B/px, steps 4 B/px, lam 4 B/px, the counters.  Re-opening replaces the state; a refused open
+ * leaves the open state as it was.  RC_EINVAL: no parameters, a value outside the ranges above, unknown flag bits; RC_ESIZE
+ * beyond the context's max_w x max_h or a ring above RC_FTLE_MAX_RING_BYTES. */
+int rcflow_ftle_open(rc_ctx* ctx, int stream, int w, int h, const rc_ftle_params* prm);
+/* One flow field (32FC2, w x h, pointer and step multiples of 8, step >= 8 w) into the ring.  Outputs (device memory, each
+ * may be NULL): d_map_xy 32FC2 (the displacements D; 8-byte aligned, step a multiple of 8), d_steps 32SC1, d_lam and d_ftle
+ * 32FC1 (4-byte aligned, steps multiples of 4), d_mask 8UC1, d_vis 8UC3, d_summary 8 int64 (8-byte aligned).  With every
+ * output NULL the push is ONE launch ("ftle@0", the ring slot): push every frame, ask for the map every k-th.  With any
+ * output it is RC_FTLE_LAUNCHES ("ftle@0" .. "ftle@2"), and what they give does not depend on which earlier pushes
+ * computed.  No host synchronisation, no device-to-host copy.  An output whose byte range [first byte, past the last)
+ * overlaps the field's or another output's is RC_EINVAL.  Row padding is never written.  Every refusal is decided before
+ * anything is queued and leaves the state as it was; RC_ESTATE before rcflow_ftle_open. */
+int rcflow_ftle_push_dev(rc_ctx* ctx, int stream, const float* d_flow_xy, size_t flow_step,
+                         float* d_map_xy, size_t map_step, int32_t* d_steps, size_t steps_step,
+                         float* d_lam, size_t lam_step, float* d_ftle, size_t ftle_step,
+                         uint8_t* d_mask, size_t mask_step, uint8_t* d_vis, size_t vis_step, long long* d_summary);
+/* Blocks until the slot's stream has finished; for hosts and tests.  The summary of the last push that computed one; zeros
+ * before that. */
+int rcflow_ftle_read(rc_ctx* ctx, int stream, long long summary[8]);
+/* threshold and vis_max from the next push on; RC_EINVAL as rcflow_ftle_open */
+int rcflow_ftle_set(rc_ctx* ctx, int stream, double threshold, double vis_max);
+/* empties the ring and zeroes the summary and the push count; keeps the allocation; asynchronous, on the slot's stream */
+int rcflow_ftle_reset(rc_ctx* ctx, int stream);
+/* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
+int rcflow_ftle_close(rc_ctx* ctx, int stream);
+/* never blocks; RC_ESTATE when nothing is open */
+int rcflow_ftle_info(rc_ctx* ctx, int stream, rc_ftle_info* info);
+
 /* Display path, ripcurrents.cpp:233-273 (= streamline_displacement / _total_motion / _ratio /
  * _positions, ripcurrents_module.cpp:13-60) on the slot's streamline field (rcflow_advect_field_dev):
  * which 0 = |pt|, 1 = dist, 2 = |pt| / dist; minMaxLoc + convertTo(CV_8UC1, 255/max) +
@@ -1220,7 +1307,7 @@ int rcflow_profile_read(rc_ctx* ctx, int cap, const char** names, int* launches,
 
 /* The same totals under the reference's own bucket names, in the order it prints them (ripcurrents.cpp:103-109,
  * :518-524): farneback, polar, threshold, overlay, erosion, codec, stream ("pathlines").  GPU time of the kernels
- * that do each bucket's work ("overlay" includes the time-exposure images and the 8-bit colour stages, "farneback" the frame stabilisation, the opposing-flow map and the motion templates); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
+ * that do each bucket's work ("overlay" includes the time-exposure images and the 8-bit colour stages, "farneback" the frame stabilisation, the opposing-flow map and the motion templates, "stream" the flow map and FTLE); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
  * classification kernels, booked under "threshold"), "codec" is 0 (video decode is host I/O outside the library).
  * names / ms: RC_PROFILE_BUCKETS entries each (either may be NULL).  Returns RC_PROFILE_BUCKETS. */
 #define RC_PROFILE_BUCKETS 7

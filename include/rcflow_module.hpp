@@ -890,4 +890,67 @@ class MotionTemplates {
     void *d_gray_ = nullptr, *d_vis_ = nullptr, *d_prims_ = nullptr;
 };
 
+
+// Flow map and FTLE on the device (rcflow_ftle_*): a ring of the last `window` flow fields, a particle from every pixel
+// carried through them, the largest eigenvalue of the Cauchy-Green tensor and its logarithm per frame.  Backward (the
+// default) its ridges are where the water gathers.  Host flow fields in; the exponent, the mask and the picture out.
+class Ftle {
+  public:
+    Ftle(Pipeline& pipe, int window = 30, int direction = RC_FTLE_BACKWARD, float dt = 1.f, int spacing = 1, double threshold = 0.1,
+         double vis_max = 0.5)
+        : pipe_(pipe) {
+        rc_ftle_params p{};
+        p.window = window; p.direction = direction; p.dt = dt; p.spacing = spacing; p.threshold = threshold; p.vis_max = vis_max;
+        check(rcflow_ftle_open(pipe.context(), 0, pipe.width(), pipe.height(), &p));
+    }
+    ~Ftle() {
+        (void)rcflow_ftle_close(pipe_.context(), 0);
+        for (void* p : {d_flow_, d_ftle_, d_mask_, d_vis_}) if (p) (void)hipFree(p);
+    }
+    Ftle(const Ftle&) = delete;
+    Ftle& operator=(const Ftle&) = delete;
+
+    // flow: 32FC2 of the pipeline's size.  Each output is optional: ftle 32FC1, mask 8UC1 (255 / 0), picture 8UC3 (JET).
+    // Without any the field only enters the ring (one launch).
+    void push(const Mat& flow, Mat* ftle = nullptr, Mat* mask = nullptr, Mat* picture = nullptr) {
+        const int w = pipe_.width(), h = pipe_.height();
+        if (flow.empty() || flow.rows != h || flow.cols != w || flow.channels != 2 || flow.elem != 4)
+            throw Error(RC_EINVAL, "Ftle::push: the field must be 32FC2 of the pipeline's size");
+        if ((ftle && !fits(*ftle, 1, 4)) || (mask && !fits(*mask, 1, 1)) || (picture && !fits(*picture, 3, 1)))
+            throw Error(RC_EINVAL, "Ftle::push: ftle 32FC1, mask 8UC1, picture 8UC3, each of the pipeline's size");
+        const size_t px = (size_t)w * h;
+        if (!d_flow_) hip_check(hipMalloc(&d_flow_, px * 8), "hipMalloc field");
+        if (ftle && !d_ftle_) hip_check(hipMalloc(&d_ftle_, px * 4), "hipMalloc ftle");
+        if (mask && !d_mask_) hip_check(hipMalloc(&d_mask_, px), "hipMalloc mask");
+        if (picture && !d_vis_) hip_check(hipMalloc(&d_vis_, px * 3), "hipMalloc picture");
+        check(rcflow_sync(pipe_.context(), 0));                  // the last push may still be reading the staging field
+        hip_check(hipMemcpy2D(d_flow_, (size_t)w * 8, flow.data, flow.step, (size_t)w * 8, h, hipMemcpyHostToDevice), "upload field");
+        check(rcflow_ftle_push_dev(pipe_.context(), 0, (const float*)d_flow_, (size_t)w * 8, nullptr, 0, nullptr, 0, nullptr, 0,
+                                   ftle ? (float*)d_ftle_ : nullptr, (size_t)w * 4, mask ? (uint8_t*)d_mask_ : nullptr, (size_t)w,
+                                   picture ? (uint8_t*)d_vis_ : nullptr, (size_t)w * 3, nullptr));
+        if (!ftle && !mask && !picture) return;
+        check(rcflow_sync(pipe_.context(), 0));
+        if (ftle) hip_check(hipMemcpy2D(ftle->data, ftle->step, d_ftle_, (size_t)w * 4, (size_t)w * 4, h, hipMemcpyDeviceToHost), "download ftle");
+        if (mask) hip_check(hipMemcpy2D(mask->data, mask->step, d_mask_, (size_t)w, (size_t)w, h, hipMemcpyDeviceToHost), "download mask");
+        if (picture) hip_check(hipMemcpy2D(picture->data, picture->step, d_vis_, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost), "download picture");
+    }
+    // waits for the pipeline's stream: the summary of the last push that had an output (include/rcflow.h: n, valid, mask,
+    // stopped, bits of the largest eigenvalue, pushes, 0, 0)
+    std::vector<long long> read() {
+        std::vector<long long> s(8);
+        check(rcflow_ftle_read(pipe_.context(), 0, s.data()));
+        return s;
+    }
+    void set(double threshold, double vis_max) { check(rcflow_ftle_set(pipe_.context(), 0, threshold, vis_max)); }
+    rc_ftle_info info() { rc_ftle_info i; check(rcflow_ftle_info(pipe_.context(), 0, &i)); return i; }
+    void reset() { check(rcflow_ftle_reset(pipe_.context(), 0)); }
+
+  private:
+    bool fits(const Mat& m, int channels, int elem) const {
+        return !m.empty() && m.rows == pipe_.height() && m.cols == pipe_.width() && m.channels == channels && m.elem == elem;
+    }
+    Pipeline& pipe_;
+    void *d_flow_ = nullptr, *d_ftle_ = nullptr, *d_mask_ = nullptr, *d_vis_ = nullptr;
+};
+
 }  // namespace rc

@@ -44,6 +44,9 @@ RC_TRACKS_MAX_REGIONS, RC_TRACKS_MAX, RC_TRACKS_LAUNCHES = 1024, 1024, 6
 TRACK_FLAGS = {"seen": 1, "born": 2, "coasting": 4, "ended": 8, "split": 16, "merged": 32, "confirmed": 64}
 # rcflow_motion_*: its one flag, the automatic stamp, the launches of a push
 RC_MOTION_FRESH, RC_MOTION_AUTO_TIME, RC_MOTION_LAUNCHES = 1, -1.0, 3
+# rcflow_ftle_*: the directions, the bounds, the launches of a push that computes
+FTLE_DIRECTIONS = {"forward": 0, "backward": 1}
+RC_FTLE_MAX_WINDOW, RC_FTLE_MAX_SPACING, RC_FTLE_LAUNCHES = 256, 16, 3
 
 ERRORS = {-1: "RC_EINVAL", -2: "RC_ENOMEM", -3: "RC_EHIP", -4: "RC_ENODEV", -5: "RC_ESIZE",
           -6: "RC_ESTATE", -7: "RC_ECOMM"}
@@ -147,6 +150,18 @@ class MotionInfo(C.Structure):
     """rc_motion_info (include/rcflow.h)."""
     _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", MotionParams), ("launches_per_push", C.c_int), ("pushes", C.c_longlong),
                 ("last_timestamp", C.c_double), ("device_bytes", C.c_size_t)]
+
+
+class FtleParams(C.Structure):
+    """rc_ftle_params (include/rcflow.h)."""
+    _fields_ = [("window", C.c_int), ("direction", C.c_int), ("dt", C.c_float), ("spacing", C.c_int), ("threshold", C.c_double),
+                ("vis_max", C.c_double), ("flags", C.c_int)]
+
+
+class FtleInfo(C.Structure):
+    """rc_ftle_info (include/rcflow.h)."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", FtleParams), ("launches_per_push", C.c_int), ("held", C.c_int),
+                ("pushes", C.c_longlong), ("device_bytes", C.c_size_t)]
 
 
 class FitParams(C.Structure):
@@ -305,6 +320,13 @@ SIGNATURES = {
     "rcflow_motion_reset": [_vp, _i],
     "rcflow_motion_close": [_vp, _i],
     "rcflow_motion_info": [_vp, _i, C.POINTER(MotionInfo)],
+    "rcflow_ftle_open": [_vp, _i, _i, _i, C.POINTER(FtleParams)],
+    "rcflow_ftle_push_dev": [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp],
+    "rcflow_ftle_read": [_vp, _i, C.POINTER(C.c_longlong)],
+    "rcflow_ftle_set": [_vp, _i, _d, _d],
+    "rcflow_ftle_reset": [_vp, _i],
+    "rcflow_ftle_close": [_vp, _i],
+    "rcflow_ftle_info": [_vp, _i, C.POINTER(FtleInfo)],
     "rcflow_comm_unique_id": [_vp],
     "rcflow_comm_init": [_vp, _vp, _i, _i],
     "rcflow_comm_destroy": [_vp],

@@ -34,6 +34,7 @@ from ._lib import TRACERS_MOVERS, TRACER_KINDS, TracersInfo, TracersParams
 from ._lib import RegionsInfo, RegionsParams
 from ._lib import TracksInfo, TracksParams
 from ._lib import RC_MOTION_AUTO_TIME, RC_MOTION_FRESH, MotionInfo, MotionParams
+from ._lib import FTLE_DIRECTIONS, FtleInfo, FtleParams
 
 __all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState"]
 
@@ -49,6 +50,7 @@ REGION_DTYPE = np.dtype([("label", "<i4"), ("area", "<i4"), ("x0", "<i4"), ("y0"
                          ("cx", "<f8"), ("cy", "<f8"), ("var_major", "<f8"), ("var_minor", "<f8"), ("angle", "<f8"),
                          ("mean_fx", "<f4"), ("mean_fy", "<f4")])
 # the eight words of a regions summary, in order
+FTLE_SUMMARY = ("held", "valid", "mask", "stopped", "max_lam_bits", "pushes", "reserved0", "reserved1")
 REGIONS_SUMMARY = ("components", "kept", "records", "foreground", "kept_pixels", "bad_pixels", "pushes", "largest_area")
 # rc_track as a numpy record (128 bytes): what Context.tracks_read returns
 TRACK_DTYPE = np.dtype([("id", "<i8"), ("parent", "<i8"), ("first_push", "<i8"), ("area_sum", "<i8"), ("fx_sum", "<i8"), ("fy_sum", "<i8"),
@@ -1356,6 +1358,68 @@ class Context:
     def tracers_close(self, stream=0):
         self._bind(stream)          # waits for the pushes queued on that stream before freeing
         check(self._lib.rcflow_tracers_close(self._h, stream))
+
+    # ------------------------------------------------------------------ flow map and FTLE
+    def ftle_open(self, w, h, window=30, direction="backward", dt=1.0, spacing=1, threshold=0.1, vis_max=0.5, stream=0):
+        """Opens the slot's flow map and FTLE for w x h flow fields (include/rcflow.h, "flow map and FTLE"): a ring of the
+        last `window` fields, a particle from every pixel carried through them ("backward": newest to oldest with -dt, whose
+        ridges are where the water gathers; "forward": oldest to newest), the largest eigenvalue of the Cauchy-Green tensor
+        from central differences at +-spacing, its logarithm per frame, a mask at ftle >= threshold and a JET picture
+        scaled to vis_max.  The ring takes 8 bytes per pixel and field of device memory (0.5 GB at 1080p and window 30)."""
+        p = FtleParams(window=int(window), direction=FTLE_DIRECTIONS[direction] if isinstance(direction, str) else int(direction),
+                       dt=float(dt), spacing=int(spacing), threshold=float(threshold), vis_max=float(vis_max), flags=0)
+        self._bind(stream)          # the state is zeroed on the slot's stream: the one the pushes will run on
+        check(self._lib.rcflow_ftle_open(self._h, stream, int(w), int(h), C.byref(p)))
+
+    def ftle_info(self, stream=0):
+        """dict(w, h, window, direction, dt, spacing, threshold, vis_max, launches_per_push, held, pushes, device_bytes);
+        never blocks."""
+        i = FtleInfo()
+        check(self._lib.rcflow_ftle_info(self._h, stream, C.byref(i)))
+        names = {v: k for k, v in FTLE_DIRECTIONS.items()}
+        return dict(w=i.w, h=i.h, window=i.prm.window, direction=names[i.prm.direction], dt=i.prm.dt, spacing=i.prm.spacing,
+                    threshold=i.prm.threshold, vis_max=i.prm.vis_max, launches_per_push=i.launches_per_push, held=i.held, pushes=i.pushes,
+                    device_bytes=i.device_bytes)
+
+    def ftle_push(self, flow, map=None, steps=None, lam=None, ftle=None, mask=None, vis=None, summary=None, stream=0):
+        """One flow field (HxWx2 float32 device tensor, dense pixels, rows may be padded) into the ring; nothing is
+        synchronised.  Outputs are preallocated device tensors, each optional: map HxWx2 float32 (the displacements), steps
+        HxW int32, lam and ftle HxW float32, mask HxW uint8 (255 / 0: what regions_push takes), vis HxWx3 uint8, summary
+        8 int64 (FTLE_SUMMARY).  Without any output the push is one launch that stores the field; with any it is
+        RC_FTLE_LAUNCHES.  The summary also stays on the slot for ftle_read."""
+        info = self.ftle_info(stream)
+        h, w = info["h"], info["w"]
+        if not _is_t(flow) or not flow.is_cuda or flow.dtype != torch.float32 or flow.dim() != 3 or tuple(flow.shape) != (h, w, 2) or \
+                flow.stride(2) != 1 or flow.stride(1) != 2:
+            raise ValueError("flow must be a %dx%dx2 float32 device tensor with dense pixels, as opened" % (h, w))
+        images = (self._out_image(map, torch.float32, "map", (h, w, 2)) + self._out_image(steps, torch.int32, "steps", (h, w)) +
+                  self._out_image(lam, torch.float32, "lam", (h, w)) + self._out_image(ftle, torch.float32, "ftle", (h, w)) +
+                  self._out_image(mask, torch.uint8, "mask", (h, w)) + self._out_image(vis, torch.uint8, "vis", (h, w, 3)))
+        sp = self._out_array(summary, torch.int64, "summary", 8)
+        self._bind(stream)
+        check(self._lib.rcflow_ftle_push_dev(self._h, stream, self._ptr(flow), flow.stride(0) * 4, *images, sp))
+
+    def ftle_read(self, stream=0):
+        """Waits for the slot's stream -> dict of the summary of the last push that computed one (FTLE_SUMMARY names, and
+        max_lam: the largest eigenvalue as a float); zeros before that."""
+        summ = np.zeros(8, np.int64)
+        self._bind(stream)
+        check(self._lib.rcflow_ftle_read(self._h, stream, summ.ctypes.data_as(C.POINTER(C.c_longlong))))
+        out = dict(zip(FTLE_SUMMARY, (int(v) for v in summ)))
+        out["max_lam"] = float(np.array([out["max_lam_bits"]], np.uint32).view(np.float32)[0])
+        return out
+
+    def ftle_set(self, threshold, vis_max, stream=0):
+        """threshold and vis_max from the next push on."""
+        check(self._lib.rcflow_ftle_set(self._h, stream, float(threshold), float(vis_max)))
+
+    def ftle_reset(self, stream=0):
+        self._bind(stream)
+        check(self._lib.rcflow_ftle_reset(self._h, stream))
+
+    def ftle_close(self, stream=0):
+        self._bind(stream)          # waits for the pushes queued on that stream before freeing
+        check(self._lib.rcflow_ftle_close(self._h, stream))
 
     # ------------------------------------------------------------------ rip regions
     def regions_open(self, w, h, connectivity=8, min_area=1, max_regions=1024, stream=0):

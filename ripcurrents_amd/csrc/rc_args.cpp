@@ -2,7 +2,7 @@
 #include "rc_args.h"
 
 int RcArgs::add(const Arg& a) {
-    if (n_ < RC_ARGS_MAX) a_[n_] = a;
+    if (n_ < cap_) a_[n_] = a;
     return n_++;                                              // past the capacity: check() refuses
 }
 
@@ -15,7 +15,7 @@ int RcArgs::array(const char* name, const void* p, size_t bytes, int align, int 
 }
 
 int RcArgs::check() const {
-    if (n_ > RC_ARGS_MAX) { rc_set_error("%s: %d arguments declared, RC_ARGS_MAX is %d", who_, n_, RC_ARGS_MAX); return RC_EINVAL; }
+    if (n_ > cap_) { rc_set_error("%s: %d arguments declared, the capacity is %d", who_, n_, cap_); return RC_EINVAL; }
     for (int i = 0; i < n_; i++) {
         const Arg& a = a_[i];
         const char* broke = nullptr;

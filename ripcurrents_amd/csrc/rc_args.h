@@ -20,7 +20,7 @@ void rc_set_error(const char* fmt, ...);
 // RC_ARG_ANY_BASE: the alignment is asked of the step alone (the flow field of rcflow_ripmap_push_dev and
 // rcflow_tracers_push_dev: an open point of DESIGN.md, kept as it was found)
 enum { RC_ARG_IN = 0, RC_ARG_OUT = 1, RC_ARG_OPTIONAL = 2, RC_ARG_ANY_BASE = 4 };
-enum { RC_ARGS_MAX = 7 };   // the largest caller's count (rcflow_tracks_push_dev, rcflow_motion_push_dev)
+enum { RC_ARGS_MAX = 7 };   // RcArgs' own capacity (rcflow_tracks_push_dev, rcflow_motion_push_dev); a longer list: RcArgsN
 
 class RcArgs {
   public:
@@ -32,12 +32,26 @@ class RcArgs {
     void in_place(int out, int in) { ip_out_ = out; ip_in_ = in; }   // `out` may be `in` itself: the same pointer and the same step
     int check() const;   // RC_OK, or RC_EINVAL with the text set
 
-  private:
+  protected:
     struct Arg { const char* name; uintptr_t p; size_t step, row_bytes; int w, h, align, flags; bool img; };
+    RcArgs(const char* who, int w, int h, Arg* store, int cap) : who_(who), w_(w), h_(h), cap_(cap), a_(store) {}   // the caller's storage
+
+  private:
     int add(const Arg& a);
     const char* who_;
-    int w_, h_, n_ = 0, ip_out_ = -1, ip_in_ = -1;
-    Arg a_[RC_ARGS_MAX];
+    int w_, h_, n_ = 0, ip_out_ = -1, ip_in_ = -1, cap_ = RC_ARGS_MAX;
+    Arg own_[RC_ARGS_MAX];
+    Arg* a_ = own_;
+};
+
+// the same collector with room for N arguments (rcflow_ftle_push_dev declares 8)
+template <int N>
+class RcArgsN : public RcArgs {
+  public:
+    RcArgsN(const char* who, int w, int h) : RcArgs(who, w, h, more_, N) {}
+
+  private:
+    Arg more_[N];
 };
 
 // one image alone: its form.  Arguments declared one by one are not compared with each other

@@ -200,6 +200,25 @@ struct RcMotion {
     RcZeroFence zf;
 };
 
+// Flow map and FTLE of one stream slot (ftle_kernels.hip).  Everything is allocated by rcflow_ftle_open and released by
+// rcflow_ftle_close / rcflow_destroy.
+struct RcFtle {
+    bool open = false;
+    int w = 0, h = 0;
+    rc_ftle_params prm{};           // threshold and vis_max: as rcflow_ftle_set left them
+    int pitch = 0;                  // row pitch of the ring in pixels (w rounded up to 2: 16-byte rows)
+    int cur = 0;                    // ring slot the next field goes to
+    long long pushes = 0;           // since open / reset; min(pushes, window) fields are held
+    RcBuf ring;                     // [window][h][pitch] float2
+    RcBuf map;                      // [h][w] float2: the displacement of the particle that started at the pixel
+    RcBuf steps;                    // [h][w] int32: the fields it passed through
+    RcBuf lam;                      // [h][w] float: the largest eigenvalue of the Cauchy-Green tensor, 0 where not valid
+    RcBuf ctl;                      // FtCtl: the ticket and the counters, zero between launches
+    RcBuf out;                      // the last computing push: 8 int64 summary
+    RcBuf jet;                      // COLORMAP_JET LUT (768 B), written once by open
+    RcZeroFence zf;
+};
+
 // warp_kernels.hip: one launch of the affine / perspective warp
 struct RcWarpArgs {
     const uint8_t* src; size_t step;
@@ -276,6 +295,7 @@ struct RcSlot {
     RcRegions rg;
     RcTracks tk;
     RcMotion mt;
+    RcFtle ft;
     RcPhaseCorr pc;
 };
 
@@ -326,7 +346,8 @@ struct rc_ctx {
 // The tracer lines (book-keeping, primitives, drawing) are the reference's "pathlines" work and are booked under "stream".
 // The rip regions label and measure the mask the classification leaves and are booked with it, under "threshold"; the rip
 // tracks follow those regions and are booked with them.  The motion templates estimate the frame's direction beside the flow, as
-// the opposing-flow map does from it, and are booked where that is, under "farneback".
+// the opposing-flow map does from it, and are booked where that is, under "farneback".  The flow map and FTLE advect a dense
+// particle field as advect_field does and are booked with it, under "stream".
 #define RC_BUCKET_TABLE(X) \
     X(RC_B_FARNEBACK, "farneback") X(RC_B_POLAR, "polar") X(RC_B_THRESHOLD, "threshold") X(RC_B_OVERLAY, "overlay") \
     X(RC_B_EROSION, "erosion") X(RC_B_CODEC, "codec") X(RC_B_STREAM, "stream")
@@ -361,7 +382,8 @@ struct rc_ctx {
                                                   @7 primitives */ \
     X(RC_K_TRACKS, "tracks", RC_B_THRESHOLD) /* @0 prepare, @1 overlap, @2 claim, @3 winner and update, @4 births and summary, @5 paint and outputs,
                                                 @6 primitives */ \
-    X(RC_K_MOTION, "motion", RC_B_FARNEBACK) /* @0 update, @1 gradient, picture and cell histograms, @2 sums and records, @3 primitives */
+    X(RC_K_MOTION, "motion", RC_B_FARNEBACK) /* @0 update, @1 gradient, picture and cell histograms, @2 sums and records, @3 primitives */ \
+    X(RC_K_FTLE, "ftle", RC_B_STREAM) /* @0 ring slot, @1 flow map, @2 tensor, outputs and summary */
 #define RC_ROW_ID(id, ...) id,
 enum { RC_BUCKET_TABLE(RC_ROW_ID) RC_B_BUCKETS };
 enum { RC_KIND_TABLE(RC_ROW_ID) RC_K_KINDS };
@@ -442,7 +464,7 @@ struct RcProfScope {
     } while (0)
 
 // ---------------------------------------------------------------------------- per-slot products
-// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks and RcMotion share one lifecycle.  A product supplies
+// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion and RcFtle share one lifecycle.  A product supplies
 //   void rc_state_free(T&)             frees every buffer and the fence; the state is T() again
 //   int rc_state_zero(RcSlot&, T&)     rc_fence_zero of what open / reset clear, and the counters
 // and open / reset / close are written once, here.
@@ -453,6 +475,7 @@ void rc_state_free(RcTracers& t);
 void rc_state_free(RcRegions& g);
 void rc_state_free(RcTracks& g);
 void rc_state_free(RcMotion& m);
+void rc_state_free(RcFtle& f);
 int rc_state_zero(RcSlot& s, RcTimex& t);
 int rc_state_zero(RcSlot& s, RcFrameStab& f);
 int rc_state_zero(RcSlot& s, RcRipMap& m);
@@ -460,6 +483,7 @@ int rc_state_zero(RcSlot& s, RcTracers& t);
 int rc_state_zero(RcSlot& s, RcRegions& g);
 int rc_state_zero(RcSlot& s, RcTracks& g);
 int rc_state_zero(RcSlot& s, RcMotion& m);
+int rc_state_zero(RcSlot& s, RcFtle& f);
 
 // The tail of every open.  The caller has validated, selected the device and built `fresh` (rc: what its allocations
 // returned).  The state that is open is touched only once nothing can be refused any more: a refused open leaves it as it
