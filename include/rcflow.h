@@ -1227,6 +1227,90 @@ int rcflow_ftle_close(rc_ctx* ctx, int stream);
 /* never blocks; RC_ESTATE when nothing is open */
 int rcflow_ftle_info(rc_ctx* ctx, int stream, rc_ftle_info* info);
 
+/* ------------------------------------------------------------------ plan view: the flow in metres per second on a ground grid
+ * A shore camera looks along the water at a shallow angle, so every product above mixes near and far water: equal pixels are
+ * wildly unequal areas, and a current far out moves a fraction of the pixels the same current moves close by.  The plan view
+ * resamples the flow field and the frame onto a regular grid on the water surface, through the camera's ground-to-image map
+ * and its radial distortion, and pushes the sampled vector through the inverse of the map's Jacobian: velocities come out in
+ * metres per second, and rcflow_ripmap_*, rcflow_regions_*, rcflow_tracks_* and rcflow_ftle_*, which take any 32FC2 field,
+ * are metric when they are given the plan field.  The reference has no such product.  tests/_planview_ref.py states the
+ * following in numpy and the kernels equal it bit for bit.
+ *
+ *  1. Table ("planview@0"), built once by open on the device.  All DOUBLE, every operation rounded on its own (no fused
+ *     multiply-add), sums left to right; only + - * /, fabs and sqrt:
+ *       project(X, Y):  px = H0*X + H1*Y + H2    py = H3*X + H4*Y + H5    pz = H6*X + H7*Y + H8
+ *                       u = px / pz    v = py / pz    xn = (u - cx) / fx    yn = (v - cy) / fy    r2 = xn*xn + yn*yn    r4 = r2*r2
+ *                       s = 1 + k1*r2 + k2*r4        g = 1 + 3*k1*r2 + 5*k2*r4      (g <= 0: past the fold of the distortion)
+ *                       U = cx + fx*(xn*s)           V = cy + fy*(yn*s)
+ *       cell (i, j):    X = x0 + i*dx, Y = y0 + j*dy; the centre and E/W = (X +- 0.5*dx, Y), S/N = (X, Y +- 0.5*dy) are projected
+ *                       a = (U_E - U_W)/dx   b = (U_S - U_N)/dy   c = (V_E - V_W)/dx   d = (V_S - V_N)/dy   det = a*d - b*c
+ *                       m00 = d/det*fps   m01 = -b/det*fps   m10 = -c/det*fps   m11 = a/det*fps   gsd = sqrt(fabs(1/det))
+ *     The cell is USABLE when pz > 0 and g > 0 at all five points, the centre's U and V, det, the four m and gsd are finite
+ *     (as doubles), det != 0 and gsd <= max_gsd.  gsd is the ground footprint of an image pixel in metres per pixel.  The
+ *     central difference over one cell works for any camera model, needs no inverse of the distortion and is exact for the
+ *     affine part of the map.  A record is eight floats, 32 bytes, each the double rounded once: U, V, m00, m01, m10, m11,
+ *     gsd, 1.0f; eight zeros where the cell is not usable (U = 0 is then rejected by the sampler: the push has one test).
+ *  2. Push ("planview@1"), per cell, fp32, each operation rounded on its own:
+ *     SEEN: the record's (U, V) passes the streamline sampler's test (ripcurrents_module.cpp:494-508) for the w x h image:
+ *     xind = (int)floorf(U), yind likewise, as x86 converts; xind < 1 || yind < 1 || xind + 2 > w || yind + 2 > h rejects.
+ *     VALID: seen, the field is given, and its bilinear sample (sx, sy) at (U, V), with that sampler's weights, products and
+ *     additions in its order, is finite in both components.
+ *     Plan field: Vx = m00*sx + m01*sy, Vy = m10*sx + m11*sy (two multiplies, one add) where valid, else (0, 0).  A large
+ *     sample may overflow them to +-inf, or to NaN: they are stored as they come.
+ *     Mask (8UC1): 255 where valid, else 0: the form rcflow_regions_push_dev takes.
+ *     Picture (8UC3), where seen: ix = (int)rintf(U * 32.f), iy likewise; source pixel (ix >> 5, iy >> 5), fractions ix & 31,
+ *     iy & 31, the 8-bit sample of the warps (weights of 2^15, rounded per channel, a tap outside the frame counts 0); black
+ *     elsewhere.  It does not depend on the field.
+ *     Summary, 8 int64: usable cells | seen cells | valid cells | the bits, as uint32, of the largest Vx*Vx + Vy*Vy over the
+ *     valid cells (NaN excepted; 0 for none) | pushes since open / reset | 0 | 0 | 0.  A push without the field has no valid
+ *     cell. */
+#define RC_PLANVIEW_LAUNCHES 1     /* of a push */
+#define RC_PLANVIEW_MAX_CELLS (1ll << 30)   /* a table of 32 GiB */
+typedef struct rc_planview_params {
+    double H[9];            /* row-major: ground (X, Y, 1) in metres -> homogeneous IDEAL (undistorted) pixel; all finite */
+    double fx, fy, cx, cy;  /* focal lengths and principal point of the distortion model, pixels; finite, fx, fy > 0 */
+    double k1, k2;          /* radial distortion (OpenCV's model without the tangential terms); finite; both 0: none */
+    double x0, y0, dx, dy;  /* ground position of plan cell (0, 0) and the cell pitch, metres; finite; dx, dy not 0, may be negative */
+    int nx, ny;             /* plan size in cells; >= 1, within the context's max_w x max_h */
+    double fps;             /* fields per second (1: metres per field); finite, > 0 */
+    double max_gsd;         /* largest ground footprint of an image pixel a cell may have, metres per pixel; > 0; +inf: no cut */
+    int flags;              /* 0 */
+} rc_planview_params;
+typedef struct rc_planview_info {
+    int w, h;                          /* the image: the field's and the frame's size */
+    rc_planview_params prm;
+    int launches_per_push;             /* RC_PLANVIEW_LAUNCHES */
+    long long pushes;                  /* since open / reset */
+    size_t device_bytes;
+} rc_planview_info;
+/* Allocates the table (32 B per plan cell) and the counters and builds the table on the slot's stream ("planview@0").
+ * Re-opening replaces the state, and is how parameters change (another tide level: another H); a refused open leaves the open
+ * state as it was.  RC_EINVAL: no parameters, w or h < 1, a value outside the ranges above, unknown flag bits; RC_ESIZE: w x h
+ * or nx x ny beyond the context's max_w x max_h, or more than RC_PLANVIEW_MAX_CELLS cells. */
+int rcflow_planview_open(rc_ctx* ctx, int stream, int w, int h, const rc_planview_params* prm);
+/* One launch ("planview@1"); no host synchronisation, no device-to-host copy.  Inputs (device memory, either may be NULL,
+ * not both): d_flow_xy 32FC2 w x h (pointer and step multiples of 8, step >= 8 w), d_bgr 8UC3 w x h.  Outputs, each may be
+ * NULL: d_plan_xy 32FC2 nx x ny (pointer and step multiples of 8), d_mask 8UC1 nx x ny and d_summary 8 int64 (8-byte
+ * aligned) need the field, d_plan_bgr 8UC3 nx x ny needs the frame.  RC_EINVAL: both inputs NULL, an output whose input is
+ * NULL, a bad pointer or step, an output whose byte range [first byte, past the last) overlaps an input's or another
+ * output's.  Row padding is never written.  Every refusal is decided before anything is queued and leaves the state as it
+ * was; RC_ESTATE before rcflow_planview_open. */
+int rcflow_planview_push_dev(rc_ctx* ctx, int stream, const float* d_flow_xy, size_t flow_step,
+                             const uint8_t* d_bgr, size_t bgr_step, float* d_plan_xy, size_t plan_step,
+                             uint8_t* d_mask, size_t mask_step, uint8_t* d_plan_bgr, size_t plan_bgr_step,
+                             long long* d_summary);
+/* Blocks until the slot's stream has finished; for hosts and tests.  The summary of the last push; zeros before the first. */
+int rcflow_planview_read(rc_ctx* ctx, int stream, long long summary[8]);
+/* Blocks; copies the table out (host memory, ny * nx * 8 floats): for tests, and for drawing what was detected on the plan
+ * grid back into the image (a usable cell's U, V is its centre's pixel). */
+int rcflow_planview_table_read(rc_ctx* ctx, int stream, float* table);
+/* zeroes the summary and the push count; keeps the table; asynchronous, on the slot's stream */
+int rcflow_planview_reset(rc_ctx* ctx, int stream);
+/* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
+int rcflow_planview_close(rc_ctx* ctx, int stream);
+/* never blocks; RC_ESTATE when nothing is open */
+int rcflow_planview_info(rc_ctx* ctx, int stream, rc_planview_info* info);
+
 /* Display path, ripcurrents.cpp:233-273 (= streamline_displacement / _total_motion / _ratio /
  * _positions, ripcurrents_module.cpp:13-60) on the slot's streamline field (rcflow_advect_field_dev):
  * which 0 = |pt|, 1 = dist, 2 = |pt| / dist; minMaxLoc + convertTo(CV_8UC1, 255/max) +
@@ -1307,7 +1391,7 @@ int rcflow_profile_read(rc_ctx* ctx, int cap, const char** names, int* launches,
 
 /* The same totals under the reference's own bucket names, in the order it prints them (ripcurrents.cpp:103-109,
  * :518-524): farneback, polar, threshold, overlay, erosion, codec, stream ("pathlines").  GPU time of the kernels
- * that do each bucket's work ("overlay" includes the time-exposure images and the 8-bit colour stages, "farneback" the frame stabilisation, the opposing-flow map and the motion templates, "stream" the flow map and FTLE); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
+ * that do each bucket's work ("overlay" includes the time-exposure images and the 8-bit colour stages, "farneback" the frame stabilisation, the opposing-flow map, the motion templates and the plan view, "stream" the flow map and FTLE); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
  * classification kernels, booked under "threshold"), "codec" is 0 (video decode is host I/O outside the library).
  * names / ms: RC_PROFILE_BUCKETS entries each (either may be NULL).  Returns RC_PROFILE_BUCKETS. */
 #define RC_PROFILE_BUCKETS 7

@@ -953,4 +953,72 @@ class Ftle {
     void *d_flow_ = nullptr, *d_ftle_ = nullptr, *d_mask_ = nullptr, *d_vis_ = nullptr;
 };
 
+// Plan view on the device (rcflow_planview_*): the flow field in metres per second, and the frame, on a regular grid on the
+// water, through the camera's ground-to-image map and its radial distortion.  Host fields and frames of the pipeline's size
+// in; the plan field, its mask and the plan picture (each nx x ny of the parameters) out.
+class PlanView {
+  public:
+    PlanView(Pipeline& pipe, const rc_planview_params& prm) : pipe_(pipe), nx_(prm.nx), ny_(prm.ny) {
+        check(rcflow_planview_open(pipe.context(), 0, pipe.width(), pipe.height(), &prm));
+    }
+    ~PlanView() {
+        (void)rcflow_planview_close(pipe_.context(), 0);
+        for (void* p : {d_flow_, d_bgr_, d_plan_, d_mask_, d_pic_}) if (p) (void)hipFree(p);
+    }
+    PlanView(const PlanView&) = delete;
+    PlanView& operator=(const PlanView&) = delete;
+
+    // flow: 32FC2, frame: 8UC3, each of the pipeline's size; either may be null, not both.  plan 32FC2 and mask 8UC1 (255 / 0)
+    // need the field, picture 8UC3 the frame; each nx x ny and optional.
+    void push(const Mat* flow, const Mat* frame, Mat* plan = nullptr, Mat* mask = nullptr, Mat* picture = nullptr) {
+        const int w = pipe_.width(), h = pipe_.height();
+        if ((flow && !fits(*flow, w, h, 2, 4)) || (frame && !fits(*frame, w, h, 3, 1)) || (!flow && !frame))
+            throw Error(RC_EINVAL, "PlanView::push: the field 32FC2, the frame 8UC3, each of the pipeline's size, and one of them at least");
+        if ((plan && !fits(*plan, nx_, ny_, 2, 4)) || (mask && !fits(*mask, nx_, ny_, 1, 1)) || (picture && !fits(*picture, nx_, ny_, 3, 1)) ||
+            (!flow && (plan || mask)) || (!frame && picture))
+            throw Error(RC_EINVAL, "PlanView::push: plan 32FC2 and mask 8UC1 need the field, picture 8UC3 the frame, each of the plan's size");
+        const size_t px = (size_t)w * h, cells = (size_t)nx_ * ny_;
+        if (flow && !d_flow_) hip_check(hipMalloc(&d_flow_, px * 8), "hipMalloc field");
+        if (frame && !d_bgr_) hip_check(hipMalloc(&d_bgr_, px * 3), "hipMalloc frame");
+        if (plan && !d_plan_) hip_check(hipMalloc(&d_plan_, cells * 8), "hipMalloc plan");
+        if (mask && !d_mask_) hip_check(hipMalloc(&d_mask_, cells), "hipMalloc mask");
+        if (picture && !d_pic_) hip_check(hipMalloc(&d_pic_, cells * 3), "hipMalloc picture");
+        check(rcflow_sync(pipe_.context(), 0));                  // the last push may still be reading the staging inputs
+        if (flow) hip_check(hipMemcpy2D(d_flow_, (size_t)w * 8, flow->data, flow->step, (size_t)w * 8, h, hipMemcpyHostToDevice), "upload field");
+        if (frame) hip_check(hipMemcpy2D(d_bgr_, (size_t)w * 3, frame->data, frame->step, (size_t)w * 3, h, hipMemcpyHostToDevice), "upload frame");
+        check(rcflow_planview_push_dev(pipe_.context(), 0, flow ? (const float*)d_flow_ : nullptr, (size_t)w * 8,
+                                       frame ? (const uint8_t*)d_bgr_ : nullptr, (size_t)w * 3, plan ? (float*)d_plan_ : nullptr, (size_t)nx_ * 8,
+                                       mask ? (uint8_t*)d_mask_ : nullptr, (size_t)nx_, picture ? (uint8_t*)d_pic_ : nullptr, (size_t)nx_ * 3,
+                                       nullptr));
+        if (!plan && !mask && !picture) return;
+        check(rcflow_sync(pipe_.context(), 0));
+        if (plan) hip_check(hipMemcpy2D(plan->data, plan->step, d_plan_, (size_t)nx_ * 8, (size_t)nx_ * 8, ny_, hipMemcpyDeviceToHost), "download plan");
+        if (mask) hip_check(hipMemcpy2D(mask->data, mask->step, d_mask_, (size_t)nx_, (size_t)nx_, ny_, hipMemcpyDeviceToHost), "download mask");
+        if (picture) hip_check(hipMemcpy2D(picture->data, picture->step, d_pic_, (size_t)nx_ * 3, (size_t)nx_ * 3, ny_, hipMemcpyDeviceToHost), "download picture");
+    }
+    // waits for the pipeline's stream: the summary of the last push (include/rcflow.h: usable, seen, valid, bits of the
+    // largest squared speed, pushes, 0, 0, 0)
+    std::vector<long long> read() {
+        std::vector<long long> s(8);
+        check(rcflow_planview_read(pipe_.context(), 0, s.data()));
+        return s;
+    }
+    // waits: ny x nx records of eight floats (U, V, m00, m01, m10, m11, gsd, 1; zeros where the cell is not usable)
+    std::vector<float> table() {
+        std::vector<float> t((size_t)nx_ * ny_ * 8);
+        check(rcflow_planview_table_read(pipe_.context(), 0, t.data()));
+        return t;
+    }
+    rc_planview_info info() { rc_planview_info i; check(rcflow_planview_info(pipe_.context(), 0, &i)); return i; }
+    void reset() { check(rcflow_planview_reset(pipe_.context(), 0)); }
+
+  private:
+    static bool fits(const Mat& m, int cols, int rows, int channels, int elem) {
+        return !m.empty() && m.rows == rows && m.cols == cols && m.channels == channels && m.elem == elem;
+    }
+    Pipeline& pipe_;
+    int nx_, ny_;
+    void *d_flow_ = nullptr, *d_bgr_ = nullptr, *d_plan_ = nullptr, *d_mask_ = nullptr, *d_pic_ = nullptr;
+};
+
 }  // namespace rc

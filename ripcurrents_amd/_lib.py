@@ -47,6 +47,8 @@ RC_MOTION_FRESH, RC_MOTION_AUTO_TIME, RC_MOTION_LAUNCHES = 1, -1.0, 3
 # rcflow_ftle_*: the directions, the bounds, the launches of a push that computes
 FTLE_DIRECTIONS = {"forward": 0, "backward": 1}
 RC_FTLE_MAX_WINDOW, RC_FTLE_MAX_SPACING, RC_FTLE_LAUNCHES = 256, 16, 3
+# rcflow_planview_*: the launches of a push
+RC_PLANVIEW_LAUNCHES = 1
 
 ERRORS = {-1: "RC_EINVAL", -2: "RC_ENOMEM", -3: "RC_EHIP", -4: "RC_ENODEV", -5: "RC_ESIZE",
           -6: "RC_ESTATE", -7: "RC_ECOMM"}
@@ -162,6 +164,19 @@ class FtleInfo(C.Structure):
     """rc_ftle_info (include/rcflow.h)."""
     _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", FtleParams), ("launches_per_push", C.c_int), ("held", C.c_int),
                 ("pushes", C.c_longlong), ("device_bytes", C.c_size_t)]
+
+
+class PlanViewParams(C.Structure):
+    """rc_planview_params (include/rcflow.h)."""
+    _fields_ = [("H", C.c_double * 9), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("k1", C.c_double), ("k2", C.c_double), ("x0", C.c_double), ("y0", C.c_double), ("dx", C.c_double), ("dy", C.c_double),
+                ("nx", C.c_int), ("ny", C.c_int), ("fps", C.c_double), ("max_gsd", C.c_double), ("flags", C.c_int)]
+
+
+class PlanViewInfo(C.Structure):
+    """rc_planview_info (include/rcflow.h)."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", PlanViewParams), ("launches_per_push", C.c_int), ("pushes", C.c_longlong),
+                ("device_bytes", C.c_size_t)]
 
 
 class FitParams(C.Structure):
@@ -327,6 +342,13 @@ SIGNATURES = {
     "rcflow_ftle_reset": [_vp, _i],
     "rcflow_ftle_close": [_vp, _i],
     "rcflow_ftle_info": [_vp, _i, C.POINTER(FtleInfo)],
+    "rcflow_planview_open": [_vp, _i, _i, _i, C.POINTER(PlanViewParams)],
+    "rcflow_planview_push_dev": [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp],
+    "rcflow_planview_read": [_vp, _i, C.POINTER(C.c_longlong)],
+    "rcflow_planview_table_read": [_vp, _i, _vp],
+    "rcflow_planview_reset": [_vp, _i],
+    "rcflow_planview_close": [_vp, _i],
+    "rcflow_planview_info": [_vp, _i, C.POINTER(PlanViewInfo)],
     "rcflow_comm_unique_id": [_vp],
     "rcflow_comm_init": [_vp, _vp, _i, _i],
     "rcflow_comm_destroy": [_vp],

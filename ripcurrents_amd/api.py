@@ -35,6 +35,7 @@ from ._lib import RegionsInfo, RegionsParams
 from ._lib import TracksInfo, TracksParams
 from ._lib import RC_MOTION_AUTO_TIME, RC_MOTION_FRESH, MotionInfo, MotionParams
 from ._lib import FTLE_DIRECTIONS, FtleInfo, FtleParams
+from ._lib import PlanViewInfo, PlanViewParams
 
 __all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState"]
 
@@ -51,6 +52,7 @@ REGION_DTYPE = np.dtype([("label", "<i4"), ("area", "<i4"), ("x0", "<i4"), ("y0"
                          ("mean_fx", "<f4"), ("mean_fy", "<f4")])
 # the eight words of a regions summary, in order
 FTLE_SUMMARY = ("held", "valid", "mask", "stopped", "max_lam_bits", "pushes", "reserved0", "reserved1")
+PLANVIEW_SUMMARY = ("usable", "seen", "valid", "max_speed2_bits", "pushes", "reserved0", "reserved1", "reserved2")
 REGIONS_SUMMARY = ("components", "kept", "records", "foreground", "kept_pixels", "bad_pixels", "pushes", "largest_area")
 # rc_track as a numpy record (128 bytes): what Context.tracks_read returns
 TRACK_DTYPE = np.dtype([("id", "<i8"), ("parent", "<i8"), ("first_push", "<i8"), ("area_sum", "<i8"), ("fx_sum", "<i8"), ("fy_sum", "<i8"),
@@ -1420,6 +1422,79 @@ class Context:
     def ftle_close(self, stream=0):
         self._bind(stream)          # waits for the pushes queued on that stream before freeing
         check(self._lib.rcflow_ftle_close(self._h, stream))
+
+    # ------------------------------------------------------------------ plan view
+    def planview_open(self, w, h, H, fx, fy, cx, cy, k1=0.0, k2=0.0, x0=0.0, y0=0.0, dx=1.0, dy=1.0, nx=1, ny=1, fps=1.0,
+                      max_gsd=float("inf"), stream=0):
+        """Opens the slot's plan view for w x h fields and frames (include/rcflow.h, "plan view"): a ground grid of nx x ny
+        cells of dx x dy metres from (x0, y0), seen through H (3 x 3, ground (X, Y, 1) in metres -> homogeneous ideal pixel)
+        and the radial distortion k1, k2 about (cx, cy) with focal lengths fx, fy.  The push resamples the field onto the
+        grid in metres per second (fps fields per second) and the frame beside it; cells whose pixel covers more than max_gsd
+        metres, or that the camera does not see, are left out.  The table takes 32 bytes per cell of device memory and is
+        built here, once, on the device; re-opening is how parameters change."""
+        p = PlanViewParams(fx=float(fx), fy=float(fy), cx=float(cx), cy=float(cy), k1=float(k1), k2=float(k2), x0=float(x0), y0=float(y0),
+                           dx=float(dx), dy=float(dy), nx=int(nx), ny=int(ny), fps=float(fps), max_gsd=float(max_gsd), flags=0)
+        p.H[:] = [float(v) for v in np.asarray(H, np.float64).reshape(9)]
+        self._bind(stream)          # the table is built and the state zeroed on the slot's stream: the one the pushes will run on
+        check(self._lib.rcflow_planview_open(self._h, stream, int(w), int(h), C.byref(p)))
+
+    def planview_info(self, stream=0):
+        """dict(w, h, the parameters (H a tuple of 9), launches_per_push, pushes, device_bytes); never blocks."""
+        i = PlanViewInfo()
+        check(self._lib.rcflow_planview_info(self._h, stream, C.byref(i)))
+        out = {k: getattr(i.prm, k) for k, _ in PlanViewParams._fields_ if k not in ("H", "flags")}
+        out.update(w=i.w, h=i.h, H=tuple(i.prm.H), launches_per_push=i.launches_per_push, pushes=i.pushes, device_bytes=i.device_bytes)
+        return out
+
+    def planview_push(self, flow=None, bgr=None, plan=None, mask=None, plan_bgr=None, summary=None, stream=0):
+        """One launch; nothing is synchronised.  Inputs (device tensors with dense pixels, rows may be padded; either may be
+        None, not both): flow HxWx2 float32, bgr HxWx3 uint8.  Outputs are preallocated device tensors, each optional: plan
+        NYxNXx2 float32 (metres per second; what ripmap_push, regions_push and ftle_push take), mask NYxNX uint8 (255 where
+        the cell is valid, else 0) and summary 8 int64 (PLANVIEW_SUMMARY) need the field, plan_bgr NYxNXx3 uint8 the frame.
+        The summary also stays on the slot for planview_read."""
+        info = self.planview_info(stream)
+        h, w, ny, nx = info["h"], info["w"], info["ny"], info["nx"]
+        ins = []
+        for t, dtype, name, ch in ((flow, torch.float32, "flow", 2), (bgr, torch.uint8, "bgr", 3)):
+            if t is None:
+                ins += [C.c_void_p(None), 0]
+                continue
+            if not _is_t(t) or not t.is_cuda or t.dtype != dtype or t.dim() != 3 or tuple(t.shape) != (h, w, ch) or t.stride(2) != 1 or \
+                    t.stride(1) != ch:
+                raise ValueError("%s must be a %dx%dx%d %s device tensor with dense pixels, as opened" % (name, h, w, ch, dtype))
+            ins += [self._ptr(t), t.stride(0) * t.element_size()]
+        images = (self._out_image(plan, torch.float32, "plan", (ny, nx, 2)) + self._out_image(mask, torch.uint8, "mask", (ny, nx)) +
+                  self._out_image(plan_bgr, torch.uint8, "plan_bgr", (ny, nx, 3)))
+        sp = self._out_array(summary, torch.int64, "summary", 8)
+        self._bind(stream)
+        check(self._lib.rcflow_planview_push_dev(self._h, stream, *ins, *images, sp))
+
+    def planview_read(self, stream=0):
+        """Waits for the slot's stream -> dict of the summary of the last push (PLANVIEW_SUMMARY names, and max_speed: the
+        largest plan speed in metres per second as a float); zeros before the first."""
+        summ = np.zeros(8, np.int64)
+        self._bind(stream)
+        check(self._lib.rcflow_planview_read(self._h, stream, summ.ctypes.data_as(C.POINTER(C.c_longlong))))
+        out = dict(zip(PLANVIEW_SUMMARY, (int(v) for v in summ)))
+        out["max_speed"] = float(np.sqrt(np.array([out["max_speed2_bits"]], np.uint32).view(np.float32)[0]))
+        return out
+
+    def planview_table(self, stream=0):
+        """Waits for the slot's stream -> the table, NY x NX x 8 float32: U, V (the pixel of the cell's centre), m00, m01, m10,
+        m11 (pixels per field -> metres per second), gsd (metres per pixel), 1; eight zeros where the cell is not usable."""
+        info = self.planview_info(stream)
+        tab = np.empty((info["ny"], info["nx"], 8), np.float32)
+        self._bind(stream)
+        check(self._lib.rcflow_planview_table_read(self._h, stream, tab.ctypes.data))
+        return tab
+
+    def planview_reset(self, stream=0):
+        self._bind(stream)
+        check(self._lib.rcflow_planview_reset(self._h, stream))
+
+    def planview_close(self, stream=0):
+        self._bind(stream)          # waits for the pushes queued on that stream before freeing
+        check(self._lib.rcflow_planview_close(self._h, stream))
 
     # ------------------------------------------------------------------ rip regions
     def regions_open(self, w, h, connectivity=8, min_area=1, max_regions=1024, stream=0):

@@ -219,6 +219,19 @@ struct RcFtle {
     RcZeroFence zf;
 };
 
+// Plan view of one stream slot (planview_kernels.hip).  Everything is allocated by rcflow_planview_open and released by
+// rcflow_planview_close / rcflow_destroy.
+struct RcPlanView {
+    bool open = false;
+    int w = 0, h = 0;               // the image: the field's and the frame's size
+    rc_planview_params prm{};
+    long long pushes = 0;           // since open / reset
+    RcBuf table;                    // [ny][nx] records of eight floats: U, V, m00, m01, m10, m11, gsd, 1; written once by open
+    RcBuf ctl;                      // PvCtl: the ticket and the counters, zero between launches
+    RcBuf out;                      // the last push: 8 int64 summary
+    RcZeroFence zf;
+};
+
 // warp_kernels.hip: one launch of the affine / perspective warp
 struct RcWarpArgs {
     const uint8_t* src; size_t step;
@@ -296,6 +309,7 @@ struct RcSlot {
     RcTracks tk;
     RcMotion mt;
     RcFtle ft;
+    RcPlanView pv;
     RcPhaseCorr pc;
 };
 
@@ -347,7 +361,9 @@ struct rc_ctx {
 // The rip regions label and measure the mask the classification leaves and are booked with it, under "threshold"; the rip
 // tracks follow those regions and are booked with them.  The motion templates estimate the frame's direction beside the flow, as
 // the opposing-flow map does from it, and are booked where that is, under "farneback".  The flow map and FTLE advect a dense
-// particle field as advect_field does and are booked with it, under "stream".
+// particle field as advect_field does and are booked with it, under "stream".  The plan view carries no particle anywhere: it
+// resamples the flow field onto the ground grid and rescales it, after which it is the field every later product takes, so
+// it is booked with the other operations on the field (flow_postop), under "farneback".
 #define RC_BUCKET_TABLE(X) \
     X(RC_B_FARNEBACK, "farneback") X(RC_B_POLAR, "polar") X(RC_B_THRESHOLD, "threshold") X(RC_B_OVERLAY, "overlay") \
     X(RC_B_EROSION, "erosion") X(RC_B_CODEC, "codec") X(RC_B_STREAM, "stream")
@@ -383,7 +399,8 @@ struct rc_ctx {
     X(RC_K_TRACKS, "tracks", RC_B_THRESHOLD) /* @0 prepare, @1 overlap, @2 claim, @3 winner and update, @4 births and summary, @5 paint and outputs,
                                                 @6 primitives */ \
     X(RC_K_MOTION, "motion", RC_B_FARNEBACK) /* @0 update, @1 gradient, picture and cell histograms, @2 sums and records, @3 primitives */ \
-    X(RC_K_FTLE, "ftle", RC_B_STREAM) /* @0 ring slot, @1 flow map, @2 tensor, outputs and summary */
+    X(RC_K_FTLE, "ftle", RC_B_STREAM) /* @0 ring slot, @1 flow map, @2 tensor, outputs and summary */ \
+    X(RC_K_PLANVIEW, "planview", RC_B_FARNEBACK) /* @0 the table (open), @1 the push */
 #define RC_ROW_ID(id, ...) id,
 enum { RC_BUCKET_TABLE(RC_ROW_ID) RC_B_BUCKETS };
 enum { RC_KIND_TABLE(RC_ROW_ID) RC_K_KINDS };
@@ -464,7 +481,7 @@ struct RcProfScope {
     } while (0)
 
 // ---------------------------------------------------------------------------- per-slot products
-// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion and RcFtle share one lifecycle.  A product supplies
+// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle and RcPlanView share one lifecycle.  A product supplies
 //   void rc_state_free(T&)             frees every buffer and the fence; the state is T() again
 //   int rc_state_zero(RcSlot&, T&)     rc_fence_zero of what open / reset clear, and the counters
 // and open / reset / close are written once, here.
@@ -476,6 +493,7 @@ void rc_state_free(RcRegions& g);
 void rc_state_free(RcTracks& g);
 void rc_state_free(RcMotion& m);
 void rc_state_free(RcFtle& f);
+void rc_state_free(RcPlanView& v);
 int rc_state_zero(RcSlot& s, RcTimex& t);
 int rc_state_zero(RcSlot& s, RcFrameStab& f);
 int rc_state_zero(RcSlot& s, RcRipMap& m);
@@ -484,6 +502,7 @@ int rc_state_zero(RcSlot& s, RcRegions& g);
 int rc_state_zero(RcSlot& s, RcTracks& g);
 int rc_state_zero(RcSlot& s, RcMotion& m);
 int rc_state_zero(RcSlot& s, RcFtle& f);
+int rc_state_zero(RcSlot& s, RcPlanView& v);
 
 // The tail of every open.  The caller has validated, selected the device and built `fresh` (rc: what its allocations
 // returned).  The state that is open is touched only once nothing can be refused any more: a refused open leaves it as it
