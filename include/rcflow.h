@@ -87,6 +87,8 @@ typedef struct rc_farneback_params {
 int rcflow_create(rc_ctx** out, int device, int max_w, int max_h, int max_streams);
 void rcflow_destroy(rc_ctx* ctx);
 int rcflow_abi_version(void);
+/* The text of the calling thread's last failed call.  Every return other than RC_OK has set it, and it starts with the
+ * name of the function that refused (a bad context or slot index, and a failed HIP call, carry no name). */
 const char* rcflow_last_error(void);
 /* Waits for everything enqueued on the slot. */
 int rcflow_sync(rc_ctx* ctx, int stream);

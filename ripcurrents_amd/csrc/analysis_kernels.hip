@@ -707,9 +707,9 @@ static int grid_for(long long items) {
     return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));   // memory-bound: cap and grid-stride
 }
 
-static int analysis_ensure(rc_ctx* ctx, RcSlot& s, int w, int h, bool reset) {
-    if (w <= 0 || h <= 0) return RC_EINVAL;
-    if (w > ctx->max_w || h > ctx->max_h) { rc_set_error("frame exceeds the context size"); return RC_ESIZE; }
+static int analysis_ensure(const char* who, rc_ctx* ctx, RcSlot& s, int w, int h, bool reset) {
+    if (w <= 0 || h <= 0) { rc_set_error("%s: an empty size %d x %d", who, w, h); return RC_EINVAL; }
+    if (int rc = rc_fits_context(who, ctx, w, h)) return rc;
     RcAnalysis& an = s.an;
     bool fresh = (an.w != w || an.h != h || !an.hist.p);
     if (!fresh && !reset) return RC_OK;
@@ -741,34 +741,25 @@ extern "C" int rcflow_analysis_reset(rc_ctx* ctx, int stream, int w, int h) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
     RC_HIP(hipSetDevice(ctx->device));
-    return analysis_ensure(ctx, *s, w, h, true);
+    return analysis_ensure(__func__, ctx, *s, w, h, true);
 }
 
-static int check_flow(const float* d_flow, size_t step, int w, int h) {
-    if (!d_flow || w <= 0 || h <= 0 || step < (size_t)w * 8 || (step & 7)) {
-        rc_set_error("bad flow field argument");
-        return RC_EINVAL;
-    }
-    return RC_OK;
-}
-
-extern "C" int rcflow_histogram_clip_dev(rc_ctx* ctx, int stream, const float* d_flows, size_t flow_frame_stride,
-                                         size_t flow_step, int count, int w, int h) {
+static int histogram_clip(const char* who, const char* name, rc_ctx* ctx, int stream, const float* d_flows, size_t flow_frame_stride, size_t flow_step,
+                          int count, int w, int h) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    int rc = check_flow(d_flows, flow_step, w, h);
+    if (count < 1 || count > 65535) { rc_set_error("%s: count %d (1..65535)", who, count); return RC_EINVAL; }
+    int rc = rc_clip_check(who, name, d_flows, flow_frame_stride, flow_step, count, w, h, 8, 8, RC_ARG_IN | RC_ARG_ANY_BASE);
     if (rc) return rc;
-    if (count < 1 || count > 65535 || (count > 1 && flow_frame_stride < flow_step * (size_t)(h - 1) + (size_t)w * 8))
-        return RC_EINVAL;
-    if ((long long)w * h > 0x3fffffffll) { rc_set_error("frame too large for the histogram kernel's 32-bit item index"); return RC_ESIZE; }
+    if ((long long)w * h > 0x3fffffffll) { rc_set_error("%s: frame too large for the histogram kernel's 32-bit item index", who); return RC_ESIZE; }
     RC_HIP(hipSetDevice(ctx->device));
-    if ((rc = analysis_ensure(ctx, *s, w, h, false))) return rc;
+    if ((rc = analysis_ensure(who, ctx, *s, w, h, false))) return rc;
     // The counters are the reference's `int` (ripcurrents.cpp:147-150, never reset there: they wrap after
     // 2^31 / (w h) frames, about four minutes of 640x480 video).  Every pixel adds at most one count, so the
     // pixels added since the last reset bound histsum: refuse the call that could wrap it.
     if (s->an.hist_added + (long long)w * h * count > 0x7fffffffll) {
-        rc_set_error("flow histogram would exceed its int32 counters (%lld pixels counted since the last reset): "
-                     "start a new segment with rcflow_histogram_reset_dev", s->an.hist_added);
+        rc_set_error("%s: flow histogram would exceed its int32 counters (%lld pixels counted since the last reset): "
+                     "start a new segment with rcflow_histogram_reset_dev", who, s->an.hist_added);
         return RC_ESTATE;
     }
     s->an.hist_added += (long long)w * h * count;
@@ -799,14 +790,18 @@ extern "C" int rcflow_histogram_clip_dev(rc_ctx* ctx, int stream, const float* d
     return RC_OK;
 }
 
+extern "C" int rcflow_histogram_clip_dev(rc_ctx* ctx, int stream, const float* d_flows, size_t flow_frame_stride,
+                                         size_t flow_step, int count, int w, int h) {
+    return histogram_clip(__func__, "d_flows", ctx, stream, d_flows, flow_frame_stride, flow_step, count, w, h);
+}
 extern "C" int rcflow_histogram_dev(rc_ctx* ctx, int stream, const float* d_flow, size_t flow_step, int w, int h) {
-    return rcflow_histogram_clip_dev(ctx, stream, d_flow, 0, flow_step, 1, w, h);
+    return histogram_clip(__func__, "d_flow", ctx, stream, d_flow, 0, flow_step, 1, w, h);
 }
 
 extern "C" int rcflow_thresholds_dev(rc_ctx* ctx, int stream) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    if (!s->an.hist.p) { rc_set_error("no histogram state: call rcflow_analysis_reset first"); return RC_ESTATE; }
+    if (!s->an.hist.p) { rc_set_error("%s: no histogram state: call rcflow_analysis_reset first", __func__); return RC_ESTATE; }
     RC_HIP(hipSetDevice(ctx->device));
     {
         RcProfScope ps(ctx, s->cur, RC_K_THRESH, 0, 4. * RC_HIST_WORDS);
@@ -820,8 +815,9 @@ extern "C" int rcflow_thresholds_dev(rc_ctx* ctx, int stream) {
 // the slot's own cumulative counters stay local, UPPER / UPPER2d / prop_above_upper become global.
 extern "C" int rcflow_thresholds_words_dev(rc_ctx* ctx, int stream, const int32_t* d_words) {
     RcSlot* s = rc_slot(ctx, stream);
-    if (!s || !d_words) return RC_EINVAL;
-    if (!s->an.thr.p) { rc_set_error("no histogram state: call rcflow_analysis_reset first"); return RC_ESTATE; }
+    if (!s) return RC_EINVAL;
+    if (int rc = rc_ptr_check(__func__, "d_words", d_words)) return rc;
+    if (!s->an.thr.p) { rc_set_error("%s: no histogram state: call rcflow_analysis_reset first", __func__); return RC_ESTATE; }
     RC_HIP(hipSetDevice(ctx->device));
     {
         RcProfScope ps(ctx, s->cur, RC_K_THRESH, 0, 4. * RC_HIST_WORDS);
@@ -835,7 +831,7 @@ extern "C" int rcflow_histogram_read(rc_ctx* ctx, int stream, int32_t* hist, int
                                      int32_t* histsum2d, float* UPPER, float* UPPER2d, float* prop) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    if (!s->an.hist.p) { rc_set_error("no histogram state"); return RC_ESTATE; }
+    if (!s->an.hist.p) { rc_set_error("%s: no histogram state", __func__); return RC_ESTATE; }
     RC_HIP(hipSetDevice(ctx->device));
     int32_t words[RC_HIST_WORDS];
     float thr[THR_WORDS];
@@ -854,8 +850,9 @@ extern "C" int rcflow_histogram_read(rc_ctx* ctx, int stream, int32_t* hist, int
 
 extern "C" int rcflow_histogram_write(rc_ctx* ctx, int stream, const int32_t* words) {
     RcSlot* s = rc_slot(ctx, stream);
-    if (!s || !words) return RC_EINVAL;
-    if (!s->an.hist.p) { rc_set_error("no histogram state"); return RC_ESTATE; }
+    if (!s) return RC_EINVAL;
+    if (int rc = rc_ptr_check(__func__, "words", words)) return rc;
+    if (!s->an.hist.p) { rc_set_error("%s: no histogram state", __func__); return RC_ESTATE; }
     RC_HIP(hipSetDevice(ctx->device));
     RC_HIP(hipMemcpyAsync(s->an.hist.p, words, RC_HIST_WORDS * 4, hipMemcpyHostToDevice, s->cur));
     RC_HIP(hipStreamSynchronize(s->cur));
@@ -868,7 +865,7 @@ extern "C" int rcflow_histogram_write(rc_ctx* ctx, int stream, const int32_t* wo
 extern "C" int rcflow_histogram_reset_dev(rc_ctx* ctx, int stream) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    if (!s->an.hist.p) { rc_set_error("no histogram state: call rcflow_analysis_reset first"); return RC_ESTATE; }
+    if (!s->an.hist.p) { rc_set_error("%s: no histogram state: call rcflow_analysis_reset first", __func__); return RC_ESTATE; }
     RC_HIP(hipSetDevice(ctx->device));
     RC_HIP(hipMemsetAsync(s->an.hist.p, 0, RC_HIST_WORDS * sizeof(int), s->cur));
     s->an.hist_added = 0;
@@ -877,31 +874,32 @@ extern "C" int rcflow_histogram_reset_dev(rc_ctx* ctx, int stream) {
 
 extern "C" int rcflow_histogram_device_ptr(rc_ctx* ctx, int stream, int32_t** d_words) {
     RcSlot* s = rc_slot(ctx, stream);
-    if (!s || !d_words) return RC_EINVAL;
-    if (!s->an.hist.p) { rc_set_error("no histogram state"); return RC_ESTATE; }
+    if (!s) return RC_EINVAL;
+    if (int rc = rc_ptr_check(__func__, "d_words", d_words)) return rc;
+    if (!s->an.hist.p) { rc_set_error("%s: no histogram state", __func__); return RC_ESTATE; }
     *d_words = (int32_t*)s->an.hist.p;
     return RC_OK;
 }
 
-int rc_analysis_ensure(rc_ctx* ctx, RcSlot& s, int w, int h) { return analysis_ensure(ctx, s, w, h, false); }
+int rc_analysis_ensure(const char* who, rc_ctx* ctx, RcSlot& s, int w, int h) { return analysis_ensure(who, ctx, s, w, h, false); }
 
 // framecount < 0: the counter is the slot's device word (an.loopc), incremented by k_loop_count in the same stream
-int rc_classify_accumulate(rc_ctx* ctx, int stream, const float* d_flow, size_t flow_step, int w, int h, int framecount,
+int rc_classify_accumulate(const char* who, rc_ctx* ctx, int stream, const float* d_flow, size_t flow_step, int w, int h, int framecount,
                            float MID, float LOWER, float* d_polar, size_t polar_step, float* d_wclass, size_t wc_step,
                            float* d_out, size_t out_step, uint8_t* d_mask, size_t mask_step) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    int rc = check_flow(d_flow, flow_step, w, h);
-    if (rc) return rc;
-    if ((d_polar && polar_step < (size_t)w * 12) || (d_wclass && wc_step < (size_t)w * 12) ||
-        (d_out && out_step < (size_t)w * 12) || (d_mask && mask_step < (size_t)w)) {
-        rc_set_error("output step smaller than a row");
-        return RC_EINVAL;
-    }
+    const int opt = RC_ARG_OUT | RC_ARG_OPTIONAL;
+    int rc;
+    if ((rc = rc_flow_check(who, "d_flow", d_flow, flow_step, w, h, RC_ARG_IN))) return rc;
+    if ((rc = rc_image_check(who, "d_polar", d_polar, polar_step, w, h, 12, 1, opt))) return rc;
+    if ((rc = rc_image_check(who, "d_wclass", d_wclass, wc_step, w, h, 12, 1, opt))) return rc;
+    if ((rc = rc_image_check(who, "d_out", d_out, out_step, w, h, 12, 1, opt))) return rc;
+    if ((rc = rc_image_check(who, "d_mask", d_mask, mask_step, w, h, 1, 1, opt))) return rc;
     RC_HIP(hipSetDevice(ctx->device));
-    if ((rc = analysis_ensure(ctx, *s, w, h, false))) return rc;
+    if ((rc = analysis_ensure(who, ctx, *s, w, h, false))) return rc;
     const int* d_fc = framecount < 0 ? (const int*)s->an.loopc.p : nullptr;
-    if (framecount < 0 && !d_fc) { rc_set_error("no device frame counter"); return RC_ESTATE; }
+    if (framecount < 0 && !d_fc) { rc_set_error("%s: no device frame counter", who); return RC_ESTATE; }
     ClassifyArgs a = {d_flow, flow_step, w, h, framecount, d_fc, MID, LOWER, (const float*)s->an.thr.p,
                       (float*)s->an.acc.p, d_polar, polar_step, d_wclass, wc_step, d_out, out_step, d_mask, mask_step};
     {
@@ -916,8 +914,8 @@ extern "C" int rcflow_classify_accumulate_dev(rc_ctx* ctx, int stream, const flo
                                               int w, int h, int framecount, float MID, float LOWER,
                                               float* d_polar, size_t polar_step, float* d_wclass, size_t wc_step,
                                               float* d_out, size_t out_step, uint8_t* d_mask, size_t mask_step) {
-    if (framecount < 0) { rc_set_error("negative framecount"); return RC_EINVAL; }
-    return rc_classify_accumulate(ctx, stream, d_flow, flow_step, w, h, framecount, MID, LOWER, d_polar, polar_step, d_wclass,
+    if (framecount < 0) { rc_set_error("%s: negative framecount %d", __func__, framecount); return RC_EINVAL; }
+    return rc_classify_accumulate(__func__, ctx, stream, d_flow, flow_step, w, h, framecount, MID, LOWER, d_polar, polar_step, d_wclass,
                                   wc_step, d_out, out_step, d_mask, mask_step);
 }
 
@@ -933,10 +931,10 @@ int rc_loop_counter(rc_ctx* ctx, RcSlot& s, bool set, int value) {
 }
 // what rcflow_histogram_dev books on the host for one more w x h field (the graph replay of rcflow_frame_loop_step
 // runs the kernels without passing through it)
-int rc_hist_book(RcSlot& s, int w, int h, bool commit) {
+int rc_hist_book(const char* who, RcSlot& s, int w, int h, bool commit) {
     if (s.an.hist_added + (long long)w * h > 0x7fffffffll) {
-        rc_set_error("the flow histogram's int32 counters would wrap (%lld pixels counted): "
-                     "start a new segment with rcflow_histogram_reset_dev", s.an.hist_added);
+        rc_set_error("%s: the flow histogram's int32 counters would wrap (%lld pixels counted): "
+                     "start a new segment with rcflow_histogram_reset_dev", who, s.an.hist_added);
         return RC_ESTATE;
     }
     if (commit) s.an.hist_added += (long long)w * h;
@@ -945,8 +943,9 @@ int rc_hist_book(RcSlot& s, int w, int h, bool commit) {
 
 extern "C" int rcflow_accumulator_read(rc_ctx* ctx, int stream, float* acc) {
     RcSlot* s = rc_slot(ctx, stream);
-    if (!s || !acc) return RC_EINVAL;
-    if (!s->an.acc.p) { rc_set_error("no analysis state"); return RC_ESTATE; }
+    if (!s) return RC_EINVAL;
+    if (int rc = rc_ptr_check(__func__, "acc", acc)) return rc;
+    if (!s->an.acc.p) { rc_set_error("%s: no analysis state", __func__); return RC_ESTATE; }
     RC_HIP(hipSetDevice(ctx->device));
     RC_HIP(hipMemcpyAsync(acc, s->an.acc.p, (size_t)s->an.w * s->an.h * 4, hipMemcpyDeviceToHost, s->cur));
     RC_HIP(hipStreamSynchronize(s->cur));
@@ -957,11 +956,12 @@ extern "C" int rcflow_advect_field_dev(rc_ctx* ctx, int stream, const float* d_f
                                        float dt, int iterations, float UPPER) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    int rc = check_flow(d_flow, flow_step, w, h);
+    int rc = rc_flow_check(__func__, "d_flow", d_flow, flow_step, w, h, RC_ARG_IN);
     if (rc) return rc;
-    if (iterations < 0 || iterations > RC_MAX_ADVECT_ITERATIONS) return RC_EINVAL;   // the reference passes 1 or 100
+    // the reference passes 1 or 100
+    if (iterations < 0 || iterations > RC_MAX_ADVECT_ITERATIONS) { rc_set_error("%s: iterations %d (0..%d)", __func__, iterations, RC_MAX_ADVECT_ITERATIONS); return RC_EINVAL; }
     RC_HIP(hipSetDevice(ctx->device));
-    if ((rc = analysis_ensure(ctx, *s, w, h, false))) return rc;
+    if ((rc = analysis_ensure(__func__, ctx, *s, w, h, false))) return rc;
     {
         RcProfScope ps(ctx, s->cur, RC_K_ADVECT_FIELD, 0, 32. * w * h);
         hipLaunchKernelGGL(k_advect_field, dim3(grid_for((long long)w * h)), dim3(RC_BLOCK), 0, s->cur,
@@ -975,7 +975,7 @@ extern "C" int rcflow_advect_field_dev(rc_ctx* ctx, int stream, const float* d_f
 extern "C" int rcflow_advect_field_read(rc_ctx* ctx, int stream, float* pt_xy, float* dist) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    if (!s->an.pt.p) { rc_set_error("no analysis state"); return RC_ESTATE; }
+    if (!s->an.pt.p) { rc_set_error("%s: no analysis state", __func__); return RC_ESTATE; }
     RC_HIP(hipSetDevice(ctx->device));
     size_t n = (size_t)s->an.w * s->an.h;
     if (pt_xy) RC_HIP(hipMemcpyAsync(pt_xy, s->an.pt.p, n * 8, hipMemcpyDeviceToHost, s->cur));
@@ -984,10 +984,9 @@ extern "C" int rcflow_advect_field_read(rc_ctx* ctx, int stream, float* pt_xy, f
     return RC_OK;
 }
 
-static int thr_ptr(rc_ctx* ctx, RcSlot& s, float UPPER, const float** thr) {
+static int thr_ptr(const char* who, RcSlot& s, float UPPER, const float** thr) {
     *thr = (const float*)s.an.thr.p;
-    if (UPPER < 0 && !s.an.thr.p) { rc_set_error("UPPER<0 needs the slot's analysis state"); return RC_ESTATE; }
-    (void)ctx;
+    if (UPPER < 0 && !s.an.thr.p) { rc_set_error("%s: UPPER<0 needs the slot's analysis state", who); return RC_ESTATE; }
     return RC_OK;
 }
 
@@ -1003,14 +1002,17 @@ extern "C" int rcflow_advect_points_dev(rc_ctx* ctx, int stream, float* d_pts, i
                                         int variant, float* d_trace) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    int rc = check_flow(d_flow, flow_step, w, h);
+    int rc = rc_flow_check(__func__, "d_flow", d_flow, flow_step, w, h, RC_ARG_IN);
     if (rc) return rc;
-    if (n < 0 || (n && !d_pts) || iterations < 0 || iterations > RC_MAX_ADVECT_ITERATIONS || variant < 0 || variant > 4)
+    if (n < 0 || iterations < 0 || iterations > RC_MAX_ADVECT_ITERATIONS || variant < 0 || variant > 4) {
+        rc_set_error("%s: n %d (>= 0), iterations %d (0..%d) or variant %d (0..4)", __func__, n, iterations, RC_MAX_ADVECT_ITERATIONS, variant);
         return RC_EINVAL;
+    }
     if (n == 0) return RC_OK;
+    if ((rc = rc_ptr_check(__func__, "d_pts", d_pts))) return rc;
     RC_HIP(hipSetDevice(ctx->device));
     const float* thr;
-    if ((rc = thr_ptr(ctx, *s, UPPER, &thr))) return rc;
+    if ((rc = thr_ptr(__func__, *s, UPPER, &thr))) return rc;
     rc_advect_points_launch(ctx, s->cur, d_pts, n, d_flow, flow_step, w, h, dt, iterations, UPPER, thr, variant, d_trace);
     RC_HIP(hipGetLastError());
     return RC_OK;
@@ -1020,12 +1022,12 @@ extern "C" int rcflow_get_delta_field_dev(rc_ctx* ctx, int stream, float* d_pt, 
                                           size_t flow_step, int w, int h, float dt, float UPPER) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    int rc = check_flow(d_flow, flow_step, w, h);
-    if (rc) return rc;
-    if (!d_pt || pt_step < (size_t)w * 8) return RC_EINVAL;
+    int rc;
+    if ((rc = rc_flow_check(__func__, "d_flow", d_flow, flow_step, w, h, RC_ARG_IN))) return rc;
+    if ((rc = rc_image_check(__func__, "d_pt", d_pt, pt_step, w, h, 8, 1, RC_ARG_OUT))) return rc;
     RC_HIP(hipSetDevice(ctx->device));
     const float* thr;
-    if ((rc = thr_ptr(ctx, *s, UPPER, &thr))) return rc;
+    if ((rc = thr_ptr(__func__, *s, UPPER, &thr))) return rc;
     hipLaunchKernelGGL(k_get_delta_field, dim3(grid_for((long long)w * h)), dim3(RC_BLOCK), 0, s->cur, d_pt, pt_step,
                        d_flow, flow_step, w, h, dt, UPPER, thr);
     RC_HIP(hipGetLastError());
@@ -1044,10 +1046,10 @@ static int flow_stats(rc_ctx* ctx, RcSlot& s, const float* d_flow, size_t step, 
     return RC_OK;
 }
 
-static int postop(rc_ctx* ctx, int stream, float* d_flow, size_t step, int w, int h, int mode) {
+static int postop(const char* who, rc_ctx* ctx, int stream, float* d_flow, size_t step, int w, int h, int mode) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    int rc = check_flow(d_flow, step, w, h);
+    int rc = rc_flow_check(who, "d_flow", d_flow, step, w, h, RC_ARG_OUT);
     if (rc) return rc;
     RC_HIP(hipSetDevice(ctx->device));
     double divx = (double)w * h, divy = (double)w * h;
@@ -1069,19 +1071,21 @@ static int postop(rc_ctx* ctx, int stream, float* d_flow, size_t step, int w, in
 }
 
 extern "C" int rcflow_subtract_average_dev(rc_ctx* ctx, int stream, float* d_flow, size_t step, int w, int h) {
-    return postop(ctx, stream, d_flow, step, w, h, 0);
+    return postop(__func__, ctx, stream, d_flow, step, w, h, 0);
 }
 extern "C" int rcflow_subtract_mean_magnitude_dev(rc_ctx* ctx, int stream, float* d_flow, size_t step, int w, int h) {
-    return postop(ctx, stream, d_flow, step, w, h, 1);
+    return postop(__func__, ctx, stream, d_flow, step, w, h, 1);
 }
 extern "C" int rcflow_stabilizer_dev(rc_ctx* ctx, int stream, float* d_flow, size_t step, int w, int h) {
-    return postop(ctx, stream, d_flow, step, w, h, 2);
+    return postop(__func__, ctx, stream, d_flow, step, w, h, 2);
 }
 
 extern "C" int rcflow_window_mean_dev(rc_ctx* ctx, int stream, float* d_avg, float* d_slot, const float* d_cur,
                                       size_t n, int window) {
     RcSlot* s = rc_slot(ctx, stream);
-    if (!s || !d_avg || !d_slot || !d_cur || window < 1) return RC_EINVAL;
+    if (!s) return RC_EINVAL;
+    if (!d_avg || !d_slot || !d_cur) { rc_set_error("%s: a null pointer among d_avg, d_slot, d_cur", __func__); return RC_EINVAL; }
+    if (window < 1) { rc_set_error("%s: window %d (>= 1)", __func__, window); return RC_EINVAL; }
     RC_HIP(hipSetDevice(ctx->device));
     float inv = (float)(1. / (float)window);
     hipLaunchKernelGGL(k_window_mean, dim3(grid_for((long long)n)), dim3(RC_BLOCK), 0, s->cur, d_avg, d_slot, d_cur, n, inv);
@@ -1093,9 +1097,10 @@ extern "C" int rcflow_vector_to_color_dev(rc_ctx* ctx, int stream, const float* 
                                           uint8_t* d_hsv, size_t hsv_step, float* max_io) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    int rc = check_flow(d_flow, step, w, h);
-    if (rc) return rc;
-    if (!d_hsv || hsv_step < (size_t)w * 3 || !max_io) return RC_EINVAL;
+    int rc;
+    if ((rc = rc_flow_check(__func__, "d_flow", d_flow, step, w, h, RC_ARG_IN))) return rc;
+    if ((rc = rc_image_check(__func__, "d_hsv", d_hsv, hsv_step, w, h, 3, 1, RC_ARG_OUT))) return rc;
+    if ((rc = rc_ptr_check(__func__, "max_io", max_io))) return rc;
     RC_HIP(hipSetDevice(ctx->device));
     if ((rc = flow_stats(ctx, *s, d_flow, step, 0, 0, w, h))) return rc;
     {
@@ -1114,9 +1119,10 @@ extern "C" int rcflow_shear_rate_to_color_dev(rc_ctx* ctx, int stream, const flo
                                               uint8_t* d_hsv, size_t hsv_step, float* max_io) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    int rc = check_flow(d_flow, step, w, h);
-    if (rc) return rc;
-    if (!d_hsv || hsv_step < (size_t)w * 3 || !max_io) return RC_EINVAL;
+    int rc;
+    if ((rc = rc_flow_check(__func__, "d_flow", d_flow, step, w, h, RC_ARG_IN))) return rc;
+    if ((rc = rc_image_check(__func__, "d_hsv", d_hsv, hsv_step, w, h, 3, 1, RC_ARG_OUT))) return rc;
+    if ((rc = rc_ptr_check(__func__, "max_io", max_io))) return rc;
     if (w <= 20 || h <= 20) { *max_io = 0.f; return RC_OK; }
     RC_HIP(hipSetDevice(ctx->device));
     if ((rc = rc_buf_ensure(s->an.scratch, (4 * 2048 + 8) * sizeof(double)))) return rc;
@@ -1141,10 +1147,10 @@ extern "C" int rcflow_create_edges_dev(rc_ctx* ctx, int stream, const uint8_t* d
                                        uint8_t* d_out, size_t out_step) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    if (!d_mask || !d_out || w <= 0 || h <= 0 || mask_step < (size_t)w || out_step < (size_t)w || d_mask == d_out) {
-        rc_set_error("bad mask arguments (in-place is not supported)");
-        return RC_EINVAL;
-    }
+    int rc;
+    if ((rc = rc_image_check(__func__, "d_mask", d_mask, mask_step, w, h, 1, 1, RC_ARG_IN))) return rc;
+    if ((rc = rc_image_check(__func__, "d_out", d_out, out_step, w, h, 1, 1, RC_ARG_OUT))) return rc;
+    if (d_mask == d_out) { rc_set_error("%s: d_out is d_mask (in-place is not supported)", __func__); return RC_EINVAL; }
     RC_HIP(hipSetDevice(ctx->device));
     {
         RcProfScope ps(ctx, s->cur, RC_K_EDGES, 0, 2. * w * h);
@@ -1155,14 +1161,18 @@ extern "C" int rcflow_create_edges_dev(rc_ctx* ctx, int stream, const uint8_t* d
     return RC_OK;
 }
 
+// the arguments of the four resize entry points: the 8UC3 source, the destination of out_ch channels and its own size
+static int rc_resize_check(const char* who, const uint8_t* d_bgr, size_t step, int sw, int sh, const char* out_name, const uint8_t* d_out,
+                           size_t out_step, int dw, int dh, int out_ch) {
+    if (int rc = rc_image_check(who, "d_bgr", d_bgr, step, sw, sh, 3, 1, RC_ARG_IN)) return rc;
+    return rc_image_check(who, out_name, d_out, out_step, dw, dh, out_ch, 1, RC_ARG_OUT);
+}
+
 extern "C" int rcflow_resize_bgr_to_gray_dev(rc_ctx* ctx, int stream, const uint8_t* d_bgr, size_t step, int sw, int sh,
                                              uint8_t* d_gray, size_t gray_step, int dw, int dh) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    if (!d_bgr || !d_gray || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || step < (size_t)sw * 3 || gray_step < (size_t)dw) {
-        rc_set_error("bad frame arguments");
-        return RC_EINVAL;
-    }
+    if (int rc = rc_resize_check(__func__, d_bgr, step, sw, sh, "d_gray", d_gray, gray_step, dw, dh, 1)) return rc;
     RC_HIP(hipSetDevice(ctx->device));
     double scale_x = 1. / ((double)dw / sw), scale_y = 1. / ((double)dh / sh);
     {
@@ -1178,10 +1188,7 @@ extern "C" int rcflow_resize_bgr_dev(rc_ctx* ctx, int stream, const uint8_t* d_b
                                      uint8_t* d_out, size_t out_step, int dw, int dh) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    if (!d_bgr || !d_out || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || step < (size_t)sw * 3 || out_step < (size_t)dw * 3) {
-        rc_set_error("bad frame arguments");
-        return RC_EINVAL;
-    }
+    if (int rc = rc_resize_check(__func__, d_bgr, step, sw, sh, "d_out", d_out, out_step, dw, dh, 3)) return rc;
     RC_HIP(hipSetDevice(ctx->device));
     double scale_x = 1. / ((double)dw / sw), scale_y = 1. / ((double)dh / sh);
     {
@@ -1294,7 +1301,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_hsv_to_bgr(const float* __restrict
 // for r, g, b as float literals and passes them through linear_colormap (float interp1 onto
 // linspace(0,1,256), then convertTo(8U, 255)).
 extern "C" int rcflow_jet_lut(uint8_t* lut_bgr) {
-    if (!lut_bgr) return RC_EINVAL;
+    if (int rc = rc_ptr_check(__func__, "lut_bgr", lut_bgr)) return rc;
     float tab[3][256], X[256];
     const float step = (1.f - 0.f) / (256 - 1);
     for (int i = 0; i < 256; i++) {
@@ -1338,12 +1345,13 @@ extern "C" int rcflow_streamline_display_dev(rc_ctx* ctx, int stream, int which,
                                              float* max_out) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    if (!s->an.pt.p || !s->an.dist.p) { rc_set_error("no streamline field in this slot (rcflow_advect_field_dev first)"); return RC_ESTATE; }
+    if (!s->an.pt.p || !s->an.dist.p) { rc_set_error("%s: no streamline field in this slot (rcflow_advect_field_dev first)", __func__); return RC_ESTATE; }
     const int w = s->an.w, h = s->an.h;
-    if (which < 0 || which > 2 || !d_bgr || bgr_step < (size_t)w * 3) { rc_set_error("bad display arguments"); return RC_EINVAL; }
-    RC_HIP(hipSetDevice(ctx->device));
-    int rc = display_lut(*s);
+    if (which < 0 || which > 2) { rc_set_error("%s: which %d (0..2)", __func__, which); return RC_EINVAL; }
+    int rc = rc_image_check(__func__, "d_bgr", d_bgr, bgr_step, w, h, 3, 1, RC_ARG_OUT);
     if (rc) return rc;
+    RC_HIP(hipSetDevice(ctx->device));
+    if ((rc = display_lut(*s))) return rc;
     unsigned int* key = (unsigned int*)((uint8_t*)s->an.jet.p + 768);
     RC_HIP(hipMemsetAsync(key, 0, 4, s->cur));
     const size_t n = (size_t)w * h;
@@ -1369,9 +1377,9 @@ extern "C" int rcflow_streamline_display_dev(rc_ctx* ctx, int stream, int which,
 extern "C" int rcflow_streamline_positions_dev(rc_ctx* ctx, int stream, float* d_density, size_t density_step) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    if (!s->an.pt.p) { rc_set_error("no streamline field in this slot"); return RC_ESTATE; }
+    if (!s->an.pt.p) { rc_set_error("%s: no streamline field in this slot", __func__); return RC_ESTATE; }
     const int w = s->an.w, h = s->an.h;
-    if (!d_density || density_step < (size_t)w * 12) return RC_EINVAL;
+    if (int rc = rc_image_check(__func__, "d_density", d_density, density_step, w, h, 12, 1, RC_ARG_OUT)) return rc;
     RC_HIP(hipSetDevice(ctx->device));
     {
         RcProfScope ps(ctx, s->cur, RC_K_DISPLAY, 0, 20. * w * h);
@@ -1386,7 +1394,9 @@ extern "C" int rcflow_hsv_to_bgr_dev(rc_ctx* ctx, int stream, const float* d_hsv
                                      float* d_bgr, size_t bgr_step) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    if (!d_hsv || !d_bgr || w <= 0 || h <= 0 || hsv_step < (size_t)w * 12 || bgr_step < (size_t)w * 12) return RC_EINVAL;
+    int rc;
+    if ((rc = rc_image_check(__func__, "d_hsv", d_hsv, hsv_step, w, h, 12, 1, RC_ARG_IN))) return rc;
+    if ((rc = rc_image_check(__func__, "d_bgr", d_bgr, bgr_step, w, h, 12, 1, RC_ARG_OUT))) return rc;
     RC_HIP(hipSetDevice(ctx->device));
     {
         RcProfScope ps(ctx, s->cur, RC_K_HSV2BGR, 0, 24. * w * h);
@@ -1399,7 +1409,8 @@ extern "C" int rcflow_hsv_to_bgr_dev(rc_ctx* ctx, int stream, const float* d_hsv
 
 extern "C" int rcflow_analysis_size(rc_ctx* ctx, int stream, int* w, int* h) {
     RcSlot* s = rc_slot(ctx, stream);
-    if (!s || !w || !h) return RC_EINVAL;
+    if (!s) return RC_EINVAL;
+    if (!w || !h) { rc_set_error("%s: a null pointer among w, h", __func__); return RC_EINVAL; }
     *w = s->an.w; *h = s->an.h;
     return RC_OK;
 }
@@ -1494,15 +1505,12 @@ void rc_area_tab(int ssize, int dsize, double scale, std::vector<int>& start, st
 }
 
 // out_ch = 1: gray (rcflow_resize_area_bgr_to_gray_dev); 3: the resized colour frame (rcflow_resize_area_bgr_dev)
-static int resize_area_run(rc_ctx* ctx, int stream, const uint8_t* d_bgr, size_t step, int sw, int sh, uint8_t* d_gray,
+static int resize_area_run(const char* who, const char* out_name, rc_ctx* ctx, int stream, const uint8_t* d_bgr, size_t step, int sw, int sh, uint8_t* d_gray,
                            size_t gray_step, int dw, int dh, int out_ch) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    if (!d_bgr || !d_gray || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || step < (size_t)sw * 3 || gray_step < (size_t)dw * out_ch) {
-        rc_set_error("bad frame arguments");
-        return RC_EINVAL;
-    }
-    if (dw > sw || dh > sh) { rc_set_error("INTER_AREA is implemented for shrinking only (the reference's use)"); return RC_EINVAL; }
+    if (int rc = rc_resize_check(who, d_bgr, step, sw, sh, out_name, d_gray, gray_step, dw, dh, out_ch)) return rc;
+    if (dw > sw || dh > sh) { rc_set_error("%s: INTER_AREA is implemented for shrinking only (the reference's use)", who); return RC_EINVAL; }
     RC_HIP(hipSetDevice(ctx->device));
     const double scale_x = (double)sw / dw, scale_y = (double)sh / dh;
     const int isx = (int)nearbyint(scale_x), isy = (int)nearbyint(scale_y);
@@ -1547,11 +1555,11 @@ static int resize_area_run(rc_ctx* ctx, int stream, const uint8_t* d_bgr, size_t
 
 extern "C" int rcflow_resize_area_bgr_to_gray_dev(rc_ctx* ctx, int stream, const uint8_t* d_bgr, size_t step, int sw,
                                                   int sh, uint8_t* d_gray, size_t gray_step, int dw, int dh) {
-    return resize_area_run(ctx, stream, d_bgr, step, sw, sh, d_gray, gray_step, dw, dh, 1);
+    return resize_area_run(__func__, "d_gray", ctx, stream, d_bgr, step, sw, sh, d_gray, gray_step, dw, dh, 1);
 }
 extern "C" int rcflow_resize_area_bgr_dev(rc_ctx* ctx, int stream, const uint8_t* d_bgr, size_t step, int sw, int sh,
                                           uint8_t* d_out, size_t out_step, int dw, int dh) {
-    return resize_area_run(ctx, stream, d_bgr, step, sw, sh, d_out, out_step, dw, dh, 3);
+    return resize_area_run(__func__, "d_out", ctx, stream, d_bgr, step, sw, sh, d_out, out_step, dw, dh, 3);
 }
 
 // create_output(subframe, outmask) ripcurrents_module.cpp:225-244 (ripcurrents.cpp:487-505): the frame the
@@ -1567,10 +1575,9 @@ extern "C" int rcflow_create_output_dev(rc_ctx* ctx, int stream, uint8_t* d_subf
                                         const uint8_t* d_outmask, size_t mask_step, int w, int h) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    if (!d_subframe_bgr || !d_outmask || w <= 0 || h <= 0 || step < (size_t)w * 3 || mask_step < (size_t)w) {
-        rc_set_error("bad frame / mask arguments");
-        return RC_EINVAL;
-    }
+    int rc;
+    if ((rc = rc_image_check(__func__, "d_subframe_bgr", d_subframe_bgr, step, w, h, 3, 1, RC_ARG_OUT))) return rc;
+    if ((rc = rc_image_check(__func__, "d_outmask", d_outmask, mask_step, w, h, 1, 1, RC_ARG_IN))) return rc;
     RC_HIP(hipSetDevice(ctx->device));
     {
         RcProfScope ps(ctx, s->cur, RC_K_OVERLAY, 0, 7. * w * h);

@@ -161,9 +161,10 @@ extern "C" int rcflow_corners_dev(rc_ctx* ctx, int stream, const uint8_t* d_gray
     static const char* who = "rcflow_corners_dev";
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    if (!d_gray || !d_pts || !d_scores || w <= 0 || h <= 0 || step < (size_t)w) { rc_set_error("%s: bad image or output arguments", who); return RC_EINVAL; }
-    int rc = rc_corner_check(who, w, h, cells_x, cells_y, margin, min_score);
-    if (rc) return rc;
+    int rc;
+    if ((rc = rc_image_check(who, "d_gray", d_gray, step, w, h, 1, 1, RC_ARG_IN))) return rc;
+    if (!d_pts || !d_scores) { rc_set_error("%s: a null pointer among d_pts, d_scores", who); return RC_EINVAL; }
+    if ((rc = rc_corner_check(who, w, h, cells_x, cells_y, margin, min_score))) return rc;
     if ((rc = rc_fits_context(who, ctx, w, h))) return rc;
     RC_HIP(hipSetDevice(ctx->device));
     rc_corner_launch(ctx, s->cur, d_gray, step, w, h, cells_x, cells_y, margin, min_score, d_pts, d_scores);

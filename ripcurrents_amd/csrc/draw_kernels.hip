@@ -220,14 +220,11 @@ extern "C" int rcflow_draw_dev(rc_ctx* ctx, int stream, uint8_t* d_img, size_t s
                                const rc_draw_prim* d_prims, int n, unsigned long long* d_skipped) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    if ((channels != 1 && channels != 3) || !d_img || w <= 0 || h <= 0 || step < (size_t)channels * w || n < 0 || (n && !d_prims)) {
-        rc_set_error("rcflow_draw_dev: bad image or list argument (channels 1 or 3, step >= channels * w, n >= 0)");
-        return RC_EINVAL;
-    }
-    if (((uintptr_t)d_prims & 15) || ((uintptr_t)d_skipped & 7)) {
-        rc_set_error("rcflow_draw_dev: d_prims must be 16-byte aligned, d_skipped 8-byte aligned");
-        return RC_EINVAL;
-    }
+    if ((channels != 1 && channels != 3) || n < 0) { rc_set_error("%s: channels %d (1 or 3) or n %d (>= 0)", __func__, channels, n); return RC_EINVAL; }
+    int rc;
+    if ((rc = rc_image_check(__func__, "d_img", d_img, step, w, h, channels, 1, RC_ARG_OUT))) return rc;
+    if ((rc = rc_ptr_check(__func__, "d_prims", d_prims, 16, n ? RC_ARG_IN : RC_ARG_OPTIONAL))) return rc;
+    if ((rc = rc_ptr_check(__func__, "d_skipped", d_skipped, 8, RC_ARG_OUT | RC_ARG_OPTIONAL))) return rc;
     if (w > RC_DRAW_COORD_MAX + 1 || h > RC_DRAW_COORD_MAX + 1 || n > RC_DRAW_MAX_PRIMS) {
         rc_set_error("rcflow_draw_dev: images up to %d x %d and %d primitives are supported", RC_DRAW_COORD_MAX + 1, RC_DRAW_COORD_MAX + 1,
                      RC_DRAW_MAX_PRIMS);
@@ -245,10 +242,11 @@ extern "C" int rcflow_trace_prims_dev(rc_ctx* ctx, int stream, const float* d_st
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
     const int per = d_start ? iters : iters - 1;
-    if (n < 0 || iters < 1 || iters > DR_MAX_TRACE_ITERS || (n && per && (!d_trace || !d_prims)) || ((uintptr_t)d_prims & 15)) {
-        rc_set_error("rcflow_trace_prims_dev: bad arguments");
-        return RC_EINVAL;
-    }
+    if (n < 0 || iters < 1 || iters > DR_MAX_TRACE_ITERS) { rc_set_error("%s: n %d (>= 0) or iters %d (1..%d)", __func__, n, iters, DR_MAX_TRACE_ITERS); return RC_EINVAL; }
+    const int lines = n && per ? 0 : RC_ARG_OPTIONAL;   // a call that writes no line may pass null lists
+    int rc;
+    if ((rc = rc_ptr_check(__func__, "d_trace", d_trace, 1, RC_ARG_IN | lines))) return rc;
+    if ((rc = rc_ptr_check(__func__, "d_prims", d_prims, 16, RC_ARG_OUT | lines))) return rc;
     if ((long long)n * per > RC_DRAW_MAX_PRIMS) {
         rc_set_error("rcflow_trace_prims_dev: more than %d lines", RC_DRAW_MAX_PRIMS);
         return RC_ESIZE;

@@ -464,7 +464,10 @@ extern "C" int rcflow_fit_motion_dev(rc_ctx* ctx, int stream, const float* d_p, 
     if (!s) return RC_EINVAL;
     int rc = rc_fit_check(who, n, w, h, prm);
     if (rc) return rc;
-    if (!d_result || (n > 0 && (!d_p || !d_q || !d_status || !d_inlier))) { rc_set_error("%s: a null point, status or output pointer", who); return RC_EINVAL; }
+    if (!d_result || (n > 0 && (!d_p || !d_q || !d_status || !d_inlier))) {
+        rc_set_error("%s: a null pointer among d_result and, for n > 0, d_p, d_q, d_status, d_inlier", who);
+        return RC_EINVAL;
+    }
     RC_HIP(hipSetDevice(ctx->device));
     if (!s->fit_ws.p) {
         if ((rc = rc_buf_ensure(s->fit_ws, 16))) return rc;

@@ -310,23 +310,30 @@ void rc_lk_track(rc_ctx* ctx, hipStream_t cur_stream, const RcLkPyr& ref, const 
 }
 
 extern "C" int rcflow_pyrlk_levels(int w, int h, int win_w, int win_h, int max_level) {
-    if (w < 1 || h < 1 || win_w < 3 || win_h < 3 || max_level < 0) return RC_EINVAL;
+    if (w < 1 || h < 1 || win_w < 3 || win_h < 3 || max_level < 0) {
+        rc_set_error("%s: size %d x %d, window %d x %d (>= 3) or max_level %d (>= 0)", __func__, w, h, win_w, win_h, max_level);
+        return RC_EINVAL;
+    }
     return lk_levels(w, h, win_w, win_h, max_level);
 }
 
-extern "C" int rcflow_pyrlk_dev(rc_ctx* ctx, int stream, const uint8_t* d_prev, size_t prev_step, const uint8_t* d_next,
-                                size_t next_step, int w, int h, const float* d_prev_pts, float* d_next_pts, int npts,
-                                uint8_t* d_status, float* d_err, int win_w, int win_h, int max_level, int crit_type,
-                                int max_count, double epsilon, int flags, double min_eig_threshold) {
-    RcSlot* s = rc_slot(ctx, stream);
-    if (!s) return RC_EINVAL;
-    if (!d_prev || !d_next || npts < 0 || (npts > 0 && (!d_prev_pts || !d_next_pts || !d_status)) || w < 1 || h < 1 ||
-        prev_step < (size_t)w || next_step < (size_t)w || win_w <= 2 || win_h <= 2 || max_level < 0) {
-        rc_set_error("bad PyrLK arguments");
-        return RC_EINVAL;
-    }
-    if (max_level >= RC_LK_MAX_LEVELS || (size_t)win_w * win_h > 128 * 128) {
-        rc_set_error("PyrLK: maxLevel < %d and windows up to 128x128 are supported", RC_LK_MAX_LEVELS);
+// the images and point lists of both forms, under the names of the device form or of the host form
+static int lk_args_check(const char* who, bool dev, const void* prev, size_t prev_step, const void* next, size_t next_step, int w, int h,
+                         const void* prev_pts, const void* next_pts, int npts, const void* status) {
+    int rc;
+    if ((rc = rc_image_check(who, dev ? "d_prev" : "prev", prev, prev_step, w, h, 1, 1, RC_ARG_IN))) return rc;
+    if ((rc = rc_image_check(who, dev ? "d_next" : "next", next, next_step, w, h, 1, 1, RC_ARG_IN))) return rc;
+    if (npts < 0) { rc_set_error("%s: npts %d (>= 0)", who, npts); return RC_EINVAL; }
+    if (npts == 0 || (prev_pts && next_pts && status)) return RC_OK;
+    rc_set_error("%s: a null pointer among %s", who, dev ? "d_prev_pts, d_next_pts, d_status" : "prev_pts, next_pts, status");
+    return RC_EINVAL;
+}
+
+static int pyrlk_run(const char* who, rc_ctx* ctx, RcSlot* s, const uint8_t* d_prev, size_t prev_step, const uint8_t* d_next, size_t next_step,
+                     int w, int h, const float* d_prev_pts, float* d_next_pts, int npts, uint8_t* d_status, float* d_err, int win_w, int win_h,
+                     int max_level, int crit_type, int max_count, double epsilon, int flags, double min_eig_threshold) {
+    if (win_w <= 2 || win_h <= 2 || max_level < 0 || max_level >= RC_LK_MAX_LEVELS || (size_t)win_w * win_h > 128 * 128) {
+        rc_set_error("%s: PyrLK windows of 3 x 3 up to 128 x 128 and 0 <= max_level < %d are supported", who, RC_LK_MAX_LEVELS);
         return RC_EINVAL;
     }
     if (npts == 0) return RC_OK;
@@ -352,6 +359,17 @@ extern "C" int rcflow_pyrlk_dev(rc_ctx* ctx, int stream, const uint8_t* d_prev, 
     return RC_OK;
 }
 
+extern "C" int rcflow_pyrlk_dev(rc_ctx* ctx, int stream, const uint8_t* d_prev, size_t prev_step, const uint8_t* d_next,
+                                size_t next_step, int w, int h, const float* d_prev_pts, float* d_next_pts, int npts,
+                                uint8_t* d_status, float* d_err, int win_w, int win_h, int max_level, int crit_type,
+                                int max_count, double epsilon, int flags, double min_eig_threshold) {
+    RcSlot* s = rc_slot(ctx, stream);
+    if (!s) return RC_EINVAL;
+    if (int rc = lk_args_check(__func__, true, d_prev, prev_step, d_next, next_step, w, h, d_prev_pts, d_next_pts, npts, d_status)) return rc;
+    return pyrlk_run(__func__, ctx, s, d_prev, prev_step, d_next, next_step, w, h, d_prev_pts, d_next_pts, npts, d_status, d_err, win_w, win_h,
+                     max_level, crit_type, max_count, epsilon, flags, min_eig_threshold);
+}
+
 // Host-pointer form (what the cv:: signature hands over): copy in, track, copy out, blocking.
 extern "C" int rcflow_pyrlk_u8(rc_ctx* ctx, int stream, const uint8_t* prev, size_t prev_step, const uint8_t* next,
                                size_t next_step, int w, int h, const float* prev_pts, float* next_pts, int npts,
@@ -359,16 +377,12 @@ extern "C" int rcflow_pyrlk_u8(rc_ctx* ctx, int stream, const uint8_t* prev, siz
                                int max_count, double epsilon, int flags, double min_eig_threshold) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    if (!prev || !next || npts < 0 || (npts > 0 && (!prev_pts || !next_pts || !status)) || w < 1 || h < 1 ||
-        prev_step < (size_t)w || next_step < (size_t)w) {
-        rc_set_error("bad PyrLK arguments");
-        return RC_EINVAL;
-    }
+    int rc = lk_args_check(__func__, false, prev, prev_step, next, next_step, w, h, prev_pts, next_pts, npts, status);
+    if (rc) return rc;
     if (npts == 0) return RC_OK;
     RC_HIP(hipSetDevice(ctx->device));
     const size_t img = (size_t)w * h, pts = (size_t)npts * 8;
-    int rc = rc_buf_ensure(s->stage_u8, 2 * img);
-    if (rc) return rc;
+    if ((rc = rc_buf_ensure(s->stage_u8, 2 * img))) return rc;
     if ((rc = rc_buf_ensure(s->stage_f32[2], 2 * pts + (size_t)npts * 4 + npts))) return rc;
     uint8_t* d_img = (uint8_t*)s->stage_u8.p;
     char* d = (char*)s->stage_f32[2].p;
@@ -376,9 +390,9 @@ extern "C" int rcflow_pyrlk_u8(rc_ctx* ctx, int stream, const uint8_t* prev, siz
     RC_HIP(hipMemcpy2DAsync(d_img + img, w, next, next_step, w, h, hipMemcpyHostToDevice, s->cur));
     RC_HIP(hipMemcpyAsync(d, prev_pts, pts, hipMemcpyHostToDevice, s->cur));
     if (flags & 4) RC_HIP(hipMemcpyAsync(d + pts, next_pts, pts, hipMemcpyHostToDevice, s->cur));
-    rc = rcflow_pyrlk_dev(ctx, stream, d_img, w, d_img + img, w, w, h, (const float*)d, (float*)(d + pts), npts,
-                          (uint8_t*)(d + 2 * pts + (size_t)npts * 4), err ? (float*)(d + 2 * pts) : nullptr, win_w, win_h, max_level,
-                          crit_type, max_count, epsilon, flags, min_eig_threshold);
+    rc = pyrlk_run(__func__, ctx, s, d_img, w, d_img + img, w, w, h, (const float*)d, (float*)(d + pts), npts,
+                   (uint8_t*)(d + 2 * pts + (size_t)npts * 4), err ? (float*)(d + 2 * pts) : nullptr, win_w, win_h, max_level, crit_type,
+                   max_count, epsilon, flags, min_eig_threshold);
     if (rc) return rc;
     RC_HIP(hipMemcpyAsync(next_pts, d + pts, pts, hipMemcpyDeviceToHost, s->cur));
     if (err) RC_HIP(hipMemcpyAsync(err, d + 2 * pts, (size_t)npts * 4, hipMemcpyDeviceToHost, s->cur));

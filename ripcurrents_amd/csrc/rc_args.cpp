@@ -44,6 +44,15 @@ int RcArgs::check() const {
     return RC_OK;
 }
 
+int rc_clip_check(const char* who, const char* name, const void* p, size_t frame_stride, size_t step, int n, int w, int h, int bpp, int align,
+                  int flags) {
+    if (int rc = rc_image_check(who, name, p, step, w, h, bpp, align, flags)) return rc;
+    const size_t frame = step * (size_t)(h - 1) + (size_t)w * bpp;   // the range of one frame
+    if (!p || n <= 1 || frame_stride >= frame) return RC_OK;
+    rc_set_error("%s: bad clip argument %s (a frame stride of %zu bytes below the %zu of a frame)", who, name, frame_stride, frame);
+    return RC_EINVAL;
+}
+
 int rc_prims_check(const char* who, const void* d_prims, int thickness, int disc_radius) {
     if (d_prims && !((uintptr_t)d_prims & 3) && thickness >= 1 && thickness <= RC_DRAW_MAX_THICKNESS && disc_radius >= 0 &&
         disc_radius <= RC_DRAW_COORD_MAX)

@@ -61,6 +61,24 @@ inline int rc_image_check(const char* who, const char* name, const void* p, size
     return a.check();
 }
 
+// a pointer alone: not null unless optional, a multiple of its alignment.  Nothing is asked of what lies behind it
+inline int rc_ptr_check(const char* who, const char* name, const void* p, int align = 1, int flags = RC_ARG_IN) {
+    RcArgs a(who, 1, 1);
+    a.array(name, p, 0, align, flags);
+    return a.check();
+}
+
+// a flow field as the entry points older than this layer ask it: rows of float2, the step a multiple of 8, nothing asked of
+// the base (an open point of DESIGN.md, kept as it was found)
+inline int rc_flow_check(const char* who, const char* name, const void* p, size_t step, int w, int h, int flags) {
+    return rc_image_check(who, name, p, step, w, h, 8, 8, flags | RC_ARG_ANY_BASE);
+}
+
+// a run of n images frame_stride bytes apart: the first frame's form, and for n > 1 a stride of at least one frame's range.
+// The bounds on n stay with each caller
+int rc_clip_check(const char* who, const char* name, const void* p, size_t frame_stride, size_t step, int n, int w, int h, int bpp, int align,
+                  int flags);
+
 // the first lines of every *_prims_dev: d_prims not null and 4-byte aligned, thickness 1..RC_DRAW_MAX_THICKNESS, disc_radius
 // 0..RC_DRAW_COORD_MAX
 int rc_prims_check(const char* who, const void* d_prims, int thickness, int disc_radius);

@@ -415,12 +415,12 @@ void rc_buf_free(RcBuf& b);
 RcSlot* rc_slot(rc_ctx* ctx, int stream);
 void rc_graph_drop(RcGraphCache& g);
 // analysis_kernels.hip, for rcflow_frame_loop_step
-int rc_classify_accumulate(rc_ctx* ctx, int stream, const float* d_flow, size_t flow_step, int w, int h, int framecount,
+int rc_classify_accumulate(const char* who, rc_ctx* ctx, int stream, const float* d_flow, size_t flow_step, int w, int h, int framecount,
                            float MID, float LOWER, float* d_polar, size_t polar_step, float* d_wclass, size_t wc_step,
                            float* d_out, size_t out_step, uint8_t* d_mask, size_t mask_step);
 int rc_loop_counter(rc_ctx* ctx, RcSlot& s, bool set, int value);
-int rc_hist_book(RcSlot& s, int w, int h, bool commit);
-int rc_analysis_ensure(rc_ctx* ctx, RcSlot& s, int w, int h);
+int rc_hist_book(const char* who, RcSlot& s, int w, int h, bool commit);
+int rc_analysis_ensure(const char* who, rc_ctx* ctx, RcSlot& s, int w, int h);
 // computeResizeAreaTab (resize.cpp) grouped by destination index (analysis_kernels.hip)
 void rc_area_tab(int ssize, int dsize, double scale, std::vector<int>& start, std::vector<int>& si, std::vector<float>& alpha);
 // the zeroing of a product's state: memsets of the buffers that are allocated on `cur`, then the event

@@ -2,6 +2,7 @@
 // Farneback entry points.  See include/rcflow.h for the reference interfaces replaced.
 
 #include <cfloat>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -140,13 +141,13 @@ static void prof_resolve(rc_ctx* ctx) {
 }
 
 extern "C" int rcflow_profile_enable(rc_ctx* ctx, int on) {
-    if (!ctx) return RC_EINVAL;
+    if (int rc = rc_ptr_check(__func__, "ctx", ctx)) return rc;
     if (!on) prof_resolve(ctx);
     ctx->prof_on = on ? 1 : 0;
     return RC_OK;
 }
 extern "C" int rcflow_profile_reset(rc_ctx* ctx) {
-    if (!ctx) return RC_EINVAL;
+    if (int rc = rc_ptr_check(__func__, "ctx", ctx)) return rc;
     prof_resolve(ctx);
     ctx->prof_ms.assign(ctx->prof_ms.size(), 0.);
     ctx->prof_bytes.assign(ctx->prof_bytes.size(), 0.);
@@ -156,7 +157,7 @@ extern "C" int rcflow_profile_reset(rc_ctx* ctx) {
 }
 extern "C" int rcflow_profile_read(rc_ctx* ctx, int cap, const char** names, int* launches,
                                    double* total_ms, double* alg_bytes, double* model_bytes) {
-    if (!ctx) return RC_EINVAL;
+    if (int rc = rc_ptr_check(__func__, "ctx", ctx)) return rc;
     prof_resolve(ctx);
     int n = 0;
     for (size_t id = 0; id < ctx->prof_ms.size() && n < cap; id++) {
@@ -174,7 +175,7 @@ extern "C" int rcflow_profile_read(rc_ctx* ctx, int cap, const char** names, int
 }
 
 extern "C" int rcflow_profile_read_buckets(rc_ctx* ctx, const char** names, double* ms) {
-    if (!ctx) return RC_EINVAL;
+    if (int rc = rc_ptr_check(__func__, "ctx", ctx)) return rc;
     prof_resolve(ctx);
     double b[RC_PROFILE_BUCKETS] = {0};
     for (size_t id = 0; id < ctx->prof_ms.size(); id++) b[kBucketOfKind[id / RC_MAX_LEVELS]] += ctx->prof_ms[id];
@@ -214,7 +215,7 @@ extern "C" int rcflow_create(rc_ctx** out, int device, int max_w, int max_h, int
     for (int i = 0; i < max_streams; i++) {
         hipError_t e = hipStreamCreateWithFlags(&ctx->slots[i].own, hipStreamNonBlocking);
         if (e != hipSuccess) {
-            rc_set_error("hipStreamCreate failed: %s", hipGetErrorString(e));
+            rc_set_error("rcflow_create: hipStreamCreate failed: %s", hipGetErrorString(e));
             rcflow_destroy(ctx);
             return RC_EHIP;
         }
@@ -300,7 +301,8 @@ extern "C" int rcflow_use_own_stream(rc_ctx* ctx, int stream) {
 // Diagnostic (not part of include/rcflow.h; tests/test_cabi_and_host.py): the pair groups the fused winsize-3 kernel would
 // walk for a launch of `pairs` consecutive pairs of a w x h scale with option chain = `chain` -- pure host logic, no GPU.
 extern "C" int rcflow_debug_chain_plan(int w, int h, int pairs, int chain, int force, int* starts, int cap) {
-    if (w <= 0 || h <= 0 || pairs < 1 || !starts || cap < 2) return RC_EINVAL;
+    if (w <= 0 || h <= 0 || pairs < 1 || cap < 2) { rc_set_error("%s: w %d, h %d, pairs %d (>= 1) or cap %d (>= 2)", __func__, w, h, pairs, cap); return RC_EINVAL; }
+    if (int rc = rc_ptr_check(__func__, "starts", starts)) return rc;
     RcIterArgs a;
     memset(&a, 0, sizeof(a));
     a.w = w; a.h = h; a.chain = chain; a.addr32 = 1; a.slot0 = 0; a.slot1 = 1; a.zstep = 1; a.nslots = pairs + 1;
@@ -313,11 +315,22 @@ extern "C" int rcflow_debug_chain_plan(int w, int h, int pairs, int chain, int f
 // per scale (buffer A then B alternate); which = 0 / 1 picks the buffer.
 extern "C" int rcflow_debug_level_flow_ptr(rc_ctx* ctx, int stream, int level, int which, float** d_flow, int* w, int* h) {
     RcSlot* s = rc_slot(ctx, stream);
-    if (!s || !s->plan.valid || level < 0 || level >= s->plan.nlev || !d_flow) return RC_EINVAL;
+    if (!s) return RC_EINVAL;
+    if (!s->plan.valid || level < 0 || level >= s->plan.nlev) { rc_set_error("%s: no plan on the slot, or level %d outside it", __func__, level); return RC_EINVAL; }
+    if (int rc = rc_ptr_check(__func__, "d_flow", d_flow)) return rc;
     *d_flow = (float*)(which ? s->FB[level].p : s->FA[level].p);
     if (w) *w = s->plan.lv[level].w;
     if (h) *h = s->plan.lv[level].h;
-    return *d_flow ? RC_OK : RC_ESTATE;
+    if (*d_flow) return RC_OK;
+    rc_set_error("%s: the level has no flow field yet", __func__);
+    return RC_ESTATE;
+}
+
+// rc_plan_prepare_poly with a text for its refusal; the ranges of n and sigma stay with each caller
+static int poly_prepare(const char* who, int n, double sigma, int exact_taps, RcPolyK& pk) {
+    const int rc = rc_plan_prepare_poly(n, sigma, exact_taps, pk);
+    if (rc) rc_set_error("%s: polynomial-expansion moment matrix is not positive definite", who);
+    return rc;
 }
 
 // Diagnostics (not part of include/rcflow.h; tests/test_plan_host.py): the plan arithmetic of rc_plan.cpp and the kind table
@@ -325,10 +338,10 @@ extern "C" int rcflow_debug_level_flow_ptr(rc_ctx* ctx, int stream, int level, i
 // ig33, ig55.
 extern "C" int rcflow_debug_plan_poly(int n, double sigma, int exact_taps, float* g, float* xg, float* xxg, double* ig, int* n_eff,
                                       double* kdc) {
-    if (n < 1 || n > RC_MAX_POLY_N || !(sigma >= 0) || !g || !xg || !xxg || !ig || !n_eff || !kdc) return RC_EINVAL;
+    if (n < 1 || n > RC_MAX_POLY_N || !(sigma >= 0)) { rc_set_error("%s: n %d (1..%d) or sigma %g (>= 0)", __func__, n, RC_MAX_POLY_N, sigma); return RC_EINVAL; }
+    if (!g || !xg || !xxg || !ig || !n_eff || !kdc) { rc_set_error("%s: a null pointer among g, xg, xxg, ig, n_eff, kdc", __func__); return RC_EINVAL; }
     RcPolyK pk;
-    const int rc = rc_plan_prepare_poly(n, sigma, exact_taps, pk);
-    if (rc) return rc;
+    if (int rc = poly_prepare(__func__, n, sigma, exact_taps, pk)) return rc;
     memcpy(g, pk.g, (n + 1) * sizeof(float));
     memcpy(xg, pk.xg, (n + 1) * sizeof(float));
     memcpy(xxg, pk.xxg, (n + 1) * sizeof(float));
@@ -339,10 +352,10 @@ extern "C" int rcflow_debug_plan_poly(int n, double sigma, int exact_taps, float
 }
 // the derived taps of the fast expansion (RcPolyK::qh, xga, xgb: taps 0..n; kdch)
 extern "C" int rcflow_debug_plan_poly_folded(int n, double sigma, int exact_taps, float* qh, float* xga, float* xgb, double* kdch) {
-    if (n < 1 || n > RC_MAX_POLY_N || !(sigma >= 0) || !qh || !xga || !xgb || !kdch) return RC_EINVAL;
+    if (n < 1 || n > RC_MAX_POLY_N || !(sigma >= 0)) { rc_set_error("%s: n %d (1..%d) or sigma %g (>= 0)", __func__, n, RC_MAX_POLY_N, sigma); return RC_EINVAL; }
+    if (!qh || !xga || !xgb || !kdch) { rc_set_error("%s: a null pointer among qh, xga, xgb, kdch", __func__); return RC_EINVAL; }
     RcPolyK pk;
-    const int rc = rc_plan_prepare_poly(n, sigma, exact_taps, pk);
-    if (rc) return rc;
+    if (int rc = poly_prepare(__func__, n, sigma, exact_taps, pk)) return rc;
     memcpy(qh, pk.qh, (n + 1) * sizeof(float));
     memcpy(xga, pk.xga, (n + 1) * sizeof(float));
     memcpy(xgb, pk.xgb, (n + 1) * sizeof(float));
@@ -350,58 +363,66 @@ extern "C" int rcflow_debug_plan_poly_folded(int n, double sigma, int exact_taps
     return RC_OK;
 }
 extern "C" int rcflow_debug_plan_pyr_kernel(int ksize, double sigma, float* taps) {
-    if (ksize < 1 || ksize > 1023 || !(sigma >= 0) || !taps) return RC_EINVAL;
+    if (ksize < 1 || ksize > 1023 || !(sigma >= 0)) { rc_set_error("%s: ksize %d (1..1023) or sigma %g (>= 0)", __func__, ksize, sigma); return RC_EINVAL; }
+    if (int rc = rc_ptr_check(__func__, "taps", taps)) return rc;
     rc_plan_gaussian_kernel(ksize, sigma, taps);
     return RC_OK;
 }
 extern "C" int rcflow_debug_kind(int id, const char** name, const char** bucket) {
-    if (id < 0 || id >= RC_K_LISTED || !name || !bucket) return RC_EINVAL;
+    if (id < 0 || id >= RC_K_LISTED) { rc_set_error("%s: id %d (0..%d)", __func__, id, RC_K_LISTED - 1); return RC_EINVAL; }
+    if (!name || !bucket) { rc_set_error("%s: a null pointer among name, bucket", __func__); return RC_EINVAL; }
     *name = kKindNames[id];
     *bucket = kBucketNames[kBucketOfKind[id]];
     return RC_OK;
 }
 
 extern "C" int rcflow_set_option(rc_ctx* ctx, const char* name, int value) {
-    if (!ctx || !name) return RC_EINVAL;
+    const char* who = __func__;
+    if (!ctx || !name) { rc_set_error("%s: a null pointer among ctx, name", who); return RC_EINVAL; }
+    auto outside = [&](int lo, int hi) {   // the value, against the option's range
+        if (value >= lo && value <= hi) return false;
+        rc_set_error("%s: %s = %d is outside %d..%d", who, name, value, lo, hi);
+        return true;
+    };
     if (!strcmp(name, "chunk")) {
-        if (value < 1 || value > 64) return RC_EINVAL;
+        if (outside(1, 64)) return RC_EINVAL;
         ctx->chunk = value;
     } else if (!strcmp(name, "exact_taps")) {
         ctx->exact_taps = value ? 1 : 0;
     } else if (!strcmp(name, "exact")) {
-        if (value < -1 || value > 1) return RC_EINVAL;
+        if (outside(-1, 1)) return RC_EINVAL;
         ctx->exact = value;
     } else if (!strcmp(name, "fuse_iters")) {
         ctx->fuse_iters = value ? 1 : 0;
     } else if (!strcmp(name, "chain")) {
-        if (value < 1 || value > 64) return RC_EINVAL;
+        if (outside(1, 64)) return RC_EINVAL;
         ctx->chain = value;
     } else if (!strcmp(name, "chain_min_blocks")) {
-        if (value < 0) return RC_EINVAL;
+        if (outside(0, INT_MAX)) return RC_EINVAL;
         ctx->chain_min_blocks = value;
     } else if (!strcmp(name, "xcd_remap")) {
         ctx->xcd_remap = value ? 1 : 0;
     } else if (!strcmp(name, "hist_blocks")) {
-        if (value < 0 || value > 65535) return RC_EINVAL;
+        if (outside(0, 65535)) return RC_EINVAL;
         ctx->hist_blocks = value;
     } else if (!strcmp(name, "overlap")) {
         ctx->overlap = value ? 1 : 0;
     } else if (!strcmp(name, "frame_overlap")) {
-        if (value < 0 || value > 2) return RC_EINVAL;
+        if (outside(0, 2)) return RC_EINVAL;
         ctx->frame_overlap = value;
     } else if (!strcmp(name, "merge_small")) {
         ctx->merge_small = value ? 1 : 0;
     } else if (!strcmp(name, "poly_mfma")) {
         ctx->poly_mfma = value ? 1 : 0;
     } else if (!strcmp(name, "poly_tile_h")) {
-        if (value != 32 && value != 48) return RC_EINVAL;
+        if (value != 32 && value != 48) { rc_set_error("%s: poly_tile_h = %d is neither 32 nor 48", who, value); return RC_EINVAL; }
         ctx->poly_tile_h = value;
     } else if (!strcmp(name, "fuse_pyr")) {
         ctx->fuse_pyr = value != 0;
     } else if (!strcmp(name, "ablate")) {
         ctx->ablate = value;
     } else {
-        rc_set_error("unknown option %s", name);
+        rc_set_error("%s: unknown option %s", who, name);
         return RC_EINVAL;
     }
     for (int i = 0; i < ctx->nstreams; i++) ctx->slots[i].plan.valid = false;
@@ -410,7 +431,10 @@ extern "C" int rcflow_set_option(rc_ctx* ctx, const char* name, int value) {
 
 // ---------------------------------------------------------------------------- plan (A7 geometry; the arithmetic is rc_plan.cpp)
 extern "C" int rcflow_level_geometry(int w, int h, double pyr_scale, int levels, int k, int* wk, int* hk) {
-    if (w <= 0 || h <= 0 || !(pyr_scale > 0 && pyr_scale < 1) || levels < 0 || k < 0) return RC_EINVAL;
+    if (w <= 0 || h <= 0 || !(pyr_scale > 0 && pyr_scale < 1) || levels < 0 || k < 0) {
+        rc_set_error("%s: size %d x %d, pyr_scale %g (inside 0..1), levels %d or k %d (>= 0)", __func__, w, h, pyr_scale, levels, k);
+        return RC_EINVAL;
+    }
     RcLevel L;
     rc_plan_level_geom(w, h, pyr_scale, k, L);
     if (wk) *wk = L.w;
@@ -418,16 +442,13 @@ extern "C" int rcflow_level_geometry(int w, int h, double pyr_scale, int levels,
     return rc_plan_crop_levels(w, h, pyr_scale, levels);
 }
 
-static int ensure_plan(rc_ctx* ctx, RcSlot& s, int w, int h, const rc_farneback_params* p, int chunk, int nslots = 0) {
+static int ensure_plan(const char* who, rc_ctx* ctx, RcSlot& s, int w, int h, const rc_farneback_params* p, int chunk, int nslots = 0) {
     if (nslots <= 0) nslots = chunk + 1;
     if (w <= 0 || h <= 0 || !rc_plan_params_valid(p)) {
-        rc_set_error("invalid Farneback arguments (w=%d h=%d)", w, h);
+        rc_set_error("%s: invalid Farneback arguments (w=%d h=%d)", who, w, h);
         return RC_EINVAL;
     }
-    if (w > ctx->max_w || h > ctx->max_h) {
-        rc_set_error("frame %dx%d exceeds the context's %dx%d", w, h, ctx->max_w, ctx->max_h);
-        return RC_ESIZE;
-    }
+    if (int rc = rc_fits_context(who, ctx, w, h)) return rc;
     RcPlan& pl = s.plan;
     // field by field: the struct has tail padding that a caller's brace-initialised copy leaves indeterminate
     const rc_farneback_params& q = pl.prm;
@@ -460,13 +481,13 @@ static int ensure_plan(rc_ctx* ctx, RcSlot& s, int w, int h, const rc_farneback_
     size_t kern_total = 0;
     for (int k = 0; k <= L; k++) {
         rc_plan_level_geom(w, h, p->pyr_scale, k, pl.lv[k]);
-        if (pl.lv[k].ksize > 1023) { rc_set_error("pyramid blur too wide"); return RC_EINVAL; }
+        if (pl.lv[k].ksize > 1023) { rc_set_error("%s: pyramid blur too wide", who); return RC_EINVAL; }
         rc_plan_pick_pyr_tile(pl.lv[k], w, h);
         pl.kern_off[k] = kern_total;
         kern_total += (pl.lv[k].ksize + 3) & ~3;
     }
-    int rc = rc_plan_prepare_poly(p->poly_n, p->poly_sigma, ctx->exact_taps || exact, pl.pk);
-    if (rc) { rc_set_error("polynomial-expansion moment matrix is not positive definite"); return rc; }
+    int rc = poly_prepare(who, p->poly_n, p->poly_sigma, ctx->exact_taps || exact, pl.pk);
+    if (rc) return rc;
     rc_plan_window(p->winsize, p->flags, pl.win);
 
     std::vector<float> kh(kern_total, 0.f);
@@ -500,8 +521,8 @@ struct RcSeed {
     size_t step, pair_stride;   // bytes
 };
 
-static int seed_layout_ok(const void* p, size_t step, size_t pair_stride) {
-    if ((((uintptr_t)p) | step | pair_stride) & 7) { rc_set_error("initial flow: pointer and strides must be multiples of 8 bytes"); return 0; }
+static int seed_layout_ok(const char* who, const void* p, size_t step, size_t pair_stride) {
+    if ((((uintptr_t)p) | step | pair_stride) & 7) { rc_set_error("%s: initial flow: pointer and strides must be multiples of 8 bytes", who); return 0; }
     return 1;
 }
 
@@ -788,18 +809,24 @@ static int compute_flows(rc_ctx* ctx, RcSlot& s, int pairs, int slot0, float* d_
 }
 
 // ---------------------------------------------------------------------------- A entry points
+// the two 8-bit images and the flow field of the two-image calls, one by one (d_flow may seed the call: in and out)
+static int pair_check(const char* who, const char* prev_name, const void* prev, size_t prev_step, const char* next_name, const void* next,
+                      size_t next_step, const char* flow_name, const void* flow, size_t flow_step, int w, int h) {
+    int rc;
+    if ((rc = rc_image_check(who, prev_name, prev, prev_step, w, h, 1, 1, RC_ARG_IN))) return rc;
+    if ((rc = rc_image_check(who, next_name, next, next_step, w, h, 1, 1, RC_ARG_IN))) return rc;
+    return rc_image_check(who, flow_name, flow, flow_step, w, h, 8, 1, RC_ARG_OUT);
+}
+
 extern "C" int rcflow_farneback_dev(rc_ctx* ctx, int stream, const uint8_t* d_prev, size_t prev_step,
                                     const uint8_t* d_next, size_t next_step, int w, int h, float* d_flow,
                                     size_t flow_step, const rc_farneback_params* p) {
     RcSlot* s = rc_slot(ctx, stream);
-    if (!s || !d_prev || !d_next || !d_flow) { if (s) rc_set_error("null image pointer"); return RC_EINVAL; }
-    if (prev_step < (size_t)w || next_step < (size_t)w || flow_step < (size_t)w * 8) {
-        rc_set_error("row step smaller than a row");
-        return RC_EINVAL;
-    }
-    RC_HIP(hipSetDevice(ctx->device));
-    int rc = ensure_plan(ctx, *s, w, h, p, ctx->chunk);
+    if (!s) return RC_EINVAL;
+    int rc = pair_check(__func__, "d_prev", d_prev, prev_step, "d_next", d_next, next_step, "d_flow", d_flow, flow_step, w, h);
     if (rc) return rc;
+    RC_HIP(hipSetDevice(ctx->device));
+    if ((rc = ensure_plan(__func__, ctx, *s, w, h, p, ctx->chunk))) return rc;
     s->primed = 0;
     s->batch_primed = 0;
     s->flow_w = s->flow_h = 0;      // the stream starts over: no resident flow field of its own (rcflow_stream_flow_ptr)
@@ -809,7 +836,7 @@ extern "C" int rcflow_farneback_dev(rc_ctx* ctx, int stream, const uint8_t* d_pr
     // OPTFLOW_USE_INITIAL_FLOW: d_flow is in/out (read by the reduction before any launch writes it)
     const RcSeed seed = {d_flow, flow_step, 0};
     const bool use_seed = (p->flags & RC_FARNEBACK_USE_INITIAL_FLOW) != 0;
-    if (use_seed && !seed_layout_ok(d_flow, flow_step, 0)) return RC_EINVAL;
+    if (use_seed && !seed_layout_ok(__func__, d_flow, flow_step, 0)) return RC_EINVAL;
     return compute_flows(ctx, *s, 1, 0, d_flow, 0, flow_step, -1, 1, use_seed ? &seed : nullptr);
 }
 
@@ -818,15 +845,12 @@ extern "C" int rcflow_farneback_u8(rc_ctx* ctx, int stream, const uint8_t* prev,
                                    size_t flow_step, double pyr_scale, int levels, int winsize, int iterations,
                                    int poly_n, double poly_sigma, int flags) {
     RcSlot* s = rc_slot(ctx, stream);
-    if (!s || !prev || !next || !flow || w <= 0 || h <= 0) { if (s) rc_set_error("null image pointer"); return RC_EINVAL; }
-    if (prev_step < (size_t)w || next_step < (size_t)w || flow_step < (size_t)w * 8) {
-        rc_set_error("row step smaller than a row");
-        return RC_EINVAL;
-    }
+    if (!s) return RC_EINVAL;
+    int rc = pair_check(__func__, "prev", prev, prev_step, "next", next, next_step, "flow", flow, flow_step, w, h);
+    if (rc) return rc;
     rc_farneback_params p = {pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
     RC_HIP(hipSetDevice(ctx->device));
-    int rc = ensure_plan(ctx, *s, w, h, &p, ctx->chunk);
-    if (rc) return rc;
+    if ((rc = ensure_plan(__func__, ctx, *s, w, h, &p, ctx->chunk))) return rc;
     size_t fb = (size_t)w * h;
     if ((rc = rc_buf_ensure(s->stage_u8, 2 * fb))) return rc;
     if ((rc = rc_buf_ensure(s->stage_flow, fb * 8))) return rc;
@@ -869,10 +893,10 @@ struct RcFrameAux {
 // RC_FARNEBACK_USE_INITIAL_FLOW: d_flow is in/out.  `resident` = d_flow is the slot's own resident field (the host-frame
 // loop): it seeds the pair only while it holds the flow of the stream's previous pair (RcSlot::flow_fresh); the first
 // pair after a priming call starts from zero.
-static int push_frame_core(rc_ctx* ctx, RcSlot* s, const uint8_t* d_frame, size_t step, int w, int h,
+static int push_frame_core(const char* who, rc_ctx* ctx, RcSlot* s, const uint8_t* d_frame, size_t step, int w, int h,
                            float* d_flow, size_t flow_step, const rc_farneback_params* p, bool two_streams,
                            const RcFrameAux* up, bool resident) {
-    int rc = ensure_plan(ctx, *s, w, h, p, ctx->chunk);   // a rebuilt plan drops `primed`
+    int rc = ensure_plan(who, ctx, *s, w, h, p, ctx->chunk);   // a rebuilt plan drops `primed`
     if (rc) return rc;
     s->batch_primed = 0;
     auto upload_on = [&](hipStream_t st) -> int {
@@ -889,10 +913,10 @@ static int push_frame_core(rc_ctx* ctx, RcSlot* s, const uint8_t* d_frame, size_
         s->flow_fresh = 0;
         return 1;
     }
-    if (!d_flow || flow_step < (size_t)w * 8) { rc_set_error("bad flow buffer"); return RC_EINVAL; }
+    if ((rc = rc_image_check(who, "d_flow", d_flow, flow_step, w, h, 8, 1, RC_ARG_OUT))) return rc;
     const RcSeed seed_desc = {d_flow, flow_step, 0};
     const bool use_seed = (p->flags & RC_FARNEBACK_USE_INITIAL_FLOW) && (!resident || s->flow_fresh);
-    if (use_seed && !seed_layout_ok(d_flow, flow_step, 0)) return RC_EINVAL;
+    if (use_seed && !seed_layout_ok(who, d_flow, flow_step, 0)) return RC_EINVAL;
     const RcSeed* seed = use_seed ? &seed_desc : nullptr;
     s->flow_fresh = 0;
     const int nxt = (s->cur_slot + 1) % s->plan.nslots;
@@ -944,12 +968,12 @@ static int push_frame_core(rc_ctx* ctx, RcSlot* s, const uint8_t* d_frame, size_
 extern "C" int rcflow_push_frame_dev(rc_ctx* ctx, int stream, const uint8_t* d_frame, size_t step, int w, int h,
                                      float* d_flow, size_t flow_step, const rc_farneback_params* p) {
     RcSlot* s = rc_slot(ctx, stream);
-    if (!s || !d_frame) { if (s) rc_set_error("null frame pointer"); return RC_EINVAL; }
-    if (step < (size_t)w) { rc_set_error("row step smaller than a row"); return RC_EINVAL; }
+    if (!s) return RC_EINVAL;
+    if (int rc = rc_image_check(__func__, "d_frame", d_frame, step, w, h, 1, 1, RC_ARG_IN)) return rc;
     RC_HIP(hipSetDevice(ctx->device));
     // option "frame_overlap" = 2: the caller guarantees that d_frame is complete when the call is made (a resident clip, a
     // producer it has synchronised) -- only then may the expansion start without waiting for the slot's stream
-    return push_frame_core(ctx, s, d_frame, step, w, h, d_flow, flow_step, p, ctx->frame_overlap >= 2, nullptr, false);
+    return push_frame_core(__func__, ctx, s, d_frame, step, w, h, d_flow, flow_step, p, ctx->frame_overlap >= 2, nullptr, false);
 }
 
 // The reference's frame loop with HOST frames (ripcurrents.cpp:198-221: video.read -> resize -> cvtColor ->
@@ -960,9 +984,9 @@ extern "C" int rcflow_push_frame_dev(rc_ctx* ctx, int stream, const uint8_t* d_f
 // while the host decodes frame t + 1.  Returns 1 when the call only primed the stream (no flow yet).
 // The slot's two page-locked staging buffers for frames of w x h bytes; returns the one the next push uses, once the
 // upload that last read it has left it.
-static int frame_staging_next(rc_ctx* ctx, RcSlot* s, int w, int h, int* idx) {
-    if (w <= 0 || h <= 0) { rc_set_error("bad frame arguments"); return RC_EINVAL; }
-    if (w > ctx->max_w || h > ctx->max_h) { rc_set_error("frame %dx%d exceeds the context's %dx%d", w, h, ctx->max_w, ctx->max_h); return RC_ESIZE; }
+static int frame_staging_next(const char* who, rc_ctx* ctx, RcSlot* s, int w, int h, int* idx) {
+    if (w <= 0 || h <= 0) { rc_set_error("%s: an empty size %d x %d", who, w, h); return RC_EINVAL; }
+    if (int rc = rc_fits_context(who, ctx, w, h)) return rc;
     RC_HIP(hipSetDevice(ctx->device));
     const size_t fb = (size_t)w * h;
     if (s->pin_bytes < fb) {
@@ -970,7 +994,7 @@ static int frame_staging_next(rc_ctx* ctx, RcSlot* s, int w, int h, int* idx) {
         for (int i = 0; i < 2; i++) {
             if (s->pin[i]) (void)hipHostFree(s->pin[i]);
             s->pin[i] = nullptr;
-            if (hipHostMalloc(&s->pin[i], fb, hipHostMallocDefault) != hipSuccess) { rc_set_error("hipHostMalloc(%zu) failed", fb); s->pin_bytes = 0; return RC_ENOMEM; }
+            if (hipHostMalloc(&s->pin[i], fb, hipHostMallocDefault) != hipSuccess) { rc_set_error("%s: hipHostMalloc(%zu) failed", who, fb); s->pin_bytes = 0; return RC_ENOMEM; }
             if (!s->pin_free[i]) RC_HIP(hipEventCreateWithFlags(&s->pin_free[i], hipEventDisableTiming));
             RC_HIP(hipEventRecord(s->pin_free[i], s->cur));
         }
@@ -985,14 +1009,14 @@ static int frame_staging_next(rc_ctx* ctx, RcSlot* s, int w, int h, int* idx) {
 }
 
 // Upload of staging buffer i (dense w x h bytes) + one step of the frame loop
-static int push_staged_frame(rc_ctx* ctx, RcSlot* s, int i, int w, int h, const rc_farneback_params* p) {
+static int push_staged_frame(const char* who, rc_ctx* ctx, RcSlot* s, int i, int w, int h, const rc_farneback_params* p) {
     const size_t fb = (size_t)w * h;
     uint8_t* d_frame = (uint8_t*)s->stage_u8.p + (size_t)i * fb;
     s->pin_i = i ^ 1;
     s->pin_acq = -1;
     // the upload belongs to the expansion's side of the two-stream frame loop (option "frame_overlap" >= 1)
     RcFrameAux up = {s->pin[i], d_frame, fb, s->pin_free[i]};
-    const int rc = push_frame_core(ctx, s, d_frame, w, w, h, (float*)s->stage_flow.p, (size_t)w * 8, p, ctx->frame_overlap >= 1, &up, true);
+    const int rc = push_frame_core(who, ctx, s, d_frame, w, w, h, (float*)s->stage_flow.p, (size_t)w * 8, p, ctx->frame_overlap >= 1, &up, true);
     if (rc == RC_OK) { s->flow_w = w; s->flow_h = h; s->flow_fresh = 1; }
     else if (rc == 1) { s->flow_w = s->flow_h = 0; }
     return rc;
@@ -1001,22 +1025,24 @@ static int push_staged_frame(rc_ctx* ctx, RcSlot* s, int i, int w, int h, const 
 extern "C" int rcflow_push_frame_u8(rc_ctx* ctx, int stream, const uint8_t* frame, size_t step, int w, int h,
                                     const rc_farneback_params* p) {
     RcSlot* s = rc_slot(ctx, stream);
-    if (!s || !frame || w <= 0 || h <= 0 || step < (size_t)w) { if (s) rc_set_error("bad frame arguments"); return RC_EINVAL; }
+    if (!s) return RC_EINVAL;
     int i, rc;
-    if ((rc = frame_staging_next(ctx, s, w, h, &i))) return rc;
+    if ((rc = rc_image_check(__func__, "frame", frame, step, w, h, 1, 1, RC_ARG_IN))) return rc;
+    if ((rc = frame_staging_next(__func__, ctx, s, w, h, &i))) return rc;
     uint8_t* dst = (uint8_t*)s->pin[i];
     if (step == (size_t)w) memcpy(dst, frame, (size_t)w * h);
     else for (int y = 0; y < h; y++) memcpy(dst + (size_t)y * w, frame + (size_t)y * step, w);
-    return push_staged_frame(ctx, s, i, w, h, p);
+    return push_staged_frame(__func__, ctx, s, i, w, h, p);
 }
 
 // The same loop without the copy: the host produces the frame INTO the staging buffer (e.g. as the destination of the
 // cvtColor at ripcurrents.cpp:210) and then pushes it.
 extern "C" int rcflow_frame_buffer_acquire(rc_ctx* ctx, int stream, int w, int h, uint8_t** host_frame, size_t* step) {
     RcSlot* s = rc_slot(ctx, stream);
-    if (!s || !host_frame) { if (s) rc_set_error("bad frame arguments"); return RC_EINVAL; }
+    if (!s) return RC_EINVAL;
     int i, rc;
-    if ((rc = frame_staging_next(ctx, s, w, h, &i))) return rc;
+    if ((rc = rc_ptr_check(__func__, "host_frame", host_frame))) return rc;
+    if ((rc = frame_staging_next(__func__, ctx, s, w, h, &i))) return rc;
     s->pin_acq = i; s->pin_w = w; s->pin_h = h;
     *host_frame = (uint8_t*)s->pin[i];
     if (step) *step = (size_t)w;
@@ -1025,17 +1051,18 @@ extern "C" int rcflow_frame_buffer_acquire(rc_ctx* ctx, int stream, int w, int h
 extern "C" int rcflow_push_frame_acquired(rc_ctx* ctx, int stream, const rc_farneback_params* p) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    if (s->pin_acq < 0 || s->pin_acq != s->pin_i) { rc_set_error("no frame buffer acquired (rcflow_frame_buffer_acquire) since the last push"); return RC_ESTATE; }
+    if (s->pin_acq < 0 || s->pin_acq != s->pin_i) { rc_set_error("%s: no frame buffer acquired (rcflow_frame_buffer_acquire) since the last push", __func__); return RC_ESTATE; }
     RC_HIP(hipSetDevice(ctx->device));
-    return push_staged_frame(ctx, s, s->pin_acq, s->pin_w, s->pin_h, p);
+    return push_staged_frame(__func__, ctx, s, s->pin_acq, s->pin_w, s->pin_h, p);
 }
 
 // Device address of the flow field the last rcflow_push_frame_u8 produced (w x h float2, dense rows), for the
 // analysis entry points; valid until the next push on the slot.
 extern "C" int rcflow_stream_flow_ptr(rc_ctx* ctx, int stream, float** d_flow, int* w, int* h) {
     RcSlot* s = rc_slot(ctx, stream);
-    if (!s || !d_flow) return RC_EINVAL;
-    if (!s->flow_w) { rc_set_error("no flow field yet: the stream has only been primed"); return RC_ESTATE; }
+    if (!s) return RC_EINVAL;
+    if (int rc = rc_ptr_check(__func__, "d_flow", d_flow)) return rc;
+    if (!s->flow_w) { rc_set_error("%s: no flow field yet: the stream has only been primed", __func__); return RC_ESTATE; }
     *d_flow = (float*)s->stage_flow.p;
     if (w) *w = s->flow_w;
     if (h) *h = s->flow_h;
@@ -1045,9 +1072,11 @@ extern "C" int rcflow_stream_flow_ptr(rc_ctx* ctx, int stream, float** d_flow, i
 // Copies that flow field to the host (CV_32FC2 layout, byte step) and waits for it.
 extern "C" int rcflow_stream_flow_read(rc_ctx* ctx, int stream, float* flow, size_t flow_step) {
     RcSlot* s = rc_slot(ctx, stream);
-    if (!s || !flow) return RC_EINVAL;
-    if (!s->flow_w) { rc_set_error("no flow field yet: the stream has only been primed"); return RC_ESTATE; }
-    if (flow_step < (size_t)s->flow_w * 8) { rc_set_error("row step smaller than a row"); return RC_EINVAL; }
+    if (!s) return RC_EINVAL;
+    int rc;
+    if ((rc = rc_ptr_check(__func__, "flow", flow))) return rc;
+    if (!s->flow_w) { rc_set_error("%s: no flow field yet: the stream has only been primed", __func__); return RC_ESTATE; }
+    if (flow_step < (size_t)s->flow_w * 8) { rc_set_error("%s: flow_step %zu below the %zu bytes of a row of flow", __func__, flow_step, (size_t)s->flow_w * 8); return RC_EINVAL; }
     RC_HIP(hipSetDevice(ctx->device));
     RC_HIP(hipMemcpy2DAsync(flow, flow_step, s->stage_flow.p, (size_t)s->flow_w * 8, (size_t)s->flow_w * 8, s->flow_h,
                             hipMemcpyDeviceToHost, s->cur));
@@ -1064,19 +1093,17 @@ extern "C" int rcflow_push_clip_dev(rc_ctx* ctx, int stream, const uint8_t* d_fr
                                     int nframes, int w, int h, float* d_flows, size_t flow_frame_stride,
                                     size_t flow_step, const rc_farneback_params* p) {
     RcSlot* s = rc_slot(ctx, stream);
-    if (!s || !d_frames || nframes < 1) { if (s) rc_set_error("bad clip arguments"); return RC_EINVAL; }
-    if (step < (size_t)w || (nframes > 1 && frame_stride < step * (size_t)(h - 1) + w)) {
-        rc_set_error("clip strides smaller than a frame");
-        return RC_EINVAL;
-    }
+    if (!s) return RC_EINVAL;
+    if (nframes < 1) { rc_set_error("%s: nframes %d (>= 1)", __func__, nframes); return RC_EINVAL; }
+    int rc = rc_clip_check(__func__, "d_frames", d_frames, frame_stride, step, nframes, w, h, 1, 1, RC_ARG_IN);
+    if (rc) return rc;
     if (p && (p->flags & RC_FARNEBACK_USE_INITIAL_FLOW)) {
-        rc_set_error("RC_FARNEBACK_USE_INITIAL_FLOW is not available for clips: the pairs of a clip are solved together, "
-                     "a pair cannot wait for its predecessor's field (use the frame-at-a-time entry points)");
+        rc_set_error("%s: RC_FARNEBACK_USE_INITIAL_FLOW is not available for clips: the pairs of a clip are solved together, "
+                     "a pair cannot wait for its predecessor's field (use the frame-at-a-time entry points)", __func__);
         return RC_EINVAL;
     }
     RC_HIP(hipSetDevice(ctx->device));
-    int rc = ensure_plan(ctx, *s, w, h, p, ctx->chunk);          // a new size / parameter set drops `primed`
-    if (rc) return rc;
+    if ((rc = ensure_plan(__func__, ctx, *s, w, h, p, ctx->chunk))) return rc;   // a new size / parameter set drops `primed`
     s->batch_primed = 0;
     s->flow_fresh = 0;
     const int C = s->plan.chunk, ns = s->plan.nslots;
@@ -1088,11 +1115,7 @@ extern "C" int rcflow_push_clip_dev(rc_ctx* ctx, int stream, const uint8_t* d_fr
         t = 1;
     }
     const int nflows = nframes - t;
-    if (nflows > 0 && (!d_flows || flow_step < (size_t)w * 8 ||
-                       (nflows > 1 && flow_frame_stride < flow_step * (size_t)(h - 1) + (size_t)w * 8))) {
-        rc_set_error("bad flow buffer");
-        return RC_EINVAL;
-    }
+    if (nflows > 0 && (rc = rc_clip_check(__func__, "d_flows", d_flows, flow_frame_stride, flow_step, nflows, w, h, 8, 1, RC_ARG_OUT))) return rc;
     for (int done = 0; t < nframes;) {
         const int np = nframes - t < C ? nframes - t : C;
         if ((rc = expand_frames(ctx, *s, d_frames + (size_t)t * frame_stride, frame_stride, step, np, (s0 + 1) % ns))) {
@@ -1117,15 +1140,15 @@ extern "C" int rcflow_farneback_clip_dev(rc_ctx* ctx, int stream, const uint8_t*
                                          size_t flow_frame_stride, size_t flow_step,
                                          const rc_farneback_params* p) {
     RcSlot* s = rc_slot(ctx, stream);
-    if (!s || !d_frames || !d_flows || nframes < 2) { if (s) rc_set_error("bad clip arguments"); return RC_EINVAL; }
-    if (step < (size_t)w || flow_step < (size_t)w * 8 || frame_stride < step * (size_t)(h - 1) + w ||
-        flow_frame_stride < flow_step * (size_t)(h - 1) + (size_t)w * 8) {
-        rc_set_error("clip strides smaller than a frame");
-        return RC_EINVAL;
-    }
+    if (!s) return RC_EINVAL;
+    if (nframes < 2) { rc_set_error("%s: nframes %d (>= 2)", __func__, nframes); return RC_EINVAL; }
+    int rc;
+    if ((rc = rc_clip_check(__func__, "d_frames", d_frames, frame_stride, step, nframes, w, h, 1, 1, RC_ARG_IN))) return rc;
+    // the stride of the fields is asked of a single field too (nframes = 2), as it always was
+    if ((rc = rc_clip_check(__func__, "d_flows", d_flows, flow_frame_stride, flow_step, nframes, w, h, 8, 1, RC_ARG_OUT))) return rc;
     if (p && (p->flags & RC_FARNEBACK_USE_INITIAL_FLOW)) {
-        rc_set_error("RC_FARNEBACK_USE_INITIAL_FLOW is not available for clips: the pairs of a clip are solved together, "
-                     "a pair cannot wait for its predecessor's field (use the frame-at-a-time entry points)");
+        rc_set_error("%s: RC_FARNEBACK_USE_INITIAL_FLOW is not available for clips: the pairs of a clip are solved together, "
+                     "a pair cannot wait for its predecessor's field (use the frame-at-a-time entry points)", __func__);
         return RC_EINVAL;
     }
     RC_HIP(hipSetDevice(ctx->device));
@@ -1133,8 +1156,7 @@ extern "C" int rcflow_farneback_clip_dev(rc_ctx* ctx, int stream, const uint8_t*
     // chunk c+1 (VALU-bound) then run on a second stream beside the flow kernels of chunk c
     // (bound by the memory system), joined by events.  Results do not depend on it.
     const bool overlap = ctx->overlap && nframes - 1 > ctx->chunk;
-    int rc = ensure_plan(ctx, *s, w, h, p, ctx->chunk, overlap ? 2 * ctx->chunk + 1 : 0);
-    if (rc) return rc;
+    if ((rc = ensure_plan(__func__, ctx, *s, w, h, p, ctx->chunk, overlap ? 2 * ctx->chunk + 1 : 0))) return rc;
     s->primed = 0;
     s->batch_primed = 0;
     const int C = s->plan.chunk, ns = s->plan.nslots;
@@ -1168,7 +1190,7 @@ extern "C" int rcflow_farneback_clip_dev(rc_ctx* ctx, int stream, const uint8_t*
     };
     auto cleanup = [&]() { for (hipEvent_t e : evs) (void)hipEventDestroy(e); };   // destruction is deferred by the runtime
     hipEvent_t fork = new_event(flow_stream);               // everything the caller queued so far (the frames)
-    if (!fork) { rc_set_error("hipEventCreate failed"); return RC_EHIP; }
+    if (!fork) { rc_set_error("%s: hipEventCreate failed", __func__); return RC_EHIP; }
     (void)hipStreamWaitEvent(exp_stream, fork, 0);
     hipEvent_t flows_done[2] = {nullptr, nullptr};          // flows of chunk c-1, c-2 (their slots get reused)
     s->cur = exp_stream;
@@ -1257,7 +1279,7 @@ struct RcLoopKey {          // everything a captured launch sequence has baked i
 };
 
 // the analysis chain of one frame on the resident flow field (ripcurrents.cpp:229-479), on s.cur
-static int loop_analysis(rc_ctx* ctx, RcSlot& s, int stream, const rc_frame_loop& L, int w, int h) {
+static int loop_analysis(const char* who, rc_ctx* ctx, RcSlot& s, int stream, const rc_frame_loop& L, int w, int h) {
     const size_t fs = (size_t)w * 8;
     float* d_flow = (float*)s.stage_flow.p;
     int rc;
@@ -1267,14 +1289,14 @@ static int loop_analysis(rc_ctx* ctx, RcSlot& s, int stream, const rc_frame_loop
                                                        L.seed_upper, L.seed_variant, nullptr))) return rc;      // :283-285
     if ((rc = rcflow_histogram_dev(ctx, stream, d_flow, fs, w, h))) return rc;                          // :319-330
     if ((rc = rcflow_thresholds_dev(ctx, stream))) return rc;                                           // :333-366
-    if ((rc = rc_classify_accumulate(ctx, stream, d_flow, fs, w, h, -1, L.MID, L.LOWER, nullptr, 0, nullptr, 0, nullptr, 0,
+    if ((rc = rc_classify_accumulate(who, ctx, stream, d_flow, fs, w, h, -1, L.MID, L.LOWER, nullptr, 0, nullptr, 0, nullptr, 0,
                                      L.d_outmask, L.mask_step))) return rc;                               // :376-439
     if (L.d_edges && (rc = rcflow_create_edges_dev(ctx, stream, L.d_outmask, L.mask_step, w, h, L.d_edges, L.edges_step))) return rc;   // :477-479
     return RC_OK;
 }
 
 // upload + expansion + flow + the analysis chain of one frame on s.cur (eager or under stream capture)
-static int loop_launches(rc_ctx* ctx, RcSlot& s, int stream, const rc_frame_loop& L, int pin, int w, int h, bool seeded) {
+static int loop_launches(const char* who, rc_ctx* ctx, RcSlot& s, int stream, const rc_frame_loop& L, int pin, int w, int h, bool seeded) {
     const size_t fb = (size_t)w * h, fs = (size_t)w * 8;
     uint8_t* d_frame = (uint8_t*)s.stage_u8.p + (size_t)pin * fb;
     float* d_flow = (float*)s.stage_flow.p;
@@ -1285,43 +1307,43 @@ static int loop_launches(rc_ctx* ctx, RcSlot& s, int stream, const rc_frame_loop
     // warm start: the resident field of the previous pair is read by the reduction before this pair's flow overwrites it
     const RcSeed seed = {d_flow, fs, 0};
     if ((rc = compute_flows(ctx, s, 1, cur, d_flow, 0, fs, nxt, 1, seeded ? &seed : nullptr))) return rc;
-    return loop_analysis(ctx, s, stream, L, w, h);
+    return loop_analysis(who, ctx, s, stream, L, w, h);
 }
 
 extern "C" int rcflow_frame_loop_step(rc_ctx* ctx, int stream, const rc_farneback_params* p, const rc_frame_loop* loop) {
     RcSlot* s = rc_slot(ctx, stream);
-    if (!s || !p || !loop) { if (s) rc_set_error("null argument"); return RC_EINVAL; }
-    if (s->pin_acq < 0 || s->pin_acq != s->pin_i) { rc_set_error("no frame buffer acquired (rcflow_frame_buffer_acquire) since the last push"); return RC_ESTATE; }
-    if (loop->nseeds < 0 || (loop->nseeds && !loop->d_seeds) || (loop->d_edges && !loop->d_outmask) || loop->iterations < 0) {
-        rc_set_error("bad frame-loop configuration");
-        return RC_EINVAL;
-    }
+    if (!s) return RC_EINVAL;
+    int rc;
+    if (!p || !loop) { rc_set_error("%s: a null pointer among p, loop", __func__); return RC_EINVAL; }
+    if (s->pin_acq < 0 || s->pin_acq != s->pin_i) { rc_set_error("%s: no frame buffer acquired (rcflow_frame_buffer_acquire) since the last push", __func__); return RC_ESTATE; }
+    if (loop->nseeds < 0 || loop->iterations < 0) { rc_set_error("%s: nseeds %d or iterations %d (>= 0)", __func__, loop->nseeds, loop->iterations); return RC_EINVAL; }
+    if (loop->nseeds && !loop->d_seeds) { rc_set_error("%s: loop->d_seeds is null with nseeds %d", __func__, loop->nseeds); return RC_EINVAL; }
+    if (loop->d_edges && !loop->d_outmask) { rc_set_error("%s: loop->d_edges needs loop->d_outmask", __func__); return RC_EINVAL; }
     RC_HIP(hipSetDevice(ctx->device));
     const int w = s->pin_w, h = s->pin_h, pin = s->pin_acq;
-    int rc;
     // the histogram stage's int32 guard, checked before anything is consumed or launched: a refused call leaves the
     // acquired frame, the stream and the analysis state as they were (reset the segment, call again)
-    if (s->primed && s->an.w == w && s->an.h == h && (rc = rc_hist_book(*s, w, h, false))) return rc;
+    if (s->primed && s->an.w == w && s->an.h == h && (rc = rc_hist_book(__func__, *s, w, h, false))) return rc;
     if (!loop->use_graph) {
         // The default: the two-stream frame push (upload and expansion of this frame beside the previous frame's flow
         // and analysis kernels, which the slot's stream may still be executing) followed by the analysis launches --
         // measured faster than one linear captured sequence per frame, which cannot overlap across frames
-        if ((rc = rc_analysis_ensure(ctx, *s, w, h))) return rc;
-        rc = push_staged_frame(ctx, s, pin, w, h, p);
+        if ((rc = rc_analysis_ensure(__func__, ctx, *s, w, h))) return rc;
+        rc = push_staged_frame(__func__, ctx, s, pin, w, h, p);
         if (rc < 0) return rc;
         if (rc == 1) {
             s->loop_fc = 0;
             if ((rc = rc_loop_counter(ctx, *s, true, 0))) return rc;
             return 1;
         }
-        if ((rc = loop_analysis(ctx, *s, stream, *loop, w, h))) return rc;
+        if ((rc = loop_analysis(__func__, ctx, *s, stream, *loop, w, h))) return rc;
         s->loop_fc++;
         return RC_OK;
     }
-    rc = ensure_plan(ctx, *s, w, h, p, 1, 2);                // a ring of two expansions: the captured sequences alternate
+    rc = ensure_plan(__func__, ctx, *s, w, h, p, 1, 2);           // a ring of two expansions: the captured sequences alternate
     if (rc) return rc;
     s->batch_primed = 0;
-    if ((rc = rc_analysis_ensure(ctx, *s, w, h))) return rc;
+    if ((rc = rc_analysis_ensure(__func__, ctx, *s, w, h))) return rc;
     const size_t fb = (size_t)w * h;
     if (!s->primed) {
         rc_graph_drop(s->loop_graph);
@@ -1338,7 +1360,7 @@ extern "C" int rcflow_frame_loop_step(rc_ctx* ctx, int stream, const rc_farnebac
         return 1;
     }
     const int cur = s->cur_slot;
-    if (cur > 1) { rc_set_error("the slot's ring is not the frame loop's: call rcflow_stream_reset first"); return RC_ESTATE; }
+    if (cur > 1) { rc_set_error("%s: the slot's ring is not the frame loop's: call rcflow_stream_reset first", __func__); return RC_ESTATE; }
     RcLoopKey key;
     memset(&key, 0, sizeof(key));
     key.loop = *loop;
@@ -1350,9 +1372,9 @@ extern "C" int rcflow_frame_loop_step(rc_ctx* ctx, int stream, const rc_farnebac
     const bool graph_ok = !ctx->prof_on && s->cur != nullptr;   // (the null stream cannot capture: eager there)
     // what the eager calls book on the host is booked here for a replay, and checked before a capture (whose calls book)
     const int state = graph_state(s->loop_graph, cur, &key, sizeof(key), graph_ok);
-    if (state != RC_GRAPH_EAGER && (rc = rc_hist_book(*s, w, h, state == RC_GRAPH_REPLAY))) return rc;
+    if (state != RC_GRAPH_EAGER && (rc = rc_hist_book(__func__, *s, w, h, state == RC_GRAPH_REPLAY))) return rc;
     if ((rc = rc_graph_step(s->loop_graph, cur, key, graph_ok, s->cur, s->cur,
-                            [&](hipStream_t) { return loop_launches(ctx, *s, stream, *loop, pin, w, h, seeded); })))
+                            [&, who = __func__](hipStream_t) { return loop_launches(who, ctx, *s, stream, *loop, pin, w, h, seeded); })))
         return rc;
     if (state == RC_GRAPH_REPLAY) s->ts_streak = 0;
     RC_HIP(hipEventRecord(s->pin_free[pin], s->cur));        // (behind the whole frame: the staging buffer comes round two frames later)
@@ -1385,15 +1407,13 @@ extern "C" int rcflow_push_batch_dev(rc_ctx* ctx, int stream, const uint8_t* d_f
                                      int nstreams, int w, int h, float* d_flows, size_t flow_frame_stride,
                                      size_t flow_step, const rc_farneback_params* p, int use_graph) {
     RcSlot* s = rc_slot(ctx, stream);
-    if (!s || !d_frames || nstreams < 1 || nstreams > 4096) { if (s) rc_set_error("bad batch arguments"); return RC_EINVAL; }
-    if (step < (size_t)w || (nstreams > 1 && frame_stride < step * (size_t)(h - 1) + w)) {
-        rc_set_error("batch strides smaller than a frame");
-        return RC_EINVAL;
-    }
+    if (!s) return RC_EINVAL;
+    if (nstreams < 1 || nstreams > 4096) { rc_set_error("%s: nstreams %d (1..4096)", __func__, nstreams); return RC_EINVAL; }
+    int rc = rc_clip_check(__func__, "d_frames", d_frames, frame_stride, step, nstreams, w, h, 1, 1, RC_ARG_IN);
+    if (rc) return rc;
     RC_HIP(hipSetDevice(ctx->device));
     // every stream keeps a ring of two expansions: slot 2*z + parity
-    int rc = ensure_plan(ctx, *s, w, h, p, nstreams, 2 * nstreams);
-    if (rc) return rc;
+    if ((rc = ensure_plan(__func__, ctx, *s, w, h, p, nstreams, 2 * nstreams))) return rc;
     s->primed = 0;
     if (!s->batch_primed) {
         rc_graph_drop(s->batch_graph);
@@ -1402,12 +1422,8 @@ extern "C" int rcflow_push_batch_dev(rc_ctx* ctx, int stream, const uint8_t* d_f
         s->batch_cur = 0;
         return 1;
     }
-    if (!d_flows || flow_step < (size_t)w * 8 ||
-        (nstreams > 1 && flow_frame_stride < flow_step * (size_t)(h - 1) + (size_t)w * 8)) {
-        rc_set_error("bad flow batch buffer");
-        return RC_EINVAL;
-    }
-    if ((p->flags & RC_FARNEBACK_USE_INITIAL_FLOW) && !seed_layout_ok(d_flows, flow_step, nstreams > 1 ? flow_frame_stride : 0)) return RC_EINVAL;
+    if ((rc = rc_clip_check(__func__, "d_flows", d_flows, flow_frame_stride, flow_step, nstreams, w, h, 8, 1, RC_ARG_OUT))) return rc;
+    if ((p->flags & RC_FARNEBACK_USE_INITIAL_FLOW) && !seed_layout_ok(__func__, d_flows, flow_step, nstreams > 1 ? flow_frame_stride : 0)) return RC_EINVAL;
     const int cur = s->batch_cur;
     const RcBatchKey key = {d_frames, frame_stride, step, d_flows, flow_frame_stride, flow_step, (void*)s->cur};
     // the null stream cannot capture: the sequence is recorded on the slot's own stream and the graph launched on the caller's
@@ -1437,15 +1453,20 @@ extern "C" int rcflow_batch_reset(rc_ctx* ctx, int stream) {
 extern "C" int rcflow_stage_pyr_level_dev(rc_ctx* ctx, int stream, const uint8_t* d_img, size_t step, int w,
                                           int h, double pyr_scale, int k, float* d_out) {
     RcSlot* s = rc_slot(ctx, stream);
-    if (!s || !d_img || !d_out || k < 0 || k >= RC_MAX_LEVELS || !(pyr_scale > 0 && pyr_scale < 1)) return RC_EINVAL;
+    if (!s) return RC_EINVAL;
+    if (!d_img || !d_out) { rc_set_error("%s: a null pointer among d_img, d_out", __func__); return RC_EINVAL; }
+    int rc;
+    if (k < 0 || k >= RC_MAX_LEVELS || !(pyr_scale > 0 && pyr_scale < 1)) {
+        rc_set_error("%s: k %d (0..%d) or pyr_scale %g (inside 0..1)", __func__, k, RC_MAX_LEVELS - 1, pyr_scale);
+        return RC_EINVAL;
+    }
     RC_HIP(hipSetDevice(ctx->device));
     RcLevel L;
     rc_plan_level_geom(w, h, pyr_scale, k, L);
     rc_plan_pick_pyr_tile(L, w, h);
     std::vector<float> kh(L.ksize);
     rc_plan_gaussian_kernel(L.ksize, L.sigma > 0 ? L.sigma : 0., kh.data());
-    int rc = rc_buf_ensure(s->stage_f32[0], kh.size() * sizeof(float));
-    if (rc) return rc;
+    if ((rc = rc_buf_ensure(s->stage_f32[0], kh.size() * sizeof(float)))) return rc;
     RC_HIP(hipMemcpyAsync(s->stage_f32[0].p, kh.data(), kh.size() * sizeof(float), hipMemcpyHostToDevice, s->cur));
     RC_HIP(hipStreamSynchronize(s->cur));
     const RcPyrArgs pa = pyr_args(ctx, L, k, d_img, step, 0, w, h, (const float*)s->stage_f32[0].p, d_out, 0, 0, 1, 1);
@@ -1457,10 +1478,12 @@ extern "C" int rcflow_stage_pyr_level_dev(rc_ctx* ctx, int stream, const uint8_t
 extern "C" int rcflow_stage_polyexp_dev(rc_ctx* ctx, int stream, const float* d_I, int w, int h, int poly_n,
                                         double poly_sigma, float* d_R5) {
     RcSlot* s = rc_slot(ctx, stream);
-    if (!s || !d_I || !d_R5 || w <= 0 || h <= 0 || poly_n < 1 || poly_n > RC_MAX_POLY_N) return RC_EINVAL;
+    if (!s) return RC_EINVAL;
+    if (!d_I || !d_R5) { rc_set_error("%s: a null pointer among d_I, d_R5", __func__); return RC_EINVAL; }
+    int rc;
+    if (w <= 0 || h <= 0 || poly_n < 1 || poly_n > RC_MAX_POLY_N) { rc_set_error("%s: size %d x %d or poly_n %d (1..%d)", __func__, w, h, poly_n, RC_MAX_POLY_N); return RC_EINVAL; }
     RC_HIP(hipSetDevice(ctx->device));
     size_t n = (size_t)w * h;
-    int rc;
     if ((rc = rc_buf_ensure(s->stage_f32[0], n * sizeof(float4)))) return rc;
     if ((rc = rc_buf_ensure(s->stage_f32[1], n * sizeof(float)))) return rc;
     RcPolyArgs qa;
@@ -1468,7 +1491,7 @@ extern "C" int rcflow_stage_polyexp_dev(rc_ctx* ctx, int stream, const float* d_
     qa.I = d_I; qa.I_slot_stride = 0;
     qa.RA = (float4*)s->stage_f32[0].p; qa.RB = (float*)s->stage_f32[1].p; qa.R_slot_stride = 0;
     qa.slot0 = 0; qa.nslots = 1; qa.zstep = 1; qa.w = w; qa.h = h; qa.tile_h = ctx->poly_tile_h; qa.valu_vertical = !ctx->poly_mfma;
-    if ((rc = rc_plan_prepare_poly(poly_n, poly_sigma, ctx->exact_taps || ctx->exact == 1, qa.pk))) return rc;
+    if ((rc = poly_prepare(__func__, poly_n, poly_sigma, ctx->exact_taps || ctx->exact == 1, qa.pk))) return rc;
     if (ctx->exact == 1) rc_launch_exact_polyexp(qa, 1, s->cur);
     else rc_launch_polyexp(qa, 1, s->cur);
     rc_launch_unpack_R5(qa.RA, qa.RB, d_R5, (int)n, ctx->exact != 1, s->cur);   // d_R5 is upstream's R in both builds
@@ -1480,12 +1503,15 @@ extern "C" int rcflow_stage_flow_iter_dev(rc_ctx* ctx, int stream, const float* 
                                           const float* d_flow_in, int w, int h, int winsize, int flags,
                                           float* d_flow_out) {
     RcSlot* s = rc_slot(ctx, stream);
-    if (!s || !d_R0 || !d_R1 || !d_flow_out || w <= 0 || h <= 0 || winsize < 1 || winsize / 2 > 24 ||
-        (flags & ~RC_FARNEBACK_GAUSSIAN))
+    if (!s) return RC_EINVAL;
+    if (!d_R0 || !d_R1 || !d_flow_out) { rc_set_error("%s: a null pointer among d_R0, d_R1, d_flow_out", __func__); return RC_EINVAL; }
+    int rc;
+    if (w <= 0 || h <= 0 || winsize < 1 || winsize / 2 > 24 || (flags & ~RC_FARNEBACK_GAUSSIAN)) {
+        rc_set_error("%s: size %d x %d, winsize %d (1..49) or flags %d (RC_FARNEBACK_GAUSSIAN alone)", __func__, w, h, winsize, flags);
         return RC_EINVAL;
+    }
     RC_HIP(hipSetDevice(ctx->device));
     size_t n = (size_t)w * h;
-    int rc;
     if ((rc = rc_buf_ensure(s->stage_f32[0], 2 * n * sizeof(float4)))) return rc;
     if ((rc = rc_buf_ensure(s->stage_f32[1], 2 * n * sizeof(float)))) return rc;
     float4* RA = (float4*)s->stage_f32[0].p;
@@ -1530,20 +1556,20 @@ extern "C" int rcflow_stage_initial_flow_dev(rc_ctx* ctx, int stream, const floa
                                              int h, double pyr_scale, int levels, float* d_out) {
     RcSlot* s = rc_slot(ctx, stream);
     if (!s) return RC_EINVAL;
-    if (!d_flow_xy || !d_out || w <= 0 || h <= 0 || !(pyr_scale > 0 && pyr_scale < 1) || levels < 0 || levels >= RC_MAX_LEVELS ||
-        flow_step < (size_t)w * 8) {
-        rc_set_error("bad initial-flow arguments");
+    int rc;
+    if ((rc = rc_image_check(__func__, "d_flow_xy", d_flow_xy, flow_step, w, h, 8, 8, RC_ARG_IN))) return rc;
+    if ((rc = rc_ptr_check(__func__, "d_out", d_out))) return rc;
+    if (!(pyr_scale > 0 && pyr_scale < 1) || levels < 0 || levels >= RC_MAX_LEVELS) {
+        rc_set_error("%s: pyr_scale %g (inside 0..1) or levels %d (0..%d)", __func__, pyr_scale, levels, RC_MAX_LEVELS - 1);
         return RC_EINVAL;
     }
-    if (!seed_layout_ok(d_flow_xy, flow_step, 0)) return RC_EINVAL;
     RC_HIP(hipSetDevice(ctx->device));
     const int L = rc_plan_crop_levels(w, h, pyr_scale, levels);
     RcLevel lv;
     rc_plan_level_geom(w, h, pyr_scale, L, lv);
     RC_HIP(hipStreamSynchronize(s->cur));      // a previous launch may still read the tables
     RcFlowAreaArgs a;
-    int rc = rc_flow_area_prepare(s->stage_f32[3], w, h, lv.w, lv.h, a);
-    if (rc) return rc;
+    if ((rc = rc_flow_area_prepare(s->stage_f32[3], w, h, lv.w, lv.h, a))) return rc;
     a.mul = (float)rc_plan_scale_pow(pyr_scale, L);
     a.src = (const char*)d_flow_xy; a.src_step = flow_step; a.src_pair_stride = 0;
     a.dst = (float2*)d_out; a.dst_pair_stride = (size_t)lv.w * lv.h;

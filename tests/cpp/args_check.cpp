@@ -220,8 +220,45 @@ int main() {
     CHECK(rc_prims_check("p", g_buf, 0, 0) == RC_EINVAL && rc_prims_check("p", g_buf, RC_DRAW_MAX_THICKNESS + 1, 0) == RC_EINVAL, "prims thickness");
     CHECK(rc_prims_check("p", g_buf, 1, -1) == RC_EINVAL && rc_prims_check("p", g_buf, 1, RC_DRAW_COORD_MAX + 1) == RC_EINVAL, "prims radius");
 
+    // 5. the named forms against the predicates the entry points spelt out before they had them, as plain integer arithmetic.
+    // rc_flow_check: p && w > 0 && h > 0 && step >= 8 * w && !(step & 7); nothing asked of the base
+    long flow_odd_base_ok = 0, clip_cases = 0;
+    for (int w = -1; w <= 5; w++)
+        for (int h = -1; h <= 4; h++)
+            for (long step = 0; step <= 8L * 5 + 9; step++)
+                for (long off = -1; off <= 15; off++) {
+                    const bool want = off >= 0 && w > 0 && h > 0 && step >= 8L * w && !(step & 7);
+                    g_text[0] = 0;
+                    const int rc = rc_flow_check("flow_form", "d_flow", off < 0 ? nullptr : g_buf + 64 + off, (size_t)step, w, h, (w + h) & 1 ? RC_ARG_OUT : RC_ARG_IN);
+                    CHECK((rc == RC_OK) == want && (rc == RC_OK || rc == RC_EINVAL), "rc_flow_check gave %d at w %d h %d step %ld off %ld", rc, w, h, step, off);
+                    CHECK(rc == RC_OK || (!strncmp(g_text, "flow_form: ", 11) && strstr(g_text, "d_flow")), "rc_flow_check's text \"%s\"", g_text);
+                    if (rc == RC_OK && (off & 7)) flow_odd_base_ok++;
+                }
+    CHECK(flow_odd_base_ok > 0, "no flow field at a base off 8 bytes was accepted");
+    // rc_clip_check: the image form of the first frame, and for n > 1 frame_stride >= step * (h - 1) + w * bpp
+    for (int bpp : {1, 8})
+        for (int w = 1; w <= 4; w++)
+            for (int h = 1; h <= 4; h++)
+                for (long pad = -1; pad <= 2; pad++)
+                    for (int n = -1; n <= 3; n++)
+                        for (long d = -2; d <= 2; d++)
+                            for (int null = 0; null < 2; null++) {
+                                const long step = (long)w * bpp + pad * (pad > 0 ? bpp : 1), bound = step * (h - 1) + (long)w * bpp, stride = bound + d;
+                                if (stride < 0) continue;
+                                const bool want = !null && step >= (long)w * bpp && (n <= 1 || stride >= bound);
+                                g_text[0] = 0;
+                                const int rc = rc_clip_check("clip_form", "d_frames", null ? nullptr : g_buf + 3, (size_t)stride, (size_t)step, n, w, h, bpp, 1, RC_ARG_IN);
+                                CHECK((rc == RC_OK) == want && (rc == RC_OK || rc == RC_EINVAL), "rc_clip_check gave %d at bpp %d w %d h %d step %ld n %d stride %ld", rc, bpp, w, h, step, n, stride);
+                                CHECK(rc == RC_OK || (!strncmp(g_text, "clip_form: ", 11) && strstr(g_text, "d_frames")), "rc_clip_check's text \"%s\"", g_text);
+                                clip_cases++;
+                            }
+    // rc_ptr_check: null, and the base against the alignment
+    CHECK(rc_ptr_check("p", "x", nullptr) == RC_EINVAL && rc_ptr_check("p", "x", nullptr, 16, RC_ARG_OPTIONAL) == RC_OK, "a null pointer");
+    for (int off = 0; off < 32; off++)
+        for (int align : {1, 8, 16}) CHECK((rc_ptr_check("p", "x", g_buf + off, align) == RC_OK) == (off % align == 0), "a pointer at %d, alignment %d", off, align);
+
     for (int k = 0; k < 8; k++) CHECK(g_seen[k] > 0, "case kind %d never occurred", k);
-    printf("args_check: ok (%ld checks; touching %ld, one byte %ld, input over input %ld)\n", g_checks, g_seen[TOUCH_OK], g_seen[ONE_BYTE_REFUSED],
-           g_seen[IN_OVER_IN_OK]);
+    printf("args_check: ok (%ld checks; touching %ld, one byte %ld, input over input %ld; flow fields at an odd base %ld, clips %ld)\n", g_checks,
+           g_seen[TOUCH_OK], g_seen[ONE_BYTE_REFUSED], g_seen[IN_OVER_IN_OK], flow_odd_base_ok, clip_cases);
     return 0;
 }

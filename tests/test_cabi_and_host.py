@@ -72,6 +72,48 @@ def test_level_geometry_entry_point_matches_oracle(orc):
     assert lib.rcflow_level_geometry(640, 480, 1.0, 2, 0, None, None) == -1
 
 
+def test_entry_points_without_a_context_name_themselves_when_they_refuse():
+    """Every refusal sets a text that starts with the entry point's name (and names the pointer, where one is null), over the
+    text an earlier call left; the codes are the ones these calls always returned."""
+    from ripcurrents_amd import _lib
+    lib = _lib.load()
+    f32, f64, i32 = (ctypes.c_float * 40)(), (ctypes.c_double * 8)(), (ctypes.c_int * 8)()
+    names = (ctypes.c_char_p * 2)()
+    for name, argtypes in (("rcflow_debug_plan_poly", [ctypes.c_int, ctypes.c_double, ctypes.c_int] + [ctypes.c_void_p] * 6),
+                           ("rcflow_debug_plan_poly_folded", [ctypes.c_int, ctypes.c_double, ctypes.c_int] + [ctypes.c_void_p] * 4),
+                           ("rcflow_debug_plan_pyr_kernel", [ctypes.c_int, ctypes.c_double, ctypes.c_void_p]),
+                           ("rcflow_debug_kind", [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+                           ("rcflow_debug_chain_plan", [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_int])):
+        getattr(lib, name).argtypes, getattr(lib, name).restype = argtypes, ctypes.c_int
+    cases = [("rcflow_level_geometry", (0, 480, 0.5, 2, 0, None, None), None), ("rcflow_level_geometry", (640, 480, 1.0, 2, 0, None, None), None),
+             ("rcflow_level_geometry", (640, 480, 0.5, -1, 0, None, None), None), ("rcflow_level_geometry", (640, 480, 0.5, 2, -1, None, None), None),
+             ("rcflow_pyrlk_levels", (0, 48, 21, 21, 3), None), ("rcflow_pyrlk_levels", (64, 48, 2, 21, 3), None), ("rcflow_pyrlk_levels", (64, 48, 21, 21, -1), None),
+             ("rcflow_jet_lut", (None,), "lut_bgr"),
+             ("rcflow_debug_chain_plan", (0, 1080, 32, 8, 0, i32, 8), None), ("rcflow_debug_chain_plan", (1920, 1080, 0, 8, 0, i32, 8), None),
+             ("rcflow_debug_chain_plan", (1920, 1080, 32, 8, 0, i32, 1), None), ("rcflow_debug_chain_plan", (1920, 1080, 32, 8, 0, None, 8), "starts"),
+             ("rcflow_debug_plan_poly", (0, 1.1, 0, f32, f32, f32, f64, i32, f64), None), ("rcflow_debug_plan_poly", (33, 1.1, 0, f32, f32, f32, f64, i32, f64), None),
+             ("rcflow_debug_plan_poly", (5, -1.0, 0, f32, f32, f32, f64, i32, f64), None)]
+    cases += [("rcflow_debug_plan_poly", tuple([5, 1.1, 0] + [None if j == i else a for j, a in enumerate((f32, f32, f32, f64, i32, f64))]), nm)
+              for i, nm in enumerate(("g", "xg", "xxg", "ig", "n_eff", "kdc"))]
+    cases += [("rcflow_debug_plan_poly_folded", (0, 1.1, 0, f32, f32, f32, f64), None)]
+    cases += [("rcflow_debug_plan_poly_folded", tuple([5, 1.1, 0] + [None if j == i else a for j, a in enumerate((f32, f32, f32, f64))]), nm)
+              for i, nm in enumerate(("qh", "xga", "xgb", "kdch"))]
+    cases += [("rcflow_debug_plan_pyr_kernel", (0, 1.0, f32), None), ("rcflow_debug_plan_pyr_kernel", (1024, 1.0, f32), None),
+              ("rcflow_debug_plan_pyr_kernel", (5, -1.0, f32), None), ("rcflow_debug_plan_pyr_kernel", (5, 1.0, None), "taps"),
+              ("rcflow_debug_kind", (-1, names, names), None), ("rcflow_debug_kind", (25, names, names), None),
+              ("rcflow_debug_kind", (0, None, names), "name"), ("rcflow_debug_kind", (0, names, None), "bucket")]
+    cases += [("rcflow_profile_enable", (None, 0), "ctx"), ("rcflow_profile_reset", (None,), "ctx"),
+              ("rcflow_profile_read", (None, 0, None, None, None, None, None), "ctx"), ("rcflow_profile_read_buckets", (None, None, None), "ctx")]
+    for name, args, named in cases:
+        assert lib.rcflow_set_option(None, b"chunk", 1) == -1                 # plants the text of another call
+        planted = lib.rcflow_last_error()
+        assert getattr(lib, name)(*args) == -1, (name, args)
+        text = lib.rcflow_last_error().decode()
+        assert text != planted.decode() and text.startswith(name + ":"), (name, args, text)
+        assert named is None or re.search(r"\b%s\b" % named, text[len(name):]), (name, args, text)
+    assert not any(f32) and not any(f64) and not any(i32)                    # nothing was written
+
+
 def test_synthetic_clips_are_deterministic():
     from ripcurrents_amd import synth
     a = synth.surf_clip(160, 120, 3, seed=1234)
