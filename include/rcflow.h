@@ -1313,6 +1313,118 @@ int rcflow_planview_close(rc_ctx* ctx, int stream);
 /* never blocks; RC_ESTATE when nothing is open */
 int rcflow_planview_info(rc_ctx* ctx, int stream, rc_planview_info* info);
 
+/* ------------------------------------------------------------------ wave spectra: period, wavenumber, celerity and depth
+ * What are the waves doing, and how deep is the water under them?  Every product above looks at the flow; this one looks at
+ * the grey value of every pixel over time.  It keeps a sliding discrete Fourier transform of the last `window` frames at a
+ * few frequency bins per pixel, and per grid cell picks the bin that carries the most power, takes the wavenumber from the
+ * phase gradient of that bin across the cell, and from frequency and wavenumber the celerity and, through the linear
+ * dispersion relation omega^2 = g k tanh(k h), the depth: the first stage of what the coastal-imaging literature calls
+ * cBathy.  A rip channel is the deep gap in the bar; the windows of ripmap and ftle are best chosen from the wave period.
+ * The input is a grey frame, normally the plan picture greyed with rcflow_resize_bgr_to_gray_dev, so that a pixel is
+ * metres_per_pixel_x by metres_per_pixel_y metres.  The reference has no such product.  tests/_waves_ref.py states the
+ * following in numpy.  Everything up to the cell sums is integer and exact, whatever the tiling.
+ *
+ *  State: a ring of `window` (W) grey frames, zero at open and reset; per pixel and bin b in bin_lo..bin_hi (K of them; bin b
+ *  is b * fps / W Hz) one complex accumulator A_b of two int32; the host's table Tc[j] = lrint(2048 cos((2 pi j) / W)),
+ *  Ts[j] = lrint(2048 sin((2 pi j) / W)), j in 0..W-1, in double.
+ *  1. Spectrum ("waves@0"), every push.  c = pushes mod W; d = new - ring[c] as int; ring[c] = new; for every bin, with
+ *     j = (b c) mod W: A_b.re += d Tc[j], A_b.im -= d Ts[j].  A_b is therefore always the table's DFT of the ring as it stands,
+ *     frames not yet pushed counting as zero.  |component| <= 255 * 2048 * W < 2^31 for W <= 4096: int32 never wraps.
+ *  2. Cell sums ("waves@1"), when any output is asked for.  sh = max(0, bit_length(255 * 2048 * W) - 15); Xs = A >> sh, an
+ *     arithmetic shift of each component, so |Xs| < 2^15.  s = spacing.  Pixel (x, y) TAKES PART when s <= x < w - s and
+ *     s <= y < h - s and, where d_mask is given, the mask is non-zero at the pixel and at its four neighbours at +-s in x and
+ *     in y.  Its cell is (min(x / (w / grid_x), grid_x - 1), min(y / (h / grid_y), grid_y - 1)), as the opposing-flow map's.
+ *     Per cell and bin six int64, in this order, over the pixels that take part (C the pixel, E, W, S, N at x+s, x-s, y+s, y-s):
+ *       n += 1    P += |Xs_C|^2    Re Cx, Im Cx += Xs_E conj(Xs_W)    Re Cy, Im Cy += Xs_S conj(Xs_N)
+ *  3. Closing per cell, in DOUBLE, every operation rounded on its own, left to right; a record is 32 bytes (rc_wave_cell).
+ *     RC_WAVES_EMPTY when n < min_pixels or every P is 0: the record is otherwise zero.  Else b* is the bin of the largest P,
+ *     the lowest bin winning ties, and with that bin's sums, every int64 converted to double once (Im negated as an integer):
+ *       kx = atan2(-Im Cx, Re Cx) / (2 s) / metres_per_pixel_x      ky likewise from Cy and metres_per_pixel_y      rad/m
+ *       kmag = sqrt(kx*kx + ky*ky)    freq_hz = b* * fps / W    omega = 6.283185307179586 * b* * fps / W
+ *       quality = (sqrt(ReCx^2 + ImCx^2) + sqrt(ReCy^2 + ImCy^2)) / (2 * P)
+ *     The sign: a wave I = cos(k.x - omega t) gives A proportional to e^{-i k.x}, so (kx, ky) points where the wave travels.
+ *     quality is near 1 for one plane wave and near 0 for noise; it is NOT bounded by 1 (Cauchy-Schwarz bounds |Cx| by the
+ *     geometric mean of the power at E and at W, not by the power at C).  RC_WAVES_NOWAVE when kmag is 0: celerity and depth
+ *     are 0.  Else celerity = omega / kmag (m/s) and t = omega*omega / (gravity * kmag): depth = atanh(t) / kmag (m) when
+ *     t < tanh_max, otherwise RC_WAVES_DEEP and depth 0 (the water is too deep for the wave to feel the bed, or k was
+ *     underestimated).  atan2 and atanh are the device's, in double: their last-place error may move a stored float by one unit
+ *     in the last place, and a t within that error of tanh_max may fall on either side.  Every integer is exact.
+ *  4. Bin map (8UC1): b* of the pixel's cell, 0 where the cell is EMPTY; a byte holds it, so a session opened with bin_hi above
+ *     255 has no bin map (RC_EINVAL when one is asked for; the records carry b* as an int).  Picture (8UC3): entry i of rcflow_jet_lut,
+ *     i = rint(depth / (float)vis_max_depth * 255) saturated to 0..255, from the record's float, as the FTLE picture; black where
+ *     the cell is EMPTY, NOWAVE or DEEP ("waves@2", when either is asked for).
+ *  5. Summary, 8 int64: held frames min(pushes, W) | pixels that take part | cells not EMPTY | cells with a depth (flags 0) |
+ *     pushes since open / reset | 0 | 0 | 0. */
+#define RC_WAVES_EMPTY 1
+#define RC_WAVES_NOWAVE 2
+#define RC_WAVES_DEEP 4
+#define RC_WAVES_MAX_WINDOW 4096
+#define RC_WAVES_MAX_BINS 16
+#define RC_WAVES_MAX_SPACING 16
+#define RC_WAVES_MAX_STATE_BYTES (4ull << 30)   /* ring plus accumulators */
+#define RC_WAVES_LAUNCHES 3        /* of a push that computes everything; a push with no output is one */
+typedef struct rc_waves_params {
+    int window;             /* W: 2..RC_WAVES_MAX_WINDOW frames */
+    int bin_lo, bin_hi;     /* 1 <= bin_lo <= bin_hi < W / 2 (2 bin_hi < W), at most RC_WAVES_MAX_BINS bins */
+    int spacing;            /* s: 1..RC_WAVES_MAX_SPACING pixels, half the baseline of the phase differences */
+    int grid_x, grid_y;     /* >= 1, <= w, h, at most RC_RIPMAP_MAX_CELLS cells */
+    int min_pixels;         /* >= 1: a cell with fewer pixels taking part is EMPTY */
+    int flags;              /* 0 */
+    double fps;             /* frames per second; finite, > 0 */
+    double metres_per_pixel_x, metres_per_pixel_y;   /* finite, > 0 */
+    double gravity;         /* m/s^2; finite, > 0 */
+    double tanh_max;        /* in (0, 1): the largest tanh(k h) a depth is given for */
+    double vis_max_depth;   /* finite, > 0: the depth the picture's last colour stands for */
+} rc_waves_params;
+typedef struct rc_wave_cell {
+    int bin;                /* b*, 0 for an EMPTY cell */
+    int flags;              /* RC_WAVES_EMPTY, RC_WAVES_NOWAVE, RC_WAVES_DEEP, or 0: every field holds */
+    float freq_hz, kx, ky, celerity, depth, quality;
+} rc_wave_cell;
+typedef struct rc_waves_info {
+    int w, h;
+    rc_waves_params prm;               /* tanh_max, min_pixels and vis_max_depth as rcflow_waves_set left them */
+    int launches_per_push;             /* RC_WAVES_LAUNCHES */
+    int bins;                          /* K */
+    int shift;                         /* sh */
+    int held;                          /* min(pushes, W) */
+    long long pushes;                  /* since open / reset */
+    size_t device_bytes;
+} rc_waves_info;
+/* Allocates everything the slot will ever need: the ring (1 B/px per frame, rows of w rounded up to 4 pixels), the
+ * accumulators (8 B/px per bin), the cell sums and records.  Re-opening replaces the state; a refused open leaves the open
+ * state as it was.  RC_EINVAL: no parameters, w or h < 1, a value outside the ranges above, unknown flag bits; RC_ESIZE beyond
+ * the context's max_w x max_h, or ring plus accumulators above RC_WAVES_MAX_STATE_BYTES. */
+int rcflow_waves_open(rc_ctx* ctx, int stream, int w, int h, const rc_waves_params* prm);
+/* One grey frame (8UC1, w x h, step >= w) into the ring and the accumulators ("waves@0").  d_mask (8UC1, may be NULL) limits
+ * the pixels that take part.  Outputs (device memory, each may be NULL): d_cells grid_y x grid_x rc_wave_cell (4-byte aligned),
+ * d_sums grid_y x grid_x x K x 6 int64 (8-byte aligned), d_bin_map 8UC1 and d_vis 8UC3 (w x h), d_summary 8 int64 (8-byte
+ * aligned).  With every output NULL the push is ONE launch: push every frame, ask for the cells every k-th.  With any output
+ * "waves@1" follows, and "waves@2" when d_bin_map or d_vis is asked for: RC_WAVES_LAUNCHES at most, and what they give does
+ * not depend on which earlier pushes computed.  No host synchronisation, no device-to-host copy.  An output whose byte range
+ * [first byte, past the last) overlaps an input's or another output's is RC_EINVAL, as is d_bin_map when bin_hi > 255; a mask
+ * given with every output NULL is checked and not read.  Row padding is never written.  Every refusal is decided before
+ * anything is queued and leaves the state as it was; RC_ESTATE before rcflow_waves_open. */
+int rcflow_waves_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_gray, size_t step, const uint8_t* d_mask, size_t mask_step,
+                          rc_wave_cell* d_cells, long long* d_sums, uint8_t* d_bin_map, size_t bin_map_step,
+                          uint8_t* d_vis, size_t vis_step, long long* d_summary);
+/* Blocks until the slot's stream has finished; for hosts and tests.  Each may be NULL: the records, the sums and the summary
+ * of the last push that computed them (host memory, the sizes of rcflow_waves_push_dev's outputs); zeros before that. */
+int rcflow_waves_read(rc_ctx* ctx, int stream, rc_wave_cell* cells, long long* sums, long long summary[8]);
+/* Blocks; the accumulators as K x h x w x 2 int32 (re, im), whatever the layout on the device; for tests */
+int rcflow_waves_spectrum_read(rc_ctx* ctx, int stream, int32_t* spectrum);
+/* never blocks; the host's table, W ints each (either may be NULL) */
+int rcflow_waves_table_read(rc_ctx* ctx, int stream, int32_t* tc, int32_t* ts);
+/* tanh_max, min_pixels and vis_max_depth from the next push on; RC_EINVAL as rcflow_waves_open */
+int rcflow_waves_set(rc_ctx* ctx, int stream, double tanh_max, int min_pixels, double vis_max_depth);
+/* zeroes the ring, the accumulators, the records, the summary and the push count; keeps the allocation; asynchronous, on
+ * the slot's stream */
+int rcflow_waves_reset(rc_ctx* ctx, int stream);
+/* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
+int rcflow_waves_close(rc_ctx* ctx, int stream);
+/* never blocks; RC_ESTATE when nothing is open, RC_EINVAL without a buffer */
+int rcflow_waves_info(rc_ctx* ctx, int stream, rc_waves_info* info);
+
 /* Display path, ripcurrents.cpp:233-273 (= streamline_displacement / _total_motion / _ratio /
  * _positions, ripcurrents_module.cpp:13-60) on the slot's streamline field (rcflow_advect_field_dev):
  * which 0 = |pt|, 1 = dist, 2 = |pt| / dist; minMaxLoc + convertTo(CV_8UC1, 255/max) +
@@ -1393,7 +1505,7 @@ int rcflow_profile_read(rc_ctx* ctx, int cap, const char** names, int* launches,
 
 /* The same totals under the reference's own bucket names, in the order it prints them (ripcurrents.cpp:103-109,
  * :518-524): farneback, polar, threshold, overlay, erosion, codec, stream ("pathlines").  GPU time of the kernels
- * that do each bucket's work ("overlay" includes the time-exposure images and the 8-bit colour stages, "farneback" the frame stabilisation, the opposing-flow map, the motion templates and the plan view, "stream" the flow map and FTLE); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
+ * that do each bucket's work ("overlay" includes the time-exposure images, the 8-bit colour stages and the wave spectra, "farneback" the frame stabilisation, the opposing-flow map, the motion templates and the plan view, "stream" the flow map and FTLE); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
  * classification kernels, booked under "threshold"), "codec" is 0 (video decode is host I/O outside the library).
  * names / ms: RC_PROFILE_BUCKETS entries each (either may be NULL).  Returns RC_PROFILE_BUCKETS. */
 #define RC_PROFILE_BUCKETS 7

@@ -1021,4 +1021,87 @@ class PlanView {
     void *d_flow_ = nullptr, *d_bgr_ = nullptr, *d_plan_ = nullptr, *d_mask_ = nullptr, *d_pic_ = nullptr;
 };
 
+// Wave spectra on the device (rcflow_waves_*): a sliding DFT of the last `window` grey frames at a few bins per pixel, and per
+// grid cell the strongest bin, its wavenumber, the celerity and the depth.  Host grey frames of the pipeline's size in; the
+// cells' records, the bin map and the depth picture out.
+class Waves {
+  public:
+    Waves(Pipeline& pipe, const rc_waves_params& prm) : pipe_(pipe) {
+        check(rcflow_waves_open(pipe.context(), 0, pipe.width(), pipe.height(), &prm));
+        rc_waves_info i;
+        check(rcflow_waves_info(pipe.context(), 0, &i));
+        cells_ = (size_t)prm.grid_x * prm.grid_y;
+        bins_ = i.bins;
+    }
+    ~Waves() {
+        (void)rcflow_waves_close(pipe_.context(), 0);
+        for (void* p : {d_gray_, d_mask_, d_bin_, d_vis_, d_summary_}) if (p) (void)hipFree(p);
+    }
+    Waves(const Waves&) = delete;
+    Waves& operator=(const Waves&) = delete;
+
+    // gray: 8UC1 of the pipeline's size; mask (8UC1, optional) limits the pixels that take part.  Each output is optional:
+    // bin_map 8UC1, picture 8UC3 (JET of the depth); compute asks for records, sums and summary, which read() and cells()
+    // then return.  Without any the frame only enters the ring and the spectrum (one launch).
+    void push(const Mat& gray, const Mat* mask = nullptr, bool compute = false, Mat* bin_map = nullptr, Mat* picture = nullptr) {
+        const int w = pipe_.width(), h = pipe_.height();
+        if (!fits(gray, 1) || (mask && !fits(*mask, 1)))
+            throw Error(RC_EINVAL, "Waves::push: the frame and the mask must be 8UC1 of the pipeline's size");
+        if ((bin_map && !fits(*bin_map, 1)) || (picture && !fits(*picture, 3)))
+            throw Error(RC_EINVAL, "Waves::push: bin_map 8UC1, picture 8UC3, each of the pipeline's size");
+        const size_t px = (size_t)w * h;
+        if (!d_gray_) hip_check(hipMalloc(&d_gray_, px), "hipMalloc frame");
+        if (mask && !d_mask_) hip_check(hipMalloc(&d_mask_, px), "hipMalloc mask");
+        if (bin_map && !d_bin_) hip_check(hipMalloc(&d_bin_, px), "hipMalloc bin map");
+        if (picture && !d_vis_) hip_check(hipMalloc(&d_vis_, px * 3), "hipMalloc picture");
+        if (compute && !d_summary_) hip_check(hipMalloc(&d_summary_, 64), "hipMalloc summary");
+        check(rcflow_sync(pipe_.context(), 0));                  // the last push may still be reading the staging frame
+        hip_check(hipMemcpy2D(d_gray_, (size_t)w, gray.data, gray.step, (size_t)w, h, hipMemcpyHostToDevice), "upload frame");
+        if (mask) hip_check(hipMemcpy2D(d_mask_, (size_t)w, mask->data, mask->step, (size_t)w, h, hipMemcpyHostToDevice), "upload mask");
+        check(rcflow_waves_push_dev(pipe_.context(), 0, (const uint8_t*)d_gray_, (size_t)w, mask ? (const uint8_t*)d_mask_ : nullptr, (size_t)w,
+                                    nullptr, nullptr, bin_map ? (uint8_t*)d_bin_ : nullptr, (size_t)w, picture ? (uint8_t*)d_vis_ : nullptr,
+                                    (size_t)w * 3, compute ? (long long*)d_summary_ : nullptr));
+        if (!bin_map && !picture) return;
+        check(rcflow_sync(pipe_.context(), 0));
+        if (bin_map) hip_check(hipMemcpy2D(bin_map->data, bin_map->step, d_bin_, (size_t)w, (size_t)w, h, hipMemcpyDeviceToHost), "download bin map");
+        if (picture) hip_check(hipMemcpy2D(picture->data, picture->step, d_vis_, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost), "download picture");
+    }
+    // each waits for the pipeline's stream: of the last push that computed (include/rcflow.h).  The summary: held frames, pixels
+    // that take part, cells not empty, cells with a depth, pushes, 0, 0, 0; the records, grid_y x grid_x; the sums,
+    // grid_y x grid_x x bins x 6
+    std::vector<long long> read() {
+        std::vector<long long> s(8);
+        check(rcflow_waves_read(pipe_.context(), 0, nullptr, nullptr, s.data()));
+        return s;
+    }
+    std::vector<rc_wave_cell> cells() {
+        std::vector<rc_wave_cell> c(cells_);
+        check(rcflow_waves_read(pipe_.context(), 0, c.data(), nullptr, nullptr));
+        return c;
+    }
+    std::vector<long long> sums() {
+        std::vector<long long> s(cells_ * bins_ * 6);
+        check(rcflow_waves_read(pipe_.context(), 0, nullptr, s.data(), nullptr));
+        return s;
+    }
+    // waits: the accumulators, bins x rows x cols x (re, im)
+    std::vector<int32_t> spectrum() {
+        std::vector<int32_t> a((size_t)bins_ * pipe_.width() * pipe_.height() * 2);
+        check(rcflow_waves_spectrum_read(pipe_.context(), 0, a.data()));
+        return a;
+    }
+    void set(double tanh_max, int min_pixels, double vis_max_depth) { check(rcflow_waves_set(pipe_.context(), 0, tanh_max, min_pixels, vis_max_depth)); }
+    rc_waves_info info() { rc_waves_info i; check(rcflow_waves_info(pipe_.context(), 0, &i)); return i; }
+    void reset() { check(rcflow_waves_reset(pipe_.context(), 0)); }
+
+  private:
+    bool fits(const Mat& m, int channels) const {
+        return !m.empty() && m.rows == pipe_.height() && m.cols == pipe_.width() && m.channels == channels && m.elem == 1;
+    }
+    Pipeline& pipe_;
+    size_t cells_ = 0;
+    int bins_ = 0;
+    void *d_gray_ = nullptr, *d_mask_ = nullptr, *d_bin_ = nullptr, *d_vis_ = nullptr, *d_summary_ = nullptr;
+};
+
 }  // namespace rc

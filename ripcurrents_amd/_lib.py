@@ -49,6 +49,9 @@ FTLE_DIRECTIONS = {"forward": 0, "backward": 1}
 RC_FTLE_MAX_WINDOW, RC_FTLE_MAX_SPACING, RC_FTLE_LAUNCHES = 256, 16, 3
 # rcflow_planview_*: the launches of a push
 RC_PLANVIEW_LAUNCHES = 1
+# rcflow_waves_*: the record's flags, the bounds, the launches of a push that computes everything
+RC_WAVES_EMPTY, RC_WAVES_NOWAVE, RC_WAVES_DEEP = 1, 2, 4
+RC_WAVES_MAX_WINDOW, RC_WAVES_MAX_BINS, RC_WAVES_MAX_SPACING, RC_WAVES_MAX_STATE_BYTES, RC_WAVES_LAUNCHES = 4096, 16, 16, 4 << 30, 3
 
 ERRORS = {-1: "RC_EINVAL", -2: "RC_ENOMEM", -3: "RC_EHIP", -4: "RC_ENODEV", -5: "RC_ESIZE",
           -6: "RC_ESTATE", -7: "RC_ECOMM"}
@@ -177,6 +180,19 @@ class PlanViewInfo(C.Structure):
     """rc_planview_info (include/rcflow.h)."""
     _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", PlanViewParams), ("launches_per_push", C.c_int), ("pushes", C.c_longlong),
                 ("device_bytes", C.c_size_t)]
+
+
+class WavesParams(C.Structure):
+    """rc_waves_params (include/rcflow.h)."""
+    _fields_ = [("window", C.c_int), ("bin_lo", C.c_int), ("bin_hi", C.c_int), ("spacing", C.c_int), ("grid_x", C.c_int), ("grid_y", C.c_int),
+                ("min_pixels", C.c_int), ("flags", C.c_int), ("fps", C.c_double), ("metres_per_pixel_x", C.c_double),
+                ("metres_per_pixel_y", C.c_double), ("gravity", C.c_double), ("tanh_max", C.c_double), ("vis_max_depth", C.c_double)]
+
+
+class WavesInfo(C.Structure):
+    """rc_waves_info (include/rcflow.h)."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", WavesParams), ("launches_per_push", C.c_int), ("bins", C.c_int), ("shift", C.c_int),
+                ("held", C.c_int), ("pushes", C.c_longlong), ("device_bytes", C.c_size_t)]
 
 
 class FitParams(C.Structure):
@@ -349,6 +365,15 @@ SIGNATURES = {
     "rcflow_planview_reset": [_vp, _i],
     "rcflow_planview_close": [_vp, _i],
     "rcflow_planview_info": [_vp, _i, C.POINTER(PlanViewInfo)],
+    "rcflow_waves_open": [_vp, _i, _i, _i, C.POINTER(WavesParams)],
+    "rcflow_waves_push_dev": [_vp, _i, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _sz, _vp],
+    "rcflow_waves_read": [_vp, _i, _vp, _vp, C.POINTER(C.c_longlong)],
+    "rcflow_waves_spectrum_read": [_vp, _i, _vp],
+    "rcflow_waves_table_read": [_vp, _i, _vp, _vp],
+    "rcflow_waves_set": [_vp, _i, C.c_double, _i, C.c_double],
+    "rcflow_waves_reset": [_vp, _i],
+    "rcflow_waves_close": [_vp, _i],
+    "rcflow_waves_info": [_vp, _i, C.POINTER(WavesInfo)],
     "rcflow_comm_unique_id": [_vp],
     "rcflow_comm_init": [_vp, _vp, _i, _i],
     "rcflow_comm_destroy": [_vp],

@@ -36,8 +36,9 @@ from ._lib import TracksInfo, TracksParams
 from ._lib import RC_MOTION_AUTO_TIME, RC_MOTION_FRESH, MotionInfo, MotionParams
 from ._lib import FTLE_DIRECTIONS, FtleInfo, FtleParams
 from ._lib import PlanViewInfo, PlanViewParams
+from ._lib import WavesInfo, WavesParams
 
-__all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState"]
+__all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState", "Waves"]
 
 
 # rc_draw_prim as a numpy record (32 bytes): what Context.draw takes and Context.tracers_prims returns
@@ -53,6 +54,10 @@ REGION_DTYPE = np.dtype([("label", "<i4"), ("area", "<i4"), ("x0", "<i4"), ("y0"
 # the eight words of a regions summary, in order
 FTLE_SUMMARY = ("held", "valid", "mask", "stopped", "max_lam_bits", "pushes", "reserved0", "reserved1")
 PLANVIEW_SUMMARY = ("usable", "seen", "valid", "max_speed2_bits", "pushes", "reserved0", "reserved1", "reserved2")
+WAVES_SUMMARY = ("held", "participating", "nonempty", "with_depth", "pushes", "reserved0", "reserved1", "reserved2")
+# rc_wave_cell as a numpy record (32 bytes): what Context.waves_read returns
+WAVE_CELL_DTYPE = np.dtype([("bin", "<i4"), ("flags", "<i4"), ("freq_hz", "<f4"), ("kx", "<f4"), ("ky", "<f4"), ("celerity", "<f4"),
+                            ("depth", "<f4"), ("quality", "<f4")])
 REGIONS_SUMMARY = ("components", "kept", "records", "foreground", "kept_pixels", "bad_pixels", "pushes", "largest_area")
 # rc_track as a numpy record (128 bytes): what Context.tracks_read returns
 TRACK_DTYPE = np.dtype([("id", "<i8"), ("parent", "<i8"), ("first_push", "<i8"), ("area_sum", "<i8"), ("fx_sum", "<i8"), ("fy_sum", "<i8"),
@@ -1496,6 +1501,91 @@ class Context:
         self._bind(stream)          # waits for the pushes queued on that stream before freeing
         check(self._lib.rcflow_planview_close(self._h, stream))
 
+    # ------------------------------------------------------------------ wave spectra
+    def waves_open(self, w, h, window=256, bin_lo=1, bin_hi=1, spacing=2, grid_x=1, grid_y=1, min_pixels=1, fps=2.0, metres_per_pixel_x=1.0,
+                   metres_per_pixel_y=1.0, gravity=9.81, tanh_max=0.95, vis_max_depth=10.0, stream=0):
+        """Opens the slot's wave spectra for w x h grey frames (include/rcflow.h, "wave spectra"): a ring of the last `window`
+        frames, a sliding DFT at bins bin_lo..bin_hi per pixel (bin b is b * fps / window Hz), and per cell of a grid_x x grid_y
+        grid the strongest bin, the wavenumber from its phase differences over 2 * spacing pixels, the celerity and the depth.
+        The state takes window + 8 * bins bytes per pixel of device memory (0.8 GB at 1080p, window 256 and 16 bins)."""
+        p = WavesParams(window=int(window), bin_lo=int(bin_lo), bin_hi=int(bin_hi), spacing=int(spacing), grid_x=int(grid_x), grid_y=int(grid_y),
+                        min_pixels=int(min_pixels), flags=0, fps=float(fps), metres_per_pixel_x=float(metres_per_pixel_x),
+                        metres_per_pixel_y=float(metres_per_pixel_y), gravity=float(gravity), tanh_max=float(tanh_max),
+                        vis_max_depth=float(vis_max_depth))
+        self._bind(stream)          # the state is zeroed on the slot's stream: the one the pushes will run on
+        check(self._lib.rcflow_waves_open(self._h, stream, int(w), int(h), C.byref(p)))
+
+    def waves_info(self, stream=0):
+        """dict(w, h, the parameters, launches_per_push, bins, shift, held, pushes, device_bytes); never blocks."""
+        i = WavesInfo()
+        check(self._lib.rcflow_waves_info(self._h, stream, C.byref(i)))
+        out = {k: getattr(i.prm, k) for k, _ in WavesParams._fields_ if k != "flags"}
+        out.update(w=i.w, h=i.h, launches_per_push=i.launches_per_push, bins=i.bins, shift=i.shift, held=i.held, pushes=i.pushes,
+                   device_bytes=i.device_bytes)
+        return out
+
+    def waves_push(self, gray, mask=None, cells=None, sums=None, bin_map=None, vis=None, summary=None, stream=0):
+        """One grey frame (HxW uint8 device tensor, rows may be padded) into the ring and the spectrum; nothing is synchronised.
+        mask (HxW uint8, optional) limits the pixels that take part.  Outputs are preallocated device tensors, each optional:
+        cells GYxGXx32 uint8 (rc_wave_cell records; view the host copy as WAVE_CELL_DTYPE), sums GYxGXxKx6 int64, bin_map HxW
+        uint8, vis HxWx3 uint8, summary 8 int64 (WAVES_SUMMARY).  Without any output the push is one launch; with any it is at
+        most RC_WAVES_LAUNCHES.  Records, sums and summary also stay on the slot for waves_read."""
+        info = self.waves_info(stream)
+        h, w, gx, gy, K = info["h"], info["w"], info["grid_x"], info["grid_y"], info["bins"]
+        ins = []
+        for t, name, need in ((gray, "gray", True), (mask, "mask", False)):
+            if t is None and not need:
+                ins += [C.c_void_p(None), 0]
+                continue
+            if not _is_t(t) or not t.is_cuda or t.dtype != torch.uint8 or tuple(t.shape) != (h, w) or t.stride(1) != 1:
+                raise ValueError("%s must be a %dx%d uint8 device tensor with dense pixels, as opened" % (name, h, w))
+            ins += [self._ptr(t), t.stride(0)]
+        cp = self._out_array(cells, torch.uint8, "cells", gy * gx * 32)
+        sp = self._out_array(sums, torch.int64, "sums", gy * gx * K * 6)
+        images = self._out_image(bin_map, torch.uint8, "bin_map", (h, w)) + self._out_image(vis, torch.uint8, "vis", (h, w, 3))
+        up = self._out_array(summary, torch.int64, "summary", 8)
+        self._bind(stream)
+        check(self._lib.rcflow_waves_push_dev(self._h, stream, *ins, cp, sp, *images, up))
+
+    def waves_read(self, stream=0):
+        """Waits for the slot's stream -> (cells GYxGX WAVE_CELL_DTYPE, sums GYxGXxKx6 int64, dict of the summary by
+        WAVES_SUMMARY names) of the last push that computed them; zeros before that."""
+        info = self.waves_info(stream)
+        gx, gy, K = info["grid_x"], info["grid_y"], info["bins"]
+        cells = np.zeros((gy, gx), WAVE_CELL_DTYPE)
+        sums = np.zeros((gy, gx, K, 6), np.int64)
+        summ = np.zeros(8, np.int64)
+        self._bind(stream)
+        check(self._lib.rcflow_waves_read(self._h, stream, cells.ctypes.data, sums.ctypes.data, summ.ctypes.data_as(C.POINTER(C.c_longlong))))
+        return cells, sums, dict(zip(WAVES_SUMMARY, (int(v) for v in summ)))
+
+    def waves_spectrum(self, stream=0):
+        """Waits for the slot's stream -> the accumulators, K x H x W x 2 int32 (re, im); for tests."""
+        info = self.waves_info(stream)
+        out = np.empty((info["bins"], info["h"], info["w"], 2), np.int32)
+        self._bind(stream)
+        check(self._lib.rcflow_waves_spectrum_read(self._h, stream, out.ctypes.data))
+        return out
+
+    def waves_table(self, stream=0):
+        """-> (Tc, Ts), `window` int32 each: the twiddle table open built; never blocks."""
+        n = self.waves_info(stream)["window"]
+        tc, ts = np.empty(n, np.int32), np.empty(n, np.int32)
+        check(self._lib.rcflow_waves_table_read(self._h, stream, tc.ctypes.data, ts.ctypes.data))
+        return tc, ts
+
+    def waves_set(self, tanh_max, min_pixels, vis_max_depth, stream=0):
+        """tanh_max, min_pixels and vis_max_depth from the next push on."""
+        check(self._lib.rcflow_waves_set(self._h, stream, float(tanh_max), int(min_pixels), float(vis_max_depth)))
+
+    def waves_reset(self, stream=0):
+        self._bind(stream)
+        check(self._lib.rcflow_waves_reset(self._h, stream))
+
+    def waves_close(self, stream=0):
+        self._bind(stream)          # waits for the pushes queued on that stream before freeing
+        check(self._lib.rcflow_waves_close(self._h, stream))
+
     # ------------------------------------------------------------------ rip regions
     def regions_open(self, w, h, connectivity=8, min_area=1, max_regions=1024, stream=0):
         """Opens the slot's region labelling for w x h masks: connected components (4 or 8 neighbours) numbered in raster
@@ -1750,6 +1840,45 @@ class Context:
         ms = (C.c_double * 7)()
         n = check(self._lib.rcflow_profile_read_buckets(self._h, names, ms))
         return {names[i].decode(): ms[i] for i in range(n)}
+
+
+class Waves:
+    """The wave spectra of one slot as an object: Context.waves_* with the context and the slot bound.  Opens on construction,
+    closes on close() or at the end of a with block."""
+
+    def __init__(self, ctx, w, h, stream=0, **params):
+        self.ctx, self.stream = ctx, stream
+        ctx.waves_open(w, h, stream=stream, **params)
+
+    def push(self, gray, **outputs):
+        self.ctx.waves_push(gray, stream=self.stream, **outputs)
+
+    def read(self):
+        return self.ctx.waves_read(self.stream)
+
+    def info(self):
+        return self.ctx.waves_info(self.stream)
+
+    def spectrum(self):
+        return self.ctx.waves_spectrum(self.stream)
+
+    def table(self):
+        return self.ctx.waves_table(self.stream)
+
+    def set(self, tanh_max, min_pixels, vis_max_depth):
+        self.ctx.waves_set(tanh_max, min_pixels, vis_max_depth, self.stream)
+
+    def reset(self):
+        self.ctx.waves_reset(self.stream)
+
+    def close(self):
+        self.ctx.waves_close(self.stream)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def _alias_tensor(ptr, n, dtype, device):

@@ -232,6 +232,25 @@ struct RcPlanView {
     RcZeroFence zf;
 };
 
+// Wave spectra of one stream slot (waves_kernels.hip).  Everything is allocated by rcflow_waves_open and released by
+// rcflow_waves_close / rcflow_destroy.
+struct RcWaves {
+    bool open = false;
+    int w = 0, h = 0;
+    rc_waves_params prm{};          // tanh_max, min_pixels and vis_max_depth: as rcflow_waves_set left them
+    int K = 0;                      // bins
+    int pitch = 0;                  // row pitch of ring and accumulators in pixels (w rounded up to 4: 4-byte and 32-byte groups)
+    int sh = 0;                     // the shift that brings an accumulator below 2^15
+    long long pushes = 0;           // since open / reset; the next frame goes to ring slot pushes mod window
+    std::vector<int> tc, ts;        // the twiddle table, built by open in double
+    RcBuf ring;                     // [window][h][pitch] bytes
+    RcBuf acc;                      // [K][h][pitch] int2 (re, im)
+    RcBuf cacc;                     // WvCtl | [cells][K][6] int64 the cells launch adds into, zero between launches
+    RcBuf out;                      // the last computing push: records [cells] | sums [cells][K][6] int64 | summary 8 int64
+    RcBuf jet;                      // COLORMAP_JET LUT (768 B), written once by open
+    RcZeroFence zf;
+};
+
 // warp_kernels.hip: one launch of the affine / perspective warp
 struct RcWarpArgs {
     const uint8_t* src; size_t step;
@@ -310,6 +329,7 @@ struct RcSlot {
     RcMotion mt;
     RcFtle ft;
     RcPlanView pv;
+    RcWaves wv;
     RcPhaseCorr pc;
 };
 
@@ -363,7 +383,9 @@ struct rc_ctx {
 // the opposing-flow map does from it, and are booked where that is, under "farneback".  The flow map and FTLE advect a dense
 // particle field as advect_field does and are booked with it, under "stream".  The plan view carries no particle anywhere: it
 // resamples the flow field onto the ground grid and rescales it, after which it is the field every later product takes, so
-// it is booked with the other operations on the field (flow_postop), under "farneback".
+// it is booked with the other operations on the field (flow_postop), under "farneback".  The wave spectra read frames, not the
+// flow, and what they leave (cells, a bin map, a depth picture) is looked at beside the time-exposure images made from the
+// same frames, so they are booked with those, under "overlay".
 #define RC_BUCKET_TABLE(X) \
     X(RC_B_FARNEBACK, "farneback") X(RC_B_POLAR, "polar") X(RC_B_THRESHOLD, "threshold") X(RC_B_OVERLAY, "overlay") \
     X(RC_B_EROSION, "erosion") X(RC_B_CODEC, "codec") X(RC_B_STREAM, "stream")
@@ -400,7 +422,8 @@ struct rc_ctx {
                                                 @6 primitives */ \
     X(RC_K_MOTION, "motion", RC_B_FARNEBACK) /* @0 update, @1 gradient, picture and cell histograms, @2 sums and records, @3 primitives */ \
     X(RC_K_FTLE, "ftle", RC_B_STREAM) /* @0 ring slot, @1 flow map, @2 tensor, outputs and summary */ \
-    X(RC_K_PLANVIEW, "planview", RC_B_FARNEBACK) /* @0 the table (open), @1 the push */
+    X(RC_K_PLANVIEW, "planview", RC_B_FARNEBACK) /* @0 the table (open), @1 the push */ \
+    X(RC_K_WAVES, "waves", RC_B_OVERLAY) /* @0 spectrum, @1 cell sums and closing, @2 bin map and picture */
 #define RC_ROW_ID(id, ...) id,
 enum { RC_BUCKET_TABLE(RC_ROW_ID) RC_B_BUCKETS };
 enum { RC_KIND_TABLE(RC_ROW_ID) RC_K_KINDS };
@@ -481,7 +504,7 @@ struct RcProfScope {
     } while (0)
 
 // ---------------------------------------------------------------------------- per-slot products
-// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle and RcPlanView share one lifecycle.  A product supplies
+// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView and RcWaves share one lifecycle.  A product supplies
 //   void rc_state_free(T&)             frees every buffer and the fence; the state is T() again
 //   int rc_state_zero(RcSlot&, T&)     rc_fence_zero of what open / reset clear, and the counters
 // and open / reset / close are written once, here.
@@ -494,6 +517,7 @@ void rc_state_free(RcTracks& g);
 void rc_state_free(RcMotion& m);
 void rc_state_free(RcFtle& f);
 void rc_state_free(RcPlanView& v);
+void rc_state_free(RcWaves& v);
 int rc_state_zero(RcSlot& s, RcTimex& t);
 int rc_state_zero(RcSlot& s, RcFrameStab& f);
 int rc_state_zero(RcSlot& s, RcRipMap& m);
@@ -503,6 +527,7 @@ int rc_state_zero(RcSlot& s, RcTracks& g);
 int rc_state_zero(RcSlot& s, RcMotion& m);
 int rc_state_zero(RcSlot& s, RcFtle& f);
 int rc_state_zero(RcSlot& s, RcPlanView& v);
+int rc_state_zero(RcSlot& s, RcWaves& v);
 
 // The tail of every open.  The caller has validated, selected the device and built `fresh` (rc: what its allocations
 // returned).  The state that is open is touched only once nothing can be refused any more: a refused open leaves it as it
