@@ -1425,6 +1425,118 @@ int rcflow_waves_close(rc_ctx* ctx, int stream);
 /* never blocks; RC_ESTATE when nothing is open, RC_EINVAL without a buffer */
 int rcflow_waves_info(rc_ctx* ctx, int stream, rc_waves_info* info);
 
+/* ------------------------------------------------------------------ ensemble PIV: cross-correlation flow on a cell grid
+ * Every velocity above comes from a differential estimator (Farneback, PyrLK): it follows the wave orbital motion frame by
+ * frame and has no answer where foam moves several pixels between frames.  This one is particle image velocimetry as the
+ * coastal-imaging literature uses it for surf-zone currents: block cross-correlation of interrogation windows between
+ * consecutive grey frames, the correlation sums added over the last `ensemble` frame pairs BEFORE the peak is taken
+ * (ensemble correlation), so that the wave-by-wave motion averages out of the summed surface and the mean current is left.
+ * It shares nothing with the polynomial expansion and serves as its cross-check.  The reference has no such product.
+ * tests/_piv_ref.py states the following in numpy.  Every sum is an integer and exact, whatever the tiling.
+ *
+ *  Grid.  M = window, R = range, D = 2 R + 1.  grid_x = (w - M - 2 R) / step + 1, grid_y likewise from h.  Cell (cx, cy) has
+ *  its template's top-left corner at (x0, y0) = (R + cx step, R + cy step).
+ *  1. Per pair and cell ("piv@0"), every push but the first after open / reset.  A is the slot's previous frame, B the pushed
+ *     one.  Sa = sum A, Saa = sum A^2 over the M x M template at (x0, y0); for every displacement (j, i) in [-R, R]^2, with B
+ *     taken at (x0 + i, y0 + j): Sab = sum A B, Sb = sum B, Sbb = sum B^2.  Every one is at most 255^2 * 64^2 < 2^31.
+ *     The ensemble: T* are the same sums over the last n = min(pairs, ensemble) pairs, as int64.  For ensemble > 1 the per-pair
+ *     int32 planes are kept in a ring, zero at open and reset: T += new - ring[slot], ring[slot] = new, slot = pair number mod
+ *     ensemble, so T always equals a rescan of the last n pairs; for ensemble = 1 T = new and there is no ring.  The pushed
+ *     frame then becomes A (a device-to-device copy on the slot's stream).  The first push after open / reset only stores its
+ *     frame: n = 0 and every record is RC_PIV_EMPTY.
+ *  2. Score, peak and record ("piv@1"), when any output is asked for.  N = n M^2.  In int64, exact, every magnitude below 2^53:
+ *       num = N Tab - Ta Tb      va = N Taa - Ta^2      vb = N Tbb - Tb^2
+ *       s = (va > 0 && vb > 0) ? ((double)num * fabs((double)num)) / ((double)va * (double)vb) : 0
+ *     each operation rounded on its own: the signed square of the zero-normalised cross-correlation.  The peak is the largest
+ *     s, scanning j outer and i inner, the first occurrence winning.  peak = (float)s.  RC_PIV_FLAT when va == 0 or the peak
+ *     s <= 0: ix, iy, dx, dy are 0.  Else ix = i, iy = j; RC_PIV_EDGE when |i| = R or |j| = R: dx = i, dy = j, no sub-pixel
+ *     step.  Otherwise per axis, in double, with r = copysign(sqrt(|s|), s) of the peak (c) and its two neighbours on the axis
+ *     (l at -1, rr at +1): e = (l - c) + (rr - c), off = e < 0 ? (l - rr) / (2 e) : 0; dx = (float)(i + off_x), dy likewise.
+ *     RC_PIV_LOWPEAK (beside EDGE or alone) when the peak s < min_peak.  The sign is Farneback's: content that moved by
+ *     (u, v) from A to B gives (u, v), in pixels per frame.
+ *  3. Validation ("piv@2"): the normalised median test of Westerweel and Scarano, in float, each operation rounded on its own.
+ *     A cell is VALID when it carries none of EMPTY, FLAT, LOWPEAK.  The valid ones among a valid cell's 8 neighbours are its
+ *     candidates.  Fewer than 3: resid = 0, not tested.  Else per component: um the median of the candidates' values (an even
+ *     count: (a + b) * 0.5f of the two middle ones), rm the median of |v_k - um|, res = |v - um| / (rm + (float)median_eps);
+ *     resid = max(res_x, res_y), RC_PIV_OUTLIER when resid > (float)median_thr.  The candidates' values are those of step 2.
+ *  4. Field (32FC2, grid_y x grid_x): (dx, dy) of a valid cell, (um_x, um_y) for an OUTLIER under RC_PIV_REPLACE, zero where the
+ *     cell is not valid: the small flow field rcflow_ripmap_push_dev, rcflow_ftle_push_dev, rcflow_regions_push_dev and the
+ *     colouring entry points take.  Picture (8UC3, w x h): the cell of pixel (x, y) is (min((x - R) / step, grid_x - 1),
+ *     min((y - R) / step, grid_y - 1)); entry i of rcflow_jet_lut, i = rint(hypotf(fx, fy) / (float)vis_max * 255) saturated to
+ *     0..255, from the cell's field value, as the FTLE picture; black where x < R or y < R and where the cell is not valid.
+ *  5. Summary, 8 int64: n | cells | valid | FLAT | LOWPEAK | EDGE | OUTLIER | pushes since open / reset. */
+#define RC_PIV_EMPTY 1
+#define RC_PIV_FLAT 2
+#define RC_PIV_EDGE 4
+#define RC_PIV_LOWPEAK 8
+#define RC_PIV_OUTLIER 16
+#define RC_PIV_REPLACE 1           /* rc_piv_params.flags: outliers hold their neighbours' median in the field */
+#define RC_PIV_MAX_WINDOW 64
+#define RC_PIV_MAX_RANGE 16
+#define RC_PIV_MAX_ENSEMBLE 256
+#define RC_PIV_MAX_PIXEL_PAIRS (1 << 18)        /* ensemble * window^2 at most: N Tab stays below 2^53 */
+#define RC_PIV_MAX_STATE_BYTES (4ull << 30)     /* ring plus accumulators */
+#define RC_PIV_LAUNCHES 3          /* of a push that computes; a push with no output is one */
+typedef struct rc_piv_params {
+    int window;             /* M: a multiple of 4, 8..RC_PIV_MAX_WINDOW: side of the interrogation window */
+    int range;              /* R: 1..RC_PIV_MAX_RANGE: search radius */
+    int step;               /* 1..M: cell pitch */
+    int ensemble;           /* E: 1..RC_PIV_MAX_ENSEMBLE frame pairs summed, E M^2 <= RC_PIV_MAX_PIXEL_PAIRS */
+    int flags;              /* RC_PIV_REPLACE or 0 */
+    double min_peak;        /* in [0, 1]: lowest accepted peak score */
+    double median_eps;      /* finite, > 0: epsilon of the median test, pixels */
+    double median_thr;      /* finite, > 0: bound of the median test */
+    double vis_max;         /* finite, > 0: the magnitude (pixels per frame) the picture's last colour stands for */
+} rc_piv_params;
+typedef struct rc_piv_cell {
+    float dx, dy;           /* pixels per frame */
+    float peak;             /* the peak's s */
+    float resid;            /* of the median test; 0 where not tested */
+    int ix, iy;             /* the integer peak */
+    int flags;              /* RC_PIV_EMPTY, FLAT, EDGE, LOWPEAK, OUTLIER */
+    int pairs;              /* n */
+} rc_piv_cell;
+typedef struct rc_piv_info {
+    int w, h;
+    rc_piv_params prm;                 /* min_peak, median_eps, median_thr and vis_max as rcflow_piv_set left them */
+    int grid_x, grid_y;
+    int launches_per_push;             /* RC_PIV_LAUNCHES */
+    int pairs;                         /* n = min(pairs, E) */
+    long long pushes;                  /* since open / reset */
+    size_t device_bytes;
+} rc_piv_info;
+/* Allocates everything the slot will ever need: the previous frame, the accumulators (24 D^2 + 16 bytes per cell), for
+ * ensemble > 1 the ring (12 D^2 + 8 bytes per cell and pair), the records.  Re-opening replaces the state; a refused open
+ * leaves the open state as it was.  RC_EINVAL: no parameters, a value outside the ranges above, unknown flag bits, w or h below
+ * M + 2 R, more than RC_RIPMAP_MAX_CELLS cells; RC_ESIZE beyond the context's max_w x max_h, or ring plus accumulators above
+ * RC_PIV_MAX_STATE_BYTES. */
+int rcflow_piv_open(rc_ctx* ctx, int stream, int w, int h, const rc_piv_params* prm);
+/* One grey frame (8UC1, w x h, step >= w): correlated against the slot's previous frame ("piv@0"), then kept as the next
+ * pair's A.  Outputs (device memory, each may be NULL): d_cells grid_y x grid_x rc_piv_cell (4-byte aligned), d_field 32FC2
+ * grid_y x grid_x (pointer and step multiples of 8), d_vis 8UC3 w x h, d_summary 8 int64 (8-byte aligned).  With every output
+ * NULL the push is "piv@0" alone: push every frame, ask every k-th time.  With any output "piv@1" and "piv@2" follow,
+ * RC_PIV_LAUNCHES in all, and what they give does not depend on which earlier pushes computed.  No host synchronisation, no
+ * device-to-host copy.  An output whose byte range [first byte, past the last) overlaps the input's or another output's is
+ * RC_EINVAL.  Row padding is never written.  Every refusal is decided before anything is queued and leaves the state as it
+ * was; RC_ESTATE before rcflow_piv_open. */
+int rcflow_piv_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_gray, size_t step, rc_piv_cell* d_cells, float* d_field,
+                        size_t field_step, uint8_t* d_vis, size_t vis_step, long long* d_summary);
+/* Blocks until the slot's stream has finished; for hosts and tests.  Each may be NULL: the records and the summary of the
+ * last push that computed them (host memory); zeros before that. */
+int rcflow_piv_read(rc_ctx* ctx, int stream, rc_piv_cell* cells, long long summary[8]);
+/* Blocks; for tests.  Each may be NULL: the accumulators as grid_y x grid_x x D x D x 3 int64 (Tab, Tb, Tbb; j outer, i
+ * inner) and the cells' own as grid_y x grid_x x 2 int64 (Ta, Taa), whatever the layout on the device */
+int rcflow_piv_sums_read(rc_ctx* ctx, int stream, long long* sums, long long* cell_sums);
+/* min_peak, median_eps, median_thr and vis_max from the next push on; RC_EINVAL as rcflow_piv_open */
+int rcflow_piv_set(rc_ctx* ctx, int stream, double min_peak, double median_eps, double median_thr, double vis_max);
+/* forgets the previous frame, zeroes the ring, the accumulators, the records, the summary and the push count; keeps the
+ * allocation; asynchronous, on the slot's stream */
+int rcflow_piv_reset(rc_ctx* ctx, int stream);
+/* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
+int rcflow_piv_close(rc_ctx* ctx, int stream);
+/* never blocks; RC_ESTATE when nothing is open, RC_EINVAL without a buffer */
+int rcflow_piv_info(rc_ctx* ctx, int stream, rc_piv_info* info);
+
 /* Display path, ripcurrents.cpp:233-273 (= streamline_displacement / _total_motion / _ratio /
  * _positions, ripcurrents_module.cpp:13-60) on the slot's streamline field (rcflow_advect_field_dev):
  * which 0 = |pt|, 1 = dist, 2 = |pt| / dist; minMaxLoc + convertTo(CV_8UC1, 255/max) +
@@ -1505,7 +1617,7 @@ int rcflow_profile_read(rc_ctx* ctx, int cap, const char** names, int* launches,
 
 /* The same totals under the reference's own bucket names, in the order it prints them (ripcurrents.cpp:103-109,
  * :518-524): farneback, polar, threshold, overlay, erosion, codec, stream ("pathlines").  GPU time of the kernels
- * that do each bucket's work ("overlay" includes the time-exposure images, the 8-bit colour stages and the wave spectra, "farneback" the frame stabilisation, the opposing-flow map, the motion templates and the plan view, "stream" the flow map and FTLE); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
+ * that do each bucket's work ("overlay" includes the time-exposure images, the 8-bit colour stages and the wave spectra, "farneback" the frame stabilisation, the opposing-flow map, the motion templates, the plan view and the ensemble PIV, "stream" the flow map and FTLE); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
  * classification kernels, booked under "threshold"), "codec" is 0 (video decode is host I/O outside the library).
  * names / ms: RC_PROFILE_BUCKETS entries each (either may be NULL).  Returns RC_PROFILE_BUCKETS. */
 #define RC_PROFILE_BUCKETS 7

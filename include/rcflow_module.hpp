@@ -1104,4 +1104,87 @@ class Waves {
     void *d_gray_ = nullptr, *d_mask_ = nullptr, *d_bin_ = nullptr, *d_vis_ = nullptr, *d_summary_ = nullptr;
 };
 
+// Ensemble PIV on the device (rcflow_piv_*): block cross-correlation between consecutive grey frames, the correlation sums added
+// over the last `ensemble` pairs, on a grid of cells.  Host grey frames of the pipeline's size in; the cells' records, the small
+// flow field (grid_y x grid_x, 32FC2) and the picture out.
+class Piv {
+  public:
+    Piv(Pipeline& pipe, const rc_piv_params& prm) : pipe_(pipe) {
+        check(rcflow_piv_open(pipe.context(), 0, pipe.width(), pipe.height(), &prm));
+        rc_piv_info i;
+        check(rcflow_piv_info(pipe.context(), 0, &i));
+        gx_ = i.grid_x; gy_ = i.grid_y;
+        disp_ = (size_t)(2 * prm.range + 1) * (2 * prm.range + 1);
+    }
+    ~Piv() {
+        (void)rcflow_piv_close(pipe_.context(), 0);
+        for (void* p : {d_gray_, d_field_, d_vis_, d_summary_}) if (p) (void)hipFree(p);
+    }
+    Piv(const Piv&) = delete;
+    Piv& operator=(const Piv&) = delete;
+
+    int grid_x() const { return gx_; }
+    int grid_y() const { return gy_; }
+
+    // gray: 8UC1 of the pipeline's size.  Each output is optional: field 32FC2 of grid_y x grid_x (pixels per frame), picture 8UC3
+    // of the pipeline's size (JET of the magnitude); compute asks for records and summary, which read() and cells() then return.
+    // Without any the frame is only correlated into the sums (one launch).
+    void push(const Mat& gray, bool compute = false, Mat* field = nullptr, Mat* picture = nullptr) {
+        const int w = pipe_.width(), h = pipe_.height();
+        if (gray.empty() || gray.rows != h || gray.cols != w || gray.channels != 1 || gray.elem != 1)
+            throw Error(RC_EINVAL, "Piv::push: the frame must be 8UC1 of the pipeline's size");
+        if (field && (field->empty() || field->rows != gy_ || field->cols != gx_ || field->channels != 2 || field->elem != 4))
+            throw Error(RC_EINVAL, "Piv::push: field 32FC2 of grid_y x grid_x");
+        if (picture && (picture->empty() || picture->rows != h || picture->cols != w || picture->channels != 3 || picture->elem != 1))
+            throw Error(RC_EINVAL, "Piv::push: picture 8UC3 of the pipeline's size");
+        const size_t px = (size_t)w * h, frow = (size_t)gx_ * 8;
+        if (!d_gray_) hip_check(hipMalloc(&d_gray_, px), "hipMalloc frame");
+        if (field && !d_field_) hip_check(hipMalloc(&d_field_, frow * gy_), "hipMalloc field");
+        if (picture && !d_vis_) hip_check(hipMalloc(&d_vis_, px * 3), "hipMalloc picture");
+        if (compute && !d_summary_) hip_check(hipMalloc(&d_summary_, 64), "hipMalloc summary");
+        check(rcflow_sync(pipe_.context(), 0));                  // the last push may still be reading the staging frame
+        hip_check(hipMemcpy2D(d_gray_, (size_t)w, gray.data, gray.step, (size_t)w, h, hipMemcpyHostToDevice), "upload frame");
+        check(rcflow_piv_push_dev(pipe_.context(), 0, (const uint8_t*)d_gray_, (size_t)w, nullptr, field ? (float*)d_field_ : nullptr, frow,
+                                  picture ? (uint8_t*)d_vis_ : nullptr, (size_t)w * 3, compute ? (long long*)d_summary_ : nullptr));
+        if (!field && !picture) return;
+        check(rcflow_sync(pipe_.context(), 0));
+        if (field) hip_check(hipMemcpy2D(field->data, field->step, d_field_, frow, frow, gy_, hipMemcpyDeviceToHost), "download field");
+        if (picture) hip_check(hipMemcpy2D(picture->data, picture->step, d_vis_, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost), "download picture");
+    }
+    // each waits for the pipeline's stream: of the last push that computed (include/rcflow.h).  The summary: pairs summed, cells,
+    // valid, flat, low peak, edge, outliers, pushes; the records, grid_y x grid_x
+    std::vector<long long> read() {
+        std::vector<long long> s(8);
+        check(rcflow_piv_read(pipe_.context(), 0, nullptr, s.data()));
+        return s;
+    }
+    std::vector<rc_piv_cell> cells() {
+        std::vector<rc_piv_cell> c((size_t)gx_ * gy_);
+        check(rcflow_piv_read(pipe_.context(), 0, c.data(), nullptr));
+        return c;
+    }
+    // waits: the accumulators, grid_y x grid_x x D x D x (Tab, Tb, Tbb); the cells' own, grid_y x grid_x x (Ta, Taa)
+    std::vector<long long> sums() {
+        std::vector<long long> s((size_t)gx_ * gy_ * disp_ * 3);
+        check(rcflow_piv_sums_read(pipe_.context(), 0, s.data(), nullptr));
+        return s;
+    }
+    std::vector<long long> cell_sums() {
+        std::vector<long long> s((size_t)gx_ * gy_ * 2);
+        check(rcflow_piv_sums_read(pipe_.context(), 0, nullptr, s.data()));
+        return s;
+    }
+    void set(double min_peak, double median_eps, double median_thr, double vis_max) {
+        check(rcflow_piv_set(pipe_.context(), 0, min_peak, median_eps, median_thr, vis_max));
+    }
+    rc_piv_info info() { rc_piv_info i; check(rcflow_piv_info(pipe_.context(), 0, &i)); return i; }
+    void reset() { check(rcflow_piv_reset(pipe_.context(), 0)); }
+
+  private:
+    Pipeline& pipe_;
+    int gx_ = 0, gy_ = 0;
+    size_t disp_ = 0;
+    void *d_gray_ = nullptr, *d_field_ = nullptr, *d_vis_ = nullptr, *d_summary_ = nullptr;
+};
+
 }  // namespace rc

@@ -52,6 +52,10 @@ RC_PLANVIEW_LAUNCHES = 1
 # rcflow_waves_*: the record's flags, the bounds, the launches of a push that computes everything
 RC_WAVES_EMPTY, RC_WAVES_NOWAVE, RC_WAVES_DEEP = 1, 2, 4
 RC_WAVES_MAX_WINDOW, RC_WAVES_MAX_BINS, RC_WAVES_MAX_SPACING, RC_WAVES_MAX_STATE_BYTES, RC_WAVES_LAUNCHES = 4096, 16, 16, 4 << 30, 3
+# rcflow_piv_*: the record's flags, the parameter flag, the bounds, the launches of a push that computes
+RC_PIV_EMPTY, RC_PIV_FLAT, RC_PIV_EDGE, RC_PIV_LOWPEAK, RC_PIV_OUTLIER = 1, 2, 4, 8, 16
+RC_PIV_REPLACE = 1
+RC_PIV_MAX_WINDOW, RC_PIV_MAX_RANGE, RC_PIV_MAX_ENSEMBLE, RC_PIV_MAX_PIXEL_PAIRS, RC_PIV_MAX_STATE_BYTES, RC_PIV_LAUNCHES = 64, 16, 256, 1 << 18, 4 << 30, 3
 
 ERRORS = {-1: "RC_EINVAL", -2: "RC_ENOMEM", -3: "RC_EHIP", -4: "RC_ENODEV", -5: "RC_ESIZE",
           -6: "RC_ESTATE", -7: "RC_ECOMM"}
@@ -193,6 +197,18 @@ class WavesInfo(C.Structure):
     """rc_waves_info (include/rcflow.h)."""
     _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", WavesParams), ("launches_per_push", C.c_int), ("bins", C.c_int), ("shift", C.c_int),
                 ("held", C.c_int), ("pushes", C.c_longlong), ("device_bytes", C.c_size_t)]
+
+
+class PivParams(C.Structure):
+    """rc_piv_params (include/rcflow.h)."""
+    _fields_ = [("window", C.c_int), ("range", C.c_int), ("step", C.c_int), ("ensemble", C.c_int), ("flags", C.c_int),
+                ("min_peak", C.c_double), ("median_eps", C.c_double), ("median_thr", C.c_double), ("vis_max", C.c_double)]
+
+
+class PivInfo(C.Structure):
+    """rc_piv_info (include/rcflow.h)."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", PivParams), ("grid_x", C.c_int), ("grid_y", C.c_int), ("launches_per_push", C.c_int),
+                ("pairs", C.c_int), ("pushes", C.c_longlong), ("device_bytes", C.c_size_t)]
 
 
 class FitParams(C.Structure):
@@ -374,6 +390,14 @@ SIGNATURES = {
     "rcflow_waves_reset": [_vp, _i],
     "rcflow_waves_close": [_vp, _i],
     "rcflow_waves_info": [_vp, _i, C.POINTER(WavesInfo)],
+    "rcflow_piv_open": [_vp, _i, _i, _i, C.POINTER(PivParams)],
+    "rcflow_piv_push_dev": [_vp, _i, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp],
+    "rcflow_piv_read": [_vp, _i, _vp, C.POINTER(C.c_longlong)],
+    "rcflow_piv_sums_read": [_vp, _i, _vp, _vp],
+    "rcflow_piv_set": [_vp, _i, C.c_double, C.c_double, C.c_double, C.c_double],
+    "rcflow_piv_reset": [_vp, _i],
+    "rcflow_piv_close": [_vp, _i],
+    "rcflow_piv_info": [_vp, _i, C.POINTER(PivInfo)],
     "rcflow_comm_unique_id": [_vp],
     "rcflow_comm_init": [_vp, _vp, _i, _i],
     "rcflow_comm_destroy": [_vp],

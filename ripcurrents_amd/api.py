@@ -37,8 +37,9 @@ from ._lib import RC_MOTION_AUTO_TIME, RC_MOTION_FRESH, MotionInfo, MotionParams
 from ._lib import FTLE_DIRECTIONS, FtleInfo, FtleParams
 from ._lib import PlanViewInfo, PlanViewParams
 from ._lib import WavesInfo, WavesParams
+from ._lib import RC_PIV_REPLACE, PivInfo, PivParams
 
-__all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState", "Waves"]
+__all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState", "Waves", "Piv"]
 
 
 # rc_draw_prim as a numpy record (32 bytes): what Context.draw takes and Context.tracers_prims returns
@@ -58,6 +59,10 @@ WAVES_SUMMARY = ("held", "participating", "nonempty", "with_depth", "pushes", "r
 # rc_wave_cell as a numpy record (32 bytes): what Context.waves_read returns
 WAVE_CELL_DTYPE = np.dtype([("bin", "<i4"), ("flags", "<i4"), ("freq_hz", "<f4"), ("kx", "<f4"), ("ky", "<f4"), ("celerity", "<f4"),
                             ("depth", "<f4"), ("quality", "<f4")])
+PIV_SUMMARY = ("pairs", "cells", "valid", "flat", "lowpeak", "edge", "outliers", "pushes")
+# rc_piv_cell as a numpy record (32 bytes): what Context.piv_read returns
+PIV_CELL_DTYPE = np.dtype([("dx", "<f4"), ("dy", "<f4"), ("peak", "<f4"), ("resid", "<f4"), ("ix", "<i4"), ("iy", "<i4"), ("flags", "<i4"),
+                           ("pairs", "<i4")])
 REGIONS_SUMMARY = ("components", "kept", "records", "foreground", "kept_pixels", "bad_pixels", "pushes", "largest_area")
 # rc_track as a numpy record (128 bytes): what Context.tracks_read returns
 TRACK_DTYPE = np.dtype([("id", "<i8"), ("parent", "<i8"), ("first_push", "<i8"), ("area_sum", "<i8"), ("fx_sum", "<i8"), ("fy_sum", "<i8"),
@@ -1586,6 +1591,76 @@ class Context:
         self._bind(stream)          # waits for the pushes queued on that stream before freeing
         check(self._lib.rcflow_waves_close(self._h, stream))
 
+    # ------------------------------------------------------------------ ensemble PIV
+    def piv_open(self, w, h, window=32, range=8, step=16, ensemble=1, replace=False, min_peak=0.25, median_eps=0.1, median_thr=2.0,
+                 vis_max=4.0, stream=0):
+        """Opens the slot's ensemble PIV for w x h grey frames (include/rcflow.h, "ensemble PIV"): interrogation windows of
+        `window` pixels every `step` pixels, searched over +-`range` pixels, the correlation sums added over the last `ensemble`
+        frame pairs before the peak is taken.  The state takes (24 + 12 * ensemble) * (2 * range + 1)^2 bytes per cell of device
+        memory, without the ring term for an ensemble of 1."""
+        p = PivParams(window=int(window), range=int(range), step=int(step), ensemble=int(ensemble), flags=RC_PIV_REPLACE if replace else 0,
+                      min_peak=float(min_peak), median_eps=float(median_eps), median_thr=float(median_thr), vis_max=float(vis_max))
+        self._bind(stream)          # the state is zeroed on the slot's stream: the one the pushes will run on
+        check(self._lib.rcflow_piv_open(self._h, stream, int(w), int(h), C.byref(p)))
+
+    def piv_info(self, stream=0):
+        """dict(w, h, the parameters, replace, grid_x, grid_y, launches_per_push, pairs, pushes, device_bytes); never blocks."""
+        i = PivInfo()
+        check(self._lib.rcflow_piv_info(self._h, stream, C.byref(i)))
+        out = {k: getattr(i.prm, k) for k, _ in PivParams._fields_ if k != "flags"}
+        out.update(replace=bool(i.prm.flags & RC_PIV_REPLACE), w=i.w, h=i.h, grid_x=i.grid_x, grid_y=i.grid_y,
+                   launches_per_push=i.launches_per_push, pairs=i.pairs, pushes=i.pushes, device_bytes=i.device_bytes)
+        return out
+
+    def piv_push(self, gray, cells=None, field=None, vis=None, summary=None, stream=0):
+        """One grey frame (HxW uint8 device tensor, rows may be padded), correlated against the slot's previous one; nothing is
+        synchronised.  Outputs are preallocated device tensors, each optional: cells GYxGXx32 uint8 (rc_piv_cell records; view
+        the host copy as PIV_CELL_DTYPE), field GYxGXx2 float32 (pixels per frame: the small flow field ripmap_push and the
+        others take), vis HxWx3 uint8, summary 8 int64 (PIV_SUMMARY).  Without any output the push is one launch; with any it
+        is RC_PIV_LAUNCHES.  Records and summary also stay on the slot for piv_read."""
+        info = self.piv_info(stream)
+        h, w, gx, gy = info["h"], info["w"], info["grid_x"], info["grid_y"]
+        if not _is_t(gray) or not gray.is_cuda or gray.dtype != torch.uint8 or tuple(gray.shape) != (h, w) or gray.stride(1) != 1:
+            raise ValueError("gray must be a %dx%d uint8 device tensor with dense pixels, as opened" % (h, w))
+        cp = self._out_array(cells, torch.uint8, "cells", gy * gx * 32)
+        fp = self._out_image(field, torch.float32, "field", (gy, gx, 2))
+        vp = self._out_image(vis, torch.uint8, "vis", (h, w, 3))
+        up = self._out_array(summary, torch.int64, "summary", 8)
+        self._bind(stream)
+        check(self._lib.rcflow_piv_push_dev(self._h, stream, self._ptr(gray), gray.stride(0), cp, *fp, *vp, up))
+
+    def piv_read(self, stream=0):
+        """Waits for the slot's stream -> (cells GYxGX PIV_CELL_DTYPE, dict of the summary by PIV_SUMMARY names) of the last
+        push that computed them; zeros before that."""
+        info = self.piv_info(stream)
+        cells = np.zeros((info["grid_y"], info["grid_x"]), PIV_CELL_DTYPE)
+        summ = np.zeros(8, np.int64)
+        self._bind(stream)
+        check(self._lib.rcflow_piv_read(self._h, stream, cells.ctypes.data, summ.ctypes.data_as(C.POINTER(C.c_longlong))))
+        return cells, dict(zip(PIV_SUMMARY, (int(v) for v in summ)))
+
+    def piv_sums(self, stream=0):
+        """Waits for the slot's stream -> (the accumulators GYxGXxDxDx3 int64: Tab, Tb, Tbb per displacement; GYxGXx2 int64: Ta,
+        Taa); for tests."""
+        info = self.piv_info(stream)
+        gx, gy, D = info["grid_x"], info["grid_y"], 2 * info["range"] + 1
+        sums, cell = np.empty((gy, gx, D, D, 3), np.int64), np.empty((gy, gx, 2), np.int64)
+        self._bind(stream)
+        check(self._lib.rcflow_piv_sums_read(self._h, stream, sums.ctypes.data, cell.ctypes.data))
+        return sums, cell
+
+    def piv_set(self, min_peak, median_eps, median_thr, vis_max, stream=0):
+        """min_peak, median_eps, median_thr and vis_max from the next push on."""
+        check(self._lib.rcflow_piv_set(self._h, stream, float(min_peak), float(median_eps), float(median_thr), float(vis_max)))
+
+    def piv_reset(self, stream=0):
+        self._bind(stream)
+        check(self._lib.rcflow_piv_reset(self._h, stream))
+
+    def piv_close(self, stream=0):
+        self._bind(stream)          # waits for the pushes queued on that stream before freeing
+        check(self._lib.rcflow_piv_close(self._h, stream))
+
     # ------------------------------------------------------------------ rip regions
     def regions_open(self, w, h, connectivity=8, min_area=1, max_regions=1024, stream=0):
         """Opens the slot's region labelling for w x h masks: connected components (4 or 8 neighbours) numbered in raster
@@ -1873,6 +1948,42 @@ class Waves:
 
     def close(self):
         self.ctx.waves_close(self.stream)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class Piv:
+    """The ensemble PIV of one slot as an object: Context.piv_* with the context and the slot bound.  Opens on construction,
+    closes on close() or at the end of a with block."""
+
+    def __init__(self, ctx, w, h, stream=0, **params):
+        self.ctx, self.stream = ctx, stream
+        ctx.piv_open(w, h, stream=stream, **params)
+
+    def push(self, gray, **outputs):
+        self.ctx.piv_push(gray, stream=self.stream, **outputs)
+
+    def read(self):
+        return self.ctx.piv_read(self.stream)
+
+    def info(self):
+        return self.ctx.piv_info(self.stream)
+
+    def sums(self):
+        return self.ctx.piv_sums(self.stream)
+
+    def set(self, min_peak, median_eps, median_thr, vis_max):
+        self.ctx.piv_set(min_peak, median_eps, median_thr, vis_max, self.stream)
+
+    def reset(self):
+        self.ctx.piv_reset(self.stream)
+
+    def close(self):
+        self.ctx.piv_close(self.stream)
 
     def __enter__(self):
         return self

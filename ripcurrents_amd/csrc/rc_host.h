@@ -251,6 +251,25 @@ struct RcWaves {
     RcZeroFence zf;
 };
 
+// Ensemble PIV of one stream slot (piv_kernels.hip).  Everything is allocated by rcflow_piv_open and released by
+// rcflow_piv_close / rcflow_destroy.
+struct RcPiv {
+    bool open = false;
+    int w = 0, h = 0;
+    rc_piv_params prm{};            // min_peak, median_eps, median_thr and vis_max: as rcflow_piv_set left them
+    int gx = 0, gy = 0;             // the cell grid
+    int nw = 0;                     // words per cell: 3 D^2 (Tab, Tb, Tbb per displacement) + 2 (Ta, Taa)
+    int pitch = 0;                  // row pitch of the previous frame in pixels (w rounded up to 4)
+    long long pushes = 0;           // since open / reset; pushes - 1 pairs have been correlated
+    RcBuf prev;                     // [h][pitch] bytes: the last pushed frame
+    RcBuf ring;                     // [ensemble][cells][nw] int32: the per-pair sums; not allocated for an ensemble of 1
+    RcBuf acc;                      // [cells][nw] int64: the sums over the last min(pairs, ensemble) pairs
+    RcBuf out;                      // the last computing push: records before validation [cells] | records [cells] | summary 8 int64
+    RcBuf ctl;                      // PvCtl: the ticket and the counters, zero between launches
+    RcBuf jet;                      // COLORMAP_JET LUT (768 B), written once by open
+    RcZeroFence zf;
+};
+
 // warp_kernels.hip: one launch of the affine / perspective warp
 struct RcWarpArgs {
     const uint8_t* src; size_t step;
@@ -330,6 +349,7 @@ struct RcSlot {
     RcFtle ft;
     RcPlanView pv;
     RcWaves wv;
+    RcPiv piv;
     RcPhaseCorr pc;
 };
 
@@ -385,7 +405,8 @@ struct rc_ctx {
 // resamples the flow field onto the ground grid and rescales it, after which it is the field every later product takes, so
 // it is booked with the other operations on the field (flow_postop), under "farneback".  The wave spectra read frames, not the
 // flow, and what they leave (cells, a bin map, a depth picture) is looked at beside the time-exposure images made from the
-// same frames, so they are booked with those, under "overlay".
+// same frames, so they are booked with those, under "overlay".  The ensemble PIV estimates a velocity field from a frame pair
+// as the Farneback kernels do, and its field goes where theirs goes, so it is booked with them, under "farneback".
 #define RC_BUCKET_TABLE(X) \
     X(RC_B_FARNEBACK, "farneback") X(RC_B_POLAR, "polar") X(RC_B_THRESHOLD, "threshold") X(RC_B_OVERLAY, "overlay") \
     X(RC_B_EROSION, "erosion") X(RC_B_CODEC, "codec") X(RC_B_STREAM, "stream")
@@ -423,7 +444,8 @@ struct rc_ctx {
     X(RC_K_MOTION, "motion", RC_B_FARNEBACK) /* @0 update, @1 gradient, picture and cell histograms, @2 sums and records, @3 primitives */ \
     X(RC_K_FTLE, "ftle", RC_B_STREAM) /* @0 ring slot, @1 flow map, @2 tensor, outputs and summary */ \
     X(RC_K_PLANVIEW, "planview", RC_B_FARNEBACK) /* @0 the table (open), @1 the push */ \
-    X(RC_K_WAVES, "waves", RC_B_OVERLAY) /* @0 spectrum, @1 cell sums and closing, @2 bin map and picture */
+    X(RC_K_WAVES, "waves", RC_B_OVERLAY) /* @0 spectrum, @1 cell sums and closing, @2 bin map and picture */ \
+    X(RC_K_PIV, "piv", RC_B_FARNEBACK) /* @0 the pair's sums, ring and accumulators, @1 score, peak and records, @2 validation, field, picture, summary */
 #define RC_ROW_ID(id, ...) id,
 enum { RC_BUCKET_TABLE(RC_ROW_ID) RC_B_BUCKETS };
 enum { RC_KIND_TABLE(RC_ROW_ID) RC_K_KINDS };
@@ -504,7 +526,7 @@ struct RcProfScope {
     } while (0)
 
 // ---------------------------------------------------------------------------- per-slot products
-// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView and RcWaves share one lifecycle.  A product supplies
+// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView, RcWaves and RcPiv share one lifecycle.  A product supplies
 //   void rc_state_free(T&)             frees every buffer and the fence; the state is T() again
 //   int rc_state_zero(RcSlot&, T&)     rc_fence_zero of what open / reset clear, and the counters
 // and open / reset / close are written once, here.
@@ -518,6 +540,7 @@ void rc_state_free(RcMotion& m);
 void rc_state_free(RcFtle& f);
 void rc_state_free(RcPlanView& v);
 void rc_state_free(RcWaves& v);
+void rc_state_free(RcPiv& v);
 int rc_state_zero(RcSlot& s, RcTimex& t);
 int rc_state_zero(RcSlot& s, RcFrameStab& f);
 int rc_state_zero(RcSlot& s, RcRipMap& m);
@@ -528,6 +551,7 @@ int rc_state_zero(RcSlot& s, RcMotion& m);
 int rc_state_zero(RcSlot& s, RcFtle& f);
 int rc_state_zero(RcSlot& s, RcPlanView& v);
 int rc_state_zero(RcSlot& s, RcWaves& v);
+int rc_state_zero(RcSlot& s, RcPiv& v);
 
 // The tail of every open.  The caller has validated, selected the device and built `fresh` (rc: what its allocations
 // returned).  The state that is open is touched only once nothing can be refused any more: a refused open leaves it as it
