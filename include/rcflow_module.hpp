@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -61,25 +62,102 @@ struct Mat {
 
 typedef struct { float x, y; } Pixel2;   // cv::Point_<float> (ripcurrents.hpp:19)
 
+// ---- the staging layer: how every class below checks a host image and moves it to and from the device ----
+
+// a non-empty view of exactly this geometry (elem = bytes per channel)
+inline bool is_image(const Mat& m, int cols, int rows, int channels, int elem) {
+    return !m.empty() && m.cols == cols && m.rows == rows && m.channels == channels && m.elem == elem;
+}
+
+// m's rows between the host view (its own step) and device memory of pitch `pitch`
+inline void copy_in(void* d, size_t pitch, const Mat& m, const char* what) {
+    hip_check(hipMemcpy2D(d, pitch, m.data, m.step, m.row_bytes(), m.rows, hipMemcpyHostToDevice), what);
+}
+inline void copy_out(const Mat& m, const void* d, size_t pitch, const char* what) {
+    hip_check(hipMemcpy2D(m.data, m.step, d, pitch, m.row_bytes(), m.rows, hipMemcpyDeviceToHost), what);
+}
+
+// One device image with dense rows, allocated at first use and freed with its owner.
+class DeviceImage {
+  public:
+    DeviceImage() = default;
+    ~DeviceImage() { if (d_) (void)hipFree(d_); }
+    DeviceImage(const DeviceImage&) = delete;
+    DeviceImage& operator=(const DeviceImage&) = delete;
+
+    // allocates at the first call, which is all that an image only the device writes needs; the geometry of that call
+    // stays, and a later call, upload or download with another is refused before anything is copied
+    void reserve(int cols, int rows, int channels, int elem) {
+        const size_t pitch = (size_t)cols * channels * elem;
+        if (d_) {
+            if (pitch != pitch_ || rows != rows_) throw Error(RC_EINVAL, "DeviceImage: not the geometry the image was allocated with");
+            return;
+        }
+        hip_check(hipMalloc(&d_, pitch * rows), "hipMalloc staging image");
+        pitch_ = pitch; rows_ = rows;
+    }
+    void upload(const Mat& m) { reserve(m.cols, m.rows, m.channels, m.elem); copy_in(d_, pitch_, m, "upload image"); }
+    void download(Mat& m) { reserve(m.cols, m.rows, m.channels, m.elem); copy_out(m, d_, pitch_, "download image"); }
+    // wanted = false: null, for an optional argument of the library that this call does not ask for
+    template <class T> T* ptr(bool wanted = true) const { return wanted ? (T*)d_ : nullptr; }
+    size_t pitch() const { return pitch_; }
+
+  private:
+    void* d_ = nullptr;
+    size_t pitch_ = 0;
+    int rows_ = 0;
+};
+
+struct StageIn { DeviceImage& dev; const Mat* host; };    // host null: not given
+struct StageOut { DeviceImage& dev; Mat* host; };         // host null: not asked for
+
+// The one order of a call that takes host images, after the caller has validated every argument: the staging images
+// of what was given and asked for are allocated, the stream is drained once before they are overwritten (the library
+// call of the last push may still be reading them), the inputs go up, `call` (the library's, returning its code) runs,
+// and only when a host output was asked for the stream is drained once more and the outputs come down.  A call without
+// host outputs returns with its work in flight; one without host inputs overwrites nothing and does not drain first.
+// Returns call's code.
+template <class Call>
+int staged(rc_ctx* ctx, std::initializer_list<StageIn> ins, Call&& call, std::initializer_list<StageOut> outs) {
+    auto given = [](const auto& s) { return s.host != nullptr; };
+    auto reserve = [](const auto& s) { if (s.host) s.dev.reserve(s.host->cols, s.host->rows, s.host->channels, s.host->elem); };
+    std::for_each(ins.begin(), ins.end(), reserve);
+    std::for_each(outs.begin(), outs.end(), reserve);
+    if (std::any_of(ins.begin(), ins.end(), given)) check(rcflow_sync(ctx, 0));
+    for (const StageIn& i : ins) if (i.host) i.dev.upload(*i.host);
+    const int rc = call();
+    check(rc);
+    if (std::any_of(outs.begin(), outs.end(), given)) check(rcflow_sync(ctx, 0));
+    for (const StageOut& o : outs) if (o.host) o.dev.download(*o.host);
+    return rc;
+}
+
+// The draw path of Regions, Tracks and MotionTemplates: the canvas goes up, `fill` writes `n` primitives on the device,
+// rcflow_draw_dev paints them, the canvas comes down.
+template <class Fill>
+void staged_draw(rc_ctx* ctx, DeviceImage& canvas, DeviceImage& prims, int n, Mat& img, Fill&& fill) {
+    prims.reserve(n, 1, 1, (int)sizeof(rc_draw_prim));
+    staged(ctx, {{canvas, &img}}, [&] {
+        const int rc = fill(prims.ptr<rc_draw_prim>());
+        if (rc < 0) return rc;
+        return rcflow_draw_dev(ctx, 0, canvas.ptr<uint8_t>(), canvas.pitch(), img.cols, img.rows, 3, prims.ptr<const rc_draw_prim>(), n, nullptr);
+    }, {{canvas, &img}});
+}
+
 // One stream slot of one GPU context plus the device copies the module functions work on.
 // The flow field stays resident on the device between calcOpticalFlowFarneback and the
 // analysis calls, like `current` does on the host in ripcurrents.cpp:221-440.
 class Pipeline {
   public:
     Pipeline(int xdim, int ydim, int device = 0) : w_(xdim), h_(ydim) {
-        check(rcflow_create(&ctx_, device, xdim, ydim, 1));
-        try {
-            hip_check(hipMalloc(&d_frames_, (size_t)2 * w_ * h_), "hipMalloc frames");
-            hip_check(hipMalloc(&d_flow_, (size_t)w_ * h_ * 8), "hipMalloc flow");
-            hip_check(hipMalloc(&d_mask_, (size_t)w_ * h_), "hipMalloc mask");
-            flow_src_ = (const float*)d_flow_;
-            check(rcflow_analysis_reset(ctx_, 0, w_, h_));
-        } catch (...) {
-            release();
-            throw;
-        }
+        check(rcflow_create(&ctx_.p, device, xdim, ydim, 1));
+        d_frames_.reserve(w_, 2 * h_, 1, 1);                     // prev above next
+        d_flow_.reserve(w_, h_, 2, 4);
+        d_mask_.reserve(w_, h_, 1, 1);
+        flow_src_ = d_flow_.ptr<float>();
+        check(rcflow_analysis_reset(ctx_, 0, w_, h_));
     }
-    ~Pipeline() { release(); }
+    ~Pipeline() { if (d_scratch_) (void)hipFree(d_scratch_); }
     Pipeline(const Pipeline&) = delete;
     Pipeline& operator=(const Pipeline&) = delete;
 
@@ -99,19 +177,10 @@ class Pipeline {
     // analysis calls below queue behind them on the same stream; only a non-null `flow` waits and downloads.
     bool pushFrame(const Mat& frame, Mat& flow, double pyr_scale, int levels, int winsize, int iterations, int poly_n,
                    double poly_sigma, int flags) {
-        if (frame.empty() || frame.channels != 1 || frame.elem != 1 || frame.cols != w_ || frame.rows != h_)
-            throw Error(RC_EINVAL, "pushFrame: frame must be 8UC1 of the pipeline's size");
-        if (flow.data && (flow.rows != h_ || flow.cols != w_ || flow.channels != 2 || flow.elem != 4))
-            throw Error(RC_EINVAL, "flow must be CV_32FC2 of the frame size");
+        if (!is_image(frame, w_, h_, 1, 1)) throw Error(RC_EINVAL, "pushFrame: frame must be 8UC1 of the pipeline's size");
+        const bool read = wanted(flow);
         rc_farneback_params p = {pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
-        const int rc = rcflow_push_frame_u8(ctx_, 0, (const uint8_t*)frame.data, frame.step, w_, h_, &p);
-        check(rc);
-        if (rc == 1) return false;
-        float* d = nullptr;
-        check(rcflow_stream_flow_ptr(ctx_, 0, &d, nullptr, nullptr));
-        flow_src_ = d;                                  // the analysis calls read the stream's resident field
-        if (flow.data) check(rcflow_stream_flow_read(ctx_, 0, (float*)flow.data, flow.step));
-        return true;
+        return pushed(rcflow_push_frame_u8(ctx_, 0, (const uint8_t*)frame.data, frame.step, w_, h_, &p), read ? &flow : nullptr);
     }
 
     // The same loop without the staging copy: frameBuffer() is the slot's next page-locked staging buffer as an 8UC1
@@ -125,17 +194,9 @@ class Pipeline {
     }
     bool pushAcquired(Mat& flow, double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma,
                       int flags) {
-        if (flow.data && (flow.rows != h_ || flow.cols != w_ || flow.channels != 2 || flow.elem != 4))
-            throw Error(RC_EINVAL, "flow must be CV_32FC2 of the frame size");
+        const bool read = wanted(flow);
         rc_farneback_params p = {pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
-        const int rc = rcflow_push_frame_acquired(ctx_, 0, &p);
-        check(rc);
-        if (rc == 1) return false;
-        float* d = nullptr;
-        check(rcflow_stream_flow_ptr(ctx_, 0, &d, nullptr, nullptr));
-        flow_src_ = d;
-        if (flow.data) check(rcflow_stream_flow_read(ctx_, 0, (float*)flow.data, flow.step));
-        return true;
+        return pushed(rcflow_push_frame_acquired(ctx_, 0, &p), read ? &flow : nullptr);
     }
 
     // One whole iteration of the frame loop (ripcurrents.cpp:194-479) behind one call: the frame produced into
@@ -146,49 +207,35 @@ class Pipeline {
     bool loopStep(double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags,
                   float dt = 2.f, int streamline_iterations = 1, float* d_seeds = nullptr, int nseeds = 0, float seed_upper = 100.f,
                   float MID = 0.5f, float LOWER = 0.2f, bool use_graph = false) {
-        if (!d_edges_) hip_check(hipMalloc(&d_edges_, (size_t)w_ * h_), "hipMalloc edges");
+        d_edges_.reserve(w_, h_, 1, 1);
         rc_farneback_params p = {pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
         rc_frame_loop L;
         std::memset(&L, 0, sizeof(L));
         L.dt = dt; L.iterations = streamline_iterations;
         L.d_seeds = d_seeds; L.nseeds = nseeds; L.seed_variant = 3; L.seed_dt = dt; L.seed_iterations = streamline_iterations; L.seed_upper = seed_upper;
         L.MID = MID; L.LOWER = LOWER;
-        L.d_outmask = (uint8_t*)d_mask_; L.mask_step = (size_t)w_; L.d_edges = (uint8_t*)d_edges_; L.edges_step = (size_t)w_;
+        L.d_outmask = d_mask_.ptr<uint8_t>(); L.mask_step = d_mask_.pitch(); L.d_edges = d_edges_.ptr<uint8_t>(); L.edges_step = d_edges_.pitch();
         L.use_graph = use_graph ? 1 : 0;
-        const int rc = rcflow_frame_loop_step(ctx_, 0, &p, &L);
-        check(rc);
-        if (rc == 1) return false;
-        float* d = nullptr;
-        check(rcflow_stream_flow_ptr(ctx_, 0, &d, nullptr, nullptr));
-        flow_src_ = d;
-        return true;
+        return pushed(rcflow_frame_loop_step(ctx_, 0, &p, &L), nullptr);
     }
-    const uint8_t* outmaskDevice() const { return (const uint8_t*)d_mask_; }
-    const uint8_t* edgesDevice() const { return (const uint8_t*)d_edges_; }
+    const uint8_t* outmaskDevice() const { return d_mask_.ptr<const uint8_t>(); }
+    const uint8_t* edgesDevice() const { return d_edges_.ptr<const uint8_t>(); }
 
     void calcOpticalFlowFarneback(const Mat& prev, const Mat& next, Mat& flow, double pyr_scale, int levels,
                                   int winsize, int iterations, int poly_n, double poly_sigma, int flags) {
-        if (prev.empty() || next.empty() || prev.rows != next.rows || prev.cols != next.cols ||
-            prev.channels != 1 || prev.elem != 1 || prev.cols != w_ || prev.rows != h_)
-            throw Error(RC_EINVAL, "calcOpticalFlowFarneback: prev/next must be 8UC1 of the pipeline's size");
-        uint8_t* df = (uint8_t*)d_frames_;
-        hip_check(hipMemcpy2D(df, w_, prev.data, prev.step, w_, h_, hipMemcpyHostToDevice), "upload prev");
-        hip_check(hipMemcpy2D(df + (size_t)w_ * h_, w_, next.data, next.step, w_, h_, hipMemcpyHostToDevice), "upload next");
-        if (flags & RC_FARNEBACK_USE_INITIAL_FLOW) {
-            // OPTFLOW_USE_INITIAL_FLOW: `flow` is in/out -- its content starts the coarsest scale (include/rcflow.h)
-            if (!flow.data || flow.rows != h_ || flow.cols != w_ || flow.channels != 2 || flow.elem != 4)
-                throw Error(RC_EINVAL, "OPTFLOW_USE_INITIAL_FLOW: flow must hold a CV_32FC2 field of the frame size");
-            hip_check(hipMemcpy2D(d_flow_, (size_t)w_ * 8, flow.data, flow.step, (size_t)w_ * 8, h_, hipMemcpyHostToDevice), "upload initial flow");
-        }
+        require_pair(prev, next, "calcOpticalFlowFarneback");
+        const bool initial = (flags & RC_FARNEBACK_USE_INITIAL_FLOW) != 0;
+        // OPTFLOW_USE_INITIAL_FLOW: `flow` is in/out -- its content starts the coarsest scale (include/rcflow.h)
+        if (initial && !is_image(flow, w_, h_, 2, 4))
+            throw Error(RC_EINVAL, "OPTFLOW_USE_INITIAL_FLOW: flow must hold a CV_32FC2 field of the frame size");
+        const bool read = wanted(flow);
+        uint8_t* df = upload_pair(prev, next);
+        if (initial) d_flow_.upload(flow);
         rc_farneback_params p = {pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
-        check(rcflow_farneback_dev(ctx_, 0, df, w_, df + (size_t)w_ * h_, w_, w_, h_, (float*)d_flow_, (size_t)w_ * 8, &p));
-        flow_src_ = (float*)d_flow_;
+        check(rcflow_farneback_dev(ctx_, 0, df, w_, df + (size_t)w_ * h_, w_, w_, h_, d_flow_.ptr<float>(), d_flow_.pitch(), &p));
+        flow_src_ = d_flow_.ptr<float>();
         check(rcflow_sync(ctx_, 0));
-        if (flow.data) {
-            if (flow.rows != h_ || flow.cols != w_ || flow.channels != 2 || flow.elem != 4)
-                throw Error(RC_EINVAL, "flow must be CV_32FC2 of the frame size");
-            hip_check(hipMemcpy2D(flow.data, flow.step, d_flow_, (size_t)w_ * 8, (size_t)w_ * 8, h_, hipMemcpyDeviceToHost), "download flow");
-        }
+        if (read) d_flow_.download(flow);
     }
 
     // cv::calcOpticalFlowPyrLK(prevImg, nextImg, prevPts, nextPts, status, err, winSize, maxLevel,
@@ -198,17 +245,13 @@ class Pipeline {
                               std::vector<Pixel2>& nextPts, std::vector<unsigned char>& status, std::vector<float>& err,
                               int win_w = 21, int win_h = 21, int maxLevel = 3, int crit_type = 3, int maxCount = 30,
                               double epsilon = 0.01, int flags = 0, double minEigThreshold = 1e-4) {
-        if (prev.empty() || next.empty() || prev.rows != next.rows || prev.cols != next.cols ||
-            prev.channels != 1 || prev.elem != 1 || prev.cols != w_ || prev.rows != h_)
-            throw Error(RC_EINVAL, "calcOpticalFlowPyrLK: prev/next must be 8UC1 of the pipeline's size");
+        require_pair(prev, next, "calcOpticalFlowPyrLK");
         const int n = (int)prevPts.size();
         const bool initial = (flags & 4) != 0;
         if (initial && (int)nextPts.size() != n) throw Error(RC_EINVAL, "OPTFLOW_USE_INITIAL_FLOW needs nextPts of prevPts' size");
         nextPts.resize(n); status.assign(n, 0); err.assign(n, 0.f);
         if (n == 0) return;
-        uint8_t* df = (uint8_t*)d_frames_;
-        hip_check(hipMemcpy2D(df, w_, prev.data, prev.step, w_, h_, hipMemcpyHostToDevice), "upload prev");
-        hip_check(hipMemcpy2D(df + (size_t)w_ * h_, w_, next.data, next.step, w_, h_, hipMemcpyHostToDevice), "upload next");
+        uint8_t* df = upload_pair(prev, next);
         // prevPts | nextPts | err | status in the pipeline's grow-only scratch buffer (no allocation in the frame loop)
         const size_t off_n = (size_t)n * 8, off_e = 2 * off_n, off_s = off_e + (size_t)n * 4;
         char* b = (char*)scratch(off_s + n);
@@ -230,10 +273,9 @@ class Pipeline {
 
     // Replace the resident flow field (e.g. after host-side edits of `current`).
     void upload_flow(const Mat& current) {
-        if (current.rows != h_ || current.cols != w_ || current.channels != 2 || current.elem != 4)
-            throw Error(RC_EINVAL, "current must be CV_32FC2 of the frame size");
-        hip_check(hipMemcpy2D(d_flow_, (size_t)w_ * 8, current.data, current.step, (size_t)w_ * 8, h_, hipMemcpyHostToDevice), "upload flow");
-        flow_src_ = (float*)d_flow_;
+        if (!is_image(current, w_, h_, 2, 4)) throw Error(RC_EINVAL, "current must be CV_32FC2 of the frame size");
+        d_flow_.upload(current);
+        flow_src_ = d_flow_.ptr<float>();
     }
 
     // create_histogram(current, hist, histsum, hist2d, histsum2d, UPPER, UPPER2d, prop_above_upper)
@@ -253,10 +295,11 @@ class Pipeline {
     // receives the wave mask.  UPPER / UPPER2d are the slot's (from create_histogram).
     void create_flow_and_accumulationbuffer(Mat& outmask, int framecount, float MID = 0.5f, float LOWER = 0.2f) {
         check(rcflow_classify_accumulate_dev(ctx_, 0, flow_src_, (size_t)w_ * 8, w_, h_, framecount, MID,
-                                             LOWER, nullptr, 0, nullptr, 0, nullptr, 0, (uint8_t*)d_mask_, w_));
+                                             LOWER, nullptr, 0, nullptr, 0, nullptr, 0, d_mask_.ptr<uint8_t>(), d_mask_.pitch()));
         check(rcflow_sync(ctx_, 0));
-        if (outmask.data)
-            hip_check(hipMemcpy2D(outmask.data, outmask.step, d_mask_, w_, w_, h_, hipMemcpyDeviceToHost), "download mask");
+        // deliberately as it always was: only outmask's data and step are read, its own geometry is not asked, and the
+        // pipeline's rows are written -- the one host image here that does not pass is_image
+        if (outmask.data) copy_out(Mat(h_, w_, 1, 1, outmask.data, outmask.step), d_mask_.ptr<void>(), d_mask_.pitch(), "download mask");
     }
     void accumulator(float* acc_x) { check(rcflow_accumulator_read(ctx_, 0, acc_x)); }
 
@@ -309,26 +352,22 @@ class Pipeline {
     void timexPush(const Mat& frame, Mat& mean, Mat& average, Mat& bright, Mat& dark) {
         Mat* outs[4] = {&mean, &average, &bright, &dark};
         const size_t img = ((size_t)w_ * h_ * 3 + 255) & ~(size_t)255;
-        auto is_8uc3 = [this](const Mat& m) { return m.rows == h_ && m.cols == w_ && m.channels == 3 && m.elem == 1; };
-        if (frame.empty() || !is_8uc3(frame)) throw Error(RC_EINVAL, "timexPush: frame must be 8UC3 of the pipeline's size");
+        if (!is_image(frame, w_, h_, 3, 1)) throw Error(RC_EINVAL, "timexPush: frame must be 8UC3 of the pipeline's size");
         for (Mat* m : outs)
-            if (!m->empty() && !is_8uc3(*m)) throw Error(RC_EINVAL, "timexPush: images must be 8UC3 of the frame size");
+            if (!m->empty() && !is_image(*m, w_, h_, 3, 1)) throw Error(RC_EINVAL, "timexPush: images must be 8UC3 of the frame size");
         uint8_t* b = (uint8_t*)scratch(5 * img);                 // grow-only: the frame and the four images
-        hip_check(hipMemcpy2D(b, (size_t)w_ * 3, frame.data, frame.step, (size_t)w_ * 3, h_, hipMemcpyHostToDevice), "upload frame");
+        const size_t pitch = frame.row_bytes();
+        copy_in(b, pitch, frame, "upload frame");
         uint8_t* d_out[4];
         size_t out_step[4];
         for (int k = 0; k < 4; k++) {
             d_out[k] = outs[k]->empty() ? nullptr : b + (k + 1) * img;
-            out_step[k] = (size_t)w_ * 3;
+            out_step[k] = pitch;
         }
-        int rc = rcflow_timex_push_dev(ctx_, 0, b, (size_t)w_ * 3, d_out, out_step);
-        if (rc == RC_OK) rc = rcflow_sync(ctx_, 0);
-        hipError_t e = hipSuccess;
-        for (int k = 0; k < 4 && rc == RC_OK && e == hipSuccess; k++)
-            if (d_out[k])
-                e = hipMemcpy2D(outs[k]->data, outs[k]->step, d_out[k], (size_t)w_ * 3, (size_t)w_ * 3, h_, hipMemcpyDeviceToHost);
-        check(rc);
-        hip_check(e, "download time-exposure image");
+        check(rcflow_timex_push_dev(ctx_, 0, b, pitch, d_out, out_step));
+        check(rcflow_sync(ctx_, 0));
+        for (int k = 0; k < 4; k++)
+            if (d_out[k]) copy_out(*outs[k], d_out[k], pitch, "download time-exposure image");
     }
     void timexReset() { check(rcflow_timex_reset(ctx_, 0)); }
     void timexClose() { check(rcflow_timex_close(ctx_, 0)); }
@@ -341,16 +380,15 @@ class Pipeline {
     void framestabOpen(int roi_x, int roi_y, int roi_w, int roi_h) { check(rcflow_framestab_open(ctx_, 0, w_, h_, roi_x, roi_y, roi_w, roi_h)); }
     void framestabPush(const Mat& frame, Mat& corrected, double shift[3] = nullptr) {
         const size_t img = ((size_t)w_ * h_ * 3 + 255) & ~(size_t)255;
-        auto is_8uc3 = [this](const Mat& m) { return !m.empty() && m.rows == h_ && m.cols == w_ && m.channels == 3 && m.elem == 1; };
-        if (!is_8uc3(frame) || !is_8uc3(corrected)) throw Error(RC_EINVAL, "framestabPush: frame and corrected must be 8UC3 of the pipeline's size");
+        if (!is_image(frame, w_, h_, 3, 1) || !is_image(corrected, w_, h_, 3, 1))
+            throw Error(RC_EINVAL, "framestabPush: frame and corrected must be 8UC3 of the pipeline's size");
         uint8_t* b = (uint8_t*)scratch(2 * img);                 // grow-only: the frame and the corrected frame
-        hip_check(hipMemcpy2D(b, (size_t)w_ * 3, frame.data, frame.step, (size_t)w_ * 3, h_, hipMemcpyHostToDevice), "upload frame");
-        int rc = rcflow_framestab_push_dev(ctx_, 0, b, (size_t)w_ * 3, b + img, (size_t)w_ * 3, nullptr);
+        const size_t pitch = frame.row_bytes();
+        copy_in(b, pitch, frame, "upload frame");
+        check(rcflow_framestab_push_dev(ctx_, 0, b, pitch, b + img, pitch, nullptr));
         double r[3] = {0., 0., 0.};
-        if (rc == RC_OK) rc = rcflow_framestab_read(ctx_, 0, r, nullptr);      // waits for the push
-        check(rc);
-        hip_check(hipMemcpy2D(corrected.data, corrected.step, b + img, (size_t)w_ * 3, (size_t)w_ * 3, h_, hipMemcpyDeviceToHost),
-                  "download corrected frame");
+        check(rcflow_framestab_read(ctx_, 0, r, nullptr));       // waits for the push
+        copy_out(corrected, b + img, pitch, "download corrected frame");
         if (shift) { shift[0] = r[0]; shift[1] = r[1]; shift[2] = r[2]; }
     }
     // Several static patches (n x (x, y, w, h), one size) and a fitted motion: model RC_STAB_TRANSLATION / _SIMILARITY /
@@ -374,17 +412,16 @@ class Pipeline {
 
   private:
     void warp(const Mat& src, Mat& dst, const double* M, int flags, bool perspective) {
-        auto is_8uc3 = [](const Mat& m) { return !m.empty() && m.channels == 3 && m.elem == 1; };
-        if (!is_8uc3(src) || !is_8uc3(dst)) throw Error(RC_EINVAL, "warp: src and dst must be 8UC3");
-        const size_t sb = ((size_t)src.cols * src.rows * 3 + 255) & ~(size_t)255, db = (size_t)dst.cols * dst.rows * 3;
+        // 8UC3 of any size: each view's own
+        if (!is_image(src, src.cols, src.rows, 3, 1) || !is_image(dst, dst.cols, dst.rows, 3, 1))
+            throw Error(RC_EINVAL, "warp: src and dst must be 8UC3");
+        const size_t sb = (src.row_bytes() * src.rows + 255) & ~(size_t)255, db = dst.row_bytes() * dst.rows;
         uint8_t* b = (uint8_t*)scratch(sb + db);
-        hip_check(hipMemcpy2D(b, (size_t)src.cols * 3, src.data, src.step, (size_t)src.cols * 3, src.rows, hipMemcpyHostToDevice), "upload image");
-        int rc = (perspective ? rcflow_warp_perspective_bgr_dev : rcflow_warp_affine_bgr_dev)(
-            ctx_, 0, b, (size_t)src.cols * 3, src.cols, src.rows, b + sb, (size_t)dst.cols * 3, dst.cols, dst.rows, M, flags);
-        if (rc == RC_OK) rc = rcflow_sync(ctx_, 0);
-        check(rc);
-        hip_check(hipMemcpy2D(dst.data, dst.step, b + sb, (size_t)dst.cols * 3, (size_t)dst.cols * 3, dst.rows, hipMemcpyDeviceToHost),
-                  "download warped image");
+        copy_in(b, src.row_bytes(), src, "upload image");
+        check((perspective ? rcflow_warp_perspective_bgr_dev : rcflow_warp_affine_bgr_dev)(
+            ctx_, 0, b, src.row_bytes(), src.cols, src.rows, b + sb, dst.row_bytes(), dst.cols, dst.rows, M, flags));
+        check(rcflow_sync(ctx_, 0));
+        copy_out(dst, b + sb, dst.row_bytes(), "download warped image");
     }
     // grow-only device scratch for the per-frame helpers (seeds, traces, display image, LK points)
     void* scratch(size_t bytes) {
@@ -398,34 +435,62 @@ class Pipeline {
         }
         return d_scratch_;
     }
-    void release() {
-        if (d_scratch_) (void)hipFree(d_scratch_);
-        d_scratch_ = nullptr; scratch_bytes_ = 0;
-        if (d_frames_) (void)hipFree(d_frames_);
-        if (d_flow_) (void)hipFree(d_flow_);
-        if (d_mask_) (void)hipFree(d_mask_);
-        if (d_edges_) (void)hipFree(d_edges_);
-        d_frames_ = d_flow_ = d_mask_ = d_edges_ = nullptr;
-        if (ctx_) rcflow_destroy(ctx_);
-        ctx_ = nullptr;
-    }
     void display(int which, Mat& bgr) {
-        if (bgr.rows != h_ || bgr.cols != w_ || bgr.channels != 3 || bgr.elem != 1)
-            throw Error(RC_EINVAL, "streamoverlay_color must be 8UC3 of the frame size");
-        void* d = scratch((size_t)w_ * h_ * 3);
-        int rc = rcflow_streamline_display_dev(ctx_, 0, which, (uint8_t*)d, (size_t)w_ * 3, nullptr);
-        if (rc == RC_OK) rc = rcflow_sync(ctx_, 0);
-        hipError_t e = rc == RC_OK ? hipMemcpy2D(bgr.data, bgr.step, d, (size_t)w_ * 3, (size_t)w_ * 3, h_, hipMemcpyDeviceToHost)
-                                   : hipSuccess;
-        check(rc);
-        hip_check(e, "download display image");
+        if (!is_image(bgr, w_, h_, 3, 1)) throw Error(RC_EINVAL, "streamoverlay_color must be 8UC3 of the frame size");
+        void* d = scratch(bgr.row_bytes() * h_);
+        check(rcflow_streamline_display_dev(ctx_, 0, which, (uint8_t*)d, bgr.row_bytes(), nullptr));
+        check(rcflow_sync(ctx_, 0));
+        copy_out(bgr, d, bgr.row_bytes(), "download display image");
     }
-    rc_ctx* ctx_ = nullptr;
+    // a null `flow` view: the field is not wanted on the host; any other must be CV_32FC2 of the frame size
+    bool wanted(const Mat& flow) const {
+        if (flow.data && !is_image(flow, w_, h_, 2, 4)) throw Error(RC_EINVAL, "flow must be CV_32FC2 of the frame size");
+        return flow.data != nullptr;
+    }
+    // the tail of a frame push: rc 1 primed the stream (no flow yet); otherwise the analysis calls read the stream's
+    // resident field from here on, and `flow` (when given) receives it
+    bool pushed(int rc, Mat* flow) {
+        check(rc);
+        if (rc == 1) return false;
+        float* d = nullptr;
+        check(rcflow_stream_flow_ptr(ctx_, 0, &d, nullptr, nullptr));
+        flow_src_ = d;
+        if (flow) check(rcflow_stream_flow_read(ctx_, 0, (float*)flow->data, flow->step));
+        return true;
+    }
+    // prev above next in d_frames_, for the two-image calls
+    void require_pair(const Mat& prev, const Mat& next, const char* who) const {
+        if (!is_image(prev, w_, h_, 1, 1) || !is_image(next, w_, h_, 1, 1))
+            throw Error(RC_EINVAL, std::string(who) + ": prev/next must be 8UC1 of the pipeline's size");
+    }
+    uint8_t* upload_pair(const Mat& prev, const Mat& next) {
+        uint8_t* df = d_frames_.ptr<uint8_t>();
+        copy_in(df, w_, prev, "upload prev");
+        copy_in(df + (size_t)w_ * h_, w_, next, "upload next");
+        return df;
+    }
+    // declared first, so destroyed last: the buffers below are freed, then the context
+    struct Context {
+        rc_ctx* p = nullptr;
+        ~Context() { if (p) rcflow_destroy(p); }
+        operator rc_ctx*() const { return p; }
+    } ctx_;
     int w_, h_;
-    void *d_frames_ = nullptr, *d_flow_ = nullptr, *d_mask_ = nullptr, *d_edges_ = nullptr, *d_scratch_ = nullptr;
+    DeviceImage d_frames_, d_flow_, d_mask_, d_edges_;
+    void* d_scratch_ = nullptr;
     size_t scratch_bytes_ = 0;
     const float* flow_src_ = nullptr;     // the field the analysis calls read: d_flow_ or the stream's resident field
 };
+
+// The reference's sparse mover: PyrLK with 50x50, maxLevel 3, COUNT+EPS 30 / 0.1, flags 10, 1e-4 (Streakline.cpp:32,
+// ripcurrents_module.cpp:775, :1162).  Returns where `pts` went.
+inline std::vector<Pixel2> track_lk(Pipeline& pipe, const Mat& u_prev, const Mat& u_current, const std::vector<Pixel2>& pts) {
+    std::vector<Pixel2> next;
+    std::vector<unsigned char> status;
+    std::vector<float> err;
+    pipe.calcOpticalFlowPyrLK(u_prev, u_current, pts, next, status, err, 50, 50, 3, 3, 30, 0.1, 10, 1e-4);
+    return next;
+}
 
 // Streakline.hpp:8-20.  run(): runLK's bookkeeping (Streakline.cpp:22-71) with the vertices moved
 // through the dense flow field resident in the pipeline (the main.cpp:961-977 precedent);
@@ -445,29 +510,22 @@ class Streakline {
     void run(Pipeline& pipe, float dt = 1.f) {
         std::vector<Pixel2> next = vertices;
         pipe.streamline(next.data(), (int)next.size(), dt, 1, 0.f, /*variant=*/4);
+        advance(pipe, next);
+    }
+
+    // Streakline::runLK(u_prev, u_current, outImg) as the reference runs it: the vertices are
+    // moved by PyrLK (track_lk).
+    void runLK(Pipeline& pipe, const Mat& u_prev, const Mat& u_current) { advance(pipe, track_lk(pipe, u_prev, u_current, vertices)); }
+
+  private:
+    // runLK's bookkeeping after the move (Streakline.cpp:35-48)
+    void advance(Pipeline& pipe, std::vector<Pixel2> next) {
         for (size_t i = 0; i < next.size(); i++)   // eliminate any large movement (Streakline.cpp:35-40)
             if (std::fabs(vertices[i].x - next[i].x) > pipe.width() * 0.1 ||
                 std::fabs(vertices[i].y - next[i].y) > pipe.height() * 0.1)
                 next[i] = vertices[i];
         vertices = next;
         vertices.insert(vertices.begin(), generationPoint);   // frameCount % 1 == 0 (Streakline.cpp:46-48)
-        numberOfVertices = (int)vertices.size();
-        frameCount++;
-    }
-
-    // Streakline::runLK(u_prev, u_current, outImg) as the reference runs it: the vertices are
-    // moved by PyrLK (50x50, maxLevel 3, COUNT+EPS 30 / 0.1, flags 10, 1e-4; Streakline.cpp:32).
-    void runLK(Pipeline& pipe, const Mat& u_prev, const Mat& u_current) {
-        std::vector<Pixel2> next;
-        std::vector<unsigned char> status;
-        std::vector<float> err;
-        pipe.calcOpticalFlowPyrLK(u_prev, u_current, vertices, next, status, err, 50, 50, 3, 3, 30, 0.1, 10, 1e-4);
-        for (size_t i = 0; i < next.size(); i++)   // eliminate any large movement (Streakline.cpp:35-40)
-            if (std::fabs(vertices[i].x - next[i].x) > pipe.width() * 0.1 ||
-                std::fabs(vertices[i].y - next[i].y) > pipe.height() * 0.1)
-                next[i] = vertices[i];
-        vertices = next;
-        vertices.insert(vertices.begin(), generationPoint);
         numberOfVertices = (int)vertices.size();
         frameCount++;
     }
@@ -483,13 +541,7 @@ class Timeline {
         float diffX = (lineEnd.x - lineStart.x) / numberOfVertices, diffY = (lineEnd.y - lineStart.y) / numberOfVertices;
         for (int i = 0; i <= numberOfVertices; i++) vertices.push_back(Pixel2{lineStart.x + diffX * i, lineStart.y + diffY * i});
     }
-    void runLK(Pipeline& pipe, const Mat& u_prev, const Mat& u_current) {
-        std::vector<Pixel2> next;
-        std::vector<unsigned char> status;
-        std::vector<float> err;
-        pipe.calcOpticalFlowPyrLK(u_prev, u_current, vertices, next, status, err, 50, 50, 3, 3, 30, 0.1, 10, 1e-4);
-        vertices = next;
-    }
+    void runLK(Pipeline& pipe, const Mat& u_prev, const Mat& u_current) { vertices = track_lk(pipe, u_prev, u_current, vertices); }
 };
 
 class PopulationMap {
@@ -505,13 +557,7 @@ class PopulationMap {
             vertices.push_back(Pixel2{randX, randY});
         }
     }
-    void runLK(Pipeline& pipe, const Mat& u_prev, const Mat& u_current) {
-        std::vector<Pixel2> next;
-        std::vector<unsigned char> status;
-        std::vector<float> err;
-        pipe.calcOpticalFlowPyrLK(u_prev, u_current, vertices, next, status, err, 50, 50, 3, 3, 30, 0.1, 10, 1e-4);
-        vertices = next;
-    }
+    void runLK(Pipeline& pipe, const Mat& u_prev, const Mat& u_current) { vertices = track_lk(pipe, u_prev, u_current, vertices); }
 };
 
 // The opposing-flow map (rcflow_ripmap_*): averageVector (ripcurrents.hpp, ripcurrents_module.cpp:386-484) finished.  Works
@@ -533,10 +579,7 @@ class RipMap {
         : pipe_(pipe), gx_(grid_x), gy_(grid_y) {
         check(rcflow_ripmap_open(pipe.context(), 0, pipe.width(), pipe.height(), window, grid_x, grid_y, source, flags));
     }
-    ~RipMap() {
-        (void)rcflow_ripmap_close(pipe_.context(), 0);
-        if (d_field_) (void)hipFree(d_field_);
-    }
+    ~RipMap() { (void)rcflow_ripmap_close(pipe_.context(), 0); }
     RipMap(const RipMap&) = delete;
     RipMap& operator=(const RipMap&) = delete;
 
@@ -547,13 +590,11 @@ class RipMap {
     void push() { check(rcflow_ripmap_push_dev(pipe_.context(), 0, pipe_.device_flow(), (size_t)pipe_.width() * 8, nullptr, 0, nullptr, 0, nullptr, nullptr)); }
     // a host field (CV_32FC2 of the pipeline's size)
     void push(const Mat& flow) {
-        const int w = pipe_.width(), h = pipe_.height();
-        if (flow.empty() || flow.rows != h || flow.cols != w || flow.channels != 2 || flow.elem != 4)
+        if (!is_image(flow, pipe_.width(), pipe_.height(), 2, 4))
             throw Error(RC_EINVAL, "RipMap::push: flow must be CV_32FC2 of the pipeline's size");
-        if (!d_field_) hip_check(hipMalloc(&d_field_, (size_t)w * h * 8), "hipMalloc field");
-        check(rcflow_sync(pipe_.context(), 0));                  // the last push may still be reading the staging field
-        hip_check(hipMemcpy2D(d_field_, (size_t)w * 8, flow.data, flow.step, (size_t)w * 8, h, hipMemcpyHostToDevice), "upload field");
-        check(rcflow_ripmap_push_dev(pipe_.context(), 0, (const float*)d_field_, (size_t)w * 8, nullptr, 0, nullptr, 0, nullptr, nullptr));
+        staged(pipe_.context(), {{d_field_, &flow}}, [&] {
+            return rcflow_ripmap_push_dev(pipe_.context(), 0, d_field_.ptr<const float>(), d_field_.pitch(), nullptr, 0, nullptr, 0, nullptr, nullptr);
+        }, {});
     }
     // waits for the pipeline's stream
     Result read() {
@@ -570,8 +611,7 @@ class RipMap {
     // 8UC1 of the frame size, 255 inside the cells the last push found opposed: what create_edges / create_output take
     void mask(Mat& m) {
         const int w = pipe_.width(), h = pipe_.height();
-        if (m.empty() || m.rows != h || m.cols != w || m.channels != 1 || m.elem != 1)
-            throw Error(RC_EINVAL, "RipMap::mask: the mask must be 8UC1 of the pipeline's size");
+        if (!is_image(m, w, h, 1, 1)) throw Error(RC_EINVAL, "RipMap::mask: the mask must be 8UC1 of the pipeline's size");
         Result r = read();
         for (int y = 0; y < h; y++) {
             unsigned char* row = (unsigned char*)m.data + (size_t)y * m.step;
@@ -584,7 +624,7 @@ class RipMap {
   private:
     Pipeline& pipe_;
     int gx_, gy_;
-    void* d_field_ = nullptr;
+    DeviceImage d_field_;
 };
 
 // Tracer lines on the device (rcflow_tracers_*): compute_streaklines / compute_timelines / compute_populationMap
@@ -599,11 +639,7 @@ class Tracers {
         p.mover = mover; p.max_lines = max_lines; p.max_vertices = max_vertices; p.dt = dt;
         check(rcflow_tracers_open(pipe.context(), 0, pipe.width(), pipe.height(), &p));
     }
-    ~Tracers() {
-        (void)rcflow_tracers_close(pipe_.context(), 0);
-        if (d_gray_) (void)hipFree(d_gray_);
-        if (d_canvas_) (void)hipFree(d_canvas_);
-    }
+    ~Tracers() { (void)rcflow_tracers_close(pipe_.context(), 0); }
     Tracers(const Tracers&) = delete;
     Tracers& operator=(const Tracers&) = delete;
 
@@ -623,13 +659,9 @@ class Tracers {
     // LK mover: the gray frame (8UC1) moves the lines; outImg (8UC3, optional) gets them drawn, as runLK(u_prev, u_current, outImg)
     // does.  Returns false from the priming push (the first frame).
     bool push(const Mat& gray, Mat* outImg = nullptr) {
-        const int w = pipe_.width(), h = pipe_.height();
-        if (gray.empty() || gray.rows != h || gray.cols != w || gray.channels != 1 || gray.elem != 1)
+        if (!is_image(gray, pipe_.width(), pipe_.height(), 1, 1))
             throw Error(RC_EINVAL, "Tracers::push: the frame must be 8UC1 of the pipeline's size");
-        if (!d_gray_) hip_check(hipMalloc(&d_gray_, (size_t)w * h), "hipMalloc gray");
-        check(rcflow_sync(pipe_.context(), 0));
-        hip_check(hipMemcpy2D(d_gray_, (size_t)w, gray.data, gray.step, (size_t)w, h, hipMemcpyHostToDevice), "upload gray");
-        return run((const uint8_t*)d_gray_, outImg);
+        return run(&gray, outImg);
     }
     // FLOW mover: the pipeline's resident flow field
     bool push(Mat* outImg = nullptr) { return run(nullptr, outImg); }
@@ -648,26 +680,16 @@ class Tracers {
 
   private:
     static int checked(int rc) { check(rc); return rc; }
-    bool run(const uint8_t* d_gray, Mat* outImg) {
-        const int w = pipe_.width(), h = pipe_.height();
-        uint8_t* canvas = nullptr;
-        if (outImg) {
-            if (outImg->empty() || outImg->rows != h || outImg->cols != w || outImg->channels != 3 || outImg->elem != 1)
-                throw Error(RC_EINVAL, "Tracers::push: outImg must be 8UC3 of the pipeline's size");
-            if (!d_canvas_) hip_check(hipMalloc(&d_canvas_, (size_t)w * h * 3), "hipMalloc canvas");
-            check(rcflow_sync(pipe_.context(), 0));
-            hip_check(hipMemcpy2D(d_canvas_, (size_t)w * 3, outImg->data, outImg->step, (size_t)w * 3, h, hipMemcpyHostToDevice), "upload canvas");
-            canvas = (uint8_t*)d_canvas_;
-        }
-        const int rc = checked(rcflow_tracers_push_dev(pipe_.context(), 0, d_gray, (size_t)w, nullptr, 0, canvas, (size_t)w * 3));
-        if (outImg) {
-            check(rcflow_sync(pipe_.context(), 0));
-            hip_check(hipMemcpy2D(outImg->data, outImg->step, d_canvas_, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost), "download canvas");
-        }
-        return rc == 0;
+    bool run(const Mat* gray, Mat* outImg) {
+        if (outImg && !is_image(*outImg, pipe_.width(), pipe_.height(), 3, 1))
+            throw Error(RC_EINVAL, "Tracers::push: outImg must be 8UC3 of the pipeline's size");
+        return staged(pipe_.context(), {{d_gray_, gray}, {d_canvas_, outImg}}, [&] {
+            return rcflow_tracers_push_dev(pipe_.context(), 0, d_gray_.ptr<const uint8_t>(gray), d_gray_.pitch(), nullptr, 0,
+                                           d_canvas_.ptr<uint8_t>(outImg), d_canvas_.pitch());
+        }, {{d_canvas_, outImg}}) == 0;
     }
     Pipeline& pipe_;
-    void *d_gray_ = nullptr, *d_canvas_ = nullptr;
+    DeviceImage d_gray_, d_canvas_;
 };
 
 // Rip regions on the device (rcflow_regions_*): the connected components of a mask (outmask of the classification, the
@@ -680,10 +702,7 @@ class Regions {
         p.connectivity = connectivity; p.min_area = min_area; p.max_regions = max_regions;
         check(rcflow_regions_open(pipe.context(), 0, pipe.width(), pipe.height(), &p));
     }
-    ~Regions() {
-        (void)rcflow_regions_close(pipe_.context(), 0);
-        for (void* p : {d_mask_, d_labels_, d_prims_, d_canvas_}) if (p) (void)hipFree(p);
-    }
+    ~Regions() { (void)rcflow_regions_close(pipe_.context(), 0); }
     Regions(const Regions&) = delete;
     Regions& operator=(const Regions&) = delete;
 
@@ -691,23 +710,16 @@ class Regions {
     // records their flow sums.  labels (32SC1, optional) and maskOut (8UC1, optional; may be `mask`) are filled when given.
     void push(const Mat& mask, bool with_flow = false, Mat* labels = nullptr, Mat* maskOut = nullptr) {
         const int w = pipe_.width(), h = pipe_.height();
-        if (mask.empty() || mask.rows != h || mask.cols != w || mask.channels != 1 || mask.elem != 1)
-            throw Error(RC_EINVAL, "Regions::push: the mask must be 8UC1 of the pipeline's size");
-        if (labels && (labels->empty() || labels->rows != h || labels->cols != w || labels->channels != 1 || labels->elem != 4))
-            throw Error(RC_EINVAL, "Regions::push: labels must be 32SC1 of the pipeline's size");
-        if (maskOut && (maskOut->empty() || maskOut->rows != h || maskOut->cols != w || maskOut->channels != 1 || maskOut->elem != 1))
-            throw Error(RC_EINVAL, "Regions::push: maskOut must be 8UC1 of the pipeline's size");
+        if (!is_image(mask, w, h, 1, 1)) throw Error(RC_EINVAL, "Regions::push: the mask must be 8UC1 of the pipeline's size");
+        if (labels && !is_image(*labels, w, h, 1, 4)) throw Error(RC_EINVAL, "Regions::push: labels must be 32SC1 of the pipeline's size");
+        if (maskOut && !is_image(*maskOut, w, h, 1, 1)) throw Error(RC_EINVAL, "Regions::push: maskOut must be 8UC1 of the pipeline's size");
         if (with_flow && !pipe_.device_flow()) throw Error(RC_ESTATE, "Regions::push: the pipeline holds no flow field");
-        if (!d_mask_) hip_check(hipMalloc(&d_mask_, (size_t)w * h), "hipMalloc mask");
-        if (labels && !d_labels_) hip_check(hipMalloc(&d_labels_, (size_t)w * h * 4), "hipMalloc labels");
-        check(rcflow_sync(pipe_.context(), 0));
-        hip_check(hipMemcpy2D(d_mask_, (size_t)w, mask.data, mask.step, (size_t)w, h, hipMemcpyHostToDevice), "upload mask");
-        check(rcflow_regions_push_dev(pipe_.context(), 0, (const uint8_t*)d_mask_, (size_t)w, with_flow ? pipe_.device_flow() : nullptr,
-                                      (size_t)w * 8, labels ? (int32_t*)d_labels_ : nullptr, (size_t)w * 4,
-                                      maskOut ? (uint8_t*)d_mask_ : nullptr, (size_t)w, nullptr, nullptr));
-        if (labels || maskOut) check(rcflow_sync(pipe_.context(), 0));
-        if (labels) hip_check(hipMemcpy2D(labels->data, labels->step, d_labels_, (size_t)w * 4, (size_t)w * 4, h, hipMemcpyDeviceToHost), "download labels");
-        if (maskOut) hip_check(hipMemcpy2D(maskOut->data, maskOut->step, d_mask_, (size_t)w, (size_t)w, h, hipMemcpyDeviceToHost), "download mask");
+        // maskOut is written in place, through the mask's own staging image
+        staged(pipe_.context(), {{d_mask_, &mask}}, [&] {
+            return rcflow_regions_push_dev(pipe_.context(), 0, d_mask_.ptr<const uint8_t>(), d_mask_.pitch(), with_flow ? pipe_.device_flow() : nullptr,
+                                           (size_t)w * 8, d_labels_.ptr<int32_t>(labels), d_labels_.pitch(),
+                                           d_mask_.ptr<uint8_t>(maskOut), d_mask_.pitch(), nullptr, nullptr);
+        }, {{d_labels_, labels}, {d_mask_, maskOut}});
     }
     // waits for the pipeline's stream: the records of the last push, in order; summary (optional): the 8 words of include/rcflow.h
     std::vector<rc_region> regions(long long* summary = nullptr) {
@@ -719,17 +731,10 @@ class Regions {
     }
     // paints the boxes, centroids and (flow_scale != 0) mean-flow lines of the last push into img (8UC3)
     void draw(Mat& img, uint32_t color = 0x00ffff, int thickness = 1, int disc_radius = 3, double flow_scale = 0.) {
-        const int w = pipe_.width(), h = pipe_.height();
-        if (img.empty() || img.rows != h || img.cols != w || img.channels != 3 || img.elem != 1)
-            throw Error(RC_EINVAL, "Regions::draw: img must be 8UC3 of the pipeline's size");
-        if (!d_prims_) hip_check(hipMalloc(&d_prims_, (size_t)6 * max_regions_ * sizeof(rc_draw_prim)), "hipMalloc prims");
-        if (!d_canvas_) hip_check(hipMalloc(&d_canvas_, (size_t)w * h * 3), "hipMalloc canvas");
-        check(rcflow_sync(pipe_.context(), 0));
-        hip_check(hipMemcpy2D(d_canvas_, (size_t)w * 3, img.data, img.step, (size_t)w * 3, h, hipMemcpyHostToDevice), "upload canvas");
-        check(rcflow_regions_prims_dev(pipe_.context(), 0, color, thickness, disc_radius, flow_scale, (rc_draw_prim*)d_prims_));
-        check(rcflow_draw_dev(pipe_.context(), 0, (uint8_t*)d_canvas_, (size_t)w * 3, w, h, 3, (const rc_draw_prim*)d_prims_, 6 * max_regions_, nullptr));
-        check(rcflow_sync(pipe_.context(), 0));
-        hip_check(hipMemcpy2D(img.data, img.step, d_canvas_, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost), "download canvas");
+        if (!is_image(img, pipe_.width(), pipe_.height(), 3, 1)) throw Error(RC_EINVAL, "Regions::draw: img must be 8UC3 of the pipeline's size");
+        staged_draw(pipe_.context(), d_canvas_, d_prims_, 6 * max_regions_, img, [&](rc_draw_prim* prims) {
+            return rcflow_regions_prims_dev(pipe_.context(), 0, color, thickness, disc_radius, flow_scale, prims);
+        });
     }
     void setMinArea(int min_area) { check(rcflow_regions_set(pipe_.context(), 0, min_area)); }
     rc_regions_info info() { rc_regions_info i; check(rcflow_regions_info(pipe_.context(), 0, &i)); return i; }
@@ -739,7 +744,7 @@ class Regions {
   private:
     Pipeline& pipe_;
     int max_regions_;
-    void *d_mask_ = nullptr, *d_labels_ = nullptr, *d_prims_ = nullptr, *d_canvas_ = nullptr;
+    DeviceImage d_mask_, d_labels_, d_prims_, d_canvas_;
 };
 
 // Rip tracks on the device (rcflow_tracks_*): the regions of a Regions object followed from push to push, with hits, misses
@@ -753,10 +758,7 @@ class Tracks {
         p.max_regions = max_regions_; p.max_tracks = max_tracks; p.min_overlap = min_overlap; p.max_misses = max_misses; p.min_hits = min_hits;
         check(rcflow_tracks_open(pipe.context(), 0, pipe.width(), pipe.height(), &p));
     }
-    ~Tracks() {
-        (void)rcflow_tracks_close(pipe_.context(), 0);
-        for (void* p : {d_mask_, d_labels_, d_records_, d_summary_, d_out_, d_prims_, d_canvas_}) if (p) (void)hipFree(p);
-    }
+    ~Tracks() { (void)rcflow_tracks_close(pipe_.context(), 0); }
     Tracks(const Tracks&) = delete;
     Tracks& operator=(const Tracks&) = delete;
 
@@ -765,26 +767,21 @@ class Tracks {
     // inside the regions of confirmed tracks.
     void push(const Mat& mask, bool with_flow = false, Mat* maskOut = nullptr) {
         const int w = pipe_.width(), h = pipe_.height();
-        if (mask.empty() || mask.rows != h || mask.cols != w || mask.channels != 1 || mask.elem != 1)
-            throw Error(RC_EINVAL, "Tracks::push: the mask must be 8UC1 of the pipeline's size");
-        if (maskOut && (maskOut->empty() || maskOut->rows != h || maskOut->cols != w || maskOut->channels != 1 || maskOut->elem != 1))
-            throw Error(RC_EINVAL, "Tracks::push: maskOut must be 8UC1 of the pipeline's size");
+        if (!is_image(mask, w, h, 1, 1)) throw Error(RC_EINVAL, "Tracks::push: the mask must be 8UC1 of the pipeline's size");
+        if (maskOut && !is_image(*maskOut, w, h, 1, 1)) throw Error(RC_EINVAL, "Tracks::push: maskOut must be 8UC1 of the pipeline's size");
         if (with_flow && !pipe_.device_flow()) throw Error(RC_ESTATE, "Tracks::push: the pipeline holds no flow field");
-        if (!d_mask_) hip_check(hipMalloc(&d_mask_, (size_t)w * h), "hipMalloc mask");
-        if (!d_labels_) hip_check(hipMalloc(&d_labels_, (size_t)w * h * 4), "hipMalloc labels");
-        if (!d_records_) hip_check(hipMalloc(&d_records_, (size_t)rg_records_ * sizeof(rc_region)), "hipMalloc records");
-        if (!d_summary_) hip_check(hipMalloc(&d_summary_, 64), "hipMalloc summary");
-        if (maskOut && !d_out_) hip_check(hipMalloc(&d_out_, (size_t)w * h), "hipMalloc mask out");
-        check(rcflow_sync(pipe_.context(), 0));
-        hip_check(hipMemcpy2D(d_mask_, (size_t)w, mask.data, mask.step, (size_t)w, h, hipMemcpyHostToDevice), "upload mask");
-        check(rcflow_regions_push_dev(pipe_.context(), 0, (const uint8_t*)d_mask_, (size_t)w, with_flow ? pipe_.device_flow() : nullptr,
-                                      (size_t)w * 8, (int32_t*)d_labels_, (size_t)w * 4, nullptr, 0, (rc_region*)d_records_, (long long*)d_summary_));
-        check(rcflow_tracks_push_dev(pipe_.context(), 0, (const int32_t*)d_labels_, (size_t)w * 4, (const rc_region*)d_records_,
-                                     (const long long*)d_summary_, nullptr, nullptr, maskOut ? (uint8_t*)d_out_ : nullptr, (size_t)w, nullptr));
-        if (maskOut) {
-            check(rcflow_sync(pipe_.context(), 0));
-            hip_check(hipMemcpy2D(maskOut->data, maskOut->step, d_out_, (size_t)w, (size_t)w, h, hipMemcpyDeviceToHost), "download mask");
-        }
+        d_labels_.reserve(w, h, 1, 4);
+        d_records_.reserve(rg_records_, 1, 1, (int)sizeof(rc_region));
+        d_summary_.reserve(8, 1, 1, 8);
+        staged(pipe_.context(), {{d_mask_, &mask}}, [&] {
+            const int rc = rcflow_regions_push_dev(pipe_.context(), 0, d_mask_.ptr<const uint8_t>(), d_mask_.pitch(),
+                                                   with_flow ? pipe_.device_flow() : nullptr, (size_t)w * 8, d_labels_.ptr<int32_t>(), d_labels_.pitch(),
+                                                   nullptr, 0, d_records_.ptr<rc_region>(), d_summary_.ptr<long long>());
+            if (rc < 0) return rc;
+            return rcflow_tracks_push_dev(pipe_.context(), 0, d_labels_.ptr<const int32_t>(), d_labels_.pitch(), d_records_.ptr<const rc_region>(),
+                                          d_summary_.ptr<const long long>(), nullptr, nullptr, d_out_.ptr<uint8_t>(maskOut), d_out_.pitch(),
+                                          nullptr);
+        }, {{d_out_, maskOut}});
     }
     // waits for the pipeline's stream: the used slots of the table after the last push, in slot order; summary (optional):
     // the 8 words of include/rcflow.h; footprint (optional): h * w words, slot + 1 of the track that last covered the pixel
@@ -797,17 +794,10 @@ class Tracks {
     }
     // paints the boxes and centroids of the confirmed tracks into img (8UC3)
     void draw(Mat& img, uint32_t color = 0x00ffff, int thickness = 1, int disc_radius = 3) {
-        const int w = pipe_.width(), h = pipe_.height();
-        if (img.empty() || img.rows != h || img.cols != w || img.channels != 3 || img.elem != 1)
-            throw Error(RC_EINVAL, "Tracks::draw: img must be 8UC3 of the pipeline's size");
-        if (!d_prims_) hip_check(hipMalloc(&d_prims_, (size_t)5 * max_tracks_ * sizeof(rc_draw_prim)), "hipMalloc prims");
-        if (!d_canvas_) hip_check(hipMalloc(&d_canvas_, (size_t)w * h * 3), "hipMalloc canvas");
-        check(rcflow_sync(pipe_.context(), 0));
-        hip_check(hipMemcpy2D(d_canvas_, (size_t)w * 3, img.data, img.step, (size_t)w * 3, h, hipMemcpyHostToDevice), "upload canvas");
-        check(rcflow_tracks_prims_dev(pipe_.context(), 0, color, thickness, disc_radius, (rc_draw_prim*)d_prims_));
-        check(rcflow_draw_dev(pipe_.context(), 0, (uint8_t*)d_canvas_, (size_t)w * 3, w, h, 3, (const rc_draw_prim*)d_prims_, 5 * max_tracks_, nullptr));
-        check(rcflow_sync(pipe_.context(), 0));
-        hip_check(hipMemcpy2D(img.data, img.step, d_canvas_, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost), "download canvas");
+        if (!is_image(img, pipe_.width(), pipe_.height(), 3, 1)) throw Error(RC_EINVAL, "Tracks::draw: img must be 8UC3 of the pipeline's size");
+        staged_draw(pipe_.context(), d_canvas_, d_prims_, 5 * max_tracks_, img, [&](rc_draw_prim* prims) {
+            return rcflow_tracks_prims_dev(pipe_.context(), 0, color, thickness, disc_radius, prims);
+        });
     }
     rc_tracks_info info() { rc_tracks_info i; check(rcflow_tracks_info(pipe_.context(), 0, &i)); return i; }
     void reset() { check(rcflow_tracks_reset(pipe_.context(), 0)); }
@@ -815,8 +805,7 @@ class Tracks {
   private:
     Pipeline& pipe_;
     int max_regions_, rg_records_, max_tracks_;
-    void *d_mask_ = nullptr, *d_labels_ = nullptr, *d_records_ = nullptr, *d_summary_ = nullptr, *d_out_ = nullptr, *d_prims_ = nullptr,
-         *d_canvas_ = nullptr;
+    DeviceImage d_mask_, d_labels_, d_records_, d_summary_, d_out_, d_prims_, d_canvas_;
 };
 
 // Motion templates on the device (rcflow_motion_*): globalOrientation (ripcurrents.hpp, ripcurrents_module.cpp:319-359) with
@@ -833,30 +822,20 @@ class MotionTemplates {
         p.grid_x = grid_x; p.grid_y = grid_y; p.flags = fresh ? RC_MOTION_FRESH : 0;
         check(rcflow_motion_open(pipe.context(), 0, pipe.width(), pipe.height(), &p));
     }
-    ~MotionTemplates() {
-        (void)rcflow_motion_close(pipe_.context(), 0);
-        for (void* p : {d_gray_, d_vis_, d_prims_}) if (p) (void)hipFree(p);
-    }
+    ~MotionTemplates() { (void)rcflow_motion_close(pipe_.context(), 0); }
     MotionTemplates(const MotionTemplates&) = delete;
     MotionTemplates& operator=(const MotionTemplates&) = delete;
 
     // gray: 8UC1 of the pipeline's size.  picture (8UC3, optional): the history as a grey image (hist_gray of :333).
     void push(const Mat& gray, double timestamp = RC_MOTION_AUTO_TIME, Mat* picture = nullptr) {
         const int w = pipe_.width(), h = pipe_.height();
-        if (gray.empty() || gray.rows != h || gray.cols != w || gray.channels != 1 || gray.elem != 1)
-            throw Error(RC_EINVAL, "MotionTemplates::push: the frame must be 8UC1 of the pipeline's size");
-        if (picture && (picture->empty() || picture->rows != h || picture->cols != w || picture->channels != 3 || picture->elem != 1))
+        if (!is_image(gray, w, h, 1, 1)) throw Error(RC_EINVAL, "MotionTemplates::push: the frame must be 8UC1 of the pipeline's size");
+        if (picture && !is_image(*picture, w, h, 3, 1))
             throw Error(RC_EINVAL, "MotionTemplates::push: the picture must be 8UC3 of the pipeline's size");
-        if (!d_gray_) hip_check(hipMalloc(&d_gray_, (size_t)w * h), "hipMalloc gray");
-        if (picture && !d_vis_) hip_check(hipMalloc(&d_vis_, (size_t)w * h * 3), "hipMalloc picture");
-        check(rcflow_sync(pipe_.context(), 0));                  // the last push may still be reading the staging frame
-        hip_check(hipMemcpy2D(d_gray_, (size_t)w, gray.data, gray.step, (size_t)w, h, hipMemcpyHostToDevice), "upload frame");
-        check(rcflow_motion_push_dev(pipe_.context(), 0, (const uint8_t*)d_gray_, (size_t)w, timestamp, nullptr, 0, nullptr, 0, nullptr, 0,
-                                     picture ? (uint8_t*)d_vis_ : nullptr, (size_t)w * 3, nullptr, nullptr));
-        if (picture) {
-            check(rcflow_sync(pipe_.context(), 0));
-            hip_check(hipMemcpy2D(picture->data, picture->step, d_vis_, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost), "download picture");
-        }
+        staged(pipe_.context(), {{d_gray_, &gray}}, [&] {
+            return rcflow_motion_push_dev(pipe_.context(), 0, d_gray_.ptr<const uint8_t>(), d_gray_.pitch(), timestamp, nullptr, 0, nullptr, 0, nullptr, 0,
+                                          d_vis_.ptr<uint8_t>(picture), d_vis_.pitch(), nullptr, nullptr);
+        }, {{d_vis_, picture}});
     }
     // waits for the pipeline's stream: the frame's record of the last push; cells (optional): grid_y x grid_x records
     rc_motion_cell read(std::vector<rc_motion_cell>* cells = nullptr, long long* silhouette = nullptr) {
@@ -869,17 +848,12 @@ class MotionTemplates {
     double angle() { return read().angle; }
     // paints a disc and a line of `length` pixels per cell and for the frame into img (8UC3); no arrowheads
     void draw(Mat& img, uint32_t color = 0x00ffff, int thickness = 1, int disc_radius = 2, double length = 15.) {
-        const int w = pipe_.width(), h = pipe_.height(), n = 2 * (cells_ + 1);
-        if (img.empty() || img.rows != h || img.cols != w || img.channels != 3 || img.elem != 1)
+        if (!is_image(img, pipe_.width(), pipe_.height(), 3, 1))
             throw Error(RC_EINVAL, "MotionTemplates::draw: img must be 8UC3 of the pipeline's size");
-        if (!d_prims_) hip_check(hipMalloc(&d_prims_, (size_t)n * sizeof(rc_draw_prim)), "hipMalloc prims");
-        if (!d_vis_) hip_check(hipMalloc(&d_vis_, (size_t)w * h * 3), "hipMalloc picture");
-        check(rcflow_sync(pipe_.context(), 0));
-        hip_check(hipMemcpy2D(d_vis_, (size_t)w * 3, img.data, img.step, (size_t)w * 3, h, hipMemcpyHostToDevice), "upload canvas");
-        check(rcflow_motion_prims_dev(pipe_.context(), 0, color, thickness, disc_radius, length, (rc_draw_prim*)d_prims_));
-        check(rcflow_draw_dev(pipe_.context(), 0, (uint8_t*)d_vis_, (size_t)w * 3, w, h, 3, (const rc_draw_prim*)d_prims_, n, nullptr));
-        check(rcflow_sync(pipe_.context(), 0));
-        hip_check(hipMemcpy2D(img.data, img.step, d_vis_, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost), "download canvas");
+        // d_vis_ serves push's picture and this canvas: both 8UC3 of the pipeline's size, never in use at once
+        staged_draw(pipe_.context(), d_vis_, d_prims_, 2 * (cells_ + 1), img, [&](rc_draw_prim* prims) {
+            return rcflow_motion_prims_dev(pipe_.context(), 0, color, thickness, disc_radius, length, prims);
+        });
     }
     rc_motion_info info() { rc_motion_info i; check(rcflow_motion_info(pipe_.context(), 0, &i)); return i; }
     void reset() { check(rcflow_motion_reset(pipe_.context(), 0)); }
@@ -887,7 +861,7 @@ class MotionTemplates {
   private:
     Pipeline& pipe_;
     int cells_;
-    void *d_gray_ = nullptr, *d_vis_ = nullptr, *d_prims_ = nullptr;
+    DeviceImage d_gray_, d_vis_, d_prims_;
 };
 
 
@@ -903,10 +877,7 @@ class Ftle {
         p.window = window; p.direction = direction; p.dt = dt; p.spacing = spacing; p.threshold = threshold; p.vis_max = vis_max;
         check(rcflow_ftle_open(pipe.context(), 0, pipe.width(), pipe.height(), &p));
     }
-    ~Ftle() {
-        (void)rcflow_ftle_close(pipe_.context(), 0);
-        for (void* p : {d_flow_, d_ftle_, d_mask_, d_vis_}) if (p) (void)hipFree(p);
-    }
+    ~Ftle() { (void)rcflow_ftle_close(pipe_.context(), 0); }
     Ftle(const Ftle&) = delete;
     Ftle& operator=(const Ftle&) = delete;
 
@@ -914,25 +885,14 @@ class Ftle {
     // Without any the field only enters the ring (one launch).
     void push(const Mat& flow, Mat* ftle = nullptr, Mat* mask = nullptr, Mat* picture = nullptr) {
         const int w = pipe_.width(), h = pipe_.height();
-        if (flow.empty() || flow.rows != h || flow.cols != w || flow.channels != 2 || flow.elem != 4)
-            throw Error(RC_EINVAL, "Ftle::push: the field must be 32FC2 of the pipeline's size");
-        if ((ftle && !fits(*ftle, 1, 4)) || (mask && !fits(*mask, 1, 1)) || (picture && !fits(*picture, 3, 1)))
+        if (!is_image(flow, w, h, 2, 4)) throw Error(RC_EINVAL, "Ftle::push: the field must be 32FC2 of the pipeline's size");
+        if ((ftle && !is_image(*ftle, w, h, 1, 4)) || (mask && !is_image(*mask, w, h, 1, 1)) || (picture && !is_image(*picture, w, h, 3, 1)))
             throw Error(RC_EINVAL, "Ftle::push: ftle 32FC1, mask 8UC1, picture 8UC3, each of the pipeline's size");
-        const size_t px = (size_t)w * h;
-        if (!d_flow_) hip_check(hipMalloc(&d_flow_, px * 8), "hipMalloc field");
-        if (ftle && !d_ftle_) hip_check(hipMalloc(&d_ftle_, px * 4), "hipMalloc ftle");
-        if (mask && !d_mask_) hip_check(hipMalloc(&d_mask_, px), "hipMalloc mask");
-        if (picture && !d_vis_) hip_check(hipMalloc(&d_vis_, px * 3), "hipMalloc picture");
-        check(rcflow_sync(pipe_.context(), 0));                  // the last push may still be reading the staging field
-        hip_check(hipMemcpy2D(d_flow_, (size_t)w * 8, flow.data, flow.step, (size_t)w * 8, h, hipMemcpyHostToDevice), "upload field");
-        check(rcflow_ftle_push_dev(pipe_.context(), 0, (const float*)d_flow_, (size_t)w * 8, nullptr, 0, nullptr, 0, nullptr, 0,
-                                   ftle ? (float*)d_ftle_ : nullptr, (size_t)w * 4, mask ? (uint8_t*)d_mask_ : nullptr, (size_t)w,
-                                   picture ? (uint8_t*)d_vis_ : nullptr, (size_t)w * 3, nullptr));
-        if (!ftle && !mask && !picture) return;
-        check(rcflow_sync(pipe_.context(), 0));
-        if (ftle) hip_check(hipMemcpy2D(ftle->data, ftle->step, d_ftle_, (size_t)w * 4, (size_t)w * 4, h, hipMemcpyDeviceToHost), "download ftle");
-        if (mask) hip_check(hipMemcpy2D(mask->data, mask->step, d_mask_, (size_t)w, (size_t)w, h, hipMemcpyDeviceToHost), "download mask");
-        if (picture) hip_check(hipMemcpy2D(picture->data, picture->step, d_vis_, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost), "download picture");
+        staged(pipe_.context(), {{d_flow_, &flow}}, [&] {
+            return rcflow_ftle_push_dev(pipe_.context(), 0, d_flow_.ptr<const float>(), d_flow_.pitch(), nullptr, 0, nullptr, 0, nullptr, 0,
+                                        d_ftle_.ptr<float>(ftle), d_ftle_.pitch(), d_mask_.ptr<uint8_t>(mask), d_mask_.pitch(),
+                                        d_vis_.ptr<uint8_t>(picture), d_vis_.pitch(), nullptr);
+        }, {{d_ftle_, ftle}, {d_mask_, mask}, {d_vis_, picture}});
     }
     // waits for the pipeline's stream: the summary of the last push that had an output (include/rcflow.h: n, valid, mask,
     // stopped, bits of the largest eigenvalue, pushes, 0, 0)
@@ -946,11 +906,8 @@ class Ftle {
     void reset() { check(rcflow_ftle_reset(pipe_.context(), 0)); }
 
   private:
-    bool fits(const Mat& m, int channels, int elem) const {
-        return !m.empty() && m.rows == pipe_.height() && m.cols == pipe_.width() && m.channels == channels && m.elem == elem;
-    }
     Pipeline& pipe_;
-    void *d_flow_ = nullptr, *d_ftle_ = nullptr, *d_mask_ = nullptr, *d_vis_ = nullptr;
+    DeviceImage d_flow_, d_ftle_, d_mask_, d_vis_;
 };
 
 // Plan view on the device (rcflow_planview_*): the flow field in metres per second, and the frame, on a regular grid on the
@@ -961,10 +918,7 @@ class PlanView {
     PlanView(Pipeline& pipe, const rc_planview_params& prm) : pipe_(pipe), nx_(prm.nx), ny_(prm.ny) {
         check(rcflow_planview_open(pipe.context(), 0, pipe.width(), pipe.height(), &prm));
     }
-    ~PlanView() {
-        (void)rcflow_planview_close(pipe_.context(), 0);
-        for (void* p : {d_flow_, d_bgr_, d_plan_, d_mask_, d_pic_}) if (p) (void)hipFree(p);
-    }
+    ~PlanView() { (void)rcflow_planview_close(pipe_.context(), 0); }
     PlanView(const PlanView&) = delete;
     PlanView& operator=(const PlanView&) = delete;
 
@@ -972,29 +926,17 @@ class PlanView {
     // need the field, picture 8UC3 the frame; each nx x ny and optional.
     void push(const Mat* flow, const Mat* frame, Mat* plan = nullptr, Mat* mask = nullptr, Mat* picture = nullptr) {
         const int w = pipe_.width(), h = pipe_.height();
-        if ((flow && !fits(*flow, w, h, 2, 4)) || (frame && !fits(*frame, w, h, 3, 1)) || (!flow && !frame))
+        if ((flow && !is_image(*flow, w, h, 2, 4)) || (frame && !is_image(*frame, w, h, 3, 1)) || (!flow && !frame))
             throw Error(RC_EINVAL, "PlanView::push: the field 32FC2, the frame 8UC3, each of the pipeline's size, and one of them at least");
-        if ((plan && !fits(*plan, nx_, ny_, 2, 4)) || (mask && !fits(*mask, nx_, ny_, 1, 1)) || (picture && !fits(*picture, nx_, ny_, 3, 1)) ||
+        if ((plan && !is_image(*plan, nx_, ny_, 2, 4)) || (mask && !is_image(*mask, nx_, ny_, 1, 1)) || (picture && !is_image(*picture, nx_, ny_, 3, 1)) ||
             (!flow && (plan || mask)) || (!frame && picture))
             throw Error(RC_EINVAL, "PlanView::push: plan 32FC2 and mask 8UC1 need the field, picture 8UC3 the frame, each of the plan's size");
-        const size_t px = (size_t)w * h, cells = (size_t)nx_ * ny_;
-        if (flow && !d_flow_) hip_check(hipMalloc(&d_flow_, px * 8), "hipMalloc field");
-        if (frame && !d_bgr_) hip_check(hipMalloc(&d_bgr_, px * 3), "hipMalloc frame");
-        if (plan && !d_plan_) hip_check(hipMalloc(&d_plan_, cells * 8), "hipMalloc plan");
-        if (mask && !d_mask_) hip_check(hipMalloc(&d_mask_, cells), "hipMalloc mask");
-        if (picture && !d_pic_) hip_check(hipMalloc(&d_pic_, cells * 3), "hipMalloc picture");
-        check(rcflow_sync(pipe_.context(), 0));                  // the last push may still be reading the staging inputs
-        if (flow) hip_check(hipMemcpy2D(d_flow_, (size_t)w * 8, flow->data, flow->step, (size_t)w * 8, h, hipMemcpyHostToDevice), "upload field");
-        if (frame) hip_check(hipMemcpy2D(d_bgr_, (size_t)w * 3, frame->data, frame->step, (size_t)w * 3, h, hipMemcpyHostToDevice), "upload frame");
-        check(rcflow_planview_push_dev(pipe_.context(), 0, flow ? (const float*)d_flow_ : nullptr, (size_t)w * 8,
-                                       frame ? (const uint8_t*)d_bgr_ : nullptr, (size_t)w * 3, plan ? (float*)d_plan_ : nullptr, (size_t)nx_ * 8,
-                                       mask ? (uint8_t*)d_mask_ : nullptr, (size_t)nx_, picture ? (uint8_t*)d_pic_ : nullptr, (size_t)nx_ * 3,
-                                       nullptr));
-        if (!plan && !mask && !picture) return;
-        check(rcflow_sync(pipe_.context(), 0));
-        if (plan) hip_check(hipMemcpy2D(plan->data, plan->step, d_plan_, (size_t)nx_ * 8, (size_t)nx_ * 8, ny_, hipMemcpyDeviceToHost), "download plan");
-        if (mask) hip_check(hipMemcpy2D(mask->data, mask->step, d_mask_, (size_t)nx_, (size_t)nx_, ny_, hipMemcpyDeviceToHost), "download mask");
-        if (picture) hip_check(hipMemcpy2D(picture->data, picture->step, d_pic_, (size_t)nx_ * 3, (size_t)nx_ * 3, ny_, hipMemcpyDeviceToHost), "download picture");
+        staged(pipe_.context(), {{d_flow_, flow}, {d_bgr_, frame}}, [&] {
+            return rcflow_planview_push_dev(pipe_.context(), 0, d_flow_.ptr<const float>(flow), d_flow_.pitch(),
+                                            d_bgr_.ptr<const uint8_t>(frame), d_bgr_.pitch(),
+                                            d_plan_.ptr<float>(plan), d_plan_.pitch(), d_mask_.ptr<uint8_t>(mask), d_mask_.pitch(),
+                                            d_pic_.ptr<uint8_t>(picture), d_pic_.pitch(), nullptr);
+        }, {{d_plan_, plan}, {d_mask_, mask}, {d_pic_, picture}});
     }
     // waits for the pipeline's stream: the summary of the last push (include/rcflow.h: usable, seen, valid, bits of the
     // largest squared speed, pushes, 0, 0, 0)
@@ -1013,12 +955,9 @@ class PlanView {
     void reset() { check(rcflow_planview_reset(pipe_.context(), 0)); }
 
   private:
-    static bool fits(const Mat& m, int cols, int rows, int channels, int elem) {
-        return !m.empty() && m.rows == rows && m.cols == cols && m.channels == channels && m.elem == elem;
-    }
     Pipeline& pipe_;
     int nx_, ny_;
-    void *d_flow_ = nullptr, *d_bgr_ = nullptr, *d_plan_ = nullptr, *d_mask_ = nullptr, *d_pic_ = nullptr;
+    DeviceImage d_flow_, d_bgr_, d_plan_, d_mask_, d_pic_;
 };
 
 // Wave spectra on the device (rcflow_waves_*): a sliding DFT of the last `window` grey frames at a few bins per pixel, and per
@@ -1029,14 +968,16 @@ class Waves {
     Waves(Pipeline& pipe, const rc_waves_params& prm) : pipe_(pipe) {
         check(rcflow_waves_open(pipe.context(), 0, pipe.width(), pipe.height(), &prm));
         rc_waves_info i;
-        check(rcflow_waves_info(pipe.context(), 0, &i));
+        try {
+            check(rcflow_waves_info(pipe.context(), 0, &i));
+        } catch (...) {                                          // no destructor runs: close what was opened
+            (void)rcflow_waves_close(pipe.context(), 0);
+            throw;
+        }
         cells_ = (size_t)prm.grid_x * prm.grid_y;
         bins_ = i.bins;
     }
-    ~Waves() {
-        (void)rcflow_waves_close(pipe_.context(), 0);
-        for (void* p : {d_gray_, d_mask_, d_bin_, d_vis_, d_summary_}) if (p) (void)hipFree(p);
-    }
+    ~Waves() { (void)rcflow_waves_close(pipe_.context(), 0); }
     Waves(const Waves&) = delete;
     Waves& operator=(const Waves&) = delete;
 
@@ -1045,26 +986,16 @@ class Waves {
     // then return.  Without any the frame only enters the ring and the spectrum (one launch).
     void push(const Mat& gray, const Mat* mask = nullptr, bool compute = false, Mat* bin_map = nullptr, Mat* picture = nullptr) {
         const int w = pipe_.width(), h = pipe_.height();
-        if (!fits(gray, 1) || (mask && !fits(*mask, 1)))
+        if (!is_image(gray, w, h, 1, 1) || (mask && !is_image(*mask, w, h, 1, 1)))
             throw Error(RC_EINVAL, "Waves::push: the frame and the mask must be 8UC1 of the pipeline's size");
-        if ((bin_map && !fits(*bin_map, 1)) || (picture && !fits(*picture, 3)))
+        if ((bin_map && !is_image(*bin_map, w, h, 1, 1)) || (picture && !is_image(*picture, w, h, 3, 1)))
             throw Error(RC_EINVAL, "Waves::push: bin_map 8UC1, picture 8UC3, each of the pipeline's size");
-        const size_t px = (size_t)w * h;
-        if (!d_gray_) hip_check(hipMalloc(&d_gray_, px), "hipMalloc frame");
-        if (mask && !d_mask_) hip_check(hipMalloc(&d_mask_, px), "hipMalloc mask");
-        if (bin_map && !d_bin_) hip_check(hipMalloc(&d_bin_, px), "hipMalloc bin map");
-        if (picture && !d_vis_) hip_check(hipMalloc(&d_vis_, px * 3), "hipMalloc picture");
-        if (compute && !d_summary_) hip_check(hipMalloc(&d_summary_, 64), "hipMalloc summary");
-        check(rcflow_sync(pipe_.context(), 0));                  // the last push may still be reading the staging frame
-        hip_check(hipMemcpy2D(d_gray_, (size_t)w, gray.data, gray.step, (size_t)w, h, hipMemcpyHostToDevice), "upload frame");
-        if (mask) hip_check(hipMemcpy2D(d_mask_, (size_t)w, mask->data, mask->step, (size_t)w, h, hipMemcpyHostToDevice), "upload mask");
-        check(rcflow_waves_push_dev(pipe_.context(), 0, (const uint8_t*)d_gray_, (size_t)w, mask ? (const uint8_t*)d_mask_ : nullptr, (size_t)w,
-                                    nullptr, nullptr, bin_map ? (uint8_t*)d_bin_ : nullptr, (size_t)w, picture ? (uint8_t*)d_vis_ : nullptr,
-                                    (size_t)w * 3, compute ? (long long*)d_summary_ : nullptr));
-        if (!bin_map && !picture) return;
-        check(rcflow_sync(pipe_.context(), 0));
-        if (bin_map) hip_check(hipMemcpy2D(bin_map->data, bin_map->step, d_bin_, (size_t)w, (size_t)w, h, hipMemcpyDeviceToHost), "download bin map");
-        if (picture) hip_check(hipMemcpy2D(picture->data, picture->step, d_vis_, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost), "download picture");
+        if (compute) d_summary_.reserve(8, 1, 1, 8);
+        staged(pipe_.context(), {{d_gray_, &gray}, {d_mask_, mask}}, [&] {
+            return rcflow_waves_push_dev(pipe_.context(), 0, d_gray_.ptr<const uint8_t>(), d_gray_.pitch(), d_mask_.ptr<const uint8_t>(mask),
+                                         d_mask_.pitch(), nullptr, nullptr, d_bin_.ptr<uint8_t>(bin_map), d_bin_.pitch(),
+                                         d_vis_.ptr<uint8_t>(picture), d_vis_.pitch(), d_summary_.ptr<long long>(compute));
+        }, {{d_bin_, bin_map}, {d_vis_, picture}});
     }
     // each waits for the pipeline's stream: of the last push that computed (include/rcflow.h).  The summary: held frames, pixels
     // that take part, cells not empty, cells with a depth, pushes, 0, 0, 0; the records, grid_y x grid_x; the sums,
@@ -1095,13 +1026,10 @@ class Waves {
     void reset() { check(rcflow_waves_reset(pipe_.context(), 0)); }
 
   private:
-    bool fits(const Mat& m, int channels) const {
-        return !m.empty() && m.rows == pipe_.height() && m.cols == pipe_.width() && m.channels == channels && m.elem == 1;
-    }
     Pipeline& pipe_;
     size_t cells_ = 0;
     int bins_ = 0;
-    void *d_gray_ = nullptr, *d_mask_ = nullptr, *d_bin_ = nullptr, *d_vis_ = nullptr, *d_summary_ = nullptr;
+    DeviceImage d_gray_, d_mask_, d_bin_, d_vis_, d_summary_;
 };
 
 // Ensemble PIV on the device (rcflow_piv_*): block cross-correlation between consecutive grey frames, the correlation sums added
@@ -1112,14 +1040,16 @@ class Piv {
     Piv(Pipeline& pipe, const rc_piv_params& prm) : pipe_(pipe) {
         check(rcflow_piv_open(pipe.context(), 0, pipe.width(), pipe.height(), &prm));
         rc_piv_info i;
-        check(rcflow_piv_info(pipe.context(), 0, &i));
+        try {
+            check(rcflow_piv_info(pipe.context(), 0, &i));
+        } catch (...) {                                          // no destructor runs: close what was opened
+            (void)rcflow_piv_close(pipe.context(), 0);
+            throw;
+        }
         gx_ = i.grid_x; gy_ = i.grid_y;
         disp_ = (size_t)(2 * prm.range + 1) * (2 * prm.range + 1);
     }
-    ~Piv() {
-        (void)rcflow_piv_close(pipe_.context(), 0);
-        for (void* p : {d_gray_, d_field_, d_vis_, d_summary_}) if (p) (void)hipFree(p);
-    }
+    ~Piv() { (void)rcflow_piv_close(pipe_.context(), 0); }
     Piv(const Piv&) = delete;
     Piv& operator=(const Piv&) = delete;
 
@@ -1131,25 +1061,15 @@ class Piv {
     // Without any the frame is only correlated into the sums (one launch).
     void push(const Mat& gray, bool compute = false, Mat* field = nullptr, Mat* picture = nullptr) {
         const int w = pipe_.width(), h = pipe_.height();
-        if (gray.empty() || gray.rows != h || gray.cols != w || gray.channels != 1 || gray.elem != 1)
-            throw Error(RC_EINVAL, "Piv::push: the frame must be 8UC1 of the pipeline's size");
-        if (field && (field->empty() || field->rows != gy_ || field->cols != gx_ || field->channels != 2 || field->elem != 4))
-            throw Error(RC_EINVAL, "Piv::push: field 32FC2 of grid_y x grid_x");
-        if (picture && (picture->empty() || picture->rows != h || picture->cols != w || picture->channels != 3 || picture->elem != 1))
-            throw Error(RC_EINVAL, "Piv::push: picture 8UC3 of the pipeline's size");
-        const size_t px = (size_t)w * h, frow = (size_t)gx_ * 8;
-        if (!d_gray_) hip_check(hipMalloc(&d_gray_, px), "hipMalloc frame");
-        if (field && !d_field_) hip_check(hipMalloc(&d_field_, frow * gy_), "hipMalloc field");
-        if (picture && !d_vis_) hip_check(hipMalloc(&d_vis_, px * 3), "hipMalloc picture");
-        if (compute && !d_summary_) hip_check(hipMalloc(&d_summary_, 64), "hipMalloc summary");
-        check(rcflow_sync(pipe_.context(), 0));                  // the last push may still be reading the staging frame
-        hip_check(hipMemcpy2D(d_gray_, (size_t)w, gray.data, gray.step, (size_t)w, h, hipMemcpyHostToDevice), "upload frame");
-        check(rcflow_piv_push_dev(pipe_.context(), 0, (const uint8_t*)d_gray_, (size_t)w, nullptr, field ? (float*)d_field_ : nullptr, frow,
-                                  picture ? (uint8_t*)d_vis_ : nullptr, (size_t)w * 3, compute ? (long long*)d_summary_ : nullptr));
-        if (!field && !picture) return;
-        check(rcflow_sync(pipe_.context(), 0));
-        if (field) hip_check(hipMemcpy2D(field->data, field->step, d_field_, frow, frow, gy_, hipMemcpyDeviceToHost), "download field");
-        if (picture) hip_check(hipMemcpy2D(picture->data, picture->step, d_vis_, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost), "download picture");
+        if (!is_image(gray, w, h, 1, 1)) throw Error(RC_EINVAL, "Piv::push: the frame must be 8UC1 of the pipeline's size");
+        if (field && !is_image(*field, gx_, gy_, 2, 4)) throw Error(RC_EINVAL, "Piv::push: field 32FC2 of grid_y x grid_x");
+        if (picture && !is_image(*picture, w, h, 3, 1)) throw Error(RC_EINVAL, "Piv::push: picture 8UC3 of the pipeline's size");
+        if (compute) d_summary_.reserve(8, 1, 1, 8);
+        staged(pipe_.context(), {{d_gray_, &gray}}, [&] {
+            return rcflow_piv_push_dev(pipe_.context(), 0, d_gray_.ptr<const uint8_t>(), d_gray_.pitch(), nullptr,
+                                       d_field_.ptr<float>(field), d_field_.pitch(), d_vis_.ptr<uint8_t>(picture), d_vis_.pitch(),
+                                       d_summary_.ptr<long long>(compute));
+        }, {{d_field_, field}, {d_vis_, picture}});
     }
     // each waits for the pipeline's stream: of the last push that computed (include/rcflow.h).  The summary: pairs summed, cells,
     // valid, flat, low peak, edge, outliers, pushes; the records, grid_y x grid_x
@@ -1184,7 +1104,7 @@ class Piv {
     Pipeline& pipe_;
     int gx_ = 0, gy_ = 0;
     size_t disp_ = 0;
-    void *d_gray_ = nullptr, *d_field_ = nullptr, *d_vis_ = nullptr, *d_summary_ = nullptr;
+    DeviceImage d_gray_, d_field_, d_vis_, d_summary_;
 };
 
 }  // namespace rc

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import _cpp
 import _ftle_ref as F
 import _regions_ref as R
 from ripcurrents_amd._lib import RC_FTLE_LAUNCHES, FtleParams, RcflowError
@@ -416,14 +417,7 @@ def test_mask_goes_straight_into_regions(ctx, mixed):
 def test_cpp_ftle_against_the_statement(ctx, tmp_path):
     """rc::Ftle (include/rcflow_module.hpp) compiled with the flags of tests/cpp's test_module and run on fields it makes
     itself from integers (exact in float, so this file makes the same ones); the summaries it prints equal the statement's."""
-    exe = str(tmp_path / "test_ftle")
-    src = os.path.join(ROOT, "tests", "cpp", "test_ftle.cpp")
-    hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc"
-    cmd = [hipcc, "-O2", "-std=c++17", "-x", "c++", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"),
-           src, "-o", exe, "-L" + os.path.join(ROOT, "ripcurrents_amd"), "-lrcflow", "-L/opt/rocm/lib", "-lamdhip64",
-           "-Wl,-rpath," + os.path.join(ROOT, "ripcurrents_amd"), "-Wl,-rpath,/opt/rocm/lib"]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert b.returncode == 0, b.stderr[-4000:]
+    exe = _cpp.build("test_ftle", tmp_path)
     n = 7
     r = subprocess.run([exe, str(n)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "test_ftle: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import _cpp
 import _motion_ref as M
 import _tracers_ref as TR
 from ripcurrents_amd._lib import RC_MOTION_LAUNCHES, MotionParams, RcflowError
@@ -399,14 +400,7 @@ def test_primitives_and_drawing(ctx, orc):
 def test_cpp_motion_against_the_statement(ctx, orc, tmp_path):
     """rc::MotionTemplates (include/rcflow_module.hpp) compiled with the flags of tests/cpp's test_module and run on the +x bar;
     the records it prints equal the numpy statement's, and the angle is 0."""
-    exe = str(tmp_path / "test_motion")
-    src = os.path.join(ROOT, "tests", "cpp", "test_motion.cpp")
-    hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc"
-    cmd = [hipcc, "-O2", "-std=c++17", "-x", "c++", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"),
-           src, "-o", exe, "-L" + os.path.join(ROOT, "ripcurrents_amd"), "-lrcflow", "-L/opt/rocm/lib", "-lamdhip64",
-           "-Wl,-rpath," + os.path.join(ROOT, "ripcurrents_amd"), "-Wl,-rpath,/opt/rocm/lib"]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert b.returncode == 0, b.stderr[-4000:]
+    exe = _cpp.build("test_motion", tmp_path)
     n = 12
     r = subprocess.run([exe, str(n)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "test_motion: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

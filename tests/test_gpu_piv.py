@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import _cpp
 import _piv_ref as R
 from ripcurrents_amd._lib import RC_PIV_LAUNCHES, RC_PIV_MAX_STATE_BYTES, PivParams, RcflowError
 from ripcurrents_amd.api import PIV_CELL_DTYPE, PIV_SUMMARY, Piv
@@ -363,14 +364,7 @@ def test_refusals_and_lifecycle(ctx):
 def test_cpp_piv_against_the_statement(ctx, tmp_path):
     """rc::Piv (include/rcflow_module.hpp) compiled with the flags of tests/cpp's test_module and run on frames it makes itself
     from integers; the summaries, peaks, flags and checksums it prints equal the statement's."""
-    exe = str(tmp_path / "test_piv")
-    src = os.path.join(ROOT, "tests", "cpp", "test_piv.cpp")
-    hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc"
-    cmd = [hipcc, "-O2", "-std=c++17", "-x", "c++", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"),
-           src, "-o", exe, "-L" + os.path.join(ROOT, "ripcurrents_amd"), "-lrcflow", "-L/opt/rocm/lib", "-lamdhip64",
-           "-Wl,-rpath," + os.path.join(ROOT, "ripcurrents_amd"), "-Wl,-rpath,/opt/rocm/lib"]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert b.returncode == 0, b.stderr[-4000:]
+    exe = _cpp.build("test_piv", tmp_path)
     n = 12
     r = subprocess.run([exe, str(n)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "test_piv: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

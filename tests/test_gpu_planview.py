@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import _cpp
 import _ftle_ref as F
 import _planview_ref as P
 import _regions_ref as R
@@ -447,14 +448,7 @@ def test_cpp_planview_against_the_statement(ctx, tmp_path):
     """rc::PlanView (include/rcflow_module.hpp) compiled with the flags of tests/cpp's test_module and run on fields and frames
     it makes itself from integers (exact in float, so this file makes the same ones) through a camera whose numbers are exact
     in double; the summaries and counts it prints equal the statement's."""
-    exe = str(tmp_path / "test_planview")
-    src = os.path.join(ROOT, "tests", "cpp", "test_planview.cpp")
-    hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc"
-    cmd = [hipcc, "-O2", "-std=c++17", "-x", "c++", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"),
-           src, "-o", exe, "-L" + os.path.join(ROOT, "ripcurrents_amd"), "-lrcflow", "-L/opt/rocm/lib", "-lamdhip64",
-           "-Wl,-rpath," + os.path.join(ROOT, "ripcurrents_amd"), "-Wl,-rpath,/opt/rocm/lib"]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert b.returncode == 0, b.stderr[-4000:]
+    exe = _cpp.build("test_planview", tmp_path)
     n = 3
     r = subprocess.run([exe, str(n)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "test_planview: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import _cpp
 import _regions_ref as R
 import _tracers_ref as TR
 from ripcurrents_amd import synth
@@ -420,13 +421,7 @@ def test_product_chain_without_a_host_round_trip(ctx):
 def test_cpp_regions_against_the_statement(ctx, tmp_path):
     """rc::Regions (include/rcflow_module.hpp) compiled as tests/cpp's programs are and run on seeded masks; what it prints
     equals the numpy statement on the same masks."""
-    exe = str(tmp_path / "test_regions")
-    src = os.path.join(ROOT, "tests", "cpp", "test_regions.cpp")
-    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"),
-           src, "-o", exe, "-L" + os.path.join(ROOT, "ripcurrents_amd"), "-lrcflow", "-L/opt/rocm/lib", "-lamdhip64",
-           "-Wl,-rpath," + os.path.join(ROOT, "ripcurrents_amd"), "-Wl,-rpath,/opt/rocm/lib"]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert b.returncode == 0, b.stderr[-4000:]
+    exe = _cpp.build("test_regions", tmp_path, gxx=True)
     w, h, n = 200, 120, 4
     r = subprocess.run([exe, str(w), str(h), str(n)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "test_regions: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

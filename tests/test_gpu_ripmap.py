@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import _cpp
 import _ripmap_ref as R
 from ripcurrents_amd import synth
 from ripcurrents_amd._lib import RcflowError
@@ -324,13 +325,7 @@ def test_synthetic_scene_flags_the_jet(ctx):
 def test_cpp_ripmap_against_ctypes(ctx, tmp_path):
     """rc::RipMap (include/rcflow_module.hpp) compiled as tests/cpp's programs are and run on a seeded field sequence;
     the sums and flags it prints equal the ctypes session's on the same fields."""
-    exe = str(tmp_path / "test_ripmap")
-    src = os.path.join(ROOT, "tests", "cpp", "test_ripmap.cpp")
-    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"),
-           src, "-o", exe, "-L" + os.path.join(ROOT, "ripcurrents_amd"), "-lrcflow", "-L/opt/rocm/lib", "-lamdhip64",
-           "-Wl,-rpath," + os.path.join(ROOT, "ripcurrents_amd"), "-Wl,-rpath,/opt/rocm/lib"]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert b.returncode == 0, b.stderr[-4000:]
+    exe = _cpp.build("test_ripmap", tmp_path, gxx=True)
     w, h, window, gx, gy, n = 97, 61, 3, 7, 5, 5
     r = subprocess.run([exe, str(w), str(h), str(window), str(gx), str(gy), str(n)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "test_ripmap: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

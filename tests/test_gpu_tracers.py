@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import _cpp
 import _tracers_ref as R
 from ripcurrents_amd import synth
 from ripcurrents_amd._lib import RcflowError
@@ -397,13 +398,7 @@ def test_trace_of_advect_points_drawn(ctx):
 def test_cpp_tracers_against_ctypes(ctx, tmp_path):
     """rc::Tracers (include/rcflow_module.hpp) compiled as tests/cpp's programs are and run on a seeded frame sequence; the
     vertices and the frame checksums it prints equal the ctypes session's on the same frames."""
-    exe = str(tmp_path / "test_tracers")
-    src = os.path.join(ROOT, "tests", "cpp", "test_tracers.cpp")
-    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"),
-           src, "-o", exe, "-L" + os.path.join(ROOT, "ripcurrents_amd"), "-lrcflow", "-L/opt/rocm/lib", "-lamdhip64",
-           "-Wl,-rpath," + os.path.join(ROOT, "ripcurrents_amd"), "-Wl,-rpath,/opt/rocm/lib"]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert b.returncode == 0, b.stderr[-4000:]
+    exe = _cpp.build("test_tracers", tmp_path, gxx=True)
     w, h, n = 320, 200, 6
     r = subprocess.run([exe, str(w), str(h), str(n)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "test_tracers: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

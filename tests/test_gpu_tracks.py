@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import _cpp
 import _regions_ref as R
 import _tracers_ref as TR
 import _tracks_ref as T
@@ -447,13 +448,7 @@ def test_push_refuses_fewer_records_than_max_regions(ctx):
 def test_cpp_tracks_against_the_statement(ctx, tmp_path):
     """rc::Tracks (include/rcflow_module.hpp) compiled as tests/cpp's programs are and run on seeded masks; what it prints
     equals the numpy statements on the same masks."""
-    exe = str(tmp_path / "test_tracks")
-    src = os.path.join(ROOT, "tests", "cpp", "test_tracks.cpp")
-    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"),
-           src, "-o", exe, "-L" + os.path.join(ROOT, "ripcurrents_amd"), "-lrcflow", "-L/opt/rocm/lib", "-lamdhip64",
-           "-Wl,-rpath," + os.path.join(ROOT, "ripcurrents_amd"), "-Wl,-rpath,/opt/rocm/lib"]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert b.returncode == 0, b.stderr[-4000:]
+    exe = _cpp.build("test_tracks", tmp_path, gxx=True)
     w, h, n = 200, 120, 9
     r = subprocess.run([exe, str(w), str(h), str(n)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "test_tracks: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import _cpp
 import _waves_ref as R
 from ripcurrents_amd._lib import RC_WAVES_LAUNCHES, RC_WAVES_MAX_STATE_BYTES, RcflowError, WavesParams
 from ripcurrents_amd.api import WAVE_CELL_DTYPE, WAVES_SUMMARY, Waves
@@ -348,14 +349,7 @@ def test_refusals_and_lifecycle(ctx):
 def test_cpp_waves_against_the_statement(ctx, tmp_path):
     """rc::Waves (include/rcflow_module.hpp) compiled with the flags of tests/cpp's test_module and run on frames it makes itself
     from integers; the summaries, bins, flags and checksums it prints equal the statement's."""
-    exe = str(tmp_path / "test_waves")
-    src = os.path.join(ROOT, "tests", "cpp", "test_waves.cpp")
-    hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc"
-    cmd = [hipcc, "-O2", "-std=c++17", "-x", "c++", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"),
-           src, "-o", exe, "-L" + os.path.join(ROOT, "ripcurrents_amd"), "-lrcflow", "-L/opt/rocm/lib", "-lamdhip64",
-           "-Wl,-rpath," + os.path.join(ROOT, "ripcurrents_amd"), "-Wl,-rpath,/opt/rocm/lib"]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert b.returncode == 0, b.stderr[-4000:]
+    exe = _cpp.build("test_waves", tmp_path)
     n = 40
     r = subprocess.run([exe, str(n)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "test_waves: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
