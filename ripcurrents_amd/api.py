@@ -53,17 +53,18 @@ REGION_DTYPE = np.dtype([("label", "<i4"), ("area", "<i4"), ("x0", "<i4"), ("y0"
                          ("cx", "<f8"), ("cy", "<f8"), ("var_major", "<f8"), ("var_minor", "<f8"), ("angle", "<f8"),
                          ("mean_fx", "<f4"), ("mean_fy", "<f4")])
 # the eight words of a regions summary, in order
+REGIONS_SUMMARY = ("components", "kept", "records", "foreground", "kept_pixels", "bad_pixels", "pushes", "largest_area")
+# the eight words of an FTLE, a plan view, a waves and a PIV summary, in order
 FTLE_SUMMARY = ("held", "valid", "mask", "stopped", "max_lam_bits", "pushes", "reserved0", "reserved1")
 PLANVIEW_SUMMARY = ("usable", "seen", "valid", "max_speed2_bits", "pushes", "reserved0", "reserved1", "reserved2")
 WAVES_SUMMARY = ("held", "participating", "nonempty", "with_depth", "pushes", "reserved0", "reserved1", "reserved2")
+PIV_SUMMARY = ("pairs", "cells", "valid", "flat", "lowpeak", "edge", "outliers", "pushes")
 # rc_wave_cell as a numpy record (32 bytes): what Context.waves_read returns
 WAVE_CELL_DTYPE = np.dtype([("bin", "<i4"), ("flags", "<i4"), ("freq_hz", "<f4"), ("kx", "<f4"), ("ky", "<f4"), ("celerity", "<f4"),
                             ("depth", "<f4"), ("quality", "<f4")])
-PIV_SUMMARY = ("pairs", "cells", "valid", "flat", "lowpeak", "edge", "outliers", "pushes")
 # rc_piv_cell as a numpy record (32 bytes): what Context.piv_read returns
 PIV_CELL_DTYPE = np.dtype([("dx", "<f4"), ("dy", "<f4"), ("peak", "<f4"), ("resid", "<f4"), ("ix", "<i4"), ("iy", "<i4"), ("flags", "<i4"),
                            ("pairs", "<i4")])
-REGIONS_SUMMARY = ("components", "kept", "records", "foreground", "kept_pixels", "bad_pixels", "pushes", "largest_area")
 # rc_track as a numpy record (128 bytes): what Context.tracks_read returns
 TRACK_DTYPE = np.dtype([("id", "<i8"), ("parent", "<i8"), ("first_push", "<i8"), ("area_sum", "<i8"), ("fx_sum", "<i8"), ("fy_sum", "<i8"),
                         ("m_sum", "<i8"), ("slot", "<i4"), ("label", "<i4"), ("flags", "<i4"), ("age", "<i4"), ("hits", "<i4"),
@@ -74,6 +75,11 @@ TRACKS_SUMMARY = ("alive", "confirmed", "born", "ended", "seen", "coasting", "un
 # rc_motion_cell as a numpy record (40 bytes): what Context.motion_read returns, per cell and for the frame
 MOTION_CELL_DTYPE = np.dtype([("angle", "<f8"), ("S", "<i8"), ("W", "<i8"), ("tsmax", "<f4"), ("n_masked", "<i4"), ("n_used", "<i4"),
                               ("peak_bin", "<i4")])
+# the name tables of _lib read the other way: the C ABI's number -> the name this layer takes and returns
+FIT_MODEL_NAMES = {v: k for k, v in FIT_MODELS.items()}
+FTLE_DIRECTION_NAMES = {v: k for k, v in FTLE_DIRECTIONS.items()}
+RIPMAP_SOURCE_NAMES = {v: k for k, v in RIPMAP_SOURCES.items()}
+TRACERS_MOVER_NAMES = {v: k for k, v in TRACERS_MOVERS.items()}
 
 
 def _params(pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags):
@@ -85,26 +91,44 @@ def _is_t(x):
     return isinstance(x, torch.Tensor)
 
 
+def _fits(t, device, dtype, shape=None, numel=None, dense=False):
+    """Whether `t` can go to a kernel as it is: a tensor on `device`, of `dtype`, of `shape` or of `numel` elements;
+    contiguous, or with dense=True an image (h, w[, ch]) of dense pixels whose row step covers a row and may be padded."""
+    if not (_is_t(t) and t.is_cuda and t.device == device and t.dtype == dtype):
+        return False
+    size, step = t.shape, t.stride()
+    if shape is not None and size != tuple(shape):
+        return False
+    if numel is not None and t.numel() != numel:
+        return False
+    if not dense:
+        return t.is_contiguous()
+    inner = 1                                      # the step of the contiguous tensor at this depth, from the innermost out
+    for k in range(len(size) - 1, 1, -1):
+        if step[k] != inner:
+            return False
+        inner *= size[k]
+    return step[1] == inner and step[0] >= inner * size[1]
+
+
 def _check_out(t, device, dtype, what, shape=None, numel=None, dense=False):
-    """A caller's output tensor: on `device` (its pointer goes to a kernel there), of `dtype`, of `shape` or of `numel`
-    elements; contiguous, or with dense=True dense pixels in rows that may be padded (a view is taken as it is)."""
-    ok = _is_t(t) and t.is_cuda and t.device == device and t.dtype == dtype
-    if ok and shape is not None:
-        ok = tuple(t.shape) == tuple(shape)
-    if ok and numel is not None:
-        ok = t.numel() == numel
-    if ok and dense:
-        inner = [1]                                # strides of the contiguous tensor below the row
-        for n in reversed(tuple(t.shape)[2:]):
-            inner.insert(0, inner[0] * n)
-        ok = list(t.stride()[1:]) == inner and t.stride(0) >= inner[0] * t.shape[1]
-    elif ok:
-        ok = t.is_contiguous()
-    if not ok:
+    """A caller's output tensor, held to _fits (a view is taken as it is) -> the tensor."""
+    if not _fits(t, device, dtype, shape, numel, dense):
         raise ValueError("%s must be a %s tensor on %s, %s, %s" % (
             what, str(dtype).replace("torch.", ""), device, "of shape %s" % (tuple(shape),) if shape is not None else "of %d" % numel,
             "with dense pixels" if dense else "contiguous"))
     return t
+
+
+def _record(rec, skip=()):
+    """A ctypes record as a dict, the fields of a nested `prm` beside the rest, without those named in `skip`."""
+    d = {}
+    for k, _ in rec._fields_:
+        if k == "prm":
+            d.update(_record(rec.prm, skip))
+        elif k not in skip:
+            d[k] = getattr(rec, k)
+    return d
 
 
 def _check_initial_flow(prev, flow):
@@ -443,23 +467,6 @@ class Context:
         self._bind(stream)
         check(self._lib.rcflow_analysis_reset(self._h, stream, w, h))
 
-    def _out_image(self, t, dtype, name, shape):
-        """An optional output image of dense pixels -> (pointer, byte step); (NULL, 0) for None."""
-        if t is None:
-            return C.c_void_p(None), 0
-        _check_out(t, self.device, dtype, name, shape=shape, dense=True)
-        return self._ptr(t), t.stride(0) * t.element_size()
-
-    def _out_array(self, t, dtype, name, numel):
-        """An optional contiguous output of `numel` elements -> its pointer; NULL for None."""
-        return C.c_void_p(None) if t is None else self._ptr(_check_out(t, self.device, dtype, name, numel=numel))
-
-    def _prims_out(self, out, n):
-        """The output of a *_prims method: n rc_draw_prim records, allocated here or the caller's, checked."""
-        if out is None:
-            return torch.empty((n, 32), dtype=torch.uint8, device=self.device)
-        return _check_out(out, self.device, torch.uint8, "out", numel=n * 32)
-
     def _flow(self, flow):
         flow = self._dev(flow, torch.float32)
         if flow.dim() != 3 or flow.shape[2] != 2 or flow.stride(2) != 1 or flow.stride(1) != 2:
@@ -735,6 +742,67 @@ class Context:
         check(fn(self._h, stream, self._ptr(f), f.stride(0), sw, sh, self._ptr(out), out.stride(0), dw, dh))
         return out
 
+    # ------------------------------------------------------------------ the per-slot products: what they share
+    def _in_image(self, t, dtype, name, shape, optional=False):
+        """An input image -> (pointer, byte step); with optional=True (NULL, 0) for None.  The one rule for it: a tensor on the
+        context's device, of `dtype` and of `shape` = (h, w[, ch]), with dense pixels and a row step of at least a row (rows
+        may be padded; a view is taken as it is).  The methods that also take numpy convert first (_dev, _img3)."""
+        if t is None and optional:
+            return C.c_void_p(None), 0
+        if not _fits(t, self.device, dtype, shape=shape, dense=True):
+            raise ValueError("%s must be a %s %s tensor on %s with dense pixels, as opened" % (
+                name, "x".join(str(n) for n in shape), str(dtype).replace("torch.", ""), self.device))
+        return self._ptr(t), t.stride(0) * t.element_size()
+
+    def _out_image(self, t, dtype, name, shape):
+        """An optional output image of dense pixels -> (pointer, byte step); (NULL, 0) for None."""
+        if t is None:
+            return C.c_void_p(None), 0
+        _check_out(t, self.device, dtype, name, shape=shape, dense=True)
+        return self._ptr(t), t.stride(0) * t.element_size()
+
+    def _out_array(self, t, dtype, name, numel):
+        """An optional contiguous output of `numel` elements -> its pointer; NULL for None."""
+        return C.c_void_p(None) if t is None else self._ptr(_check_out(t, self.device, dtype, name, numel=numel))
+
+    def _out_or_new(self, out, dtype, name, shape, dense=False, any_shape=False):
+        """The caller's output, checked, or a new tensor of `shape`.  The caller's is contiguous, or with dense=True an image
+        whose rows may be padded; with any_shape=True only its element count is held to `shape`."""
+        if out is None:
+            return torch.empty(tuple(shape), dtype=dtype, device=self.device)
+        if any_shape:
+            return _check_out(out, self.device, dtype, name, numel=int(np.prod(shape)))
+        return _check_out(out, self.device, dtype, name, shape=shape, dense=dense)
+
+    def _prims_out(self, out, n):
+        """The output of a *_prims method: n rc_draw_prim records."""
+        return self._out_or_new(out, torch.uint8, "out", (n, 32), any_shape=True)
+
+    def _summary(self, fn, stream, names, *args, bits=None):
+        """Calls a *_read entry point, whose last argument is the slot's summary of 8 int64, on the slot's stream -> the
+        summary as a dict by `names`.  bits = (key, new_name, transform): the word `key` holds the bits of a float32, and
+        transform of that float is added as new_name."""
+        summ = np.zeros(8, np.int64)
+        self._bind(stream)
+        check(fn(self._h, stream, *args, summ.ctypes.data_as(C.POINTER(C.c_longlong))))
+        out = dict(zip(names, (int(v) for v in summ)))
+        if bits is not None:
+            key, new_name, transform = bits
+            out[new_name] = float(transform(np.array([out[key]], np.uint32).view(np.float32)[0]))
+        return out
+
+    def _info(self, product, rec, stream):
+        """rcflow_<product>_info into the ctypes record `rec` -> rec; never blocks.  A push reads the geometry it holds its
+        arguments to from the record; <product>_info returns it as a dict."""
+        check(getattr(self._lib, "rcflow_%s_info" % product)(self._h, stream, C.byref(rec)))
+        return rec
+
+    def _lifecycle(self, product, verb, stream):
+        """rcflow_<product>_reset / _close.  Both bind the slot to the stream the pushes ran on first: the reset is queued
+        behind them, and the close waits for the pushes queued on that stream before it frees the state."""
+        self._bind(stream)
+        check(getattr(self._lib, "rcflow_%s_%s" % (product, verb))(self._h, stream))
+
     # ------------------------------------------------------------------ time-exposure images
     def _img3(self, a):
         """An (h, w, 3) uint8 device image with dense pixels; rows may have any step (views are taken as they are)."""
@@ -748,10 +816,7 @@ class Context:
     def _cvt_u8(self, fn, img, out, stream):
         a = self._img3(img)
         h, w = a.shape[:2]
-        if out is None:
-            out = torch.empty((h, w, 3), dtype=torch.uint8, device=self.device)
-        else:
-            _check_out(out, self.device, torch.uint8, "out", shape=a.shape, dense=True)
+        out = self._out_or_new(out, torch.uint8, "out", a.shape, dense=True)
         self._bind(stream)
         check(fn(self._h, stream, self._ptr(a), a.stride(0), w, h, self._ptr(out), out.stride(0)))
         return out
@@ -791,35 +856,26 @@ class Context:
         for every open product, as the reference shows after this frame.  `out` (optional) maps product names to
         preallocated images to write into, or to None to update that product's state without producing its image."""
         info = self.timex_info(stream)
-        f = self._img3(frame)
-        if tuple(f.shape[:2]) != (info["h"], info["w"]):
-            raise ValueError("frame must be %dx%dx3, as opened" % (info["h"], info["w"]))
+        shape = (info["h"], info["w"], 3)
+        f = self._img3(frame)       # held to the end of the call: it may be a copy made here
+        fp, fstep = self._in_image(f, torch.uint8, "frame", shape)
         out = dict(out or {})
         res = {}
         ptrs, steps = (C.c_void_p * 4)(), (C.c_size_t * 4)()
         for k, name in enumerate(TIMEX_PRODUCTS):
-            if name in out:
-                t = out[name]
-                if t is None:
-                    continue
-                _check_out(t, self.device, torch.uint8, "out[%r]" % name, shape=f.shape, dense=True)
-            elif name in info["products"]:
-                t = torch.empty(tuple(f.shape), dtype=torch.uint8, device=self.device)
-            else:
-                continue
-            res[name] = t
+            if out[name] is None if name in out else name not in info["products"]:
+                continue            # asked not to produce it, or not open and not asked for
+            res[name] = t = self._out_or_new(out.get(name), torch.uint8, "out[%r]" % name, shape, dense=True)
             ptrs[k], steps[k] = t.data_ptr(), t.stride(0)
         self._bind(stream)
-        check(self._lib.rcflow_timex_push_dev(self._h, stream, self._ptr(f), f.stride(0), ptrs, steps))
+        check(self._lib.rcflow_timex_push_dev(self._h, stream, fp, fstep, ptrs, steps))
         return res
 
     def timex_reset(self, stream=0):
-        self._bind(stream)
-        check(self._lib.rcflow_timex_reset(self._h, stream))
+        self._lifecycle("timex", "reset", stream)
 
     def timex_close(self, stream=0):
-        self._bind(stream)          # waits for the pushes queued on that stream before freeing
-        check(self._lib.rcflow_timex_close(self._h, stream))
+        self._lifecycle("timex", "close", stream)
 
     # ------------------------------------------------------------------ frame stabilisation
     def phase_correlate(self, a, b, window=True, out=None, stream=0):
@@ -832,10 +888,7 @@ class Context:
         ta = ta if ta.stride(1) == 1 else ta.contiguous()
         tb = tb if tb.stride(1) == 1 else tb.contiguous()
         h, w = ta.shape
-        if out is None:
-            out = torch.empty(3, dtype=torch.float64, device=self.device)
-        else:
-            _check_out(out, self.device, torch.float64, "out", numel=3)
+        out = self._out_or_new(out, torch.float64, "out", (3,), any_shape=True)
         self._bind(stream)
         check(self._lib.rcflow_phase_correlate_dev(self._h, stream, self._ptr(ta), ta.stride(0) * 4, self._ptr(tb),
                                                    tb.stride(0) * 4, w, h, 1 if window else 0, self._ptr(out)))
@@ -845,10 +898,7 @@ class Context:
         """warpAffine(frame, [1 0 -shift_x; 0 1 -shift_y]) on an 8UC3 frame (main.cpp:1749-1751): out(x, y) =
         frame(x + shift_x, y + shift_y), bilinear in 1/32 px, zero outside.  `out` (optional): the image to write."""
         f = self._img3(frame)
-        if out is None:
-            out = torch.empty(tuple(f.shape), dtype=torch.uint8, device=self.device)
-        else:
-            _check_out(out, self.device, torch.uint8, "out", shape=f.shape, dense=True)
+        out = self._out_or_new(out, torch.uint8, "out", f.shape, dense=True)
         self._bind(stream)
         check(self._lib.rcflow_warp_translate_bgr_dev(self._h, stream, self._ptr(f), f.stride(0), f.shape[1], f.shape[0],
                                                       self._ptr(out), out.stride(0), float(shift_x), float(shift_y)))
@@ -860,10 +910,7 @@ class Context:
         m = np.ascontiguousarray(np.asarray(M, np.float64)).reshape(-1)
         if m.size != nm:
             raise ValueError("expected a matrix of %d entries" % nm)
-        if out is None:
-            out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=self.device)
-        else:
-            _check_out(out, self.device, torch.uint8, "out", shape=(dh, dw, 3), dense=True)
+        out = self._out_or_new(out, torch.uint8, "out", (dh, dw, 3), dense=True)
         self._bind(stream)
         check(fn(self._h, stream, self._ptr(f), f.stride(0), f.shape[1], f.shape[0], self._ptr(out), out.stride(0), dw, dh,
                  m.ctypes.data_as(C.POINTER(C.c_double)), RC_WARP_INVERSE_MAP if inverse_map else 0))
@@ -912,10 +959,9 @@ class Context:
         used, cnt, frames = C.c_int(0), C.c_int(0), C.c_longlong(0)
         self._bind(stream)
         check(self._lib.rcflow_framestab_read_motion(self._h, stream, mo, C.byref(used), C.byref(cnt), sh, C.byref(frames)))
-        names = {v: k for k, v in FIT_MODELS.items()}
-        return dict(motion=np.array(mo[:]).reshape(2, 3), model_used=names.get(used.value), patches_used=cnt.value,
+        return dict(motion=np.array(mo[:]).reshape(2, 3), model_used=FIT_MODEL_NAMES.get(used.value), patches_used=cnt.value,
                     shifts=np.array(sh[:3 * n.value]).reshape(n.value, 3), frames_pushed=frames.value,
-                    rois=[tuple(rois[4 * k:4 * k + 4]) for k in range(n.value)], model=names[model.value],
+                    rois=[tuple(rois[4 * k:4 * k + 4]) for k in range(n.value)], model=FIT_MODEL_NAMES[model.value],
                     min_response=minr.value, anchor="first" if flags.value & RC_STAB_ANCHOR_FIRST else "previous")
 
     def framestab_info(self, stream=0):
@@ -933,18 +979,12 @@ class Context:
         `result` (optional): a contiguous float64 device tensor of 3 that receives shift_x, shift_y, response of this
         push; nothing is synchronised, so a row of a larger tensor per push collects a whole clip's track."""
         info = self.framestab_info(stream)
-        f = self._img3(frame)
-        if tuple(f.shape[:2]) != (info["h"], info["w"]):
-            raise ValueError("frame must be %dx%dx3, as opened" % (info["h"], info["w"]))
-        if out is None:
-            out = torch.empty(tuple(f.shape), dtype=torch.uint8, device=self.device)
-        else:
-            _check_out(out, self.device, torch.uint8, "out", shape=f.shape, dense=True)
-        rp = C.c_void_p(None)
-        if result is not None:
-            rp = self._ptr(_check_out(result, self.device, torch.float64, "result", numel=3))
+        f = self._img3(frame)       # held to the end of the call: it may be a copy made here
+        fp, fstep = self._in_image(f, torch.uint8, "frame", (info["h"], info["w"], 3))
+        out = self._out_or_new(out, torch.uint8, "out", f.shape, dense=True)
+        rp = self._out_array(result, torch.float64, "result", 3)
         self._bind(stream)
-        check(self._lib.rcflow_framestab_push_dev(self._h, stream, self._ptr(f), f.stride(0), self._ptr(out), out.stride(0), rp))
+        check(self._lib.rcflow_framestab_push_dev(self._h, stream, fp, fstep, self._ptr(out), out.stride(0), rp))
         return out
 
     def framestab_read(self, stream=0):
@@ -956,12 +996,10 @@ class Context:
         return (r[0], r[1], r[2]), n.value
 
     def framestab_reset(self, stream=0):
-        self._bind(stream)
-        check(self._lib.rcflow_framestab_reset(self._h, stream))
+        self._lifecycle("framestab", "reset", stream)
 
     def framestab_close(self, stream=0):
-        self._bind(stream)          # waits for the pushes queued on that stream before freeing
-        check(self._lib.rcflow_framestab_close(self._h, stream))
+        self._lifecycle("framestab", "close", stream)
 
     # ------------------------------------------------------------------ tracked corners, a robust fitted motion
     def corners(self, gray, cells=(16, 12), margin=12, min_score=1, pts=None, scores=None, stream=0):
@@ -974,14 +1012,8 @@ class Context:
         g = g if g.stride(1) == 1 else g.contiguous()
         h, w = g.shape
         n = int(cells[0]) * int(cells[1])
-        if pts is None:
-            pts = torch.empty((max(n, 0), 2), dtype=torch.float32, device=self.device)
-        else:
-            _check_out(pts, self.device, torch.float32, "pts", shape=(n, 2))
-        if scores is None:
-            scores = torch.empty((max(n, 0),), dtype=torch.int32, device=self.device)
-        else:
-            _check_out(scores, self.device, torch.int32, "scores", shape=(n,))
+        pts = self._out_or_new(pts, torch.float32, "pts", (max(n, 0), 2))
+        scores = self._out_or_new(scores, torch.int32, "scores", (max(n, 0),))
         self._bind(stream)
         check(self._lib.rcflow_corners_dev(self._h, stream, self._ptr(g), g.stride(0), w, h, int(cells[0]), int(cells[1]), int(margin),
                                            int(min_score), self._ptr(pts), self._ptr(scores)))
@@ -1020,8 +1052,7 @@ class Context:
         self.sync(stream)
         raw = res.cpu().numpy()
         ints = raw[9:].view(np.int32)
-        names = {v: k for k, v in FIT_MODELS.items()}
-        out = dict(T=raw[:9].reshape(3, 3).copy(), model_used=names.get(int(ints[0])), n_valid=int(ints[1]), n_inliers=int(ints[2]),
+        out = dict(T=raw[:9].reshape(3, 3).copy(), model_used=FIT_MODEL_NAMES.get(int(ints[0])), n_valid=int(ints[1]), n_inliers=int(ints[2]),
                    winner=int(ints[3]), inlier=inl[:n].cpu().numpy())
         if smp is not None:
             out["samples"] = smp.cpu().numpy()
@@ -1052,8 +1083,7 @@ class Context:
         pts, inl, sc = np.zeros((n, 4), np.float32), np.zeros(n, np.uint8), np.zeros(n, np.int32)
         check(self._lib.rcflow_framestab_read_tracks(self._h, stream, T, C.byref(used), C.byref(nv), C.byref(ni), pts.ctypes.data,
                                                      inl.ctypes.data, sc.ctypes.data, n, C.byref(cells), C.byref(frames)))
-        names = {v: k for k, v in FIT_MODELS.items()}
-        return dict(T=np.array(T[:]).reshape(3, 3), model_used=names.get(used.value), n_valid=nv.value, n_inliers=ni.value, pts=pts,
+        return dict(T=np.array(T[:]).reshape(3, 3), model_used=FIT_MODEL_NAMES.get(used.value), n_valid=nv.value, n_inliers=ni.value, pts=pts,
                     inlier=inl, scores=sc, frames_pushed=frames.value)
 
     # ------------------------------------------------------------------ the opposing-flow map
@@ -1077,7 +1107,7 @@ class Context:
         check(self._lib.rcflow_ripmap_info(self._h, stream, *[C.byref(x) for x in v], C.byref(k), C.byref(m), C.byref(frames),
                                            C.byref(nbytes)))
         w, h, window, gx, gy, source, flags = (x.value for x in v)
-        return dict(w=w, h=h, window=window, grid=(gx, gy), source={b: a for a, b in RIPMAP_SOURCES.items()}[source],
+        return dict(w=w, h=h, window=window, grid=(gx, gy), source=RIPMAP_SOURCE_NAMES[source],
                     wait_full=bool(flags & RC_RIPMAP_WAIT_FULL), min_opposition_cos2=k.value, min_cell_mag=m.value,
                     frames_pushed=frames.value, device_bytes=nbytes.value)
 
@@ -1094,12 +1124,9 @@ class Context:
         (mean x, mean y, angle to the frame's direction, opposed), summary 8 float64.  Nothing is synchronised."""
         info = self.ripmap_info(stream)
         h, w, (gx, gy) = info["h"], info["w"], info["grid"]
-        fp, fstep = C.c_void_p(None), 0
         if flow is not None:
             flow = self._dev(flow, torch.float32)
-            if flow.dim() != 3 or tuple(flow.shape) != (h, w, 2) or flow.stride(2) != 1 or flow.stride(1) != 2:
-                raise ValueError("flow must be %dx%dx2 float32 with dense pixels, as opened" % (h, w))
-            fp, fstep = self._ptr(flow), flow.stride(0) * 4
+        fp, fstep = self._in_image(flow, torch.float32, "flow", (h, w, 2), optional=True)
         hp, hstep = self._out_image(hsv, torch.uint8, "hsv", (h, w, 3))
         mp, mstep = self._out_image(mask, torch.uint8, "mask", (h, w))
         cp = C.c_void_p(None) if cells is None else self._ptr(_check_out(cells, self.device, torch.float32, "cells", shape=(gy, gx, 4)))
@@ -1110,10 +1137,7 @@ class Context:
     def ripmap_mean(self, out=None, stream=0):
         """The window mean as it stands -> HxWx2 float32 device tensor (a copy, queued on the slot's stream)."""
         info = self.ripmap_info(stream)
-        if out is None:
-            out = torch.empty((info["h"], info["w"], 2), dtype=torch.float32, device=self.device)
-        else:
-            _check_out(out, self.device, torch.float32, "out", shape=(info["h"], info["w"], 2), dense=True)
+        out = self._out_or_new(out, torch.float32, "out", (info["h"], info["w"], 2), dense=True)
         self._bind(stream)
         check(self._lib.rcflow_ripmap_mean_dev(self._h, stream, self._ptr(out), out.stride(0) * 4))
         return out
@@ -1133,12 +1157,10 @@ class Context:
                     max_magnitude=summary[6], sums=sums, frames_pushed=frames.value)
 
     def ripmap_reset(self, stream=0):
-        self._bind(stream)
-        check(self._lib.rcflow_ripmap_reset(self._h, stream))
+        self._lifecycle("ripmap", "reset", stream)
 
     def ripmap_close(self, stream=0):
-        self._bind(stream)          # waits for the pushes queued on that stream before freeing
-        check(self._lib.rcflow_ripmap_close(self._h, stream))
+        self._lifecycle("ripmap", "close", stream)
 
     # ------------------------------------------------------------------ motion templates
     def motion_open(self, w, h, diff_threshold=30, duration=1.0, delta1=0.25, delta2=1.0, grid=(1, 1), fresh=False, stream=0):
@@ -1155,11 +1177,10 @@ class Context:
     def motion_info(self, stream=0):
         """dict(w, h, diff_threshold, duration, delta1, delta2, grid, fresh, launches_per_push, pushes, last_timestamp,
         device_bytes); never blocks."""
-        i = MotionInfo()
-        check(self._lib.rcflow_motion_info(self._h, stream, C.byref(i)))
-        return dict(w=i.w, h=i.h, diff_threshold=i.prm.diff_threshold, duration=i.prm.duration, delta1=i.prm.delta1, delta2=i.prm.delta2,
-                    grid=(i.prm.grid_x, i.prm.grid_y), fresh=bool(i.prm.flags & RC_MOTION_FRESH), launches_per_push=i.launches_per_push,
-                    pushes=i.pushes, last_timestamp=i.last_timestamp, device_bytes=i.device_bytes)
+        i = self._info("motion", MotionInfo(), stream)
+        d = _record(i, skip=("flags", "grid_x", "grid_y"))
+        d.update(grid=(i.prm.grid_x, i.prm.grid_y), fresh=bool(i.prm.flags & RC_MOTION_FRESH))
+        return d
 
     def motion_push(self, gray, timestamp=None, mhi=None, orient=None, mask=None, vis=None, cells=None, frame=None, stream=0):
         """One gray frame (HxW uint8 device tensor, dense pixels, rows may be padded): three launches, nothing is synchronised.
@@ -1167,15 +1188,15 @@ class Context:
         device tensors, each optional: mhi and orient HxW float32, mask HxW uint8 (255 / 0), vis HxWx3 uint8 (the history as
         a grey picture), cells a contiguous uint8 tensor of grid_y * grid_x * 40 bytes (rc_motion_cell records,
         MOTION_CELL_DTYPE), frame one such record.  The records also stay on the slot for motion_read / motion_prims."""
-        info = self.motion_info(stream)
-        h, w, (gx, gy) = info["h"], info["w"], info["grid"]
-        _check_out(gray, self.device, torch.uint8, "gray", shape=(h, w), dense=True)
+        i = self._info("motion", MotionInfo(), stream)
+        h, w, gx, gy = i.h, i.w, i.prm.grid_x, i.prm.grid_y
+        gp, gstep = self._in_image(gray, torch.uint8, "gray", (h, w))
         images = (self._out_image(mhi, torch.float32, "mhi", (h, w)) + self._out_image(orient, torch.float32, "orient", (h, w)) +
                   self._out_image(mask, torch.uint8, "mask", (h, w)) + self._out_image(vis, torch.uint8, "vis", (h, w, 3)))
         cp = self._out_array(cells, torch.uint8, "cells", gx * gy * MOTION_CELL_DTYPE.itemsize)
         fp = self._out_array(frame, torch.uint8, "frame", MOTION_CELL_DTYPE.itemsize)
         self._bind(stream)
-        check(self._lib.rcflow_motion_push_dev(self._h, stream, self._ptr(gray), gray.stride(0),
+        check(self._lib.rcflow_motion_push_dev(self._h, stream, gp, gstep,
                                                RC_MOTION_AUTO_TIME if timestamp is None else float(timestamp), *images, cp, fp))
 
     def motion_read(self, stream=0):
@@ -1199,12 +1220,10 @@ class Context:
         return out
 
     def motion_reset(self, stream=0):
-        self._bind(stream)
-        check(self._lib.rcflow_motion_reset(self._h, stream))
+        self._lifecycle("motion", "reset", stream)
 
     def motion_close(self, stream=0):
-        self._bind(stream)          # waits for the pushes queued on that stream before freeing
-        check(self._lib.rcflow_motion_close(self._h, stream))
+        self._lifecycle("motion", "close", stream)
 
     def globalOrientation(self, prev, cur, stream=0):
         """The reference's call in one line (ripcurrents_module.cpp:319-359): the direction of the motion between two gray
@@ -1232,11 +1251,9 @@ class Context:
         padded) in place, in list order, by the rules of include/rcflow.h.  prims: a device uint8 / int32 tensor holding
         32-byte rc_draw_prim records, or a numpy array of DRAW_PRIM_DTYPE (copied to the device).  skipped: an optional
         one-element int64 device tensor that is increased by the number of skipped primitives."""
-        if not (_is_t(img) and img.is_cuda and img.device == self.device and img.dtype == torch.uint8 and img.dim() in (2, 3)):
-            raise ValueError("img must be a uint8 tensor on %s of shape HxW or HxWx3" % self.device)
-        ch = 1 if img.dim() == 2 else int(img.shape[2])
-        if ch not in (1, 3) or img.stride(1) != ch or (img.dim() == 3 and img.stride(2) != 1) or img.stride(0) < ch * img.shape[1]:
-            raise ValueError("img must have 1 or 3 channels and dense pixels")
+        ch = int(img.shape[2]) if _is_t(img) and img.dim() == 3 else 1
+        if not (_is_t(img) and img.dim() in (2, 3) and ch in (1, 3) and _fits(img, self.device, torch.uint8, dense=True)):
+            raise ValueError("img must be a uint8 tensor on %s of shape HxW or HxWx3, with dense pixels" % self.device)
         if isinstance(prims, np.ndarray):
             if prims.dtype != DRAW_PRIM_DTYPE:
                 raise ValueError("prims must have dtype DRAW_PRIM_DTYPE")
@@ -1309,11 +1326,9 @@ class Context:
 
     def tracers_info(self, stream=0):
         """dict of rc_tracers_info; never blocks."""
-        info = TracersInfo()
-        check(self._lib.rcflow_tracers_info(self._h, stream, C.byref(info)))
-        d = {k: getattr(info, k) for k, _ in TracersInfo._fields_}
-        d["mover"] = {b: a for a, b in TRACERS_MOVERS.items()}[info.mover]
-        d["primed"] = bool(info.primed)
+        info = self._info("tracers", TracersInfo(), stream)
+        d = _record(info)
+        d.update(mover=TRACERS_MOVER_NAMES[info.mover], primed=bool(info.primed))
         return d
 
     def tracers_push(self, gray=None, flow=None, canvas=None, stream=0):
@@ -1321,22 +1336,14 @@ class Context:
         device tensor, dense pixels), draws the lines into it in place.  gray: HxW uint8 (mover "lk"); flow: HxWx2 float32
         (mover "flow"; None: the field push_frame_host / frame_loop_step left on the slot).  Nothing is synchronised.
         Returns False from a priming push (mover "lk": the first frame), else True."""
-        info = self.tracers_info(stream)
-        h, w = info["h"], info["w"]
-        gp, gstep, fp, fstep, cp, cstep = C.c_void_p(None), 0, C.c_void_p(None), 0, C.c_void_p(None), 0
-        if info["mover"] == "lk":
-            g = self._dev(gray, torch.uint8)
-            if g.dim() != 2 or tuple(g.shape) != (h, w) or g.stride(1) != 1:
-                raise ValueError("gray must be %dx%d uint8 with dense pixels, as opened" % (h, w))
-            gp, gstep = self._ptr(g), g.stride(0)
-        elif flow is not None:
-            flow = self._dev(flow, torch.float32)
-            if flow.dim() != 3 or tuple(flow.shape) != (h, w, 2) or flow.stride(2) != 1 or flow.stride(1) != 2:
-                raise ValueError("flow must be %dx%dx2 float32 with dense pixels, as opened" % (h, w))
-            fp, fstep = self._ptr(flow), flow.stride(0) * 4
-        if canvas is not None:
-            _check_out(canvas, self.device, torch.uint8, "canvas", shape=(h, w, 3), dense=True)
-            cp, cstep = self._ptr(canvas), canvas.stride(0)
+        i = self._info("tracers", TracersInfo(), stream)
+        h, w = i.h, i.w
+        lk = i.mover == TRACERS_MOVERS["lk"]        # the mover's own input is looked at, the other one ignored
+        gray = self._dev(gray, torch.uint8) if lk else None
+        flow = self._dev(flow, torch.float32) if not lk and flow is not None else None
+        gp, gstep = self._in_image(gray, torch.uint8, "gray", (h, w), optional=not lk)
+        fp, fstep = self._in_image(flow, torch.float32, "flow", (h, w, 2), optional=True)
+        cp, cstep = self._out_image(canvas, torch.uint8, "canvas", (h, w, 3))
         self._bind(stream)
         return check(self._lib.rcflow_tracers_push_dev(self._h, stream, gp, gstep, fp, fstep, cp, cstep)) == 0
 
@@ -1364,12 +1371,10 @@ class Context:
         return host.numpy().view(DRAW_PRIM_DTYPE).reshape(-1).copy()
 
     def tracers_reset(self, stream=0):
-        self._bind(stream)
-        check(self._lib.rcflow_tracers_reset(self._h, stream))
+        self._lifecycle("tracers", "reset", stream)
 
     def tracers_close(self, stream=0):
-        self._bind(stream)          # waits for the pushes queued on that stream before freeing
-        check(self._lib.rcflow_tracers_close(self._h, stream))
+        self._lifecycle("tracers", "close", stream)
 
     # ------------------------------------------------------------------ flow map and FTLE
     def ftle_open(self, w, h, window=30, direction="backward", dt=1.0, spacing=1, threshold=0.1, vis_max=0.5, stream=0):
@@ -1386,12 +1391,10 @@ class Context:
     def ftle_info(self, stream=0):
         """dict(w, h, window, direction, dt, spacing, threshold, vis_max, launches_per_push, held, pushes, device_bytes);
         never blocks."""
-        i = FtleInfo()
-        check(self._lib.rcflow_ftle_info(self._h, stream, C.byref(i)))
-        names = {v: k for k, v in FTLE_DIRECTIONS.items()}
-        return dict(w=i.w, h=i.h, window=i.prm.window, direction=names[i.prm.direction], dt=i.prm.dt, spacing=i.prm.spacing,
-                    threshold=i.prm.threshold, vis_max=i.prm.vis_max, launches_per_push=i.launches_per_push, held=i.held, pushes=i.pushes,
-                    device_bytes=i.device_bytes)
+        i = self._info("ftle", FtleInfo(), stream)
+        d = _record(i, skip=("flags",))
+        d["direction"] = FTLE_DIRECTION_NAMES[d["direction"]]
+        return d
 
     def ftle_push(self, flow, map=None, steps=None, lam=None, ftle=None, mask=None, vis=None, summary=None, stream=0):
         """One flow field (HxWx2 float32 device tensor, dense pixels, rows may be padded) into the ring; nothing is
@@ -1399,39 +1402,30 @@ class Context:
         HxW int32, lam and ftle HxW float32, mask HxW uint8 (255 / 0: what regions_push takes), vis HxWx3 uint8, summary
         8 int64 (FTLE_SUMMARY).  Without any output the push is one launch that stores the field; with any it is
         RC_FTLE_LAUNCHES.  The summary also stays on the slot for ftle_read."""
-        info = self.ftle_info(stream)
-        h, w = info["h"], info["w"]
-        if not _is_t(flow) or not flow.is_cuda or flow.dtype != torch.float32 or flow.dim() != 3 or tuple(flow.shape) != (h, w, 2) or \
-                flow.stride(2) != 1 or flow.stride(1) != 2:
-            raise ValueError("flow must be a %dx%dx2 float32 device tensor with dense pixels, as opened" % (h, w))
+        i = self._info("ftle", FtleInfo(), stream)
+        h, w = i.h, i.w
+        fp, fstep = self._in_image(flow, torch.float32, "flow", (h, w, 2))
         images = (self._out_image(map, torch.float32, "map", (h, w, 2)) + self._out_image(steps, torch.int32, "steps", (h, w)) +
                   self._out_image(lam, torch.float32, "lam", (h, w)) + self._out_image(ftle, torch.float32, "ftle", (h, w)) +
                   self._out_image(mask, torch.uint8, "mask", (h, w)) + self._out_image(vis, torch.uint8, "vis", (h, w, 3)))
         sp = self._out_array(summary, torch.int64, "summary", 8)
         self._bind(stream)
-        check(self._lib.rcflow_ftle_push_dev(self._h, stream, self._ptr(flow), flow.stride(0) * 4, *images, sp))
+        check(self._lib.rcflow_ftle_push_dev(self._h, stream, fp, fstep, *images, sp))
 
     def ftle_read(self, stream=0):
         """Waits for the slot's stream -> dict of the summary of the last push that computed one (FTLE_SUMMARY names, and
         max_lam: the largest eigenvalue as a float); zeros before that."""
-        summ = np.zeros(8, np.int64)
-        self._bind(stream)
-        check(self._lib.rcflow_ftle_read(self._h, stream, summ.ctypes.data_as(C.POINTER(C.c_longlong))))
-        out = dict(zip(FTLE_SUMMARY, (int(v) for v in summ)))
-        out["max_lam"] = float(np.array([out["max_lam_bits"]], np.uint32).view(np.float32)[0])
-        return out
+        return self._summary(self._lib.rcflow_ftle_read, stream, FTLE_SUMMARY, bits=("max_lam_bits", "max_lam", float))
 
     def ftle_set(self, threshold, vis_max, stream=0):
         """threshold and vis_max from the next push on."""
         check(self._lib.rcflow_ftle_set(self._h, stream, float(threshold), float(vis_max)))
 
     def ftle_reset(self, stream=0):
-        self._bind(stream)
-        check(self._lib.rcflow_ftle_reset(self._h, stream))
+        self._lifecycle("ftle", "reset", stream)
 
     def ftle_close(self, stream=0):
-        self._bind(stream)          # waits for the pushes queued on that stream before freeing
-        check(self._lib.rcflow_ftle_close(self._h, stream))
+        self._lifecycle("ftle", "close", stream)
 
     # ------------------------------------------------------------------ plan view
     def planview_open(self, w, h, H, fx, fy, cx, cy, k1=0.0, k2=0.0, x0=0.0, y0=0.0, dx=1.0, dy=1.0, nx=1, ny=1, fps=1.0,
@@ -1450,11 +1444,10 @@ class Context:
 
     def planview_info(self, stream=0):
         """dict(w, h, the parameters (H a tuple of 9), launches_per_push, pushes, device_bytes); never blocks."""
-        i = PlanViewInfo()
-        check(self._lib.rcflow_planview_info(self._h, stream, C.byref(i)))
-        out = {k: getattr(i.prm, k) for k, _ in PlanViewParams._fields_ if k not in ("H", "flags")}
-        out.update(w=i.w, h=i.h, H=tuple(i.prm.H), launches_per_push=i.launches_per_push, pushes=i.pushes, device_bytes=i.device_bytes)
-        return out
+        i = self._info("planview", PlanViewInfo(), stream)
+        d = _record(i, skip=("H", "flags"))
+        d["H"] = tuple(i.prm.H)
+        return d
 
     def planview_push(self, flow=None, bgr=None, plan=None, mask=None, plan_bgr=None, summary=None, stream=0):
         """One launch; nothing is synchronised.  Inputs (device tensors with dense pixels, rows may be padded; either may be
@@ -1462,17 +1455,10 @@ class Context:
         NYxNXx2 float32 (metres per second; what ripmap_push, regions_push and ftle_push take), mask NYxNX uint8 (255 where
         the cell is valid, else 0) and summary 8 int64 (PLANVIEW_SUMMARY) need the field, plan_bgr NYxNXx3 uint8 the frame.
         The summary also stays on the slot for planview_read."""
-        info = self.planview_info(stream)
-        h, w, ny, nx = info["h"], info["w"], info["ny"], info["nx"]
-        ins = []
-        for t, dtype, name, ch in ((flow, torch.float32, "flow", 2), (bgr, torch.uint8, "bgr", 3)):
-            if t is None:
-                ins += [C.c_void_p(None), 0]
-                continue
-            if not _is_t(t) or not t.is_cuda or t.dtype != dtype or t.dim() != 3 or tuple(t.shape) != (h, w, ch) or t.stride(2) != 1 or \
-                    t.stride(1) != ch:
-                raise ValueError("%s must be a %dx%dx%d %s device tensor with dense pixels, as opened" % (name, h, w, ch, dtype))
-            ins += [self._ptr(t), t.stride(0) * t.element_size()]
+        i = self._info("planview", PlanViewInfo(), stream)
+        h, w, ny, nx = i.h, i.w, i.prm.ny, i.prm.nx
+        ins = (self._in_image(flow, torch.float32, "flow", (h, w, 2), optional=True) +
+               self._in_image(bgr, torch.uint8, "bgr", (h, w, 3), optional=True))
         images = (self._out_image(plan, torch.float32, "plan", (ny, nx, 2)) + self._out_image(mask, torch.uint8, "mask", (ny, nx)) +
                   self._out_image(plan_bgr, torch.uint8, "plan_bgr", (ny, nx, 3)))
         sp = self._out_array(summary, torch.int64, "summary", 8)
@@ -1482,12 +1468,7 @@ class Context:
     def planview_read(self, stream=0):
         """Waits for the slot's stream -> dict of the summary of the last push (PLANVIEW_SUMMARY names, and max_speed: the
         largest plan speed in metres per second as a float); zeros before the first."""
-        summ = np.zeros(8, np.int64)
-        self._bind(stream)
-        check(self._lib.rcflow_planview_read(self._h, stream, summ.ctypes.data_as(C.POINTER(C.c_longlong))))
-        out = dict(zip(PLANVIEW_SUMMARY, (int(v) for v in summ)))
-        out["max_speed"] = float(np.sqrt(np.array([out["max_speed2_bits"]], np.uint32).view(np.float32)[0]))
-        return out
+        return self._summary(self._lib.rcflow_planview_read, stream, PLANVIEW_SUMMARY, bits=("max_speed2_bits", "max_speed", np.sqrt))
 
     def planview_table(self, stream=0):
         """Waits for the slot's stream -> the table, NY x NX x 8 float32: U, V (the pixel of the cell's centre), m00, m01, m10,
@@ -1499,12 +1480,10 @@ class Context:
         return tab
 
     def planview_reset(self, stream=0):
-        self._bind(stream)
-        check(self._lib.rcflow_planview_reset(self._h, stream))
+        self._lifecycle("planview", "reset", stream)
 
     def planview_close(self, stream=0):
-        self._bind(stream)          # waits for the pushes queued on that stream before freeing
-        check(self._lib.rcflow_planview_close(self._h, stream))
+        self._lifecycle("planview", "close", stream)
 
     # ------------------------------------------------------------------ wave spectra
     def waves_open(self, w, h, window=256, bin_lo=1, bin_hi=1, spacing=2, grid_x=1, grid_y=1, min_pixels=1, fps=2.0, metres_per_pixel_x=1.0,
@@ -1522,12 +1501,8 @@ class Context:
 
     def waves_info(self, stream=0):
         """dict(w, h, the parameters, launches_per_push, bins, shift, held, pushes, device_bytes); never blocks."""
-        i = WavesInfo()
-        check(self._lib.rcflow_waves_info(self._h, stream, C.byref(i)))
-        out = {k: getattr(i.prm, k) for k, _ in WavesParams._fields_ if k != "flags"}
-        out.update(w=i.w, h=i.h, launches_per_push=i.launches_per_push, bins=i.bins, shift=i.shift, held=i.held, pushes=i.pushes,
-                   device_bytes=i.device_bytes)
-        return out
+        i = self._info("waves", WavesInfo(), stream)
+        return _record(i, skip=("flags",))
 
     def waves_push(self, gray, mask=None, cells=None, sums=None, bin_map=None, vis=None, summary=None, stream=0):
         """One grey frame (HxW uint8 device tensor, rows may be padded) into the ring and the spectrum; nothing is synchronised.
@@ -1535,16 +1510,9 @@ class Context:
         cells GYxGXx32 uint8 (rc_wave_cell records; view the host copy as WAVE_CELL_DTYPE), sums GYxGXxKx6 int64, bin_map HxW
         uint8, vis HxWx3 uint8, summary 8 int64 (WAVES_SUMMARY).  Without any output the push is one launch; with any it is at
         most RC_WAVES_LAUNCHES.  Records, sums and summary also stay on the slot for waves_read."""
-        info = self.waves_info(stream)
-        h, w, gx, gy, K = info["h"], info["w"], info["grid_x"], info["grid_y"], info["bins"]
-        ins = []
-        for t, name, need in ((gray, "gray", True), (mask, "mask", False)):
-            if t is None and not need:
-                ins += [C.c_void_p(None), 0]
-                continue
-            if not _is_t(t) or not t.is_cuda or t.dtype != torch.uint8 or tuple(t.shape) != (h, w) or t.stride(1) != 1:
-                raise ValueError("%s must be a %dx%d uint8 device tensor with dense pixels, as opened" % (name, h, w))
-            ins += [self._ptr(t), t.stride(0)]
+        i = self._info("waves", WavesInfo(), stream)
+        h, w, gx, gy, K = i.h, i.w, i.prm.grid_x, i.prm.grid_y, i.bins
+        ins = self._in_image(gray, torch.uint8, "gray", (h, w)) + self._in_image(mask, torch.uint8, "mask", (h, w), optional=True)
         cp = self._out_array(cells, torch.uint8, "cells", gy * gx * 32)
         sp = self._out_array(sums, torch.int64, "sums", gy * gx * K * 6)
         images = self._out_image(bin_map, torch.uint8, "bin_map", (h, w)) + self._out_image(vis, torch.uint8, "vis", (h, w, 3))
@@ -1559,10 +1527,7 @@ class Context:
         gx, gy, K = info["grid_x"], info["grid_y"], info["bins"]
         cells = np.zeros((gy, gx), WAVE_CELL_DTYPE)
         sums = np.zeros((gy, gx, K, 6), np.int64)
-        summ = np.zeros(8, np.int64)
-        self._bind(stream)
-        check(self._lib.rcflow_waves_read(self._h, stream, cells.ctypes.data, sums.ctypes.data, summ.ctypes.data_as(C.POINTER(C.c_longlong))))
-        return cells, sums, dict(zip(WAVES_SUMMARY, (int(v) for v in summ)))
+        return cells, sums, self._summary(self._lib.rcflow_waves_read, stream, WAVES_SUMMARY, cells.ctypes.data, sums.ctypes.data)
 
     def waves_spectrum(self, stream=0):
         """Waits for the slot's stream -> the accumulators, K x H x W x 2 int32 (re, im); for tests."""
@@ -1584,12 +1549,10 @@ class Context:
         check(self._lib.rcflow_waves_set(self._h, stream, float(tanh_max), int(min_pixels), float(vis_max_depth)))
 
     def waves_reset(self, stream=0):
-        self._bind(stream)
-        check(self._lib.rcflow_waves_reset(self._h, stream))
+        self._lifecycle("waves", "reset", stream)
 
     def waves_close(self, stream=0):
-        self._bind(stream)          # waits for the pushes queued on that stream before freeing
-        check(self._lib.rcflow_waves_close(self._h, stream))
+        self._lifecycle("waves", "close", stream)
 
     # ------------------------------------------------------------------ ensemble PIV
     def piv_open(self, w, h, window=32, range=8, step=16, ensemble=1, replace=False, min_peak=0.25, median_eps=0.1, median_thr=2.0,
@@ -1605,12 +1568,10 @@ class Context:
 
     def piv_info(self, stream=0):
         """dict(w, h, the parameters, replace, grid_x, grid_y, launches_per_push, pairs, pushes, device_bytes); never blocks."""
-        i = PivInfo()
-        check(self._lib.rcflow_piv_info(self._h, stream, C.byref(i)))
-        out = {k: getattr(i.prm, k) for k, _ in PivParams._fields_ if k != "flags"}
-        out.update(replace=bool(i.prm.flags & RC_PIV_REPLACE), w=i.w, h=i.h, grid_x=i.grid_x, grid_y=i.grid_y,
-                   launches_per_push=i.launches_per_push, pairs=i.pairs, pushes=i.pushes, device_bytes=i.device_bytes)
-        return out
+        i = self._info("piv", PivInfo(), stream)
+        d = _record(i, skip=("flags",))
+        d["replace"] = bool(i.prm.flags & RC_PIV_REPLACE)
+        return d
 
     def piv_push(self, gray, cells=None, field=None, vis=None, summary=None, stream=0):
         """One grey frame (HxW uint8 device tensor, rows may be padded), correlated against the slot's previous one; nothing is
@@ -1618,26 +1579,22 @@ class Context:
         the host copy as PIV_CELL_DTYPE), field GYxGXx2 float32 (pixels per frame: the small flow field ripmap_push and the
         others take), vis HxWx3 uint8, summary 8 int64 (PIV_SUMMARY).  Without any output the push is one launch; with any it
         is RC_PIV_LAUNCHES.  Records and summary also stay on the slot for piv_read."""
-        info = self.piv_info(stream)
-        h, w, gx, gy = info["h"], info["w"], info["grid_x"], info["grid_y"]
-        if not _is_t(gray) or not gray.is_cuda or gray.dtype != torch.uint8 or tuple(gray.shape) != (h, w) or gray.stride(1) != 1:
-            raise ValueError("gray must be a %dx%d uint8 device tensor with dense pixels, as opened" % (h, w))
+        i = self._info("piv", PivInfo(), stream)
+        h, w, gx, gy = i.h, i.w, i.grid_x, i.grid_y
+        gp = self._in_image(gray, torch.uint8, "gray", (h, w))
         cp = self._out_array(cells, torch.uint8, "cells", gy * gx * 32)
         fp = self._out_image(field, torch.float32, "field", (gy, gx, 2))
         vp = self._out_image(vis, torch.uint8, "vis", (h, w, 3))
         up = self._out_array(summary, torch.int64, "summary", 8)
         self._bind(stream)
-        check(self._lib.rcflow_piv_push_dev(self._h, stream, self._ptr(gray), gray.stride(0), cp, *fp, *vp, up))
+        check(self._lib.rcflow_piv_push_dev(self._h, stream, *gp, cp, *fp, *vp, up))
 
     def piv_read(self, stream=0):
         """Waits for the slot's stream -> (cells GYxGX PIV_CELL_DTYPE, dict of the summary by PIV_SUMMARY names) of the last
         push that computed them; zeros before that."""
         info = self.piv_info(stream)
         cells = np.zeros((info["grid_y"], info["grid_x"]), PIV_CELL_DTYPE)
-        summ = np.zeros(8, np.int64)
-        self._bind(stream)
-        check(self._lib.rcflow_piv_read(self._h, stream, cells.ctypes.data, summ.ctypes.data_as(C.POINTER(C.c_longlong))))
-        return cells, dict(zip(PIV_SUMMARY, (int(v) for v in summ)))
+        return cells, self._summary(self._lib.rcflow_piv_read, stream, PIV_SUMMARY, cells.ctypes.data)
 
     def piv_sums(self, stream=0):
         """Waits for the slot's stream -> (the accumulators GYxGXxDxDx3 int64: Tab, Tb, Tbb per displacement; GYxGXx2 int64: Ta,
@@ -1654,12 +1611,10 @@ class Context:
         check(self._lib.rcflow_piv_set(self._h, stream, float(min_peak), float(median_eps), float(median_thr), float(vis_max)))
 
     def piv_reset(self, stream=0):
-        self._bind(stream)
-        check(self._lib.rcflow_piv_reset(self._h, stream))
+        self._lifecycle("piv", "reset", stream)
 
     def piv_close(self, stream=0):
-        self._bind(stream)          # waits for the pushes queued on that stream before freeing
-        check(self._lib.rcflow_piv_close(self._h, stream))
+        self._lifecycle("piv", "close", stream)
 
     # ------------------------------------------------------------------ rip regions
     def regions_open(self, w, h, connectivity=8, min_area=1, max_regions=1024, stream=0):
@@ -1672,9 +1627,8 @@ class Context:
 
     def regions_info(self, stream=0):
         """dict of rc_regions_info; never blocks."""
-        info = RegionsInfo()
-        check(self._lib.rcflow_regions_info(self._h, stream, C.byref(info)))
-        return {k: getattr(info, k) for k, _ in RegionsInfo._fields_}
+        info = self._info("regions", RegionsInfo(), stream)
+        return _record(info)
 
     def regions_set(self, min_area, stream=0):
         """min_area from the next push on."""
@@ -1686,21 +1640,18 @@ class Context:
         Outputs are preallocated device tensors, each optional: labels HxW int32, mask_out HxW uint8 (255 inside a kept
         component; may be `mask` itself), regions a contiguous uint8 tensor of max_regions * 144 bytes (rc_region records,
         REGION_DTYPE), summary 8 int64.  The records and the summary also stay on the slot for regions_read / regions_prims."""
-        info = self.regions_info(stream)
-        h, w = info["h"], info["w"]
-        _check_out(mask, self.device, torch.uint8, "mask", shape=(h, w), dense=True)
-        fp, fstep = C.c_void_p(None), 0
+        i = self._info("regions", RegionsInfo(), stream)
+        h, w = i.h, i.w
+        mp, mstep = self._in_image(mask, torch.uint8, "mask", (h, w))
         if flow is not None:
             flow = self._dev(flow, torch.float32)
-            if flow.dim() != 3 or tuple(flow.shape) != (h, w, 2) or flow.stride(2) != 1 or flow.stride(1) != 2:
-                raise ValueError("flow must be %dx%dx2 float32 with dense pixels, as opened" % (h, w))
-            fp, fstep = self._ptr(flow), flow.stride(0) * 4
+        fp, fstep = self._in_image(flow, torch.float32, "flow", (h, w, 2), optional=True)
         lp, lstep = self._out_image(labels, torch.int32, "labels", (h, w))
         op, ostep = self._out_image(mask_out, torch.uint8, "mask_out", (h, w))
-        rp = self._out_array(regions, torch.uint8, "regions", info["max_regions"] * REGION_DTYPE.itemsize)
+        rp = self._out_array(regions, torch.uint8, "regions", i.max_regions * REGION_DTYPE.itemsize)
         sp = self._out_array(summary, torch.int64, "summary", 8)
         self._bind(stream)
-        check(self._lib.rcflow_regions_push_dev(self._h, stream, self._ptr(mask), mask.stride(0), fp, fstep, lp, lstep, op, ostep, rp, sp))
+        check(self._lib.rcflow_regions_push_dev(self._h, stream, mp, mstep, fp, fstep, lp, lstep, op, ostep, rp, sp))
 
     def regions_prims(self, color=0x00ffff, thickness=1, disc_radius=3, flow_scale=0.0, out=None, stream=0):
         """The records of the last push as 6 * max_regions primitives for draw() -> a device uint8 tensor of rc_draw_prim
@@ -1717,18 +1668,15 @@ class Context:
         """Waits for the slot's stream -> (records of the last push as a numpy array of REGION_DTYPE, dict of the summary
         with the names of REGIONS_SUMMARY)."""
         cap = self.regions_info(stream)["max_regions"]
-        rec, n, summ = np.zeros(cap, REGION_DTYPE), C.c_int(0), np.zeros(8, np.int64)
-        self._bind(stream)
-        check(self._lib.rcflow_regions_read(self._h, stream, rec.ctypes.data, cap, C.byref(n), summ.ctypes.data))
-        return rec[:n.value].copy(), dict(zip(REGIONS_SUMMARY, (int(v) for v in summ)))
+        rec, n = np.zeros(cap, REGION_DTYPE), C.c_int(0)
+        summ = self._summary(self._lib.rcflow_regions_read, stream, REGIONS_SUMMARY, rec.ctypes.data, cap, C.byref(n))
+        return rec[:n.value].copy(), summ
 
     def regions_reset(self, stream=0):
-        self._bind(stream)
-        check(self._lib.rcflow_regions_reset(self._h, stream))
+        self._lifecycle("regions", "reset", stream)
 
     def regions_close(self, stream=0):
-        self._bind(stream)          # waits for the pushes queued on that stream before freeing
-        check(self._lib.rcflow_regions_close(self._h, stream))
+        self._lifecycle("regions", "close", stream)
 
     # ------------------------------------------------------------------ rip tracks
     def tracks_open(self, w, h, max_regions=1024, max_tracks=64, min_overlap=1, max_misses=2, min_hits=3, stream=0):
@@ -1742,11 +1690,8 @@ class Context:
 
     def tracks_info(self, stream=0):
         """dict of rc_tracks_info, the parameters beside the rest; never blocks."""
-        info = TracksInfo()
-        check(self._lib.rcflow_tracks_info(self._h, stream, C.byref(info)))
-        d = {k: getattr(info, k) for k, _ in TracksInfo._fields_ if k != "prm"}
-        d.update({k: getattr(info.prm, k) for k, _ in TracksParams._fields_})
-        return d
+        info = self._info("tracks", TracksInfo(), stream)
+        return _record(info)
 
     def tracks_push(self, labels, regions, regions_summary, tracks=None, track_of_label=None, mask_out=None, summary=None, stream=0):
         """One set of regions, as regions_push left it on the device: labels HxW int32 (dense pixels, rows may be padded),
@@ -1756,20 +1701,20 @@ class Context:
         max_tracks * 128 bytes (rc_track records, TRACK_DTYPE), track_of_label max_regions + 1 int32, mask_out HxW uint8
         (255 inside the regions of confirmed tracks), summary 8 int64.  The table and the summary also stay on the slot for
         tracks_read / tracks_prims."""
-        info = self.tracks_info(stream)
-        h, w = info["h"], info["w"]
-        _check_out(labels, self.device, torch.int32, "labels", shape=(h, w), dense=True)
+        i = self._info("tracks", TracksInfo(), stream)
+        h, w, max_regions = i.h, i.w, i.prm.max_regions
+        lbl = self._in_image(labels, torch.int32, "labels", (h, w))
         ok = _is_t(regions) and regions.is_cuda and regions.device == self.device and regions.dtype == torch.uint8 and regions.is_contiguous()
-        if not ok or regions.numel() % REGION_DTYPE.itemsize or regions.numel() < info["max_regions"] * REGION_DTYPE.itemsize:
+        if not ok or regions.numel() % REGION_DTYPE.itemsize or regions.numel() < max_regions * REGION_DTYPE.itemsize:
             raise ValueError("regions must be a contiguous uint8 tensor of at least max_regions (%d) rc_region records on %s" % (
-                info["max_regions"], self.device))
+                max_regions, self.device))
         _check_out(regions_summary, self.device, torch.int64, "regions_summary", numel=8)
-        tp = self._out_array(tracks, torch.uint8, "tracks", info["max_tracks"] * TRACK_DTYPE.itemsize)
-        lp = self._out_array(track_of_label, torch.int32, "track_of_label", info["max_regions"] + 1)
+        tp = self._out_array(tracks, torch.uint8, "tracks", i.prm.max_tracks * TRACK_DTYPE.itemsize)
+        lp = self._out_array(track_of_label, torch.int32, "track_of_label", max_regions + 1)
         op, ostep = self._out_image(mask_out, torch.uint8, "mask_out", (h, w))
         sp = self._out_array(summary, torch.int64, "summary", 8)
         self._bind(stream)
-        check(self._lib.rcflow_tracks_push_dev(self._h, stream, self._ptr(labels), labels.stride(0) * 4, self._ptr(regions),
+        check(self._lib.rcflow_tracks_push_dev(self._h, stream, *lbl, self._ptr(regions),
                                                self._ptr(regions_summary), tp, lp, op, ostep, sp))
 
     def tracks_prims(self, color=0x00ffff, thickness=1, disc_radius=3, out=None, stream=0):
@@ -1786,18 +1731,14 @@ class Context:
         """Waits for the slot's stream -> (the table as a numpy array of max_tracks TRACK_DTYPE records in slot order, the
         footprint as an HxW int32 array, dict of the summary with the names of TRACKS_SUMMARY)."""
         info = self.tracks_info(stream)
-        tab, foot, summ = np.zeros(info["max_tracks"], TRACK_DTYPE), np.zeros((info["h"], info["w"]), np.int32), np.zeros(8, np.int64)
-        self._bind(stream)
-        check(self._lib.rcflow_tracks_read(self._h, stream, tab.ctypes.data, len(tab), foot.ctypes.data, summ.ctypes.data))
-        return tab, foot, dict(zip(TRACKS_SUMMARY, (int(v) for v in summ)))
+        tab, foot = np.zeros(info["max_tracks"], TRACK_DTYPE), np.zeros((info["h"], info["w"]), np.int32)
+        return tab, foot, self._summary(self._lib.rcflow_tracks_read, stream, TRACKS_SUMMARY, tab.ctypes.data, len(tab), foot.ctypes.data)
 
     def tracks_reset(self, stream=0):
-        self._bind(stream)
-        check(self._lib.rcflow_tracks_reset(self._h, stream))
+        self._lifecycle("tracks", "reset", stream)
 
     def tracks_close(self, stream=0):
-        self._bind(stream)          # waits for the pushes queued on that stream before freeing
-        check(self._lib.rcflow_tracks_close(self._h, stream))
+        self._lifecycle("tracks", "close", stream)
 
     def _an_size(self, stream):
         w, h = C.c_int(0), C.c_int(0)
@@ -1917,22 +1858,44 @@ class Context:
         return {names[i].decode(): ms[i] for i in range(n)}
 
 
-class Waves:
-    """The wave spectra of one slot as an object: Context.waves_* with the context and the slot bound.  Opens on construction,
-    closes on close() or at the end of a with block."""
+class _Product:
+    """One per-slot product as an object: Context.<product>_* with the context and the slot bound.  Opens on construction,
+    closes on close() or at the end of a with block.  A subclass names its product and adds what only that product has."""
+    product = None
 
     def __init__(self, ctx, w, h, stream=0, **params):
         self.ctx, self.stream = ctx, stream
-        ctx.waves_open(w, h, stream=stream, **params)
+        self._method("open")(w, h, stream=stream, **params)
+
+    def _method(self, verb):
+        return getattr(self.ctx, "%s_%s" % (self.product, verb))
 
     def push(self, gray, **outputs):
-        self.ctx.waves_push(gray, stream=self.stream, **outputs)
+        self._method("push")(gray, stream=self.stream, **outputs)
 
     def read(self):
-        return self.ctx.waves_read(self.stream)
+        return self._method("read")(self.stream)
 
     def info(self):
-        return self.ctx.waves_info(self.stream)
+        return self._method("info")(self.stream)
+
+    def reset(self):
+        self._method("reset")(self.stream)
+
+    def close(self):
+        self._method("close")(self.stream)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class Waves(_Product):
+    """The wave spectra of one slot as an object: Context.waves_* with the context and the slot bound.  Opens on construction,
+    closes on close() or at the end of a with block."""
+    product = "waves"
 
     def spectrum(self):
         return self.ctx.waves_spectrum(self.stream)
@@ -1943,53 +1906,17 @@ class Waves:
     def set(self, tanh_max, min_pixels, vis_max_depth):
         self.ctx.waves_set(tanh_max, min_pixels, vis_max_depth, self.stream)
 
-    def reset(self):
-        self.ctx.waves_reset(self.stream)
 
-    def close(self):
-        self.ctx.waves_close(self.stream)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
-class Piv:
+class Piv(_Product):
     """The ensemble PIV of one slot as an object: Context.piv_* with the context and the slot bound.  Opens on construction,
     closes on close() or at the end of a with block."""
-
-    def __init__(self, ctx, w, h, stream=0, **params):
-        self.ctx, self.stream = ctx, stream
-        ctx.piv_open(w, h, stream=stream, **params)
-
-    def push(self, gray, **outputs):
-        self.ctx.piv_push(gray, stream=self.stream, **outputs)
-
-    def read(self):
-        return self.ctx.piv_read(self.stream)
-
-    def info(self):
-        return self.ctx.piv_info(self.stream)
+    product = "piv"
 
     def sums(self):
         return self.ctx.piv_sums(self.stream)
 
     def set(self, min_peak, median_eps, median_thr, vis_max):
         self.ctx.piv_set(min_peak, median_eps, median_thr, vis_max, self.stream)
-
-    def reset(self):
-        self.ctx.piv_reset(self.stream)
-
-    def close(self):
-        self.ctx.piv_close(self.stream)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 def _alias_tensor(ptr, n, dtype, device):
