@@ -1537,6 +1537,175 @@ int rcflow_piv_close(rc_ctx* ctx, int stream);
 /* never blocks; RC_ESTATE when nothing is open, RC_EINVAL without a buffer */
 int rcflow_piv_info(rc_ctx* ctx, int stream, rc_piv_info* info);
 
+/* ------------------------------------------------------------------ transects: time stacks, line velocity, flux and jets
+ * Every product above answers "what does the field look like?".  This one answers what is asked once a rip has been found:
+ * how strong is it, how wide is its neck, how does it pulse?  In shore-camera work those numbers come from lines laid across
+ * the picture ("pixel instruments"): the grey values along a line, one row per frame, are a time stack; the cross-line velocity
+ * along an alongshore line against time shows the pulsation; its integral along the line is the offshore transport, and the
+ * stretches where it exceeds a threshold are the rip necks; the slope of the streaks in a time stack gives the along-line drift
+ * of foam.  The reference has no such product.  tests/_transects_ref.py states the following in numpy.  Every integer is exact;
+ * every float operation is rounded on its own.
+ *
+ *  Geometry (host, in double, once; rcflow_transects_plan gives it without a context).  Line i runs from (x0, y0) to (x1, y1) in
+ *  pixels and has n samples, 2..RC_TRANSECTS_MAX_SAMPLES; at most RC_TRANSECTS_MAX_LINES lines, S = sum of n at most
+ *  RC_TRANSECTS_MAX_TOTAL.  Sample j: t = j / (n - 1), x = x0 + (x1 - x0) t, X = lrint(16 x), Y likewise: positions are
+ *  quantised to 1/16 pixel; 0 <= X <= 16 (w - 1) and 0 <= Y <= 16 (h - 1).  The endpoints are the floats' values taken to
+ *  double.  dx = x1 - x0, dy = y1 - y0, len = hypot(dx, dy) > 0; tangent e = (dx, dy) / len, normal nrm = (dy, -dx) / len, both
+ *  stored as floats: positive cross-line velocity is to the left of the direction of travel as the picture shows it (y down): a
+ *  line drawn left to right has its positive side up the picture.  ds = len * metres_per_pixel / (n - 1) (left to right);
+ *  scale = (float)(metres_per_pixel * fps).  The table is in line order, `first` of a line being the sum of the n before it.
+ *  1. Every push ("transects@0", one launch, a block per line).  c = pushes mod T.  Per sample, ix = X >> 4, fx = X & 15, iy and
+ *     fy likewise, ix1 = min(ix + 1, w - 1), iy1 likewise; p00 = (ix, iy), p10 = (ix1, iy), p01 = (ix, iy1), p11 = (ix1, iy1).
+ *     GRAY: g = ((16 - fx) (16 - fy) p00 + fx (16 - fy) p10 + (16 - fx) fy p01 + fx fy p11 + 128) >> 8 into ring_g[c][s].
+ *     FLOW: a = fx / 16.f, b = fy / 16.f; per component top = p00 + a (p10 - p00), bot = p01 + a (p11 - p01),
+ *     val = top + b (bot - top); ut = (u ex + v ey) scale, un = (u nx + v ny) scale into ring_f[c][s].
+ *     Correlation (D = range >= 1): the interior of a line is j in [D, n - D).  For a pair of rows (A older, B pushed lag pushes
+ *     later), sums over the interior, d in -D..D: Tab[d] = sum A[j] B[j + d], Tb[d] = sum B[j + d], Tbb[d] = sum B[j + d]^2,
+ *     Ta = sum A[j], Taa = sum A[j]^2.  The int64 accumulators of a line are at all times these sums over every pair (r, r + lag)
+ *     whose two rows the ring holds: pairs = max(0, min(pushes, T) - lag) of them.  The pushed row's pair is added; the pair whose
+ *     older row the push overwrites is computed again from the ring rows and taken off, before the slot is written: no per-pair
+ *     memory.  With D = 0 nothing is correlated and pairs is 0.
+ *  2. Records ("transects@1", a block per line, when d_records, d_sums, d_profile or d_summary is asked for).
+ *     Velocity along the line.  N = pairs (n - 2 D); in int64, exact, below 2^61: num = N Tab - Ta Tb, va = N Taa - Ta^2,
+ *     vb = N Tbb - Tb^2; s[d] = (va > 0 && vb > 0) ? ((double)num * fabs((double)num)) / ((double)va * (double)vb) : 0.
+ *     RC_TRANSECTS_EMPTY when pairs = 0, RC_TRANSECTS_FLAT when every s is 0: peak_shift, v_along, corr_peak are 0.  Else q is
+ *     the first largest s (d = q - D), r = copysign(sqrt|s|, s); when 0 < q < 2 D and den = (r[q-1] - 2 r[q]) + r[q+1] < 0,
+ *     delta = 0.5 (r[q-1] - r[q+1]) / den, else delta = 0; q at the rim also sets RC_TRANSECTS_EDGE.  peak_shift = q - D,
+ *     v_along = (float)((((q - D) + delta) * ds * fps) / lag), corr_peak = (float)r[q].  Foam that moves towards (x1, y1) gives
+ *     a positive v_along, in metres per second.
+ *     Transport across the line (FLOW).  held = min(pushes, T).  Per sample and component the window mean is the sequential
+ *     float sum over the held rows, oldest first, divided by (float)held: d_profile, S x (ut, un).  Q(x) = (int64)rint((double)x
+ *     * 65536).  A sample either of whose means is not finite or reaches 2^20 in magnitude is bad: counted, part of nothing.
+ *     Per line, exact: Fpos = sum max(Q(un), 0), Fneg = sum min(Q(un), 0), Ft = sum Q(ut), n_valid.  A sample is IN when it
+ *     is not bad and Q(un) >= Q(jet_min) (of the double); a jet is a maximal run of consecutive IN samples of one line.  The
+ *     record keeps the number of jets and, for the jet of the largest sum of Q(un) (the first winning ties): start, length,
+ *     sum, the largest Q(un) in it and the sample that has it (the first).  Without FLOW every one of these is 0.
+ *     Record: mean_along = (float)(((double)Ft / 65536) / n_valid), mean_cross likewise from Fpos + Fneg (0 for n_valid = 0);
+ *     flux_out = (float)(((double)Fpos / 65536) * ds), flux_in from Fneg, jet_flux from the jet's sum, in m^2/s;
+ *     jet_peak = (float)((double)peak / 65536).  d_sums, 16 int64 per line: Fpos, Fneg, Ft, n_valid, bad, jets, jet_start,
+ *     jet_len, jet sum, jet peak, jet_peak_at, N, num, va, vb (of q; 0 when EMPTY or FLAT), q.
+ *     Summary, 8 int64: held | pairs | lines with a velocity (neither EMPTY nor FLAT) | lines with a jet | jets | bad samples |
+ *     pushes since open / reset | 0.
+ *  3. Pictures ("transects@2", when d_stack or d_hov is asked for), S wide and T high: row r is the r-th oldest held row, so the
+ *     newest is lowest; rows past held are 0.  d_stack (8UC1, needs GRAY): the grey ring.  d_hov (8UC3, needs FLOW): entry i of
+ *     rcflow_jet_lut, i = rint(un / (float)vis_max * 127.5f + 127.5f) saturated to 0..255, un from the ring; black where un is
+ *     not finite.
+ * The rules that are not obvious from the above.  RC_TRANSECTS_MAX_TOTAL is RC_TRANSECTS_MAX_LINES * RC_TRANSECTS_MAX_SAMPLES:
+ * every line may be of full length, and it is RC_TRANSECTS_MAX_STATE_BYTES that bounds the rings (4096 rows of 65536 samples
+ * would be 2.4 GB: RC_ESIZE).  The square of num is taken in double, as the PIV score is.  FLAT is "every s is 0".  jet_min is
+ * below 2^20, the magnitude at which a mean is bad, so Q(jet_min) is below 2^36.  d_stack on a session without GRAY and d_hov on
+ * one without FLOW are RC_EINVAL.  With range 0 nothing is correlated: pairs is 0 and every record is EMPTY. */
+#define RC_TRANSECTS_GRAY 1
+#define RC_TRANSECTS_FLOW 2
+#define RC_TRANSECTS_EMPTY 1
+#define RC_TRANSECTS_FLAT 2
+#define RC_TRANSECTS_EDGE 4
+#define RC_TRANSECTS_MAX_LINES 64
+#define RC_TRANSECTS_MAX_SAMPLES 1024
+#define RC_TRANSECTS_MAX_TOTAL 65536       /* S at most: MAX_LINES * MAX_SAMPLES, so that every line may be of full length */
+#define RC_TRANSECTS_MAX_WINDOW 4096
+#define RC_TRANSECTS_MAX_LAG 8
+#define RC_TRANSECTS_MAX_RANGE 16
+#define RC_TRANSECTS_MAX_STATE_BYTES (1ull << 30)     /* the rings */
+#define RC_TRANSECTS_SUMS 16             /* int64 per line in d_sums */
+#define RC_TRANSECTS_LAUNCHES 3          /* of a push that asks for everything; a push with no output is one */
+typedef struct rc_transect_line {
+    float x0, y0, x1, y1;   /* pixels */
+    int n;                  /* samples, 2..RC_TRANSECTS_MAX_SAMPLES */
+} rc_transect_line;
+typedef struct rc_transect_sample {
+    int X, Y;               /* position in 1/16 pixel */
+    int line;               /* the line it belongs to */
+    int offset;             /* j: its place on that line */
+} rc_transect_sample;
+typedef struct rc_transect_geom {
+    int first, n;           /* the line's samples are table[first .. first + n) */
+    float ex, ey;           /* tangent */
+    float nx, ny;           /* normal */
+    float scale;            /* (float)(metres_per_pixel * fps) */
+    int pad;
+    double len;             /* pixels */
+    double ds;              /* metres between neighbouring samples */
+} rc_transect_geom;
+typedef struct rc_transects_params {
+    int window;             /* T: 2..RC_TRANSECTS_MAX_WINDOW rows held */
+    int sources;            /* RC_TRANSECTS_GRAY, RC_TRANSECTS_FLOW or both */
+    int lag;                /* 1..RC_TRANSECTS_MAX_LAG frames between the rows of a pair */
+    int range;              /* D: 0..RC_TRANSECTS_MAX_RANGE samples; 0: no correlation.  D >= 1 needs GRAY, T > lag, every n >= 2 D + 8 */
+    int flags;              /* 0 */
+    int pad;
+    double fps;             /* finite, > 0 */
+    double metres_per_pixel; /* finite, > 0; for metric numbers push the plan view's picture and field */
+    double jet_min;         /* > 0 and below 2^20 (no mean reaches that): m/s; a sample at or above it belongs to a jet */
+    double vis_max;         /* finite, > 0: m/s; the speed the Hovmoeller picture's end colours stand for */
+} rc_transects_params;
+typedef struct rc_transect {
+    int flags;              /* RC_TRANSECTS_EMPTY, FLAT, EDGE */
+    int pairs;
+    int peak_shift;         /* q - D, samples per lag frames */
+    float v_along;          /* m/s */
+    float corr_peak;        /* r[q] */
+    float mean_along, mean_cross;   /* m/s, of the window means over the valid samples */
+    float flux_out, flux_in;        /* m^2/s: the positive and the negative part of the cross-line transport */
+    int jets;
+    int jet_start, jet_len; /* of the strongest jet, in samples of the line */
+    float jet_flux;         /* m^2/s */
+    float jet_peak;         /* m/s */
+    int jet_peak_at;        /* sample */
+    int bad;                /* samples */
+} rc_transect;
+typedef struct rc_transects_info {
+    int w, h;
+    rc_transects_params prm;           /* jet_min and vis_max as rcflow_transects_set left them */
+    int lines, samples;                /* S */
+    int launches_per_push;             /* RC_TRANSECTS_LAUNCHES */
+    int held;                          /* min(pushes, T) */
+    int pairs;
+    int pad;
+    long long pushes;                  /* since open / reset */
+    size_t device_bytes;
+} rc_transects_info;
+/* The geometry alone: no context, no GPU.  table: S records in line order, geom: n_lines records, total: S; each may be NULL.
+ * RC_EINVAL: no lines, more than RC_TRANSECTS_MAX_LINES, an n outside 2..RC_TRANSECTS_MAX_SAMPLES, S above RC_TRANSECTS_MAX_TOTAL, an
+ * endpoint that is not finite, a line of no length, a sample outside the picture, fps or metres_per_pixel not finite and > 0. */
+int rcflow_transects_plan(int w, int h, const rc_transect_line* lines, int n_lines, double metres_per_pixel, double fps,
+                          rc_transect_sample* table, rc_transect_geom* geom, int* total);
+/* Allocates everything the slot will ever need: the table, the rings (T S bytes of grey, 8 T S bytes of flow), the accumulators,
+ * the records.  Re-opening replaces the state; a refused open leaves the open state as it was.  RC_EINVAL as
+ * rcflow_transects_plan, no parameters, a value outside the ranges above, unknown source or flag bits; RC_ESIZE beyond the
+ * context's max_w x max_h, or rings above RC_TRANSECTS_MAX_STATE_BYTES. */
+int rcflow_transects_open(rc_ctx* ctx, int stream, int w, int h, const rc_transect_line* lines, int n_lines, const rc_transects_params* prm);
+/* One frame: d_gray (8UC1, w x h, step >= w) when GRAY was opened and NULL otherwise, d_flow_xy (32FC2, w x h, pointer and step
+ * multiples of 8) when FLOW was opened and NULL otherwise; anything else is RC_EINVAL.  Outputs (device memory, each may be
+ * NULL): d_records lines x rc_transect (4-byte aligned), d_sums lines x RC_TRANSECTS_SUMS int64 (8-byte aligned), d_profile S x 2
+ * float (8-byte aligned), d_stack 8UC1 and d_hov 8UC3, S wide and T high, d_summary 8 int64 (8-byte aligned).  With every
+ * output NULL the push is "transects@0" alone; "transects@1" follows for records, sums, profile or summary and "transects@2"
+ * for a picture, and what they give does not depend on which earlier pushes computed.  No host synchronisation, no
+ * device-to-host copy.  An output whose byte range overlaps an input's or another output's is RC_EINVAL.  Row padding is never
+ * written.  Every refusal is decided before anything is queued and leaves the state as it was; RC_ESTATE before
+ * rcflow_transects_open.  RC_EHIP (the runtime refused a launch) is no refusal: launches before it may have written the rings and
+ * the accumulators while the push count stays, so the state is undefined until rcflow_transects_reset. */
+int rcflow_transects_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_gray, size_t step, const float* d_flow_xy, size_t flow_step,
+                              rc_transect* d_records, long long* d_sums, float* d_profile, uint8_t* d_stack, size_t stack_step,
+                              uint8_t* d_hov, size_t hov_step, long long* d_summary);
+/* Blocks until the slot's stream has finished; for hosts and tests.  Each may be NULL: the records and the summary of the last
+ * push that computed them (host memory); zeros before that. */
+int rcflow_transects_read(rc_ctx* ctx, int stream, rc_transect* records, long long summary[8]);
+/* Blocks; for tests.  Each may be NULL: the accumulators as lines x (2 D + 1) x 3 int64 (Tab, Tb, Tbb; d = -D first) and the
+ * lines' own as lines x 2 int64 (Ta, Taa) */
+int rcflow_transects_sums_read(rc_ctx* ctx, int stream, long long* sums, long long* line_sums);
+/* Blocks.  Each may be NULL: the open session's table (S records) and per-line constants (lines records), from the device */
+int rcflow_transects_table_read(rc_ctx* ctx, int stream, rc_transect_sample* table, rc_transect_geom* geom);
+/* jet_min and vis_max from the next push on; RC_EINVAL unless jet_min is > 0 and below 2^20 and vis_max finite and > 0 */
+int rcflow_transects_set(rc_ctx* ctx, int stream, double jet_min, double vis_max);
+/* zeroes the rings, the accumulators, the records, the summary and the push count; keeps the table and the allocation;
+ * asynchronous, on the slot's stream */
+int rcflow_transects_reset(rc_ctx* ctx, int stream);
+/* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
+int rcflow_transects_close(rc_ctx* ctx, int stream);
+/* never blocks; RC_ESTATE when nothing is open, RC_EINVAL without a buffer */
+int rcflow_transects_info(rc_ctx* ctx, int stream, rc_transects_info* info);
+
 /* Display path, ripcurrents.cpp:233-273 (= streamline_displacement / _total_motion / _ratio /
  * _positions, ripcurrents_module.cpp:13-60) on the slot's streamline field (rcflow_advect_field_dev):
  * which 0 = |pt|, 1 = dist, 2 = |pt| / dist; minMaxLoc + convertTo(CV_8UC1, 255/max) +
@@ -1617,7 +1786,7 @@ int rcflow_profile_read(rc_ctx* ctx, int cap, const char** names, int* launches,
 
 /* The same totals under the reference's own bucket names, in the order it prints them (ripcurrents.cpp:103-109,
  * :518-524): farneback, polar, threshold, overlay, erosion, codec, stream ("pathlines").  GPU time of the kernels
- * that do each bucket's work ("overlay" includes the time-exposure images, the 8-bit colour stages and the wave spectra, "farneback" the frame stabilisation, the opposing-flow map, the motion templates, the plan view and the ensemble PIV, "stream" the flow map and FTLE); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
+ * that do each bucket's work ("overlay" includes the time-exposure images, the 8-bit colour stages and the wave spectra, "farneback" the frame stabilisation, the opposing-flow map, the motion templates, the plan view and the ensemble PIV, "stream" the flow map and FTLE and the transects); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
  * classification kernels, booked under "threshold"), "codec" is 0 (video decode is host I/O outside the library).
  * names / ms: RC_PROFILE_BUCKETS entries each (either may be NULL).  Returns RC_PROFILE_BUCKETS. */
 #define RC_PROFILE_BUCKETS 7

@@ -1107,4 +1107,96 @@ class Piv {
     DeviceImage d_gray_, d_field_, d_vis_, d_summary_;
 };
 
+// Transects on the device (rcflow_transects_*): straight lines across the picture, sampled at every push into rings of the last
+// `window` rows.  Host grey frames and flow fields of the pipeline's size in, whichever the parameters' sources name; the
+// lines' records (drift along the line, transport across it, jets), the window means, the time stack and the Hovmoeller
+// picture out.
+class Transects {
+  public:
+    Transects(Pipeline& pipe, const std::vector<rc_transect_line>& lines, const rc_transects_params& prm) : pipe_(pipe) {
+        check(rcflow_transects_open(pipe.context(), 0, pipe.width(), pipe.height(), lines.data(), (int)lines.size(), &prm));
+        rc_transects_info i;
+        try {
+            check(rcflow_transects_info(pipe.context(), 0, &i));
+        } catch (...) {                                          // no destructor runs: close what was opened
+            (void)rcflow_transects_close(pipe.context(), 0);
+            throw;
+        }
+        lines_ = i.lines; samples_ = i.samples; window_ = prm.window; shifts_ = 2 * prm.range + 1;
+    }
+    ~Transects() { (void)rcflow_transects_close(pipe_.context(), 0); }
+    Transects(const Transects&) = delete;
+    Transects& operator=(const Transects&) = delete;
+
+    int lines() const { return lines_; }
+    int samples() const { return samples_; }
+
+    // gray: 8UC1, flow: 32FC2, both of the pipeline's size; exactly those the session was opened for, the other null.  Each
+    // output is optional: profile 32FC2 of 1 x samples (the window means along and across), stack 8UC1 and hov 8UC3 of
+    // window x samples; compute asks for records, sums and summary, which read(), records() and line_sums() then return.
+    // Without any the frame is only sampled into the rings (one launch).
+    void push(const Mat* gray, const Mat* flow, bool compute = false, Mat* profile = nullptr, Mat* stack = nullptr, Mat* hov = nullptr) {
+        const int w = pipe_.width(), h = pipe_.height();
+        if (gray && !is_image(*gray, w, h, 1, 1)) throw Error(RC_EINVAL, "Transects::push: the frame must be 8UC1 of the pipeline's size");
+        if (flow && !is_image(*flow, w, h, 2, 4)) throw Error(RC_EINVAL, "Transects::push: the field must be 32FC2 of the pipeline's size");
+        if (profile && !is_image(*profile, samples_, 1, 2, 4)) throw Error(RC_EINVAL, "Transects::push: profile 32FC2 of 1 x samples");
+        if (stack && !is_image(*stack, samples_, window_, 1, 1)) throw Error(RC_EINVAL, "Transects::push: stack 8UC1 of window x samples");
+        if (hov && !is_image(*hov, samples_, window_, 3, 1)) throw Error(RC_EINVAL, "Transects::push: hov 8UC3 of window x samples");
+        if (compute) { d_summary_.reserve(8, 1, 1, 8); d_sums_.reserve(RC_TRANSECTS_SUMS, lines_, 1, 8); }
+        staged(pipe_.context(), {{d_gray_, gray}, {d_flow_, flow}}, [&] {
+            return rcflow_transects_push_dev(pipe_.context(), 0, d_gray_.ptr<const uint8_t>(gray), d_gray_.pitch(), d_flow_.ptr<const float>(flow),
+                                             d_flow_.pitch(), nullptr, d_sums_.ptr<long long>(compute), d_profile_.ptr<float>(profile),
+                                             d_stack_.ptr<uint8_t>(stack), d_stack_.pitch(), d_hov_.ptr<uint8_t>(hov), d_hov_.pitch(),
+                                             d_summary_.ptr<long long>(compute));
+        }, {{d_profile_, profile}, {d_stack_, stack}, {d_hov_, hov}});
+    }
+    // each waits for the pipeline's stream: of the last push that computed (include/rcflow.h).  The summary: rows held, pairs,
+    // lines with a velocity, lines with a jet, jets, bad samples, pushes, 0; the records, one per line
+    std::vector<long long> read() {
+        std::vector<long long> s(8);
+        check(rcflow_transects_read(pipe_.context(), 0, nullptr, s.data()));
+        return s;
+    }
+    std::vector<rc_transect> records() {
+        std::vector<rc_transect> r((size_t)lines_);
+        check(rcflow_transects_read(pipe_.context(), 0, r.data(), nullptr));
+        return r;
+    }
+    // waits: the RC_TRANSECTS_SUMS int64 of every line of the last push that computed
+    std::vector<long long> line_sums() {
+        std::vector<long long> s((size_t)lines_ * RC_TRANSECTS_SUMS);
+        if (d_sums_.pitch()) {
+            check(rcflow_sync(pipe_.context(), 0));
+            Mat m(lines_, RC_TRANSECTS_SUMS, 1, 8, s.data());
+            d_sums_.download(m);
+        }
+        return s;
+    }
+    // waits: the accumulators, lines x (2 range + 1) x (Tab, Tb, Tbb)
+    std::vector<long long> sums() {
+        std::vector<long long> s((size_t)lines_ * shifts_ * 3);
+        check(rcflow_transects_sums_read(pipe_.context(), 0, s.data(), nullptr));
+        return s;
+    }
+    // waits: the session's table, one record per sample in line order
+    std::vector<rc_transect_sample> table() {
+        std::vector<rc_transect_sample> t((size_t)samples_);
+        check(rcflow_transects_table_read(pipe_.context(), 0, t.data(), nullptr));
+        return t;
+    }
+    std::vector<rc_transect_geom> geometry() {
+        std::vector<rc_transect_geom> g((size_t)lines_);
+        check(rcflow_transects_table_read(pipe_.context(), 0, nullptr, g.data()));
+        return g;
+    }
+    void set(double jet_min, double vis_max) { check(rcflow_transects_set(pipe_.context(), 0, jet_min, vis_max)); }
+    rc_transects_info info() { rc_transects_info i; check(rcflow_transects_info(pipe_.context(), 0, &i)); return i; }
+    void reset() { check(rcflow_transects_reset(pipe_.context(), 0)); }
+
+  private:
+    Pipeline& pipe_;
+    int lines_ = 0, samples_ = 0, window_ = 0, shifts_ = 0;
+    DeviceImage d_gray_, d_flow_, d_profile_, d_stack_, d_hov_, d_sums_, d_summary_;
+};
+
 }  // namespace rc

@@ -56,6 +56,11 @@ RC_WAVES_MAX_WINDOW, RC_WAVES_MAX_BINS, RC_WAVES_MAX_SPACING, RC_WAVES_MAX_STATE
 RC_PIV_EMPTY, RC_PIV_FLAT, RC_PIV_EDGE, RC_PIV_LOWPEAK, RC_PIV_OUTLIER = 1, 2, 4, 8, 16
 RC_PIV_REPLACE = 1
 RC_PIV_MAX_WINDOW, RC_PIV_MAX_RANGE, RC_PIV_MAX_ENSEMBLE, RC_PIV_MAX_PIXEL_PAIRS, RC_PIV_MAX_STATE_BYTES, RC_PIV_LAUNCHES = 64, 16, 256, 1 << 18, 4 << 30, 3
+# rcflow_transects_*: the sources, the record's flags, the bounds, the int64 per line of d_sums, the launches of a push that asks for everything
+RC_TRANSECTS_GRAY, RC_TRANSECTS_FLOW = 1, 2
+RC_TRANSECTS_EMPTY, RC_TRANSECTS_FLAT, RC_TRANSECTS_EDGE = 1, 2, 4
+RC_TRANSECTS_MAX_LINES, RC_TRANSECTS_MAX_SAMPLES, RC_TRANSECTS_MAX_TOTAL, RC_TRANSECTS_MAX_WINDOW = 64, 1024, 65536, 4096
+RC_TRANSECTS_MAX_LAG, RC_TRANSECTS_MAX_RANGE, RC_TRANSECTS_MAX_STATE_BYTES, RC_TRANSECTS_SUMS, RC_TRANSECTS_LAUNCHES = 8, 16, 1 << 30, 16, 3
 
 ERRORS = {-1: "RC_EINVAL", -2: "RC_ENOMEM", -3: "RC_EHIP", -4: "RC_ENODEV", -5: "RC_ESIZE",
           -6: "RC_ESTATE", -7: "RC_ECOMM"}
@@ -209,6 +214,24 @@ class PivInfo(C.Structure):
     """rc_piv_info (include/rcflow.h)."""
     _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", PivParams), ("grid_x", C.c_int), ("grid_y", C.c_int), ("launches_per_push", C.c_int),
                 ("pairs", C.c_int), ("pushes", C.c_longlong), ("device_bytes", C.c_size_t)]
+
+
+class TransectLine(C.Structure):
+    """rc_transect_line (include/rcflow.h)."""
+    _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("x1", C.c_float), ("y1", C.c_float), ("n", C.c_int)]
+
+
+class TransectsParams(C.Structure):
+    """rc_transects_params (include/rcflow.h)."""
+    _fields_ = [("window", C.c_int), ("sources", C.c_int), ("lag", C.c_int), ("range", C.c_int), ("flags", C.c_int), ("pad", C.c_int),
+                ("fps", C.c_double), ("metres_per_pixel", C.c_double), ("jet_min", C.c_double), ("vis_max", C.c_double)]
+
+
+class TransectsInfo(C.Structure):
+    """rc_transects_info (include/rcflow.h)."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", TransectsParams), ("lines", C.c_int), ("samples", C.c_int),
+                ("launches_per_push", C.c_int), ("held", C.c_int), ("pairs", C.c_int), ("pad", C.c_int), ("pushes", C.c_longlong),
+                ("device_bytes", C.c_size_t)]
 
 
 class FitParams(C.Structure):
@@ -398,6 +421,16 @@ SIGNATURES = {
     "rcflow_piv_reset": [_vp, _i],
     "rcflow_piv_close": [_vp, _i],
     "rcflow_piv_info": [_vp, _i, C.POINTER(PivInfo)],
+    "rcflow_transects_plan": [_i, _i, C.POINTER(TransectLine), _i, C.c_double, C.c_double, _vp, _vp, C.POINTER(C.c_int)],
+    "rcflow_transects_open": [_vp, _i, _i, _i, C.POINTER(TransectLine), _i, C.POINTER(TransectsParams)],
+    "rcflow_transects_push_dev": [_vp, _i, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp],
+    "rcflow_transects_read": [_vp, _i, _vp, C.POINTER(C.c_longlong)],
+    "rcflow_transects_sums_read": [_vp, _i, _vp, _vp],
+    "rcflow_transects_table_read": [_vp, _i, _vp, _vp],
+    "rcflow_transects_set": [_vp, _i, C.c_double, C.c_double],
+    "rcflow_transects_reset": [_vp, _i],
+    "rcflow_transects_close": [_vp, _i],
+    "rcflow_transects_info": [_vp, _i, C.POINTER(TransectsInfo)],
     "rcflow_comm_unique_id": [_vp],
     "rcflow_comm_init": [_vp, _vp, _i, _i],
     "rcflow_comm_destroy": [_vp],

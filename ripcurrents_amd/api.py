@@ -38,8 +38,9 @@ from ._lib import FTLE_DIRECTIONS, FtleInfo, FtleParams
 from ._lib import PlanViewInfo, PlanViewParams
 from ._lib import WavesInfo, WavesParams
 from ._lib import RC_PIV_REPLACE, PivInfo, PivParams
+from ._lib import RC_TRANSECTS_FLOW, RC_TRANSECTS_GRAY, RC_TRANSECTS_SUMS, TransectLine, TransectsInfo, TransectsParams
 
-__all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState", "Waves", "Piv"]
+__all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState", "Waves", "Piv", "Transects"]
 
 
 # rc_draw_prim as a numpy record (32 bytes): what Context.draw takes and Context.tracers_prims returns
@@ -65,6 +66,19 @@ WAVE_CELL_DTYPE = np.dtype([("bin", "<i4"), ("flags", "<i4"), ("freq_hz", "<f4")
 # rc_piv_cell as a numpy record (32 bytes): what Context.piv_read returns
 PIV_CELL_DTYPE = np.dtype([("dx", "<f4"), ("dy", "<f4"), ("peak", "<f4"), ("resid", "<f4"), ("ix", "<i4"), ("iy", "<i4"), ("flags", "<i4"),
                            ("pairs", "<i4")])
+# the eight words of a transects summary, in order
+TRANSECTS_SUMMARY = ("held", "pairs", "with_velocity", "with_jet", "jets", "bad", "pushes", "reserved")
+# rc_transect as a numpy record (64 bytes): what Context.transects_read returns
+TRANSECT_DTYPE = np.dtype([("flags", "<i4"), ("pairs", "<i4"), ("peak_shift", "<i4"), ("v_along", "<f4"), ("corr_peak", "<f4"),
+                           ("mean_along", "<f4"), ("mean_cross", "<f4"), ("flux_out", "<f4"), ("flux_in", "<f4"), ("jets", "<i4"),
+                           ("jet_start", "<i4"), ("jet_len", "<i4"), ("jet_flux", "<f4"), ("jet_peak", "<f4"), ("jet_peak_at", "<i4"), ("bad", "<i4")])
+# rc_transect_sample (16 bytes) and rc_transect_geom (48 bytes): what transects_plan and Context.transects_table return
+TRANSECT_SAMPLE_DTYPE = np.dtype([("X", "<i4"), ("Y", "<i4"), ("line", "<i4"), ("offset", "<i4")])
+TRANSECT_GEOM_DTYPE = np.dtype([("first", "<i4"), ("n", "<i4"), ("ex", "<f4"), ("ey", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("scale", "<f4"),
+                                ("pad", "<i4"), ("len", "<f8"), ("ds", "<f8")])
+# the int64 of a line in d_sums / the sums output of transects_push
+TRANSECTS_SUMS = ("flux_pos", "flux_neg", "flux_along", "valid", "bad", "jets", "jet_start", "jet_len", "jet_sum", "jet_peak", "jet_peak_at",
+                  "N", "num", "va", "vb", "q")
 # rc_track as a numpy record (128 bytes): what Context.tracks_read returns
 TRACK_DTYPE = np.dtype([("id", "<i8"), ("parent", "<i8"), ("first_push", "<i8"), ("area_sum", "<i8"), ("fx_sum", "<i8"), ("fy_sum", "<i8"),
                         ("m_sum", "<i8"), ("slot", "<i4"), ("label", "<i4"), ("flags", "<i4"), ("age", "<i4"), ("hits", "<i4"),
@@ -1616,6 +1630,79 @@ class Context:
     def piv_close(self, stream=0):
         self._lifecycle("piv", "close", stream)
 
+    # ------------------------------------------------------------------ transects
+    def transects_open(self, w, h, lines, window=256, gray=True, flow=True, lag=1, range=0, fps=1.0, metres_per_pixel=1.0, jet_min=0.25,
+                       vis_max=2.0, stream=0):
+        """Opens the slot's transects on w x h frames (include/rcflow.h, "transects"): `lines` is a sequence of (x0, y0, x1, y1, n),
+        straight lines in pixels with n samples each; the last `window` rows are held, of the grey frame (gray), of the field's
+        components along and across each line (flow) or of both.  range >= 1 correlates every grey row with the one `lag` pushes
+        later over +-range samples, for the drift along the line.  The rings take window * samples * (1 + 8) bytes."""
+        arr = _transect_lines(lines)
+        p = TransectsParams(window=int(window), sources=(RC_TRANSECTS_GRAY if gray else 0) | (RC_TRANSECTS_FLOW if flow else 0), lag=int(lag),
+                            range=int(range), flags=0, pad=0, fps=float(fps), metres_per_pixel=float(metres_per_pixel), jet_min=float(jet_min),
+                            vis_max=float(vis_max))
+        self._bind(stream)          # the state is zeroed on the slot's stream: the one the pushes will run on
+        check(self._lib.rcflow_transects_open(self._h, stream, int(w), int(h), arr, len(arr), C.byref(p)))
+
+    def transects_info(self, stream=0):
+        """dict(w, h, the parameters, gray, flow, lines, samples, launches_per_push, held, pairs, pushes, device_bytes); never blocks."""
+        i = self._info("transects", TransectsInfo(), stream)
+        d = _record(i, skip=("flags", "pad", "sources"))
+        d["gray"], d["flow"] = bool(i.prm.sources & RC_TRANSECTS_GRAY), bool(i.prm.sources & RC_TRANSECTS_FLOW)
+        return d
+
+    def transects_push(self, gray=None, flow=None, records=None, sums=None, profile=None, stack=None, hov=None, summary=None, stream=0):
+        """One frame: gray (HxW uint8 device tensor) and / or flow (HxWx2 float32), exactly what was opened, rows may be padded;
+        nothing is synchronised.  Outputs are preallocated device tensors, each optional: records LINESx64 uint8 (rc_transect
+        records; view the host copy as TRANSECT_DTYPE), sums LINESx16 int64 (TRANSECTS_SUMS), profile SAMPLESx2 float32 (the window
+        means along and across), stack WINDOWxSAMPLES uint8 (the time stack, oldest row first), hov WINDOWxSAMPLESx3 uint8 (the
+        cross-line velocity against time), summary 8 int64 (TRANSECTS_SUMMARY).  Without any output the push is one launch."""
+        i = self._info("transects", TransectsInfo(), stream)
+        h, w, L, S, T = i.h, i.w, i.lines, i.samples, i.prm.window
+        gp = self._in_image(gray, torch.uint8, "gray", (h, w), optional=True)
+        fp = self._in_image(flow, torch.float32, "flow", (h, w, 2), optional=True)
+        rp = self._out_array(records, torch.uint8, "records", L * 64)
+        sp = self._out_array(sums, torch.int64, "sums", L * RC_TRANSECTS_SUMS)
+        pp = self._out_array(profile, torch.float32, "profile", S * 2)
+        kp = self._out_image(stack, torch.uint8, "stack", (T, S))
+        hp = self._out_image(hov, torch.uint8, "hov", (T, S, 3))
+        up = self._out_array(summary, torch.int64, "summary", 8)
+        self._bind(stream)
+        check(self._lib.rcflow_transects_push_dev(self._h, stream, *gp, *fp, rp, sp, pp, *kp, *hp, up))
+
+    def transects_read(self, stream=0):
+        """Waits for the slot's stream -> (records LINES TRANSECT_DTYPE, dict of the summary by TRANSECTS_SUMMARY names) of the
+        last push that computed them; zeros before that."""
+        rec = np.zeros(self.transects_info(stream)["lines"], TRANSECT_DTYPE)
+        return rec, self._summary(self._lib.rcflow_transects_read, stream, TRANSECTS_SUMMARY, rec.ctypes.data)
+
+    def transects_sums(self, stream=0):
+        """Waits for the slot's stream -> (the accumulators LINESx(2 range + 1)x3 int64: Tab, Tb, Tbb per shift; LINESx2 int64:
+        Ta, Taa); for tests."""
+        info = self.transects_info(stream)
+        sums, line = np.empty((info["lines"], 2 * info["range"] + 1, 3), np.int64), np.empty((info["lines"], 2), np.int64)
+        self._bind(stream)
+        check(self._lib.rcflow_transects_sums_read(self._h, stream, sums.ctypes.data, line.ctypes.data))
+        return sums, line
+
+    def transects_table(self, stream=0):
+        """Waits -> (SAMPLES TRANSECT_SAMPLE_DTYPE, LINES TRANSECT_GEOM_DTYPE): the open session's table, from the device."""
+        info = self.transects_info(stream)
+        table, geom = np.zeros(info["samples"], TRANSECT_SAMPLE_DTYPE), np.zeros(info["lines"], TRANSECT_GEOM_DTYPE)
+        self._bind(stream)
+        check(self._lib.rcflow_transects_table_read(self._h, stream, table.ctypes.data, geom.ctypes.data))
+        return table, geom
+
+    def transects_set(self, jet_min, vis_max, stream=0):
+        """jet_min and vis_max from the next push on."""
+        check(self._lib.rcflow_transects_set(self._h, stream, float(jet_min), float(vis_max)))
+
+    def transects_reset(self, stream=0):
+        self._lifecycle("transects", "reset", stream)
+
+    def transects_close(self, stream=0):
+        self._lifecycle("transects", "close", stream)
+
     # ------------------------------------------------------------------ rip regions
     def regions_open(self, w, h, connectivity=8, min_area=1, max_regions=1024, stream=0):
         """Opens the slot's region labelling for w x h masks: connected components (4 or 8 neighbours) numbered in raster
@@ -1917,6 +2004,44 @@ class Piv(_Product):
 
     def set(self, min_peak, median_eps, median_thr, vis_max):
         self.ctx.piv_set(min_peak, median_eps, median_thr, vis_max, self.stream)
+
+
+class Transects(_Product):
+    """The transects of one slot as an object: Context.transects_* with the context and the slot bound.  Opens on construction
+    (lines and the parameters of Context.transects_open as keywords), closes on close() or at the end of a with block."""
+    product = "transects"
+
+    def push(self, gray=None, flow=None, **outputs):
+        self.ctx.transects_push(gray, flow, stream=self.stream, **outputs)
+
+    def sums(self):
+        return self.ctx.transects_sums(self.stream)
+
+    def table(self):
+        return self.ctx.transects_table(self.stream)
+
+    def set(self, jet_min, vis_max):
+        self.ctx.transects_set(jet_min, vis_max, self.stream)
+
+
+def _transect_lines(lines):
+    """(x0, y0, x1, y1, n) per line -> the ctypes array of rc_transect_line"""
+    rows = [tuple(l) for l in lines]
+    if not rows or any(len(r) != 5 for r in rows):
+        raise ValueError("lines must be a non-empty sequence of (x0, y0, x1, y1, n)")
+    return (TransectLine * len(rows))(*[TransectLine(float(r[0]), float(r[1]), float(r[2]), float(r[3]), int(r[4])) for r in rows])
+
+
+def transects_plan(w, h, lines, metres_per_pixel=1.0, fps=1.0):
+    """rcflow_transects_plan: the sample table and the per-line constants of `lines` on a w x h picture, without a context or a
+    GPU -> (SAMPLES TRANSECT_SAMPLE_DTYPE, LINES TRANSECT_GEOM_DTYPE)."""
+    lib = _lib.load()
+    arr = _transect_lines(lines)
+    total = C.c_int(0)
+    check(lib.rcflow_transects_plan(int(w), int(h), arr, len(arr), float(metres_per_pixel), float(fps), None, None, C.byref(total)))
+    table, geom = np.zeros(total.value, TRANSECT_SAMPLE_DTYPE), np.zeros(len(arr), TRANSECT_GEOM_DTYPE)
+    check(lib.rcflow_transects_plan(int(w), int(h), arr, len(arr), float(metres_per_pixel), float(fps), table.ctypes.data, geom.ctypes.data, None))
+    return table, geom
 
 
 def _alias_tensor(ptr, n, dtype, device):

@@ -270,6 +270,25 @@ struct RcPiv {
     RcZeroFence zf;
 };
 
+// Transects of one stream slot (transects_kernels.hip).  Everything is allocated by rcflow_transects_open and released by
+// rcflow_transects_close / rcflow_destroy.
+struct RcTransects {
+    bool open = false;
+    int w = 0, h = 0;
+    rc_transects_params prm{};      // jet_min and vis_max: as rcflow_transects_set left them
+    int L = 0, S = 0;               // lines, samples in all
+    int nw = 0;                     // words per line: 3 (2 D + 1) (Tab, Tb, Tbb per shift) + 2 (Ta, Taa)
+    long long pushes = 0;           // since open / reset; the next row goes to ring slot pushes mod window
+    RcBuf table;                    // [S] rc_transect_sample | [L] rc_transect_geom, written once by open
+    RcBuf ring_g;                   // [window][S] bytes; GRAY
+    RcBuf ring_f;                   // [window][S] float2 (ut, un); FLOW
+    RcBuf acc;                      // [L][nw] int64: the sums over the pairs the ring holds
+    RcBuf out;                      // the last computing push: records [L] | sums [L][RC_TRANSECTS_SUMS] int64 | summary 8 int64
+    RcBuf ctl;                      // TsCtl: the ticket and the counters, zero between launches
+    RcBuf jet;                      // COLORMAP_JET LUT (768 B), written once by open
+    RcZeroFence zf;
+};
+
 // warp_kernels.hip: one launch of the affine / perspective warp
 struct RcWarpArgs {
     const uint8_t* src; size_t step;
@@ -350,6 +369,7 @@ struct RcSlot {
     RcPlanView pv;
     RcWaves wv;
     RcPiv piv;
+    RcTransects ts;
     RcPhaseCorr pc;
 };
 
@@ -406,7 +426,9 @@ struct rc_ctx {
 // it is booked with the other operations on the field (flow_postop), under "farneback".  The wave spectra read frames, not the
 // flow, and what they leave (cells, a bin map, a depth picture) is looked at beside the time-exposure images made from the
 // same frames, so they are booked with those, under "overlay".  The ensemble PIV estimates a velocity field from a frame pair
-// as the Farneback kernels do, and its field goes where theirs goes, so it is booked with them, under "farneback".
+// as the Farneback kernels do, and its field goes where theirs goes, so it is booked with them, under "farneback".  The transects
+// sample the frame and the field along lines and keep what they find from push to push, as the tracer lines do with their
+// vertices, and are booked with them, under "stream".
 #define RC_BUCKET_TABLE(X) \
     X(RC_B_FARNEBACK, "farneback") X(RC_B_POLAR, "polar") X(RC_B_THRESHOLD, "threshold") X(RC_B_OVERLAY, "overlay") \
     X(RC_B_EROSION, "erosion") X(RC_B_CODEC, "codec") X(RC_B_STREAM, "stream")
@@ -445,7 +467,8 @@ struct rc_ctx {
     X(RC_K_FTLE, "ftle", RC_B_STREAM) /* @0 ring slot, @1 flow map, @2 tensor, outputs and summary */ \
     X(RC_K_PLANVIEW, "planview", RC_B_FARNEBACK) /* @0 the table (open), @1 the push */ \
     X(RC_K_WAVES, "waves", RC_B_OVERLAY) /* @0 spectrum, @1 cell sums and closing, @2 bin map and picture */ \
-    X(RC_K_PIV, "piv", RC_B_FARNEBACK) /* @0 the pair's sums, ring and accumulators, @1 score, peak and records, @2 validation, field, picture, summary */
+    X(RC_K_PIV, "piv", RC_B_FARNEBACK) /* @0 the pair's sums, ring and accumulators, @1 score, peak and records, @2 validation, field, picture, summary */ \
+    X(RC_K_TRANSECTS, "transects", RC_B_STREAM) /* @0 sampling, rings and accumulators, @1 velocity, transport, jets, records and summary, @2 time stack and Hovmoeller picture */
 #define RC_ROW_ID(id, ...) id,
 enum { RC_BUCKET_TABLE(RC_ROW_ID) RC_B_BUCKETS };
 enum { RC_KIND_TABLE(RC_ROW_ID) RC_K_KINDS };
@@ -526,7 +549,7 @@ struct RcProfScope {
     } while (0)
 
 // ---------------------------------------------------------------------------- per-slot products
-// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView, RcWaves and RcPiv share one lifecycle.  A product supplies
+// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView, RcWaves, RcPiv and RcTransects share one lifecycle.  A product supplies
 //   void rc_state_free(T&)             frees every buffer and the fence; the state is T() again
 //   int rc_state_zero(RcSlot&, T&)     rc_fence_zero of what open / reset clear, and the counters
 // and open / reset / close are written once, here.
@@ -541,6 +564,7 @@ void rc_state_free(RcFtle& f);
 void rc_state_free(RcPlanView& v);
 void rc_state_free(RcWaves& v);
 void rc_state_free(RcPiv& v);
+void rc_state_free(RcTransects& v);
 int rc_state_zero(RcSlot& s, RcTimex& t);
 int rc_state_zero(RcSlot& s, RcFrameStab& f);
 int rc_state_zero(RcSlot& s, RcRipMap& m);
@@ -552,6 +576,7 @@ int rc_state_zero(RcSlot& s, RcFtle& f);
 int rc_state_zero(RcSlot& s, RcPlanView& v);
 int rc_state_zero(RcSlot& s, RcWaves& v);
 int rc_state_zero(RcSlot& s, RcPiv& v);
+int rc_state_zero(RcSlot& s, RcTransects& v);
 
 // The tail of every open.  The caller has validated, selected the device and built `fresh` (rc: what its allocations
 // returned).  The state that is open is touched only once nothing can be refused any more: a refused open leaves it as it
