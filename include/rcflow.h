@@ -1706,6 +1706,122 @@ int rcflow_transects_close(rc_ctx* ctx, int stream);
 /* never blocks; RC_ESTATE when nothing is open, RC_EINVAL without a buffer */
 int rcflow_transects_info(rc_ctx* ctx, int stream, rc_transects_info* info);
 
+/* ------------------------------------------------------------------ flow kinematics: vorticity, divergence, Okubo-Weiss, cores
+ * Every product above says where the water goes.  This one says how the field turns and spreads at a point, which is what a
+ * rip looks like in a velocity field: the neck is a jet between two shear layers of opposite vorticity, the head a
+ * counter-rotating vortex pair, the feeders converge (negative divergence).  It is the Eulerian counterpart of the FTLE: one
+ * field in, no ring, stateless in time (time averaging is the caller's: push rcflow_ripmap_mean_dev's window mean).  It takes
+ * every 32FC2 field the library makes (Farneback, the window mean, the plan view's metric field, the PIV field) and its mask
+ * goes into rcflow_regions_* / rcflow_tracks_* unchanged.  The reference has only the display colouring of the raw one-pixel
+ * Jacobian's norm (rcflow_shear_rate_to_color_dev).  tests/_kinematics_ref.py states the following in numpy and the kernels
+ * equal it bit for bit.  All fp32 unless stated, each operation rounded on its own (no fused multiply-add); every integer
+ * is exact.  Picture coordinates: x to the right, y DOWN, so positive vorticity turns CLOCKWISE as the picture shows it.
+ *
+ *  Taps (host, double; rcflow_kinematics_taps gives them without a context).  R = radius.  e_k = exp(-k^2 / (2 sigma^2)) for
+ *  k = 0..R; Z = e_0 + 2 (e_1 + ... + e_R), the bracket summed ascending, then doubled, then e_0 added; g_k = (float)(e_k / Z).
+ *  R = 0: g_0 = 1 and sigma is ignored.
+ *  Interior.  m = R + s, s = spacing.  A pixel is INTERIOR when m <= x < w - m and m <= y < h - m.  No index is ever clamped:
+ *  nothing outside the picture is read (a replicated border would bias the derivatives).
+ *
+ *  1. "kinematics@0".  Per component F of the field, horizontally: H = g_0 * F(x, y), then for k = 1..R
+ *     H = H + g_k * (F(x - k, y) + F(x + k, y)), the bracket rounded first.  Then vertically, the same recurrence on H:
+ *     S = g_0 * H(x, y), S = S + g_k * (H(x, y - k) + H(x, y + k)).  inv = (float)(scale / (2 s)); E, W, S, N the smoothed
+ *     values at x + s, x - s, y + s, y - s:
+ *       ux = (S_E.x - S_W.x) * inv    vx = (S_E.y - S_W.y) * inv    uy = (S_S.x - S_N.x) * inv    vy = (S_S.y - S_N.y) * inv
+ *     An interior pixel is BAD when any of the four is not finite or reaches 8 in magnitude; it is counted, its omega, div
+ *     and ow are 0 and it is part of nothing.  VALID: interior and not bad.  For a valid pixel
+ *       omega = vx - uy    div = ux + vy    sn = ux - vy    ss = vx + uy    ow = (sn*sn + ss*ss) - omega*omega
+ *       e = omega*omega    w2 = ow*ow
+ *     Outside the interior omega, div and ow are 0.  Q(x) = (int64)rint((double)x * 65536); the bound 8 gives |omega| < 16,
+ *     |ow| < 512 and w2 < 2^18, so with w * h <= 2^25 every sum stays below 2^59.  Per cell (ripmap's rule: column
+ *     min(x / (w / grid_x), grid_x - 1), likewise for rows), int64: n_valid, n_bad, sum Q(omega), sum Q(div), sum Q(e),
+ *     sum Q(ow), sum Q(w2).  Also the largest |omega| over the valid pixels.  d_omega, d_div and d_ow are written here.
+ *     Threshold, by the launch's last-arriving workgroup, in double with + - * / only: n, SW, SW2 the sums of n_valid,
+ *     Q(ow), Q(w2) over the cells; mean = ((double)SW / 65536) / n; m2 = ((double)SW2 / 65536) / n; var = m2 - mean * mean,
+ *     0 when that is negative or n = 0.  With RC_KINEMATICS_RELATIVE T2 = (ow_k * ow_k) * var (the usual "W below -0.2 sigma_W"
+ *     with no square root in it), else T2 = ow_min * ow_min, computed on the host.
+ *  2. "kinematics@1".  A valid pixel is a CORE when ow < 0, (double)ow * (double)ow > T2 (the product is exact) and
+ *     fabsf(omega) >= (float)omega_min.  Mask (8UC1): 255 at a core, else 0; it is what rcflow_regions_push_dev takes.
+ *     Picture (8UC3): entry i of rcflow_jet_lut, i = rint(omega / (float)vis_max * 127.5f + 127.5f) saturated to 0..255, as the
+ *     transects' Hovmoeller picture; black where the pixel is not valid.  Per cell four more int64: core pixels with
+ *     omega > 0, core pixels with omega < 0, sum Q(omega) over each kind: RC_KINEMATICS_SUMS words per cell in that order
+ *     after the seven above.  The last-arriving workgroup closes the records in double: flags RC_KINEMATICS_EMPTY when
+ *     n_valid = 0, RC_KINEMATICS_CW when positive cores >= min_core, RC_KINEMATICS_CCW likewise; with S the cell's sum Q(.)
+ *     a mean is (float)(((double)S / 65536) / n_valid) and a circulation (float)(((double)S / 65536) * pixel_area).  For an
+ *     empty cell every value except flags is 0.
+ *     Summary, 8 int64: valid pixels | bad pixels | cores cw | cores ccw | the bits of T2 (a double) | cells with both CW and
+ *     CCW | pushes since open / reset | the bits of the largest |omega| as uint32. */
+#define RC_KINEMATICS_RELATIVE 1         /* rc_kinematics_params::flags: the threshold is ow_k^2 times the variance of ow */
+#define RC_KINEMATICS_EMPTY 1            /* rc_kinematics_cell::flags */
+#define RC_KINEMATICS_CW 2
+#define RC_KINEMATICS_CCW 4
+#define RC_KINEMATICS_MAX_RADIUS 8
+#define RC_KINEMATICS_MAX_SPACING 8
+#define RC_KINEMATICS_MAX_PIXELS (1 << 25)
+#define RC_KINEMATICS_SUMS 11            /* int64 per cell in d_sums */
+#define RC_KINEMATICS_LAUNCHES 2         /* of a push with any output; a push with none queues nothing */
+typedef struct rc_kinematics_params {
+    int radius;             /* R: 0..RC_KINEMATICS_MAX_RADIUS, half-width of the smoothing; 0: none */
+    int spacing;            /* s: 1..RC_KINEMATICS_MAX_SPACING, half-width of the central differences */
+    int grid_x, grid_y;     /* >= 1, <= w, h, at most RC_RIPMAP_MAX_CELLS cells */
+    int min_core;           /* >= 1: core pixels of one sign that flag a cell */
+    int flags;              /* RC_KINEMATICS_RELATIVE or 0 */
+    int pad[2];             /* so that the doubles are aligned; not read */
+    double sigma;           /* finite, > 0; ignored when R = 0 */
+    double scale;           /* finite, > 0: differences into rates: fps for a pixel field, 1 / metres per cell for the plan view's */
+    double pixel_area;      /* finite, > 0: the area one pixel stands for */
+    double ow_k;            /* finite, >= 0: RELATIVE */
+    double ow_min;          /* finite, >= 0: otherwise */
+    double omega_min;       /* finite, >= 0 */
+    double vis_max;         /* finite, > 0: the |omega| the picture's end colours stand for */
+} rc_kinematics_params;
+typedef struct rc_kinematics_cell {
+    int flags;              /* RC_KINEMATICS_EMPTY, CW, CCW */
+    int n, bad;             /* the cell's n_valid, n_bad */
+    float mean_vorticity, circulation, mean_divergence, enstrophy, mean_ow;
+    int cores_cw, cores_ccw;
+    float circulation_cw, circulation_ccw;
+} rc_kinematics_cell;       /* 48 bytes */
+typedef struct rc_kinematics_info {
+    int w, h;
+    rc_kinematics_params prm;          /* ow_k, ow_min, omega_min and vis_max as rcflow_kinematics_set left them */
+    int margin;                        /* m = R + s */
+    int launches_per_push;             /* RC_KINEMATICS_LAUNCHES */
+    long long pushes;                  /* since open / reset */
+    size_t device_bytes;
+} rc_kinematics_info;
+/* The taps g_0..g_radius into taps[radius + 1]; needs no context and no GPU.  RC_EINVAL: radius outside
+ * 0..RC_KINEMATICS_MAX_RADIUS, no buffer, or with radius > 0 a sigma that is not finite and > 0. */
+int rcflow_kinematics_taps(int radius, double sigma, float* taps);
+/* Allocates two planes of 4 B/px, the cell sums and the records.  Re-opening replaces the state; a refused open leaves the open
+ * state as it was.  RC_EINVAL: no parameters, a value outside the ranges above, unknown flag bits, w < 2 m + 1 or h < 2 m + 1;
+ * RC_ESIZE beyond the context's max_w x max_h or w * h above RC_KINEMATICS_MAX_PIXELS. */
+int rcflow_kinematics_open(rc_ctx* ctx, int stream, int w, int h, const rc_kinematics_params* prm);
+/* One flow field (32FC2, w x h, pointer and step multiples of 8, step >= 8 w).  Outputs (device memory, each may be NULL):
+ * d_omega, d_div, d_ow 32FC1 (4-byte aligned, steps multiples of 4), d_mask 8UC1, d_vis 8UC3, d_cells grid_y x grid_x
+ * rc_kinematics_cell (4-byte aligned), d_sums grid_y x grid_x x RC_KINEMATICS_SUMS int64 and d_summary 8 int64 (8-byte
+ * aligned).  With every output NULL the push only counts and queues no launch; with any it is RC_KINEMATICS_LAUNCHES, and
+ * what they give depends neither on which outputs were asked for nor on earlier pushes.  No host synchronisation, no
+ * device-to-host copy.  An output whose byte range overlaps the field's or another output's is RC_EINVAL.  Row padding is never
+ * written.  Every refusal is decided before anything is queued and leaves the state as it was; RC_ESTATE before
+ * rcflow_kinematics_open. */
+int rcflow_kinematics_push_dev(rc_ctx* ctx, int stream, const float* d_flow_xy, size_t flow_step,
+                               float* d_omega, size_t omega_step, float* d_div, size_t div_step, float* d_ow, size_t ow_step,
+                               uint8_t* d_mask, size_t mask_step, uint8_t* d_vis, size_t vis_step,
+                               rc_kinematics_cell* d_cells, long long* d_sums, long long* d_summary);
+/* Blocks until the slot's stream has finished; for hosts and tests.  Records, sums and summary of the last push that had an
+ * output (each may be NULL); zeros before that. */
+int rcflow_kinematics_read(rc_ctx* ctx, int stream, rc_kinematics_cell* cells, long long* sums, long long summary[8]);
+/* ow_k, ow_min, omega_min and vis_max from the next push on; RC_EINVAL as rcflow_kinematics_open */
+int rcflow_kinematics_set(rc_ctx* ctx, int stream, double ow_k, double ow_min, double omega_min, double vis_max);
+/* zeroes the records, the sums, the summary and the push count; keeps the parameters as set and the allocation; asynchronous,
+ * on the slot's stream */
+int rcflow_kinematics_reset(rc_ctx* ctx, int stream);
+/* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
+int rcflow_kinematics_close(rc_ctx* ctx, int stream);
+/* never blocks; RC_ESTATE when nothing is open, RC_EINVAL without a buffer (as rcflow_transects_info) */
+int rcflow_kinematics_info(rc_ctx* ctx, int stream, rc_kinematics_info* info);
+
 /* Display path, ripcurrents.cpp:233-273 (= streamline_displacement / _total_motion / _ratio /
  * _positions, ripcurrents_module.cpp:13-60) on the slot's streamline field (rcflow_advect_field_dev):
  * which 0 = |pt|, 1 = dist, 2 = |pt| / dist; minMaxLoc + convertTo(CV_8UC1, 255/max) +
@@ -1786,7 +1902,7 @@ int rcflow_profile_read(rc_ctx* ctx, int cap, const char** names, int* launches,
 
 /* The same totals under the reference's own bucket names, in the order it prints them (ripcurrents.cpp:103-109,
  * :518-524): farneback, polar, threshold, overlay, erosion, codec, stream ("pathlines").  GPU time of the kernels
- * that do each bucket's work ("overlay" includes the time-exposure images, the 8-bit colour stages and the wave spectra, "farneback" the frame stabilisation, the opposing-flow map, the motion templates, the plan view and the ensemble PIV, "stream" the flow map and FTLE and the transects); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
+ * that do each bucket's work ("overlay" includes the time-exposure images, the 8-bit colour stages and the wave spectra, "farneback" the frame stabilisation, the opposing-flow map, the motion templates, the plan view, the ensemble PIV and the flow kinematics, "stream" the flow map and FTLE and the transects); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
  * classification kernels, booked under "threshold"), "codec" is 0 (video decode is host I/O outside the library).
  * names / ms: RC_PROFILE_BUCKETS entries each (either may be NULL).  Returns RC_PROFILE_BUCKETS. */
 #define RC_PROFILE_BUCKETS 7

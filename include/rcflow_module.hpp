@@ -1199,4 +1199,69 @@ class Transects {
     DeviceImage d_gray_, d_flow_, d_profile_, d_stack_, d_hov_, d_sums_, d_summary_;
 };
 
+// Flow kinematics on the device (rcflow_kinematics_*): vorticity (positive: clockwise on the picture), divergence and the
+// Okubo-Weiss parameter of one flow field, the vortex cores and a record per cell of a grid.  Stateless in time.  Host flow
+// fields of the pipeline's size in; the planes, the core mask and the picture out.
+class Kinematics {
+  public:
+    Kinematics(Pipeline& pipe, const rc_kinematics_params& prm) : pipe_(pipe), cells_(prm.grid_x * prm.grid_y) {
+        check(rcflow_kinematics_open(pipe.context(), 0, pipe.width(), pipe.height(), &prm));
+    }
+    ~Kinematics() { (void)rcflow_kinematics_close(pipe_.context(), 0); }
+    Kinematics(const Kinematics&) = delete;
+    Kinematics& operator=(const Kinematics&) = delete;
+
+    // the taps of the smoothing, g_0..g_radius; needs no GPU
+    static std::vector<float> taps(int radius, double sigma) {
+        std::vector<float> g((size_t)(radius < 0 ? 0 : radius) + 1);
+        check(rcflow_kinematics_taps(radius, sigma, g.data()));
+        return g;
+    }
+    // flow: 32FC2 of the pipeline's size.  Each output is optional: omega, div and ow 32FC1, mask 8UC1 (255 at a core), picture
+    // 8UC3 (JET of the vorticity); compute asks for the records, the sums and the summary alone.  Those stay on the session
+    // after any push with an output, for read(), cells() and sums().  Without any the push is only counted.
+    void push(const Mat& flow, Mat* omega = nullptr, Mat* div = nullptr, Mat* ow = nullptr, Mat* mask = nullptr, Mat* picture = nullptr,
+              bool compute = false) {
+        const int w = pipe_.width(), h = pipe_.height();
+        if (!is_image(flow, w, h, 2, 4)) throw Error(RC_EINVAL, "Kinematics::push: the field must be 32FC2 of the pipeline's size");
+        if ((omega && !is_image(*omega, w, h, 1, 4)) || (div && !is_image(*div, w, h, 1, 4)) || (ow && !is_image(*ow, w, h, 1, 4)) ||
+            (mask && !is_image(*mask, w, h, 1, 1)) || (picture && !is_image(*picture, w, h, 3, 1)))
+            throw Error(RC_EINVAL, "Kinematics::push: omega, div and ow 32FC1, mask 8UC1, picture 8UC3, each of the pipeline's size");
+        if (compute) d_summary_.reserve(8, 1, 1, 8);
+        staged(pipe_.context(), {{d_flow_, &flow}}, [&] {
+            return rcflow_kinematics_push_dev(pipe_.context(), 0, d_flow_.ptr<const float>(), d_flow_.pitch(), d_omega_.ptr<float>(omega),
+                                              d_omega_.pitch(), d_div_.ptr<float>(div), d_div_.pitch(), d_ow_.ptr<float>(ow), d_ow_.pitch(),
+                                              d_mask_.ptr<uint8_t>(mask), d_mask_.pitch(), d_vis_.ptr<uint8_t>(picture), d_vis_.pitch(), nullptr,
+                                              nullptr, d_summary_.ptr<long long>(compute));
+        }, {{d_omega_, omega}, {d_div_, div}, {d_ow_, ow}, {d_mask_, mask}, {d_vis_, picture}});
+    }
+    // each waits for the pipeline's stream: of the last push that had an output (include/rcflow.h).  The summary: valid pixels, bad
+    // pixels, cores cw, cores ccw, the bits of the squared threshold (a double), cells with both, pushes, the bits of the largest |omega|
+    std::vector<long long> read() {
+        std::vector<long long> s(8);
+        check(rcflow_kinematics_read(pipe_.context(), 0, nullptr, nullptr, s.data()));
+        return s;
+    }
+    std::vector<rc_kinematics_cell> cells() {
+        std::vector<rc_kinematics_cell> r((size_t)cells_);
+        check(rcflow_kinematics_read(pipe_.context(), 0, r.data(), nullptr, nullptr));
+        return r;
+    }
+    std::vector<long long> sums() {
+        std::vector<long long> s((size_t)cells_ * RC_KINEMATICS_SUMS);
+        check(rcflow_kinematics_read(pipe_.context(), 0, nullptr, s.data(), nullptr));
+        return s;
+    }
+    void set(double ow_k, double ow_min, double omega_min, double vis_max) {
+        check(rcflow_kinematics_set(pipe_.context(), 0, ow_k, ow_min, omega_min, vis_max));
+    }
+    rc_kinematics_info info() { rc_kinematics_info i; check(rcflow_kinematics_info(pipe_.context(), 0, &i)); return i; }
+    void reset() { check(rcflow_kinematics_reset(pipe_.context(), 0)); }
+
+  private:
+    Pipeline& pipe_;
+    int cells_ = 0;
+    DeviceImage d_flow_, d_omega_, d_div_, d_ow_, d_mask_, d_vis_, d_summary_;
+};
+
 }  // namespace rc

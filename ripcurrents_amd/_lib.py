@@ -61,6 +61,10 @@ RC_TRANSECTS_GRAY, RC_TRANSECTS_FLOW = 1, 2
 RC_TRANSECTS_EMPTY, RC_TRANSECTS_FLAT, RC_TRANSECTS_EDGE = 1, 2, 4
 RC_TRANSECTS_MAX_LINES, RC_TRANSECTS_MAX_SAMPLES, RC_TRANSECTS_MAX_TOTAL, RC_TRANSECTS_MAX_WINDOW = 64, 1024, 65536, 4096
 RC_TRANSECTS_MAX_LAG, RC_TRANSECTS_MAX_RANGE, RC_TRANSECTS_MAX_STATE_BYTES, RC_TRANSECTS_SUMS, RC_TRANSECTS_LAUNCHES = 8, 16, 1 << 30, 16, 3
+# rcflow_kinematics_*: the parameter flag, the record's flags, the bounds, the int64 per cell of d_sums, the launches of a push with an output
+RC_KINEMATICS_RELATIVE = 1
+RC_KINEMATICS_EMPTY, RC_KINEMATICS_CW, RC_KINEMATICS_CCW = 1, 2, 4
+RC_KINEMATICS_MAX_RADIUS, RC_KINEMATICS_MAX_SPACING, RC_KINEMATICS_MAX_PIXELS, RC_KINEMATICS_SUMS, RC_KINEMATICS_LAUNCHES = 8, 8, 1 << 25, 11, 2
 
 ERRORS = {-1: "RC_EINVAL", -2: "RC_ENOMEM", -3: "RC_EHIP", -4: "RC_ENODEV", -5: "RC_ESIZE",
           -6: "RC_ESTATE", -7: "RC_ECOMM"}
@@ -232,6 +236,26 @@ class TransectsInfo(C.Structure):
     _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", TransectsParams), ("lines", C.c_int), ("samples", C.c_int),
                 ("launches_per_push", C.c_int), ("held", C.c_int), ("pairs", C.c_int), ("pad", C.c_int), ("pushes", C.c_longlong),
                 ("device_bytes", C.c_size_t)]
+
+
+class KinematicsParams(C.Structure):
+    """rc_kinematics_params (include/rcflow.h)."""
+    _fields_ = [("radius", C.c_int), ("spacing", C.c_int), ("grid_x", C.c_int), ("grid_y", C.c_int), ("min_core", C.c_int), ("flags", C.c_int),
+                ("pad", C.c_int * 2), ("sigma", C.c_double), ("scale", C.c_double), ("pixel_area", C.c_double), ("ow_k", C.c_double),
+                ("ow_min", C.c_double), ("omega_min", C.c_double), ("vis_max", C.c_double)]
+
+
+class KinematicsCell(C.Structure):
+    """rc_kinematics_cell (include/rcflow.h), 48 bytes; numpy: api.KINEMATICS_CELL_DTYPE."""
+    _fields_ = [("flags", C.c_int), ("n", C.c_int), ("bad", C.c_int), ("mean_vorticity", C.c_float), ("circulation", C.c_float),
+                ("mean_divergence", C.c_float), ("enstrophy", C.c_float), ("mean_ow", C.c_float), ("cores_cw", C.c_int), ("cores_ccw", C.c_int),
+                ("circulation_cw", C.c_float), ("circulation_ccw", C.c_float)]
+
+
+class KinematicsInfo(C.Structure):
+    """rc_kinematics_info (include/rcflow.h)."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", KinematicsParams), ("margin", C.c_int), ("launches_per_push", C.c_int),
+                ("pushes", C.c_longlong), ("device_bytes", C.c_size_t)]
 
 
 class FitParams(C.Structure):
@@ -431,6 +455,14 @@ SIGNATURES = {
     "rcflow_transects_reset": [_vp, _i],
     "rcflow_transects_close": [_vp, _i],
     "rcflow_transects_info": [_vp, _i, C.POINTER(TransectsInfo)],
+    "rcflow_kinematics_taps": [_i, _d, C.POINTER(C.c_float)],
+    "rcflow_kinematics_open": [_vp, _i, _i, _i, C.POINTER(KinematicsParams)],
+    "rcflow_kinematics_push_dev": [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp],
+    "rcflow_kinematics_read": [_vp, _i, _vp, _vp, C.POINTER(C.c_longlong)],
+    "rcflow_kinematics_set": [_vp, _i, _d, _d, _d, _d],
+    "rcflow_kinematics_reset": [_vp, _i],
+    "rcflow_kinematics_close": [_vp, _i],
+    "rcflow_kinematics_info": [_vp, _i, C.POINTER(KinematicsInfo)],
     "rcflow_comm_unique_id": [_vp],
     "rcflow_comm_init": [_vp, _vp, _i, _i],
     "rcflow_comm_destroy": [_vp],

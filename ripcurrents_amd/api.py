@@ -39,8 +39,9 @@ from ._lib import PlanViewInfo, PlanViewParams
 from ._lib import WavesInfo, WavesParams
 from ._lib import RC_PIV_REPLACE, PivInfo, PivParams
 from ._lib import RC_TRANSECTS_FLOW, RC_TRANSECTS_GRAY, RC_TRANSECTS_SUMS, TransectLine, TransectsInfo, TransectsParams
+from ._lib import RC_KINEMATICS_MAX_RADIUS, RC_KINEMATICS_RELATIVE, RC_KINEMATICS_SUMS, KinematicsInfo, KinematicsParams
 
-__all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState", "Waves", "Piv", "Transects"]
+__all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState", "Waves", "Piv", "Transects", "Kinematics"]
 
 
 # rc_draw_prim as a numpy record (32 bytes): what Context.draw takes and Context.tracers_prims returns
@@ -79,6 +80,14 @@ TRANSECT_GEOM_DTYPE = np.dtype([("first", "<i4"), ("n", "<i4"), ("ex", "<f4"), (
 # the int64 of a line in d_sums / the sums output of transects_push
 TRANSECTS_SUMS = ("flux_pos", "flux_neg", "flux_along", "valid", "bad", "jets", "jet_start", "jet_len", "jet_sum", "jet_peak", "jet_peak_at",
                   "N", "num", "va", "vb", "q")
+# the eight words of a kinematics summary, in order
+KINEMATICS_SUMMARY = ("valid", "bad", "cores_cw", "cores_ccw", "t2_bits", "cells_both", "pushes", "max_omega_bits")
+# rc_kinematics_cell as a numpy record (48 bytes): what Context.kinematics_read returns
+KINEMATICS_CELL_DTYPE = np.dtype([("flags", "<i4"), ("n", "<i4"), ("bad", "<i4"), ("mean_vorticity", "<f4"), ("circulation", "<f4"),
+                                  ("mean_divergence", "<f4"), ("enstrophy", "<f4"), ("mean_ow", "<f4"), ("cores_cw", "<i4"),
+                                  ("cores_ccw", "<i4"), ("circulation_cw", "<f4"), ("circulation_ccw", "<f4")])
+# the int64 of a cell in d_sums / the sums output of kinematics_push
+KINEMATICS_SUMS = ("n_valid", "n_bad", "omega", "div", "e", "ow", "w2", "cores_cw", "cores_ccw", "omega_cw", "omega_ccw")
 # rc_track as a numpy record (128 bytes): what Context.tracks_read returns
 TRACK_DTYPE = np.dtype([("id", "<i8"), ("parent", "<i8"), ("first_push", "<i8"), ("area_sum", "<i8"), ("fx_sum", "<i8"), ("fy_sum", "<i8"),
                         ("m_sum", "<i8"), ("slot", "<i4"), ("label", "<i4"), ("flags", "<i4"), ("age", "<i4"), ("hits", "<i4"),
@@ -1703,6 +1712,69 @@ class Context:
     def transects_close(self, stream=0):
         self._lifecycle("transects", "close", stream)
 
+    # ------------------------------------------------------------------ flow kinematics
+    def kinematics_open(self, w, h, radius=2, sigma=1.5, spacing=1, grid_x=1, grid_y=1, scale=1.0, pixel_area=1.0, ow_k=0.2, ow_min=0.0,
+                        omega_min=0.0, min_core=1, vis_max=0.5, relative=True, stream=0):
+        """Opens the slot's flow kinematics for w x h flow fields (include/rcflow.h, "flow kinematics"): the field smoothed with
+        Gaussian taps of half-width `radius`, central differences at +-spacing times `scale` (frames per second for a pixel field),
+        vorticity (positive: clockwise on the picture), divergence and the Okubo-Weiss parameter, the vortex cores (ow below
+        -ow_k standard deviations of ow with relative=True, else below -ow_min; |omega| at least omega_min) and a record per cell
+        of a grid_x x grid_y grid.  The state takes 8 bytes per pixel of device memory."""
+        p = KinematicsParams(radius=int(radius), spacing=int(spacing), grid_x=int(grid_x), grid_y=int(grid_y), min_core=int(min_core),
+                             flags=RC_KINEMATICS_RELATIVE if relative else 0, sigma=float(sigma), scale=float(scale),
+                             pixel_area=float(pixel_area), ow_k=float(ow_k), ow_min=float(ow_min), omega_min=float(omega_min),
+                             vis_max=float(vis_max))
+        self._bind(stream)          # the state is zeroed on the slot's stream: the one the pushes will run on
+        check(self._lib.rcflow_kinematics_open(self._h, stream, int(w), int(h), C.byref(p)))
+
+    def kinematics_info(self, stream=0):
+        """dict(w, h, the parameters, relative, margin, launches_per_push, pushes, device_bytes); never blocks."""
+        i = self._info("kinematics", KinematicsInfo(), stream)
+        d = _record(i, skip=("flags", "pad"))
+        d["relative"] = bool(i.prm.flags & RC_KINEMATICS_RELATIVE)
+        return d
+
+    def kinematics_push(self, flow, omega=None, div=None, ow=None, mask=None, vis=None, cells=None, sums=None, summary=None, stream=0):
+        """One flow field (HxWx2 float32 device tensor, dense pixels, rows may be padded); nothing is synchronised.  Outputs are
+        preallocated device tensors, each optional: omega, div and ow HxW float32, mask HxW uint8 (255 at a vortex core: what
+        regions_push takes), vis HxWx3 uint8, cells GYxGXx48 uint8 (rc_kinematics_cell records; view the host copy as
+        KINEMATICS_CELL_DTYPE), sums GYxGXx11 int64 (KINEMATICS_SUMS), summary 8 int64 (KINEMATICS_SUMMARY).  Without any output
+        the push only counts; with any it is RC_KINEMATICS_LAUNCHES.  Records, sums and summary also stay on the slot for
+        kinematics_read."""
+        i = self._info("kinematics", KinematicsInfo(), stream)
+        h, w, nc = i.h, i.w, i.prm.grid_x * i.prm.grid_y
+        fp, fstep = self._in_image(flow, torch.float32, "flow", (h, w, 2))
+        images = (self._out_image(omega, torch.float32, "omega", (h, w)) + self._out_image(div, torch.float32, "div", (h, w)) +
+                  self._out_image(ow, torch.float32, "ow", (h, w)) + self._out_image(mask, torch.uint8, "mask", (h, w)) +
+                  self._out_image(vis, torch.uint8, "vis", (h, w, 3)))
+        cp = self._out_array(cells, torch.uint8, "cells", nc * 48)
+        sp = self._out_array(sums, torch.int64, "sums", nc * RC_KINEMATICS_SUMS)
+        up = self._out_array(summary, torch.int64, "summary", 8)
+        self._bind(stream)
+        check(self._lib.rcflow_kinematics_push_dev(self._h, stream, fp, fstep, *images, cp, sp, up))
+
+    def kinematics_read(self, stream=0):
+        """Waits for the slot's stream -> (cells GYxGX KINEMATICS_CELL_DTYPE, sums GYxGXx11 int64, dict of the summary by
+        KINEMATICS_SUMMARY names, with t2: the squared threshold, and max_omega: the largest |omega| as a float) of the last push
+        that had an output; zeros before that."""
+        info = self.kinematics_info(stream)
+        gx, gy = info["grid_x"], info["grid_y"]
+        cells, sums = np.zeros((gy, gx), KINEMATICS_CELL_DTYPE), np.zeros((gy, gx, RC_KINEMATICS_SUMS), np.int64)
+        out = self._summary(self._lib.rcflow_kinematics_read, stream, KINEMATICS_SUMMARY, cells.ctypes.data, sums.ctypes.data,
+                            bits=("max_omega_bits", "max_omega", float))
+        out["t2"] = float(np.array([out["t2_bits"]], np.int64).view(np.float64)[0])
+        return cells, sums, out
+
+    def kinematics_set(self, ow_k, ow_min, omega_min, vis_max, stream=0):
+        """ow_k, ow_min, omega_min and vis_max from the next push on."""
+        check(self._lib.rcflow_kinematics_set(self._h, stream, float(ow_k), float(ow_min), float(omega_min), float(vis_max)))
+
+    def kinematics_reset(self, stream=0):
+        self._lifecycle("kinematics", "reset", stream)
+
+    def kinematics_close(self, stream=0):
+        self._lifecycle("kinematics", "close", stream)
+
     # ------------------------------------------------------------------ rip regions
     def regions_open(self, w, h, connectivity=8, min_area=1, max_regions=1024, stream=0):
         """Opens the slot's region labelling for w x h masks: connected components (4 or 8 neighbours) numbered in raster
@@ -2022,6 +2094,22 @@ class Transects(_Product):
 
     def set(self, jet_min, vis_max):
         self.ctx.transects_set(jet_min, vis_max, self.stream)
+
+
+class Kinematics(_Product):
+    """The flow kinematics of one slot as an object: Context.kinematics_* with the context and the slot bound.  Opens on
+    construction (the parameters of Context.kinematics_open as keywords), closes on close() or at the end of a with block."""
+    product = "kinematics"
+
+    def set(self, ow_k, ow_min, omega_min, vis_max):
+        self.ctx.kinematics_set(ow_k, ow_min, omega_min, vis_max, self.stream)
+
+
+def kinematics_taps(radius, sigma):
+    """rcflow_kinematics_taps: the smoothing taps g_0..g_radius as float32, without a context or a GPU."""
+    taps = np.zeros(max(0, min(int(radius), RC_KINEMATICS_MAX_RADIUS)) + 1, np.float32)
+    check(_lib.load().rcflow_kinematics_taps(int(radius), float(sigma), taps.ctypes.data_as(C.POINTER(C.c_float))))
+    return taps
 
 
 def _transect_lines(lines):

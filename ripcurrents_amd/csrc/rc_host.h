@@ -289,6 +289,22 @@ struct RcTransects {
     RcZeroFence zf;
 };
 
+// Flow kinematics of one stream slot (kinematics_kernels.hip).  Everything is allocated by rcflow_kinematics_open and released
+// by rcflow_kinematics_close / rcflow_destroy.
+struct RcKinematics {
+    bool open = false;
+    int w = 0, h = 0;
+    rc_kinematics_params prm{};     // ow_k, ow_min, omega_min and vis_max: as rcflow_kinematics_set left them
+    float taps[RC_KINEMATICS_MAX_RADIUS + 1] = {};
+    long long pushes = 0;           // since open / reset
+    RcBuf planes;                   // [2][h][w] float between the launches: omega (one NaN pattern where the pixel is not valid) | ow
+    RcBuf acc;                      // [cells][RC_KINEMATICS_SUMS] int64 the launches add into, zero between pushes
+    RcBuf out;                      // the last computing push: summary 8 int64 | sums [cells][RC_KINEMATICS_SUMS] int64 | records [cells]
+    RcBuf ctl;                      // KnCtl: the tickets, the largest |omega| and T2, zero between pushes
+    RcBuf jet;                      // COLORMAP_JET LUT (768 B), written once by open
+    RcZeroFence zf;
+};
+
 // warp_kernels.hip: one launch of the affine / perspective warp
 struct RcWarpArgs {
     const uint8_t* src; size_t step;
@@ -370,6 +386,7 @@ struct RcSlot {
     RcWaves wv;
     RcPiv piv;
     RcTransects ts;
+    RcKinematics kn;
     RcPhaseCorr pc;
 };
 
@@ -428,7 +445,9 @@ struct rc_ctx {
 // same frames, so they are booked with those, under "overlay".  The ensemble PIV estimates a velocity field from a frame pair
 // as the Farneback kernels do, and its field goes where theirs goes, so it is booked with them, under "farneback".  The transects
 // sample the frame and the field along lines and keep what they find from push to push, as the tracer lines do with their
-// vertices, and are booked with them, under "stream".
+// vertices, and are booked with them, under "stream".  The flow kinematics differentiate one flow field, pixel for pixel, with
+// no state from push to push: an operation on the field as the shear-rate colouring among the post-ops (flow_postop) is, so they
+// are booked with those, under "farneback".
 #define RC_BUCKET_TABLE(X) \
     X(RC_B_FARNEBACK, "farneback") X(RC_B_POLAR, "polar") X(RC_B_THRESHOLD, "threshold") X(RC_B_OVERLAY, "overlay") \
     X(RC_B_EROSION, "erosion") X(RC_B_CODEC, "codec") X(RC_B_STREAM, "stream")
@@ -468,7 +487,8 @@ struct rc_ctx {
     X(RC_K_PLANVIEW, "planview", RC_B_FARNEBACK) /* @0 the table (open), @1 the push */ \
     X(RC_K_WAVES, "waves", RC_B_OVERLAY) /* @0 spectrum, @1 cell sums and closing, @2 bin map and picture */ \
     X(RC_K_PIV, "piv", RC_B_FARNEBACK) /* @0 the pair's sums, ring and accumulators, @1 score, peak and records, @2 validation, field, picture, summary */ \
-    X(RC_K_TRANSECTS, "transects", RC_B_STREAM) /* @0 sampling, rings and accumulators, @1 velocity, transport, jets, records and summary, @2 time stack and Hovmoeller picture */
+    X(RC_K_TRANSECTS, "transects", RC_B_STREAM) /* @0 sampling, rings and accumulators, @1 velocity, transport, jets, records and summary, @2 time stack and Hovmoeller picture */ \
+    X(RC_K_KINEMATICS, "kinematics", RC_B_FARNEBACK) /* @0 smoothing, derivatives, invariants, first sums and the threshold, @1 cores, mask, picture, records and summary */
 #define RC_ROW_ID(id, ...) id,
 enum { RC_BUCKET_TABLE(RC_ROW_ID) RC_B_BUCKETS };
 enum { RC_KIND_TABLE(RC_ROW_ID) RC_K_KINDS };
@@ -549,7 +569,7 @@ struct RcProfScope {
     } while (0)
 
 // ---------------------------------------------------------------------------- per-slot products
-// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView, RcWaves, RcPiv and RcTransects share one lifecycle.  A product supplies
+// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView, RcWaves, RcPiv, RcTransects and RcKinematics share one lifecycle.  A product supplies
 //   void rc_state_free(T&)             frees every buffer and the fence; the state is T() again
 //   int rc_state_zero(RcSlot&, T&)     rc_fence_zero of what open / reset clear, and the counters
 // and open / reset / close are written once, here.
@@ -565,6 +585,7 @@ void rc_state_free(RcPlanView& v);
 void rc_state_free(RcWaves& v);
 void rc_state_free(RcPiv& v);
 void rc_state_free(RcTransects& v);
+void rc_state_free(RcKinematics& k);
 int rc_state_zero(RcSlot& s, RcTimex& t);
 int rc_state_zero(RcSlot& s, RcFrameStab& f);
 int rc_state_zero(RcSlot& s, RcRipMap& m);
@@ -577,6 +598,7 @@ int rc_state_zero(RcSlot& s, RcPlanView& v);
 int rc_state_zero(RcSlot& s, RcWaves& v);
 int rc_state_zero(RcSlot& s, RcPiv& v);
 int rc_state_zero(RcSlot& s, RcTransects& v);
+int rc_state_zero(RcSlot& s, RcKinematics& k);
 
 // The tail of every open.  The caller has validated, selected the device and built `fresh` (rc: what its allocations
 // returned).  The state that is open is touched only once nothing can be refused any more: a refused open leaves it as it
