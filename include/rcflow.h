@@ -1822,6 +1822,154 @@ int rcflow_kinematics_close(rc_ctx* ctx, int stream);
 /* never blocks; RC_ESTATE when nothing is open, RC_EINVAL without a buffer (as rcflow_transects_info) */
 int rcflow_kinematics_info(rc_ctx* ctx, int stream, rc_kinematics_info* info);
 
+/* ------------------------------------------------------------------ shoreline: wet/dry split, waterline per line, runup
+ * Every product above measures the water; this one says where it ends.  The waterline fixes where "offshore" is and bounds the
+ * surf zone the opposing-flow map, the regions and the transects are read in; its movement over a window is the runup, whose
+ * excursion and per-mille exceedance position are the statistics of the swash.  It takes the pictures that are already on the
+ * device: the time-exposure MEAN, the plan view's picture, a raw 8UC3 frame, or an 8UC1 plane of the caller's.  The reference
+ * has no such product.  tests/_shoreline_ref.py states the following in numpy and the kernels equal it bit for bit on every
+ * output.  Everything is exact integer arithmetic except the two places that say double; there every operation is rounded on
+ * its own.
+ *
+ *  Geometry (host, once; rcflow_shoreline_plan gives it without a context).  Lines are rc_transect_line records running FROM
+ *  LAND (x0, y0) TO SEA (x1, y1), listed in alongshore order.  The table (rc_transect_sample) and the per-line constants
+ *  (rc_transect_geom) are those of rcflow_transects_plan with fps = 1: positions quantised to 1/16 pixel, ds in metres.  Limits
+ *  of its own: 1..RC_SHORE_MAX_LINES lines, n in RC_SHORE_MIN_SAMPLES..RC_SHORE_MAX_SAMPLES, S = sum of n at most
+ *  RC_SHORE_MAX_TOTAL.
+ *  1. "shoreline@0", pixels.  Indicator I per pixel: RC_SHORE_RMB byte2 - byte0 + 255 (R - B + 255 of a BGR picture, 0..510),
+ *     RC_SHORE_GRAY (byte0 * 1868 + byte1 * 9617 + byte2 * 4899 + 8192) >> 14 (the library's BGR -> grey integers),
+ *     RC_SHORE_PLANE the byte of the caller's 8UC1 plane.  Box sum over (2 r + 1)^2 with a REPLICATED border (coordinates clamped
+ *     to the picture: harmless for an intensity, unlike the kinematics' derivatives).  A = (2 r + 1)^2; J = (2 sum + A) / (2 A),
+ *     uint16 in 0..510, kept in a state plane.  Histogram of J, 511 live bins of uint32, over every pixel or over those where
+ *     the push's d_roi (8UC1) is non-zero; N its total.  Otsu, by the launch's last-arriving workgroup: S1 = sum i h[i],
+ *     S2 = sum i^2 h[i]; for t = 0..509 in order w0 += h[t], m0 += t h[t], w1 = N - w0, t skipped when w0 or w1 is 0;
+ *     a = S1 w0 - m0 N (int64); s = ((double)a * (double)a) / ((double)w0 * (double)w1); the FIRST largest s wins, thr its t.
+ *     tot = (double)N * (double)S2 - (double)S1 * (double)S1; eta = tot > 0 ? s / tot : 0, Otsu's separability in 0..1.  With
+ *     no admissible t (N = 0, or one bin) thr = -1 and eta = 0.  A fixed threshold >= 0 is used as given, eta is s / tot of
+ *     that t (0 when it is skipped), and thr is still -1 when N = 0.  With thr = -1 every line is RC_SHORE_EMPTY (k 0, pos -1,
+ *     agree 0) and the mask is 0.  w * h <= RC_SHORE_MAX_PIXELS keeps every int64 below 2^59.
+ *  2. "shoreline@1", lines, a wave a line.  V[j]: the integer bilinear sample of J at the table position, the GRAY formula of the
+ *     transects (weights in 16ths, + 128 >> 8, ix1 = min(ix + 1, w - 1), iy1 likewise).  wet[j] = V[j] <= thr, or V[j] > thr with
+ *     wet_is_high.  BEST SPLIT, not first crossing: for k in 0..n, score(k) = #dry in [0, k) + #wet in [k, n); k* is the smallest
+ *     k of the largest score (the most landward among equals), agree = score(k*).  k* = n: RC_SHORE_DRY, k* = 0: RC_SHORE_WET,
+ *     both with pos = -1 and wx = wy = 0.  Otherwise sample k* - 1 is dry and k* is wet; a = V[k* - 1], b = V[k*], d = |b - a|,
+ *     e = |2 thr + 1 - 2 a|; frac = (e * 256 + d) / (2 d), 0..256; pos = (k* - 1) * 256 + frac, in 1/256 sample.
+ *     RC_SHORE_UNSURE on every line that is not EMPTY when eta < min_sep.  The waterline point in 1/256 pixel, from the table's
+ *     end positions Xa, Xb (1/16 px): wx = 16 Xa + floor((16 (Xb - Xa) pos + 128 (n - 1)) / (256 (n - 1))), wy likewise.
+ *  3. "shoreline@2", along the shore and over the window, a workgroup a line.  On each side of line i the neighbour is the
+ *     nearest line within 2 places that has a position in this push (outliers included).  A line with a position and a neighbour
+ *     is RC_SHORE_OUTLIER when for every such neighbour max(|dwx|, |dwy|) > (int64)rint(max_jump * 256).  It keeps pos, wx and wy.
+ *     Ring: slot pushes mod T of the line takes pos, or -1 for no position or an outlier.  Over the held = min(pushes + 1, T)
+ *     slots, on the values >= 0: nv, pos_min, pos_max, the int64 sum, and pos_q = the value at ascending rank
+ *     (nv * p + 999) / 1000 - 1, the position that p per mille of the waterlines reached or passed landward; all 0 with
+ *     RC_SHORE_NO_WINDOW when nv = 0.  Record: x = (float)((double)wx / 256), y likewise, dist_m = (float)(((double)pos / 256)
+ *     * ds) (0 without a position), pos_mean = (float)((double)sum / (double)nv), excursion_m = (float)(((double)(pos_max -
+ *     pos_min) / 256) * ds).  Summary, 8 int64: thr | N | (int64)rint(eta * 2^32) | lines with a position and no OUTLIER | DRY
+ *     lines | WET lines | outliers | pushes since open / reset.
+ *  4. "shoreline@3", when a picture is asked for: d_mask 8UC1, 255 where J is wet (what rcflow_regions_push_dev and
+ *     rcflow_create_edges_dev take); d_plane 16UC1, J; d_hist 512 uint32, the last bin 0.
+ *  5. "shoreline@4": rcflow_shoreline_prims_dev gives 2 lines - 1 primitives of the last push for rcflow_draw_dev: record 2 i a
+ *     disc at ((wx + 128) >> 8, (wy + 128) >> 8) for line i when it has a position and is no OUTLIER; record 2 i + 1 the
+ *     segment from such a line i to the next such line after it (lines between them that have none are bridged); all-zero
+ *     records elsewhere, as rcflow_regions_prims_dev leaves them. */
+#define RC_SHORE_RMB 0                   /* rc_shoreline_params::source */
+#define RC_SHORE_GRAY 1
+#define RC_SHORE_PLANE 2
+#define RC_SHORE_EMPTY 1                 /* rc_shoreline::flags */
+#define RC_SHORE_DRY 2
+#define RC_SHORE_WET 4
+#define RC_SHORE_UNSURE 8
+#define RC_SHORE_OUTLIER 16
+#define RC_SHORE_NO_WINDOW 32
+#define RC_SHORE_MAX_LINES 1024
+#define RC_SHORE_MIN_SAMPLES 8
+#define RC_SHORE_MAX_SAMPLES 1024
+#define RC_SHORE_MAX_TOTAL 262144
+#define RC_SHORE_MAX_RADIUS 7
+#define RC_SHORE_MAX_WINDOW 4096
+#define RC_SHORE_MAX_PIXELS (1 << 25)
+#define RC_SHORE_MAX_STATE_BYTES (64ull << 20)   /* the ring: window x lines int32 */
+#define RC_SHORE_HIST 512                /* uint32 in d_hist: 511 live bins and a zero */
+#define RC_SHORE_LAUNCHES 4              /* of a push that asks for a picture; 3 otherwise */
+typedef struct rc_shoreline_params {
+    int source;             /* RC_SHORE_RMB, RC_SHORE_GRAY (both 8UC3) or RC_SHORE_PLANE (8UC1) */
+    int radius;             /* r: 0..RC_SHORE_MAX_RADIUS, half-width of the box */
+    int wet_is_high;        /* 0: wet where J <= thr; 1: wet where J > thr */
+    int threshold;          /* -1: Otsu; 0..509: fixed */
+    int window;             /* T: 2..RC_SHORE_MAX_WINDOW pushes held per line */
+    int permille;           /* p: 1..999 */
+    int flags;              /* 0 */
+    int pad;
+    double min_sep;         /* 0..1: below this separability every line is RC_SHORE_UNSURE */
+    double max_jump;        /* pixels, > 0 and <= 16384: the outlier test */
+    double metres_per_pixel; /* finite, > 0 */
+} rc_shoreline_params;
+typedef struct rc_shoreline {
+    int flags;              /* RC_SHORE_EMPTY, DRY, WET, UNSURE, OUTLIER, NO_WINDOW */
+    int k;                  /* k*: the first wet sample of the best split */
+    int pos;                /* 1/256 sample from the land end, or -1 */
+    int agree;              /* score(k*): samples on the side the split puts them */
+    int wx, wy;             /* the waterline point in 1/256 pixel */
+    float x, y;             /* the same in pixels */
+    float dist_m;           /* metres from the land end */
+    int nv;                 /* positions in the window */
+    int pos_min, pos_max, pos_q;
+    float pos_mean;
+    float excursion_m;      /* metres between pos_min and pos_max */
+    int pad;
+} rc_shoreline;             /* 64 bytes */
+typedef struct rc_shoreline_info {
+    int w, h;
+    rc_shoreline_params prm;           /* threshold, min_sep and max_jump as rcflow_shoreline_set left them */
+    int lines, samples;                /* S */
+    int launches_per_push;             /* RC_SHORE_LAUNCHES */
+    int held;                          /* min(pushes, T) */
+    long long pushes;                  /* since open / reset */
+    size_t device_bytes;
+} rc_shoreline_info;
+/* The geometry alone: no context, no GPU.  table: S records in line order, geom: n_lines records, total: S; each may be NULL.
+ * RC_EINVAL: no lines, more than RC_SHORE_MAX_LINES, an n outside RC_SHORE_MIN_SAMPLES..RC_SHORE_MAX_SAMPLES, S above
+ * RC_SHORE_MAX_TOTAL, an endpoint that is not finite, a line of no length, a sample outside the picture, metres_per_pixel not
+ * finite and > 0. */
+int rcflow_shoreline_plan(int w, int h, const rc_transect_line* lines, int n_lines, double metres_per_pixel,
+                          rc_transect_sample* table, rc_transect_geom* geom, int* total);
+/* Allocates everything the slot will ever need: the table, the plane (2 B/px), the ring (4 T lines bytes), the records.
+ * Re-opening replaces the state; a refused open leaves the open state as it was.  RC_EINVAL as rcflow_shoreline_plan, no
+ * parameters, a value outside the ranges above, unknown flag bits; RC_ESIZE beyond the context's max_w x max_h, w * h above
+ * RC_SHORE_MAX_PIXELS, or a ring above RC_SHORE_MAX_STATE_BYTES. */
+int rcflow_shoreline_open(rc_ctx* ctx, int stream, int w, int h, const rc_transect_line* lines, int n_lines, const rc_shoreline_params* prm);
+/* One picture: d_image w x h with `channels` bytes a pixel, 3 for RC_SHORE_RMB and RC_SHORE_GRAY, 1 for RC_SHORE_PLANE (anything
+ * else is RC_EINVAL); d_roi (8UC1, may be NULL): the histogram counts where it is non-zero.  Outputs (device memory, each may be
+ * NULL): d_records lines x rc_shoreline (4-byte aligned), d_mask 8UC1, d_plane 16UC1 (pointer and step multiples of 2), d_hist
+ * RC_SHORE_HIST uint32 (4-byte aligned), d_summary 8 int64 (8-byte aligned).  "shoreline@0..@2" run on every push, because the
+ * ring must be fed; "shoreline@3" follows when d_mask, d_plane or d_hist is asked for; what a push gives does not depend on which
+ * outputs earlier pushes asked for.  No host synchronisation, no device-to-host copy.  An output whose byte range overlaps an
+ * input's or another output's is RC_EINVAL.  Row padding is never written.  Every refusal is decided before anything is queued
+ * and leaves the state as it was; RC_ESTATE before rcflow_shoreline_open.  RC_EHIP (the runtime refused a launch) is no refusal:
+ * launches before it may have written the ring while the push count stays, so the state is undefined until
+ * rcflow_shoreline_reset. */
+int rcflow_shoreline_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_image, size_t step, int channels, const uint8_t* d_roi, size_t roi_step,
+                              rc_shoreline* d_records, uint8_t* d_mask, size_t mask_step, uint16_t* d_plane, size_t plane_step,
+                              uint32_t* d_hist, long long* d_summary);
+/* 2 lines - 1 primitives of the last push into d_prims ("shoreline@4"); thickness and disc_radius as rcflow_regions_prims_dev */
+int rcflow_shoreline_prims_dev(rc_ctx* ctx, int stream, uint32_t color, int thickness, int disc_radius, rc_draw_prim* d_prims);
+/* Blocks until the slot's stream has finished; for hosts and tests.  Each may be NULL: the records and the summary of the last
+ * push (host memory); zeros before the first. */
+int rcflow_shoreline_read(rc_ctx* ctx, int stream, rc_shoreline* records, long long summary[8]);
+/* Blocks.  The runup time series, lines x T int32 (host memory): per line the held positions oldest first, then -1 up to T */
+int rcflow_shoreline_ring_read(rc_ctx* ctx, int stream, int* ring);
+/* Blocks.  Each may be NULL: the open session's table (S records) and per-line constants (lines records), from the device */
+int rcflow_shoreline_table_read(rc_ctx* ctx, int stream, rc_transect_sample* table, rc_transect_geom* geom);
+/* threshold, min_sep and max_jump from the next push on; RC_EINVAL as rcflow_shoreline_open */
+int rcflow_shoreline_set(rc_ctx* ctx, int stream, int threshold, double min_sep, double max_jump);
+/* zeroes the ring, the records, the summary and the push count; keeps the table, the allocation and the parameters as
+ * rcflow_shoreline_set left them; asynchronous, on the slot's stream */
+int rcflow_shoreline_reset(rc_ctx* ctx, int stream);
+/* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
+int rcflow_shoreline_close(rc_ctx* ctx, int stream);
+/* never blocks; RC_ESTATE when nothing is open, RC_EINVAL without a buffer */
+int rcflow_shoreline_info(rc_ctx* ctx, int stream, rc_shoreline_info* info);
+
 /* Display path, ripcurrents.cpp:233-273 (= streamline_displacement / _total_motion / _ratio /
  * _positions, ripcurrents_module.cpp:13-60) on the slot's streamline field (rcflow_advect_field_dev):
  * which 0 = |pt|, 1 = dist, 2 = |pt| / dist; minMaxLoc + convertTo(CV_8UC1, 255/max) +
@@ -1902,7 +2050,7 @@ int rcflow_profile_read(rc_ctx* ctx, int cap, const char** names, int* launches,
 
 /* The same totals under the reference's own bucket names, in the order it prints them (ripcurrents.cpp:103-109,
  * :518-524): farneback, polar, threshold, overlay, erosion, codec, stream ("pathlines").  GPU time of the kernels
- * that do each bucket's work ("overlay" includes the time-exposure images, the 8-bit colour stages and the wave spectra, "farneback" the frame stabilisation, the opposing-flow map, the motion templates, the plan view, the ensemble PIV and the flow kinematics, "stream" the flow map and FTLE and the transects); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
+ * that do each bucket's work ("overlay" includes the time-exposure images, the 8-bit colour stages, the wave spectra and the shoreline, "farneback" the frame stabilisation, the opposing-flow map, the motion templates, the plan view, the ensemble PIV and the flow kinematics, "stream" the flow map and FTLE and the transects); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
  * classification kernels, booked under "threshold"), "codec" is 0 (video decode is host I/O outside the library).
  * names / ms: RC_PROFILE_BUCKETS entries each (either may be NULL).  Returns RC_PROFILE_BUCKETS. */
 #define RC_PROFILE_BUCKETS 7

@@ -1264,4 +1264,61 @@ class Kinematics {
     DeviceImage d_flow_, d_omega_, d_div_, d_ow_, d_mask_, d_vis_, d_summary_;
 };
 
+// Shoreline on the device (rcflow_shoreline_*): the wet/dry split of a picture, the waterline along lines laid from land to sea
+// and its runup statistics over the last `window` pushes.  Host pictures of the pipeline's size in (8UC3, or 8UC1 for
+// RC_SHORE_PLANE); the records, the wet mask and the smoothed plane out.
+class Shoreline {
+  public:
+    Shoreline(Pipeline& pipe, const std::vector<rc_transect_line>& lines, const rc_shoreline_params& prm)
+        : pipe_(pipe), lines_((int)lines.size()), window_(prm.window), channels_(prm.source == RC_SHORE_PLANE ? 1 : 3) {
+        check(rcflow_shoreline_open(pipe.context(), 0, pipe.width(), pipe.height(), lines.data(), (int)lines.size(), &prm));
+    }
+    ~Shoreline() { (void)rcflow_shoreline_close(pipe_.context(), 0); }
+    Shoreline(const Shoreline&) = delete;
+    Shoreline& operator=(const Shoreline&) = delete;
+
+    int lines() const { return lines_; }
+
+    // image: 8UC3 (8UC1 for RC_SHORE_PLANE) of the pipeline's size; roi: 8UC1, the histogram counts where it is non-zero.  Each
+    // output is optional: mask 8UC1 (255 where wet), plane 16UC1 (the smoothed indicator).  The records and the summary stay on
+    // the session after every push, for read() and records().
+    void push(const Mat& image, const Mat* roi = nullptr, Mat* mask = nullptr, Mat* plane = nullptr) {
+        const int w = pipe_.width(), h = pipe_.height();
+        if (!is_image(image, w, h, channels_, 1)) throw Error(RC_EINVAL, "Shoreline::push: the picture must be 8UC3 (8UC1 for a plane) of the pipeline's size");
+        if ((roi && !is_image(*roi, w, h, 1, 1)) || (mask && !is_image(*mask, w, h, 1, 1)) || (plane && !is_image(*plane, w, h, 1, 2)))
+            throw Error(RC_EINVAL, "Shoreline::push: roi and mask 8UC1, plane 16UC1, each of the pipeline's size");
+        staged(pipe_.context(), {{d_image_, &image}, {d_roi_, roi}}, [&] {
+            return rcflow_shoreline_push_dev(pipe_.context(), 0, d_image_.ptr<const uint8_t>(), d_image_.pitch(), channels_,
+                                             d_roi_.ptr<const uint8_t>(roi), d_roi_.pitch(), nullptr, d_mask_.ptr<uint8_t>(mask), d_mask_.pitch(),
+                                             d_plane_.ptr<uint16_t>(plane), d_plane_.pitch(), nullptr, nullptr);
+        }, {{d_mask_, mask}, {d_plane_, plane}});
+    }
+    // each waits for the pipeline's stream: of the last push (include/rcflow.h).  The summary: threshold, pixels counted, the
+    // separability times 2^32, lines with a position, dry lines, wet lines, outliers, pushes; the records, one per line
+    std::vector<long long> read() {
+        std::vector<long long> s(8);
+        check(rcflow_shoreline_read(pipe_.context(), 0, nullptr, s.data()));
+        return s;
+    }
+    std::vector<rc_shoreline> records() {
+        std::vector<rc_shoreline> r((size_t)lines_);
+        check(rcflow_shoreline_read(pipe_.context(), 0, r.data(), nullptr));
+        return r;
+    }
+    // waits: the runup time series, lines x window, per line the held positions oldest first, then -1
+    std::vector<int> ring() {
+        std::vector<int> r((size_t)lines_ * window_);
+        check(rcflow_shoreline_ring_read(pipe_.context(), 0, r.data()));
+        return r;
+    }
+    void set(int threshold, double min_sep, double max_jump) { check(rcflow_shoreline_set(pipe_.context(), 0, threshold, min_sep, max_jump)); }
+    rc_shoreline_info info() { rc_shoreline_info i; check(rcflow_shoreline_info(pipe_.context(), 0, &i)); return i; }
+    void reset() { check(rcflow_shoreline_reset(pipe_.context(), 0)); }
+
+  private:
+    Pipeline& pipe_;
+    int lines_ = 0, window_ = 0, channels_ = 3;
+    DeviceImage d_image_, d_roi_, d_mask_, d_plane_;
+};
+
 }  // namespace rc

@@ -65,6 +65,11 @@ RC_TRANSECTS_MAX_LAG, RC_TRANSECTS_MAX_RANGE, RC_TRANSECTS_MAX_STATE_BYTES, RC_T
 RC_KINEMATICS_RELATIVE = 1
 RC_KINEMATICS_EMPTY, RC_KINEMATICS_CW, RC_KINEMATICS_CCW = 1, 2, 4
 RC_KINEMATICS_MAX_RADIUS, RC_KINEMATICS_MAX_SPACING, RC_KINEMATICS_MAX_PIXELS, RC_KINEMATICS_SUMS, RC_KINEMATICS_LAUNCHES = 8, 8, 1 << 25, 11, 2
+# rcflow_shoreline_*: the sources, the record's flags, the bounds, the words of d_hist, the launches of a push that asks for a picture
+SHORE_SOURCES = {"rmb": 0, "gray": 1, "plane": 2}
+RC_SHORE_EMPTY, RC_SHORE_DRY, RC_SHORE_WET, RC_SHORE_UNSURE, RC_SHORE_OUTLIER, RC_SHORE_NO_WINDOW = 1, 2, 4, 8, 16, 32
+RC_SHORE_MAX_LINES, RC_SHORE_MIN_SAMPLES, RC_SHORE_MAX_SAMPLES, RC_SHORE_MAX_TOTAL, RC_SHORE_MAX_RADIUS, RC_SHORE_MAX_WINDOW = 1024, 8, 1024, 262144, 7, 4096
+RC_SHORE_MAX_PIXELS, RC_SHORE_MAX_STATE_BYTES, RC_SHORE_HIST, RC_SHORE_LAUNCHES = 1 << 25, 64 << 20, 512, 4
 
 ERRORS = {-1: "RC_EINVAL", -2: "RC_ENOMEM", -3: "RC_EHIP", -4: "RC_ENODEV", -5: "RC_ESIZE",
           -6: "RC_ESTATE", -7: "RC_ECOMM"}
@@ -256,6 +261,26 @@ class KinematicsInfo(C.Structure):
     """rc_kinematics_info (include/rcflow.h)."""
     _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", KinematicsParams), ("margin", C.c_int), ("launches_per_push", C.c_int),
                 ("pushes", C.c_longlong), ("device_bytes", C.c_size_t)]
+
+
+class ShorelineParams(C.Structure):
+    """rc_shoreline_params (include/rcflow.h), 56 bytes."""
+    _fields_ = [("source", C.c_int), ("radius", C.c_int), ("wet_is_high", C.c_int), ("threshold", C.c_int), ("window", C.c_int),
+                ("permille", C.c_int), ("flags", C.c_int), ("pad", C.c_int), ("min_sep", C.c_double), ("max_jump", C.c_double),
+                ("metres_per_pixel", C.c_double)]
+
+
+class ShorelineRecord(C.Structure):
+    """rc_shoreline (include/rcflow.h), 64 bytes; numpy: api.SHORELINE_DTYPE."""
+    _fields_ = [("flags", C.c_int), ("k", C.c_int), ("pos", C.c_int), ("agree", C.c_int), ("wx", C.c_int), ("wy", C.c_int), ("x", C.c_float),
+                ("y", C.c_float), ("dist_m", C.c_float), ("nv", C.c_int), ("pos_min", C.c_int), ("pos_max", C.c_int), ("pos_q", C.c_int),
+                ("pos_mean", C.c_float), ("excursion_m", C.c_float), ("pad", C.c_int)]
+
+
+class ShorelineInfo(C.Structure):
+    """rc_shoreline_info (include/rcflow.h)."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", ShorelineParams), ("lines", C.c_int), ("samples", C.c_int),
+                ("launches_per_push", C.c_int), ("held", C.c_int), ("pushes", C.c_longlong), ("device_bytes", C.c_size_t)]
 
 
 class FitParams(C.Structure):
@@ -463,6 +488,17 @@ SIGNATURES = {
     "rcflow_kinematics_reset": [_vp, _i],
     "rcflow_kinematics_close": [_vp, _i],
     "rcflow_kinematics_info": [_vp, _i, C.POINTER(KinematicsInfo)],
+    "rcflow_shoreline_plan": [_i, _i, C.POINTER(TransectLine), _i, C.c_double, _vp, _vp, C.POINTER(C.c_int)],
+    "rcflow_shoreline_open": [_vp, _i, _i, _i, C.POINTER(TransectLine), _i, C.POINTER(ShorelineParams)],
+    "rcflow_shoreline_push_dev": [_vp, _i, _vp, _sz, _i, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp],
+    "rcflow_shoreline_prims_dev": [_vp, _i, C.c_uint32, _i, _i, _vp],
+    "rcflow_shoreline_read": [_vp, _i, _vp, C.POINTER(C.c_longlong)],
+    "rcflow_shoreline_ring_read": [_vp, _i, _vp],
+    "rcflow_shoreline_table_read": [_vp, _i, _vp, _vp],
+    "rcflow_shoreline_set": [_vp, _i, _i, _d, _d],
+    "rcflow_shoreline_reset": [_vp, _i],
+    "rcflow_shoreline_close": [_vp, _i],
+    "rcflow_shoreline_info": [_vp, _i, C.POINTER(ShorelineInfo)],
     "rcflow_comm_unique_id": [_vp],
     "rcflow_comm_init": [_vp, _vp, _i, _i],
     "rcflow_comm_destroy": [_vp],

@@ -40,8 +40,10 @@ from ._lib import WavesInfo, WavesParams
 from ._lib import RC_PIV_REPLACE, PivInfo, PivParams
 from ._lib import RC_TRANSECTS_FLOW, RC_TRANSECTS_GRAY, RC_TRANSECTS_SUMS, TransectLine, TransectsInfo, TransectsParams
 from ._lib import RC_KINEMATICS_MAX_RADIUS, RC_KINEMATICS_RELATIVE, RC_KINEMATICS_SUMS, KinematicsInfo, KinematicsParams
+from ._lib import RC_SHORE_HIST, SHORE_SOURCES, ShorelineInfo, ShorelineParams
 
-__all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState", "Waves", "Piv", "Transects", "Kinematics"]
+__all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState", "Waves", "Piv", "Transects", "Kinematics",
+           "Shoreline"]
 
 
 # rc_draw_prim as a numpy record (32 bytes): what Context.draw takes and Context.tracers_prims returns
@@ -88,6 +90,12 @@ KINEMATICS_CELL_DTYPE = np.dtype([("flags", "<i4"), ("n", "<i4"), ("bad", "<i4")
                                   ("cores_ccw", "<i4"), ("circulation_cw", "<f4"), ("circulation_ccw", "<f4")])
 # the int64 of a cell in d_sums / the sums output of kinematics_push
 KINEMATICS_SUMS = ("n_valid", "n_bad", "omega", "div", "e", "ow", "w2", "cores_cw", "cores_ccw", "omega_cw", "omega_ccw")
+# the eight words of a shoreline summary, in order
+SHORELINE_SUMMARY = ("thr", "N", "eta_q32", "positions", "dry", "wet", "outliers", "pushes")
+# rc_shoreline as a numpy record (64 bytes): what Context.shoreline_read returns
+SHORELINE_DTYPE = np.dtype([("flags", "<i4"), ("k", "<i4"), ("pos", "<i4"), ("agree", "<i4"), ("wx", "<i4"), ("wy", "<i4"), ("x", "<f4"),
+                            ("y", "<f4"), ("dist_m", "<f4"), ("nv", "<i4"), ("pos_min", "<i4"), ("pos_max", "<i4"), ("pos_q", "<i4"),
+                            ("pos_mean", "<f4"), ("excursion_m", "<f4"), ("pad", "<i4")])
 # rc_track as a numpy record (128 bytes): what Context.tracks_read returns
 TRACK_DTYPE = np.dtype([("id", "<i8"), ("parent", "<i8"), ("first_push", "<i8"), ("area_sum", "<i8"), ("fx_sum", "<i8"), ("fy_sum", "<i8"),
                         ("m_sum", "<i8"), ("slot", "<i4"), ("label", "<i4"), ("flags", "<i4"), ("age", "<i4"), ("hits", "<i4"),
@@ -103,6 +111,7 @@ FIT_MODEL_NAMES = {v: k for k, v in FIT_MODELS.items()}
 FTLE_DIRECTION_NAMES = {v: k for k, v in FTLE_DIRECTIONS.items()}
 RIPMAP_SOURCE_NAMES = {v: k for k, v in RIPMAP_SOURCES.items()}
 TRACERS_MOVER_NAMES = {v: k for k, v in TRACERS_MOVERS.items()}
+SHORE_SOURCE_NAMES = {v: k for k, v in SHORE_SOURCES.items()}
 
 
 def _params(pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags):
@@ -1775,6 +1784,91 @@ class Context:
     def kinematics_close(self, stream=0):
         self._lifecycle("kinematics", "close", stream)
 
+    # ------------------------------------------------------------------ shoreline
+    def shoreline_open(self, w, h, lines, source="rmb", radius=2, wet_is_high=0, threshold=-1, window=512, permille=20, min_sep=0.0,
+                       max_jump=8.0, metres_per_pixel=1.0, stream=0):
+        """Opens the slot's shoreline on w x h pictures (include/rcflow.h, "shoreline"): `lines` is a sequence of (x0, y0, x1, y1, n),
+        straight lines in pixels FROM LAND TO SEA with n samples each, listed in alongshore order.  source: "rmb" (R - B + 255 of a
+        BGR picture), "gray", or "plane" (an HxW uint8 indicator of the caller's); the indicator is smoothed by a box of half-width
+        `radius` and split at Otsu's threshold (threshold=-1) or a fixed one; the last `window` positions of every line are held
+        for the runup statistics.  The state takes 2 bytes per pixel and 4 * window bytes per line of device memory."""
+        arr = _transect_lines(lines)
+        p = ShorelineParams(source=SHORE_SOURCES[source], radius=int(radius), wet_is_high=int(wet_is_high), threshold=int(threshold),
+                            window=int(window), permille=int(permille), flags=0, pad=0, min_sep=float(min_sep), max_jump=float(max_jump),
+                            metres_per_pixel=float(metres_per_pixel))
+        self._bind(stream)          # the state is zeroed on the slot's stream: the one the pushes will run on
+        check(self._lib.rcflow_shoreline_open(self._h, stream, int(w), int(h), arr, len(arr), C.byref(p)))
+
+    def shoreline_info(self, stream=0):
+        """dict(w, h, the parameters, source by name, lines, samples, launches_per_push, held, pushes, device_bytes); never blocks."""
+        i = self._info("shoreline", ShorelineInfo(), stream)
+        d = _record(i, skip=("flags", "pad"))
+        d["source"] = SHORE_SOURCE_NAMES[i.prm.source]
+        return d
+
+    def shoreline_push(self, image, roi=None, records=None, mask=None, plane=None, hist=None, summary=None, stream=0):
+        """One picture: HxWx3 uint8 (HxW for the "plane" source) device tensor, rows may be padded; roi: HxW uint8, the histogram
+        counts where it is non-zero; nothing is synchronised.  Outputs are preallocated device tensors, each optional: records
+        LINESx64 uint8 (rc_shoreline records; view the host copy as SHORELINE_DTYPE), mask HxW uint8 (255 where wet: what
+        regions_push takes), plane HxW int16 (the smoothed indicator, 0..510), hist 512 int32, summary 8 int64 (SHORELINE_SUMMARY).
+        Records and summary also stay on the slot for shoreline_read."""
+        i = self._info("shoreline", ShorelineInfo(), stream)
+        h, w, ch = i.h, i.w, 1 if i.prm.source == SHORE_SOURCES["plane"] else 3
+        if not _is_t(image) or image.dim() != (2 if ch == 1 else 3):
+            raise ValueError("image must be an %s uint8 device tensor, as opened" % ("HxW" if ch == 1 else "HxWx3"))
+        ip = self._in_image(image, torch.uint8, "image", (h, w) if ch == 1 else (h, w, 3))
+        qp = self._in_image(roi, torch.uint8, "roi", (h, w), optional=True)
+        rp = self._out_array(records, torch.uint8, "records", i.lines * 64)
+        mp = self._out_image(mask, torch.uint8, "mask", (h, w))
+        pp = self._out_image(plane, torch.int16, "plane", (h, w))
+        hp = self._out_array(hist, torch.int32, "hist", RC_SHORE_HIST)
+        up = self._out_array(summary, torch.int64, "summary", 8)
+        self._bind(stream)
+        check(self._lib.rcflow_shoreline_push_dev(self._h, stream, *ip, ch, *qp, rp, *mp, *pp, hp, up))
+
+    def shoreline_prims(self, color=0x00ffff, thickness=1, disc_radius=2, out=None, stream=0):
+        """The waterline of the last push as 2 * lines - 1 primitives for draw() -> a device uint8 tensor of rc_draw_prim records:
+        a disc per line with a position that is no outlier and a segment to the next such line; kind 0 elsewhere."""
+        out = self._prims_out(out, 2 * self.shoreline_info(stream)["lines"] - 1)
+        self._bind(stream)
+        check(self._lib.rcflow_shoreline_prims_dev(self._h, stream, int(color), int(thickness), int(disc_radius), self._ptr(out)))
+        return out
+
+    def shoreline_read(self, stream=0):
+        """Waits for the slot's stream -> (records LINES SHORELINE_DTYPE, dict of the summary by SHORELINE_SUMMARY names, with eta:
+        Otsu's separability as a float) of the last push; zeros before the first."""
+        rec = np.zeros(self.shoreline_info(stream)["lines"], SHORELINE_DTYPE)
+        out = self._summary(self._lib.rcflow_shoreline_read, stream, SHORELINE_SUMMARY, rec.ctypes.data)
+        out["eta"] = out["eta_q32"] / 4294967296.0
+        return rec, out
+
+    def shoreline_ring(self, stream=0):
+        """Waits -> LINESxWINDOW int32, the runup time series: per line the held positions (1/256 sample) oldest first, -1 where
+        the line had none, and -1 past what is held."""
+        info = self.shoreline_info(stream)
+        ring = np.empty((info["lines"], info["window"]), np.int32)
+        self._bind(stream)
+        check(self._lib.rcflow_shoreline_ring_read(self._h, stream, ring.ctypes.data))
+        return ring
+
+    def shoreline_table(self, stream=0):
+        """Waits -> (SAMPLES TRANSECT_SAMPLE_DTYPE, LINES TRANSECT_GEOM_DTYPE): the open session's table, from the device."""
+        info = self.shoreline_info(stream)
+        table, geom = np.zeros(info["samples"], TRANSECT_SAMPLE_DTYPE), np.zeros(info["lines"], TRANSECT_GEOM_DTYPE)
+        self._bind(stream)
+        check(self._lib.rcflow_shoreline_table_read(self._h, stream, table.ctypes.data, geom.ctypes.data))
+        return table, geom
+
+    def shoreline_set(self, threshold, min_sep, max_jump, stream=0):
+        """threshold, min_sep and max_jump from the next push on."""
+        check(self._lib.rcflow_shoreline_set(self._h, stream, int(threshold), float(min_sep), float(max_jump)))
+
+    def shoreline_reset(self, stream=0):
+        self._lifecycle("shoreline", "reset", stream)
+
+    def shoreline_close(self, stream=0):
+        self._lifecycle("shoreline", "close", stream)
+
     # ------------------------------------------------------------------ rip regions
     def regions_open(self, w, h, connectivity=8, min_area=1, max_regions=1024, stream=0):
         """Opens the slot's region labelling for w x h masks: connected components (4 or 8 neighbours) numbered in raster
@@ -2105,6 +2199,27 @@ class Kinematics(_Product):
         self.ctx.kinematics_set(ow_k, ow_min, omega_min, vis_max, self.stream)
 
 
+class Shoreline(_Product):
+    """The shoreline of one slot as an object: Context.shoreline_* with the context and the slot bound.  Opens on construction
+    (lines and the parameters of Context.shoreline_open as keywords), closes on close() or at the end of a with block."""
+    product = "shoreline"
+
+    def push(self, image, roi=None, **outputs):
+        self.ctx.shoreline_push(image, roi, stream=self.stream, **outputs)
+
+    def prims(self, **kw):
+        return self.ctx.shoreline_prims(stream=self.stream, **kw)
+
+    def ring(self):
+        return self.ctx.shoreline_ring(self.stream)
+
+    def table(self):
+        return self.ctx.shoreline_table(self.stream)
+
+    def set(self, threshold, min_sep, max_jump):
+        self.ctx.shoreline_set(threshold, min_sep, max_jump, self.stream)
+
+
 def kinematics_taps(radius, sigma):
     """rcflow_kinematics_taps: the smoothing taps g_0..g_radius as float32, without a context or a GPU."""
     taps = np.zeros(max(0, min(int(radius), RC_KINEMATICS_MAX_RADIUS)) + 1, np.float32)
@@ -2129,6 +2244,18 @@ def transects_plan(w, h, lines, metres_per_pixel=1.0, fps=1.0):
     check(lib.rcflow_transects_plan(int(w), int(h), arr, len(arr), float(metres_per_pixel), float(fps), None, None, C.byref(total)))
     table, geom = np.zeros(total.value, TRANSECT_SAMPLE_DTYPE), np.zeros(len(arr), TRANSECT_GEOM_DTYPE)
     check(lib.rcflow_transects_plan(int(w), int(h), arr, len(arr), float(metres_per_pixel), float(fps), table.ctypes.data, geom.ctypes.data, None))
+    return table, geom
+
+
+def shoreline_plan(w, h, lines, metres_per_pixel=1.0):
+    """rcflow_shoreline_plan: the sample table and the per-line constants of `lines` (land to sea) on a w x h picture, without a
+    context or a GPU -> (SAMPLES TRANSECT_SAMPLE_DTYPE, LINES TRANSECT_GEOM_DTYPE)."""
+    lib = _lib.load()
+    arr = _transect_lines(lines)
+    total = C.c_int(0)
+    check(lib.rcflow_shoreline_plan(int(w), int(h), arr, len(arr), float(metres_per_pixel), None, None, C.byref(total)))
+    table, geom = np.zeros(total.value, TRANSECT_SAMPLE_DTYPE), np.zeros(len(arr), TRANSECT_GEOM_DTYPE)
+    check(lib.rcflow_shoreline_plan(int(w), int(h), arr, len(arr), float(metres_per_pixel), table.ctypes.data, geom.ctypes.data, None))
     return table, geom
 
 

@@ -305,6 +305,23 @@ struct RcKinematics {
     RcZeroFence zf;
 };
 
+// Shoreline of one stream slot (shoreline_kernels.hip).  Everything is allocated by rcflow_shoreline_open and released by
+// rcflow_shoreline_close / rcflow_destroy.
+struct RcShoreline {
+    bool open = false;
+    int w = 0, h = 0;
+    rc_shoreline_params prm{};      // threshold, min_sep and max_jump: as rcflow_shoreline_set left them
+    int L = 0, S = 0;               // lines, samples in all
+    long long pushes = 0;           // since open / reset; the next position goes to ring slot pushes mod window
+    RcBuf table;                    // [S] rc_transect_sample | [L] rc_transect_geom, written once by open
+    RcBuf plane;                    // [h][w] uint16: J, written by every push before it is read
+    RcBuf ring;                     // [L][window] int32: a line's positions, -1 for none
+    RcBuf lin;                      // [L] ShLine: what shoreline@1 hands to shoreline@2
+    RcBuf out;                      // the last push: records [L] | summary 8 int64 | histogram RC_SHORE_HIST uint32
+    RcBuf ctl;                      // ShCtl: the tickets, the counters and the live histogram (zero between launches), thr, N and eta
+    RcZeroFence zf;
+};
+
 // warp_kernels.hip: one launch of the affine / perspective warp
 struct RcWarpArgs {
     const uint8_t* src; size_t step;
@@ -387,6 +404,7 @@ struct RcSlot {
     RcPiv piv;
     RcTransects ts;
     RcKinematics kn;
+    RcShoreline sh;
     RcPhaseCorr pc;
 };
 
@@ -447,7 +465,8 @@ struct rc_ctx {
 // sample the frame and the field along lines and keep what they find from push to push, as the tracer lines do with their
 // vertices, and are booked with them, under "stream".  The flow kinematics differentiate one flow field, pixel for pixel, with
 // no state from push to push: an operation on the field as the shear-rate colouring among the post-ops (flow_postop) is, so they
-// are booked with those, under "farneback".
+// are booked with those, under "farneback".  The shoreline works on pictures, not on flow: the time-exposure MEAN, the plan view's
+// picture or a frame, as the time-exposure images and the wave spectra do, and is booked with them, under "overlay".
 #define RC_BUCKET_TABLE(X) \
     X(RC_B_FARNEBACK, "farneback") X(RC_B_POLAR, "polar") X(RC_B_THRESHOLD, "threshold") X(RC_B_OVERLAY, "overlay") \
     X(RC_B_EROSION, "erosion") X(RC_B_CODEC, "codec") X(RC_B_STREAM, "stream")
@@ -488,7 +507,8 @@ struct rc_ctx {
     X(RC_K_WAVES, "waves", RC_B_OVERLAY) /* @0 spectrum, @1 cell sums and closing, @2 bin map and picture */ \
     X(RC_K_PIV, "piv", RC_B_FARNEBACK) /* @0 the pair's sums, ring and accumulators, @1 score, peak and records, @2 validation, field, picture, summary */ \
     X(RC_K_TRANSECTS, "transects", RC_B_STREAM) /* @0 sampling, rings and accumulators, @1 velocity, transport, jets, records and summary, @2 time stack and Hovmoeller picture */ \
-    X(RC_K_KINEMATICS, "kinematics", RC_B_FARNEBACK) /* @0 smoothing, derivatives, invariants, first sums and the threshold, @1 cores, mask, picture, records and summary */
+    X(RC_K_KINEMATICS, "kinematics", RC_B_FARNEBACK) /* @0 smoothing, derivatives, invariants, first sums and the threshold, @1 cores, mask, picture, records and summary */ \
+    X(RC_K_SHORELINE, "shoreline", RC_B_OVERLAY) /* @0 indicator, box, plane, histogram and Otsu, @1 lines, @2 outliers, ring, window and records, @3 mask, plane and histogram out, @4 primitives */
 #define RC_ROW_ID(id, ...) id,
 enum { RC_BUCKET_TABLE(RC_ROW_ID) RC_B_BUCKETS };
 enum { RC_KIND_TABLE(RC_ROW_ID) RC_K_KINDS };
@@ -546,6 +566,11 @@ void rc_draw_launch(rc_ctx* ctx, hipStream_t cur, uint8_t* d_img, size_t step, i
                     int n, unsigned long long* d_skipped);
 // warp_kernels.hip
 void rc_warp_launch(rc_ctx* ctx, hipStream_t cur, RcWarpArgs& a, bool perspective);
+// transects_kernels.hip: the per-line part of rcflow_transects_plan, shared with rcflow_shoreline_plan.  Line i's samples from
+// table[first] on and its constants into geom[i] (each may be null); RC_EINVAL with the text set for an endpoint that is not
+// finite, a line of no length or a sample outside the picture.  The bounds on n stay with each caller
+int rc_line_plan(const char* who, int w, int h, const rc_transect_line& l, int i, int first, double metres_per_pixel, double fps,
+                 rc_transect_sample* table, rc_transect_geom* geom);
 // initial_flow_kernels.hip
 int rc_flow_area_prepare(RcBuf& tab, int W, int H, int w, int h, RcFlowAreaArgs& a);
 
@@ -569,7 +594,7 @@ struct RcProfScope {
     } while (0)
 
 // ---------------------------------------------------------------------------- per-slot products
-// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView, RcWaves, RcPiv, RcTransects and RcKinematics share one lifecycle.  A product supplies
+// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView, RcWaves, RcPiv, RcTransects, RcKinematics and RcShoreline share one lifecycle.  A product supplies
 //   void rc_state_free(T&)             frees every buffer and the fence; the state is T() again
 //   int rc_state_zero(RcSlot&, T&)     rc_fence_zero of what open / reset clear, and the counters
 // and open / reset / close are written once, here.
@@ -586,6 +611,7 @@ void rc_state_free(RcWaves& v);
 void rc_state_free(RcPiv& v);
 void rc_state_free(RcTransects& v);
 void rc_state_free(RcKinematics& k);
+void rc_state_free(RcShoreline& v);
 int rc_state_zero(RcSlot& s, RcTimex& t);
 int rc_state_zero(RcSlot& s, RcFrameStab& f);
 int rc_state_zero(RcSlot& s, RcRipMap& m);
@@ -599,6 +625,7 @@ int rc_state_zero(RcSlot& s, RcWaves& v);
 int rc_state_zero(RcSlot& s, RcPiv& v);
 int rc_state_zero(RcSlot& s, RcTransects& v);
 int rc_state_zero(RcSlot& s, RcKinematics& k);
+int rc_state_zero(RcSlot& s, RcShoreline& v);
 
 // The tail of every open.  The caller has validated, selected the device and built `fresh` (rc: what its allocations
 // returned).  The state that is open is touched only once nothing can be refused any more: a refused open leaves it as it

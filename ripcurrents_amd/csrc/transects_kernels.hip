@@ -370,6 +370,37 @@ static bool ts_pos(double v) { return v > 0. && v <= 1.7976931348623157e308; }  
 static bool ts_jet(double v) { return v > 0. && v < 1048576.; }                      // a mean of 2^20 or more is bad and in no jet: such a threshold says nothing
 static bool ts_fin(double v) { return v >= -1.7976931348623157e308 && v <= 1.7976931348623157e308; }
 
+int rc_line_plan(const char* who, int w, int h, const rc_transect_line& l, int i, int first, double metres_per_pixel, double fps,
+                 rc_transect_sample* table, rc_transect_geom* geom) {
+    const double x0 = l.x0, y0 = l.y0, x1 = l.x1, y1 = l.y1;
+    if (!ts_fin(x0) || !ts_fin(y0) || !ts_fin(x1) || !ts_fin(y1)) { rc_set_error("%s: line %d has an endpoint that is not finite", who, i); return RC_EINVAL; }
+    const double dx = x1 - x0, dy = y1 - y0, len = hypot(dx, dy);
+    if (!(len > 0.) || !ts_fin(len)) { rc_set_error("%s: line %d has no length", who, i); return RC_EINVAL; }
+    for (int j = 0; j < l.n; j++) {
+        const double t = (double)j / (double)(l.n - 1), x = x0 + dx * t, y = y0 + dy * t;
+        const double X = rint(16. * x), Y = rint(16. * y);
+        if (!(X >= 0. && X <= 16. * (w - 1) && Y >= 0. && Y <= 16. * (h - 1))) {
+            rc_set_error("%s: sample %d of line %d lies at (%g, %g), outside the %d x %d picture", who, j, i, x, y, w, h);
+            return RC_EINVAL;
+        }
+        if (table) {
+            rc_transect_sample& s = table[first + j];
+            s.X = (int)X; s.Y = (int)Y; s.line = i; s.offset = j;
+        }
+    }
+    if (geom) {
+        rc_transect_geom& g = geom[i];
+        g.first = first; g.n = l.n;
+        g.ex = (float)(dx / len); g.ey = (float)(dy / len);
+        g.nx = (float)(dy / len); g.ny = (float)(-dx / len);
+        g.scale = (float)(metres_per_pixel * fps);
+        g.pad = 0;
+        g.len = len;
+        g.ds = (len * metres_per_pixel) / (double)(l.n - 1);
+    }
+    return RC_OK;
+}
+
 extern "C" int rcflow_transects_plan(int w, int h, const rc_transect_line* lines, int n_lines, double metres_per_pixel, double fps,
                                      rc_transect_sample* table, rc_transect_geom* geom, int* total) {
     static const char* who = "rcflow_transects_plan";
@@ -392,34 +423,8 @@ extern "C" int rcflow_transects_plan(int w, int h, const rc_transect_line* lines
     }
     int first = 0;
     for (int i = 0; i < n_lines; i++) {
-        const rc_transect_line& l = lines[i];
-        const double x0 = l.x0, y0 = l.y0, x1 = l.x1, y1 = l.y1;
-        if (!ts_fin(x0) || !ts_fin(y0) || !ts_fin(x1) || !ts_fin(y1)) { rc_set_error("%s: line %d has an endpoint that is not finite", who, i); return RC_EINVAL; }
-        const double dx = x1 - x0, dy = y1 - y0, len = hypot(dx, dy);
-        if (!(len > 0.) || !ts_fin(len)) { rc_set_error("%s: line %d has no length", who, i); return RC_EINVAL; }
-        for (int j = 0; j < l.n; j++) {
-            const double t = (double)j / (double)(l.n - 1), x = x0 + dx * t, y = y0 + dy * t;
-            const double X = rint(16. * x), Y = rint(16. * y);
-            if (!(X >= 0. && X <= 16. * (w - 1) && Y >= 0. && Y <= 16. * (h - 1))) {
-                rc_set_error("%s: sample %d of line %d lies at (%g, %g), outside the %d x %d picture", who, j, i, x, y, w, h);
-                return RC_EINVAL;
-            }
-            if (table) {
-                rc_transect_sample& s = table[first + j];
-                s.X = (int)X; s.Y = (int)Y; s.line = i; s.offset = j;
-            }
-        }
-        if (geom) {
-            rc_transect_geom& g = geom[i];
-            g.first = first; g.n = l.n;
-            g.ex = (float)(dx / len); g.ey = (float)(dy / len);
-            g.nx = (float)(dy / len); g.ny = (float)(-dx / len);
-            g.scale = (float)(metres_per_pixel * fps);
-            g.pad = 0;
-            g.len = len;
-            g.ds = (len * metres_per_pixel) / (double)(l.n - 1);
-        }
-        first += l.n;
+        if (int rc = rc_line_plan(who, w, h, lines[i], i, first, metres_per_pixel, fps, table, geom)) return rc;
+        first += lines[i].n;
     }
     if (total) *total = first;
     return RC_OK;
