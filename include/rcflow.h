@@ -1970,6 +1970,154 @@ int rcflow_shoreline_close(rc_ctx* ctx, int stream);
 /* never blocks; RC_ESTATE when nothing is open, RC_EINVAL without a buffer */
 int rcflow_shoreline_info(rc_ctx* ctx, int stream, rc_shoreline_info* info);
 
+/* ------------------------------------------------------------------ surf: breaking fraction, variance image, rip channels
+ * The shoreline bounds the surf zone on the land side; this product says where the waves break, how often, and where the band of
+ * breaking has a hole.  A rip channel shows as a gap in that band: dark in a time exposure, quiet in the variance image, with a
+ * low fraction of time breaking.  It uses no flow at all, so it cross-checks the flow-side detectors where Farneback is least to
+ * be trusted: inside the foam.  It takes grey frames (8UC1: rcflow_resize_bgr_to_gray_dev, the plan view's picture).  The
+ * reference has no such product.  tests/_surf_ref.py states the following in numpy and the kernels equal it bit for bit on every
+ * output of every push.  Everything is exact integer arithmetic except the float conversions named under the records; those are
+ * computed in double, each operation rounded on its own.
+ *
+ *  Geometry (host, once; rcflow_surf_plan gives it without a context).  Lines are rc_transect_line records FROM LAND TO SEA in
+ *  alongshore order; the table and the per-line constants are the shoreline's (positions in 1/16 pixel, fps = 1), the limits its
+ *  own: 0..RC_SURF_MAX_LINES lines, n in RC_SURF_MIN_SAMPLES..RC_SURF_MAX_SAMPLES, S = sum of n at most RC_SURF_MAX_TOTAL.  With
+ *  ZERO lines the session is pixels only: "surf@1" and "surf@2" do not run and the line outputs must be NULL.
+ *  State.  A ring of W = window grey frames, zero at open and reset.  Per pixel S1 = sum of the ring (uint32), S2 = sum of its
+ *  squares (uint32: 4096 * 255^2 < 2^32), Q (uint16) = flags set among the held frames; a flag ring of one bit per pixel and held
+ *  frame.  The planes have a row pitch P = w rounded up to 4 and the flags are kept per run of 256 pixels of P h, so the state is
+ *  P h (W + 10) + 32 W ceil(P h / 256) bytes; beyond RC_SURF_MAX_STATE_BYTES rcflow_surf_open answers RC_ESIZE with the count.
+ *  1. "surf@0", pixels, every push.  g: the frame.  c = pushes mod W; old = ring[c]; S1 += g - old; S2 += g^2 - old^2; ring[c] = g.
+ *     n = min(pushes + 1, W).  b = (g >= bright) and (g n >= S1 + delta n), S1 after the update: bright now AND at least delta above
+ *     the pixel's own window mean; persistent foam, white sand and a saturated sky are bright but not above their mean; on the
+ *     very first push nothing breaks when delta > 0.  Q += b - bit[c]; bit[c] = b.  Outputs of the same launch, each optional:
+ *     d_now 8UC1 255 where b; d_surf 8UC1 255 where Q 1000 >= q_min n (what rcflow_regions_push_dev takes); d_q 16UC1 Q;
+ *     d_mean 8UC1 (2 S1 + n) / (2 n); d_sd 8UC1 min(255, isqrt(4 (n S2 - S1^2) / n^2)), twice the standard deviation, the
+ *     variance image: int64, the inner division floors, isqrt the exact floor square root; d_picture 8UC3 entry i of
+ *     rcflow_jet_lut, i = min(255, Q 255000 / (vis_permille n)).  Counts for the summary, by the launch's last-arriving
+ *     workgroup: pixels with b, pixels in surf, sum of Q.
+ *  2. "surf@1", lines, a wave a line.  V[j]: the integer bilinear sample of the Q plane at the table position (the shoreline's
+ *     formula: weights in 16ths, + 128 >> 8, ix1 = min(ix + 1, w - 1), iy1 likewise).  in[j] = V[j] 1000 >= q_min n.  Runs are the
+ *     maximal runs of consecutive in-samples at least min_run long; k0 the first sample of the first run, k1 the last sample of
+ *     the last run; RC_SURF_NOBAND with k0 = k1 = -1, the edge points and width_m 0 when there is none.  load B = sum of V over
+ *     all samples; peak = max V, kpeak its first index.  The inner (ix, iy) and outer (ox, oy) edge points in 1/256 pixel by the
+ *     shoreline's formula, X = 16 Xa + floor((16 (Xb - Xa) pos + 128 (n - 1)) / (256 (n - 1))) with pos = 256 k0 and 256 k1.
+ *     width_m = (float)((double)(k1 - k0 + 1) * ds).
+ *  3. "surf@2", along the shore, one workgroup.  For line i of L: lo = max(0, i - span), hi = min(L - 1, i + span), m = hi - lo + 1;
+ *     ref = the value of ascending rank (m - 1) / 2 among B[lo..hi], the lower median with the line itself included.
+ *     RC_SURF_NOREF when ref < max(min_load, 1); otherwise RC_SURF_CHANNEL when B 1000 < ratio ref (int64).  share = ref > 0 ?
+ *     min(B 1000 / ref, RC_SURF_MAX_SHARE) : 1000.  Channels are the maximal runs of consecutive CHANNEL lines at least min_lines
+ *     long, in line order; their lines also carry RC_SURF_IN_CHANNEL.  The first RC_SURF_MAX_CHANNELS are recorded (the records
+ *     past them are zero), the summary counts them all.  rc_surf_channel: first, count, centre = the line of least share (lowest
+ *     index on ties), its share; the centre point (cx, cy) in 1/256 pixel on the centre line (n_c samples) at pos: the flanking
+ *     lines are first - 1 and first + count, E those that exist and have a band; pos = (sum over E of 128 (k0 + k1)) / |E|
+ *     (integer division) clamped to 256 (n_c - 1), and 128 (n_c - 1) with E empty.  width_m: with (dx, dy) in 1/16 pixel between
+ *     the land ends (the table's first samples) of lines max(first - 1, 0) and min(first + count, L - 1),
+ *     (float)((sqrt((double)(dx^2 + dy^2)) / 16) * metres_per_pixel).
+ *     Summary, 8 int64: n | pixels breaking now | surf pixels | sum of Q | lines with a band | CHANNEL lines | channels (all) |
+ *     pushes since open / reset.
+ *  4. "surf@3": rcflow_surf_prims_dev gives L - 1 + RC_SURF_MAX_CHANNELS primitives of the last push for rcflow_draw_dev: record
+ *     i < L - 1 the segment from line i's outer edge point ((ox + 128) >> 8, (oy + 128) >> 8) to that of the next line that has a
+ *     band, when line i has one (the breaker line, bridged over channel lines as the shoreline bridges); record L - 1 + k a disc
+ *     at channel k's centre; all-zero records elsewhere and before the first push. */
+#define RC_SURF_NOBAND 1                 /* rc_surf_line::flags */
+#define RC_SURF_NOREF 2
+#define RC_SURF_CHANNEL 4
+#define RC_SURF_IN_CHANNEL 8
+#define RC_SURF_MAX_LINES 1024
+#define RC_SURF_MIN_SAMPLES 8
+#define RC_SURF_MAX_SAMPLES 1024
+#define RC_SURF_MAX_TOTAL 262144
+#define RC_SURF_MAX_WINDOW 4096
+#define RC_SURF_MAX_SPAN 32
+#define RC_SURF_MAX_CHANNELS 32
+#define RC_SURF_MAX_SHARE 1000000
+#define RC_SURF_MAX_PIXELS (1 << 25)
+#define RC_SURF_MAX_STATE_BYTES (4ull << 30)     /* ring, flag ring, S1, S2 and Q */
+#define RC_SURF_LAUNCHES 3               /* of a push of a session with lines; 1 without */
+typedef struct rc_surf_params {
+    int window;             /* W: 2..RC_SURF_MAX_WINDOW frames held per pixel */
+    int bright;             /* 0..255: a breaking pixel is at least this bright */
+    int delta;              /* 0..255: and at least this far above its window mean */
+    int q_min;              /* per mille, 1..1000: fraction of time breaking that puts a pixel in the surf zone */
+    int min_run;            /* 1..64 samples in a surf run */
+    int span;               /* a: 0..RC_SURF_MAX_SPAN lines on either side for the alongshore reference */
+    int ratio;              /* per mille, 1..999: a line below this share of the reference is a channel line */
+    int min_load;           /* >= 0: the smallest reference that counts */
+    int min_lines;          /* 1..64 lines in a channel */
+    int vis_permille;       /* 1..1000: the fraction the picture's last colour stands for */
+    int flags;              /* 0 */
+    int pad;
+    double metres_per_pixel; /* finite, > 0 */
+} rc_surf_params;
+typedef struct rc_surf_line {
+    int flags;              /* RC_SURF_NOBAND, NOREF, CHANNEL, IN_CHANNEL */
+    int k0, k1;             /* the band's first and last sample, or -1 */
+    int load;               /* B */
+    int peak, kpeak;        /* the largest V and its first sample */
+    int ix, iy;             /* the inner edge point in 1/256 pixel */
+    int ox, oy;             /* the outer edge point */
+    int ref;                /* the alongshore reference */
+    int share;              /* per mille of it */
+    float width_m;          /* the band's width in metres */
+    int pad[3];
+} rc_surf_line;             /* 64 bytes */
+typedef struct rc_surf_channel {
+    int first, count;       /* its lines */
+    int centre;             /* the line of least share */
+    int share;              /* there */
+    int cx, cy;             /* the centre point in 1/256 pixel */
+    float width_m;          /* alongshore, in metres */
+    int pad;
+} rc_surf_channel;          /* 32 bytes */
+typedef struct rc_surf_info {
+    int w, h;
+    rc_surf_params prm;                /* as rcflow_surf_set left them */
+    int lines, samples;                /* S */
+    int launches_per_push;             /* RC_SURF_LAUNCHES, or 1 without lines */
+    int held;                          /* min(pushes, W) */
+    long long pushes;                  /* since open / reset */
+    size_t device_bytes;
+} rc_surf_info;
+/* The geometry alone: no context, no GPU.  table: S records in line order, geom: n_lines records, total: S; each may be NULL.
+ * RC_EINVAL as rcflow_shoreline_plan, except that no lines at all are allowed (lines may then be NULL). */
+int rcflow_surf_plan(int w, int h, const rc_transect_line* lines, int n_lines, double metres_per_pixel, rc_transect_sample* table,
+                     rc_transect_geom* geom, int* total);
+/* Allocates everything the slot will ever need (the state above, the table, the records).  Re-opening replaces the state; a
+ * refused open leaves the open state as it was.  RC_EINVAL as rcflow_surf_plan, no parameters, a value outside the ranges above,
+ * unknown flag bits; RC_ESIZE beyond the context's max_w x max_h, w * h above RC_SURF_MAX_PIXELS, or a state above
+ * RC_SURF_MAX_STATE_BYTES. */
+int rcflow_surf_open(rc_ctx* ctx, int stream, int w, int h, const rc_transect_line* lines, int n_lines, const rc_surf_params* prm);
+/* One grey frame: d_gray w x h, channels = 1 (anything else is RC_EINVAL).  Outputs (device memory, each may be NULL): d_now,
+ * d_surf, d_mean, d_sd 8UC1; d_q 16UC1 (pointer and step multiples of 2); d_picture 8UC3; d_lines lines x rc_surf_line and
+ * d_channels RC_SURF_MAX_CHANNELS x rc_surf_channel (4-byte aligned; RC_EINVAL on a session without lines); d_summary 8 int64
+ * (8-byte aligned).  Every launch runs on every push, because the state must be fed; what a push gives does not depend on which
+ * outputs it or earlier pushes asked for.  No host synchronisation, no device-to-host copy.  An output whose byte range overlaps
+ * the frame's or another output's is RC_EINVAL.  Row padding is never written.  Every refusal is decided before anything is
+ * queued and leaves the state as it was; RC_ESTATE before rcflow_surf_open.  RC_EHIP (the runtime refused a launch) is no
+ * refusal: the state is undefined until rcflow_surf_reset. */
+int rcflow_surf_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_gray, size_t step, int channels, uint8_t* d_now, size_t now_step,
+                         uint8_t* d_surf, size_t surf_step, uint16_t* d_q, size_t q_step, uint8_t* d_mean, size_t mean_step, uint8_t* d_sd,
+                         size_t sd_step, uint8_t* d_picture, size_t picture_step, rc_surf_line* d_lines, rc_surf_channel* d_channels,
+                         long long* d_summary);
+/* lines - 1 + RC_SURF_MAX_CHANNELS primitives of the last push into d_prims ("surf@3"); thickness and disc_radius as
+ * rcflow_regions_prims_dev; RC_EINVAL on a session without lines */
+int rcflow_surf_prims_dev(rc_ctx* ctx, int stream, uint32_t color, int thickness, int disc_radius, rc_draw_prim* d_prims);
+/* Blocks until the slot's stream has finished; for hosts and tests.  Each may be NULL: the line records, the
+ * RC_SURF_MAX_CHANNELS channel records and the summary of the last push (host memory); zeros before the first. */
+int rcflow_surf_read(rc_ctx* ctx, int stream, rc_surf_line* lines, rc_surf_channel* channels, long long summary[8]);
+/* Blocks.  Each may be NULL: the open session's table (S records) and per-line constants (lines records), from the device */
+int rcflow_surf_table_read(rc_ctx* ctx, int stream, rc_transect_sample* table, rc_transect_geom* geom);
+/* bright, delta, q_min, ratio, min_load and vis_permille from the next push on; RC_EINVAL as rcflow_surf_open */
+int rcflow_surf_set(rc_ctx* ctx, int stream, int bright, int delta, int q_min, int ratio, int min_load, int vis_permille);
+/* zeroes the ring, the flags, the sums, the records, the summary and the push count; keeps the table, the allocation and the
+ * parameters as rcflow_surf_set left them; asynchronous, on the slot's stream */
+int rcflow_surf_reset(rc_ctx* ctx, int stream);
+/* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
+int rcflow_surf_close(rc_ctx* ctx, int stream);
+/* never blocks; RC_ESTATE when nothing is open, RC_EINVAL without a buffer */
+int rcflow_surf_info(rc_ctx* ctx, int stream, rc_surf_info* info);
+
 /* Display path, ripcurrents.cpp:233-273 (= streamline_displacement / _total_motion / _ratio /
  * _positions, ripcurrents_module.cpp:13-60) on the slot's streamline field (rcflow_advect_field_dev):
  * which 0 = |pt|, 1 = dist, 2 = |pt| / dist; minMaxLoc + convertTo(CV_8UC1, 255/max) +
@@ -2050,7 +2198,7 @@ int rcflow_profile_read(rc_ctx* ctx, int cap, const char** names, int* launches,
 
 /* The same totals under the reference's own bucket names, in the order it prints them (ripcurrents.cpp:103-109,
  * :518-524): farneback, polar, threshold, overlay, erosion, codec, stream ("pathlines").  GPU time of the kernels
- * that do each bucket's work ("overlay" includes the time-exposure images, the 8-bit colour stages, the wave spectra and the shoreline, "farneback" the frame stabilisation, the opposing-flow map, the motion templates, the plan view, the ensemble PIV and the flow kinematics, "stream" the flow map and FTLE and the transects); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
+ * that do each bucket's work ("overlay" includes the time-exposure images, the 8-bit colour stages, the wave spectra, the shoreline and the surf zone, "farneback" the frame stabilisation, the opposing-flow map, the motion templates, the plan view, the ensemble PIV and the flow kinematics, "stream" the flow map and FTLE and the transects); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
  * classification kernels, booked under "threshold"), "codec" is 0 (video decode is host I/O outside the library).
  * names / ms: RC_PROFILE_BUCKETS entries each (either may be NULL).  Returns RC_PROFILE_BUCKETS. */
 #define RC_PROFILE_BUCKETS 7

@@ -1321,4 +1321,72 @@ class Shoreline {
     DeviceImage d_image_, d_roi_, d_mask_, d_plane_;
 };
 
+// the pictures of a Surf::push, each optional: now, surf, mean and sd 8UC1, q 16UC1, picture 8UC3
+struct SurfPictures { Mat* now = nullptr; Mat* surf = nullptr; Mat* q = nullptr; Mat* mean = nullptr; Mat* sd = nullptr; Mat* picture = nullptr; };
+
+// Surf zone on the device (rcflow_surf_*): per pixel the fraction of the last `window` frames in which it broke, the window mean
+// and the variance image; along lines laid from land to sea the band of breaking, and along the shore the rip channels: the
+// holes in that band.  Host grey frames (8UC1) of the pipeline's size in; the pictures, the line and the channel records out.
+// Without lines the session is pixels only.
+class Surf {
+  public:
+    using Pictures = SurfPictures;
+
+    Surf(Pipeline& pipe, const std::vector<rc_transect_line>& lines, const rc_surf_params& prm) : pipe_(pipe), lines_((int)lines.size()) {
+        check(rcflow_surf_open(pipe.context(), 0, pipe.width(), pipe.height(), lines.empty() ? nullptr : lines.data(), (int)lines.size(), &prm));
+    }
+    ~Surf() { (void)rcflow_surf_close(pipe_.context(), 0); }
+    Surf(const Surf&) = delete;
+    Surf& operator=(const Surf&) = delete;
+
+    int lines() const { return lines_; }
+
+    // gray: 8UC1 of the pipeline's size.  The records and the summary stay on the session after every push, for read(), records()
+    // and channels().
+    void push(const Mat& gray, const Pictures& out = Pictures()) {
+        const int w = pipe_.width(), h = pipe_.height();
+        if (!is_image(gray, w, h, 1, 1)) throw Error(RC_EINVAL, "Surf::push: the frame must be 8UC1 of the pipeline's size");
+        for (const Mat* m : {out.now, out.surf, out.mean, out.sd})
+            if (m && !is_image(*m, w, h, 1, 1)) throw Error(RC_EINVAL, "Surf::push: now, surf, mean and sd 8UC1, each of the pipeline's size");
+        if ((out.q && !is_image(*out.q, w, h, 1, 2)) || (out.picture && !is_image(*out.picture, w, h, 3, 1)))
+            throw Error(RC_EINVAL, "Surf::push: q 16UC1, picture 8UC3, each of the pipeline's size");
+        staged(pipe_.context(), {{d_gray_, &gray}}, [&] {
+            return rcflow_surf_push_dev(pipe_.context(), 0, d_gray_.ptr<const uint8_t>(), d_gray_.pitch(), 1, d_now_.ptr<uint8_t>(out.now), d_now_.pitch(),
+                                        d_surf_.ptr<uint8_t>(out.surf), d_surf_.pitch(), d_q_.ptr<uint16_t>(out.q), d_q_.pitch(),
+                                        d_mean_.ptr<uint8_t>(out.mean), d_mean_.pitch(), d_sd_.ptr<uint8_t>(out.sd), d_sd_.pitch(),
+                                        d_picture_.ptr<uint8_t>(out.picture), d_picture_.pitch(), nullptr, nullptr, nullptr);
+        }, {{d_now_, out.now}, {d_surf_, out.surf}, {d_q_, out.q}, {d_mean_, out.mean}, {d_sd_, out.sd}, {d_picture_, out.picture}});
+    }
+    // each waits for the pipeline's stream: of the last push (include/rcflow.h).  The summary: frames held, pixels breaking now,
+    // surf pixels, the sum of Q, lines with a band, channel lines, channels, pushes; the line records, one per line; the
+    // recorded channels
+    std::vector<long long> read() {
+        std::vector<long long> s(8);
+        check(rcflow_surf_read(pipe_.context(), 0, nullptr, nullptr, s.data()));
+        return s;
+    }
+    std::vector<rc_surf_line> records() {
+        std::vector<rc_surf_line> r((size_t)lines_);
+        check(rcflow_surf_read(pipe_.context(), 0, r.empty() ? nullptr : r.data(), nullptr, nullptr));
+        return r;
+    }
+    std::vector<rc_surf_channel> channels() {
+        std::vector<rc_surf_channel> c(RC_SURF_MAX_CHANNELS);
+        long long s[8];
+        check(rcflow_surf_read(pipe_.context(), 0, nullptr, c.data(), s));
+        c.resize((size_t)std::min<long long>(s[6], RC_SURF_MAX_CHANNELS));
+        return c;
+    }
+    void set(int bright, int delta, int q_min, int ratio, int min_load, int vis_permille) {
+        check(rcflow_surf_set(pipe_.context(), 0, bright, delta, q_min, ratio, min_load, vis_permille));
+    }
+    rc_surf_info info() { rc_surf_info i; check(rcflow_surf_info(pipe_.context(), 0, &i)); return i; }
+    void reset() { check(rcflow_surf_reset(pipe_.context(), 0)); }
+
+  private:
+    Pipeline& pipe_;
+    int lines_ = 0;
+    DeviceImage d_gray_, d_now_, d_surf_, d_q_, d_mean_, d_sd_, d_picture_;
+};
+
 }  // namespace rc

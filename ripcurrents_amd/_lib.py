@@ -70,6 +70,10 @@ SHORE_SOURCES = {"rmb": 0, "gray": 1, "plane": 2}
 RC_SHORE_EMPTY, RC_SHORE_DRY, RC_SHORE_WET, RC_SHORE_UNSURE, RC_SHORE_OUTLIER, RC_SHORE_NO_WINDOW = 1, 2, 4, 8, 16, 32
 RC_SHORE_MAX_LINES, RC_SHORE_MIN_SAMPLES, RC_SHORE_MAX_SAMPLES, RC_SHORE_MAX_TOTAL, RC_SHORE_MAX_RADIUS, RC_SHORE_MAX_WINDOW = 1024, 8, 1024, 262144, 7, 4096
 RC_SHORE_MAX_PIXELS, RC_SHORE_MAX_STATE_BYTES, RC_SHORE_HIST, RC_SHORE_LAUNCHES = 1 << 25, 64 << 20, 512, 4
+# rcflow_surf_*: the line record's flags, the bounds, the channel records of a push, the launches of a push with lines
+RC_SURF_NOBAND, RC_SURF_NOREF, RC_SURF_CHANNEL, RC_SURF_IN_CHANNEL = 1, 2, 4, 8
+RC_SURF_MAX_LINES, RC_SURF_MIN_SAMPLES, RC_SURF_MAX_SAMPLES, RC_SURF_MAX_TOTAL, RC_SURF_MAX_WINDOW, RC_SURF_MAX_SPAN = 1024, 8, 1024, 262144, 4096, 32
+RC_SURF_MAX_CHANNELS, RC_SURF_MAX_SHARE, RC_SURF_MAX_PIXELS, RC_SURF_MAX_STATE_BYTES, RC_SURF_LAUNCHES = 32, 1000000, 1 << 25, 4 << 30, 3
 
 ERRORS = {-1: "RC_EINVAL", -2: "RC_ENOMEM", -3: "RC_EHIP", -4: "RC_ENODEV", -5: "RC_ESIZE",
           -6: "RC_ESTATE", -7: "RC_ECOMM"}
@@ -280,6 +284,31 @@ class ShorelineRecord(C.Structure):
 class ShorelineInfo(C.Structure):
     """rc_shoreline_info (include/rcflow.h)."""
     _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", ShorelineParams), ("lines", C.c_int), ("samples", C.c_int),
+                ("launches_per_push", C.c_int), ("held", C.c_int), ("pushes", C.c_longlong), ("device_bytes", C.c_size_t)]
+
+
+class SurfParams(C.Structure):
+    """rc_surf_params (include/rcflow.h), 56 bytes."""
+    _fields_ = [("window", C.c_int), ("bright", C.c_int), ("delta", C.c_int), ("q_min", C.c_int), ("min_run", C.c_int), ("span", C.c_int),
+                ("ratio", C.c_int), ("min_load", C.c_int), ("min_lines", C.c_int), ("vis_permille", C.c_int), ("flags", C.c_int), ("pad", C.c_int),
+                ("metres_per_pixel", C.c_double)]
+
+
+class SurfLine(C.Structure):
+    """rc_surf_line (include/rcflow.h), 64 bytes; numpy: api.SURF_LINE_DTYPE."""
+    _fields_ = [("flags", C.c_int), ("k0", C.c_int), ("k1", C.c_int), ("load", C.c_int), ("peak", C.c_int), ("kpeak", C.c_int), ("ix", C.c_int),
+                ("iy", C.c_int), ("ox", C.c_int), ("oy", C.c_int), ("ref", C.c_int), ("share", C.c_int), ("width_m", C.c_float), ("pad", C.c_int * 3)]
+
+
+class SurfChannel(C.Structure):
+    """rc_surf_channel (include/rcflow.h), 32 bytes; numpy: api.SURF_CHANNEL_DTYPE."""
+    _fields_ = [("first", C.c_int), ("count", C.c_int), ("centre", C.c_int), ("share", C.c_int), ("cx", C.c_int), ("cy", C.c_int),
+                ("width_m", C.c_float), ("pad", C.c_int)]
+
+
+class SurfInfo(C.Structure):
+    """rc_surf_info (include/rcflow.h)."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", SurfParams), ("lines", C.c_int), ("samples", C.c_int),
                 ("launches_per_push", C.c_int), ("held", C.c_int), ("pushes", C.c_longlong), ("device_bytes", C.c_size_t)]
 
 
@@ -499,6 +528,16 @@ SIGNATURES = {
     "rcflow_shoreline_reset": [_vp, _i],
     "rcflow_shoreline_close": [_vp, _i],
     "rcflow_shoreline_info": [_vp, _i, C.POINTER(ShorelineInfo)],
+    "rcflow_surf_plan": [_i, _i, C.POINTER(TransectLine), _i, C.c_double, _vp, _vp, C.POINTER(C.c_int)],
+    "rcflow_surf_open": [_vp, _i, _i, _i, C.POINTER(TransectLine), _i, C.POINTER(SurfParams)],
+    "rcflow_surf_push_dev": [_vp, _i, _vp, _sz, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp],
+    "rcflow_surf_prims_dev": [_vp, _i, C.c_uint32, _i, _i, _vp],
+    "rcflow_surf_read": [_vp, _i, _vp, _vp, C.POINTER(C.c_longlong)],
+    "rcflow_surf_table_read": [_vp, _i, _vp, _vp],
+    "rcflow_surf_set": [_vp, _i, _i, _i, _i, _i, _i, _i],
+    "rcflow_surf_reset": [_vp, _i],
+    "rcflow_surf_close": [_vp, _i],
+    "rcflow_surf_info": [_vp, _i, C.POINTER(SurfInfo)],
     "rcflow_comm_unique_id": [_vp],
     "rcflow_comm_init": [_vp, _vp, _i, _i],
     "rcflow_comm_destroy": [_vp],

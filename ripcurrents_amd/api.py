@@ -41,9 +41,10 @@ from ._lib import RC_PIV_REPLACE, PivInfo, PivParams
 from ._lib import RC_TRANSECTS_FLOW, RC_TRANSECTS_GRAY, RC_TRANSECTS_SUMS, TransectLine, TransectsInfo, TransectsParams
 from ._lib import RC_KINEMATICS_MAX_RADIUS, RC_KINEMATICS_RELATIVE, RC_KINEMATICS_SUMS, KinematicsInfo, KinematicsParams
 from ._lib import RC_SHORE_HIST, SHORE_SOURCES, ShorelineInfo, ShorelineParams
+from ._lib import RC_SURF_MAX_CHANNELS, SurfInfo, SurfParams
 
 __all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState", "Waves", "Piv", "Transects", "Kinematics",
-           "Shoreline"]
+           "Shoreline", "Surf"]
 
 
 # rc_draw_prim as a numpy record (32 bytes): what Context.draw takes and Context.tracers_prims returns
@@ -96,6 +97,13 @@ SHORELINE_SUMMARY = ("thr", "N", "eta_q32", "positions", "dry", "wet", "outliers
 SHORELINE_DTYPE = np.dtype([("flags", "<i4"), ("k", "<i4"), ("pos", "<i4"), ("agree", "<i4"), ("wx", "<i4"), ("wy", "<i4"), ("x", "<f4"),
                             ("y", "<f4"), ("dist_m", "<f4"), ("nv", "<i4"), ("pos_min", "<i4"), ("pos_max", "<i4"), ("pos_q", "<i4"),
                             ("pos_mean", "<f4"), ("excursion_m", "<f4"), ("pad", "<i4")])
+# the eight words of a surf summary, in order
+SURF_SUMMARY = ("n", "now", "surf", "sum_q", "bands", "channel_lines", "channels", "pushes")
+# rc_surf_line (64 bytes) and rc_surf_channel (32 bytes) as numpy records: what Context.surf_read returns
+SURF_LINE_DTYPE = np.dtype([("flags", "<i4"), ("k0", "<i4"), ("k1", "<i4"), ("load", "<i4"), ("peak", "<i4"), ("kpeak", "<i4"), ("ix", "<i4"),
+                            ("iy", "<i4"), ("ox", "<i4"), ("oy", "<i4"), ("ref", "<i4"), ("share", "<i4"), ("width_m", "<f4"), ("pad", "<i4", (3,))])
+SURF_CHANNEL_DTYPE = np.dtype([("first", "<i4"), ("count", "<i4"), ("centre", "<i4"), ("share", "<i4"), ("cx", "<i4"), ("cy", "<i4"),
+                               ("width_m", "<f4"), ("pad", "<i4")])
 # rc_track as a numpy record (128 bytes): what Context.tracks_read returns
 TRACK_DTYPE = np.dtype([("id", "<i8"), ("parent", "<i8"), ("first_push", "<i8"), ("area_sum", "<i8"), ("fx_sum", "<i8"), ("fy_sum", "<i8"),
                         ("m_sum", "<i8"), ("slot", "<i4"), ("label", "<i4"), ("flags", "<i4"), ("age", "<i4"), ("hits", "<i4"),
@@ -1869,6 +1877,85 @@ class Context:
     def shoreline_close(self, stream=0):
         self._lifecycle("shoreline", "close", stream)
 
+    # ------------------------------------------------------------------ surf zone
+    def surf_open(self, w, h, lines=(), window=256, bright=180, delta=40, q_min=100, min_run=3, span=6, ratio=500, min_load=0, min_lines=2,
+                  vis_permille=500, metres_per_pixel=1.0, stream=0):
+        """Opens the slot's surf zone on w x h grey frames (include/rcflow.h, "surf"): `lines` is a sequence of (x0, y0, x1, y1, n),
+        straight lines in pixels FROM LAND TO SEA with n samples each, listed in alongshore order; without lines the session is
+        pixels only.  A pixel breaks in a frame when it is at least `bright` and at least `delta` above its mean over the last
+        `window` frames; it is in the surf zone when it broke in q_min per mille of them; a line whose load falls below `ratio` per
+        mille of the lower median of the lines within `span` of it is a channel line.  The state takes about window + 10 bytes
+        per pixel of device memory."""
+        arr = _transect_lines(lines) if len(lines) else None
+        p = SurfParams(window=int(window), bright=int(bright), delta=int(delta), q_min=int(q_min), min_run=int(min_run), span=int(span),
+                       ratio=int(ratio), min_load=int(min_load), min_lines=int(min_lines), vis_permille=int(vis_permille), flags=0, pad=0,
+                       metres_per_pixel=float(metres_per_pixel))
+        self._bind(stream)          # the state is zeroed on the slot's stream: the one the pushes will run on
+        check(self._lib.rcflow_surf_open(self._h, stream, int(w), int(h), arr, len(lines), C.byref(p)))
+
+    def surf_info(self, stream=0):
+        """dict(w, h, the parameters, lines, samples, launches_per_push, held, pushes, device_bytes); never blocks."""
+        return _record(self._info("surf", SurfInfo(), stream), skip=("flags", "pad"))
+
+    def surf_push(self, gray, now=None, surf=None, q=None, mean=None, sd=None, picture=None, lines=None, channels=None, summary=None, stream=0):
+        """One grey frame: HxW uint8 device tensor, rows may be padded; nothing is synchronised.  Outputs are preallocated device
+        tensors, each optional: now HxW uint8 (255 where the pixel breaks in this frame), surf HxW uint8 (255 in the surf zone: what
+        regions_push takes), q HxW int16 (frames of the window in which the pixel broke), mean HxW uint8, sd HxW uint8 (twice the
+        standard deviation: the variance image), picture HxWx3 uint8 (q in JET colours), lines LINESx64 uint8 (rc_surf_line
+        records; view the host copy as SURF_LINE_DTYPE), channels 32x32 uint8 (rc_surf_channel; SURF_CHANNEL_DTYPE), summary 8 int64
+        (SURF_SUMMARY).  Records and summary also stay on the slot for surf_read."""
+        i = self._info("surf", SurfInfo(), stream)
+        h, w = i.h, i.w
+        if not _is_t(gray) or gray.dim() != 2:
+            raise ValueError("gray must be an HxW uint8 device tensor, as opened")
+        gp = self._in_image(gray, torch.uint8, "gray", (h, w))
+        np_ = self._out_image(now, torch.uint8, "now", (h, w))
+        sp = self._out_image(surf, torch.uint8, "surf", (h, w))
+        qp = self._out_image(q, torch.int16, "q", (h, w))
+        mp = self._out_image(mean, torch.uint8, "mean", (h, w))
+        dp = self._out_image(sd, torch.uint8, "sd", (h, w))
+        pp = self._out_image(picture, torch.uint8, "picture", (h, w, 3))
+        lp = self._out_array(lines, torch.uint8, "lines", i.lines * 64)
+        cp = self._out_array(channels, torch.uint8, "channels", RC_SURF_MAX_CHANNELS * 32)
+        up = self._out_array(summary, torch.int64, "summary", 8)
+        self._bind(stream)
+        check(self._lib.rcflow_surf_push_dev(self._h, stream, *gp, 1, *np_, *sp, *qp, *mp, *dp, *pp, lp, cp, up))
+
+    def surf_prims(self, color=0x00ffff, thickness=1, disc_radius=3, out=None, stream=0):
+        """The breaker line and the channels of the last push as lines - 1 + 32 primitives for draw() -> a device uint8 tensor of
+        rc_draw_prim records: a segment from the outer edge of every line with a band to that of the next such line, a disc at
+        every recorded channel's centre; kind 0 elsewhere."""
+        out = self._prims_out(out, self.surf_info(stream)["lines"] - 1 + RC_SURF_MAX_CHANNELS)
+        self._bind(stream)
+        check(self._lib.rcflow_surf_prims_dev(self._h, stream, int(color), int(thickness), int(disc_radius), self._ptr(out)))
+        return out
+
+    def surf_read(self, stream=0):
+        """Waits for the slot's stream -> (lines LINES SURF_LINE_DTYPE, channels SURF_CHANNEL_DTYPE: the recorded ones, dict of the
+        summary by SURF_SUMMARY names) of the last push; zeros before the first."""
+        rec = np.zeros(self.surf_info(stream)["lines"], SURF_LINE_DTYPE)
+        chan = np.zeros(RC_SURF_MAX_CHANNELS, SURF_CHANNEL_DTYPE)
+        out = self._summary(self._lib.rcflow_surf_read, stream, SURF_SUMMARY, rec.ctypes.data if rec.size else None, chan.ctypes.data)
+        return rec, chan[:min(out["channels"], RC_SURF_MAX_CHANNELS)], out
+
+    def surf_table(self, stream=0):
+        """Waits -> (SAMPLES TRANSECT_SAMPLE_DTYPE, LINES TRANSECT_GEOM_DTYPE): the open session's table, from the device."""
+        info = self.surf_info(stream)
+        table, geom = np.zeros(info["samples"], TRANSECT_SAMPLE_DTYPE), np.zeros(info["lines"], TRANSECT_GEOM_DTYPE)
+        self._bind(stream)
+        check(self._lib.rcflow_surf_table_read(self._h, stream, table.ctypes.data if table.size else None, geom.ctypes.data if geom.size else None))
+        return table, geom
+
+    def surf_set(self, bright, delta, q_min, ratio, min_load, vis_permille, stream=0):
+        """bright, delta, q_min, ratio, min_load and vis_permille from the next push on."""
+        check(self._lib.rcflow_surf_set(self._h, stream, int(bright), int(delta), int(q_min), int(ratio), int(min_load), int(vis_permille)))
+
+    def surf_reset(self, stream=0):
+        self._lifecycle("surf", "reset", stream)
+
+    def surf_close(self, stream=0):
+        self._lifecycle("surf", "close", stream)
+
     # ------------------------------------------------------------------ rip regions
     def regions_open(self, w, h, connectivity=8, min_area=1, max_regions=1024, stream=0):
         """Opens the slot's region labelling for w x h masks: connected components (4 or 8 neighbours) numbered in raster
@@ -2220,6 +2307,21 @@ class Shoreline(_Product):
         self.ctx.shoreline_set(threshold, min_sep, max_jump, self.stream)
 
 
+class Surf(_Product):
+    """The surf zone of one slot as an object: Context.surf_* with the context and the slot bound.  Opens on construction (lines
+    and the parameters of Context.surf_open as keywords), closes on close() or at the end of a with block."""
+    product = "surf"
+
+    def prims(self, **kw):
+        return self.ctx.surf_prims(stream=self.stream, **kw)
+
+    def table(self):
+        return self.ctx.surf_table(self.stream)
+
+    def set(self, bright, delta, q_min, ratio, min_load, vis_permille):
+        self.ctx.surf_set(bright, delta, q_min, ratio, min_load, vis_permille, self.stream)
+
+
 def kinematics_taps(radius, sigma):
     """rcflow_kinematics_taps: the smoothing taps g_0..g_radius as float32, without a context or a GPU."""
     taps = np.zeros(max(0, min(int(radius), RC_KINEMATICS_MAX_RADIUS)) + 1, np.float32)
@@ -2256,6 +2358,19 @@ def shoreline_plan(w, h, lines, metres_per_pixel=1.0):
     check(lib.rcflow_shoreline_plan(int(w), int(h), arr, len(arr), float(metres_per_pixel), None, None, C.byref(total)))
     table, geom = np.zeros(total.value, TRANSECT_SAMPLE_DTYPE), np.zeros(len(arr), TRANSECT_GEOM_DTYPE)
     check(lib.rcflow_shoreline_plan(int(w), int(h), arr, len(arr), float(metres_per_pixel), table.ctypes.data, geom.ctypes.data, None))
+    return table, geom
+
+
+def surf_plan(w, h, lines, metres_per_pixel=1.0):
+    """rcflow_surf_plan: the sample table and the per-line constants of `lines` (land to sea) on a w x h picture, without a context
+    or a GPU -> (SAMPLES TRANSECT_SAMPLE_DTYPE, LINES TRANSECT_GEOM_DTYPE)."""
+    lib = _lib.load()
+    arr = _transect_lines(lines) if len(lines) else None
+    total = C.c_int(0)
+    check(lib.rcflow_surf_plan(int(w), int(h), arr, len(lines), float(metres_per_pixel), None, None, C.byref(total)))
+    table, geom = np.zeros(total.value, TRANSECT_SAMPLE_DTYPE), np.zeros(len(lines), TRANSECT_GEOM_DTYPE)
+    if len(lines):
+        check(lib.rcflow_surf_plan(int(w), int(h), arr, len(lines), float(metres_per_pixel), table.ctypes.data, geom.ctypes.data, None))
     return table, geom
 
 

@@ -322,6 +322,25 @@ struct RcShoreline {
     RcZeroFence zf;
 };
 
+// Surf zone of one stream slot (surf_kernels.hip).  Everything is allocated by rcflow_surf_open and released by
+// rcflow_surf_close / rcflow_destroy.
+struct RcSurf {
+    bool open = false;
+    int w = 0, h = 0;
+    rc_surf_params prm{};           // bright, delta, q_min, ratio, min_load and vis_permille: as rcflow_surf_set left them
+    int L = 0, S = 0;               // lines, samples in all
+    int P = 0, tiles = 0;           // row pitch of the state planes in pixels (w rounded up to 4); runs of 256 pixels in P h
+    long long pushes = 0;           // since open / reset; the next frame goes to ring slot pushes mod window
+    RcBuf table;                    // [S] rc_transect_sample | [L] rc_transect_geom, written once by open
+    RcBuf ring;                     // [window][h][P] bytes: the grey frames
+    RcBuf bits;                     // [window][tiles][4] uint64: the flags, word k of a tile holds pixel 4 lane + k in bit `lane`
+    RcBuf sums;                     // S1 [h][P] uint32 | S2 [h][P] uint32 | Q [h][P] uint16
+    RcBuf out;                      // the last push: summary 8 int64 | channels [RC_SURF_MAX_CHANNELS] | lines [L]
+    RcBuf ctl;                      // SfCtl: the ticket, the last surf@0's counts, every block's counts
+    RcBuf jet;                      // COLORMAP_JET, 768 bytes
+    RcZeroFence zf;
+};
+
 // warp_kernels.hip: one launch of the affine / perspective warp
 struct RcWarpArgs {
     const uint8_t* src; size_t step;
@@ -405,6 +424,7 @@ struct RcSlot {
     RcTransects ts;
     RcKinematics kn;
     RcShoreline sh;
+    RcSurf sf;
     RcPhaseCorr pc;
 };
 
@@ -466,7 +486,8 @@ struct rc_ctx {
 // vertices, and are booked with them, under "stream".  The flow kinematics differentiate one flow field, pixel for pixel, with
 // no state from push to push: an operation on the field as the shear-rate colouring among the post-ops (flow_postop) is, so they
 // are booked with those, under "farneback".  The shoreline works on pictures, not on flow: the time-exposure MEAN, the plan view's
-// picture or a frame, as the time-exposure images and the wave spectra do, and is booked with them, under "overlay".
+// picture or a frame, as the time-exposure images and the wave spectra do, and is booked with them, under "overlay".  The surf zone
+// is the time exposure's fourth picture and what is read off it, and is booked there too.
 #define RC_BUCKET_TABLE(X) \
     X(RC_B_FARNEBACK, "farneback") X(RC_B_POLAR, "polar") X(RC_B_THRESHOLD, "threshold") X(RC_B_OVERLAY, "overlay") \
     X(RC_B_EROSION, "erosion") X(RC_B_CODEC, "codec") X(RC_B_STREAM, "stream")
@@ -508,7 +529,8 @@ struct rc_ctx {
     X(RC_K_PIV, "piv", RC_B_FARNEBACK) /* @0 the pair's sums, ring and accumulators, @1 score, peak and records, @2 validation, field, picture, summary */ \
     X(RC_K_TRANSECTS, "transects", RC_B_STREAM) /* @0 sampling, rings and accumulators, @1 velocity, transport, jets, records and summary, @2 time stack and Hovmoeller picture */ \
     X(RC_K_KINEMATICS, "kinematics", RC_B_FARNEBACK) /* @0 smoothing, derivatives, invariants, first sums and the threshold, @1 cores, mask, picture, records and summary */ \
-    X(RC_K_SHORELINE, "shoreline", RC_B_OVERLAY) /* @0 indicator, box, plane, histogram and Otsu, @1 lines, @2 outliers, ring, window and records, @3 mask, plane and histogram out, @4 primitives */
+    X(RC_K_SHORELINE, "shoreline", RC_B_OVERLAY) /* @0 indicator, box, plane, histogram and Otsu, @1 lines, @2 outliers, ring, window and records, @3 mask, plane and histogram out, @4 primitives */ \
+    X(RC_K_SURF, "surf", RC_B_OVERLAY) /* @0 ring, sums, flags, pictures and counts, @1 lines, @2 reference, channels, records and summary, @3 primitives */
 #define RC_ROW_ID(id, ...) id,
 enum { RC_BUCKET_TABLE(RC_ROW_ID) RC_B_BUCKETS };
 enum { RC_KIND_TABLE(RC_ROW_ID) RC_K_KINDS };
@@ -566,7 +588,7 @@ void rc_draw_launch(rc_ctx* ctx, hipStream_t cur, uint8_t* d_img, size_t step, i
                     int n, unsigned long long* d_skipped);
 // warp_kernels.hip
 void rc_warp_launch(rc_ctx* ctx, hipStream_t cur, RcWarpArgs& a, bool perspective);
-// transects_kernels.hip: the per-line part of rcflow_transects_plan, shared with rcflow_shoreline_plan.  Line i's samples from
+// transects_kernels.hip: the per-line part of rcflow_transects_plan, shared with rcflow_shoreline_plan and rcflow_surf_plan.  Line i's samples from
 // table[first] on and its constants into geom[i] (each may be null); RC_EINVAL with the text set for an endpoint that is not
 // finite, a line of no length or a sample outside the picture.  The bounds on n stay with each caller
 int rc_line_plan(const char* who, int w, int h, const rc_transect_line& l, int i, int first, double metres_per_pixel, double fps,
@@ -594,7 +616,7 @@ struct RcProfScope {
     } while (0)
 
 // ---------------------------------------------------------------------------- per-slot products
-// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView, RcWaves, RcPiv, RcTransects, RcKinematics and RcShoreline share one lifecycle.  A product supplies
+// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView, RcWaves, RcPiv, RcTransects, RcKinematics, RcShoreline and RcSurf share one lifecycle.  A product supplies
 //   void rc_state_free(T&)             frees every buffer and the fence; the state is T() again
 //   int rc_state_zero(RcSlot&, T&)     rc_fence_zero of what open / reset clear, and the counters
 // and open / reset / close are written once, here.
@@ -612,6 +634,7 @@ void rc_state_free(RcPiv& v);
 void rc_state_free(RcTransects& v);
 void rc_state_free(RcKinematics& k);
 void rc_state_free(RcShoreline& v);
+void rc_state_free(RcSurf& v);
 int rc_state_zero(RcSlot& s, RcTimex& t);
 int rc_state_zero(RcSlot& s, RcFrameStab& f);
 int rc_state_zero(RcSlot& s, RcRipMap& m);
@@ -626,6 +649,7 @@ int rc_state_zero(RcSlot& s, RcPiv& v);
 int rc_state_zero(RcSlot& s, RcTransects& v);
 int rc_state_zero(RcSlot& s, RcKinematics& k);
 int rc_state_zero(RcSlot& s, RcShoreline& v);
+int rc_state_zero(RcSlot& s, RcSurf& v);
 
 // The tail of every open.  The caller has validated, selected the device and built `fresh` (rc: what its allocations
 // returned).  The state that is open is touched only once nothing can be refused any more: a refused open leaves it as it
