@@ -116,8 +116,9 @@ int rcflow_use_own_stream(rc_ctx* ctx, int stream);
  * Measurement switches, all speed-only except where noted: "xcd_remap" (1) XCD-aware tile order;
  * "poly_tile_h" (32 | 48) rows per expansion block -- changes the per-tile DC and with it the last
  * bits of R; "poly_mfma" (0) vertical pass of the expansion on the matrix cores -- different
- * summation order, same tolerance; "overlap" (0) clip path on two streams; "hist_blocks" (0 = default)
- * cap on histogram blocks; "frame_overlap" (0 | 1 | 2, default 1): the frame loop on two streams -- upload and expansion of
+ * summation order, same tolerance; "overlap" (0) clip path on two streams; "hist_blocks" (0 = default, 8192)
+ * cap on histogram blocks per launch: divided by the launch's field count, with a floor of 8 blocks per field (see
+ * rcflow_histogram_clip_dev); "frame_overlap" (0 | 1 | 2, default 1): the frame loop on two streams -- upload and expansion of
  * frame t+1 beside the flow kernels of frame t; 1 = rcflow_push_frame_u8 only (the library owns the upload), 2 = also
  * rcflow_push_frame_dev, the caller then guaranteeing that d_frame is complete when the call is made; "merge_small" (1) merged launches for calls of one or two frames; "fuse_pyr" (1)
  * pyramid scales 1 and 2 written by the scale-0 expansion launch (pyr_scale 0.5, exact half / quarter sizes);
@@ -250,7 +251,12 @@ int rcflow_histogram_dev(rc_ctx* ctx, int stream, const float* d_flow_xy, size_t
  * 2^31 / (w*h) frames): a call that could carry histsum past INT32_MAX returns RC_ESTATE and counts nothing;
  * rcflow_histogram_reset_dev starts a new segment (asynchronous zero of the counters only). */
 int rcflow_histogram_reset_dev(rc_ctx* ctx, int stream);
-/* The same for `count` resident flow fields in one launch (a segment's flows). */
+/* The same for `count` resident flow fields in one launch (a segment's flows), flow_frame_stride bytes apart: for
+ * count > 1 at least one frame's range and a multiple of 8 (RC_EINVAL otherwise); ignored for count == 1.  The launch is
+ * (blocks per field) x count blocks of 256 threads, a thread taking items of 2 x 4 pixels in rounds: blocks per field =
+ * min(ceil(items / 256), 2048, max(8, B / count)) with B = option "hist_blocks", or 8192 when that is 0 -- the option is
+ * divided by `count` and has a floor of 8 blocks per field.  32 fields of 1920 x 1080 with the default: 256 blocks per
+ * field and four rounds. */
 int rcflow_histogram_clip_dev(rc_ctx* ctx, int stream, const float* d_flows_xy,
                               size_t flow_frame_stride, size_t flow_step, int count, int w, int h);
 /* Replaces the threshold scans of create_histogram (ripcurrents_module.cpp:109-144):

@@ -48,9 +48,17 @@ int rc_clip_check(const char* who, const char* name, const void* p, size_t frame
                   int flags) {
     if (int rc = rc_image_check(who, name, p, step, w, h, bpp, align, flags)) return rc;
     const size_t frame = step * (size_t)(h - 1) + (size_t)w * bpp;   // the range of one frame
-    if (!p || n <= 1 || frame_stride >= frame) return RC_OK;
-    rc_set_error("%s: bad clip argument %s (a frame stride of %zu bytes below the %zu of a frame)", who, name, frame_stride, frame);
-    return RC_EINVAL;
+    if (!p || n <= 1) return RC_OK;
+    if (frame_stride < frame) {
+        rc_set_error("%s: bad clip argument %s (a frame stride of %zu bytes below the %zu of a frame)", who, name, frame_stride, frame);
+        return RC_EINVAL;
+    }
+    // the rows of frames 1, 2, ... start at p + k * frame_stride: held to the alignment the step is held to
+    if (frame_stride % align) {
+        rc_set_error("%s: bad clip argument %s (a frame stride of %zu bytes that is no multiple of the alignment %d)", who, name, frame_stride, align);
+        return RC_EINVAL;
+    }
+    return RC_OK;
 }
 
 int rc_prims_check(const char* who, const void* d_prims, int thickness, int disc_radius) {

@@ -74,8 +74,9 @@ inline int rc_flow_check(const char* who, const char* name, const void* p, size_
     return rc_image_check(who, name, p, step, w, h, 8, 8, flags | RC_ARG_ANY_BASE);
 }
 
-// a run of n images frame_stride bytes apart: the first frame's form, and for n > 1 a stride of at least one frame's range.
-// The bounds on n stay with each caller
+// a run of n images frame_stride bytes apart: the first frame's form, and for n > 1 a stride of at least one frame's range
+// that is a multiple of the alignment (every later frame's rows are then aligned as the first frame's are).  The bounds on n
+// stay with each caller
 int rc_clip_check(const char* who, const char* name, const void* p, size_t frame_stride, size_t step, int n, int w, int h, int bpp, int align,
                   int flags);
 

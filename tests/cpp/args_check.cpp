@@ -252,6 +252,28 @@ int main() {
                                 CHECK(rc == RC_OK || (!strncmp(g_text, "clip_form: ", 11) && strstr(g_text, "d_frames")), "rc_clip_check's text \"%s\"", g_text);
                                 clip_cases++;
                             }
+    // the frame stride against the alignment, as rcflow_histogram_clip_dev declares its float2 clip (align 8, any base): for n > 1 a
+    // stride that is no multiple of it would start the rows of frame 1 off the alignment and is refused; for n <= 1 the stride is
+    // not looked at; with align 1 (8-bit frames, and the flow outputs of the Farneback clips) every stride of a frame or more passes
+    long clip_stride_refused = 0, clip_stride_ignored = 0;
+    for (int w = 1; w <= 3; w++)
+        for (int h = 1; h <= 3; h++)
+            for (long pad = 0; pad <= 16; pad += 8)
+                for (int n = 0; n <= 3; n++)
+                    for (long d = 0; d <= 17; d++)
+                        for (int align : {1, 8}) {
+                            const long step = 8L * w + pad, bound = step * (h - 1) + 8L * w, stride = bound + d;
+                            const bool want = n <= 1 || stride % align == 0;
+                            g_text[0] = 0;
+                            const int rc = rc_clip_check("clip_form", "d_flows", g_buf + 4, (size_t)stride, (size_t)step, n, w, h, 8, align, RC_ARG_IN | RC_ARG_ANY_BASE);
+                            CHECK((rc == RC_OK) == want && (rc == RC_OK || rc == RC_EINVAL), "rc_clip_check gave %d at align %d w %d h %d step %ld n %d stride %ld", rc, align, w, h, step, n, stride);
+                            CHECK(rc == RC_OK || (!strncmp(g_text, "clip_form: ", 11) && strstr(g_text, "d_flows")), "rc_clip_check's text \"%s\"", g_text);
+                            if (!want) clip_stride_refused++;
+                            if (n <= 1 && stride % align) clip_stride_ignored++;
+                            clip_cases++;
+                        }
+    CHECK(clip_stride_refused > 0 && clip_stride_ignored > 0, "no clip with a frame stride off the alignment was refused (%ld) or, with one frame, accepted (%ld)",
+          clip_stride_refused, clip_stride_ignored);
     // rc_ptr_check: null, and the base against the alignment
     CHECK(rc_ptr_check("p", "x", nullptr) == RC_EINVAL && rc_ptr_check("p", "x", nullptr, 16, RC_ARG_OPTIONAL) == RC_OK, "a null pointer");
     for (int off = 0; off < 32; off++)

@@ -63,7 +63,9 @@ def _table(dev_in, dev_out, host_in, host_out):
     entry("rcflow_histogram_dev", flow, flow_bad)
     entry("rcflow_histogram_clip_dev", [("d_flows", I), ("flow_frame_stride", FS * H), ("flow_step", FS), ("count", 2), ("w", W), ("h", H)],
           ptr("d_flows", "flow_step", 8, FS) + [({"flow_frame_stride": FS * (H - 1) + W * 8 - 1}, "d_flows", EINVAL), ({"count": 0}, None, EINVAL),
-                                               ({"count": 65536}, None, EINVAL)])
+                                               ({"count": 65536}, None, EINVAL),
+                                               # a frame stride off the 8 bytes of a float2: the rows of frame 1 would be 4-byte aligned
+                                               ({"flow_frame_stride": FS * H + 4}, "d_flows", EINVAL)])
     entry("rcflow_thresholds_words_dev", [("d_words", I)], ptr("d_words"))
     entry("rcflow_histogram_write", [("words", HI)], ptr("words"))
     entry("rcflow_histogram_device_ptr", [("d_words", vp)], ptr("d_words"))
