@@ -552,6 +552,13 @@ SIGNATURES = {
     "rcflow_profile_read": [_vp, _i, C.POINTER(C.c_char_p), C.POINTER(_i), C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)],
 }
 
+# diagnostics librcflow.so exports beside the interface of include/rcflow.h (the test hooks of rcflow_api.hip that take a
+# context): name -> argtypes
+DEBUG_SIGNATURES = {
+    "rcflow_debug_level_R": [_vp, _i, _i, _i, _vp, C.POINTER(_i), C.POINTER(_i)],
+    "rcflow_debug_level_image": [_vp, _i, _i, _i, _vp, C.POINTER(_i), C.POINTER(_i)],
+}
+
 _LIB = None
 
 
@@ -570,6 +577,10 @@ def load():
         fn.argtypes = args
         fn.restype = C.c_char_p if name == "rcflow_last_error" else C.c_int
     lib.rcflow_destroy.restype = None
+    for name, args in DEBUG_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = args
+        fn.restype = C.c_int
     _LIB = lib
     return lib
 

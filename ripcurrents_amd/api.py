@@ -475,6 +475,28 @@ class Context:
                                                  self._ptr(R)))
         return R
 
+    def debug_level_R(self, w, h, pyr_scale, level, slot, stream=0):
+        """Diagnostic (rcflow_debug_level_R): upstream's R (h_k x w_k x 5) that the slot's last Farneback call, on w x h
+        frames at `pyr_scale`, left in ring entry `slot` of scale `level`."""
+        return self._debug_level(self._lib.rcflow_debug_level_R, w, h, pyr_scale, level, slot, stream, (5,))
+
+    def debug_level_image(self, w, h, pyr_scale, level, slot, stream=0):
+        """Diagnostic (rcflow_debug_level_image): the pyramid image (h_k x w_k) of ring entry `slot` of scale `level` >= 1."""
+        return self._debug_level(self._lib.rcflow_debug_level_image, w, h, pyr_scale, level, slot, stream, ())
+
+    def _debug_level(self, fn, w, h, pyr_scale, level, slot, stream, tail):
+        _, wk, hk = self.level_geometry(w, h, pyr_scale, 64, max(level, 0))
+        # the plan's own size of the scale, asked before anything is written (rcflow_debug_level_flow_ptr reports it whether
+        # or not the scale has a flow field yet)
+        gw, gh, p = C.c_int(), C.c_int(), C.c_void_p()
+        rc = self._lib.rcflow_debug_level_flow_ptr(self._h, C.c_int(stream), C.c_int(level), C.c_int(0), C.byref(p), C.byref(gw), C.byref(gh))
+        if rc in (0, -6) and (gw.value, gh.value) != (wk, hk):
+            raise RcflowError(-1, "the slot's plan has %d x %d at scale %d, not %d x %d" % (gw.value, gh.value, level, wk, hk))
+        out = torch.empty((hk, wk) + tail, dtype=torch.float32, device=self.device)
+        self._bind(stream)
+        check(fn(self._h, stream, level, slot, self._ptr(out), None, None))
+        return out
+
     def stage_initial_flow(self, flow, pyr_scale, levels, stream=0):
         """The reduction OPTFLOW_USE_INITIAL_FLOW applies to the initial field (rcflow_stage_initial_flow_dev):
         HxWx2 float32 (any row stride) -> the coarsest scale's h_k x w_k x 2, times pyr_scale^k."""

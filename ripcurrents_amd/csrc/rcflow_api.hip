@@ -332,6 +332,56 @@ extern "C" int rcflow_debug_level_flow_ptr(rc_ctx* ctx, int stream, int level, i
     return RC_ESTATE;
 }
 
+// Diagnostics (not part of include/rcflow.h; tests/test_gpu_polyexp_forms.py): what the level driver's expansion launches
+// of the slot's last Farneback call left in ring entry `slot` of scale `level` -- valid after any Farneback call on the
+// slot, until the next one.  Which frame an entry holds is the driver's: the two-image calls put prev in entry 0 and next
+// in entry 1; rcflow_farneback_clip_dev puts frame t in entry t % nslots (nslots = chunk + 1, or 2 chunk + 1 when option
+// "overlap" splits a clip longer than a chunk), so a clip that fits the ring has frame t in entry t.
+static int level_entry(const char* who, rc_ctx* ctx, int stream, int level, int slot, const void* d_out, const char* out_name, RcSlot** ps) {
+    RcSlot* s = rc_slot(ctx, stream);
+    if (!s) return RC_EINVAL;
+    if (!s->plan.valid) { rc_set_error("%s: no plan on the slot (no Farneback call since the last size, parameter or option change)", who); return RC_ESTATE; }
+    if (level < 0 || level >= s->plan.nlev || slot < 0 || slot >= s->plan.nslots) {
+        rc_set_error("%s: level %d (0..%d) or slot %d (0..%d) outside the plan", who, level, s->plan.nlev - 1, slot, s->plan.nslots - 1);
+        return RC_EINVAL;
+    }
+    if (int rc = rc_ptr_check(who, out_name, d_out, 4, RC_ARG_OUT)) return rc;
+    RC_HIP(hipSetDevice(ctx->device));
+    if (s->aux) RC_HIP(hipStreamSynchronize(s->aux));       // the two-stream forms expand on the slot's second stream
+    *ps = s;
+    return RC_OK;
+}
+
+// The entry's R as upstream's (y, x, yy, xx, xy) per pixel: d_R5 = h x w x 5 floats, dense.  The planes are unpacked with
+// the stored scale of the plan that wrote them (1/2 and 1/4 on the fast path, 1 under option "exact": powers of two, so
+// the unpacked values are exactly what the kernel computed).
+extern "C" int rcflow_debug_level_R(rc_ctx* ctx, int stream, int level, int slot, float* d_R5, int* w, int* h) {
+    RcSlot* s = nullptr;
+    if (int rc = level_entry(__func__, ctx, stream, level, slot, d_R5, "d_R5", &s)) return rc;
+    const RcLevel& L = s->plan.lv[level];
+    const size_t n = (size_t)L.w * L.h;
+    rc_launch_unpack_R5((const float4*)s->RA[level].p + (size_t)slot * n, (const float*)s->RB[level].p + (size_t)slot * n, d_R5, (int)n,
+                        !s->plan.exact, s->cur);
+    RC_HIP(hipGetLastError());
+    if (w) *w = L.w;
+    if (h) *h = L.h;
+    return RC_OK;
+}
+
+// The entry's pyramid image I[level]: d_I = h x w floats, dense.  Scale 0 has an image only under option "exact" (the fast
+// path blurs the 8-bit frame inside the expansion).
+extern "C" int rcflow_debug_level_image(rc_ctx* ctx, int stream, int level, int slot, float* d_I, int* w, int* h) {
+    RcSlot* s = nullptr;
+    if (int rc = level_entry(__func__, ctx, stream, level, slot, d_I, "d_I", &s)) return rc;
+    if (level == 0 && !s->plan.exact) { rc_set_error("%s: level 0 has no image on the fast path (it is fused into the expansion)", __func__); return RC_EINVAL; }
+    const RcLevel& L = s->plan.lv[level];
+    const size_t n = (size_t)L.w * L.h;
+    RC_HIP(hipMemcpyAsync(d_I, (const float*)s->I[level].p + (size_t)slot * n, n * sizeof(float), hipMemcpyDeviceToDevice, s->cur));
+    if (w) *w = L.w;
+    if (h) *h = L.h;
+    return RC_OK;
+}
+
 // rc_plan_prepare_poly with a text for its refusal; the ranges of n and sigma stay with each caller
 static int poly_prepare(const char* who, int n, double sigma, int exact_taps, RcPolyK& pk) {
     const int rc = rc_plan_prepare_poly(n, sigma, exact_taps, pk);

@@ -114,6 +114,20 @@ def test_entry_points_without_a_context_name_themselves_when_they_refuse():
     assert not any(f32) and not any(f64) and not any(i32)                    # nothing was written
 
 
+def test_level_diagnostics_are_exported_and_refuse_a_null_context():
+    """rcflow_debug_level_R / rcflow_debug_level_image read back what the level driver's expansion launches wrote
+    (tests/test_gpu_polyexp_forms.py); they are not part of include/rcflow.h and have signatures of their own in _lib.py."""
+    from ripcurrents_amd import _lib
+    lib = _lib.load()
+    assert set(_lib.DEBUG_SIGNATURES) == {"rcflow_debug_level_R", "rcflow_debug_level_image"}
+    assert not set(_lib.DEBUG_SIGNATURES) & set(_lib.SIGNATURES)
+    out, i32 = (ctypes.c_float * 8)(), ctypes.pointer(ctypes.c_int(7))
+    for name in _lib.DEBUG_SIGNATURES:
+        assert getattr(lib, name)(None, 0, 0, 0, out, i32, i32) == -1
+        assert b"context" in lib.rcflow_last_error()
+    assert not any(out) and i32.contents.value == 7
+
+
 def test_synthetic_clips_are_deterministic():
     from ripcurrents_amd import synth
     a = synth.surf_clip(160, 120, 3, seed=1234)

@@ -295,6 +295,39 @@ def test_refusals_after_priming_acquiring_and_planning(ctx, buffers):
     assert bool((dev_out == SENTINEL).all()) and not bool(dev_in.any())
 
 
+def test_level_diagnostics_refuse_without_a_plan_and_outside_it(ctx, buffers):
+    """rcflow_debug_level_R / rcflow_debug_level_image (not part of include/rcflow.h): RC_ESTATE while the slot has no plan (an
+    option change drops it), RC_EINVAL for a level or a ring entry outside the plan, a null or misaligned output and scale 0's
+    image on the fast path; nothing is written."""
+    dev_in, dev_out, host_in, host_out = buffers
+    I, O = dev_in.data_ptr(), dev_out.data_ptr()
+    i32 = C.pointer(C.c_int(0))
+    P = C.byref(FarnebackParams(0.5, 1, 3, 1, 5, 1.1, 0))
+    names = (("rcflow_debug_level_R", "d_R5"), ("rcflow_debug_level_image", "d_I"))
+
+    def entries(bad_of):
+        return [Entry(name, [("level", 0), ("slot", 0), (out, O), ("w", i32), ("h", i32)], bad_of(name, out), 2) for name, out in names]
+
+    ctx.set_option("chunk", 32)                  # its default: every slot's plan is dropped
+    rows = refused_calls(ctx, entries(lambda name, out: [({}, None, ESTATE), ({"level": 99}, None, ESTATE), ({out: None}, None, ESTATE)]))
+    # a plan of 2 scales (33 x 23 is cropped to scale 0 alone at levels = 1; 80 x 72 keeps scale 1) and chunk + 1 = 33 entries
+    w, h = 80, 72
+    assert ctx._lib.rcflow_level_geometry(w, h, 0.5, 1, 0, None, None) == 1
+    assert ctx._lib.rcflow_farneback_dev(ctx._h, 0, I, w, I + w * h, w, w, h, I + (64 << 10), w * 8, P) == 0
+    rows += refused_calls(ctx, entries(lambda name, out: [({"level": -1}, None, EINVAL), ({"level": 2}, None, EINVAL), ({"slot": -1}, None, EINVAL),
+                                                          ({"slot": 33}, None, EINVAL), ({out: None}, out, EINVAL), ({out: O + 2}, out, EINVAL)] +
+                                       ([({}, None, EINVAL)] if name.endswith("image") else [])))
+    print("[refusals] %d refused calls of the level diagnostics" % len(rows))
+    wrong = _wrong(rows)
+    assert len(rows) == 19 and not wrong, "\n".join(wrong)
+    # accepted at the edge of the plan: the last scale, the last ring entry
+    for name, _ in names:
+        assert getattr(ctx._lib, name)(ctx._h, 0, 1, 32, I + (128 << 10), i32, i32) == 0 and i32.contents.value == 36
+    ctx.sync()
+    torch.cuda.synchronize()
+    assert bool((dev_out == SENTINEL).all())
+
+
 def test_stage_polyexp_takes_a_negative_sigma_as_the_default(ctx):
     """Accepted, as it always was: the plan arithmetic reads any poly_sigma below FLT_EPSILON as 0.3 n (rc_plan.cpp), so -1 gives the
     planes of 0, bit for bit; the level drivers refuse a negative sigma, this stage entry point never did."""
