@@ -139,6 +139,13 @@ def update_matrices(R0, R1, flow):
     for i in range(min(5, h)):
         sy[i] *= border[i]; sy[h - 1 - i] *= border[i]
     sc = sy[:, None] * sx[None, :]
+    # optflow.cpp scales a pixel only where `(unsigned)(x - BORDER) >= (unsigned)(width - BORDER*2) || (unsigned)(y - BORDER)
+    # >= (unsigned)(height - BORDER*2)` holds.  For width (height) of 6..9 the right side wraps and the test is true for
+    # columns (rows) width - 5 .. 4 alone: the other columns keep scale 1 unless their row is scaled.  The C++ oracle and
+    # the kernels carry the same test; the factors themselves are the products above.
+    u32 = lambda v: np.asarray(v, np.int64) % (1 << 32)
+    in_border = (u32(xs - 5) >= u32(w - 10)) | (u32(ys - 5) >= u32(h - 10))
+    sc = np.where(in_border, sc, 1.0)
     r2, r3, r4, r5, r6 = r2 * sc, r3 * sc, r4 * sc, r5 * sc, r6 * sc
     M = np.empty((h, w, 5))
     M[..., 0] = r4 * r4 + r6 * r6

@@ -559,6 +559,15 @@ DEBUG_SIGNATURES = {
     "rcflow_debug_level_image": [_vp, _i, _i, _i, _vp, C.POINTER(_i), C.POINTER(_i)],
 }
 
+# diagnostics of the flow iteration (tests/test_gpu_flow_forms.py): the copy form of rcflow_debug_level_flow_ptr, which takes a
+# context, and the host-only form function, which takes none
+DEBUG_FLOW_SIGNATURES = {
+    "rcflow_debug_level_flow": [_vp, _i, _i, _i, _i, _vp, C.POINTER(_i), C.POINTER(_i)],
+    "rcflow_debug_flow_form": [_i] * 11 + [C.POINTER(_i), _i],
+}
+# RcFlowKernel of csrc/rc_common.h (tests/test_cabi_and_host.py compares the two)
+FLOW_KERNELS = {1: "w3", 2: "tile", 3: "big", 4: "sweep", 5: "runtime", 6: "rrc"}
+
 _LIB = None
 
 
@@ -577,7 +586,7 @@ def load():
         fn.argtypes = args
         fn.restype = C.c_char_p if name == "rcflow_last_error" else C.c_int
     lib.rcflow_destroy.restype = None
-    for name, args in DEBUG_SIGNATURES.items():
+    for name, args in list(DEBUG_SIGNATURES.items()) + list(DEBUG_FLOW_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int

@@ -484,6 +484,26 @@ class Context:
         """Diagnostic (rcflow_debug_level_image): the pyramid image (h_k x w_k) of ring entry `slot` of scale `level` >= 1."""
         return self._debug_level(self._lib.rcflow_debug_level_image, w, h, pyr_scale, level, slot, stream, ())
 
+    def debug_level_flow(self, w, h, pyr_scale, level, which, pair=0, stream=0):
+        """Diagnostic (rcflow_debug_level_flow): buffer A (which = 0) or B (1) of scale `level`, pair `pair` of the slot's last
+        Farneback call, as h_k x w_k x 2 -- the flow field one of the scale's launches wrote (see rcflow_api.hip)."""
+        fn = self._lib.rcflow_debug_level_flow
+        return self._debug_level(lambda hdl, st, lv, sl, out, gw, gh: fn(hdl, st, lv, which, sl, out, gw, gh), w, h, pyr_scale, level, pair,
+                                 stream, (2,))
+
+    @staticmethod
+    def debug_flow_form(w, h, pairs, winsize, flags=0, solve=1, in_mode=1, fuse=1, chain=1, chain_min_blocks=0, ablate=0):
+        """Diagnostic (rcflow_debug_flow_form; host logic, no context, no GPU): the kernel and tile a flow-iteration launch
+        takes, as a dict (kernel: one of _lib.FLOW_KERNELS' names)."""
+        fn = _lib.load().rcflow_debug_flow_form
+        buf = (C.c_int * 16)()
+        n = check(fn(w, h, pairs, winsize, flags, solve, in_mode, fuse, chain, chain_min_blocks, ablate, buf, 16))
+        names = ("kernel", "tw", "th", "nt", "nit", "d", "groups", "tiles_x", "tiles_y", "grid_y", "interior")
+        assert n == len(names)
+        f = dict(zip(names, buf[:n]))
+        f["kernel"] = _lib.FLOW_KERNELS[f["kernel"]]
+        return f
+
     def _debug_level(self, fn, w, h, pyr_scale, level, slot, stream, tail):
         _, wk, hk = self.level_geometry(w, h, pyr_scale, 64, max(level, 0))
         # the plan's own size of the scale, asked before anything is written (rcflow_debug_level_flow_ptr reports it whether

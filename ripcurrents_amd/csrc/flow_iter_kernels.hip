@@ -19,6 +19,7 @@
 // 20: SURVEY.md section 2.2); any other winsize takes the generic runtime kernel.
 
 #include <cstdlib>
+#include <cstring>
 
 #include "rc_device.h"
 
@@ -489,13 +490,30 @@ __global__ __launch_bounds__(NT) void k_flow_iter_big(RcIterArgs a) {
     }
 }
 
+// Every launcher below takes its tile and its grid from the launch's RcFlowForm (rc_flow_form), which also picked the
+// launcher: the form the tests are told is the form that runs.  The tile rc_flow_form reports for a kernel and the tile
+// the kernel's template is instantiated with come from the same constexpr functions, checked where each is instantiated.
+constexpr int RC_W3_TW = 64, RC_W3_TH = 16;                                   // k_flow_iter_w3
+constexpr int RC_SWEEP_TW = 64, RC_SWEEP_CH = 8, RC_SWEEP_NT = 1024;          // k_flow_iter_sweep
+constexpr int RC_RRC_TW = 28, RC_RRC_NT = 256;                                // k_flow_iter2_rrc: 32 columns x 8 row groups
+constexpr int rc_big_tw(int m) { return m == 10 ? 64 : 32; }                  // k_flow_iter_big (m = 5, 64 wide: 6 % slower, one block per CU)
+constexpr int rc_big_nt(int m) { return m == 2 ? 512 : 1024; }
+constexpr int rc_tile_tw(int m) { return m == 5 || m == 10 ? 32 : 64; }       // k_flow_iter<TW, TH, M, G>
+constexpr int rc_tile_th(int m) { return m == 5 || m == 10 ? 32 : 16; }
+constexpr int rc_rrc_d(int nit) { return nit == 4 ? RC_RR_D : 4; }
+constexpr int rc_rrc_th(int nit) { return 8 * nit - 4; }
+static void rc_form_grid(RcIterArgs& a, const RcFlowForm& f) {
+    a.tw = f.tw; a.th = f.th;
+    a.tiles_x = f.tiles_x; a.tiles_y = f.tiles_y;
+}
+
 template <int M, int G, int NT, int TW = 32>
-static void launch_iter_big(RcIterArgs a, int pairs, hipStream_t s) {
+static void launch_iter_big(RcIterArgs a, const RcFlowForm& f, int pairs, hipStream_t s) {
     constexpr int MW = TW + 2 * M, MH = 32 + 2 * M, MP = MW | 1;
     const size_t lds = sizeof(float) * 5 * (size_t)MP * (MH + 32);
+    static_assert(TW == rc_big_tw(M) && NT == rc_big_nt(M), "rc_flow_form reports this kernel's tile and block");
     RC_ALLOW_LDS((k_flow_iter_big<M, G, NT, TW>), lds);
-    a.tw = TW; a.th = 32;
-    a.tiles_x = (a.w + TW - 1) / TW; a.tiles_y = (a.h + 31) / 32;
+    rc_form_grid(a, f);
     hipLaunchKernelGGL((k_flow_iter_big<M, G, NT, TW>), dim3(a.tiles_x * a.tiles_y, pairs, 1), dim3(NT), lds, s, a);
 }
 
@@ -648,20 +666,12 @@ __global__ __launch_bounds__(NT) void k_flow_iter_sweep(RcIterArgs a) {
 }
 
 template <int M, int NT, int BATCH>
-static void launch_iter_sweep(RcIterArgs a, int pairs, hipStream_t s) {
+static void launch_iter_sweep(RcIterArgs a, const RcFlowForm& f, int pairs, hipStream_t s) {
     using S = RcSweep<M>;
     static_assert(S::RING / S::CH <= 4, "step dispatch covers four ring phases");
+    static_assert(S::TW == RC_SWEEP_TW && S::CH == RC_SWEEP_CH && NT == RC_SWEEP_NT, "rc_flow_form reports this kernel's strip, step and block");
     RC_ALLOW_LDS((k_flow_iter_sweep<M, NT, BATCH>), S::LDS);
-    a.tw = S::TW;
-    a.tiles_x = (a.w + S::TW - 1) / S::TW;
-    // segment height: as tall as still leaves every CU a few blocks
-    const int want = 4 * 512;
-    int segs = (want + a.tiles_x * pairs - 1) / (a.tiles_x * pairs);
-    int rs = (a.h + segs - 1) / segs;
-    rs = ((rs + S::CH - 1) / S::CH) * S::CH;
-    if (rs < 32) rs = 32;
-    a.th = rs;
-    a.tiles_y = (a.h + rs - 1) / rs;
+    rc_form_grid(a, f);       // (th = rows per segment: rc_sweep_segment_rows)
     hipLaunchKernelGGL((k_flow_iter_sweep<M, NT, BATCH>), dim3(a.tiles_x * a.tiles_y, pairs, 1), dim3(NT), S::LDS, s, a);
 }
 
@@ -674,7 +684,7 @@ static void launch_iter_sweep(RcIterArgs a, int pairs, hipStream_t s) {
 #define RC_W3_THREADS 512
 template <int IN_MODE, int GAUSS_>
 __global__ __launch_bounds__(RC_W3_THREADS) void k_flow_iter_w3(RcIterArgs a) {
-    constexpr int TW = 64, TH = 16, MW = TW + 2, MH = TH + 2, MP = MW | 1;
+    constexpr int TW = RC_W3_TW, TH = RC_W3_TH, MW = TW + 2, MH = TH + 2, MP = MW | 1;
     constexpr int NITEMS = MW * MH, NIT = (NITEMS + RC_W3_THREADS - 1) / RC_W3_THREADS;
     extern __shared__ __align__(16) float smf[];
     float* Ms = smf;                    // [5][MH][MP]
@@ -796,9 +806,8 @@ __global__ __launch_bounds__(RC_W3_THREADS) void k_flow_iter_w3(RcIterArgs a) {
 }
 
 template <int IN_MODE, int G>
-static void launch_w3(RcIterArgs a, int pairs, hipStream_t s) {
-    a.tw = 64; a.th = 16;
-    a.tiles_x = (a.w + 63) / 64; a.tiles_y = (a.h + 15) / 16;
+static void launch_w3(RcIterArgs a, const RcFlowForm& f, int pairs, hipStream_t s) {
+    rc_form_grid(a, f);
     size_t lds = sizeof(float) * 5 * 18 * 67;
     hipLaunchKernelGGL((k_flow_iter_w3<IN_MODE, G>), dim3(a.tiles_x * a.tiles_y, pairs, 1), dim3(RC_W3_THREADS), lds, s, a);
 }
@@ -1296,10 +1305,10 @@ __global__ __launch_bounds__(NG * MW, MINB) void k_flow_iter2_rrc(RcIterArgs a, 
 }
 
 template <int IN_MODE, int G, int NIT, int D, int MINB, int MW = 32, int NG = 8>
-static void launch_rrc_t(RcIterArgs a, const RcChainPlan& cp, int pairs, hipStream_t s) {
+static void launch_rrc_t(RcIterArgs a, const RcFlowForm& f, const RcChainPlan& cp, int pairs, hipStream_t s) {
     constexpr int MH = NG * NIT, TW = MW - 4, TH = MH - 4;
-    a.tw = TW; a.th = TH;
-    a.tiles_x = (a.w + TW - 1) / TW; a.tiles_y = (a.h + TH - 1) / TH;
+    static_assert(TW == RC_RRC_TW && TH == rc_rrc_th(NIT) && D == rc_rrc_d(NIT) && NG * MW == RC_RRC_NT, "rc_flow_form reports this kernel's tile, margin and block");
+    rc_form_grid(a, f);
     constexpr int WN = (MW + 2 * D) * (MH + 2 * D), WNP = (WN + 63) & ~63;
     const size_t lds = sizeof(float) * (5 * WNP + NG * 2 * 5 * MW);
     RC_ALLOW_LDS((k_flow_iter2_rrc<IN_MODE, G, NIT, D, MINB, MW, NG>), lds);
@@ -1329,18 +1338,18 @@ static void rc_chain_plan(const RcIterArgs& a, int pairs, long long tiles, RcCha
     cp.ngroups = n;
 }
 
+static void rc_flow_form_plan(const RcIterArgs& a, int pairs, int fuse, RcFlowForm& f, RcChainPlan& cp);
+
 template <int IN_MODE, int G>
 static void launch_w3x2(RcIterArgs a, int pairs, hipStream_t s) {
-    // A launch of fewer blocks than the GPU holds at once (1024 = 256 CUs x 4) lasts one block's lifetime:
-    // shorter tiles then finish sooner (frame-at-a-time calls, coarse scales).  Same bits.
-    const long long tiles = (long long)((a.w + 27) / 28) * ((a.h + 27) / 28), blocks = tiles * pairs;
-    // consecutive pairs of one stream (pair z + 1's previous frame is pair z's next frame): tile chains
+    RcFlowForm f;
     RcChainPlan cp;
-    rc_chain_plan(a, pairs, tiles, cp);
-    if (cp.ngroups) launch_rrc_t<IN_MODE, G, 4, RC_RR_D, 4>(a, cp, pairs, s);       // 28x28 tile, chains of pairs
-    else if (blocks < 512) launch_rrc_t<IN_MODE, G, 2, 4, 6>(a, cp, pairs, s);      // 28x12 tile, 6 blocks per CU
-    else if (blocks < 1024) launch_rrc_t<IN_MODE, G, 3, 4, 5>(a, cp, pairs, s);     // 28x20 tile, 5 blocks per CU
-    else launch_rrc_t<IN_MODE, G, 4, RC_RR_D, 4>(a, cp, pairs, s);                  // 28x28 tile, 4 blocks per CU
+    rc_flow_form_plan(a, pairs, 2, f, cp);
+    switch (f.nit) {
+        case 2: launch_rrc_t<IN_MODE, G, 2, 4, 6>(a, f, cp, pairs, s); break;             // 28x12 tile, 6 blocks per CU
+        case 3: launch_rrc_t<IN_MODE, G, 3, 4, 5>(a, f, cp, pairs, s); break;             // 28x20 tile, 5 blocks per CU
+        default: launch_rrc_t<IN_MODE, G, 4, RC_RR_D, 4>(a, f, cp, pairs, s); break;      // 28x28 tile, 4 blocks per CU, chains of pairs
+    }
 }
 
 // (the fused kernel addresses with 32-bit offsets: frames or caller strides beyond 4 GB take one launch per iteration)
@@ -1363,29 +1372,17 @@ int rc_flow_chain_groups(const RcIterArgs& a, int pairs, int* starts, int cap) {
     return cp.ngroups;
 }
 
-void rc_launch_flow_iter2(const RcIterArgs& a, int pairs, hipStream_t s) {
-    const int g = a.win.gaussian ? 1 : 0;
-    switch (a.in_mode * 2 + g) {
-        case 0: launch_w3x2<0, 0>(a, pairs, s); break;
-        case 1: launch_w3x2<0, 1>(a, pairs, s); break;
-        case 2: launch_w3x2<1, 0>(a, pairs, s); break;
-        case 3: launch_w3x2<1, 1>(a, pairs, s); break;
-        case 4: launch_w3x2<2, 0>(a, pairs, s); break;
-        default: launch_w3x2<2, 1>(a, pairs, s); break;
-    }
-}
-
 static size_t iter_lds(int tw, int th, int m, bool two_buffers) {
     int MW = tw + 2 * m, MH = th + 2 * m, MP = MW | 1;
     return sizeof(float) * (5 * (size_t)MH * MP + (two_buffers ? 5 * (size_t)th * MP : 0));
 }
 
 template <int TW, int TH, int M, int G>
-static void launch_iter_t(RcIterArgs a, int pairs, hipStream_t s) {
+static void launch_iter_t(RcIterArgs a, const RcFlowForm& f, int pairs, hipStream_t s) {
     size_t lds = iter_lds(TW, TH, M, M > 1);
+    static_assert(TW == rc_tile_tw(M) && TH == rc_tile_th(M), "rc_flow_form reports this kernel's tile");
     RC_ALLOW_LDS((k_flow_iter<TW, TH, M, G>), lds);
-    a.tw = TW; a.th = TH;
-    a.tiles_x = (a.w + TW - 1) / TW; a.tiles_y = (a.h + TH - 1) / TH;
+    rc_form_grid(a, f);
     hipLaunchKernelGGL((k_flow_iter<TW, TH, M, G>), dim3(a.tiles_x * a.tiles_y, pairs, 1), dim3(RC_BLOCK), lds, s, a);
 }
 
@@ -1404,41 +1401,113 @@ static void pick_runtime_tile(int m, int& tw, int& th) {
     }
 }
 
-void rc_launch_flow_iter(const RcIterArgs& a, int pairs, hipStream_t s) {
+// Rows per segment of the strip-sweep kernel: as tall as still leaves every CU a few blocks.
+static int rc_sweep_segment_rows(int w, int h, int pairs) {
+    const int want = 4 * 512, strips = (w + RC_SWEEP_TW - 1) / RC_SWEEP_TW;
+    int segs = (want + strips * pairs - 1) / (strips * pairs);
+    int rs = (h + segs - 1) / segs;
+    rs = ((rs + RC_SWEEP_CH - 1) / RC_SWEEP_CH) * RC_SWEEP_CH;
+    return rs < 32 ? 32 : rs;
+}
+
+// The one place that decides which kernel a launch runs and on which tile.
+static void rc_flow_form_plan(const RcIterArgs& a, int pairs, int fuse, RcFlowForm& f, RcChainPlan& cp) {
     const int m = a.win.m, g = a.win.gaussian ? 1 : 0;
-    if (m == 1 && a.solve) {
-        switch (a.in_mode * 2 + g) {
-            case 0: launch_w3<0, 0>(a, pairs, s); break;
-            case 1: launch_w3<0, 1>(a, pairs, s); break;
-            case 2: launch_w3<1, 0>(a, pairs, s); break;
-            case 3: launch_w3<1, 1>(a, pairs, s); break;
-            case 4: launch_w3<2, 0>(a, pairs, s); break;
-            default: launch_w3<2, 1>(a, pairs, s); break;
-        }
-        return;
-    }
-    if (m == 1) { g ? launch_iter_t<64, 16, 1, 1>(a, pairs, s) : launch_iter_t<64, 16, 1, 0>(a, pairs, s); return; }
-    if (a.solve) {
+    memset(&f, 0, sizeof(f));
+    cp.ngroups = 0;
+    if (fuse == 2) {
+        // A launch of fewer blocks than the GPU holds at once (1024 = 256 CUs x 4) lasts one block's lifetime:
+        // shorter tiles then finish sooner (frame-at-a-time calls, coarse scales).  Same bits.
+        const long long tiles = (long long)((a.w + 27) / 28) * ((a.h + 27) / 28), blocks = tiles * pairs;
+        // consecutive pairs of one stream (pair z + 1's previous frame is pair z's next frame): tile chains
+        rc_chain_plan(a, pairs, tiles, cp);
+        f.kernel = RC_FK_RRC; f.nt = RC_RRC_NT; f.groups = cp.ngroups;
+        f.nit = (cp.ngroups || blocks >= 1024) ? 4 : blocks < 512 ? 2 : 3;
+        f.d = rc_rrc_d(f.nit);
+        f.tw = RC_RRC_TW; f.th = rc_rrc_th(f.nit);
+    } else if (m == 1 && a.solve) {
+        f.kernel = RC_FK_W3; f.tw = RC_W3_TW; f.th = RC_W3_TH; f.nt = RC_W3_THREADS;
+    } else if (m == 1) {
+        f.kernel = RC_FK_TILE; f.tw = rc_tile_tw(m); f.th = rc_tile_th(m); f.nt = RC_BLOCK;
+    } else if (a.solve && (m == 2 || m == 5 || m == 10)) {
         // 16 waves per CU: LDS 50 KB (m = 2) -> 3 blocks x 512 threads, 64 KB (m = 5) -> 2 x 1024, 142 KB (m = 10, 64 x 32 tile) -> 1 x 1024
-        if (m == 2) { g ? launch_iter_big<2, 1, 512>(a, pairs, s) : launch_iter_big<2, 0, 512>(a, pairs, s); return; }
         // Gaussian winsize 10 / 20: the strip-sweep kernel once the launch is big enough to fill the GPU
         // with strips (measured crossover, scripts/exp21.py); bit-identical to the tile kernel
         // (RC_ABL_TILE_WINDOW forces the tile kernel, RC_ABL_FORCE_SWEEP the sweep)
         const long long work = (long long)a.w * a.h * pairs;
-        if (g && (m == 5 || m == 10) && !(a.ablate & RC_ABL_TILE_WINDOW) &&
-            ((a.ablate & RC_ABL_FORCE_SWEEP) || work >= (m == 10 ? 900000ll : 8000000ll))) {
-            m == 5 ? launch_iter_sweep<5, 1024, 1>(a, pairs, s) : launch_iter_sweep<10, 1024, 1>(a, pairs, s);
-            return;
+        if (g && m != 2 && !(a.ablate & RC_ABL_TILE_WINDOW) && ((a.ablate & RC_ABL_FORCE_SWEEP) || work >= (m == 10 ? 900000ll : 8000000ll))) {
+            f.kernel = RC_FK_SWEEP; f.tw = RC_SWEEP_TW; f.th = rc_sweep_segment_rows(a.w, a.h, pairs); f.nt = RC_SWEEP_NT;
+        } else {
+            f.kernel = RC_FK_BIG; f.tw = rc_big_tw(m); f.th = 32; f.nt = rc_big_nt(m);
         }
-        if (m == 5) { g ? launch_iter_big<5, 1, 1024>(a, pairs, s) : launch_iter_big<5, 0, 1024>(a, pairs, s); return; }   // (64 wide: 6 % slower, one block per CU)
-        if (m == 10) { g ? launch_iter_big<10, 1, 1024, 64>(a, pairs, s) : launch_iter_big<10, 0, 1024, 64>(a, pairs, s); return; }
+    } else if (m == 2 || m == 5 || m == 10) {
+        f.kernel = RC_FK_TILE; f.tw = rc_tile_tw(m); f.th = rc_tile_th(m); f.nt = RC_BLOCK;
+    } else {
+        f.kernel = RC_FK_RUNTIME; f.nt = RC_BLOCK;
+        pick_runtime_tile(m, f.tw, f.th);
     }
-    if (m == 2) { g ? launch_iter_t<64, 16, 2, 1>(a, pairs, s) : launch_iter_t<64, 16, 2, 0>(a, pairs, s); return; }
-    if (m == 5) { g ? launch_iter_t<32, 32, 5, 1>(a, pairs, s) : launch_iter_t<32, 32, 5, 0>(a, pairs, s); return; }
-    if (m == 10) { g ? launch_iter_t<32, 32, 10, 1>(a, pairs, s) : launch_iter_t<32, 32, 10, 0>(a, pairs, s); return; }
+    f.tiles_x = (a.w + f.tw - 1) / f.tw;
+    f.tiles_y = (a.h + f.th - 1) / f.th;
+    f.grid_y = cp.ngroups ? cp.ngroups : pairs;
+    if (f.kernel == RC_FK_RRC) {
+        // k_flow_iter2_rrc's own test, per tile: the 32 x 8 NIT grid of M starts 2 px before the tile
+        int nx = 0, ny = 0;
+        for (int t = 0; t < f.tiles_x; t++) nx += (t * f.tw - 2 >= 5 && t * f.tw - 2 + 32 <= a.w - 5) ? 1 : 0;
+        for (int t = 0; t < f.tiles_y; t++) ny += (t * f.th - 2 >= 5 && t * f.th - 2 + 8 * f.nit <= a.h - 5) ? 1 : 0;
+        f.interior = nx * ny;
+    }
+}
+
+void rc_flow_form(const RcIterArgs& a, int pairs, int fuse, RcFlowForm& f) {
+    RcChainPlan cp;
+    rc_flow_form_plan(a, pairs, fuse, f, cp);
+}
+
+void rc_launch_flow_iter2(const RcIterArgs& a, int pairs, hipStream_t s) {
+    const int g = a.win.gaussian ? 1 : 0;
+    switch (a.in_mode * 2 + g) {
+        case 0: launch_w3x2<0, 0>(a, pairs, s); break;
+        case 1: launch_w3x2<0, 1>(a, pairs, s); break;
+        case 2: launch_w3x2<1, 0>(a, pairs, s); break;
+        case 3: launch_w3x2<1, 1>(a, pairs, s); break;
+        case 4: launch_w3x2<2, 0>(a, pairs, s); break;
+        default: launch_w3x2<2, 1>(a, pairs, s); break;
+    }
+}
+
+void rc_launch_flow_iter(const RcIterArgs& a, int pairs, hipStream_t s) {
+    const int m = a.win.m, g = a.win.gaussian ? 1 : 0;
+    RcFlowForm f;
+    rc_flow_form(a, pairs, 1, f);
+    switch (f.kernel) {
+        case RC_FK_W3:
+            switch (a.in_mode * 2 + g) {
+                case 0: launch_w3<0, 0>(a, f, pairs, s); break;
+                case 1: launch_w3<0, 1>(a, f, pairs, s); break;
+                case 2: launch_w3<1, 0>(a, f, pairs, s); break;
+                case 3: launch_w3<1, 1>(a, f, pairs, s); break;
+                case 4: launch_w3<2, 0>(a, f, pairs, s); break;
+                default: launch_w3<2, 1>(a, f, pairs, s); break;
+            }
+            return;
+        case RC_FK_SWEEP:
+            m == 5 ? launch_iter_sweep<5, 1024, 1>(a, f, pairs, s) : launch_iter_sweep<10, 1024, 1>(a, f, pairs, s);
+            return;
+        case RC_FK_BIG:
+            if (m == 2) { g ? launch_iter_big<2, 1, 512>(a, f, pairs, s) : launch_iter_big<2, 0, 512>(a, f, pairs, s); }
+            else if (m == 5) { g ? launch_iter_big<5, 1, 1024>(a, f, pairs, s) : launch_iter_big<5, 0, 1024>(a, f, pairs, s); }
+            else { g ? launch_iter_big<10, 1, 1024, 64>(a, f, pairs, s) : launch_iter_big<10, 0, 1024, 64>(a, f, pairs, s); }
+            return;
+        case RC_FK_TILE:
+            if (m == 1) { g ? launch_iter_t<64, 16, 1, 1>(a, f, pairs, s) : launch_iter_t<64, 16, 1, 0>(a, f, pairs, s); }
+            else if (m == 2) { g ? launch_iter_t<64, 16, 2, 1>(a, f, pairs, s) : launch_iter_t<64, 16, 2, 0>(a, f, pairs, s); }
+            else if (m == 5) { g ? launch_iter_t<32, 32, 5, 1>(a, f, pairs, s) : launch_iter_t<32, 32, 5, 0>(a, f, pairs, s); }
+            else { g ? launch_iter_t<32, 32, 10, 1>(a, f, pairs, s) : launch_iter_t<32, 32, 10, 0>(a, f, pairs, s); }
+            return;
+        default: break;
+    }
     RcIterArgs b = a;
-    pick_runtime_tile(m, b.tw, b.th);
-    b.tiles_x = (b.w + b.tw - 1) / b.tw; b.tiles_y = (b.h + b.th - 1) / b.th;
+    rc_form_grid(b, f);
     size_t lds = iter_lds(b.tw, b.th, m, true);
     RC_ALLOW_LDS((k_flow_iter<0, 0, 0, 0>), lds);
     hipLaunchKernelGGL((k_flow_iter<0, 0, 0, 0>), dim3(b.tiles_x * b.tiles_y, pairs, 1), dim3(RC_BLOCK), lds, s, b);

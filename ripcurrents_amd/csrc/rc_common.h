@@ -135,6 +135,29 @@ struct RcChainPlan {
     int start[RC_MAX_CHAIN_GROUPS + 1];
 };
 
+// Which kernel a flow-iteration launch runs, on which tile (rc_flow_form: host logic only).  rc_launch_flow_iter and
+// rc_launch_flow_iter2 switch on this answer, and rcflow_debug_flow_form reports it to the tests, which assert the form
+// they claim to test before they run it.
+enum RcFlowKernel : int {
+    RC_FK_W3 = 1,        // k_flow_iter_w3<in_mode, gauss>: winsize 3, one iteration, 64 x 16 tile
+    RC_FK_TILE = 2,      // k_flow_iter<TW, TH, M, G>: compile-time tile (iterations == 0, or a window without a faster form)
+    RC_FK_BIG = 3,       // k_flow_iter_big<M, G, NT, TW>: m = 2 / 5 / 10, 32 or 64 x 32 tile
+    RC_FK_SWEEP = 4,     // k_flow_iter_sweep<M>: Gaussian m = 5 / 10, strips of 64 columns, th = rows per segment
+    RC_FK_RUNTIME = 5,   // k_flow_iter<0, 0, 0, 0>: any other window, runtime tile
+    RC_FK_RRC = 6,       // k_flow_iter2_rrc<in_mode, gauss, NIT, D>: winsize 3, two iterations, 28 x (8 NIT - 4) tile
+};
+struct RcFlowForm {
+    int kernel;               // RcFlowKernel
+    int tw, th;               // output tile
+    int nt;                   // threads per block
+    int nit, d;               // RC_FK_RRC: rows per thread and the R1 window's margin; 0 otherwise
+    int groups;               // RC_FK_RRC: chain groups (0 = independent pairs)
+    int tiles_x, tiles_y;
+    int grid_y;               // block rows of the launch: pairs, or chain groups
+    int interior;             // RC_FK_RRC: tiles whose M grid lies at least 5 px inside the image (the straight-line path)
+};
+#define RC_FLOW_FORM_INTS 11
+
 // Option "exact" (exact_kernels.hip): one scale of the upstream CPU operation order, staged through HBM.
 struct RcExactArgs {
     const float4* RA;         // R slot base of this scale
@@ -194,6 +217,8 @@ void rc_launch_polyexp_multi(const RcPolyArgs* a, int nlev, int frames, hipStrea
     int rc_flow_iter_can_fuse2(const RcIterArgs& a);                          \
     int rc_flow_iter2_r0_reads(const RcIterArgs& a, int pairs);               \
     int rc_flow_chain_groups(const RcIterArgs& a, int pairs, int* starts, int cap); \
+    /* the form a launch of `fuse` (1 or 2) iterations takes: what the two launchers switch on */ \
+    void rc_flow_form(const RcIterArgs& a, int pairs, int fuse, RcFlowForm& f); \
     void rc_launch_flow_iter2(const RcIterArgs& a, int pairs, hipStream_t s);
 namespace rc_flow_fast { RC_FLOW_DECLS }
 namespace rc_flow_exact { RC_FLOW_DECLS }

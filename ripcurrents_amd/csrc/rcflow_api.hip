@@ -316,6 +316,32 @@ extern "C" int rcflow_debug_chain_plan(int w, int h, int pairs, int chain, int f
     return rc_flow_fast::rc_flow_chain_groups(a, pairs, starts, cap);
 }
 
+// Diagnostic (not part of include/rcflow.h; tests/test_cabi_and_host.py, tests/test_gpu_flow_forms.py): the form a flow-iteration
+// launch of `fuse` (1 or 2) iterations takes for `pairs` consecutive pairs of a w x h scale -- rc_flow_form, the function the
+// launchers themselves switch on.  Pure host logic, no context, no GPU.  out = kernel (RcFlowKernel), tile w, tile h, threads,
+// NIT, D, chain groups, tiles_x, tiles_y, block rows, interior tiles; returns RC_FLOW_FORM_INTS.
+extern "C" int rcflow_debug_flow_form(int w, int h, int pairs, int winsize, int flags, int solve, int in_mode, int fuse, int chain,
+                                      int chain_min_blocks, int ablate, int* out, int cap) {
+    if (w <= 0 || h <= 0 || pairs < 1 || winsize < 1 || winsize / 2 > 24 || (flags & ~RC_FARNEBACK_GAUSSIAN) || in_mode < 0 || in_mode > 2 ||
+        (fuse != 1 && fuse != 2) || chain_min_blocks < 0 || cap < RC_FLOW_FORM_INTS) {
+        rc_set_error("%s: w %d, h %d, pairs %d (>= 1), winsize %d (1..49), flags %d (RC_FARNEBACK_GAUSSIAN alone), in_mode %d (0..2), fuse %d (1, 2), "
+                     "chain_min_blocks %d (>= 0) or cap %d (>= %d)", __func__, w, h, pairs, winsize, flags, in_mode, fuse, chain_min_blocks, cap, RC_FLOW_FORM_INTS);
+        return RC_EINVAL;
+    }
+    if (int rc = rc_ptr_check(__func__, "out", out)) return rc;
+    RcIterArgs a;
+    memset(&a, 0, sizeof(a));
+    a.w = w; a.h = h; a.chain = chain; a.chain_min_blocks = chain_min_blocks; a.addr32 = 1; a.slot0 = 0; a.slot1 = 1; a.zstep = 1; a.nslots = pairs + 1;
+    a.ablate = ablate; a.solve = solve ? 1 : 0; a.in_mode = in_mode;
+    rc_plan_window(winsize, flags, a.win);
+    if (fuse == 2 && !rc_flow_fast::rc_flow_iter_can_fuse2(a)) { rc_set_error("%s: fuse 2 needs winsize 2 or 3 and solve", __func__); return RC_EINVAL; }
+    RcFlowForm f;
+    rc_flow_fast::rc_flow_form(a, pairs, fuse, f);
+    const int v[RC_FLOW_FORM_INTS] = {f.kernel, f.tw, f.th, f.nt, f.nit, f.d, f.groups, f.tiles_x, f.tiles_y, f.grid_y, f.interior};
+    for (int i = 0; i < RC_FLOW_FORM_INTS; i++) out[i] = v[i];
+    return RC_FLOW_FORM_INTS;
+}
+
 // Diagnostic (not part of include/rcflow.h; scripts/r3/level_errors.py): the flow field a scale's last launch wrote
 // for pair 0 of the slot's last call -- valid for scales >= 1 after a call whose iterations fit one or two launches
 // per scale (buffer A then B alternate); which = 0 / 1 picks the buffer.
@@ -363,6 +389,31 @@ extern "C" int rcflow_debug_level_R(rc_ctx* ctx, int stream, int level, int slot
     rc_launch_unpack_R5((const float4*)s->RA[level].p + (size_t)slot * n, (const float*)s->RB[level].p + (size_t)slot * n, d_R5, (int)n,
                         !s->plan.exact, s->cur);
     RC_HIP(hipGetLastError());
+    if (w) *w = L.w;
+    if (h) *h = L.h;
+    return RC_OK;
+}
+
+// The copy form of rcflow_debug_level_flow_ptr for any pair of the slot's last call (tests/test_gpu_flow_forms.py): buffer A
+// (which = 0) or B (which = 1) of scale `level`, pair `pair`, as h x w x 2 floats, dense.  The launches of a scale that do not
+// write the caller's output alternate A, B, A, ...: with option fuse_iters = 0 the last launch of a scale >= 1 and its
+// predecessor survive there, at scale 0 the two launches before the last (whose output is the caller's).
+extern "C" int rcflow_debug_level_flow(rc_ctx* ctx, int stream, int level, int which, int pair, float* d_out, int* w, int* h) {
+    RcSlot* s = rc_slot(ctx, stream);
+    if (!s) return RC_EINVAL;
+    if (!s->plan.valid) { rc_set_error("%s: no plan on the slot (no Farneback call since the last size, parameter or option change)", __func__); return RC_ESTATE; }
+    if (level < 0 || level >= s->plan.nlev || which < 0 || which > 1 || pair < 0 || pair >= s->plan.chunk) {
+        rc_set_error("%s: level %d (0..%d), which %d (0, 1) or pair %d (0..%d) outside the plan", __func__, level, s->plan.nlev - 1, which, pair,
+                     s->plan.chunk - 1);
+        return RC_EINVAL;
+    }
+    const RcLevel& L = s->plan.lv[level];
+    const size_t n = (size_t)L.w * L.h;
+    const RcBuf& B = which ? s->FB[level] : s->FA[level];
+    if (!B.p || ((size_t)pair + 1) * n * 8 > B.bytes) { rc_set_error("%s: the level has no flow field yet", __func__); return RC_ESTATE; }
+    if (int rc = rc_ptr_check(__func__, "d_out", d_out, 4, RC_ARG_OUT)) return rc;
+    RC_HIP(hipSetDevice(ctx->device));
+    RC_HIP(hipMemcpyAsync(d_out, (const char*)B.p + (size_t)pair * n * 8, n * 8, hipMemcpyDeviceToDevice, s->cur));
     if (w) *w = L.w;
     if (h) *h = L.h;
     return RC_OK;
@@ -1601,6 +1652,7 @@ extern "C" int rcflow_stage_flow_iter_dev(rc_ctx* ctx, int stream, const float* 
     a.in_mode = d_flow_in ? 1 : 0; a.fin = (const float2*)d_flow_in; a.fin_pair_stride = n;
     a.fout = (char*)d_flow_out; a.fout_step = (size_t)w * 8; a.fout_pair_stride = n * 8;
     a.solve = 1; a.win = win; a.xcd_remap = ctx->xcd_remap;
+    a.ablate = ctx->ablate;      // (RC_ABL_TILE_WINDOW / RC_ABL_FORCE_SWEEP choose the kernel here as in the level driver)
     rc_flow_fast::rc_launch_flow_iter(a, 1, s->cur);
     RC_HIP(hipGetLastError());
     return RC_OK;

@@ -257,6 +257,93 @@ def test_tile_chain_plan_invariants():
         assert tail == sorted(tail, reverse=True), lens                       # halving tail, never growing again
 
 
+def test_flow_form_host_logic():
+    """rcflow_debug_flow_form: the kernel, tile and grid a flow-iteration launch takes -- rc_flow_form, the function
+    rc_launch_flow_iter and rc_launch_flow_iter2 switch on (tests/test_gpu_flow_forms.py asserts it before every case).
+    Pure host code: runs without a GPU."""
+    from ripcurrents_amd import _lib
+    from ripcurrents_amd.api import Context
+    form = Context.debug_flow_form
+    # the flow diagnostics have a signature table of their own, and the kernel names are RcFlowKernel's, value for value
+    assert set(_lib.DEBUG_FLOW_SIGNATURES) == {"rcflow_debug_level_flow", "rcflow_debug_flow_form"}
+    assert not set(_lib.DEBUG_FLOW_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.DEBUG_SIGNATURES))
+    hdr = open(os.path.join(ROOT, "ripcurrents_amd", "csrc", "rc_common.h")).read()
+    enum = re.search(r"enum RcFlowKernel : int \{(.*?)\};", hdr, re.S).group(1)
+    assert {int(v): k.lower() for k, v in re.findall(r"RC_FK_(\w+) = (\d+)", enum)} == _lib.FLOW_KERNELS
+    out, i32 = (ctypes.c_float * 8)(), ctypes.pointer(ctypes.c_int(7))
+    assert _lib.load().rcflow_debug_level_flow(None, 0, 0, 0, 0, out, i32, i32) == -1 and b"context" in _lib.load().rcflow_last_error()
+    assert not any(out) and i32.contents.value == 7
+
+    def kt(f):
+        return f["kernel"], f["tw"], f["th"]
+
+    # one iteration per launch
+    assert kt(form(333, 251, 1, 3)) == ("w3", 64, 16) and kt(form(333, 251, 1, 2, 256)) == ("w3", 64, 16)
+    assert kt(form(333, 251, 1, 3, solve=0)) == ("tile", 64, 16) and kt(form(333, 251, 1, 10, 256, solve=0)) == ("tile", 32, 32)
+    assert kt(form(333, 251, 1, 5, solve=0)) == ("tile", 64, 16) and kt(form(333, 251, 1, 21, solve=0)) == ("tile", 32, 32)
+    assert kt(form(333, 251, 1, 4)) == ("big", 32, 32) and form(333, 251, 1, 5, 256)["nt"] == 512
+    assert kt(form(333, 251, 1, 10)) == ("big", 32, 32) and kt(form(333, 251, 1, 11, 256)) == ("big", 32, 32)
+    assert kt(form(333, 251, 1, 20, 256)) == ("big", 64, 32) and kt(form(333, 251, 1, 21)) == ("big", 64, 32)
+    # the strip sweep: Gaussian m = 5 / 10 from the measured crossovers on, or forced; never for a box window or m = 2
+    assert form(333, 217, 1, 20, 256, ablate=8388608)["kernel"] == "sweep" and form(333, 217, 1, 10, 256, ablate=8388608)["kernel"] == "sweep"
+    assert form(333, 217, 1, 20, 0, ablate=8388608)["kernel"] == "big" and form(333, 217, 1, 5, 256, ablate=8388608)["kernel"] == "big"
+    assert form(1000, 900, 1, 20, 256)["kernel"] == "sweep" and form(1000, 899, 1, 20, 256)["kernel"] == "big"
+    assert form(1000, 900, 1, 20, 256, ablate=65536)["kernel"] == "big" and form(1000, 900, 1, 20, 256, ablate=65536 | 8388608)["kernel"] == "big"
+    assert form(2000, 1000, 4, 10, 256)["kernel"] == "sweep" and form(2000, 1000, 3, 10, 256)["kernel"] == "big"
+    f = form(333, 217, 1, 20, 256, ablate=8388608)
+    assert f["tw"] == 64 and f["th"] % 8 == 0 and f["th"] >= 32 and f["tiles_x"] == 6 and f["tiles_y"] == -(-217 // f["th"]) and f["nt"] == 1024
+    f = form(1920, 1080, 32, 20, 256)               # 30 strips x 32 pairs: 3 segments of 360 rows
+    assert (f["kernel"], f["th"], f["tiles_y"], f["grid_y"]) == ("sweep", 360, 3, 32)
+    # any other window: the runtime tile, the best halo efficiency that fits LDS
+    def runtime_tile(m):
+        best, pick = -1.0, (8, 8)
+        for tw, th in ((64, 16), (32, 32), (64, 8), (32, 16), (16, 16), (16, 8), (8, 8)):
+            lds = 4 * 5 * ((tw + 2 * m) | 1) * (2 * th + 2 * m)            # M planes of tile + halo, V planes of the tile's rows
+            eff = tw * th / ((tw + 2 * m) * (th + 2 * m)) * (0.6 if lds > 64 << 10 else 1.0) * (0.95 if tw < 64 else 1.0)
+            if lds <= 150 << 10 and eff > best:
+                best, pick = eff, (tw, th)
+        return pick
+
+    seen = set()
+    for ws in (1, 7, 9, 15, 31, 49):
+        for flags in (0, 256):
+            f = form(97, 70, 1, ws, flags)
+            assert f["kernel"] == "runtime" and (f["tw"], f["th"]) == runtime_tile(ws // 2), (ws, f)
+            assert (f["tiles_x"], f["tiles_y"], f["nt"]) == (-(-97 // f["tw"]), -(-70 // f["th"]), 256)
+            seen.add((f["tw"], f["th"]))
+    assert len(seen) >= 2                            # more than one runtime tile among the windows the GPU test runs
+    # two iterations per launch: 28 x 12 below 512 blocks, 28 x 20 below 1024, else 28 x 28; chains always 28 x 28
+    for pairs, blocks, nit, d in ((4, 432, 2, 4), (5, 540, 3, 4), (10, 1080, 4, 3)):
+        f = form(333, 251, pairs, 3, fuse=2)
+        assert 108 * pairs == blocks and (f["kernel"], f["tw"], f["th"], f["nit"], f["d"], f["groups"], f["grid_y"]) == ("rrc", 28, 8 * nit - 4, nit, d, 0, pairs)
+        assert f["tiles_x"] == 12 and f["tiles_y"] == -(-251 // f["th"]) and f["nt"] == 256
+    f = form(333, 251, 10, 3, fuse=2, chain=8)       # too few blocks for chains unless forced
+    assert f["groups"] == 0 and f["nit"] == 4
+    f = form(333, 251, 10, 3, fuse=2, chain=8, ablate=33554432)
+    assert (f["nit"], f["th"], f["groups"], f["grid_y"]) == (4, 28, 3, 3)            # 10 pairs: chains of 8, 1, 1
+    f = form(333, 251, 3, 3, fuse=2, chain=2, ablate=33554432)
+    assert (f["nit"], f["groups"]) == (4, 2)                                          # a chained launch is 28 x 28 whatever its size
+    assert form(1920, 1080, 32, 3, fuse=2, chain=8)["groups"] == 7
+    # interior tiles: the 32 x 8 NIT grid of M, 2 px before the tile, at least 5 px inside the image
+    assert form(62, 30, 1, 3, fuse=2)["interior"] == 0 and form(63, 31, 1, 3, fuse=2)["interior"] == 1
+    assert form(97, 70, 1, 3, fuse=2)["interior"] == 2 * 4 and form(57, 41, 1, 3, fuse=2)["interior"] == 0
+    f = form(333, 251, 10, 3, fuse=2)
+    assert f["interior"] == 10 * 7                   # tiles 1..10 of 12, rows 1..7 of 9
+    assert form(333, 251, 1, 3)["interior"] == 0     # only the fused kernel has the path
+    # refusals: a fused launch of a window that cannot fuse, sizes, a short buffer
+    import ctypes as C
+    from ripcurrents_amd import _lib
+    lib = _lib.load()
+    buf = (C.c_int * 16)()
+    for args in ((333, 251, 1, 5, 0, 1, 1, 2, 1, 0, 0, buf, 16), (333, 251, 1, 3, 0, 0, 1, 2, 1, 0, 0, buf, 16), (0, 251, 1, 3, 0, 1, 1, 1, 1, 0, 0, buf, 16),
+                 (333, 251, 0, 3, 0, 1, 1, 1, 1, 0, 0, buf, 16), (333, 251, 1, 50, 0, 1, 1, 1, 1, 0, 0, buf, 16), (333, 251, 1, 3, 1, 1, 1, 1, 1, 0, 0, buf, 16),
+                 (333, 251, 1, 3, 0, 1, 3, 1, 1, 0, 0, buf, 16), (333, 251, 1, 3, 0, 1, 1, 3, 1, 0, 0, buf, 16), (333, 251, 1, 3, 0, 1, 1, 1, 1, 0, 0, buf, 10),
+                 (333, 251, 1, 3, 0, 1, 1, 1, 1, 0, 0, None, 16)):
+        assert lib.rcflow_debug_flow_form(*args) == -1, args
+        assert lib.rcflow_last_error().decode().startswith("rcflow_debug_flow_form:")
+    assert not any(buf)
+
+
 def test_output_validator_refuses_what_is_not_on_the_device():
     import torch
     from ripcurrents_amd.api import _check_out

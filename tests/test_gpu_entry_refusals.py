@@ -328,6 +328,31 @@ def test_level_diagnostics_refuse_without_a_plan_and_outside_it(ctx, buffers):
     assert bool((dev_out == SENTINEL).all())
 
 
+def test_level_flow_diagnostic_refuses_without_a_plan_and_outside_it(ctx, buffers):
+    """rcflow_debug_level_flow (not part of include/rcflow.h; the copy form of rcflow_debug_level_flow_ptr): RC_ESTATE while the
+    slot has no plan, RC_EINVAL for a level, a buffer or a pair outside the plan and for a null or misaligned output; nothing is
+    written.  Accepted at the edge of the plan: the last scale, buffer B, the plan's last pair."""
+    dev_in, dev_out, host_in, host_out = buffers
+    I, O = dev_in.data_ptr(), dev_out.data_ptr()
+    i32 = C.pointer(C.c_int(0))
+    P = C.byref(FarnebackParams(0.5, 1, 3, 2, 5, 1.1, 0))
+    name = "rcflow_debug_level_flow"
+    args = [("level", 0), ("which", 0), ("pair", 0), ("d_out", O), ("w", i32), ("h", i32)]
+    ctx.set_option("chunk", 32)                  # its default: every slot's plan is dropped
+    rows = refused_calls(ctx, [Entry(name, args, [({}, None, ESTATE), ({"level": 99}, None, ESTATE), ({"d_out": None}, None, ESTATE)], 2)])
+    w, h = 80, 72                                # two scales (see the test above), chunk 32
+    assert ctx._lib.rcflow_farneback_dev(ctx._h, 0, I, w, I + w * h, w, w, h, I + (64 << 10), w * 8, P) == 0
+    rows += refused_calls(ctx, [Entry(name, args, [({"level": -1}, None, EINVAL), ({"level": 2}, None, EINVAL), ({"which": -1}, None, EINVAL),
+                                                   ({"which": 2}, None, EINVAL), ({"pair": -1}, None, EINVAL), ({"pair": 32}, None, EINVAL),
+                                                   ({"d_out": None}, "d_out", EINVAL), ({"d_out": O + 2}, "d_out", EINVAL)], 2)])
+    wrong = _wrong(rows)
+    assert len(rows) == 11 and not wrong, "\n".join(wrong)
+    assert ctx._lib.rcflow_debug_level_flow(ctx._h, 0, 1, 1, 31, I + (128 << 10), i32, i32) == 0 and i32.contents.value == 36
+    ctx.sync()
+    torch.cuda.synchronize()
+    assert bool((dev_out == SENTINEL).all())
+
+
 def test_stage_polyexp_takes_a_negative_sigma_as_the_default(ctx):
     """Accepted, as it always was: the plan arithmetic reads any poly_sigma below FLT_EPSILON as 0.3 n (rc_plan.cpp), so -1 gives the
     planes of 0, bit for bit; the level drivers refuse a negative sigma, this stage entry point never did."""
