@@ -16,8 +16,8 @@
 #include <cstring>
 #include <vector>
 
-#include "rc_device.h"
 #include "rc_host.h"
+#include "rc_reduce.h"
 
 #define RC_MAX_ADVECT_ITERATIONS 65536   // a kernel that never returns is a hung GPU, not a slow call
 #define THR_UPPER 0
@@ -92,12 +92,6 @@ __device__ __forceinline__ int rc_hist_key_fast(float2 f, bool& exact_needed) {
     // (int)u < 36 wherever dir_ok holds: u = 36 needs a >= 359.99999, whose fractional part fails the guard
     const int d = (int)u;
     return counted ? (int)__umul24((unsigned)d, (unsigned)RC_HIST_BINS) + bin : -1;
-}
-
-__device__ __forceinline__ int rc_wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // PLAIN (decided by the launcher, rc_hist_rows_plain): every item whole and every row 16-byte aligned.
@@ -214,7 +208,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_polar_hist_rows(const float* flow0
             const int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
             const int kL = __builtin_amdgcn_readlane(A, leader);
             const bool same = A == kL;
-            const int sum = rc_wave_sum(same ? cnt : 0);
+            const int sum = rc_wave_sum_all(same ? cnt : 0);
             if (lane == leader) atomicAdd(&lh[kL], sum);
             else if (A >= 0 && !same) atomicAdd(&lh[A], cnt);
         }
@@ -463,15 +457,6 @@ __global__ __launch_bounds__(RC_BLOCK) void k_get_delta_field(float* pt, size_t 
 // ============================================================================ B7 post-ops
 // Two-stage deterministic reductions: per-block partials in double, then one block folds
 // them in a fixed order.  part[b] = (sum x, sum y, sum |f|, max |f|)
-__device__ __forceinline__ double rc_wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float rc_wave_max(float v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_down(v, o, 64));
-    return v;
-}
-
 __global__ __launch_bounds__(RC_BLOCK) void k_flow_stats_partial(const float* flow, size_t step, int x0, int y0,
                                                                  int w, int h, double* part) {
     double sx = 0, sy = 0, sm = 0;
@@ -486,7 +471,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_flow_stats_partial(const float* fl
         mx = fmaxf(mx, mag);
     }
     __shared__ double sh[4][4];
-    sx = rc_wave_sum(sx); sy = rc_wave_sum(sy); sm = rc_wave_sum(sm); mx = rc_wave_max(mx);
+    sx = rc_wave_sum_lane0(sx); sy = rc_wave_sum_lane0(sy); sm = rc_wave_sum_lane0(sm); mx = rc_wave_max_lane0(mx);
     int wv = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) { sh[wv][0] = sx; sh[wv][1] = sy; sh[wv][2] = sm; sh[wv][3] = mx; }
     __syncthreads();
@@ -592,7 +577,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_shear_to_color(const float* flow, 
         mx = fmaxf(mx, fro);
     }
     __shared__ float sh[4];
-    mx = rc_wave_max(mx);
+    mx = rc_wave_max_lane0(mx);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = mx;
     __syncthreads();
     if (threadIdx.x == 0) part_max[blockIdx.x] = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));

@@ -8,7 +8,7 @@
 // (the 8 x 8 elimination of a homography works on a matrix in LDS, so nothing is indexed in registers and the kernel has
 // no scratch), the 64 lanes stride the points and the wave reduces the count.  The workgroup's best goes into one packed
 // 64-bit maximum (count << 32 | ~index: most inliers, lowest index) and the workgroup that arrives LAST refits on the
-// winner's inliers, recounts, refits again and walks the ladder.  The hand-off is k_stab_correlate_multi's: agent-scope
+// winner's inliers, recounts, refits again and walks the ladder.  The hand-off is rc_ticket_release (rc_reduce.h): agent-scope
 // atomics, one release fence, the ticket, one acquire fence (DESIGN.md section 7c says why a plain flag is not enough).
 //
 // Sums of the refits run over the valid list in a fixed order, so they are a function of the input alone: thread t adds
@@ -19,6 +19,7 @@
 #include <string.h>
 
 #include "rc_host.h"
+#include "rc_reduce.h"
 
 #define FT_BLOCK 256
 #define FT_WAVES (FT_BLOCK / 64)
@@ -300,8 +301,7 @@ __global__ __launch_bounds__(FT_BLOCK) void k_robust_fit(const RcFitArgs a) {
     int smax = 0;
     if (a.scores) {
         for (int i = i0; i < i1; i++) smax = max(smax, a.scores[i]);
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) smax = max(smax, __shfl_xor(smax, o, 64));
+        smax = rc_wave_max_all(smax);
         if (lane == 0) scan[wave] = smax;
         __syncthreads();
         smax = max(max(scan[0], scan[1]), max(scan[2], scan[3]));
@@ -349,8 +349,7 @@ __global__ __launch_bounds__(FT_BLOCK) void k_robust_fit(const RcFitArgs a) {
 #pragma unroll
         for (int i = 0; i < 9; i++) T[i] = wv[89 + i];
         for (int i = lane; i < nv; i += 64) count += ft_inlier(T, pts[i], a.thr2) ? 1 : 0;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) count += __shfl_xor(count, o, 64);
+        count = rc_wave_sum_all(count);
     }
     if (lane == 0) keys[wave] = j < a.hyp ? ((unsigned long long)(unsigned)count << 32) | (0xffffffffu - (unsigned)j) : 0ull;
     __syncthreads();
@@ -358,15 +357,10 @@ __global__ __launch_bounds__(FT_BLOCK) void k_robust_fit(const RcFitArgs a) {
         unsigned long long key = keys[0];
         for (int k = 1; k < FT_WAVES; k++) key = keys[k] > key ? keys[k] : key;
         (void)__hip_atomic_fetch_max(a.ws, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         unsigned* ticket = (unsigned*)(a.ws + 1);
-        const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         int last = 0;
-        if (t == gridDim.x - 1) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            const unsigned long long best = __hip_atomic_load(a.ws, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (rc_ticket_release(ticket, gridDim.x)) {
+            const unsigned long long best = rc_acc_load(a.ws);
             __hip_atomic_store(a.ws, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             last = 1;

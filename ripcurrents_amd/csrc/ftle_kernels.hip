@@ -18,13 +18,13 @@
 //   ftle@2  tensor   central differences of the map at +-spacing, lam, ftle, mask, picture; the integer sums per wave by
 //                    ballot and popcount over the rows it walks, met in LDS, one atomic per block and counter (the
 //                    launch keeps to about FT_MAX_BLOCKS blocks: they all end on the same two lines); the last-arriving block
-//                    writes the summary and leaves the counters zero (the ticket of ripmap_kernels.hip).
+//                    writes the summary and leaves the counters zero (rc_hand_off_fenced of rc_reduce.h).
 
 #include <math.h>
 #include <string.h>
 
-#include "rc_device.h"
 #include "rc_host.h"
+#include "rc_reduce.h"
 
 #define FT_WAVES 4
 static_assert(RC_BLOCK == 64 * FT_WAVES, "a block is FT_WAVES waves");
@@ -35,7 +35,7 @@ static_assert(RC_BLOCK == 64 * FT_WAVES, "a block is FT_WAVES waves");
 
 // RcFtle::ctl.  The ticket has a 128-byte line of its own: every block adds to it.
 struct FtCtl {
-    unsigned ticket; unsigned pad0[31];
+    RcTicketLine t;
     unsigned valid, mask, stopped, maxbits; unsigned pad1[28];
 };
 static_assert(sizeof(FtCtl) == 256, "two lines");
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_ft_tensor(const FtTenArgs a) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int x = blockIdx.x * 64 + lane;
     if (a.vis)
-        for (int i = threadIdx.x; i < 768; i += RC_BLOCK) lut[i] = a.jet[i];
+        rc_stage_jet(lut, a.jet);
     if (threadIdx.x < 4) sums[threadIdx.x] = 0;
     __syncthreads();
     const int s = a.s;
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_ft_tensor(const FtTenArgs a) {
         if (valid && lam == lam) mb = max(mb, __float_as_uint(lam));              // lam >= 0: its bits order as integers
     }
     // the integer sums: per wave, then the block's in LDS, then one atomic per counter
-    for (int o = 32; o > 0; o >>= 1) mb = max(mb, (unsigned)__shfl_xor((int)mb, o, 64));
+    mb = rc_wave_max_all(mb);
     if (lane == 0) {
         if (nv) atomicAdd(&sums[0], nv);
         if (nm) atomicAdd(&sums[1], nm);
@@ -189,33 +189,25 @@ __global__ __launch_bounds__(RC_BLOCK) void k_ft_tensor(const FtTenArgs a) {
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        if (sums[0]) __hip_atomic_fetch_add(&a.ctl->valid, sums[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (sums[1]) __hip_atomic_fetch_add(&a.ctl->mask, sums[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (sums[2]) __hip_atomic_fetch_add(&a.ctl->stopped, sums[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (sums[0]) rc_acc_add(&a.ctl->valid, sums[0]);
+        if (sums[1]) rc_acc_add(&a.ctl->mask, sums[1]);
+        if (sums[2]) rc_acc_add(&a.ctl->stopped, sums[2]);
         if (sums[3]) __hip_atomic_fetch_max(&a.ctl->maxbits, sums[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     // the ticket: every thread's stores and the block's atomics, __threadfence, the barrier, one ticket
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned t = __hip_atomic_fetch_add(&a.ctl->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = t == a.nblocks - 1u;
-        __threadfence();
-    }
-    __syncthreads();
-    if (!last || threadIdx.x != 0) return;
+    if (!rc_hand_off_fenced(&a.ctl->t.ticket, a.nblocks, &last) || threadIdx.x != 0) return;
     long long r[8];
     r[0] = a.n;
-    r[1] = (long long)__hip_atomic_exchange(&a.ctl->valid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    r[2] = (long long)__hip_atomic_exchange(&a.ctl->mask, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    r[3] = (long long)__hip_atomic_exchange(&a.ctl->stopped, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    r[4] = (long long)__hip_atomic_exchange(&a.ctl->maxbits, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    r[1] = (long long)rc_acc_take(&a.ctl->valid);
+    r[2] = (long long)rc_acc_take(&a.ctl->mask);
+    r[3] = (long long)rc_acc_take(&a.ctl->stopped);
+    r[4] = (long long)rc_acc_take(&a.ctl->maxbits);
     r[5] = a.pushes; r[6] = 0; r[7] = 0;
     for (int k = 0; k < 8; k++) {
         a.rec[k] = r[k];
         if (a.rec2) a.rec2[k] = r[k];
     }
-    __hip_atomic_store(&a.ctl->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // for the next push (stream order)
+    __hip_atomic_store(&a.ctl->t.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // for the next push (stream order)
 }
 
 // ============================================================================ host side
@@ -267,12 +259,7 @@ extern "C" int rcflow_ftle_open(rc_ctx* ctx, int stream, int w, int h, const rc_
     if (!rc) rc = rc_buf_ensure(n.lam, px * 4);
     if (!rc) rc = rc_buf_ensure(n.ctl, sizeof(FtCtl));
     if (!rc) rc = rc_buf_ensure(n.out, 64);
-    if (!rc) rc = rc_buf_ensure(n.jet, 768);
-    if (!rc) {
-        uint8_t lut[768];
-        rcflow_jet_lut(lut);
-        if (hipMemcpy(n.jet.p, lut, 768, hipMemcpyHostToDevice) != hipSuccess) { rc_set_error("%s: the colour table's upload failed", who); rc = RC_EHIP; }
-    }
+    if (!rc) rc = rc_jet_ensure(n.jet, who);
     return rc_state_install(*s, s->ft, n, rc);
 }
 

@@ -16,8 +16,8 @@
 //                 the arrays are packed.  The cell sums: a lane's column, hence its cell column, does not
 //                 change from row to row, so it adds in registers while the cell row stays; then the wave reduces per cell
 //                 column, the block's waves meet in LDS and the block issues one 64-bit atomic per sum and cell it touched
-//                 (the pattern of ripmap_kernels.hip).  The last-arriving block takes the threshold from the sums (the
-//                 ticket of ftle_kernels.hip, handed over as ripmap_kernels.hip does: one release a block).  omega and ow go to
+//                 (the pattern of ripmap_kernels.hip).  The last-arriving block takes the threshold from the sums
+//                 (rc_hand_off_release of rc_reduce.h: one release a block).  omega and ow go to
 //                 two state planes, omega as one NaN pattern where the pixel is not valid.
 //   kinematics@1  streams the two planes, a wave 64 columns of as many rows as keep the launch to about KN_MAX_BLOCKS blocks: cores,
 //                 mask, picture, four more sums per cell the same way; the last-arriving block
@@ -26,8 +26,8 @@
 #include <math.h>
 #include <string.h>
 
-#include "rc_device.h"
 #include "rc_host.h"
+#include "rc_reduce.h"
 
 #define KN_WAVES 4
 static_assert(RC_BLOCK == 64 * KN_WAVES, "a block is KN_WAVES waves");
@@ -45,19 +45,11 @@ static_assert(sizeof(rc_kinematics_cell) == 48, "rc_kinematics_cell is 48 bytes"
 
 // RcKinematics::ctl.  Each ticket has a 128-byte line of its own: every block adds to it.
 struct KnCtl {
-    unsigned ticket0; unsigned pad0[31];
-    unsigned ticket1; unsigned pad1[31];
+    RcTicketLine t0, t1;
     unsigned maxbits; unsigned pad2; double t2; unsigned pad3[28];
 };
 static_assert(sizeof(KnCtl) == 384, "three lines");
 
-__device__ __forceinline__ long long kn_wave_sum(long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ void kn_add(long long* p, long long v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ long long kn_load(long long* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ long long kn_take(long long* p) { return __hip_atomic_exchange(p, 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // Q(x) = (int64)rint((double)x * 65536).  A scaling by 2^16 is exact in float as well, so the float's rounding to an integer is
 // the double's; |x| < 2^15 (omega, div, e, ow) fits 32 bits, w2 < 2^18 does not
 __device__ __forceinline__ long long kn_q(float x) { return (long long)(int)rintf(x * 65536.0f); }
@@ -90,14 +82,14 @@ __device__ __forceinline__ void kn_flush(long long* acc, int off, long long* tab
     for (int cx = f.cxa; cx <= f.cxb; cx++) {
         long long t[N];
 #pragma unroll
-        for (int k = 0; k < N; k++) t[k] = kn_wave_sum(cxl == cx ? v[k] : 0ll);
+        for (int k = 0; k < N; k++) t[k] = rc_wave_sum_all(cxl == cx ? v[k] : 0ll);
         if ((threadIdx.x & 63) == 0) {
 #pragma unroll
             for (int k = 0; k < N; k++) {
                 if (!t[k]) continue;
                 if (f.lds) __hip_atomic_fetch_add((kn_lds_u64*)(tab + N * ((cy - f.cya) * f.nx + (cx - f.cxa)) + k), (unsigned long long)t[k],
                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                else kn_add(acc + RC_KINEMATICS_SUMS * ((size_t)cy * gx + cx) + off + k, t[k]);
+                else rc_acc_add(acc + RC_KINEMATICS_SUMS * ((size_t)cy * gx + cx) + off + k, t[k]);
             }
         }
     }
@@ -113,26 +105,9 @@ __device__ __forceinline__ void kn_table_out(long long* acc, int off, const long
         const long long val = tab[i];
         const int c = i / N, k = i - N * c;
         const int cy = f.cya + c / f.nx, cx = f.cxa + c % f.nx;
-        if (val) kn_add(acc + RC_KINEMATICS_SUMS * ((size_t)cy * gx + cx) + off + k, val);
+        if (val) rc_acc_add(acc + RC_KINEMATICS_SUMS * ((size_t)cy * gx + cx) + off + k, val);
     }
 }
-
-// The hand-off of ripmap_kernels.hip: every wave's stores and atomics have been performed, then ONE release, the ticket, and for
-// the last arriver ONE acquire.  `last` is the block's shared flag: true in the last-arriving block
-#define KN_HAND_OFF(ticket, nblocks, last)                                                                        \
-    do {                                                                                                          \
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                          \
-        __syncthreads();                                                                                          \
-        if (threadIdx.x == 0) {                                                                                   \
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");                                                    \
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                      \
-            const unsigned t_ = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   \
-            const int l_ = t_ == (nblocks) - 1u;                                                                  \
-            if (l_) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");                                            \
-            last = l_;                                                                                            \
-        }                                                                                                         \
-        __syncthreads();                                                                                          \
-    } while (0)
 
 // ============================================================================ kinematics@0
 struct KnArgs0 {
@@ -256,20 +231,19 @@ __global__ __launch_bounds__(RC_BLOCK) void k_kn_field(const KnArgs0 a) {
     kn_table_out<KN_S0>(a.acc, 0, tab, f, a.gx);
     __syncthreads();                                          // the next tile overwrites the table and the arrays
   }
-    for (int o = 32; o > 0; o >>= 1) mb = max(mb, (unsigned)__shfl_xor((int)mb, o, 64));
+    mb = rc_wave_max_all(mb);
     if (lane == 0 && mb) atomicMax(&bmax, mb);
     __syncthreads();
     if (threadIdx.x == 0 && bmax) __hip_atomic_fetch_max(&a.ctl->maxbits, bmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    KN_HAND_OFF(&a.ctl->ticket0, a.nblocks, last);
-    if (!last) return;
+    if (!rc_hand_off_release(&a.ctl->t0.ticket, a.nblocks, &last)) return;
 
     // the threshold, by the last-arriving block: the sums stay for kinematics@1
     long long n = 0, sw = 0, sw2 = 0;
     for (int c = threadIdx.x; c < a.gx * a.gy; c += RC_BLOCK) {
         long long* q = a.acc + (size_t)RC_KINEMATICS_SUMS * c;
-        n += kn_load(q); sw += kn_load(q + 5); sw2 += kn_load(q + 6);
+        n += rc_acc_load(q); sw += rc_acc_load(q + 5); sw2 += rc_acc_load(q + 6);
     }
-    n = kn_wave_sum(n); sw = kn_wave_sum(sw); sw2 = kn_wave_sum(sw2);
+    n = rc_wave_sum_all(n); sw = rc_wave_sum_all(sw); sw2 = rc_wave_sum_all(sw2);
     if (lane == 0) { red[3 * wv] = n; red[3 * wv + 1] = sw; red[3 * wv + 2] = sw2; }
     __syncthreads();
     if (threadIdx.x != 0) return;
@@ -287,7 +261,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_kn_field(const KnArgs0 a) {
         t2 = a.k2 * var;
     }
     a.ctl->t2 = t2;                                           // read by the next launch (stream order)
-    __hip_atomic_store(&a.ctl->ticket0, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&a.ctl->t0.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ============================================================================ kinematics@1
@@ -319,7 +293,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_kn_cores(const KnArgs1 a) {
     if (f.lds)
         for (int i = threadIdx.x; i < KN_S1 * f.ntab; i += RC_BLOCK) tab[i] = 0;
     if (a.vis)
-        for (int i = threadIdx.x; i < 768; i += RC_BLOCK) lut[i] = a.jet[i];
+        rc_stage_jet(lut, a.jet);
     __syncthreads();
     const double t2 = a.ctl->t2;
     const int x = x0 + lane;
@@ -357,15 +331,14 @@ __global__ __launch_bounds__(RC_BLOCK) void k_kn_cores(const KnArgs1 a) {
     if (cur_cy >= 0) kn_flush<KN_S1>(a.acc, KN_S0, tab, f, a.gx, cur_cy, cxl, v);
     __syncthreads();
     kn_table_out<KN_S1>(a.acc, KN_S0, tab, f, a.gx);
-    KN_HAND_OFF(&a.ctl->ticket1, a.nblocks, last);
-    if (!last) return;
+    if (!rc_hand_off_release(&a.ctl->t1.ticket, a.nblocks, &last)) return;
 
     // records and summary, by the last-arriving block; every counter is left zero for the next push
     long long tv = 0, tb = 0, tcw = 0, tccw = 0, both = 0;
     for (int c = threadIdx.x; c < a.gx * a.gy; c += RC_BLOCK) {
         long long w[RC_KINEMATICS_SUMS];
         for (int k = 0; k < RC_KINEMATICS_SUMS; k++) {
-            w[k] = kn_take(a.acc + (size_t)RC_KINEMATICS_SUMS * c + k);
+            w[k] = rc_acc_take(a.acc + (size_t)RC_KINEMATICS_SUMS * c + k);
             a.sums[(size_t)RC_KINEMATICS_SUMS * c + k] = w[k];
             if (a.sums2) a.sums2[(size_t)RC_KINEMATICS_SUMS * c + k] = w[k];
         }
@@ -393,7 +366,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_kn_cores(const KnArgs1 a) {
         tv += w[0]; tb += w[1]; tcw += w[7]; tccw += w[8];
         both += (r.flags & (RC_KINEMATICS_CW | RC_KINEMATICS_CCW)) == (RC_KINEMATICS_CW | RC_KINEMATICS_CCW);
     }
-    tv = kn_wave_sum(tv); tb = kn_wave_sum(tb); tcw = kn_wave_sum(tcw); tccw = kn_wave_sum(tccw); both = kn_wave_sum(both);
+    tv = rc_wave_sum_all(tv); tb = rc_wave_sum_all(tb); tcw = rc_wave_sum_all(tcw); tccw = rc_wave_sum_all(tccw); both = rc_wave_sum_all(both);
     if (lane == 0) { red[5 * wv] = tv; red[5 * wv + 1] = tb; red[5 * wv + 2] = tcw; red[5 * wv + 3] = tccw; red[5 * wv + 4] = both; }
     __syncthreads();
     if (threadIdx.x != 0) return;
@@ -408,7 +381,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_kn_cores(const KnArgs1 a) {
         a.summary[k] = r[k];
         if (a.summary2) a.summary2[k] = r[k];
     }
-    __hip_atomic_store(&a.ctl->ticket1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // for the next push (stream order)
+    __hip_atomic_store(&a.ctl->t1.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // for the next push (stream order)
 }
 
 // ============================================================================ host side
@@ -490,12 +463,7 @@ extern "C" int rcflow_kinematics_open(rc_ctx* ctx, int stream, int w, int h, con
     if (!rc) rc = rc_buf_ensure(n.acc, nc * RC_KINEMATICS_SUMS * 8);
     if (!rc) rc = rc_buf_ensure(n.out, 64 + nc * (RC_KINEMATICS_SUMS * 8 + sizeof(rc_kinematics_cell)));
     if (!rc) rc = rc_buf_ensure(n.ctl, sizeof(KnCtl));
-    if (!rc) rc = rc_buf_ensure(n.jet, 768);
-    if (!rc) {
-        uint8_t lut[768];
-        rcflow_jet_lut(lut);
-        if (hipMemcpy(n.jet.p, lut, 768, hipMemcpyHostToDevice) != hipSuccess) { rc_set_error("%s: the colour table's upload failed", who); rc = RC_EHIP; }
-    }
+    if (!rc) rc = rc_jet_ensure(n.jet, who);
     return rc_state_install(*s, s->kn, n, rc);
 }
 

@@ -16,7 +16,7 @@
 //   motion@2  sums      S, W and n_used per cell and for the frame as 64-bit integers (no order of addition), summed in
 //                       registers while a wave stays in a cell row, per wave over the lanes of a cell, then one atomic
 //                       each; the last-arriving workgroup writes the records and leaves the tables zero.
-// The hand-off to a launch's last workgroup is the opposing-flow map's ticket: every thread's atomics, __threadfence, the
+// The hand-off to a launch's last workgroup is rc_hand_off_fenced (rc_reduce.h): every thread's atomics, __threadfence, the
 // block's barrier, one ticket; the finish reads the tables with atomic exchanges, where the adds were made.
 
 #include <math.h>
@@ -24,6 +24,7 @@
 
 #include "rc_host.h"
 #include "rc_pix3.h"
+#include "rc_reduce.h"
 
 #define MT_WAVES 4
 static_assert(RC_BLOCK == 64 * MT_WAVES, "a block is MT_WAVES waves");
@@ -36,8 +37,7 @@ static_assert(RC_BLOCK == 64 * MT_WAVES, "a block is MT_WAVES waves");
 
 // control words at the start of RcMotion::tab.  Each ticket has a 128-byte line of its own: every block adds to it.
 struct MtCtl {
-    unsigned ticket1; unsigned pad0[31];
-    unsigned ticket2; unsigned pad1[31];
+    RcTicketLine t1, t2;
     unsigned long long sil;         // pixels of this push's silhouette
     unsigned pad2[30];
 };
@@ -48,27 +48,6 @@ struct MtInfo { float base, b, del, tsmax; int n_masked, peak, pad0, pad1; };
 static_assert(sizeof(MtInfo) == 32 && sizeof(rc_motion_cell) == 40, "table strides");
 
 typedef float mt_f4u __attribute__((ext_vector_type(4), aligned(4)));   // a 16-byte access to a 4-byte aligned row
-
-__device__ __forceinline__ long long mt_wave_sum(long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ void mt_add(long long* p, long long v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ long long mt_take(long long* p) { return __hip_atomic_exchange(p, 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ unsigned mt_take(unsigned* p) { return __hip_atomic_exchange(p, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the block's ticket: true in every thread of the launch's last-arriving block, whose threads then see every other block's atomics
-__device__ __forceinline__ bool mt_last_block(unsigned* ticket, unsigned nblocks, int* last) {
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *last = t == nblocks - 1u;
-        __threadfence();
-    }
-    __syncthreads();
-    return *last != 0;
-}
 
 // ============================================================================ motion@0: update
 struct MtUpdArgs {
@@ -114,9 +93,9 @@ __global__ __launch_bounds__(RC_BLOCK) void k_mt_update(const MtUpdArgs a) {
                 for (int k = 0; k < n; k++) r[k] = m[k];
         }
     }
-    cnt = (int)mt_wave_sum(cnt);
+    cnt = (int)rc_wave_sum_lane0((long long)cnt);
     if ((threadIdx.x & 63) == 0 && cnt)
-        __hip_atomic_fetch_add(&a.ctl->sil, (unsigned long long)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        rc_acc_add(&a.ctl->sil, (unsigned long long)cnt);
 }
 
 // ============================================================================ motion@1: gradient
@@ -157,8 +136,8 @@ __device__ void mt_grad_finish(const MtGradArgs& a, unsigned* fr /* [MT_USED] */
     __syncthreads();
     for (int c = threadIdx.x; c < ncell; c += RC_BLOCK) {
         unsigned cnt[13];
-        for (int k = 0; k < 13; k++) cnt[k] = mt_take(a.hist + (size_t)c * MT_WORDS + k);
-        const unsigned mb = mt_take(a.hist + (size_t)c * MT_WORDS + 13);
+        for (int k = 0; k < 13; k++) cnt[k] = rc_acc_take(a.hist + (size_t)c * MT_WORDS + k);
+        const unsigned mb = rc_acc_take(a.hist + (size_t)c * MT_WORDS + 13);
         a.info[c] = mt_info(cnt, mb, a);
         for (int k = 0; k < 13; k++)
             if (cnt[k]) atomicAdd(&fr[k], cnt[k]);
@@ -169,7 +148,7 @@ __device__ void mt_grad_finish(const MtGradArgs& a, unsigned* fr /* [MT_USED] */
     unsigned cnt[13];
     for (int k = 0; k < 13; k++) cnt[k] = fr[k];
     a.info[ncell] = mt_info(cnt, fr[13], a);
-    __hip_atomic_store(&a.ctl->ticket1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // for the next push (stream order)
+    __hip_atomic_store(&a.ctl->t1.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // for the next push (stream order)
 }
 
 __global__ __launch_bounds__(RC_BLOCK) void k_mt_gradient(const MtGradArgs a) {
@@ -240,7 +219,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_mt_gradient(const MtGradArgs a) {
             const bool mine = key == kk;
             const unsigned long long grp = __ballot(mine);
             unsigned gmax = mine ? bits : 0u;
-            for (int o = 32; o > 0; o >>= 1) gmax = max(gmax, (unsigned)__shfl_xor((int)gmax, o, 64));
+            gmax = rc_wave_max_all(gmax);
             if (lane == leader) {
                 const int sl = kk >> 4, bn = kk & 15;
                 const unsigned n = (unsigned)__popcll(grp);
@@ -249,7 +228,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_mt_gradient(const MtGradArgs a) {
                     atomicMax(&tab[sl * MT_USED + 13], gmax);
                 } else {
                     unsigned* t = a.hist + (size_t)sl * MT_WORDS;
-                    __hip_atomic_fetch_add(t + bn, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    rc_acc_add(t + bn, n);
                     __hip_atomic_fetch_max(t + 13, gmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
             }
@@ -263,10 +242,10 @@ __global__ __launch_bounds__(RC_BLOCK) void k_mt_gradient(const MtGradArgs a) {
             if (!val) continue;
             const int c = i / MT_USED, k = i - c * MT_USED;
             unsigned* t = a.hist + ((size_t)(cya + c / nx) * a.gx + (cxa + c % nx)) * MT_WORDS + k;
-            if (k < 13) __hip_atomic_fetch_add(t, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (k < 13) rc_acc_add(t, val);
             else __hip_atomic_fetch_max(t, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-    if (mt_last_block(&a.ctl->ticket1, a.nblocks, &last)) mt_grad_finish(a, fr);
+    if (rc_hand_off_fenced(&a.ctl->t1.ticket, a.nblocks, &last)) mt_grad_finish(a, fr);
 }
 
 // ============================================================================ motion@2: sums
@@ -307,10 +286,10 @@ __device__ __forceinline__ void mt_flush(const MtSumArgs& a, int cxa, int cxb, i
 #pragma unroll
             for (int k = 0; k < 4; k++)
                 if (cxl[k] == cx) { vs += s[k]; vw += wq[k]; vn += n[k]; }
-            vs = mt_wave_sum(vs); vw = mt_wave_sum(vw); vn = mt_wave_sum(vn);
+            vs = rc_wave_sum_lane0(vs); vw = rc_wave_sum_lane0(vw); vn = rc_wave_sum_lane0(vn);
             if ((threadIdx.x & 63) == 0 && vn) {
                 long long* t = a.acc + 3 * ((size_t)cy * a.gx + cx);
-                mt_add(t, vs); mt_add(t + 1, vw); mt_add(t + 2, vn);
+                rc_acc_add(t, vs); rc_acc_add(t + 1, vw); rc_acc_add(t + 2, vn);
             }
         }
     } else {
@@ -318,7 +297,7 @@ __device__ __forceinline__ void mt_flush(const MtSumArgs& a, int cxa, int cxb, i
         for (int k = 0; k < 4; k++)
             if (n[k]) {
                 long long* t = a.acc + 3 * ((size_t)cy * a.gx + cxl[k]);
-                mt_add(t, s[k]); mt_add(t + 1, wq[k]); mt_add(t + 2, (long long)n[k]);
+                rc_acc_add(t, s[k]); rc_acc_add(t + 1, wq[k]); rc_acc_add(t + 2, (long long)n[k]);
             }
     }
 #pragma unroll
@@ -329,7 +308,7 @@ __device__ __forceinline__ void mt_flush(const MtSumArgs& a, int cxa, int cxb, i
 __device__ void mt_sum_finish(const MtSumArgs& a) {
     const int ncell = a.gx * a.gy;
     for (int c = threadIdx.x; c <= ncell; c += RC_BLOCK) {
-        const long long S = mt_take(a.acc + 3 * (size_t)c), W = mt_take(a.acc + 3 * (size_t)c + 1), n = mt_take(a.acc + 3 * (size_t)c + 2);
+        const long long S = rc_acc_take(a.acc + 3 * (size_t)c), W = rc_acc_take(a.acc + 3 * (size_t)c + 1), n = rc_acc_take(a.acc + 3 * (size_t)c + 2);
         const MtInfo f = a.info[c];                           // the previous launch's
         rc_motion_cell r;
         double ang = (double)f.base + (W ? (double)S / (double)W : 0.);
@@ -341,8 +320,8 @@ __device__ void mt_sum_finish(const MtSumArgs& a) {
         else if (a.frame2) *a.frame2 = r;
     }
     if (threadIdx.x != 0) return;
-    *a.sil_out = (long long)__hip_atomic_exchange(&a.ctl->sil, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&a.ctl->ticket2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // for the next push (stream order)
+    *a.sil_out = (long long)rc_acc_take(&a.ctl->sil);
+    __hip_atomic_store(&a.ctl->t2.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // for the next push (stream order)
 }
 
 __global__ __launch_bounds__(RC_BLOCK) void k_mt_sums(const MtSumArgs a) {
@@ -385,13 +364,13 @@ __global__ __launch_bounds__(RC_BLOCK) void k_mt_sums(const MtSumArgs a) {
         }
     }
     if (cur_cy >= 0) mt_flush(a, cxa, cxb, cur_cy, cxl, s, wq, n);
-    fs = mt_wave_sum(fs); fw = mt_wave_sum(fw);
-    const long long fnn = mt_wave_sum((long long)fn);
+    fs = rc_wave_sum_lane0(fs); fw = rc_wave_sum_lane0(fw);
+    const long long fnn = rc_wave_sum_lane0((long long)fn);
     if (lane == 0 && fnn) {
         long long* t = a.acc + 3 * (size_t)(a.gx * a.gy);
-        mt_add(t, fs); mt_add(t + 1, fw); mt_add(t + 2, fnn);
+        rc_acc_add(t, fs); rc_acc_add(t + 1, fw); rc_acc_add(t + 2, fnn);
     }
-    if (mt_last_block(&a.ctl->ticket2, a.nblocks, &last)) mt_sum_finish(a);
+    if (rc_hand_off_fenced(&a.ctl->t2.ticket, a.nblocks, &last)) mt_sum_finish(a);
 }
 
 // ============================================================================ motion@3: primitives

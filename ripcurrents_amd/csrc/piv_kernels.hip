@@ -26,8 +26,8 @@
 #include <math.h>
 #include <string.h>
 
-#include "rc_device.h"
 #include "rc_host.h"
+#include "rc_reduce.h"
 
 #define PV_WAVES 4
 static_assert(RC_BLOCK == 64 * PV_WAVES, "a block is PV_WAVES waves");
@@ -404,14 +404,12 @@ __global__ __launch_bounds__(RC_BLOCK) void k_pv_validate(const PvValArgs a) {
         __syncthreads();
         if (threadIdx.x == 0) {
             for (int k = 0; k < 5; k++)
-                if (cnt[k]) atomicAdd(&a.ctl->cnt[k], cnt[k]);
-            __threadfence();                                      // the counts before the ticket
-            last = atomicAdd(&a.ctl->ticket, 1u) == (unsigned)a.nbc - 1u;
+                if (cnt[k]) rc_acc_add(&a.ctl->cnt[k], cnt[k]);
+            last = rc_ticket_fenced(&a.ctl->ticket, (unsigned)a.nbc);                 // the counts before the ticket
             if (last) {
-                __threadfence();
                 long long s[8] = {a.n, ncell, 0, 0, 0, 0, 0, a.pushes};
-                for (int k = 0; k < 5; k++) s[2 + k] = atomicExch(&a.ctl->cnt[k], 0u);     // zero for the next push (stream order)
-                atomicExch(&a.ctl->ticket, 0u);
+                for (int k = 0; k < 5; k++) s[2 + k] = rc_acc_take(&a.ctl->cnt[k]);     // zero for the next push (stream order)
+                rc_acc_take(&a.ctl->ticket);
                 for (int k = 0; k < 8; k++) {
                     a.summary[k] = s[k];
                     if (a.summary2) a.summary2[k] = s[k];
@@ -422,7 +420,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_pv_validate(const PvValArgs a) {
     }
     // ---- a lane a pixel: first the cells the block's pixels lie in, a lane a cell
     const int b = blockIdx.x - a.nbc, bx = (a.w + 63) / 64, xb = (b % bx) * 64, yb = (b / bx) * PV_WAVES;
-    for (int i = threadIdx.x; i < 768; i += RC_BLOCK) lut[i] = a.jet[i];
+    rc_stage_jet(lut, a.jet);
     const int xa = max(xb, a.R), xe = min(xb + 63, a.w - 1), ya = max(yb, a.R), ye = min(yb + PV_WAVES - 1, a.h - 1);
     int cxa = 0, cya = 0, ncx = 0, ncy = 0;
     if (xa <= xe && ya <= ye) {
@@ -520,12 +518,7 @@ extern "C" int rcflow_piv_open(rc_ctx* ctx, int stream, int w, int h, const rc_p
     if (!rc) rc = rc_buf_ensure(n.acc, (size_t)(words * 8ull));
     if (!rc) rc = rc_buf_ensure(n.out, nc * 64 + 64);
     if (!rc) rc = rc_buf_ensure(n.ctl, sizeof(PvCtl));
-    if (!rc) rc = rc_buf_ensure(n.jet, 768);
-    if (!rc) {
-        uint8_t lut[768];
-        rcflow_jet_lut(lut);
-        if (hipMemcpy(n.jet.p, lut, 768, hipMemcpyHostToDevice) != hipSuccess) { rc_set_error("%s: the colour table's upload failed", who); rc = RC_EHIP; }
-    }
+    if (!rc) rc = rc_jet_ensure(n.jet, who);
     return rc_state_install(*s, s->piv, n, rc);
 }
 

@@ -16,13 +16,14 @@
 //                       aligned: the form of ftle@1), two multiplies and an add per component, the warps' 8-bit sample for
 //                       the picture; counts by ballot and popcount, the maximum as integer bits, a block's sums met in
 //                       LDS, three atomics per block on its shard's three lines, and the last-arriving block writes the
-//                       summary and leaves the counters zero (the ticket of ftle@2 without its fences: see the closing).
+//                       summary and leaves the counters zero (a ticket without a fence: see the closing).
 
 #include <math.h>
 #include <string.h>
 
 #include "rc_host.h"
 #include "rc_pix3.h"
+#include "rc_reduce.h"
 
 #define PV_WAVES 4
 static_assert(RC_BLOCK == 64 * PV_WAVES, "a block is PV_WAVES waves");
@@ -60,8 +61,6 @@ __device__ __forceinline__ PvProj pv_project(const rc_planview_params& p, double
     return o;
 }
 
-__device__ __forceinline__ bool pv_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }            // NaN fails
-
 __global__ __launch_bounds__(RC_BLOCK) void k_pv_table(const rc_planview_params p, float4* table) {
     const int i = blockIdx.x * 64 + (threadIdx.x & 63), j = blockIdx.y * PV_WAVES + (threadIdx.x >> 6);
     if (i >= p.nx || j >= p.ny) return;
@@ -73,8 +72,8 @@ __global__ __launch_bounds__(RC_BLOCK) void k_pv_table(const rc_planview_params 
     const double det = a * d - b * c;
     const double m00 = d / det * p.fps, m01 = -b / det * p.fps, m10 = -c / det * p.fps, m11 = a / det * p.fps;
     const double gsd = sqrt(fabs(1. / det));
-    const bool usable = C.ok && E.ok && W.ok && S.ok && N.ok && pv_finite(C.U) && pv_finite(C.V) && pv_finite(det) && pv_finite(m00) &&
-                        pv_finite(m01) && pv_finite(m10) && pv_finite(m11) && pv_finite(gsd) && det != 0. && gsd <= p.max_gsd;
+    const bool usable = C.ok && E.ok && W.ok && S.ok && N.ok && rc_finite(C.U) && rc_finite(C.V) && rc_finite(det) && rc_finite(m00) &&
+                        rc_finite(m01) && rc_finite(m10) && rc_finite(m11) && rc_finite(gsd) && det != 0. && gsd <= p.max_gsd;
     float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0;
     if (usable) {
         r0 = make_float4((float)C.U, (float)C.V, (float)m00, (float)m01);
@@ -101,27 +100,25 @@ struct PvPushArgs {
     unsigned nblocks;
 };
 
-// The closing, without a fence: a release at agent scope writes the L2's dirty lines back, and this launch has just dirtied
-// all of its output; 1024 blocks ending in __threadfence took 90 to 180 us whatever the plan's size.  Nothing but
-// atomics passes between blocks here, and a fence orders what this needs no order for.  What it needs: the block that draws
-// the last ticket finds every block's sums.  A block's ticket is made from the values its two other atomics returned (`dep`,
-// always 0: a count has no bit 63, the bits of a number that is no NaN and not negative no bit 31), so it is issued after
-// they were performed where atomics of agent scope are performed; the last block's exchanges are issued after its ticket
-// returned (the branch).  The valid count rides on the ticket word itself.
+// The closing, without a fence: rc_reduce.h says why a launch that has just dirtied all of its output wants none, what gfx950
+// gives instead and what a port needs (DESIGN 7l has the times).  Here a block's ticket is made from the values its two other
+// atomics returned (`dep`, always 0: a count has no bit 63, the bits of a number that is no NaN and not negative no bit 31), so it
+// is issued after they were performed; the last block's exchanges are issued after its ticket returned (the branch).  The valid
+// count rides on the ticket word itself.
 // Adds s to the lines; true for the last of n arrivals, which gets the totals in s and leaves the lines zero.
 __device__ __forceinline__ bool pv_arrive(PvLines* L, PvSums& s, unsigned n) {
     const unsigned long long c0 =
-        __hip_atomic_fetch_add(&L->cells, (unsigned long long)s.usable | ((unsigned long long)s.seen << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        rc_acc_add_old(&L->cells, (unsigned long long)s.usable | ((unsigned long long)s.seen << 32));
     const unsigned m0 = s.maxbits ? __hip_atomic_fetch_max(&L->maxbits, s.maxbits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
     const unsigned long long dep = (c0 >> 63) | (unsigned long long)(m0 >> 31);
     const unsigned long long t =
-        __hip_atomic_fetch_add(&L->ticket, ((1ull << 32) | (unsigned long long)s.valid) + dep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        rc_acc_add_old(&L->ticket, ((1ull << 32) | (unsigned long long)s.valid) + dep);
     if ((unsigned)(t >> 32) != n - 1u) return false;
-    const unsigned long long c = __hip_atomic_exchange(&L->cells, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long c = rc_acc_take(&L->cells);
     s.usable = (unsigned)c;
     s.seen = (unsigned)(c >> 32);
     s.valid += (unsigned)t;
-    s.maxbits = __hip_atomic_exchange(&L->maxbits, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s.maxbits = rc_acc_take(&L->maxbits);
     __hip_atomic_store(&L->ticket, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // for the next arrivals (stream order)
     return true;
 }
@@ -191,7 +188,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_pv_push(const PvPushArgs a) {
         nu += (unsigned)__popcll(__ballot(t1.w != 0.f)); ns += (unsigned)__popcll(__ballot(seen)); nv += (unsigned)__popcll(__ballot(valid));
     }
     // the integer sums: per wave, then the block's in LDS, then one atomic per counter
-    for (int o = 32; o > 0; o >>= 1) mb = max(mb, (unsigned)__shfl_xor((int)mb, o, 64));
+    mb = rc_wave_max_all(mb);
     if (lane == 0) {
         if (nu) atomicAdd(&sums[0], nu);
         if (ns) atomicAdd(&sums[1], ns);

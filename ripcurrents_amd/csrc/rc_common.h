@@ -18,6 +18,9 @@ __device__ __forceinline__ int rc_cvt_i32_x86(float v) {
     return (v >= -2147483648.f && v < 2147483648.f) ? (int)v : (int)0x80000000;
 }
 
+// finite: neither an infinity nor a NaN (NaN fails the comparison)
+__host__ __device__ __forceinline__ bool rc_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }
+
 // helpers the analysis kernels share (analysis_kernels.hip, ripmap_kernels.hip)
 __device__ __forceinline__ const float2* rc_row2(const float* base, size_t step, int y) {
     return (const float2*)((const char*)base + (size_t)y * step);

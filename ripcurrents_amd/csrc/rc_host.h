@@ -542,6 +542,8 @@ static_assert(RC_B_BUCKETS == RC_PROFILE_BUCKETS, "include/rcflow.h promises RC_
 
 int rc_buf_ensure(RcBuf& b, size_t bytes);
 void rc_buf_free(RcBuf& b);
+// a product's COLORMAP_JET table (768 bytes) on the device, by its open call `who`
+int rc_jet_ensure(RcBuf& b, const char* who);
 RcSlot* rc_slot(rc_ctx* ctx, int stream);
 void rc_graph_drop(RcGraphCache& g);
 // analysis_kernels.hip, for rcflow_frame_loop_step

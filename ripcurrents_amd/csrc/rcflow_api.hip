@@ -41,6 +41,14 @@ void rc_buf_free(RcBuf& b) {
     b.p = nullptr;
     b.bytes = 0;
 }
+int rc_jet_ensure(RcBuf& b, const char* who) {
+    const int rc = rc_buf_ensure(b, 768);
+    if (rc) return rc;
+    uint8_t lut[768];
+    rcflow_jet_lut(lut);
+    if (hipMemcpy(b.p, lut, 768, hipMemcpyHostToDevice) != hipSuccess) { rc_set_error("%s: the colour table's upload failed", who); return RC_EHIP; }
+    return RC_OK;
+}
 RcSlot* rc_slot(rc_ctx* ctx, int stream) {
     if (!ctx || stream < 0 || stream >= ctx->nstreams) {
         rc_set_error("bad context or stream index %d", stream);

@@ -9,7 +9,7 @@
 //               mean in k_window_mean's operation order; the mean in 16.16 fixed point summed per cell (int64: the sum
 //               does not depend on the order of addition, so it equals numpy's whatever the tiling); the colour triple
 //               of the mean scaled by the PREVIOUS push's maximum, this push's maximum kept on the device;
-//   finish      the launch's last-arriving workgroup (ticket hand-off as k_stab_correlate_multi's) takes the global
+//   finish      the launch's last-arriving workgroup (rc_hand_off_release of rc_reduce.h) takes the global
 //               vector, decides every cell in double in a fixed order, writes cells and summary and zeroes the sums.
 // Deviations from averageVector as written, each because the original cannot work: the ring expires (it was passed by
 // value there); a cell's mean divides by that cell's own population (there: cell (5, 5)'s); directions are compared
@@ -23,6 +23,7 @@
 
 #include "rc_host.h"
 #include "rc_pix3.h"
+#include "rc_reduce.h"
 
 #define RM_WAVES 4
 static_assert(RC_BLOCK == 64 * RM_WAVES, "a block is RM_WAVES waves, a run of rows each");
@@ -31,8 +32,7 @@ static_assert(RC_BLOCK == 64 * RM_WAVES, "a block is RM_WAVES waves, a run of ro
 
 // control words at the start of RcRipMap::acc.  The ticket has a 128-byte line of its own: every block adds to it.
 struct RmCtl {
-    unsigned ticket;            // arrivals of the running launch
-    unsigned pad0[31];
+    RcTicketLine t;             // arrivals of the running launch
     unsigned max_acc;           // bits of this push's maximum |mean| so far (non-negative floats order as integers)
     float scale;                // the previous push's maximum: the colour scale of the next one
     unsigned long long bad;     // pixels left out of the sums by this push
@@ -61,21 +61,6 @@ struct RmArgs {
 
 typedef float rm_f4u __attribute__((ext_vector_type(4), aligned(1)));   // a 16-byte access of unknown alignment
 
-__device__ __forceinline__ long long rm_wave_sum(long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float rm_wave_max(float v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_down(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ void rm_add(long long* p, long long v) {
-    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ long long rm_take(long long* p) {      // read and zero in one operation, where the adds were made
-    return __hip_atomic_exchange(p, 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // get_delta from a zero point (ripcurrents_module.cpp:395-397, :650-679): k_get_delta_field's arithmetic with p = 0, dt = 2
 __device__ __forceinline__ float2 rm_delta(const RmArgs& a, int xo, int yo, float UPPER) {
     float2 p = make_float2(0.f, 0.f);
@@ -97,7 +82,7 @@ __device__ __forceinline__ void rm_flush(const RmArgs& a, long long* tab, bool l
         long long vx = (cxl[0] == cx ? sx[0] : 0) + (cxl[1] == cx ? sx[1] : 0);
         long long vy = (cxl[0] == cx ? sy[0] : 0) + (cxl[1] == cx ? sy[1] : 0);
         long long vn = (cxl[0] == cx ? sn[0] : 0) + (cxl[1] == cx ? sn[1] : 0);
-        vx = rm_wave_sum(vx); vy = rm_wave_sum(vy); vn = rm_wave_sum(vn);
+        vx = rc_wave_sum_lane0(vx); vy = rc_wave_sum_lane0(vy); vn = rc_wave_sum_lane0(vn);
         if ((threadIdx.x & 63) == 0 && vn) {
             if (lds) {
                 long long* t = tab + 3 * ((cy - cya) * nx + (cx - cxa));
@@ -106,7 +91,7 @@ __device__ __forceinline__ void rm_flush(const RmArgs& a, long long* tab, bool l
                 atomicAdd((unsigned long long*)t + 2, (unsigned long long)vn);
             } else {
                 long long* t = a.acc + 3 * ((size_t)cy * a.gx + cx);
-                rm_add(t, vx); rm_add(t + 1, vy); rm_add(t + 2, vn);
+                rc_acc_add(t, vx); rc_acc_add(t + 1, vy); rc_acc_add(t + 2, vn);
             }
         }
     }
@@ -120,11 +105,11 @@ __device__ void rm_finish(const RmArgs& a, long long* red /* [RM_WAVES][4] */) {
     const int ncell = a.gx * a.gy, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     long long gx = 0, gy = 0, gn = 0, live = 0;
     for (int c = threadIdx.x; c < ncell; c += RC_BLOCK) {
-        const long long sx = rm_take(a.acc + 3 * c), sy = rm_take(a.acc + 3 * c + 1), n = rm_take(a.acc + 3 * c + 2);
+        const long long sx = rc_acc_take(a.acc + 3 * c), sy = rc_acc_take(a.acc + 3 * c + 1), n = rc_acc_take(a.acc + 3 * c + 2);
         a.sums[3 * c] = sx; a.sums[3 * c + 1] = sy; a.sums[3 * c + 2] = n;     // read back below by this same thread
         gx += sx; gy += sy; gn += n; live += n > 0;
     }
-    gx = rm_wave_sum(gx); gy = rm_wave_sum(gy); gn = rm_wave_sum(gn); live = rm_wave_sum(live);
+    gx = rc_wave_sum_lane0(gx); gy = rc_wave_sum_lane0(gy); gn = rc_wave_sum_lane0(gn); live = rc_wave_sum_lane0(live);
     if (lane == 0) { red[4 * wv] = gx; red[4 * wv + 1] = gy; red[4 * wv + 2] = gn; red[4 * wv + 3] = live; }
     __syncthreads();
     gx = gy = gn = live = 0;
@@ -152,14 +137,14 @@ __device__ void rm_finish(const RmArgs& a, long long* red /* [RM_WAVES][4] */) {
         if (a.cells2) a.cells2[c] = o;
         opp += opposed;
     }
-    opp = rm_wave_sum(opp);
+    opp = rc_wave_sum_lane0(opp);
     if (lane == 0) red[4 * wv] = opp;
     __syncthreads();
     if (threadIdx.x != 0) return;
     opp = 0;
     for (int k = 0; k < RM_WAVES; k++) opp += red[4 * k];
-    const unsigned long long bad = __hip_atomic_exchange(&a.ctl->bad, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned mbits = __hip_atomic_exchange(&a.ctl->max_acc, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long bad = rc_acc_take(&a.ctl->bad);
+    const unsigned mbits = rc_acc_take(&a.ctl->max_acc);
     const float mx = __uint_as_float(mbits);
     a.ctl->scale = mx;                       // every block of this launch read the old one before it drew its ticket
     double dir = atan2(Gy, Gx) * deg;
@@ -175,7 +160,7 @@ __device__ void rm_finish(const RmArgs& a, long long* red /* [RM_WAVES][4] */) {
         a.summary[k] = s[k];
         if (a.summary2) a.summary2[k] = s[k];
     }
-    __hip_atomic_store(&a.ctl->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // for the next push (stream order)
+    __hip_atomic_store(&a.ctl->t.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // for the next push (stream order)
 }
 
 template <int SOURCE>
@@ -279,8 +264,8 @@ __global__ __launch_bounds__(RC_BLOCK) void k_ripmap(const RmArgs a) {
         }
     }
     if (cur_cy >= 0) rm_flush(a, tab, lds, cxa, cxb, cya, cur_cy, cxl, sx, sy, sn);
-    bad = (unsigned)rm_wave_sum((long long)bad);
-    mx = rm_wave_max(mx);
+    bad = (unsigned)rc_wave_sum_lane0((long long)bad);
+    mx = rc_wave_max_lane0(mx);
     if (lane == 0) { red[wv] = bad; red_max[wv] = mx; }
     __syncthreads();
     // one atomic per sum and cell the block touched, as lanes of one instruction
@@ -288,31 +273,19 @@ __global__ __launch_bounds__(RC_BLOCK) void k_ripmap(const RmArgs a) {
         const long long val = tab[threadIdx.x];
         const int c = threadIdx.x / 3, k = threadIdx.x - 3 * c, nx = cxb - cxa + 1;
         const int cy = cya + c / nx, cx = cxa + c % nx;
-        if (val) rm_add(a.acc + 3 * ((size_t)cy * a.gx + cx) + k, val);
+        if (val) rc_acc_add(a.acc + 3 * ((size_t)cy * a.gx + cx) + k, val);
     }
     if (threadIdx.x == 0) {
         unsigned b = 0;
         float m = 0.f;
         for (int k = 0; k < RM_WAVES; k++) { b += (unsigned)red[k]; m = fmaxf(m, red_max[k]); }
-        if (b) __hip_atomic_fetch_add(&a.ctl->bad, (unsigned long long)b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (b) rc_acc_add(&a.ctl->bad, (unsigned long long)b);
         // the maximum only grows: a block below what is there already has nothing to add
         const unsigned mb = __float_as_uint(m);
-        if (mb > __hip_atomic_load(&a.ctl->max_acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+        if (mb > rc_acc_load(&a.ctl->max_acc))
             __hip_atomic_fetch_max(&a.ctl->max_acc, mb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    // hand-off: every wave's atomics have been performed, then ONE release, the ticket, and for the last arriver ONE acquire
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned t = __hip_atomic_fetch_add(&a.ctl->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int l = t == a.nblocks - 1u;
-        if (l) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        last = l;
-    }
-    __syncthreads();
-    if (last) rm_finish(a, red);
+    if (rc_hand_off_release(&a.ctl->t.ticket, a.nblocks, &last)) rm_finish(a, red);
 }
 
 // "ripmap@1": 255 inside an opposed cell.  A thread owns 4 consecutive pixels of a row (rc_pix3.h's span, one byte each).

@@ -12,7 +12,7 @@
 //                picture, goes into LDS as uint16: a lane takes 4 pixels of the tile's 64 columns at once (12 bytes of an 8UC3 row),
 //                a wave 4 rows a pass; the 2 r halo columns pixel by pixel.  Horizontal sums into a second array, vertical sums
 //                from it, a wave one LDS row at a time; J to the state plane; the histogram per wave in LDS, met and flushed once
-//                per block as one atomic per bin it touched.  The last-arriving block (the hand-off of kinematics_kernels.hip)
+//                per block as one atomic per bin it touched.  The last-arriving block (rc_hand_off_release of rc_reduce.h)
 //                takes the histogram out, leaves it zero, and its first wave scans the 511 bins: a lane 8 bins, the prefix sums by
 //                a wave scan, the first largest score by a wave reduction;
 //   shoreline@1  a wave a line: the samples into LDS, a lane a run of consecutive samples, the dry counts before each run by a wave
@@ -29,13 +29,14 @@
 
 #include "rc_pix3.h"
 #include "rc_host.h"
+#include "rc_reduce.h"
 
 #define SH_WAVES 4
 static_assert(RC_BLOCK == 64 * SH_WAVES, "a block is SH_WAVES waves");
 #define SH_TW 64
 #define SH_RPW 8               // rows a wave walks
 #define SH_TH (SH_WAVES * SH_RPW)
-#define SH_MAX_BLOCKS 512      // every block ends in a flush, a release and a ticket on one line (kinematics_kernels.hip); at 1080p caps of
+#define SH_MAX_BLOCKS 512      // every block ends in a flush, a release and a ticket on one line (as kinematics@0); at 1080p caps of
                                // 128, 256, 512 and 1024 gave 44, 31, 28 and 37 us (profiles/shoreline_kernel_summary.md)
 #define SH_FH (SH_TH + 2 * RC_SHORE_MAX_RADIUS)
 #define SH_FW (SH_TW + 2 * RC_SHORE_MAX_RADIUS)
@@ -45,7 +46,7 @@ static_assert(RC_SHORE_MAX_SAMPLES <= 64 * 16 && RC_SHORE_MAX_WINDOW == 4096, "s
 
 // RcShoreline::ctl.  Each ticket has a 128-byte line of its own: every block adds to it
 struct ShCtl {
-    unsigned ticket0; unsigned pad0[31];
+    RcTicketLine t0;
     unsigned ticket2, cnt[4]; unsigned pad1[27];
     int thr; unsigned pad2; long long N; double eta; unsigned pad3[26];   // of the last shoreline@0
     unsigned hist[RC_SHORE_HIST];                                          // live: zero between launches
@@ -55,26 +56,6 @@ static_assert(sizeof(ShCtl) == 384 + 4 * RC_SHORE_HIST, "three lines and the his
 // what shoreline@1 hands to shoreline@2
 struct ShLine { int flags, k, pos, agree, wx, wy, pad[2]; };
 
-// the hand-off of kinematics_kernels.hip: every wave's stores and atomics performed, ONE release, the ticket, ONE acquire
-#define SH_HAND_OFF(ticket, nblocks, last)                                                                        \
-    do {                                                                                                          \
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                          \
-        __syncthreads();                                                                                          \
-        if (threadIdx.x == 0) {                                                                                   \
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");                                                    \
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                      \
-            const unsigned t_ = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   \
-            const int l_ = t_ == (nblocks) - 1u;                                                                  \
-            if (l_) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");                                            \
-            last = l_;                                                                                            \
-        }                                                                                                         \
-        __syncthreads();                                                                                          \
-    } while (0)
-
-__device__ __forceinline__ long long sh_wave_sum(long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ bool sh_wet(int v, int thr, int high) { return high ? v > thr : v <= thr; }
 
 // ============================================================================ shoreline@0: indicator, box, plane, histogram, Otsu
@@ -168,15 +149,14 @@ __global__ __launch_bounds__(RC_BLOCK) void k_sh_pixels(const ShArgs0 a) {
     __syncthreads();
     for (int b = threadIdx.x; b < SH_LIVE; b += RC_BLOCK) {
         const unsigned v = hist[0][b] + hist[1][b] + hist[2][b] + hist[3][b];
-        if (v) __hip_atomic_fetch_add(&a.ctl->hist[b], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (v) rc_acc_add(&a.ctl->hist[b], v);
     }
-    SH_HAND_OFF(&a.ctl->ticket0, a.nblocks, last);
-    if (!last) return;
+    if (!rc_hand_off_release(&a.ctl->t0.ticket, a.nblocks, &last)) return;
 
     // Otsu, by the last-arriving block: the histogram out of the live words, which are left zero for the next push
     unsigned* lh = hist[0];
     for (int b = threadIdx.x; b < RC_SHORE_HIST; b += RC_BLOCK) {
-        const unsigned v = b < SH_LIVE ? __hip_atomic_exchange(&a.ctl->hist[b], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+        const unsigned v = b < SH_LIVE ? rc_acc_take(&a.ctl->hist[b]) : 0u;
         lh[b] = v;
         a.hist_out[b] = v;
     }
@@ -193,7 +173,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_sh_pixels(const ShArgs0 a) {
         const long long tw = __shfl_up(pw, o, 64), tm = __shfl_up(pm, o, 64);
         if (lane >= o) { pw += tw; pm += tm; }
     }
-    const long long N = __shfl(pw, 63, 64), S1 = __shfl(pm, 63, 64), S2 = sh_wave_sum(l2);
+    const long long N = __shfl(pw, 63, 64), S1 = __shfl(pm, 63, 64), S2 = rc_wave_sum_all(l2);
     long long w0 = pw - lw, m0 = pm - lm;
     double best = -1., sfix = 0.;
     int bt = -1;
@@ -223,7 +203,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_sh_pixels(const ShArgs0 a) {
     a.ctl->thr = thr;                                         // read by the next launches (stream order)
     a.ctl->N = N;
     a.ctl->eta = thr >= 0 && tot > 0. ? s / tot : 0.;
-    __hip_atomic_store(&a.ctl->ticket0, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&a.ctl->t0.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ============================================================================ shoreline@1: samples, best split, position
@@ -235,11 +215,6 @@ struct ShArgs1 {
     int w, h, L, wet_is_high;
     double min_sep;
 };
-
-__device__ __forceinline__ long long sh_floor_div(long long a, long long b) {   // b > 0
-    const long long q = a / b;
-    return q - (a % b != 0 && a < 0);
-}
 
 __global__ __launch_bounds__(RC_BLOCK) void k_sh_lines(const ShArgs1 a) {
     __shared__ uint16_t Vs[SH_WAVES][RC_SHORE_MAX_SAMPLES];
@@ -304,8 +279,8 @@ __global__ __launch_bounds__(RC_BLOCK) void k_sh_lines(const ShArgs1 a) {
         const long long pos = (long long)(bk - 1) * 256 + frac, den = 256ll * (n - 1);
         const rc_transect_sample sa = a.table[first], sb = a.table[(size_t)first + n - 1];
         o.pos = (int)pos;
-        o.wx = (int)(16ll * sa.X + sh_floor_div(16ll * (sb.X - sa.X) * pos + 128ll * (n - 1), den));
-        o.wy = (int)(16ll * sa.Y + sh_floor_div(16ll * (sb.Y - sa.Y) * pos + 128ll * (n - 1), den));
+        o.wx = (int)(16ll * sa.X + rc_floor_div(16ll * (sb.X - sa.X) * pos + 128ll * (n - 1), den));
+        o.wy = (int)(16ll * sa.Y + rc_floor_div(16ll * (sb.Y - sa.Y) * pos + 128ll * (n - 1), den));
     }
     a.lin[line] = o;
 }
@@ -391,17 +366,15 @@ __global__ __launch_bounds__(RC_BLOCK) void k_sh_records(const ShArgs2 a) {
     }
     a.rec[line] = r;
     if (a.rec2) a.rec2[line] = r;
-    if (cur >= 0) atomicAdd(&a.ctl->cnt[0], 1u);
-    if (r.flags & RC_SHORE_DRY) atomicAdd(&a.ctl->cnt[1], 1u);
-    if (r.flags & RC_SHORE_WET) atomicAdd(&a.ctl->cnt[2], 1u);
-    if (r.flags & RC_SHORE_OUTLIER) atomicAdd(&a.ctl->cnt[3], 1u);
-    __threadfence();                                          // the counts before the ticket (transects@1)
-    last = atomicAdd(&a.ctl->ticket2, 1u) == (unsigned)a.L - 1u;
+    if (cur >= 0) rc_acc_add(&a.ctl->cnt[0], 1u);
+    if (r.flags & RC_SHORE_DRY) rc_acc_add(&a.ctl->cnt[1], 1u);
+    if (r.flags & RC_SHORE_WET) rc_acc_add(&a.ctl->cnt[2], 1u);
+    if (r.flags & RC_SHORE_OUTLIER) rc_acc_add(&a.ctl->cnt[3], 1u);
+    last = rc_ticket_fenced(&a.ctl->ticket2, (unsigned)a.L);  // the counts before the ticket
     if (last) {
-        __threadfence();
         long long s[8] = {a.ctl->thr, a.ctl->N, (long long)rint(a.ctl->eta * 4294967296.), 0, 0, 0, 0, a.pushes};
-        for (int k = 0; k < 4; k++) s[3 + k] = atomicExch(&a.ctl->cnt[k], 0u);      // zero for the next push (stream order)
-        atomicExch(&a.ctl->ticket2, 0u);
+        for (int k = 0; k < 4; k++) s[3 + k] = rc_acc_take(&a.ctl->cnt[k]);      // zero for the next push (stream order)
+        rc_acc_take(&a.ctl->ticket2);
         for (int k = 0; k < 8; k++) {
             a.summary[k] = s[k];
             if (a.summary2) a.summary2[k] = s[k];
@@ -467,7 +440,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_sh_prims(const rc_shoreline* rec, 
 }
 
 // ============================================================================ host side
-static bool sh_pos(double v) { return v > 0. && v <= 1.7976931348623157e308; }       // finite and > 0; NaN fails
+static bool sh_pos(double v) { return v > 0. && rc_finite(v); }
 static bool sh_settable(int threshold, double min_sep, double max_jump) {
     return threshold >= -1 && threshold <= SH_LIVE - 2 && min_sep >= 0. && min_sep <= 1. && max_jump > 0. && max_jump <= 16384.;
 }

@@ -32,6 +32,7 @@
 
 #include "rc_host.h"
 #include "rc_pix3.h"
+#include "rc_reduce.h"
 
 #define ST_BLOCK 1024                    // the correlate workgroup: 16 waves
 #define ST_RED_BYTES 256                 // per-wave (value, index) of the arg-max
@@ -223,8 +224,8 @@ __global__ __launch_bounds__(ST_BLOCK) void k_stab_correlate(const StArgs p) { s
 // Workgroup k correlates patch k (the body above, unchanged) and thread 0 of the workgroup that finishes LAST fits the
 // motion to the gated shifts, so a push stays at two launches.  Hand-off between workgroups (they run on different CUs
 // and XCDs, whose L1 / L2 do not see each other's plain stores): thread 0 stores its three doubles again with
-// agent-scope atomic stores, drains them, does ONE agent-scope release fence, drains again, then draws a ticket with an
-// agent-scope atomic add; the thread that draws n - 1 does ONE agent-scope acquire fence and reads all the shifts with
+// agent-scope atomic stores, then rc_ticket_release (rc_reduce.h): drain, ONE agent-scope release fence, drain, the
+// ticket; the thread that draws n - 1 does ONE agent-scope acquire fence, and reads all the shifts with
 // agent-scope atomic loads.  Nothing waits for anything: no spinning, any dispatch order works.  The last arriver zeroes
 // the ticket for the next push (stream order), and open / reset zero it with the rest of the state.
 struct StMultiArgs {
@@ -237,7 +238,6 @@ struct StMultiArgs {
     int rx[RC_STAB_MAX_PATCHES], ry[RC_STAB_MAX_PATCHES];
 };
 
-__device__ __forceinline__ double st_ld(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // One lane, fp64; products and sums round one by one (-ffp-contract=off), in the order of tests/_framewarp_ref.py
 __device__ void st_fit(const StMultiArgs& m) {
@@ -247,11 +247,11 @@ __device__ void st_fit(const StMultiArgs& m) {
     unsigned mask = 0;
     int cnt = 0;
     for (int k = 0; k < m.n; k++) {
-        const double r = st_ld(sh + 3 * k + 2);
+        const double r = rc_acc_load(sh + 3 * k + 2);
         if (!(r >= m.min_response)) continue;
         mask |= 1u << k; cnt++;
         px += (double)m.rx[k] + hx; py += (double)m.ry[k] + hy;
-        tx += st_ld(sh + 3 * k); ty += st_ld(sh + 3 * k + 1);
+        tx += rc_acc_load(sh + 3 * k); ty += rc_acc_load(sh + 3 * k + 1);
         rmin = r < rmin ? r : rmin;
     }
     double b00 = 0., b01 = 0., b10 = 0., b11 = 0.;
@@ -263,7 +263,7 @@ __device__ void st_fit(const StMultiArgs& m) {
         for (int k = 0; k < m.n; k++) {
             if (!(mask >> k & 1u)) continue;
             const double ux = ((double)m.rx[k] + hx) - px, uy = ((double)m.ry[k] + hy) - py;
-            const double ex = st_ld(sh + 3 * k) - tx, ey = st_ld(sh + 3 * k + 1) - ty;
+            const double ex = rc_acc_load(sh + 3 * k) - tx, ey = rc_acc_load(sh + 3 * k + 1) - ty;
             sxx += ux * ux; sxy += ux * uy; syy += uy * uy;
             xdx += ux * ex; ydx += uy * ex; xdy += ux * ey; ydy += uy * ey;
         }
@@ -305,13 +305,8 @@ __global__ __launch_bounds__(ST_BLOCK) void k_stab_correlate_multi(const StMulti
     // this thread wrote p.res (st_peak); again as write-through stores, then release, then the ticket
 #pragma unroll
     for (int i = 0; i < 3; i++) __hip_atomic_store(p.res + i, p.res[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     unsigned* ticket = (unsigned*)(m.state + RC_FS_TICKET);
-    const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (t != (unsigned)(m.n - 1)) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    if (!rc_ticket_release(ticket, (unsigned)m.n)) return;
     __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     st_fit(m);
 }

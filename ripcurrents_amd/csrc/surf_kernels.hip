@@ -14,7 +14,7 @@
 //           256 pixels four uint64, word k holding pixel 4 lane + k in bit `lane`; the outgoing flags are read the same way and
 //           picked out by lane.  The picture's index depends on Q alone: a table per block in LDS.  The three counts by a wave
 //           reduction and LDS to a place per block, then the ticket and the last-arriving block's hand-over
-//           (kinematics_kernels.hip), which adds the places up;
+//           (rc_hand_off_release of rc_reduce.h), which adds the places up;
 //   surf@1  a wave a line: the samples of the Q plane, four a lane in flight; the in-samples as a bit mask across the lanes by the
 //           wave's ballot, the runs of min_run and more by shifting and masking it;
 //   surf@2  one block: a thread a line takes the rank among at most 65 loads by counting, thread 0 walks the lines for the
@@ -26,13 +26,13 @@
 
 #include <vector>
 
-#include "rc_device.h"
 #include "rc_host.h"
+#include "rc_reduce.h"
 
 #define SF_WAVES 4
 static_assert(RC_BLOCK == 64 * SF_WAVES, "a block is SF_WAVES waves");
 #define SF_TILE 256            // pixels a wave takes at a time
-#define SF_MAX_BLOCKS 256      // every block ends in a release and a ticket on one line (kinematics_kernels.hip), and the launch pays for each:
+#define SF_MAX_BLOCKS 256      // every block ends in a release and a ticket on one line (as kinematics@0), and the launch pays for each:
                                // at 1080p caps of 128, 256, 512 and 1024 gave 30, 22, 26 and 36 us without outputs and 48, 33, 33 and 43 us
                                // with all six (profiles/surf_kernel_summary.md)
 #define SF_DIV_BITS 22         // the numerators of sf_div are below 2^22
@@ -45,27 +45,11 @@ static_assert(RC_SURF_MAX_WINDOW == 4096 && RC_SURF_MAX_SAMPLES == 1024 && RC_SU
 // by plain stores, so the ticket is the launch's only atomic on a shared line
 struct SfPart { unsigned now, surf; unsigned long long sumq; };
 struct SfCtl {
-    unsigned ticket0; unsigned pad0[31];
+    RcTicketLine t0;
     long long res[3]; unsigned pad1[26];                                 // of the last surf@0: now | surf | sum Q
     SfPart part[SF_MAX_BLOCKS];                                            // written by every block of every launch
 };
 static_assert(sizeof(SfCtl) == 256 + 16 * SF_MAX_BLOCKS, "two lines and the blocks' counts");
-
-// the hand-off of kinematics_kernels.hip: every wave's stores and atomics performed, ONE release, the ticket, ONE acquire
-#define SF_HAND_OFF(ticket, nblocks, last)                                                                        \
-    do {                                                                                                          \
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                          \
-        __syncthreads();                                                                                          \
-        if (threadIdx.x == 0) {                                                                                   \
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");                                                    \
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                      \
-            const unsigned t_ = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   \
-            const int l_ = t_ == (nblocks) - 1u;                                                                  \
-            if (l_) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");                                            \
-            last = l_;                                                                                            \
-        }                                                                                                         \
-        __syncthreads();                                                                                          \
-    } while (0)
 
 // floor(v / d) for v < 2^SF_DIV_BITS by a multiplication: m = ceil(2^s / d) with s = SF_DIV_BITS + ceil(log2 d) is exact there
 // (Granlund and Montgomery); d is the same for every pixel of a push, so the host finds m and s
@@ -79,11 +63,6 @@ static SfDiv sf_div_of(unsigned d) {
     return r;
 }
 __device__ __forceinline__ unsigned sf_div(unsigned v, SfDiv d) { return (unsigned)(((unsigned long long)v * d.m) >> d.s); }
-
-__device__ __forceinline__ unsigned sf_wave_sum(unsigned v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // ============================================================================ surf@0: ring, sums, flags, pictures, counts
 struct SfArgs0 {
@@ -130,7 +109,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_sf_pixels(const SfArgs0 a) {
     if (threadIdx.x == 0) { cnt[0] = cnt[1] = 0u; sq = 0ull; }
     if (a.pic) {
         for (int i = threadIdx.x; i <= a.n; i += RC_BLOCK) qi[i] = (uint8_t)min(255u, (unsigned)i * 255000u / a.vis_n);
-        for (int i = threadIdx.x; i < 768; i += RC_BLOCK) jet[i] = a.jet[i];
+        rc_stage_jet(jet, a.jet);
     }
     __syncthreads();
     unsigned c_now = 0, c_surf = 0, c_q = 0;                  // a lane's: at most 2^25 / (64 SF_WAVES SF_MAX_BLOCKS) * 4 pixels of Q <= 4096
@@ -236,9 +215,9 @@ __global__ __launch_bounds__(RC_BLOCK) void k_sf_pixels(const SfArgs0 a) {
             }
         }
     }
-    c_now = sf_wave_sum(c_now); c_surf = sf_wave_sum(c_surf);
+    c_now = rc_wave_sum_all(c_now); c_surf = rc_wave_sum_all(c_surf);
     unsigned long long wq = c_q;
-    for (int o = 32; o > 0; o >>= 1) wq += __shfl_xor(wq, o, 64);
+    wq = rc_wave_sum_all(wq);
     if (lane == 0) { atomicAdd(&cnt[0], c_now); atomicAdd(&cnt[1], c_surf); atomicAdd(&sq, wq); }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -246,26 +225,25 @@ __global__ __launch_bounds__(RC_BLOCK) void k_sf_pixels(const SfArgs0 a) {
         p.now = cnt[0]; p.surf = cnt[1]; p.sumq = sq;
         a.ctl->part[blockIdx.x] = p;
     }
-    SF_HAND_OFF(&a.ctl->ticket0, a.nblocks, last);
-    if (!last) return;
+    if (!rc_hand_off_release(&a.ctl->t0.ticket, a.nblocks, &last)) return;
     // the last-arriving block adds up the blocks' counts
     if (threadIdx.x == 0) { cnt[0] = cnt[1] = 0u; sq = 0ull; }
     __syncthreads();
     unsigned p_now = 0, p_surf = 0;
     unsigned long long p_q = 0;
     for (unsigned b = threadIdx.x; b < a.nblocks; b += RC_BLOCK) {
-        p_now += __hip_atomic_load(&a.ctl->part[b].now, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        p_surf += __hip_atomic_load(&a.ctl->part[b].surf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        p_q += __hip_atomic_load(&a.ctl->part[b].sumq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        p_now += rc_acc_load(&a.ctl->part[b].now);
+        p_surf += rc_acc_load(&a.ctl->part[b].surf);
+        p_q += rc_acc_load(&a.ctl->part[b].sumq);
     }
-    p_now = sf_wave_sum(p_now); p_surf = sf_wave_sum(p_surf);
-    for (int o = 32; o > 0; o >>= 1) p_q += __shfl_xor(p_q, o, 64);
+    p_now = rc_wave_sum_all(p_now); p_surf = rc_wave_sum_all(p_surf);
+    p_q = rc_wave_sum_all(p_q);
     if (lane == 0) { atomicAdd(&cnt[0], p_now); atomicAdd(&cnt[1], p_surf); atomicAdd(&sq, p_q); }
     __syncthreads();
     if (threadIdx.x != 0) return;
     const long long r0 = cnt[0], r1 = cnt[1], r2 = (long long)sq;
     a.ctl->res[0] = r0; a.ctl->res[1] = r1; a.ctl->res[2] = r2;          // read by surf@2 (stream order)
-    __hip_atomic_store(&a.ctl->ticket0, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&a.ctl->t0.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (a.lines == 0) {
         const long long s[8] = {a.n, r0, r1, r2, 0, 0, 0, a.pushes};
         for (int k = 0; k < 8; k++) {
@@ -283,13 +261,9 @@ struct SfArgs1 {
     int w, h, P, L, qthr, min_run;
 };
 
-__device__ __forceinline__ long long sf_floor_div(long long a, long long b) {   // b > 0
-    const long long q = a / b;
-    return q - (a % b != 0 && a < 0);
-}
 // the point at pos (1/256 sample) of a line of n samples from Xa to Xb (1/16 pixel), in 1/256 pixel: the shoreline's formula
 __device__ __forceinline__ int sf_point(int Xa, int Xb, long long pos, int n) {
-    return (int)(16ll * Xa + sf_floor_div(16ll * (Xb - Xa) * pos + 128ll * (n - 1), 256ll * (n - 1)));
+    return (int)(16ll * Xa + rc_floor_div(16ll * (Xb - Xa) * pos + 128ll * (n - 1), 256ll * (n - 1)));
 }
 
 // the in-samples of a line as a bit mask: lane u < 16 holds samples 64 u .. 64 u + 63, the others 0.  The mask shifted down by s
@@ -599,15 +573,10 @@ extern "C" int rcflow_surf_open(rc_ctx* ctx, int stream, int w, int h, const rc_
     if (!rc) rc = rc_buf_ensure(n.sums, (size_t)sums);
     if (!rc) rc = rc_buf_ensure(n.out, 64 + RC_SURF_MAX_CHANNELS * sizeof(rc_surf_channel) + (size_t)n_lines * sizeof(rc_surf_line));
     if (!rc) rc = rc_buf_ensure(n.ctl, sizeof(SfCtl));
-    if (!rc) rc = rc_buf_ensure(n.jet, 768);
+    if (!rc) rc = rc_jet_ensure(n.jet, who);
     if (!rc && host.size() && hipMemcpy(n.table.p, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) {
         rc_set_error("%s: the upload of the table failed", who);
         rc = RC_EHIP;
-    }
-    if (!rc) {
-        uint8_t lut[768];
-        rcflow_jet_lut(lut);
-        if (hipMemcpy(n.jet.p, lut, 768, hipMemcpyHostToDevice) != hipSuccess) { rc_set_error("%s: the colour table's upload failed", who); rc = RC_EHIP; }
     }
     return rc_state_install(*s, s->sf, n, rc);
 }

@@ -29,8 +29,8 @@
 
 #include <vector>
 
-#include "rc_device.h"
 #include "rc_host.h"
+#include "rc_reduce.h"
 
 #define TS_ROW (RC_TRANSECTS_MAX_SAMPLES / 4 + 16)   // dwords of a grey row in LDS: the samples and a zero tail the last tasks read
 #define TS_CH 8                                      // transects@0: dwords of the interior a task covers
@@ -316,16 +316,14 @@ __global__ __launch_bounds__(RC_BLOCK) void k_ts_records(const TsRecArgs a) {
         a.sums[(size_t)line * RC_TRANSECTS_SUMS + k] = sm[k];
         if (a.sums2) a.sums2[(size_t)line * RC_TRANSECTS_SUMS + k] = sm[k];
     }
-    if (!(r.flags & (RC_TRANSECTS_EMPTY | RC_TRANSECTS_FLAT))) atomicAdd(&a.ctl->cnt[0], 1u);
-    if (jets) { atomicAdd(&a.ctl->cnt[1], 1u); atomicAdd(&a.ctl->cnt[2], (unsigned)jets); }
-    if (bad) atomicAdd(&a.ctl->cnt[3], (unsigned)bad);
-    __threadfence();                                              // the counts before the ticket
-    last = atomicAdd(&a.ctl->ticket, 1u) == (unsigned)a.L - 1u;
+    if (!(r.flags & (RC_TRANSECTS_EMPTY | RC_TRANSECTS_FLAT))) rc_acc_add(&a.ctl->cnt[0], 1u);
+    if (jets) { rc_acc_add(&a.ctl->cnt[1], 1u); rc_acc_add(&a.ctl->cnt[2], (unsigned)jets); }
+    if (bad) rc_acc_add(&a.ctl->cnt[3], (unsigned)bad);
+    last = rc_ticket_fenced(&a.ctl->ticket, (unsigned)a.L);       // the counts before the ticket
     if (last) {
-        __threadfence();
         long long s[8] = {a.held, a.pairs, 0, 0, 0, 0, a.pushes, 0};
-        for (int k = 0; k < 4; k++) s[2 + k] = atomicExch(&a.ctl->cnt[k], 0u);     // zero for the next push (stream order)
-        atomicExch(&a.ctl->ticket, 0u);
+        for (int k = 0; k < 4; k++) s[2 + k] = rc_acc_take(&a.ctl->cnt[k]);     // zero for the next push (stream order)
+        rc_acc_take(&a.ctl->ticket);
         for (int k = 0; k < 8; k++) {
             a.summary[k] = s[k];
             if (a.summary2) a.summary2[k] = s[k];

@@ -22,8 +22,8 @@
 
 #include <vector>
 
-#include "rc_device.h"
 #include "rc_host.h"
+#include "rc_reduce.h"
 
 #define WV_WAVES 4
 static_assert(RC_BLOCK == 64 * WV_WAVES, "a block is WV_WAVES waves");
@@ -34,8 +34,7 @@ static_assert(RC_BLOCK == 64 * WV_WAVES, "a block is WV_WAVES waves");
 // however many blocks queue for it (4096 blocks on one ticket: 45 us), so a block arrives at the shard of its number modulo
 // WV_SHARDS and only a shard's last block goes on to the top (the two levels of planview@1)
 #define WV_SHARDS 16
-struct WvLine { unsigned ticket; unsigned pad[31]; };
-struct WvCtl { WvLine shard[WV_SHARDS], top, unused; };
+struct WvCtl { RcTicketLine shard[WV_SHARDS], top, unused; };
 static_assert(sizeof(WvCtl) == 128 * (WV_SHARDS + 2), "the cell sums start after eighteen lines");
 
 typedef uint32_t wv_u32u __attribute__((aligned(1)));     // four pixels of a caller's row: no alignment is asked of it
@@ -93,20 +92,9 @@ struct WvCellArgs {
     unsigned nblocks;
 };
 
-__device__ __forceinline__ long long wv_wave_sum(long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ long long wv_add(long long* p, long long v) {
-    return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ long long wv_take(long long* p) {      // read and zero in one operation, where the adds were made
-    return __hip_atomic_exchange(p, 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // true for the last of n arrivals, which leaves the ticket zero for the next push (stream order)
 __device__ __forceinline__ bool wv_arrive(unsigned* ticket, unsigned n) {
-    if (__hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != n - 1u) return false;
+    if (rc_acc_add_old(ticket, 1u) != n - 1u) return false;
     __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return true;
 }
@@ -116,15 +104,15 @@ __device__ __forceinline__ void wv_flush(const WvCellArgs& a, int k, int cxa, in
     for (int cx = cxa; cx <= cxb; cx++) {
         long long t[6];
 #pragma unroll
-        for (int q = 0; q < 6; q++) t[q] = wv_wave_sum(cxl == cx ? v[q] : 0);
+        for (int q = 0; q < 6; q++) t[q] = rc_wave_sum_lane0(cxl == cx ? v[q] : 0ll);
         if ((threadIdx.x & 63) == 0 && t[0]) {
             long long* p = a.cacc + 6 * (((size_t)cy * a.gx + cx) * a.K + k);
             // the old values are asked for and thrown away: an atomic that returns has been performed once the wave's vmcnt
             // has counted it, which the hand-off at the end of the kernel waits for
             long long r[6];
-            r[0] = k == 0 ? wv_add(p, t[0]) : 0;
+            r[0] = k == 0 ? rc_acc_add_old(p, t[0]) : 0;
 #pragma unroll
-            for (int q = 1; q < 6; q++) r[q] = wv_add(p + q, t[q]);
+            for (int q = 1; q < 6; q++) r[q] = rc_acc_add_old(p + q, t[q]);
             asm volatile("" ::"v"(r[0]), "v"(r[1]), "v"(r[2]), "v"(r[3]), "v"(r[4]), "v"(r[5]));
         }
     }
@@ -145,7 +133,7 @@ __device__ void wv_finish(const WvCellArgs& a, unsigned long long* red /* [3] */
 #pragma unroll
         for (int u = 0; u < 16; u++) {
             const int i = i0 + u * RC_BLOCK;
-            t[u] = i < nword ? wv_take(a.cacc + i) : 0;
+            t[u] = i < nword ? rc_acc_take(a.cacc + i) : 0;
         }
 #pragma unroll
         for (int u = 0; u < 16; u++) {
@@ -274,16 +262,10 @@ __global__ __launch_bounds__(RC_BLOCK) void k_wv_cells(const WvCellArgs a) {
         }
     }
     if (cur_cy >= 0) wv_flush(a, k, cxa, cxb, cur_cy, cxl, v);
-    // The hand-off, without a fence (planview@1's reasoning): nothing but atomics passes between blocks, and a release
-    // at agent scope would write back an L2 this launch has dirtied nothing in.  What it needs: the block that draws the last
-    // ticket finds every block's sums.  Every add above returns its old value, so a wave's vmcnt reaches 0 only when its adds have
-    // been performed where atomics of agent scope are performed; the barrier joins the block's waves; then the block's ticket, and
-    // for a shard's last block the top's, each issued after the one before returned.  The last block's exchanges are issued
-    // after its ticket returned (the branch through `last`).
-    // This is an argument about gfx950, not one the HIP memory model makes: relaxed atomics order nothing there.  A port to another
-    // architecture, or a compiler that no longer waits for an atomic's returned value as for a load's, needs ripmap@0's release
-    // before the ticket and acquire after the last one back.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // The hand-off, without a fence: rc_reduce.h says why nothing but the wait is needed on gfx950 and what a port needs instead.
+    // Every add above returned its old value, so a wave's vmcnt reaches 0 only when its adds have been performed; the barrier joins
+    // the block's waves; then the block's ticket, and for a shard's last block the top's, each issued after the one before returned
+    rc_wait_performed();
     __syncthreads();
     if (threadIdx.x == 0) {
         const unsigned bid = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, g = bid % WV_SHARDS;

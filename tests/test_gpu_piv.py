@@ -154,6 +154,20 @@ def test_case_against_the_statement(ctx, name):
         assert abs(rec["dx"].mean() - u) <= 0.05 and abs(rec["dy"].mean() - v) <= 0.05 and not (rec["flags"] & R.EDGE).any()
 
 
+def test_more_cells_than_one_validating_block(ctx):
+    """piv@2 gives a validating block 256 cells, and the launch's last such block adds the blocks' counts up behind the ticket.
+    No case of the statement's has more than 256 cells; 46 x 44 under a window of 8, a range of 2 and a step of 2 has 18 x 17 = 306:
+    two blocks, 256 and 50 valid cells.  Pushes 2 and 3 compute, and the third finds the ticket and the counters zero"""
+    name = "two validating blocks"
+    if name not in _REF:
+        case = R.Case(46, 44, R.Params(8, 2, 2, 1, 0, 0.25, 0.1, 2.0, 2.0), R.drifting_frames(46, 44, 3, 26, [(0, 0), (1, 0), (1, 1)]), {2, 3}, pad=3)
+        _REF[name] = (case,) + R.run_case(case, ctx.jet_lut())
+    case, ref, outs = _REF[name]
+    assert ref.gx * ref.gy == 306 and [int(o["summary"][2]) for _, o, _ in outs] == [306, 306]
+    run(ctx, name)
+    ctx.piv_close()
+
+
 def test_result_does_not_depend_on_which_pushes_computed(ctx):
     """one session computes at every push, one at the marked ones only (pushes with no output between them), on two slots open
     at once: the same bytes at the end"""
