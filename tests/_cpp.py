@@ -19,3 +19,10 @@ def build(name, tmp_path, gxx=False):
     b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
     assert b.returncode == 0, b.stderr[-4000:]
     return exe
+
+
+def run(name, tmp_path, *args, gxx=False, timeout=300):
+    """builds tests/cpp/<name>.cpp, runs it with `args` and holds it to exit status 0 and its "<name>: ok" line; returns its stdout"""
+    r = subprocess.run([build(name, tmp_path, gxx=gxx)] + [str(a) for a in args], capture_output=True, text=True, timeout=timeout)
+    assert r.returncode == 0 and name + ": ok" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+    return r.stdout

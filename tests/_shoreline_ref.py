@@ -334,3 +334,9 @@ def beach(w, h, t, seed=7, period=16, amp=5, foam=False, noise=6):
 def beach_lines(w, h):
     """the issue's lines: horizontal, rows 4, 9, ..., from x = 4 (land) to x = w - 5 (sea), a sample a pixel"""
     return [(4.0, float(y), float(w - 5), float(y), w - 8) for y in range(4, h, 5)]
+
+
+def ragged_lines(w, h):
+    """diagonals with fractional ends, the last row, the last column (the ix1 and iy1 clamps), n = 8 and n = 1024"""
+    return [(1.3, 2.7, w - 1.6, h - 2.2, 33), (0.0, float(h - 1), float(w - 1), float(h - 1), 40), (float(w - 1), 0.0, float(w - 1), float(h - 1), 19),
+            (2.5, h - 1.25, w - 1.0, 0.0, 8), (0.0, 0.0, float(w - 1), float(h - 1), 1024), (0.4, 17.5, w - 1.4, 17.5, 129)]

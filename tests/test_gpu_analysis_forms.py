@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 import torch
 
+from _dev import Padded, same_bits
 from ripcurrents_amd.api import Context, HistState
 
 pytestmark = pytest.mark.gpu
@@ -131,10 +132,6 @@ def _assert_state(st, ost, what):
     assert np.array_equal(st.prop_above_upper, ost.prop_above_upper, equal_nan=True), what + ": prop_above_upper"
 
 
-def _bits(t):
-    return t.view(torch.int32)
-
-
 def _check_clip(ctx, orc, dev, backing, flows):
     """One clip call on a reset slot == the oracle after T fields; a second one without a reset == the oracle after 2 T (the
     fold cleared the partial tables); after histogram_reset, T single calls give the words of the one clip call; the input
@@ -159,7 +156,7 @@ def _check_clip(ctx, orc, dev, backing, flows):
     assert np.array_equal(ctx.histogram_words().cpu().numpy(), words), "T single calls against one clip call"
     st1 = ctx.histogram_read()
     assert np.float32(st1.UPPER) == np.float32(st.UPPER) and np.array_equal(st1.UPPER2d, st.UPPER2d, equal_nan=True)
-    assert torch.equal(_bits(backing), _bits(before)), "the input was written"
+    assert same_bits(_np(backing), _np(before)), "the input was written"
 
 
 # ---------------------------------------------------------------------------- A: sizing
@@ -356,25 +353,16 @@ def _wild_field(seed, w=BW, h=BH):
     return _ref(("wild", seed, w, h), make)
 
 
-def _padded(h, w, ch, dtype, pad, fill, zero=False):
-    """(backing, its [h, w(, ch)] view): rows `pad` pixels longer than the view, the backing filled with `fill`."""
-    big = torch.full((h, w + pad) + ((ch,) if ch else ()), fill, dtype=dtype, device="cuda")
-    view = big[:, :w]
-    if zero:
-        view.zero_()
-    return big, view
-
-
 def _flow_view(f, pad):
-    """The field on the device with rows padded by `pad` sentinel pixels (the whole buffer, the view)."""
-    h, w = f.shape[:2]
-    big, view = _padded(h, w, 2, torch.float32, pad, FSENT)
-    view.copy_(torch.as_tensor(f).cuda())
-    return big, view
+    """The field on the device with rows padded by `pad` sentinel pixels."""
+    return Padded.of(f, pad, FSENT)
 
 
-def _padding_kept(big, w, fill):
-    return bool((big[:, w:] == fill).all())
+def _zeroed(shape, dtype, pad, fill):
+    """An output of zeros in rows `pad` pixels longer and `fill` there."""
+    p = Padded.empty(shape, dtype, pad, fill)
+    p.view.zero_()
+    return p
 
 
 def _eq(a, b):
@@ -418,26 +406,27 @@ def test_capped_classify_accumulate(ctx, orc, pad):
                 rows.append((fc, wc, p2, out, mask, acc[..., 0].copy()))
         return rows
     rows = _ref("classify", make)
-    fbig, fv = _flow_view(f, pad)
-    fbefore = fbig.clone()
+    fl = _flow_view(f, pad)
+    fv, fbefore = fl.view, fl.base.clone()
     ctx.analysis_reset(w, h)
     st = HistState()
     ctx.create_histogram(fv, st)
     _assert_state(st, ost, "histogram of the field")
     for fc, wc, p2, out, mask, acc in rows:
-        o = {n: _padded(h, w, 3, torch.float32, pad, FSENT) for n in ("polar", "waterclass", "out")}
-        o["outmask"] = _padded(h, w, 0, torch.uint8, pad, BSENT)
+        o = {n: Padded.empty((h, w, 3), torch.float32, pad, FSENT) for n in ("polar", "waterclass", "out")}
+        o["outmask"] = Padded.empty((h, w), torch.uint8, pad, BSENT)
         ctx._bind(0)
         args = []
         for n in ("polar", "waterclass", "out", "outmask"):
-            args += [o[n][1].data_ptr(), o[n][1].stride(0) * o[n][1].element_size()]
+            args += [o[n].view.data_ptr(), o[n].view.stride(0) * o[n].view.element_size()]
         assert ctx._lib.rcflow_classify_accumulate_dev(ctx._h, 0, fv.data_ptr(), fv.stride(0) * 4, w, h, fc, 0.5, 0.2, *args) == 0
-        assert _eq(_np(o["waterclass"][1]), wc) and _eq(_np(o["polar"][1]), p2), fc
-        assert _eq(_np(o["out"][1]), out) and _eq(_np(o["outmask"][1]), mask), fc
+        assert _eq(_np(o["waterclass"].view), wc) and _eq(_np(o["polar"].view), p2), fc
+        assert _eq(_np(o["out"].view), out) and _eq(_np(o["outmask"].view), mask), fc
         assert _eq(ctx.accumulator(w, h), acc), fc
-        assert all(_padding_kept(o[n][0], w, FSENT) for n in ("polar", "waterclass", "out")) and _padding_kept(o["outmask"][0], w, BSENT)
+        for n in ("polar", "waterclass", "out", "outmask"):
+            o[n].check(n)
     assert rows[-1][5].reshape(-1)[CAP_ITEMS:].max() >= 2.0          # the accumulator did count in the second pass
-    assert torch.equal(_bits(fbig), _bits(fbefore))
+    assert same_bits(_np(fl.base), _np(fbefore))
 
 
 @PADS
@@ -457,7 +446,8 @@ def test_capped_streamline_field(ctx, orc, pad):
                 res.append((pt, dist))
         return res
     (pt_e, dist_e), (pt_s, dist_s) = _ref("streamline", make)
-    fbig, fv = _flow_view(f, pad)
+    fl = _flow_view(f, pad)
+    fv = fl.view
     ctx.analysis_reset(w, h)
     for _ in range(3):
         ctx.streamline_field(fv, 2.0, 2, UPPER=1.7)
@@ -472,7 +462,7 @@ def test_capped_streamline_field(ctx, orc, pad):
         ctx.streamline_field(fv, 2.0, 2)                  # UPPER < 0: the slot's
     gpt, gdist = ctx.streamline_field_state(w, h)
     assert _eq(gpt, pt_s) and _eq(gdist, dist_s)
-    assert _padding_kept(fbig, w, FSENT)
+    fl.check("the field")
 
 
 @PADS
@@ -487,13 +477,14 @@ def test_capped_get_delta_field(ctx, orc, pad):
                 orc.get_delta_field(ref, f, 2.0, 1.8)
         return ref
     ref = _ref("delta", make)
-    fbig, fv = _flow_view(f, pad)
-    pbig, pt = _padded(h, w, 2, torch.float32, pad, FSENT, zero=True)
+    fl, particles = _flow_view(f, pad), _zeroed((h, w, 2), torch.float32, pad, FSENT)
+    fv, pt = fl.view, particles.view
     ctx._bind(0)
     for _ in range(3):
         assert ctx._lib.rcflow_get_delta_field_dev(ctx._h, 0, pt.data_ptr(), pt.stride(0) * 4, fv.data_ptr(), fv.stride(0) * 4, w, h, 2.0, 1.8) == 0
     assert _eq(_np(pt), ref) and np.nanmax(np.abs(ref.reshape(-1, 2)[CAP_ITEMS:])) > 1.0
-    assert _padding_kept(pbig, w, FSENT) and _padding_kept(fbig, w, FSENT)
+    particles.check("the particles")
+    fl.check("the field")
 
 
 def test_capped_window_mean(ctx, orc):
@@ -530,19 +521,20 @@ def test_capped_colouring(ctx, orc, pad):
     vec, shear = _ref("colour", make)
     gmd = C.c_float(0.0)
     for t in range(2):          # the first frame divides by max_displacement == 0 like the reference
-        fbig, fv = _flow_view(_finite_field(30 + t, 2.0), pad)
-        hbig, hsv = _padded(h, w, 3, torch.uint8, pad, BSENT, zero=True)
+        fl, picture = _flow_view(_finite_field(30 + t, 2.0), pad), _zeroed((h, w, 3), torch.uint8, pad, BSENT)
+        fv, hsv = fl.view, picture.view
         ctx._bind(0)
         assert ctx._lib.rcflow_vector_to_color_dev(ctx._h, 0, fv.data_ptr(), fv.stride(0) * 4, w, h, hsv.data_ptr(), hsv.stride(0), C.byref(gmd)) == 0
         assert gmd.value == vec[t][1] and np.array_equal(_np(hsv), vec[t][0])
-        assert _padding_kept(hbig, w, BSENT) and _padding_kept(fbig, w, FSENT)
+        picture.check("the picture")
+        fl.check("the field")
     gmf = 0.0
     for t in range(2):
-        fbig, fv = _flow_view(_finite_field(40 + t, 2.0), pad)
-        hbig, hsv = _padded(h, w, 3, torch.uint8, pad, BSENT, zero=True)
-        got, gmf = ctx.shearRateToColor(fv, gmf, hsv=hsv)
+        fl, picture = _flow_view(_finite_field(40 + t, 2.0), pad), _zeroed((h, w, 3), torch.uint8, pad, BSENT)
+        got, gmf = ctx.shearRateToColor(fl.view, gmf, hsv=picture.view)
         assert gmf == shear[t][1] and gmf > 0 and np.array_equal(_np(got), shear[t][0])
-        assert _padding_kept(hbig, w, BSENT) and _padding_kept(fbig, w, FSENT)
+        picture.check("the picture")
+        fl.check("the field")
 
 
 # the oracle's mean magnitude of _finite_field(4, 1.2) against the float64 sum of the same magnitudes, measured on the CPU
@@ -576,10 +568,10 @@ def test_capped_postops(ctx, orc, pad):
     for gpu, ref, bar in ((ctx.subtructAverage, ref_avg, 2.4e-7 * max(1.0, np.abs(ref_avg).max())),
                           (ctx.stabilizer, ref_stab, 2.4e-7 * max(1.0, np.abs(ref_stab).max())),
                           (ctx.subtructMeanMagnitude, ref_mm, 4 * MEAN_MAG_REF_ERR * mean64 + 1e-6)):
-        fbig, fv = _flow_view(f, pad)
-        got = _np(gpu(fv))
+        fl = _flow_view(f, pad)
+        got = _np(gpu(fl.view))
         err = np.abs(got - ref)
         print("[postops] %s pad %d: max error %.3g (first pass %.3g, second pass %.3g), bar %.3g" % (
             gpu.__name__, pad, err.max(), err.reshape(-1, 2)[:CAP_ITEMS].max(), err.reshape(-1, 2)[CAP_ITEMS:].max(), bar))
         assert err.max() <= bar, gpu.__name__
-        assert _padding_kept(fbig, w, FSENT)
+        fl.check("the field")

@@ -1,6 +1,4 @@
 """rc::Kinematics (include/rcflow_module.hpp) on the rotation field, in the program tests/cpp/test_kinematics.cpp."""
-import subprocess
-
 import pytest
 
 import _cpp
@@ -11,6 +9,4 @@ pytestmark = pytest.mark.gpu
 def test_cpp_kinematics_on_the_rotation_field(tmp_path):
     """compiled with the flags of tests/cpp's test_module: the program pushes the analytic rotation field through the class and
     holds planes, mask, picture, records, sums and summary to numbers it computes itself"""
-    exe = _cpp.build("test_kinematics", tmp_path)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "test_kinematics: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    _cpp.run("test_kinematics", tmp_path)

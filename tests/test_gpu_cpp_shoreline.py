@@ -1,6 +1,4 @@
 """rc::Shoreline (include/rcflow_module.hpp) on a step picture, in the program tests/cpp/test_shoreline.cpp."""
-import subprocess
-
 import pytest
 
 import _cpp
@@ -11,6 +9,4 @@ pytestmark = pytest.mark.gpu
 def test_cpp_shoreline_on_the_step_picture(tmp_path):
     """compiled with the flags of tests/cpp's test_module: the program pushes a sand / water step through the class and holds mask,
     plane, records, summary and ring to numbers it computes itself"""
-    exe = _cpp.build("test_shoreline", tmp_path)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "test_shoreline: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    _cpp.run("test_shoreline", tmp_path)

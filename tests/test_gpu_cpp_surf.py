@@ -1,6 +1,4 @@
 """rc::Surf (include/rcflow_module.hpp) on a two-level picture with one gap, in the program tests/cpp/test_surf.cpp."""
-import subprocess
-
 import pytest
 
 import _cpp
@@ -11,6 +9,4 @@ pytestmark = pytest.mark.gpu
 def test_cpp_surf_on_the_band_with_a_gap(tmp_path):
     """compiled with the flags of tests/cpp's test_module: the program alternates a band with a hole and plain water through the
     class and holds the six pictures, the line records, the channel and the summary to numbers it computes itself"""
-    exe = _cpp.build("test_surf", tmp_path)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "test_surf: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    _cpp.run("test_surf", tmp_path)

@@ -1,6 +1,4 @@
 """rc::Transects (include/rcflow_module.hpp) against the C ABI, in the program tests/cpp/test_transects.cpp."""
-import subprocess
-
 import pytest
 
 import _cpp
@@ -11,6 +9,4 @@ pytestmark = pytest.mark.gpu
 def test_cpp_transects_against_the_c_abi(tmp_path):
     """compiled with the flags of tests/cpp's test_module: the program pushes frames it makes itself through the class and through
     the C ABI on a second context, and compares every output byte for byte"""
-    exe = _cpp.build("test_transects", tmp_path)
-    r = subprocess.run([exe, "9"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "test_transects: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    _cpp.run("test_transects", tmp_path, 9)

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+from _dev import EINVAL, ESIZE, ESTATE, SENTINEL, raw
 from ripcurrents_amd import synth
 from ripcurrents_amd._lib import FarnebackParams, FitParams, FrameLoop
 from ripcurrents_amd.api import HistState
@@ -25,8 +26,6 @@ pytestmark = pytest.mark.gpu
 
 W, H = 33, 23
 SW, SH = 24, 22                       # rcflow_shear_rate_to_color_dev
-EINVAL, ESIZE, ESTATE = -1, -5, -6
-SENTINEL = 0xA5
 FS, S1, S3, S12 = W * 8, W, W * 3, W * 12    # the bytes of a row: float2, 8U, 8UC3, 32FC3
 
 # one entry point: its arguments after (ctx, stream) in order, and the refused variations of them.  A variation is
@@ -186,7 +185,7 @@ def _table(dev_in, dev_out, host_in, host_out):
 def refused_calls(ctx, table):
     """Makes every refused call of the table: (entry point, changes, named argument, expected code, returned code, text,
     whether the text is still the planted one)."""
-    lib, hdl = ctx._lib, ctx._h
+    lib, hdl = raw(ctx)
     rows = []
     for e in table:
         fn = getattr(lib, e.name)
@@ -218,7 +217,7 @@ def buffers(ctx):
 def primed_refusals(ctx, dev_in, dev_out):
     """The refusals that come after state: primes the stream, then the batch, acquires a frame buffer, and makes the refused
     calls of each state in between.  The accepted calls queue work on dev_in only.  Rows as refused_calls gives them."""
-    lib, hdl = ctx._lib, ctx._h
+    lib, hdl = raw(ctx)
     I, O = dev_in, dev_out
     p = FarnebackParams(0.5, 1, 3, 1, 5, 1.1, 0)
     P = C.byref(p)

@@ -8,12 +8,11 @@ import pytest
 import torch
 
 import _framestab_ref as R
+from _dev import EINVAL, ESIZE, ESTATE
 from ripcurrents_amd._lib import RcflowError
 from ripcurrents_amd.api import Context
 
 pytestmark = pytest.mark.gpu
-
-EINVAL, ESIZE, ESTATE = -1, -5, -6
 
 
 def _patches(w, h, d, seed=3):

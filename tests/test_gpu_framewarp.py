@@ -10,13 +10,13 @@ import torch
 
 import _framestab_ref as S
 import _framewarp_ref as W
+from _dev import EINVAL, ESIZE, ESTATE
 from ripcurrents_amd import synth
 from ripcurrents_amd._lib import RcflowError
 from ripcurrents_amd.api import Context
 
 pytestmark = pytest.mark.gpu
 
-EINVAL, ESIZE, ESTATE = -1, -5, -6
 SIZES = ((640, 480), (333, 251), (1920, 1080), (5, 3), (4, 1))
 
 

@@ -2,8 +2,6 @@
 and mask bit for bit, the summary field for field, ftle within one unit in the last place (its logarithm is the device's, in
 double, rounded to float once), the picture equal where ftle is and one JET entry off at most elsewhere."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,63 +10,24 @@ import torch
 import _cpp
 import _ftle_ref as F
 import _regions_ref as R
+from _dev import EINVAL, ESIZE, ESTATE, NULL as null, SENTINEL, Outputs, Padded, bits, ordered, ptr, raw
 from ripcurrents_amd._lib import RC_FTLE_LAUNCHES, FtleParams, RcflowError
 from ripcurrents_amd.api import FTLE_SUMMARY
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EINVAL, ESIZE, ESTATE = -1, -5, -6
 f32 = np.float32
-SENTINEL = 0xA5
 NAMES = {F.FORWARD: "forward", F.BACKWARD: "backward"}
-SHAPES = (("map", (2,), torch.float32), ("steps", (), torch.int32), ("lam", (), torch.float32), ("ftle", (), torch.float32),
-          ("mask", (), torch.uint8), ("vis", (3,), torch.uint8))
 
 
-def padded(shape, dtype, pad):
-    """A device tensor of `shape` that is a view into rows `pad` pixels longer, the whole filled with a sentinel."""
-    full = (shape[0], shape[1] + pad) + tuple(shape[2:])
-    base = torch.empty(full, dtype=dtype, device="cuda")
-    base.view(torch.uint8).fill_(SENTINEL)
-    return base, base[:, :shape[1]]
-
-
-class Outputs:
-    def __init__(self, w, h, pad=0):
-        self.pad, self.base, self.t = pad, {}, {}
-        for name, tail, dtype in SHAPES:
-            self.base[name], self.t[name] = padded((h, w) + tail, dtype, pad)
-        self.summary = torch.full((8,), -1, dtype=torch.int64, device="cuda")
-
-    def kw(self):
-        return dict(self.t, summary=self.summary)
-
-    def host(self):
-        out = {k: v.cpu().numpy() for k, v in self.t.items()}
-        out["summary"] = self.summary.cpu().numpy()
-        if self.pad:
-            for k, b in self.base.items():
-                assert (b[:, b.shape[1] - self.pad:].contiguous().view(torch.uint8) == SENTINEL).all(), "row padding of %s was written" % k
-        return out
+def outputs(w, h, pad=0):
+    f, b = torch.float32, torch.uint8
+    return Outputs({"map": ((h, w, 2), f), "steps": ((h, w), torch.int32), "lam": ((h, w), f), "ftle": ((h, w), f), "mask": ((h, w), b),
+                    "vis": ((h, w, 3), b)}, dict(summary=((8,), torch.int64, -1)), pad)
 
 
 def dev_field(f, pad=0):
-    if not pad:
-        return torch.as_tensor(np.ascontiguousarray(f)).cuda()
-    base, v = padded(f.shape, torch.float32, pad)
-    v.copy_(torch.as_tensor(np.ascontiguousarray(f)).cuda())
-    return v
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def ordered(a):
-    """float32 -> integers in the floats' order"""
-    i = np.ascontiguousarray(a).view(np.int32).astype(np.int64)
-    return np.where(i < 0, -(i & 0x7FFFFFFF), i)
+    return Padded.of(f, pad).view
 
 
 def compare(got, read, want, lut, what):
@@ -97,7 +56,7 @@ def run(ctx, fields, window, direction, spacing=1, threshold=0.15, vis_max=0.4, 
     if reopen:
         ctx.ftle_open(w, h, window=window, direction=NAMES[direction], dt=dt, spacing=spacing, threshold=threshold, vis_max=vis_max, stream=stream)
     ref = F.FtleRef(w, h, lut, window, direction, dt, spacing, threshold, vis_max)
-    out = Outputs(w, h, pad)
+    out = outputs(w, h, pad)
     want = None
     for t, f in enumerate(fields):
         last = t == len(fields) - 1
@@ -240,7 +199,7 @@ def test_outputs_are_optional_and_launches_counted(ctx, mixed):
     ctx.profile_enable(False)
     assert np.array_equal(only.cpu().numpy(), want["mask"])
     assert [ctx.ftle_read()[k] for k in FTLE_SUMMARY] == [int(v) for v in want["summary"]]
-    out = Outputs(w, h)
+    out = outputs(w, h)
     ctx.ftle_push(dev_field(mixed[4]), **out.kw())                # does not depend on which earlier pushes computed
     compare(out.host(), ctx.ftle_read(), ref.push(mixed[4]), lut, "(after pushes without outputs)")
     summ = torch.zeros(8, dtype=torch.int64, device="cuda")
@@ -259,8 +218,7 @@ def test_refusals_and_lifecycle(ctx, mixed):
         with pytest.raises(RcflowError) as e:
             call()
         assert e.value.code == ESTATE and str(e.value).split(": ", 1)[1]
-    lib, hdl = ctx._lib, ctx._h
-    null = C.c_void_p(None)
+    lib, hdl = raw(ctx)
     assert lib.rcflow_ftle_push_dev(hdl, 0, null, 0, null, 0, null, 0, null, 0, null, 0, null, 0, null, 0, null) == ESTATE
     for bad in (dict(window=0), dict(window=257), dict(direction=2), dict(direction=-1), dict(dt=0.0), dict(dt=-1.0), dict(dt=float("inf")),
                 dict(dt=float("nan")), dict(spacing=0), dict(spacing=17), dict(threshold=float("nan")), dict(threshold=float("inf")),
@@ -293,9 +251,8 @@ def test_refusals_and_lifecycle(ctx, mixed):
     assert e.value.code == ESIZE and ctx.ftle_info() == before
 
     d = dev_field(mixed[2])
-    o = Outputs(w, h)
+    o = outputs(w, h)
     big = torch.zeros(h * w * 8 + 256, dtype=torch.uint8, device="cuda")
-    ptr = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
 
     def push(flow=None, step=8 * w, map=(null, 0), steps=(null, 0), lam=(null, 0), ftle=(null, 0), mask=(null, 0), vis=(null, 0), summ=null, slot=0):
         fp = ptr(d) if flow is None else flow
@@ -373,7 +330,7 @@ def test_two_slots_on_two_streams(ctx, mixed):
     ctx.ftle_open(131, 70, window=3, direction="backward", threshold=0.15, vis_max=0.4, stream=0)
     ctx.ftle_open(67, 45, window=2, direction="forward", spacing=2, threshold=0.1, vis_max=0.3, stream=1)
     ra, rb = F.FtleRef(131, 70, lut, 3, F.BACKWARD, 1.0, 1, 0.15, 0.4), F.FtleRef(67, 45, lut, 2, F.FORWARD, 1.0, 2, 0.1, 0.3)
-    oa, ob = Outputs(131, 70), Outputs(67, 45)
+    oa, ob = outputs(131, 70), outputs(67, 45)
     torch.cuda.synchronize()                                      # the outputs were filled on the default stream
     for a, b in zip(mixed, fb):
         da, db = dev_field(a), dev_field(b)
@@ -417,11 +374,8 @@ def test_mask_goes_straight_into_regions(ctx, mixed):
 def test_cpp_ftle_against_the_statement(ctx, tmp_path):
     """rc::Ftle (include/rcflow_module.hpp) compiled with the flags of tests/cpp's test_module and run on fields it makes
     itself from integers (exact in float, so this file makes the same ones); the summaries it prints equal the statement's."""
-    exe = _cpp.build("test_ftle", tmp_path)
     n = 7
-    r = subprocess.run([exe, str(n)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "test_ftle: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
-    lines = [l.split() for l in r.stdout.splitlines() if l.startswith("push ")]
+    lines = [l.split() for l in _cpp.run("test_ftle", tmp_path, n).splitlines() if l.startswith("push ")]
     assert len(lines) == n
     w, h = 67, 45
     ref = F.FtleRef(w, h, ctx.jet_lut(), 4, F.BACKWARD, 1.0, 2, 0.05, 0.25)

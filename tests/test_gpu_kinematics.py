@@ -9,59 +9,27 @@ import torch
 
 import _kinematics_ref as K
 import _regions_ref as R
+from _dev import EINVAL, ESIZE, ESTATE, NULL as null, SENTINEL, Outputs, Padded, bits, ptr, raw
 from ripcurrents_amd._lib import RC_KINEMATICS_LAUNCHES, KinematicsParams, RcflowError
 from ripcurrents_amd.api import KINEMATICS_CELL_DTYPE, KINEMATICS_SUMMARY, Kinematics
 
 pytestmark = pytest.mark.gpu
 
-EINVAL, ESIZE, ESTATE = -1, -5, -6
-f32 = np.float32
-SENTINEL = 0xA5
-SHAPES = (("omega", (), torch.float32), ("div", (), torch.float32), ("ow", (), torch.float32), ("mask", (), torch.uint8),
-          ("vis", (3,), torch.uint8))
 FLOATS = ("mean_vorticity", "circulation", "mean_divergence", "enstrophy", "mean_ow", "circulation_cw", "circulation_ccw")
 
 
-def padded(shape, dtype, pad):
-    """A device tensor of `shape` that is a view into rows `pad` pixels longer, the whole filled with a sentinel."""
-    full = (shape[0], shape[1] + pad) + tuple(shape[2:])
-    base = torch.empty(full, dtype=dtype, device="cuda")
-    base.view(torch.uint8).fill_(SENTINEL)
-    return base, base[:, :shape[1]]
+def views(d):
+    d["cells"], d["sums"] = d["cells"].view(KINEMATICS_CELL_DTYPE), d["sums"].reshape(-1, K.SUMS)
 
 
-class Outputs:
-    def __init__(self, w, h, gx, gy, pad=0):
-        self.pad, self.base, self.t = pad, {}, {}
-        for name, tail, dtype in SHAPES:
-            self.base[name], self.t[name] = padded((h, w) + tail, dtype, pad)
-        self.t["cells"] = torch.full((gy * gx * 48,), SENTINEL, dtype=torch.uint8, device="cuda")
-        self.t["sums"] = torch.full((gy * gx * K.SUMS,), -1, dtype=torch.int64, device="cuda")
-        self.t["summary"] = torch.full((8,), -1, dtype=torch.int64, device="cuda")
-
-    def kw(self, only=None):
-        return {k: v for k, v in self.t.items() if only is None or k in only}
-
-    def host(self):
-        out = {k: v.cpu().numpy() for k, v in self.t.items()}
-        out["cells"] = out["cells"].view(KINEMATICS_CELL_DTYPE)
-        out["sums"] = out["sums"].reshape(-1, K.SUMS)
-        if self.pad:
-            for k, b in self.base.items():
-                assert (b[:, b.shape[1] - self.pad:].contiguous().view(torch.uint8) == SENTINEL).all(), "row padding of %s was written" % k
-        return out
+def outputs(w, h, gx, gy, pad=0):
+    f, b, i64 = torch.float32, torch.uint8, torch.int64
+    return Outputs(dict(omega=((h, w), f), div=((h, w), f), ow=((h, w), f), mask=((h, w), b), vis=((h, w, 3), b)),
+                   dict(cells=((gy * gx * 48,), b, None), sums=((gy * gx * K.SUMS,), i64, -1), summary=((8,), i64, -1)), pad, views)
 
 
 def dev_field(f, pad=0):
-    if not pad:
-        return torch.as_tensor(np.ascontiguousarray(f)).cuda()
-    base, v = padded(f.shape, torch.float32, pad)
-    v.copy_(torch.as_tensor(np.ascontiguousarray(f)).cuda())
-    return v
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
+    return Padded.of(f, pad).view
 
 
 def compare_one(name, got, want, what):
@@ -115,11 +83,11 @@ def test_case_against_the_statement(ctx, cases, wanted, name, pad):
     f, p = cases[name]
     h, w = f.shape[:2]
     open_case(ctx, f, p)
-    out = Outputs(w, h, p["grid_x"], p["grid_y"], pad)
+    out = outputs(w, h, p["grid_x"], p["grid_y"], pad)
     ctx.kinematics_push(dev_field(f, pad), **out.kw())
     compare(out.host(), ctx.kinematics_read(), wanted[name], "in case %s" % name)
     # a second push of the same field gives the same: every counter was left zero
-    out2 = Outputs(w, h, p["grid_x"], p["grid_y"], pad)
+    out2 = outputs(w, h, p["grid_x"], p["grid_y"], pad)
     ctx.kinematics_push(dev_field(f, pad), **out2.kw())
     want2 = dict(wanted[name], summary=wanted[name]["summary"].copy())
     want2["summary"][6] = 2
@@ -147,7 +115,7 @@ def test_each_output_alone_and_a_push_with_none(ctx, cases, wanted):
     ctx.profile_reset()
     n = 3
     for name in ("omega", "div", "ow", "mask", "vis", "cells", "sums", "summary"):
-        out = Outputs(w, h, p["grid_x"], p["grid_y"])
+        out = outputs(w, h, p["grid_x"], p["grid_y"])
         ctx.kinematics_push(d, **out.kw(only=(name,)))
         n += 1
         got = out.host()
@@ -188,7 +156,7 @@ def test_set_acts_from_the_next_push_and_reset_keeps_it(ctx, cases, wanted):
     h, w = f.shape[:2]
     lut = ctx.jet_lut()
     open_case(ctx, f, p)
-    out = Outputs(w, h, p["grid_x"], p["grid_y"])
+    out = outputs(w, h, p["grid_x"], p["grid_y"])
     d = dev_field(f)
     ctx.kinematics_push(d, **out.kw())
     compare(out.host(), ctx.kinematics_read(), wanted["surf"], "before set")
@@ -220,8 +188,7 @@ def test_refusals_and_lifecycle(ctx, cases, wanted):
         with pytest.raises(RcflowError) as e:
             call()
         assert e.value.code == ESTATE and str(e.value).split(": ", 1)[1]
-    lib, hdl = ctx._lib, ctx._h
-    null = C.c_void_p(None)
+    lib, hdl = raw(ctx)
     assert lib.rcflow_kinematics_push_dev(hdl, 0, null, 0, null, 0, null, 0, null, 0, null, 0, null, 0, null, null, null) == ESTATE
     nan, inf = float("nan"), float("inf")
     for bad in (dict(radius=-1), dict(radius=9), dict(sigma=0.0), dict(sigma=nan), dict(sigma=inf), dict(spacing=0), dict(spacing=9),
@@ -253,7 +220,7 @@ def test_refusals_and_lifecycle(ctx, cases, wanted):
     open_case(ctx, f, good)
     assert lib.rcflow_kinematics_info(hdl, 0, None) == EINVAL     # no buffer
     d = dev_field(f)
-    o = Outputs(w, h, good["grid_x"], good["grid_y"])
+    o = outputs(w, h, good["grid_x"], good["grid_y"])
     ctx.kinematics_push(d, **o.kw())
     before = ctx.kinematics_info()
     assert (before["w"], before["h"], before["radius"], before["spacing"], before["margin"], before["relative"], before["pushes"]) == (w, h, 3, 2, 5, True, 1)
@@ -266,7 +233,6 @@ def test_refusals_and_lifecycle(ctx, cases, wanted):
     assert e.value.code == ESIZE and ctx.kinematics_info() == before
 
     big = torch.zeros(h * w * 8 + 256, dtype=torch.uint8, device="cuda")
-    ptr = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
 
     def push(flow=None, step=8 * w, omega=(null, 0), div=(null, 0), ow=(null, 0), mask=(null, 0), vis=(null, 0), cells=null, sums=null,
              summ=null, slot=0):
@@ -319,7 +285,7 @@ def test_refusals_and_lifecycle(ctx, cases, wanted):
     f3, p3 = cases["no_smoothing"]
     open_case(ctx, f3, p3)
     assert ctx.kinematics_info()["w"] == 37 and ctx.kinematics_info()["pushes"] == 0
-    o3 = Outputs(37, 29, 37, 29)
+    o3 = outputs(37, 29, 37, 29)
     ctx.kinematics_push(dev_field(f3), **o3.kw())
     compare(o3.host(), ctx.kinematics_read(), wanted["no_smoothing"], "(after a re-open)")
     ctx.kinematics_close()
@@ -330,8 +296,8 @@ def test_two_slots(ctx, cases, wanted):
     (fa, pa), (fb, pb) = cases["surf"], cases["sliver_row"]
     open_case(ctx, fa, pa, stream=0)
     open_case(ctx, fb, pb, stream=1)
-    oa = Outputs(fa.shape[1], fa.shape[0], pa["grid_x"], pa["grid_y"])
-    ob = Outputs(fb.shape[1], fb.shape[0], pb["grid_x"], pb["grid_y"])
+    oa = outputs(fa.shape[1], fa.shape[0], pa["grid_x"], pa["grid_y"])
+    ob = outputs(fb.shape[1], fb.shape[0], pb["grid_x"], pb["grid_y"])
     ctx.kinematics_push(dev_field(fa), stream=0, **oa.kw())
     ctx.kinematics_push(dev_field(fb), stream=1, **ob.kw())
     compare(oa.host(), ctx.kinematics_read(stream=0), wanted["surf"], "(slot 0)")
@@ -346,7 +312,7 @@ def test_product_object_holds_its_arguments_to_the_session(ctx, cases, wanted):
     h, w = f.shape[:2]
     with Kinematics(ctx, w, h, **p) as kn:
         assert kn.info()["margin"] == 3 and kn.info()["relative"] is False
-        out = Outputs(w, h, p["grid_x"], p["grid_y"])
+        out = outputs(w, h, p["grid_x"], p["grid_y"])
         kn.push(dev_field(f), **out.kw())
         compare(out.host(), kn.read(), wanted["pair"], "(through api.Kinematics)")
         for bad in (dict(omega=torch.zeros((h, w + 1), dtype=torch.float32, device="cuda")),

@@ -2,8 +2,6 @@
 push: history, orientation, mask and picture bit for bit; every cell's and the frame's record field for field (the angle is
 a double computed from equal integers by the stated operations, so it is equal too); the silhouette's pixel count."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,52 +10,24 @@ import torch
 import _cpp
 import _motion_ref as M
 import _tracers_ref as TR
+from _dev import EINVAL, ESIZE, ESTATE, NULL as null, SENTINEL, Outputs, Padded, ptr, raw, same_bits
 from ripcurrents_amd._lib import RC_MOTION_LAUNCHES, MotionParams, RcflowError
 from ripcurrents_amd.api import DRAW_PRIM_DTYPE, MOTION_CELL_DTYPE
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EINVAL, ESIZE, ESTATE = -1, -5, -6
 f32 = np.float32
 BAR = dict(diff_threshold=30, duration=8, delta1=0.5, delta2=2.5)
 TEX = dict(diff_threshold=12, duration=6, delta1=0.5, delta2=2.5)
-SENTINEL = 0xA5
 
 
-def padded(shape, dtype, pad):
-    """A device tensor of `shape` that is a view into rows `pad` pixels longer, the whole filled with a sentinel."""
-    full = (shape[0], shape[1] + pad) + tuple(shape[2:])
-    base = torch.empty(full, dtype=dtype, device="cuda")
-    base.view(torch.uint8).fill_(SENTINEL)
-    return base, base[:, :shape[1]]
+def views(d):
+    d["cells"], d["frame"] = d["cells"].view(MOTION_CELL_DTYPE), d["frame"].view(MOTION_CELL_DTYPE)[0]
 
 
-class Outputs:
-    def __init__(self, w, h, grid, pad=0):
-        self.pad = pad
-        self.base, self.t = {}, {}
-        for name, shape, dtype in (("mhi", (h, w), torch.float32), ("orient", (h, w), torch.float32), ("mask", (h, w), torch.uint8),
-                                   ("vis", (h, w, 3), torch.uint8)):
-            self.base[name], self.t[name] = padded(shape, dtype, pad)
-        self.cells = torch.zeros(grid[0] * grid[1] * 40, dtype=torch.uint8, device="cuda")
-        self.frame = torch.zeros(40, dtype=torch.uint8, device="cuda")
-
-    def kw(self):
-        return dict(mhi=self.t["mhi"], orient=self.t["orient"], mask=self.t["mask"], vis=self.t["vis"], cells=self.cells, frame=self.frame)
-
-    def host(self):
-        out = {k: v.cpu().numpy() for k, v in self.t.items()}
-        out["cells"] = self.cells.cpu().numpy().view(MOTION_CELL_DTYPE)
-        out["frame"] = self.frame.cpu().numpy().view(MOTION_CELL_DTYPE)[0]
-        if self.pad:
-            for k, b in self.base.items():
-                assert (b[:, b.shape[1] - self.pad:].contiguous().view(torch.uint8) == SENTINEL).all(), "row padding of %s was written" % k
-        return out
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
+def outputs(w, h, grid, pad=0):
+    return Outputs(dict(mhi=((h, w), torch.float32), orient=((h, w), torch.float32), mask=((h, w), torch.uint8), vis=((h, w, 3), torch.uint8)),
+                   dict(cells=((grid[0] * grid[1] * 40,), torch.uint8, 0), frame=((40,), torch.uint8, 0)), pad, views)
 
 
 def records_equal(got, want, what):
@@ -83,11 +53,7 @@ def compare(read, out, want, what):
 
 
 def dev_frame(f, pad=0):
-    if not pad:
-        return torch.as_tensor(f).cuda()
-    base, v = padded(f.shape, torch.uint8, pad)
-    v.copy_(torch.as_tensor(f).cuda())
-    return v
+    return Padded.of(f, pad).view
 
 
 def run(ctx, orc, frames, prm, grid=(1, 1), stamps=None, pad=0, stream=0, reopen=True, fresh=False):
@@ -96,7 +62,7 @@ def run(ctx, orc, frames, prm, grid=(1, 1), stamps=None, pad=0, stream=0, reopen
     if reopen:
         ctx.motion_open(w, h, grid=grid, fresh=fresh, stream=stream, **prm)
     ref = M.MotionRef(w, h, orc.fast_atan2_deg, grid=grid, fresh=fresh, **prm)
-    out = Outputs(w, h, grid, pad)
+    out = outputs(w, h, grid, pad)
     want = None
     for t, f in enumerate(frames):
         ts = None if stamps is None else stamps[t]
@@ -159,7 +125,7 @@ def test_fresh_equals_global_orientation_and_a_reopened_session(ctx, orc):
     frames = M.texture_clip(w, h, 4, step=2)
     prm = dict(diff_threshold=30, duration=1.0, delta1=0.25, delta2=1.0)        # the reference's numbers
     ctx.motion_open(w, h, grid=(1, 1), fresh=True, **prm)
-    out = Outputs(w, h, (1, 1))
+    out = outputs(w, h, (1, 1))
     ctx.motion_push(dev_frame(frames[0]))
     for a, b in zip(frames, frames[1:]):
         ctx.motion_push(dev_frame(b), **out.kw())
@@ -170,7 +136,7 @@ def test_fresh_equals_global_orientation_and_a_reopened_session(ctx, orc):
         assert set(np.unique(fresh["vis"])) <= {0, 255} and set(np.unique(fresh["mhi"])) <= {f32(0), f32(1)}
         # a session with a history, re-opened before the pair, stamps 0 and 1
         ctx.motion_open(w, h, grid=(1, 1), stream=1, **prm)
-        out2 = Outputs(w, h, (1, 1))
+        out2 = outputs(w, h, (1, 1))
         ctx.motion_push(dev_frame(a), timestamp=0.0, stream=1)
         ctx.motion_push(dev_frame(b), timestamp=1.0, stream=1, **out2.kw())
         again, aread = out2.host(), ctx.motion_read(stream=1)
@@ -195,7 +161,7 @@ def test_null_outputs_still_advance_the_state(ctx, orc):
         ctx.motion_push(dev_frame(f))                           # every output pointer NULL
         want = ref.push(f)
         compare(ctx.motion_read(), None, want, "(no outputs)")
-    out = Outputs(97, 61, (7, 5))
+    out = outputs(97, 61, (7, 5))
     ctx.motion_push(dev_frame(frames[5]), **out.kw())
     compare(ctx.motion_read(), out.host(), ref.push(frames[5]), "(outputs after five pushes without)")
     ctx.motion_close()
@@ -225,7 +191,7 @@ def test_reopen_replaces_and_a_refused_reopen_keeps_the_state(ctx, orc):
         ctx.motion_open(4000, 2160, **TEX)
     assert e.value.code == ESIZE
     assert ctx.motion_info() == before
-    out = Outputs(97, 61, (7, 5))
+    out = outputs(97, 61, (7, 5))
     ctx.motion_push(dev_frame(frames[3]), **out.kw())           # the old state still works, and continues
     compare(ctx.motion_read(), out.host(), ref.push(frames[3]), "(after refused re-opens)")
     run(ctx, orc, M.texture_clip(64, 48, 3), TEX, grid=(2, 2))  # another size replaces it
@@ -241,7 +207,7 @@ def test_two_slots_on_two_streams(ctx, orc):
     ctx.motion_open(67, 45, grid=(3, 2), stream=1, **BAR)
     ra = M.MotionRef(97, 61, orc.fast_atan2_deg, grid=(7, 5), **TEX)
     rb = M.MotionRef(67, 45, orc.fast_atan2_deg, grid=(3, 2), **BAR)
-    oa, ob = Outputs(97, 61, (7, 5)), Outputs(67, 45, (3, 2))
+    oa, ob = outputs(97, 61, (7, 5)), outputs(67, 45, (3, 2))
     torch.cuda.synchronize()                                    # the outputs were filled on the default stream
     for a, b in zip(fa, fb):
         with torch.cuda.stream(s0):
@@ -270,7 +236,7 @@ def test_every_refusal_returns_its_code_and_queues_nothing(ctx, orc):
         with pytest.raises(RcflowError) as e:
             ctx.motion_open(**dict(dict(TEX, w=w, h=h), **bad))
         assert e.value.code == EINVAL and str(e.value).split(": ", 1)[1], bad
-    lib, hdl = ctx._lib, ctx._h
+    lib, hdl = raw(ctx)
     p = MotionParams(diff_threshold=12, duration=6.0, delta1=0.5, delta2=2.5, grid_x=1, grid_y=1, flags=2)
     assert lib.rcflow_motion_open(hdl, 0, w, h, C.byref(p)) == EINVAL             # unknown flag bits
     assert lib.rcflow_motion_open(hdl, 0, w, h, None) == EINVAL
@@ -282,14 +248,12 @@ def test_every_refusal_returns_its_code_and_queues_nothing(ctx, orc):
     frames = M.texture_clip(w, h, 4)
     ref, _ = run(ctx, orc, frames[:2], TEX, grid=(7, 5), stamps=[1.0, 2.0])
     g = dev_frame(frames[2])
-    out = Outputs(w, h, (7, 5))
-    null = C.c_void_p(None)
+    out = outputs(w, h, (7, 5))
 
     def push(gray=None, step=w, ts=3.0, mhi=(null, 0), orient=(null, 0), mask=(null, 0), vis=(null, 0), cells=null, frame=null):
-        gp = C.c_void_p(g.data_ptr()) if gray is None else gray
+        gp = ptr(g) if gray is None else gray
         return lib.rcflow_motion_push_dev(hdl, 0, gp, step, ts, mhi[0], mhi[1], orient[0], orient[1], mask[0], mask[1], vis[0], vis[1], cells, frame)
 
-    ptr = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
     big = torch.zeros(h * w * 4 + 64, dtype=torch.uint8, device="cuda")
     refused = [
         push(ts=2.0), push(ts=1.5), push(ts=float("nan")), push(ts=float("inf")), push(ts=-2.0), push(ts=2.0 ** 24 + 2),   # the timestamp rules
@@ -354,7 +318,7 @@ def test_profile_and_launch_count(ctx):
     frames = [dev_frame(f) for f in M.texture_clip(320, 240, 4)]
     ctx.motion_open(320, 240, grid=(10, 8), **TEX)
     assert ctx.motion_info()["launches_per_push"] == RC_MOTION_LAUNCHES <= 3
-    out = Outputs(320, 240, (10, 8))
+    out = outputs(320, 240, (10, 8))
     ctx.profile_enable(True)
     ctx.profile_reset()
     for k, f in enumerate(frames):
@@ -400,11 +364,9 @@ def test_primitives_and_drawing(ctx, orc):
 def test_cpp_motion_against_the_statement(ctx, orc, tmp_path):
     """rc::MotionTemplates (include/rcflow_module.hpp) compiled with the flags of tests/cpp's test_module and run on the +x bar;
     the records it prints equal the numpy statement's, and the angle is 0."""
-    exe = _cpp.build("test_motion", tmp_path)
     n = 12
-    r = subprocess.run([exe, str(n)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "test_motion: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
-    lines = [l.split() for l in r.stdout.splitlines() if l.startswith("push ")]
+    stdout = _cpp.run("test_motion", tmp_path, n)
+    lines = [l.split() for l in stdout.splitlines() if l.startswith("push ")]
     assert len(lines) == n
     ref = M.MotionRef(67, 45, orc.fast_atan2_deg, grid=(3, 2), **BAR)
     for t, (l, f) in enumerate(zip(lines, M.bar_clip("+x", n=n))):
@@ -413,4 +375,4 @@ def test_cpp_motion_against_the_statement(ctx, orc, tmp_path):
         assert int(l[1]) == t + 1 and float(l[2]) == fr["angle"]
         assert [int(v) for v in l[3:]] == [fr["S"], fr["W"], fr["n_masked"], fr["n_used"], fr["peak_bin"], want["silhouette"],
                                            int((want["vis"][..., 0] != 0).sum())], "push %d" % (t + 1)
-    assert [l for l in r.stdout.splitlines() if l.startswith("angle ")] == ["angle 0"]
+    assert [l for l in stdout.splitlines() if l.startswith("angle ")] == ["angle 0"]

@@ -5,8 +5,6 @@ picture wherever the statement's magnitude is not within that of a colour's boun
 On the MI355X every float came out equal to the statement's: no cell of any case differed at all (the count is printed by
 compare() and asserted to stay within the one unit the device's double division and square root are allowed)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,24 +12,14 @@ import torch
 
 import _cpp
 import _piv_ref as R
+from _dev import EINVAL, ESIZE, ESTATE, NULL as null, SENTINEL, Outputs, Padded, ordered, ptr, raw, reference
 from ripcurrents_amd._lib import RC_PIV_LAUNCHES, RC_PIV_MAX_STATE_BYTES, PivParams, RcflowError
 from ripcurrents_amd.api import PIV_CELL_DTYPE, PIV_SUMMARY, Piv
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EINVAL, ESIZE, ESTATE = -1, -5, -6
-SENTINEL = 0xA5
 FLOATS = ("dx", "dy", "peak", "resid")
-_REF = {}
-
-
-def reference(ctx, name):
-    """the statement's outputs of a case, computed once for the whole file and never changed"""
-    if name not in _REF:
-        case = R.cases()[name]
-        _REF[name] = (case,) + R.run_case(case, ctx.jet_lut())
-    return _REF[name]
+dev_frames = Padded.stack
 
 
 def open_kw(p):
@@ -40,43 +28,11 @@ def open_kw(p):
     return kw
 
 
-def padded(shape, dtype, pad, fill=SENTINEL):
-    """A device tensor of `shape` that is a view into rows `pad` pixels longer, the whole filled with a sentinel."""
-    base = torch.full((shape[0], shape[1] + pad) + tuple(shape[2:]), fill, dtype=dtype, device="cuda")
-    return base, base[:, :shape[1]]
-
-
-def dev_frames(frames, pad):
-    """all frames of a case in one upload, rows `pad` bytes longer than the frame"""
-    a = np.stack(frames)
-    base = torch.full((a.shape[0], a.shape[1], a.shape[2] + pad), SENTINEL, dtype=torch.uint8, device="cuda")
-    base[:, :, :a.shape[2]] = torch.as_tensor(a).cuda()
-    return [base[t, :, :a.shape[2]] for t in range(a.shape[0])]
-
-
-class Outputs:
-    def __init__(self, w, h, gx, gy, pad=0):
-        self.pad = pad
-        self.vis_base, self.vis = padded((h, w, 3), torch.uint8, pad)
-        self.field_base, self.field = padded((gy, gx, 2), torch.float32, pad, -7.0)
-        self.cells = torch.full((gy * gx * 32,), SENTINEL, dtype=torch.uint8, device="cuda")
-        self.summary = torch.full((8,), -1, dtype=torch.int64, device="cuda")
-        self.gx, self.gy = gx, gy
-
-    def kw(self):
-        return dict(cells=self.cells, field=self.field, vis=self.vis, summary=self.summary)
-
-    def host(self):
-        if self.pad:
-            assert (self.vis_base[:, self.vis.shape[1]:] == SENTINEL).all() and (self.field_base[:, self.gx:] == -7.0).all(), "row padding was written"
-        return dict(cells=self.cells.cpu().numpy().view(PIV_CELL_DTYPE).reshape(self.gy, self.gx), field=self.field.cpu().numpy(),
-                    vis=self.vis.cpu().numpy(), summary=self.summary.cpu().numpy())
-
-
-def ordered(a):
-    """float32 -> integers in which neighbouring floats differ by one"""
-    i = np.ascontiguousarray(a, np.float32).view(np.int32).astype(np.int64)
-    return np.where(i < 0, -(i & 0x7FFFFFFF), i)
+def outputs(w, h, gx, gy, pad=0):
+    def views(d):
+        d["cells"] = d["cells"].view(PIV_CELL_DTYPE).reshape(gy, gx)
+    return Outputs(dict(vis=((h, w, 3), torch.uint8), field=((gy, gx, 2), torch.float32, -7.0)),
+                   dict(cells=((gy * gx * 32,), torch.uint8, None), summary=((8,), torch.int64, -1)), pad, views)
 
 
 def compare(got, read, want, case, p, what):
@@ -113,14 +69,14 @@ def check_sums(ctx, ref, stream, what):
 
 def run(ctx, name, stream=0, compute_all=False):
     """a case through the device session; compares at every computing push.  -> the device outputs of the last one"""
-    case, ref, outs = reference(ctx, name)
+    case, ref, outs = reference(R, ctx, name)
     p = case.p
     ctx.piv_open(case.w, case.h, stream=stream, **open_kw(p))
     info = ctx.piv_info(stream=stream)
     assert (info["grid_x"], info["grid_y"]) == (ref.gx, ref.gy) and info["launches_per_push"] == RC_PIV_LAUNCHES
     frames = dev_frames(case.frames, case.pad)
     want = {t: (o, q) for t, o, q in outs}
-    out = Outputs(case.w, case.h, ref.gx, ref.gy, case.pad)
+    out = outputs(case.w, case.h, ref.gx, ref.gy, case.pad)
     check = R.PivRef(case.w, case.h, R.Params(**p.kw()))         # the accumulators after every computing push
     got = None
     for t, f in enumerate(frames, 1):
@@ -159,10 +115,8 @@ def test_more_cells_than_one_validating_block(ctx):
     No case of the statement's has more than 256 cells; 46 x 44 under a window of 8, a range of 2 and a step of 2 has 18 x 17 = 306:
     two blocks, 256 and 50 valid cells.  Pushes 2 and 3 compute, and the third finds the ticket and the counters zero"""
     name = "two validating blocks"
-    if name not in _REF:
-        case = R.Case(46, 44, R.Params(8, 2, 2, 1, 0, 0.25, 0.1, 2.0, 2.0), R.drifting_frames(46, 44, 3, 26, [(0, 0), (1, 0), (1, 1)]), {2, 3}, pad=3)
-        _REF[name] = (case,) + R.run_case(case, ctx.jet_lut())
-    case, ref, outs = _REF[name]
+    case = R.Case(46, 44, R.Params(8, 2, 2, 1, 0, 0.25, 0.1, 2.0, 2.0), R.drifting_frames(46, 44, 3, 26, [(0, 0), (1, 0), (1, 1)]), {2, 3}, pad=3)
+    case, ref, outs = reference(R, ctx, name, case)
     assert ref.gx * ref.gy == 306 and [int(o["summary"][2]) for _, o, _ in outs] == [306, 306]
     run(ctx, name)
     ctx.piv_close()
@@ -186,13 +140,13 @@ def test_result_does_not_depend_on_which_pushes_computed(ctx):
 
 
 def test_each_output_alone(ctx):
-    case, ref, outs = reference(ctx, "ragged")
+    case, ref, outs = reference(R, ctx, "ragged")
     p = case.p
     want = outs[2][1]                                             # push 3
     with Piv(ctx, case.w, case.h, **open_kw(p)) as pv:
         frames = dev_frames(case.frames[:3], 0)
         for name in ("cells", "field", "vis", "summary"):
-            o = Outputs(case.w, case.h, ref.gx, ref.gy)
+            o = outputs(case.w, case.h, ref.gx, ref.gy)
             pv.reset()
             pv.push(frames[0])
             pv.push(frames[1])
@@ -210,7 +164,7 @@ def test_each_output_alone(ctx):
             if name != "field":
                 assert (got["field"] == -7.0).all(), "field was written"
             if name != "cells":
-                assert (o.cells == SENTINEL).all()
+                assert (o.t["cells"] == SENTINEL).all()
             if name != "summary":
                 assert (got["summary"] == -1).all()
             assert [pv.read()[1][k] for k in PIV_SUMMARY] == [int(v) for v in want["summary"]]
@@ -218,9 +172,9 @@ def test_each_output_alone(ctx):
 
 # ---------------------------------------------------------------------------- the profile
 def test_profile_books_the_launches(ctx):
-    case, ref, outs = reference(ctx, "ring")
+    case, ref, outs = reference(R, ctx, "ring")
     frames = dev_frames(case.frames[:4], 0)
-    o = Outputs(case.w, case.h, ref.gx, ref.gy)
+    o = outputs(case.w, case.h, ref.gx, ref.gy)
     ctx.piv_open(case.w, case.h, **open_kw(case.p))
     ctx.profile_enable(True)
     ctx.profile_reset()
@@ -244,7 +198,7 @@ def test_profile_books_the_launches(ctx):
 
 # ---------------------------------------------------------------------------- arguments and lifecycle
 def test_refusals_and_lifecycle(ctx):
-    case, ref0, outs = reference(ctx, "ring")
+    case, ref0, outs = reference(R, ctx, "ring")
     p, w, h = case.p, case.w, case.h
     good = open_kw(p)
     gx, gy = ref0.gx, ref0.gy
@@ -253,8 +207,7 @@ def test_refusals_and_lifecycle(ctx):
         with pytest.raises(RcflowError) as e:
             call()
         assert e.value.code == ESTATE and str(e.value).split(": ", 1)[1]
-    lib, hdl = ctx._lib, ctx._h
-    null = C.c_void_p(None)
+    lib, hdl = raw(ctx)
     assert lib.rcflow_piv_push_dev(hdl, 0, null, 0, null, null, 0, null, 0, null) == ESTATE       # a push before open
     nan, inf = float("nan"), float("inf")
     for bad in (dict(window=6), dict(window=68), dict(window=10), dict(window=4), dict(range=0), dict(range=17), dict(step=0), dict(step=17),
@@ -290,7 +243,7 @@ def test_refusals_and_lifecycle(ctx):
     ctx.piv_open(w, h, **good)
     ref = R.PivRef(w, h, R.Params(**p.kw()), ctx.jet_lut())
     frames = dev_frames(case.frames, 0)
-    o = Outputs(w, h, gx, gy)
+    o = outputs(w, h, gx, gy)
     for t in range(5):
         ctx.piv_push(frames[t])
         ref.push(case.frames[t], compute=False)
@@ -311,7 +264,6 @@ def test_refusals_and_lifecycle(ctx):
 
     g = frames[5]
     buf = torch.zeros(3 * w * h + 1024, dtype=torch.uint8, device="cuda")
-    ptr = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
 
     def push(gray=None, step=w, cells=null, field=(null, 0), vis=(null, 0), summ=null, slot=0):
         return lib.rcflow_piv_push_dev(hdl, slot, ptr(g) if gray is None else gray, step, cells, field[0], field[1], vis[0], vis[1], summ)
@@ -378,13 +330,10 @@ def test_refusals_and_lifecycle(ctx):
 def test_cpp_piv_against_the_statement(ctx, tmp_path):
     """rc::Piv (include/rcflow_module.hpp) compiled with the flags of tests/cpp's test_module and run on frames it makes itself
     from integers; the summaries, peaks, flags and checksums it prints equal the statement's."""
-    exe = _cpp.build("test_piv", tmp_path)
     n = 12
-    r = subprocess.run([exe, str(n)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "test_piv: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [l.split() for l in _cpp.run("test_piv", tmp_path, n).splitlines() if l.startswith("push ")]
     case = R.cpp_case(n)
     ref = R.PivRef(case.w, case.h, case.p, ctx.jet_lut())
-    lines = [l.split() for l in r.stdout.splitlines() if l.startswith("push ")]
     assert len(lines) == n // 3
     k = 0
     for t in range(n):

@@ -2,8 +2,6 @@
 field, the mask, the picture and both copies of the summary, all bit for bit."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,57 +11,23 @@ import _cpp
 import _ftle_ref as F
 import _planview_ref as P
 import _regions_ref as R
+from _dev import EINVAL, ESIZE, ESTATE, NULL as null, SENTINEL, Outputs, Padded, bits, ptr, raw
 from ripcurrents_amd._lib import RC_PLANVIEW_LAUNCHES, PlanViewParams, RcflowError
 from ripcurrents_amd.api import FTLE_SUMMARY, PLANVIEW_SUMMARY
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EINVAL, ESIZE, ESTATE = -1, -5, -6
 f32 = np.float32
-SENTINEL = 0xA5
 W, H = 97, 53
-SHAPES = (("plan", (2,), torch.float32), ("mask", (), torch.uint8), ("plan_bgr", (3,), torch.uint8))
 
 
-def padded(shape, dtype, pad):
-    """A device tensor of `shape` that is a view into rows `pad` pixels longer, the whole filled with a sentinel."""
-    full = (shape[0], shape[1] + pad) + tuple(shape[2:])
-    base = torch.empty(full, dtype=dtype, device="cuda")
-    base.view(torch.uint8).fill_(SENTINEL)
-    return base, base[:, :shape[1]]
-
-
-class Outputs:
-    def __init__(self, nx, ny, pad=0):
-        self.pad, self.base, self.t = pad, {}, {}
-        for name, tail, dtype in SHAPES:
-            self.base[name], self.t[name] = padded((ny, nx) + tail, dtype, pad)
-        self.summary = torch.full((8,), -1, dtype=torch.int64, device="cuda")
-
-    def kw(self):
-        return dict(self.t, summary=self.summary)
-
-    def host(self):
-        out = {k: v.cpu().numpy() for k, v in self.t.items()}
-        out["summary"] = self.summary.cpu().numpy()
-        if self.pad:
-            for k, b in self.base.items():
-                assert (b[:, b.shape[1] - self.pad:].contiguous().view(torch.uint8) == SENTINEL).all(), "row padding of %s was written" % k
-        return out
+def outputs(nx, ny, pad=0):
+    return Outputs(dict(plan=((ny, nx, 2), torch.float32), mask=((ny, nx), torch.uint8), plan_bgr=((ny, nx, 3), torch.uint8)),
+                   dict(summary=((8,), torch.int64, -1)), pad)
 
 
 def dev(a, pad=0):
-    t = torch.as_tensor(np.ascontiguousarray(a)).cuda()
-    if not pad:
-        return t
-    _, v = padded(a.shape, t.dtype, pad)
-    v.copy_(t)
-    return v
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
+    return Padded.of(a, pad).view
 
 
 def compare(got, read, want, what):
@@ -79,7 +43,7 @@ def run(ctx, w, h, p, fields, frames, pad=0, stream=0):
     ctx.planview_open(w, h, stream=stream, **p.kw())
     ref = P.PlanViewRef(w, h, p)
     assert np.array_equal(bits(ctx.planview_table(stream=stream)), bits(ref.table)), "table differs"
-    out = Outputs(p.nx, p.ny, pad)
+    out = outputs(p.nx, p.ny, pad)
     want = None
     for t, (f, g) in enumerate(zip(fields, frames)):
         ctx.planview_push(dev(f, pad), dev(g, pad), stream=stream, **out.kw())
@@ -206,7 +170,7 @@ def test_each_output_and_each_input_alone(ctx):
     assert ctx.planview_read() == dict(dict.fromkeys(PLANVIEW_SUMMARY, 0), max_speed=0.0)
     df, dg = dev(f), dev(g)
     for name in ("plan", "mask", "plan_bgr", "summary"):
-        o = Outputs(p.nx, p.ny)
+        o = outputs(p.nx, p.ny)
         ctx.planview_push(df, dg, **{name: o.kw()[name]})
         want = ref.push(f, g)
         got = o.host()
@@ -217,13 +181,13 @@ def test_each_output_and_each_input_alone(ctx):
                 assert (got[other].view(np.uint8) == SENTINEL).all(), "%s was written" % other
         assert [ctx.planview_read()[k] for k in PLANVIEW_SUMMARY] == [int(v) for v in want["summary"]]
     # the field alone, the frame alone
-    o = Outputs(p.nx, p.ny)
-    ctx.planview_push(df, None, plan=o.t["plan"], mask=o.t["mask"], summary=o.summary)
+    o = outputs(p.nx, p.ny)
+    ctx.planview_push(df, None, plan=o.t["plan"], mask=o.t["mask"], summary=o.t["summary"])
     want = ref.push(f, None)
     got = o.host()
     assert np.array_equal(bits(got["plan"]), bits(want["plan"])) and np.array_equal(got["mask"], want["mask"])
     assert np.array_equal(got["summary"], want["summary"]) and (got["plan_bgr"] == SENTINEL).all()
-    o = Outputs(p.nx, p.ny)
+    o = outputs(p.nx, p.ny)
     ctx.planview_push(None, dg, plan_bgr=o.t["plan_bgr"])
     want = ref.push(None, g)
     assert np.array_equal(o.host()["plan_bgr"], want["bgr"])
@@ -243,7 +207,7 @@ def test_identity_returns_the_field_and_the_frame(ctx):
     f, g = P.wavy_field(w, h), P.frame(w, h)
     assert np.isfinite(f).all() and (f != 0).all()
     ctx.planview_open(w, h, **P.identity(w, h).kw())
-    o = Outputs(w, h)
+    o = outputs(w, h)
     ctx.planview_push(dev(f), dev(g), **o.kw())
     got = o.host()
     inner = np.zeros((h, w), bool)
@@ -300,7 +264,7 @@ def test_profile_books_one_table_and_one_push_launch(ctx):
     p = P.shore_camera()
     (f,), (g,) = inputs(W, H, 1)
     df, dg = dev(f), dev(g)
-    o = Outputs(p.nx, p.ny)
+    o = outputs(p.nx, p.ny)
     ctx.planview_close()
     ctx.profile_enable(True)
     ctx.profile_reset()
@@ -332,8 +296,7 @@ def test_refusals_and_lifecycle(ctx):
         with pytest.raises(RcflowError) as e:
             call()
         assert e.value.code == ESTATE and str(e.value).split(": ", 1)[1]
-    lib, hdl = ctx._lib, ctx._h
-    null = C.c_void_p(None)
+    lib, hdl = raw(ctx)
     assert lib.rcflow_planview_push_dev(hdl, 0, null, 0, null, 0, null, 0, null, 0, null, 0, null) == ESTATE
     nan, inf = float("nan"), float("inf")
     Hbad = list(p.H)
@@ -377,7 +340,6 @@ def test_refusals_and_lifecycle(ctx):
 
     df, dg = dev(f2), dev(g2)
     big = torch.zeros(ny * nx * 8 + 512, dtype=torch.uint8, device="cuda")
-    ptr = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
 
     def push(flow=None, fstep=8 * W, bgr=None, bstep=3 * W, plan=(null, 0), mask=(null, 0), pic=(null, 0), summ=null, slot=0):
         fp = ptr(df) if flow is None else flow
@@ -405,7 +367,7 @@ def test_refusals_and_lifecycle(ctx):
     assert push(slot=2) == EINVAL                                 # no such slot
     assert ctx.planview_info() == before
     # nothing was queued and nothing changed: the second push gives what the statement gives
-    o = Outputs(nx, ny)
+    o = outputs(nx, ny)
     ctx.planview_push(df, dg, **o.kw())
     compare(o.host(), ctx.planview_read(), ref.push(f2, g2), "(after the refusals)")
     # an accepted boundary: the mask begins at the first byte after the plan field's range, in one allocation
@@ -448,16 +410,14 @@ def test_cpp_planview_against_the_statement(ctx, tmp_path):
     """rc::PlanView (include/rcflow_module.hpp) compiled with the flags of tests/cpp's test_module and run on fields and frames
     it makes itself from integers (exact in float, so this file makes the same ones) through a camera whose numbers are exact
     in double; the summaries and counts it prints equal the statement's."""
-    exe = _cpp.build("test_planview", tmp_path)
     n = 3
-    r = subprocess.run([exe, str(n)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "test_planview: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    stdout = _cpp.run("test_planview", tmp_path, n)
     p = P.Params([90.0, 45.0, 165.0, 0.0, -6.5625, 933.125, 0.0, 0.9375, 3.4375], 90.0, 90.0, 48.0, 26.0, -0.125, 0.03125, -30.0, -6.0, 1.0, 1.5,
                  61, 37, 10.0, 0.6)
     ref = P.PlanViewRef(W, H, p)
-    tl = [l.split() for l in r.stdout.splitlines() if l.startswith("table ")]
+    tl = [l.split() for l in stdout.splitlines() if l.startswith("table ")]
     assert len(tl) == 1 and int(tl[0][1]) == int((ref.table[..., 7] != 0).sum()) > 0
-    lines = [l.split() for l in r.stdout.splitlines() if l.startswith("push ")]
+    lines = [l.split() for l in stdout.splitlines() if l.startswith("push ")]
     assert len(lines) == n
     y, x = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
     for t, l in enumerate(lines):

@@ -2,9 +2,6 @@
 every case -- labels, the opened mask, the integer fields of every record, the summary, the primitives -- is compared with
 np.array_equal; the derived doubles within 1e-6 * max(1, |b|), the angle only where the two variances differ by more than
 1e-3 of the larger.  Outputs sit between fence bytes in rows with poisoned padding; nothing is sampled."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
@@ -12,39 +9,12 @@ import torch
 import _cpp
 import _regions_ref as R
 import _tracers_ref as TR
+from _dev import EINVAL, ESIZE, ESTATE, SENTINEL, Fenced
 from ripcurrents_amd import synth
 from ripcurrents_amd._lib import RC_REGIONS_LAUNCHES, RcflowError
 from ripcurrents_amd.api import DRAW_PRIM_DTYPE, REGION_DTYPE
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EINVAL, ESIZE, ESTATE = -1, -5, -6
-FENCE = 0xA5
-
-
-class Fenced:
-    """h rows of `row` elements inside a device allocation filled with FENCE bytes: `lead` elements before the first row (an
-    unaligned base), `pad` elements after every row, 64 bytes after the last."""
-
-    def __init__(self, h, row, dtype, pad=0, lead=0, fill=None):
-        self.h, self.row, self.pad, self.lead = h, row, pad, lead
-        self.item = torch.empty((), dtype=dtype).element_size()
-        self.step = row + pad
-        self.bytes = torch.full(((lead + h * self.step) * self.item + 64,), FENCE, dtype=torch.uint8, device="cuda")
-        self.view = torch.as_strided(self.bytes[:(lead + h * self.step) * self.item].view(dtype), (h, row), (self.step, 1), lead)
-        if fill is not None:
-            self.view.copy_(torch.as_tensor(np.ascontiguousarray(fill).reshape(h, row)).cuda())
-
-    def check(self, what):
-        b = self.bytes.cpu().numpy()
-        n = self.h * self.step * self.item
-        assert (b[:self.lead * self.item] == FENCE).all() and (b[self.lead * self.item + n:] == FENCE).all(), "fence bytes around %s changed" % what
-        rows = b[self.lead * self.item:self.lead * self.item + n].reshape(self.h, self.step * self.item)
-        assert (rows[:, self.row * self.item:] == FENCE).all(), "row padding of %s was written" % what
-
-    def numpy(self):
-        return self.view.cpu().numpy()
 
 
 def compare_records(got, want, what):
@@ -283,7 +253,7 @@ def test_set_reset_reopen_refusals(ctx):
         assert after[0] == before[0] and np.array_equal(after[1][0], before[1][0]) and after[1][1] == before[1][1], "refusal %d changed the state" % i
     want = push_and_check(ctx, m, 4, 20, 32, opened=True, pushes=3)
     # an accepted boundary: the labels begin at the first byte after the mask's range, in one allocation
-    one = torch.full((5 * h * w + 64,), FENCE, dtype=torch.uint8, device="cuda")
+    one = torch.full((5 * h * w + 64,), SENTINEL, dtype=torch.uint8, device="cuda")
     tm, tl = one[:h * w].view(h, w), one[h * w:5 * h * w].view(torch.int32).view(h, w)
     assert tl.data_ptr() == tm.data_ptr() + (h - 1) * tm.stride(0) + w
     tm.copy_(dm)
@@ -292,7 +262,7 @@ def test_set_reset_reopen_refusals(ctx):
     ctx.regions_push(dm, labels=lab)                          # the same with separate allocations
     apart = ctx.regions_read()
     assert np.array_equal(tl.cpu().numpy(), lab.cpu().numpy()) and np.array_equal(tl.cpu().numpy(), want["labels"])
-    assert np.array_equal(tm.cpu().numpy(), m) and (one[5 * h * w:] == FENCE).all()
+    assert np.array_equal(tm.cpu().numpy(), m) and (one[5 * h * w:] == SENTINEL).all()
     assert touching[0].tobytes() == apart[0].tobytes() and dict(touching[1], pushes=5) == apart[1] and touching[1]["pushes"] == 4
     ctx.regions_reset()
     assert ctx.regions_info()["pushes"] == 0 and ctx.regions_info()["min_area"] == 20
@@ -421,11 +391,8 @@ def test_product_chain_without_a_host_round_trip(ctx):
 def test_cpp_regions_against_the_statement(ctx, tmp_path):
     """rc::Regions (include/rcflow_module.hpp) compiled as tests/cpp's programs are and run on seeded masks; what it prints
     equals the numpy statement on the same masks."""
-    exe = _cpp.build("test_regions", tmp_path, gxx=True)
     w, h, n = 200, 120, 4
-    r = subprocess.run([exe, str(w), str(h), str(n)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "test_regions: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
-    lines = [l for l in r.stdout.splitlines() if l.startswith("push ")]
+    lines = [l for l in _cpp.run("test_regions", tmp_path, w, h, n, gxx=True).splitlines() if l.startswith("push ")]
     assert len(lines) == n
 
     def fnv(a):

@@ -1,22 +1,17 @@
 """The opposing-flow map on the device (ripmap_kernels.hip) against its numpy statement (tests/_ripmap_ref.py), after every
 push: mean, sums, counts, flags and mask bit for bit; cell means as floats; angles within 1e-9 degrees."""
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
 import _cpp
 import _ripmap_ref as R
+from _dev import EINVAL, ESIZE, ESTATE, NULL, ptr, raw
 from ripcurrents_amd import synth
 from ripcurrents_amd._lib import RcflowError
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EINVAL, ESIZE, ESTATE = -1, -5, -6
 f32 = np.float32
 
 
@@ -239,18 +234,18 @@ def test_refusals_leave_the_state_as_it_was(ctx):
     assert e.value.code == ESTATE
     flows = fields(w, h, 3)
     ref = run(ctx, flows[:2], 3, (7, 5))
-    lib, hd = ctx._lib, ctx._h
+    lib, hd = raw(ctx)
     for args in ((w, h, 0, 7, 5, 0, 0), (w, h, 3, 98, 5, 0, 0), (w, h, 3, 7, 62, 0, 0), (w, h, 3, 0, 5, 0, 0),
                  (w, h, 3, 7, 5, 2, 0), (w, h, 3, 7, 5, 0, 2), (0, h, 3, 7, 5, 0, 0)):
         assert lib.rcflow_ripmap_open(hd, 0, *args) == EINVAL, args
     assert lib.rcflow_ripmap_open(hd, 0, 4000, 61, 3, 7, 5, 0, 0) == ESIZE
     d = torch.as_tensor(flows[2]).cuda()
     hsv = torch.zeros((h, w, 3), dtype=torch.uint8, device="cuda")
-    p, z = C.c_void_p(d.data_ptr()), C.c_void_p(None)
+    p, z = ptr(d), NULL
     assert lib.rcflow_ripmap_push_dev(hd, 0, p, w * 8 - 8, z, 0, z, 0, z, z) == EINVAL
     assert lib.rcflow_ripmap_push_dev(hd, 0, p, w * 8 + 4, z, 0, z, 0, z, z) == EINVAL
-    assert lib.rcflow_ripmap_push_dev(hd, 0, p, w * 8, C.c_void_p(hsv.data_ptr()), 3 * w - 1, z, 0, z, z) == EINVAL
-    assert lib.rcflow_ripmap_push_dev(hd, 0, p, w * 8, z, 0, C.c_void_p(hsv.data_ptr()), w - 1, z, z) == EINVAL
+    assert lib.rcflow_ripmap_push_dev(hd, 0, p, w * 8, ptr(hsv), 3 * w - 1, z, 0, z, z) == EINVAL
+    assert lib.rcflow_ripmap_push_dev(hd, 0, p, w * 8, z, 0, ptr(hsv), w - 1, z, z) == EINVAL
     assert lib.rcflow_ripmap_mean_dev(hd, 0, z, w * 8) == EINVAL
     with pytest.raises(ValueError):
         ctx.ripmap_push(torch.zeros((h, w + 1, 2), device="cuda"))
@@ -325,11 +320,8 @@ def test_synthetic_scene_flags_the_jet(ctx):
 def test_cpp_ripmap_against_ctypes(ctx, tmp_path):
     """rc::RipMap (include/rcflow_module.hpp) compiled as tests/cpp's programs are and run on a seeded field sequence;
     the sums and flags it prints equal the ctypes session's on the same fields."""
-    exe = _cpp.build("test_ripmap", tmp_path, gxx=True)
     w, h, window, gx, gy, n = 97, 61, 3, 7, 5, 5
-    r = subprocess.run([exe, str(w), str(h), str(window), str(gx), str(gy), str(n)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "test_ripmap: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
-    lines = [l.split() for l in r.stdout.splitlines() if l.startswith("push ")]
+    lines = [l.split() for l in _cpp.run("test_ripmap", tmp_path, w, h, window, gx, gy, n, gxx=True).splitlines() if l.startswith("push ")]
     assert len(lines) == n
     # the program's fields: v(x, y, t) = ((x * 7 + y * 3 + t * 11) % 17 - 8) / 4, ((x * 5 + y * 13 + t * 7) % 19 - 9) / 4
     y, x = np.mgrid[0:h, 0:w]

@@ -9,40 +9,23 @@ import torch
 import _regions_ref as RG
 import _shoreline_ref as S
 import _tracers_ref as TR
+from _dev import EINVAL, ESIZE, ESTATE, NULL as null, SENTINEL, Outputs, Padded, ptr, raw
+from _shoreline_ref import ragged_lines
 from ripcurrents_amd._lib import RC_SHORE_LAUNCHES, RcflowError, ShorelineInfo, ShorelineParams, TransectLine
 from ripcurrents_amd.api import DRAW_PRIM_DTYPE, SHORELINE_DTYPE, SHORELINE_SUMMARY, Shoreline
 
 pytestmark = pytest.mark.gpu
 
-EINVAL, ESIZE, ESTATE = -1, -5, -6
-SENTINEL = 0xA5
+dev_image = Padded.of                                             # a picture on the device, rows `pad` pixels longer and the sentinel there
 
 
-def dev_image(a, pad=0):
-    """a picture on the device, rows `pad` pixels longer than the picture and full of the sentinel there -> (view, base)"""
-    base = torch.full((a.shape[0], a.shape[1] + pad) + a.shape[2:], SENTINEL, dtype=torch.uint8, device="cuda")
-    base[:, :a.shape[1]] = torch.as_tensor(a).cuda()
-    return base[:, :a.shape[1]], base
+def views(d):
+    d["records"], d["plane"], d["hist"] = d["records"].view(SHORELINE_DTYPE), d["plane"].view(np.uint16), d["hist"].view(np.uint32)
 
 
-class Outputs:
-    def __init__(self, L, w, h, pad=0):
-        self.w, self.pad = w, pad
-        self.records = torch.full((L * 64,), SENTINEL, dtype=torch.uint8, device="cuda")
-        self.summary = torch.full((8,), -1, dtype=torch.int64, device="cuda")
-        self.hist = torch.full((512,), -1, dtype=torch.int32, device="cuda")
-        self.mask_base = torch.full((h, w + pad), SENTINEL, dtype=torch.uint8, device="cuda")
-        self.plane_base = torch.full((h, w + pad), -23131, dtype=torch.int16, device="cuda")
-
-    def kw(self):
-        return dict(records=self.records, summary=self.summary, hist=self.hist, mask=self.mask_base[:, :self.w], plane=self.plane_base[:, :self.w])
-
-    def host(self):
-        d = {k: v.cpu().numpy() for k, v in self.kw().items()}
-        if self.pad:
-            assert (self.mask_base[:, self.w:] == SENTINEL).all() and (self.plane_base[:, self.w:] == -23131).all(), "row padding was written"
-        d["records"], d["plane"], d["hist"] = d["records"].view(SHORELINE_DTYPE), d["plane"].view(np.uint16), d["hist"].view(np.uint32)
-        return d
+def outputs(L, w, h, pad=0):
+    return Outputs(dict(mask=((h, w), torch.uint8), plane=((h, w), torch.int16)),
+                   dict(records=((L * 64,), torch.uint8, None), summary=((8,), torch.int64, -1), hist=((512,), torch.int32, -1)), pad, views)
 
 
 def compare(got, read, want, what):
@@ -65,17 +48,18 @@ def run(ctx, w, h, lines, p, images, rois=None, pad=0, stream=0, keep_open=False
     assert (info["lines"], info["samples"], info["launches_per_push"], info["source"]) == (ref.L, len(ref.table), RC_SHORE_LAUNCHES, p.kw()["source"])
     table, geom = ctx.shoreline_table(stream=stream)
     assert table.tobytes() == ref.table.tobytes() and geom.tobytes() == ref.geom.tobytes()
-    out, wants = Outputs(ref.L, w, h, pad), []
+    out, wants = outputs(ref.L, w, h, pad), []
     for t, img in enumerate(images):
         roi = None if rois is None else rois[t]
-        d, base = dev_image(img, pad)
-        droi = None if roi is None else dev_image(roi, pad)[0]
-        ctx.shoreline_push(d, droi, stream=stream, **out.kw())
+        d = dev_image(img, pad)
+        droi = None if roi is None else dev_image(roi, pad).view
+        ctx.shoreline_push(d.view, droi, stream=stream, **out.kw())
         want = ref.push(img, roi)
         what = "after push %d" % (t + 1)
         compare(out.host(), ctx.shoreline_read(stream=stream), want, what)
         assert np.array_equal(ctx.shoreline_ring(stream=stream), ref.ring_read()), "the ring differs " + what
-        assert np.array_equal(base[:, :w].cpu().numpy(), img) and (pad == 0 or (base[:, w:] == SENTINEL).all()), "the picture was written"
+        assert np.array_equal(d.view.cpu().numpy(), img), "the picture was written"
+        d.check("the picture")
         info = ctx.shoreline_info(stream=stream)
         assert (info["held"], info["pushes"]) == (min(t + 1, p.window), t + 1)
         wants.append(want)
@@ -86,12 +70,6 @@ def run(ctx, w, h, lines, p, images, rois=None, pad=0, stream=0, keep_open=False
 
 def flags_seen(wants):
     return int(np.bitwise_or.reduce(np.concatenate([x["records"]["flags"] for x in wants])))
-
-
-def ragged_lines(w, h):
-    """diagonals with fractional ends, the last row, the last column (the ix1 and iy1 clamps), n = 8 and n = 1024"""
-    return [(1.3, 2.7, w - 1.6, h - 2.2, 33), (0.0, float(h - 1), float(w - 1), float(h - 1), 40), (float(w - 1), 0.0, float(w - 1), float(h - 1), 19),
-            (2.5, h - 1.25, w - 1.0, 0.0, 8), (0.0, 0.0, float(w - 1), float(h - 1), 1024), (0.4, 17.5, w - 1.4, 17.5, 129)]
 
 
 def polygon_roi(w, h):
@@ -214,11 +192,11 @@ def test_each_output_alone_and_a_push_with_none(ctx):
     imgs = [S.beach(w, h, t) for t in range(7)]
     ref = S.ShorelineRef(w, h, lines, p)
     ctx.shoreline_open(w, h, lines, **p.kw())
-    out = Outputs(ref.L, w, h)
+    out = outputs(ref.L, w, h)
     for t, key in enumerate(("records", "summary", "hist", "mask", "plane", None, "all")):
-        d = dev_image(imgs[t])[0]
+        d = dev_image(imgs[t]).view
         want = ref.push(imgs[t])
-        fresh = Outputs(ref.L, w, h)
+        fresh = outputs(ref.L, w, h)
         if key == "all":
             ctx.shoreline_push(d, **out.kw())
             compare(out.host(), ctx.shoreline_read(), want, "after the single outputs")
@@ -230,7 +208,7 @@ def test_each_output_alone_and_a_push_with_none(ctx):
             assert np.array_equal(a, b), "%s alone differs" % key
         for other in ("summary", "hist", "mask", "plane"):
             if other != key:
-                assert np.array_equal(fresh.kw()[other].cpu().numpy(), Outputs(ref.L, w, h).kw()[other].cpu().numpy()), "%s was written" % other
+                assert np.array_equal(fresh.kw()[other].cpu().numpy(), outputs(ref.L, w, h).kw()[other].cpu().numpy()), "%s was written" % other
         rec, summ = ctx.shoreline_read()
         assert rec.tobytes() == want["records"].tobytes() and [summ[k] for k in SHORELINE_SUMMARY] == [int(v) for v in want["summary"]]
         assert np.array_equal(ctx.shoreline_ring(), ref.ring_read())
@@ -246,7 +224,7 @@ def test_mask_goes_straight_into_regions(ctx):
     ctx.shoreline_open(w, h, S.beach_lines(w, h), **p.kw())
     ctx.regions_open(w, h, connectivity=8, min_area=16, max_regions=16)
     mask = torch.zeros((h, w), dtype=torch.uint8, device="cuda")
-    ctx.shoreline_push(dev_image(img)[0], mask=mask)
+    ctx.shoreline_push(dev_image(img).view, mask=mask)
     ctx.regions_push(mask)                                        # the same stream: no host round trip in between
     rec, summ = ctx.regions_read()
     wr = RG.regions(want["mask"], 8, 16, 16, None, 1)
@@ -268,7 +246,7 @@ def test_primitives_painted_by_draw(ctx):
     ctx.shoreline_open(w, h, lines, **p.kw())
     empty = ctx.shoreline_prims(color=0x3060f0, thickness=2, disc_radius=2).cpu().numpy().view(DRAW_PRIM_DTYPE).ravel()
     assert empty.size == 2 * len(lines) - 1 and not empty.view(np.uint8).any()                 # before the first push
-    ctx.shoreline_push(dev_image(noisy)[0])
+    ctx.shoreline_push(dev_image(noisy).view)
     want = ref.push(noisy)
     fl = want["records"]["flags"]
     assert (fl & S.OUTLIER).any() and (fl & S.WET).any() and ((fl & S.OUTLIER) == 0).sum() > 10
@@ -276,11 +254,12 @@ def test_primitives_painted_by_draw(ctx):
     got, wp = prims.cpu().numpy().view(DRAW_PRIM_DTYPE).ravel(), ref.prims(0x3060f0, 2, 2)
     assert got.tobytes() == wp.tobytes()
     assert (wp["kind"] == S.LINE).sum() == (wp["kind"] == S.DISC).sum() - 1 and (wp["kind"] == 0).any()
-    canvas, base = dev_image(noisy, 4)
-    ctx.draw(canvas, prims)
+    canvas = dev_image(noisy, 4)
+    ctx.draw(canvas.view, prims)
     painted = noisy.copy()
     TR.draw(painted, wp)
-    assert np.array_equal(canvas.cpu().numpy(), painted) and (base[:, w:] == SENTINEL).all() and not np.array_equal(painted, noisy)
+    assert np.array_equal(canvas.view.cpu().numpy(), painted) and not np.array_equal(painted, noisy)
+    canvas.check("the canvas")
     ctx.shoreline_close()
 
 
@@ -291,8 +270,8 @@ def test_set_acts_from_the_next_push_and_reset_keeps_it(ctx):
     imgs = [S.beach(w, h, t) for t in range(4)]
     ref = S.ShorelineRef(w, h, lines, p)
     ctx.shoreline_open(w, h, lines, **p.kw())
-    out = Outputs(ref.L, w, h)
-    push = lambda t: (ctx.shoreline_push(dev_image(imgs[t])[0], **out.kw()), compare(out.host(), ctx.shoreline_read(), ref.push(imgs[t]), "push %d" % t))
+    out = outputs(ref.L, w, h)
+    push = lambda t: (ctx.shoreline_push(dev_image(imgs[t]).view, **out.kw()), compare(out.host(), ctx.shoreline_read(), ref.push(imgs[t]), "push %d" % t))
     push(0)
     ctx.shoreline_set(240, 0.995, 0.05)
     ref.set(240, 0.995, 0.05)
@@ -319,11 +298,11 @@ def test_two_slots(ctx):
     ra, rb = S.ShorelineRef(wa, ha, la, pa), S.ShorelineRef(wb, hb, lb, pb)
     ctx.shoreline_open(wa, ha, la, stream=0, **pa.kw())
     ctx.shoreline_open(wb, hb, lb, stream=1, **pb.kw())
-    oa, ob = Outputs(ra.L, wa, ha), Outputs(rb.L, wb, hb)
+    oa, ob = outputs(ra.L, wa, ha), outputs(rb.L, wb, hb)
     for t in range(4):
         ia, ib = S.beach(wa, ha, t), S.beach(wb, hb, t, seed=9)
-        ctx.shoreline_push(dev_image(ia)[0], stream=0, **oa.kw())
-        ctx.shoreline_push(dev_image(ib)[0], stream=1, **ob.kw())
+        ctx.shoreline_push(dev_image(ia).view, stream=0, **oa.kw())
+        ctx.shoreline_push(dev_image(ib).view, stream=1, **ob.kw())
         compare(oa.host(), ctx.shoreline_read(stream=0), ra.push(ia), "slot 0, push %d" % t)
         compare(ob.host(), ctx.shoreline_read(stream=1), rb.push(ib), "slot 1, push %d" % t)
     ctx.shoreline_close(stream=1)
@@ -337,14 +316,14 @@ def test_product_object(ctx):
     ref = S.ShorelineRef(w, h, S.beach_lines(w, h), p)
     with Shoreline(ctx, w, h, lines=S.beach_lines(w, h), **p.kw()) as sh:
         img = S.beach(w, h, 0)
-        sh.push(dev_image(img)[0])
+        sh.push(dev_image(img).view)
         rec, summ = sh.read()
         want = ref.push(img)
         assert rec.tobytes() == want["records"].tobytes() and abs(summ["eta"] - want["eta"]) < 2.0 ** -32
         assert sh.info()["pushes"] == 1 and sh.ring().shape == (ref.L, 4) and sh.table()[0].size == len(ref.table)
         assert sh.prims().shape == (2 * ref.L - 1, 32)
         with pytest.raises(ValueError):
-            sh.push(dev_image(img[..., 0].copy())[0])               # a plane into an 8UC3 session
+            sh.push(dev_image(img[..., 0].copy()).view)               # a plane into an 8UC3 session
         sh.set(-1, 0.5, 4.0)
         sh.reset()
         assert sh.info()["pushes"] == 0
@@ -358,8 +337,7 @@ def test_refusals_and_lifecycle(ctx):
     lines, good = S.beach_lines(w, h), S.Params(radius=2, window=4)
     L = len(lines)
     ctx.shoreline_close()
-    lib, hdl = ctx._lib, ctx._h
-    null = C.c_void_p(None)
+    lib, hdl = raw(ctx)
 
     def text():
         return (lib.rcflow_last_error() or b"").decode()
@@ -414,9 +392,8 @@ def test_refusals_and_lifecycle(ctx):
         with pytest.raises(RcflowError):
             ctx.shoreline_open(w, h, lines, **dict(kw, **bad))
     assert ctx.shoreline_info() == before
-    img, _ = dev_image(S.beach(w, h, 1))
+    img = dev_image(S.beach(w, h, 1)).view
     big = torch.zeros(8 * h * w + 256, dtype=torch.uint8, device="cuda")
-    ptr = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
 
     def push(image=None, step=3 * w, ch=3, roi=(null, 0), rec=null, mask=(null, 0), plane=(null, 0), hist=null, summ=null, slot=0):
         return lib.rcflow_shoreline_push_dev(hdl, slot, ptr(img) if image is None else image, step, ch, roi[0], roi[1], rec, mask[0], mask[1],
@@ -442,7 +419,7 @@ def test_refusals_and_lifecycle(ctx):
     assert text().startswith("rcflow_shoreline_prims_dev")
     assert ctx.shoreline_info() == before
     # nothing was queued and nothing changed: the second push gives what the statement gives
-    out = Outputs(L, w, h)
+    out = outputs(L, w, h)
     ctx.shoreline_push(img, **out.kw())
     compare(out.host(), ctx.shoreline_read(), ref.push(S.beach(w, h, 1)), "(after the refusals)")
     # an accepted boundary: the plane begins at the first byte after the mask's range, in one allocation

@@ -9,51 +9,32 @@ import torch
 import _regions_ref as RG
 import _surf_ref as S
 import _tracers_ref as TR
+from _dev import EINVAL, ESIZE, ESTATE, NULL as null, SENTINEL, Outputs, Padded, ptr, raw
+from _shoreline_ref import ragged_lines
 from ripcurrents_amd._lib import RC_SURF_LAUNCHES, RcflowError, SurfInfo, SurfParams, TransectLine
 from ripcurrents_amd.api import DRAW_PRIM_DTYPE, SURF_CHANNEL_DTYPE, SURF_LINE_DTYPE, SURF_SUMMARY, Surf
-from test_gpu_shoreline import ragged_lines
 
 pytestmark = pytest.mark.gpu
 
-EINVAL, ESIZE, ESTATE = -1, -5, -6
-SENTINEL = 0xA5
 IMAGES = ("now", "surf", "q", "mean", "sd", "picture")
 ARRAYS = ("lines", "channels", "summary")
+dev_image = Padded.of                                             # a picture on the device, rows `pad` pixels longer and the sentinel there
 
 
-def dev_image(a, pad=0):
-    """a picture on the device, rows `pad` pixels longer than the picture and full of the sentinel there -> (view, base)"""
-    base = torch.full((a.shape[0], a.shape[1] + pad) + a.shape[2:], SENTINEL, dtype=torch.uint8, device="cuda")
-    base[:, :a.shape[1]] = torch.as_tensor(a).cuda()
-    return base[:, :a.shape[1]], base
+def views(d):
+    d["q"] = d["q"].view(np.uint16)
+    if "lines" in d:
+        d["lines"], d["channels"] = d["lines"].view(SURF_LINE_DTYPE), d["channels"].view(SURF_CHANNEL_DTYPE)
 
 
-class Outputs:
-    def __init__(self, L, w, h, pad=0):
-        self.w, self.pad, self.L = w, pad, L
-        self.base = {k: torch.full((h, w + pad), SENTINEL, dtype=torch.uint8, device="cuda") for k in ("now", "surf", "mean", "sd")}
-        self.base["q"] = torch.full((h, w + pad), -23131, dtype=torch.int16, device="cuda")
-        self.base["picture"] = torch.full((h, w + pad, 3), SENTINEL, dtype=torch.uint8, device="cuda")
-        self.lines = torch.full((L * 64,), SENTINEL, dtype=torch.uint8, device="cuda")
-        self.channels = torch.full((32 * 32,), SENTINEL, dtype=torch.uint8, device="cuda")
-        self.summary = torch.full((8,), -1, dtype=torch.int64, device="cuda")
-
-    def kw(self):
-        d = {k: v[:, :self.w] for k, v in self.base.items()}
-        d["summary"] = self.summary
-        if self.L:
-            d["lines"], d["channels"] = self.lines, self.channels
-        return d
-
-    def host(self):
-        d = {k: v.cpu().numpy() for k, v in self.kw().items()}
-        if self.pad:
-            for k, v in self.base.items():
-                assert (v[:, self.w:] == (-23131 if k == "q" else SENTINEL)).all(), "row padding of %s was written" % k
-        d["q"] = d["q"].view(np.uint16)
-        if self.L:
-            d["lines"], d["channels"] = d["lines"].view(SURF_LINE_DTYPE), d["channels"].view(SURF_CHANNEL_DTYPE)
-        return d
+def outputs(L, w, h, pad=0):
+    """a session without lines takes no line and no channel records"""
+    planes = {k: ((h, w), torch.uint8) for k in ("now", "surf", "mean", "sd")}
+    planes.update(q=((h, w), torch.int16), picture=((h, w, 3), torch.uint8))
+    flat = dict(summary=((8,), torch.int64, -1))
+    if L:
+        flat.update(lines=((L * 64,), torch.uint8, None), channels=((32 * 32,), torch.uint8, None))
+    return Outputs(planes, flat, pad, views)
 
 
 def compare(got, read, want, what):
@@ -80,17 +61,18 @@ def run(ctx, w, h, lines, p, frames, pad=0, stream=0, keep_open=False, compare_f
     assert info["device_bytes"] >= S.state_bytes(w, h, p.window)
     table, geom = ctx.surf_table(stream=stream)
     assert table.tobytes() == ref.table.tobytes() and geom.tobytes() == ref.geom.tobytes()
-    out, wants = Outputs(ref.L, w, h, pad), []
+    out, wants = outputs(ref.L, w, h, pad), []
     for t, img in enumerate(frames):
-        d, base = dev_image(img, pad)
+        d = dev_image(img, pad)
         want = ref.push(img)
         if t < compare_from:
-            ctx.surf_push(d, stream=stream)
+            ctx.surf_push(d.view, stream=stream)
             continue
-        ctx.surf_push(d, stream=stream, **out.kw())
+        ctx.surf_push(d.view, stream=stream, **out.kw())
         what = "after push %d" % (t + 1)
         compare(out.host(), ctx.surf_read(stream=stream), want, what)
-        assert np.array_equal(base[:, :w].cpu().numpy(), img) and (pad == 0 or (base[:, w:] == SENTINEL).all()), "the frame was written"
+        assert np.array_equal(d.view.cpu().numpy(), img), "the frame was written"
+        d.check("the frame")
         info = ctx.surf_info(stream=stream)
         assert (info["held"], info["pushes"]) == (min(t + 1, p.window), t + 1)
         wants.append(want)
@@ -284,15 +266,14 @@ def test_pixels_only_session(ctx):
     p = S.Params(window=3, bright=128, delta=20)
     ref, wants = run(ctx, w, h, [], p, random_frames(w, h, 5, seed=6), pad=4, keep_open=True)
     assert all(int(x["summary"][4]) == 0 and int(x["summary"][1]) == int((x["now"] != 0).sum()) for x in wants)
-    lib, hdl = ctx._lib, ctx._h
-    null = C.c_void_p(None)
-    img = dev_image(random_frames(w, h, 1, seed=7)[0])[0]
+    lib, hdl = raw(ctx)
+    img = dev_image(random_frames(w, h, 1, seed=7)[0]).view
     buf = torch.zeros(4096, dtype=torch.uint8, device="cuda")
     before = ctx.surf_info()
-    args = lambda lines, chans: (hdl, 0, C.c_void_p(img.data_ptr()), w, 1) + (null, 0) * 6 + (lines, chans, null)
-    for lines, chans in ((C.c_void_p(buf.data_ptr()), null), (null, C.c_void_p(buf.data_ptr()))):
+    args = lambda lines, chans: (hdl, 0, ptr(img), w, 1) + (null, 0) * 6 + (lines, chans, null)
+    for lines, chans in ((ptr(buf), null), (null, ptr(buf))):
         assert lib.rcflow_surf_push_dev(*args(lines, chans)) == EINVAL and (lib.rcflow_last_error() or b"").decode().startswith("rcflow_surf_push_dev")
-    assert lib.rcflow_surf_prims_dev(hdl, 0, 1, 1, 2, C.c_void_p(buf.data_ptr())) == EINVAL
+    assert lib.rcflow_surf_prims_dev(hdl, 0, 1, 1, 2, ptr(buf)) == EINVAL
     assert ctx.surf_info() == before
     rl, rc, rs = ctx.surf_read()
     assert rl.size == 0 and rc.size == 0 and rs["pushes"] == 5
@@ -308,11 +289,11 @@ def test_each_output_alone_and_a_push_with_none(ctx):
     frames = random_frames(w, h, len(keys), seed=8)
     ref = S.SurfRef(w, h, lines, p, ctx.jet_lut())
     ctx.surf_open(w, h, lines, **p.kw())
-    out = Outputs(ref.L, w, h)
+    out = outputs(ref.L, w, h)
     for t, key in enumerate(keys):
-        d = dev_image(frames[t])[0]
+        d = dev_image(frames[t]).view
         want = ref.push(frames[t])
-        fresh, untouched = Outputs(ref.L, w, h), Outputs(ref.L, w, h)
+        fresh, untouched = outputs(ref.L, w, h), outputs(ref.L, w, h)
         if key == "all":
             ctx.surf_push(d, **out.kw())
             compare(out.host(), ctx.surf_read(), want, "after the single outputs")
@@ -338,7 +319,7 @@ def test_surf_mask_goes_straight_into_regions(ctx):
     for t in range(34):
         f = S.surf_scene(t)
         want = ref.push(f)
-        ctx.surf_push(dev_image(f)[0], surf=mask)
+        ctx.surf_push(dev_image(f).view, surf=mask)
     ctx.regions_push(mask)                                        # the same stream: no host round trip in between
     rec, summ = ctx.regions_read()
     wr = RG.regions(want["surf"], 8, 16, 16, None, 1)
@@ -356,16 +337,17 @@ def test_primitives_painted_by_draw(ctx):
     for t in range(12):
         f = S.surf_scene(t)
         ref.push(f)
-        ctx.surf_push(dev_image(f)[0])
+        ctx.surf_push(dev_image(f).view)
     prims = ctx.surf_prims(color=0x3060f0, thickness=2, disc_radius=3)
     got, wp = prims.cpu().numpy().view(DRAW_PRIM_DTYPE).ravel(), ref.prims(0x3060f0, 2, 3)
     assert got.tobytes() == wp.tobytes()
     assert (wp["kind"] == S.LINE_PRIM).sum() == 32 - 5 - 1 and (wp["kind"] == S.DISC).sum() == 2 and (wp["kind"][:31] == 0).sum() == 5
-    canvas, base = dev_image(np.repeat(f[..., None], 3, axis=2), 4)
-    ctx.draw(canvas, prims)
+    canvas = dev_image(np.repeat(f[..., None], 3, axis=2), 4)
+    ctx.draw(canvas.view, prims)
     painted = np.repeat(f[..., None], 3, axis=2)
     TR.draw(painted, wp)
-    assert np.array_equal(canvas.cpu().numpy(), painted) and (base[:, w:] == SENTINEL).all() and not np.array_equal(painted, np.repeat(f[..., None], 3, axis=2))
+    assert np.array_equal(canvas.view.cpu().numpy(), painted) and not np.array_equal(painted, np.repeat(f[..., None], 3, axis=2))
+    canvas.check("the canvas")
     ctx.surf_close()
 
 
@@ -375,11 +357,11 @@ def test_set_acts_from_the_next_push_and_reset_keeps_it(ctx):
     lines, p = S.scene_lines(), S.Params(**dict(S.asdict(S.SCENE), window=6))
     ref = S.SurfRef(w, h, lines, p, ctx.jet_lut())
     ctx.surf_open(w, h, lines, **p.kw())
-    out = Outputs(ref.L, w, h)
+    out = outputs(ref.L, w, h)
 
     def push(t):
         f = S.surf_scene(t)
-        ctx.surf_push(dev_image(f)[0], **out.kw())
+        ctx.surf_push(dev_image(f).view, **out.kw())
         compare(out.host(), ctx.surf_read(), ref.push(f), "push %d" % t)
     for t in range(4):
         push(t)
@@ -408,12 +390,12 @@ def test_two_slots(ctx):
     ra, rb = S.SurfRef(wa, ha, la, pa, ctx.jet_lut()), S.SurfRef(wb, hb, lb, pb, ctx.jet_lut())
     ctx.surf_open(wa, ha, la, stream=0, **pa.kw())
     ctx.surf_open(wb, hb, lb, stream=1, **pb.kw())
-    oa, ob = Outputs(ra.L, wa, ha), Outputs(rb.L, wb, hb)
+    oa, ob = outputs(ra.L, wa, ha), outputs(rb.L, wb, hb)
     fb = random_frames(wb, hb, 6, seed=9)
     for t in range(6):
         ia, ib = S.surf_scene(t), fb[t]
-        ctx.surf_push(dev_image(ia)[0], stream=0, **oa.kw())
-        ctx.surf_push(dev_image(ib)[0], stream=1, **ob.kw())
+        ctx.surf_push(dev_image(ia).view, stream=0, **oa.kw())
+        ctx.surf_push(dev_image(ib).view, stream=1, **ob.kw())
         compare(oa.host(), ctx.surf_read(stream=0), ra.push(ia), "slot 0, push %d" % t)
         compare(ob.host(), ctx.surf_read(stream=1), rb.push(ib), "slot 1, push %d" % t)
     ctx.surf_close(stream=1)
@@ -427,13 +409,13 @@ def test_product_object(ctx):
     with Surf(ctx, w, h, lines=S.scene_lines(), **S.SCENE.kw()) as sf:
         f = S.surf_scene(0)
         sd = torch.zeros((h, w), dtype=torch.uint8, device="cuda")
-        sf.push(dev_image(f)[0], sd=sd)
+        sf.push(dev_image(f).view, sd=sd)
         want = ref.push(f)
         rl, rc, rs = sf.read()
         assert rl.tobytes() == want["lines"].tobytes() and rs["pushes"] == 1 and np.array_equal(sd.cpu().numpy(), want["sd"])
         assert sf.info()["pushes"] == 1 and sf.table()[0].size == len(ref.table) and sf.prims().shape == (ref.L - 1 + 32, 32)
         with pytest.raises(ValueError):
-            sf.push(dev_image(np.repeat(f[..., None], 3, axis=2))[0])            # a colour frame into a grey session
+            sf.push(dev_image(np.repeat(f[..., None], 3, axis=2)).view)            # a colour frame into a grey session
         sf.set(200, 10, 400, 950, 30, 250)
         sf.reset()
         assert sf.info()["pushes"] == 0
@@ -447,8 +429,7 @@ def test_refusals_and_lifecycle(ctx):
     lines, good = S.scene_lines(), S.Params(**dict(S.asdict(S.SCENE), window=4))
     L = len(lines)
     ctx.surf_close()
-    lib, hdl = ctx._lib, ctx._h
-    null = C.c_void_p(None)
+    lib, hdl = raw(ctx)
 
     def text():
         return (lib.rcflow_last_error() or b"").decode()
@@ -501,9 +482,8 @@ def test_refusals_and_lifecycle(ctx):
         with pytest.raises(RcflowError):
             ctx.surf_open(w, h, lines, **dict(kw, **bad))
     assert ctx.surf_info() == before
-    img, _ = dev_image(S.surf_scene(1))
+    img = dev_image(S.surf_scene(1)).view
     big = torch.zeros(8 * h * w + 4096, dtype=torch.uint8, device="cuda")
-    ptr = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
     N = (null, 0)
 
     def push(image=None, step=w, ch=1, now=N, surf=N, q=N, mean=N, sd=N, pic=N, rec=null, chan=null, summ=null, slot=0):
@@ -532,7 +512,7 @@ def test_refusals_and_lifecycle(ctx):
     assert text().startswith("rcflow_surf_prims_dev")
     assert ctx.surf_info() == before
     # nothing was queued and nothing changed: the second push gives what the statement gives
-    out = Outputs(L, w, h)
+    out = outputs(L, w, h)
     ctx.surf_push(img, **out.kw())
     compare(out.host(), ctx.surf_read(), ref.push(S.surf_scene(1)), "(after the refusals)")
     # an accepted boundary: q begins at the first byte after now's range, in one allocation

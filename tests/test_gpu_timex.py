@@ -7,13 +7,13 @@ import pytest
 import torch
 
 import _timex_ref as R
+from _dev import EINVAL, ESIZE, ESTATE
 from ripcurrents_amd import synth
 from ripcurrents_amd._lib import RcflowError
 
 pytestmark = pytest.mark.gpu
 
 ALL = ("mean", "average", "bright", "dark")
-EINVAL, ESIZE, ESTATE = -1, -5, -6
 
 
 def colour_clip(w, h, frames, seed=7):

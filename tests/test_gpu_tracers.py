@@ -1,35 +1,28 @@
 """Tracer lines on the device (tracer_kernels.hip, draw_kernels.hip): positions against the host classes of api.py driven
 with the same frames, the canvas and the drawing stage against the numpy statement (tests/_tracers_ref.py); everything is
 compared after every push, bit for bit."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
 import _cpp
 import _tracers_ref as R
+from _dev import EINVAL, ESIZE, ESTATE, Padded
 from ripcurrents_amd import synth
 from ripcurrents_amd._lib import RcflowError
 from ripcurrents_amd.api import DRAW_PRIM_DTYPE, PopulationMap, Streakline, Timeline
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EINVAL, ESIZE, ESTATE = -1, -5, -6
 f32 = np.float32
 
 
-def padded(a, pad, fill=0):
-    """a device copy of the host array `a` as a view into rows that are `pad` elements longer; returns (view, whole)"""
-    t = torch.as_tensor(a)
-    whole = torch.full((t.shape[0], t.shape[1] * (t.shape[2] if t.dim() == 3 else 1) + pad), fill, dtype=t.dtype)
-    whole[:, :whole.shape[1] - pad] = t.reshape(t.shape[0], -1)
-    whole = whole.cuda()
-    view = whole[:, :whole.shape[1] - pad].view(t.shape) if t.dim() == 2 else \
-        torch.as_strided(whole, tuple(t.shape), (whole.stride(0), t.shape[2], 1))
-    return view, whole
+def padded_rows(a, pad, fill=0):
+    """a device copy of the host array `a` as a view into rows that are `pad` elements (not pixels) longer; returns (view, the
+    Padded of the rows as (h, w * channels))"""
+    a = np.asarray(a)
+    whole = Padded.of(a.reshape(a.shape[0], -1), pad, fill)
+    return torch.as_strided(whole.base, a.shape, (whole.base.stride(0),) + ((a.shape[2], 1) if a.ndim == 3 else (1,))), whole
 
 
 def frame_bgr(w, h, t):
@@ -82,7 +75,7 @@ def check_push(ctx, host, ref, canvas_dev, canvas_in, whole=None, what="", strea
     assert np.array_equal(got[~touched], canvas_in[~touched]), "a pixel outside every primitive changed " + what
     assert touched.any()
     if whole is not None:
-        assert (whole[:, canvas_dev.shape[1] * 3:] == 0xA5).all().item(), "padding bytes changed " + what
+        whole.check("the canvas " + what)
 
 
 @pytest.mark.parametrize("w,h,pad", [(640, 480, 0), (333, 251, 5)])
@@ -95,9 +88,9 @@ def test_lk_session_against_the_host_classes(ctx, w, h, pad):
     info = ctx.tracers_info()
     assert info["lines"] == 8 and info["points"] == 5 + 10 + 7 + 12 and not info["primed"] and info["pushes"] == 0
     for t in range(n):
-        gray, _ = padded(clip[t], pad)
+        gray, _ = padded_rows(clip[t], pad)
         cin = frame_bgr(w, h, t)
-        canvas, whole = padded(cin, pad, 0xA5)
+        canvas, whole = padded_rows(cin, pad, 0xA5)
         moved = ctx.tracers_push(gray=gray, canvas=canvas)
         assert moved == (t > 0)
         if t == 0:
@@ -127,12 +120,12 @@ def run_flow_session(ctx, w, h, fields, resident, max_vertices=64, pad=0, stream
     out = []
     for t, f in enumerate(fields):
         cin = frame_bgr(w, h, t)
-        canvas, whole = padded(cin, pad, 0xA5)
+        canvas, whole = padded_rows(cin, pad, 0xA5)
         if resident:
             d = torch.as_tensor(f).cuda()
             ctx.tracers_push(flow=d, canvas=canvas, stream=stream)
         else:
-            d, _ = padded(f, 2 * pad)
+            d, _ = padded_rows(f, 2 * pad)
             ctx.tracers_push(flow=d, canvas=canvas, stream=stream)
         for o in host:
             o.run(ctx, f, w, h, dt=1.0, stream=stream)
@@ -398,11 +391,8 @@ def test_trace_of_advect_points_drawn(ctx):
 def test_cpp_tracers_against_ctypes(ctx, tmp_path):
     """rc::Tracers (include/rcflow_module.hpp) compiled as tests/cpp's programs are and run on a seeded frame sequence; the
     vertices and the frame checksums it prints equal the ctypes session's on the same frames."""
-    exe = _cpp.build("test_tracers", tmp_path, gxx=True)
     w, h, n = 320, 200, 6
-    r = subprocess.run([exe, str(w), str(h), str(n)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "test_tracers: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
-    lines = [l for l in r.stdout.splitlines() if l.startswith("push ")]
+    lines = [l for l in _cpp.run("test_tracers", tmp_path, w, h, n, gxx=True).splitlines() if l.startswith("push ")]
     assert len(lines) == n
     ctx.tracers_open(w, h, "lk", max_lines=8, max_vertices=6)
     for i in range(5):

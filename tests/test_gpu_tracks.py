@@ -3,8 +3,6 @@ of the table (all integer fields, mean_fx / mean_fy as bits), track_of_label, th
 (through rcflow_tracks_read) is compared with np.array_equal.  No tolerance anywhere.  Outputs and the padded label image sit
 between fence bytes."""
 import itertools
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,38 +12,11 @@ import _cpp
 import _regions_ref as R
 import _tracers_ref as TR
 import _tracks_ref as T
+from _dev import EINVAL, ESIZE, ESTATE, Fenced
 from ripcurrents_amd._lib import RC_REGIONS_LAUNCHES, RC_TRACKS_LAUNCHES, RcflowError
 from ripcurrents_amd.api import DRAW_PRIM_DTYPE, TRACK_DTYPE
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EINVAL, ESIZE, ESTATE = -1, -5, -6
-FENCE = 0xA5
-
-
-class Fenced:
-    """h rows of `row` elements inside a device allocation filled with FENCE bytes: `lead` elements before the first row (an
-    unaligned base), `pad` elements after every row, 64 bytes after the last."""
-
-    def __init__(self, h, row, dtype, pad=0, lead=0, fill=None):
-        self.h, self.row, self.pad, self.lead = h, row, pad, lead
-        self.item = torch.empty((), dtype=dtype).element_size()
-        self.step = row + pad
-        self.bytes = torch.full(((lead + h * self.step) * self.item + 64,), FENCE, dtype=torch.uint8, device="cuda")
-        self.view = torch.as_strided(self.bytes[:(lead + h * self.step) * self.item].view(dtype), (h, row), (self.step, 1), lead)
-        if fill is not None:
-            self.view.copy_(torch.as_tensor(np.ascontiguousarray(fill).reshape(h, row)).cuda())
-
-    def check(self, what):
-        b = self.bytes.cpu().numpy()
-        n = self.h * self.step * self.item
-        assert (b[:self.lead * self.item] == FENCE).all() and (b[self.lead * self.item + n:] == FENCE).all(), "fence bytes around %s changed" % what
-        rows = b[self.lead * self.item:self.lead * self.item + n].reshape(self.h, self.step * self.item)
-        assert (rows[:, self.row * self.item:] == FENCE).all(), "row padding of %s was written" % what
-
-    def numpy(self):
-        return self.view.cpu().numpy()
 
 
 def same_table(got, want, what):
@@ -448,11 +419,8 @@ def test_push_refuses_fewer_records_than_max_regions(ctx):
 def test_cpp_tracks_against_the_statement(ctx, tmp_path):
     """rc::Tracks (include/rcflow_module.hpp) compiled as tests/cpp's programs are and run on seeded masks; what it prints
     equals the numpy statements on the same masks."""
-    exe = _cpp.build("test_tracks", tmp_path, gxx=True)
     w, h, n = 200, 120, 9
-    r = subprocess.run([exe, str(w), str(h), str(n)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "test_tracks: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
-    lines = [l for l in r.stdout.splitlines() if l.startswith("push ")]
+    lines = [l for l in _cpp.run("test_tracks", tmp_path, w, h, n, gxx=True).splitlines() if l.startswith("push ")]
     assert len(lines) == n
 
     def fnv(a):

@@ -6,12 +6,12 @@ import torch
 
 import _framewarp_ref as W
 import _trackstab_ref as R
+from _dev import EINVAL, ESIZE, ESTATE
 from ripcurrents_amd import synth
 from ripcurrents_amd._lib import RcflowError
 
 pytestmark = pytest.mark.gpu
 
-EINVAL, ESIZE, ESTATE = -1, -5, -6
 NAMES = {v: k for k, v in R.MODELS.items()}
 
 

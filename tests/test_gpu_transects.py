@@ -9,69 +9,28 @@ import pytest
 import torch
 
 import _transects_ref as R
+from _dev import EINVAL, ESIZE, ESTATE, NULL as null, SENTINEL, Outputs, Padded, ptr, raw, reference, ulps
 from ripcurrents_amd._lib import RC_TRANSECTS_LAUNCHES, RC_TRANSECTS_MAX_STATE_BYTES, RcflowError, TransectLine, TransectsParams
 from ripcurrents_amd.api import TRANSECT_DTYPE, TRANSECTS_SUMMARY, Transects
 
 pytestmark = pytest.mark.gpu
 
-EINVAL, ESIZE, ESTATE = -1, -5, -6
-SENTINEL = 0xA5
-_REF = {}
-
-
-def reference(ctx, name):
-    """the statement's outputs of a case, computed once for the whole file and never changed"""
-    if name not in _REF:
-        case = R.cases()[name]
-        _REF[name] = (case,) + R.run_case(case, ctx.jet_lut())
-    return _REF[name]
-
-
 def dev_frames(frames, pad, fill):
-    """all frames of a case in one upload, rows `pad` pixels longer than the frame"""
-    if frames is None:
-        return None
-    a = np.stack(frames)
-    base = torch.full(a.shape[:2] + (a.shape[2] + pad,) + a.shape[3:], fill, dtype=torch.as_tensor(a[:1]).dtype, device="cuda")
-    base[:, :, :a.shape[2]] = torch.as_tensor(a).cuda()
-    return [base[t, :, :a.shape[2]] for t in range(a.shape[0])]
+    """all frames of a case in one upload, rows `pad` pixels longer than the frame and `fill` there"""
+    return None if frames is None else Padded.stack(frames, pad, fill)
 
 
-class Outputs:
-    def __init__(self, L, S, T, gray, flow, pad=0):
-        self.pad, self.S = pad, S
-        self.records = torch.full((L * 64,), SENTINEL, dtype=torch.uint8, device="cuda")
-        self.sums = torch.full((L * 16,), -1, dtype=torch.int64, device="cuda")
-        self.profile = torch.full((S * 2,), -7.0, dtype=torch.float32, device="cuda")
-        self.summary = torch.full((8,), -1, dtype=torch.int64, device="cuda")
-        self.stack_base = torch.full((T, S + pad), SENTINEL, dtype=torch.uint8, device="cuda") if gray else None
-        self.hov_base = torch.full((T, S + pad, 3), SENTINEL, dtype=torch.uint8, device="cuda") if flow else None
-
-    def kw(self):
-        d = dict(records=self.records, sums=self.sums, profile=self.profile, summary=self.summary)
-        if self.stack_base is not None:
-            d["stack"] = self.stack_base[:, :self.S]
-        if self.hov_base is not None:
-            d["hov"] = self.hov_base[:, :self.S]
-        return d
-
-    def host(self):
-        d = {k: v.cpu().numpy() for k, v in self.kw().items()}
-        for base in (self.stack_base, self.hov_base):
-            if self.pad and base is not None:
-                assert (base[:, self.S:] == SENTINEL).all(), "row padding was written"
-        d["records"] = d["records"].view(TRANSECT_DTYPE)
-        d["sums"], d["profile"] = d["sums"].reshape(-1, 16), d["profile"].reshape(-1, 2)
-        return d
+def views(d):
+    d["records"], d["sums"], d["profile"] = d["records"].view(TRANSECT_DTYPE), d["sums"].reshape(-1, 16), d["profile"].reshape(-1, 2)
 
 
-def ulps(a, b):
-    """units in the last place between float32 arrays; NaN against NaN is 0"""
-    def ordered(x):
-        i = np.ascontiguousarray(x, np.float32).view(np.int32).astype(np.int64)
-        return np.where(i < 0, -(i & 0x7FFFFFFF), i)
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    return np.where(np.isnan(a) & np.isnan(b), 0, np.abs(ordered(a) - ordered(b)))
+def outputs(L, S, T, gray, flow, pad=0):
+    """the time stack only where there are grey frames, the Hovmoeller picture only where there is flow"""
+    planes = dict(stack=((T, S), torch.uint8)) if gray else {}
+    if flow:
+        planes["hov"] = ((T, S, 3), torch.uint8)
+    return Outputs(planes, dict(records=((L * 64,), torch.uint8, None), sums=((L * 16,), torch.int64, -1), profile=((S * 2,), torch.float32, -7.0),
+                                summary=((8,), torch.int64, -1)), pad, views)
 
 
 def compare(got, read, want, what):
@@ -105,7 +64,7 @@ def check_sums(ctx, ref, stream, what):
 
 def run(ctx, name, stream=0, compute_all=True):
     """a case through the device session; compares at every computing push.  -> the device outputs of the last one"""
-    case, _, outs = reference(ctx, name)
+    case, _, outs = reference(R, ctx, name)
     p = case.p
     ctx.transects_open(case.w, case.h, case.lines, stream=stream, **p.kw())
     info = ctx.transects_info(stream=stream)
@@ -114,7 +73,7 @@ def run(ctx, name, stream=0, compute_all=True):
     table, geom = ctx.transects_table(stream=stream)
     assert table.tobytes() == check.table.tobytes() and geom.tobytes() == check.geom.tobytes()
     gray, flow = dev_frames(case.gray, case.pad, SENTINEL), dev_frames(case.flow, case.pad, 3.0)
-    out = Outputs(check.L, check.S, p.window, gray is not None, flow is not None, case.pad)
+    out = outputs(check.L, check.S, p.window, gray is not None, flow is not None, case.pad)
     got = None
     for t in range(len(outs)):
         g, f = gray[t] if gray else None, flow[t] if flow else None
@@ -137,7 +96,7 @@ def run(ctx, name, stream=0, compute_all=True):
 def test_case_against_the_statement(ctx, name):
     got = run(ctx, name)
     ctx.transects_close()
-    case, ref, outs = reference(ctx, name)
+    case, ref, outs = reference(R, ctx, name)
     flags = [o["records"]["flags"] for o in outs]
     if name == "three":                                           # the first lag pushes are EMPTY; bad samples and jets occur
         assert all((f == R.EMPTY).all() for f in flags[:case.p.lag]) and not (flags[-1] & R.EMPTY).any()
@@ -153,10 +112,10 @@ def test_case_against_the_statement(ctx, name):
 
 def test_the_flow_ring_holds_the_statements_samples(ctx):
     """the first push's window mean is its row of the ring: (ut, un) of every sample, NaN and infinities included"""
-    case, ref, outs = reference(ctx, "three")
+    case, ref, outs = reference(R, ctx, "three")
     with Transects(ctx, case.w, case.h, lines=case.lines, **case.p.kw()) as ts:
-        o = Outputs(ref.L, ref.S, case.p.window, True, True)
-        ts.push(dev_frames(case.gray[:1], 0, 0)[0], dev_frames(case.flow[:1], 0, 0.0)[0], profile=o.profile)
+        o = outputs(ref.L, ref.S, case.p.window, True, True)
+        ts.push(dev_frames(case.gray[:1], 0, 0)[0], dev_frames(case.flow[:1], 0, 0.0)[0], profile=o.t["profile"])
         row = R.TransectsRef(case.w, case.h, case.lines, case.p).sample_flow(case.flow[0])
         u = ulps(o.host()["profile"], row)
         print("%d of %d ring floats differ" % (int((u > 0).sum()), u.size))
@@ -181,12 +140,12 @@ def test_result_does_not_depend_on_which_pushes_computed(ctx):
 
 
 def test_each_output_alone(ctx):
-    case, ref, outs = reference(ctx, "three")
+    case, ref, outs = reference(R, ctx, "three")
     want = outs[2]
     gray, flow = dev_frames(case.gray[:3], 0, 0), dev_frames(case.flow[:3], 0, 0.0)
     with Transects(ctx, case.w, case.h, lines=case.lines, **case.p.kw()) as ts:
         for name in ("records", "sums", "profile", "stack", "hov", "summary"):
-            o = Outputs(ref.L, ref.S, case.p.window, True, True)
+            o = outputs(ref.L, ref.S, case.p.window, True, True)
             ts.reset()
             ts.push(gray[0], flow[0])
             ts.push(gray[1], flow[1])
@@ -203,13 +162,13 @@ def test_each_output_alone(ctx):
                 if other != name:
                     assert (got[other] == SENTINEL).all(), other + " was written"
             if name != "records":
-                assert (o.records == SENTINEL).all()
+                assert (o.t["records"] == SENTINEL).all()
             if name != "sums":
-                assert (o.sums == -1).all()
+                assert (o.t["sums"] == -1).all()
             if name != "profile":
-                assert (o.profile == -7.0).all()
+                assert (o.t["profile"] == -7.0).all()
             if name != "summary":
-                assert (o.summary == -1).all()
+                assert (o.t["summary"] == -1).all()
             if name in ("stack", "hov"):
                 assert ts.read()[1] == dict.fromkeys(TRANSECTS_SUMMARY, 0)       # a picture alone computes no records
             else:
@@ -241,9 +200,9 @@ def test_python_class_holds_its_arguments_to_the_session(ctx):
 
 # ---------------------------------------------------------------------------- the profile
 def test_profile_books_the_launches(ctx):
-    case, ref, outs = reference(ctx, "three")
+    case, ref, outs = reference(R, ctx, "three")
     gray, flow = dev_frames(case.gray[:4], 0, 0), dev_frames(case.flow[:4], 0, 0.0)
-    o = Outputs(ref.L, ref.S, case.p.window, True, True)
+    o = outputs(ref.L, ref.S, case.p.window, True, True)
     ctx.transects_open(case.w, case.h, case.lines, **case.p.kw())
     ctx.profile_enable(True)
     ctx.profile_reset()
@@ -253,7 +212,7 @@ def test_profile_books_the_launches(ctx):
     torch.cuda.synchronize()
     assert read() == {"transects@0": 3}
     ctx.profile_reset()
-    ctx.transects_push(gray[3], flow[3], summary=o.summary)
+    ctx.transects_push(gray[3], flow[3], summary=o.t["summary"])
     torch.cuda.synchronize()
     assert read() == {"transects@0": 1, "transects@1": 1}
     ctx.profile_reset()
@@ -269,7 +228,7 @@ def test_profile_books_the_launches(ctx):
 
 # ---------------------------------------------------------------------------- arguments and lifecycle
 def test_refusals_and_lifecycle(ctx):
-    case, ref0, outs = reference(ctx, "three")
+    case, ref0, outs = reference(R, ctx, "three")
     p, w, h, lines = case.p, case.w, case.h, case.lines
     good = p.kw()
     L, S, T = ref0.L, ref0.S, p.window
@@ -279,8 +238,7 @@ def test_refusals_and_lifecycle(ctx):
         with pytest.raises(RcflowError) as e:
             call()
         assert e.value.code == ESTATE and str(e.value).split(": ", 1)[1]
-    lib, hdl = ctx._lib, ctx._h
-    null = C.c_void_p(None)
+    lib, hdl = raw(ctx)
     assert lib.rcflow_transects_push_dev(hdl, 0, null, 0, null, 0, null, null, null, null, 0, null, 0, null) == ESTATE       # a push before open
     nan, inf = float("nan"), float("inf")
     for bad in (dict(window=1), dict(window=4097), dict(gray=False, flow=False), dict(lag=0), dict(lag=9), dict(range=-1), dict(range=17),
@@ -313,7 +271,7 @@ def test_refusals_and_lifecycle(ctx):
     ctx.transects_open(w, h, lines, **good)
     ref = R.TransectsRef(w, h, lines, R.Params(**R.asdict(p)), ctx.jet_lut())
     gray, flow = dev_frames(case.gray, 0, 0), dev_frames(case.flow, 0, 0.0)
-    o = Outputs(L, S, T, True, True)
+    o = outputs(L, S, T, True, True)
     for t in range(7):
         ctx.transects_push(gray[t], flow[t])
         ref.push(case.gray[t], case.flow[t], compute=False)
@@ -334,7 +292,6 @@ def test_refusals_and_lifecycle(ctx):
 
     g, f = gray[7], flow[7]
     buf = torch.zeros(4 * T * S + 4096, dtype=torch.uint8, device="cuda")
-    ptr = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
 
     def push(gr=(ptr(g), w), fl=(ptr(f), 8 * w), rec=null, sums=null, prof=null, stack=(null, 0), hov=(null, 0), summ=null, slot=0):
         return lib.rcflow_transects_push_dev(hdl, slot, gr[0], gr[1], fl[0], fl[1], rec, sums, prof, stack[0], stack[1], hov[0], hov[1], summ)

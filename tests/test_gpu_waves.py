@@ -2,8 +2,6 @@
 accumulators, the cell sums, the bin map, the summary and every integer of the records bit for bit; the records' floats within
 one unit in the last place; the picture wherever the statement's depth is not within that of a colour's boundary."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,69 +9,27 @@ import torch
 
 import _cpp
 import _waves_ref as R
+from _dev import EINVAL, ESIZE, ESTATE, NULL as null, SENTINEL, Outputs, Padded, ordered, ptr, raw, reference
 from ripcurrents_amd._lib import RC_WAVES_LAUNCHES, RC_WAVES_MAX_STATE_BYTES, RcflowError, WavesParams
 from ripcurrents_amd.api import WAVE_CELL_DTYPE, WAVES_SUMMARY, Waves
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EINVAL, ESIZE, ESTATE = -1, -5, -6
-SENTINEL = 0xA5
 FLOATS = ("freq_hz", "kx", "ky", "celerity", "depth", "quality")
-_REF = {}
 
 
-def reference(ctx, name):
-    """the statement's outputs of a case, computed once for the whole file and never changed"""
-    if name not in _REF:
-        case = R.cases()[name]
-        _REF[name] = (case,) + R.run_case(case, ctx.jet_lut())
-    return _REF[name]
-
-
-def padded(shape, dtype, pad):
-    """A device tensor of `shape` that is a view into rows `pad` pixels longer, the whole filled with a sentinel."""
-    base = torch.full((shape[0], shape[1] + pad) + tuple(shape[2:]), SENTINEL, dtype=dtype, device="cuda")
-    return base, base[:, :shape[1]]
-
-
-def dev_frames(frames, pad):
-    """all frames of a case in one upload, rows `pad` bytes longer than the frame"""
-    a = np.stack(frames)
-    base = torch.full((a.shape[0], a.shape[1], a.shape[2] + pad), SENTINEL, dtype=torch.uint8, device="cuda")
-    base[:, :, :a.shape[2]] = torch.as_tensor(a).cuda()
-    return [base[t, :, :a.shape[2]] for t in range(a.shape[0])]
+dev_frames = Padded.stack
 
 
 def dev_image(a, pad):
     return dev_frames([a], pad)[0]
 
 
-class Outputs:
-    def __init__(self, w, h, gx, gy, K, pad=0):
-        self.pad = pad
-        self.bin_base, self.bin_map = padded((h, w), torch.uint8, pad)
-        self.vis_base, self.vis = padded((h, w, 3), torch.uint8, pad)
-        self.cells = torch.full((gy * gx * 32,), SENTINEL, dtype=torch.uint8, device="cuda")
-        self.sums = torch.full((gy, gx, K, 6), -1, dtype=torch.int64, device="cuda")
-        self.summary = torch.full((8,), -1, dtype=torch.int64, device="cuda")
-        self.gx, self.gy = gx, gy
-
-    def kw(self):
-        return dict(cells=self.cells, sums=self.sums, bin_map=self.bin_map, vis=self.vis, summary=self.summary)
-
-    def host(self):
-        if self.pad:
-            w = self.bin_map.shape[1]
-            assert (self.bin_base[:, w:] == SENTINEL).all() and (self.vis_base[:, w:] == SENTINEL).all(), "row padding was written"
-        return dict(cells=self.cells.cpu().numpy().view(WAVE_CELL_DTYPE).reshape(self.gy, self.gx), sums=self.sums.cpu().numpy(),
-                    bin_map=self.bin_map.cpu().numpy(), vis=self.vis.cpu().numpy(), summary=self.summary.cpu().numpy())
-
-
-def ordered(a):
-    """float32 -> integers in which neighbouring floats differ by one"""
-    i = np.ascontiguousarray(a, np.float32).view(np.int32).astype(np.int64)
-    return np.where(i < 0, -(i & 0x7FFFFFFF), i)
+def outputs(w, h, gx, gy, K, pad=0):
+    def views(d):
+        d["cells"] = d["cells"].view(WAVE_CELL_DTYPE).reshape(gy, gx)
+    return Outputs(dict(bin_map=((h, w), torch.uint8), vis=((h, w, 3), torch.uint8)),
+                   dict(cells=((gy * gx * 32,), torch.uint8, None), sums=((gy, gx, K, 6), torch.int64, -1), summary=((8,), torch.int64, -1)), pad, views)
 
 
 def doubtful_cells(want, vis_max_depth):
@@ -103,7 +59,7 @@ def compare(got, read, want, case, vis_max_depth, what):
 
 def run(ctx, name, stream=0, compute_all=False):
     """a case through the device session; compares at every computing push.  -> the device outputs of the last one"""
-    case, ref, outs = reference(ctx, name)
+    case, ref, outs = reference(R, ctx, name)
     p = case.p
     ctx.waves_open(case.w, case.h, stream=stream, **p.kw())
     tc, ts = ctx.waves_table(stream=stream)
@@ -114,7 +70,7 @@ def run(ctx, name, stream=0, compute_all=False):
     mask = None if case.mask is None else dev_image(case.mask, case.pad)
     want = dict(outs)
     vis_max = p.vis_max_depth
-    out = Outputs(case.w, case.h, p.grid_x, p.grid_y, len(p.bins), case.pad)
+    out = outputs(case.w, case.h, p.grid_x, p.grid_y, len(p.bins), case.pad)
     got = None
     check = R.WavesRef(case.w, case.h, p) if len(case.frames) <= 300 else None      # the accumulators after every computing push
     for t, f in enumerate(frames, 1):
@@ -158,7 +114,7 @@ def test_result_does_not_depend_on_which_pushes_computed(ctx):
 
 
 def test_each_output_alone(ctx):
-    case, ref, outs = reference(ctx, "three-kinds")
+    case, ref, outs = reference(R, ctx, "three-kinds")
     p = case.p
     with Waves(ctx, case.w, case.h, **p.kw()) as wv:
         frames = dev_frames(case.frames[:16], 0)
@@ -168,7 +124,7 @@ def test_each_output_alone(ctx):
         want = outs[0][1]
         wv.push(frames[15])
         for name in ("cells", "sums", "bin_map", "vis", "summary"):
-            o = Outputs(case.w, case.h, p.grid_x, p.grid_y, len(p.bins))
+            o = outputs(case.w, case.h, p.grid_x, p.grid_y, len(p.bins))
             ctx.waves_reset()
             for f in frames[:15]:
                 wv.push(f)
@@ -184,7 +140,7 @@ def test_each_output_alone(ctx):
                 if other != name:
                     assert (got[other] == SENTINEL).all(), "%s was written" % other
             if name != "cells":
-                assert (o.cells == SENTINEL).all()
+                assert (o.t["cells"] == SENTINEL).all()
             if name != "summary":
                 assert (got["summary"] == -1).all()
             assert [wv.read()[2][k] for k in WAVES_SUMMARY] == [int(v) for v in want["summary"]]
@@ -192,10 +148,10 @@ def test_each_output_alone(ctx):
 
 # ---------------------------------------------------------------------------- the profile
 def test_profile_books_the_launches(ctx):
-    case, ref, outs = reference(ctx, "w7")
+    case, ref, outs = reference(R, ctx, "w7")
     p = case.p
     frames = dev_frames(case.frames[:4], 0)
-    o = Outputs(case.w, case.h, p.grid_x, p.grid_y, len(p.bins))
+    o = outputs(case.w, case.h, p.grid_x, p.grid_y, len(p.bins))
     ctx.waves_open(case.w, case.h, **p.kw())
     ctx.profile_enable(True)
     ctx.profile_reset()
@@ -205,7 +161,7 @@ def test_profile_books_the_launches(ctx):
     torch.cuda.synchronize()
     assert read() == {"waves@0": 2}
     ctx.profile_reset()
-    ctx.waves_push(frames[2], summary=o.summary)
+    ctx.waves_push(frames[2], summary=o.t["summary"])
     torch.cuda.synchronize()
     assert read() == {"waves@0": 1, "waves@1": 1}
     ctx.profile_reset()
@@ -220,7 +176,7 @@ def test_profile_books_the_launches(ctx):
 
 # ---------------------------------------------------------------------------- arguments and lifecycle
 def test_refusals_and_lifecycle(ctx):
-    case, ref0, outs = reference(ctx, "w7")
+    case, ref0, outs = reference(R, ctx, "w7")
     p, w, h = case.p, case.w, case.h
     good = p.kw()
     gx, gy, K = p.grid_x, p.grid_y, len(p.bins)
@@ -229,8 +185,7 @@ def test_refusals_and_lifecycle(ctx):
         with pytest.raises(RcflowError) as e:
             call()
         assert e.value.code == ESTATE and str(e.value).split(": ", 1)[1]
-    lib, hdl = ctx._lib, ctx._h
-    null = C.c_void_p(None)
+    lib, hdl = raw(ctx)
     assert lib.rcflow_waves_push_dev(hdl, 0, null, 0, null, 0, null, null, null, 0, null, 0, null) == ESTATE
     nan, inf = float("nan"), float("inf")
     for bad in (dict(window=1), dict(window=2, bin_lo=1, bin_hi=1), dict(window=4097), dict(bin_lo=0), dict(bin_lo=4), dict(bin_hi=4),
@@ -259,7 +214,7 @@ def test_refusals_and_lifecycle(ctx):
     ctx.waves_open(w, h, **good)
     ref = R.WavesRef(w, h, R.Params(**good), ctx.jet_lut())
     frames = dev_frames(case.frames, 0)
-    o = Outputs(w, h, gx, gy, K)
+    o = outputs(w, h, gx, gy, K)
     for t in range(9):
         ctx.waves_push(frames[t])
         ref.push(case.frames[t], compute=False)
@@ -280,7 +235,6 @@ def test_refusals_and_lifecycle(ctx):
     g = frames[9]
     mask = torch.ones((h, w), dtype=torch.uint8, device="cuda")
     buf = torch.zeros(max(3 * w * h, gy * gx * K * 48) + 1024, dtype=torch.uint8, device="cuda")
-    ptr = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
 
     def push(gray=None, step=w, msk=(null, 0), cells=null, sums=null, bm=(null, 0), vis=(null, 0), summ=null, slot=0):
         return lib.rcflow_waves_push_dev(hdl, slot, ptr(g) if gray is None else gray, step, msk[0], msk[1], cells, sums, bm[0], bm[1],
@@ -335,11 +289,11 @@ def test_refusals_and_lifecycle(ctx):
     ctx.waves_close(stream=1)
     # a bin above 255 does not fit the bin map's byte: the map is refused, the other outputs are not
     ctx.waves_open(w, h, **dict(good, window=600, bin_lo=255, bin_hi=256))
-    o2 = Outputs(w, h, gx, gy, 2)
+    o2 = outputs(w, h, gx, gy, 2)
     with pytest.raises(RcflowError) as e:
-        ctx.waves_push(frames[0], bin_map=o2.bin_map)
+        ctx.waves_push(frames[0], bin_map=o2.t["bin_map"])
     assert e.value.code == EINVAL and ctx.waves_info()["pushes"] == 0 and not ctx.waves_spectrum().any()
-    ctx.waves_push(frames[0], cells=o2.cells, sums=o2.sums, vis=o2.vis, summary=o2.summary)
+    ctx.waves_push(frames[0], **o2.kw(only=("cells", "sums", "vis", "summary")))
     assert ctx.waves_info()["pushes"] == 1 and o2.host()["summary"][4] == 1 and (o2.host()["bin_map"] == SENTINEL).all()
     ctx.waves_close()
     ctx.waves_close()                                             # closing twice is fine
@@ -349,13 +303,10 @@ def test_refusals_and_lifecycle(ctx):
 def test_cpp_waves_against_the_statement(ctx, tmp_path):
     """rc::Waves (include/rcflow_module.hpp) compiled with the flags of tests/cpp's test_module and run on frames it makes itself
     from integers; the summaries, bins, flags and checksums it prints equal the statement's."""
-    exe = _cpp.build("test_waves", tmp_path)
     n = 40
-    r = subprocess.run([exe, str(n)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "test_waves: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [l.split() for l in _cpp.run("test_waves", tmp_path, n).splitlines() if l.startswith("push ")]
     case = R.cpp_case(n)
     ref = R.WavesRef(case.w, case.h, case.p, ctx.jet_lut())
-    lines = [l.split() for l in r.stdout.splitlines() if l.startswith("push ")]
     assert len(lines) == n // 5
     k = 0
     for t in range(n):

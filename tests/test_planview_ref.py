@@ -6,14 +6,11 @@ import numpy as np
 import pytest
 
 import _planview_ref as P
+from _dev import bits
 
 f32 = np.float32
 W, H = 97, 53
 DISTORTED = dict(k1=-0.12, k2=0.02)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 # ---------------------------------------------------------------------------- the classes of cells
