@@ -2124,6 +2124,108 @@ int rcflow_surf_close(rc_ctx* ctx, int stream);
 /* never blocks; RC_ESTATE when nothing is open, RC_EINVAL without a buffer */
 int rcflow_surf_info(rc_ctx* ctx, int stream, rc_surf_info* info);
 
+/* ------------------------------------------------------------------ mean flow: mean current, steadiness, spread, seaward-jet mask
+ * What the water does on average over some wave periods, per pixel, and how reliably it does it: the quantity time-averaged
+ * optical-flow rip detection rests on.  A rip neck is a place where the flow is steady (|mean vector| close to the mean speed), fast
+ * enough to matter, and runs seaward; wave orbital motion is fast but unsteady, noise is steady nowhere.  The mask goes straight
+ * into rcflow_regions_push_dev / rcflow_tracks_push_dev, the exact mean field into the kinematics, FTLE, the transects and the plan
+ * view.  The reference has no such product.  tests/_meanflow_ref.py states the following in numpy and the kernels equal it bit for
+ * bit on every output of every push.  Integers are exact; the few float results are computed in double, each operation rounded
+ * on its own; no atan2 and no angle is computed anywhere on the device.
+ *
+ *  Sample.  The input is a flow field, w x h CV_32FC2 (pointer and step multiples of 8); d_flow_xy NULL is the field the slot's
+ *  frame loop left resident (rcflow_stream_flow_ptr), as rcflow_ripmap_push_dev takes it.  A pixel's sample is BAD when a component
+ *  is not finite or fabsf(component) >= 500.0f; otherwise q = (int)rintf(component * 64.0f) per component: 1/64 pixel, |q| <= 32000.
+ *  State.  A ring of W = window entries (int16 u, int16 v) per pixel, u = -32768 for a bad sample; an entry that was never written
+ *  counts as bad.  Per pixel, over the valid entries held: n their count (uint16), Su, Sv (int32: 4096 * 32000 < 2^31), Suu, Svv,
+ *  Suv (int64), Sm = the sum of m = isqrt(u^2 + v^2), the exact floor square root (uint32).  A push at slot c = pushes mod W takes
+ *  the old entry out of the sums if it was valid, puts the new one in if it is valid, and stores the new entry or the bad marker.
+ *  The planes have a row pitch P = w rounded up to 4, so the state is P h (4 W + 38) bytes; beyond RC_MEANFLOW_MAX_STATE_BYTES
+ *  rcflow_meanflow_open answers RC_ESIZE with the count.
+ *  1. "meanflow@0", every push.  After the update a pixel is FILLED when n >= min_fill; a pixel that is not gives zeros in every
+ *     picture.  d_mean 32FC2 (pointer and step multiples of 8): (float)(((double)Su / 64.0) / (double)n), likewise v: the field
+ *     every flow consumer takes.  d_steady 16UC1, per mille: R = isqrt(Su^2 + Sv^2) in int64; st = Sm > 0 ? min(1000, R 1000 / Sm)
+ *     : 0.  d_std 32FC2, the major and the minor standard deviation in pixels: a = n Suu - Su^2, c = n Svv - Sv^2, b = n Suv -
+ *     Su Sv in int64 (n Suu stays below 1.8e16); A, B, C their doubles; r = sqrt((A - C) (A - C) + 4.0 (B B)); l1 = ((A + C) + r)
+ *     0.5; l2 = max(((A + C) - r) 0.5, 0); major = (float)(sqrt(l1) / (64.0 (double)n)), minor the same from l2.  The ellipse's
+ *     orientation is not part of this product.  d_picture 8UC3: entry st 255 / 1000 of rcflow_jet_lut, black where the pixel is
+ *     not filled.  Cells are the opposing-flow map's: grid_x x grid_y of them, w / grid_x by h / grid_y pixels, the remainder
+ *     columns and rows to the last cell, at most RC_RIPMAP_MAX_CELLS.  RC_MEANFLOW_SUMS = 8 int64 per cell: filled pixels | sum of
+ *     n | sum of Su | sum of Sv | sum of Sm | mask pixels | pixels whose newest sample was bad | 0; all over the cell's filled
+ *     pixels, except the bad count, which is over all of them.  G = the sum over all cells of (sum of Su, sum of Sv).
+ *  2. "meanflow@1", every push.  d_mask 8UC1, 255 / 0 (what rcflow_regions_push_dev takes).  A pixel is in when it is filled,
+ *     st >= steady_min, R >= smin_q n in int64 with smin_q = ceil(speed_min * 64) taken on the host, and it runs along D, decided
+ *     in double as the opposing-flow map decides its cells: S = ((double)Su, (double)Sv); D = (dir_x, dir_y) with
+ *     RC_MEANFLOW_DIR_FIXED, D = (-(double)Gx, -(double)Gy) of THIS push with RC_MEANFLOW_DIR_OPPOSED; dot = Sx Dx + Sy Dy;
+ *     cc = Sx Sx + Sy Sy; dd = Dx Dx + Dy Dy; in iff dot > 0 && dot dot >= min_cos2 (cc dd).  With G = 0 nothing is opposed.
+ *     Records, rc_meanflow_cell, closed by the launch's last-arriving workgroup in double: RC_MEANFLOW_EMPTY when the cell has no
+ *     filled pixel (the floats are then 0); mean_x = (float)(((double)(sum of Su) / 64.0) / (double)(sum of n)), mean_y likewise;
+ *     steadiness = (float)((sqrt(sx sx + sy sy) / (double)(sum of Sm)) * 1000.0) with sx, sy the doubles of the sums of Su and Sv,
+ *     and 0 when the sum of Sm is 0.  Summary, 8 int64: filled pixels | mask pixels | newest-bad pixels | Gx | Gy | sum of Sm |
+ *     held = min(pushes, W) | pushes since open / reset. */
+#define RC_MEANFLOW_DIR_FIXED 1          /* rc_meanflow_params::flags: exactly one of the two */
+#define RC_MEANFLOW_DIR_OPPOSED 2
+#define RC_MEANFLOW_EMPTY 1              /* rc_meanflow_cell::flags */
+#define RC_MEANFLOW_MAX_WINDOW 4096
+#define RC_MEANFLOW_SUMS 8
+#define RC_MEANFLOW_MAX_STATE_BYTES (4ull << 30)     /* ring and sum planes */
+#define RC_MEANFLOW_LAUNCHES 2           /* of every push */
+typedef struct rc_meanflow_params {
+    int window;             /* W: 2..RC_MEANFLOW_MAX_WINDOW samples held per pixel */
+    int grid_x, grid_y;     /* cells, as rcflow_ripmap_open */
+    int min_fill;           /* 1..window valid samples make a pixel filled */
+    int steady_min;         /* per mille, 0..1000 */
+    int flags;              /* RC_MEANFLOW_DIR_FIXED or RC_MEANFLOW_DIR_OPPOSED */
+    double speed_min;       /* pixels per field, finite, 0..400: the least |mean vector| of a mask pixel */
+    double min_cos2;        /* K: 0 <= K < 1, the least squared cosine between the mean vector and D */
+    double dir_x, dir_y;    /* D with RC_MEANFLOW_DIR_FIXED: finite, not both 0; not looked at otherwise */
+} rc_meanflow_params;       /* 56 bytes */
+typedef struct rc_meanflow_cell {
+    int flags;              /* RC_MEANFLOW_EMPTY */
+    int filled;             /* filled pixels */
+    int mask;               /* mask pixels */
+    int bad;                /* pixels whose newest sample was bad */
+    float mean_x, mean_y;   /* pixels per field */
+    float steadiness;       /* per mille, of the cell's summed vector */
+    int pad;
+} rc_meanflow_cell;         /* 32 bytes */
+typedef struct rc_meanflow_info {
+    int w, h;
+    rc_meanflow_params prm;            /* as rcflow_meanflow_set left them */
+    int launches_per_push;             /* RC_MEANFLOW_LAUNCHES */
+    int held;                          /* min(pushes, W) */
+    long long pushes;                  /* since open / reset */
+    size_t device_bytes;
+} rc_meanflow_info;
+/* Allocates everything the slot will ever need (the state above, the records).  Re-opening replaces the state; a refused open
+ * leaves the open state as it was.  RC_EINVAL without parameters, for a value outside the ranges above, flags that are not
+ * exactly one of the two directions, a grid that does not fit; RC_ESIZE beyond the context's max_w x max_h or for a state above
+ * RC_MEANFLOW_MAX_STATE_BYTES. */
+int rcflow_meanflow_open(rc_ctx* ctx, int stream, int w, int h, const rc_meanflow_params* prm);
+/* One flow field.  Outputs (device memory, each may be NULL): d_mean and d_std 32FC2 (pointer and step multiples of 8), d_steady
+ * 16UC1 (multiples of 2), d_mask 8UC1, d_picture 8UC3; d_cells cells x rc_meanflow_cell (4-byte aligned), d_sums cells x
+ * RC_MEANFLOW_SUMS int64 and d_summary 8 int64 (8-byte aligned).  Both launches run on every push, because the state must be fed;
+ * what a push gives does not depend on which outputs it or earlier pushes asked for.  No host synchronisation, no device-to-host
+ * copy.  An output whose byte range overlaps the field's or another output's is RC_EINVAL.  Row padding is never written.  Every
+ * refusal is decided before anything is queued and leaves the state as it was; RC_ESTATE before rcflow_meanflow_open, and with
+ * d_flow_xy NULL while no field is resident (RC_ESIZE when the resident field has another size).  RC_EHIP (the runtime refused a
+ * launch) is no refusal: the state is undefined until rcflow_meanflow_reset. */
+int rcflow_meanflow_push_dev(rc_ctx* ctx, int stream, const float* d_flow_xy, size_t flow_step, float* d_mean, size_t mean_step,
+                             uint16_t* d_steady, size_t steady_step, float* d_std, size_t std_step, uint8_t* d_mask, size_t mask_step,
+                             uint8_t* d_picture, size_t picture_step, rc_meanflow_cell* d_cells, long long* d_sums, long long* d_summary);
+/* Blocks until the slot's stream has finished; for hosts and tests.  Each may be NULL: the records, the cell sums and the summary
+ * of the last push (host memory); zeros before the first. */
+int rcflow_meanflow_read(rc_ctx* ctx, int stream, rc_meanflow_cell* cells, long long* sums, long long summary[8]);
+/* steady_min, speed_min, min_cos2, dir_x, dir_y and min_fill from the next push on; RC_EINVAL as rcflow_meanflow_open */
+int rcflow_meanflow_set(rc_ctx* ctx, int stream, int steady_min, double speed_min, double min_cos2, double dir_x, double dir_y, int min_fill);
+/* empties the ring and zeroes the sums, the records, the summary and the push count; keeps the allocation and the parameters as
+ * rcflow_meanflow_set left them; asynchronous, on the slot's stream */
+int rcflow_meanflow_reset(rc_ctx* ctx, int stream);
+/* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
+int rcflow_meanflow_close(rc_ctx* ctx, int stream);
+/* never blocks; RC_ESTATE when nothing is open, RC_EINVAL without a buffer */
+int rcflow_meanflow_info(rc_ctx* ctx, int stream, rc_meanflow_info* info);
+
 /* Display path, ripcurrents.cpp:233-273 (= streamline_displacement / _total_motion / _ratio /
  * _positions, ripcurrents_module.cpp:13-60) on the slot's streamline field (rcflow_advect_field_dev):
  * which 0 = |pt|, 1 = dist, 2 = |pt| / dist; minMaxLoc + convertTo(CV_8UC1, 255/max) +
@@ -2204,7 +2306,7 @@ int rcflow_profile_read(rc_ctx* ctx, int cap, const char** names, int* launches,
 
 /* The same totals under the reference's own bucket names, in the order it prints them (ripcurrents.cpp:103-109,
  * :518-524): farneback, polar, threshold, overlay, erosion, codec, stream ("pathlines").  GPU time of the kernels
- * that do each bucket's work ("overlay" includes the time-exposure images, the 8-bit colour stages, the wave spectra, the shoreline and the surf zone, "farneback" the frame stabilisation, the opposing-flow map, the motion templates, the plan view, the ensemble PIV and the flow kinematics, "stream" the flow map and FTLE and the transects); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
+ * that do each bucket's work ("overlay" includes the time-exposure images, the 8-bit colour stages, the wave spectra, the shoreline and the surf zone, "farneback" the frame stabilisation, the opposing-flow map, the motion templates, the plan view, the ensemble PIV, the flow kinematics and the mean flow, "stream" the flow map and FTLE and the transects); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
  * classification kernels, booked under "threshold"), "codec" is 0 (video decode is host I/O outside the library).
  * names / ms: RC_PROFILE_BUCKETS entries each (either may be NULL).  Returns RC_PROFILE_BUCKETS. */
 #define RC_PROFILE_BUCKETS 7

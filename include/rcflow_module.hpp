@@ -1389,4 +1389,67 @@ class Surf {
     DeviceImage d_gray_, d_now_, d_surf_, d_q_, d_mean_, d_sd_, d_picture_;
 };
 
+// the pictures of a MeanFlow::push, each optional: mean and stddev (major, minor) 32FC2, steady 16UC1, mask 8UC1, picture 8UC3
+struct MeanFlowPictures { Mat* mean = nullptr; Mat* steady = nullptr; Mat* stddev = nullptr; Mat* mask = nullptr; Mat* picture = nullptr; };
+
+// Mean current on the device (rcflow_meanflow_*): per pixel the exact mean of the last `window` flow samples, the steadiness
+// |sum of vectors| / sum of magnitudes in per mille, the major and minor standard deviation, and the mask of the pixels that are
+// steady, fast enough and run along a direction, or against the picture's own mean vector.  Host flow fields (32FC2) of the
+// pipeline's size in; the pictures and a record per cell of a grid out.
+class MeanFlow {
+  public:
+    using Pictures = MeanFlowPictures;
+
+    MeanFlow(Pipeline& pipe, const rc_meanflow_params& prm) : pipe_(pipe), cells_(prm.grid_x * prm.grid_y) {
+        check(rcflow_meanflow_open(pipe.context(), 0, pipe.width(), pipe.height(), &prm));
+    }
+    ~MeanFlow() { (void)rcflow_meanflow_close(pipe_.context(), 0); }
+    MeanFlow(const MeanFlow&) = delete;
+    MeanFlow& operator=(const MeanFlow&) = delete;
+
+    // flow: 32FC2 of the pipeline's size.  The records, the sums and the summary stay on the session after every push, for read(),
+    // cells() and sums().
+    void push(const Mat& flow, const Pictures& out = Pictures()) {
+        const int w = pipe_.width(), h = pipe_.height();
+        if (!is_image(flow, w, h, 2, 4)) throw Error(RC_EINVAL, "MeanFlow::push: the field must be 32FC2 of the pipeline's size");
+        if ((out.mean && !is_image(*out.mean, w, h, 2, 4)) || (out.stddev && !is_image(*out.stddev, w, h, 2, 4)) ||
+            (out.steady && !is_image(*out.steady, w, h, 1, 2)) || (out.mask && !is_image(*out.mask, w, h, 1, 1)) ||
+            (out.picture && !is_image(*out.picture, w, h, 3, 1)))
+            throw Error(RC_EINVAL, "MeanFlow::push: mean and std 32FC2, steady 16UC1, mask 8UC1, picture 8UC3, each of the pipeline's size");
+        staged(pipe_.context(), {{d_flow_, &flow}}, [&] {
+            return rcflow_meanflow_push_dev(pipe_.context(), 0, d_flow_.ptr<const float>(), d_flow_.pitch(), d_mean_.ptr<float>(out.mean), d_mean_.pitch(),
+                                            d_steady_.ptr<uint16_t>(out.steady), d_steady_.pitch(), d_std_.ptr<float>(out.stddev), d_std_.pitch(),
+                                            d_mask_.ptr<uint8_t>(out.mask), d_mask_.pitch(), d_picture_.ptr<uint8_t>(out.picture), d_picture_.pitch(),
+                                            nullptr, nullptr, nullptr);
+        }, {{d_mean_, out.mean}, {d_steady_, out.steady}, {d_std_, out.stddev}, {d_mask_, out.mask}, {d_picture_, out.picture}});
+    }
+    // each waits for the pipeline's stream: of the last push (include/rcflow.h).  The summary: filled pixels, mask pixels, pixels
+    // whose newest sample was bad, Gx, Gy, the sum of Sm, samples held, pushes
+    std::vector<long long> read() {
+        std::vector<long long> s(8);
+        check(rcflow_meanflow_read(pipe_.context(), 0, nullptr, nullptr, s.data()));
+        return s;
+    }
+    std::vector<rc_meanflow_cell> cells() {
+        std::vector<rc_meanflow_cell> r((size_t)cells_);
+        check(rcflow_meanflow_read(pipe_.context(), 0, r.data(), nullptr, nullptr));
+        return r;
+    }
+    std::vector<long long> sums() {
+        std::vector<long long> s((size_t)cells_ * RC_MEANFLOW_SUMS);
+        check(rcflow_meanflow_read(pipe_.context(), 0, nullptr, s.data(), nullptr));
+        return s;
+    }
+    void set(int steady_min, double speed_min, double min_cos2, double dir_x, double dir_y, int min_fill) {
+        check(rcflow_meanflow_set(pipe_.context(), 0, steady_min, speed_min, min_cos2, dir_x, dir_y, min_fill));
+    }
+    rc_meanflow_info info() { rc_meanflow_info i; check(rcflow_meanflow_info(pipe_.context(), 0, &i)); return i; }
+    void reset() { check(rcflow_meanflow_reset(pipe_.context(), 0)); }
+
+  private:
+    Pipeline& pipe_;
+    int cells_ = 0;
+    DeviceImage d_flow_, d_mean_, d_steady_, d_std_, d_mask_, d_picture_;
+};
+
 }  // namespace rc

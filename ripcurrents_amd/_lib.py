@@ -74,6 +74,9 @@ RC_SHORE_MAX_PIXELS, RC_SHORE_MAX_STATE_BYTES, RC_SHORE_HIST, RC_SHORE_LAUNCHES 
 RC_SURF_NOBAND, RC_SURF_NOREF, RC_SURF_CHANNEL, RC_SURF_IN_CHANNEL = 1, 2, 4, 8
 RC_SURF_MAX_LINES, RC_SURF_MIN_SAMPLES, RC_SURF_MAX_SAMPLES, RC_SURF_MAX_TOTAL, RC_SURF_MAX_WINDOW, RC_SURF_MAX_SPAN = 1024, 8, 1024, 262144, 4096, 32
 RC_SURF_MAX_CHANNELS, RC_SURF_MAX_SHARE, RC_SURF_MAX_PIXELS, RC_SURF_MAX_STATE_BYTES, RC_SURF_LAUNCHES = 32, 1000000, 1 << 25, 4 << 30, 3
+# rcflow_meanflow_*: the direction flags, the record's flag, the bounds, the words of a cell's sums, the launches of a push
+RC_MEANFLOW_DIR_FIXED, RC_MEANFLOW_DIR_OPPOSED, RC_MEANFLOW_EMPTY = 1, 2, 1
+RC_MEANFLOW_MAX_WINDOW, RC_MEANFLOW_SUMS, RC_MEANFLOW_MAX_STATE_BYTES, RC_MEANFLOW_LAUNCHES = 4096, 8, 4 << 30, 2
 
 ERRORS = {-1: "RC_EINVAL", -2: "RC_ENOMEM", -3: "RC_EHIP", -4: "RC_ENODEV", -5: "RC_ESIZE",
           -6: "RC_ESTATE", -7: "RC_ECOMM"}
@@ -304,6 +307,24 @@ class SurfChannel(C.Structure):
     """rc_surf_channel (include/rcflow.h), 32 bytes; numpy: api.SURF_CHANNEL_DTYPE."""
     _fields_ = [("first", C.c_int), ("count", C.c_int), ("centre", C.c_int), ("share", C.c_int), ("cx", C.c_int), ("cy", C.c_int),
                 ("width_m", C.c_float), ("pad", C.c_int)]
+
+
+class MeanflowParams(C.Structure):
+    """rc_meanflow_params (include/rcflow.h), 56 bytes."""
+    _fields_ = [("window", C.c_int), ("grid_x", C.c_int), ("grid_y", C.c_int), ("min_fill", C.c_int), ("steady_min", C.c_int), ("flags", C.c_int),
+                ("speed_min", C.c_double), ("min_cos2", C.c_double), ("dir_x", C.c_double), ("dir_y", C.c_double)]
+
+
+class MeanflowCell(C.Structure):
+    """rc_meanflow_cell (include/rcflow.h), 32 bytes; numpy: api.MEANFLOW_CELL_DTYPE."""
+    _fields_ = [("flags", C.c_int), ("filled", C.c_int), ("mask", C.c_int), ("bad", C.c_int), ("mean_x", C.c_float), ("mean_y", C.c_float),
+                ("steadiness", C.c_float), ("pad", C.c_int)]
+
+
+class MeanflowInfo(C.Structure):
+    """rc_meanflow_info (include/rcflow.h)."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", MeanflowParams), ("launches_per_push", C.c_int), ("held", C.c_int),
+                ("pushes", C.c_longlong), ("device_bytes", C.c_size_t)]
 
 
 class SurfInfo(C.Structure):
@@ -538,6 +559,13 @@ SIGNATURES = {
     "rcflow_surf_reset": [_vp, _i],
     "rcflow_surf_close": [_vp, _i],
     "rcflow_surf_info": [_vp, _i, C.POINTER(SurfInfo)],
+    "rcflow_meanflow_open": [_vp, _i, _i, _i, C.POINTER(MeanflowParams)],
+    "rcflow_meanflow_push_dev": [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp],
+    "rcflow_meanflow_read": [_vp, _i, _vp, _vp, C.POINTER(C.c_longlong)],
+    "rcflow_meanflow_set": [_vp, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _i],
+    "rcflow_meanflow_reset": [_vp, _i],
+    "rcflow_meanflow_close": [_vp, _i],
+    "rcflow_meanflow_info": [_vp, _i, C.POINTER(MeanflowInfo)],
     "rcflow_comm_unique_id": [_vp],
     "rcflow_comm_init": [_vp, _vp, _i, _i],
     "rcflow_comm_destroy": [_vp],

@@ -42,9 +42,10 @@ from ._lib import RC_TRANSECTS_FLOW, RC_TRANSECTS_GRAY, RC_TRANSECTS_SUMS, Trans
 from ._lib import RC_KINEMATICS_MAX_RADIUS, RC_KINEMATICS_RELATIVE, RC_KINEMATICS_SUMS, KinematicsInfo, KinematicsParams
 from ._lib import RC_SHORE_HIST, SHORE_SOURCES, ShorelineInfo, ShorelineParams
 from ._lib import RC_SURF_MAX_CHANNELS, SurfInfo, SurfParams
+from ._lib import RC_MEANFLOW_DIR_FIXED, RC_MEANFLOW_DIR_OPPOSED, RC_MEANFLOW_SUMS, MeanflowInfo, MeanflowParams
 
 __all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState", "Waves", "Piv", "Transects", "Kinematics",
-           "Shoreline", "Surf"]
+           "Shoreline", "Surf", "MeanFlow"]
 
 
 # rc_draw_prim as a numpy record (32 bytes): what Context.draw takes and Context.tracers_prims returns
@@ -117,6 +118,11 @@ MOTION_CELL_DTYPE = np.dtype([("angle", "<f8"), ("S", "<i8"), ("W", "<i8"), ("ts
 # the name tables of _lib read the other way: the C ABI's number -> the name this layer takes and returns
 FIT_MODEL_NAMES = {v: k for k, v in FIT_MODELS.items()}
 FTLE_DIRECTION_NAMES = {v: k for k, v in FTLE_DIRECTIONS.items()}
+# the eight words of a mean-flow summary and of a cell's sums, in order; rc_meanflow_cell (32 bytes) as a numpy record
+MEANFLOW_SUMMARY = ("filled", "mask", "bad", "gx", "gy", "sum_m", "held", "pushes")
+MEANFLOW_SUMS = ("filled", "n", "su", "sv", "sm", "mask", "bad", "zero")
+MEANFLOW_CELL_DTYPE = np.dtype([("flags", "<i4"), ("filled", "<i4"), ("mask", "<i4"), ("bad", "<i4"), ("mean_x", "<f4"), ("mean_y", "<f4"),
+                                ("steadiness", "<f4"), ("pad", "<i4")])
 RIPMAP_SOURCE_NAMES = {v: k for k, v in RIPMAP_SOURCES.items()}
 TRACERS_MOVER_NAMES = {v: k for k, v in TRACERS_MOVERS.items()}
 SHORE_SOURCE_NAMES = {v: k for k, v in SHORE_SOURCES.items()}
@@ -1998,6 +2004,67 @@ class Context:
     def surf_close(self, stream=0):
         self._lifecycle("surf", "close", stream)
 
+    # ------------------------------------------------------------------ mean flow
+    def meanflow_open(self, w, h, window=300, grid_x=30, grid_y=30, min_fill=None, steady_min=600, opposed=False, speed_min=0.5, min_cos2=0.5,
+                      dir_x=0.0, dir_y=-1.0, stream=0):
+        """Opens the slot's mean current on w x h flow fields (include/rcflow.h, "mean flow"): per pixel the exact mean of the last
+        `window` samples in 1/64 pixel, the steadiness |sum of vectors| / sum of magnitudes in per mille, the major and minor
+        standard deviation, and a mask of the pixels with at least min_fill (default: window) valid samples that are steady
+        (steady_min per mille), at least speed_min pixels per field fast and within min_cos2 of the direction (dir_x, dir_y), or
+        with opposed=True of the direction against the picture's own summed mean vector.  The state takes 4 * window + 38 bytes
+        per pixel of device memory."""
+        p = MeanflowParams(window=int(window), grid_x=int(grid_x), grid_y=int(grid_y), min_fill=int(window if min_fill is None else min_fill),
+                           steady_min=int(steady_min), flags=RC_MEANFLOW_DIR_OPPOSED if opposed else RC_MEANFLOW_DIR_FIXED,
+                           speed_min=float(speed_min), min_cos2=float(min_cos2), dir_x=float(dir_x), dir_y=float(dir_y))
+        self._bind(stream)          # the state is zeroed on the slot's stream: the one the pushes will run on
+        check(self._lib.rcflow_meanflow_open(self._h, stream, int(w), int(h), C.byref(p)))
+
+    def meanflow_info(self, stream=0):
+        """dict(w, h, the parameters, opposed, launches_per_push, held, pushes, device_bytes); never blocks."""
+        i = self._info("meanflow", MeanflowInfo(), stream)
+        d = _record(i, skip=("flags", "pad"))
+        d["opposed"] = i.prm.flags == RC_MEANFLOW_DIR_OPPOSED
+        return d
+
+    def meanflow_push(self, flow=None, mean=None, steady=None, std=None, mask=None, picture=None, cells=None, sums=None, summary=None, stream=0):
+        """One flow field (HxWx2 float32 device tensor, dense pixels, rows may be padded; None: the field push_frame_host /
+        frame_loop_step left on the slot); nothing is synchronised.  Outputs are preallocated device tensors, each optional: mean
+        HxWx2 float32 (the field every flow consumer takes), steady HxW int16 (per mille), std HxWx2 float32 (major, minor), mask
+        HxW uint8 (255 in a steady jet: what regions_push takes), picture HxWx3 uint8 (the steadiness in JET colours), cells
+        GYxGXx32 uint8 (rc_meanflow_cell records; view the host copy as MEANFLOW_CELL_DTYPE), sums GYxGXx8 int64 (MEANFLOW_SUMS),
+        summary 8 int64 (MEANFLOW_SUMMARY).  Records, sums and summary also stay on the slot for meanflow_read."""
+        i = self._info("meanflow", MeanflowInfo(), stream)
+        h, w, nc = i.h, i.w, i.prm.grid_x * i.prm.grid_y
+        fp, fstep = self._in_image(flow, torch.float32, "flow", (h, w, 2), optional=True)
+        images = (self._out_image(mean, torch.float32, "mean", (h, w, 2)) + self._out_image(steady, torch.int16, "steady", (h, w)) +
+                  self._out_image(std, torch.float32, "std", (h, w, 2)) + self._out_image(mask, torch.uint8, "mask", (h, w)) +
+                  self._out_image(picture, torch.uint8, "picture", (h, w, 3)))
+        cp = self._out_array(cells, torch.uint8, "cells", nc * 32)
+        sp = self._out_array(sums, torch.int64, "sums", nc * RC_MEANFLOW_SUMS)
+        up = self._out_array(summary, torch.int64, "summary", 8)
+        self._bind(stream)
+        check(self._lib.rcflow_meanflow_push_dev(self._h, stream, fp, fstep, *images, cp, sp, up))
+
+    def meanflow_read(self, stream=0):
+        """Waits for the slot's stream -> (cells GYxGX MEANFLOW_CELL_DTYPE, sums GYxGXx8 int64, dict of the summary by
+        MEANFLOW_SUMMARY names) of the last push; zeros before the first."""
+        info = self.meanflow_info(stream)
+        gx, gy = info["grid_x"], info["grid_y"]
+        cells, sums = np.zeros((gy, gx), MEANFLOW_CELL_DTYPE), np.zeros((gy, gx, RC_MEANFLOW_SUMS), np.int64)
+        out = self._summary(self._lib.rcflow_meanflow_read, stream, MEANFLOW_SUMMARY, cells.ctypes.data, sums.ctypes.data)
+        return cells, sums, out
+
+    def meanflow_set(self, steady_min, speed_min, min_cos2, dir_x, dir_y, min_fill, stream=0):
+        """steady_min, speed_min, min_cos2, dir_x, dir_y and min_fill from the next push on."""
+        check(self._lib.rcflow_meanflow_set(self._h, stream, int(steady_min), float(speed_min), float(min_cos2), float(dir_x), float(dir_y),
+                                            int(min_fill)))
+
+    def meanflow_reset(self, stream=0):
+        self._lifecycle("meanflow", "reset", stream)
+
+    def meanflow_close(self, stream=0):
+        self._lifecycle("meanflow", "close", stream)
+
     # ------------------------------------------------------------------ rip regions
     def regions_open(self, w, h, connectivity=8, min_area=1, max_regions=1024, stream=0):
         """Opens the slot's region labelling for w x h masks: connected components (4 or 8 neighbours) numbered in raster
@@ -2362,6 +2429,18 @@ class Surf(_Product):
 
     def set(self, bright, delta, q_min, ratio, min_load, vis_permille):
         self.ctx.surf_set(bright, delta, q_min, ratio, min_load, vis_permille, self.stream)
+
+
+class MeanFlow(_Product):
+    """The mean current of one slot as an object: Context.meanflow_* with the context and the slot bound.  Opens on construction
+    (the parameters of Context.meanflow_open as keywords), closes on close() or at the end of a with block."""
+    product = "meanflow"
+
+    def push(self, flow=None, **outputs):
+        self.ctx.meanflow_push(flow, stream=self.stream, **outputs)
+
+    def set(self, steady_min, speed_min, min_cos2, dir_x, dir_y, min_fill):
+        self.ctx.meanflow_set(steady_min, speed_min, min_cos2, dir_x, dir_y, min_fill, self.stream)
 
 
 def kinematics_taps(radius, sigma):

@@ -341,6 +341,23 @@ struct RcSurf {
     RcZeroFence zf;
 };
 
+// Mean current of one stream slot (meanflow_kernels.hip).  Everything is allocated by rcflow_meanflow_open and released by
+// rcflow_meanflow_close / rcflow_destroy.
+struct RcMeanflow {
+    bool open = false;
+    int w = 0, h = 0;
+    rc_meanflow_params prm{};       // steady_min, speed_min, min_cos2, dir_x, dir_y and min_fill: as rcflow_meanflow_set left them
+    int P = 0;                      // row pitch of the state planes in pixels (w rounded up to 4)
+    long long pushes = 0;           // since open / reset; the next sample goes to ring slot pushes mod window
+    RcBuf ring;                     // [window][h][P] uint32: u | v << 16 in 1/64 pixel, 0x8000 for a bad sample; not read before it has wrapped
+    RcBuf sums;                     // Suu | Svv | Suv [h][P] int64 | Su | Sv [h][P] int32 | Sm [h][P] uint32 | n [h][P] uint16
+    RcBuf acc;                      // [cells][RC_MEANFLOW_SUMS] int64 the launches add into, zero between pushes
+    RcBuf out;                      // the last push: summary 8 int64 | sums [cells][RC_MEANFLOW_SUMS] int64 | records [cells]
+    RcBuf ctl;                      // MfCtl: the tickets and G
+    RcBuf jet;                      // COLORMAP_JET, 768 bytes
+    RcZeroFence zf;
+};
+
 // warp_kernels.hip: one launch of the affine / perspective warp
 struct RcWarpArgs {
     const uint8_t* src; size_t step;
@@ -425,6 +442,7 @@ struct RcSlot {
     RcKinematics kn;
     RcShoreline sh;
     RcSurf sf;
+    RcMeanflow mf;
     RcPhaseCorr pc;
 };
 
@@ -487,7 +505,8 @@ struct rc_ctx {
 // no state from push to push: an operation on the field as the shear-rate colouring among the post-ops (flow_postop) is, so they
 // are booked with those, under "farneback".  The shoreline works on pictures, not on flow: the time-exposure MEAN, the plan view's
 // picture or a frame, as the time-exposure images and the wave spectra do, and is booked with them, under "overlay".  The surf zone
-// is the time exposure's fourth picture and what is read off it, and is booked there too.
+// is the time exposure's fourth picture and what is read off it, and is booked there too.  The mean current keeps a window over
+// the flow field and decides from its mean, as the opposing-flow map does, and is booked where that is, under "farneback".
 #define RC_BUCKET_TABLE(X) \
     X(RC_B_FARNEBACK, "farneback") X(RC_B_POLAR, "polar") X(RC_B_THRESHOLD, "threshold") X(RC_B_OVERLAY, "overlay") \
     X(RC_B_EROSION, "erosion") X(RC_B_CODEC, "codec") X(RC_B_STREAM, "stream")
@@ -530,7 +549,8 @@ struct rc_ctx {
     X(RC_K_TRANSECTS, "transects", RC_B_STREAM) /* @0 sampling, rings and accumulators, @1 velocity, transport, jets, records and summary, @2 time stack and Hovmoeller picture */ \
     X(RC_K_KINEMATICS, "kinematics", RC_B_FARNEBACK) /* @0 smoothing, derivatives, invariants, first sums and the threshold, @1 cores, mask, picture, records and summary */ \
     X(RC_K_SHORELINE, "shoreline", RC_B_OVERLAY) /* @0 indicator, box, plane, histogram and Otsu, @1 lines, @2 outliers, ring, window and records, @3 mask, plane and histogram out, @4 primitives */ \
-    X(RC_K_SURF, "surf", RC_B_OVERLAY) /* @0 ring, sums, flags, pictures and counts, @1 lines, @2 reference, channels, records and summary, @3 primitives */
+    X(RC_K_SURF, "surf", RC_B_OVERLAY) /* @0 ring, sums, flags, pictures and counts, @1 lines, @2 reference, channels, records and summary, @3 primitives */ \
+    X(RC_K_MEANFLOW, "meanflow", RC_B_FARNEBACK) /* @0 ring, sums, mean, steadiness, spread, picture, cell sums and G, @1 mask, records and summary */
 #define RC_ROW_ID(id, ...) id,
 enum { RC_BUCKET_TABLE(RC_ROW_ID) RC_B_BUCKETS };
 enum { RC_KIND_TABLE(RC_ROW_ID) RC_K_KINDS };
@@ -618,7 +638,7 @@ struct RcProfScope {
     } while (0)
 
 // ---------------------------------------------------------------------------- per-slot products
-// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView, RcWaves, RcPiv, RcTransects, RcKinematics, RcShoreline and RcSurf share one lifecycle.  A product supplies
+// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView, RcWaves, RcPiv, RcTransects, RcKinematics, RcShoreline, RcSurf and RcMeanflow share one lifecycle.  A product supplies
 //   void rc_state_free(T&)             frees every buffer and the fence; the state is T() again
 //   int rc_state_zero(RcSlot&, T&)     rc_fence_zero of what open / reset clear, and the counters
 // and open / reset / close are written once, here.
@@ -637,6 +657,7 @@ void rc_state_free(RcTransects& v);
 void rc_state_free(RcKinematics& k);
 void rc_state_free(RcShoreline& v);
 void rc_state_free(RcSurf& v);
+void rc_state_free(RcMeanflow& v);
 int rc_state_zero(RcSlot& s, RcTimex& t);
 int rc_state_zero(RcSlot& s, RcFrameStab& f);
 int rc_state_zero(RcSlot& s, RcRipMap& m);
@@ -652,6 +673,7 @@ int rc_state_zero(RcSlot& s, RcTransects& v);
 int rc_state_zero(RcSlot& s, RcKinematics& k);
 int rc_state_zero(RcSlot& s, RcShoreline& v);
 int rc_state_zero(RcSlot& s, RcSurf& v);
+int rc_state_zero(RcSlot& s, RcMeanflow& v);
 
 // The tail of every open.  The caller has validated, selected the device and built `fresh` (rc: what its allocations
 // returned).  The state that is open is touched only once nothing can be refused any more: a refused open leaves it as it
