@@ -2226,6 +2226,137 @@ int rcflow_meanflow_close(rc_ctx* ctx, int stream);
 /* never blocks; RC_ESTATE when nothing is open, RC_EINVAL without a buffer */
 int rcflow_meanflow_info(rc_ctx* ctx, int stream, rc_meanflow_info* info);
 
+/* ------------------------------------------------------------------ flow check: residual, texture, round trip, valid mask
+ * Which vectors of a dense flow field mean anything.  Farneback answers at every pixel: on sky, dry sand, glare and textureless
+ * water there is nothing to match, along a straight crest only the normal component is defined, and where foam moves several
+ * pixels a frame the match is lost.  Sparse PyrLK returns status and err; this is the dense counterpart.  One launch per push looks
+ * at both grey frames and the field (a second, of one workgroup, closes the records) and gives per pixel a set of flags, the mask of the VALID pixels (what
+ * rcflow_regions_push_dev takes) and the field with the rejected vectors replaced by NaN or zero: every consumer of a field (the
+ * opposing-flow map, the mean flow, the kinematics, the transects) leaves a sample that is not finite out and counts it, so the
+ * checked field goes into them as it is.  The reference has no such product.  tests/_flowcheck_ref.py states the following in numpy
+ * and the kernel equals it bit for bit on every output of every push.  Every decision is integer and exact; the few float outputs
+ * are computed in double, each operation rounded on its own; no atan2 and no float bilinear weight anywhere.
+ *
+ *  Inputs of a push.  d_next 8UC1, w x h.  d_prev 8UC1, or NULL: the frame the slot holds, which is the d_next of the push before
+ *  (every push ends in a device-to-device copy of d_next on the slot's stream, behind the launch).  d_flow_xy 32FC2 from prev to
+ *  next with next(x + u) ~ prev(x) (Farneback's convention; pointer and step multiples of 8); NULL is the field the slot's frame
+ *  loop left resident (rcflow_stream_flow_ptr), with the rules of rcflow_meanflow_push_dev.  d_back_xy 32FC2 from next to prev, or
+ *  NULL: no round-trip test.  The two-image entry point with the frames swapped gives the backward field.
+ *  With d_prev NULL and no frame held, the FIRST push since rcflow_flowcheck_open is the copy alone (as the first push of
+ *  rcflow_piv_push_dev): no launch, no output written, RC_OK; it counts in `pushes` and not in `computing pushes`.  After
+ *  rcflow_flowcheck_reset, which forgets the held frame but not the counts, such a push is RC_ESTATE.
+ *  Sample (the mean flow's rule).  A pixel is BAD when a component of u is not finite or fabsf(component) >= 500.0f; otherwise
+ *  q = (int)rintf(component * 64.0f) per component: 1/64 pixel, |q| <= 32000.
+ *  Target.  X = 64 x + qx, Y = 64 y + qy.  The pixel is OUT when X < 0, Y < 0, X > 64 (w - 1) or Y > 64 (h - 1).  Otherwise
+ *  x0 = X >> 6, fx = X & 63, x1 = min(x0 + 1, w - 1), likewise y, and Wn = (64-fx)(64-fy) next[y0,x0] + fx (64-fy) next[y0,x1] +
+ *  (64-fx) fy next[y1,x0] + fx fy next[y1,x1], an integer not above 255 * 4096.  A pixel is OK when it is neither BAD nor OUT; then
+ *  res = |Wn - 4096 prev[y,x]| and res0 = 4096 |next[y,x] - prev[y,x]|.
+ *  Window.  The (2 r + 1)^2 box, r = radius, clipped to the picture: N its pixels inside the picture, Nr those of them that are
+ *  OK; R, R0 the sums of res, res0 over the OK ones, each with its own flow (both stay below 2^31); gx = prev[y, min(x+1,w-1)] -
+ *  prev[y, max(x-1,0)] and gy likewise (central differences, replicated border); a, c, b the sums of gx^2, gy^2, gx gy over the N
+ *  pixels, in int32.
+ *  Tests.  rc_flowcheck_params::tests says which of FLAT, RESID, NOGAIN, FB and FAST run; one that is off sets no bit.  BAD and OUT
+ *  always run.  A BAD pixel has bit BAD only; an OUT pixel has OUT and whatever FLAT and FAST give.
+ *   FLAT    t = tex_min N; the pixel passes iff a + c >= 2 t and (a - t)(c - t) >= b b in int64: the smaller eigenvalue of the mean
+ *           structure tensor is at least tex_min, without a square root.
+ *   RESID   (OK pixels) res_q = floor(res_max * 4096) taken on the host; set iff R > res_q Nr in int64.
+ *   NOGAIN  (OK pixels with q != (0, 0), gain_pm > 0) set iff 1000 R > gain_pm R0: the flow must explain the change between the
+ *           frames better than no motion does.
+ *   FB      (OK pixels, d_back_xy given) the back field's samples follow the sample rule.  If any of the four back samples at
+ *           (x0,y0), (x1,y0), (x0,y1), (x1,y1) is BAD the bit is set.  Otherwise bx = the sum of the same four integer weights
+ *           times qbx, in int32, bxr = floor((bx + 2048) / 4096), and by, byr likewise; ex = qx + bxr, ey = qy + byr; e2 = ex^2 +
+ *           ey^2, m2 = qx^2 + qy^2 + bxr^2 + byr^2; set iff 1024 e2 > fb_rel_q m2 + fb_abs_q, with fb_rel_q = rint(fb_rel * 1024)
+ *           and fb_abs_q = floor(fb_abs * fb_abs * 4194304.0) taken on the host.  fb_rel = 0.01 and fb_abs^2 = 0.5 (fb_abs =
+ *           0.70710678) are the usual pair.
+ *   FAST    smax_q = floor(speed_max * 64); set iff qx^2 + qy^2 > smax_q^2.
+ *  A pixel is VALID iff its flags are 0.
+ *  Outputs, each may be NULL.  d_flags 8UC1.  d_mask 8UC1, 255 / 0.  d_checked 32FC2: the input's bits where the pixel is VALID,
+ *  else both components 0x7fc00000 (RC_FLOWCHECK_FILL_NAN) or 0.0f (RC_FLOWCHECK_FILL_ZERO).  d_resid 32FC2: ((float)((double)R /
+ *  (4096.0 * (double)Nr)), the same from R0), zeros where the pixel is not OK.  d_texture 32FC1, every pixel: with A, B, C the
+ *  doubles of a, b, c: l = ((A + C) - sqrt((A - C)(A - C) + 4.0 (B B))) * 0.5, clamped below at 0, and (float)(l / (double)N).
+ *  d_picture 8UC3: (g, g, g) with g = prev[y,x] where VALID, else the colour of the lowest set bit, in B, G, R: BAD (255, 0, 255),
+ *  OUT (128, 128, 128), FLAT (255, 0, 0), RESID (0, 0, 255), NOGAIN (0, 165, 255), FB (0, 255, 255), FAST (0, 255, 0).
+ *  Cells are the opposing-flow map's grid.  RC_FLOWCHECK_SUMS = 10 int64 per cell: the pixels that are VALID | that have BAD | OUT |
+ *  FLAT | RESID | NOGAIN | FB | FAST | the sum of qx over the VALID | of qy.  Records, rc_flowcheck_cell, closed by a second, small launch
+ *  ("flowcheck@1"): valid_pm = valid * 1000 / pixels; mean_x = (float)(((double)(sum of qx) / 64.0) / (double)valid),
+ *  mean_y likewise; both 0 and RC_FLOWCHECK_NONE_VALID set with none valid.  Summary, 10 int64: the eight counts over the picture
+ *  | computing pushes | pushes, both since open. */
+#define RC_FLOWCHECK_BAD 1               /* the flags of a pixel */
+#define RC_FLOWCHECK_OUT 2
+#define RC_FLOWCHECK_FLAT 4
+#define RC_FLOWCHECK_RESID 8
+#define RC_FLOWCHECK_NOGAIN 16
+#define RC_FLOWCHECK_FB 32
+#define RC_FLOWCHECK_FAST 64
+#define RC_FLOWCHECK_TESTS 124           /* what rc_flowcheck_params::tests may hold */
+#define RC_FLOWCHECK_FILL_NAN 1          /* rc_flowcheck_params::flags: exactly one of the two */
+#define RC_FLOWCHECK_FILL_ZERO 2
+#define RC_FLOWCHECK_NONE_VALID 1        /* rc_flowcheck_cell::flags */
+#define RC_FLOWCHECK_MAX_RADIUS 7
+#define RC_FLOWCHECK_SUMS 10
+#define RC_FLOWCHECK_SUMMARY 10
+#define RC_FLOWCHECK_LAUNCHES 2          /* of a computing push */
+typedef struct rc_flowcheck_params {
+    int radius;             /* r: 0..RC_FLOWCHECK_MAX_RADIUS */
+    int grid_x, grid_y;     /* cells, as rcflow_ripmap_open */
+    int tests;              /* a subset of RC_FLOWCHECK_TESTS */
+    int flags;              /* RC_FLOWCHECK_FILL_NAN or RC_FLOWCHECK_FILL_ZERO */
+    int tex_min;            /* 0..65025: the least smaller eigenvalue of the mean structure tensor, grey levels squared */
+    int gain_pm;            /* 0..1000 per mille; 0: NOGAIN sets nothing */
+    int pad;
+    double res_max;         /* grey levels, 0..255: the largest window-mean residual */
+    double fb_rel;          /* 0..1 */
+    double fb_abs;          /* pixels, 0..500 */
+    double speed_max;       /* pixels per frame, 0..1000 */
+} rc_flowcheck_params;      /* 64 bytes */
+typedef struct rc_flowcheck_cell {
+    int flags;              /* RC_FLOWCHECK_NONE_VALID */
+    int pixels;
+    int valid;
+    int valid_pm;           /* valid * 1000 / pixels */
+    float mean_x, mean_y;   /* of the VALID pixels, pixels per frame */
+    int pad[2];
+} rc_flowcheck_cell;        /* 32 bytes */
+typedef struct rc_flowcheck_info {
+    int w, h;
+    rc_flowcheck_params prm;           /* as rcflow_flowcheck_set left them */
+    int launches_per_push;             /* RC_FLOWCHECK_LAUNCHES */
+    int held;                          /* 1 while a frame is held */
+    long long pushes, computing;       /* since open */
+    size_t device_bytes;
+} rc_flowcheck_info;
+/* Allocates everything the slot will ever need.  Re-opening replaces the state; a refused open leaves the open state as it was.
+ * RC_EINVAL without parameters, for a value outside the ranges above (or not finite), an unknown bit in tests, flags that are not
+ * exactly one of the two fills, a grid that does not fit; RC_ESIZE beyond the context's max_w x max_h. */
+int rcflow_flowcheck_open(rc_ctx* ctx, int stream, int w, int h, const rc_flowcheck_params* prm);
+/* One pair of frames and its field.  Images: d_next, d_prev, d_flags, d_mask 8UC1; d_flow_xy, d_back_xy, d_checked, d_resid 32FC2
+ * (pointer and step multiples of 8); d_texture 32FC1 (multiples of 4); d_picture 8UC3; d_cells cells x rc_flowcheck_cell (4-byte
+ * aligned), d_sums cells x RC_FLOWCHECK_SUMS int64 and d_summary RC_FLOWCHECK_SUMMARY int64 (8-byte aligned).  What a push gives
+ * does not depend on which outputs it asked for.  No host synchronisation, no device-to-host copy.  An output whose byte range
+ * overlaps an input's or another output's is RC_EINVAL: d_checked over the field too, because a workgroup reads its neighbours'
+ * vectors.  Row padding is never written.  Every refusal is decided before anything is queued and leaves the state as it was;
+ * RC_ESTATE before rcflow_flowcheck_open, with d_prev NULL while no frame is held (but see the first push, above), and with
+ * d_flow_xy NULL while no field is resident (RC_ESIZE when the resident field has another size).  RC_EHIP (the runtime refused a
+ * launch) is no refusal: the state is undefined until rcflow_flowcheck_reset. */
+int rcflow_flowcheck_push_dev(rc_ctx* ctx, int stream, const uint8_t* d_next, size_t next_step, const uint8_t* d_prev, size_t prev_step,
+                              const float* d_flow_xy, size_t flow_step, const float* d_back_xy, size_t back_step, uint8_t* d_flags,
+                              size_t flags_step, uint8_t* d_mask, size_t mask_step, float* d_checked, size_t checked_step, float* d_resid,
+                              size_t resid_step, float* d_texture, size_t texture_step, uint8_t* d_picture, size_t picture_step,
+                              rc_flowcheck_cell* d_cells, long long* d_sums, long long* d_summary);
+/* Blocks until the slot's stream has finished; for hosts and tests.  Each may be NULL: the records, the cell sums and the summary
+ * of the last computing push (host memory), zeros before the first; the summary's last two words are the counts as they stand. */
+int rcflow_flowcheck_read(rc_ctx* ctx, int stream, rc_flowcheck_cell* cells, long long* sums, long long summary[RC_FLOWCHECK_SUMMARY]);
+/* tests, tex_min, res_max, gain_pm, fb_rel, fb_abs and speed_max from the next push on; RC_EINVAL as rcflow_flowcheck_open */
+int rcflow_flowcheck_set(rc_ctx* ctx, int stream, int tests, int tex_min, double res_max, int gain_pm, double fb_rel, double fb_abs,
+                         double speed_max);
+/* forgets the held frame and zeroes the records, the sums and the summary's counts of pixels; keeps the allocation, the
+ * parameters as rcflow_flowcheck_set left them and the push counts; asynchronous, on the slot's stream */
+int rcflow_flowcheck_reset(rc_ctx* ctx, int stream);
+/* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
+int rcflow_flowcheck_close(rc_ctx* ctx, int stream);
+/* never blocks; RC_ESTATE when nothing is open, RC_EINVAL without a buffer */
+int rcflow_flowcheck_info(rc_ctx* ctx, int stream, rc_flowcheck_info* info);
+
 /* Display path, ripcurrents.cpp:233-273 (= streamline_displacement / _total_motion / _ratio /
  * _positions, ripcurrents_module.cpp:13-60) on the slot's streamline field (rcflow_advect_field_dev):
  * which 0 = |pt|, 1 = dist, 2 = |pt| / dist; minMaxLoc + convertTo(CV_8UC1, 255/max) +
@@ -2306,7 +2437,7 @@ int rcflow_profile_read(rc_ctx* ctx, int cap, const char** names, int* launches,
 
 /* The same totals under the reference's own bucket names, in the order it prints them (ripcurrents.cpp:103-109,
  * :518-524): farneback, polar, threshold, overlay, erosion, codec, stream ("pathlines").  GPU time of the kernels
- * that do each bucket's work ("overlay" includes the time-exposure images, the 8-bit colour stages, the wave spectra, the shoreline and the surf zone, "farneback" the frame stabilisation, the opposing-flow map, the motion templates, the plan view, the ensemble PIV, the flow kinematics and the mean flow, "stream" the flow map and FTLE and the transects); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
+ * that do each bucket's work ("overlay" includes the time-exposure images, the 8-bit colour stages, the wave spectra, the shoreline and the surf zone, "farneback" the frame stabilisation, the opposing-flow map, the motion templates, the plan view, the ensemble PIV, the flow kinematics, the mean flow and the flow check, "stream" the flow map and FTLE and the transects); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
  * classification kernels, booked under "threshold"), "codec" is 0 (video decode is host I/O outside the library).
  * names / ms: RC_PROFILE_BUCKETS entries each (either may be NULL).  Returns RC_PROFILE_BUCKETS. */
 #define RC_PROFILE_BUCKETS 7

@@ -1452,4 +1452,76 @@ class MeanFlow {
     DeviceImage d_flow_, d_mean_, d_steady_, d_std_, d_mask_, d_picture_;
 };
 
+// the pictures of a FlowCheck::push, each optional: flags and mask 8UC1, checked and resid 32FC2, texture 32FC1, picture 8UC3
+struct FlowCheckPictures {
+    Mat* flags = nullptr; Mat* mask = nullptr; Mat* checked = nullptr; Mat* resid = nullptr; Mat* texture = nullptr; Mat* picture = nullptr;
+};
+
+// Flow check on the device (rcflow_flowcheck_*): which vectors of a dense field mean anything.  Host grey frames (8UC1) and flow
+// fields (32FC2) of the pipeline's size in; per pixel the flags, the mask of the valid pixels and the field with the rejected
+// vectors replaced by NaN or zero out, and a record per cell of a grid.
+class FlowCheck {
+  public:
+    using Pictures = FlowCheckPictures;
+
+    FlowCheck(Pipeline& pipe, const rc_flowcheck_params& prm) : pipe_(pipe), cells_(prm.grid_x * prm.grid_y) {
+        check(rcflow_flowcheck_open(pipe.context(), 0, pipe.width(), pipe.height(), &prm));
+    }
+    ~FlowCheck() { (void)rcflow_flowcheck_close(pipe_.context(), 0); }
+    FlowCheck(const FlowCheck&) = delete;
+    FlowCheck& operator=(const FlowCheck&) = delete;
+
+    // next: 8UC1; prev: 8UC1, or null for the frame of the push before (the first push then only stores its frame); flow: 32FC2 from
+    // prev to next; back: 32FC2 from next to prev, or null for no round-trip test.  The records, the sums and the summary stay on
+    // the session after every push, for read(), cells() and sums().  The pictures of a push that only stores its frame are left as they were.
+    void push(const Mat& next, const Mat* prev, const Mat& flow, const Mat* back = nullptr, const Pictures& asked = Pictures()) {
+        const int w = pipe_.width(), h = pipe_.height();
+        if (!is_image(next, w, h, 1, 1) || (prev && !is_image(*prev, w, h, 1, 1)))
+            throw Error(RC_EINVAL, "FlowCheck::push: the frames must be 8UC1 of the pipeline's size");
+        if (!is_image(flow, w, h, 2, 4) || (back && !is_image(*back, w, h, 2, 4)))
+            throw Error(RC_EINVAL, "FlowCheck::push: the fields must be 32FC2 of the pipeline's size");
+        if ((asked.flags && !is_image(*asked.flags, w, h, 1, 1)) || (asked.mask && !is_image(*asked.mask, w, h, 1, 1)) ||
+            (asked.checked && !is_image(*asked.checked, w, h, 2, 4)) || (asked.resid && !is_image(*asked.resid, w, h, 2, 4)) ||
+            (asked.texture && !is_image(*asked.texture, w, h, 1, 4)) || (asked.picture && !is_image(*asked.picture, w, h, 3, 1)))
+            throw Error(RC_EINVAL, "FlowCheck::push: flags and mask 8UC1, checked and resid 32FC2, texture 32FC1, picture 8UC3, each of the pipeline's size");
+        const Pictures out = prev || info().held ? asked : Pictures();        // a push that only stores its frame writes no picture
+        staged(pipe_.context(), {{d_next_, &next}, {d_prev_, prev}, {d_flow_, &flow}, {d_back_, back}}, [&] {
+            return rcflow_flowcheck_push_dev(pipe_.context(), 0, d_next_.ptr<const uint8_t>(), d_next_.pitch(), d_prev_.ptr<const uint8_t>(prev), d_prev_.pitch(),
+                                             d_flow_.ptr<const float>(), d_flow_.pitch(), d_back_.ptr<const float>(back), d_back_.pitch(),
+                                             d_flags_.ptr<uint8_t>(out.flags), d_flags_.pitch(), d_mask_.ptr<uint8_t>(out.mask), d_mask_.pitch(),
+                                             d_checked_.ptr<float>(out.checked), d_checked_.pitch(), d_resid_.ptr<float>(out.resid), d_resid_.pitch(),
+                                             d_texture_.ptr<float>(out.texture), d_texture_.pitch(), d_picture_.ptr<uint8_t>(out.picture),
+                                             d_picture_.pitch(), nullptr, nullptr, nullptr);
+        }, {{d_flags_, out.flags}, {d_mask_, out.mask}, {d_checked_, out.checked}, {d_resid_, out.resid}, {d_texture_, out.texture},
+            {d_picture_, out.picture}});
+    }
+    // each waits for the pipeline's stream: of the last computing push (include/rcflow.h).  The summary: the pixels that are VALID,
+    // that have BAD, OUT, FLAT, RESID, NOGAIN, FB, FAST, the computing pushes, the pushes
+    std::vector<long long> read() {
+        std::vector<long long> s(RC_FLOWCHECK_SUMMARY);
+        check(rcflow_flowcheck_read(pipe_.context(), 0, nullptr, nullptr, s.data()));
+        return s;
+    }
+    std::vector<rc_flowcheck_cell> cells() {
+        std::vector<rc_flowcheck_cell> r((size_t)cells_);
+        check(rcflow_flowcheck_read(pipe_.context(), 0, r.data(), nullptr, nullptr));
+        return r;
+    }
+    std::vector<long long> sums() {
+        std::vector<long long> s((size_t)cells_ * RC_FLOWCHECK_SUMS);
+        check(rcflow_flowcheck_read(pipe_.context(), 0, nullptr, s.data(), nullptr));
+        return s;
+    }
+    void set(int tests, int tex_min, double res_max, int gain_pm, double fb_rel, double fb_abs, double speed_max) {
+        check(rcflow_flowcheck_set(pipe_.context(), 0, tests, tex_min, res_max, gain_pm, fb_rel, fb_abs, speed_max));
+    }
+    rc_flowcheck_info info() { rc_flowcheck_info i; check(rcflow_flowcheck_info(pipe_.context(), 0, &i)); return i; }
+    void reset() { check(rcflow_flowcheck_reset(pipe_.context(), 0)); }
+
+  private:
+    Pipeline& pipe_;
+    int cells_ = 0;
+    DeviceImage d_next_, d_prev_, d_flow_, d_back_, d_flags_, d_mask_, d_checked_, d_resid_, d_texture_, d_picture_;
+};
+
 }  // namespace rc

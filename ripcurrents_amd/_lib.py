@@ -77,6 +77,10 @@ RC_SURF_MAX_CHANNELS, RC_SURF_MAX_SHARE, RC_SURF_MAX_PIXELS, RC_SURF_MAX_STATE_B
 # rcflow_meanflow_*: the direction flags, the record's flag, the bounds, the words of a cell's sums, the launches of a push
 RC_MEANFLOW_DIR_FIXED, RC_MEANFLOW_DIR_OPPOSED, RC_MEANFLOW_EMPTY = 1, 2, 1
 RC_MEANFLOW_MAX_WINDOW, RC_MEANFLOW_SUMS, RC_MEANFLOW_MAX_STATE_BYTES, RC_MEANFLOW_LAUNCHES = 4096, 8, 4 << 30, 2
+# rcflow_flowcheck_*: a pixel's flags, the tests that can be switched, the fills, the record's flag, the bounds, the launches of a push
+RC_FLOWCHECK_BAD, RC_FLOWCHECK_OUT, RC_FLOWCHECK_FLAT, RC_FLOWCHECK_RESID, RC_FLOWCHECK_NOGAIN, RC_FLOWCHECK_FB, RC_FLOWCHECK_FAST = 1, 2, 4, 8, 16, 32, 64
+RC_FLOWCHECK_TESTS, RC_FLOWCHECK_FILL_NAN, RC_FLOWCHECK_FILL_ZERO, RC_FLOWCHECK_NONE_VALID = 124, 1, 2, 1
+RC_FLOWCHECK_MAX_RADIUS, RC_FLOWCHECK_SUMS, RC_FLOWCHECK_SUMMARY, RC_FLOWCHECK_LAUNCHES = 7, 10, 10, 2
 
 ERRORS = {-1: "RC_EINVAL", -2: "RC_ENOMEM", -3: "RC_EHIP", -4: "RC_ENODEV", -5: "RC_ESIZE",
           -6: "RC_ESTATE", -7: "RC_ECOMM"}
@@ -327,6 +331,25 @@ class MeanflowInfo(C.Structure):
                 ("pushes", C.c_longlong), ("device_bytes", C.c_size_t)]
 
 
+class FlowcheckParams(C.Structure):
+    """rc_flowcheck_params (include/rcflow.h), 64 bytes."""
+    _fields_ = [("radius", C.c_int), ("grid_x", C.c_int), ("grid_y", C.c_int), ("tests", C.c_int), ("flags", C.c_int), ("tex_min", C.c_int),
+                ("gain_pm", C.c_int), ("pad", C.c_int), ("res_max", C.c_double), ("fb_rel", C.c_double), ("fb_abs", C.c_double),
+                ("speed_max", C.c_double)]
+
+
+class FlowcheckCell(C.Structure):
+    """rc_flowcheck_cell (include/rcflow.h), 32 bytes; numpy: api.FLOWCHECK_CELL_DTYPE."""
+    _fields_ = [("flags", C.c_int), ("pixels", C.c_int), ("valid", C.c_int), ("valid_pm", C.c_int), ("mean_x", C.c_float), ("mean_y", C.c_float),
+                ("pad", C.c_int * 2)]
+
+
+class FlowcheckInfo(C.Structure):
+    """rc_flowcheck_info (include/rcflow.h)."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", FlowcheckParams), ("launches_per_push", C.c_int), ("held", C.c_int),
+                ("pushes", C.c_longlong), ("computing", C.c_longlong), ("device_bytes", C.c_size_t)]
+
+
 class SurfInfo(C.Structure):
     """rc_surf_info (include/rcflow.h)."""
     _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", SurfParams), ("lines", C.c_int), ("samples", C.c_int),
@@ -566,6 +589,13 @@ SIGNATURES = {
     "rcflow_meanflow_reset": [_vp, _i],
     "rcflow_meanflow_close": [_vp, _i],
     "rcflow_meanflow_info": [_vp, _i, C.POINTER(MeanflowInfo)],
+    "rcflow_flowcheck_open": [_vp, _i, _i, _i, C.POINTER(FlowcheckParams)],
+    "rcflow_flowcheck_push_dev": [_vp, _i] + [_vp, _sz] * 10 + [_vp, _vp, _vp],
+    "rcflow_flowcheck_read": [_vp, _i, _vp, _vp, C.POINTER(C.c_longlong)],
+    "rcflow_flowcheck_set": [_vp, _i, _i, _i, C.c_double, _i, C.c_double, C.c_double, C.c_double],
+    "rcflow_flowcheck_reset": [_vp, _i],
+    "rcflow_flowcheck_close": [_vp, _i],
+    "rcflow_flowcheck_info": [_vp, _i, C.POINTER(FlowcheckInfo)],
     "rcflow_comm_unique_id": [_vp],
     "rcflow_comm_init": [_vp, _vp, _i, _i],
     "rcflow_comm_destroy": [_vp],

@@ -43,9 +43,10 @@ from ._lib import RC_KINEMATICS_MAX_RADIUS, RC_KINEMATICS_RELATIVE, RC_KINEMATIC
 from ._lib import RC_SHORE_HIST, SHORE_SOURCES, ShorelineInfo, ShorelineParams
 from ._lib import RC_SURF_MAX_CHANNELS, SurfInfo, SurfParams
 from ._lib import RC_MEANFLOW_DIR_FIXED, RC_MEANFLOW_DIR_OPPOSED, RC_MEANFLOW_SUMS, MeanflowInfo, MeanflowParams
+from ._lib import RC_FLOWCHECK_FILL_NAN, RC_FLOWCHECK_FILL_ZERO, RC_FLOWCHECK_SUMMARY, RC_FLOWCHECK_SUMS, RC_FLOWCHECK_TESTS, FlowcheckInfo, FlowcheckParams
 
 __all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState", "Waves", "Piv", "Transects", "Kinematics",
-           "Shoreline", "Surf", "MeanFlow"]
+           "Shoreline", "Surf", "MeanFlow", "FlowCheck"]
 
 
 # rc_draw_prim as a numpy record (32 bytes): what Context.draw takes and Context.tracers_prims returns
@@ -123,6 +124,12 @@ MEANFLOW_SUMMARY = ("filled", "mask", "bad", "gx", "gy", "sum_m", "held", "pushe
 MEANFLOW_SUMS = ("filled", "n", "su", "sv", "sm", "mask", "bad", "zero")
 MEANFLOW_CELL_DTYPE = np.dtype([("flags", "<i4"), ("filled", "<i4"), ("mask", "<i4"), ("bad", "<i4"), ("mean_x", "<f4"), ("mean_y", "<f4"),
                                 ("steadiness", "<f4"), ("pad", "<i4")])
+# the ten words of a flow-check summary and of a cell's sums, in order; the flags of a pixel by name; rc_flowcheck_cell (32 bytes)
+FLOWCHECK_SUMMARY = ("valid", "bad", "out", "flat", "resid", "nogain", "fb", "fast", "computing", "pushes")
+FLOWCHECK_SUMS = ("valid", "bad", "out", "flat", "resid", "nogain", "fb", "fast", "sum_qx", "sum_qy")
+FLOWCHECK_FLAGS = {"bad": 1, "out": 2, "flat": 4, "resid": 8, "nogain": 16, "fb": 32, "fast": 64}
+FLOWCHECK_CELL_DTYPE = np.dtype([("flags", "<i4"), ("pixels", "<i4"), ("valid", "<i4"), ("valid_pm", "<i4"), ("mean_x", "<f4"), ("mean_y", "<f4"),
+                                 ("pad", "<i4", (2,))])
 RIPMAP_SOURCE_NAMES = {v: k for k, v in RIPMAP_SOURCES.items()}
 TRACERS_MOVER_NAMES = {v: k for k, v in TRACERS_MOVERS.items()}
 SHORE_SOURCE_NAMES = {v: k for k, v in SHORE_SOURCES.items()}
@@ -2065,6 +2072,75 @@ class Context:
     def meanflow_close(self, stream=0):
         self._lifecycle("meanflow", "close", stream)
 
+    # ------------------------------------------------------------------ flow check
+    def flowcheck_open(self, w, h, radius=4, grid_x=30, grid_y=30, tests=RC_FLOWCHECK_TESTS, fill="nan", tex_min=1, gain_pm=0, res_max=1.5,
+                       fb_rel=0.01, fb_abs=0.7071067811865476, speed_max=1000.0, stream=0):
+        """Opens the slot's flow check on w x h frames and fields (include/rcflow.h, "flow check"): per pixel the residual of the
+        match its vector claims, the texture of the previous frame and the round trip against a backward field, over a clipped
+        (2 radius + 1)^2 window, and from them the flags (FLOWCHECK_FLAGS), the mask of the valid pixels and the field with the
+        rejected vectors replaced by NaN (fill="nan") or zero (fill="zero").  tests: which of flat, resid, nogain, fb and fast run,
+        as the sum of their FLOWCHECK_FLAGS."""
+        if fill not in ("nan", "zero"):
+            raise ValueError("fill is 'nan' or 'zero'")
+        p = FlowcheckParams(radius=int(radius), grid_x=int(grid_x), grid_y=int(grid_y), tests=int(tests),
+                            flags=RC_FLOWCHECK_FILL_NAN if fill == "nan" else RC_FLOWCHECK_FILL_ZERO, tex_min=int(tex_min), gain_pm=int(gain_pm),
+                            res_max=float(res_max), fb_rel=float(fb_rel), fb_abs=float(fb_abs), speed_max=float(speed_max))
+        self._bind(stream)          # the state is zeroed on the slot's stream: the one the pushes will run on
+        check(self._lib.rcflow_flowcheck_open(self._h, stream, int(w), int(h), C.byref(p)))
+
+    def flowcheck_info(self, stream=0):
+        """dict(w, h, the parameters, fill, launches_per_push, held, pushes, computing, device_bytes); never blocks."""
+        i = self._info("flowcheck", FlowcheckInfo(), stream)
+        d = _record(i, skip=("flags", "pad"))
+        d["fill"] = "nan" if i.prm.flags == RC_FLOWCHECK_FILL_NAN else "zero"
+        return d
+
+    def flowcheck_push(self, next, prev=None, flow=None, back=None, flags=None, mask=None, checked=None, resid=None, texture=None, picture=None,
+                       cells=None, sums=None, summary=None, stream=0):
+        """One pair of grey frames (HxW uint8 device tensors; prev None: the frame of the push before, which the slot holds) and
+        the field from prev to next (HxWx2 float32, dense pixels, rows may be padded; None: the field push_frame_host /
+        frame_loop_step left on the slot); back: the field from next to prev for the round-trip test, or None.  Nothing is
+        synchronised.  Outputs are preallocated device tensors, each optional: flags and mask HxW uint8 (mask: 255 where valid, what
+        regions_push takes), checked HxWx2 float32 (what meanflow_push, ripmap_push and kinematics_push take), resid HxWx2 float32
+        (window-mean residual with the flow and with no motion, grey levels), texture HxW float32, picture HxWx3 uint8, cells
+        GYxGXx32 uint8 (rc_flowcheck_cell records; view the host copy as FLOWCHECK_CELL_DTYPE), sums GYxGXx10 int64
+        (FLOWCHECK_SUMS), summary 10 int64 (FLOWCHECK_SUMMARY).  Records, sums and summary also stay on the slot for
+        flowcheck_read.  The first push after the open with prev None only stores its frame."""
+        i = self._info("flowcheck", FlowcheckInfo(), stream)
+        h, w, nc = i.h, i.w, i.prm.grid_x * i.prm.grid_y
+        ins = (self._in_image(next, torch.uint8, "next", (h, w)) + self._in_image(prev, torch.uint8, "prev", (h, w), optional=True) +
+               self._in_image(flow, torch.float32, "flow", (h, w, 2), optional=True) + self._in_image(back, torch.float32, "back", (h, w, 2), optional=True))
+        images = (self._out_image(flags, torch.uint8, "flags", (h, w)) + self._out_image(mask, torch.uint8, "mask", (h, w)) +
+                  self._out_image(checked, torch.float32, "checked", (h, w, 2)) + self._out_image(resid, torch.float32, "resid", (h, w, 2)) +
+                  self._out_image(texture, torch.float32, "texture", (h, w)) + self._out_image(picture, torch.uint8, "picture", (h, w, 3)))
+        cp = self._out_array(cells, torch.uint8, "cells", nc * 32)
+        sp = self._out_array(sums, torch.int64, "sums", nc * RC_FLOWCHECK_SUMS)
+        up = self._out_array(summary, torch.int64, "summary", RC_FLOWCHECK_SUMMARY)
+        self._bind(stream)
+        check(self._lib.rcflow_flowcheck_push_dev(self._h, stream, *ins, *images, cp, sp, up))
+
+    def flowcheck_read(self, stream=0):
+        """Waits for the slot's stream -> (cells GYxGX FLOWCHECK_CELL_DTYPE, sums GYxGXx10 int64, dict of the summary by
+        FLOWCHECK_SUMMARY names) of the last computing push; zeros before the first."""
+        info = self.flowcheck_info(stream)
+        gx, gy = info["grid_x"], info["grid_y"]
+        cells, sums = np.zeros((gy, gx), FLOWCHECK_CELL_DTYPE), np.zeros((gy, gx, RC_FLOWCHECK_SUMS), np.int64)
+        summ = np.zeros(RC_FLOWCHECK_SUMMARY, np.int64)
+        self._bind(stream)
+        check(self._lib.rcflow_flowcheck_read(self._h, stream, cells.ctypes.data, sums.ctypes.data, summ.ctypes.data_as(C.POINTER(C.c_longlong))))
+        return cells, sums, dict(zip(FLOWCHECK_SUMMARY, (int(v) for v in summ)))
+
+    def flowcheck_set(self, tests, tex_min, res_max, gain_pm, fb_rel, fb_abs, speed_max, stream=0):
+        """tests, tex_min, res_max, gain_pm, fb_rel, fb_abs and speed_max from the next push on."""
+        check(self._lib.rcflow_flowcheck_set(self._h, stream, int(tests), int(tex_min), float(res_max), int(gain_pm), float(fb_rel), float(fb_abs),
+                                             float(speed_max)))
+
+    def flowcheck_reset(self, stream=0):
+        self._lifecycle("flowcheck", "reset", stream)
+
+    def flowcheck_close(self, stream=0):
+        self._lifecycle("flowcheck", "close", stream)
+
     # ------------------------------------------------------------------ rip regions
     def regions_open(self, w, h, connectivity=8, min_area=1, max_regions=1024, stream=0):
         """Opens the slot's region labelling for w x h masks: connected components (4 or 8 neighbours) numbered in raster
@@ -2441,6 +2517,18 @@ class MeanFlow(_Product):
 
     def set(self, steady_min, speed_min, min_cos2, dir_x, dir_y, min_fill):
         self.ctx.meanflow_set(steady_min, speed_min, min_cos2, dir_x, dir_y, min_fill, self.stream)
+
+
+class FlowCheck(_Product):
+    """The flow check of one slot as an object: Context.flowcheck_* with the context and the slot bound.  Opens on construction
+    (the parameters of Context.flowcheck_open as keywords), closes on close() or at the end of a with block."""
+    product = "flowcheck"
+
+    def push(self, next, prev=None, flow=None, back=None, **outputs):
+        self.ctx.flowcheck_push(next, prev, flow, back, stream=self.stream, **outputs)
+
+    def set(self, tests, tex_min, res_max, gain_pm, fb_rel, fb_abs, speed_max):
+        self.ctx.flowcheck_set(tests, tex_min, res_max, gain_pm, fb_rel, fb_abs, speed_max, self.stream)
 
 
 def kinematics_taps(radius, sigma):

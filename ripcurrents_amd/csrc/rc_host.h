@@ -358,6 +358,20 @@ struct RcMeanflow {
     RcZeroFence zf;
 };
 
+// Flow check of one stream slot (flowcheck_kernels.hip).  Everything is allocated by rcflow_flowcheck_open and released by
+// rcflow_flowcheck_close / rcflow_destroy.
+struct RcFlowcheck {
+    bool open = false;
+    int w = 0, h = 0;
+    rc_flowcheck_params prm{};      // tests and the thresholds: as rcflow_flowcheck_set left them
+    bool held = false;              // `prev` holds the d_next of the push before
+    long long pushes = 0, computing = 0;      // since open; a reset keeps them
+    RcBuf prev;                     // [h][w] uint8, dense: the held frame
+    RcBuf acc;                      // [cells][RC_FLOWCHECK_SUMS] int64 the launch adds into, zero between pushes
+    RcBuf out;                      // the last computing push: summary 10 int64 (a line) | sums [cells][RC_FLOWCHECK_SUMS] int64 | records [cells]
+    RcZeroFence zf;
+};
+
 // warp_kernels.hip: one launch of the affine / perspective warp
 struct RcWarpArgs {
     const uint8_t* src; size_t step;
@@ -443,6 +457,7 @@ struct RcSlot {
     RcShoreline sh;
     RcSurf sf;
     RcMeanflow mf;
+    RcFlowcheck fc;
     RcPhaseCorr pc;
 };
 
@@ -550,7 +565,8 @@ struct rc_ctx {
     X(RC_K_KINEMATICS, "kinematics", RC_B_FARNEBACK) /* @0 smoothing, derivatives, invariants, first sums and the threshold, @1 cores, mask, picture, records and summary */ \
     X(RC_K_SHORELINE, "shoreline", RC_B_OVERLAY) /* @0 indicator, box, plane, histogram and Otsu, @1 lines, @2 outliers, ring, window and records, @3 mask, plane and histogram out, @4 primitives */ \
     X(RC_K_SURF, "surf", RC_B_OVERLAY) /* @0 ring, sums, flags, pictures and counts, @1 lines, @2 reference, channels, records and summary, @3 primitives */ \
-    X(RC_K_MEANFLOW, "meanflow", RC_B_FARNEBACK) /* @0 ring, sums, mean, steadiness, spread, picture, cell sums and G, @1 mask, records and summary */
+    X(RC_K_MEANFLOW, "meanflow", RC_B_FARNEBACK) /* @0 ring, sums, mean, steadiness, spread, picture, cell sums and G, @1 mask, records and summary */ \
+    X(RC_K_FLOWCHECK, "flowcheck", RC_B_FARNEBACK) /* @0 staging, gather, box sums, the tests, every output and cell sums, @1 records and summary */
 #define RC_ROW_ID(id, ...) id,
 enum { RC_BUCKET_TABLE(RC_ROW_ID) RC_B_BUCKETS };
 enum { RC_KIND_TABLE(RC_ROW_ID) RC_K_KINDS };
@@ -638,7 +654,7 @@ struct RcProfScope {
     } while (0)
 
 // ---------------------------------------------------------------------------- per-slot products
-// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView, RcWaves, RcPiv, RcTransects, RcKinematics, RcShoreline, RcSurf and RcMeanflow share one lifecycle.  A product supplies
+// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView, RcWaves, RcPiv, RcTransects, RcKinematics, RcShoreline, RcSurf, RcMeanflow and RcFlowcheck share one lifecycle.  A product supplies
 //   void rc_state_free(T&)             frees every buffer and the fence; the state is T() again
 //   int rc_state_zero(RcSlot&, T&)     rc_fence_zero of what open / reset clear, and the counters
 // and open / reset / close are written once, here.
@@ -658,6 +674,7 @@ void rc_state_free(RcKinematics& k);
 void rc_state_free(RcShoreline& v);
 void rc_state_free(RcSurf& v);
 void rc_state_free(RcMeanflow& v);
+void rc_state_free(RcFlowcheck& v);
 int rc_state_zero(RcSlot& s, RcTimex& t);
 int rc_state_zero(RcSlot& s, RcFrameStab& f);
 int rc_state_zero(RcSlot& s, RcRipMap& m);
@@ -674,6 +691,7 @@ int rc_state_zero(RcSlot& s, RcKinematics& k);
 int rc_state_zero(RcSlot& s, RcShoreline& v);
 int rc_state_zero(RcSlot& s, RcSurf& v);
 int rc_state_zero(RcSlot& s, RcMeanflow& v);
+int rc_state_zero(RcSlot& s, RcFlowcheck& v);
 
 // The tail of every open.  The caller has validated, selected the device and built `fresh` (rc: what its allocations
 // returned).  The state that is open is touched only once nothing can be refused any more: a refused open leaves it as it
