@@ -2357,6 +2357,143 @@ int rcflow_flowcheck_close(rc_ctx* ctx, int stream);
 /* never blocks; RC_ESTATE when nothing is open, RC_EINVAL without a buffer */
 int rcflow_flowcheck_info(rc_ctx* ctx, int stream, rc_flowcheck_info* info);
 
+/* ------------------------------------------------------------------ drifters: fates, retention, escape by origin
+ * From where on this beach is a swimmer carried out, where does everything else end, and how fast?  A population of up to
+ * RC_DRIFTERS_MAX virtual drifters is kept on the device.  Every push moves them through one flow field in exact integers and lets
+ * them die by a named fate; dead drifters are released again at their homes on request.  The product keeps the visit density (the
+ * reference's population map, as a picture), a census by place and by origin cell, and residence-time histograms: the surf-zone
+ * retention and exit rate of field drifter studies.  The reference moves a cloud and draws it (PopulationMap::runLK) and counts
+ * nothing.  tests/_drifters_ref.py states the following in numpy and the kernels equal it bit for bit on every output of every push.
+ * Integers are exact; sums are integer atomics, so no result depends on the order of addition; the few floats for people are
+ * computed in double, each operation rounded on its own.
+ *
+ *  Field sample (the mean flow's rule, word for word).  d_flow_xy 32FC2, pointer and step multiples of 8; NULL is the field the slot's
+ *  frame loop left resident (rcflow_stream_flow_ptr), with the rules of rcflow_meanflow_push_dev.  A pixel is BAD when a component is
+ *  not finite or fabsf(component) >= 500.0f; otherwise q = (int)rintf(component * 64.0f) per component.
+ *  State, 24 bytes a drifter: home (HX, HY) and position (X, Y), int32 in 1/64 pixel, always inside 0..64 (w-1) x 0..64 (h-1); age,
+ *  int32; st, int32: -1 WAITING, 0 ALIVE, f > 0 dead by fate f.  The pixel of a position is ((X + 32) >> 6, (Y + 32) >> 6).
+ *  Fates: 1 EDGE_LEFT, 2 EDGE_TOP, 3 EDGE_RIGHT, 4 EDGE_BOTTOM, 5 BAD, 6 AGED, 8 + z ZONE z (z = 1..7); RC_DRIFTERS_SHORE is 9 (zone
+ *  1) and RC_DRIFTERS_OFFSHORE 10 (zone 2).  There are 16 slots; 0 and 7 are never used.
+ *  One push ("drifters@0"), per drifter, in this order:
+ *   1. Release.  A drifter is released when st == -1, or when st > 0 and RC_DRIFTERS_RESPAWN is set: its position becomes its home,
+ *      its age 0, and it is counted as released in the summary and in its origin cell; its step is (0, 0), T is its home, and
+ *      nothing is sampled.  Without RESPAWN a dead drifter does nothing and is counted nowhere.  A drifter with st == 0 moves.
+ *   2. Move.  ix = X >> 6, fx = X & 63, likewise y; the right and lower neighbours are clamped to w - 1, h - 1.  The four weights
+ *      (64-fx)(64-fy), fx (64-fy), (64-fx) fy, fx fy sum to 4096.  A corner of weight 0 is not looked at; a corner of weight > 0
+ *      that is BAD makes the fate BAD and the position is kept.  Otherwise D = sum of w_i q_i per component (int32), step =
+ *      (D * dt_q + 2^19) >> 20 in int64 with an arithmetic shift (floor), dt_q = rint(dt * 256) taken on the host, 1..65536; T =
+ *      position + step in int64.
+ *   3. Edge, the first that holds: Tx < 0 -> 1; Tx > 64 (w-1) -> 3; Ty < 0 -> 2; Ty > 64 (h-1) -> 4.  The position is kept.
+ *   4. Zone, only when no fate is set so far, a drifter just released (at its home) included: z = min(d_zone byte at T's pixel, 7);
+ *      z > 0 -> fate 8 + z and the position becomes T.  d_zone (8UC1) NULL means every byte is 0.
+ *   5. Age.  A drifter that moved (st was 0; whatever became of it) gets age + 1.  If it has no fate, max_age > 0 and age >= max_age,
+ *      the fate is AGED and the position becomes T.
+ *   6. Alive.  With no fate the position becomes T and st = 0; the drifter adds 1 to the per-push occupancy word of its pixel, 1 to
+ *      the visits of that pixel's by-place cell and its step to that cell's step sums.  Otherwise st = fate, and the death is booked
+ *      in the by-place cell of the pixel of the position it ends on, in the by-origin cell of its home's pixel, in the histogram
+ *      and in the summary.
+ *  Cells are the opposing-flow map's: grid_x x grid_y, the remainder to the last cell, at most RC_RIPMAP_MAX_CELLS.  Both tables are
+ *  RC_DRIFTERS_SUMS = 8 int64 a cell, accumulated since open or reset.  Fates fall in four classes: SHORE, OFFSHORE, EDGE (1..4),
+ *  other.
+ *   By place:  visits | sum of step u | sum of step v | deaths SHORE | OFFSHORE | EDGE | other | sum of age at the OFFSHORE deaths.
+ *   By origin: released | deaths SHORE | OFFSHORE | EDGE | other | sum of age at SHORE deaths | at OFFSHORE deaths | 0.
+ *  Histograms: 4 classes x RC_DRIFTERS_HIST_BINS = 32 bins of uint64, bin = min(31, age / age_bin), since open or reset.
+ *  Summary, RC_DRIFTERS_SUMMARY = 24 int64: drifters | alive after this push | released | pushes since open / reset | sum of age at
+ *  SHORE deaths | at OFFSHORE deaths | 0 | 0 | deaths by fate 0..15; all but the first two since open or reset.
+ *  Records, rc_drifters_cell, floats for people on which no decision depends, taken in double: RC_DRIFTERS_EMPTY when the cell's
+ *  visits and released are both 0; mean_u = (float)(((double)sum of u / 64.0) / (double)visits), mean_v likewise (by place); escape =
+ *  (float)((double)OFFSHORE / (double)all deaths), beached likewise with SHORE, mean_exit_age = (float)((double)sum of age at the
+ *  OFFSHORE deaths / (double)OFFSHORE) (all three by origin); each 0 when its denominator is 0.
+ *  The per-pixel launch ("drifters@1") adds the occupancy plane into the density plane and zeroes it; the density is uint32 state,
+ *  exact while drifters x pushes < 2^32.  It also closes the records and the summary.  Outputs, each may be NULL: d_now 16UC1,
+ *  min(occupancy, 65535); d_density 32-bit unsigned; d_live 8UC1, 255 where occupancy >= live_min, else 0 (what
+ *  rcflow_regions_push_dev takes: where drifters crowd is where foam gathers); d_picture 8UC3, entry min(255, density * 255 /
+ *  density_full) of rcflow_jet_lut in uint64, black where the density is 0.  Per drifter, each may be NULL: d_xy 32FC1 n x 2,
+ *  (float)X / 64.0f, which is exact; d_age int32; d_state uint8, 0 alive, 255 waiting, else the fate.  Row padding is never written. */
+#define RC_DRIFTERS_MAX (1 << 22)
+#define RC_DRIFTERS_SUMS 8
+#define RC_DRIFTERS_HIST_BINS 32
+#define RC_DRIFTERS_SUMMARY 24
+#define RC_DRIFTERS_LAUNCHES 2           /* of every push */
+#define RC_DRIFTERS_RESPAWN 1            /* rc_drifters_params::flags */
+#define RC_DRIFTERS_EMPTY 1              /* rc_drifters_cell::flags */
+#define RC_DRIFTERS_EDGE_LEFT 1          /* the fates */
+#define RC_DRIFTERS_EDGE_TOP 2
+#define RC_DRIFTERS_EDGE_RIGHT 3
+#define RC_DRIFTERS_EDGE_BOTTOM 4
+#define RC_DRIFTERS_BAD 5
+#define RC_DRIFTERS_AGED 6
+#define RC_DRIFTERS_ZONE 8               /* + z, z = 1..7 */
+#define RC_DRIFTERS_SHORE 9
+#define RC_DRIFTERS_OFFSHORE 10
+typedef struct rc_drifters_params {
+    int max_drifters;       /* 1..RC_DRIFTERS_MAX */
+    int grid_x, grid_y;     /* cells, as rcflow_ripmap_open */
+    int max_age;            /* >= 0; 0: nobody dies of age */
+    int age_bin;            /* >= 1: pushes per histogram bin */
+    int density_full;       /* >= 1: the density the picture's last colour stands for */
+    int live_min;           /* >= 1 */
+    int flags;              /* 0 or RC_DRIFTERS_RESPAWN */
+    double dt;              /* fields per push: rint(dt * 256) in 1..65536 */
+} rc_drifters_params;       /* 40 bytes */
+typedef struct rc_drifters_cell {
+    int flags;              /* RC_DRIFTERS_EMPTY */
+    int pad0;
+    float mean_u, mean_v;   /* by place: the mean step of the visits, pixels per push */
+    float escape, beached;  /* by origin: the shares of the deaths that were OFFSHORE, SHORE */
+    float mean_exit_age;    /* by origin: pushes from release to an OFFSHORE death */
+    int pad1;
+} rc_drifters_cell;         /* 32 bytes */
+typedef struct rc_drifters_info {
+    int w, h;
+    rc_drifters_params prm;            /* as rcflow_drifters_set left them */
+    int launches_per_push;             /* RC_DRIFTERS_LAUNCHES */
+    int drifters;                      /* seeded so far */
+    long long pushes;                  /* since open / reset */
+    size_t device_bytes;
+} rc_drifters_info;
+/* Allocates everything the slot will ever need.  Re-opening replaces the state; a refused open leaves the open state as it was.
+ * RC_EINVAL without parameters, for a value outside the ranges above (or a dt that is not finite), a grid that does not fit;
+ * RC_ESIZE beyond the context's max_w x max_h. */
+int rcflow_drifters_open(rc_ctx* ctx, int stream, int w, int h, const rc_drifters_params* prm);
+/* Appends n drifters as WAITING from host points, n x (x, y) doubles in pixels: X = llrint(x * 64.0) taken on the host.  A point
+ * that is not finite or lies outside 0..w-1 x 0..h-1 is RC_EINVAL and nothing is added; more than max_drifters in all is RC_ESIZE.
+ * Blocks, as rcflow_tracers_add does.  Drifters seeded after pushes are released by the next push. */
+int rcflow_drifters_seed(rc_ctx* ctx, int stream, const double* xy, int n);
+/* One field.  d_zone 8UC1 or NULL; d_now 16UC1 (pointer and step multiples of 2), d_density 32-bit (multiples of 4), d_live 8UC1,
+ * d_picture 8UC3; d_xy n x 2 floats (8-byte aligned), d_age n int32, d_state n bytes, n the drifters seeded; d_cells cells x
+ * rc_drifters_cell (4-byte aligned), d_place and d_origin cells x RC_DRIFTERS_SUMS int64, d_hist 4 x RC_DRIFTERS_HIST_BINS uint64 and
+ * d_summary RC_DRIFTERS_SUMMARY int64 (8-byte aligned).  What a push does to the state does not depend on which outputs it asked
+ * for.  No host synchronisation, no device-to-host copy.  An output whose byte range overlaps an input's or another output's is
+ * RC_EINVAL.  Every refusal is decided before anything is queued and leaves the state as it was; RC_ESTATE before
+ * rcflow_drifters_open, with no drifter seeded, and with d_flow_xy NULL while no field is resident (RC_ESIZE when the resident
+ * field has another size).  RC_EHIP (the runtime refused a launch) is no refusal: the state is undefined until
+ * rcflow_drifters_reset. */
+int rcflow_drifters_push_dev(rc_ctx* ctx, int stream, const float* d_flow_xy, size_t flow_step, const uint8_t* d_zone, size_t zone_step,
+                             uint16_t* d_now, size_t now_step, uint32_t* d_density, size_t density_step, uint8_t* d_live, size_t live_step,
+                             uint8_t* d_picture, size_t picture_step, float* d_xy, int32_t* d_age, uint8_t* d_state, rc_drifters_cell* d_cells,
+                             long long* d_place, long long* d_origin, unsigned long long* d_hist, long long* d_summary);
+/* Blocks until the slot's stream has finished; for hosts and tests.  Each may be NULL (host memory): the records and the summary of
+ * the last push, zeros before the first; both tables and the histograms as they stand. */
+int rcflow_drifters_read(rc_ctx* ctx, int stream, rc_drifters_cell* cells, long long* place, long long* origin, unsigned long long* hist,
+                         long long summary[RC_DRIFTERS_SUMMARY]);
+/* dt, max_age, density_full, live_min and flags (the RESPAWN bit) from the next push on; RC_EINVAL as rcflow_drifters_open */
+int rcflow_drifters_set(rc_ctx* ctx, int stream, double dt, int max_age, int density_full, int live_min, int flags);
+/* every drifter goes to WAITING at its home with age 0; tables, histograms, density, the last push's records and summary and the
+ * push count go to zero; keeps the allocation, the drifters and the parameters as rcflow_drifters_set left them; asynchronous, on
+ * the slot's stream */
+int rcflow_drifters_reset(rc_ctx* ctx, int stream);
+/* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
+int rcflow_drifters_close(rc_ctx* ctx, int stream);
+/* never blocks; RC_ESTATE when nothing is open, RC_EINVAL without a buffer */
+int rcflow_drifters_info(rc_ctx* ctx, int stream, rc_drifters_info* info);
+/* The zones helper ("drifters@2"), stateless and one launch: the shoreline's wet mask and the surf zone's mask into the byte map a
+ * push takes, without a host round trip.  A pixel with a zero d_wet byte is zone 1 (SHORE); otherwise a pixel with a zero d_inside
+ * byte is zone 2 (OFFSHORE); otherwise 0.  All three 8UC1, w x h.  Either input may be NULL (no such zone), not both (RC_EINVAL);
+ * d_zone may overlap neither. */
+int rcflow_drifters_zones_dev(rc_ctx* ctx, int stream, const uint8_t* d_wet, size_t wet_step, const uint8_t* d_inside, size_t inside_step, int w,
+                              int h, uint8_t* d_zone, size_t zone_step);
+
 /* Display path, ripcurrents.cpp:233-273 (= streamline_displacement / _total_motion / _ratio /
  * _positions, ripcurrents_module.cpp:13-60) on the slot's streamline field (rcflow_advect_field_dev):
  * which 0 = |pt|, 1 = dist, 2 = |pt| / dist; minMaxLoc + convertTo(CV_8UC1, 255/max) +
@@ -2437,7 +2574,7 @@ int rcflow_profile_read(rc_ctx* ctx, int cap, const char** names, int* launches,
 
 /* The same totals under the reference's own bucket names, in the order it prints them (ripcurrents.cpp:103-109,
  * :518-524): farneback, polar, threshold, overlay, erosion, codec, stream ("pathlines").  GPU time of the kernels
- * that do each bucket's work ("overlay" includes the time-exposure images, the 8-bit colour stages, the wave spectra, the shoreline and the surf zone, "farneback" the frame stabilisation, the opposing-flow map, the motion templates, the plan view, the ensemble PIV, the flow kinematics, the mean flow and the flow check, "stream" the flow map and FTLE and the transects); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
+ * that do each bucket's work ("overlay" includes the time-exposure images, the 8-bit colour stages, the wave spectra, the shoreline and the surf zone, "farneback" the frame stabilisation, the opposing-flow map, the motion templates, the plan view, the ensemble PIV, the flow kinematics, the mean flow and the flow check, "stream" the flow map and FTLE, the transects and the drifters); "polar" is 0 (the cartToPolar of :305-309 is fused into the histogram and
  * classification kernels, booked under "threshold"), "codec" is 0 (video decode is host I/O outside the library).
  * names / ms: RC_PROFILE_BUCKETS entries each (either may be NULL).  Returns RC_PROFILE_BUCKETS. */
 #define RC_PROFILE_BUCKETS 7

@@ -1524,4 +1524,80 @@ class FlowCheck {
     DeviceImage d_next_, d_prev_, d_flow_, d_back_, d_flags_, d_mask_, d_checked_, d_resid_, d_texture_, d_picture_;
 };
 
+// the pictures of a Drifters::push, each optional: now 16UC1, density 32-bit unsigned (one channel of 4 bytes), live 8UC1, picture 8UC3
+struct DriftersPictures { Mat* now = nullptr; Mat* density = nullptr; Mat* live = nullptr; Mat* picture = nullptr; };
+
+// Virtual drifters on the device (rcflow_drifters_*): a population of points that every push moves through a flow field in exact
+// integers until they die by a named fate, released again at their homes on request.  Host flow fields (32FC2) and zone maps (8UC1)
+// of the pipeline's size in; the visit density as pictures, the census by place and by origin cell, the residence-time histograms
+// and a summary out.  The per-drifter arrays of the entry point are for consumers on the device and are not staged here.
+class Drifters {
+  public:
+    using Pictures = DriftersPictures;
+
+    Drifters(Pipeline& pipe, const rc_drifters_params& prm) : pipe_(pipe), cells_(prm.grid_x * prm.grid_y) {
+        check(rcflow_drifters_open(pipe.context(), 0, pipe.width(), pipe.height(), &prm));
+    }
+    ~Drifters() { (void)rcflow_drifters_close(pipe_.context(), 0); }
+    Drifters(const Drifters&) = delete;
+    Drifters& operator=(const Drifters&) = delete;
+
+    // n x (x, y) in pixels: waiting drifters, released at these homes by the next push
+    void seed(const std::vector<double>& xy) { check(rcflow_drifters_seed(pipe_.context(), 0, xy.data(), (int)(xy.size() / 2))); }
+
+    // flow: 32FC2 of the pipeline's size; zone: 8UC1 (1 shore, 2 offshore, up to 7), or null for none.  The records, both tables, the
+    // histograms and the summary stay on the session after every push.
+    void push(const Mat& flow, const Mat* zone = nullptr, const Pictures& out = Pictures()) {
+        const int w = pipe_.width(), h = pipe_.height();
+        if (!is_image(flow, w, h, 2, 4)) throw Error(RC_EINVAL, "Drifters::push: the field must be 32FC2 of the pipeline's size");
+        if (zone && !is_image(*zone, w, h, 1, 1)) throw Error(RC_EINVAL, "Drifters::push: the zones must be 8UC1 of the pipeline's size");
+        if ((out.now && !is_image(*out.now, w, h, 1, 2)) || (out.density && !is_image(*out.density, w, h, 1, 4)) ||
+            (out.live && !is_image(*out.live, w, h, 1, 1)) || (out.picture && !is_image(*out.picture, w, h, 3, 1)))
+            throw Error(RC_EINVAL, "Drifters::push: now 16UC1, density one channel of 4 bytes, live 8UC1, picture 8UC3, each of the pipeline's size");
+        staged(pipe_.context(), {{d_flow_, &flow}, {d_zone_, zone}}, [&] {
+            return rcflow_drifters_push_dev(pipe_.context(), 0, d_flow_.ptr<const float>(), d_flow_.pitch(), d_zone_.ptr<const uint8_t>(zone), d_zone_.pitch(),
+                                            d_now_.ptr<uint16_t>(out.now), d_now_.pitch(), d_density_.ptr<uint32_t>(out.density), d_density_.pitch(),
+                                            d_live_.ptr<uint8_t>(out.live), d_live_.pitch(), d_picture_.ptr<uint8_t>(out.picture), d_picture_.pitch(),
+                                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+        }, {{d_now_, out.now}, {d_density_, out.density}, {d_live_, out.live}, {d_picture_, out.picture}});
+    }
+    // each waits for the pipeline's stream (include/rcflow.h).  The summary: drifters, alive, released, pushes, the sums of age at the
+    // SHORE and at the OFFSHORE deaths, 0, 0, the deaths by fate 0..15
+    std::vector<long long> read() {
+        std::vector<long long> s(RC_DRIFTERS_SUMMARY);
+        check(rcflow_drifters_read(pipe_.context(), 0, nullptr, nullptr, nullptr, nullptr, s.data()));
+        return s;
+    }
+    std::vector<rc_drifters_cell> cells() {
+        std::vector<rc_drifters_cell> r((size_t)cells_);
+        check(rcflow_drifters_read(pipe_.context(), 0, r.data(), nullptr, nullptr, nullptr, nullptr));
+        return r;
+    }
+    std::vector<long long> place() {
+        std::vector<long long> s((size_t)cells_ * RC_DRIFTERS_SUMS);
+        check(rcflow_drifters_read(pipe_.context(), 0, nullptr, s.data(), nullptr, nullptr, nullptr));
+        return s;
+    }
+    std::vector<long long> origin() {
+        std::vector<long long> s((size_t)cells_ * RC_DRIFTERS_SUMS);
+        check(rcflow_drifters_read(pipe_.context(), 0, nullptr, nullptr, s.data(), nullptr, nullptr));
+        return s;
+    }
+    std::vector<unsigned long long> hist() {
+        std::vector<unsigned long long> s((size_t)4 * RC_DRIFTERS_HIST_BINS);
+        check(rcflow_drifters_read(pipe_.context(), 0, nullptr, nullptr, nullptr, s.data(), nullptr));
+        return s;
+    }
+    void set(double dt, int max_age, int density_full, int live_min, int flags) {
+        check(rcflow_drifters_set(pipe_.context(), 0, dt, max_age, density_full, live_min, flags));
+    }
+    rc_drifters_info info() { rc_drifters_info i; check(rcflow_drifters_info(pipe_.context(), 0, &i)); return i; }
+    void reset() { check(rcflow_drifters_reset(pipe_.context(), 0)); }
+
+  private:
+    Pipeline& pipe_;
+    int cells_ = 0;
+    DeviceImage d_flow_, d_zone_, d_now_, d_density_, d_live_, d_picture_;
+};
+
 }  // namespace rc

@@ -81,6 +81,10 @@ RC_MEANFLOW_MAX_WINDOW, RC_MEANFLOW_SUMS, RC_MEANFLOW_MAX_STATE_BYTES, RC_MEANFL
 RC_FLOWCHECK_BAD, RC_FLOWCHECK_OUT, RC_FLOWCHECK_FLAT, RC_FLOWCHECK_RESID, RC_FLOWCHECK_NOGAIN, RC_FLOWCHECK_FB, RC_FLOWCHECK_FAST = 1, 2, 4, 8, 16, 32, 64
 RC_FLOWCHECK_TESTS, RC_FLOWCHECK_FILL_NAN, RC_FLOWCHECK_FILL_ZERO, RC_FLOWCHECK_NONE_VALID = 124, 1, 2, 1
 RC_FLOWCHECK_MAX_RADIUS, RC_FLOWCHECK_SUMS, RC_FLOWCHECK_SUMMARY, RC_FLOWCHECK_LAUNCHES = 7, 10, 10, 2
+# rcflow_drifters_*: the bounds, the words of a cell's sums and of the summary, the launches of a push, the flags, the fates
+RC_DRIFTERS_MAX, RC_DRIFTERS_SUMS, RC_DRIFTERS_HIST_BINS, RC_DRIFTERS_SUMMARY, RC_DRIFTERS_LAUNCHES = 1 << 22, 8, 32, 24, 2
+RC_DRIFTERS_RESPAWN, RC_DRIFTERS_EMPTY = 1, 1
+DRIFTERS_FATES = {"edge_left": 1, "edge_top": 2, "edge_right": 3, "edge_bottom": 4, "bad": 5, "aged": 6, "shore": 9, "offshore": 10}
 
 ERRORS = {-1: "RC_EINVAL", -2: "RC_ENOMEM", -3: "RC_EHIP", -4: "RC_ENODEV", -5: "RC_ESIZE",
           -6: "RC_ESTATE", -7: "RC_ECOMM"}
@@ -350,6 +354,24 @@ class FlowcheckInfo(C.Structure):
                 ("pushes", C.c_longlong), ("computing", C.c_longlong), ("device_bytes", C.c_size_t)]
 
 
+class DriftersParams(C.Structure):
+    """rc_drifters_params (include/rcflow.h), 40 bytes."""
+    _fields_ = [("max_drifters", C.c_int), ("grid_x", C.c_int), ("grid_y", C.c_int), ("max_age", C.c_int), ("age_bin", C.c_int),
+                ("density_full", C.c_int), ("live_min", C.c_int), ("flags", C.c_int), ("dt", C.c_double)]
+
+
+class DriftersCell(C.Structure):
+    """rc_drifters_cell (include/rcflow.h), 32 bytes; numpy: api.DRIFTERS_CELL_DTYPE."""
+    _fields_ = [("flags", C.c_int), ("pad0", C.c_int), ("mean_u", C.c_float), ("mean_v", C.c_float), ("escape", C.c_float),
+                ("beached", C.c_float), ("mean_exit_age", C.c_float), ("pad1", C.c_int)]
+
+
+class DriftersInfo(C.Structure):
+    """rc_drifters_info (include/rcflow.h)."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", DriftersParams), ("launches_per_push", C.c_int), ("drifters", C.c_int),
+                ("pushes", C.c_longlong), ("device_bytes", C.c_size_t)]
+
+
 class SurfInfo(C.Structure):
     """rc_surf_info (include/rcflow.h)."""
     _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", SurfParams), ("lines", C.c_int), ("samples", C.c_int),
@@ -596,6 +618,15 @@ SIGNATURES = {
     "rcflow_flowcheck_reset": [_vp, _i],
     "rcflow_flowcheck_close": [_vp, _i],
     "rcflow_flowcheck_info": [_vp, _i, C.POINTER(FlowcheckInfo)],
+    "rcflow_drifters_open": [_vp, _i, _i, _i, C.POINTER(DriftersParams)],
+    "rcflow_drifters_seed": [_vp, _i, C.POINTER(C.c_double), _i],
+    "rcflow_drifters_push_dev": [_vp, _i] + [_vp, _sz] * 6 + [_vp] * 8,
+    "rcflow_drifters_read": [_vp, _i, _vp, _vp, _vp, _vp, C.POINTER(C.c_longlong)],
+    "rcflow_drifters_set": [_vp, _i, C.c_double, _i, _i, _i, _i],
+    "rcflow_drifters_reset": [_vp, _i],
+    "rcflow_drifters_close": [_vp, _i],
+    "rcflow_drifters_info": [_vp, _i, C.POINTER(DriftersInfo)],
+    "rcflow_drifters_zones_dev": [_vp, _i, _vp, _sz, _vp, _sz, _i, _i, _vp, _sz],
     "rcflow_comm_unique_id": [_vp],
     "rcflow_comm_init": [_vp, _vp, _i, _i],
     "rcflow_comm_destroy": [_vp],

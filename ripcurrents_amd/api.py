@@ -44,9 +44,10 @@ from ._lib import RC_SHORE_HIST, SHORE_SOURCES, ShorelineInfo, ShorelineParams
 from ._lib import RC_SURF_MAX_CHANNELS, SurfInfo, SurfParams
 from ._lib import RC_MEANFLOW_DIR_FIXED, RC_MEANFLOW_DIR_OPPOSED, RC_MEANFLOW_SUMS, MeanflowInfo, MeanflowParams
 from ._lib import RC_FLOWCHECK_FILL_NAN, RC_FLOWCHECK_FILL_ZERO, RC_FLOWCHECK_SUMMARY, RC_FLOWCHECK_SUMS, RC_FLOWCHECK_TESTS, FlowcheckInfo, FlowcheckParams
+from ._lib import RC_DRIFTERS_HIST_BINS, RC_DRIFTERS_RESPAWN, RC_DRIFTERS_SUMMARY, RC_DRIFTERS_SUMS, DriftersInfo, DriftersParams
 
 __all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState", "Waves", "Piv", "Transects", "Kinematics",
-           "Shoreline", "Surf", "MeanFlow", "FlowCheck"]
+           "Shoreline", "Surf", "MeanFlow", "FlowCheck", "Drifters"]
 
 
 # rc_draw_prim as a numpy record (32 bytes): what Context.draw takes and Context.tracers_prims returns
@@ -130,6 +131,12 @@ FLOWCHECK_SUMS = ("valid", "bad", "out", "flat", "resid", "nogain", "fb", "fast"
 FLOWCHECK_FLAGS = {"bad": 1, "out": 2, "flat": 4, "resid": 8, "nogain": 16, "fb": 32, "fast": 64}
 FLOWCHECK_CELL_DTYPE = np.dtype([("flags", "<i4"), ("pixels", "<i4"), ("valid", "<i4"), ("valid_pm", "<i4"), ("mean_x", "<f4"), ("mean_y", "<f4"),
                                  ("pad", "<i4", (2,))])
+# the 24 words of a drifters summary and the eight of a cell in each table, in order; rc_drifters_cell (32 bytes) as a numpy record
+DRIFTERS_SUMMARY = ("drifters", "alive", "released", "pushes", "age_shore", "age_offshore", "zero6", "zero7") + tuple("fate%d" % f for f in range(16))
+DRIFTERS_PLACE = ("visits", "su", "sv", "shore", "offshore", "edge", "other", "age_offshore")
+DRIFTERS_ORIGIN = ("released", "shore", "offshore", "edge", "other", "age_shore", "age_offshore", "zero")
+DRIFTERS_CELL_DTYPE = np.dtype([("flags", "<i4"), ("pad0", "<i4"), ("mean_u", "<f4"), ("mean_v", "<f4"), ("escape", "<f4"), ("beached", "<f4"),
+                                ("mean_exit_age", "<f4"), ("pad1", "<i4")])
 RIPMAP_SOURCE_NAMES = {v: k for k, v in RIPMAP_SOURCES.items()}
 TRACERS_MOVER_NAMES = {v: k for k, v in TRACERS_MOVERS.items()}
 SHORE_SOURCE_NAMES = {v: k for k, v in SHORE_SOURCES.items()}
@@ -2141,6 +2148,94 @@ class Context:
     def flowcheck_close(self, stream=0):
         self._lifecycle("flowcheck", "close", stream)
 
+    # ------------------------------------------------------------------ drifters
+    def drifters_open(self, w, h, max_drifters=1 << 16, grid_x=30, grid_y=30, dt=1.0, max_age=0, age_bin=8, density_full=16, live_min=1,
+                      respawn=False, stream=0):
+        """Opens the slot's virtual drifters on w x h flow fields (include/rcflow.h, "drifters"): up to max_drifters points that
+        every push moves dt fields through the field in exact integers, until they die by a fate (an edge, a bad vector, max_age
+        pushes, a zone of the push's byte map); with respawn=True the dead are released again at their homes.  Keeps the visit
+        density, the census by place and by origin on a grid_x x grid_y grid, and residence-time histograms of age_bin pushes a
+        bin.  The state takes 24 bytes a drifter and 8 a pixel of device memory."""
+        p = DriftersParams(max_drifters=int(max_drifters), grid_x=int(grid_x), grid_y=int(grid_y), max_age=int(max_age), age_bin=int(age_bin),
+                           density_full=int(density_full), live_min=int(live_min), flags=RC_DRIFTERS_RESPAWN if respawn else 0, dt=float(dt))
+        self._bind(stream)          # the state is zeroed on the slot's stream: the one the pushes will run on
+        check(self._lib.rcflow_drifters_open(self._h, stream, int(w), int(h), C.byref(p)))
+
+    def drifters_info(self, stream=0):
+        """dict(w, h, the parameters, respawn, launches_per_push, drifters, pushes, device_bytes); never blocks."""
+        i = self._info("drifters", DriftersInfo(), stream)
+        d = _record(i, skip=("flags",))
+        d["respawn"] = bool(i.prm.flags & RC_DRIFTERS_RESPAWN)
+        return d
+
+    def drifters_seed(self, xy, stream=0):
+        """Appends the host points xy (N x 2, pixels) as waiting drifters; they are released at these homes by the next push.
+        Blocks."""
+        pts = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+        self._bind(stream)
+        check(self._lib.rcflow_drifters_seed(self._h, stream, pts.ctypes.data_as(C.POINTER(C.c_double)), pts.shape[0]))
+
+    def drifters_push(self, flow=None, zone=None, now=None, density=None, live=None, picture=None, xy=None, age=None, state=None, cells=None,
+                      place=None, origin=None, hist=None, summary=None, stream=0):
+        """One flow field (HxWx2 float32 device tensor, dense pixels, rows may be padded; None: the field push_frame_host /
+        frame_loop_step left on the slot) and the zones (HxW uint8: 1 shore, 2 offshore, up to 7; None: no zone; drifters_zones
+        makes it); nothing is synchronised.  Outputs are preallocated device tensors, each optional: now HxW int16 (this push's
+        occupancy, saturated, as uint16 bits), density HxW int32 (uint32 bits), live HxW uint8 (255 where at least live_min
+        drifters are: what regions_push takes), picture HxWx3 uint8 (the density in JET colours); per drifter xy Nx2 float32, age
+        N int32, state N uint8 (0 alive, 255 waiting, else the fate); cells GYxGXx32 uint8 (rc_drifters_cell records; view the
+        host copy as DRIFTERS_CELL_DTYPE), place and origin GYxGXx8 int64 (DRIFTERS_PLACE, DRIFTERS_ORIGIN), hist 4x32 int64
+        (uint64 bits), summary 24 int64 (DRIFTERS_SUMMARY).  All of the last five also stay on the slot for drifters_read."""
+        i = self._info("drifters", DriftersInfo(), stream)
+        h, w, nc, n = i.h, i.w, i.prm.grid_x * i.prm.grid_y, i.drifters
+        ins = self._in_image(flow, torch.float32, "flow", (h, w, 2), optional=True) + self._in_image(zone, torch.uint8, "zone", (h, w), optional=True)
+        images = (self._out_image(now, torch.int16, "now", (h, w)) + self._out_image(density, torch.int32, "density", (h, w)) +
+                  self._out_image(live, torch.uint8, "live", (h, w)) + self._out_image(picture, torch.uint8, "picture", (h, w, 3)))
+        arrays = (self._out_array(xy, torch.float32, "xy", 2 * n), self._out_array(age, torch.int32, "age", n),
+                  self._out_array(state, torch.uint8, "state", n), self._out_array(cells, torch.uint8, "cells", nc * 32),
+                  self._out_array(place, torch.int64, "place", nc * RC_DRIFTERS_SUMS), self._out_array(origin, torch.int64, "origin", nc * RC_DRIFTERS_SUMS),
+                  self._out_array(hist, torch.int64, "hist", 4 * RC_DRIFTERS_HIST_BINS), self._out_array(summary, torch.int64, "summary", RC_DRIFTERS_SUMMARY))
+        self._bind(stream)
+        check(self._lib.rcflow_drifters_push_dev(self._h, stream, *ins, *images, *arrays))
+
+    def drifters_read(self, stream=0):
+        """Waits for the slot's stream -> (cells GYxGX DRIFTERS_CELL_DTYPE, place GYxGXx8 int64, origin GYxGXx8 int64, hist 4x32
+        uint64, dict of the summary by DRIFTERS_SUMMARY names): the records and the summary of the last push, zeros before the
+        first; the tables and the histograms as they stand."""
+        info = self.drifters_info(stream)
+        gx, gy = info["grid_x"], info["grid_y"]
+        cells = np.zeros((gy, gx), DRIFTERS_CELL_DTYPE)
+        place, origin = np.zeros((gy, gx, RC_DRIFTERS_SUMS), np.int64), np.zeros((gy, gx, RC_DRIFTERS_SUMS), np.int64)
+        hist, summ = np.zeros((4, RC_DRIFTERS_HIST_BINS), np.uint64), np.zeros(RC_DRIFTERS_SUMMARY, np.int64)
+        self._bind(stream)
+        check(self._lib.rcflow_drifters_read(self._h, stream, cells.ctypes.data, place.ctypes.data, origin.ctypes.data, hist.ctypes.data,
+                                             summ.ctypes.data_as(C.POINTER(C.c_longlong))))
+        return cells, place, origin, hist, dict(zip(DRIFTERS_SUMMARY, (int(v) for v in summ)))
+
+    def drifters_set(self, dt, max_age, density_full, live_min, respawn, stream=0):
+        """dt, max_age, density_full, live_min and respawn from the next push on."""
+        check(self._lib.rcflow_drifters_set(self._h, stream, float(dt), int(max_age), int(density_full), int(live_min),
+                                            RC_DRIFTERS_RESPAWN if respawn else 0))
+
+    def drifters_reset(self, stream=0):
+        self._lifecycle("drifters", "reset", stream)
+
+    def drifters_close(self, stream=0):
+        self._lifecycle("drifters", "close", stream)
+
+    def drifters_zones(self, wet=None, inside=None, out=None, stream=0):
+        """The zones a push takes from the shoreline's wet mask and the surf zone's mask (HxW uint8 device tensors, either may be
+        None, not both): 1 (shore) where wet is 0, else 2 (offshore) where inside is 0, else 0 -> HxW uint8; one launch, nothing
+        is synchronised."""
+        src = wet if wet is not None else inside
+        if src is None:
+            raise ValueError("wet and inside are both None")
+        h, w = int(src.shape[0]), int(src.shape[1])
+        ins = self._in_image(wet, torch.uint8, "wet", (h, w), optional=True) + self._in_image(inside, torch.uint8, "inside", (h, w), optional=True)
+        out = self._out_or_new(out, torch.uint8, "out", (h, w), dense=True)
+        self._bind(stream)
+        check(self._lib.rcflow_drifters_zones_dev(self._h, stream, *ins, w, h, self._ptr(out), out.stride(0)))
+        return out
+
     # ------------------------------------------------------------------ rip regions
     def regions_open(self, w, h, connectivity=8, min_area=1, max_regions=1024, stream=0):
         """Opens the slot's region labelling for w x h masks: connected components (4 or 8 neighbours) numbered in raster
@@ -2529,6 +2624,21 @@ class FlowCheck(_Product):
 
     def set(self, tests, tex_min, res_max, gain_pm, fb_rel, fb_abs, speed_max):
         self.ctx.flowcheck_set(tests, tex_min, res_max, gain_pm, fb_rel, fb_abs, speed_max, self.stream)
+
+
+class Drifters(_Product):
+    """The virtual drifters of one slot as an object: Context.drifters_* with the context and the slot bound.  Opens on construction
+    (the parameters of Context.drifters_open as keywords), closes on close() or at the end of a with block."""
+    product = "drifters"
+
+    def seed(self, xy):
+        self.ctx.drifters_seed(xy, self.stream)
+
+    def push(self, flow=None, zone=None, **outputs):
+        self.ctx.drifters_push(flow, zone, stream=self.stream, **outputs)
+
+    def set(self, dt, max_age, density_full, live_min, respawn):
+        self.ctx.drifters_set(dt, max_age, density_full, live_min, respawn, self.stream)
 
 
 def kinematics_taps(radius, sigma):

@@ -372,6 +372,26 @@ struct RcFlowcheck {
     RcZeroFence zf;
 };
 
+// Virtual drifters of one stream slot (drifters_kernels.hip).  Everything is allocated by rcflow_drifters_open and released by
+// rcflow_drifters_close / rcflow_destroy.
+struct RcDrifters {
+    bool open = false;
+    int w = 0, h = 0;
+    rc_drifters_params prm{};       // dt, max_age, density_full, live_min and the RESPAWN bit: as rcflow_drifters_set left them
+    int P = 0;                      // row pitch of the occupancy and density planes in pixels (w rounded up to 4)
+    int n = 0;                      // drifters seeded; a reset keeps them
+    long long pushes = 0;           // since open / reset
+    RcBuf st;                       // HX | HY | X | Y | age | st, [max_drifters] int32 each: 24 bytes a drifter
+    RcBuf occ;                      // [h][P] uint32: the occupancy of the push under way, zero between pushes
+    RcBuf dens;                     // [h][P] uint32: the visit density
+    RcBuf tab;                      // by place | by origin, [cells][RC_DRIFTERS_SUMS] int64 each, since open / reset
+    RcBuf stat;                     // the summary's cumulative words, RC_DRIFTERS_SUMMARY int64 | the histograms [4][RC_DRIFTERS_HIST_BINS] uint64
+    RcBuf out;                      // the last push: summary RC_DRIFTERS_SUMMARY int64 | records [cells]
+    RcBuf ctl;                      // DrCtl: the living of the push under way
+    RcBuf jet;                      // COLORMAP_JET, 768 bytes
+    RcZeroFence zf;
+};
+
 // warp_kernels.hip: one launch of the affine / perspective warp
 struct RcWarpArgs {
     const uint8_t* src; size_t step;
@@ -458,6 +478,7 @@ struct RcSlot {
     RcSurf sf;
     RcMeanflow mf;
     RcFlowcheck fc;
+    RcDrifters dr;
     RcPhaseCorr pc;
 };
 
@@ -521,7 +542,8 @@ struct rc_ctx {
 // are booked with those, under "farneback".  The shoreline works on pictures, not on flow: the time-exposure MEAN, the plan view's
 // picture or a frame, as the time-exposure images and the wave spectra do, and is booked with them, under "overlay".  The surf zone
 // is the time exposure's fourth picture and what is read off it, and is booked there too.  The mean current keeps a window over
-// the flow field and decides from its mean, as the opposing-flow map does, and is booked where that is, under "farneback".
+// the flow field and decides from its mean, as the opposing-flow map does, and is booked where that is, under "farneback".  The
+// virtual drifters carry points through the field as the tracer lines do and are booked with them, under "stream".
 #define RC_BUCKET_TABLE(X) \
     X(RC_B_FARNEBACK, "farneback") X(RC_B_POLAR, "polar") X(RC_B_THRESHOLD, "threshold") X(RC_B_OVERLAY, "overlay") \
     X(RC_B_EROSION, "erosion") X(RC_B_CODEC, "codec") X(RC_B_STREAM, "stream")
@@ -566,7 +588,8 @@ struct rc_ctx {
     X(RC_K_SHORELINE, "shoreline", RC_B_OVERLAY) /* @0 indicator, box, plane, histogram and Otsu, @1 lines, @2 outliers, ring, window and records, @3 mask, plane and histogram out, @4 primitives */ \
     X(RC_K_SURF, "surf", RC_B_OVERLAY) /* @0 ring, sums, flags, pictures and counts, @1 lines, @2 reference, channels, records and summary, @3 primitives */ \
     X(RC_K_MEANFLOW, "meanflow", RC_B_FARNEBACK) /* @0 ring, sums, mean, steadiness, spread, picture, cell sums and G, @1 mask, records and summary */ \
-    X(RC_K_FLOWCHECK, "flowcheck", RC_B_FARNEBACK) /* @0 staging, gather, box sums, the tests, every output and cell sums, @1 records and summary */
+    X(RC_K_FLOWCHECK, "flowcheck", RC_B_FARNEBACK) /* @0 staging, gather, box sums, the tests, every output and cell sums, @1 records and summary */ \
+    X(RC_K_DRIFTERS, "drifters", RC_B_STREAM) /* @0 release, gather, fates and the scattered adds, @1 density, pictures, records and summary, @2 the zones helper */
 #define RC_ROW_ID(id, ...) id,
 enum { RC_BUCKET_TABLE(RC_ROW_ID) RC_B_BUCKETS };
 enum { RC_KIND_TABLE(RC_ROW_ID) RC_K_KINDS };
@@ -654,7 +677,7 @@ struct RcProfScope {
     } while (0)
 
 // ---------------------------------------------------------------------------- per-slot products
-// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView, RcWaves, RcPiv, RcTransects, RcKinematics, RcShoreline, RcSurf, RcMeanflow and RcFlowcheck share one lifecycle.  A product supplies
+// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView, RcWaves, RcPiv, RcTransects, RcKinematics, RcShoreline, RcSurf, RcMeanflow, RcFlowcheck and RcDrifters share one lifecycle.  A product supplies
 //   void rc_state_free(T&)             frees every buffer and the fence; the state is T() again
 //   int rc_state_zero(RcSlot&, T&)     rc_fence_zero of what open / reset clear, and the counters
 // and open / reset / close are written once, here.
@@ -675,6 +698,7 @@ void rc_state_free(RcShoreline& v);
 void rc_state_free(RcSurf& v);
 void rc_state_free(RcMeanflow& v);
 void rc_state_free(RcFlowcheck& v);
+void rc_state_free(RcDrifters& v);
 int rc_state_zero(RcSlot& s, RcTimex& t);
 int rc_state_zero(RcSlot& s, RcFrameStab& f);
 int rc_state_zero(RcSlot& s, RcRipMap& m);
@@ -692,6 +716,7 @@ int rc_state_zero(RcSlot& s, RcShoreline& v);
 int rc_state_zero(RcSlot& s, RcSurf& v);
 int rc_state_zero(RcSlot& s, RcMeanflow& v);
 int rc_state_zero(RcSlot& s, RcFlowcheck& v);
+int rc_state_zero(RcSlot& s, RcDrifters& v);
 
 // The tail of every open.  The caller has validated, selected the device and built `fresh` (rc: what its allocations
 // returned).  The state that is open is touched only once nothing can be refused any more: a refused open leaves it as it
