@@ -2494,6 +2494,119 @@ int rcflow_drifters_info(rc_ctx* ctx, int stream, rc_drifters_info* info);
 int rcflow_drifters_zones_dev(rc_ctx* ctx, int stream, const uint8_t* d_wet, size_t wet_step, const uint8_t* d_inside, size_t inside_step, int w,
                               int h, uint8_t* d_zone, size_t zone_step);
 
+/* ------------------------------------------------------------------ flow infill: holes of a checked field filled from a pyramid
+ * The flow check hands on a field with the rejected vectors replaced by NaN.  The mean flow, the opposing-flow map, the kinematics
+ * and the transects leave such a sample out; the Lagrangian products cannot: the flow map's particle stops for good at a rejected
+ * sample, a drifter dies BAD, the plan view resamples the NaN.  This is the "replace" that closes every PIV validation: the rejected
+ * vectors are interpolated from their valid neighbours, by pull-push over a pyramid of block sums, O(pixels) whatever the size of
+ * the holes, and a byte per pixel says how far the value was fetched from, so that nobody mistakes an interpolated vector for a
+ * measured one.  A vector the caller had an answer for is never changed.  The reference has no such product.
+ * tests/_infill_ref.py states the following in numpy and the kernels equal it bit for bit on every output of every push.  Every
+ * decision and every output value is an exact integer in 1/64 pixel; the only floats produced are (float)F / 64.0f with |F| <= 32000,
+ * which are exact, and the records' means, taken in double, each operation rounded on its own.
+ *
+ *  Inputs of a push.  d_flow_xy 32FC2 (pointer and step multiples of 8); NULL is the field the slot's frame loop left resident
+ *  (rcflow_stream_flow_ptr), with the rules of rcflow_meanflow_push_dev.  d_valid 8UC1 or NULL: what rcflow_flowcheck_push_dev
+ *  writes as d_mask.  d_domain 8UC1 or NULL: where a value is wanted, the shoreline's wet mask or a region of interest.
+ *  Sizes.  w_0 = w, h_0 = h, w_(l+1) = (w_l + 1) >> 1 and h likewise; a level may shrink to 1 x 1 and stay there.  L = levels.
+ *  1. Classes, per pixel (the mean flow's sample rule).  The pixel is BAD when a component is not finite or fabsf(component) >=
+ *     500.0f; otherwise q = (int)rintf(component * 64.0f) per component.  It is KNOWN iff it is not BAD and (d_valid is NULL or its
+ *     byte != 0).  With hold > 0 there is a state per pixel, a held q and an age byte, 255 (nothing held) after open and reset: a
+ *     KNOWN pixel stores (q, 0); a pixel that is not KNOWN with age < hold is HELD, its value the held q, and its age becomes
+ *     age + 1; any other pixel is a HOLE and its age becomes 255.  With hold = 0 a pixel is KNOWN or a HOLE.  The state does not look
+ *     at d_domain, nor at which outputs a push asks for.
+ *  2. Pull.  S_0 = (qx, qy, 1) at KNOWN and HELD pixels, (0, 0, 0) at holes.  S_(l+1)[Y, X] = the sum of S_l over rows 2Y, 2Y + 1
+ *     and columns 2X, 2X + 1 that lie inside level l, l = 0..L-1, in int32: |SX| <= 4^7 * 32000 < 2^30.
+ *  3. Push.  rdiv(a, b) = floor((2 a + b) / (2 b)), b > 0, the floor towards minus infinity.  A cell of level l >= 1 is OWN iff
+ *     N_l >= min_known; at level 0 OWN means KNOWN or HELD.  Level L: a cell has a value iff it is OWN; then F = (rdiv(SX, N),
+ *     rdiv(SY, N)) and lev = L.  Level l < L, from L - 1 down to 0: an OWN cell has F = its own mean (its q at level 0) and lev = l.
+ *     Any other cell (x, y) looks at four entries of level l + 1: X0 = x >> 1, X1 = clamp(X0 + (x & 1 ? 1 : -1), 0, w_(l+1) - 1),
+ *     Y0 and Y1 likewise; (Y0, X0), (Y0, X1), (Y1, X0), (Y1, X1) weigh 9, 3, 3, 1, each counted also where the clamp makes two of
+ *     them one cell.  A = the weights of the entries that have a value.  A = 0: the cell has none.  Otherwise F = rdiv(sum of
+ *     weight * F_entry, A) per component in int32 and lev = the largest lev among those entries: the coarsest level that
+ *     contributed.
+ *  4. Outputs, each may be NULL.  A pixel is WANTED iff d_domain is NULL or its byte != 0.  The pattern is both components
+ *     0x7fc00000 (RC_INFILL_LEAVE_NAN) or 0.0f (RC_INFILL_LEAVE_ZERO).  By the first class that holds:
+ *       KNOWN          d_source 0                       d_filled the input's bits, unchanged
+ *       not WANTED     RC_INFILL_OUTSIDE 254            the pattern
+ *       HELD           RC_INFILL_HELD 64                (float)q_held / 64.0f
+ *       has a value    lev, 1..7                        (float)F / 64.0f
+ *       else           RC_INFILL_UNFILLED 255           the pattern
+ *     d_mask 8UC1: 255 where d_source <= 64, else 0 (what rcflow_regions_push_dev takes).  d_picture 8UC3 in B, G, R: KNOWN (64, 64,
+ *     64), HELD (255, 255, 255), lev l entry l * 255 / 7 of rcflow_jet_lut, UNFILLED (255, 0, 255), OUTSIDE (0, 0, 0).
+ *  5. Cells are the opposing-flow map's grid.  RC_INFILL_SUMS = 8 int64 per cell, the counts by the source byte: KNOWN | HELD |
+ *     FILLED (1..7) | UNFILLED | OUTSIDE | the sum of Fx over the pixels with a value (source <= 64; q for KNOWN and HELD) | of Fy |
+ *     the sum of lev over FILLED.  Records, rc_infill_cell, closed by a last, small launch: known_pm = KNOWN * 1000 / pixels,
+ *     valued_pm = (KNOWN + HELD + FILLED) * 1000 / pixels, mean_x = (float)(((double)(sum of Fx) / 64.0) / (double)valued), mean_y
+ *     likewise, mean_level = (float)((double)(sum of lev) / (double)FILLED); each float is 0 when its denominator is 0, and
+ *     RC_INFILL_NONE is set when no pixel of the cell has a value.  Summary, RC_INFILL_SUMMARY = 16 int64: the five counts over the
+ *     picture | pushes since open / reset | 0 | 0 | the FILLED pixels by lev 0..7 (the first is always 0). */
+#define RC_INFILL_LEAVE_NAN 1            /* rc_infill_params::flags: exactly one of the two */
+#define RC_INFILL_LEAVE_ZERO 2
+#define RC_INFILL_HELD 64                /* d_source; 0 is KNOWN, 1..7 the level a value came from */
+#define RC_INFILL_OUTSIDE 254
+#define RC_INFILL_UNFILLED 255
+#define RC_INFILL_NONE 1                 /* rc_infill_cell::flags */
+#define RC_INFILL_MAX_LEVELS 7
+#define RC_INFILL_MAX_MIN_KNOWN 16384
+#define RC_INFILL_MAX_HOLD 254
+#define RC_INFILL_SUMS 8
+#define RC_INFILL_SUMMARY 16
+#define RC_INFILL_LAUNCHES 4             /* of a push with levels >= 5; one fewer below: "infill@1" has nothing to do */
+typedef struct rc_infill_params {
+    int levels;             /* L: 1..RC_INFILL_MAX_LEVELS */
+    int min_known;          /* 1..RC_INFILL_MAX_MIN_KNOWN: the KNOWN and HELD pixels a cell of level >= 1 needs to take its own mean */
+    int hold;               /* 0..RC_INFILL_MAX_HOLD pushes a pixel keeps its last KNOWN vector; fixed at open */
+    int grid_x, grid_y;     /* cells, as rcflow_ripmap_open */
+    int flags;              /* RC_INFILL_LEAVE_NAN or RC_INFILL_LEAVE_ZERO */
+    int pad[6];             /* zero */
+} rc_infill_params;         /* 48 bytes */
+typedef struct rc_infill_cell {
+    int flags;              /* RC_INFILL_NONE */
+    int pixels;
+    int known_pm;           /* KNOWN * 1000 / pixels */
+    int valued_pm;          /* (KNOWN + HELD + FILLED) * 1000 / pixels */
+    float mean_x, mean_y;   /* of the pixels with a value, pixels per frame */
+    float mean_level;       /* of the FILLED pixels */
+    int pad;
+} rc_infill_cell;           /* 32 bytes */
+typedef struct rc_infill_info {
+    int w, h;
+    rc_infill_params prm;              /* as rcflow_infill_set left them */
+    int launches_per_push;             /* RC_INFILL_LAUNCHES with levels >= 5, one fewer below */
+    int pad;
+    long long pushes;                  /* since open / reset */
+    size_t device_bytes;
+} rc_infill_info;
+/* Allocates everything the slot will ever need, for every value rcflow_infill_set may give.  Re-opening replaces the state; a
+ * refused open leaves the open state as it was.  RC_EINVAL without parameters, for a value outside the ranges above, flags that are
+ * not exactly one of the two, a pad word that is not zero, a grid that does not fit; RC_ESIZE beyond the context's max_w x max_h. */
+int rcflow_infill_open(rc_ctx* ctx, int stream, int w, int h, const rc_infill_params* prm);
+/* One field.  Images: d_valid, d_domain, d_source, d_mask 8UC1; d_flow_xy, d_filled 32FC2 (pointer and step multiples of 8);
+ * d_picture 8UC3; d_cells cells x rc_infill_cell (4-byte aligned), d_sums cells x RC_INFILL_SUMS int64 and d_summary
+ * RC_INFILL_SUMMARY int64 (8-byte aligned).  What a push gives and what it does to the held state do not depend on which outputs
+ * it asked for.  No host synchronisation, no device-to-host copy.  An output whose byte range overlaps an input's or another
+ * output's is RC_EINVAL, d_filled over the field too: filling in place is not part of this product.  Row padding is never written.
+ * Every refusal is decided before anything is queued and leaves state and outputs as they were; RC_ESTATE before
+ * rcflow_infill_open and with d_flow_xy NULL while no field is resident (RC_ESIZE when the resident field has another size).
+ * RC_EHIP (the runtime refused a launch) is no refusal: the state is undefined until rcflow_infill_reset. */
+int rcflow_infill_push_dev(rc_ctx* ctx, int stream, const float* d_flow_xy, size_t flow_step, const uint8_t* d_valid, size_t valid_step,
+                           const uint8_t* d_domain, size_t domain_step, float* d_filled, size_t filled_step, uint8_t* d_source,
+                           size_t source_step, uint8_t* d_mask, size_t mask_step, uint8_t* d_picture, size_t picture_step,
+                           rc_infill_cell* d_cells, long long* d_sums, long long* d_summary);
+/* Blocks until the slot's stream has finished; for hosts and tests.  Each may be NULL: the records, the cell sums and the summary
+ * of the last push (host memory), zeros before the first and after a reset. */
+int rcflow_infill_read(rc_ctx* ctx, int stream, rc_infill_cell* cells, long long* sums, long long summary[RC_INFILL_SUMMARY]);
+/* levels, min_known and flags from the next push on; RC_EINVAL as rcflow_infill_open.  hold is fixed at open */
+int rcflow_infill_set(rc_ctx* ctx, int stream, int levels, int min_known, int flags);
+/* forgets the held state and zeroes the records, the sums, the summary and the push count; keeps the allocation and the parameters
+ * as rcflow_infill_set left them; asynchronous, on the slot's stream */
+int rcflow_infill_reset(rc_ctx* ctx, int stream);
+/* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
+int rcflow_infill_close(rc_ctx* ctx, int stream);
+/* never blocks; RC_ESTATE when nothing is open, RC_EINVAL without a buffer */
+int rcflow_infill_info(rc_ctx* ctx, int stream, rc_infill_info* info);
+
 /* Display path, ripcurrents.cpp:233-273 (= streamline_displacement / _total_motion / _ratio /
  * _positions, ripcurrents_module.cpp:13-60) on the slot's streamline field (rcflow_advect_field_dev):
  * which 0 = |pt|, 1 = dist, 2 = |pt| / dist; minMaxLoc + convertTo(CV_8UC1, 255/max) +

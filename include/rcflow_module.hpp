@@ -1600,4 +1600,66 @@ class Drifters {
     DeviceImage d_flow_, d_zone_, d_now_, d_density_, d_live_, d_picture_;
 };
 
+// the pictures of an Infill::push, each optional: filled 32FC2, source and mask 8UC1, picture 8UC3
+struct InfillPictures { Mat* filled = nullptr; Mat* source = nullptr; Mat* mask = nullptr; Mat* picture = nullptr; };
+
+// Flow infill on the device (rcflow_infill_*): the holes of a checked flow field filled from a pyramid of block sums.  Host flow
+// fields (32FC2), valid masks and domains (8UC1) of the pipeline's size in; the filled field, a byte per pixel that says where the
+// value came from, the mask of the pixels with a value and a picture out, and a record per cell of a grid.
+class Infill {
+  public:
+    using Pictures = InfillPictures;
+
+    Infill(Pipeline& pipe, const rc_infill_params& prm) : pipe_(pipe), cells_(prm.grid_x * prm.grid_y) {
+        check(rcflow_infill_open(pipe.context(), 0, pipe.width(), pipe.height(), &prm));
+    }
+    ~Infill() { (void)rcflow_infill_close(pipe_.context(), 0); }
+    Infill(const Infill&) = delete;
+    Infill& operator=(const Infill&) = delete;
+
+    // flow: 32FC2; valid: 8UC1 (what FlowCheck writes as mask), or null: every finite vector is valid; domain: 8UC1, or null: a
+    // value is wanted everywhere.  The records, the sums and the summary stay on the session after every push, for read(), cells()
+    // and sums().
+    void push(const Mat& flow, const Mat* valid = nullptr, const Mat* domain = nullptr, const Pictures& out = Pictures()) {
+        const int w = pipe_.width(), h = pipe_.height();
+        if (!is_image(flow, w, h, 2, 4)) throw Error(RC_EINVAL, "Infill::push: the field must be 32FC2 of the pipeline's size");
+        if ((valid && !is_image(*valid, w, h, 1, 1)) || (domain && !is_image(*domain, w, h, 1, 1)))
+            throw Error(RC_EINVAL, "Infill::push: valid and domain must be 8UC1 of the pipeline's size");
+        if ((out.filled && !is_image(*out.filled, w, h, 2, 4)) || (out.source && !is_image(*out.source, w, h, 1, 1)) ||
+            (out.mask && !is_image(*out.mask, w, h, 1, 1)) || (out.picture && !is_image(*out.picture, w, h, 3, 1)))
+            throw Error(RC_EINVAL, "Infill::push: filled 32FC2, source and mask 8UC1, picture 8UC3, each of the pipeline's size");
+        staged(pipe_.context(), {{d_flow_, &flow}, {d_valid_, valid}, {d_domain_, domain}}, [&] {
+            return rcflow_infill_push_dev(pipe_.context(), 0, d_flow_.ptr<const float>(), d_flow_.pitch(), d_valid_.ptr<const uint8_t>(valid), d_valid_.pitch(),
+                                          d_domain_.ptr<const uint8_t>(domain), d_domain_.pitch(), d_filled_.ptr<float>(out.filled), d_filled_.pitch(),
+                                          d_source_.ptr<uint8_t>(out.source), d_source_.pitch(), d_mask_.ptr<uint8_t>(out.mask), d_mask_.pitch(),
+                                          d_picture_.ptr<uint8_t>(out.picture), d_picture_.pitch(), nullptr, nullptr, nullptr);
+        }, {{d_filled_, out.filled}, {d_source_, out.source}, {d_mask_, out.mask}, {d_picture_, out.picture}});
+    }
+    // each waits for the pipeline's stream (include/rcflow.h).  The summary: the pixels that are KNOWN, HELD, FILLED, UNFILLED,
+    // OUTSIDE, the pushes, 0, 0, the FILLED pixels by lev 0..7
+    std::vector<long long> read() {
+        std::vector<long long> s(RC_INFILL_SUMMARY);
+        check(rcflow_infill_read(pipe_.context(), 0, nullptr, nullptr, s.data()));
+        return s;
+    }
+    std::vector<rc_infill_cell> cells() {
+        std::vector<rc_infill_cell> r((size_t)cells_);
+        check(rcflow_infill_read(pipe_.context(), 0, r.data(), nullptr, nullptr));
+        return r;
+    }
+    std::vector<long long> sums() {
+        std::vector<long long> s((size_t)cells_ * RC_INFILL_SUMS);
+        check(rcflow_infill_read(pipe_.context(), 0, nullptr, s.data(), nullptr));
+        return s;
+    }
+    void set(int levels, int min_known, int flags) { check(rcflow_infill_set(pipe_.context(), 0, levels, min_known, flags)); }
+    rc_infill_info info() { rc_infill_info i; check(rcflow_infill_info(pipe_.context(), 0, &i)); return i; }
+    void reset() { check(rcflow_infill_reset(pipe_.context(), 0)); }
+
+  private:
+    Pipeline& pipe_;
+    int cells_ = 0;
+    DeviceImage d_flow_, d_valid_, d_domain_, d_filled_, d_source_, d_mask_, d_picture_;
+};
+
 }  // namespace rc

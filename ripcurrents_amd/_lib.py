@@ -84,6 +84,9 @@ RC_FLOWCHECK_MAX_RADIUS, RC_FLOWCHECK_SUMS, RC_FLOWCHECK_SUMMARY, RC_FLOWCHECK_L
 # rcflow_drifters_*: the bounds, the words of a cell's sums and of the summary, the launches of a push, the flags, the fates
 RC_DRIFTERS_MAX, RC_DRIFTERS_SUMS, RC_DRIFTERS_HIST_BINS, RC_DRIFTERS_SUMMARY, RC_DRIFTERS_LAUNCHES = 1 << 22, 8, 32, 24, 2
 RC_DRIFTERS_RESPAWN, RC_DRIFTERS_EMPTY = 1, 1
+# rcflow_infill_*: the flags, the source bytes, the record's flag, the bounds, the words of a cell's sums and of the summary, the most launches of a push
+RC_INFILL_LEAVE_NAN, RC_INFILL_LEAVE_ZERO, RC_INFILL_HELD, RC_INFILL_OUTSIDE, RC_INFILL_UNFILLED, RC_INFILL_NONE = 1, 2, 64, 254, 255, 1
+RC_INFILL_MAX_LEVELS, RC_INFILL_MAX_MIN_KNOWN, RC_INFILL_MAX_HOLD, RC_INFILL_SUMS, RC_INFILL_SUMMARY, RC_INFILL_LAUNCHES = 7, 16384, 254, 8, 16, 4
 DRIFTERS_FATES = {"edge_left": 1, "edge_top": 2, "edge_right": 3, "edge_bottom": 4, "bad": 5, "aged": 6, "shore": 9, "offshore": 10}
 
 ERRORS = {-1: "RC_EINVAL", -2: "RC_ENOMEM", -3: "RC_EHIP", -4: "RC_ENODEV", -5: "RC_ESIZE",
@@ -352,6 +355,24 @@ class FlowcheckInfo(C.Structure):
     """rc_flowcheck_info (include/rcflow.h)."""
     _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", FlowcheckParams), ("launches_per_push", C.c_int), ("held", C.c_int),
                 ("pushes", C.c_longlong), ("computing", C.c_longlong), ("device_bytes", C.c_size_t)]
+
+
+class InfillParams(C.Structure):
+    """rc_infill_params (include/rcflow.h), 48 bytes."""
+    _fields_ = [("levels", C.c_int), ("min_known", C.c_int), ("hold", C.c_int), ("grid_x", C.c_int), ("grid_y", C.c_int), ("flags", C.c_int),
+                ("pad", C.c_int * 6)]
+
+
+class InfillCell(C.Structure):
+    """rc_infill_cell (include/rcflow.h), 32 bytes; numpy: api.INFILL_CELL_DTYPE."""
+    _fields_ = [("flags", C.c_int), ("pixels", C.c_int), ("known_pm", C.c_int), ("valued_pm", C.c_int), ("mean_x", C.c_float), ("mean_y", C.c_float),
+                ("mean_level", C.c_float), ("pad", C.c_int)]
+
+
+class InfillInfo(C.Structure):
+    """rc_infill_info (include/rcflow.h)."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", InfillParams), ("launches_per_push", C.c_int), ("pad", C.c_int),
+                ("pushes", C.c_longlong), ("device_bytes", C.c_size_t)]
 
 
 class DriftersParams(C.Structure):
@@ -627,6 +648,13 @@ SIGNATURES = {
     "rcflow_drifters_close": [_vp, _i],
     "rcflow_drifters_info": [_vp, _i, C.POINTER(DriftersInfo)],
     "rcflow_drifters_zones_dev": [_vp, _i, _vp, _sz, _vp, _sz, _i, _i, _vp, _sz],
+    "rcflow_infill_open": [_vp, _i, _i, _i, C.POINTER(InfillParams)],
+    "rcflow_infill_push_dev": [_vp, _i] + [_vp, _sz] * 7 + [_vp, _vp, _vp],
+    "rcflow_infill_read": [_vp, _i, _vp, _vp, C.POINTER(C.c_longlong)],
+    "rcflow_infill_set": [_vp, _i, _i, _i, _i],
+    "rcflow_infill_reset": [_vp, _i],
+    "rcflow_infill_close": [_vp, _i],
+    "rcflow_infill_info": [_vp, _i, C.POINTER(InfillInfo)],
     "rcflow_comm_unique_id": [_vp],
     "rcflow_comm_init": [_vp, _vp, _i, _i],
     "rcflow_comm_destroy": [_vp],

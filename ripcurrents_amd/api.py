@@ -45,9 +45,10 @@ from ._lib import RC_SURF_MAX_CHANNELS, SurfInfo, SurfParams
 from ._lib import RC_MEANFLOW_DIR_FIXED, RC_MEANFLOW_DIR_OPPOSED, RC_MEANFLOW_SUMS, MeanflowInfo, MeanflowParams
 from ._lib import RC_FLOWCHECK_FILL_NAN, RC_FLOWCHECK_FILL_ZERO, RC_FLOWCHECK_SUMMARY, RC_FLOWCHECK_SUMS, RC_FLOWCHECK_TESTS, FlowcheckInfo, FlowcheckParams
 from ._lib import RC_DRIFTERS_HIST_BINS, RC_DRIFTERS_RESPAWN, RC_DRIFTERS_SUMMARY, RC_DRIFTERS_SUMS, DriftersInfo, DriftersParams
+from ._lib import RC_INFILL_LEAVE_NAN, RC_INFILL_LEAVE_ZERO, RC_INFILL_SUMMARY, RC_INFILL_SUMS, InfillInfo, InfillParams
 
 __all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState", "Waves", "Piv", "Transects", "Kinematics",
-           "Shoreline", "Surf", "MeanFlow", "FlowCheck", "Drifters"]
+           "Shoreline", "Surf", "MeanFlow", "FlowCheck", "Drifters", "Infill"]
 
 
 # rc_draw_prim as a numpy record (32 bytes): what Context.draw takes and Context.tracers_prims returns
@@ -137,6 +138,12 @@ DRIFTERS_PLACE = ("visits", "su", "sv", "shore", "offshore", "edge", "other", "a
 DRIFTERS_ORIGIN = ("released", "shore", "offshore", "edge", "other", "age_shore", "age_offshore", "zero")
 DRIFTERS_CELL_DTYPE = np.dtype([("flags", "<i4"), ("pad0", "<i4"), ("mean_u", "<f4"), ("mean_v", "<f4"), ("escape", "<f4"), ("beached", "<f4"),
                                 ("mean_exit_age", "<f4"), ("pad1", "<i4")])
+# the 16 words of an infill summary and the eight of a cell's sums, in order; the source bytes by name; rc_infill_cell (32 bytes)
+INFILL_SUMMARY = ("known", "held", "filled", "unfilled", "outside", "pushes", "zero6", "zero7") + tuple("lev%d" % k for k in range(8))
+INFILL_SUMS = ("known", "held", "filled", "unfilled", "outside", "sum_fx", "sum_fy", "sum_lev")
+INFILL_SOURCES = {"known": 0, "held": 64, "outside": 254, "unfilled": 255}
+INFILL_CELL_DTYPE = np.dtype([("flags", "<i4"), ("pixels", "<i4"), ("known_pm", "<i4"), ("valued_pm", "<i4"), ("mean_x", "<f4"), ("mean_y", "<f4"),
+                              ("mean_level", "<f4"), ("pad", "<i4")])
 RIPMAP_SOURCE_NAMES = {v: k for k, v in RIPMAP_SOURCES.items()}
 TRACERS_MOVER_NAMES = {v: k for k, v in TRACERS_MOVERS.items()}
 SHORE_SOURCE_NAMES = {v: k for k, v in SHORE_SOURCES.items()}
@@ -2236,6 +2243,71 @@ class Context:
         check(self._lib.rcflow_drifters_zones_dev(self._h, stream, *ins, w, h, self._ptr(out), out.stride(0)))
         return out
 
+    # ------------------------------------------------------------------ flow infill
+    def infill_open(self, w, h, levels=7, min_known=1, hold=0, grid_x=30, grid_y=30, leave="nan", stream=0):
+        """Opens the slot's flow infill on w x h fields (include/rcflow.h, "flow infill"): the vectors that are not finite or that
+        the valid mask rejects are replaced by a mix of their valid neighbours, taken from a pyramid of `levels` levels of block
+        sums; a cell of the pyramid with at least min_known known pixels takes its own mean.  hold: the pushes a pixel keeps its
+        last known vector before it counts as a hole.  leave: what a pixel without a value gets, "nan" or "zero"."""
+        if leave not in ("nan", "zero"):
+            raise ValueError("leave is 'nan' or 'zero'")
+        p = InfillParams(levels=int(levels), min_known=int(min_known), hold=int(hold), grid_x=int(grid_x), grid_y=int(grid_y),
+                         flags=RC_INFILL_LEAVE_NAN if leave == "nan" else RC_INFILL_LEAVE_ZERO)
+        self._bind(stream)          # the state is zeroed on the slot's stream: the one the pushes will run on
+        check(self._lib.rcflow_infill_open(self._h, stream, int(w), int(h), C.byref(p)))
+
+    def infill_info(self, stream=0):
+        """dict(w, h, the parameters, leave, launches_per_push, pushes, device_bytes); never blocks."""
+        i = self._info("infill", InfillInfo(), stream)
+        d = _record(i, skip=("flags", "pad"))
+        d["leave"] = "nan" if i.prm.flags == RC_INFILL_LEAVE_NAN else "zero"
+        return d
+
+    def infill_push(self, flow=None, valid=None, domain=None, filled=None, source=None, mask=None, picture=None, cells=None, sums=None,
+                    summary=None, stream=0):
+        """One field (HxWx2 float32 device tensor, dense pixels, rows may be padded; None: the field push_frame_host /
+        frame_loop_step left on the slot), the mask of its valid vectors (HxW uint8, what flowcheck_push writes as mask; None: every
+        finite vector is valid) and the domain a value is wanted in (HxW uint8; None: everywhere).  Nothing is synchronised.
+        Outputs are preallocated device tensors, each optional: filled HxWx2 float32 (what ftle_push, drifters_push and
+        planview_push take), source HxW uint8 (0 known, 1..7 the level a value came from, INFILL_SOURCES), mask HxW uint8 (255
+        where the pixel has a value, what regions_push takes), picture HxWx3 uint8, cells GYxGXx32 uint8 (rc_infill_cell records;
+        view the host copy as INFILL_CELL_DTYPE), sums GYxGXx8 int64 (INFILL_SUMS), summary 16 int64 (INFILL_SUMMARY).  Records,
+        sums and summary also stay on the slot for infill_read."""
+        i = self._info("infill", InfillInfo(), stream)
+        h, w, nc = i.h, i.w, i.prm.grid_x * i.prm.grid_y
+        ins = (self._in_image(flow, torch.float32, "flow", (h, w, 2), optional=True) + self._in_image(valid, torch.uint8, "valid", (h, w), optional=True) +
+               self._in_image(domain, torch.uint8, "domain", (h, w), optional=True))
+        images = (self._out_image(filled, torch.float32, "filled", (h, w, 2)) + self._out_image(source, torch.uint8, "source", (h, w)) +
+                  self._out_image(mask, torch.uint8, "mask", (h, w)) + self._out_image(picture, torch.uint8, "picture", (h, w, 3)))
+        cp = self._out_array(cells, torch.uint8, "cells", nc * 32)
+        sp = self._out_array(sums, torch.int64, "sums", nc * RC_INFILL_SUMS)
+        up = self._out_array(summary, torch.int64, "summary", RC_INFILL_SUMMARY)
+        self._bind(stream)
+        check(self._lib.rcflow_infill_push_dev(self._h, stream, *ins, *images, cp, sp, up))
+
+    def infill_read(self, stream=0):
+        """Waits for the slot's stream -> (cells GYxGX INFILL_CELL_DTYPE, sums GYxGXx8 int64, dict of the summary by
+        INFILL_SUMMARY names) of the last push; zeros before the first and after a reset."""
+        info = self.infill_info(stream)
+        gx, gy = info["grid_x"], info["grid_y"]
+        cells, sums = np.zeros((gy, gx), INFILL_CELL_DTYPE), np.zeros((gy, gx, RC_INFILL_SUMS), np.int64)
+        summ = np.zeros(RC_INFILL_SUMMARY, np.int64)
+        self._bind(stream)
+        check(self._lib.rcflow_infill_read(self._h, stream, cells.ctypes.data, sums.ctypes.data, summ.ctypes.data_as(C.POINTER(C.c_longlong))))
+        return cells, sums, dict(zip(INFILL_SUMMARY, (int(v) for v in summ)))
+
+    def infill_set(self, levels, min_known, leave, stream=0):
+        """levels, min_known and leave ("nan" or "zero") from the next push on."""
+        if leave not in ("nan", "zero"):
+            raise ValueError("leave is 'nan' or 'zero'")
+        check(self._lib.rcflow_infill_set(self._h, stream, int(levels), int(min_known), RC_INFILL_LEAVE_NAN if leave == "nan" else RC_INFILL_LEAVE_ZERO))
+
+    def infill_reset(self, stream=0):
+        self._lifecycle("infill", "reset", stream)
+
+    def infill_close(self, stream=0):
+        self._lifecycle("infill", "close", stream)
+
     # ------------------------------------------------------------------ rip regions
     def regions_open(self, w, h, connectivity=8, min_area=1, max_regions=1024, stream=0):
         """Opens the slot's region labelling for w x h masks: connected components (4 or 8 neighbours) numbered in raster
@@ -2639,6 +2711,18 @@ class Drifters(_Product):
 
     def set(self, dt, max_age, density_full, live_min, respawn):
         self.ctx.drifters_set(dt, max_age, density_full, live_min, respawn, self.stream)
+
+
+class Infill(_Product):
+    """The flow infill of one slot as an object: Context.infill_* with the context and the slot bound.  Opens on construction
+    (the parameters of Context.infill_open as keywords), closes on close() or at the end of a with block."""
+    product = "infill"
+
+    def push(self, flow=None, valid=None, domain=None, **outputs):
+        self.ctx.infill_push(flow, valid, domain, stream=self.stream, **outputs)
+
+    def set(self, levels, min_known, leave):
+        self.ctx.infill_set(levels, min_known, leave, self.stream)
 
 
 def kinematics_taps(radius, sigma):

@@ -392,6 +392,21 @@ struct RcDrifters {
     RcZeroFence zf;
 };
 
+// Flow infill of one stream slot (infill_kernels.hip).  Everything is allocated by rcflow_infill_open, for every value
+// rcflow_infill_set may give, and released by rcflow_infill_close / rcflow_destroy.
+struct RcInfill {
+    bool open = false;
+    int w = 0, h = 0;
+    rc_infill_params prm{};         // levels, min_known and flags: as rcflow_infill_set left them
+    long long pushes = 0;           // since open / reset
+    RcBuf q;                        // [h][w] uint32, qx | qy << 16: the value of a KNOWN or HELD pixel; with hold > 0 the held state
+    RcBuf age;                      // [h][w] uint8, age + 1 modulo 256: 0 nothing held (a HOLE), 1 KNOWN, 2..255 HELD; the class plane of a push
+    RcBuf lev;                      // S_1..S_7, int4 (SX, SY, N, 0) a cell | V_5..V_7, int2 (Fx | Fy << 16, lev or -1) a cell
+    RcBuf acc;                      // [cells][RC_INFILL_SUMS] int64 the launch adds into | 8 int64 by lev, zero between pushes
+    RcBuf out;                      // the last push: summary 16 int64 | sums [cells][RC_INFILL_SUMS] int64 | records [cells]
+    RcZeroFence zf;
+};
+
 // warp_kernels.hip: one launch of the affine / perspective warp
 struct RcWarpArgs {
     const uint8_t* src; size_t step;
@@ -479,6 +494,7 @@ struct RcSlot {
     RcMeanflow mf;
     RcFlowcheck fc;
     RcDrifters dr;
+    RcInfill inf;
     RcPhaseCorr pc;
 };
 
@@ -589,7 +605,8 @@ struct rc_ctx {
     X(RC_K_SURF, "surf", RC_B_OVERLAY) /* @0 ring, sums, flags, pictures and counts, @1 lines, @2 reference, channels, records and summary, @3 primitives */ \
     X(RC_K_MEANFLOW, "meanflow", RC_B_FARNEBACK) /* @0 ring, sums, mean, steadiness, spread, picture, cell sums and G, @1 mask, records and summary */ \
     X(RC_K_FLOWCHECK, "flowcheck", RC_B_FARNEBACK) /* @0 staging, gather, box sums, the tests, every output and cell sums, @1 records and summary */ \
-    X(RC_K_DRIFTERS, "drifters", RC_B_STREAM) /* @0 release, gather, fates and the scattered adds, @1 density, pictures, records and summary, @2 the zones helper */
+    X(RC_K_DRIFTERS, "drifters", RC_B_STREAM) /* @0 release, gather, fates and the scattered adds, @1 density, pictures, records and summary, @2 the zones helper */ \
+    X(RC_K_INFILL, "infill", RC_B_FARNEBACK) /* @0 classes, held state and the pull to level 4, @1 the pull above and the push down to level 5, @2 the push to the pixels, every output and cell sums, @3 records and summary */
 #define RC_ROW_ID(id, ...) id,
 enum { RC_BUCKET_TABLE(RC_ROW_ID) RC_B_BUCKETS };
 enum { RC_KIND_TABLE(RC_ROW_ID) RC_K_KINDS };
@@ -677,7 +694,7 @@ struct RcProfScope {
     } while (0)
 
 // ---------------------------------------------------------------------------- per-slot products
-// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView, RcWaves, RcPiv, RcTransects, RcKinematics, RcShoreline, RcSurf, RcMeanflow, RcFlowcheck and RcDrifters share one lifecycle.  A product supplies
+// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView, RcWaves, RcPiv, RcTransects, RcKinematics, RcShoreline, RcSurf, RcMeanflow, RcFlowcheck, RcDrifters and RcInfill share one lifecycle.  A product supplies
 //   void rc_state_free(T&)             frees every buffer and the fence; the state is T() again
 //   int rc_state_zero(RcSlot&, T&)     rc_fence_zero of what open / reset clear, and the counters
 // and open / reset / close are written once, here.
@@ -699,6 +716,7 @@ void rc_state_free(RcSurf& v);
 void rc_state_free(RcMeanflow& v);
 void rc_state_free(RcFlowcheck& v);
 void rc_state_free(RcDrifters& v);
+void rc_state_free(RcInfill& v);
 int rc_state_zero(RcSlot& s, RcTimex& t);
 int rc_state_zero(RcSlot& s, RcFrameStab& f);
 int rc_state_zero(RcSlot& s, RcRipMap& m);
@@ -717,6 +735,7 @@ int rc_state_zero(RcSlot& s, RcSurf& v);
 int rc_state_zero(RcSlot& s, RcMeanflow& v);
 int rc_state_zero(RcSlot& s, RcFlowcheck& v);
 int rc_state_zero(RcSlot& s, RcDrifters& v);
+int rc_state_zero(RcSlot& s, RcInfill& v);
 
 // The tail of every open.  The caller has validated, selected the device and built `fresh` (rc: what its allocations
 // returned).  The state that is open is touched only once nothing can be refused any more: a refused open leaves it as it
