@@ -2607,6 +2607,154 @@ int rcflow_infill_close(rc_ctx* ctx, int stream);
 /* never blocks; RC_ESTATE when nothing is open, RC_EINVAL without a buffer */
 int rcflow_infill_info(rc_ctx* ctx, int stream, rc_infill_info* info);
 
+/* ------------------------------------------------------------------ offshore frame: exact distance to shore, cross / along flow
+ * The shoreline gives a wet mask, the flow products give a field; this joins them.  For every pixel the exact Euclidean distance to
+ * the shore and the shore point it is nearest to (the map, made when the shore has moved), and per push the field projected on the
+ * local shore normal: how fast the water runs away from the shore, how far out, and at which place along the beach, also on a curved
+ * beach or behind a headland, where one direction for the whole picture is wrong.  The reference has no such product.
+ * tests/_offshore_ref.py states the following in numpy and the kernels equal it bit for bit on every output of every call.  Every
+ * decision and every stored value is an exact integer; the only floats produced are (float)v / 64.0f with |v| < 2^24, which are
+ * exact, and the records' means, taken in double, each operation rounded on its own.
+ *
+ *  1. The map (rcflow_offshore_map_dev).  d_wet 8UC1, non-zero is water: what rcflow_shoreline_push_dev writes as its wet mask.  A
+ *     pixel's class is wet or dry.  For a pixel p = (x, y) the candidates are the pixels of the OTHER class; d2(p) = the least
+ *     (x - x')^2 + (y - y')^2 over them, int32; near(p) = the raster index y' * w + x' of the candidate that attains it, the smallest
+ *     index when several do.  With no pixel of the other class in the picture d2 = RC_OFFSHORE_FAR and near = -1.  Exact and
+ *     uncapped: no chamfer, no search radius.  r = floor(sqrt(4096 * d2)) taken exactly in int64: the distance in 1/64 pixel.  Both
+ *     planes stay in the slot's state until the next map or a reset.  Outputs, each may be NULL:
+ *       d_dist2 32SC1    d2, negated on dry pixels; FAR stays +-0x7fffffff
+ *       d_near 32SC1     near
+ *       d_sdist 32SC1    r, negated on dry pixels; FAR stays +-0x7fffffff
+ *       d_picture 8UC3   B, G, R by the first rule that holds: FAR (0, 0, 0); dry (64, 64, 64); wet entry
+ *                        min(r / 64, max_dist) * 255 / max_dist of rcflow_jet_lut, in integers, max_dist as it stands at the call
+ *     Map summary, RC_OFFSHORE_SUMMARY = 8 int64: wet pixels | dry pixels | wet pixels that are not FAR | the largest d2 over those |
+ *     the sum of d2 over those | the sum of d2 over the dry pixels that are not FAR | 0 | maps since open / reset.
+ *  2. The push (rcflow_offshore_push_dev), one flow field on the slot's map.  Each pixel takes the first class that holds:
+ *       RC_OFFSHORE_C_DRY 3    the pixel is dry
+ *       RC_OFFSHORE_C_FAR 2    d2 is FAR or d2 > max_dist^2
+ *       RC_OFFSHORE_C_NEAR 1   d2 < min_dist^2
+ *       RC_OFFSHORE_C_BAD 4    the mean current's sample rule: a component is not finite or fabsf(component) >= 500.0f
+ *       RC_OFFSHORE_C_OK 0     otherwise
+ *     At an OK pixel q = (int)rintf(component * 64.0f) per component and n = (x - near % w, y - near / w): the vector from the
+ *     nearest shore point to the pixel, |n|^2 = d2.  C = qx nx + qy ny and A = -qx ny + qy nx fit int32 because max_dist <= 4095.
+ *     rdiv(a, b) = floor((2 a + b) / (2 b)), b > 0, the floor towards minus infinity, in int64.  cross = rdiv(64 C, r) and along =
+ *     rdiv(64 A, r), in 1/64 pixel per field.  Positive cross is away from the shore.  Along is the component on the normal turned
+ *     by a quarter from +x towards +y: with the land at the top of the picture (n = (0, 1)) positive along runs towards -x.
+ *     Outputs, each may be NULL:
+ *       d_cross_along 32FC2   ((float)cross / 64.0f, (float)along / 64.0f); 0x7fc00000 in both components at every pixel not OK
+ *       d_class 8UC1          the class
+ *       d_mask 8UC1           255 where the pixel is OK and cross >= cmin_q, cmin_q = (int)ceil((double)cross_min * 64.0) taken on
+ *                             the host; 0 elsewhere.  What rcflow_regions_push_dev takes
+ *       d_picture 8UC3        OK: with S = max(4 cmin_q, 1), c = clamp(cross, -S, S) and m = |c| * 255 / S in integers, B, G, R =
+ *                             (255 - m, 255 - m, 255) for c >= 0 (white to red: seaward) and (255, 255 - m, 255 - m) for c < 0
+ *                             (white to blue: shoreward); DRY (64, 64, 64), FAR (0, 0, 0), NEAR (128, 128, 128), BAD (255, 0, 255)
+ *  3. The table, stations x bins cells of RC_OFFSHORE_SUMS = 4 int64, station-major: count | sum of cross | sum of along | mask
+ *     pixels.  An OK pixel's bin is r / (64 * bin_width); its station x * stations / w with RC_OFFSHORE_STATION_X, y * stations / h
+ *     with RC_OFFSHORE_STATION_Y (the nearest point's own coordinate was tried as the station and dropped: on a cuspate shore the
+ *     few protruding points collect every far pixel).  An OK pixel whose bin is >= bins is counted per station as "beyond" and
+ *     enters no cell.
+ *  4. Records, rc_offshore_station, one per station, closed by a last, small launch.  first = the lowest bin with count >=
+ *     min_count; when there is none RC_OFFSHORE_EMPTY is set and every number but `beyond` is 0.  From first outwards a bin PASSES
+ *     when count >= min_count and sum of cross >= cmin_q * count.  reach_end = one past the last bin of the unbroken run of passing
+ *     bins that starts at first, 0 when first itself fails.  peak_bin = the passing bin (inside the run or beyond a break) with the
+ *     largest rdiv(sum of cross, count), the lowest such bin, -1 when no bin passes; peak_cross is that value.  count, mean_cross
+ *     = (float)(((double)(sum of cross over the run) / 64.0) / (double)(count over the run)) and mean_along likewise are of the run's
+ *     bins, 0 with an empty run.  RC_OFFSHORE_RIP is set when reach_end - first >= rip_bins.
+ *     Push summary, 8 int64: the pixels by class 0..4 (OK, NEAR, FAR, DRY, BAD) | mask pixels | stations flagged RIP | pushes since
+ *     open / reset.
+ *  5. The band (rcflow_offshore_band_dev), one launch on the slot's map: 255 where the pixel is wet, not FAR and
+ *     (int)ceil((double)lo * 64.0) <= r < (int)ceil((double)hi * 64.0), 0 elsewhere.  The "inside" mask of
+ *     rcflow_drifters_zones_dev, a d_domain for rcflow_infill_push_dev. */
+#define RC_OFFSHORE_FAR 0x7fffffff       /* d2 and r where the picture has no pixel of the other class */
+#define RC_OFFSHORE_STATION_X 1          /* rc_offshore_params::flags: exactly one of the two */
+#define RC_OFFSHORE_STATION_Y 2
+#define RC_OFFSHORE_C_OK 0               /* d_class */
+#define RC_OFFSHORE_C_NEAR 1
+#define RC_OFFSHORE_C_FAR 2
+#define RC_OFFSHORE_C_DRY 3
+#define RC_OFFSHORE_C_BAD 4
+#define RC_OFFSHORE_EMPTY 1              /* rc_offshore_station::flags */
+#define RC_OFFSHORE_RIP 2
+#define RC_OFFSHORE_MAX_DIST 4095
+#define RC_OFFSHORE_MAX_STATIONS 256
+#define RC_OFFSHORE_MAX_BINS 256
+#define RC_OFFSHORE_MAX_BIN_WIDTH 256
+#define RC_OFFSHORE_MAX_SIDE 32767       /* of the picture: d2 and the raster index are int32 */
+#define RC_OFFSHORE_SUMS 4
+#define RC_OFFSHORE_SUMMARY 8
+#define RC_OFFSHORE_MAP_LAUNCHES 3
+#define RC_OFFSHORE_PUSH_LAUNCHES 2
+typedef struct rc_offshore_params {
+    int min_dist;           /* 0..max_dist, pixels: nearer pixels are NEAR (swash, the waterline's own error) */
+    int max_dist;           /* 1..RC_OFFSHORE_MAX_DIST, pixels: farther pixels are FAR */
+    int stations;           /* 1..RC_OFFSHORE_MAX_STATIONS along the beach; fixed at open */
+    int bins;               /* 1..RC_OFFSHORE_MAX_BINS of distance; fixed at open */
+    int bin_width;          /* 1..RC_OFFSHORE_MAX_BIN_WIDTH pixels */
+    int min_count;          /* >= 1: the OK pixels a bin needs to count */
+    int rip_bins;           /* 1..bins: the passing bins in a row that make a station a rip */
+    float cross_min;        /* finite, 0..400 pixels per field: the mean cross flow a bin needs to pass, the cross flow of the mask */
+    int flags;              /* RC_OFFSHORE_STATION_X or RC_OFFSHORE_STATION_Y */
+    int pad[3];             /* zero */
+} rc_offshore_params;       /* 48 bytes */
+typedef struct rc_offshore_station {
+    int flags;              /* RC_OFFSHORE_EMPTY, RC_OFFSHORE_RIP */
+    int first;              /* the lowest bin with count >= min_count */
+    int reach_end;          /* one past the run of passing bins from first; reach_end * bin_width pixels is the rip's reach */
+    int peak_bin;           /* -1: no bin passes */
+    int peak_cross;         /* rdiv(sum of cross, count) of peak_bin, 1/64 pixel per field */
+    int count;              /* OK pixels of the run's bins */
+    int beyond;             /* OK pixels of the station past the last bin */
+    int pad0;
+    float mean_cross, mean_along;   /* of the run, pixels per field */
+    int pad1[2];
+} rc_offshore_station;      /* 48 bytes */
+typedef struct rc_offshore_info {
+    int w, h;
+    rc_offshore_params prm;            /* as rcflow_offshore_set left them */
+    int launches_per_map;              /* RC_OFFSHORE_MAP_LAUNCHES */
+    int launches_per_push;             /* RC_OFFSHORE_PUSH_LAUNCHES */
+    int have_map;                      /* 1 after a map, 0 after open and reset */
+    int pad;
+    long long maps, pushes;            /* since open / reset */
+    size_t device_bytes;
+} rc_offshore_info;
+/* Allocates everything the slot will ever need, for every value rcflow_offshore_set may give.  Re-opening replaces the state; a
+ * refused open leaves the open state as it was.  RC_EINVAL without parameters, for a value outside the ranges above, flags that are
+ * not exactly one of the two, a pad word that is not zero; RC_ESIZE beyond the context's max_w x max_h or RC_OFFSHORE_MAX_SIDE. */
+int rcflow_offshore_open(rc_ctx* ctx, int stream, int w, int h, const rc_offshore_params* prm);
+/* Called when the shore has moved, not every push: RC_OFFSHORE_MAP_LAUNCHES launches.  d_wet 8UC1; d_dist2, d_near, d_sdist 32SC1
+ * (pointer and step multiples of 4); d_picture 8UC3; d_summary RC_OFFSHORE_SUMMARY int64 (8-byte aligned).  What a call gives does
+ * not depend on which outputs it asked for.  No host synchronisation, no device-to-host copy.  An output whose byte range overlaps
+ * the input's or another output's is RC_EINVAL.  Row padding is never written.  Every refusal is decided before anything is queued
+ * and leaves state and outputs as they were; RC_ESTATE before rcflow_offshore_open.  RC_EHIP (the runtime refused a launch) is no
+ * refusal: the state is undefined until rcflow_offshore_reset. */
+int rcflow_offshore_map_dev(rc_ctx* ctx, int stream, const uint8_t* d_wet, size_t wet_step, int* d_dist2, size_t dist2_step, int* d_near,
+                            size_t near_step, int* d_sdist, size_t sdist_step, uint8_t* d_picture, size_t picture_step, long long* d_summary);
+/* One field: RC_OFFSHORE_PUSH_LAUNCHES launches.  d_flow_xy 32FC2 (pointer and step multiples of 8); NULL is the field the slot's
+ * frame loop left resident (rcflow_stream_flow_ptr), with the rules of rcflow_meanflow_push_dev: RC_ESTATE while none is resident,
+ * RC_ESIZE when its size differs.  d_cross_along 32FC2; d_class, d_mask 8UC1; d_picture 8UC3; d_stations stations x
+ * rc_offshore_station (4-byte aligned); d_table stations x bins x RC_OFFSHORE_SUMS int64 and d_summary RC_OFFSHORE_SUMMARY int64
+ * (8-byte aligned).  RC_ESTATE before any map (after open and after a reset).  Otherwise the rules of rcflow_offshore_map_dev. */
+int rcflow_offshore_push_dev(rc_ctx* ctx, int stream, const float* d_flow_xy, size_t flow_step, float* d_cross_along, size_t cross_along_step,
+                             uint8_t* d_class, size_t class_step, uint8_t* d_mask, size_t mask_step, uint8_t* d_picture, size_t picture_step,
+                             rc_offshore_station* d_stations, long long* d_table, long long* d_summary);
+/* One launch on the slot's map: d_band 8UC1, required.  lo and hi in pixels, finite, 0 <= lo <= hi <= 65536 (RC_EINVAL otherwise).
+ * RC_ESTATE before any map.  Changes nothing of the state. */
+int rcflow_offshore_band_dev(rc_ctx* ctx, int stream, float lo, float hi, uint8_t* d_band, size_t band_step);
+/* Blocks until the slot's stream has finished; for hosts and tests.  Each may be NULL: the records and the table of the last push,
+ * the summary of the last push and of the last map (host memory), zeros before the first and after a reset. */
+int rcflow_offshore_read(rc_ctx* ctx, int stream, rc_offshore_station* stations, long long* table, long long push_summary[RC_OFFSHORE_SUMMARY],
+                         long long map_summary[RC_OFFSHORE_SUMMARY]);
+/* everything but stations and bins, which must be the values given at open, from the next call on; RC_EINVAL as rcflow_offshore_open */
+int rcflow_offshore_set(rc_ctx* ctx, int stream, const rc_offshore_params* prm);
+/* forgets the map and zeroes the records, the table, the summaries and the counts; keeps the allocation and the parameters as
+ * rcflow_offshore_set left them; asynchronous, on the slot's stream */
+int rcflow_offshore_reset(rc_ctx* ctx, int stream);
+/* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
+int rcflow_offshore_close(rc_ctx* ctx, int stream);
+/* never blocks; RC_ESTATE when nothing is open, RC_EINVAL without a buffer */
+int rcflow_offshore_info(rc_ctx* ctx, int stream, rc_offshore_info* info);
+
 /* Display path, ripcurrents.cpp:233-273 (= streamline_displacement / _total_motion / _ratio /
  * _positions, ripcurrents_module.cpp:13-60) on the slot's streamline field (rcflow_advect_field_dev):
  * which 0 = |pt|, 1 = dist, 2 = |pt| / dist; minMaxLoc + convertTo(CV_8UC1, 255/max) +

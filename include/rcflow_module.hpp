@@ -1662,4 +1662,92 @@ class Infill {
     DeviceImage d_flow_, d_valid_, d_domain_, d_filled_, d_source_, d_mask_, d_picture_;
 };
 
+// the pictures of an Offshore::map, each optional: dist2, near and sdist 32SC1, picture 8UC3
+struct OffshoreMapPictures { Mat* dist2 = nullptr; Mat* near = nullptr; Mat* sdist = nullptr; Mat* picture = nullptr; };
+// the pictures of an Offshore::push, each optional: cross_along 32FC2, cls and mask 8UC1, picture 8UC3
+struct OffshorePushPictures { Mat* cross_along = nullptr; Mat* cls = nullptr; Mat* mask = nullptr; Mat* picture = nullptr; };
+
+// Offshore frame on the device (rcflow_offshore_*): the exact distance of every pixel to the shore, and a flow field projected on
+// the local shore normal.  Host wet masks (8UC1) and flow fields (32FC2) of the pipeline's size in; the distance planes, the cross /
+// along field, the class, the mask of the seaward flow and pictures out, a record per station along the beach and a table of
+// stations x bins of distance.
+class Offshore {
+  public:
+    using MapPictures = OffshoreMapPictures;
+    using PushPictures = OffshorePushPictures;
+
+    Offshore(Pipeline& pipe, const rc_offshore_params& prm) : pipe_(pipe), stations_(prm.stations), bins_(prm.bins) {
+        check(rcflow_offshore_open(pipe.context(), 0, pipe.width(), pipe.height(), &prm));
+    }
+    ~Offshore() { (void)rcflow_offshore_close(pipe_.context(), 0); }
+    Offshore(const Offshore&) = delete;
+    Offshore& operator=(const Offshore&) = delete;
+
+    // wet: 8UC1, non-zero is water (what Shoreline writes as its wet mask).  Called when the shore has moved; the map stays on the
+    // session for push() and band(), its summary for map_summary()
+    void map(const Mat& wet, const MapPictures& out = MapPictures()) {
+        const int w = pipe_.width(), h = pipe_.height();
+        if (!is_image(wet, w, h, 1, 1)) throw Error(RC_EINVAL, "Offshore::map: the wet mask must be 8UC1 of the pipeline's size");
+        if ((out.dist2 && !is_image(*out.dist2, w, h, 1, 4)) || (out.near && !is_image(*out.near, w, h, 1, 4)) ||
+            (out.sdist && !is_image(*out.sdist, w, h, 1, 4)) || (out.picture && !is_image(*out.picture, w, h, 3, 1)))
+            throw Error(RC_EINVAL, "Offshore::map: dist2, near and sdist 32SC1, picture 8UC3, each of the pipeline's size");
+        staged(pipe_.context(), {{d_wet_, &wet}}, [&] {
+            return rcflow_offshore_map_dev(pipe_.context(), 0, d_wet_.ptr<const uint8_t>(), d_wet_.pitch(), d_dist2_.ptr<int>(out.dist2), d_dist2_.pitch(),
+                                           d_near_.ptr<int>(out.near), d_near_.pitch(), d_sdist_.ptr<int>(out.sdist), d_sdist_.pitch(),
+                                           d_picture_.ptr<uint8_t>(out.picture), d_picture_.pitch(), nullptr);
+        }, {{d_dist2_, out.dist2}, {d_near_, out.near}, {d_sdist_, out.sdist}, {d_picture_, out.picture}});
+    }
+    // flow: 32FC2.  The records, the table and the summary stay on the session after every push, for stations(), table() and read()
+    void push(const Mat& flow, const PushPictures& out = PushPictures()) {
+        const int w = pipe_.width(), h = pipe_.height();
+        if (!is_image(flow, w, h, 2, 4)) throw Error(RC_EINVAL, "Offshore::push: the field must be 32FC2 of the pipeline's size");
+        if ((out.cross_along && !is_image(*out.cross_along, w, h, 2, 4)) || (out.cls && !is_image(*out.cls, w, h, 1, 1)) ||
+            (out.mask && !is_image(*out.mask, w, h, 1, 1)) || (out.picture && !is_image(*out.picture, w, h, 3, 1)))
+            throw Error(RC_EINVAL, "Offshore::push: cross_along 32FC2, cls and mask 8UC1, picture 8UC3, each of the pipeline's size");
+        staged(pipe_.context(), {{d_flow_, &flow}}, [&] {
+            return rcflow_offshore_push_dev(pipe_.context(), 0, d_flow_.ptr<const float>(), d_flow_.pitch(), d_ca_.ptr<float>(out.cross_along), d_ca_.pitch(),
+                                            d_cls_.ptr<uint8_t>(out.cls), d_cls_.pitch(), d_mask_.ptr<uint8_t>(out.mask), d_mask_.pitch(),
+                                            d_picture_.ptr<uint8_t>(out.picture), d_picture_.pitch(), nullptr, nullptr, nullptr);
+        }, {{d_ca_, out.cross_along}, {d_cls_, out.cls}, {d_mask_, out.mask}, {d_picture_, out.picture}});
+    }
+    // band: 8UC1 of the pipeline's size: 255 where the pixel is wet and lo <= its distance to the shore < hi, in pixels
+    void band(float lo, float hi, Mat& band) {
+        if (!is_image(band, pipe_.width(), pipe_.height(), 1, 1)) throw Error(RC_EINVAL, "Offshore::band: the band must be 8UC1 of the pipeline's size");
+        staged(pipe_.context(), {}, [&] {
+            return rcflow_offshore_band_dev(pipe_.context(), 0, lo, hi, d_band_.ptr<uint8_t>(), d_band_.pitch());
+        }, {{d_band_, &band}});
+    }
+    // each waits for the pipeline's stream (include/rcflow.h).  The push summary: the pixels that are OK, NEAR, FAR, DRY, BAD, the mask
+    // pixels, the stations flagged RIP, the pushes.  The map summary: wet, dry, wet and not FAR, the largest d2 and the sum of d2 over
+    // those, the sum of d2 over the dry pixels, 0, the maps
+    std::vector<long long> read() {
+        std::vector<long long> s(RC_OFFSHORE_SUMMARY);
+        check(rcflow_offshore_read(pipe_.context(), 0, nullptr, nullptr, s.data(), nullptr));
+        return s;
+    }
+    std::vector<long long> map_summary() {
+        std::vector<long long> s(RC_OFFSHORE_SUMMARY);
+        check(rcflow_offshore_read(pipe_.context(), 0, nullptr, nullptr, nullptr, s.data()));
+        return s;
+    }
+    std::vector<rc_offshore_station> stations() {
+        std::vector<rc_offshore_station> r((size_t)stations_);
+        check(rcflow_offshore_read(pipe_.context(), 0, r.data(), nullptr, nullptr, nullptr));
+        return r;
+    }
+    std::vector<long long> table() {
+        std::vector<long long> t((size_t)stations_ * bins_ * RC_OFFSHORE_SUMS);
+        check(rcflow_offshore_read(pipe_.context(), 0, nullptr, t.data(), nullptr, nullptr));
+        return t;
+    }
+    void set(const rc_offshore_params& prm) { check(rcflow_offshore_set(pipe_.context(), 0, &prm)); }
+    rc_offshore_info info() { rc_offshore_info i; check(rcflow_offshore_info(pipe_.context(), 0, &i)); return i; }
+    void reset() { check(rcflow_offshore_reset(pipe_.context(), 0)); }
+
+  private:
+    Pipeline& pipe_;
+    int stations_ = 0, bins_ = 0;
+    DeviceImage d_wet_, d_flow_, d_dist2_, d_near_, d_sdist_, d_ca_, d_cls_, d_mask_, d_band_, d_picture_;
+};
+
 }  // namespace rc

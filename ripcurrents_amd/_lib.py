@@ -87,6 +87,11 @@ RC_DRIFTERS_RESPAWN, RC_DRIFTERS_EMPTY = 1, 1
 # rcflow_infill_*: the flags, the source bytes, the record's flag, the bounds, the words of a cell's sums and of the summary, the most launches of a push
 RC_INFILL_LEAVE_NAN, RC_INFILL_LEAVE_ZERO, RC_INFILL_HELD, RC_INFILL_OUTSIDE, RC_INFILL_UNFILLED, RC_INFILL_NONE = 1, 2, 64, 254, 255, 1
 RC_INFILL_MAX_LEVELS, RC_INFILL_MAX_MIN_KNOWN, RC_INFILL_MAX_HOLD, RC_INFILL_SUMS, RC_INFILL_SUMMARY, RC_INFILL_LAUNCHES = 7, 16384, 254, 8, 16, 4
+# rcflow_offshore_*: the far value, the station flags, the classes, the record's flags, the bounds, the words of a cell and of a summary, the launches
+RC_OFFSHORE_FAR, RC_OFFSHORE_STATION_X, RC_OFFSHORE_STATION_Y, RC_OFFSHORE_EMPTY, RC_OFFSHORE_RIP = 0x7fffffff, 1, 2, 1, 2
+RC_OFFSHORE_C_OK, RC_OFFSHORE_C_NEAR, RC_OFFSHORE_C_FAR, RC_OFFSHORE_C_DRY, RC_OFFSHORE_C_BAD = 0, 1, 2, 3, 4
+RC_OFFSHORE_MAX_DIST, RC_OFFSHORE_MAX_STATIONS, RC_OFFSHORE_MAX_BINS, RC_OFFSHORE_MAX_BIN_WIDTH, RC_OFFSHORE_MAX_SIDE = 4095, 256, 256, 256, 32767
+RC_OFFSHORE_SUMS, RC_OFFSHORE_SUMMARY, RC_OFFSHORE_MAP_LAUNCHES, RC_OFFSHORE_PUSH_LAUNCHES = 4, 8, 3, 2
 DRIFTERS_FATES = {"edge_left": 1, "edge_top": 2, "edge_right": 3, "edge_bottom": 4, "bad": 5, "aged": 6, "shore": 9, "offshore": 10}
 
 ERRORS = {-1: "RC_EINVAL", -2: "RC_ENOMEM", -3: "RC_EHIP", -4: "RC_ENODEV", -5: "RC_ESIZE",
@@ -375,6 +380,24 @@ class InfillInfo(C.Structure):
                 ("pushes", C.c_longlong), ("device_bytes", C.c_size_t)]
 
 
+class OffshoreParams(C.Structure):
+    """rc_offshore_params (include/rcflow.h), 48 bytes."""
+    _fields_ = [("min_dist", C.c_int), ("max_dist", C.c_int), ("stations", C.c_int), ("bins", C.c_int), ("bin_width", C.c_int),
+                ("min_count", C.c_int), ("rip_bins", C.c_int), ("cross_min", C.c_float), ("flags", C.c_int), ("pad", C.c_int * 3)]
+
+
+class OffshoreStation(C.Structure):
+    """rc_offshore_station (include/rcflow.h), 48 bytes; numpy: api.OFFSHORE_STATION_DTYPE."""
+    _fields_ = [("flags", C.c_int), ("first", C.c_int), ("reach_end", C.c_int), ("peak_bin", C.c_int), ("peak_cross", C.c_int), ("count", C.c_int),
+                ("beyond", C.c_int), ("pad0", C.c_int), ("mean_cross", C.c_float), ("mean_along", C.c_float), ("pad1", C.c_int * 2)]
+
+
+class OffshoreInfo(C.Structure):
+    """rc_offshore_info (include/rcflow.h)."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", OffshoreParams), ("launches_per_map", C.c_int), ("launches_per_push", C.c_int),
+                ("have_map", C.c_int), ("pad", C.c_int), ("maps", C.c_longlong), ("pushes", C.c_longlong), ("device_bytes", C.c_size_t)]
+
+
 class DriftersParams(C.Structure):
     """rc_drifters_params (include/rcflow.h), 40 bytes."""
     _fields_ = [("max_drifters", C.c_int), ("grid_x", C.c_int), ("grid_y", C.c_int), ("max_age", C.c_int), ("age_bin", C.c_int),
@@ -655,6 +678,15 @@ SIGNATURES = {
     "rcflow_infill_reset": [_vp, _i],
     "rcflow_infill_close": [_vp, _i],
     "rcflow_infill_info": [_vp, _i, C.POINTER(InfillInfo)],
+    "rcflow_offshore_open": [_vp, _i, _i, _i, C.POINTER(OffshoreParams)],
+    "rcflow_offshore_map_dev": [_vp, _i] + [_vp, _sz] * 5 + [_vp],
+    "rcflow_offshore_push_dev": [_vp, _i] + [_vp, _sz] * 5 + [_vp, _vp, _vp],
+    "rcflow_offshore_band_dev": [_vp, _i, C.c_float, C.c_float, _vp, _sz],
+    "rcflow_offshore_read": [_vp, _i, _vp, _vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
+    "rcflow_offshore_set": [_vp, _i, C.POINTER(OffshoreParams)],
+    "rcflow_offshore_reset": [_vp, _i],
+    "rcflow_offshore_close": [_vp, _i],
+    "rcflow_offshore_info": [_vp, _i, C.POINTER(OffshoreInfo)],
     "rcflow_comm_unique_id": [_vp],
     "rcflow_comm_init": [_vp, _vp, _i, _i],
     "rcflow_comm_destroy": [_vp],

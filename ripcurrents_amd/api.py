@@ -46,9 +46,10 @@ from ._lib import RC_MEANFLOW_DIR_FIXED, RC_MEANFLOW_DIR_OPPOSED, RC_MEANFLOW_SU
 from ._lib import RC_FLOWCHECK_FILL_NAN, RC_FLOWCHECK_FILL_ZERO, RC_FLOWCHECK_SUMMARY, RC_FLOWCHECK_SUMS, RC_FLOWCHECK_TESTS, FlowcheckInfo, FlowcheckParams
 from ._lib import RC_DRIFTERS_HIST_BINS, RC_DRIFTERS_RESPAWN, RC_DRIFTERS_SUMMARY, RC_DRIFTERS_SUMS, DriftersInfo, DriftersParams
 from ._lib import RC_INFILL_LEAVE_NAN, RC_INFILL_LEAVE_ZERO, RC_INFILL_SUMMARY, RC_INFILL_SUMS, InfillInfo, InfillParams
+from ._lib import RC_OFFSHORE_STATION_X, RC_OFFSHORE_STATION_Y, RC_OFFSHORE_SUMMARY, RC_OFFSHORE_SUMS, OffshoreInfo, OffshoreParams
 
 __all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState", "Waves", "Piv", "Transects", "Kinematics",
-           "Shoreline", "Surf", "MeanFlow", "FlowCheck", "Drifters", "Infill"]
+           "Shoreline", "Surf", "MeanFlow", "FlowCheck", "Drifters", "Infill", "Offshore"]
 
 
 # rc_draw_prim as a numpy record (32 bytes): what Context.draw takes and Context.tracers_prims returns
@@ -144,6 +145,15 @@ INFILL_SUMS = ("known", "held", "filled", "unfilled", "outside", "sum_fx", "sum_
 INFILL_SOURCES = {"known": 0, "held": 64, "outside": 254, "unfilled": 255}
 INFILL_CELL_DTYPE = np.dtype([("flags", "<i4"), ("pixels", "<i4"), ("known_pm", "<i4"), ("valued_pm", "<i4"), ("mean_x", "<f4"), ("mean_y", "<f4"),
                               ("mean_level", "<f4"), ("pad", "<i4")])
+# the eight words of an offshore map summary and of a push summary, the four of a table cell, the classes by name; rc_offshore_station
+# (48 bytes)
+OFFSHORE_MAP_SUMMARY = ("wet", "dry", "wet_near_shore", "max_d2", "sum_d2_wet", "sum_d2_dry", "zero", "maps")
+OFFSHORE_PUSH_SUMMARY = ("ok", "near", "far", "dry", "bad", "mask", "rips", "pushes")
+OFFSHORE_SUMS = ("count", "sum_cross", "sum_along", "mask")
+OFFSHORE_CLASSES = {"ok": 0, "near": 1, "far": 2, "dry": 3, "bad": 4}
+OFFSHORE_STATION_DTYPE = np.dtype([("flags", "<i4"), ("first", "<i4"), ("reach_end", "<i4"), ("peak_bin", "<i4"), ("peak_cross", "<i4"),
+                                   ("count", "<i4"), ("beyond", "<i4"), ("pad0", "<i4"), ("mean_cross", "<f4"), ("mean_along", "<f4"),
+                                   ("pad1", "<i4", (2,))])
 RIPMAP_SOURCE_NAMES = {v: k for k, v in RIPMAP_SOURCES.items()}
 TRACERS_MOVER_NAMES = {v: k for k, v in TRACERS_MOVERS.items()}
 SHORE_SOURCE_NAMES = {v: k for k, v in SHORE_SOURCES.items()}
@@ -2308,6 +2318,101 @@ class Context:
     def infill_close(self, stream=0):
         self._lifecycle("infill", "close", stream)
 
+    # ------------------------------------------------------------------ offshore frame
+    @staticmethod
+    def _offshore_params(min_dist, max_dist, stations, bins, bin_width, min_count, rip_bins, cross_min, station):
+        if station not in ("x", "y"):
+            raise ValueError("station is 'x' or 'y'")
+        return OffshoreParams(min_dist=int(min_dist), max_dist=int(max_dist), stations=int(stations), bins=int(bins), bin_width=int(bin_width),
+                              min_count=int(min_count), rip_bins=int(rip_bins), cross_min=float(cross_min),
+                              flags=RC_OFFSHORE_STATION_X if station == "x" else RC_OFFSHORE_STATION_Y)
+
+    def offshore_open(self, w, h, min_dist=2, max_dist=200, stations=16, bins=20, bin_width=10, min_count=16, rip_bins=3, cross_min=0.25,
+                      station="x", stream=0):
+        """Opens the slot's offshore frame on w x h pictures (include/rcflow.h, "offshore frame"): the exact distance of every pixel
+        to the shore and, per push, the flow across and along the local shore normal.  Wet pixels between min_dist and max_dist
+        pixels from the shore take part; they are summed in a table of `stations` places along the beach (by the pixel's x or y:
+        station "x" or "y") times `bins` rings of bin_width pixels of distance.  A bin passes with at least min_count pixels and a
+        mean cross flow of at least cross_min pixels per field; rip_bins passing bins in a row from the shore out flag a station."""
+        p = self._offshore_params(min_dist, max_dist, stations, bins, bin_width, min_count, rip_bins, cross_min, station)
+        self._bind(stream)          # the state is zeroed on the slot's stream: the one the calls will run on
+        check(self._lib.rcflow_offshore_open(self._h, stream, int(w), int(h), C.byref(p)))
+
+    def offshore_info(self, stream=0):
+        """dict(w, h, the parameters, station, launches_per_map, launches_per_push, have_map, maps, pushes, device_bytes); never blocks."""
+        i = self._info("offshore", OffshoreInfo(), stream)
+        d = _record(i, skip=("flags", "pad"))
+        d["station"] = "x" if i.prm.flags == RC_OFFSHORE_STATION_X else "y"
+        return d
+
+    def offshore_map(self, wet, dist2=None, near=None, sdist=None, picture=None, summary=None, stream=0):
+        """The map, when the shore has moved: wet HxW uint8 device tensor (non-zero is water: what shoreline_push writes as mask; rows
+        may be padded).  Nothing is synchronised.  Outputs are preallocated device tensors, each optional: dist2 HxW int32 (the
+        squared distance to the nearest pixel of the other class, negated on land), near HxW int32 (that pixel's raster index), sdist
+        HxW int32 (the distance in 1/64 pixel, negated on land), picture HxWx3 uint8, summary 8 int64 (OFFSHORE_MAP_SUMMARY).  The
+        map stays on the slot for offshore_push and offshore_band, the summary for offshore_read."""
+        i = self._info("offshore", OffshoreInfo(), stream)
+        h, w = i.h, i.w
+        args = (self._in_image(wet, torch.uint8, "wet", (h, w)) + self._out_image(dist2, torch.int32, "dist2", (h, w)) +
+                self._out_image(near, torch.int32, "near", (h, w)) + self._out_image(sdist, torch.int32, "sdist", (h, w)) +
+                self._out_image(picture, torch.uint8, "picture", (h, w, 3)))
+        up = self._out_array(summary, torch.int64, "summary", RC_OFFSHORE_SUMMARY)
+        self._bind(stream)
+        check(self._lib.rcflow_offshore_map_dev(self._h, stream, *args, up))
+
+    def offshore_push(self, flow=None, cross_along=None, cls=None, mask=None, picture=None, stations=None, table=None, summary=None, stream=0):
+        """One field (HxWx2 float32 device tensor, dense pixels, rows may be padded; None: the field push_frame_host /
+        frame_loop_step left on the slot) on the slot's map.  Nothing is synchronised.  Outputs are preallocated device tensors, each
+        optional: cross_along HxWx2 float32 (the flow away from the shore and along it, NaN where the pixel takes no part), cls HxW
+        uint8 (OFFSHORE_CLASSES), mask HxW uint8 (255 where the cross flow reaches cross_min: what regions_push takes), picture
+        HxWx3 uint8, stations STATIONSx48 uint8 (rc_offshore_station records; view the host copy as OFFSHORE_STATION_DTYPE), table
+        STATIONSxBINSx4 int64 (OFFSHORE_SUMS), summary 8 int64 (OFFSHORE_PUSH_SUMMARY).  Records, table and summary also stay on the
+        slot for offshore_read."""
+        i = self._info("offshore", OffshoreInfo(), stream)
+        h, w, ns, nb = i.h, i.w, i.prm.stations, i.prm.bins
+        args = (self._in_image(flow, torch.float32, "flow", (h, w, 2), optional=True) +
+                self._out_image(cross_along, torch.float32, "cross_along", (h, w, 2)) + self._out_image(cls, torch.uint8, "cls", (h, w)) +
+                self._out_image(mask, torch.uint8, "mask", (h, w)) + self._out_image(picture, torch.uint8, "picture", (h, w, 3)))
+        rp = self._out_array(stations, torch.uint8, "stations", ns * 48)
+        tp = self._out_array(table, torch.int64, "table", ns * nb * RC_OFFSHORE_SUMS)
+        up = self._out_array(summary, torch.int64, "summary", RC_OFFSHORE_SUMMARY)
+        self._bind(stream)
+        check(self._lib.rcflow_offshore_push_dev(self._h, stream, *args, rp, tp, up))
+
+    def offshore_band(self, lo, hi, out=None, stream=0):
+        """-> HxW uint8: 255 where the pixel is wet and lo <= its distance to the shore < hi, in pixels, on the slot's map; one launch,
+        nothing is synchronised.  The `inside` of drifters_zones, a domain for infill_push."""
+        i = self._info("offshore", OffshoreInfo(), stream)
+        out = self._out_or_new(out, torch.uint8, "out", (i.h, i.w), dense=True)
+        self._bind(stream)
+        check(self._lib.rcflow_offshore_band_dev(self._h, stream, float(lo), float(hi), self._ptr(out), out.stride(0)))
+        return out
+
+    def offshore_read(self, stream=0):
+        """Waits for the slot's stream -> (stations OFFSHORE_STATION_DTYPE, table STATIONSxBINSx4 int64, dict of the last push's
+        summary by OFFSHORE_PUSH_SUMMARY names, dict of the last map's by OFFSHORE_MAP_SUMMARY names); zeros before the first and
+        after a reset."""
+        i = self._info("offshore", OffshoreInfo(), stream)
+        recs = np.zeros(i.prm.stations, OFFSHORE_STATION_DTYPE)
+        table = np.zeros((i.prm.stations, i.prm.bins, RC_OFFSHORE_SUMS), np.int64)
+        ps, ms = np.zeros(RC_OFFSHORE_SUMMARY, np.int64), np.zeros(RC_OFFSHORE_SUMMARY, np.int64)
+        self._bind(stream)
+        ll = C.POINTER(C.c_longlong)
+        check(self._lib.rcflow_offshore_read(self._h, stream, recs.ctypes.data, table.ctypes.data, ps.ctypes.data_as(ll), ms.ctypes.data_as(ll)))
+        return (recs, table, dict(zip(OFFSHORE_PUSH_SUMMARY, (int(v) for v in ps))), dict(zip(OFFSHORE_MAP_SUMMARY, (int(v) for v in ms))))
+
+    def offshore_set(self, min_dist, max_dist, bin_width, min_count, rip_bins, cross_min, station, stream=0):
+        """Everything but stations and bins, from the next call on."""
+        i = self._info("offshore", OffshoreInfo(), stream)
+        p = self._offshore_params(min_dist, max_dist, i.prm.stations, i.prm.bins, bin_width, min_count, rip_bins, cross_min, station)
+        check(self._lib.rcflow_offshore_set(self._h, stream, C.byref(p)))
+
+    def offshore_reset(self, stream=0):
+        self._lifecycle("offshore", "reset", stream)
+
+    def offshore_close(self, stream=0):
+        self._lifecycle("offshore", "close", stream)
+
     # ------------------------------------------------------------------ rip regions
     def regions_open(self, w, h, connectivity=8, min_area=1, max_regions=1024, stream=0):
         """Opens the slot's region labelling for w x h masks: connected components (4 or 8 neighbours) numbered in raster
@@ -2723,6 +2828,24 @@ class Infill(_Product):
 
     def set(self, levels, min_known, leave):
         self.ctx.infill_set(levels, min_known, leave, self.stream)
+
+
+class Offshore(_Product):
+    """The offshore frame of one slot as an object: Context.offshore_* with the context and the slot bound.  Opens on construction
+    (the parameters of Context.offshore_open as keywords), closes on close() or at the end of a with block."""
+    product = "offshore"
+
+    def map(self, wet, **outputs):
+        self.ctx.offshore_map(wet, stream=self.stream, **outputs)
+
+    def push(self, flow=None, **outputs):
+        self.ctx.offshore_push(flow, stream=self.stream, **outputs)
+
+    def band(self, lo, hi, out=None):
+        return self.ctx.offshore_band(lo, hi, out, self.stream)
+
+    def set(self, min_dist, max_dist, bin_width, min_count, rip_bins, cross_min, station):
+        self.ctx.offshore_set(min_dist, max_dist, bin_width, min_count, rip_bins, cross_min, station, self.stream)
 
 
 def kinematics_taps(radius, sigma):

@@ -50,34 +50,16 @@ __device__ __forceinline__ int dr_class(int fate) {
     return fate == RC_DRIFTERS_SHORE ? 0 : fate == RC_DRIFTERS_OFFSHORE ? 1 : fate <= RC_DRIFTERS_EDGE_BOTTOM ? 2 : 3;
 }
 
-// The wave's lanes fall into runs of consecutive lanes with one key (a cell, a pixel; -1 for none): neighbouring drifters are
-// neighbours in memory, so the runs are long.  Every lane of the wave calls these.  -> the last lane of the lane's run; head: the
-// lane is its run's first
-__device__ __forceinline__ int dr_run(int key, int lane, bool& head) {
-    const int prev = __shfl_up(key, 1, 64);
-    head = lane == 0 || key != prev;
-    const unsigned long long heads = __ballot(head);
-    const unsigned long long after = lane == 63 ? 0ull : heads >> (lane + 1);
-    return after ? lane + __ffsll((long long)after) - 1 : 63;
-}
-// the sum of v over the lane's run from the lane on: in the run's first lane, the run's sum
-__device__ __forceinline__ long long dr_run_sum(long long v, int lane, int end) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long t = __shfl_down(v, o, 64);
-        if (lane + o <= end) v += t;
-    }
-    return v;
-}
+// the runs of consecutive lanes with one key: rc_run and rc_run_sum of rc_reduce.h
 // key: the lane's cell, -1 for none (its v is zero then).  One atomic per run and word that is not zero
 __device__ __forceinline__ void dr_cell_add(long long* tab, int key, const long long (&v)[RC_DRIFTERS_SUMS], int lane) {
     if (!__any(key >= 0)) return;
     bool head;
-    const int end = dr_run(key, lane, head);
+    const int end = rc_run(key, lane, head);
 #pragma unroll
     for (int k = 0; k < RC_DRIFTERS_SUMS; k++) {
         if (!__any(v[k] != 0)) continue;
-        const long long s = dr_run_sum(v[k], lane, end);
+        const long long s = rc_run_sum(v[k], lane, end);
         if (head && key >= 0 && s) rc_acc_add(tab + (size_t)RC_DRIFTERS_SUMS * key + k, s);
     }
 }
@@ -190,7 +172,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_dr_move(const DrArgs0 a) {
     }
     if (am) {                                                     // the occupancy: a run of lanes on one pixel adds its length
         bool head;
-        const int end = dr_run(opx, lane, head);
+        const int end = rc_run(opx, lane, head);
         if (head && opx >= 0) rc_acc_add(a.occ + opx, (unsigned)(end - lane + 1));
     }
     dr_cell_add(a.place, pkey, pv, lane);

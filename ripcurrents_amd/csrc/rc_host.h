@@ -407,6 +407,21 @@ struct RcInfill {
     RcZeroFence zf;
 };
 
+// Offshore frame of one stream slot (offshore_kernels.hip).  Everything is allocated by rcflow_offshore_open and released by
+// rcflow_offshore_close / rcflow_destroy.
+struct RcOffshore {
+    bool open = false, have_map = false;
+    int w = 0, h = 0;
+    rc_offshore_params prm{};       // everything but stations and bins: as rcflow_offshore_set left them
+    long long maps = 0, pushes = 0; // since open / reset
+    RcBuf col;                      // 2 x [h][w] int16: per class (dry, wet) the row of the nearest pixel of the class in the column, -1 none
+    RcBuf d2, near;                 // [h][w] int32 each: the map, d2 negated on dry pixels
+    RcBuf jet;                      // COLORMAP_JET, 768 bytes
+    RcBuf acc;                      // int64 the launches add into, zero between calls: 8 of a map | table | beyond [stations] | 8 of a push
+    RcBuf out;                      // the last calls: map summary 8 | push summary 8 | table | records
+    RcZeroFence zf;
+};
+
 // warp_kernels.hip: one launch of the affine / perspective warp
 struct RcWarpArgs {
     const uint8_t* src; size_t step;
@@ -495,6 +510,7 @@ struct RcSlot {
     RcFlowcheck fc;
     RcDrifters dr;
     RcInfill inf;
+    RcOffshore off;
     RcPhaseCorr pc;
 };
 
@@ -559,7 +575,9 @@ struct rc_ctx {
 // picture or a frame, as the time-exposure images and the wave spectra do, and is booked with them, under "overlay".  The surf zone
 // is the time exposure's fourth picture and what is read off it, and is booked there too.  The mean current keeps a window over
 // the flow field and decides from its mean, as the opposing-flow map does, and is booked where that is, under "farneback".  The
-// virtual drifters carry points through the field as the tracer lines do and are booked with them, under "stream".
+// virtual drifters carry points through the field as the tracer lines do and are booked with them, under "stream".  The offshore
+// frame projects one flow field on the shore normal, pixel for pixel, as the post-ops work on the field, and is booked with
+// them, under "farneback"; its map is made from a mask when the shore has moved and is booked with it.
 #define RC_BUCKET_TABLE(X) \
     X(RC_B_FARNEBACK, "farneback") X(RC_B_POLAR, "polar") X(RC_B_THRESHOLD, "threshold") X(RC_B_OVERLAY, "overlay") \
     X(RC_B_EROSION, "erosion") X(RC_B_CODEC, "codec") X(RC_B_STREAM, "stream")
@@ -606,7 +624,8 @@ struct rc_ctx {
     X(RC_K_MEANFLOW, "meanflow", RC_B_FARNEBACK) /* @0 ring, sums, mean, steadiness, spread, picture, cell sums and G, @1 mask, records and summary */ \
     X(RC_K_FLOWCHECK, "flowcheck", RC_B_FARNEBACK) /* @0 staging, gather, box sums, the tests, every output and cell sums, @1 records and summary */ \
     X(RC_K_DRIFTERS, "drifters", RC_B_STREAM) /* @0 release, gather, fates and the scattered adds, @1 density, pictures, records and summary, @2 the zones helper */ \
-    X(RC_K_INFILL, "infill", RC_B_FARNEBACK) /* @0 classes, held state and the pull to level 4, @1 the pull above and the push down to level 5, @2 the push to the pixels, every output and cell sums, @3 records and summary */
+    X(RC_K_INFILL, "infill", RC_B_FARNEBACK) /* @0 classes, held state and the pull to level 4, @1 the pull above and the push down to level 5, @2 the push to the pixels, every output and cell sums, @3 records and summary */ \
+    X(RC_K_OFFSHORE, "offshore", RC_B_FARNEBACK) /* @0 the map's column pass, @1 its row pass, every output and sums, @2 its summary, @3 the push: classes, components, every output and the table, @4 records and summary, @5 the band */
 #define RC_ROW_ID(id, ...) id,
 enum { RC_BUCKET_TABLE(RC_ROW_ID) RC_B_BUCKETS };
 enum { RC_KIND_TABLE(RC_ROW_ID) RC_K_KINDS };
@@ -694,7 +713,7 @@ struct RcProfScope {
     } while (0)
 
 // ---------------------------------------------------------------------------- per-slot products
-// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView, RcWaves, RcPiv, RcTransects, RcKinematics, RcShoreline, RcSurf, RcMeanflow, RcFlowcheck, RcDrifters and RcInfill share one lifecycle.  A product supplies
+// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView, RcWaves, RcPiv, RcTransects, RcKinematics, RcShoreline, RcSurf, RcMeanflow, RcFlowcheck, RcDrifters, RcInfill and RcOffshore share one lifecycle.  A product supplies
 //   void rc_state_free(T&)             frees every buffer and the fence; the state is T() again
 //   int rc_state_zero(RcSlot&, T&)     rc_fence_zero of what open / reset clear, and the counters
 // and open / reset / close are written once, here.
@@ -717,6 +736,7 @@ void rc_state_free(RcMeanflow& v);
 void rc_state_free(RcFlowcheck& v);
 void rc_state_free(RcDrifters& v);
 void rc_state_free(RcInfill& v);
+void rc_state_free(RcOffshore& v);
 int rc_state_zero(RcSlot& s, RcTimex& t);
 int rc_state_zero(RcSlot& s, RcFrameStab& f);
 int rc_state_zero(RcSlot& s, RcRipMap& m);
@@ -736,6 +756,7 @@ int rc_state_zero(RcSlot& s, RcMeanflow& v);
 int rc_state_zero(RcSlot& s, RcFlowcheck& v);
 int rc_state_zero(RcSlot& s, RcDrifters& v);
 int rc_state_zero(RcSlot& s, RcInfill& v);
+int rc_state_zero(RcSlot& s, RcOffshore& v);
 
 // The tail of every open.  The caller has validated, selected the device and built `fresh` (rc: what its allocations
 // returned).  The state that is open is touched only once nothing can be refused any more: a refused open leaves it as it

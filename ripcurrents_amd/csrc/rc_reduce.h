@@ -32,6 +32,27 @@ __device__ __forceinline__ float rc_wave_max_lane0(float v) {
     return v;
 }
 
+// ---------------------------------------------------------------------------------------------------- runs of lanes
+// The wave's lanes fall into runs of consecutive lanes with one key (a cell, a pixel; -1 for none): where neighbours in memory are
+// neighbours in the picture the runs are long, and a run needs one atomic per word, not one per lane (the drifters, the offshore
+// table).  Every lane of the wave calls these.  -> the last lane of the lane's run; head: the lane is its run's first
+__device__ __forceinline__ int rc_run(int key, int lane, bool& head) {
+    const int prev = __shfl_up(key, 1, 64);
+    head = lane == 0 || key != prev;
+    const unsigned long long heads = __ballot(head);
+    const unsigned long long after = lane == 63 ? 0ull : heads >> (lane + 1);
+    return after ? lane + __ffsll((long long)after) - 1 : 63;
+}
+// the sum of v over the lane's run from the lane on: in the run's first lane, the run's sum
+__device__ __forceinline__ long long rc_run_sum(long long v, int lane, int end) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const long long t = __shfl_down(v, o, 64);
+        if (lane + o <= end) v += t;
+    }
+    return v;
+}
+
 // ---------------------------------------------------------------------------------------------------- accumulator words
 // Words in memory that every block of a launch adds to and the last block reads.  Relaxed, agent scope: each is one atomic
 // performed in L2, which orders nothing else; what orders them against the ticket is the hand-off below.

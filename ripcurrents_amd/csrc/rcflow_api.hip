@@ -271,6 +271,7 @@ static void slot_free(RcSlot& s) {
     rc_state_free(s.fc);
     rc_state_free(s.dr);
     rc_state_free(s.inf);
+    rc_state_free(s.off);
     rc_buf_free(s.pc.tab); rc_buf_free(s.pc.scratch);
     rc_graph_drop(s.loop_graph);
     for (auto& e : s.fev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
