@@ -122,6 +122,8 @@ int rcflow_use_own_stream(rc_ctx* ctx, int stream);
  * frame t+1 beside the flow kernels of frame t; 1 = rcflow_push_frame_u8 only (the library owns the upload), 2 = also
  * rcflow_push_frame_dev, the caller then guaranteeing that d_frame is complete when the call is made; "merge_small" (1) merged launches for calls of one or two frames; "fuse_pyr" (1)
  * pyramid scales 1 and 2 written by the scale-0 expansion launch (pyr_scale 0.5, exact half / quarter sizes);
+ * "outlines_early" (1) a pointer round of rcflow_outlines_push_dev returns at once when the round before it changed nothing (0: every
+ * round does its work; same bits);
  * "ablate" bit field selecting the alternative kernel forms the bit-identity tests compare against (0 in production):
  * 2 option exact, box windows of winsize 3 / 5: plain scans; 16 the same with the matrices inside the column scan;
  * 4096 earlier pyramid kernels; 65536 tile kernel for Gaussian winsize 10 / 20 whatever the launch size; 8388608
@@ -2754,6 +2756,120 @@ int rcflow_offshore_reset(rc_ctx* ctx, int stream);
 int rcflow_offshore_close(rc_ctx* ctx, int stream);
 /* never blocks; RC_ESTATE when nothing is open, RC_EINVAL without a buffer */
 int rcflow_offshore_info(rc_ctx* ctx, int stream, rc_offshore_info* info);
+
+/* ------------------------------------------------------------------ region outlines: boundaries traced into ordered polygons
+ * Every product above that ends in a mask (the regions' and the tracks' label planes, the shoreline's wet mask, the surf-zone mask,
+ * the offshore band, the vortex cores, the FTLE ridges) can be handed on as a shape: the boundary of every region as an ordered
+ * polygon of lattice corners, holes told apart from outer boundaries, with perimeter and signed area.  Everything is an integer and
+ * does not depend on the order in which the device arrives at it; tests/_outlines_ref.py states it by a sequential walk.
+ *
+ *  1. Input.  Exactly one of d_labels (32SC1: the label plane of rcflow_regions_push_dev, the footprint of the tracks; pointer and
+ *     step multiples of 4) and d_mask (8UC1: a non-zero byte is label 1).  A pixel with label 0 belongs to nothing.  A side of the
+ *     picture is at most RC_OUTLINES_MAX_SIDE, so that a corner stays within RC_DRAW_COORD_MAX and a crack's key within int32.
+ *  2. Cracks.  A crack is one side of a pixel, directed.  Pixel P = (x, y) with label L != 0 has the sides s = 0 N, 1 E, 2 S, 3 W;
+ *     side s is a crack when the 4-neighbour across it lies outside the picture or has a label other than L (another non-zero label
+ *     counts like background).  A crack runs with P on its right, y down: N (x, y) -> (x+1, y); E (x+1, y) -> (x+1, y+1);
+ *     S (x+1, y+1) -> (x, y+1); W (x, y+1) -> (x, y).  Its key is (y * w + x) * 4 + s.
+ *  3. Successor.  For side s: d the crack's direction, (1,0), (0,1), (-1,0), (0,-1); a the step across it, (0,-1), (1,0), (0,1),
+ *     (-1,0); R = P + d; Lp = P + d + a; same(X): X is inside the picture and has label L.  Connectivity 8 takes the first that
+ *     holds of: same(Lp): turn left, to (Lp, (s+3)%4); same(R): straight on, to (R, s); else turn right, to (P, (s+1)%4).
+ *     Connectivity 4 takes the first that holds of: not same(R): turn right; same(Lp): turn left; else straight on.  The successor is
+ *     a permutation of the cracks, which therefore fall into disjoint closed loops.
+ *  4. Loops.  A loop's leader is its crack with the smallest key; a crack's rank is its number of steps from the leader; loops are
+ *     numbered in increasing order of their leader's key.  cracks: the loop's length, the perimeter in pixel sides.  area2: the sum
+ *     over its cracks of x0 * y1 - x1 * y0 from (x0, y0) to (x1, y1), twice the signed area, positive for an outer boundary and
+ *     negative for a hole.  A turn crack is one whose successor has another side; vertex j of a loop is the second corner of its
+ *     j-th turn crack in rank order; verts is their number, always even and at least 4.  The box x0, y0, x1, y1 is the inclusive box
+ *     of the loop's corners.
+ *  5. Filter and caps.  Loops with cracks < min_cracks are dropped and the rest renumbered in order (min_cracks <= 4 keeps all).
+ *     The first min(kept, max_loops) get a record.  Vertex offsets are the running sum of verts over the kept loops in order; a
+ *     loop is stored whole when offset + verts <= max_vertices, otherwise its offset is -1, RC_OUTLINE_NOVERTS is set and none of
+ *     its vertices is written.  A picture with more cracks than max_cracks gives no loops: records and vertices are zero bytes, the
+ *     summary carries the true crack count and the overflow word, and the host re-opens larger.  Nothing is truncated silently and
+ *     nothing is written past a cap.
+ *  6. Outputs.  d_loops: max_loops records, zero bytes beyond the written ones.  d_verts: max_vertices pairs (x, y) of int32, lattice
+ *     corners in 0..w and 0..h, zero beyond the written ones.  d_summary, RC_OUTLINES_SUMMARY int64: 0 the cracks of the picture (true
+ *     also on overflow), 1 the loops before the filter, 2 the loops kept, 3 the records written, 4 the vertices of the kept loops,
+ *     5 the vertices written, 6 1 when the cracks overflowed, else 0, 7 the pushes since open or reset.
+ *  7. Primitives.  rcflow_outlines_prims_dev gives max_vertices records of rc_draw_prim from the last push: stored vertex i of a loop
+ *     gives a line of `thickness` and `color` from it to the loop's next vertex, the last one to the first, every coordinate
+ *     min(x, w - 1), min(y, h - 1); every other slot is an all-zero record, which rcflow_draw_dev skips AND COUNTS, as it does with
+ *     the regions' primitives.  The count is fixed, so the host never reads the device to know it.
+ *
+ * A push is RC_OUTLINES_FIXED_LAUNCHES + 2 * rounds launches, rounds = ceil(log2(max_cracks)), whatever the picture holds
+ * ("outlines@0".."outlines@10", launches that belong together under one name; the primitives are "outlines@11"): the sides and their
+ * count per block of pixels, and a scan of the block counts; the cracks compacted in key order with their successor's key; the
+ * successor's place in that list; `rounds` rounds of pointer doubling that carry the smallest key of the window, each its own launch
+ * from one buffer pair into the other, after which every crack knows its loop's leader; every loop cut before its leader; `rounds`
+ * rounds of list ranking; the loops numbered; the cracks scattered to loop order; area, box and turns added per loop; the turns
+ * scanned into vertex places and the vertices written; the records closed.  A round that finds that the round before it changed
+ * nothing returns at once; the launch count stays what rcflow_outlines_info says.
+ * Simplifying a polygon (Douglas-Peucker) is left to the host, which does it on a few thousand vertices in microseconds. */
+#define RC_OUTLINES_MAX_SIDE 16383
+#define RC_OUTLINES_MAX_CRACKS (1 << 25)     /* 36 bytes of state a crack */
+#define RC_OUTLINES_MAX_LOOPS (1 << 20)
+#define RC_OUTLINES_MAX_VERTICES (1 << 24)   /* RC_DRAW_MAX_PRIMS: the primitives of one call to rcflow_draw_dev */
+#define RC_OUTLINES_SUMMARY 8
+#define RC_OUTLINES_FIXED_LAUNCHES 13
+#define RC_OUTLINE_HOLE 1                    /* rc_outline_loop::flags: area2 < 0 */
+#define RC_OUTLINE_NOVERTS 2                 /* the loop's vertices did not fit max_vertices: offset -1, none written */
+typedef struct rc_outlines_params {
+    int connectivity;       /* 4 or 8 */
+    int min_cracks;         /* >= 1: shorter loops are dropped */
+    int max_cracks;         /* 4..RC_OUTLINES_MAX_CRACKS: the cracks of a picture the slot has room for */
+    int max_loops;          /* 1..RC_OUTLINES_MAX_LOOPS: the records */
+    int max_vertices;       /* 4..RC_OUTLINES_MAX_VERTICES: the vertices, and the primitives of rcflow_outlines_prims_dev */
+    int flags;              /* 0 */
+    int pad[2];             /* zero */
+} rc_outlines_params;       /* 32 bytes */
+typedef struct rc_outline_loop {
+    int32_t label;
+    int32_t flags;          /* RC_OUTLINE_HOLE, RC_OUTLINE_NOVERTS */
+    int32_t x, y;           /* the leader's pixel: of an outer boundary the first pixel of the region in raster order */
+    int32_t cracks;         /* the perimeter in pixel sides */
+    int32_t verts;
+    int32_t offset;         /* of the loop's first vertex in d_verts, in vertices; -1 with RC_OUTLINE_NOVERTS */
+    int32_t pad;
+    int32_t x0, y0, x1, y1; /* the inclusive box of the corners */
+    long long area2;        /* twice the signed area */
+} rc_outline_loop;          /* 56 bytes, 8-byte aligned */
+typedef struct rc_outlines_info {
+    int w, h;
+    rc_outlines_params prm;            /* min_cracks as rcflow_outlines_set left it */
+    int rounds;                        /* ceil(log2(max_cracks)) */
+    int launches_per_push;             /* RC_OUTLINES_FIXED_LAUNCHES + 2 * rounds */
+    long long pushes;                  /* since open / reset */
+    size_t device_bytes;
+} rc_outlines_info;
+/* Allocates everything the slot will ever need.  Re-opening replaces the state; a refused open leaves the open state as it was.
+ * RC_EINVAL without parameters, for a value outside the ranges above, flags or a pad word that is not zero; RC_ESIZE beyond the
+ * context's max_w x max_h or RC_OUTLINES_MAX_SIDE. */
+int rcflow_outlines_open(rc_ctx* ctx, int stream, int w, int h, const rc_outlines_params* prm);
+/* One picture.  Exactly one of d_labels and d_mask (RC_EINVAL for both or neither); d_loops max_loops x rc_outline_loop and d_summary
+ * RC_OUTLINES_SUMMARY int64 (8-byte aligned), d_verts 2 * max_vertices int32 (4-byte aligned), each optional: the state is updated
+ * whatever is asked for, and what a call gives does not depend on what it asked for.  No host synchronisation, no device-to-host
+ * copy.  An output whose byte range overlaps the input's or another output's is RC_EINVAL.  The input is never written.  Every
+ * refusal is decided before anything is queued and leaves state and outputs as they were; RC_ESTATE before rcflow_outlines_open.
+ * RC_EHIP (the runtime refused a launch) is no refusal: the state is undefined until rcflow_outlines_reset. */
+int rcflow_outlines_push_dev(rc_ctx* ctx, int stream, const int32_t* d_labels, size_t labels_step, const uint8_t* d_mask, size_t mask_step,
+                             rc_outline_loop* d_loops, int32_t* d_verts, long long* d_summary);
+/* max_vertices primitives of the last push into d_prims ("outlines@11"; all zero before the first and after a reset).  RC_EINVAL:
+ * d_prims NULL or not 4-byte aligned, thickness outside 1..RC_DRAW_MAX_THICKNESS. */
+int rcflow_outlines_prims_dev(rc_ctx* ctx, int stream, uint32_t color, int thickness, rc_draw_prim* d_prims);
+/* Blocks until the slot's stream has finished; for hosts and tests.  The first min(written, cap) records of the last push into
+ * `loops` and the first min(written, vcap) vertices into `verts` (2 int32 each); *n the records written, *nv the vertices written;
+ * each pointer may be NULL (with its cap 0).  Zeros before the first push and after a reset.  RC_EINVAL for a negative cap or a cap
+ * without a buffer. */
+int rcflow_outlines_read(rc_ctx* ctx, int stream, rc_outline_loop* loops, int cap, int* n, int32_t* verts, int vcap, int* nv,
+                         long long summary[RC_OUTLINES_SUMMARY]);
+/* min_cracks >= 1 (RC_EINVAL otherwise), from the next push on */
+int rcflow_outlines_set(rc_ctx* ctx, int stream, int min_cracks);
+/* zeroes the records, the vertices, the summary and the push count; keeps the allocation and min_cracks; asynchronous, on the slot's stream */
+int rcflow_outlines_reset(rc_ctx* ctx, int stream);
+/* frees the state (rcflow_destroy does the same); RC_OK when nothing is open */
+int rcflow_outlines_close(rc_ctx* ctx, int stream);
+/* never blocks; RC_ESTATE when nothing is open, RC_EINVAL without a buffer */
+int rcflow_outlines_info(rc_ctx* ctx, int stream, rc_outlines_info* info);
 
 /* Display path, ripcurrents.cpp:233-273 (= streamline_displacement / _total_motion / _ratio /
  * _positions, ripcurrents_module.cpp:13-60) on the slot's streamline field (rcflow_advect_field_dev):

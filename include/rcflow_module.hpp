@@ -1750,4 +1750,63 @@ class Offshore {
     DeviceImage d_wet_, d_flow_, d_dist2_, d_near_, d_sdist_, d_ca_, d_cls_, d_mask_, d_band_, d_picture_;
 };
 
+// the loops of an Outlines::read: the records written, in order, and the stored vertices, (x, y) pairs of lattice corners; loop r's
+// polygon is vertices 2 * r.offset .. 2 * (r.offset + r.verts) unless r.offset is -1.  summary: the 8 words of include/rcflow.h
+struct OutlinesResult {
+    std::vector<rc_outline_loop> loops;
+    std::vector<int32_t> verts;
+    long long summary[RC_OUTLINES_SUMMARY] = {};
+};
+
+// Region outlines on the device (rcflow_outlines_*): the boundaries of a label plane (32SC1: what Regions::push writes as labels) or
+// of a mask (8UC1, non-zero is label 1) of the pipeline's size traced into ordered polygons, outer boundaries and holes told apart.
+// Host images in, records and vertices out.
+class Outlines {
+  public:
+    Outlines(Pipeline& pipe, const rc_outlines_params& prm) : pipe_(pipe), prm_(prm) {
+        check(rcflow_outlines_open(pipe.context(), 0, pipe.width(), pipe.height(), &prm));
+    }
+    ~Outlines() { (void)rcflow_outlines_close(pipe_.context(), 0); }
+    Outlines(const Outlines&) = delete;
+    Outlines& operator=(const Outlines&) = delete;
+
+    // plane: 32SC1 labels or an 8UC1 mask.  Records, vertices and summary stay on the session after every push, for read() and draw()
+    void push(const Mat& plane) {
+        const int w = pipe_.width(), h = pipe_.height();
+        const bool labels = is_image(plane, w, h, 1, 4);
+        if (!labels && !is_image(plane, w, h, 1, 1)) throw Error(RC_EINVAL, "Outlines::push: the plane must be 32SC1 or 8UC1 of the pipeline's size");
+        DeviceImage& d = labels ? d_labels_ : d_mask_;
+        staged(pipe_.context(), {{d, &plane}}, [&] {
+            return rcflow_outlines_push_dev(pipe_.context(), 0, d_labels_.ptr<const int32_t>(labels), labels ? d_labels_.pitch() : 0,
+                                            d_mask_.ptr<const uint8_t>(!labels), labels ? 0 : d_mask_.pitch(), nullptr, nullptr, nullptr);
+        }, {});
+    }
+    // waits for the pipeline's stream
+    OutlinesResult read() {
+        OutlinesResult r;
+        r.loops.resize((size_t)prm_.max_loops);
+        r.verts.resize(2 * (size_t)prm_.max_vertices);
+        int n = 0, nv = 0;
+        check(rcflow_outlines_read(pipe_.context(), 0, r.loops.data(), prm_.max_loops, &n, r.verts.data(), prm_.max_vertices, &nv, r.summary));
+        r.loops.resize((size_t)n);
+        r.verts.resize(2 * (size_t)nv);
+        return r;
+    }
+    // paints the stored polygons of the last push into img (8UC3), every vertex clamped into the picture
+    void draw(Mat& img, uint32_t color = 0x00ffff, int thickness = 1) {
+        if (!is_image(img, pipe_.width(), pipe_.height(), 3, 1)) throw Error(RC_EINVAL, "Outlines::draw: img must be 8UC3 of the pipeline's size");
+        staged_draw(pipe_.context(), d_canvas_, d_prims_, prm_.max_vertices, img, [&](rc_draw_prim* prims) {
+            return rcflow_outlines_prims_dev(pipe_.context(), 0, color, thickness, prims);
+        });
+    }
+    void setMinCracks(int min_cracks) { check(rcflow_outlines_set(pipe_.context(), 0, min_cracks)); }
+    rc_outlines_info info() { rc_outlines_info i; check(rcflow_outlines_info(pipe_.context(), 0, &i)); return i; }
+    void reset() { check(rcflow_outlines_reset(pipe_.context(), 0)); }
+
+  private:
+    Pipeline& pipe_;
+    rc_outlines_params prm_;
+    DeviceImage d_labels_, d_mask_, d_prims_, d_canvas_;
+};
+
 }  // namespace rc

@@ -92,6 +92,9 @@ RC_OFFSHORE_FAR, RC_OFFSHORE_STATION_X, RC_OFFSHORE_STATION_Y, RC_OFFSHORE_EMPTY
 RC_OFFSHORE_C_OK, RC_OFFSHORE_C_NEAR, RC_OFFSHORE_C_FAR, RC_OFFSHORE_C_DRY, RC_OFFSHORE_C_BAD = 0, 1, 2, 3, 4
 RC_OFFSHORE_MAX_DIST, RC_OFFSHORE_MAX_STATIONS, RC_OFFSHORE_MAX_BINS, RC_OFFSHORE_MAX_BIN_WIDTH, RC_OFFSHORE_MAX_SIDE = 4095, 256, 256, 256, 32767
 RC_OFFSHORE_SUMS, RC_OFFSHORE_SUMMARY, RC_OFFSHORE_MAP_LAUNCHES, RC_OFFSHORE_PUSH_LAUNCHES = 4, 8, 3, 2
+# rcflow_outlines_*: the bounds, the words of a summary, the launches that do not depend on the rounds, the record's flags
+RC_OUTLINES_MAX_SIDE, RC_OUTLINES_MAX_CRACKS, RC_OUTLINES_MAX_LOOPS, RC_OUTLINES_MAX_VERTICES = 16383, 1 << 25, 1 << 20, 1 << 24
+RC_OUTLINES_SUMMARY, RC_OUTLINES_FIXED_LAUNCHES, RC_OUTLINE_HOLE, RC_OUTLINE_NOVERTS = 8, 13, 1, 2
 DRIFTERS_FATES = {"edge_left": 1, "edge_top": 2, "edge_right": 3, "edge_bottom": 4, "bad": 5, "aged": 6, "shore": 9, "offshore": 10}
 
 ERRORS = {-1: "RC_EINVAL", -2: "RC_ENOMEM", -3: "RC_EHIP", -4: "RC_ENODEV", -5: "RC_ESIZE",
@@ -398,6 +401,25 @@ class OffshoreInfo(C.Structure):
                 ("have_map", C.c_int), ("pad", C.c_int), ("maps", C.c_longlong), ("pushes", C.c_longlong), ("device_bytes", C.c_size_t)]
 
 
+class OutlinesParams(C.Structure):
+    """rc_outlines_params (include/rcflow.h), 32 bytes."""
+    _fields_ = [("connectivity", C.c_int), ("min_cracks", C.c_int), ("max_cracks", C.c_int), ("max_loops", C.c_int), ("max_vertices", C.c_int),
+                ("flags", C.c_int), ("pad", C.c_int * 2)]
+
+
+class OutlineLoop(C.Structure):
+    """rc_outline_loop (include/rcflow.h), 56 bytes; numpy: api.OUTLINE_LOOP_DTYPE."""
+    _fields_ = [("label", C.c_int32), ("flags", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("cracks", C.c_int32), ("verts", C.c_int32),
+                ("offset", C.c_int32), ("pad", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32),
+                ("area2", C.c_longlong)]
+
+
+class OutlinesInfo(C.Structure):
+    """rc_outlines_info (include/rcflow.h)."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("prm", OutlinesParams), ("rounds", C.c_int), ("launches_per_push", C.c_int),
+                ("pushes", C.c_longlong), ("device_bytes", C.c_size_t)]
+
+
 class DriftersParams(C.Structure):
     """rc_drifters_params (include/rcflow.h), 40 bytes."""
     _fields_ = [("max_drifters", C.c_int), ("grid_x", C.c_int), ("grid_y", C.c_int), ("max_age", C.c_int), ("age_bin", C.c_int),
@@ -687,6 +709,14 @@ SIGNATURES = {
     "rcflow_offshore_reset": [_vp, _i],
     "rcflow_offshore_close": [_vp, _i],
     "rcflow_offshore_info": [_vp, _i, C.POINTER(OffshoreInfo)],
+    "rcflow_outlines_open": [_vp, _i, _i, _i, C.POINTER(OutlinesParams)],
+    "rcflow_outlines_push_dev": [_vp, _i] + [_vp, _sz] * 2 + [_vp, _vp, _vp],
+    "rcflow_outlines_prims_dev": [_vp, _i, C.c_uint32, _i, _vp],
+    "rcflow_outlines_read": [_vp, _i, _vp, _i, C.POINTER(_i), _vp, _i, C.POINTER(_i), C.POINTER(C.c_longlong)],
+    "rcflow_outlines_set": [_vp, _i, _i],
+    "rcflow_outlines_reset": [_vp, _i],
+    "rcflow_outlines_close": [_vp, _i],
+    "rcflow_outlines_info": [_vp, _i, C.POINTER(OutlinesInfo)],
     "rcflow_comm_unique_id": [_vp],
     "rcflow_comm_init": [_vp, _vp, _i, _i],
     "rcflow_comm_destroy": [_vp],

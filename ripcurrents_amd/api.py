@@ -47,9 +47,10 @@ from ._lib import RC_FLOWCHECK_FILL_NAN, RC_FLOWCHECK_FILL_ZERO, RC_FLOWCHECK_SU
 from ._lib import RC_DRIFTERS_HIST_BINS, RC_DRIFTERS_RESPAWN, RC_DRIFTERS_SUMMARY, RC_DRIFTERS_SUMS, DriftersInfo, DriftersParams
 from ._lib import RC_INFILL_LEAVE_NAN, RC_INFILL_LEAVE_ZERO, RC_INFILL_SUMMARY, RC_INFILL_SUMS, InfillInfo, InfillParams
 from ._lib import RC_OFFSHORE_STATION_X, RC_OFFSHORE_STATION_Y, RC_OFFSHORE_SUMMARY, RC_OFFSHORE_SUMS, OffshoreInfo, OffshoreParams
+from ._lib import RC_OUTLINES_SUMMARY, OutlinesInfo, OutlinesParams
 
 __all__ = ["Context", "FarnebackParams", "Streakline", "Timeline", "PopulationMap", "HistState", "Waves", "Piv", "Transects", "Kinematics",
-           "Shoreline", "Surf", "MeanFlow", "FlowCheck", "Drifters", "Infill", "Offshore"]
+           "Shoreline", "Surf", "MeanFlow", "FlowCheck", "Drifters", "Infill", "Offshore", "Outlines"]
 
 
 # rc_draw_prim as a numpy record (32 bytes): what Context.draw takes and Context.tracers_prims returns
@@ -154,6 +155,11 @@ OFFSHORE_CLASSES = {"ok": 0, "near": 1, "far": 2, "dry": 3, "bad": 4}
 OFFSHORE_STATION_DTYPE = np.dtype([("flags", "<i4"), ("first", "<i4"), ("reach_end", "<i4"), ("peak_bin", "<i4"), ("peak_cross", "<i4"),
                                    ("count", "<i4"), ("beyond", "<i4"), ("pad0", "<i4"), ("mean_cross", "<f4"), ("mean_along", "<f4"),
                                    ("pad1", "<i4", (2,))])
+# the eight words of an outlines summary; rc_outline_loop (56 bytes) and its flags by name
+OUTLINES_SUMMARY = ("cracks", "loops", "kept", "records", "vertices_kept", "vertices", "overflow", "pushes")
+OUTLINE_FLAGS = {"hole": 1, "noverts": 2}
+OUTLINE_LOOP_DTYPE = np.dtype([("label", "<i4"), ("flags", "<i4"), ("x", "<i4"), ("y", "<i4"), ("cracks", "<i4"), ("verts", "<i4"), ("offset", "<i4"),
+                               ("pad", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("area2", "<i8")])
 RIPMAP_SOURCE_NAMES = {v: k for k, v in RIPMAP_SOURCES.items()}
 TRACERS_MOVER_NAMES = {v: k for k, v in TRACERS_MOVERS.items()}
 SHORE_SOURCE_NAMES = {v: k for k, v in SHORE_SOURCES.items()}
@@ -2413,6 +2419,68 @@ class Context:
     def offshore_close(self, stream=0):
         self._lifecycle("offshore", "close", stream)
 
+    # ------------------------------------------------------------------ region outlines
+    def outlines_open(self, w, h, connectivity=8, min_cracks=4, max_cracks=1 << 20, max_loops=1024, max_vertices=1 << 16, stream=0):
+        """Opens the slot's boundary tracing for w x h label planes and masks (include/rcflow.h, "region outlines"): every boundary
+        as an ordered polygon of lattice corners, outer boundaries and holes told apart.  Loops shorter than min_cracks pixel sides
+        are dropped; the first max_loops of the rest get a record, and their vertices are stored while they fit max_vertices.  A
+        picture with more than max_cracks boundary sides gives no loops and says so in the summary.  36 bytes of device memory per
+        crack of max_cracks and 5 per pixel."""
+        p = OutlinesParams(connectivity=int(connectivity), min_cracks=int(min_cracks), max_cracks=int(max_cracks), max_loops=int(max_loops),
+                           max_vertices=int(max_vertices), flags=0)
+        self._bind(stream)          # the state is zeroed on the slot's stream: the one the pushes will run on
+        check(self._lib.rcflow_outlines_open(self._h, stream, int(w), int(h), C.byref(p)))
+
+    def outlines_info(self, stream=0):
+        """dict(w, h, the parameters, rounds, launches_per_push, pushes, device_bytes); never blocks."""
+        return _record(self._info("outlines", OutlinesInfo(), stream), skip=("flags", "pad"))
+
+    def outlines_set(self, min_cracks, stream=0):
+        """min_cracks from the next push on."""
+        check(self._lib.rcflow_outlines_set(self._h, stream, int(min_cracks)))
+
+    def outlines_push(self, labels=None, mask=None, loops=None, verts=None, summary=None, stream=0):
+        """One picture, exactly one of labels (HxW int32 device tensor: what regions_push writes as labels, the tracks' footprint) and
+        mask (HxW uint8, non-zero is label 1); dense pixels, rows may be padded.  Nothing is synchronised.  Outputs are preallocated
+        device tensors, each optional: loops a contiguous uint8 tensor of max_loops * 56 bytes (rc_outline_loop records; view the
+        host copy as OUTLINE_LOOP_DTYPE), verts max_vertices x 2 int32 (x, y of lattice corners), summary 8 int64
+        (OUTLINES_SUMMARY).  All three also stay on the slot for outlines_read / outlines_prims."""
+        i = self._info("outlines", OutlinesInfo(), stream)
+        h, w = i.h, i.w
+        if (labels is None) == (mask is None):
+            raise ValueError("exactly one of labels and mask")
+        args = self._in_image(labels, torch.int32, "labels", (h, w), optional=True) + self._in_image(mask, torch.uint8, "mask", (h, w), optional=True)
+        lp = self._out_array(loops, torch.uint8, "loops", i.prm.max_loops * OUTLINE_LOOP_DTYPE.itemsize)
+        vp = self._out_array(verts, torch.int32, "verts", i.prm.max_vertices * 2)
+        up = self._out_array(summary, torch.int64, "summary", RC_OUTLINES_SUMMARY)
+        self._bind(stream)
+        check(self._lib.rcflow_outlines_push_dev(self._h, stream, *args, lp, vp, up))
+
+    def outlines_prims(self, color=0x00ffff, thickness=1, out=None, stream=0):
+        """The stored vertices of the last push as max_vertices primitives for draw() -> a device uint8 tensor of rc_draw_prim records:
+        per stored vertex a line to its loop's next vertex; every other slot is kind 0, which draw() skips (and counts)."""
+        out = self._prims_out(out, self._info("outlines", OutlinesInfo(), stream).prm.max_vertices)
+        self._bind(stream)
+        check(self._lib.rcflow_outlines_prims_dev(self._h, stream, int(color), int(thickness), self._ptr(out)))
+        return out
+
+    def outlines_read(self, stream=0):
+        """Waits for the slot's stream -> (the records of the last push as a numpy array of OUTLINE_LOOP_DTYPE, its stored vertices
+        Nx2 int32, dict of the summary by OUTLINES_SUMMARY names).  Loop r's polygon is verts[r.offset:r.offset + r.verts] unless
+        r.offset is -1."""
+        i = self._info("outlines", OutlinesInfo(), stream)
+        rec, verts = np.zeros(i.prm.max_loops, OUTLINE_LOOP_DTYPE), np.zeros((i.prm.max_vertices, 2), np.int32)
+        n, nv = C.c_int(0), C.c_int(0)
+        summ = self._summary(self._lib.rcflow_outlines_read, stream, OUTLINES_SUMMARY, rec.ctypes.data, len(rec), C.byref(n), verts.ctypes.data,
+                             len(verts), C.byref(nv))
+        return rec[:n.value].copy(), verts[:nv.value].copy(), summ
+
+    def outlines_reset(self, stream=0):
+        self._lifecycle("outlines", "reset", stream)
+
+    def outlines_close(self, stream=0):
+        self._lifecycle("outlines", "close", stream)
+
     # ------------------------------------------------------------------ rip regions
     def regions_open(self, w, h, connectivity=8, min_area=1, max_regions=1024, stream=0):
         """Opens the slot's region labelling for w x h masks: connected components (4 or 8 neighbours) numbered in raster
@@ -2846,6 +2914,21 @@ class Offshore(_Product):
 
     def set(self, min_dist, max_dist, bin_width, min_count, rip_bins, cross_min, station):
         self.ctx.offshore_set(min_dist, max_dist, bin_width, min_count, rip_bins, cross_min, station, self.stream)
+
+
+class Outlines(_Product):
+    """The region outlines of one slot as an object: Context.outlines_* with the context and the slot bound.  Opens on construction
+    (the parameters of Context.outlines_open as keywords), closes on close() or at the end of a with block."""
+    product = "outlines"
+
+    def push(self, labels=None, mask=None, **outputs):
+        self.ctx.outlines_push(labels, mask, stream=self.stream, **outputs)
+
+    def prims(self, color=0x00ffff, thickness=1, out=None):
+        return self.ctx.outlines_prims(color, thickness, out, self.stream)
+
+    def set(self, min_cracks):
+        self.ctx.outlines_set(min_cracks, self.stream)
 
 
 def kinematics_taps(radius, sigma):

@@ -422,6 +422,27 @@ struct RcOffshore {
     RcZeroFence zf;
 };
 
+// Region outlines of one stream slot (outline_kernels.hip).  Everything is allocated by rcflow_outlines_open and released by
+// rcflow_outlines_close / rcflow_destroy.
+struct RcOutlines {
+    bool open = false;
+    int w = 0, h = 0, rounds = 0;
+    rc_outlines_params prm{};       // min_cracks: as rcflow_outlines_set left it
+    long long pushes = 0;           // since open / reset
+    RcBuf bits;                     // [h][w] uint8: the four side bits of a pixel
+    RcBuf base;                     // [h][w] int32: the cracks before the pixel in key order
+    RcBuf blk;                      // counts of the pixel blocks | their bases | the partials of the scans over cracks
+    RcBuf kt;                       // [max_cracks] uint32: key | turn << 31, in key order
+    RcBuf succ, lead;               // [max_cracks] int32 each: the successor's place, the leader's place
+    RcBuf pair[2];                  // [max_cracks] int2 each: the rounds' buffer pair; after them (number, offset) per leader
+    RcBuf okt, ok;                  // [max_cracks] each: key | turn << 31 and the loop's number, in loop order
+    RcBuf loops;                    // [max_loops]: leader's key, offset, length | the measures the launches add into
+    RcBuf ctl;                      // OlCtl: what a push's launches hand each other
+    RcBuf vnext;                    // [max_vertices] int32: the next vertex of a stored vertex's loop (the primitives)
+    RcBuf out;                      // the last push: summary 8 int64 | records [max_loops] | vertices [max_vertices][2]
+    RcZeroFence zf;
+};
+
 // warp_kernels.hip: one launch of the affine / perspective warp
 struct RcWarpArgs {
     const uint8_t* src; size_t step;
@@ -511,6 +532,7 @@ struct RcSlot {
     RcDrifters dr;
     RcInfill inf;
     RcOffshore off;
+    RcOutlines ol;
     RcPhaseCorr pc;
 };
 
@@ -539,6 +561,7 @@ struct rc_ctx {
     int poly_mfma = 0;          // option "poly_mfma": vertical pass of the expansion on the matrix cores (measured 25 % slower)
     int hist_blocks = 0;       // option "hist_blocks": cap on histogram blocks per launch (0 = default)
     int fuse_pyr = 1;         // scale-0 expansion also writes pyramid scales 1 and 2 (exact 2:1 / 4:1 sizes)
+    int outlines_early = 1;   // option "outlines_early": a pointer round of the region outlines returns at once when the round before it changed nothing
     int ablate = 0;
     void* comm = nullptr;      // RcComm (comm_rccl.hip): the histogram all-reduce over RCCL
     int prof_on = 0;
@@ -577,7 +600,8 @@ struct rc_ctx {
 // the flow field and decides from its mean, as the opposing-flow map does, and is booked where that is, under "farneback".  The
 // virtual drifters carry points through the field as the tracer lines do and are booked with them, under "stream".  The offshore
 // frame projects one flow field on the shore normal, pixel for pixel, as the post-ops work on the field, and is booked with
-// them, under "farneback"; its map is made from a mask when the shore has moved and is booked with it.
+// them, under "farneback"; its map is made from a mask when the shore has moved and is booked with it.  The region outlines trace
+// the masks and label planes the regions label and are booked with them, under "threshold".
 #define RC_BUCKET_TABLE(X) \
     X(RC_B_FARNEBACK, "farneback") X(RC_B_POLAR, "polar") X(RC_B_THRESHOLD, "threshold") X(RC_B_OVERLAY, "overlay") \
     X(RC_B_EROSION, "erosion") X(RC_B_CODEC, "codec") X(RC_B_STREAM, "stream")
@@ -625,7 +649,8 @@ struct rc_ctx {
     X(RC_K_FLOWCHECK, "flowcheck", RC_B_FARNEBACK) /* @0 staging, gather, box sums, the tests, every output and cell sums, @1 records and summary */ \
     X(RC_K_DRIFTERS, "drifters", RC_B_STREAM) /* @0 release, gather, fates and the scattered adds, @1 density, pictures, records and summary, @2 the zones helper */ \
     X(RC_K_INFILL, "infill", RC_B_FARNEBACK) /* @0 classes, held state and the pull to level 4, @1 the pull above and the push down to level 5, @2 the push to the pixels, every output and cell sums, @3 records and summary */ \
-    X(RC_K_OFFSHORE, "offshore", RC_B_FARNEBACK) /* @0 the map's column pass, @1 its row pass, every output and sums, @2 its summary, @3 the push: classes, components, every output and the table, @4 records and summary, @5 the band */
+    X(RC_K_OFFSHORE, "offshore", RC_B_FARNEBACK) /* @0 the map's column pass, @1 its row pass, every output and sums, @2 its summary, @3 the push: classes, components, every output and the table, @4 records and summary, @5 the band */ \
+    X(RC_K_OUTLINES, "outlines", RC_B_THRESHOLD) /* @0 sides, block counts and their scan, @1 the cracks in key order, @2 the successor's place, @3 a leader round, @4 the cut before the leader, @5 a rank round, @6 loop partials, their scan, numbers and offsets, @7 the cracks in loop order, @8 turn partials, area and box, @9 the scan of turns, vertex offsets and vertices, @10 records and summary, @11 primitives */
 #define RC_ROW_ID(id, ...) id,
 enum { RC_BUCKET_TABLE(RC_ROW_ID) RC_B_BUCKETS };
 enum { RC_KIND_TABLE(RC_ROW_ID) RC_K_KINDS };
@@ -713,7 +738,7 @@ struct RcProfScope {
     } while (0)
 
 // ---------------------------------------------------------------------------- per-slot products
-// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView, RcWaves, RcPiv, RcTransects, RcKinematics, RcShoreline, RcSurf, RcMeanflow, RcFlowcheck, RcDrifters, RcInfill and RcOffshore share one lifecycle.  A product supplies
+// RcTimex, RcFrameStab, RcRipMap, RcTracers, RcRegions, RcTracks, RcMotion, RcFtle, RcPlanView, RcWaves, RcPiv, RcTransects, RcKinematics, RcShoreline, RcSurf, RcMeanflow, RcFlowcheck, RcDrifters, RcInfill, RcOffshore and RcOutlines share one lifecycle.  A product supplies
 //   void rc_state_free(T&)             frees every buffer and the fence; the state is T() again
 //   int rc_state_zero(RcSlot&, T&)     rc_fence_zero of what open / reset clear, and the counters
 // and open / reset / close are written once, here.
@@ -737,6 +762,7 @@ void rc_state_free(RcFlowcheck& v);
 void rc_state_free(RcDrifters& v);
 void rc_state_free(RcInfill& v);
 void rc_state_free(RcOffshore& v);
+void rc_state_free(RcOutlines& v);
 int rc_state_zero(RcSlot& s, RcTimex& t);
 int rc_state_zero(RcSlot& s, RcFrameStab& f);
 int rc_state_zero(RcSlot& s, RcRipMap& m);
@@ -757,6 +783,7 @@ int rc_state_zero(RcSlot& s, RcFlowcheck& v);
 int rc_state_zero(RcSlot& s, RcDrifters& v);
 int rc_state_zero(RcSlot& s, RcInfill& v);
 int rc_state_zero(RcSlot& s, RcOffshore& v);
+int rc_state_zero(RcSlot& s, RcOutlines& v);
 
 // The tail of every open.  The caller has validated, selected the device and built `fresh` (rc: what its allocations
 // returned).  The state that is open is touched only once nothing can be refused any more: a refused open leaves it as it

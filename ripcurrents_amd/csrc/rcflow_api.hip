@@ -272,6 +272,7 @@ static void slot_free(RcSlot& s) {
     rc_state_free(s.dr);
     rc_state_free(s.inf);
     rc_state_free(s.off);
+    rc_state_free(s.ol);
     rc_buf_free(s.pc.tab); rc_buf_free(s.pc.scratch);
     rc_graph_drop(s.loop_graph);
     for (auto& e : s.fev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
@@ -539,6 +540,8 @@ extern "C" int rcflow_set_option(rc_ctx* ctx, const char* name, int value) {
         ctx->poly_tile_h = value;
     } else if (!strcmp(name, "fuse_pyr")) {
         ctx->fuse_pyr = value != 0;
+    } else if (!strcmp(name, "outlines_early")) {
+        ctx->outlines_early = value ? 1 : 0;
     } else if (!strcmp(name, "ablate")) {
         ctx->ablate = value;
     } else {
